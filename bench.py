@@ -11,10 +11,14 @@ HBM.  ``value`` = damped-operator calls per second summed over ranks; with N>1
 every rank holds its own 32-sample shard (weak scaling) and each matvec ends in
 one all-reduce of the 44.7 MB partial product.
 
-Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
-``roofline`` (dominant hand-written kernel: K2 update_xr, HIP-event timed inside
-the timed region) and ``cpu_baseline`` (the oracle -- the reference's algorithm
-restated on torch-CPU -- timed on a bounded sample on this box's host cores).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times ``--steps``
+steps, writes ``--dump-outputs`` if asked and prints the contract's keys with the
+run's configuration.  ``--full`` adds everything else: the float64 check of the
+operator before it is timed, ``roofline`` (dominant hand-written kernel: K2
+update_xr, HIP-event timed inside the timed region), the Martens / default-damping
+solves, ``step_ms``, ``train_bn`` and ``cpu_baseline`` (the oracle -- the
+reference's algorithm restated on torch-CPU -- timed on a bounded sample on the
+host cores).
 """
 
 import argparse
@@ -44,6 +48,14 @@ def parse():
     ap.add_argument("--damping", type=float, default=1e-3,
                     help="Tikhonov damping; 1e-3 keeps all 250 iterations numerically alive "
                          "(with 1.0 this random-init problem converges to fp32 round-off in ~15)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the float64 check of the operator before it is timed (NHWC "
+                         "falls back to NCHW on failure), HIP-event kernel timing inside the timed region (`roofline`), "
+                         "the Martens / default-damping solves, the 256 MiB roofline leg, complete steps (`step_ms`), "
+                         "the train-mode BatchNorm child run and the CPU baseline (each --no-* switch skips its leg)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed solve returned (see dump_outputs) to "
+                         "DIR/<name>.npy, float32, under 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--rung-timeout", default="480,360,300,300",
                     help="multi-rank runs: wall-clock bound in seconds of each rung of the data-parallel fallback ladder "
@@ -505,7 +517,7 @@ def train_bn_leg(args):
     import subprocess
 
     cmd = [sys.executable, os.path.abspath(__file__), "--bn", "train", "--steps", "4", "--warmup", "2",
-           "--iters", str(args.iters), "--batch", str(args.batch), "--no-cpu-baseline", "--no-beyond-l3",
+           "--iters", str(args.iters), "--batch", str(args.batch), "--full", "--no-cpu-baseline", "--no-beyond-l3",
            "--no-train-bn"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     try:
@@ -525,8 +537,38 @@ def train_bn_leg(args):
         return {"error": repr(exc)}
 
 
+DUMP_BYTES = 60_000_000  # --dump-outputs: the payload of all files together (64 MB with room for the .npy headers)
+
+
+def dump_outputs(out_dir, xs, ms):
+    """``--dump-outputs``: what the last timed ``cg()`` call returned to its caller, as float32 -- every iterate it
+    handed back (``x_iter<k>.npy``, k = PCG iteration) and, for a Martens-terminated solve, the quadratic's values
+    (``m_iters.npy``).  The budget is split evenly over the files; a longer vector is written as a fixed sample: its
+    entries at the first K indices of ``torch.randperm(N, generator=torch.Generator().manual_seed(0))`` in increasing
+    order, the same indices for every vector of length N, so that two builds compare entry for entry."""
+    import numpy as np
+
+    arrays = {f"x_iter{k}": x for k, x in enumerate(xs) if x is not None}
+    if ms is not None:
+        arrays["m_iters"] = torch.stack(ms)
+    keep = DUMP_BYTES // 4 // len(arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    samples = {}
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        n = t.numel()
+        if n > keep:
+            if n not in samples:
+                perm = torch.randperm(n, generator=torch.Generator().manual_seed(0))
+                samples[n] = perm[:keep].sort().values.to(t.device)
+            t = t[samples[n]]
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
 def main():
     args = parse()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"bench: --steps {args.steps} --warmup {args.warmup}: at least one timed step, no negative warmup")
     if args.conv:
         os.environ["HF_CONV"] = args.conv
     if not args.engine:
@@ -799,32 +841,34 @@ def main():
         if args.chunk >= 0 and not (child and int(os.environ.get("HF_BENCH_RUNG", "0")) > 0):
             os.environ["HF_CHUNKED_ALLREDUCE"] = "1" if args.chunk else "0"
     args.overlap = max(args.overlap, 0)  # (the autograd two-graph split: only on request)
-    op, grad, diag, n, err = checked(bool(args.channels_last), overlap=bool(args.overlap))
-    def note_text(err):
-        if check.get("masked"):
-            return ("max-norm error against float64 stock autograd on this operator's own ReLU decisions {:.1e} "
-                    "(on the float64 network's decisions {:.1e}); stock fp32 autograd likewise {:.1e} ({:.1e})"
-                    ).format(err, check["err_plain"], check["stock_err"], check["stock_err_plain"])
-        return "max-norm error against float64 stock autograd {:.1e}, stock fp32 autograd {:.1e}".format(
-            err, check["stock_err_plain"])
+    if not args.full:
+        # the operator HessianFree.step() builds, behind the fused engine's own first-use check against the autograd
+        # product at its default tolerance (--full raises it to 5x what stock fp32 autograd achieves when that is
+        # larger); the comparison with float64 stock autograd and the NHWC -> NCHW fallback it drives are --full's
+        op, grad, diag, n = build_operator(bool(args.channels_last), overlap=bool(args.overlap))
+        layout = ("NHWC" if args.channels_last else "NCHW") + " (not compared with float64 stock autograd: --full)"
+    else:
+        op, grad, diag, n, err = checked(bool(args.channels_last), overlap=bool(args.overlap))
 
-    class _Note:  # (keeps the two call sites below unchanged)
-        @staticmethod
-        def format(err, _unused):
-            return note_text(err)
+        def note_text(err):
+            if check.get("masked"):
+                return ("max-norm error against float64 stock autograd on this operator's own ReLU decisions {:.1e} "
+                        "(on the float64 network's decisions {:.1e}); stock fp32 autograd likewise {:.1e} ({:.1e})"
+                        ).format(err, check["err_plain"], check["stock_err"], check["stock_err_plain"])
+            return "max-norm error against float64 stock autograd {:.1e}, stock fp32 autograd {:.1e}".format(
+                err, check["stock_err_plain"])
 
-    note = _Note
-    layout = ("NHWC" if args.channels_last else "NCHW") + " (" + note.format(err, check["stock_err"]) + ")"
-    if not err < check["tol_eff"] and args.channels_last:
-        print(f"[bench] NHWC product off by {err:.2e} (float64 reference); using NCHW",
-              file=sys.stderr, flush=True)
-        del op
-        args.channels_last = 0
-        op, grad, diag, n, err = checked(False)
-        layout = "NCHW (NHWC failed its check; " + note.format(err, check["stock_err"]) + ")"
-    if not err < check["tol_eff"]:
-        raise SystemExit(f"bench: the curvature product is off by {err:.2e} against float64 stock autograd")
-    del check["want"], check["v"]
+        layout = ("NHWC" if args.channels_last else "NCHW") + " (" + note_text(err) + ")"
+        if not err < check["tol_eff"] and args.channels_last:
+            print(f"[bench] NHWC product off by {err:.2e} (float64 reference); using NCHW",
+                  file=sys.stderr, flush=True)
+            del op
+            args.channels_last = 0
+            op, grad, diag, n, err = checked(False)
+            layout = "NCHW (NHWC failed its check; " + note_text(err) + ")"
+        if not err < check["tol_eff"]:
+            raise SystemExit(f"bench: the curvature product is off by {err:.2e} against float64 stock autograd")
+        del check["want"], check["v"]
 
     if group is not None:
         # one-off timing of THE collective of this path: the operator's own reduction of a product
@@ -874,67 +918,68 @@ def main():
         solve(martens=True)
         per = max(1, op.calls - c0)
         solves_per_step = max(1, -(-args.min_calls // (per * max(1, args.steps))))
-    ws = enable_kernel_timing(device, n, torch.float32, not os.environ.get("HF_BENCH_NO_TIMING"))
+    ws = (enable_kernel_timing(device, n, torch.float32, not os.environ.get("HF_BENCH_NO_TIMING"))
+          if args.full else None)
     calls0 = op.calls
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         for _r in range(solves_per_step):
-            xs, _, reason = solve(martens=timed_martens)
+            xs, ms, reason = solve(martens=timed_martens)
     barrier()
     dt = time.perf_counter() - t0
-    timing = read_kernel_timing(ws)
-    enable_kernel_timing(device, n, torch.float32, False)
+    if ws is not None:
+        timing = read_kernel_timing(ws)
+        enable_kernel_timing(device, n, torch.float32, False)
     matvecs = op.calls - calls0
     iters_done = len(xs) - 1
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, xs, ms)
 
     if group is not None:
         tt = torch.tensor([dt], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tt.item())
 
-    # CG-iters/sec to Martens' criterion (second half of BASELINE.json's metric), twice: at the timed region's damping
-    # (--damping; the reference's fixture `solve_martens` of this problem: 36 iterations at 1e-3) and at the
-    # optimizer's DEFAULT damping 1.0 (the reference's own trace of this problem never reaches Martens'
-    # test there: it ends by tolerance after 12-15 iterations -- cg.py:95-115 evaluates Martens' test first, then the
-    # iteration count, NaN, the tolerances), through exactly the call `HessianFree.step` makes (tol 1e-5, max_iter 250)
-    barrier()
-    t1 = time.perf_counter()
-    xs_m, _, reason_m = solve(martens=True)
-    barrier()
-    dt_m = time.perf_counter() - t1
-    A_default = hf.DampedCurvature(op, 1.0)
-
-    def solve_default():
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            return hf.cg(A_default, b, M=M, max_iter=250, martens_conv_crit=True, store_x_at_iters=None)
-
-    default_leg = None
-    try:  # (the headline must not depend on this leg; under data parallelism every rank takes the same branch: the
-        # solver's kernels and the lockstep rule are deterministic, an exception here is a host-side one on all ranks)
-        solve_default()  # (graph arguments of the new operator object: once, untimed)
+    if args.full:
+        # CG-iters/sec to Martens' criterion (second half of BASELINE.json's metric), twice: at the timed region's
+        # damping (--damping; the reference's fixture `solve_martens` of this problem: 36 iterations at 1e-3) and at the
+        # optimizer's DEFAULT damping 1.0 (the reference's own trace of this problem never reaches
+        # Martens' test there: it ends by tolerance after 12-15 iterations -- cg.py:95-115 evaluates Martens' test first,
+        # then the iteration count, NaN, the tolerances), through exactly the call `HessianFree.step` makes (tol 1e-5,
+        # max_iter 250)
         barrier()
         t1 = time.perf_counter()
-        xs_d, _, reason_d = solve_default()
+        xs_m, _, reason_m = solve(martens=True)
         barrier()
-        dt_d = time.perf_counter() - t1
-        default_leg = {"damping": 1.0, "iters": len(xs_d) - 1, "reason": reason_d, "iters_per_s": (len(xs_d) - 1) / dt_d,
-                       "call": "cg(A, b, max_iter=250, martens_conv_crit=True, store_x_at_iters=None): the call "
-                               "HessianFree.step makes (optimizer.py:265-274), wall time incl. A(x0), the backtracking "
-                               "grid's snapshots and the final sync"}
-    except Exception as exc:  # noqa: BLE001
-        if group is not None:
-            raise
-        default_leg = {"error": repr(exc)}
+        dt_m = time.perf_counter() - t1
+        A_default = hf.DampedCurvature(op, 1.0)
+
+        def solve_default():
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                return hf.cg(A_default, b, M=M, max_iter=250, martens_conv_crit=True, store_x_at_iters=None)
+
+        default_leg = None
+        try:  # (the headline must not depend on this leg; under data parallelism every rank takes the same branch: the
+            # solver's kernels and the lockstep rule are deterministic, an exception here is a host-side one on all ranks)
+            solve_default()  # (graph arguments of the new operator object: once, untimed)
+            barrier()
+            t1 = time.perf_counter()
+            xs_d, _, reason_d = solve_default()
+            barrier()
+            dt_d = time.perf_counter() - t1
+            default_leg = {"damping": 1.0, "iters": len(xs_d) - 1, "reason": reason_d,
+                           "iters_per_s": (len(xs_d) - 1) / dt_d,
+                           "call": "cg(A, b, max_iter=250, martens_conv_crit=True, store_x_at_iters=None): the call "
+                                   "HessianFree.step makes (optimizer.py:265-274), wall time incl. A(x0), the "
+                                   "backtracking grid's snapshots and the final sync"}
+        except Exception as exc:  # noqa: BLE001
+            if group is not None:
+                raise
+            default_leg = {"error": repr(exc)}
 
     if rank == 0:
-        k2_s = timing["k2_ms"] * 1e-3
-        # K2 reads x,r,p,Bp,b(,minv), writes x,r; K1 8N, K3 12N (16N with minv)
-        k2_bytes = (32.0 if M is not None else 28.0) * n
-        it_bytes = (56.0 if M is not None else 48.0) * n
-        achieved = k2_bytes / k2_s / 1e9 if k2_s > 0 else 0.0
-        all3 = (timing["k1_ms"] + timing["k2_ms"] + timing["k3_ms"]) * 1e-3
         fused = bool(getattr(op, "_iteration_graphs", None))
         line = {
             "metric": "GGN-matvecs/sec (damped operator calls inside the PCG loop)",
@@ -957,8 +1002,8 @@ def main():
                             + f", max_iter {args.iters}), "
                             f"damping {args.damping}"
                             + (" (SURVEY.md 8(d) states 1.0: with 1.0 this random-init problem is at fp32 round-off "
-                               "after ~15 iterations and 250 iterations cannot be sustained; `cg_to_martens` is the "
-                               "Martens-terminated solve at THIS damping, `cg_default_damping` the solve at the "
+                               "after ~15 iterations and 250 iterations cannot be sustained; with --full, `cg_to_martens` "
+                               "is the Martens-terminated solve at THIS damping, `cg_default_damping` the solve at the "
                                "optimizer's default 1.0 -- which ends by tolerance, as the reference's --, and `step_ms` "
                                "runs complete default steps, damping 1.0 + LM)"
                                if args.damping != 1.0 and not hessian else "")
@@ -979,8 +1024,8 @@ def main():
                           + ("; eval-BN fused (hf_chan_affine)" if args.fuse_bn else "")
                           + ("; conv tangent fused" if args.fuse_conv else "")
                           + "; convolutions: " + (os.environ.get("HF_CONV") or "auto") + "; " + layout
-                          + ("; deterministic (two products bitwise equal)" if check.get("deterministic")
-                             else "; NOT bitwise repeatable (library kernels with atomics)")
+                          + (("; deterministic (two products bitwise equal)" if check.get("deterministic")
+                              else "; NOT bitwise repeatable (library kernels with atomics)") if args.full else "")
                           + ("; HessianFree.path_report(): "
                              + json.dumps({k: (v and {"path": v["path"], "declined": v["declined"]})
                                            for k, v in state["opt"].path_report().items()})
@@ -1023,69 +1068,78 @@ def main():
                                             1: "forced two-phase"}.get(args.chunk)},
             },
             "cg_iters_per_s": world * args.steps * solves_per_step * iters_done / dt,
-            "cg_to_martens": {"damping": args.damping, "iters": len(xs_m) - 1, "reason": reason_m,
-                              "iters_per_s": (len(xs_m) - 1) / dt_m,
-                              "call": "cg(A, b, max_iter=--iters, tol=0, martens_conv_crit=True, store_x_at_iters=[0])"},
-            "cg_default_damping": default_leg,
-            "roofline": {
-                "bound": "hbm",
-                "kernel": "k_update_xr (K2)",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": None,
-                "traffic_source": None,
-                "alg_bytes_per_launch": k2_bytes,
-                "avg_launch_ms": timing["k2_ms"],
-                "launches_timed": timing["n"],
-                "timing": "HIP events on the launch stream around K1/K2/K3"
-                          + (f" (event-record nodes of every {_TIMING_SAMPLE}th iteration's graph)" if fused else
-                             " of every iteration"),
-                "all_pcg_kernels": {
-                    "k1_ms": timing["k1_ms"], "k2_ms": timing["k2_ms"], "k3_ms": timing["k3_ms"],
-                    "alg_bytes_per_iter": it_bytes,
-                    "achieved_GBs": it_bytes / all3 / 1e9 if all3 > 0 else 0.0,
-                },
-            },
         }
-        prof = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(prof):
-            try:
-                key = f"k_update_xr_{n}" + ("_precond" if M is not None else "")
-                val = json.load(open(prof)).get(key)
-                if val is not None:
-                    line["roofline"]["traffic"] = val
-                    line["roofline"]["traffic_source"] = (
-                        "static: profiles/traffic.json (round 6 binary, scripts/collect_r06_profiles.sh) -- rocprofv3 "
-                        "--pmc FETCH_SIZE / WRITE_SIZE passes taken on scripts/pcg_kernel_bench.py (the same kernel at "
-                        "the same N; --pmc aborts this full command on this stack), not re-measured in this run")
-            except Exception:
-                pass
-        if world == 1 and not dist_on and not args.no_beyond_l3:
-            try:
-                bc = beyond_cache_roofline(device)
-                line["roofline"]["frac_beyond_l3"] = bc["k2_frac"]
-                line["roofline"]["beyond_l3"] = bc
-                line["roofline"]["note"] = (
-                    f"frac: K2 at this workload's N = {n} (six {4 * n / 1e6:.1f} MB vectors = "
-                    f"{6 * 4 * n / 2**20:.0f} MiB, at the edge of the 256 MiB Infinity Cache: partly served on-die); "
-                    "frac_beyond_l3: the same kernel on 256 MiB vectors, measured in this run -- the plain HBM figure")
-            except Exception as exc:  # noqa: BLE001
-                line["roofline"]["beyond_l3"] = {"error": repr(exc)}
-        if world == 1 and not dist_on and not args.no_step_timing:
-            try:
-                line["step_ms"] = full_step_timing(args, device)
-            except Exception as exc:  # noqa: BLE001  (the headline number must not depend on this leg)
-                line["step_ms"] = {"error": repr(exc)}
-        if (world == 1 and not dist_on and not args.no_train_bn and args.bn == "eval" and args.workload == "resnet18"
-                and args.curvature == "ggn" and not args.acc):
-            line["train_bn"] = train_bn_leg(args)
-        if world == 1 and not args.no_cpu_baseline:
-            try:
-                line["cpu_baseline"] = cpu_baseline(args)
-            except Exception as exc:  # noqa: BLE001  (the headline must not depend on this leg)
-                line["cpu_baseline"] = {"error": repr(exc)}
+        if args.full:
+            k2_s = timing["k2_ms"] * 1e-3
+            # K2 reads x,r,p,Bp,b(,minv), writes x,r; K1 8N, K3 12N (16N with minv)
+            k2_bytes = (32.0 if M is not None else 28.0) * n
+            it_bytes = (56.0 if M is not None else 48.0) * n
+            achieved = k2_bytes / k2_s / 1e9 if k2_s > 0 else 0.0
+            all3 = (timing["k1_ms"] + timing["k2_ms"] + timing["k3_ms"]) * 1e-3
+            line.update({
+                "cg_to_martens": {"damping": args.damping, "iters": len(xs_m) - 1, "reason": reason_m,
+                                  "iters_per_s": (len(xs_m) - 1) / dt_m,
+                                  "call": "cg(A, b, max_iter=--iters, tol=0, martens_conv_crit=True, store_x_at_iters=[0])"},
+                "cg_default_damping": default_leg,
+                "roofline": {
+                    "bound": "hbm",
+                    "kernel": "k_update_xr (K2)",
+                    "achieved": achieved,
+                    "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": None,
+                    "traffic_source": None,
+                    "alg_bytes_per_launch": k2_bytes,
+                    "avg_launch_ms": timing["k2_ms"],
+                    "launches_timed": timing["n"],
+                    "timing": "HIP events on the launch stream around K1/K2/K3"
+                              + (f" (event-record nodes of every {_TIMING_SAMPLE}th iteration's graph)" if fused else
+                                 " of every iteration"),
+                    "all_pcg_kernels": {
+                        "k1_ms": timing["k1_ms"], "k2_ms": timing["k2_ms"], "k3_ms": timing["k3_ms"],
+                        "alg_bytes_per_iter": it_bytes,
+                        "achieved_GBs": it_bytes / all3 / 1e9 if all3 > 0 else 0.0,
+                    },
+                },
+            })
+            prof = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(prof):
+                try:
+                    key = f"k_update_xr_{n}" + ("_precond" if M is not None else "")
+                    val = json.load(open(prof)).get(key)
+                    if val is not None:
+                        line["roofline"]["traffic"] = val
+                        line["roofline"]["traffic_source"] = (
+                            "static: profiles/traffic.json (round 6 binary, scripts/collect_r06_profiles.sh) -- rocprofv3 "
+                            "--pmc FETCH_SIZE / WRITE_SIZE passes taken on scripts/pcg_kernel_bench.py (the same kernel at "
+                            "the same N; --pmc aborts this full command on this stack), not re-measured in this run")
+                except Exception:
+                    pass
+            if world == 1 and not dist_on and not args.no_beyond_l3:
+                try:
+                    bc = beyond_cache_roofline(device)
+                    line["roofline"]["frac_beyond_l3"] = bc["k2_frac"]
+                    line["roofline"]["beyond_l3"] = bc
+                    line["roofline"]["note"] = (
+                        f"frac: K2 at this workload's N = {n} (six {4 * n / 1e6:.1f} MB vectors = "
+                        f"{6 * 4 * n / 2**20:.0f} MiB, at the edge of the 256 MiB Infinity Cache: partly served on-die); "
+                        "frac_beyond_l3: the same kernel on 256 MiB vectors, measured in this run -- the plain HBM figure")
+                except Exception as exc:  # noqa: BLE001
+                    line["roofline"]["beyond_l3"] = {"error": repr(exc)}
+            if world == 1 and not dist_on and not args.no_step_timing:
+                try:
+                    line["step_ms"] = full_step_timing(args, device)
+                except Exception as exc:  # noqa: BLE001  (the headline number must not depend on this leg)
+                    line["step_ms"] = {"error": repr(exc)}
+            if (world == 1 and not dist_on and not args.no_train_bn and args.bn == "eval" and args.workload == "resnet18"
+                    and args.curvature == "ggn" and not args.acc):
+                line["train_bn"] = train_bn_leg(args)
+            if world == 1 and not args.no_cpu_baseline:
+                try:
+                    line["cpu_baseline"] = cpu_baseline(args)
+                except Exception as exc:  # noqa: BLE001  (the headline must not depend on this leg)
+                    line["cpu_baseline"] = {"error": repr(exc)}
         print(json.dumps(line), flush=True)
     if group is not None:
         torch.distributed.barrier()

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 # the whole GPU suite with its tolerance log and durations
 ( time HF_TOL_LOG="$OUT/r05_tolerance_sites.jsonl" python -m pytest tests -q -m gpu --durations=15 ) > "$OUT/full_suite.log" 2>&1; echo "full_suite rc=$?" >> "$OUT/rc.log"
 # headline, as the driver runs it
-python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/r05_bench_n1.json" 2> "$OUT/r05_bench_n1.err"; echo "bench_n1 rc=$?" >> "$OUT/rc.log"
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/r05_bench_n1.json" 2> "$OUT/r05_bench_n1.err"; echo "bench_n1 rc=$?" >> "$OUT/rc.log"
 # rocprofv3 summary of the same command (no CPU leg, no step / train-mode legs: kernels of the timed loop)
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -- python3 bench.py --no-cpu-baseline --no-step-timing --no-beyond-l3 --no-train-bn > "$OUT/r05_bench_n1_under_rocprof.json" 2> "$OUT/prof_bench.log"
 find /tmp/prof_bench -name "*kernel_stats.csv" -exec cp {} "$OUT/r05_bench_n1_kernel_stats.csv" \;
@@ -22,7 +22,7 @@ rm -rf /tmp/pmck_FETCH_SIZE /tmp/pmck_WRITE_SIZE
 # other workloads
 : > "$OUT/r05_other_workloads.jsonl"
 for args in "--workload allcnnc" "--workload allcnnc --curvature hessian --precond 1 --damping 1.0" "--workload resnet50" "--workload resnet18 --bn train" "--workload resnet18 --curvature hessian" "--workload resnet18 --bn train --curvature hessian" "--workload resnet18 --acc 16,16"; do
-  python bench.py $args --steps 3 --warmup 1 >> "$OUT/r05_other_workloads.jsonl" 2>> "$OUT/other.err"
+  python bench.py $args --steps 3 --warmup 1 --full >> "$OUT/r05_other_workloads.jsonl" 2>> "$OUT/other.err"
 done
 # data-parallel paths that one GPU can exercise
 python bench.py --force-dist 1 --chunk 0 --no-cpu-baseline --no-step-timing > "$OUT/r05_bench_1rank_rccl.json" 2>> "$OUT/dp.err"

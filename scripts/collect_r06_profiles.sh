@@ -7,7 +7,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 # headline, as the driver runs it
-python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/r06_bench_n1.json" 2> "$OUT/r06_bench_n1.err"; echo "bench_n1 rc=$?" >> "$OUT/rc.log"
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/r06_bench_n1.json" 2> "$OUT/r06_bench_n1.err"; echo "bench_n1 rc=$?" >> "$OUT/rc.log"
 # rocprofv3 summary of the same command (no CPU leg, no step / train-mode legs: kernels of the timed loop)
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -- python3 bench.py --no-cpu-baseline --no-step-timing --no-beyond-l3 --no-train-bn > "$OUT/r06_bench_n1_under_rocprof.json" 2> "$OUT/prof_bench.log"
 find /tmp/prof_bench -name "*kernel_stats.csv" -exec cp {} "$OUT/r06_bench_n1_kernel_stats.csv" \;
@@ -40,7 +40,7 @@ PY
 # other workloads (each with step_ms)
 : > "$OUT/r06_other_workloads.jsonl"
 for args in "--workload allcnnc" "--workload allcnnc --curvature hessian --precond 1 --damping 1.0" "--workload resnet50" "--workload resnet18 --bn train" "--workload resnet18 --curvature hessian" "--workload resnet18 --bn train --curvature hessian" "--workload resnet18 --acc 16,16" "--workload resnet18 --freeze stem+layer1"; do
-  python bench.py $args --steps 3 --warmup 1 --no-train-bn >> "$OUT/r06_other_workloads.jsonl" 2>> "$OUT/other.err"
+  python bench.py $args --steps 3 --warmup 1 --full --no-train-bn >> "$OUT/r06_other_workloads.jsonl" 2>> "$OUT/other.err"
 done
 # data-parallel paths that one GPU can exercise: 1-rank RCCL group (both forms), 2 and 8 rank processes over gloo through
 # the fallback ladder (own launcher and under torch.distributed.run, as the driver starts it), fault injection

@@ -11,7 +11,7 @@ for rep in 1 2; do
   done
 done
 python scripts/pcg_kernel_bench.py --sizes 1387108,11175370,25557032 --precond 1 > $OUT/pcg_kernel_bench_precond.jsonl 2>> $OUT/err.log
-python bench.py --acc 16,16 --steps 5 --warmup 2 --no-cpu-baseline --no-beyond-l3 --no-train-bn > $OUT/bench_acc_16_16.json 2>> $OUT/err.log
-python bench.py --freeze stem+layer1 --steps 5 --warmup 2 --no-cpu-baseline --no-beyond-l3 --no-train-bn > $OUT/bench_frozen.json 2>> $OUT/err.log
-python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-beyond-l3 --no-train-bn > $OUT/bench_plain.json 2>> $OUT/err.log
+python bench.py --acc 16,16 --steps 5 --warmup 2 --full --no-cpu-baseline --no-beyond-l3 --no-train-bn > $OUT/bench_acc_16_16.json 2>> $OUT/err.log
+python bench.py --freeze stem+layer1 --steps 5 --warmup 2 --full --no-cpu-baseline --no-beyond-l3 --no-train-bn > $OUT/bench_frozen.json 2>> $OUT/err.log
+python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-beyond-l3 --no-train-bn > $OUT/bench_plain.json 2>> $OUT/err.log
 tail -c 600 $OUT/err.log

@@ -579,3 +579,35 @@ def test_randomised_configurations_match_kernel_arithmetic_oracle():
         if martens:
             np.testing.assert_allclose(np.array([float(m) for m in gm]), np.array([float(m) for m in om]),
                                        rtol=1e-4, atol=1e-6, equal_nan=True, err_msg=str(tag))
+
+
+def test_bench_plain_run_dumps_what_the_last_timed_solve_returned(tmp_path):
+    """``bench.py`` without ``--full``: the timed steps and one line with the contract's keys, none of the ``--full``
+    legs; ``--dump-outputs``: the last timed solve's iterates (x0 and the final one), float32, within 64 MB."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run(
+        [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--iters", "20",
+         "--dump-outputs", str(out)],
+        env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["value"] > 0
+    assert rec["unit"] == "matvecs/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+    assert "20 PCG iterations in the last step (42 operator calls in 2 steps" in rec["config"]["workload"]
+    assert not {"roofline", "cg_to_martens", "cg_default_damping", "step_ms", "train_bn", "cpu_baseline"} & set(rec)
+    files = sorted(os.listdir(out))
+    assert files == ["x_iter0.npy", "x_iter20.npy"]
+    assert sum(os.path.getsize(out / f) for f in files) <= 64_000_000
+    x0, x = np.load(out / "x_iter0.npy"), np.load(out / "x_iter20.npy")
+    assert x0.dtype == x.dtype == np.float32 and x0.shape == x.shape == (7_500_000,)
+    assert not x0.any() and np.isfinite(x).all() and np.abs(x).max() > 0

@@ -176,3 +176,32 @@ def test_bench_ladder_control_flow_with_stand_in_ranks(launcher):
     # every rung fails: non-zero, no line
     p, lines = _ladder({"STUB_FAIL_RUNGS": "0,1,2,3"}, launcher)
     assert p.returncode != 0 and not lines
+
+
+# ---------------------------------------------------------------------------------------------------------
+# ``bench.py --dump-outputs``: what the last timed solve returned, float32, whole or as a fixed seeded sample
+# ---------------------------------------------------------------------------------------------------------
+def test_bench_dump_outputs_writes_a_fixed_sample_within_the_budget(tmp_path, monkeypatch):
+    import bench
+
+    assert bench.DUMP_BYTES + 4 * 256 <= 64_000_000  # (three .npy headers of at most 256 bytes each)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8000)  # 2000 float32 entries in all
+    g = torch.Generator().manual_seed(3)
+    n = 5000
+    xs = [torch.zeros(n), None, None, torch.randn(n, generator=g, dtype=torch.float64)]
+    ms = [torch.tensor(v) for v in (0.0, -1.5, -2.25, -2.5)]
+    for out in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(out), xs, ms)
+    assert sorted(os.listdir(tmp_path / "a")) == ["m_iters.npy", "x_iter0.npy", "x_iter3.npy"]
+    keep = 8000 // 4 // 3
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values.numpy()
+    for name in ("m_iters", "x_iter0", "x_iter3"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "x_iter3.npy"), xs[3].numpy()[idx].astype(np.float32))
+    assert not np.load(tmp_path / "a" / "x_iter0.npy").any()
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "m_iters.npy"), [0.0, -1.5, -2.25, -2.5])
+    # a solve without Martens' criterion returns no m values; short vectors are written whole
+    bench.dump_outputs(str(tmp_path / "c"), [torch.ones(7), torch.arange(7.0)], None)
+    assert sorted(os.listdir(tmp_path / "c")) == ["x_iter0.npy", "x_iter1.npy"]
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "x_iter1.npy"), np.arange(7.0, dtype=np.float32))
