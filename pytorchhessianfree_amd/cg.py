@@ -132,18 +132,22 @@ _TIMING_SAMPLE = 16  # with kernel timing on, every 16th fused iteration runs th
 
 def _iteration_graph(matvec, ws, Bp, damping, mode, with_product):
     """The operator's cached :class:`_IterationGraph` for this workspace, or ``None``
-    when the operator is not a captured graph / fusion is switched off
-    (``HF_FUSE_ITERATION=0``)."""
+    when the operator is not a captured graph, ``with_product`` is asked of an operator
+    without a single product graph (``raw_graph()`` returns ``None``: see
+    ``curvature.CapturedOperator``), or fusion is switched off (``HF_FUSE_ITERATION=0``)."""
     if os.environ.get("HF_FUSE_ITERATION", "1") == "0":
         return None
     raw = getattr(matvec, "raw_graph", None)
     if raw is None:
         return None
+    product = raw() if with_product else None
+    if with_product and product is None:
+        return None
     cache = matvec.__dict__.setdefault("_iteration_graphs", {})
     key = (id(ws), mode, bool(with_product), bool(ws.timing))
     g = cache.get(key)
     if g is None:
-        g = cache[key] = _IterationGraph(ws, raw() if with_product else None, Bp, damping, mode, ws.timing)
+        g = cache[key] = _IterationGraph(ws, product, Bp, damping, mode, ws.timing)
     g.refresh(Bp, damping)
     return g
 
@@ -355,7 +359,7 @@ def cg(
 
     # A hipGraph-captured operator whose buffers the solver adopted runs the whole
     # iteration -- product, K1, K2, K3 -- as ONE graph launch; with a process group the
-    # all-reduce separates the product graph from a K1-K3 graph.
+    # all-reduce separates the product from a K1-K3 graph (curvature.CapturedOperator).
     fused = None
     if mode != _lib.HF_M_EXTERNAL and p_vec is ib and hasattr(matvec, "replay_local"):
         fused = _iteration_graph(matvec, ws, matvec.output_buffer, damping, mode,
@@ -373,16 +377,9 @@ def cg(
             timed = fused.timing and (it % _TIMING_SAMPLE == 0 or it == 3)
             if timed and timed_pending:
                 fused.collect()  # iteration it-16: long finished, does not stall the pipeline
-            if group is None:
-                matvec.calls += 1
-            else:
-                fused_reduce = getattr(matvec, "replay_and_reduce", None)
-                if fused_reduce is not None:  # (the operator overlaps its collective with its own sweep)
-                    fused_reduce()
-                else:
-                    matvec.replay_local()
-                    matvec.reduce(matvec.output_buffer)
-                matvec.calls += 1
+            if group is not None:
+                matvec.replay_and_reduce()
+            matvec.calls += 1
             fused.launch(stream, timed)
             timed_pending = timed_pending or timed
         else:

@@ -258,18 +258,118 @@ class HessianOperator(_Operator):
         return self._finish(Hv, out)
 
 
-class GraphedOperator:
+_capture_streams = {}  # one capture stream per device, shared by every captured operator
+
+
+class CapturedOperator:
+    """A curvature operator whose local product is captured once as hipGraph(s) and replayed per matvec.  The
+    contract :func:`~pytorchhessianfree_amd.cg.cg` relies on, for every subclass:
+
+    * ``input_buffer`` / ``output_buffer``: the captured product reads the one and writes the other.  ``cg()``
+      adopts ``input_buffer`` as its search direction ``p`` (its update kernel writes the next direction straight
+      into the graph's input: no copy); ``local`` / ``__call__`` copy any other input vector in first.  A returned
+      ``output_buffer`` is overwritten by the next product.
+    * ``replay_local()``: this rank's product, ``input_buffer -> output_buffer``.  ``reduce(t)``: the in-place sum
+      of a local product over ``group`` (the wrapped engine's compact all-reduce when it has one).
+      ``replay_and_reduce()``: one product summed over the ranks -- ``replay_local()`` then
+      ``reduce(output_buffer)`` unless a subclass overlaps the two.
+    * ``raw_graph``: ``None`` as a class attribute means ``cg()`` calls the operator in every iteration.  As a
+      method it lets ``cg()`` fuse K1-K3 into one graph launch per iteration; the product joins that graph only
+      when ``raw_graph()`` returns a handle (the single product graph, owned by the operator) and there is no
+      group.  ``raw_graph()`` returning ``None`` means the product has no single graph: without a group ``cg()``
+      then takes its unfused loop.  Under a group ``cg()`` calls ``replay_and_reduce()`` before every K1-K3 launch.
+    * ``calls``: products taken, counted by ``cg()`` also for those it replays itself.  ``group``: the process
+      group, ``None`` for a single process.  ``op``: the captured eager operator or engine.
+
+    The data-parallel all-reduce stays outside the graphs.  Subclasses build on the device's capture stream
+    (``_enter_capture``), allocate the two buffers with ``_allocate`` and capture with ``_capture``."""
+
+    calls = 0
+    group = None
+    _side = None            # (two-phase products: the probed side stream of distributed.two_phase_all_reduce ...)
+    side_runs_beside = None  # (... and the probe's verdict)
+
+    def _enter_capture(self):
+        """Point ``self.stream`` at the device's capture stream, ordered after the current stream; returns the
+        current stream (the caller makes it wait for the capture stream when done)."""
+        cur = torch.cuda.current_stream()
+        dev = torch.cuda.current_device()
+        stream = _capture_streams.get(dev)
+        if stream is None:
+            stream = _capture_streams[dev] = torch.cuda.Stream()
+        self.stream = stream
+        stream.wait_stream(cur)
+        return cur
+
+    def _allocate(self, n, dtype, device):
+        self.n = n
+        self.input_buffer = torch.zeros(n, dtype=dtype, device=device)
+        self.output_buffer = torch.zeros(n, dtype=dtype, device=device)
+
+    def _capture(self, fn, keep=False, pool=None):
+        """``fn`` captured on ``self.stream``.  ``keep``: the raw ``hipGraph_t`` stays available (``cg()`` clones
+        it into its one-launch-per-iteration graph, product -> K1 -> K2 -> K3, hf_pcg_graph_*)."""
+        g = torch.cuda.CUDAGraph(keep_graph=True) if keep else torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=self.stream, pool=pool):
+            fn()
+        if keep:
+            g.instantiate()
+        return g
+
+    def raw_graph(self):
+        """The captured product as a raw ``hipGraph_t`` (an int), owned by ``self.graph``."""
+        return self.graph.raw_cuda_graph()
+
+    def replay_local(self):
+        self.graph.replay()
+
+    def reduce(self, t):
+        inner = getattr(self.op, "reduce", None)  # (the captured operator's own rule, if it has one)
+        if inner is not None:
+            return inner(t, self.group)
+        return _all_reduce_sum(t, self.group)
+
+    @property
+    def reduce_bytes(self):
+        return getattr(self.op, "reduce_bytes", self.output_buffer.nbytes)
+
+    def replay_and_reduce(self):
+        self.replay_local()
+        self.reduce(self.output_buffer)
+
+    def _load(self, v):
+        if v.data_ptr() != self.input_buffer.data_ptr():
+            self.input_buffer.copy_(v)
+
+    def _result(self, out):
+        if out is not None:
+            out.copy_(self.output_buffer)
+            return out
+        return self.output_buffer
+
+    def local(self, v, out=None):
+        """This rank's product of ``v`` (no communication)."""
+        self._load(v)
+        self.replay_local()
+        return self._result(out)
+
+    def __call__(self, v, out=None):
+        self.calls += 1
+        self._load(v)
+        if self.group is None:
+            self.replay_local()
+        else:
+            self.replay_and_reduce()
+        return self._result(out)
+
+
+class GraphedOperator(CapturedOperator):
     """The local part of a curvature operator (autograd sweeps + ``hf_pack``)
     captured ONCE into a hipGraph and replayed per matvec.
 
     On a ResNet-18 one GGN matvec is ~700 small kernels; issued eagerly the host
     needs longer to launch them than the MI355X needs to run them.  A graph
-    replay costs one launch.  The graph reads its input from ``input_buffer`` and
-    writes ``output_buffer``; :func:`~pytorchhessianfree_amd.cg.cg` adopts
-    ``input_buffer`` as its search-direction vector ``p`` (the update kernel writes
-    the next direction straight into the graph's input: no copy), any other input
-    vector is copied in first.  The result tensor is overwritten by the next call.
-    The data-parallel all-reduce stays outside the graph.
+    replay costs one launch.
 
     ``builder()`` must run the forward pass and return the eager operator; it is
     executed on the capture stream because autograd issues backward kernels on
@@ -291,7 +391,6 @@ class GraphedOperator:
         return "hipGraph replay of autograd sweeps + hf_pack"
 
     _captured_before = False  # later captures in a process need a single warm-up run
-    _streams = {}             # one capture stream per device, shared by all instances
 
     def __init__(self, builder, warmup=None, params=None):
         if warmup is None:
@@ -311,52 +410,34 @@ class GraphedOperator:
             # a lingering earlier graph of ours ties the parameters to that stream only
             gc.collect()
         try:
-            self._capture(builder, warmup)
+            self._build(builder, warmup)
         finally:
             for p, g in stash:
                 p.grad = g
 
-    def _capture(self, builder, warmup):
-        cur = torch.cuda.current_stream()
-        dev = torch.cuda.current_device()
-        if dev not in GraphedOperator._streams:
-            GraphedOperator._streams[dev] = torch.cuda.Stream()
-        self.stream = GraphedOperator._streams[dev]
-        self.stream.wait_stream(cur)
+    def _build(self, builder, warmup):
+        cur = self._enter_capture()
         with torch.cuda.stream(self.stream):
             self.op = builder()
-            ref = self.op.params[0]
-            self.n, self.group = self.op.n, self.op.group
-            self.params = self.op.params
-            self.input_buffer = torch.zeros(self.n, dtype=ref.dtype, device=ref.device)
-            self.output_buffer = torch.empty(self.n, dtype=ref.dtype, device=ref.device)
+            self.group, self.params = self.op.group, self.op.params
+            self._allocate(self.op.n, self.params[0].dtype, self.params[0].device)
+            self._plan()
             for _ in range(warmup):
-                self.op.local(self.input_buffer, out=self.output_buffer)
+                self._product()
         self.stream.synchronize()
-        # keep_graph: the raw hipGraph_t stays available, so that cg() can clone it into
-        # its one-launch-per-iteration graph (product -> K1 -> K2 -> K3, hf_pcg_graph_*)
-        self.graph = torch.cuda.CUDAGraph(keep_graph=True)
-        with torch.cuda.graph(self.graph, stream=self.stream):
-            self.op.local(self.input_buffer, out=self.output_buffer)
-        self.graph.instantiate()
+        self._capture_product()
         cur.wait_stream(self.stream)
         torch.cuda.synchronize()
-        self.calls = 0
         self._verify_replay()
 
-    def raw_graph(self):
-        """The captured product as a raw ``hipGraph_t`` (an int), owned by ``self.graph``."""
-        return self.graph.raw_cuda_graph()
+    def _plan(self):
+        pass
 
-    def replay_local(self):
-        """Replay the captured local product: reads ``input_buffer``, writes ``output_buffer``."""
-        self.graph.replay()
+    def _product(self):
+        self.op.local(self.input_buffer, out=self.output_buffer)
 
-    def reduce(self, t):
-        inner = getattr(self.op, "reduce", None)  # (the captured operator's own rule, if it has one)
-        if inner is not None:
-            return inner(t, self.group)
-        return _all_reduce_sum(t, self.group)
+    def _capture_product(self):
+        self.graph = self._capture(self._product, keep=True)
 
     _verified = set()  # signatures whose first capture in this process was checked
 
@@ -392,7 +473,7 @@ class GraphedOperator:
             self.op.local(self.input_buffer, out=want)
             errs = []
             for _ in range(2):
-                self._replay()
+                self.replay_local()
                 errs.append(float((self.output_buffer - want).abs().max() / want.abs().max().clamp_min(1e-30)))
             self.input_buffer.zero_()
         self.stream.synchronize()
@@ -405,33 +486,18 @@ class GraphedOperator:
                 "graph_matvec=False (eager) or prepare the model with modelprep.prepare_model.")
         GraphedOperator._verified.add(key)
 
-    def _replay(self):
-        self.graph.replay()
-
-    def local(self, v, out=None):
-        if v.data_ptr() != self.input_buffer.data_ptr():
-            self.input_buffer.copy_(v)
-        self.graph.replay()
-        if out is not None:
-            out.copy_(self.output_buffer)
-            return out
-        return self.output_buffer
-
-    def __call__(self, v, out=None):
-        self.calls += 1
-        return self.reduce(self.local(v, out))
-
 
 class OverlappedGraphedOperator(GraphedOperator):
     """Data-parallel variant: the local product is captured as TWO hipGraphs so that
     the all-reduce of the last layers' part of the vector (the adjoint sweep
     produces it first; on conv nets it is most of the bytes) runs while the rest
-    of the sweep is still computing:
+    of the sweep is still computing -- the schedule of
+    :func:`~pytorchhessianfree_amd.distributed.two_phase_all_reduce`:
 
         replay G1 (tangent sweep, H_L, adjoint of the tail, pack tail)
-        all-reduce(out[offset:])   -- asynchronous, on the collective's stream
+        all-reduce(out[offset:])   -- on a side stream
         replay G2 (adjoint of the head, pack head)          <- overlaps
-        all-reduce(out[:offset])   -- asynchronous
+        all-reduce(out[:offset])
         wait for both
 
     The collectives stay outside the graphs.  Results are those of the unsplit
@@ -451,87 +517,35 @@ class OverlappedGraphedOperator(GraphedOperator):
         self._tail_fraction = tail_fraction
         super().__init__(builder, params=params)
 
-    def _capture(self, builder, warmup):
-        cur = torch.cuda.current_stream()
-        dev = torch.cuda.current_device()
-        if dev not in GraphedOperator._streams:
-            GraphedOperator._streams[dev] = torch.cuda.Stream()
-        self.stream = GraphedOperator._streams[dev]
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            self.op = builder()
-            if not isinstance(self.op, GGNOperator):
-                raise TypeError("OverlappedGraphedOperator needs a GGNOperator")
-            ref = self.op.params[0]
-            self.n, self.group, self.params = self.op.n, self.op.group, self.op.params
-            self.cut, self.offset = self.op.split_point(self._tail_fraction)
-            self.input_buffer = torch.zeros(self.n, dtype=ref.dtype, device=ref.device)
-            self.output_buffer = torch.empty(self.n, dtype=ref.dtype, device=ref.device)
-            for _ in range(warmup):
-                self.op.phase_tail(self.input_buffer, self.output_buffer, self.cut, self.offset)
-                self.op.phase_head(self.output_buffer, self.cut, self.offset)
-        self.stream.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=self.stream):
-            self.op.phase_tail(self.input_buffer, self.output_buffer, self.cut, self.offset)
-        self.graph_head = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph_head, stream=self.stream, pool=self.graph.pool()):
-            self.op.phase_head(self.output_buffer, self.cut, self.offset)
-        cur.wait_stream(self.stream)
-        torch.cuda.synchronize()
-        self.calls = 0
-        self._verify_replay()
+    def _plan(self):
+        if not isinstance(self.op, GGNOperator):
+            raise TypeError("OverlappedGraphedOperator needs a GGNOperator")
+        self.cut, self.offset = self.op.split_point(self._tail_fraction)
 
-    def _replay(self):
+    def _phase_tail(self):
+        self.op.phase_tail(self.input_buffer, self.output_buffer, self.cut, self.offset)
+
+    def _phase_head(self):
+        self.op.phase_head(self.output_buffer, self.cut, self.offset)
+
+    def _product(self):
+        self._phase_tail()
+        self._phase_head()
+
+    def _capture_product(self):
+        self.graph = self._capture(self._phase_tail)
+        self.graph_head = self._capture(self._phase_head, pool=self.graph.pool())
+
+    def replay_local(self):
         self.graph.replay()
         self.graph_head.replay()
 
-    def local(self, v, out=None):
-        if v.data_ptr() != self.input_buffer.data_ptr():
-            self.input_buffer.copy_(v)
-        self.graph.replay()
-        self.graph_head.replay()
-        if out is not None:
-            out.copy_(self.output_buffer)
-            return out
-        return self.output_buffer
+    def replay_and_reduce(self):
+        from .distributed import two_phase_all_reduce
 
-    def __call__(self, v, out=None):
-        self.calls += 1
-        if self.group is None:
-            return self.local(v, out)
-        if v.data_ptr() != self.input_buffer.data_ptr():
-            self.input_buffer.copy_(v)
-        from . import distributed as hfdist
-
-        dist, buf = torch.distributed, self.output_buffer
-        tail, head = buf[self.offset:], buf[: self.offset]
-        side_comm = hfdist.side_comm(tail, self.group)
-        if side_comm is not None:
-            # direct RCCL: the tail's all-reduce runs on a side stream with its own
-            # communicator while the head's adjoint sweep replays; the head's all-reduce
-            # follows on the compute stream -- one event hand-off in, one out
-            cur = torch.cuda.current_stream()
-            if getattr(self, "_side", None) is None:
-                self._side = torch.cuda.Stream()
-            self.graph.replay()
-            self._side.wait_stream(cur)
-            with torch.cuda.stream(self._side):
-                side_comm.all_reduce_sum(tail)
-            self.graph_head.replay()
-            hfdist.all_reduce_sum(head, self.group)
-            cur.wait_stream(self._side)
-        else:
-            self.graph.replay()
-            w_tail = dist.all_reduce(tail, group=self.group, async_op=True)
-            self.graph_head.replay()
-            w_head = dist.all_reduce(head, group=self.group, async_op=True)
-            w_tail.wait()
-            w_head.wait()
-        if out is not None:
-            out.copy_(buf)
-            return out
-        return buf
+        buf = self.output_buffer
+        two_phase_all_reduce(self.graph.replay, self.graph_head.replay, [buf[: self.offset]],
+                             [buf[self.offset:]], self.group, self)
 
 
 def maybe_graphed(builder, enable=True, params=None):

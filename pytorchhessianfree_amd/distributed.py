@@ -185,3 +185,87 @@ def all_reduce_sum(t, group):
             return comm.all_reduce_sum(t)
     torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.SUM, group=group)
     return t
+
+
+def _runs_beside(cand, cur):
+    """Whether work on stream ``cand`` executes while ``cur`` is busy: a few ms of streaming updates on ``cur``, a
+    trivial kernel on ``cand``; concurrent iff the trivial one has finished while the updates have not.  The
+    scratch vector is sized from the free memory (256 MiB at most, ~1/16 of what is free at least 4 MiB; more passes
+    over a smaller vector keep ``cur`` busy for the same few ms) so that a nearly full GPU cannot fail a
+    data-parallel step here; ``None`` if even that cannot be allocated (the caller then takes a plain stream)."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    long_done, short_done = torch.cuda.Event(), torch.cuda.Event()
+    try:
+        free = torch.cuda.mem_get_info(dev)[0]
+        n = max(1 << 20, min(1 << 26, int(free // 64)))  # elements (x 4 bytes)
+        big = torch.zeros(n, device=dev)
+        scratch = torch.zeros(64, device=dev)
+    except RuntimeError:  # (out of memory)
+        return None
+    torch.cuda.synchronize()
+    with torch.cuda.stream(cur):
+        for _ in range(max(24, 24 * (1 << 26) // n)):
+            big.add_(1.0)
+        long_done.record(cur)
+    with torch.cuda.stream(cand):
+        scratch.add_(1.0)
+        short_done.record(cand)
+    short_done.synchronize()
+    beside = not long_done.query()
+    long_done.synchronize()
+    return beside
+
+
+def _concurrent_stream(cur, candidates=8):
+    """A side stream whose work runs BESIDE ``cur``'s.  HIP streams of one priority share four hardware queues; a
+    side stream that lands on the compute stream's queue (one pool stream in four) runs in line with the sweep
+    instead of beside it: its all-reduce hides nothing (stand-in kernels: scripts/experiments/stream_handover.hip,
+    profiles/r05_stream_handover.jsonl; in the session: profiles/r05_two_phase_side_stream.jsonl).  Probed, not
+    assumed: the first of a few pool streams that demonstrably overlaps with ``cur``; the last one tried if none
+    does.  (On a 1-rank group, where the collective is the identity, an in-line side stream is the CHEAPER one --
+    no cross-queue dependency, ~725 instead of ~790 us per iteration; it is not taken for that.)"""
+    cand, beside = None, False
+    for _ in range(candidates):
+        cand = torch.cuda.Stream()
+        beside = _runs_beside(cand, cur)
+        if beside or beside is None:
+            break
+    return cand, bool(beside)
+
+
+def two_phase_all_reduce(replay_a, replay_b, head, tail, group, owner):
+    """One data-parallel product in two phases, the sum of its first-final part hidden behind the rest of the sweep:
+
+        replay_a()                       -> the ``tail`` pieces are final
+        side stream, second communicator:   all-reduce(tail pieces, ONE grouped launch)   <- overlaps replay_b
+        replay_b()                       -> the ``head`` pieces are final
+        compute stream:                     all-reduce(head pieces)
+        join: the compute stream waits for the side stream
+
+    Without a second direct communicator the tail pieces go to ``torch.distributed`` asynchronously and the head
+    synchronously; the sums are the same bits either way.  The side stream is probed once (``_concurrent_stream``)
+    and kept on ``owner`` (``owner._side``), its verdict as ``owner.side_runs_beside`` -- False: no pool stream was
+    seen to overlap with the compute stream, or the probe could not allocate its scratch; the tail's all-reduce then
+    hides less.  Returns after the join."""
+    cur = torch.cuda.current_stream()
+    comm = side_comm(tail[0], group)
+    if comm is not None and owner._side is None:
+        owner._side, owner.side_runs_beside = _concurrent_stream(cur)
+        owner._side_events = torch.cuda.Event(), torch.cuda.Event()
+    works = []
+    replay_a()
+    if comm is not None:
+        ev_a, ev_t = owner._side_events
+        ev_a.record(cur)
+        owner._side.wait_event(ev_a)
+        with torch.cuda.stream(owner._side):
+            comm.all_reduce_sum_multi(tail)
+            ev_t.record(owner._side)
+    else:
+        works = [torch.distributed.all_reduce(piece, group=group, async_op=True) for piece in tail]
+    replay_b()
+    all_reduce_sum_multi(head, group)
+    if comm is not None:
+        cur.wait_event(ev_t)
+    for work in works:
+        work.wait()

@@ -49,7 +49,7 @@ class _HessianExtras:
 
     def _extras_fork(self):
         # (``_extras_allowed = False``: the caller already runs this engine on one of several parallel branches --
-        # session.AccumulatedSession -- and a fork inside a forked capture branch crashes hipStreamEndCapture
+        # acc_session.AccumulatedSession -- and a fork inside a forked capture branch crashes hipStreamEndCapture
         # on this stack: segfault in capture_end, round-4 batch r4f)
         # (measured, profiles/r04_hessian_parallel_branch.jsonl: ResNet-18 form 1 922-930, form 2 947-959 matvecs/s;
         # All-CNN-C form 1 521, form 2 283 -- its 128-wide tile configurations spill a three-problem argument block)

@@ -111,7 +111,7 @@ class HessianFree(_Accumulation, _SessionSteps, torch.optim.Optimizer):
         self._session = None
         self._session_failures = 0
         self._session_off = False
-        # ... and its acc_step counterpart (session.AccumulatedSession: one engine per data chunk)
+        # ... and its acc_step counterpart (acc_session.AccumulatedSession: one engine per data chunk)
         self._acc_session = None
         self._acc_session_failures = 0
         self._acc_session_off = False

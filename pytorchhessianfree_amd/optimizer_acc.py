@@ -1,6 +1,6 @@
 """``acc_step`` of the reference (optimizer.py:519-606) and the accumulation helpers ``_acc*`` (:608-814),
 ``test_reduction`` (:817-926): loss / gradient / curvature products accumulated over lists of mini-batches -- on the
-accumulated engine session where the model family is covered (``session.AccumulatedSession``), else by the generic
+accumulated engine session where the model family is covered (``acc_session.AccumulatedSession``), else by the generic
 accumulation with per-chunk operators cached per step.  Mixin of ``optimizer.HessianFree``."""
 
 from contextlib import nullcontext
@@ -10,6 +10,7 @@ import torch
 
 from . import curvature
 from .cg import cg
+from .optimizer_session import _any_rank_refused, _refusal, _verify_every
 
 
 class _Accumulation:
@@ -80,16 +81,13 @@ class _Accumulation:
             self._note_path("acc_step", "eager", self._acc_decline)
             return None
         sess = self._acc_session_step_local(model, loss_func, lists, reduction, curvature_opt)
-        if self._acc_comm is not None:
-            ok = torch.tensor([1 if sess is not None else 0], dtype=torch.int32, device=self.device)
-            torch.distributed.all_reduce(ok, op=torch.distributed.ReduceOp.MIN, group=self._acc_comm)
-            if int(ok.item()) == 0:
-                if sess is not None:
-                    self._acc_decline = "another rank's accumulated session was refused (the ranks decide together)"
-                self._acc_session, self._acc_session_off = None, True
-                sess = None
-            if sess is not None:  # (the count-weighted loss summed over the ranks)
-                sess.base_loss = sess.reduce_losses(sess.loss_buf.reshape(1)).tolist()[0]
+        if _any_rank_refused(sess is not None, self._acc_comm, self.device):
+            if sess is not None:
+                self._acc_decline = "another rank's accumulated session was refused (the ranks decide together)"
+            self._acc_session, self._acc_session_off = None, True
+            sess = None
+        if sess is not None and self._acc_comm is not None:  # (the count-weighted loss summed over the ranks)
+            sess.base_loss = sess.reduce_losses(sess.loss_buf.reshape(1)).tolist()[0]
         if sess is None:
             self._note_path("acc_step", "eager", self._acc_decline)
         else:
@@ -99,9 +97,8 @@ class _Accumulation:
     _acc_decline = None  # why the accumulated session was not taken (last refusal)
 
     def _acc_session_step_local(self, model, loss_func, lists, reduction, curvature_opt):
-        import os
-
-        from .session import AccumulatedSession, _NoEngine
+        from .acc_session import AccumulatedSession
+        from .session import _NoEngine
 
         self._ensure_arena()
         memo = {}
@@ -129,15 +126,12 @@ class _Accumulation:
                                                  hessian=hessian, group=self._acc_comm, why=why)
             slots = sess.accepts(*args) if sess is not None else None
             if slots is None:
-                self._acc_decline = ("; ".join(dict.fromkeys(why)) if why else
-                                     "a freshly built accumulated session does not accept this call's own data lists")
-                self._acc_session_failures += 1
-                if self._acc_session_failures >= 2:
-                    self._acc_session_off = True
-                    self._acc_decline += " (refused twice: not tried again)"
+                self._acc_session_failures, self._acc_session_off, self._acc_decline = _refusal(
+                    self._acc_session_failures, "; ".join(dict.fromkeys(why)) if why else
+                    "a freshly built accumulated session does not accept this call's own data lists")
                 return None
             self._acc_session = sess
-        every = 1 if os.environ.get("HF_SESSION_VERIFY") == "1" else int(os.environ.get("HF_SESSION_VERIFY_EVERY", "16"))
+        every = _verify_every()
         try:
             sess.begin_step(slots, verify=every > 0 and sess.steps > 0 and sess.steps % every == 0,
                             reduce=self._acc_comm is None)

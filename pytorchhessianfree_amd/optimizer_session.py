@@ -3,11 +3,37 @@ forward / gradient / trial losses as graph replays (reference optimizer.py:216-2
 empirical-Fisher preconditioner from the session's engine (``get_preconditioner``, optimizer.py:928-952 -- which here
 RETURNS it) and the batched trial-loss evaluation ``_SessionTrials``.  Mixin of ``optimizer.HessianFree``."""
 
+import os
 from warnings import warn
 
 import torch
 
 from .preconditioners import diag_EF_preconditioner
+
+
+def _any_rank_refused(have, group, device):
+    """Whether some rank of ``group`` has no session (``have`` is this rank's answer; ONE MIN all-reduce, every rank
+    gets the same verdict).  The session path and the generic path issue different collectives, so a rank whose
+    session was refused takes every rank with it.  ``group=None``: ``False``."""
+    if group is None:
+        return False
+    ok = torch.tensor([1 if have else 0], dtype=torch.int32, device=device)
+    torch.distributed.all_reduce(ok, op=torch.distributed.ReduceOp.MIN, group=group)
+    return int(ok.item()) == 0
+
+
+def _refusal(failures, decline):
+    """``(failures, off, decline)`` after one more refusal of a session: the second in a row switches it off."""
+    failures += 1
+    if failures >= 2:
+        return failures, True, decline + " (refused twice: not tried again)"
+    return failures, False, decline
+
+
+def _verify_every():
+    """Every how many steps a session is re-verified against the model's own forward pass (``HF_SESSION_VERIFY=1``:
+    every step; else ``HF_SESSION_VERIFY_EVERY``, default 16; 0: never)."""
+    return 1 if os.environ.get("HF_SESSION_VERIFY") == "1" else int(os.environ.get("HF_SESSION_VERIFY_EVERY", "16"))
 
 
 class _SessionSteps:
@@ -21,19 +47,14 @@ class _SessionSteps:
         if self._session_off:
             return None, None
         sess, a, b = self._session_step_local(forward)
-        if self.process_group is not None:
-            # one decision for all ranks: the session path and the generic path issue different
-            # collectives, so a rank whose session was refused takes every rank with it
-            ok = torch.tensor([1 if sess is not None else 0], dtype=torch.int32, device=self.device)
-            torch.distributed.all_reduce(ok, op=torch.distributed.ReduceOp.MIN, group=self.process_group)
-            if int(ok.item()) == 0:
-                # EVERY rank switches the session off, whether it had one or not: a rank whose session was
-                # merely refused this once would otherwise issue this all-reduce again on the next step while
-                # its peers go straight to the generic path's gradient all-reduce
-                if sess is not None:
-                    self._session_decline = "another rank's session was refused (the ranks decide together)"
-                self._session, self._session_off = None, True
-                return None, None
+        if _any_rank_refused(sess is not None, self.process_group, self.device):
+            # EVERY rank switches the session off, whether it had one or not: a rank whose session was
+            # merely refused this once would otherwise issue this all-reduce again on the next step while
+            # its peers go straight to the generic path's gradient all-reduce
+            if sess is not None:
+                self._session_decline = "another rank's session was refused (the ranks decide together)"
+            self._session, self._session_off = None, True
+            return None, None
         if sess is None:
             return None, None
         if getattr(sess, "mode_pending", False):  # (data parallel, once: single graph or chunked all-reduce)
@@ -45,14 +66,12 @@ class _SessionSteps:
         from .modelprep import session_forward
         from .session import EngineSession
 
-        import os
-
         # From its second step on the session answers the model's forward pass itself, so comparing the caller's
         # loss with the session's says nothing about the forward pass any more.  Every K-th step (K =
         # ``HF_SESSION_VERIFY_EVERY``, default 16; ``HF_SESSION_VERIFY=1``: every step) the model therefore runs
         # its OWN forward pass and the session must reproduce its logits (1e-4) and loss (1e-5): a layer swapped,
         # frozen or re-configured behind the captured graphs shows up here instead of never
-        every = 1 if os.environ.get("HF_SESSION_VERIFY") == "1" else int(os.environ.get("HF_SESSION_VERIFY_EVERY", "16"))
+        every = _verify_every()
         verify = self._session is not None and every > 0 and self._session.steps % every == 0
         with session_forward(None if verify else self._session):  # (an existing session answers the forward pass)
             loss, outputs = forward()
@@ -78,12 +97,9 @@ class _SessionSteps:
                            "installs the layers the fused engine reads)")
             spec = sess.accepts(*args) if sess is not None else None
             if spec is None:
-                self._session_decline = ("; ".join(dict.fromkeys(why)) if why else
-                                         "a freshly built session does not accept this step's own forward pass")
-                self._session_failures += 1
-                if self._session_failures >= 2:
-                    self._session_off = True
-                    self._session_decline += " (refused twice: not tried again)"
+                self._session_failures, self._session_off, self._session_decline = _refusal(
+                    self._session_failures, "; ".join(dict.fromkeys(why)) if why else
+                    "a freshly built session does not accept this step's own forward pass")
                 return None, None, None
             self._session = sess
         own = sess.begin_step(outputs, spec)
@@ -125,8 +141,6 @@ class _SessionSteps:
     def _engine_diag_ef(self, model, loss_func, inputs, targets, reduction):
         """``sum_i g_i^2`` (/ N) on the session's engine, or ``None`` (no session for this model / shape / loss, train
         mode, data parallelism): the caller then takes the autograd construction."""
-        import os
-
         sess = self._session
         if (sess is None or self.process_group is not None
                 or reduction not in ("mean", "sum")):

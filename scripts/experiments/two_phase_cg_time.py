@@ -21,8 +21,8 @@ import torch.distributed as dist  # noqa: E402
 torch.cuda.set_device(0)
 dist.init_process_group("nccl")
 import pytorchhessianfree_amd as hf  # noqa: E402
+from pytorchhessianfree_amd import distributed as hfdist  # noqa: E402
 from pytorchhessianfree_amd import modelprep  # noqa: E402
-from pytorchhessianfree_amd import session as hfsession  # noqa: E402
 from pytorchhessianfree_amd import testproblems as tp  # noqa: E402
 
 model, (x, t), lossf = tp.resnet18_mnist(batch_size=32, device="cuda", data_seed=1)
@@ -50,22 +50,22 @@ def run(label, chunk):
 
 
 picked = []
-probed_pick = hfsession._concurrent_stream
+probed_pick = hfdist._concurrent_stream
 
 
 def next_pool_stream(cur, candidates=8):
     """(experiment) the NEXT pool stream whatever the probe says; the probe's verdict is recorded."""
     cand = torch.cuda.Stream()
-    picked.append(bool(hfsession._runs_beside(cand, cur)))
+    picked.append(bool(hfdist._runs_beside(cand, cur)))
     return cand, picked[-1]  # (round 6: the probe's verdict is returned and kept on the session)
 
 
 run("single graph + one compact all-reduce", "0")
-hfsession._concurrent_stream = next_pool_stream
+hfdist._concurrent_stream = next_pool_stream
 for k in range(8):
     run(f"two-phase, side stream = pool stream {k}", "1")
     print(json.dumps({"pool_stream": k, "probe_says_concurrent": picked[-1]}), flush=True)
-hfsession._concurrent_stream = probed_pick
+hfdist._concurrent_stream = probed_pick
 for k in range(3):
     run(f"two-phase, side stream chosen by the probe (session {k})", "1")
 dist.destroy_process_group()

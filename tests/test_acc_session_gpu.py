@@ -1,4 +1,4 @@
-"""GPU: ``HessianFree.acc_step()`` on the fused engine (``session.AccumulatedSession``) -- loss, gradient and every
+"""GPU: ``HessianFree.acc_step()`` on the fused engine (``acc_session.AccumulatedSession``) -- loss, gradient and every
 curvature product accumulated over lists of data chunks (reference ``/root/reference/hessianfree/optimizer.py:
 519-606, :608-684, :767-814``), one engine per chunk, the chunks' sweeps on parallel branches of ONE product
 graph inside ``cg()``'s iteration graph, trial losses as graph replays.
@@ -79,7 +79,7 @@ def test_acc_step_on_engine_equals_step_on_whole_batch_and_is_repeatable():
     acc, fa = _resnet_runs("acc", 2)
     sess = acc._acc_session
     # (eval-mode BatchNorm couples no samples and both chunks carry the weight 1 / 32 per sample: ONE engine on the
-    # concatenated chunks -- session.AccumulatedSession._merge_groups)
+    # concatenated chunks -- acc_session.AccumulatedSession._merge_groups)
     assert sess is not None and sess.steps == 2 and len(sess.engines) == 1 and sess.groups == [[0, 1]]
     assert "engine" in sess.mode and "ONE batch" in sess.mode
     whole, fw = _resnet_runs("step", 2)

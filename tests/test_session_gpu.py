@@ -762,3 +762,35 @@ def test_session_follows_a_frozen_weight_that_is_changed_between_steps(monkeypat
         opt.step(forward)
         assert opt._session is sess and sess.steps == 3
     assert not [w for w in rec if "persistent engine session" in str(w.message)], [str(w.message) for w in rec]
+
+
+def test_chunked_engine_operator_without_a_group_solves_like_the_single_graph():
+    """``session.ChunkedEngineOperator`` built without a process group (``plan_phases`` does not look at the group)
+    has no single product graph: ``raw_graph()`` returns ``None``, and ``cg()`` must call it in every iteration
+    instead of fusing K1-K3 around a product it never replays (that iterated on a stale ``output_buffer``).  The
+    model of the chunked leg of gpu_workers/dp_two_ranks.py, against a ``GraphedOperator`` of the same builder:
+    products to 1e-6 of the max-norm (``choose_product_mode``'s bound), solutions to 1e-5 of the max-norm (the
+    single- vs two-graph test, test_optimizer_gpu.py)."""
+    from pytorchhessianfree_amd.session import ChunkedEngineOperator
+
+    net, (xb, tb), ce = tp.resnet18_mnist(batch_size=6, device=DEV, data_seed=40)
+    modelprep.prepare_model(net, channels_last=True)
+    ps = [p for p in net.parameters() if p.requires_grad]
+
+    def builder():
+        o = net(xb)
+        return curvature.ggn_operator(ce(o, tb), o, ps)
+
+    chunked = ChunkedEngineOperator(builder, params=ps)
+    assert chunked.group is None and chunked.raw_graph() is None
+    single = curvature.GraphedOperator(builder, params=ps)
+    v = torch.randn(chunked.n, device=DEV, generator=torch.Generator(device=DEV).manual_seed(8))
+    a, b = chunked(v).clone(), single(v).clone()
+    within(float((a - b).abs().max() / b.abs().max()), 1e-6)
+    grad = torch.randn(chunked.n, device=DEV, generator=torch.Generator(device=DEV).manual_seed(9))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        xa, _, ra = hf.cg(hf.DampedCurvature(chunked, 0.1), grad, max_iter=12, tol=0.0, store_x_at_iters=[0])
+        xs, _, rs = hf.cg(hf.DampedCurvature(single, 0.1), grad, max_iter=12, tol=0.0, store_x_at_iters=[0])
+    assert ra == rs and len(xa) == len(xs)
+    within(float((xa[-1] - xs[-1]).abs().max() / xs[-1].abs().max()), 1e-5)

@@ -184,11 +184,11 @@ def test_ce_loss_spec_reads_the_loss_structure():
     assert ce_loss_spec(ce(leaf, t), leaf) is not None
 
 
-def test_accumulated_session_plans_engines_by_chunk_identity():
+def test_acc_session_plans_engines_by_chunk_identity():
     """``acc_step`` on the engine keys one engine per DISTINCT chunk (identity of its tensors): lists that share
     chunks -- the default, one list for loss, gradient and curvature (optimizer.py:519-606) -- share engines; distinct
     lists get their own; a chunk listed twice in one list is one engine (its weight counts twice)."""
-    from pytorchhessianfree_amd.session import AccumulatedSession
+    from pytorchhessianfree_amd.acc_session import AccumulatedSession
 
     a, b, c = [(torch.zeros(4, 3), torch.zeros(4)) for _ in range(3)]
     one = [a, b]
@@ -201,13 +201,13 @@ def test_accumulated_session_plans_engines_by_chunk_identity():
     assert len(slots) == 1 and roles == [(0, 0), (0,), (0,)]
 
 
-def test_accumulated_session_merges_chunks_of_equal_per_sample_weight():
+def test_acc_session_merges_chunks_of_equal_per_sample_weight():
     """Chunks that appear in the same lists the same number of times carry one per-sample weight (optimizer.py:
     677-684: ``N_k / sum N`` per chunk = ``1 / sum N`` per sample): for a model that does not couple the samples of
     a batch they run as ONE batch (the reference's own statement, tests/test_optimizer_acc.py:116-175).  Not merged:
     a train-mode BatchNorm / active dropout anywhere in the model, chunks of different shape, chunks with different
     list membership."""
-    from pytorchhessianfree_amd.session import AccumulatedSession
+    from pytorchhessianfree_amd.acc_session import AccumulatedSession
 
     net = torch.nn.Sequential(torch.nn.Conv2d(3, 4, 3), torch.nn.BatchNorm2d(4), torch.nn.Dropout(0.5)).eval()
     mk = lambda n, hw=8: (torch.zeros(n, 3, hw, hw), torch.zeros(n, dtype=torch.int64))  # noqa: E731
@@ -255,3 +255,28 @@ def test_mse_loss_spec_reads_the_loss_structure():
     assert mse_loss_spec(torch.nn.functional.mse_loss(out, t) + 0.1 * out.sum(), out) is None
     leaf = out.detach().clone().requires_grad_(True)  # (logits handed out as a leaf by a persistent session)
     assert mse_loss_spec(torch.nn.functional.mse_loss(leaf, t), leaf) is not None
+
+
+def test_iteration_graph_of_an_operator_without_a_product_graph_is_none(monkeypatch):
+    """``cg()``'s contract with a captured operator (``curvature.CapturedOperator``): a ``raw_graph()`` that returns
+    ``None`` -- two product graphs, no single one -- cannot be fused WITH its product, so ``_iteration_graph`` gives
+    ``None`` and ``cg()`` takes the unfused loop, which calls the operator.  (A K1-K3-only graph there would iterate
+    on a stale ``output_buffer``: a ``ChunkedEngineOperator`` without a process group did.)"""
+    import importlib
+
+    hfcg = importlib.import_module("pytorchhessianfree_amd.cg")
+
+    def no_library(*args, **kwargs):
+        raise AssertionError("the native library was touched")
+
+    monkeypatch.setattr(hfcg, "_IterationGraph", no_library)
+    monkeypatch.setattr(hfcg._lib, "load", no_library)
+    monkeypatch.delenv("HF_FUSE_ITERATION", raising=False)
+
+    class TwoGraphs:
+        def raw_graph(self):
+            return None
+
+    op = TwoGraphs()
+    assert hfcg._iteration_graph(op, None, None, 0.1, 0, with_product=True) is None
+    assert not getattr(op, "_iteration_graphs", None)
