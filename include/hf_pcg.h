@@ -275,7 +275,11 @@ int hf_chan_affine_ex(void* out, const void* a, const void* x, const void* mean,
  * workgroups each take a share of the rows and ALL channels, reading whole contiguous rows
  * (the default kernel gives each workgroup one 16-byte channel column of all rows: one cache
  * line per lane) -- and gw / gb receive `row_blocks` partial sums each, c elements apart, for
- * hf_pack_ex to add up.  ceil(rows / row_blocks) rows per workgroup; no empty workgroup allowed. */
+ * hf_pack_ex to add up.  ceil(rows / row_blocks) rows per workgroup; a row_blocks whose last share would start behind the
+ * end -- (row_blocks - 1) * ceil(rows / row_blocks) >= rows: an empty workgroup -- is refused with HF_ERR_ARG, as are
+ * (row_blocks > 1) slab strides that are not multiples of 4 elements and gw without x / mean / rstd.
+ * Rounding: gx, gres are fp32 throughout; gw / gb are accumulated in fp64 (xhat = (x - mean)*rstd is rounded to the
+ * dtype before the product) and rounded once per partial row. */
 int hf_chan_affine_bwd_ex(void* gx, void* gw, void* gb, void* gres, const void* gy, int gy_splits,
                           int64_t gy_slab, const void* gy2, int gy2_splits, int64_t gy2_slab,
                           const void* x, const void* mean, const void* rstd, const void* w,
@@ -283,7 +287,7 @@ int hf_chan_affine_bwd_ex(void* gx, void* gw, void* gb, void* gres, const void* 
                           int row_blocks, int dtype, void* stream);
 /* TWO independent layers in one launch (a residual block's first BatchNorm and its downsample
  * branch's, whose inputs come out of one grouped convolution launch): the arguments of
- * hf_chan_affine_ex resp. hf_chan_affine_bwd_ex (row_blocks >= 2) per problem; NHWC fp32 only. */
+ * hf_chan_affine_ex resp. hf_chan_affine_bwd_ex (row_blocks >= 2, same refusals) per problem; NHWC fp32 only. */
 typedef struct hf_affine_problem {
   void* out;
   const void *a, *x, *mean, *rstd, *w, *q, *r, *add, *mask_src;
@@ -334,6 +338,8 @@ int hf_bn_forward(void* y, void* y2, int64_t y2_ld, void* a_out, const void* a, 
  * S_x (`part_x`) and S_1 (`part_1`) -- what hf_chan_affine_bwd_ex wrote with gx = NULL, or the tangent convolution's
  * own epilogue (hf_conv2d_nhwc_group_slabs_bnsum) -- up in the same fixed order, forms q and r (vq / vr nullable: the
  * adjoint has none) and applies  out = mask_src > 0 ? t : 0,  t = sum(a slabs)*(w*rstd) + xhat*q + r + add.
+ * Rounding of q / r: the column sums are taken in fp64 and rounded to fp32, 1/count is rounded to fp32, then
+ * k = (w*rstd)*(1/count), q = vq - k*S_x -- six fp32 roundings.
  * (Round 4 also shipped the finalisation as a launch of its own, as the reduction launch's last workgroup and as one
  * launch around a grid barrier; measured slower -- profiles/r04_train_bn_forms.jsonl -- and removed in ABI v11.)
  */
@@ -387,7 +393,8 @@ int hf_bn_forward_train(void* y, void* y2, int64_t y2_ld, const void* a, const v
  * sum(g_z' xhat), sum(g_z'), rstd sum(g_z a') (`nparts` rows: what hf_chan_affine_bwd_ex leaves) and of sum(a' xhat),
  * sum(a') (`nparts_t` rows: hf_chan_affine_bwd_ex's, or the tangent convolution's epilogue sums) and
  * writes coef ([6][c]) and the closed-form share of g_gamma' (gw_corr, [c]: one more partial row for hf_pack_ex);
- * g_gamma1 / g_beta1: the first-order parameter gradients of the layer.  hf_bn_train_hessian_apply is the elementwise
+ * g_gamma1 / g_beta1: the first-order parameter gradients of the layer (the closed form is evaluated in fp64, every
+ * coefficient rounded to fp32 once).  hf_bn_train_hessian_apply is the elementwise
  * pass; a' arrives as the tangent convolution's `t_splits` split-K slabs.  fp32 NHWC, c % 4 == 0.
  */
 int hf_bn_train_hessian_coeffs(void* coef, void* gw_corr, const void* sum_gx2, const void* sum_g2, const void* sum_ga,
@@ -545,6 +552,7 @@ int hf_conv2d_nhwc_backward(void* dx, void* dw, const void* dy, const void* x, c
  * ggn_vector_product_from_plist (optimizer.py:461) obtains by differentiating the loss
  * twice (~14 small kernels per product); the host verifies this closed form against that
  * autograd sweep once per operator before using it.  [rows, cols] row-major, contiguous.
+ * <p, v> is accumulated in fp64 and rounded to the dtype once; `scale` is rounded to the dtype.
  */
 int hf_softmax_ce_hvp(void* out, const void* p, const void* v, double scale, int64_t rows,
                       int64_t cols, int dtype, void* stream);
@@ -605,7 +613,9 @@ int hf_linear_ce_head_slabs(int64_t rows);
  * examples/example_utils.py:59-83: logits = mean over the last map), inside J^T H_L J v, one launch:
  *   Jv[n,k] = mean_hw t[n,hw,k];  HJv = scale * p * (Jv - <p, Jv>);  g[n,hw,k] = HJv[n,k] / hw
  * t, g NHWC [n, hw, k]; p = softmax(logits) [n, k].  jv_out (nullable) receives Jv.  One workgroup per
- * sample.  Replaced: a mean reduction, hf_softmax_ce_hvp, a division and a broadcast copy.
+ * sample.  Replaced: a mean reduction, hf_softmax_ce_hvp, a division and a broadcast copy.  k <= 1024 (HF_ERR_ARG
+ * beyond).  The mean is a sequential fp32 sum over hw and one division; <p, Jv> is accumulated in fp64 and rounded once;
+ * `scale` is rounded to fp32.
  */
 int hf_pool_ce_head(void* g, void* jv_out, const void* t, const void* p, double scale, int64_t n, int64_t hw,
                     int64_t k, int dtype, void* stream);

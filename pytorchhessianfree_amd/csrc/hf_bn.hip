@@ -1307,6 +1307,21 @@ int hf_chan_affine_pair(const hf_affine_problem* problems, int dtype, void* stre
   return HF_OK;
 }
 
+// What the row-major adjoint kernel (row_blocks > 1) needs beyond its shape limits: every workgroup's row share starts
+// inside the tensor (share i covers rows [i*per, (i+1)*per), per = ceil(rows / row_blocks): an empty share would be a
+// partial row of zeros the caller did not plan for), slab strides that keep the 16-byte loads aligned, and the
+// statistics whenever the scale's gradient is asked for (without x the kernel would leave gw = 0).
+static bool adjoint_rows_args_ok(int64_t rows, int row_blocks, int gy_splits, int64_t gy_slab, const void* gy2,
+                                 int gy2_splits, int64_t gy2_slab, const void* gw, const void* x, const void* mean,
+                                 const void* rstd) {
+  const int64_t per = (rows + row_blocks - 1) / row_blocks;
+  if ((int64_t)(row_blocks - 1) * per >= rows) return false;
+  if (gy_splits > 1 && (gy_slab <= 0 || (gy_slab & 3))) return false;
+  if (gy2 && gy2_splits > 1 && (gy2_slab <= 0 || (gy2_slab & 3))) return false;
+  if (gw && (!x || !mean || !rstd)) return false;
+  return true;
+}
+
 int hf_chan_affine_bwd_pair(const hf_bn_adjoint_problem* problems, int dtype, void* stream) {
   if (!problems || dtype != HF_F32) return HF_ERR_ARG;
   BnAdjArgs q[2];
@@ -1317,6 +1332,9 @@ int hf_chan_affine_bwd_pair(const hf_bn_adjoint_problem* problems, int dtype, vo
       return HF_ERR_ARG;
     if (!(p.c % 4 == 0 && p.c / 4 <= BLOCK)) return HF_ERR_ARG;
     const int64_t rows = p.n * p.hw;
+    if (!adjoint_rows_args_ok(rows, p.row_blocks, p.gy_splits, p.gy_slab, p.gy2, p.gy2_splits, p.gy2_slab, p.gw, p.x,
+                              p.mean, p.rstd))
+      return HF_ERR_ARG;
     if (rows * p.c > 0x7fffffffLL || !aligned16(p.gy) || (p.gy2 && !aligned16(p.gy2)) || (p.x && !aligned16(p.x)) ||
         (p.mask_src && !aligned16(p.mask_src)) || (p.gx && !aligned16(p.gx)) || (p.gres && !aligned16(p.gres)))
       return HF_ERR_ALIGN;
@@ -1393,6 +1411,8 @@ int hf_chan_affine_bwd_ex(void* gx, void* gw, void* gb, void* gres, const void* 
   if (row_blocks > 1) {
     if (!(channels_last && c % 4 == 0 && c / 4 <= BLOCK && dtype == HF_F32)) return HF_ERR_ARG;
     const int64_t rows = n * hw;
+    if (!adjoint_rows_args_ok(rows, row_blocks, gy_splits, gy_slab, gy2, gy2_splits, gy2_slab, gw, x, mean, rstd))
+      return HF_ERR_ARG;
     if (rows * c > 0x7fffffffLL || !aligned16(gy) || (gy2 && !aligned16(gy2)) || (x && !aligned16(x)) ||
         (mask_src && !aligned16(mask_src)) || (gx && !aligned16(gx)) || (gres && !aligned16(gres)))
       return HF_ERR_ALIGN;

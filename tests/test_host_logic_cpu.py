@@ -585,10 +585,9 @@ def test_train_mode_batchnorm_hessian_closed_forms():
         dg_z = mask * (2 * y * dy)                     # second-order masked cotangent (the loss' own curvature)
         # the five row sums the kernels read, then the closed forms
         s_gx, s_g, s_ga = (dg_z * xh).sum(0), dg_z.sum(0), r * (g_z * da).sum(0)
-        corr = -r * (S1 * g_bet + Sx * g_gam)
-        dgg = s_gx + s_ga + corr
-        mG, m2, mGx = (dgam * g_bet + gam * s_g) / m, (dgam * g_gam + gam * dgg) / m, gam * g_gam / m
-        c = (-r * Sx, r * dgam, r * gam, -r * r * mGx, r * r * mGx * Sx - r * m2, -r * mG + r * r * mGx * S1)
+        from layer_refs import train_hessian_closed_form  # (shared with the kernel-level tests of these launches)
+
+        c, corr, dgg = train_hessian_closed_form(s_gx, s_g, s_ga, S1, Sx, g_gam, g_bet, gam, dgam, r, m)
         got_a = c[0] * g_a + c[1] * g_z + c[2] * dg_z + c[3] * da + c[4] * xh + c[5]
     assert float((got_a - want_a).abs().max()) < 1e-12
     assert float((dgg - want_g).abs().max()) < 1e-12 and float((s_g - want_b).abs().max()) < 1e-12
