@@ -37,14 +37,7 @@ __device__ __forceinline__ void chan_affine_body(
     const T rs = rstd ? rstd[c] : (T)1;  // (no BatchNorm: conv + bias layers of plain stacks)
     T acc = (T)0;
     if (a) {
-      T av = a[i];
-      for (int sp = 1; sp < a_splits; sp += 8) {  // split-K slabs: eight loads in flight, summed in split order
-        T t8[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t8[u] = a[(long long)(sp + u < a_splits ? sp + u : 0) * a_slab + i];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) av += sp + u < a_splits ? t8[u] : (T)0;
-      }
+      const T av = slab_sum<8>(a[i], a, i, a_splits, a_slab);  // split-K slabs: eight loads in flight
       acc = av * ((w ? w[c] : (T)1) * rs);
     }
     if (q) acc += ((x[i] - mean[c]) * rs) * q[c];
@@ -64,10 +57,6 @@ __device__ __forceinline__ void chan_affine_body(
 // memory-side cache the producer's slabs sit in), not bytes; the scalar walk above paid one per slab batch of
 // eight, one for w[c], one for x / q / r, one for add, one for the mask.  Same expressions, same order of
 // additions: bitwise the scalar walk's results.
-struct alignas(16) F4 { float e[4]; };
-
-__device__ __forceinline__ F4 ld4(const float* p) { return *reinterpret_cast<const F4*>(p); }
-
 __device__ __forceinline__ void chan_affine_v4_body(
     float* __restrict__ out, const float* __restrict__ a, const float* __restrict__ x,
     const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ w,
@@ -85,18 +74,7 @@ __device__ __forceinline__ void chan_affine_v4_body(
     if (r) r4 = ld4(r + c);
     if (add) addv = ld4(add + (add_ld ? row * add_ld + c : i));
     if (mask_src && !relu_self) mv = ld4(mask_src + i);
-    if (a) {
-      av = ld4(a + i);
-      for (int sp = 1; sp < a_splits; sp += 16) {  // split-K slabs: sixteen loads in flight, summed in split order
-        F4 t[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) t[u] = ld4(a + (long long)(sp + u < a_splits ? sp + u : 0) * a_slab + i);
-#pragma unroll
-        for (int u = 0; u < 16; ++u)
-#pragma unroll
-          for (int k = 0; k < 4; ++k) av.e[k] += sp + u < a_splits ? t[u].e[k] : 0.f;
-      }
-    }
+    if (a) av = slab_sum<16>(ld4(a + i), a, i, a_splits, a_slab);  // split-K slabs: sixteen loads in flight
     F4 o;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -192,6 +170,7 @@ __global__ __launch_bounds__(BLOCK) void k_chan_affine_bwd(
         const I idx = (n * C + c) * HW + ((I)lane - n * HW);
         T g = gy[idx], h = gy2 ? gy2[idx] : (T)0;
         const T m = mask_src ? mask_src[idx] : (T)1, xv = x ? x[idx] : (T)0;
+        // (written out, not slab_sum<16>: through the helper the fp64 instantiations got 8-16 instructions more)
         for (int sp = 1; sp < s1; sp += 16) {
           T v[16];
 #pragma unroll
@@ -240,6 +219,7 @@ __global__ __launch_bounds__(BLOCK) void k_chan_affine_bwd(
 #pragma unroll
       for (int t = 0; t < ITER; ++t) {
         if (e0 + (I)t * TPC < per) {
+          // (depth 1, unpredicated, written out: slab_sum<1> laid these loops out with 13-36 instructions more)
           for (int sp = 1; sp < s1; ++sp) g[t] += gy[(long long)sp * l1 + idx[t]];
           if (gy2)
             for (int sp = 1; sp < s2; ++sp) h[t] += gy2[(long long)sp * l2 + idx[t]];
@@ -275,11 +255,11 @@ __global__ __launch_bounds__(BLOCK) void k_chan_affine_bwd(
   }
 }
 
-// first + slabs 1..n-1 of a W-wide column, eight loads in flight, added in split order
+// first + slabs 1..n-1 of a W-wide column, eight loads in flight, added in split order.  (k_chan_affine_bwd_nhwc's own
+// copy of hf_common.h's slab_sum<8, true>: with that one the W = 4 kernels, which keep SGPRs in VGPR lanes, came out
+// 44-101 instructions longer)
 template <typename T, typename Col, int W>
-__device__ __forceinline__ Col slab_sum(Col first, const T* p, int n, long long stride) {
-  // batches of eight loads, ALL in flight before the first add; the last batch is predicated
-  // instead of a one-by-one tail (a tail of dependent load-add pairs costs a round trip each)
+__device__ __forceinline__ Col col_slab_sum(Col first, const T* p, int n, long long stride) {
   for (int sp = 1; sp < n; sp += 8) {
     Col v[8];
 #pragma unroll
@@ -311,7 +291,7 @@ __global__ __launch_bounds__(BS) void k_chan_affine_bwd_nhwc(
     const T* __restrict__ mask_src, I rows, I C, int s1 = 1, long long l1 = 0, int s2 = 1,
     long long l2 = 0, int row_blocks = 1) {
   __shared__ double lds[2 * W * (BS / 64)];
-  struct alignas(sizeof(T) * W) Col { T e[W]; };
+  using Col = ColOf<T, W>;
   // row_blocks > 1: block (q, rb) owns channel column q and the rb-th share of the rows and
   // writes its per-channel partial sums to gw/gb + rb*C (hf_pack_ex adds the shares up)
   const I cq = (I)blockIdx.x % (C / W), rb = (I)blockIdx.x / (C / W);
@@ -351,8 +331,10 @@ __global__ __launch_bounds__(BS) void k_chan_affine_bwd_nhwc(
         const I r = r0 + (I)t * BS;
         if (r < row_hi) {
           const I idx = r * C + c0;
-          if (s1 > 1) g[t] = slab_sum<T, Col, W>(g[t], gy + idx, s1, l1);  // split-K slabs, in split order
-          if (gy2 && s2 > 1) h[t] = slab_sum<T, Col, W>(h[t], gy2 + idx, s2, l2);
+          // split-K slabs: batches of eight, the last one predicated instead of a one-by-one tail (a tail of
+          // dependent load-add pairs costs a round trip each)
+          if (s1 > 1) g[t] = col_slab_sum<T, Col, W>(g[t], gy + idx, s1, l1);
+          if (gy2 && s2 > 1) h[t] = col_slab_sum<T, Col, W>(h[t], gy2 + idx, s2, l2);
         }
       }
     }
@@ -394,6 +376,32 @@ __global__ __launch_bounds__(BS) void k_chan_affine_bwd_nhwc(
   }
 }
 
+// Cross-row sums of a ROW-MAJOR thread map (thread (ty, tx) = (threadIdx.x / quads, threadIdx.x % quads), ty < RP, holds
+// eight sums of its rows in acc): red[k][ty][tx] (consecutive lanes -> consecutive words: no bank conflicts), then
+// 8*quads threads each add one (k, tx) column over ty in a fixed order and hand it to sink(k, tx, sum).  (The first
+// version let the `quads` threads of ty == 0 walk all 8 sums serially: 8*RP dependent LDS reads per thread behind
+// 8-way bank conflicts -- 72 % of the adjoint kernel's LDS cycles were conflict cycles,
+// profiles/r03_engine_kernel_counters.json.)  Same summation order, bitwise the same sums.
+// Contract: a BLOCK-thread workgroup calls it with all its threads and passes its own map (tx, ty, live == ty < RP;
+// RP * quads <= BLOCK, threads that are not live hold nothing); red holds 8 * RP * quads <= 8 * BLOCK doubles and must
+// be free on entry.  There is one barrier, between the stores and the column sums, and none at the end: a caller that
+// reuses red, or reads from other threads what sink wrote, puts its own __syncthreads after the call.
+template <typename Sink>
+__device__ __forceinline__ void cross_row_sums(const double (&acc)[8], double* red, unsigned RP, unsigned quads,
+                                               unsigned tx, unsigned ty, bool live, Sink&& sink) {
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) red[(k * RP + ty) * quads + tx] = acc[k];
+  }
+  __syncthreads();
+  for (unsigned idx = threadIdx.x; idx < 8 * quads; idx += BLOCK) {
+    const unsigned k = idx / quads, col = idx - k * quads;
+    double sum = 0.0;
+    for (unsigned t = 0; t < RP; ++t) sum += red[(k * RP + t) * quads + col];  // fixed order over ty
+    sink(k, col, sum);
+  }
+}
+
 // BatchNorm adjoint, NHWC fp32, ROW-MAJOR thread map: thread (ty, tx) owns the 16-byte channel
 // column tx of rows ty, ty + RP, ... of its block's row share, so that a wave reads whole
 // contiguous rows (the column-per-block kernel above reads 16 bytes every C*4 bytes: one cache
@@ -405,8 +413,7 @@ __device__ __forceinline__ void bn_adjoint_rows_body(
     const float* __restrict__ gy, int s1, long long l1, const float* __restrict__ gy2, int s2, long long l2,
     const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
     const float* __restrict__ w, const float* __restrict__ mask_src, unsigned rows, unsigned C,
-    unsigned rows_per_block, unsigned bid, double* red, const bool publish = false) {
-  struct alignas(16) Col { float e[4]; };
+    unsigned rows_per_block, unsigned bid, double* red) {
   const unsigned quads = C / 4, RP = BLOCK / quads;
   const unsigned tx = threadIdx.x % quads, ty = threadIdx.x / quads;
   const unsigned c0 = tx * 4;
@@ -428,14 +435,11 @@ __device__ __forceinline__ void bn_adjoint_rows_body(
     for (unsigned r = row_lo + ty; r < row_hi; r += 2 * RP) {
       const bool two = r + RP < row_hi;
       const unsigned idx0 = r * C + c0, idx1 = (two ? r + RP : r) * C + c0;
-      Col g0 = *reinterpret_cast<const Col*>(gy + idx0), g1 = *reinterpret_cast<const Col*>(gy + idx1);
-      Col h0, h1, x0, x1, m0, m1;
-      if (gy2) { h0 = *reinterpret_cast<const Col*>(gy2 + idx0); h1 = *reinterpret_cast<const Col*>(gy2 + idx1); }
-      if (x) { x0 = *reinterpret_cast<const Col*>(x + idx0); x1 = *reinterpret_cast<const Col*>(x + idx1); }
-      if (mask_src) {
-        m0 = *reinterpret_cast<const Col*>(mask_src + idx0);
-        m1 = *reinterpret_cast<const Col*>(mask_src + idx1);
-      }
+      F4 g0 = ld4(gy + idx0), g1 = ld4(gy + idx1);
+      F4 h0, h1, x0, x1, m0, m1;
+      if (gy2) { h0 = ld4(gy2 + idx0); h1 = ld4(gy2 + idx1); }
+      if (x) { x0 = ld4(x + idx0); x1 = ld4(x + idx1); }
+      if (mask_src) { m0 = ld4(mask_src + idx0); m1 = ld4(mask_src + idx1); }
       // split-K slabs of both rows and both cotangents: one loop, 8 slabs x up to 4 columns in flight per
       // pass (each column still adds its slabs in split order: bitwise the one-column-at-a-time sums, which
       // cost a round trip per column and batch)
@@ -444,19 +448,21 @@ __device__ __forceinline__ void bn_adjoint_rows_body(
       // VGPRs -- measured +0.5 % on ResNet-18, -1.5 % on All-CNN-C's large maps: profiles/r04_rows_straight_rejected.jsonl)
       const int smax = (gy2 && s2 > s1) ? s2 : s1;
       for (int sp = 1; sp < smax; sp += 8) {
-        Col vg0[8], vg1[8], vh0[8], vh1[8];
+        // (written out, not slab_issue / slab_add: those issue one row's eight loads back to back, this loop the two rows'
+        // loads of a slab next to each other -- another load order, 4 VGPRs and 58 instructions more)
+        F4 vg0[8], vg1[8], vh0[8], vh1[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
           const long long o1 = (long long)(sp + u < s1 ? sp + u : 0) * l1;
-          vg0[u] = *reinterpret_cast<const Col*>(gy + o1 + idx0);
-          vg1[u] = *reinterpret_cast<const Col*>(gy + o1 + idx1);
+          vg0[u] = ld4(gy + o1 + idx0);
+          vg1[u] = ld4(gy + o1 + idx1);
         }
         if (gy2 && s2 > 1) {
 #pragma unroll
           for (int u = 0; u < 8; ++u) {
             const long long o2 = (long long)(sp + u < s2 ? sp + u : 0) * l2;
-            vh0[u] = *reinterpret_cast<const Col*>(gy2 + o2 + idx0);
-            vh1[u] = *reinterpret_cast<const Col*>(gy2 + o2 + idx1);
+            vh0[u] = ld4(gy2 + o2 + idx0);
+            vh1[u] = ld4(gy2 + o2 + idx1);
           }
         }
 #pragma unroll
@@ -476,7 +482,7 @@ __device__ __forceinline__ void bn_adjoint_rows_body(
           }
         }
       }
-      Col o0, o1;
+      F4 o0, o1;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         float a0 = gy2 ? g0.e[k] + h0.e[k] : g0.e[k], a1 = gy2 ? g1.e[k] + h1.e[k] : g1.e[k];
@@ -490,31 +496,14 @@ __device__ __forceinline__ void bn_adjoint_rows_body(
           acc[2 * k + 1] += (double)a1;
         }
       }
-      if (gres) { *reinterpret_cast<Col*>(gres + idx0) = g0; if (two) *reinterpret_cast<Col*>(gres + idx1) = g1; }
-      if (gx) { *reinterpret_cast<Col*>(gx + idx0) = o0; if (two) *reinterpret_cast<Col*>(gx + idx1) = o1; }
+      if (gres) { *reinterpret_cast<F4*>(gres + idx0) = g0; if (two) *reinterpret_cast<F4*>(gres + idx1) = g1; }
+      if (gx) { *reinterpret_cast<F4*>(gx + idx0) = o0; if (two) *reinterpret_cast<F4*>(gx + idx1) = o1; }
     }
   }
-  // cross-row sums: red[k][ty][tx] (consecutive lanes -> consecutive words: no bank conflicts), then
-  // 8*quads threads each add one (k, tx) column over ty in a fixed order.  (The first version let the
-  // `quads` threads of ty == 0 walk all 8 sums serially: 8*RP dependent LDS reads per thread behind
-  // 8-way bank conflicts -- 72 % of this kernel's LDS cycles were conflict cycles,
-  // profiles/r03_engine_kernel_counters.json.)  Same summation order, bitwise the same sums.
-  if (live) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) red[(k * RP + ty) * quads + tx] = acc[k];
-  }
-  __syncthreads();
-  for (unsigned idx = threadIdx.x; idx < 8 * quads; idx += BLOCK) {
-    const unsigned k = idx / quads, col = idx - k * quads;
-    double sum = 0.0;
-    for (unsigned t = 0; t < RP; ++t) sum += red[(k * RP + t) * quads + col];  // fixed order over ty
+  cross_row_sums(acc, red, RP, quads, tx, ty, live, [&](unsigned k, unsigned col, double sum) {
     float* dst = (k & 1) ? gb : gw;
-    if (dst) {
-      // publish: write-through (sc1) store -- visible device-wide once drained, no release fence (in-launch readers)
-      if (publish) __hip_atomic_store(dst + bid * C + col * 4 + (k >> 1), (float)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else dst[bid * C + col * 4 + (k >> 1)] = (float)sum;
-    }
-  }
+    if (dst) dst[bid * C + col * 4 + (k >> 1)] = (float)sum;
+  });
 }
 
 __global__ __launch_bounds__(BLOCK) void k_bn_adjoint_rows(
@@ -584,6 +573,7 @@ __device__ __forceinline__ void final_column_sums2(const float* __restrict__ row
   }
   if (live) {
     for (unsigned p0 = ty + NB * G; p0 < nrows; p0 += NB * G) { issue(p0); add(p0); }
+    // (cross_row_sums written out: its stores belong into this `if (live)`; as a call behind it the train kernels changed)
 #pragma unroll
     for (int k = 0; k < 8; ++k) scratch[(k * G + ty) * quads + tx] = a[k];
   }
@@ -600,10 +590,10 @@ __device__ __forceinline__ void final_column_sums2(const float* __restrict__ row
 // ---- train-mode BatchNorm: the per-channel finalisation in the CONSUMER's prologue ---------------------------
 // k_chan_affine_v4 whose workgroups first add the reduction launch's partial rows up themselves (plain loads: the
 // rows come from the PREVIOUS launch; every workgroup the same fixed order, so the same q / r everywhere) --
-//   q = vq - w*rstd*S_x/m,  r = vr - w*rstd*S_1/m   (hf_bn_train_coeffs),  then  out = mask(a*(w*rstd) + xhat*q + r + add).
+//   q = vq - w*rstd*S_x/m,  r = vr - w*rstd*S_1/m,  then  out = mask(a*(w*rstd) + xhat*q + r + add).
 // The redundant sums cost each workgroup one more round trip (nparts * C * 8 bytes out of L2); the finalisation as the
-// reduction launch's TAIL (k_bn_adjoint_rows_train) costs a ticket, a drain and a one-workgroup re-read, as its own
-// launch (k_bn_train_coeffs) a launch boundary more.
+// reduction launch's tail would cost a ticket, a drain and a one-workgroup re-read, as its own launch a launch boundary
+// more.
 struct AffTrainArgs {
   float* out;
   const float *a, *x, *mean, *rstd, *w, *part_x, *part_1;
@@ -649,7 +639,8 @@ __device__ __forceinline__ void affine_train_body(const AffTrainArgs& p, unsigne
     if (ADD) addv = ld4(add + (add_ld ? rr * add_ld + cc : ii));
     if (MASK) mv = ld4(mask_src + ii);
     av = ld4(a + ii);
-    if (SLABS) {
+    if (SLABS) {  // the first batch: added behind the finalisation.  (This and the loop below are written out: through
+                  // slab_issue / slab_add the slab variants of the train kernels came out 42-99 instructions shorter)
 #pragma unroll
       for (int u = 0; u < 16; ++u) t[u] = ld4(a + (long long)(1 + u < a_splits ? 1 + u : 0) * a_slab + ii);
     }
@@ -722,7 +713,6 @@ __global__ __launch_bounds__(BLOCK) void k_chan_affine_v4_train_pair(const AffTr
 __global__ __launch_bounds__(BLOCK) void k_bn_stats_rows(
     float* __restrict__ a_out, const float* __restrict__ a, int splits, long long slab, double* part,
     unsigned rows, unsigned C, unsigned rows_per_block) {
-  struct alignas(16) Col { float e[4]; };
   __shared__ double red[BLOCK * 8];
   const unsigned quads = C / 4, RP = BLOCK / quads;
   const unsigned tx = threadIdx.x % quads, ty = threadIdx.x / quads;
@@ -736,18 +726,19 @@ __global__ __launch_bounds__(BLOCK) void k_bn_stats_rows(
   if (live) {
     for (unsigned r = row_lo + ty; r < row_hi; r += RP) {
       const unsigned idx = r * C + c0;
-      Col v = *reinterpret_cast<const Col*>(a + idx);
+      F4 v = ld4(a + idx);
+      // (written out: slab_sum<8> cost this kernel two instructions more)
       for (int sp = 1; sp < splits; sp += 8) {  // eight slabs in flight, added in split order
-        Col t[8];
+        F4 t[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-          t[u] = *reinterpret_cast<const Col*>(a + (long long)(sp + u < splits ? sp + u : 0) * slab + idx);
+          t[u] = ld4(a + (long long)(sp + u < splits ? sp + u : 0) * slab + idx);
 #pragma unroll
         for (int u = 0; u < 8; ++u)
 #pragma unroll
           for (int k = 0; k < 4; ++k) v.e[k] += sp + u < splits ? t[u].e[k] : 0.f;
       }
-      if (a_out) *reinterpret_cast<Col*>(a_out + idx) = v;
+      if (a_out) *reinterpret_cast<F4*>(a_out + idx) = v;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         acc[2 * k] += (double)v.e[k];
@@ -755,17 +746,9 @@ __global__ __launch_bounds__(BLOCK) void k_bn_stats_rows(
       }
     }
   }
-  if (live) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) red[(k * RP + ty) * quads + tx] = acc[k];
-  }
-  __syncthreads();
-  for (unsigned idx = threadIdx.x; idx < 8 * quads; idx += BLOCK) {
-    const unsigned k = idx / quads, col = idx - k * quads;
-    double sum = 0.0;
-    for (unsigned t = 0; t < RP; ++t) sum += red[(k * RP + t) * quads + col];  // fixed order over ty
+  cross_row_sums(acc, red, RP, quads, tx, ty, live, [&](unsigned k, unsigned col, double sum) {
     part[((size_t)blockIdx.x * 2 + (k & 1)) * C + col * 4 + (k >> 1)] = sum;
-  }
+  });
 }
 
 // Two independent layers' adjoints in ONE launch (see k_chan_affine_pair).
@@ -802,7 +785,7 @@ __global__ __launch_bounds__(BLOCK) void k_bn_adjoint_pre(
     const T* __restrict__ mask_src, const T* __restrict__ w, const T* __restrict__ rstd,
     unsigned total, unsigned C) {
   for (unsigned i = blockIdx.x * BLOCK + threadIdx.x; i < total; i += gridDim.x * BLOCK) {
-    T g = gyA[i];
+    T g = gyA[i];  // (depth 1, unpredicated, written out: slab_sum<1> cost two instructions and two SGPRs more)
     for (int sp = 1; sp < a_splits; ++sp) g += gyA[(long long)sp * a_slab + i];
     if (gyB) {
       T h = gyB[i];
@@ -828,14 +811,7 @@ __global__ __launch_bounds__(BLOCK) void k_bn_forward(
     const float* __restrict__ res, unsigned res_ld, int relu, unsigned total, unsigned C) {
   for (unsigned i = blockIdx.x * BLOCK + threadIdx.x; i < total; i += gridDim.x * BLOCK) {
   const unsigned c = i % C, row = i / C;
-  float av = a[i];
-  for (int sp = 1; sp < splits; sp += 8) {  // eight slabs in flight, summed in split order
-    float t8[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) t8[u] = a[(long long)(sp + u < splits ? sp + u : 0) * slab + i];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) av += sp + u < splits ? t8[u] : 0.f;
-  }
+  const float av = slab_sum<8>(a[i], a, i, splits, slab);  // eight slabs in flight
   if (a_out) a_out[i] = av;
   float t = av;
   if (rstd) t = ((av - mean[c]) * rstd[c]) * w[c];
@@ -1026,6 +1002,7 @@ __global__ __launch_bounds__(BLOCK) void k_bn_train_hessian_apply(
     const F4 mu = ld4(mean + c), rs = ld4(rstd + c);
     const F4 va = ld4(ga1 + i), v1 = ld4(gz1 + i), v2 = ld4(gz2 + i), xa = ld4(a + i);
     F4 ta = ld4(t + i);
+    // (written out: slab_sum<8, true> cost this kernel three instructions and two VGPRs more)
     for (int sp = 1; sp < t_splits; sp += 8) {  // the tangent convolution's slabs: eight in flight, added in split order
       F4 sl[8];
 #pragma unroll
@@ -1147,15 +1124,53 @@ static bool affine_vec4_ok(const void* out, const void* a, const void* x, const 
   return nhwc && c % 4 == 0 && out_ld % 4 == 0 && add_ld % 4 == 0 && a_slab % 4 == 0 && 2 * total < 0x7fffffffLL;
 }
 
+// One problem of hf_chan_affine_ex / hf_chan_affine_pair, any dtype and size: the refusals, and whether the
+// quad-per-thread walk may run.
+static int check_aff(bool& vec4, const void* out, const void* a, const void* x, const void* mean, const void* rstd,
+                     const void* w, const void* q, const void* r, const void* add, const void* mask_src, int64_t n,
+                     int64_t c, int64_t hw, int channels_last, int64_t out_ld, int64_t add_ld, int a_splits,
+                     int64_t a_slab) {
+  if (a_splits < 1 || (a_splits > 1 && (!a || a_slab <= 0))) return HF_ERR_ARG;
+  if (!out || n <= 0 || c <= 0 || hw <= 0) return HF_ERR_ARG;
+  if (q && (!x || !mean || !rstd)) return HF_ERR_ARG;
+  // a leading dimension is that of a buffer with MORE channels: >= 2x would be the
+  // tangent buffers' case, anything above the dense one is accepted
+  const int64_t dense = channels_last ? c : c * hw;
+  if ((out_ld && out_ld < dense) || (add_ld && (add_ld < dense || !add)) ||
+      out_ld > 0x3fffffffLL || add_ld > 0x3fffffffLL)
+    return HF_ERR_ARG;
+  vec4 = affine_vec4_ok(out, a, x, mean, rstd, w, q, r, add, mask_src, (long long)n * c * hw, c,
+                        channels_last || hw == 1, out_ld, add_ld, a_slab);
+  return HF_OK;
+}
+
+// The same problem as the fp32 kernel arguments with 32-bit sizes, which hold while 2 * total < 2^31: larger problems
+// are refused, so a filled AffArgs is always valid.
+static int fill_aff(AffArgs& k, void* out, const void* a, const void* x, const void* mean, const void* rstd,
+                    const void* w, const void* q, const void* r, const void* add, const void* mask_src, int relu_self,
+                    int64_t n, int64_t c, int64_t hw, int channels_last, int64_t out_ld, int64_t add_ld, int a_splits,
+                    int64_t a_slab) {
+  bool vec4 = false;
+  const int rc = check_aff(vec4, out, a, x, mean, rstd, w, q, r, add, mask_src, n, c, hw, channels_last, out_ld, add_ld,
+                           a_splits, a_slab);
+  if (rc) return rc;
+  const long long total = (long long)n * c * hw;
+  if (2 * total >= 0x7fffffffLL) return HF_ERR_ARG;
+  k = AffArgs{(float*)out, (const float*)a, (const float*)x, (const float*)mean, (const float*)rstd, (const float*)w,
+              (const float*)q, (const float*)r, (const float*)add, (const float*)mask_src, relu_self, (unsigned)total,
+              (unsigned)c, (unsigned)hw, channels_last, (unsigned)out_ld, (unsigned)add_ld, a_splits,
+              (long long)a_slab, vec4 ? 1 : 0};
+  return HF_OK;
+}
+
 template <typename T>
 static void launch_chan_affine(hipStream_t s, void* out, const void* a, const void* x,
                                const void* mean, const void* rstd, const void* w, const void* q,
                                const void* r, const void* add, const void* mask_src,
                                int relu_self, long long total, long long c, long long hw,
-                               int nhwc, long long out_ld, long long add_ld, int a_splits = 1,
-                               long long a_slab = 0) {
-  if (sizeof(T) == 4 && affine_vec4_ok(out, a, x, mean, rstd, w, q, r, add, mask_src, total, c, nhwc || hw == 1,
-                                       out_ld, add_ld, a_slab))
+                               int nhwc, long long out_ld, long long add_ld, int a_splits, long long a_slab,
+                               bool vec4) {
+  if (sizeof(T) == 4 && vec4)
     hipLaunchKernelGGL(k_chan_affine_v4, dim3(wide_grid(total / 4)), dim3(BLOCK), 0, s, (float*)out,
                        (const float*)a, (const float*)x, (const float*)mean, (const float*)rstd, (const float*)w,
                        (const float*)q, (const float*)r, (const float*)add, (const float*)mask_src, relu_self,
@@ -1186,23 +1201,18 @@ int hf_chan_affine_ex(void* out, const void* a, const void* x, const void* mean,
                       const void* mask_src, int relu_self, int64_t n, int64_t c, int64_t hw,
                       int channels_last, int64_t out_ld, int64_t add_ld, int a_splits, int64_t a_slab,
                       int dtype, void* stream) {
-  if (a_splits < 1 || (a_splits > 1 && (!a || a_slab <= 0))) return HF_ERR_ARG;
-  if (!out || n <= 0 || c <= 0 || hw <= 0) return HF_ERR_ARG;
-  if (q && (!x || !mean || !rstd)) return HF_ERR_ARG;
-  // a leading dimension is that of a buffer with MORE channels: >= 2x would be the
-  // tangent buffers' case, anything above the dense one is accepted
-  const int64_t dense = channels_last ? c : c * hw;
-  if ((out_ld && out_ld < dense) || (add_ld && (add_ld < dense || !add)) ||
-      out_ld > 0x3fffffffLL || add_ld > 0x3fffffffLL)
-    return HF_ERR_ARG;
+  bool vec4 = false;
+  const int rc = check_aff(vec4, out, a, x, mean, rstd, w, q, r, add, mask_src, n, c, hw, channels_last, out_ld, add_ld,
+                           a_splits, a_slab);
+  if (rc) return rc;
   const long long total = (long long)n * c * hw;
   hipStream_t s = (hipStream_t)stream;
   if (dtype == HF_F32)
     launch_chan_affine<float>(s, out, a, x, mean, rstd, w, q, r, add, mask_src, relu_self, total, c, hw,
-                              channels_last, out_ld, add_ld, a_splits, a_slab);
+                              channels_last, out_ld, add_ld, a_splits, a_slab, vec4);
   else if (dtype == HF_F64)
     launch_chan_affine<double>(s, out, a, x, mean, rstd, w, q, r, add, mask_src, relu_self, total, c, hw,
-                               channels_last, out_ld, add_ld, a_splits, a_slab);
+                               channels_last, out_ld, add_ld, a_splits, a_slab, false);
   else
     return HF_ERR_ARG;
   HF_HIP(hipGetLastError());
@@ -1285,21 +1295,10 @@ int hf_chan_affine_pair(const hf_affine_problem* problems, int dtype, void* stre
   unsigned blocks[2];
   for (int i = 0; i < 2; ++i) {
     const hf_affine_problem& p = problems[i];
-    if (p.a_splits < 1 || (p.a_splits > 1 && (!p.a || p.a_slab <= 0))) return HF_ERR_ARG;
-    if (!p.out || p.n <= 0 || p.c <= 0 || p.hw <= 0 || (p.q && (!p.x || !p.mean || !p.rstd))) return HF_ERR_ARG;
-    const int64_t dense = p.c;  // NHWC
-    if ((p.out_ld && p.out_ld < dense) || (p.add_ld && (p.add_ld < dense || !p.add)) ||
-        p.out_ld > 0x3fffffffLL || p.add_ld > 0x3fffffffLL)
-      return HF_ERR_ARG;
-    const long long total = (long long)p.n * p.c * p.hw;
-    if (2 * total >= 0x7fffffffLL) return HF_ERR_ARG;
-    q[i] = AffArgs{(float*)p.out, (const float*)p.a, (const float*)p.x, (const float*)p.mean,
-                   (const float*)p.rstd, (const float*)p.w, (const float*)p.q, (const float*)p.r,
-                   (const float*)p.add, (const float*)p.mask_src, p.relu_self, (unsigned)total, (unsigned)p.c,
-                   (unsigned)p.hw, 1, (unsigned)p.out_ld, (unsigned)p.add_ld, p.a_splits, (long long)p.a_slab, 0};
-    q[i].vec4 = affine_vec4_ok(p.out, p.a, p.x, p.mean, p.rstd, p.w, p.q, p.r, p.add, p.mask_src, total, p.c, 1,
-                               p.out_ld, p.add_ld, p.a_slab) ? 1 : 0;
-    blocks[i] = (unsigned)wide_grid(q[i].vec4 ? total / 4 : total);
+    const int rc = fill_aff(q[i], p.out, p.a, p.x, p.mean, p.rstd, p.w, p.q, p.r, p.add, p.mask_src, p.relu_self, p.n,
+                            p.c, p.hw, 1 /* NHWC */, p.out_ld, p.add_ld, p.a_splits, p.a_slab);
+    if (rc) return rc;
+    blocks[i] = (unsigned)wide_grid(q[i].vec4 ? q[i].total / 4 : q[i].total);
   }
   hipLaunchKernelGGL(k_chan_affine_pair, dim3(blocks[0] + blocks[1]), dim3(BLOCK), 0, (hipStream_t)stream, q[0],
                      q[1], blocks[0]);
@@ -1307,19 +1306,29 @@ int hf_chan_affine_pair(const hf_affine_problem* problems, int dtype, void* stre
   return HF_OK;
 }
 
-// What the row-major adjoint kernel (row_blocks > 1) needs beyond its shape limits: every workgroup's row share starts
+// One problem of the row-share form (hf_chan_affine_bwd_ex with row_blocks > 1, hf_chan_affine_bwd_pair; fp32 NHWC).
+// What the row-major adjoint kernel needs beyond its shape limits: every workgroup's row share starts
 // inside the tensor (share i covers rows [i*per, (i+1)*per), per = ceil(rows / row_blocks): an empty share would be a
 // partial row of zeros the caller did not plan for), slab strides that keep the 16-byte loads aligned, and the
 // statistics whenever the scale's gradient is asked for (without x the kernel would leave gw = 0).
-static bool adjoint_rows_args_ok(int64_t rows, int row_blocks, int gy_splits, int64_t gy_slab, const void* gy2,
-                                 int gy2_splits, int64_t gy2_slab, const void* gw, const void* x, const void* mean,
-                                 const void* rstd) {
-  const int64_t per = (rows + row_blocks - 1) / row_blocks;
-  if ((int64_t)(row_blocks - 1) * per >= rows) return false;
-  if (gy_splits > 1 && (gy_slab <= 0 || (gy_slab & 3))) return false;
-  if (gy2 && gy2_splits > 1 && (gy2_slab <= 0 || (gy2_slab & 3))) return false;
-  if (gw && (!x || !mean || !rstd)) return false;
-  return true;
+static int fill_bn_adj_rows(BnAdjArgs& k, void* gx, void* gw, void* gb, void* gres, const void* gy, int gy_splits,
+                            int64_t gy_slab, const void* gy2, int gy2_splits, int64_t gy2_slab, const void* x,
+                            const void* mean, const void* rstd, const void* w, const void* mask_src, int64_t n,
+                            int64_t c, int64_t hw, int row_blocks) {
+  if (!gy || n <= 0 || c <= 0 || hw <= 0 || gy_splits < 1 || gy2_splits < 1 || row_blocks < 2) return HF_ERR_ARG;
+  if (!(c % 4 == 0 && c / 4 <= BLOCK)) return HF_ERR_ARG;
+  const int64_t rows = n * hw, per = (rows + row_blocks - 1) / row_blocks;
+  if ((int64_t)(row_blocks - 1) * per >= rows) return HF_ERR_ARG;
+  if (gy_splits > 1 && (gy_slab <= 0 || (gy_slab & 3))) return HF_ERR_ARG;
+  if (gy2 && gy2_splits > 1 && (gy2_slab <= 0 || (gy2_slab & 3))) return HF_ERR_ARG;
+  if (gw && (!x || !mean || !rstd)) return HF_ERR_ARG;
+  if (rows * c > 0x7fffffffLL || !aligned16(gy) || (gy2 && !aligned16(gy2)) || (x && !aligned16(x)) ||
+      (mask_src && !aligned16(mask_src)) || (gx && !aligned16(gx)) || (gres && !aligned16(gres)))
+    return HF_ERR_ALIGN;
+  k = BnAdjArgs{(float*)gx, (float*)gw, (float*)gb, (float*)gres, (const float*)gy, gy_splits, (long long)gy_slab,
+                (const float*)gy2, gy2_splits, (long long)gy2_slab, (const float*)x, (const float*)mean,
+                (const float*)rstd, (const float*)w, (const float*)mask_src, (unsigned)rows, (unsigned)c, (unsigned)per};
+  return HF_OK;
 }
 
 int hf_chan_affine_bwd_pair(const hf_bn_adjoint_problem* problems, int dtype, void* stream) {
@@ -1328,21 +1337,9 @@ int hf_chan_affine_bwd_pair(const hf_bn_adjoint_problem* problems, int dtype, vo
   unsigned blocks[2];
   for (int i = 0; i < 2; ++i) {
     const hf_bn_adjoint_problem& p = problems[i];
-    if (!p.gy || p.n <= 0 || p.c <= 0 || p.hw <= 0 || p.gy_splits < 1 || p.gy2_splits < 1 || p.row_blocks < 2)
-      return HF_ERR_ARG;
-    if (!(p.c % 4 == 0 && p.c / 4 <= BLOCK)) return HF_ERR_ARG;
-    const int64_t rows = p.n * p.hw;
-    if (!adjoint_rows_args_ok(rows, p.row_blocks, p.gy_splits, p.gy_slab, p.gy2, p.gy2_splits, p.gy2_slab, p.gw, p.x,
-                              p.mean, p.rstd))
-      return HF_ERR_ARG;
-    if (rows * p.c > 0x7fffffffLL || !aligned16(p.gy) || (p.gy2 && !aligned16(p.gy2)) || (p.x && !aligned16(p.x)) ||
-        (p.mask_src && !aligned16(p.mask_src)) || (p.gx && !aligned16(p.gx)) || (p.gres && !aligned16(p.gres)))
-      return HF_ERR_ALIGN;
-    const unsigned rpb = (unsigned)((rows + p.row_blocks - 1) / p.row_blocks);
-    q[i] = BnAdjArgs{(float*)p.gx, (float*)p.gw, (float*)p.gb, (float*)p.gres, (const float*)p.gy, p.gy_splits,
-                     (long long)p.gy_slab, (const float*)p.gy2, p.gy2_splits, (long long)p.gy2_slab,
-                     (const float*)p.x, (const float*)p.mean, (const float*)p.rstd, (const float*)p.w,
-                     (const float*)p.mask_src, (unsigned)rows, (unsigned)p.c, rpb};
+    const int rc = fill_bn_adj_rows(q[i], p.gx, p.gw, p.gb, p.gres, p.gy, p.gy_splits, p.gy_slab, p.gy2, p.gy2_splits,
+                                    p.gy2_slab, p.x, p.mean, p.rstd, p.w, p.mask_src, p.n, p.c, p.hw, p.row_blocks);
+    if (rc) return rc;
     blocks[i] = (unsigned)p.row_blocks;
   }
   hipLaunchKernelGGL(k_bn_adjoint_rows_pair, dim3(blocks[0] + blocks[1]), dim3(BLOCK), 0, (hipStream_t)stream,
@@ -1409,19 +1406,14 @@ int hf_chan_affine_bwd_ex(void* gx, void* gw, void* gb, void* gres, const void* 
   if (!gy || n <= 0 || c <= 0 || hw <= 0 || gy_splits < 1 || gy2_splits < 1 || row_blocks < 1) return HF_ERR_ARG;
   // row shares: the row-major NHWC fp32 kernel
   if (row_blocks > 1) {
-    if (!(channels_last && c % 4 == 0 && c / 4 <= BLOCK && dtype == HF_F32)) return HF_ERR_ARG;
-    const int64_t rows = n * hw;
-    if (!adjoint_rows_args_ok(rows, row_blocks, gy_splits, gy_slab, gy2, gy2_splits, gy2_slab, gw, x, mean, rstd))
-      return HF_ERR_ARG;
-    if (rows * c > 0x7fffffffLL || !aligned16(gy) || (gy2 && !aligned16(gy2)) || (x && !aligned16(x)) ||
-        (mask_src && !aligned16(mask_src)) || (gx && !aligned16(gx)) || (gres && !aligned16(gres)))
-      return HF_ERR_ALIGN;
-    const unsigned rpb = (unsigned)((rows + row_blocks - 1) / row_blocks);
-    hipLaunchKernelGGL(k_bn_adjoint_rows, dim3((unsigned)row_blocks), dim3(BLOCK), 0, (hipStream_t)stream,
-                       (float*)gx, (float*)gw, (float*)gb, (float*)gres, (const float*)gy, gy_splits,
-                       (long long)gy_slab, (const float*)gy2, gy2_splits, (long long)gy2_slab, (const float*)x,
-                       (const float*)mean, (const float*)rstd, (const float*)w, (const float*)mask_src,
-                       (unsigned)rows, (unsigned)c, rpb);
+    if (!(channels_last && dtype == HF_F32)) return HF_ERR_ARG;
+    BnAdjArgs k;
+    const int rc = fill_bn_adj_rows(k, gx, gw, gb, gres, gy, gy_splits, gy_slab, gy2, gy2_splits, gy2_slab, x, mean,
+                                    rstd, w, mask_src, n, c, hw, row_blocks);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_bn_adjoint_rows, dim3((unsigned)row_blocks), dim3(BLOCK), 0, (hipStream_t)stream, k.gx, k.gw,
+                       k.gb, k.gres, k.gy, k.s1, k.l1, k.gy2, k.s2, k.l2, k.x, k.mean, k.rstd, k.w, k.mask_src, k.rows,
+                       k.C, k.rows_per_block);
     HF_HIP(hipGetLastError());
     return HF_OK;
   }

@@ -1,5 +1,5 @@
 // hf_common.h -- what the translation units of libhfpcg.so share: workgroup size, 16-byte vector types, the
-// fixed-order block reduction, error / alignment / grid helpers.  gfx950 (wave64) only.
+// fixed-order block reduction, the split-K slab sum, error / alignment / grid helpers.  gfx950 (wave64) only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -79,6 +79,65 @@ __device__ __forceinline__ void reduce_partials(const double* __restrict__ part,
     for (int k = 0; k < K; ++k) out[k] += part[k * stride + i];
   }
   block_allreduce<K>(out, lds);
+}
+
+// ---------------------------------------------------------------------------
+// split-K slabs.  A producer leaves n slabs `stride` elements apart; every consumer adds them up as
+//   first (slab 0), then slabs 1 .. n-1 in split order,
+// NB loads in flight per round trip (all issued before the first addition), a load past the last slab reads slab 0
+// (valid memory) and is discarded.  The order of the additions does not depend on NB: bitwise the same sums.
+// V is what a thread owns of each slab: a scalar T or a W-wide aligned column of T.
+// ---------------------------------------------------------------------------
+template <typename T, int W>
+struct alignas(sizeof(T) * W) ColOf { T e[W]; };
+using F4 = ColOf<float, 4>;  // the 16-byte quad of floats
+
+__device__ __forceinline__ F4 ld4(const float* p) { return *reinterpret_cast<const F4*>(p); }
+
+// s += v where `on`.  BRANCH picks the spelling: a select (the additions are straight-line code) or a branch around
+// them; the sums are the same, the register allocation of the kernel around them is not, so each site says which.
+template <bool BRANCH, typename T>
+__device__ __forceinline__ void add_where(T& s, const T& v, bool on) {
+  if (BRANCH) { if (on) s += v; }
+  else s += on ? v : (T)0;
+}
+template <bool BRANCH, typename T, int W>
+__device__ __forceinline__ void add_where(ColOf<T, W>& s, const ColOf<T, W>& v, bool on) {
+  if (BRANCH) {
+    if (on) {
+#pragma unroll
+      for (int k = 0; k < W; ++k) s.e[k] += v.e[k];
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < W; ++k) s.e[k] += on ? v.e[k] : (T)0;
+  }
+}
+
+// first half: issue the loads of slabs sp .. sp+NB-1 (this thread's part of a slab starts `off` elements into it)
+template <int NB, typename V, typename T, typename I>
+__device__ __forceinline__ void slab_issue(V (&v)[NB], const T* p, I off, int sp, int n, long long stride) {
+#pragma unroll
+  for (int u = 0; u < NB; ++u)
+    v[u] = *reinterpret_cast<const V*>(p + (long long)(sp + u < n ? sp + u : 0) * stride + off);
+}
+
+// second half: add that batch in split order, predicated
+template <bool BRANCH, int NB, typename V>
+__device__ __forceinline__ void slab_add(V& s, const V (&v)[NB], int sp, int n) {
+#pragma unroll
+  for (int u = 0; u < NB; ++u) add_where<BRANCH>(s, v[u], sp + u < n);
+}
+
+// first + slabs 1 .. n-1
+template <int NB, bool BRANCH = false, typename V, typename T, typename I>
+__device__ __forceinline__ V slab_sum(V first, const T* p, I off, int n, long long stride) {
+  for (int sp = 1; sp < n; sp += NB) {
+    V v[NB];
+    slab_issue(v, p, off, sp, n, stride);
+    slab_add<BRANCH>(first, v, sp, n);
+  }
+  return first;
 }
 
 template <int K>

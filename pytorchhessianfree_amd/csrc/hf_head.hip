@@ -6,10 +6,7 @@
 //
 // All tensors fp32, activations NHWC.
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "hf_pcg.h"
+#include "hf_common.h"
 
 namespace {
 
@@ -68,24 +65,9 @@ __global__ __launch_bounds__(HB) void k_maxpool_adjoint(float* __restrict__ g, c
       // slabs in batches of eight, all in flight before the first addition (one at a time is a dependent round
       // trip per slab: the first block's data gradient arrives as ~15 of them); same order of additions
       float v = A[o];
-      float w = B ? B[o] : 0.f;
-      for (int s = 1; s < a_splits; s += 8) {
-        float t8[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t8[u] = A[(size_t)(s + u < a_splits ? s + u : 0) * a_slab + o];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v += s + u < a_splits ? t8[u] : 0.f;
-      }
-      if (B) {
-        for (int s = 1; s < b_splits; s += 8) {
-          float t8[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) t8[u] = B[(size_t)(s + u < b_splits ? s + u : 0) * b_slab + o];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) w += s + u < b_splits ? t8[u] : 0.f;
-        }
-        v = v + w;
-      }
+      const float w = B ? B[o] : 0.f;
+      v = slab_sum<8>(v, A, o, a_splits, a_slab);
+      if (B) v = v + slab_sum<8>(w, B, o, b_splits, b_slab);
       acc += v;
     }
   g[i] = acc;

@@ -340,7 +340,20 @@ def mask_like(gen, *shape, dtype=torch.float32):
 
 
 EVAL_SHAPES = [(1568, 64), (32, 512), (200, 96), (37, 12), (5, 4), (130, 260), (64, 1024), (3, 20)]
-SLAB_COUNTS = [(1, None), (1, 1), (3, 1), (8, 1), (9, 2), (1, 9), (2, 17), (17, 17)]
+# Up to 17 slabs a 16-deep batch loop (which starts at slab 1) makes one pass.  18 is the first count with a second
+# pass, 33 fills two passes exactly, 34 adds a third with one live load; the 8-deep loops end on a partial batch at 18
+# and 34.
+SLAB_COUNTS_ONE_PASS = [(1, None), (1, 1), (3, 1), (8, 1), (9, 2), (1, 9), (2, 17), (17, 17)]
+SLAB_COUNTS_MORE_PASSES = [(18, 1), (1, 18), (34, 33)]
+SLAB_COUNTS = SLAB_COUNTS_ONE_PASS + SLAB_COUNTS_MORE_PASSES
+
+
+def eval_cases():
+    """(shape, slab counts, i) of the eval-mode forms; i numbers the cases and picks each one's variant.  The counts
+    with more than one 16-deep pass come last, so that the cases before them keep their numbers."""
+    pairs = [(sh, sl) for sh in EVAL_SHAPES for sl in SLAB_COUNTS_ONE_PASS] + \
+            [(sh, sl) for sh in EVAL_SHAPES for sl in SLAB_COUNTS_MORE_PASSES]
+    return [(sh, sl, i) for i, (sh, sl) in enumerate(pairs)]
 
 
 def eval_inputs(rows, c, s1, s2, dtype=torch.float32, tag="eval"):
@@ -504,11 +517,12 @@ def pick(o, names, drop):
 
 
 # (rows, c, splits, nparts): c in {4, 12, 96, 1024} x nparts in {1, 7, 64, 257} (both sides of HF_FCS_BATCH * G partial
-# rows per pass), splits in {1, 8, 9}
+# rows per pass), splits in {1, 8, 9}; then 18 and 34 slabs: a second and a third 16-deep pass
 TRAIN_CASES = [(64, 4, 1, 1), (37, 4, 8, 7), (50, 4, 9, 64), (40, 4, 8, 257),
                (37, 12, 8, 1), (33, 12, 9, 7), (200, 12, 1, 64), (64, 12, 9, 257),
                (200, 96, 9, 1), (130, 96, 1, 7), (64, 96, 8, 64), (37, 96, 9, 257),
-               (32, 1024, 8, 1), (5, 1024, 9, 7), (16, 1024, 1, 64), (32, 1024, 8, 257)]
+               (32, 1024, 8, 1), (5, 1024, 9, 7), (16, 1024, 1, 64), (32, 1024, 8, 257),
+               (37, 12, 18, 7), (32, 1024, 34, 64)]
 
 
 def train_inputs(rows, c, splits, nparts):

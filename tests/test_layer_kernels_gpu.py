@@ -89,7 +89,7 @@ def _ld(v, c):
     return v.ld[0] * c + v.ld[1] if v.ld[0] else 0
 
 
-CASES = [(sh, sl, i) for i, (sh, sl) in enumerate((sh, sl) for sh in L.EVAL_SHAPES for sl in L.SLAB_COUNTS)]
+CASES = L.eval_cases()
 _ids = lambda v: str(v).replace(" ", "")  # noqa: E731
 
 
@@ -207,12 +207,17 @@ def _check_bwd(k, outs):
 
 def _bwd_cases():
     out = []
-    for i, (sh, sl) in enumerate((sh, sl) for sh in L.EVAL_SHAPES for sl in L.SLAB_COUNTS):
+    for sh, sl, i in CASES:
         ch = L.row_block_choices(*sh)
         out.append((sh, sl, i, ch[i % len(ch)]))
     for j, sh in enumerate(L.EVAL_SHAPES):
         for m, rb in enumerate(L.row_block_choices(*sh)):
-            out.append((sh, L.SLAB_COUNTS[(3 * j + m) % len(L.SLAB_COUNTS)], j + m, rb))
+            out.append((sh, L.SLAB_COUNTS_ONE_PASS[(3 * j + m) % len(L.SLAB_COUNTS_ONE_PASS)], j + m, rb))
+    # more than one 16-deep pass without row shares: the channel-per-wave kernel with one element per lane (rows <= 64)
+    # and with several (200 rows) for odd i (hw = 1), the column-per-block kernel for even i
+    for sh in ((32, 512), (37, 12), (200, 96)):
+        for sl in L.SLAB_COUNTS_MORE_PASSES:
+            out += [(sh, sl, 5, 1), (sh, sl, 0, 1)]
     return out
 
 

@@ -270,7 +270,7 @@ def _col_ratio(elem64, want_e, M_e, R):
     return L.ratio(elem64.sum(0).float(), want_e.sum(0), M_e.sum(0), R)
 
 
-CASES = [(shape, sl, i) for i, (shape, sl) in enumerate((sh, sl) for sh in L.EVAL_SHAPES for sl in L.SLAB_COUNTS)]
+CASES = L.eval_cases()
 
 
 @pytest.mark.parametrize("shape,slabs,i", CASES, ids=lambda v: str(v).replace(" ", ""))
