@@ -471,7 +471,9 @@ int hf_conv2d_nhwc_slabs_unpack(void* out, const void* act, const void* mat, int
  * hf_bn_adjoint_pre: both cotangents; hf_pack_ex: sources).  Measured 6-11 us per launch on the
  * ResNet-18 shapes against 12-20 us with the in-launch reduction.  `hf_conv2d_nhwc_plan`
  * returns the number of splits the launch will use (>= 1; pure host arithmetic), which the
- * caller needs to size the slab buffer; pass it back as `splits`.  For direction 2 every slab
+ * caller needs to size the slab buffer; pass it back as `splits`.  One host function, plan_problem() in
+ * csrc/hf_conv.hip, is the single definition of that plan: hf_conv2d_nhwc_plan and every launching entry
+ * point run it, and a launch whose `splits` is not the planned count is refused.  For direction 2 every slab
  * must be zero-initialised once if the geometry has taps that never meet data; `out_c` (0 = c)
  * restricts the output to X's first out_c channels, laid out [k][r][q][out_c] -- X may carry
  * zero-padding channels that make its rows 16-byte multiples (the 49-tap im2col of a stem).

@@ -493,19 +493,23 @@ class ConvProblem(ctypes.Structure):
                                                             ("mat_ld", c_int64)]
 
 
+def _fill_problem(q, prob):
+    direction, out, act, mat, geo, splits, act_ld, out_c = prob[:8]
+    q.mat_ld = prob[8] if len(prob) > 8 else 0
+    n, h, w, c, k, r, s, st, pd = geo
+    q.direction, q.out, q.act, q.mat = int(direction), out.data_ptr(), act.data_ptr(), mat.data_ptr()
+    q.n, q.h, q.w, q.c, q.k, q.r, q.s = n, h, w, c, k, r, s
+    q.stride_h, q.stride_w, q.pad_h, q.pad_w = st[0], st[1], pd[0], pd[1]
+    q.act_ld, q.out_c, q.splits = act_ld, out_c, splits
+    q.slab_stride = out.shape[1] if out.dim() == 2 else 0
+
+
 def conv_group_slabs(problems, device):
     """One launch for up to 4 slab-mode convolutions; ``problems``: tuples ``(direction, out, act, mat,
-    (n, h, w, c, k, r, s, stride, padding), splits, act_ld, out_c)`` with ``out`` a [splits, ...] buffer."""
+    (n, h, w, c, k, r, s, stride, padding), splits, act_ld, out_c[, mat_ld])`` with ``out`` a [splits, ...] buffer."""
     arr = (ConvProblem * len(problems))()
     for q, prob in zip(arr, problems):
-        direction, out, act, mat, geo, splits, act_ld, out_c = prob[:8]
-        q.mat_ld = prob[8] if len(prob) > 8 else 0
-        n, h, w, c, k, r, s, st, pd = geo
-        q.direction, q.out, q.act, q.mat = int(direction), out.data_ptr(), act.data_ptr(), mat.data_ptr()
-        q.n, q.h, q.w, q.c, q.k, q.r, q.s = n, h, w, c, k, r, s
-        q.stride_h, q.stride_w, q.pad_h, q.pad_w = st[0], st[1], pd[0], pd[1]
-        q.act_ld, q.out_c, q.splits = act_ld, out_c, splits
-        q.slab_stride = out.shape[1] if out.dim() == 2 else 0
+        _fill_problem(q, prob)
     check(load().hf_conv2d_nhwc_group_slabs(ctypes.cast(arr, c_void_p), len(problems), HF_F32,
                                             current_stream_ptr(device)), "hf_conv2d_nhwc_group_slabs")
 
@@ -536,17 +540,6 @@ def conv_group_slabs_bnsum(problems, sums, device):
         return False
     check(rc, "hf_conv2d_nhwc_group_slabs_bnsum")
     return True
-
-
-def _fill_problem(q, prob):
-    direction, out, act, mat, geo, splits, act_ld, out_c = prob[:8]
-    q.mat_ld = prob[8] if len(prob) > 8 else 0
-    n, h, w, c, k, r, s, st, pd = geo
-    q.direction, q.out, q.act, q.mat = int(direction), out.data_ptr(), act.data_ptr(), mat.data_ptr()
-    q.n, q.h, q.w, q.c, q.k, q.r, q.s = n, h, w, c, k, r, s
-    q.stride_h, q.stride_w, q.pad_h, q.pad_w = st[0], st[1], pd[0], pd[1]
-    q.act_ld, q.out_c, q.splits = act_ld, out_c, splits
-    q.slab_stride = out.shape[1] if out.dim() == 2 else 0
 
 
 def conv_dw_slabs(d_problem, w_problem, device):

@@ -816,13 +816,6 @@ __global__ __launch_bounds__(CT) void k_conv_dw(const ConvArgs d, const ConvArgs
 // same tensor (a residual block's first convolution and its downsample branch): one launch for
 // both tangent convolutions, one for both layers' data + weight gradients.
 constexpr int GROUP_MAX = 4;
-struct GroupArgs {
-  ConvArgs a[GROUP_MAX];
-  int tn[GROUP_MAX];       // 1: weight gradient (TN body), 0: forward / data gradient (NT body)
-  int start[GROUP_MAX + 1];
-  int n;
-};
-
 // (the problems arrive as SEPARATE by-value arguments: indexing an array of them inside one by-value
 // struct made hipcc copy all 1.2 KB to scratch memory, and every field read in the K loops a scratch
 // load -- measured 3x on the 128-wide configurations)
@@ -953,7 +946,7 @@ FastDiv make_fastdiv(int64_t d) {
 }
 
 // the divisors of the kernels' prologues (see FastDiv); called on the copy that is handed to the launch
-void seal(ConvArgs& a, int direction) {
+void seal(ConvArgs& a) {
   const int bk = a.big ? Big::BK : Small::BK;
   const int bn = a.big == 1 ? Big::BN : a.big == 2 ? Big96::BN : Small::BN;
   a.fd_tiles_n = make_fastdiv(a.tiles_n);
@@ -964,13 +957,12 @@ void seal(ConvArgs& a, int direction) {
   a.fd_csteps = make_fastdiv((a.cs + bk - 1) / bk);
   a.fd_cblocks = make_fastdiv((a.cs + bn - 1) / bn);
   a.fd_cs = make_fastdiv(a.cs);
-  (void)direction;
 }
 
-// Fill `a` for one direction; returns the number of workgroups (<= 0: error code).
+// ---- one launcher per kernel family: each seals its copies and owns the choice of the instantiation ----
 void launch_one(int direction, const ConvArgs& a_in, int64_t blocks, hipStream_t stream) {
   ConvArgs a = a_in;
-  seal(a, direction);
+  seal(a);
   const dim3 grid((unsigned)blocks), block(CT);
   if (direction <= 1) {
     if (a.scalar) hipLaunchKernelGGL((k_conv_nt<true, Small>), grid, block, 0, stream, a);
@@ -991,8 +983,8 @@ void launch_one(int direction, const ConvArgs& a_in, int64_t blocks, hipStream_t
 
 void launch_dw(const ConvArgs& d_in, const ConvArgs& w_in, int64_t bd, int64_t bw, hipStream_t stream) {
   ConvArgs d = d_in, w = w_in;
-  seal(d, 1);
-  seal(w, 2);
+  seal(d);
+  seal(w);
   const dim3 grid((unsigned)(bd + bw)), block(CT);
   const bool big = d.big || w.big, cls = d.ncls > 0;
   if (big && cls) hipLaunchKernelGGL((k_conv_dw<true, true>), grid, block, 0, stream, d, w, (int)bd);
@@ -1001,21 +993,54 @@ void launch_dw(const ConvArgs& d_in, const ConvArgs& w_in, int64_t bd, int64_t b
   else hipLaunchKernelGGL((k_conv_dw<false, false>), grid, block, 0, stream, d, w, (int)bd);
 }
 
-// Which tile configuration a problem runs in: a pure function of its geometry (hf_conv2d_nhwc_plan and
-// every launch path must agree).  Big (128x128) needs both output dimensions to fill most of a tile
-// and enough GEMM rows that the 64x64 kernel would be issue-bound.
-inline int hf_env_dclass() { return 1; }  // (strided data gradients are enumerated by residue class: 1 268 -> 1 292, round 3)
+// (64x64 tiles, no residue classes: the planner has refused everything else)
+void launch_unpack(const ConvArgs& a_in, int64_t blocks, const hf_shared::UnpackArgs& u, const float* usrc,
+                   int ublocks, hipStream_t stream) {
+  ConvArgs a = a_in;
+  seal(a);
+  const dim3 grid((unsigned)(blocks + ublocks)), block(CT);
+  if (a.scalar) hipLaunchKernelGGL((k_conv_nt_unpack<true, Small>), grid, block, 0, stream, a, u, usrc, (int)blocks);
+  else hipLaunchKernelGGL((k_conv_nt_unpack<false, Small>), grid, block, 0, stream, a, u, usrc, (int)blocks);
+}
 
-inline int hf_env_big() { return -1; }  // (-1: by geometry; 0 / 1 force a configuration when bisecting)
+// Problem i of a grouped launch takes the next `blocks` workgroups (`m` zeroed before the first; the unused slots
+// stay empty ranges at the end).
+int group_add(GroupMeta& m, int i, bool tn, int64_t blocks) {
+  const int64_t end = m.start[i] + blocks;
+  if (end > 0x7fffffffLL) return HF_ERR_ARG;
+  m.tn[i] = tn;
+  for (int j = i + 1; j <= GROUP_MAX; ++j) m.start[j] = (int)end;
+  m.n = i + 1;
+  return HF_OK;
+}
 
+// `a`: GROUP_MAX problems, those from m.n on zeroed.  bnsum: the instantiations whose epilogue writes the BatchNorm
+// partial sums (tangent convolutions on 64x64 tiles only: the planner has refused everything else).
+void launch_group(ConvArgs (&a)[GROUP_MAX], const GroupMeta& m, bool bnsum, hipStream_t st) {
+  bool big = false, cls = false;
+  for (int i = 0; i < m.n; ++i) {
+    big = big || a[i].big;
+    cls = cls || a[i].ncls > 0;
+    seal(a[i]);
+  }
+  const dim3 grid((unsigned)m.start[GROUP_MAX]), block(CT);
+  if (bnsum && m.n == 1 && a[0].bn_part_1)
+    hipLaunchKernelGGL((k_conv_nt<false, Small, false, true>), grid, block, 0, st, a[0]);
+  else if (bnsum) hipLaunchKernelGGL((k_conv_group<false, false, true>), grid, block, 0, st, a[0], a[1], a[2], a[3], m);
+  else if (big && cls) hipLaunchKernelGGL((k_conv_group<true, true>), grid, block, 0, st, a[0], a[1], a[2], a[3], m);
+  else if (big) hipLaunchKernelGGL((k_conv_group<true, false>), grid, block, 0, st, a[0], a[1], a[2], a[3], m);
+  else if (cls) hipLaunchKernelGGL((k_conv_group<false, true>), grid, block, 0, st, a[0], a[1], a[2], a[3], m);
+  else hipLaunchKernelGGL((k_conv_group<false, false>), grid, block, 0, st, a[0], a[1], a[2], a[3], m);
+}
+
+// Which tile configuration a problem runs in: a pure function of its geometry.  Big (128x128) needs both output
+// dimensions to fill most of a tile and enough GEMM rows that the 64x64 kernel would be issue-bound.
 int want_big(int direction, int64_t rows, int64_t dim_m, int64_t dim_n, int64_t red, int64_t mult, bool scalar,
              bool all_taps = false, bool slab_mode = false) {
   // dim_m x dim_n: the output matrix (NT: rows x nout; TN: kout x cs per tap, `mult` = live taps of them);
   // red: length of the reduction; rows: GEMM rows of the layer.
   // Returns 0 (Small), 1 (Big: 128x128) or 2 (Big96: 128x96), whichever wastes less of its tiles.
   if (scalar) return 0;
-  const int force = hf_env_big();
-  if (force == 0) return 0;
   auto fill = [](int64_t d, int64_t t) { return (double)d / (double)(((d + t - 1) / t) * t); };
   const double f128 = fill(dim_m, 128) * fill(dim_n, 128), f96 = fill(dim_m, 128) * fill(dim_n, 96);
   int kind = f96 > f128 + 1e-9 ? 2 : 1;
@@ -1027,7 +1052,6 @@ int want_big(int direction, int64_t rows, int64_t dim_m, int64_t dim_n, int64_t 
     if (fflat > fbest + 0.05) { kind = 3; fbest = fflat; flat_tiles = (dim_m / 96) * ((mult * dim_n + 127) / 128); }
   }
   const bool fits = fbest >= 0.7;
-  if (force > 0) return fits ? kind : 0;
   // ... and only where the launch has enough work to give ~3 workgroups per CU a K loop of >= 8 steps of 16 each
   // (a looser rule -- any reduction of >= 64 steps, splits capped at 8 steps per workgroup -- was measured to put
   // ResNet-50 layers on the 128-wide tiles and lose: 289 -> 268 matvecs/s): with a handful of steps per workgroup the 128-wide
@@ -1056,18 +1080,29 @@ static int apply_out_c(ConvArgs& a, int64_t out_c) {
   return HF_OK;
 }
 
-int64_t setup(ConvArgs& a, int direction, void* out, const void* act, const void* mat, int64_t n, int64_t h,
-              int64_t w, int64_t c, int64_t k, int64_t r, int64_t s, int64_t stride_h, int64_t stride_w,
-              int64_t pad_h, int64_t pad_w, int64_t act_ld, float* ws, int64_t ws_bytes, int* tickets,
-              int64_t n_tickets, int target_blocks, int slab_splits = -1, int64_t slab_stride = 0,
-              int64_t mat_ld = 0) {
+// What the stand-alone calls with the in-launch (ticket) reduction bring along; the slab-mode calls have none.
+struct Scratch {
+  float* ws;
+  int64_t ws_bytes;
+  int* tickets;
+  int64_t n_tickets;
+  int target_blocks;  // (<= 0: the split count comes from the cost model)
+};
+
+// Fill `a` for problem `p`; returns the number of workgroups (<= 0: error code).  `tickets`: ticket mode on the
+// scratch `sc`; else slab mode with p.splits splits (0: the plan -- choose them, towards sc->target_blocks workgroups
+// if `sc` names a count > 0).
+int64_t setup(ConvArgs& a, const hf_conv_problem& p, const Scratch* sc, bool tickets) {
+  const int direction = p.direction, slab_splits = tickets ? -1 : p.splits, target_blocks = sc ? sc->target_blocks : 0;
+  const int64_t n = p.n, h = p.h, w = p.w, c = p.c, k = p.k, r = p.r, s = p.s, stride_h = p.stride_h,
+                stride_w = p.stride_w, pad_h = p.pad_h, pad_w = p.pad_w;
   const int64_t oh = (h + 2 * pad_h - r) / stride_h + 1, ow = (w + 2 * pad_w - s) / stride_w + 1;
   memset(&a, 0, sizeof(a));
-  a.src = (const float*)act;
-  a.mat = (const float*)mat;
-  a.out = (float*)out;
-  a.ws = ws;
-  a.tickets = tickets;
+  a.src = (const float*)p.act;
+  a.mat = (const float*)p.mat;
+  a.out = (float*)p.out;
+  a.ws = sc ? sc->ws : nullptr;
+  a.tickets = sc ? sc->tickets : nullptr;
   a.R = (int)r; a.S = (int)s;
   a.stride_h = (int)stride_h; a.stride_w = (int)stride_w; a.pad_h = (int)pad_h; a.pad_w = (int)pad_w;
   a.shift_h = a.shift_w = -1;
@@ -1101,16 +1136,17 @@ int64_t setup(ConvArgs& a, int direction, void* out, const void* act, const void
   }
   a.out_c = a.cs;
   a.rows = (int)rows;
-  a.cs_ld = (int)(act_ld > 0 ? act_ld : a.cs);
-  a.mat_ld = (int)(mat_ld > 0 ? mat_ld : a.cs);
+  a.cs_ld = (int)(p.act_ld > 0 ? p.act_ld : a.cs);
+  a.mat_ld = (int)(p.mat_ld > 0 ? p.mat_ld : a.cs);
   a.scalar = ((c % 4) || (k % 4) || (a.cs_ld % 4) || (a.mat_ld % 4)) ? 1 : 0;
-  if (a.cs_ld < a.cs || a.mat_ld < a.cs || (mat_ld > 0 && direction == 2)) return HF_ERR_ARG;
-  // strided data gradient in slab mode: residue classes of the input pixel (see ConvArgs)
+  if (a.cs_ld < a.cs || a.mat_ld < a.cs || (p.mat_ld > 0 && direction == 2)) return HF_ERR_ARG;
+  // strided data gradient in slab mode: residue classes of the input pixel (see ConvArgs; 1 268 -> 1 292 matvecs/s,
+  // round 3)
   int cls_taps_max = a.ntaps;
   // (large maps only: on ResNet-18's <= 1568-row layers the launch is latency-bound either way and the extra
   // partially-filled row tiles cost ~1 % of the bench)
   const bool classes = direction == 1 && slab_splits >= 0 && (stride_h > 1 || stride_w > 1) &&
-                       stride_h * stride_w <= 4 && !a.scalar && n * h * w >= 2048 && hf_env_dclass();
+                       stride_h * stride_w <= 4 && !a.scalar && n * h * w >= 2048;
   struct { int py, px, hc, wc, ntaps; unsigned char r[MAX_TAPS], q[MAX_TAPS]; } cl[4];
   int ncls = 0;
   if (classes) {
@@ -1165,7 +1201,7 @@ int64_t setup(ConvArgs& a, int direction, void* out, const void* act, const void
   const int64_t tiles = (int64_t)a.tiles_m * a.tiles_n;
   if (slab_splits >= 0) {  // consumer-side reduction: no workspace, no tickets
     a.slabs = 1;
-    a.slab_stride = slab_stride;
+    a.slab_stride = p.slab_stride;
     int sp = slab_splits > 0 ? slab_splits : choose_splits(tiles, red_steps, target_blocks, 0, true, BK);
     // strided data gradients by residue class: the classes' K loops differ by up to 4x (1 ... 4 taps of a 3x3 / stride 2
     // kernel) and a uniform split leaves the short ones with 2 steps per workgroup -- with one workgroup per CU already
@@ -1178,51 +1214,100 @@ int64_t setup(ConvArgs& a, int direction, void* out, const void* act, const void
   }
   // more output tiles than ticket counters (large batches / maps): such a launch fills the chip
   // without a K split, and an unsplit launch draws no tickets
-  a.splits = tiles > n_tickets ? 1 : choose_splits(tiles, red_steps, target_blocks, ws_bytes, false, BK,
-                                                    (int64_t)BM * BN);
+  a.splits = tiles > sc->n_tickets ? 1 : choose_splits(tiles, red_steps, target_blocks, sc->ws_bytes, false, BK,
+                                                        (int64_t)BM * BN);
   return tiles * a.splits;
 }
 
-int check_common(const void* out, const void* act, const void* mat, const void* workspace, const void* tickets,
-                 int dtype, int64_t n, int64_t h, int64_t w, int64_t c, int64_t k, int64_t r, int64_t s,
-                 int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w) {
-  if (!out || !act || !mat || !workspace || !tickets) return HF_ERR_ARG;
+// what a LAUNCH needs on top of the field ranges: pointers, their alignment, 32-bit index space
+int check_common(const hf_conv_problem& p, int64_t oh, int64_t ow, int dtype, const Scratch* sc) {
+  if (!p.out || !p.act || !p.mat || (sc && (!sc->ws || !sc->tickets))) return HF_ERR_ARG;
   if (dtype != HF_F32) return HF_ERR_ARG;
-  if (n <= 0 || h <= 0 || w <= 0 || c <= 0 || k <= 0 || r <= 0 || s <= 0 || stride_h <= 0 ||
-      stride_w <= 0 || pad_h < 0 || pad_w < 0 || r * s > MAX_TAPS)
-    return HF_ERR_ARG;
-  const int64_t oh = (h + 2 * pad_h - r) / stride_h + 1, ow = (w + 2 * pad_w - s) / stride_w + 1;
-  if (oh <= 0 || ow <= 0) return HF_ERR_ARG;
   // (channel counts that are not multiples of 4 run the element-wise gather variant)
-  if (!aligned16(workspace) || (((c % 4) == 0 && (k % 4) == 0) &&
-                                (!aligned16(out) || !aligned16(act) || !aligned16(mat))))
+  if ((sc && !aligned16(sc->ws)) || (((p.c % 4) == 0 && (p.k % 4) == 0) &&
+                                     (!aligned16(p.out) || !aligned16(p.act) || !aligned16(p.mat))))
     return HF_ERR_ALIGN;
-  if (n * h * w * (c > k ? c : k) > 0x7fffffffLL || n * oh * ow * (c > k ? c : k) > 0x7fffffffLL ||
-      k * r * s * c > 0x7fffffffLL)
+  const int64_t ck = p.c > p.k ? p.c : p.k;
+  if (p.n * p.h * p.w * ck > 0x7fffffffLL || p.n * oh * ow * ck > 0x7fffffffLL || p.k * p.r * p.s * p.c > 0x7fffffffLL)
     return HF_ERR_ARG;
+  return HF_OK;
+}
+
+// THE planner: the one place that turns a problem description into kernel arguments, for hf_conv2d_nhwc_plan and
+// for every launching entry point alike -- what the plan answers and what a launch runs cannot drift apart.  In
+// this order (it fixes which code a call with several faults returns):
+//   1. field ranges, the out_c rule included;  2. check_common (launches only);  3. setup;
+//   4. the planned split count is the caller's (slab-mode launches: ask hf_conv2d_nhwc_plan first);
+//   5. what the caller's launch form cannot run (`allow`);  6. apply_out_c.
+// `sc`: ticket mode.  PLAN_ONLY: no launch follows -- no pointers, no 2^31 limits, p.splits == 0, and `sc` (nullable)
+// only carries target_blocks.
+enum : unsigned {
+  ALLOW_SCALAR = 1,  // the form has the element-wise gather variant (channel counts not multiples of 4)
+  ALLOW_BIG = 2,     // ... the 128-wide tile configurations
+  ALLOW_CLS = 4,     // ... the residue-class enumeration of strided data gradients
+  ALLOW_ALL = 7,
+  PLAN_ONLY = 8,
+};
+
+int plan_problem(const hf_conv_problem& p, int dtype, const Scratch* sc, unsigned allow, ConvArgs& a, int64_t& blocks) {
+  const bool plan = allow & PLAN_ONLY, tickets = sc && !plan, slab_launch = !sc && !plan;
+  if (p.direction < 0 || p.direction > 2 || (slab_launch && p.splits < 1) || p.slab_stride < 0 || p.mat_ld < 0)
+    return HF_ERR_ARG;
+  if (p.out_c < 0 || p.out_c > p.c || (p.out_c && p.direction != 2)) return HF_ERR_ARG;
+  if (p.n <= 0 || p.h <= 0 || p.w <= 0 || p.c <= 0 || p.k <= 0 || p.r <= 0 || p.s <= 0 || p.stride_h <= 0 ||
+      p.stride_w <= 0 || p.pad_h < 0 || p.pad_w < 0 || p.r * p.s > MAX_TAPS)
+    return HF_ERR_ARG;
+  const int64_t oh = (p.h + 2 * p.pad_h - p.r) / p.stride_h + 1, ow = (p.w + 2 * p.pad_w - p.s) / p.stride_w + 1;
+  if (oh <= 0 || ow <= 0) return HF_ERR_ARG;
+  if (!plan) {
+    const int rc = check_common(p, oh, ow, dtype, sc);
+    if (rc) return rc;
+  }
+  blocks = setup(a, p, sc, tickets);
+  if (blocks <= 0) return (int)blocks;
+  if (slab_launch && a.splits != p.splits) return HF_ERR_ARG;
+  if ((a.scalar && !(allow & ALLOW_SCALAR)) || (a.big && !(allow & ALLOW_BIG)) || (a.ncls > 0 && !(allow & ALLOW_CLS)))
+    return HF_ERR_ARG;
+  return apply_out_c(a, p.out_c);
+}
+
+// One problem, every variant.
+int launch_single(const hf_conv_problem& p, int dtype, const Scratch* sc, void* stream) {
+  ConvArgs a;
+  int64_t blocks;
+  const int rc = plan_problem(p, dtype, sc, ALLOW_ALL, a, blocks);
+  if (rc) return rc;
+  launch_one(p.direction, a, blocks, (hipStream_t)stream);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+// One forward / data-gradient problem and one weight-gradient problem in one launch (16-byte gathers only).
+int launch_pair(const hf_conv_problem& d, const hf_conv_problem& w, int dtype, const Scratch* sd, const Scratch* sw,
+                void* stream) {
+  ConvArgs a[2];
+  int64_t blocks[2];
+  int rc = plan_problem(d, dtype, sd, ALLOW_BIG | ALLOW_CLS, a[0], blocks[0]);
+  if (!rc) rc = plan_problem(w, dtype, sw, ALLOW_BIG | ALLOW_CLS, a[1], blocks[1]);
+  if (rc) return rc;
+  launch_dw(a[0], a[1], blocks[0], blocks[1], (hipStream_t)stream);
+  HF_HIP(hipGetLastError());
   return HF_OK;
 }
 
 }  // namespace
 
-// C linkage comes from hf_pcg.h
+// C linkage comes from hf_pcg.h.  The positional entry points describe their problem as an hf_conv_problem
+// {direction, out, act, mat, n .. pad_w, act_ld, out_c, splits, slab_stride, mat_ld} and go the way of the struct ones.
 int hf_conv2d_nhwc(int direction, void* out, const void* act, const void* mat, int64_t n,
                    int64_t h, int64_t w, int64_t c, int64_t k, int64_t r, int64_t s,
                    int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
                    int64_t act_ld, void* workspace, int64_t workspace_bytes, void* tickets,
                    int64_t n_tickets, int target_blocks, int dtype, void* stream) {
-  if (direction < 0 || direction > 2) return HF_ERR_ARG;
-  const int rc = check_common(out, act, mat, workspace, tickets, dtype, n, h, w, c, k, r, s, stride_h,
-                              stride_w, pad_h, pad_w);
-  if (rc) return rc;
-  ConvArgs a;
-  const int64_t blocks = setup(a, direction, out, act, mat, n, h, w, c, k, r, s, stride_h, stride_w, pad_h,
-                               pad_w, act_ld, (float*)workspace, workspace_bytes, (int*)tickets, n_tickets,
-                               target_blocks);
-  if (blocks <= 0) return (int)blocks;
-  launch_one(direction, a, blocks, (hipStream_t)stream);
-  HF_HIP(hipGetLastError());
-  return HF_OK;
+  const hf_conv_problem p = {direction, out, act, mat, n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w,
+                             act_ld, 0, 0, 0, 0};
+  const Scratch sc = {(float*)workspace, workspace_bytes, (int*)tickets, n_tickets, target_blocks};
+  return launch_single(p, dtype, &sc, stream);
 }
 
 int hf_conv2d_nhwc_backward(void* dx, void* dw, const void* dy, const void* x, const void* w_t, int64_t n,
@@ -1230,25 +1315,15 @@ int hf_conv2d_nhwc_backward(void* dx, void* dw, const void* dy, const void* x, c
                             int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
                             void* workspace, int64_t workspace_bytes, void* tickets, int64_t n_tickets,
                             int target_blocks, int dtype, void* stream) {
-  if (!dx || !dw) return HF_ERR_ARG;
-  int rc = check_common(dx, dy, w_t, workspace, tickets, dtype, n, h, w, c, k, r, s, stride_h, stride_w,
-                        pad_h, pad_w);
-  if (rc) return rc;
-  if (!x || !aligned16(x) || !aligned16(dw)) return x ? HF_ERR_ALIGN : HF_ERR_ARG;
+  if (!dx || !dw) return HF_ERR_ARG;  // (ahead of any alignment verdict on the other operands, as ever)
+  const hf_conv_problem d = {1, dx, dy, w_t, n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w, 0, 0, 0, 0, 0};
+  const hf_conv_problem g = {2, dw, x, dy, n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w, 0, 0, 0, 0, 0};
   // the two halves get disjoint halves of the scratch (they run concurrently)
   const int64_t half_ws = (workspace_bytes / 2) & ~(int64_t)15, half_t = n_tickets / 2;
-  ConvArgs d, g;
-  const int64_t bd = setup(d, 1, dx, dy, w_t, n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w, 0,
-                           (float*)workspace, half_ws, (int*)tickets, half_t, target_blocks);
-  if (bd <= 0) return (int)bd;
-  const int64_t bw = setup(g, 2, dw, x, dy, n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w, 0,
-                           (float*)((char*)workspace + half_ws), half_ws, (int*)tickets + half_t, half_t,
-                           target_blocks);
-  if (bw <= 0) return (int)bw;
-  if (d.scalar || g.scalar) return HF_ERR_ARG;  // the merged launch has the 16-byte gather variant only
-  launch_dw(d, g, bd, bw, (hipStream_t)stream);
-  HF_HIP(hipGetLastError());
-  return HF_OK;
+  const Scratch sd = {(float*)workspace, half_ws, (int*)tickets, half_t, target_blocks};
+  const Scratch sw = {workspace ? (float*)((char*)workspace + half_ws) : nullptr, half_ws,
+                      tickets ? (int*)tickets + half_t : nullptr, half_t, target_blocks};
+  return launch_pair(d, g, dtype, &sd, &sw, stream);
 }
 
 // ---- consumer-side reduction ("slab") variants ---------------------------------------
@@ -1259,37 +1334,22 @@ int hf_conv2d_nhwc_backward(void* dx, void* dw, const void* dy, const void* x, c
 int hf_conv2d_nhwc_plan(int direction, int64_t n, int64_t h, int64_t w, int64_t c, int64_t k, int64_t r,
                         int64_t s, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
                         int target_blocks) {
-  if (direction < 0 || direction > 2) return HF_ERR_ARG;
-  if (n <= 0 || h <= 0 || w <= 0 || c <= 0 || k <= 0 || r <= 0 || s <= 0 || stride_h <= 0 || stride_w <= 0 ||
-      pad_h < 0 || pad_w < 0 || r * s > MAX_TAPS)
-    return HF_ERR_ARG;
+  const hf_conv_problem p = {direction, nullptr, nullptr, nullptr, n, h, w, c, k, r, s, stride_h, stride_w, pad_h,
+                             pad_w, 0, 0, 0, 0, 0};
+  const Scratch sc = {nullptr, 0, nullptr, 0, target_blocks};
   ConvArgs a;
-  float dummy = 0.f;
-  const int64_t blocks = setup(a, direction, &dummy, &dummy, &dummy, n, h, w, c, k, r, s, stride_h, stride_w,
-                               pad_h, pad_w, 0, nullptr, 0, nullptr, 0, target_blocks, 0, 0);
-  if (blocks <= 0) return (int)blocks;
-  return a.splits;
+  int64_t blocks;
+  const int rc = plan_problem(p, HF_F32, &sc, ALLOW_ALL | PLAN_ONLY, a, blocks);
+  return rc ? rc : a.splits;
 }
 
 int hf_conv2d_nhwc_slabs(int direction, void* out, const void* act, const void* mat, int64_t n, int64_t h,
                          int64_t w, int64_t c, int64_t k, int64_t r, int64_t s, int64_t stride_h,
                          int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t act_ld, int64_t mat_ld,
                          int64_t out_c, int splits, int64_t slab_stride, int dtype, void* stream) {
-  if (direction < 0 || direction > 2 || splits < 1 || slab_stride < 0 || mat_ld < 0) return HF_ERR_ARG;
-  if (out_c < 0 || out_c > c || (out_c && direction != 2)) return HF_ERR_ARG;
-  alignas(16) float dummy_ws[4];
-  const int rc = check_common(out, act, mat, dummy_ws, dummy_ws, dtype, n, h, w, c, k, r, s, stride_h, stride_w,
-                              pad_h, pad_w);
-  if (rc) return rc;
-  ConvArgs a;
-  const int64_t blocks = setup(a, direction, out, act, mat, n, h, w, c, k, r, s, stride_h, stride_w, pad_h,
-                               pad_w, act_ld, nullptr, 0, nullptr, 0, 0, splits, slab_stride, mat_ld);
-  if (blocks <= 0) return (int)blocks;
-  if (a.splits != splits) return HF_ERR_ARG;  // ask hf_conv2d_nhwc_plan first
-  if (apply_out_c(a, out_c)) return HF_ERR_ARG;
-  launch_one(direction, a, blocks, (hipStream_t)stream);
-  HF_HIP(hipGetLastError());
-  return HF_OK;
+  const hf_conv_problem p = {direction, out, act, mat, n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w,
+                             act_ld, out_c, splits, slab_stride, mat_ld};
+  return launch_single(p, dtype, nullptr, stream);
 }
 
 int hf_conv2d_nhwc_slabs_unpack(void* out, const void* act, const void* mat, int64_t n, int64_t h, int64_t w,
@@ -1299,34 +1359,23 @@ int hf_conv2d_nhwc_slabs_unpack(void* out, const void* act, const void* mat, int
                                 const int64_t* unumels, const int64_t* uslabs, const int64_t* uinners,
                                 const int64_t* ulive, const int64_t* uhalves, int n_tensors, int dtype,
                                 void* stream) {
-  if (splits < 1 || slab_stride < 0 || mat_ld < 0 || dtype != HF_F32) return HF_ERR_ARG;
   if (!usrc || !udsts || !usrc_offs || !unumels || !uslabs || !uinners || n_tensors < 1) return HF_ERR_ARG;
   if (uhalves)  // (transposed copies run as LDS-tiled workgroups of hf_unpack_weights' own kernel only)
     for (int t_ = 0; t_ < n_tensors; ++t_)
       if (uhalves[t_] == 2) return HF_ERR_ARG;
-  alignas(16) float dummy_ws[4];
-  const int rc = check_common(out, act, mat, dummy_ws, dummy_ws, dtype, n, h, w, c, k, r, s, stride_h, stride_w,
-                              pad_h, pad_w);
-  if (rc) return rc;
+  const hf_conv_problem p = {0, out, act, mat, n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w,
+                             act_ld, 0, splits, slab_stride, mat_ld};
   ConvArgs a;
-  const int64_t blocks = setup(a, 0, out, act, mat, n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w, act_ld,
-                               nullptr, 0, nullptr, 0, 0, splits, slab_stride, mat_ld);
-  if (blocks <= 0) return (int)blocks;
-  if (a.splits != splits || a.big || a.ncls > 0) return HF_ERR_ARG;  // (small-map launches only: ask the plan first)
+  int64_t blocks;
+  const int rc = plan_problem(p, dtype, nullptr, ALLOW_SCALAR, a, blocks);  // (small-map launches only)
+  if (rc) return rc;
   hf_shared::UnpackArgs u;
   int ublocks = 0;
   const int next = hf_shared::fill_unpack_args<float>(u, &ublocks, 0, udsts, usrc_offs, unumels, uslabs, uinners,
                                                       ulive, uhalves, n_tensors, /*allow_transposed=*/false);
   if (next < 0) return next;
   if (next != n_tensors || ublocks < 1) return HF_ERR_ARG;  // more tensors than one argument block holds
-  seal(a, 0);
-  const dim3 grid((unsigned)(blocks + ublocks)), block(CT);
-  if (a.scalar)
-    hipLaunchKernelGGL((k_conv_nt_unpack<true, Small>), grid, block, 0, (hipStream_t)stream, a, u, (const float*)usrc,
-                       (int)blocks);
-  else
-    hipLaunchKernelGGL((k_conv_nt_unpack<false, Small>), grid, block, 0, (hipStream_t)stream, a, u,
-                       (const float*)usrc, (int)blocks);
+  launch_unpack(a, blocks, u, (const float*)usrc, ublocks, (hipStream_t)stream);
   HF_HIP(hipGetLastError());
   return HF_OK;
 }
@@ -1336,51 +1385,17 @@ int hf_conv2d_nhwc_backward_slabs(void* dx, void* dw, const void* dy, const void
                                   int64_t s, int64_t stride_h, int64_t stride_w, int64_t pad_h,
                                   int64_t pad_w, int splits_d, int64_t slab_stride_d, int splits_w,
                                   int64_t slab_stride_w, int dtype, void* stream) {
-  if (!dx || !dw || !x || splits_d < 1 || splits_w < 1) return HF_ERR_ARG;
-  alignas(16) float dummy_ws[4];
-  int rc = check_common(dx, dy, w_t, dummy_ws, dummy_ws, dtype, n, h, w, c, k, r, s, stride_h, stride_w, pad_h,
-                        pad_w);
-  if (rc) return rc;
-  if (!aligned16(x) || !aligned16(dw)) return HF_ERR_ALIGN;
-  ConvArgs d, g;
-  const int64_t bd = setup(d, 1, dx, dy, w_t, n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w, 0, nullptr,
-                           0, nullptr, 0, 0, splits_d, slab_stride_d);
-  if (bd <= 0) return (int)bd;
-  const int64_t bw = setup(g, 2, dw, x, dy, n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w, 0, nullptr, 0,
-                           nullptr, 0, 0, splits_w, slab_stride_w);
-  if (bw <= 0) return (int)bw;
-  if (d.splits != splits_d || g.splits != splits_w) return HF_ERR_ARG;
-  if (d.scalar || g.scalar) return HF_ERR_ARG;  // the merged launch has the 16-byte gather variant only
-  launch_dw(d, g, bd, bw, (hipStream_t)stream);
-  HF_HIP(hipGetLastError());
-  return HF_OK;
+  if (!dx || !dw || !x || splits_d < 1 || splits_w < 1) return HF_ERR_ARG;  // (ahead of any alignment verdict, as ever)
+  const hf_conv_problem d = {1, dx, dy, w_t, n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w,
+                             0, 0, splits_d, slab_stride_d, 0};
+  const hf_conv_problem g = {2, dw, x, dy, n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w,
+                             0, 0, splits_w, slab_stride_w, 0};
+  return launch_pair(d, g, dtype, nullptr, nullptr, stream);
 }
 
 int hf_conv2d_nhwc_dw_slabs(const hf_conv_problem* d, const hf_conv_problem* w, int dtype, void* stream) {
-  if (!d || !w || d->direction > 1 || d->direction < 0 || w->direction != 2) return HF_ERR_ARG;
-  ConvArgs a[2];
-  int64_t blocks[2];
-  alignas(16) float dummy_ws[4];
-  const hf_conv_problem* pr[2] = {d, w};
-  for (int i = 0; i < 2; ++i) {
-    const hf_conv_problem& q = *pr[i];
-    if (q.splits < 1 || q.slab_stride < 0 || q.mat_ld < 0 || q.out_c < 0 || q.out_c > q.c || (q.out_c && i == 0))
-      return HF_ERR_ARG;
-    const int rc = check_common(q.out, q.act, q.mat, dummy_ws, dummy_ws, dtype, q.n, q.h, q.w, q.c, q.k, q.r, q.s,
-                                q.stride_h, q.stride_w, q.pad_h, q.pad_w);
-    if (rc) return rc;
-    blocks[i] = setup(a[i], q.direction, q.out, q.act, q.mat, q.n, q.h, q.w, q.c, q.k, q.r, q.s, q.stride_h,
-                      q.stride_w, q.pad_h, q.pad_w, q.act_ld, nullptr, 0, nullptr, 0, 0, q.splits, q.slab_stride,
-                      q.mat_ld);
-    if (blocks[i] <= 0) return (int)blocks[i];
-    if (a[i].splits != q.splits || a[i].scalar) return HF_ERR_ARG;
-    if (apply_out_c(a[i], q.out_c)) return HF_ERR_ARG;
-  }
-  const dim3 grid((unsigned)(blocks[0] + blocks[1]));
-  (void)grid;
-  launch_dw(a[0], a[1], blocks[0], blocks[1], (hipStream_t)stream);
-  HF_HIP(hipGetLastError());
-  return HF_OK;
+  if (!d || !w || d->direction > 1 || w->direction != 2) return HF_ERR_ARG;
+  return launch_pair(*d, *w, dtype, nullptr, nullptr, stream);
 }
 
 // Tangent convolutions (direction 0, slab mode, 64x64 tiles) whose epilogue also writes the per-channel partial sums
@@ -1390,95 +1405,42 @@ int hf_conv2d_nhwc_dw_slabs(const hf_conv_problem* d, const hf_conv_problem* w, 
 int hf_conv2d_nhwc_group_slabs_bnsum(const hf_conv_problem* problems, int n_problems, const hf_conv_bnsum* sums,
                                      int dtype, void* stream) {
   if (!problems || !sums || n_problems < 1 || n_problems > GROUP_MAX) return HF_ERR_ARG;
-  GroupArgs q;
-  memset(&q, 0, sizeof(q));
-  int64_t total = 0;
-  alignas(16) float dummy_ws[4];
+  ConvArgs a[GROUP_MAX];
+  GroupMeta m;
+  memset(a, 0, sizeof(a));
+  memset(&m, 0, sizeof(m));
   for (int i = 0; i < n_problems; ++i) {
-    const hf_conv_problem& pr = problems[i];
-    if (pr.direction != 0 || pr.splits < 1 || pr.slab_stride < 0 || pr.mat_ld < 0 || pr.out_c) return HF_ERR_ARG;
-    const int rc = check_common(pr.out, pr.act, pr.mat, dummy_ws, dummy_ws, dtype, pr.n, pr.h, pr.w, pr.c, pr.k,
-                                pr.r, pr.s, pr.stride_h, pr.stride_w, pr.pad_h, pr.pad_w);
+    if (problems[i].direction != 0) return HF_ERR_ARG;
+    int64_t blocks;
+    const int rc = plan_problem(problems[i], dtype, nullptr, 0, a[i], blocks);
     if (rc) return rc;
-    ConvArgs& a = q.a[i];
-    const int64_t blocks = setup(a, 0, pr.out, pr.act, pr.mat, pr.n, pr.h, pr.w, pr.c, pr.k, pr.r, pr.s,
-                                 pr.stride_h, pr.stride_w, pr.pad_h, pr.pad_w, pr.act_ld, nullptr, 0, nullptr, 0, 0,
-                                 pr.splits, pr.slab_stride, pr.mat_ld);
-    if (blocks <= 0) return (int)blocks;
-    if (a.splits != pr.splits || a.scalar || a.big || a.ncls > 0 || !a.slabs) return HF_ERR_ARG;
     const hf_conv_bnsum& b = sums[i];
     if (b.part_1) {
       if (!b.part_x || !b.x || !b.mean || !b.rstd) return HF_ERR_ARG;
-      if (b.part_rows != (int64_t)a.tiles_m * a.splits) return HF_ERR_ARG;  // (= ceil(rows / 64) * splits)
-      a.bn_x = (const float*)b.x; a.bn_mean = (const float*)b.mean; a.bn_rstd = (const float*)b.rstd;
-      a.bn_part_x = (float*)b.part_x; a.bn_part_1 = (float*)b.part_1;
+      if (b.part_rows != (int64_t)a[i].tiles_m * a[i].splits) return HF_ERR_ARG;  // (= ceil(rows / 64) * splits)
+      a[i].bn_x = (const float*)b.x; a[i].bn_mean = (const float*)b.mean; a[i].bn_rstd = (const float*)b.rstd;
+      a[i].bn_part_x = (float*)b.part_x; a[i].bn_part_1 = (float*)b.part_1;
     }
-    q.start[i] = (int)total;
-    total += blocks;
-    if (total > 0x7fffffffLL) return HF_ERR_ARG;
+    if (group_add(m, i, false, blocks)) return HF_ERR_ARG;
   }
-  GroupMeta m;
-  memset(&m, 0, sizeof(m));
-  for (int i = 0; i < GROUP_MAX; ++i) m.start[i] = i < n_problems ? q.start[i] : (int)total;
-  m.start[GROUP_MAX] = (int)total;
-  m.n = n_problems;
-  for (int i = 0; i < n_problems; ++i) seal(q.a[i], 0);
-  const dim3 grid((unsigned)total), block(CT);
-  hipStream_t st = (hipStream_t)stream;
-  if (n_problems == 1 && q.a[0].bn_part_1)
-    hipLaunchKernelGGL((k_conv_nt<false, Small, false, true>), grid, block, 0, st, q.a[0]);
-  else
-    hipLaunchKernelGGL((k_conv_group<false, false, true>), grid, block, 0, st, q.a[0], q.a[1], q.a[2], q.a[3], m);
+  launch_group(a, m, /*bnsum=*/true, (hipStream_t)stream);
   HF_HIP(hipGetLastError());
   return HF_OK;
 }
 
 int hf_conv2d_nhwc_group_slabs(const hf_conv_problem* problems, int n_problems, int dtype, void* stream) {
   if (!problems || n_problems < 1 || n_problems > GROUP_MAX) return HF_ERR_ARG;
-  GroupArgs q;  // (~1.2 KB, passed to the kernel by value)
-  memset(&q, 0, sizeof(q));
-  int64_t total = 0;
-  alignas(16) float dummy_ws[4];
-  for (int i = 0; i < n_problems; ++i) {
-    const hf_conv_problem& pr = problems[i];
-    if (pr.direction < 0 || pr.direction > 2 || pr.splits < 1 || pr.slab_stride < 0 || pr.mat_ld < 0) return HF_ERR_ARG;
-    if (pr.out_c < 0 || pr.out_c > pr.c || (pr.out_c && pr.direction != 2)) return HF_ERR_ARG;
-    const int rc = check_common(pr.out, pr.act, pr.mat, dummy_ws, dummy_ws, dtype, pr.n, pr.h, pr.w, pr.c, pr.k,
-                                pr.r, pr.s, pr.stride_h, pr.stride_w, pr.pad_h, pr.pad_w);
-    if (rc) return rc;
-    const int64_t blocks = setup(q.a[i], pr.direction, pr.out, pr.act, pr.mat, pr.n, pr.h, pr.w, pr.c, pr.k, pr.r,
-                                 pr.s, pr.stride_h, pr.stride_w, pr.pad_h, pr.pad_w, pr.act_ld, nullptr, 0,
-                                 nullptr, 0, 0, pr.splits, pr.slab_stride, pr.mat_ld);
-    if (blocks <= 0) return (int)blocks;
-    if (q.a[i].splits != pr.splits) return HF_ERR_ARG;  // ask hf_conv2d_nhwc_plan first
-    if (q.a[i].scalar) return HF_ERR_ARG;               // the grouped launch has the 16-byte gather variant only
-    if (apply_out_c(q.a[i], pr.out_c)) return HF_ERR_ARG;
-    q.tn[i] = pr.direction == 2;
-    q.start[i] = (int)total;
-    total += blocks;
-    if (total > 0x7fffffffLL) return HF_ERR_ARG;
-  }
-  q.start[n_problems] = (int)total;
-  q.n = n_problems;
-  bool anybig = false;
-  for (int i = 0; i < n_problems; ++i) anybig = anybig || q.a[i].big;
+  ConvArgs a[GROUP_MAX];  // (passed to the kernel by value, one argument each)
   GroupMeta m;
+  memset(a, 0, sizeof(a));
   memset(&m, 0, sizeof(m));
-  for (int i = 0; i < GROUP_MAX; ++i) {
-    m.tn[i] = q.tn[i];
-    m.start[i] = i <= n_problems ? q.start[i] : (int)total;  // (unused slots: empty ranges at the end)
+  for (int i = 0; i < n_problems; ++i) {
+    int64_t blocks;
+    const int rc = plan_problem(problems[i], dtype, nullptr, ALLOW_BIG | ALLOW_CLS, a[i], blocks);
+    if (rc) return rc;
+    if (group_add(m, i, problems[i].direction == 2, blocks)) return HF_ERR_ARG;
   }
-  m.start[GROUP_MAX] = (int)total;
-  m.n = n_problems;
-  bool anycls = false;
-  for (int i = 0; i < n_problems; ++i) anycls = anycls || q.a[i].ncls > 0;
-  for (int i = 0; i < n_problems; ++i) seal(q.a[i], 0);
-  const dim3 grid((unsigned)total), block(CT);
-  hipStream_t st = (hipStream_t)stream;
-  if (anybig && anycls) hipLaunchKernelGGL((k_conv_group<true, true>), grid, block, 0, st, q.a[0], q.a[1], q.a[2], q.a[3], m);
-  else if (anybig) hipLaunchKernelGGL((k_conv_group<true, false>), grid, block, 0, st, q.a[0], q.a[1], q.a[2], q.a[3], m);
-  else if (anycls) hipLaunchKernelGGL((k_conv_group<false, true>), grid, block, 0, st, q.a[0], q.a[1], q.a[2], q.a[3], m);
-  else hipLaunchKernelGGL((k_conv_group<false, false>), grid, block, 0, st, q.a[0], q.a[1], q.a[2], q.a[3], m);
+  launch_group(a, m, /*bnsum=*/false, (hipStream_t)stream);
   HF_HIP(hipGetLastError());
   return HF_OK;
 }

@@ -318,3 +318,178 @@ def test_weight_gradient_of_a_zero_padded_operand_on_the_flat_96_row_tiles():
         (gw,) = torch.autograd.grad(y, w0, gy4.double())
         got4 = out4.sum(0).view(k, 3, 3, out_c).permute(0, 3, 1, 2)
         within(float((got4.double() - gw).abs().max() / gw.abs().max()), 2e-5)
+
+
+_ARG, _ALIGN = -1, -2  # HF_ERR_ARG, HF_ERR_ALIGN of include/hf_pcg.h
+_GEO_FIELDS = ("n", "h", "w", "c", "k", "r", "s", "stride_h", "stride_w", "pad_h", "pad_w")
+_SINGLE = ("nhwc", "slabs", "slabs_unpack")                 # one problem, stand-alone: these have scalar gathers
+_PAIR = ("backward", "backward_slabs", "dw_slabs")          # a data gradient and a weight gradient
+_GROUP = ("group_slabs", "group_slabs_bnsum")
+_STRUCT = ("dw_slabs",) + _GROUP                            # problems handed over as hf_conv_problem
+_SLAB = tuple(f for f in _SINGLE + _PAIR + _GROUP if f not in ("nhwc", "backward"))
+_ALL = _SINGLE + _PAIR + _GROUP
+
+
+class _Call:
+    """One call of a launching entry point on (2, 4, 4, c, 8, 3, 3, stride 1, pad 1), through the C ABI.  Every pointer
+    is the start of its own zeroed 64 KB device buffer -- more than any direction of this geometry reads or writes, the
+    split-K slabs included -- so that a call that is wrongly NOT refused runs a valid kernel.  ``P``: the problems as
+    dicts of the ``hf_conv_problem`` fields (``kinds``: F / D / W per problem); a case edits one of them."""
+
+    def __init__(self, form, kinds=None, c=8):
+        kinds = kinds or {"nhwc": "F", "slabs": "F", "slabs_unpack": "F", "group_slabs_bnsum": "FF"}.get(form, "DW")
+        self.form, self.dtype, self.n_problems, self.part_rows_off = form, _lib.HF_F32, len(kinds), 0
+        self.bufs = []
+        self.P = [self._problem("FDW".index(kind), c) for kind in kinds]
+
+    def buf(self):
+        self.bufs.append(torch.zeros(1 << 14, device=DEV))
+        return self.bufs[-1]
+
+    def _problem(self, d, c):
+        n, h, k = 2, 4, 8
+        q = dict(direction=d, n=n, h=h, w=h, c=c, k=k, r=3, s=3, stride_h=1, stride_w=1, pad_h=1, pad_w=1, act_ld=0,
+                 out_c=0, mat_ld=0, splits=_lib.conv_plan(d, n, h, h, c, k, 3, 3, (1, 1), (1, 1)),
+                 slab_stride=(n * h * h * k, n * h * h * c, k * 9 * c)[d])
+        q["_t"] = tuple(self.buf() for _ in range(3))
+        q["out"], q["act"], q["mat"] = (t.data_ptr() for t in q["_t"])
+        return q
+
+    def run(self):
+        lib, P, dev = _lib.load(), _lib.c_void_p, torch.device(DEV)
+        st, (ws, tk) = _lib.current_stream_ptr(dev), _lib.conv_scratch(dev)
+        scratch = (P(ws.data_ptr()), ws.numel() * 4, P(tk.data_ptr()), tk.numel(), 0)
+        geo = lambda q: [q[f] for f in _GEO_FIELDS]
+        a, b = self.P[0], self.P[-1]
+        if self.form == "nhwc":
+            return lib.hf_conv2d_nhwc(a["direction"], P(a["out"]), P(a["act"]), P(a["mat"]), *geo(a), a["act_ld"],
+                                      *scratch, self.dtype, st)
+        if self.form == "backward":  # (dx, dw, dy, x, w_t)
+            return lib.hf_conv2d_nhwc_backward(P(a["out"]), P(b["out"]), P(a["act"]), P(b["act"]), P(a["mat"]), *geo(a),
+                                               *scratch, self.dtype, st)
+        if self.form == "slabs":
+            return lib.hf_conv2d_nhwc_slabs(a["direction"], P(a["out"]), P(a["act"]), P(a["mat"]), *geo(a), a["act_ld"],
+                                            a["mat_ld"], a["out_c"], a["splits"], a["slab_stride"], self.dtype, st)
+        if self.form == "slabs_unpack":
+            v, dst = self.buf(), _cl(torch.zeros(4, 8, 3, 3, device=DEV))  # scatters v[:144] into a [4, 2 * 4, 3, 3] operand
+            self.bufs.append(dst)
+            return lib.hf_conv2d_nhwc_slabs_unpack(P(a["out"]), P(a["act"]), P(a["mat"]), *geo(a), a["act_ld"],
+                                                   a["mat_ld"], a["splits"], a["slab_stride"], P(v.data_ptr()),
+                                                   *_lib.unpack_table(v, [(0, dst, 4)]), self.dtype, st)
+        if self.form == "backward_slabs":
+            return lib.hf_conv2d_nhwc_backward_slabs(P(a["out"]), P(b["out"]), P(a["act"]), P(b["act"]), P(a["mat"]),
+                                                     *geo(a), a["splits"], a["slab_stride"], b["splits"],
+                                                     b["slab_stride"], self.dtype, st)
+        arr = (_lib.ConvProblem * max(self.n_problems, len(self.P)))()
+        for i, q in enumerate(arr):
+            for f, val in self.P[i % len(self.P)].items():
+                if not f.startswith("_"):
+                    setattr(q, f, val)
+        if self.form == "dw_slabs":
+            return lib.hf_conv2d_nhwc_dw_slabs(_lib.ctypes.byref(arr[0]), _lib.ctypes.byref(arr[1]), self.dtype, st)
+        if self.form == "group_slabs":
+            return lib.hf_conv2d_nhwc_group_slabs(_lib.ctypes.cast(arr, P), self.n_problems, self.dtype, st)
+        bn = (_lib.ConvBnSum * len(arr))()
+        for q, s in zip(arr, bn):  # (32 rows: one row tile)
+            s.x, s.mean, s.rstd, s.part_x, s.part_1 = (self.buf().data_ptr() for _ in range(5))
+            s.part_rows = q.splits + self.part_rows_off
+        return lib.hf_conv2d_nhwc_group_slabs_bnsum(_lib.ctypes.cast(arr, P), self.n_problems, _lib.ctypes.cast(bn, P),
+                                                    self.dtype, st)
+
+
+def _set(i, **fields):
+    return lambda call: call.P[i].update(fields)
+
+
+def _off_by_4_bytes(i, field):
+    return lambda call: call.P[i].update({field: call.P[i][field] + 4})
+
+
+def test_every_launching_entry_point_refuses_what_it_cannot_run():
+    """One fault per call, over all eight launching entry points of ``hf_conv.hip``: the return code is the one written
+    here (read off the library's host code as it was before the entry points were put on one planner: ``HF_ERR_ARG``
+    for a null pointer, float64, a direction, split count, stride, leading dimension or ``out_c`` out of range or wrong
+    for the form, a problem count outside 1..4, a wrong ``part_rows``; ``HF_ERR_ALIGN`` for an operand off the 16-byte
+    grid when the channel counts are multiples of 4).  With c = 6 the same misaligned operand is legal for the
+    stand-alone calls, which run their element-wise gathers and match float64 (2e-5 of the result's max-norm), and
+    ``HF_ERR_ARG`` for the merged and grouped forms, which have no such variant.  Unedited, every call returns 0.
+    (``hf_conv2d_nhwc_backward_slabs`` is not asked about ``slab_stride < 0``: it began to refuse it with this test.)"""
+    for form in _ALL:
+        assert _Call(form).run() == 0, form
+    assert _Call("slabs", "W").run() == 0 and _Call("slabs", "D").run() == 0 and _Call("nhwc", "W").run() == 0
+    not_single = _PAIR + _GROUP
+    with_mat_ld = ("slabs", "slabs_unpack") + _STRUCT
+    with_act_ld = ("nhwc",) + with_mat_ld
+
+    def dtype_f64(call):
+        call.dtype = _lib.HF_F64
+
+    def count(n):
+        return lambda call: setattr(call, "n_problems", n)
+
+    def part_rows(call):
+        call.part_rows_off = 1
+
+    cases = [  # (what is wrong, entry points, problem kinds or None for the form's own, edit, expected code)
+        ("out = NULL", _ALL, None, _set(0, out=None), _ARG),
+        ("act = NULL", _ALL, None, _set(0, act=None), _ARG),
+        ("mat = NULL", _ALL, None, _set(0, mat=None), _ARG),
+        ("x = NULL", not_single, None, _set(1, act=None), _ARG),
+        ("dw = NULL", not_single, None, _set(1, out=None), _ARG),
+        ("float64", _ALL, None, dtype_f64, _ARG),
+        ("direction 3", ("nhwc", "slabs", "group_slabs"), None, _set(0, direction=3), _ARG),
+        ("direction -1", ("nhwc", "slabs", "group_slabs"), None, _set(0, direction=-1), _ARG),
+        ("d.direction 2", ("dw_slabs",), None, _set(0, direction=2), _ARG),
+        ("w.direction 1", ("dw_slabs",), None, _set(1, direction=1), _ARG),
+        ("direction 1 with sums", ("group_slabs_bnsum",), None, _set(0, direction=1), _ARG),
+        ("splits 0", _SLAB, None, _set(0, splits=0), _ARG),
+        ("splits 0, second problem", tuple(f for f in _SLAB if f in not_single), None, _set(1, splits=0), _ARG),
+        ("splits = plan + 1", _SLAB, None, lambda call: call.P[0].update(splits=call.P[0]["splits"] + 1), _ARG),
+        ("splits = plan + 1, second problem", tuple(f for f in _SLAB if f in not_single), None,
+         lambda call: call.P[1].update(splits=call.P[1]["splits"] + 1), _ARG),
+        ("slab_stride -1", tuple(f for f in _SLAB if f != "backward_slabs"), None, _set(0, slab_stride=-1), _ARG),
+        ("mat_ld -4", with_mat_ld, None, _set(0, mat_ld=-4), _ARG),
+        ("mat_ld on a weight gradient", ("slabs",), "W", _set(0, mat_ld=8), _ARG),
+        ("mat_ld on a weight gradient", ("dw_slabs", "group_slabs"), None, _set(1, mat_ld=8), _ARG),
+        ("act_ld < c", with_act_ld, None, _set(0, act_ld=4), _ARG),
+        ("out_c > c", ("slabs",), "W", _set(0, out_c=9), _ARG),
+        ("out_c > c", ("dw_slabs", "group_slabs"), None, _set(1, out_c=9), _ARG),
+        ("out_c > c", ("group_slabs_bnsum",), None, _set(0, out_c=9), _ARG),
+        ("out_c, no weight gradient", ("slabs",) + _STRUCT, None, _set(0, out_c=4), _ARG),
+        ("out 4 bytes off", _ALL, None, _off_by_4_bytes(0, "out"), _ALIGN),
+        ("act 4 bytes off", _ALL, None, _off_by_4_bytes(0, "act"), _ALIGN),
+        ("mat 4 bytes off", _ALL, None, _off_by_4_bytes(0, "mat"), _ALIGN),
+        ("x 4 bytes off", not_single, None, _off_by_4_bytes(1, "act"), _ALIGN),
+        ("dw 4 bytes off", not_single, None, _off_by_4_bytes(1, "out"), _ALIGN),
+        ("no problems", _GROUP, None, count(0), _ARG),
+        ("five problems", _GROUP, None, count(5), _ARG),
+        ("part_rows + 1", ("group_slabs_bnsum",), None, part_rows, _ARG),
+    ]
+    wrong = []
+    for what, forms, kinds, edit, want in cases:
+        for form in forms:
+            call = _Call(form, kinds)
+            edit(call)
+            got = call.run()
+            if got != want:
+                wrong.append((what, form, got, want))
+    assert not wrong, wrong
+
+    # c = 6: the activation operand 4 bytes off the grid
+    gen = torch.Generator(device=DEV).manual_seed(23)
+    for form in _ALL:
+        call = _Call(form, c=6)
+        q = call.P[0]
+        q["act"] += 4
+        if form not in _SINGLE:
+            assert call.run() == _ARG, form
+            continue
+        x, wt = torch.randn(2, 4, 4, 6, device=DEV, generator=gen), torch.randn(8, 3, 3, 6, device=DEV, generator=gen)
+        q["_t"][1][1:1 + x.numel()] = x.flatten()
+        q["_t"][2][:wt.numel()] = wt.flatten()
+        assert call.run() == 0, form
+        slabs = 1 if form == "nhwc" else q["splits"]
+        got = q["_t"][0][:slabs * 256].view(slabs, 2, 4, 4, 8).sum(0)
+        want = torch.nn.functional.conv2d(x.permute(0, 3, 1, 2).double(), wt.permute(0, 3, 1, 2).double(), None, 1, 1)
+        want = want.permute(0, 2, 3, 1)
+        within(float((got.double() - want).abs().max() / want.abs().max()), 2e-5, note=form)

@@ -976,17 +976,35 @@ def test_grouped_launches_equal_the_single_ones_bitwise():
     w3T, w1T = w3.permute(1, 2, 3, 0).contiguous(), w1.permute(1, 2, 3, 0).contiguous()
     probs = [(0, geo3, x, w3, n * 16 * k), (0, geo1, x, w1, n * 16 * k), (1, geo3, gy, w3T, x.numel()),
              (2, geo1, x, gy, w1.numel())]
-    singles, grouped, group_args = [], [], []
-    for d, geo, act, mat, numel in probs:
-        sp = _lib.conv_plan(d, *geo[:7], geo[7], geo[8])
-        a, b = torch.zeros(sp, numel, device=DEV), torch.zeros(sp, numel, device=DEV)
-        _lib.conv2d_nhwc_slabs(d, a, act, mat, *geo[:7], geo[7], geo[8], sp)
-        singles.append(a)
-        grouped.append(b)
-        group_args.append((d, b, act, mat, geo, sp, 0, 0))
-    _lib.conv_group_slabs(group_args, x.device)
-    for a, b in zip(singles, grouped):
-        assert torch.equal(a, b)
+
+    def singles_and_group(probs):
+        singles, grouped, group_args = [], [], []
+        for d, geo, act, mat, numel in probs:
+            sp = _lib.conv_plan(d, *geo[:7], geo[7], geo[8])
+            a, b = torch.zeros(sp, numel, device=DEV), torch.zeros(sp, numel, device=DEV)
+            _lib.conv2d_nhwc_slabs(d, a, act, mat, *geo[:7], geo[7], geo[8], sp)
+            singles.append(a)
+            grouped.append(b)
+            group_args.append((d, b, act, mat, geo, sp, 0, 0))
+        _lib.conv_group_slabs(group_args, x.device)
+        for a, b in zip(singles, grouped):
+            assert torch.equal(a, b)
+        return singles, group_args
+
+    singles_and_group(probs)
+    # A launch of the instantiation for 128-wide tiles AND residue classes: the data gradient of a stride-2 layer on
+    # 32 x 32 maps (4 classes of 8192 rows, 96 output columns: 256 tiles of 128 x 96, 48 reduction steps -- the plan
+    # leaves such a launch unsplit, which only the class rule does: 512 / 256 tiles would give 2) with the layer's
+    # weight gradient and a forward convolution; data + weight gradient also as the merged launch.
+    geo_s, geo_f = (32, 32, 32, 96, 192, 3, 3, (2, 2), (1, 1)), (32, 32, 32, 96, 96, 3, 3, (1, 1), (1, 1))
+    xb, gyb = _cl(r_(32, 96, 32, 32)), _cl(r_(32, 192, 16, 16))
+    ws, wf = _cl(r_(192, 96, 3, 3)), _cl(r_(96, 96, 3, 3))
+    assert _lib.conv_plan(1, *geo_s[:7], geo_s[7], geo_s[8]) == 1
+    singles, group_args = singles_and_group([(1, geo_s, gyb, ws.permute(1, 2, 3, 0).contiguous(), xb.numel()),
+                                             (2, geo_s, xb, gyb, ws.numel()), (0, geo_f, xb, wf, 32 * 32 * 32 * 96)])
+    merged = [torch.zeros_like(t) for t in singles[:2]]
+    _lib.conv_dw_slabs(*((q[0], out, *q[2:]) for q, out in zip(group_args, merged)), x.device)
+    assert torch.equal(merged[0], singles[0]) and torch.equal(merged[1], singles[1])
 
     # BatchNorm tangent / adjoint pairs against the single launches
     lib, st, P = _lib.load(), _lib.current_stream_ptr(x.device), _lib.c_void_p

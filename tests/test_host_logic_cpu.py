@@ -621,3 +621,64 @@ def test_path_report_names_the_path_of_every_call():
         opt.step(forward=forward, grad=torch.ones(n), mvp=lambda v: 2.0 * v)
         assert opt.path_report()["step"]["path"] == "user"
     assert not [w for w in rec if "slower path" in str(w.message)]
+
+
+def conv_plan_geometries():
+    """The geometries of ``tests/golden/conv_plan.npz``, rows of (direction, n, h, w, c, k, r, s, stride_h, stride_w,
+    pad_h, pad_w): the shapes of ``test_conv_gpu.GEOMS``; every convolution of the three bench topologies at batch 32,
+    each also with 2c input channels (the tangent operand); the stem as a product over its im2col; a grid over strides,
+    pads, windows and map heights; geometries the planner refuses."""
+    from pytorchhessianfree_amd import testproblems as tp
+    from test_conv_gpu import GEOMS
+
+    geoms = [(n, h, w, c, k, r, s, *st, *pd) for n, h, w, c, k, r, s, st, pd in GEOMS]
+    for net, shape in ((tp.ResNet18(), (1, 28, 28)), (tp.AllCNNC(), (3, 32, 32)), (tp.ResNet50(), (3, 64, 64))):
+        def record(m, inp, _out):
+            _, c, h, w = inp[0].shape
+            for cin in (c, 2 * c):
+                geoms.append((32, h, w, cin, m.out_channels, *m.kernel_size, *m.stride, *m.padding))
+        hooks = [m.register_forward_hook(record) for m in net.modules() if isinstance(m, torch.nn.Conv2d)]
+        with torch.no_grad():
+            net.eval()(torch.zeros(1, *shape))
+        for hk in hooks:
+            hk.remove()
+    geoms += [(rows, 1, 1, c, k, 1, 1, 1, 1, 0, 0) for rows in (32 * 196, 32 * 1024) for c in (49, 52, 244)
+              for k in (64, 96)]
+    geoms += [(32, h, h, 64, 64, r, s, st, st, pd, pd) for st in (1, 2, 3) for pd in (0, 1) for r in (1, 3, 5)
+              for s in (1, 3, 5) for h in (1, 2, 5)]  # (windows larger than the padded map among them: refused)
+    geoms = list(dict.fromkeys(geoms))
+    rows = [(d, *g) for g in geoms for d in (0, 1, 2)]
+    base = (32, 7, 7, 64, 64, 3, 3, 1, 1, 1, 1)
+    rows += [(0, 2, 9, 9, 8, 8, 9, 8, 1, 1, 4, 4),   # r * s > MAX_TAPS
+             (1, 2, 2, 2, 8, 8, 5, 5, 1, 1, 0, 0),   # a window larger than the padded input
+             (3, *base), (-1, *base)]                # no such direction
+    for i in range(len(base)):                       # a zero or negative field (a zero padding is none)
+        rows += [(i % 3, *base[:i], v, *base[i + 1:]) for v in (0, -1) if not (v == 0 and i >= 9)]
+    return np.asarray(rows, dtype=np.int64)
+
+
+def write_conv_plan_golden(path):
+    """Regenerates the fixture from the library in use (``HF_PCG_LIB``: the build whose plan is to be pinned)."""
+    from pytorchhessianfree_amd import _lib
+
+    geoms = conv_plan_geometries()
+    splits = np.asarray([_lib.load().hf_conv2d_nhwc_plan(*(int(v) for v in g), 0) for g in geoms], dtype=np.int32)
+    np.savez_compressed(path, geoms=geoms, splits=splits)
+
+
+def test_convolution_plan_reproduces_the_pinned_split_counts():
+    """``hf_conv2d_nhwc_plan`` (pure host arithmetic: runs without a GPU) answers every geometry of
+    ``tests/golden/conv_plan.npz`` with the recorded split count, or the recorded refusal code where ``splits`` is
+    negative.  The split count fixes the fp32 summation order of every convolution of the curvature product, and every
+    launching entry point refuses a count that is not the planner's: drift of the planner shows here first.  The file
+    was written by ``write_conv_plan_golden`` from the library BEFORE all entry points were put on one planner."""
+    from pytorchhessianfree_amd import _lib
+
+    gold = load_golden("conv_plan.npz")
+    geoms, want = gold["geoms"], gold["splits"]
+    assert np.array_equal(geoms, conv_plan_geometries())  # (the fixture covers what the generator says it does)
+    assert (want < 0).sum() >= 20 and (want > 1).sum() >= 100 and len(want) > 600
+    plan = _lib.load().hf_conv2d_nhwc_plan
+    got = np.asarray([plan(*(int(v) for v in g), 0) for g in geoms], dtype=np.int32)
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, [(geoms[i].tolist(), int(want[i]), int(got[i])) for i in bad[:10]]
