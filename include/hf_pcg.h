@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 13
+#define HF_ABI_VERSION 14
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -621,6 +621,51 @@ int hf_linear_ce_head_slabs(int64_t rows);
  */
 int hf_pool_ce_head(void* g, void* jv_out, const void* t, const void* p, double scale, int64_t n, int64_t hw,
                     int64_t k, int dtype, void* stream);
+
+/* ---- fully-connected layers inside the GGN product (hf_dense.hip) ---------------- */
+/*
+ * The sweeps of BackPACK's R-op / L-op (optimizer.py:457-462) through nn.Linear layers of a prepared MLP
+ * (examples/run_mwe.py, run_small_nn.py; tests/test_utils.py:19-52), as skinny fp32 MFMA GEMMs that read the weight
+ * W [c_out, c_in] and the vector's slice V (same shape) IN PLACE in the flat parameter / CG vectors and write the weight
+ * gradient straight into the product vector.  `rows` is the batch, 1 <= rows <= 256; c_in, c_out <= 2^20.  Operands
+ * need only 4-byte alignment and c_in / c_out need not be multiples of anything: the 16-byte forms are chosen on the
+ * host where base pointers and row pitches allow them.  No atomics; bitwise repeatable.  HF_F32 only.  Anything else is
+ * refused with HF_ERR_ARG before any launch.
+ *
+ * Split reductions leave `splits` slabs, `slab_stride` elements apart, in the output's own layout; the consumer
+ * (hf_dense_act_tangent / hf_dense_act_adjoint) adds them as slab 0, then slabs 1 .. n-1 in split order.  A reduction of
+ * `len` entries (c_in for T, c_out for D) accepts 1 <= splits <= 32 with (splits - 1) * kper < len, kper =
+ * ceil(ceil(len / splits) / 32) * 32 (no split starts behind the end); hf_dense_plan returns the counts the engine uses
+ * (about 512 workgroups per launch).  One host function is the definition of both rules; the launching entry points
+ * run it.
+ *
+ * Rounding.  Every slab entry is the sum, in wave order, of four partial sums, each an fmaf chain over every fourth
+ * 8-entry step of the split's range in ascending order (per entry first t_x*W, then x*V).  hf_dense_wgrad: one fmaf chain
+ * over the rows in ascending order, then one multiplication by `scale` (rounded to fp32).
+ */
+int hf_dense_plan(int64_t rows, int64_t c_in, int64_t c_out, int* splits_t, int* splits_d);
+/* T: out_slabs[s][r][o] = sum over split s's share of c_in of  t_x[r][i] W[o][i] + x[r][i] V[o][i].
+ * t_x == NULL (the first live layer) or V == NULL (a frozen weight) drops that term (not both); with t_x = NULL,
+ * V = W it is the forward GEMM x W^T.  t_x and x share the row pitch ld_x (0 = c_in). */
+int hf_dense_tangent_slabs(void* out_slabs, const void* t_x, const void* x, const void* W, const void* V, int64_t rows,
+                           int64_t c_in, int64_t c_out, int64_t ld_x, int splits, int64_t slab_stride, int dtype,
+                           void* stream);
+/* D: out_slabs[s][r][i] = sum over split s's share of c_out of  g_a[r][o] W[o][i]  (no transposed copy of W). */
+int hf_dense_dgrad_slabs(void* out_slabs, const void* g_a, const void* W, int64_t rows, int64_t c_in, int64_t c_out,
+                         int splits, int64_t slab_stride, int dtype, void* stream);
+/* W: out[o][i] = scale * sum_r g_a[r][o] x[r][i], written once (out = product vector + the weight's offset). */
+int hf_dense_wgrad(void* out, const void* g_a, const void* x, int64_t rows, int64_t c_in, int64_t c_out, double scale,
+                   int dtype, void* stream);
+/* act: 0 identity, 1 relu, 2 tanh; y [rows, c] is the layer's OUTPUT (NULL allowed for identity); the factor act'(y)
+ * is  y > 0  for relu (as hf_chan_affine's mask) and  1 - y*y  for tanh (y*y, 1 - ., s * .: three roundings).
+ *   hf_dense_act_tangent: t_y[r][j] = (sum of slabs + v_b[j]) * act'(y[r][j])     (v_b: bias tangent, nullable)
+ *   hf_dense_act_adjoint: g_a[r][j] = (sum of slabs) * act'(y[r][j]);
+ *                         g_b_out[j] = scale * sum_r g_a[r][j]  (nullable; rows in ascending order, accumulated in
+ *                         fp64, rounded to fp32 once, then multiplied by `scale` rounded to fp32). */
+int hf_dense_act_tangent(void* t_y, const void* slabs, int splits, int64_t slab_stride, const void* v_b, const void* y,
+                         int act, int64_t rows, int64_t c, int dtype, void* stream);
+int hf_dense_act_adjoint(void* g_a, void* g_b_out, const void* slabs, int splits, int64_t slab_stride, const void* y,
+                         int act, int64_t rows, int64_t c, double scale, int dtype, void* stream);
 
 /* ---- RCCL (resolved at run time from the already-loaded librccl) ----------- */
 typedef struct hf_comm hf_comm_t;

@@ -11,9 +11,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 # one translation unit per kernel family: PCG solver | gather / scatter | BatchNorm / bias maps | convolutions |
-# pooling + classifier heads | the RCCL shim
+# pooling + classifier heads | fully-connected layers | the RCCL shim
 SOURCES = [os.path.join(HERE, f) for f in ("hf_pcg.hip", "hf_pack.hip", "hf_bn.hip", "hf_conv.hip", "hf_head.hip",
-                                           "hf_rccl.hip")]
+                                           "hf_dense.hip", "hf_rccl.hip")]
 HDR = os.path.join(ROOT, "include", "hf_pcg.h")
 HDRS_SHARED = [os.path.join(HERE, f) for f in ("hf_common.h", "hf_unpack.h")]
 OUT = os.path.join(HERE, "libhfpcg.so")

@@ -1,0 +1,411 @@
+// hf_dense.hip -- fully-connected layers inside the GGN product (the dense-stack curvature engine, engine/dense.py):
+// skinny fp32 GEMMs (batch rows <= 256) on __builtin_amdgcn_mfma_f32_32x32x2f32 that read the weight [c_out, c_in] and
+// the matching slice of the CG vector IN PLACE in the flat vectors -- no [W | v_W] copy, no transposed copy, no gather
+// afterwards -- plus the two elementwise passes between them.  fp32, wave64, no atomics; partial results of a split
+// reduction leave as slabs that the consumer adds by the rule of hf_common.h::slab_sum; every kernel sums in one fixed
+// order, so two launches on the same operands agree bitwise.
+//
+// Fragment layout of the 32x32x2 MFMA (wave64): lane l supplies A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31];
+// accumulator register q of lane l is C[(q & 3) + 8 * (q >> 2) + 4 * (l >> 5)][l & 31].  The reduction index may be
+// visited in any order as long as A and B agree, so a lane takes FOUR consecutive k (one 16-byte load where the operand
+// allows it) and feeds them to four MFMAs; likewise four consecutive output columns per lane where the OUTPUT is the
+// wide operand (hf_dense_wgrad).
+//
+// Operands may sit anywhere in a flat parameter vector (4-byte aligned, row lengths that are no multiple of 4): the host
+// picks the 16-byte form only when base pointers and row pitches allow it, else the kernels load element by element.
+// Every load is predicated on its row and column: nothing outside rows x c is ever read.
+#include "hf_common.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int DENSE_MAX_ROWS = 256;
+constexpr int DENSE_MAX_SPLITS = 32;
+constexpr int64_t DENSE_MAX_C = 1 << 20;
+constexpr int DENSE_KSTEP = 32;        // reduction entries one pass of a workgroup consumes: 4 waves x 8
+constexpr int DENSE_TARGET_BLOCKS = 512;
+
+// ---- the plan: ONE definition, run by hf_dense_plan and by every launching entry point ----------------------------
+inline bool dense_dims_ok(int64_t rows, int64_t c_in, int64_t c_out) {
+  return rows >= 1 && rows <= DENSE_MAX_ROWS && c_in >= 1 && c_in <= DENSE_MAX_C && c_out >= 1 && c_out <= DENSE_MAX_C;
+}
+
+// reduction entries per split: a multiple of DENSE_KSTEP
+inline int64_t dense_kper(int64_t len, int splits) {
+  const int64_t per = (len + splits - 1) / splits;
+  return (per + DENSE_KSTEP - 1) / DENSE_KSTEP * DENSE_KSTEP;
+}
+
+// a split count the kernels accept for a reduction of `len` entries: no split may start behind the end
+inline bool dense_split_ok(int64_t len, int splits) {
+  if (splits < 1 || splits > DENSE_MAX_SPLITS) return false;
+  return (int64_t)(splits - 1) * dense_kper(len, splits) < len;
+}
+
+// the planned count: about DENSE_TARGET_BLOCKS workgroups of one 32-column tile each
+inline int dense_planned_splits(int64_t len, int64_t out_cols) {
+  const int64_t tiles = (out_cols + 31) / 32;
+  int64_t want = (DENSE_TARGET_BLOCKS + tiles - 1) / tiles;
+  if (want > DENSE_MAX_SPLITS) want = DENSE_MAX_SPLITS;
+  int s = (int)want;
+  while (s > 1 && !dense_split_ok(len, s)) --s;
+  return s;
+}
+
+struct DensePlan {
+  int splits_t, splits_d;
+};
+
+inline int dense_plan(int64_t rows, int64_t c_in, int64_t c_out, DensePlan* p) {
+  if (!dense_dims_ok(rows, c_in, c_out)) return HF_ERR_ARG;
+  p->splits_t = dense_planned_splits(c_in, c_out);   // T: reduction over c_in, output [rows, c_out]
+  p->splits_d = dense_planned_splits(c_out, c_in);   // D: reduction over c_out, output [rows, c_in]
+  return HF_OK;
+}
+
+inline bool quad_ok(const void* p, int64_t pitch) { return aligned16(p) && (pitch & 3) == 0; }
+
+// ---- device helpers ------------------------------------------------------------------------------------------------
+struct Quad { float e[4]; };
+
+// p[k .. k+3] of a row that ends at `end`; `ok` = the row exists.  Entries outside read as zero and are not touched.
+template <bool ALIGNED>
+__device__ __forceinline__ Quad ld_quad(const float* __restrict__ p, int k, int end, bool ok) {
+  Quad q;
+  if (ALIGNED && ok && k + 4 <= end) {
+    const F4 v = ld4(p + k);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) q.e[e] = v.e[e];
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) q.e[e] = (ok && k + e < end) ? p[k + e] : 0.0f;
+  }
+  return q;
+}
+
+// The four waves of a workgroup hold partial sums of the same 32x32 tile (each took every fourth 8-entry step of the
+// split's range): added in wave order ((w0 + w1) + w2) + w3 through LDS and written to out[row0 + .][col0 + .].
+__device__ __forceinline__ void store_tile_sum(float (*red)[1024], const f32x16& acc, float* __restrict__ out, int row0,
+                                               int rows, int col0, int cols) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();  // (the previous tile's readers are done)
+#pragma unroll
+  for (int q = 0; q < 16; ++q) red[wave][q * 64 + lane] = acc[q];
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int e = threadIdx.x + 256 * u, q = e >> 6, ln = e & 63;
+    float s = red[0][e];
+    s += red[1][e];
+    s += red[2][e];
+    s += red[3][e];
+    const int r = row0 + (q & 3) + 8 * (q >> 2) + 4 * (ln >> 5), c = col0 + (ln & 31);
+    if (r < rows && c < cols) out[(size_t)r * cols + c] = s;
+  }
+}
+
+// ---- T: slab s of  t_x . W^T + x . V^T  over the split's share of c_in ------------------------------------------
+// grid (ceil(c_out / 32), splits); per lane one row of W / V (c_in contiguous) and one row of t_x / x per row tile.
+// Order of the additions into one accumulator: k ascending within the wave's steps, per k first t_x*W then x*V.
+template <int MT, bool ALIGNED>
+__global__ __launch_bounds__(BLOCK) void k_dense_tangent(float* __restrict__ out, const float* __restrict__ tx,
+                                                         const float* __restrict__ x, const float* __restrict__ W,
+                                                         const float* __restrict__ V, int rows, int c_in, int c_out,
+                                                         int ld_x, int kper, long long slab_stride) {
+  __shared__ float red[WAVES][1024];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
+  const int o = blockIdx.x * 32 + j;
+  const bool o_ok = o < c_out;
+  const int kb = blockIdx.y * kper, ke = min(kb + kper, c_in);
+  const float* wrow = W + (size_t)(o_ok ? o : 0) * c_in;
+  const float* vrow = V ? V + (size_t)(o_ok ? o : 0) * c_in : nullptr;
+  f32x16 acc[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[m][q] = 0.0f;
+  for (int k0 = kb + 8 * wave; k0 < ke; k0 += DENSE_KSTEP) {
+    const int k = k0 + 4 * h;
+    Quad w4 = {}, v4 = {};
+    if (tx) w4 = ld_quad<ALIGNED>(wrow, k, ke, o_ok);
+    if (V) v4 = ld_quad<ALIGNED>(vrow, k, ke, o_ok);
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const int r = 32 * m + j;
+      const bool r_ok = r < rows;
+      const size_t ro = (size_t)(r_ok ? r : 0) * ld_x;
+      Quad t4 = {}, x4 = {};
+      if (tx) t4 = ld_quad<ALIGNED>(tx + ro, k, ke, r_ok);
+      if (V) x4 = ld_quad<ALIGNED>(x + ro, k, ke, r_ok);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        if (tx) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(t4.e[s], w4.e[s], acc[m], 0, 0, 0);
+        if (V) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(x4.e[s], v4.e[s], acc[m], 0, 0, 0);
+      }
+    }
+  }
+  float* slab = out + (long long)blockIdx.y * slab_stride;
+#pragma unroll
+  for (int m = 0; m < MT; ++m) store_tile_sum(red, acc[m], slab, 32 * m, rows, blockIdx.x * 32, c_out);
+}
+
+// ---- D: slab s of  g_a . W  over the split's share of c_out -----------------------------------------------------
+// grid (ceil(c_in / 32), splits); B[k][j] = W[k][i0 + j]: 128 contiguous bytes per weight row and load, no transposed
+// copy.  Order of the additions: k ascending within the wave's steps.
+template <int MT, bool ALIGNED>
+__global__ __launch_bounds__(BLOCK) void k_dense_dgrad(float* __restrict__ out, const float* __restrict__ g,
+                                                       const float* __restrict__ W, int rows, int c_in, int c_out,
+                                                       int kper, long long slab_stride) {
+  __shared__ float red[WAVES][1024];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
+  const int i = blockIdx.x * 32 + j;
+  const bool i_ok = i < c_in;
+  const int kb = blockIdx.y * kper, ke = min(kb + kper, c_out);
+  f32x16 acc[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[m][q] = 0.0f;
+  for (int k0 = kb + 8 * wave; k0 < ke; k0 += DENSE_KSTEP) {
+    const int k = k0 + 4 * h;
+    float w[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) w[s] = (i_ok && k + s < ke) ? W[(size_t)(k + s) * c_in + i] : 0.0f;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const int r = 32 * m + j;
+      const bool r_ok = r < rows;
+      const Quad g4 = ld_quad<ALIGNED>(g + (size_t)(r_ok ? r : 0) * c_out, k, ke, r_ok);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(g4.e[s], w[s], acc[m], 0, 0, 0);
+    }
+  }
+  float* slab = out + (long long)blockIdx.y * slab_stride;
+#pragma unroll
+  for (int m = 0; m < MT; ++m) store_tile_sum(red, acc[m], slab, 32 * m, rows, blockIdx.x * 32, c_in);
+}
+
+// ---- W: out[o][i] = scale * sum_r g_a[r][o] * x[r][i], written once ----------------------------------------------
+// grid (ceil(c_in / 128), ceil(c_out / 128)); wave w owns output rows o0 + 32 w .. + 31 and 128 columns, lane column j
+// holding the four consecutive columns i0 + 4 j + u in accumulators u = 0..3 (one 16-byte store per output row where the
+// destination allows it).  The reduction runs over the batch rows in ascending order; `scale` multiplies the finished
+// sum (one more rounding).
+template <bool ALIGNED>
+__global__ __launch_bounds__(BLOCK) void k_dense_wgrad(float* __restrict__ out, const float* __restrict__ g,
+                                                       const float* __restrict__ x, int rows, int c_in, int c_out,
+                                                       float scale) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
+  const int o0 = blockIdx.y * 128 + 32 * wave, i0 = blockIdx.x * 128 + 4 * j;
+  if (o0 >= c_out) return;  // (no barrier in this kernel)
+  const int o = o0 + j;
+  const bool o_ok = o < c_out;
+  f32x16 acc[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[u][q] = 0.0f;
+  for (int r0 = 0; r0 < rows; r0 += 2) {
+    const int r = r0 + h;
+    const bool r_ok = r < rows;
+    const float a = (r_ok && o_ok) ? g[(size_t)r * c_out + o] : 0.0f;
+    const Quad b4 = ld_quad<ALIGNED>(x + (size_t)(r_ok ? r : 0) * c_in, i0, c_in, r_ok);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b4.e[u], acc[u], 0, 0, 0);
+  }
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int oo = o0 + (q & 3) + 8 * (q >> 2) + 4 * h;
+    if (oo >= c_out) continue;
+    float* dst = out + (size_t)oo * c_in + i0;
+    if (ALIGNED && i0 + 4 <= c_in) {
+      F4 v;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v.e[u] = acc[u][q] * scale;
+      *reinterpret_cast<F4*>(dst) = v;
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (i0 + u < c_in) dst[u] = acc[u][q] * scale;
+    }
+  }
+}
+
+// ---- activation factor ---------------------------------------------------------------------------------------------
+enum { ACT_IDENTITY = 0, ACT_RELU = 1, ACT_TANH = 2 };
+
+// s * act'(y): relu  y > 0 ? s : 0  (as k_chan_affine);  tanh  s * (1 - y*y)  (three roundings)
+__device__ __forceinline__ float act_apply(float s, const float* __restrict__ y, int idx, int act) {
+  if (act == ACT_RELU) return y[idx] > 0.0f ? s : 0.0f;
+  if (act == ACT_TANH) {
+    const float yy = y[idx];
+    return s * (1.0f - yy * yy);
+  }
+  return s;
+}
+
+// t_y = (sum of slabs + v_b[col]) * act'(y)
+__global__ __launch_bounds__(BLOCK) void k_dense_act_tangent(float* __restrict__ ty, const float* __restrict__ slabs,
+                                                             int splits, long long stride, const float* __restrict__ vb,
+                                                             const float* __restrict__ y, int act, int total, int c) {
+  const int idx = blockIdx.x * BLOCK + threadIdx.x;
+  if (idx >= total) return;
+  float s = slab_sum<4>(slabs[idx], slabs, idx, splits, stride);
+  if (vb) s += vb[idx % c];
+  ty[idx] = act_apply(s, y, idx, act);
+}
+
+// g_a = (sum of slabs) * act'(y);  g_b[col] = scale * sum_rows g_a -- one thread per column walks the rows in order,
+// the column sum is kept in fp64 and rounded to fp32 once, then multiplied by `scale`.
+constexpr int ADJ_BLOCK = 64;
+__global__ __launch_bounds__(ADJ_BLOCK) void k_dense_act_adjoint(float* __restrict__ ga, float* __restrict__ gb,
+                                                                 const float* __restrict__ slabs, int splits,
+                                                                 long long stride, const float* __restrict__ y, int act,
+                                                                 int rows, int c, float scale) {
+  const int col = blockIdx.x * ADJ_BLOCK + threadIdx.x;
+  if (col >= c) return;
+  double sum = 0.0;
+  for (int r = 0; r < rows; ++r) {
+    const int idx = r * c + col;
+    const float s = slab_sum<4>(slabs[idx], slabs, idx, splits, stride);
+    const float gv = act_apply(s, y, idx, act);
+    ga[idx] = gv;
+    sum += (double)gv;
+  }
+  if (gb) gb[col] = (float)sum * scale;
+}
+
+inline bool act_args_ok(const void* slabs, int splits, int64_t slab_stride, const void* y, int act, int64_t rows,
+                        int64_t c, int dtype) {
+  if (dtype != HF_F32 || !slabs) return false;
+  if (rows < 1 || rows > DENSE_MAX_ROWS || c < 1 || c > DENSE_MAX_C) return false;
+  if (splits < 1 || splits > DENSE_MAX_SPLITS) return false;
+  if (splits > 1 && slab_stride < rows * c) return false;
+  if (act < ACT_IDENTITY || act > ACT_TANH) return false;
+  if (act != ACT_IDENTITY && !y) return false;
+  return true;
+}
+
+#define DENSE_MT_SWITCH(mt, CALL) \
+  switch (mt) {                   \
+    case 1: CALL(1); break;       \
+    case 2: CALL(2); break;       \
+    case 3: CALL(3); break;       \
+    case 4: CALL(4); break;       \
+    case 5: CALL(5); break;       \
+    case 6: CALL(6); break;       \
+    case 7: CALL(7); break;       \
+    default: CALL(8); break;      \
+  }
+
+}  // namespace
+
+extern "C" {
+
+int hf_dense_plan(int64_t rows, int64_t c_in, int64_t c_out, int* splits_t, int* splits_d) {
+  DensePlan p;
+  if (!splits_t || !splits_d) return HF_ERR_ARG;
+  const int rc = dense_plan(rows, c_in, c_out, &p);
+  if (rc != HF_OK) return rc;
+  *splits_t = p.splits_t;
+  *splits_d = p.splits_d;
+  return HF_OK;
+}
+
+int hf_dense_tangent_slabs(void* out_slabs, const void* t_x, const void* x, const void* W, const void* V, int64_t rows,
+                           int64_t c_in, int64_t c_out, int64_t ld_x, int splits, int64_t slab_stride, int dtype,
+                           void* stream) {
+  DensePlan p;
+  if (dense_plan(rows, c_in, c_out, &p) != HF_OK) return HF_ERR_ARG;
+  if (dtype != HF_F32 || !out_slabs) return HF_ERR_ARG;
+  if (!t_x && !V) return HF_ERR_ARG;           // nothing to compute
+  if ((t_x && !W) || (V && !x)) return HF_ERR_ARG;
+  if (ld_x == 0) ld_x = c_in;
+  if (ld_x < c_in || ld_x > DENSE_MAX_C) return HF_ERR_ARG;
+  if (!dense_split_ok(c_in, splits)) return HF_ERR_ARG;
+  if (splits > 1 && slab_stride < rows * c_out) return HF_ERR_ARG;
+  const bool al = (!t_x || (quad_ok(t_x, ld_x) && quad_ok(W, c_in))) && (!V || (quad_ok(x, ld_x) && quad_ok(V, c_in)));
+  const int mt = (int)((rows + 31) / 32), kper = (int)dense_kper(c_in, splits);
+  const dim3 grid((unsigned)((c_out + 31) / 32), (unsigned)splits);
+  hipStream_t st = (hipStream_t)stream;
+#define CALL_T(MT)                                                                                                     \
+  do {                                                                                                                 \
+    if (al)                                                                                                            \
+      k_dense_tangent<MT, true><<<grid, BLOCK, 0, st>>>((float*)out_slabs, (const float*)t_x, (const float*)x,         \
+                                                        (const float*)W, (const float*)V, (int)rows, (int)c_in,        \
+                                                        (int)c_out, (int)ld_x, kper, (long long)slab_stride);          \
+    else                                                                                                               \
+      k_dense_tangent<MT, false><<<grid, BLOCK, 0, st>>>((float*)out_slabs, (const float*)t_x, (const float*)x,        \
+                                                         (const float*)W, (const float*)V, (int)rows, (int)c_in,       \
+                                                         (int)c_out, (int)ld_x, kper, (long long)slab_stride);         \
+  } while (0)
+  DENSE_MT_SWITCH(mt, CALL_T)
+#undef CALL_T
+  return (int)hipGetLastError();
+}
+
+int hf_dense_dgrad_slabs(void* out_slabs, const void* g_a, const void* W, int64_t rows, int64_t c_in, int64_t c_out,
+                         int splits, int64_t slab_stride, int dtype, void* stream) {
+  DensePlan p;
+  if (dense_plan(rows, c_in, c_out, &p) != HF_OK) return HF_ERR_ARG;
+  if (dtype != HF_F32 || !out_slabs || !g_a || !W) return HF_ERR_ARG;
+  if (!dense_split_ok(c_out, splits)) return HF_ERR_ARG;
+  if (splits > 1 && slab_stride < rows * c_in) return HF_ERR_ARG;
+  const bool al = quad_ok(g_a, c_out);
+  const int mt = (int)((rows + 31) / 32), kper = (int)dense_kper(c_out, splits);
+  const dim3 grid((unsigned)((c_in + 31) / 32), (unsigned)splits);
+  hipStream_t st = (hipStream_t)stream;
+#define CALL_D(MT)                                                                                                    \
+  do {                                                                                                                \
+    if (al)                                                                                                           \
+      k_dense_dgrad<MT, true><<<grid, BLOCK, 0, st>>>((float*)out_slabs, (const float*)g_a, (const float*)W,          \
+                                                      (int)rows, (int)c_in, (int)c_out, kper, (long long)slab_stride); \
+    else                                                                                                              \
+      k_dense_dgrad<MT, false><<<grid, BLOCK, 0, st>>>((float*)out_slabs, (const float*)g_a, (const float*)W,         \
+                                                       (int)rows, (int)c_in, (int)c_out, kper,                        \
+                                                       (long long)slab_stride);                                       \
+  } while (0)
+  DENSE_MT_SWITCH(mt, CALL_D)
+#undef CALL_D
+  return (int)hipGetLastError();
+}
+
+int hf_dense_wgrad(void* out, const void* g_a, const void* x, int64_t rows, int64_t c_in, int64_t c_out, double scale,
+                   int dtype, void* stream) {
+  DensePlan p;
+  if (dense_plan(rows, c_in, c_out, &p) != HF_OK) return HF_ERR_ARG;
+  if (dtype != HF_F32 || !out || !g_a || !x) return HF_ERR_ARG;
+  if (!(scale == scale)) return HF_ERR_ARG;
+  const bool al = quad_ok(out, c_in) && quad_ok(x, c_in);
+  const dim3 grid((unsigned)((c_in + 127) / 128), (unsigned)((c_out + 127) / 128));
+  hipStream_t st = (hipStream_t)stream;
+  if (al)
+    k_dense_wgrad<true><<<grid, BLOCK, 0, st>>>((float*)out, (const float*)g_a, (const float*)x, (int)rows, (int)c_in,
+                                                (int)c_out, (float)scale);
+  else
+    k_dense_wgrad<false><<<grid, BLOCK, 0, st>>>((float*)out, (const float*)g_a, (const float*)x, (int)rows, (int)c_in,
+                                                 (int)c_out, (float)scale);
+  return (int)hipGetLastError();
+}
+
+int hf_dense_act_tangent(void* t_y, const void* slabs, int splits, int64_t slab_stride, const void* v_b, const void* y,
+                         int act, int64_t rows, int64_t c, int dtype, void* stream) {
+  if (!t_y || !act_args_ok(slabs, splits, slab_stride, y, act, rows, c, dtype)) return HF_ERR_ARG;
+  const int total = (int)(rows * c);
+  k_dense_act_tangent<<<(total + BLOCK - 1) / BLOCK, BLOCK, 0, (hipStream_t)stream>>>(
+      (float*)t_y, (const float*)slabs, splits, (long long)slab_stride, (const float*)v_b, (const float*)y, act, total,
+      (int)c);
+  return (int)hipGetLastError();
+}
+
+int hf_dense_act_adjoint(void* g_a, void* g_b_out, const void* slabs, int splits, int64_t slab_stride, const void* y,
+                         int act, int64_t rows, int64_t c, double scale, int dtype, void* stream) {
+  if (!g_a || !act_args_ok(slabs, splits, slab_stride, y, act, rows, c, dtype)) return HF_ERR_ARG;
+  if (!(scale == scale)) return HF_ERR_ARG;
+  k_dense_act_adjoint<<<(unsigned)((c + ADJ_BLOCK - 1) / ADJ_BLOCK), ADJ_BLOCK, 0, (hipStream_t)stream>>>(
+      (float*)g_a, (float*)g_b_out, (const float*)slabs, splits, (long long)slab_stride, (const float*)y, act, (int)rows,
+      (int)c, (float)scale);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -59,9 +59,11 @@ class FusedGGNEngine(_Topology, _Buffers, _Forward, _TangentSweep, _AdjointSweep
 
     # ------------------------------------------------------------------------------------
     @classmethod
-    def try_build(cls, loss, outputs, params, weight=1.0, group=None, hessian=False, why=None):
+    def try_build(cls, loss, outputs, params, weight=1.0, group=None, hessian=False, why=None, need_session=False):
         """The engine for the model that produced ``outputs``, or ``None``; ``why`` (a list) receives one line per
-        reason it was not taken -- what ``HessianFree.path_report()`` and its one-time warning quote."""
+        reason it was not taken -- what ``HessianFree.path_report()`` and its one-time warning quote.
+        ``need_session``: the caller (a persistent session) needs the engine's own forward pass, loss head and
+        gradient sweep; kinds without them are not built."""
         why = [] if why is None else why
         if os.environ.get("HF_ENGINE", "1") == "0":
             why.append("the fused engine is switched off (HF_ENGINE=0)")
@@ -76,12 +78,18 @@ class FusedGGNEngine(_Topology, _Buffers, _Forward, _TangentSweep, _AdjointSweep
             why.append(f"the model output is not a CUDA float32 [batch, classes] tensor (got {outputs.dtype}, "
                        f"{tuple(outputs.shape)}, {outputs.device})")
             return None
+        from .dense import DenseStackEngine
         from .plain import PlainStackEngine
 
-        kinds = [cls] if cls is not FusedGGNEngine else [FusedGGNEngine, PlainStackEngine]
-        if hessian:
-            kinds = [k for k in kinds if k.supports_hessian]
+        kinds = [cls] if cls is not FusedGGNEngine else [FusedGGNEngine, PlainStackEngine, DenseStackEngine]
+        if any(isinstance(m, torch.nn.Conv2d) for m in model.modules()):
+            kinds = [k for k in kinds if k is not DenseStackEngine]  # (a conv net is no dense stack: nothing to say)
         for kind in kinds:
+            # (asked of the CLASS, in the kinds' order: nothing is built that the caller could not use)
+            reason = kind.unavailable(hessian, need_session)
+            if reason is not None:
+                why.append(f"{kind.__name__}: {reason}")
+                continue
             try:
                 return kind(model, loss, outputs, params, weight, group, hessian=hessian)
             except _Unsupported as exc:
@@ -106,6 +114,16 @@ class FusedGGNEngine(_Topology, _Buffers, _Forward, _TangentSweep, _AdjointSweep
     # TRAIN-mode BatchNorm (round 5): the batch statistics' share of the adjoint's tangent in closed form per channel
     # (hf_bn_train_hessian_coeffs / _apply; the formulas stand in csrc/hf_bn.hip and DESIGN.md section 4.3).
     supports_hessian = True
+    supports_session = True
+
+    @classmethod
+    def unavailable(cls, hessian, need_session):
+        """Why this kind cannot serve a caller who wants Hessian products / a persistent session, or ``None``."""
+        if hessian and not cls.supports_hessian:
+            return "no Hessian products (GGN only)"
+        if need_session and not cls.supports_session:
+            return "no persistent session on this engine yet"
+        return None
 
     def __init__(self, model, loss, outputs, params, weight, group, hessian=False):
         super().__init__(params, weight, group)

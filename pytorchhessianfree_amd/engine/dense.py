@@ -1,0 +1,303 @@
+"""The dense-stack engine: GGN products of a prepared MLP (``Linear [ReLU | Tanh] ... Linear``) on the package's own
+skinny-GEMM kernels (csrc/hf_dense.hip) -- the nets of the reference's examples/run_mwe.py, run_small_nn.py and of its
+own test problem (tests/test_utils.py:19-52)."""
+
+import os
+
+import torch
+from torch import nn
+
+from .. import _lib
+from ..curvature import GGNOperator, _Operator
+from .common import _Node, _P, _Unsupported, _ce_node, _ptr, _same, loss_spec_of
+from .core import FusedGGNEngine
+
+_ACT = {None: 0, nn.ReLU: 1, nn.Tanh: 2}
+
+
+class _Layer:
+    """``Linear(+bias) [ReLU | Tanh]``: the module, its activation code, parameter indices and static buffers."""
+
+    def __init__(self, lin, act):
+        self.lin, self.act = lin, act
+        self.c_out, self.c_in = lin.weight.shape
+        self.dead = self.first_live = False
+
+
+def _addr(base, words):
+    return _P(base + 4 * words)
+
+
+class DenseStackEngine(FusedGGNEngine):
+    """The sweeps of the GGN product for a stack of fully-connected layers.  Per live layer and product: the tangent GEMM
+    ``t_x W^T + x V^T`` (W and the vector's slice V read in place in the flat vectors) -> bias tangent and ``act'``;
+    the loss Hessian on the output tangent; in reverse ``act'`` and the bias gradient -> the weight gradient, written
+    straight into the product vector -> the data gradient.  5 launches per hidden layer, no gather launch, bitwise
+    repeatable.  GGN only; one process; no persistent session (``loss_spec`` stays ``None``)."""
+
+    mode = ("fused curvature engine (dense stack): own skinny MFMA GEMMs that read the weights and the vector in place "
+            "(split reductions as slabs summed by the consumer kernel), bias / activation fused, 5 launches per hidden "
+            "layer, weight gradients written straight into the product")
+    supports_hessian = False
+    supports_session = False
+    max_rows = 256
+
+    @classmethod
+    def unavailable(cls, hessian, need_session):
+        # Opt-in until its speed on large MLPs is measured against the hipGraph-replayed autograd sweeps
+        # (scripts/bench_dense_engine.py): products are tested, the gain is not.
+        if os.environ.get("HF_DENSE_ENGINE", "0") != "1":
+            return "the dense-stack engine is opt-in (set HF_DENSE_ENGINE=1)"
+        reason = super().unavailable(hessian, False)
+        if reason is None and need_session:
+            reason = "the dense-stack engine has no session yet"
+        return reason
+
+    def __init__(self, model, loss, outputs, params, weight, group, hessian=False):
+        _Operator.__init__(self, params, weight, group)
+        if hessian:
+            raise _Unsupported("Hessian products are not implemented for dense stacks (GGN only)")
+        if group is not None:
+            raise _Unsupported("data parallelism is not implemented for dense stacks")
+        self.hessian, self.train_bn, self.frozen_any = False, False, False
+        self.outputs, self.dev = outputs, outputs.device
+        self._index = {id(p): i for i, p in enumerate(self.params)}
+        offs, o = [], 0
+        for p in self.params:
+            offs.append(o)
+            o += p.numel()
+        self._offs = offs
+        self._layout(model)
+        self._allocate()
+        self.forward_own()
+        want = outputs.detach()
+        err = float((self.logits - want).abs().max() / want.abs().max().clamp_min(1e-30))
+        if not err < 1e-4:
+            raise _Unsupported(f"the engine's forward pass differs from the model's output by {err:.2e}")
+        self._loss_setup(loss, outputs)
+        self._verify(loss)
+        if self._at != "own":
+            self.forward_own()
+        for u in self.layers:  # the model's own activations were only needed up to here
+            u.rx = u.ry = None
+        self._rec_in = None
+
+    # ---- topology ----------------------------------------------------------------------------
+    def _layout(self, model):
+        x_in = getattr(self.outputs, "_hf_input", None)
+        if not isinstance(x_in, torch.Tensor) or x_in.dtype != torch.float32 or not x_in.is_cuda:
+            raise _Unsupported("no recorded float32 GPU input")
+        leaves = [m for m in model.modules() if not list(m.children())]
+
+        def io(m):
+            rec = getattr(m, "_hf_io", None)
+            if rec is None or len(rec) != 2 or rec[0] is None:
+                raise _Unsupported(f"{type(m).__name__} has no record of this forward pass")
+            return rec
+
+        layers, cur, i = [], x_in.detach(), 0
+        while i < len(leaves):
+            m = leaves[i]
+            dropout = isinstance(m, (nn.Dropout, nn.Dropout1d, nn.Dropout2d, nn.Dropout3d, nn.AlphaDropout))
+            if isinstance(m, nn.Identity) or (dropout and (not m.training or m.p == 0)):
+                i += 1
+                continue
+            if dropout:
+                raise _Unsupported("a training-mode model with active dropout")
+            if type(m) is nn.Flatten and not layers:
+                fx, fy = io(m)
+                if not _same(fx, cur) or fy.dim() != 2:
+                    raise _Unsupported("Flatten does not turn the input into [batch, features]")
+                cur = fy
+            elif type(m) is nn.Linear:
+                cx, cy = io(m)
+                if cx.dim() != 2 or not _same(cx, cur):
+                    raise _Unsupported(f"linear {len(layers)}: its input is not the previous [batch, features] activation")
+                nxt = leaves[i + 1] if i + 1 < len(leaves) else None
+                act, y = None, cy
+                if type(nxt) in (nn.ReLU, nn.Tanh):
+                    if getattr(nxt, "inplace", False):
+                        raise _Unsupported(f"linear {len(layers)}: followed by an in-place activation")
+                    rx, ry = io(nxt)
+                    if not _same(rx, cy):
+                        raise _Unsupported(f"{type(nxt).__name__} does not read linear {len(layers)}'s output")
+                    act, y = type(nxt), ry
+                    i += 1
+                u = _Layer(m, _ACT[act])
+                u.rx, u.ry = cx, y
+                u.pw = self._param(m.weight)
+                u.pb = self._param(m.bias) if m.bias is not None else None
+                layers.append(u)
+                cur = y
+            else:
+                raise _Unsupported(f"unsupported layer {type(m).__name__}")
+            i += 1
+        if not layers:
+            raise _Unsupported("no Linear layer")
+        if layers[-1].act != 0:
+            raise _Unsupported("the stack does not end in a Linear layer")
+        out = self.outputs.detach()
+        if out.data_ptr() != layers[-1].ry.data_ptr() or tuple(out.shape) != tuple(layers[-1].ry.shape):
+            raise _Unsupported("the network output is not the last Linear layer's output")
+        self.rows = int(out.shape[0])
+        if self.rows > self.max_rows:
+            raise _Unsupported(f"batch {self.rows} > {self.max_rows} rows")
+        used = {k for u in layers for k in (u.pw, u.pb) if k is not None}
+        if used != set(range(len(self.params))):
+            raise _Unsupported("the parameter list has entries the engine's layers do not cover")
+        # frozen layers at the input end: dead for both sweeps; the first layer with a trainable parameter reads a
+        # tangent-free input and needs no data gradient
+        self.dead_layers = 0
+        for u in layers:
+            if u.pw is not None or u.pb is not None:
+                break
+            u.dead = True
+            self.dead_layers += 1
+        if self.dead_layers == len(layers):
+            raise _Unsupported("every layer is frozen")
+        layers[self.dead_layers].first_live = True
+        self.layers, self.model_ref = layers, model
+        self._rec_in = layers[0].rx
+
+    def _allocate(self):
+        f32, dev, rows, lib = torch.float32, self.dev, self.rows, _lib.load()
+        self.x_in = torch.empty((rows, self.layers[0].c_in), dtype=f32, device=dev)
+        self.x_in.copy_(self._rec_in)
+        x, widest = self.x_in, 0
+        for u in self.layers:
+            st, sd = _lib.c_int(), _lib.c_int()
+            _lib.check(lib.hf_dense_plan(rows, u.c_in, u.c_out, st, sd), "hf_dense_plan")
+            u.sT, u.sD = st.value, sd.value
+            u.x = x
+            u.y = torch.empty((rows, u.c_out), dtype=f32, device=dev)
+            u.tslabs = torch.empty((u.sT, rows * u.c_out), dtype=f32, device=dev)
+            if not u.dead:
+                u.ty = torch.empty_like(u.y)
+                u.ga = torch.empty_like(u.y)
+                u.dslabs = None if u.first_live else torch.empty((u.sD, rows * u.c_in), dtype=f32, device=dev)
+            widest = max(widest, u.c_out)
+            x = u.y
+        self.logits = self.layers[-1].y
+        self._g_last = torch.empty_like(self.logits)
+        self._zero = torch.zeros(rows * widest, dtype=f32, device=dev)  # (a tangent GEMM with no live term)
+
+    # ---- launches ----------------------------------------------------------------------------
+    def _tangent(self, u, t_x, v_w):
+        """``u.tslabs <- t_x W^T + x V^T`` (either term may be absent, not both)."""
+        w = u.lin.weight
+        _lib.check(_lib.load().hf_dense_tangent_slabs(
+            _ptr(u.tslabs), _ptr(t_x), _ptr(u.x), _ptr(w), v_w, self.rows, u.c_in, u.c_out, 0, u.sT, u.tslabs.shape[1],
+            _lib.HF_F32, _lib.current_stream_ptr(self.dev)), "hf_dense_tangent_slabs")
+
+    def _act_tangent(self, out, slabs, splits, stride, v_b, y, act, c):
+        _lib.check(_lib.load().hf_dense_act_tangent(
+            _ptr(out), _ptr(slabs), splits, stride, v_b, _ptr(y), act, self.rows, c, _lib.HF_F32,
+            _lib.current_stream_ptr(self.dev)), "hf_dense_act_tangent")
+
+    # ---- forward -----------------------------------------------------------------------------
+    def forward_own(self, refresh=False, update_running=True):
+        """The model's forward pass on the engine's static buffers: the tangent kernel with ``t_x = NULL, V = W`` is
+        the forward GEMM; bias by the slab-summing pass, the activation by ATen (once per step, not per product)."""
+        for u in self.layers:
+            w = u.lin.weight
+            _lib.check(_lib.load().hf_dense_tangent_slabs(
+                _ptr(u.tslabs), None, _ptr(u.x), _ptr(w), _ptr(w), self.rows, u.c_in, u.c_out, 0, u.sT,
+                u.tslabs.shape[1], _lib.HF_F32, _lib.current_stream_ptr(self.dev)), "hf_dense_tangent_slabs")
+            self._act_tangent(u.y, u.tslabs, u.sT, u.tslabs.shape[1], _ptr(u.lin.bias), None, 0, u.c_out)
+            if u.act == 1:
+                torch.relu_(u.y)
+            elif u.act == 2:
+                torch.tanh_(u.y)
+        self._at = "own"
+        return self.logits
+
+    def _load_recorded(self, outputs):
+        """The activations the MODEL's forward pass recorded (same ReLU decisions as the autograd operator the first
+        product is compared with)."""
+        self.x_in.copy_(self._rec_in)
+        for u in self.layers:
+            u.y.copy_(u.ry)
+        self._at = "recorded"
+
+    # ---- loss --------------------------------------------------------------------------------
+    def _loss_setup(self, loss, outputs):
+        (self._dl,) = torch.autograd.grad(loss, outputs, create_graph=True, retain_graph=True)
+        self._ce = GGNOperator._closed_form_loss_hessian(self, _Node(_ce_node(loss)), outputs)
+        self._mse2 = None
+        if self._ce is None:
+            spec = loss_spec_of(loss, outputs)
+            if spec is None or spec["kind"] != "mse":
+                raise _Unsupported("the loss is neither a plain softmax cross-entropy nor a mean-squared error")
+            self._mse2 = 2.0 / float(outputs.numel()) if spec["reduction"] == "mean" else 2.0
+        elif self._ce[0].shape[1] > 1024:
+            raise _Unsupported("more than 1024 classes")
+        self._dl = None
+        self.loss_spec = None  # (no own loss head: no persistent session on this engine yet)
+
+    def gradient(self, out=None):
+        raise RuntimeError("the dense-stack engine has no gradient sweep (no session yet)")
+
+    def _not_here(what):  # noqa: N805  (the conv engines' entry points this kind inherits but does not have)
+        def refuse(self, *args, **kwargs):
+            raise RuntimeError(f"the dense-stack engine has no {what}: it serves GGN products of one batch in one "
+                               "process only (no session, no diag-EF preconditioner, no data parallelism)")
+        refuse.__name__ = what
+        return refuse
+
+    for _name in ("diag_ef", "set_batch", "set_targets", "refresh_weights", "refresh_frozen", "layer_signature",
+                  "phase_split", "local_phase_a", "local_phase_b"):
+        locals()[_name] = _not_here(_name)
+    del _name, _not_here
+
+    # ---- the product -------------------------------------------------------------------------
+    def local(self, v, out=None):
+        if out is None:
+            out = torch.empty(self.n, dtype=torch.float32, device=self.dev)
+        v = v.detach()
+        if not v.is_contiguous():
+            v = v.contiguous()
+        if v.dtype != torch.float32 or v.numel() != self.n or out.dtype != torch.float32 or out.numel() != self.n \
+                or not out.is_contiguous():
+            raise RuntimeError("dense-stack engine: vector and product must be contiguous float32 of the parameters' size")
+        lib, dev, rows, offs = _lib.load(), self.dev, self.rows, self._offs
+        vp, op = v.data_ptr(), out.data_ptr()
+        live = self.layers[self.dead_layers:]
+        t_x = None
+        for u in live:
+            v_w = _addr(vp, offs[u.pw]) if u.pw is not None else None
+            v_b = _addr(vp, offs[u.pb]) if u.pb is not None else None
+            if t_x is None and v_w is None:  # (only the bias of the first live layer carries a tangent)
+                slabs, splits = self._zero, 1
+            else:
+                self._tangent(u, t_x, v_w)
+                slabs, splits = u.tslabs, u.sT
+            self._act_tangent(u.ty, slabs, splits, u.tslabs.shape[1], v_b, u.y, u.act, u.c_out)
+            t_x = u.ty
+        stream = _lib.current_stream_ptr(dev)
+        if self._ce is not None:
+            _lib.check(lib.hf_softmax_ce_hvp(_ptr(self._g_last), _ptr(self._ce[0]), _ptr(t_x), float(self._ce[1]), rows,
+                                             self.logits.shape[1], _lib.HF_F32, stream), "hf_softmax_ce_hvp")
+        else:
+            torch.mul(t_x, self._mse2, out=self._g_last)
+        slabs, splits, stride = self._g_last, 1, 0
+        for u in reversed(live):
+            g_b = _addr(op, offs[u.pb]) if u.pb is not None else None
+            _lib.check(lib.hf_dense_act_adjoint(_ptr(u.ga), g_b, _ptr(slabs), splits, stride, _ptr(u.y), u.act, rows,
+                                                u.c_out, self.weight, _lib.HF_F32, stream), "hf_dense_act_adjoint")
+            if u.pw is not None:
+                _lib.check(lib.hf_dense_wgrad(_addr(op, offs[u.pw]), _ptr(u.ga), _ptr(u.x), rows, u.c_in, u.c_out,
+                                              self.weight, _lib.HF_F32, stream), "hf_dense_wgrad")
+            if not u.first_live:
+                _lib.check(lib.hf_dense_dgrad_slabs(_ptr(u.dslabs), _ptr(u.ga), _ptr(u.lin.weight), rows, u.c_in,
+                                                    u.c_out, u.sD, u.dslabs.shape[1], _lib.HF_F32, stream),
+                           "hf_dense_dgrad_slabs")
+                slabs, splits, stride = u.dslabs, u.sD, u.dslabs.shape[1]
+        return out
+
+    # ---- one process only ----------------------------------------------------------------------
+    @property
+    def reduce_bytes(self):
+        return 4 * self.n
+
+    def reduce(self, t, group=None):
+        return t

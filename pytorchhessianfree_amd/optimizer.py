@@ -388,6 +388,12 @@ class HessianFree(_Accumulation, _SessionSteps, torch.optim.Optimizer):
                 decline = self._session_decline if self.graph_matvec and not user_mvp and not user_grad else None
                 if holder["why"] and not decline:
                     decline = "; ".join(dict.fromkeys(holder["why"]))
+                elif decline:
+                    # (the dense-stack kind has no session, so the session never looked at the model with it: what the
+                    # per-step build found -- a layer, a batch size -- belongs next to "no session yet")
+                    extra = [w for w in dict.fromkeys(holder["why"]) if w.startswith("DenseStackEngine:") and w not in decline]
+                    if extra:
+                        decline = "; ".join([decline] + extra)
                 self._note_path("step", path, decline)
         return mvp, grad, init_loss, sess
 

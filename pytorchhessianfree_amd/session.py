@@ -183,7 +183,7 @@ class EngineSession(_TwoPhaseProduct, _Session):
 
         def builder():
             holder["eng"] = FusedGGNEngine.try_build(loss, outputs, list(params), weight=weight, group=group,
-                                                     hessian=hessian, why=why)
+                                                     hessian=hessian, why=why, need_session=True)
             return holder["eng"]
 
         sess = cls.__new__(cls)
@@ -203,6 +203,8 @@ class EngineSession(_TwoPhaseProduct, _Session):
             if eng is None or eng.loss_spec is None:
                 cur.wait_stream(self.stream)
                 raise _NoEngine("the fused engine does not cover this model" if eng is None else
+                                "the dense-stack engine has no session yet (its products run as engine-graphed)"
+                                if not getattr(eng, "supports_session", True) else
                                 "the engine's own forward pass does not reproduce this train-mode model, or the loss "
                                 "is neither a plain softmax cross-entropy nor a mean-squared error")
             self.op = self.engine = eng
@@ -480,7 +482,7 @@ class ChunkedEngineOperator(_TwoPhaseProduct, CapturedOperator):
         cur = self._enter_capture()
         with torch.cuda.stream(self.stream):
             eng = builder()
-            if not isinstance(eng, FusedGGNEngine):
+            if not isinstance(eng, FusedGGNEngine) or not eng.supports_session:
                 raise TypeError("ChunkedEngineOperator needs the fused curvature engine")
             self.split = self.plan_phases(eng, tail_fraction)
             if self.split is None:

@@ -1,0 +1,103 @@
+// Host-only check of hf_dense.hip's planner and argument validators: no kernel is launched (accepted shapes only go
+// through hf_dense_plan; every launching call below must be refused before it reaches the device).  Build with the host
+// half of the translation unit instrumented and run on any machine, GPU or not:
+//
+//   hipcc --offload-arch=gfx950 -std=c++17 -Iinclude -Xarch_host -fsanitize=address,undefined \
+//       scripts/dense_plan_host_check.cpp pytorchhessianfree_amd/csrc/hf_dense.hip -o dense_plan_host_check
+//
+// Exit status 0 and no sanitizer report = pass.
+#include <cstdio>
+#include <cstdlib>
+
+#include "hf_pcg.h"
+
+static int failures = 0;
+#define EXPECT(cond)                                              \
+  do {                                                            \
+    if (!(cond)) {                                                \
+      std::printf("FAILED line %d: %s\n", __LINE__, #cond);       \
+      ++failures;                                                 \
+    }                                                             \
+  } while (0)
+
+static bool split_ok(long long len, int splits) {
+  if (splits < 1 || splits > 32) return false;
+  const long long per = (len + splits - 1) / splits, kper = (per + 31) / 32 * 32;
+  return (splits - 1) * kper < len;
+}
+
+int main() {
+  static const long long shapes[][3] = {{1, 1, 1},      {3, 7, 5},     {16, 10, 10},     {32, 5, 3},
+                                        {33, 65, 31},   {64, 128, 96}, {64, 260, 132},   {65, 64, 64},
+                                        {256, 36, 68},  {64, 3072, 4096}, {64, 4096, 3072}, {64, 3072, 100},
+                                        {17, 3072, 64}, {256, 1 << 20, 1}, {1, 1, 1 << 20}};
+  for (const auto& s : shapes) {
+    int st = -1, sd = -1;
+    EXPECT(hf_dense_plan(s[0], s[1], s[2], &st, &sd) == HF_OK);
+    EXPECT(split_ok(s[1], st) && split_ok(s[2], sd));
+  }
+  // every count the rule accepts or refuses, over reduction lengths around the 32-entry step
+  for (long long len : {1LL, 31LL, 32LL, 33LL, 64LL, 65LL, 260LL, 3072LL, 1LL << 20})
+    for (int sp = -1; sp <= 34; ++sp) {
+      float dummy[4] = {0, 0, 0, 0};
+      // refused counts must come back as HF_ERR_ARG; accepted ones are not launched here
+      if (!split_ok(len, sp)) {
+        EXPECT(hf_dense_tangent_slabs(dummy, dummy, dummy, dummy, dummy, 1, len, 1, 0, sp, 1 << 20, HF_F32, nullptr) ==
+               HF_ERR_ARG);
+        EXPECT(hf_dense_dgrad_slabs(dummy, dummy, dummy, 1, 1, len, sp, 1 << 20, HF_F32, nullptr) == HF_ERR_ARG);
+      }
+    }
+  float b[4] = {0, 0, 0, 0};
+  int st, sd;
+  static const long long bad[][3] = {{0, 4, 4}, {257, 4, 4}, {4, 0, 4}, {4, 4, 0}, {4, (1 << 20) + 1, 4},
+                                     {4, 4, (1 << 20) + 1}, {-1, 4, 4}, {4, -1, 4}, {4, 4, -1}};
+  for (const auto& s : bad) {
+    EXPECT(hf_dense_plan(s[0], s[1], s[2], &st, &sd) == HF_ERR_ARG);
+    EXPECT(hf_dense_tangent_slabs(b, b, b, b, b, s[0], s[1], s[2], 0, 1, 0, HF_F32, nullptr) == HF_ERR_ARG);
+    EXPECT(hf_dense_dgrad_slabs(b, b, b, s[0], s[1], s[2], 1, 0, HF_F32, nullptr) == HF_ERR_ARG);
+    EXPECT(hf_dense_wgrad(b, b, b, s[0], s[1], s[2], 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  }
+  EXPECT(hf_dense_plan(4, 4, 4, nullptr, &sd) == HF_ERR_ARG);
+  EXPECT(hf_dense_plan(4, 4, 4, &st, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_tangent_slabs(b, b, b, b, b, 4, 40, 4, 0, 1, 0, HF_F64, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_tangent_slabs(nullptr, b, b, b, b, 4, 40, 4, 0, 1, 0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_tangent_slabs(b, nullptr, b, b, nullptr, 4, 40, 4, 0, 1, 0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_tangent_slabs(b, b, b, nullptr, b, 4, 40, 4, 0, 1, 0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_tangent_slabs(b, b, nullptr, b, b, 4, 40, 4, 0, 1, 0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_tangent_slabs(b, b, b, b, b, 4, 40, 4, 39, 1, 0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_tangent_slabs(b, b, b, b, b, 4, 40, 4, 0, 2, 15, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_dgrad_slabs(b, b, b, 4, 4, 40, 1, 0, HF_F64, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_dgrad_slabs(nullptr, b, b, 4, 4, 40, 1, 0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_dgrad_slabs(b, nullptr, b, 4, 4, 40, 1, 0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_dgrad_slabs(b, b, nullptr, 4, 4, 40, 1, 0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_dgrad_slabs(b, b, b, 4, 4, 40, 2, 15, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_wgrad(b, b, b, 4, 4, 4, 1.0, HF_F64, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_wgrad(nullptr, b, b, 4, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_wgrad(b, nullptr, b, 4, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_wgrad(b, b, nullptr, 4, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_wgrad(b, b, b, 4, 4, 4, 0.0 / 0.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_tangent(nullptr, b, 1, 0, b, b, 1, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_tangent(b, nullptr, 1, 0, b, b, 1, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_tangent(b, b, 0, 0, b, b, 1, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_tangent(b, b, 33, 16, b, b, 1, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_tangent(b, b, 2, 15, b, b, 1, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_tangent(b, b, 1, 0, b, b, 3, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_tangent(b, b, 1, 0, b, b, -1, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_tangent(b, b, 1, 0, b, nullptr, 2, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_tangent(b, b, 1, 0, b, b, 1, 0, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_tangent(b, b, 1, 0, b, b, 1, 257, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_tangent(b, b, 1, 0, b, b, 1, 4, 0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_tangent(b, b, 1, 0, b, b, 1, 4, 4, HF_F64, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_adjoint(nullptr, b, b, 1, 0, b, 1, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_adjoint(b, b, nullptr, 1, 0, b, 1, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_adjoint(b, b, b, 0, 0, b, 1, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_adjoint(b, b, b, 2, 15, b, 1, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_adjoint(b, b, b, 1, 0, b, 3, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_adjoint(b, b, b, 1, 0, nullptr, 1, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_adjoint(b, b, b, 1, 0, b, 1, 257, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_adjoint(b, b, b, 1, 0, b, 1, 4, 0, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_adjoint(b, b, b, 1, 0, b, 1, 4, 4, 0.0 / 0.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_adjoint(b, b, b, 1, 0, b, 1, 4, 4, 1.0, HF_F64, nullptr) == HF_ERR_ARG);
+  std::printf(failures ? "%d check(s) failed\n" : "dense plan / validator host check: ok\n", failures);
+  return failures ? 1 : 0;
+}
