@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 14
+#define HF_ABI_VERSION 15
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -656,6 +656,19 @@ int hf_dense_dgrad_slabs(void* out_slabs, const void* g_a, const void* W, int64_
 /* W: out[o][i] = scale * sum_r g_a[r][o] x[r][i], written once (out = product vector + the weight's offset). */
 int hf_dense_wgrad(void* out, const void* g_a, const void* x, int64_t rows, int64_t c_in, int64_t c_out, double scale,
                    int dtype, void* stream);
+/* The diagonal of the empirical Fisher of one layer (Martens' preconditioner, preconditioners.py:11-105) without a
+ * per-sample gradient: the per-sample weight gradient is the outer product g_a[r][:] (x) x[r][:], so the sum of its
+ * squares over the batch is the weight-gradient GEMM on squared operands; g_a holds PER-SAMPLE cotangents.
+ *   hf_dense_sq_wgrad:  out[o][i] = scale * sum_r g_a[r][o]^2 x[r][i]^2, written once.  Contract, tiling and traffic
+ *                       of hf_dense_wgrad (one kernel body): each operand is squared after its load (one rounding
+ *                       each), then one fmaf chain over the rows in ascending order, then one multiplication by `scale`.
+ *   hf_dense_sq_colsum: out[j] = scale * sum_r g_a[r][j]^2  (the bias; g_a [rows, c]): rows in ascending order, the
+ *                       squares exact and their sum accumulated in fp64, rounded to fp32 once, then multiplied by
+ *                       `scale` rounded to fp32 -- the rule of hf_dense_act_adjoint's g_b_out.
+ * NULL pointers, dtype != HF_F32, dimensions outside the ranges above and a NaN `scale` are refused. */
+int hf_dense_sq_wgrad(void* out, const void* g_a, const void* x, int64_t rows, int64_t c_in, int64_t c_out, double scale,
+                      int dtype, void* stream);
+int hf_dense_sq_colsum(void* out, const void* g_a, int64_t rows, int64_t c, double scale, int dtype, void* stream);
 /* act: 0 identity, 1 relu, 2 tanh; y [rows, c] is the layer's OUTPUT (NULL allowed for identity); the factor act'(y)
  * is  y > 0  for relu (as hf_chan_affine's mask) and  1 - y*y  for tanh (y*y, 1 - ., s * .: three roundings).
  *   hf_dense_act_tangent: t_y[r][j] = (sum of slabs + v_b[j]) * act'(y[r][j])     (v_b: bias tangent, nullable)

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HF_PCG_LIB") or os.path.join(_HERE, "csrc", "libhfpcg.so")
 
 HF_F32, HF_F64 = 0, 1
-ABI_VERSION = 14
+ABI_VERSION = 15
 HF_ERR_ARG = -1  # hf_status of include/hf_pcg.h: null / negative / inconsistent argument
 HF_M_NONE, HF_M_DIAG, HF_M_EXTERNAL = 0, 1, 2
 REASONS = {
@@ -158,6 +158,8 @@ SIGNATURES = {
     "hf_dense_tangent_slabs": (c_int, [c_void_p] * 5 + [c_int64] * 4 + [c_int, c_int64, c_int, c_void_p]),
     "hf_dense_dgrad_slabs": (c_int, [c_void_p] * 3 + [c_int64] * 3 + [c_int, c_int64, c_int, c_void_p]),
     "hf_dense_wgrad": (c_int, [c_void_p] * 3 + [c_int64] * 3 + [c_double, c_int, c_void_p]),
+    "hf_dense_sq_wgrad": (c_int, [c_void_p] * 3 + [c_int64] * 3 + [c_double, c_int, c_void_p]),
+    "hf_dense_sq_colsum": (c_int, [c_void_p] * 2 + [c_int64] * 2 + [c_double, c_int, c_void_p]),
     "hf_dense_act_tangent": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_int64, c_int64,
                                      c_int, c_void_p]),
     "hf_dense_act_adjoint": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int64,

@@ -122,7 +122,8 @@ SWITCHES = {
     # name: (default, what the non-default value does, test that exercises it)
     "HF_ENGINE": ("1", "0: curvature products by the autograd operators (no fused engine)",
                   "tests/test_engine_gpu.py::test_engine_declines_what_it_does_not_know"),
-    "HF_DENSE_ENGINE": ("0", "1: prepared MLPs (Linear [ReLU | Tanh] ... Linear) take the dense-stack curvature engine",
+    "HF_DENSE_ENGINE": ("0", "1: prepared MLPs (Linear [ReLU | Tanh] ... Linear) take the dense-stack curvature engine "
+                        "(GGN products; the diagonal empirical Fisher of diag_EF_backpack)",
                         "tests/test_dense_engine_gpu.py::test_dense_engine_is_opt_in"),
     "HF_ENGINE_VERIFY": ("first", "always / never: the engine's first-use check against the autograd product",
                          "tests/test_engine_gpu.py::test_train_mode_prologue_form_variants_agree_and_state_is_independent_of_the_first_use_check"),

@@ -1,7 +1,8 @@
 // hf_dense.hip -- fully-connected layers inside the GGN product (the dense-stack curvature engine, engine/dense.py):
 // skinny fp32 GEMMs (batch rows <= 256) on __builtin_amdgcn_mfma_f32_32x32x2f32 that read the weight [c_out, c_in] and
 // the matching slice of the CG vector IN PLACE in the flat vectors -- no [W | v_W] copy, no transposed copy, no gather
-// afterwards -- plus the two elementwise passes between them.  fp32, wave64, no atomics; partial results of a split
+// afterwards -- plus the two elementwise passes between them, and the diagonal of the empirical Fisher of the same layers
+// (the weight-gradient GEMM on squared operands, a column sum of squares).  fp32, wave64, no atomics; partial results of a split
 // reduction leave as slabs that the consumer adds by the rule of hf_common.h::slab_sum; every kernel sums in one fixed
 // order, so two launches on the same operands agree bitwise.
 //
@@ -190,8 +191,9 @@ __global__ __launch_bounds__(BLOCK) void k_dense_dgrad(float* __restrict__ out, 
 // grid (ceil(c_in / 128), ceil(c_out / 128)); wave w owns output rows o0 + 32 w .. + 31 and 128 columns, lane column j
 // holding the four consecutive columns i0 + 4 j + u in accumulators u = 0..3 (one 16-byte store per output row where the
 // destination allows it).  The reduction runs over the batch rows in ascending order; `scale` multiplies the finished
-// sum (one more rounding).
-template <bool ALIGNED>
+// sum (one more rounding).  SQ: both operands are squared after the load (one rounding each) -- the diagonal of the
+// empirical Fisher of the layer's weight, sum_r (g_a[r][o] x[r][i])^2, without a per-sample gradient (hf_dense_sq_wgrad).
+template <bool ALIGNED, bool SQ>
 __global__ __launch_bounds__(BLOCK) void k_dense_wgrad(float* __restrict__ out, const float* __restrict__ g,
                                                        const float* __restrict__ x, int rows, int c_in, int c_out,
                                                        float scale) {
@@ -208,8 +210,13 @@ __global__ __launch_bounds__(BLOCK) void k_dense_wgrad(float* __restrict__ out, 
   for (int r0 = 0; r0 < rows; r0 += 2) {
     const int r = r0 + h;
     const bool r_ok = r < rows;
-    const float a = (r_ok && o_ok) ? g[(size_t)r * c_out + o] : 0.0f;
-    const Quad b4 = ld_quad<ALIGNED>(x + (size_t)(r_ok ? r : 0) * c_in, i0, c_in, r_ok);
+    float a = (r_ok && o_ok) ? g[(size_t)r * c_out + o] : 0.0f;
+    Quad b4 = ld_quad<ALIGNED>(x + (size_t)(r_ok ? r : 0) * c_in, i0, c_in, r_ok);
+    if (SQ) {
+      a *= a;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) b4.e[u] *= b4.e[u];
+    }
 #pragma unroll
     for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b4.e[u], acc[u], 0, 0, 0);
   }
@@ -275,6 +282,20 @@ __global__ __launch_bounds__(ADJ_BLOCK) void k_dense_act_adjoint(float* __restri
   if (gb) gb[col] = (float)sum * scale;
 }
 
+// out[col] = scale * sum_rows g_a^2 -- the rule of k_dense_act_adjoint's bias sum: one thread per column walks the rows in
+// order, the squares (exact in fp64) are summed in fp64, the sum is rounded to fp32 once, then multiplied by `scale`.
+__global__ __launch_bounds__(ADJ_BLOCK) void k_dense_sq_colsum(float* __restrict__ out, const float* __restrict__ ga,
+                                                               int rows, int c, float scale) {
+  const int col = blockIdx.x * ADJ_BLOCK + threadIdx.x;
+  if (col >= c) return;
+  double sum = 0.0;
+  for (int r = 0; r < rows; ++r) {
+    const double gv = (double)ga[(size_t)r * c + col];
+    sum += gv * gv;
+  }
+  out[col] = (float)sum * scale;
+}
+
 inline bool act_args_ok(const void* slabs, int splits, int64_t slab_stride, const void* y, int act, int64_t rows,
                         int64_t c, int dtype) {
   if (dtype != HF_F32 || !slabs) return false;
@@ -284,6 +305,26 @@ inline bool act_args_ok(const void* slabs, int splits, int64_t slab_stride, cons
   if (act < ACT_IDENTITY || act > ACT_TANH) return false;
   if (act != ACT_IDENTITY && !y) return false;
   return true;
+}
+
+// hf_dense_wgrad (SQ = false) and hf_dense_sq_wgrad (SQ = true): one validator, one launch
+template <bool SQ>
+int dense_wgrad_launch(void* out, const void* g_a, const void* x, int64_t rows, int64_t c_in, int64_t c_out, double scale,
+                       int dtype, void* stream) {
+  DensePlan p;
+  if (dense_plan(rows, c_in, c_out, &p) != HF_OK) return HF_ERR_ARG;
+  if (dtype != HF_F32 || !out || !g_a || !x) return HF_ERR_ARG;
+  if (!(scale == scale)) return HF_ERR_ARG;
+  const bool al = quad_ok(out, c_in) && quad_ok(x, c_in);
+  const dim3 grid((unsigned)((c_in + 127) / 128), (unsigned)((c_out + 127) / 128));
+  hipStream_t st = (hipStream_t)stream;
+  if (al)
+    k_dense_wgrad<true, SQ><<<grid, BLOCK, 0, st>>>((float*)out, (const float*)g_a, (const float*)x, (int)rows,
+                                                    (int)c_in, (int)c_out, (float)scale);
+  else
+    k_dense_wgrad<false, SQ><<<grid, BLOCK, 0, st>>>((float*)out, (const float*)g_a, (const float*)x, (int)rows,
+                                                     (int)c_in, (int)c_out, (float)scale);
+  return (int)hipGetLastError();
 }
 
 #define DENSE_MT_SWITCH(mt, CALL) \
@@ -372,19 +413,20 @@ int hf_dense_dgrad_slabs(void* out_slabs, const void* g_a, const void* W, int64_
 
 int hf_dense_wgrad(void* out, const void* g_a, const void* x, int64_t rows, int64_t c_in, int64_t c_out, double scale,
                    int dtype, void* stream) {
-  DensePlan p;
-  if (dense_plan(rows, c_in, c_out, &p) != HF_OK) return HF_ERR_ARG;
-  if (dtype != HF_F32 || !out || !g_a || !x) return HF_ERR_ARG;
+  return dense_wgrad_launch<false>(out, g_a, x, rows, c_in, c_out, scale, dtype, stream);
+}
+
+int hf_dense_sq_wgrad(void* out, const void* g_a, const void* x, int64_t rows, int64_t c_in, int64_t c_out, double scale,
+                      int dtype, void* stream) {
+  return dense_wgrad_launch<true>(out, g_a, x, rows, c_in, c_out, scale, dtype, stream);
+}
+
+int hf_dense_sq_colsum(void* out, const void* g_a, int64_t rows, int64_t c, double scale, int dtype, void* stream) {
+  if (!dense_dims_ok(rows, c, c)) return HF_ERR_ARG;
+  if (dtype != HF_F32 || !out || !g_a) return HF_ERR_ARG;
   if (!(scale == scale)) return HF_ERR_ARG;
-  const bool al = quad_ok(out, c_in) && quad_ok(x, c_in);
-  const dim3 grid((unsigned)((c_in + 127) / 128), (unsigned)((c_out + 127) / 128));
-  hipStream_t st = (hipStream_t)stream;
-  if (al)
-    k_dense_wgrad<true><<<grid, BLOCK, 0, st>>>((float*)out, (const float*)g_a, (const float*)x, (int)rows, (int)c_in,
-                                                (int)c_out, (float)scale);
-  else
-    k_dense_wgrad<false><<<grid, BLOCK, 0, st>>>((float*)out, (const float*)g_a, (const float*)x, (int)rows, (int)c_in,
-                                                 (int)c_out, (float)scale);
+  k_dense_sq_colsum<<<(unsigned)((c + ADJ_BLOCK - 1) / ADJ_BLOCK), ADJ_BLOCK, 0, (hipStream_t)stream>>>(
+      (float*)out, (const float*)g_a, (int)rows, (int)c, (float)scale);
   return (int)hipGetLastError();
 }
 

@@ -33,7 +33,11 @@ class DenseStackEngine(FusedGGNEngine):
     ``t_x W^T + x V^T`` (W and the vector's slice V read in place in the flat vectors) -> bias tangent and ``act'``;
     the loss Hessian on the output tangent; in reverse ``act'`` and the bias gradient -> the weight gradient, written
     straight into the product vector -> the data gradient.  5 launches per hidden layer, no gather launch, bitwise
-    repeatable.  GGN only; one process; no persistent session (``loss_spec`` stays ``None``)."""
+    repeatable.  GGN only; one process; no persistent session (``loss_spec`` stays ``None``).
+
+    ``diag_ef``: the diagonal of the empirical Fisher (Martens' preconditioner) of the same batch from ONE adjoint sweep
+    with per-sample cotangents -- per layer the weight-gradient GEMM on squared operands and a column sum of squares,
+    written straight into the flat vector: at most 4 launches per live layer, no per-sample gradient is formed."""
 
     mode = ("fused curvature engine (dense stack): own skinny MFMA GEMMs that read the weights and the vector in place "
             "(split reductions as slabs summed by the consumer kernel), bias / activation fused, 5 launches per hidden "
@@ -231,6 +235,15 @@ class DenseStackEngine(FusedGGNEngine):
             self._mse2 = 2.0 / float(outputs.numel()) if spec["reduction"] == "mean" else 2.0
         elif self._ce[0].shape[1] > 1024:
             raise _Unsupported("more than 1024 classes")
+        else:  # (no host read of the targets: a batch with an ignored target has failed the closed form's check)
+            spec = loss_spec_of(loss, outputs, check_values=False)
+        # diag_ef: the reduction of a PLAIN cross-entropy / MSE (None: no per-sample reading of this loss) and the
+        # per-sample cotangents at the logits -- a `mean` loss carries 1/N, `loss_function(model(x_i), t_i)` does not
+        self._reduction = spec["reduction"] if spec is not None and "quadratic" not in spec else None
+        self._g_ef = None
+        if self._reduction is not None:
+            per_sample = float(outputs.shape[0]) if self._reduction == "mean" else 1.0
+            self._g_ef = (self._dl.detach() * per_sample).contiguous()
         self._dl = None
         self.loss_spec = None  # (no own loss head: no persistent session on this engine yet)
 
@@ -240,11 +253,11 @@ class DenseStackEngine(FusedGGNEngine):
     def _not_here(what):  # noqa: N805  (the conv engines' entry points this kind inherits but does not have)
         def refuse(self, *args, **kwargs):
             raise RuntimeError(f"the dense-stack engine has no {what}: it serves GGN products of one batch in one "
-                               "process only (no session, no diag-EF preconditioner, no data parallelism)")
+                               "process only (no session, no data parallelism)")
         refuse.__name__ = what
         return refuse
 
-    for _name in ("diag_ef", "set_batch", "set_targets", "refresh_weights", "refresh_frozen", "layer_signature",
+    for _name in ("set_batch", "set_targets", "refresh_weights", "refresh_frozen", "layer_signature",
                   "phase_split", "local_phase_a", "local_phase_b"):
         locals()[_name] = _not_here(_name)
     del _name, _not_here
@@ -294,6 +307,47 @@ class DenseStackEngine(FusedGGNEngine):
                 slabs, splits, stride = u.dslabs, u.sD, u.dslabs.shape[1]
         return out
 
+    # ---- diagonal of the empirical Fisher ---------------------------------------------------------
+    def diag_ef(self, reduction="mean", out=None):
+        """``sum_i g_i^2`` (``sum``) / ``(1/N) sum_i g_i^2`` (``mean``) over the per-sample gradients ``g_i`` of the
+        engine's batch: the quantity of ``preconditioners.diag_EF_autograd`` / ``diag_EF_backpack``.  The per-sample
+        weight gradient of a ``Linear`` layer is the outer product ``g_a[r] (x) x[r]``, so the layer's entries are
+        ``sum_r g_a[r][o]^2 x[r][i]^2`` (``hf_dense_sq_wgrad``) and ``sum_r g_a[r][o]^2`` (``hf_dense_sq_colsum``) of ONE
+        adjoint sweep whose cotangents are the per-sample ones; the ``1/N`` of ``mean`` is the kernels' ``scale``.
+        Frozen parameters have no entry; the rank ``weight`` does not enter.  No allocation (given ``out``), no host
+        synchronisation: capturable on one stream."""
+        if reduction not in ("sum", "mean"):
+            raise ValueError(f"reduction {reduction} is not supported.")
+        if self._reduction is None:
+            raise RuntimeError("engine.diag_ef needs a plain softmax cross-entropy / MSE loss")
+        if self._reduction != reduction:
+            raise RuntimeError("engine.diag_ef: the loss's reduction differs from the requested one")
+        if self._at != "own":
+            raise RuntimeError("engine.diag_ef: the engine's buffers do not hold its own forward pass")
+        if out is None:
+            out = torch.empty(self.n, dtype=torch.float32, device=self.dev)
+        if out.dtype != torch.float32 or out.numel() != self.n or not out.is_contiguous() or out.device != self.dev:
+            raise RuntimeError("dense-stack engine: the diagonal must be contiguous float32 of the parameters' size")
+        lib, rows, offs, op = _lib.load(), self.rows, self._offs, out.data_ptr()
+        scale = 1.0 / rows if reduction == "mean" else 1.0
+        stream = _lib.current_stream_ptr(self.dev)
+        slabs, splits, stride = self._g_ef, 1, 0
+        for u in reversed(self.layers[self.dead_layers:]):
+            _lib.check(lib.hf_dense_act_adjoint(_ptr(u.ga), None, _ptr(slabs), splits, stride, _ptr(u.y), u.act, rows,
+                                                u.c_out, 1.0, _lib.HF_F32, stream), "hf_dense_act_adjoint")
+            if u.pw is not None:
+                _lib.check(lib.hf_dense_sq_wgrad(_addr(op, offs[u.pw]), _ptr(u.ga), _ptr(u.x), rows, u.c_in, u.c_out,
+                                                 scale, _lib.HF_F32, stream), "hf_dense_sq_wgrad")
+            if u.pb is not None:
+                _lib.check(lib.hf_dense_sq_colsum(_addr(op, offs[u.pb]), _ptr(u.ga), rows, u.c_out, scale, _lib.HF_F32,
+                                                  stream), "hf_dense_sq_colsum")
+            if not u.first_live:
+                _lib.check(lib.hf_dense_dgrad_slabs(_ptr(u.dslabs), _ptr(u.ga), _ptr(u.lin.weight), rows, u.c_in,
+                                                    u.c_out, u.sD, u.dslabs.shape[1], _lib.HF_F32, stream),
+                           "hf_dense_dgrad_slabs")
+                slabs, splits, stride = u.dslabs, u.sD, u.dslabs.shape[1]
+        return out
+
     # ---- one process only ----------------------------------------------------------------------
     @property
     def reduce_bytes(self):
@@ -301,3 +355,39 @@ class DenseStackEngine(FusedGGNEngine):
 
     def reduce(self, t, group=None):
         return t
+
+
+def diag_ef_of(model, loss_function, inputs, targets, reduction, why=None):
+    """The diagonal of the empirical Fisher of ``loss_function(model(inputs), targets)`` on the dense-stack engine, or
+    ``None`` (``why``, a list, receives the reason): the switch is unset, the tensors are not CUDA float32, the model
+    has a convolution or is no prepared MLP the engine covers, batch > 256, another loss.  Only this engine kind is
+    ever built from here."""
+    why = [] if why is None else why
+    if os.environ.get("HF_DENSE_ENGINE", "0") != "1":
+        why.append("the dense-stack engine is opt-in (set HF_DENSE_ENGINE=1)")
+        return None
+    if not (isinstance(inputs, torch.Tensor) and inputs.is_cuda and inputs.dtype == torch.float32):
+        why.append("the inputs are not a CUDA float32 tensor")
+        return None
+    params = [p for p in model.parameters() if p.requires_grad]
+    if not params or any(not p.is_cuda or p.dtype != torch.float32 for p in params):
+        why.append("the parameters are not CUDA float32 tensors")
+        return None
+    if any(isinstance(m, nn.Conv2d) for m in model.modules()):
+        why.append("a model with convolutions is no dense stack")
+        return None
+    outputs = model(inputs)
+    loss = loss_function(outputs, targets)
+    if not isinstance(outputs, torch.Tensor) or not isinstance(loss, torch.Tensor) or not loss.requires_grad:
+        why.append("the loss does not depend on the parameters")
+        return None
+    eng = DenseStackEngine.try_build(loss, outputs, params, why=why)
+    if eng is None:
+        return None
+    if eng._reduction is None:
+        why.append("DenseStackEngine: the loss has no per-sample reading (neither a plain cross-entropy nor an MSE)")
+        return None
+    if eng._reduction != reduction:  # (the caller's own construction answers, as with a conv engine's session)
+        why.append(f"DenseStackEngine: the loss's reduction ({eng._reduction}) differs from the requested one")
+        return None
+    return eng.diag_ef(reduction)

@@ -126,7 +126,9 @@ class _SessionSteps:
         (optimizer.py:928-952).  Unlike the reference, the result is returned.  With a persistent engine
         session for ``model`` (from the second ``step`` on) the diagonal comes from ONE adjoint sweep of the engine
         plus per-sample weight-gradient launches (``engine.diag_ef``) instead of one backward pass per sample
-        (``use_backpack=False``) / a batched per-sample-gradient pass (``True``): the same quantity."""
+        (``use_backpack=False``) / a batched per-sample-gradient pass (``True``): the same quantity.  Without a
+        session, ``use_backpack=True`` on a prepared MLP with ``HF_DENSE_ENGINE=1`` takes the dense-stack engine's
+        sweep (``preconditioners.diag_EF_backpack``)."""
         diag = self._engine_diag_ef(model, loss_func, inputs, targets, reduction)
         if diag is not None:
             from .preconditioners import diag_to_preconditioner

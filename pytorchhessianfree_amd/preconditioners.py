@@ -14,7 +14,9 @@ Differences in mechanism, not in result:
 * ``diag_EF_backpack`` keeps its name for drop-in compatibility but does not
   need BackPACK: the per-sample gradients come from one batched
   ``torch.func.vmap(grad)`` pass.  Like BackPACK's version it only sees the part
-  of the loss that flows through ``loss_function(model(x), t)``.
+  of the loss that flows through ``loss_function(model(x), t)``.  For a prepared
+  MLP with ``HF_DENSE_ENGINE=1`` no per-sample gradient is formed at all: the
+  dense-stack engine's ``diag_ef`` (own kernels, one adjoint sweep) answers.
 """
 
 import torch
@@ -55,10 +57,22 @@ def diag_EF_autograd(model, loss_function, inputs, targets, reduction):
     return diag
 
 
-def diag_EF_backpack(model, loss_function, inputs, targets, reduction):
+def diag_EF_backpack(model, loss_function, inputs, targets, reduction, why=None):
     """Same quantity from ONE batched per-sample-gradient pass (the role BackPACK's
-    ``SumGradSquared`` plays in preconditioners.py:11-60)."""
+    ``SumGradSquared`` plays in preconditioners.py:11-60).  A prepared MLP with ``HF_DENSE_ENGINE=1``
+    takes the dense-stack engine's closed form instead (``engine.dense.diag_ef_of``: one adjoint sweep,
+    no per-sample gradient); ``why`` (a list) receives the reason whenever it does not."""
     _check_reduction(reduction)
+    from .engine.dense import diag_ef_of
+
+    diag = diag_ef_of(model, loss_function, inputs, targets, reduction, why=why)
+    if diag is not None:
+        return diag
+    return _diag_EF_vmap(model, loss_function, inputs, targets, reduction)
+
+
+def _diag_EF_vmap(model, loss_function, inputs, targets, reduction):
+    """``diag_EF_backpack`` by ``torch.func.vmap(grad)``: materialises the per-sample gradients."""
     from torch.func import functional_call, grad, vmap
 
     names, params = [], []

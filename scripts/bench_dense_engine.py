@@ -7,7 +7,15 @@ the 1-GPU leg of BASELINE.json configs[4] as ``tests/test_optimizer_gpu.py::_mlp
 
 The operator is the one ``HessianFree(graph_matvec=True).step()`` hands to ``cg()`` (``HessianFree.linearise``); the
 timed region is ``--reps`` repetitions of ``--steps`` solves of ``--iters`` iterations (``tol = 0``: every solve runs
-all of them), each repetition timed on its own after ``--warmup`` untimed solves.  Prints one JSON line."""
+all of them), each repetition timed on its own after ``--warmup`` untimed solves.  Prints one JSON line.
+
+    python scripts/bench_dense_engine.py --diag-ef        # the diagonal empirical-Fisher preconditioner instead
+
+``--diag-ef``: wall time per call (after ``--warmup`` untimed calls) and ``torch.cuda.max_memory_allocated`` of the
+diagonal of the same model and batch by ``diag_EF_backpack`` with ``HF_DENSE_ENGINE=1`` on the prepared model (the
+dense-stack engine's sweep), ``diag_EF_backpack`` with the switch unset (the ``vmap`` per-sample gradients) and
+``diag_EF_autograd`` (one backward pass per sample) -- ``--reps`` JSON lines each, one child process per route so that
+no route sees another's cached blocks in its peak."""
 
 import argparse
 import json
@@ -33,8 +41,78 @@ def mlp25m(device):
     return net.to(device), x.to(device), t.to(device)
 
 
+DIAG_ROUTES = ("backpack_engine", "backpack_vmap", "autograd")
+
+
+def diag_ef_route(route, warmup, reps):
+    """``reps`` JSON lines for one route of the diagonal empirical Fisher (this process runs nothing else)."""
+    dev = torch.device("cuda")
+    model, x, t = mlp25m(dev)
+    if route == "backpack_engine":
+        os.environ["HF_DENSE_ENGINE"] = "1"
+    else:
+        os.environ.pop("HF_DENSE_ENGINE", None)
+    if route == "backpack_engine":  # (the other two routes run the stock model, as before this engine existed)
+        modelprep.prepare_model(model)
+    lossf = torch.nn.CrossEntropyLoss()
+    fn = hf.diag_EF_autograd if route == "autograd" else hf.diag_EF_backpack
+    why = []
+    if route != "autograd":
+        from pytorchhessianfree_amd.engine.dense import diag_ef_of
+
+        on_engine = diag_ef_of(model, lossf, x, t, "mean", why=why) is not None
+        assert on_engine == (route == "backpack_engine"), why
+
+    def call():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return fn(model, lossf, x, t, "mean")
+
+    for _ in range(warmup):
+        call()
+    n = sum(p.numel() for p in model.parameters())
+    sweep_ms = None
+    if route == "backpack_engine":  # the sweep alone on ONE engine (a call of the public route builds its own)
+        from pytorchhessianfree_amd.engine.dense import DenseStackEngine
+
+        o = model(x)
+        eng = DenseStackEngine.try_build(lossf(o, t), o, list(model.parameters()))
+        out = eng.diag_ef("mean")
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(20):
+            eng.diag_ef("mean", out=out)
+        torch.cuda.synchronize()
+        sweep_ms = round(1e3 * (time.perf_counter() - t0) / 20, 3)
+        del eng, out, o
+    for rep in range(reps):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        t0 = time.perf_counter()
+        d = call()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        print(json.dumps({
+            "bench": "dense_diag_ef_mlp25m", "route": route, "rep": rep, "n": n, "batch": int(x.shape[0]),
+            "ms_per_call": round(1e3 * dt, 3), "max_memory_allocated_mb": round(torch.cuda.max_memory_allocated() / 2**20, 1),
+            "allocated_before_mb": round(base / 2**20, 1), "engine_sweep_alone_ms": sweep_ms, "diag_max": float(d.max()), "declined": why,
+            "device": torch.cuda.get_device_name(0)}), flush=True)
+        del d
+
+
+def diag_ef_bench(args):
+    import subprocess
+
+    for route in DIAG_ROUTES:
+        subprocess.run([sys.executable, os.path.abspath(__file__), "--diag-ef-route", route, "--warmup", str(args.warmup),
+                        "--reps", str(args.reps)], check=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--diag-ef", action="store_true")
+    ap.add_argument("--diag-ef-route", choices=DIAG_ROUTES, default=None)
     ap.add_argument("--prepared", type=int, default=1)
     ap.add_argument("--iters", type=int, default=250)
     ap.add_argument("--steps", type=int, default=2)
@@ -42,6 +120,10 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--damping", type=float, default=1.0)
     args = ap.parse_args()
+    if args.diag_ef_route:
+        return diag_ef_route(args.diag_ef_route, args.warmup, args.reps)
+    if args.diag_ef:
+        return diag_ef_bench(args)
     dev = torch.device("cuda")
     model, x, t = mlp25m(dev)
     if args.prepared:

@@ -56,6 +56,9 @@ int main() {
     EXPECT(hf_dense_tangent_slabs(b, b, b, b, b, s[0], s[1], s[2], 0, 1, 0, HF_F32, nullptr) == HF_ERR_ARG);
     EXPECT(hf_dense_dgrad_slabs(b, b, b, s[0], s[1], s[2], 1, 0, HF_F32, nullptr) == HF_ERR_ARG);
     EXPECT(hf_dense_wgrad(b, b, b, s[0], s[1], s[2], 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+    EXPECT(hf_dense_sq_wgrad(b, b, b, s[0], s[1], s[2], 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+    if (s[1] == 4)  // (rows, c) = (s[0], s[2]): only where one of THOSE two is out of range
+      EXPECT(hf_dense_sq_colsum(b, b, s[0], s[2], 1.0, HF_F32, nullptr) == HF_ERR_ARG);
   }
   EXPECT(hf_dense_plan(4, 4, 4, nullptr, &sd) == HF_ERR_ARG);
   EXPECT(hf_dense_plan(4, 4, 4, &st, nullptr) == HF_ERR_ARG);
@@ -76,6 +79,15 @@ int main() {
   EXPECT(hf_dense_wgrad(b, nullptr, b, 4, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
   EXPECT(hf_dense_wgrad(b, b, nullptr, 4, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
   EXPECT(hf_dense_wgrad(b, b, b, 4, 4, 4, 0.0 / 0.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_sq_wgrad(b, b, b, 4, 4, 4, 1.0, HF_F64, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_sq_wgrad(nullptr, b, b, 4, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_sq_wgrad(b, nullptr, b, 4, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_sq_wgrad(b, b, nullptr, 4, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_sq_wgrad(b, b, b, 4, 4, 4, 0.0 / 0.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_sq_colsum(b, b, 4, 4, 1.0, HF_F64, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_sq_colsum(nullptr, b, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_sq_colsum(b, nullptr, 4, 4, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_sq_colsum(b, b, 4, 4, 0.0 / 0.0, HF_F32, nullptr) == HF_ERR_ARG);
   EXPECT(hf_dense_act_tangent(nullptr, b, 1, 0, b, b, 1, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
   EXPECT(hf_dense_act_tangent(b, nullptr, 1, 0, b, b, 1, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
   EXPECT(hf_dense_act_tangent(b, b, 0, 0, b, b, 1, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
