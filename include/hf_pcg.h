@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 16
+#define HF_ABI_VERSION 17
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -711,6 +711,35 @@ int hf_dense_dgrad2_slabs(void* out_slabs, const void* g_a, const void* W, const
 int hf_dense_act_adjoint2(void* g_a, void* g_b_out, const void* slabs, int splits, int64_t slab_stride, const void* y,
                           int act, const void* t_y, const void* h, int64_t rows, int64_t c, double scale, int dtype,
                           void* stream);
+
+/* The forward pass and the loss head of a dense stack on the engine's static buffers (what a persistent session replays
+ * for every step and every trial point).  Contracts of the neighbours: HF_F32 only, rows <= 256, 4-byte alignment
+ * suffices, ragged sizes, no atomics, bitwise repeatable; NULL operands, sizes outside the ranges, an unknown `act` /
+ * `kind`, a bad split count or stride, a NaN scale and another dtype are refused with HF_ERR_ARG before any launch.
+ *   hf_dense_act_forward: y[r][j] = act(sum of slabs + b[j])  (b nullable).  The slab sum is hf_dense_act_tangent's:
+ *                         slab 0, then slabs 1 .. n-1 in split order, then the bias (one rounding each).  act: 0 the
+ *                         sum itself, 1  s <= 0 ? +0 : s  (max(s, 0); -0 becomes +0, a NaN stays a NaN as in torch.relu), 2  tanhf(s).
+ *                         One launch.
+ *   hf_dense_loss_head:   the loss of logits [rows, c] against `targets`; at most two launches, no host read.  Writes
+ *                         dl = d * scale_g and dl_ps = d * scale_ps (nullable) with d the rounded difference below --
+ *                         subtraction, rounding, product, rounding: never one fused multiply-add --, the loss value
+ *                         (one float) and `flag` (one int32, by an ordinary store).  `work`: 512 doubles of scratch,
+ *                         8-byte aligned (as int64 targets must be).
+ *     kind 0, softmax cross-entropy (c <= 1024; targets int64 class indices [rows]): per row m = max_j x[j],
+ *       e[j] = expf(x[j] - m), S = sum_j e[j] in fp64 (a fixed tree), p[j] = e[j] / (float)S (written to `p`),
+ *       d[j] = p[j] - (j == t ? 1 : 0).  The row's loss term is log(S) - (x[t] - m) in fp64 (= -log p[t] without the
+ *       rounding of p); loss = (float)(coef * sum_r term_r), the rows added in ascending order in fp64 (coef: 1 for
+ *       `sum`, 1 / rows for `mean`).  A target outside [0, c) sets the flag; its row has no one in the one-hot and adds
+ *       nothing to the loss.
+ *     kind 1, mean-squared error (c <= 2^20; targets float [rows, c]; p is not touched): d = x - t,
+ *       loss = (float)(sum d*d) * (float)coef -- the squares are exact in fp64 and are added in fp64 in a fixed order
+ *       (per thread ascending, a fixed tree per workgroup, the workgroups ascending), rounded to fp32 once, then
+ *       multiplied by coef rounded to fp32.  The flag is written as 0. */
+int hf_dense_act_forward(void* y, const void* slabs, int splits, int64_t slab_stride, const void* b, int act,
+                         int64_t rows, int64_t c, int dtype, void* stream);
+int hf_dense_loss_head(int kind, const void* logits, const void* targets, void* p, void* dl, void* dl_ps, void* loss,
+                       void* flag, void* work, double scale_g, double scale_ps, double coef, int64_t rows, int64_t c,
+                       int dtype, void* stream);
 
 /* ---- RCCL (resolved at run time from the already-loaded librccl) ----------- */
 typedef struct hf_comm hf_comm_t;

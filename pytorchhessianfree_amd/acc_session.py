@@ -158,7 +158,7 @@ class AccumulatedSession(_Session):
                     else:
                         # (group=None: the ranks' sum is taken once, after the chunks' sum)
                         eng = FusedGGNEngine.try_build(loss, out, params, weight=1.0, group=None, hessian=hessian,
-                                                       why=self._why, need_session=True)
+                                                       why=self._why, need_session=True, for_acc=True)
                 if eng is None or eng.loss_spec is None:
                     cur.wait_stream(self.stream)
                     raise _NoEngine("the fused engine does not cover this model / loss")

@@ -128,6 +128,10 @@ SWITCHES = {
     "HF_DENSE_HESSIAN": ("0", "1: with HF_DENSE_ENGINE=1, curvature_opt='hessian' on a prepared MLP takes the dense-stack "
                          "engine's Hessian products (forward over reverse on its own kernels) instead of double backward",
                          "tests/test_dense_hess_engine_gpu.py::test_hessian_switch_gates_try_build"),
+    "HF_DENSE_SESSION": ("0", "1: with HF_DENSE_ENGINE=1, step() on a prepared MLP with a plain cross-entropy / MSE loss "
+                         "runs on a persistent session of the dense-stack engine (forward pass, loss head, gradient "
+                         "and trial losses as graph replays) instead of engine-graphed",
+                         "tests/test_dense_session_engine_gpu.py::test_switch_and_declines"),
     "HF_ENGINE_VERIFY": ("first", "always / never: the engine's first-use check against the autograd product",
                          "tests/test_engine_gpu.py::test_train_mode_prologue_form_variants_agree_and_state_is_independent_of_the_first_use_check"),
     "HF_ENGINE_DEBUG": ("", "1: say why a model was not taken by the engine",

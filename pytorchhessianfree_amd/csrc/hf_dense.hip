@@ -4,7 +4,9 @@
 // afterwards -- plus the two elementwise passes between them, the diagonal of the empirical Fisher of the same layers
 // (the weight-gradient GEMM on squared operands, a column sum of squares), and the second-order adjoint sweep of the
 // Hessian product (forward over reverse: the two-term forms hf_dense_wgrad2 / hf_dense_dgrad2_slabs of the W and D GEMMs
-// and the tanh curvature term of hf_dense_act_adjoint2 -- each the body of its sibling under a template flag).
+// and the tanh curvature term of hf_dense_act_adjoint2 -- each the body of its sibling under a template flag), and what a
+// persistent session replays per step and per trial point: the forward pass's slab sum + bias + activation
+// (hf_dense_act_forward) and the loss head on the logits (hf_dense_loss_head: softmax cross-entropy or mean-squared error).
 // fp32, wave64, no atomics; partial results of a split
 // reduction leave as slabs that the consumer adds by the rule of hf_common.h::slab_sum; every kernel sums in one fixed
 // order, so two launches on the same operands agree bitwise.
@@ -439,6 +441,136 @@ int dense_dgrad_launch(void* out_slabs, const void* g_a, const void* W, const vo
   return (int)hipGetLastError();
 }
 
+// ---- forward pass of a layer: y = act(sum of slabs + b[col]) ------------------------------------------------------
+// The slab sum and the bias addition are k_dense_act_tangent's; then relu  s <= 0 ? +0 : s  (a NaN stays a NaN, as in
+// ATen's relu: a trial point whose hidden layer is NaN must not report a finite loss) or  tanhf(s).
+__global__ __launch_bounds__(BLOCK) void k_dense_act_forward(float* __restrict__ y, const float* __restrict__ slabs,
+                                                             int splits, long long stride, const float* __restrict__ b,
+                                                             int act, int total, int c) {
+  const int idx = blockIdx.x * BLOCK + threadIdx.x;
+  if (idx >= total) return;
+  float s = slab_sum<4>(slabs[idx], slabs, idx, splits, stride);
+  if (b) s += b[idx % c];
+  if (act == ACT_RELU) s = s <= 0.0f ? 0.0f : s;
+  if (act == ACT_TANH) s = tanhf(s);
+  y[idx] = s;
+}
+
+// ---- the loss head on logits [rows, c] --------------------------------------------------------------------------------
+enum { LOSS_CE = 0, LOSS_MSE = 1 };
+constexpr int LOSS_CE_MAX_C = 1024;          // 4 columns per thread of one workgroup
+constexpr int LOSS_WORK_DOUBLES = 512;       // the workspace: row terms + row marks (ce), block partials (mse)
+
+// max over the workgroup, the same value in every thread
+__device__ __forceinline__ float block_max(float v, float* lds /*WAVES*/) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) lds[wave] = v;
+  __syncthreads();
+  float m = lds[0];
+#pragma unroll
+  for (int w = 1; w < WAVES; ++w) m = fmaxf(m, lds[w]);
+  __syncthreads();
+  return m;
+}
+
+// One workgroup per row: m = row maximum; e = expf(x - m); S = sum of the e in fp64 (per thread its columns ascending,
+// then the fixed tree of block_allreduce); p = e / (float)S; d = p - onehot (rounded), dl = d * scale_g (rounded),
+// dl_ps = d * scale_ps (rounded).  The row's loss term log(S) - (x[t] - m) in fp64 goes to work[r], its mark (target
+// outside [0, c): no one in onehot, term 0) to work[rows + r].
+__global__ __launch_bounds__(BLOCK) void k_dense_ce_rows(const float* __restrict__ logits,
+                                                         const long long* __restrict__ targets, float* __restrict__ p,
+                                                         float* __restrict__ dl, float* __restrict__ dl_ps,
+                                                         double* __restrict__ work, float scale_g, float scale_ps,
+                                                         int rows, int c) {
+  __shared__ float lds_m[WAVES];
+  __shared__ double lds_s[WAVES];
+  const int r = blockIdx.x;
+  const float* x = logits + (size_t)r * c;
+  float xv[4], m = -INFINITY;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int col = threadIdx.x + BLOCK * u;
+    xv[u] = col < c ? x[col] : -INFINITY;
+    m = fmaxf(m, xv[u]);
+  }
+  m = block_max(m, lds_m);
+  float e[4];
+  double part[1] = {0.0};
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int col = threadIdx.x + BLOCK * u;
+    e[u] = col < c ? expf(xv[u] - m) : 0.0f;
+    part[0] += (double)e[u];
+  }
+  block_allreduce<1>(part, lds_s);
+  const float sf = (float)part[0];
+  const long long t = targets[r];
+  const bool ok = t >= 0 && t < (long long)c;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int col = threadIdx.x + BLOCK * u;
+    if (col >= c) continue;
+    const size_t idx = (size_t)r * c + col;
+    const float pv = e[u] / sf;
+    const float d = pv - ((ok && (long long)col == t) ? 1.0f : 0.0f);
+    p[idx] = pv;
+    dl[idx] = d * scale_g;
+    if (dl_ps) dl_ps[idx] = d * scale_ps;
+  }
+  if (threadIdx.x == 0) {
+    work[r] = ok ? log(part[0]) - ((double)x[t] - (double)m) : 0.0;
+    work[rows + r] = ok ? 0.0 : 1.0;
+  }
+}
+
+// d = out - t (rounded), dl = d * scale_g, dl_ps = d * scale_ps; the squares d*d (exact in fp64) are summed in fp64: per
+// thread over its grid-stride elements in ascending order, then the fixed tree of block_allreduce -> work[block].
+__global__ __launch_bounds__(BLOCK) void k_dense_mse_part(const float* __restrict__ out, const float* __restrict__ tg,
+                                                          float* __restrict__ dl, float* __restrict__ dl_ps,
+                                                          double* __restrict__ work, float scale_g, float scale_ps,
+                                                          long long total) {
+  __shared__ double lds_s[WAVES];
+  double part[1] = {0.0};
+  const long long step = (long long)gridDim.x * BLOCK;
+  for (long long idx = (long long)blockIdx.x * BLOCK + threadIdx.x; idx < total; idx += step) {
+    const float d = out[idx] - tg[idx];
+    dl[idx] = d * scale_g;
+    if (dl_ps) dl_ps[idx] = d * scale_ps;
+    part[0] += (double)d * (double)d;
+  }
+  block_allreduce<1>(part, lds_s);
+  if (threadIdx.x == 0) work[blockIdx.x] = part[0];
+}
+
+// The loss value and the flag: one thread adds work[0 .. n-1] in ascending order in fp64.  ce: loss = (float)(sum * coef),
+// flag = some row mark work[n .. 2n-1] is set; mse: loss = (float)sum * (float)coef, flag = 0.
+__global__ __launch_bounds__(BLOCK) void k_dense_loss_finish(const double* __restrict__ work, int n, int kind, double coef,
+                                                             float* __restrict__ loss, int* __restrict__ flag) {
+  __shared__ double terms[LOSS_WORK_DOUBLES];
+  const int have = kind == LOSS_CE ? 2 * n : n;
+  for (int i = threadIdx.x; i < have; i += BLOCK) terms[i] = work[i];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double sum = 0.0;
+  for (int i = 0; i < n; ++i) sum += terms[i];
+  int bad = 0;
+  if (kind == LOSS_CE) {
+    for (int i = n; i < 2 * n; ++i) bad |= terms[i] != 0.0;
+    *loss = (float)(sum * coef);
+  } else {
+    *loss = (float)sum * (float)coef;
+  }
+  *flag = bad;
+}
+
+// workgroups of the mse pass: 1024 elements each at first, at most LOSS_WORK_DOUBLES
+inline int mse_blocks(int64_t total) {
+  const int64_t g = (total + 4 * BLOCK - 1) / (4 * BLOCK);
+  return (int)(g < 1 ? 1 : g > LOSS_WORK_DOUBLES ? LOSS_WORK_DOUBLES : g);
+}
+
 }  // namespace
 
 extern "C" {
@@ -541,6 +673,42 @@ int hf_dense_act_adjoint2(void* g_a, void* g_b_out, const void* slabs, int split
                           void* stream) {
   return dense_act_adjoint_launch(true, g_a, g_b_out, slabs, splits, slab_stride, y, act, t_y, h, rows, c, scale, dtype,
                                   stream);
+}
+
+int hf_dense_act_forward(void* y, const void* slabs, int splits, int64_t slab_stride, const void* b, int act,
+                         int64_t rows, int64_t c, int dtype, void* stream) {
+  if (!y || !act_args_ok(slabs, splits, slab_stride, y, act, rows, c, dtype)) return HF_ERR_ARG;
+  const int total = (int)(rows * c);
+  k_dense_act_forward<<<(total + BLOCK - 1) / BLOCK, BLOCK, 0, (hipStream_t)stream>>>(
+      (float*)y, (const float*)slabs, splits, (long long)slab_stride, (const float*)b, act, total, (int)c);
+  return (int)hipGetLastError();
+}
+
+int hf_dense_loss_head(int kind, const void* logits, const void* targets, void* p, void* dl, void* dl_ps, void* loss,
+                       void* flag, void* work, double scale_g, double scale_ps, double coef, int64_t rows, int64_t c,
+                       int dtype, void* stream) {
+  if (dtype != HF_F32 || (kind != LOSS_CE && kind != LOSS_MSE)) return HF_ERR_ARG;
+  if (!logits || !targets || !dl || !loss || !flag || !work || (kind == LOSS_CE && !p)) return HF_ERR_ARG;
+  if ((((uintptr_t)work) & 7) != 0 || (kind == LOSS_CE && (((uintptr_t)targets) & 7) != 0)) return HF_ERR_ARG;
+  if (rows < 1 || rows > DENSE_MAX_ROWS || c < 1 || c > (kind == LOSS_CE ? (int64_t)LOSS_CE_MAX_C : DENSE_MAX_C))
+    return HF_ERR_ARG;
+  if (!(scale_g == scale_g) || !(scale_ps == scale_ps) || !(coef == coef)) return HF_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  int n;
+  if (kind == LOSS_CE) {
+    n = (int)rows;
+    k_dense_ce_rows<<<(unsigned)rows, BLOCK, 0, st>>>((const float*)logits, (const long long*)targets, (float*)p,
+                                                      (float*)dl, (float*)dl_ps, (double*)work, (float)scale_g,
+                                                      (float)scale_ps, (int)rows, (int)c);
+  } else {
+    n = mse_blocks(rows * c);
+    k_dense_mse_part<<<(unsigned)n, BLOCK, 0, st>>>((const float*)logits, (const float*)targets, (float*)dl,
+                                                    (float*)dl_ps, (double*)work, (float)scale_g, (float)scale_ps,
+                                                    (long long)(rows * c));
+  }
+  HF_HIP(hipGetLastError());
+  k_dense_loss_finish<<<1, BLOCK, 0, st>>>((const double*)work, n, kind, coef, (float*)loss, (int*)flag);
+  return (int)hipGetLastError();
 }
 
 }  // extern "C"

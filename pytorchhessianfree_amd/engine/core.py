@@ -59,11 +59,13 @@ class FusedGGNEngine(_Topology, _Buffers, _Forward, _TangentSweep, _AdjointSweep
 
     # ------------------------------------------------------------------------------------
     @classmethod
-    def try_build(cls, loss, outputs, params, weight=1.0, group=None, hessian=False, why=None, need_session=False):
+    def try_build(cls, loss, outputs, params, weight=1.0, group=None, hessian=False, why=None, need_session=False,
+                  for_acc=False):
         """The engine for the model that produced ``outputs``, or ``None``; ``why`` (a list) receives one line per
         reason it was not taken -- what ``HessianFree.path_report()`` and its one-time warning quote.
         ``need_session``: the caller (a persistent session) needs the engine's own forward pass, loss head and
-        gradient sweep; kinds without them are not built."""
+        gradient sweep; kinds without them are not built.  ``for_acc``: the caller is ``acc_step``'s accumulated session
+        (one engine per data chunk); kinds that serve ``step()`` sessions only (``acc_decline``) are not built."""
         why = [] if why is None else why
         if os.environ.get("HF_ENGINE", "1") == "0":
             why.append("the fused engine is switched off (HF_ENGINE=0)")
@@ -87,6 +89,8 @@ class FusedGGNEngine(_Topology, _Buffers, _Forward, _TangentSweep, _AdjointSweep
         for kind in kinds:
             # (asked of the CLASS, in the kinds' order: nothing is built that the caller could not use)
             reason = kind.unavailable(hessian, need_session)
+            if reason is None and for_acc:
+                reason = kind.acc_decline
             if reason is not None:
                 why.append(f"{kind.__name__}: {reason}")
                 continue
@@ -115,6 +119,8 @@ class FusedGGNEngine(_Topology, _Buffers, _Forward, _TangentSweep, _AdjointSweep
     # (hf_bn_train_hessian_coeffs / _apply; the formulas stand in csrc/hf_bn.hip and DESIGN.md section 4.3).
     supports_hessian = True
     supports_session = True
+    supports_two_phase = True  # (phase_split / local_phase_a / local_phase_b: the chunked, overlapped all-reduce)
+    acc_decline = None         # why this kind does not serve acc_step's accumulated session, if it does not
 
     @classmethod
     def unavailable(cls, hessian, need_session):

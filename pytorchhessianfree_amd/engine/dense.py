@@ -9,7 +9,7 @@ from torch import nn
 
 from .. import _lib
 from ..curvature import GGNOperator, _Operator
-from .common import _Node, _P, _Unsupported, _ce_node, _ptr, _same, loss_spec_of
+from .common import _Node, _P, _Unsupported, _ce_node, _flat_view, _ptr, _same, loss_spec_of
 from .core import FusedGGNEngine
 
 _ACT = {None: 0, nn.ReLU: 1, nn.Tanh: 2}
@@ -33,7 +33,15 @@ class DenseStackEngine(FusedGGNEngine):
     ``t_x W^T + x V^T`` (W and the vector's slice V read in place in the flat vectors) -> bias tangent and ``act'``;
     the loss Hessian on the output tangent; in reverse ``act'`` and the bias gradient -> the weight gradient, written
     straight into the product vector -> the data gradient.  5 launches per hidden layer, no gather launch, bitwise
-    repeatable.  One process; no persistent session (``loss_spec`` stays ``None``).
+    repeatable.  One process.
+
+    Session mode (opt-in: ``HF_DENSE_SESSION=1``; a plain cross-entropy / MSE loss): ``loss_spec`` is set and the engine
+    has what ``session.EngineSession`` replays -- ``set_batch`` / ``set_targets`` (copies into static buffers), its own
+    forward pass (per layer the forward GEMM and ``hf_dense_act_forward``) ending in its own loss head
+    (``hf_dense_loss_head``: probabilities, ``d loss / d logits``, the per-sample cotangents of ``diag_ef``, the loss
+    value and the bad-target flag, at most two launches) and ``gradient()`` in GGN mode too.  The kernels read every
+    weight in place, trainable or frozen, so there is nothing to refresh per parameter point.  Without the switch
+    ``loss_spec`` stays ``None`` and ``step()`` runs as ``engine-graphed``.
 
     ``hessian=True`` (opt-in: ``HF_DENSE_HESSIAN=1``): the Hessian product by forward over reverse on the same sweeps.
     ``gradient()`` keeps the first-order cotangents ``g_l = h_l * act'(a_l)`` of every live layer (and ``h_l`` of tanh
@@ -52,7 +60,12 @@ class DenseStackEngine(FusedGGNEngine):
             "layer, weight gradients written straight into the product; Hessian products by forward over reverse on "
             "the same sweeps")
     supports_hessian = True
-    supports_session = False
+    supports_session = False  # (per instance: True once the constructor has set up the session mode)
+    supports_two_phase = False
+    # acc_step builds one engine per data chunk and sums their products: not served here (asked before anything is built)
+    acc_decline = "the dense-stack engine serves step() sessions only"
+    session_decline = None    # why THIS engine, built with HF_DENSE_SESSION=1, has no session mode
+    has_weight_copies = False  # (weights are read in place: a session captures no refresh graph)
     max_rows = 256
 
     @classmethod
@@ -66,9 +79,16 @@ class DenseStackEngine(FusedGGNEngine):
         if hessian and os.environ.get("HF_DENSE_HESSIAN", "0") != "1":
             return "no Hessian products unless HF_DENSE_HESSIAN=1 (opt-in on top of HF_DENSE_ENGINE=1)"
         reason = super().unavailable(hessian, False)
-        if reason is None and need_session:
-            reason = "the dense-stack engine has no session yet"
+        # the session: opt-in of its own until a complete step() on it beats the engine-graphed one by more than the
+        # spread of the measurement (profiles/r13_dense_session.jsonl: 4.4-4.5 ms gained on
+        # 18.2 ms, 5.5-5.9 ms spread)
+        if reason is None and need_session and not cls._session_switch():
+            reason = "the dense-stack engine has no session yet (opt-in: set HF_DENSE_SESSION=1)"
         return reason
+
+    @staticmethod
+    def _session_switch():
+        return os.environ.get("HF_DENSE_SESSION", "0") == "1"
 
     def __init__(self, model, loss, outputs, params, weight, group, hessian=False):
         _Operator.__init__(self, params, weight, group)
@@ -98,6 +118,11 @@ class DenseStackEngine(FusedGGNEngine):
         for u in self.layers:  # the model's own activations were only needed up to here
             u.rx = u.ry = None
         self._rec_in = None
+        if self.loss_spec is not None:
+            self.outputs = None  # nothing of the step's autograd graph stays alive in the engine
+            from ..modelprep import release_records
+
+            release_records(model)
 
     # ---- topology ----------------------------------------------------------------------------
     def _layout(self, model):
@@ -174,13 +199,15 @@ class DenseStackEngine(FusedGGNEngine):
             raise _Unsupported("every layer is frozen")
         layers[self.dead_layers].first_live = True
         self.layers, self.model_ref = layers, model
-        self._rec_in = layers[0].rx
+        self._rec_in, self._in_shape = layers[0].rx, tuple(x_in.shape)
 
     def _allocate(self):
         f32, dev, rows, lib = torch.float32, self.dev, self.rows, _lib.load()
-        self.x_in = torch.empty((rows, self.layers[0].c_in), dtype=f32, device=dev)
-        self.x_in.copy_(self._rec_in)
-        x, widest = self.x_in, 0
+        # the input in the MODEL's shape (what a session's ``set_batch`` receives); the first layer reads it flattened
+        self.x_in = torch.empty(self._in_shape, dtype=f32, device=dev)
+        self._x2d = self.x_in.view(rows, self.layers[0].c_in)
+        self._x2d.copy_(self._rec_in)
+        x, widest = self._x2d, 0
         for u in self.layers:
             st, sd = _lib.c_int(), _lib.c_int()
             _lib.check(lib.hf_dense_plan(rows, u.c_in, u.c_out, st, sd), "hf_dense_plan")
@@ -192,6 +219,7 @@ class DenseStackEngine(FusedGGNEngine):
                 u.ty = torch.empty_like(u.y)
                 u.ga = torch.empty_like(u.y)
                 u.dslabs = None if u.first_live else torch.empty((u.sD, rows * u.c_in), dtype=f32, device=dev)
+                u.g1 = u.h1 = None
                 if self.hessian:  # first-order g_l = h_l * act'(a_l); h_l where the activation has a curvature
                     u.g1 = torch.empty_like(u.y)
                     u.h1 = torch.empty_like(u.y) if u.act == 2 else None
@@ -200,6 +228,9 @@ class DenseStackEngine(FusedGGNEngine):
         self.logits = self.layers[-1].y
         self._g_last = torch.empty_like(self.logits)
         self._zero = torch.zeros(rows * widest, dtype=f32, device=dev)  # (a tangent GEMM with no live term)
+        # the parameters as ONE flat vector, when they are consecutive views of one (the optimizer's arena): a session
+        # is valid only while they stay where its graphs read them
+        self._flat_params = _flat_view(self.params, self.n)
 
     # ---- launches ----------------------------------------------------------------------------
     def _tangent(self, u, t_x, v_w):
@@ -217,26 +248,31 @@ class DenseStackEngine(FusedGGNEngine):
     # ---- forward -----------------------------------------------------------------------------
     def forward_own(self, refresh=False, update_running=True):
         """The model's forward pass on the engine's static buffers: the tangent kernel with ``t_x = NULL, V = W`` is
-        the forward GEMM; bias by the slab-summing pass, the activation by ATen (once per step, not per product)."""
+        the forward GEMM; slab sum, bias and activation in one pass (``hf_dense_act_forward``); in session mode the loss
+        head.  Weights are read in place (``refresh``: nothing to do), there are no running statistics.  Two launches
+        per layer, no allocation, no host synchronisation: capturable."""
+        lib, stream = _lib.load(), _lib.current_stream_ptr(self.dev)
         for u in self.layers:
             w = u.lin.weight
-            _lib.check(_lib.load().hf_dense_tangent_slabs(
+            _lib.check(lib.hf_dense_tangent_slabs(
                 _ptr(u.tslabs), None, _ptr(u.x), _ptr(w), _ptr(w), self.rows, u.c_in, u.c_out, 0, u.sT,
-                u.tslabs.shape[1], _lib.HF_F32, _lib.current_stream_ptr(self.dev)), "hf_dense_tangent_slabs")
-            self._act_tangent(u.y, u.tslabs, u.sT, u.tslabs.shape[1], _ptr(u.lin.bias), None, 0, u.c_out)
-            if u.act == 1:
-                torch.relu_(u.y)
-            elif u.act == 2:
-                torch.tanh_(u.y)
+                u.tslabs.shape[1], _lib.HF_F32, stream), "hf_dense_tangent_slabs")
+            _lib.check(lib.hf_dense_act_forward(
+                _ptr(u.y), _ptr(u.tslabs), u.sT, u.tslabs.shape[1], _ptr(u.lin.bias), u.act, self.rows, u.c_out,
+                _lib.HF_F32, stream), "hf_dense_act_forward")
+        if getattr(self, "loss_spec", None) is not None:
+            self._loss_head()
         self._at = "own"
         return self.logits
 
     def _load_recorded(self, outputs):
         """The activations the MODEL's forward pass recorded (same ReLU decisions as the autograd operator the first
         product is compared with)."""
-        self.x_in.copy_(self._rec_in)
+        self._x2d.copy_(self._rec_in)
         for u in self.layers:
             u.y.copy_(u.ry)
+        if getattr(self, "loss_spec", None) is not None:
+            self._loss_head()
         self._at = "recorded"
 
     # ---- loss --------------------------------------------------------------------------------
@@ -262,13 +298,99 @@ class DenseStackEngine(FusedGGNEngine):
             self._g_ef = (self._dl.detach() * per_sample).contiguous()
         self._h_last = self._dl.detach().contiguous() if self.hessian else None  # d loss / d logits
         self._dl = None
-        self.loss_spec = None  # (no own loss head: no persistent session on this engine yet)
+        self.loss_spec = None  # (no own loss head without the session mode)
+        if not self._session_switch():
+            return
+        if self._reduction is None:
+            self.session_decline = ("the dense-stack engine's session takes a plain cross-entropy / MSE loss (no "
+                                    "quadratic regulariser)")
+            return
+        # session mode: the engine's own loss head fills static buffers at every forward pass
+        rows, c = self.logits.shape
+        mean = self._reduction == "mean"
+        if self._ce is not None:
+            self._kind, self._scale_g, self._coef = 0, float(self._ce[1]), (1.0 / rows if mean else 1.0)
+            self._p = torch.empty_like(self.logits)
+            self._ce = (self._p, self._ce[1])  # the static buffer hf_softmax_ce_hvp reads
+        else:
+            self._kind, self._scale_g, self._coef = 1, self._mse2, (1.0 / (rows * c) if mean else 1.0)
+            self._p = None
+        self._scale_ps = self._scale_g * (float(rows) if mean else 1.0)
+        self._targets = torch.empty_like(spec["targets"], memory_format=torch.contiguous_format)
+        self._targets.copy_(spec["targets"])
+        self._h_last, self._g_ef = torch.empty_like(self.logits), torch.empty_like(self.logits)
+        self.loss_buf = torch.zeros((), dtype=torch.float32, device=self.dev)
+        self.bad_targets = torch.zeros((), dtype=torch.int32, device=self.dev)
+        self._work = torch.empty(512, dtype=torch.float64, device=self.dev)
+        self.loss_spec, self.supports_session = spec, True
+        self._sig_slots = self._signature_slots()
+        self._sig_frozen = [t for u in self.layers for t, k in ((u.lin.weight, u.pw), (u.lin.bias, u.pb))
+                            if k is None and t is not None]
+        self._loss_head()
+
+    def _loss_head(self):
+        """Session mode: probabilities, ``d loss / d logits``, the per-sample cotangents, the loss value and the
+        bad-target flag of the current logits and targets -- one call of ``hf_dense_loss_head`` (two launches)."""
+        rows, c = self.logits.shape
+        _lib.check(_lib.load().hf_dense_loss_head(
+            self._kind, _ptr(self.logits), _ptr(self._targets), _ptr(self._p), _ptr(self._h_last), _ptr(self._g_ef),
+            _ptr(self.loss_buf), _ptr(self.bad_targets), _ptr(self._work), self._scale_g, self._scale_ps, self._coef,
+            rows, c, _lib.HF_F32, _lib.current_stream_ptr(self.dev)), "hf_dense_loss_head")
+
+    # ---- per batch / per parameter point (session mode) ----------------------------------------------------------
+    def _session_only(self, what):
+        if self.loss_spec is None:
+            raise RuntimeError(f"the dense-stack engine has no {what} without its session mode (HF_DENSE_SESSION=1, a "
+                               "plain cross-entropy / MSE loss): it then serves products of one batch only")
+
+    def set_batch(self, x, targets=None):
+        """A new input batch of the same shape (and its targets): copies into the static buffers."""
+        self._session_only("set_batch")
+        if tuple(x.shape) != tuple(self._in_shape):
+            raise RuntimeError("engine: input shape changed")
+        self.x_in.copy_(x)
+        if targets is not None:
+            self.set_targets(targets)
+
+    def set_targets(self, targets):
+        self._session_only("set_targets")
+        if targets.dtype.is_floating_point != (self._kind == 1) or tuple(targets.shape) != tuple(self._targets.shape):
+            raise RuntimeError("engine: the targets are not those of the loss the engine was built for")
+        self._targets.copy_(targets)
+
+    def refresh_weights(self, transposed=False):
+        """Nothing to do: the kernels read every weight in place, trainable or frozen."""
+        self._session_only("refresh_weights")
+
+    def refresh_frozen(self):
+        self._session_only("refresh_frozen")
+
+    def _signature_slots(self):
+        """Where the model holds its ``Linear`` / activation / Dropout modules -- ``(parent, name)`` per module, found
+        by ONE walk at construction: the per-step signature looks the slots up instead of walking the module tree."""
+        kinds = (nn.Linear, nn.ReLU, nn.Tanh, nn.Dropout, nn.Dropout1d, nn.Dropout2d, nn.Dropout3d, nn.AlphaDropout)
+        return [(parent, name) for parent in self.model_ref.modules() for name, child in parent._modules.items()
+                if isinstance(child, kinds)]
+
+    def layer_signature(self):
+        """What the captured graphs of a session bake in about the model besides shapes: the identities of the modules
+        the MODEL holds now where its ``Linear`` / activation / Dropout modules stood at construction (a swapped layer
+        is another stack), every Dropout's ``(training, p)``, the addresses of FROZEN weights and biases (kernel
+        arguments; the trainable ones are covered by the flat vector's address) and ``model.training``.  Compared
+        several times per step: a few dictionary look-ups, no walk over the module tree (a module ADDED elsewhere shows
+        up in the periodic re-verification against the model's own forward pass)."""
+        self._session_only("layer_signature")
+        now = [parent._modules.get(name) for parent, name in self._sig_slots]
+        mods = tuple((id(m), getattr(m, "training", None), getattr(m, "p", None)) for m in now)
+        frozen = tuple(t.data_ptr() for t in self._sig_frozen)
+        return mods, frozen, bool(self.model_ref.training)
 
     def gradient(self, out=None):
         """The first-order adjoint sweep from ``d loss / d logits`` at the activations the buffers hold: keeps ``g_l`` of
         every live layer (``h_l`` of tanh layers) for the Hessian products; with ``out`` also ``weight * d loss /
-        d params`` in the flat vector.  Existing kernels only; no allocation, no host synchronisation."""
-        if not self.hessian:
+        d params`` in the flat vector.  In session mode also for a GGN engine: its cotangents go through the products'
+        own ``ga`` buffers (nothing is kept).  Existing kernels only; no allocation, no host synchronisation."""
+        if not self.hessian and self.loss_spec is None:
             raise RuntimeError("the dense-stack engine keeps first-order cotangents in Hessian mode only")
         if out is not None and (out.dtype != torch.float32 or out.numel() != self.n or not out.is_contiguous()
                                 or out.device != self.dev):
@@ -281,14 +403,15 @@ class DenseStackEngine(FusedGGNEngine):
             if u.h1 is not None:  # h_l itself: the slab sum, no factor
                 _lib.check(lib.hf_dense_act_adjoint(_ptr(u.h1), None, _ptr(slabs), splits, stride, None, 0, rows, u.c_out,
                                                     1.0, _lib.HF_F32, stream), "hf_dense_act_adjoint")
+            g = u.g1 if u.g1 is not None else u.ga
             g_b = _addr(op, offs[u.pb]) if out is not None and u.pb is not None else None
-            _lib.check(lib.hf_dense_act_adjoint(_ptr(u.g1), g_b, _ptr(slabs), splits, stride, _ptr(u.y), u.act, rows,
+            _lib.check(lib.hf_dense_act_adjoint(_ptr(g), g_b, _ptr(slabs), splits, stride, _ptr(u.y), u.act, rows,
                                                 u.c_out, self.weight, _lib.HF_F32, stream), "hf_dense_act_adjoint")
             if out is not None and u.pw is not None:
-                _lib.check(lib.hf_dense_wgrad(_addr(op, offs[u.pw]), _ptr(u.g1), _ptr(u.x), rows, u.c_in, u.c_out,
+                _lib.check(lib.hf_dense_wgrad(_addr(op, offs[u.pw]), _ptr(g), _ptr(u.x), rows, u.c_in, u.c_out,
                                               self.weight, _lib.HF_F32, stream), "hf_dense_wgrad")
             if not u.first_live:
-                _lib.check(lib.hf_dense_dgrad_slabs(_ptr(u.dslabs), _ptr(u.g1), _ptr(u.lin.weight), rows, u.c_in,
+                _lib.check(lib.hf_dense_dgrad_slabs(_ptr(u.dslabs), _ptr(g), _ptr(u.lin.weight), rows, u.c_in,
                                                     u.c_out, u.sD, u.dslabs.shape[1], _lib.HF_F32, stream),
                            "hf_dense_dgrad_slabs")
                 slabs, splits, stride = u.dslabs, u.sD, u.dslabs.shape[1]
@@ -296,13 +419,12 @@ class DenseStackEngine(FusedGGNEngine):
 
     def _not_here(what):  # noqa: N805  (the conv engines' entry points this kind inherits but does not have)
         def refuse(self, *args, **kwargs):
-            raise RuntimeError(f"the dense-stack engine has no {what}: it serves GGN products of one batch in one "
-                               "process only (no session, no data parallelism)")
+            raise RuntimeError(f"the dense-stack engine has no {what}: it serves one process only (no data "
+                               "parallelism, no two-phase product)")
         refuse.__name__ = what
         return refuse
 
-    for _name in ("set_batch", "set_targets", "refresh_weights", "refresh_frozen", "layer_signature",
-                  "phase_split", "local_phase_a", "local_phase_b"):
+    for _name in ("phase_split", "local_phase_a", "local_phase_b"):
         locals()[_name] = _not_here(_name)
     del _name, _not_here
 

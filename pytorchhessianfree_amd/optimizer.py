@@ -389,8 +389,9 @@ class HessianFree(_Accumulation, _SessionSteps, torch.optim.Optimizer):
                 if holder["why"] and not decline:
                     decline = "; ".join(dict.fromkeys(holder["why"]))
                 elif decline:
-                    # (the dense-stack kind has no session, so the session never looked at the model with it: what the
-                    # per-step build found -- a layer, a batch size -- belongs next to "no session yet")
+                    # (without HF_DENSE_SESSION=1 the dense-stack kind has no session, so the session never looked at the
+                    # model with it: what the per-step build found -- a layer, a batch size -- belongs next to "no
+                    # session yet")
                     extra = [w for w in dict.fromkeys(holder["why"]) if w.startswith("DenseStackEngine:") and w not in decline]
                     if extra:
                         decline = "; ".join([decline] + extra)

@@ -190,7 +190,8 @@ class EngineSession(_TwoPhaseProduct, _Session):
         try:
             sess._build(builder, params)
         except _NoEngine as exc:
-            if not why:
+            # (an engine that was built but declines the session says so itself; else the kinds' own lines stand)
+            if not why or getattr(holder.get("eng"), "session_decline", None):
                 why.append(exc.reason)
             return None
         return sess
@@ -203,6 +204,8 @@ class EngineSession(_TwoPhaseProduct, _Session):
             if eng is None or eng.loss_spec is None:
                 cur.wait_stream(self.stream)
                 raise _NoEngine("the fused engine does not cover this model" if eng is None else
+                                f"{type(eng).__name__}: {eng.session_decline}"
+                                if getattr(eng, "session_decline", None) else
                                 "the dense-stack engine has no session yet (its products run as engine-graphed)"
                                 if not getattr(eng, "supports_session", True) else
                                 "the engine's own forward pass does not reproduce this train-mode model, or the loss "
@@ -224,7 +227,9 @@ class EngineSession(_TwoPhaseProduct, _Session):
                     self._phase_b()
         self.stream.synchronize()
         with torch.no_grad():
-            self.g_wT = self._capture(lambda: eng.refresh_weights(transposed=True))
+            # (an engine that reads its weights in place has nothing to capture here: an empty hipGraph warns)
+            self.g_wT = (self._capture(lambda: eng.refresh_weights(transposed=True))
+                         if getattr(eng, "has_weight_copies", True) else _NoGraph())
             self.g_fwd = self._capture(lambda: eng.forward_own(refresh=True))
             # train-mode BatchNorm: a forward pass moves the running statistics.  The step that CREATES the
             # session has already run the model itself (the stock layers moved them): its refresh replays a
@@ -482,7 +487,7 @@ class ChunkedEngineOperator(_TwoPhaseProduct, CapturedOperator):
         cur = self._enter_capture()
         with torch.cuda.stream(self.stream):
             eng = builder()
-            if not isinstance(eng, FusedGGNEngine) or not eng.supports_session:
+            if not isinstance(eng, FusedGGNEngine) or not eng.supports_session or not eng.supports_two_phase:
                 raise TypeError("ChunkedEngineOperator needs the fused curvature engine")
             self.split = self.plan_phases(eng, tail_fraction)
             if self.split is None:
@@ -503,6 +508,13 @@ class ChunkedEngineOperator(_TwoPhaseProduct, CapturedOperator):
 
     def raw_graph(self):  # (two graphs, no single product graph: cg() fuses K1-K3 only, under a group)
         return None
+
+
+class _NoGraph:
+    """Stands in for a captured graph where an engine has nothing to launch."""
+
+    def replay(self):
+        pass
 
 
 class _NoEngine(Exception):

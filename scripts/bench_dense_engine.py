@@ -17,7 +17,15 @@ all of them), each repetition timed on its own after ``--warmup`` untimed solves
 diagonal of the same model and batch by ``diag_EF_backpack`` with ``HF_DENSE_ENGINE=1`` on the prepared model (the
 dense-stack engine's sweep), ``diag_EF_backpack`` with the switch unset (the ``vmap`` per-sample gradients) and
 ``diag_EF_autograd`` (one backward pass per sample) -- ``--reps`` JSON lines each, one child process per route so that
-no route sees another's cached blocks in its peak."""
+no route sees another's cached blocks in its peak.
+
+    python scripts/bench_dense_engine.py --step-ms --session 1    # step() on the dense-stack engine's persistent session
+    python scripts/bench_dense_engine.py --step-ms --session 0    # step() as engine-graphed (the engine rebuilt per step)
+
+``--step-ms``: wall time per COMPLETE default ``HessianFree(graph_matvec=True).step()`` of the prepared model, a fresh
+batch per step: ``--reps`` repetitions of ``--steps`` steps, each repetition timed on its own after ``--warmup`` untimed
+repetitions; one process per leg.  With ``--session 1`` (``HF_DENSE_SESSION=1``) also the number of kernel launches of one
+replay of the session's forward graph."""
 
 import argparse
 import json
@@ -111,8 +119,75 @@ def diag_ef_bench(args):
                         "--reps", str(args.reps)], check=True)
 
 
+def step_ms(args):
+    """One JSON line: ms per complete step() of the prepared 25.5 M-parameter MLP, with or without the session."""
+    os.environ["HF_DENSE_ENGINE"] = "1"
+    if args.session:
+        os.environ["HF_DENSE_SESSION"] = "1"
+    else:
+        os.environ.pop("HF_DENSE_SESSION", None)
+    if args.curvature == "hessian":
+        os.environ["HF_DENSE_HESSIAN"] = "1"
+    dev = torch.device("cuda")
+    model, x, t = mlp25m(dev)
+    modelprep.prepare_model(model)
+    lossf = torch.nn.CrossEntropyLoss()
+    opt = hf.HessianFree(model.parameters(), curvature_opt=args.curvature, graph_matvec=True)
+    gen = torch.Generator(device=dev).manual_seed(2)
+    batch = {}
+
+    def forward():
+        o = model(batch["x"])
+        return lossf(o, batch["t"]), o
+
+    def steps():
+        finals = []
+        for _ in range(args.steps):
+            batch["x"] = torch.rand(x.shape, device=dev, generator=gen)
+            batch["t"] = torch.randint(0, 100, t.shape, device=dev, generator=gen)
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                finals.append(opt.step(forward))
+        return finals
+
+    for _ in range(args.warmup):
+        steps()
+    ms, paths = [], set()
+    for _ in range(args.reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        finals = steps()
+        torch.cuda.synchronize()
+        ms.append(1e3 * (time.perf_counter() - t0) / args.steps)
+        paths.add(opt.path_report()["step"]["path"])
+    fwd_launches = None
+    sess = getattr(opt, "_session", None)
+    if sess is not None:  # every entry point of the forward pass is one launch, the loss head two
+        from pytorchhessianfree_amd import _lib
+
+        calls, check = [], _lib.check
+        _lib.check = lambda rc, what: (calls.append(what), check(rc, what))[1]
+        try:
+            with torch.no_grad():
+                sess.engine.forward_own(refresh=True)
+        finally:
+            _lib.check = check
+        torch.cuda.synchronize()
+        fwd_launches = len(calls) + calls.count("hf_dense_loss_head")
+    mid = sorted(ms)[len(ms) // 2]
+    print(json.dumps({
+        "bench": "dense_step_ms_mlp25m", "curvature": args.curvature, "session_switch": bool(args.session),
+        "path": sorted(paths), "declined": opt.path_report()["step"]["declined"],
+        "n": sum(p.numel() for p in model.parameters()), "batch": int(x.shape[0]), "steps": args.steps,
+        "warmup": args.warmup, "reps": args.reps, "step_ms": [round(v, 2) for v in ms], "median_step_ms": round(mid, 2),
+        "spread_ms": round(max(ms) - min(ms), 2), "g_fwd_launches": fwd_launches, "final_loss": finals[-1],
+        "session_steps": getattr(sess, "steps", None), "device": torch.cuda.get_device_name(0)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--step-ms", action="store_true")
+    ap.add_argument("--session", type=int, default=1)
     ap.add_argument("--diag-ef", action="store_true")
     ap.add_argument("--diag-ef-route", choices=DIAG_ROUTES, default=None)
     ap.add_argument("--prepared", type=int, default=1)
@@ -127,6 +202,8 @@ def main():
         return diag_ef_route(args.diag_ef_route, args.warmup, args.reps)
     if args.diag_ef:
         return diag_ef_bench(args)
+    if args.step_ms:
+        return step_ms(args)
     dev = torch.device("cuda")
     model, x, t = mlp25m(dev)
     if args.prepared:

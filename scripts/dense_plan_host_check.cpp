@@ -146,6 +146,46 @@ int main() {
   EXPECT(hf_dense_act_adjoint2(b, b, b, 1, 0, b, 2, b, b, 4, 0, 1.0, HF_F32, nullptr) == HF_ERR_ARG);
   EXPECT(hf_dense_act_adjoint2(b, b, b, 1, 0, b, 2, b, b, 4, 4, 0.0 / 0.0, HF_F32, nullptr) == HF_ERR_ARG);
   EXPECT(hf_dense_act_adjoint2(b, b, b, 1, 0, b, 2, b, b, 4, 4, 1.0, HF_F64, nullptr) == HF_ERR_ARG);
+  // the forward activation pass: each operand, the sizes, the split rule, the activation code, the dtype
+  EXPECT(hf_dense_act_forward(nullptr, b, 1, 0, b, 1, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_forward(b, nullptr, 1, 0, b, 1, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_forward(b, b, 0, 0, b, 1, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_forward(b, b, 33, 16, b, 1, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_forward(b, b, 2, 15, b, 1, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_forward(b, b, 1, 0, b, 3, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_forward(b, b, 1, 0, b, -1, 4, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_forward(b, b, 1, 0, b, 1, 0, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_forward(b, b, 1, 0, b, 1, 257, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_forward(b, b, 1, 0, b, 1, 4, 0, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_act_forward(b, b, 1, 0, b, 1, 4, 4, HF_F64, nullptr) == HF_ERR_ARG);
+  // the loss head, both kinds (0 cross-entropy, 1 mean-squared error): operands, sizes, kind, scales, dtype, workspace
+  alignas(8) double w[512];
+  long long tg[4] = {0, 0, 0, 0};
+  const double nan = 0.0 / 0.0;
+  for (int kind = 0; kind <= 1; ++kind) {
+    const void* t = kind == 0 ? (const void*)tg : (const void*)b;
+    EXPECT(hf_dense_loss_head(kind, nullptr, t, b, b, b, b, b, w, 1.0, 1.0, 1.0, 1, 4, HF_F32, nullptr) == HF_ERR_ARG);
+    EXPECT(hf_dense_loss_head(kind, b, nullptr, b, b, b, b, b, w, 1.0, 1.0, 1.0, 1, 4, HF_F32, nullptr) == HF_ERR_ARG);
+    EXPECT(hf_dense_loss_head(kind, b, t, b, nullptr, b, b, b, w, 1.0, 1.0, 1.0, 1, 4, HF_F32, nullptr) == HF_ERR_ARG);
+    EXPECT(hf_dense_loss_head(kind, b, t, b, b, b, nullptr, b, w, 1.0, 1.0, 1.0, 1, 4, HF_F32, nullptr) == HF_ERR_ARG);
+    EXPECT(hf_dense_loss_head(kind, b, t, b, b, b, b, nullptr, w, 1.0, 1.0, 1.0, 1, 4, HF_F32, nullptr) == HF_ERR_ARG);
+    EXPECT(hf_dense_loss_head(kind, b, t, b, b, b, b, b, nullptr, 1.0, 1.0, 1.0, 1, 4, HF_F32, nullptr) == HF_ERR_ARG);
+    EXPECT(hf_dense_loss_head(kind, b, t, b, b, b, b, b, (char*)w + 4, 1.0, 1.0, 1.0, 1, 4, HF_F32, nullptr) ==
+           HF_ERR_ARG);
+    EXPECT(hf_dense_loss_head(kind, b, t, b, b, b, b, b, w, 1.0, 1.0, 1.0, 0, 4, HF_F32, nullptr) == HF_ERR_ARG);
+    EXPECT(hf_dense_loss_head(kind, b, t, b, b, b, b, b, w, 1.0, 1.0, 1.0, 257, 4, HF_F32, nullptr) == HF_ERR_ARG);
+    EXPECT(hf_dense_loss_head(kind, b, t, b, b, b, b, b, w, 1.0, 1.0, 1.0, 1, 0, HF_F32, nullptr) == HF_ERR_ARG);
+    EXPECT(hf_dense_loss_head(kind, b, t, b, b, b, b, b, w, 1.0, 1.0, 1.0, 1, (1 << 20) + 1, HF_F32, nullptr) ==
+           HF_ERR_ARG);
+    EXPECT(hf_dense_loss_head(kind, b, t, b, b, b, b, b, w, nan, 1.0, 1.0, 1, 4, HF_F32, nullptr) == HF_ERR_ARG);
+    EXPECT(hf_dense_loss_head(kind, b, t, b, b, b, b, b, w, 1.0, nan, 1.0, 1, 4, HF_F32, nullptr) == HF_ERR_ARG);
+    EXPECT(hf_dense_loss_head(kind, b, t, b, b, b, b, b, w, 1.0, 1.0, nan, 1, 4, HF_F32, nullptr) == HF_ERR_ARG);
+    EXPECT(hf_dense_loss_head(kind, b, t, b, b, b, b, b, w, 1.0, 1.0, 1.0, 1, 4, HF_F64, nullptr) == HF_ERR_ARG);
+  }
+  EXPECT(hf_dense_loss_head(0, b, tg, nullptr, b, b, b, b, w, 1.0, 1.0, 1.0, 1, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_loss_head(0, b, tg, b, b, b, b, b, w, 1.0, 1.0, 1.0, 1, 1025, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_loss_head(2, b, tg, b, b, b, b, b, w, 1.0, 1.0, 1.0, 1, 4, HF_F32, nullptr) == HF_ERR_ARG);
+  EXPECT(hf_dense_loss_head(-1, b, tg, b, b, b, b, b, w, 1.0, 1.0, 1.0, 1, 4, HF_F32, nullptr) == HF_ERR_ARG);
   std::printf(failures ? "%d check(s) failed\n" : "dense plan / validator host check: ok\n", failures);
   return failures ? 1 : 0;
 }
