@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 17
+#define HF_ABI_VERSION 18
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -515,6 +515,27 @@ typedef struct hf_conv_problem {
   int64_t mat_ld;           /* see hf_conv2d_nhwc_slabs; 0 = dense */
 } hf_conv_problem;
 int hf_conv2d_nhwc_group_slabs(const hf_conv_problem* problems, int n_problems, int dtype, void* stream);
+/* What a launch of problem `p` WILL run: the answer of plan_problem(), the planner every launching entry point goes
+ * through, as plain numbers.  Host arithmetic only: the pointers of `p` are ignored and nothing is launched.
+ *   ticket_mode == 0: a slab-mode launch (hf_conv2d_nhwc_slabs and the merged forms); p->splits == 0 means "choose",
+ *                     as hf_conv2d_nhwc_plan does (towards target_blocks workgroups if > 0), p->splits > 0 is the
+ *                     caller's count, cut back to one that leaves no split without a step; ws_bytes / n_tickets unused.
+ *   ticket_mode != 0: a launch of hf_conv2d_nhwc with this workspace size, ticket count and target_blocks
+ *                     (hf_conv2d_nhwc_backward gives each half half of both).
+ * Refusals are the codes a launch of the same problem returns for its geometry (HF_ERR_ARG). */
+typedef struct hf_conv_plan_info {
+  int config;               /* tile configuration: 0 Small 64x64, 1 Big 128x128, 2 Big96 128x96, 3 Flat96 96x128 */
+  int scalar;               /* 1: element-wise gathers (a channel count or leading dimension not a multiple of 4) */
+  int ncls;                 /* residue classes a strided data gradient is enumerated by; 0: plain enumeration */
+  int cls_taps[4];          /* live taps of class i < ncls (0: the class writes zeros) */
+  int live_taps;            /* taps that meet data somewhere */
+  int tiles_m, tiles_n;     /* output tiles (classes: the row tiles of all classes) */
+  int steps;                /* reduction steps of one output tile (classes: of the class with most taps) */
+  int splits;               /* K-splits: each takes ceil(steps / splits) steps, the last ones what is left */
+  int64_t blocks;           /* workgroups = tiles_m * tiles_n * splits */
+} hf_conv_plan_info;
+int hf_conv2d_nhwc_plan_info(const hf_conv_problem* p, int ticket_mode, int64_t ws_bytes, int64_t n_tickets,
+                             int target_blocks, hf_conv_plan_info* out);
 /* Tangent convolutions in front of TRAIN-mode BatchNorm layers (optimizer.py:457-462 with a model in train mode,
  * examples/run_resnet18_mnist.py:19-35): hf_conv2d_nhwc_group_slabs for direction-0 problems whose epilogue ALSO
  * writes, per problem with part_1 != NULL, the per-channel partial sums of every (row tile, split)'s output tile,

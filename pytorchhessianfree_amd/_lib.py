@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HF_PCG_LIB") or os.path.join(_HERE, "csrc", "libhfpcg.so")
 
 HF_F32, HF_F64 = 0, 1
-ABI_VERSION = 17
+ABI_VERSION = 18
 HF_ERR_ARG = -1  # hf_status of include/hf_pcg.h: null / negative / inconsistent argument
 HF_M_NONE, HF_M_DIAG, HF_M_EXTERNAL = 0, 1, 2
 REASONS = {
@@ -122,6 +122,7 @@ SIGNATURES = {
                                     + [c_int, c_int, c_void_p]),
     "hf_conv2d_nhwc_group_slabs": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "hf_conv2d_nhwc_dw_slabs": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "hf_conv2d_nhwc_plan_info": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p]),
     "hf_chan_affine_pair": (c_int, [c_void_p, c_int, c_void_p]),
     "hf_chan_affine_bwd_pair": (c_int, [c_void_p, c_int, c_void_p]),
     "hf_conv2d_nhwc_backward_slabs": (c_int, [c_void_p] * 5 + [c_int64] * 11
@@ -576,6 +577,31 @@ def conv_plan(direction, n, h, w, c, k, r, s, stride, padding):
     if sp < 1:
         check(sp, "hf_conv2d_nhwc_plan")
     return sp
+
+
+class ConvPlanInfo(ctypes.Structure):
+    """``hf_conv_plan_info`` of include/hf_pcg.h."""
+
+    _fields_ = [("config", c_int), ("scalar", c_int), ("ncls", c_int), ("cls_taps", c_int * 4), ("live_taps", c_int),
+                ("tiles_m", c_int), ("tiles_n", c_int), ("steps", c_int), ("splits", c_int), ("blocks", c_int64)]
+
+
+def conv_plan_info(direction, n, h, w, c, k, r, s, stride, padding, splits=0, act_ld=0, mat_ld=0, out_c=0,
+                   tickets=None, target_blocks=0):
+    """What a launch of this geometry will run (``hf_conv2d_nhwc_plan_info``; host arithmetic, no GPU), as a dict of
+    the ``hf_conv_plan_info`` fields with ``cls_taps`` cut to ``ncls`` entries.  Slab mode with ``splits`` (0: the
+    planner chooses), or ticket mode with ``tickets = (workspace bytes, ticket counters)``."""
+    q = ConvProblem()
+    q.direction, q.n, q.h, q.w, q.c, q.k, q.r, q.s = int(direction), n, h, w, c, k, r, s
+    q.stride_h, q.stride_w, q.pad_h, q.pad_w = stride[0], stride[1], padding[0], padding[1]
+    q.act_ld, q.mat_ld, q.out_c, q.splits = act_ld, mat_ld, out_c, int(splits)
+    info = ConvPlanInfo()
+    ws_bytes, n_tickets = tickets if tickets is not None else (0, 0)
+    check(load().hf_conv2d_nhwc_plan_info(ctypes.byref(q), int(tickets is not None), ws_bytes, n_tickets,
+                                          int(target_blocks), ctypes.byref(info)), "hf_conv2d_nhwc_plan_info")
+    out = {name: getattr(info, name) for name, _ in ConvPlanInfo._fields_ if name != "cls_taps"}
+    out["cls_taps"] = tuple(info.cls_taps[:info.ncls])
+    return out
 
 
 def conv2d_nhwc_slabs(direction, out, act, mat, n, h, w, c, k, r, s, stride, padding, splits, act_ld=0, out_c=0,

@@ -1239,18 +1239,20 @@ int check_common(const hf_conv_problem& p, int64_t oh, int64_t ow, int dtype, co
 //   1. field ranges, the out_c rule included;  2. check_common (launches only);  3. setup;
 //   4. the planned split count is the caller's (slab-mode launches: ask hf_conv2d_nhwc_plan first);
 //   5. what the caller's launch form cannot run (`allow`);  6. apply_out_c.
-// `sc`: ticket mode.  PLAN_ONLY: no launch follows -- no pointers, no 2^31 limits, p.splits == 0, and `sc` (nullable)
-// only carries target_blocks.
+// `sc`: ticket mode.  PLAN_ONLY: no launch follows -- no pointers, no 2^31 limits, p.splits == 0 means "choose", and
+// `sc` (nullable) only carries target_blocks -- unless PLAN_TICKETS asks for the plan of a ticket-mode launch on the
+// sizes `sc` names (hf_conv2d_nhwc_plan_info).
 enum : unsigned {
   ALLOW_SCALAR = 1,  // the form has the element-wise gather variant (channel counts not multiples of 4)
   ALLOW_BIG = 2,     // ... the 128-wide tile configurations
   ALLOW_CLS = 4,     // ... the residue-class enumeration of strided data gradients
   ALLOW_ALL = 7,
   PLAN_ONLY = 8,
+  PLAN_TICKETS = 16,
 };
 
 int plan_problem(const hf_conv_problem& p, int dtype, const Scratch* sc, unsigned allow, ConvArgs& a, int64_t& blocks) {
-  const bool plan = allow & PLAN_ONLY, tickets = sc && !plan, slab_launch = !sc && !plan;
+  const bool plan = allow & PLAN_ONLY, tickets = sc && (!plan || (allow & PLAN_TICKETS)), slab_launch = !sc && !plan;
   if (p.direction < 0 || p.direction > 2 || (slab_launch && p.splits < 1) || p.slab_stride < 0 || p.mat_ld < 0)
     return HF_ERR_ARG;
   if (p.out_c < 0 || p.out_c > p.c || (p.out_c && p.direction != 2)) return HF_ERR_ARG;
@@ -1341,6 +1343,28 @@ int hf_conv2d_nhwc_plan(int direction, int64_t n, int64_t h, int64_t w, int64_t 
   int64_t blocks;
   const int rc = plan_problem(p, HF_F32, &sc, ALLOW_ALL | PLAN_ONLY, a, blocks);
   return rc ? rc : a.splits;
+}
+
+int hf_conv2d_nhwc_plan_info(const hf_conv_problem* p, int ticket_mode, int64_t ws_bytes, int64_t n_tickets,
+                             int target_blocks, hf_conv_plan_info* out) {
+  if (!p || !out || (ticket_mode && (ws_bytes < 0 || n_tickets < 0))) return HF_ERR_ARG;
+  const Scratch sc = {nullptr, ws_bytes, nullptr, n_tickets, target_blocks};
+  ConvArgs a;
+  int64_t blocks;
+  const int rc = plan_problem(*p, HF_F32, &sc, ALLOW_ALL | PLAN_ONLY | (ticket_mode ? PLAN_TICKETS : 0), a, blocks);
+  if (rc) return rc;
+  memset(out, 0, sizeof(*out));
+  out->config = a.big;
+  out->scalar = a.scalar;
+  out->ncls = a.ncls;
+  for (int i = 0; i < a.ncls; ++i) out->cls_taps[i] = a.cls_tap0[i + 1] - a.cls_tap0[i];
+  out->live_taps = a.ntaps;
+  out->tiles_m = a.tiles_m;
+  out->tiles_n = a.tiles_n;
+  out->steps = a.steps;
+  out->splits = a.splits;
+  out->blocks = blocks;
+  return HF_OK;
 }
 
 int hf_conv2d_nhwc_slabs(int direction, void* out, const void* act, const void* mat, int64_t n, int64_t h,
