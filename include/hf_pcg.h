@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 18
+#define HF_ABI_VERSION 19
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -77,6 +77,25 @@ const char* hf_error_string(int code);
 /* max_blocks: grid size of the vector kernels (0 = default: 2 per CU). */
 int hf_pcg_create(hf_pcg_t** out, int64_t n, int dtype, int max_blocks);
 int hf_pcg_destroy(hf_pcg_t* h);
+
+/* What the handle WILL launch, as plain numbers: filled by the functions the launches themselves use (the grid
+ * rule, the two non-temporal policies); host arithmetic, nothing is launched.  grid_init: k_init / k_init_external
+ * (unroll 1); grid_k2 is also k_dot_ry's grid and the number of partial sums K3 re-reduces; width: elements per
+ * 16-byte vector.  A kernel's tile is 256 * unroll * width elements. */
+typedef struct hf_pcg_plan {
+  int32_t grid_init, grid_k1, grid_k2, grid_k3;
+  int32_t grid_cap;                        /* partial-sum slots per sum */
+  int32_t unroll_k1, unroll_k2, unroll_k3;
+  int32_t width;
+  int32_t nt_k12, nt_k3;                   /* non-temporal streams of K1/K2 resp. K3: 0 / 1 */
+} hf_pcg_plan;
+int hf_pcg_plan_info(const hf_pcg_t* h, hf_pcg_plan* out);
+/* Non-temporal streams of K1/K2 (`k12`) and of K3 (`k3`): -1 = by vector length (the default: from 16 M resp.
+ * 64 M elements), 0 = off, 1 = on.  Stored in the handle; direct launches and hf_pcg_graph_* follow it.  Only
+ * before the handle's first hf_pcg_begin (HF_ERR_STATE afterwards: a graph built earlier must not go stale);
+ * HF_ERR_ARG for other values.  Both settings compute the same bits: only the cache policy of the loads and
+ * stores differs.  The solver's callers keep the default; the kernel tests reach every instantiation with it. */
+int hf_pcg_set_streaming(hf_pcg_t* h, int k12, int k3);
 
 /*
  * Begin a solve (cg.py:75-76, :177-192).  On entry `x` holds x0 (zeros when the

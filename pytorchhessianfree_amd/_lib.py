@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HF_PCG_LIB") or os.path.join(_HERE, "csrc", "libhfpcg.so")
 
 HF_F32, HF_F64 = 0, 1
-ABI_VERSION = 18
+ABI_VERSION = 19
 HF_ERR_ARG = -1  # hf_status of include/hf_pcg.h: null / negative / inconsistent argument
 HF_M_NONE, HF_M_DIAG, HF_M_EXTERNAL = 0, 1, 2
 REASONS = {
@@ -50,12 +50,21 @@ class Status(ctypes.Structure):
     ]
 
 
+class PcgPlan(ctypes.Structure):
+    """``hf_pcg_plan`` of include/hf_pcg.h."""
+
+    _fields_ = [(nm, ctypes.c_int32) for nm in ("grid_init", "grid_k1", "grid_k2", "grid_k3", "grid_cap", "unroll_k1",
+                                                "unroll_k2", "unroll_k3", "width", "nt_k12", "nt_k3")]
+
+
 # name -> (restype, argtypes); must list EVERY symbol include/hf_pcg.h declares
 SIGNATURES = {
     "hf_abi_version": (c_int, []),
     "hf_error_string": (ctypes.c_char_p, [c_int]),
     "hf_pcg_create": (c_int, [ctypes.POINTER(c_void_p), c_int64, c_int, c_int]),
     "hf_pcg_destroy": (c_int, [c_void_p]),
+    "hf_pcg_plan_info": (c_int, [c_void_p, ctypes.POINTER(PcgPlan)]),
+    "hf_pcg_set_streaming": (c_int, [c_void_p, c_int, c_int]),
     "hf_pcg_begin": (
         c_int,
         [c_void_p] * 6

@@ -589,6 +589,7 @@ struct hf_pcg {
   int store_x0;
   void* m_hist;
   int begun, inited, finished;
+  int stream_k12, stream_k3;  // hf_pcg_set_streaming: -1 by size, 0 off, 1 on
   // timing
   int timing;
   int64_t t_count;
@@ -618,7 +619,14 @@ int grid_for(const hf_pcg* h, int unroll) {
 
 // non-temporal streams for vectors that cannot stay cached between their uses (see HF_LD)
 bool nt_streams(const hf_pcg* h) {
+  if (h->stream_k12 >= 0) return h->stream_k12 != 0;  // hf_pcg_set_streaming
   return h->n >= 16000000LL;  // (six fp32 vectors of 1.5 x the 256 MiB Infinity Cache)
+}
+
+// K3's own threshold (see HF_LD: below it K3's operands are still on-die)
+bool nt_streams_k3(const hf_pcg* h) {
+  if (h->stream_k3 >= 0) return h->stream_k3 != 0;
+  return h->n >= HF_K3_NT_MIN;
 }
 }  // namespace
 
@@ -645,6 +653,7 @@ int hf_pcg_create(hf_pcg_t** out, int64_t n, int dtype, int max_blocks) {
   memset(h, 0, sizeof(*h));
   h->n = n;
   h->dtype = dtype;
+  h->stream_k12 = h->stream_k3 = -1;
   const bool explicit_blocks = max_blocks != 0;
   if (max_blocks == 0) {
     int dev = 0, cus = 256;
@@ -847,7 +856,7 @@ static void build_k2(hf_pcg* h, const void* Bp, double damping, KLaunch& k) {
 
 template <typename T>
 static void build_k3(hf_pcg* h, const void* yext, KLaunch& k) {
-  const bool nt = h->n >= HF_K3_NT_MIN;  // (see HF_LD: below that K3's operands are on-die)
+  const bool nt = nt_streams_k3(h);
   switch (h->precond) {
     case HF_M_NONE: k.func = nt ? (const void*)&k_update_p<T, HF_M_NONE, U3, true> : (const void*)&k_update_p<T, HF_M_NONE, U3, false>; break;
     case HF_M_DIAG: k.func = nt ? (const void*)&k_update_p<T, HF_M_DIAG, U3, true> : (const void*)&k_update_p<T, HF_M_DIAG, U3, false>; break;
@@ -903,6 +912,31 @@ static int update_p_impl(hf_pcg* h, const void* yext, hipStream_t s) {
   KLaunch k;
   build_k3<T>(h, yext, k);
   return launch(k, s);
+}
+
+int hf_pcg_set_streaming(hf_pcg_t* h, int k12, int k3) {
+  if (!h || k12 < -1 || k12 > 1 || k3 < -1 || k3 > 1) return HF_ERR_ARG;
+  if (h->begun) return HF_ERR_STATE;  // a graph built for this handle must not go stale
+  h->stream_k12 = k12;
+  h->stream_k3 = k3;
+  return HF_OK;
+}
+
+int hf_pcg_plan_info(const hf_pcg_t* h, hf_pcg_plan* out) {
+  if (!h || !out) return HF_ERR_ARG;
+  memset(out, 0, sizeof(*out));
+  out->grid_init = grid_for(h, 1);
+  out->grid_k1 = grid_for(h, U1);
+  out->grid_k2 = grid_for(h, U2);
+  out->grid_k3 = grid_for(h, U3);
+  out->grid_cap = h->grid_cap;
+  out->unroll_k1 = U1;
+  out->unroll_k2 = U2;
+  out->unroll_k3 = U3;
+  out->width = h->dtype == HF_F32 ? 4 : 2;
+  out->nt_k12 = nt_streams(h) ? 1 : 0;
+  out->nt_k3 = nt_streams_k3(h) ? 1 : 0;
+  return HF_OK;
 }
 
 int hf_pcg_curvature(hf_pcg_t* h, const void* Bp, double damping, void* stream) {
