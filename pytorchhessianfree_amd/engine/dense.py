@@ -13,6 +13,8 @@ from .common import _Node, _P, _Unsupported, _ce_node, _flat_view, _ptr, _same, 
 from .core import FusedGGNEngine
 
 _ACT = {None: 0, nn.ReLU: 1, nn.Tanh: 2}
+_OPT_IN = "the dense-stack engine is opt-in (set HF_DENSE_ENGINE=1)"
+_GRADIENT, _PRODUCT, _DIAG_EF = range(3)  # what an adjoint sweep is for
 
 
 class _Layer:
@@ -72,8 +74,8 @@ class DenseStackEngine(FusedGGNEngine):
     def unavailable(cls, hessian, need_session):
         # Opt-in until its speed on large MLPs is measured against the hipGraph-replayed autograd sweeps
         # (scripts/bench_dense_engine.py): products are tested, the gain is not.
-        if os.environ.get("HF_DENSE_ENGINE", "0") != "1":
-            return "the dense-stack engine is opt-in (set HF_DENSE_ENGINE=1)"
+        if not cls._engine_switch():
+            return _OPT_IN
         # Hessian products: opt-in of their own until they beat the hipGraph-replayed double backward by more than the
         # spread of the measurement (profiles/r12_dense_hessian.jsonl)
         if hessian and os.environ.get("HF_DENSE_HESSIAN", "0") != "1":
@@ -85,6 +87,10 @@ class DenseStackEngine(FusedGGNEngine):
         if reason is None and need_session and not cls._session_switch():
             reason = "the dense-stack engine has no session yet (opt-in: set HF_DENSE_SESSION=1)"
         return reason
+
+    @staticmethod
+    def _engine_switch():
+        return os.environ.get("HF_DENSE_ENGINE", "0") == "1"
 
     @staticmethod
     def _session_switch():
@@ -102,6 +108,7 @@ class DenseStackEngine(FusedGGNEngine):
             offs.append(o)
             o += p.numel()
         self._offs = offs
+        self.loss_spec = None  # (set by _loss_setup in session mode: no own loss head before)
         self._layout(model)
         self._allocate()
         self.forward_own()
@@ -233,17 +240,21 @@ class DenseStackEngine(FusedGGNEngine):
         self._flat_params = _flat_view(self.params, self.n)
 
     # ---- launches ----------------------------------------------------------------------------
+    def _launch(self, name, *args):
+        """One launching entry point of the library (all end in ``int dtype, void* stream``) on the current stream:
+        tensors go as their addresses."""
+        args = [_ptr(a) if isinstance(a, torch.Tensor) else a for a in args]
+        _lib.check(getattr(_lib.load(), name)(*args, _lib.HF_F32, _lib.current_stream_ptr(self.dev)), name)
+
     def _tangent(self, u, t_x, v_w):
         """``u.tslabs <- t_x W^T + x V^T`` (either term may be absent, not both)."""
-        w = u.lin.weight
-        _lib.check(_lib.load().hf_dense_tangent_slabs(
-            _ptr(u.tslabs), _ptr(t_x), _ptr(u.x), _ptr(w), v_w, self.rows, u.c_in, u.c_out, 0, u.sT, u.tslabs.shape[1],
-            _lib.HF_F32, _lib.current_stream_ptr(self.dev)), "hf_dense_tangent_slabs")
+        self._launch("hf_dense_tangent_slabs", u.tslabs, t_x, u.x, u.lin.weight, v_w, self.rows, u.c_in, u.c_out, 0, u.sT,
+                     u.tslabs.shape[1])
 
-    def _act_tangent(self, out, slabs, splits, stride, v_b, y, act, c):
-        _lib.check(_lib.load().hf_dense_act_tangent(
-            _ptr(out), _ptr(slabs), splits, stride, v_b, _ptr(y), act, self.rows, c, _lib.HF_F32,
-            _lib.current_stream_ptr(self.dev)), "hf_dense_act_tangent")
+    def _flat(self, noun, *vecs):
+        for t in vecs:
+            if t.dtype != torch.float32 or t.numel() != self.n or not t.is_contiguous() or t.device != self.dev:
+                raise RuntimeError(f"dense-stack engine: {noun} must be contiguous float32 of the parameters' size")
 
     # ---- forward -----------------------------------------------------------------------------
     def forward_own(self, refresh=False, update_running=True):
@@ -251,16 +262,11 @@ class DenseStackEngine(FusedGGNEngine):
         the forward GEMM; slab sum, bias and activation in one pass (``hf_dense_act_forward``); in session mode the loss
         head.  Weights are read in place (``refresh``: nothing to do), there are no running statistics.  Two launches
         per layer, no allocation, no host synchronisation: capturable."""
-        lib, stream = _lib.load(), _lib.current_stream_ptr(self.dev)
         for u in self.layers:
-            w = u.lin.weight
-            _lib.check(lib.hf_dense_tangent_slabs(
-                _ptr(u.tslabs), None, _ptr(u.x), _ptr(w), _ptr(w), self.rows, u.c_in, u.c_out, 0, u.sT,
-                u.tslabs.shape[1], _lib.HF_F32, stream), "hf_dense_tangent_slabs")
-            _lib.check(lib.hf_dense_act_forward(
-                _ptr(u.y), _ptr(u.tslabs), u.sT, u.tslabs.shape[1], _ptr(u.lin.bias), u.act, self.rows, u.c_out,
-                _lib.HF_F32, stream), "hf_dense_act_forward")
-        if getattr(self, "loss_spec", None) is not None:
+            self._tangent(u, None, u.lin.weight)
+            self._launch("hf_dense_act_forward", u.y, u.tslabs, u.sT, u.tslabs.shape[1], u.lin.bias, u.act, self.rows,
+                         u.c_out)
+        if self.loss_spec is not None:
             self._loss_head()
         self._at = "own"
         return self.logits
@@ -271,7 +277,7 @@ class DenseStackEngine(FusedGGNEngine):
         self._x2d.copy_(self._rec_in)
         for u in self.layers:
             u.y.copy_(u.ry)
-        if getattr(self, "loss_spec", None) is not None:
+        if self.loss_spec is not None:
             self._loss_head()
         self._at = "recorded"
 
@@ -298,8 +304,7 @@ class DenseStackEngine(FusedGGNEngine):
             self._g_ef = (self._dl.detach() * per_sample).contiguous()
         self._h_last = self._dl.detach().contiguous() if self.hessian else None  # d loss / d logits
         self._dl = None
-        self.loss_spec = None  # (no own loss head without the session mode)
-        if not self._session_switch():
+        if not self._session_switch():  # (no own loss head without the session mode: loss_spec stays None)
             return
         if self._reduction is None:
             self.session_decline = ("the dense-stack engine's session takes a plain cross-entropy / MSE loss (no "
@@ -332,10 +337,8 @@ class DenseStackEngine(FusedGGNEngine):
         """Session mode: probabilities, ``d loss / d logits``, the per-sample cotangents, the loss value and the
         bad-target flag of the current logits and targets -- one call of ``hf_dense_loss_head`` (two launches)."""
         rows, c = self.logits.shape
-        _lib.check(_lib.load().hf_dense_loss_head(
-            self._kind, _ptr(self.logits), _ptr(self._targets), _ptr(self._p), _ptr(self._h_last), _ptr(self._g_ef),
-            _ptr(self.loss_buf), _ptr(self.bad_targets), _ptr(self._work), self._scale_g, self._scale_ps, self._coef,
-            rows, c, _lib.HF_F32, _lib.current_stream_ptr(self.dev)), "hf_dense_loss_head")
+        self._launch("hf_dense_loss_head", self._kind, self.logits, self._targets, self._p, self._h_last, self._g_ef,
+                     self.loss_buf, self.bad_targets, self._work, self._scale_g, self._scale_ps, self._coef, rows, c)
 
     # ---- per batch / per parameter point (session mode) ----------------------------------------------------------
     def _session_only(self, what):
@@ -392,29 +395,47 @@ class DenseStackEngine(FusedGGNEngine):
         own ``ga`` buffers (nothing is kept).  Existing kernels only; no allocation, no host synchronisation."""
         if not self.hessian and self.loss_spec is None:
             raise RuntimeError("the dense-stack engine keeps first-order cotangents in Hessian mode only")
-        if out is not None and (out.dtype != torch.float32 or out.numel() != self.n or not out.is_contiguous()
-                                or out.device != self.dev):
-            raise RuntimeError("dense-stack engine: the gradient must be contiguous float32 of the parameters' size")
-        lib, rows, offs = _lib.load(), self.rows, self._offs
-        op = out.data_ptr() if out is not None else None
-        stream = _lib.current_stream_ptr(self.dev)
-        slabs, splits, stride = self._h_last, 1, 0
+        if out is not None:
+            self._flat("the gradient", out)
+        return self._adjoint_sweep(_GRADIENT, self._h_last, out)
+
+    def _adjoint_sweep(self, what, seed, out, v=None, scale=None):
+        """THE adjoint sweep: from the cotangent ``seed`` at the logits through the live layers in reverse, per layer the
+        activation adjoint -> the weight output -> (``_DIAG_EF``) the bias output -> the data gradient, as slabs the next
+        activation adjoint sums.  ``_GRADIENT`` keeps ``g_l`` (``h_l`` of tanh layers) where a Hessian engine has buffers
+        for them and writes ``weight * gradient`` if there is an ``out``; ``_PRODUCT`` carries, on a Hessian engine, the
+        second-order terms of the vector ``v`` where a layer has them; ``_DIAG_EF`` writes sums of squares times
+        ``scale`` (per-sample cotangents: the rank ``weight`` does not enter, the bias has a kernel of its own)."""
+        launch, rows, offs, weight = self._launch, self.rows, self._offs, self.weight
+        diag, second = what == _DIAG_EF, what == _PRODUCT and self.hessian
+        slabs, splits, stride = seed, 1, 0
         for u in reversed(self.layers[self.dead_layers:]):
-            if u.h1 is not None:  # h_l itself: the slab sum, no factor
-                _lib.check(lib.hf_dense_act_adjoint(_ptr(u.h1), None, _ptr(slabs), splits, stride, None, 0, rows, u.c_out,
-                                                    1.0, _lib.HF_F32, stream), "hf_dense_act_adjoint")
-            g = u.g1 if u.g1 is not None else u.ga
-            g_b = _addr(op, offs[u.pb]) if out is not None and u.pb is not None else None
-            _lib.check(lib.hf_dense_act_adjoint(_ptr(g), g_b, _ptr(slabs), splits, stride, _ptr(u.y), u.act, rows,
-                                                u.c_out, self.weight, _lib.HF_F32, stream), "hf_dense_act_adjoint")
-            if out is not None and u.pw is not None:
-                _lib.check(lib.hf_dense_wgrad(_addr(op, offs[u.pw]), _ptr(g), _ptr(u.x), rows, u.c_in, u.c_out,
-                                              self.weight, _lib.HF_F32, stream), "hf_dense_wgrad")
-            if not u.first_live:
-                _lib.check(lib.hf_dense_dgrad_slabs(_ptr(u.dslabs), _ptr(g), _ptr(u.lin.weight), rows, u.c_in,
-                                                    u.c_out, u.sD, u.dslabs.shape[1], _lib.HF_F32, stream),
-                           "hf_dense_dgrad_slabs")
-                slabs, splits, stride = u.dslabs, u.sD, u.dslabs.shape[1]
+            o_w = _addr(out.data_ptr(), offs[u.pw]) if out is not None and u.pw is not None else None
+            o_b = _addr(out.data_ptr(), offs[u.pb]) if out is not None and u.pb is not None else None
+            g = u.g1 if what == _GRADIENT and u.g1 is not None else u.ga
+            if what == _GRADIENT and u.h1 is not None:  # h_l itself: the slab sum, no factor
+                launch("hf_dense_act_adjoint", u.h1, None, slabs, splits, stride, None, 0, rows, u.c_out, 1.0)
+            if second and u.act == 2:  # tanh: the curvature term -2 a t_a h
+                launch("hf_dense_act_adjoint2", g, o_b, slabs, splits, stride, u.y, u.act, u.ty, u.h1, rows, u.c_out, weight)
+            else:
+                launch("hf_dense_act_adjoint", g, None if diag else o_b, slabs, splits, stride, u.y, u.act, rows, u.c_out,
+                       1.0 if diag else weight)
+            if o_w is not None and diag:
+                launch("hf_dense_sq_wgrad", o_w, g, u.x, rows, u.c_in, u.c_out, scale)
+            elif o_w is not None and second and u.t_in is not None:  # + g^T t_x (none enters the first live layer)
+                launch("hf_dense_wgrad2", o_w, g, u.x, u.g1, u.t_in, rows, u.c_in, u.c_out, weight)
+            elif o_w is not None:
+                launch("hf_dense_wgrad", o_w, g, u.x, rows, u.c_in, u.c_out, weight)
+            if o_b is not None and diag:
+                launch("hf_dense_sq_colsum", o_b, g, rows, u.c_out, scale)
+            if u.first_live:
+                break
+            if second and u.pw is not None:  # + g V (a frozen weight has no tangent)
+                launch("hf_dense_dgrad2_slabs", u.dslabs, g, u.lin.weight, u.g1, _addr(v.data_ptr(), offs[u.pw]), rows,
+                       u.c_in, u.c_out, u.sD, u.dslabs.shape[1])
+            else:
+                launch("hf_dense_dgrad_slabs", u.dslabs, g, u.lin.weight, rows, u.c_in, u.c_out, u.sD, u.dslabs.shape[1])
+            slabs, splits, stride = u.dslabs, u.sD, u.dslabs.shape[1]
         return out
 
     def _not_here(what):  # noqa: N805  (the conv engines' entry points this kind inherits but does not have)
@@ -435,14 +456,10 @@ class DenseStackEngine(FusedGGNEngine):
         v = v.detach()
         if not v.is_contiguous():
             v = v.contiguous()
-        if v.dtype != torch.float32 or v.numel() != self.n or out.dtype != torch.float32 or out.numel() != self.n \
-                or not out.is_contiguous():
-            raise RuntimeError("dense-stack engine: vector and product must be contiguous float32 of the parameters' size")
-        lib, dev, rows, offs = _lib.load(), self.dev, self.rows, self._offs
-        vp, op = v.data_ptr(), out.data_ptr()
-        live = self.layers[self.dead_layers:]
-        t_x, second = None, self.hessian
-        for u in live:
+        self._flat("vector and product", v, out)
+        vp, offs = v.data_ptr(), self._offs
+        t_x = None
+        for u in self.layers[self.dead_layers:]:
             u.t_in = t_x  # (the tangent of the layer's input: the Hessian's second weight-gradient term)
             v_w = _addr(vp, offs[u.pw]) if u.pw is not None else None
             v_b = _addr(vp, offs[u.pb]) if u.pb is not None else None
@@ -451,42 +468,14 @@ class DenseStackEngine(FusedGGNEngine):
             else:
                 self._tangent(u, t_x, v_w)
                 slabs, splits = u.tslabs, u.sT
-            self._act_tangent(u.ty, slabs, splits, u.tslabs.shape[1], v_b, u.y, u.act, u.c_out)
+            self._launch("hf_dense_act_tangent", u.ty, slabs, splits, u.tslabs.shape[1], v_b, u.y, u.act, self.rows, u.c_out)
             t_x = u.ty
-        stream = _lib.current_stream_ptr(dev)
         if self._ce is not None:
-            _lib.check(lib.hf_softmax_ce_hvp(_ptr(self._g_last), _ptr(self._ce[0]), _ptr(t_x), float(self._ce[1]), rows,
-                                             self.logits.shape[1], _lib.HF_F32, stream), "hf_softmax_ce_hvp")
+            self._launch("hf_softmax_ce_hvp", self._g_last, self._ce[0], t_x, float(self._ce[1]), self.rows,
+                         self.logits.shape[1])
         else:
             torch.mul(t_x, self._mse2, out=self._g_last)
-        slabs, splits, stride = self._g_last, 1, 0
-        for u in reversed(live):
-            g_b = _addr(op, offs[u.pb]) if u.pb is not None else None
-            if second and u.act == 2:  # tanh: the curvature term -2 a t_a h
-                _lib.check(lib.hf_dense_act_adjoint2(_ptr(u.ga), g_b, _ptr(slabs), splits, stride, _ptr(u.y), u.act,
-                                                     _ptr(u.ty), _ptr(u.h1), rows, u.c_out, self.weight, _lib.HF_F32,
-                                                     stream), "hf_dense_act_adjoint2")
-            else:
-                _lib.check(lib.hf_dense_act_adjoint(_ptr(u.ga), g_b, _ptr(slabs), splits, stride, _ptr(u.y), u.act, rows,
-                                                    u.c_out, self.weight, _lib.HF_F32, stream), "hf_dense_act_adjoint")
-            if u.pw is not None and second and u.t_in is not None:  # + g^T t_x (no tangent enters the first live layer)
-                _lib.check(lib.hf_dense_wgrad2(_addr(op, offs[u.pw]), _ptr(u.ga), _ptr(u.x), _ptr(u.g1), _ptr(u.t_in),
-                                               rows, u.c_in, u.c_out, self.weight, _lib.HF_F32, stream),
-                           "hf_dense_wgrad2")
-            elif u.pw is not None:
-                _lib.check(lib.hf_dense_wgrad(_addr(op, offs[u.pw]), _ptr(u.ga), _ptr(u.x), rows, u.c_in, u.c_out,
-                                              self.weight, _lib.HF_F32, stream), "hf_dense_wgrad")
-            if not u.first_live:
-                if second and u.pw is not None:  # + g V (a frozen weight has no tangent)
-                    _lib.check(lib.hf_dense_dgrad2_slabs(_ptr(u.dslabs), _ptr(u.ga), _ptr(u.lin.weight), _ptr(u.g1),
-                                                         _addr(vp, offs[u.pw]), rows, u.c_in, u.c_out, u.sD,
-                                                         u.dslabs.shape[1], _lib.HF_F32, stream), "hf_dense_dgrad2_slabs")
-                else:
-                    _lib.check(lib.hf_dense_dgrad_slabs(_ptr(u.dslabs), _ptr(u.ga), _ptr(u.lin.weight), rows, u.c_in,
-                                                        u.c_out, u.sD, u.dslabs.shape[1], _lib.HF_F32, stream),
-                               "hf_dense_dgrad_slabs")
-                slabs, splits, stride = u.dslabs, u.sD, u.dslabs.shape[1]
-        return out
+        return self._adjoint_sweep(_PRODUCT, self._g_last, out, v=v)
 
     # ---- diagonal of the empirical Fisher ---------------------------------------------------------
     def diag_ef(self, reduction="mean", out=None):
@@ -507,27 +496,8 @@ class DenseStackEngine(FusedGGNEngine):
             raise RuntimeError("engine.diag_ef: the engine's buffers do not hold its own forward pass")
         if out is None:
             out = torch.empty(self.n, dtype=torch.float32, device=self.dev)
-        if out.dtype != torch.float32 or out.numel() != self.n or not out.is_contiguous() or out.device != self.dev:
-            raise RuntimeError("dense-stack engine: the diagonal must be contiguous float32 of the parameters' size")
-        lib, rows, offs, op = _lib.load(), self.rows, self._offs, out.data_ptr()
-        scale = 1.0 / rows if reduction == "mean" else 1.0
-        stream = _lib.current_stream_ptr(self.dev)
-        slabs, splits, stride = self._g_ef, 1, 0
-        for u in reversed(self.layers[self.dead_layers:]):
-            _lib.check(lib.hf_dense_act_adjoint(_ptr(u.ga), None, _ptr(slabs), splits, stride, _ptr(u.y), u.act, rows,
-                                                u.c_out, 1.0, _lib.HF_F32, stream), "hf_dense_act_adjoint")
-            if u.pw is not None:
-                _lib.check(lib.hf_dense_sq_wgrad(_addr(op, offs[u.pw]), _ptr(u.ga), _ptr(u.x), rows, u.c_in, u.c_out,
-                                                 scale, _lib.HF_F32, stream), "hf_dense_sq_wgrad")
-            if u.pb is not None:
-                _lib.check(lib.hf_dense_sq_colsum(_addr(op, offs[u.pb]), _ptr(u.ga), rows, u.c_out, scale, _lib.HF_F32,
-                                                  stream), "hf_dense_sq_colsum")
-            if not u.first_live:
-                _lib.check(lib.hf_dense_dgrad_slabs(_ptr(u.dslabs), _ptr(u.ga), _ptr(u.lin.weight), rows, u.c_in,
-                                                    u.c_out, u.sD, u.dslabs.shape[1], _lib.HF_F32, stream),
-                           "hf_dense_dgrad_slabs")
-                slabs, splits, stride = u.dslabs, u.sD, u.dslabs.shape[1]
-        return out
+        self._flat("the diagonal", out)
+        return self._adjoint_sweep(_DIAG_EF, self._g_ef, out, scale=1.0 / self.rows if reduction == "mean" else 1.0)
 
     # ---- one process only ----------------------------------------------------------------------
     @property
@@ -544,8 +514,8 @@ def diag_ef_of(model, loss_function, inputs, targets, reduction, why=None):
     has a convolution or is no prepared MLP the engine covers, batch > 256, another loss.  Only this engine kind is
     ever built from here."""
     why = [] if why is None else why
-    if os.environ.get("HF_DENSE_ENGINE", "0") != "1":
-        why.append("the dense-stack engine is opt-in (set HF_DENSE_ENGINE=1)")
+    if not DenseStackEngine._engine_switch():
+        why.append(_OPT_IN)
         return None
     if not (isinstance(inputs, torch.Tensor) and inputs.is_cuda and inputs.dtype == torch.float32):
         why.append("the inputs are not a CUDA float32 tensor")

@@ -7,37 +7,16 @@ evaluation is inside the bound and that wrong variants are outside).  Bound of e
 would poison the result), outputs in NaN-filled buffers with 64 guard words; every launch is issued twice and compared
 bitwise; everything runs 16-byte aligned and 4 bytes off that grid."""
 
-import numpy as np
 import pytest
 import torch
 from tol import within
 
 import dense_diag_refs as ddr
 import dense_refs as dr
+from dense_guarded import DEV, ERR_ARG, F32, GUARD, NAN, In, P, _ids, st
 from pytorchhessianfree_amd import _lib
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-GUARD = 64
-NAN = float("nan")
-P = _lib.c_void_p
-ERR_ARG = _lib.HF_ERR_ARG
-F32 = _lib.HF_F32
-_ids = lambda v: str(v).replace(" ", "")  # noqa: E731
-
-
-def st():
-    return _lib.current_stream_ptr(torch.device(DEV))
-
-
-class In:
-    """An operand inside a NaN-filled buffer, ``off`` floats behind a 16-byte boundary."""
-
-    def __init__(self, arr, off):
-        arr = np.ascontiguousarray(arr, dtype=np.float32)
-        self.buf = torch.full((arr.size + off + 8,), NAN, device=DEV)
-        self.buf[off:off + arr.size].copy_(torch.from_numpy(arr).reshape(-1))
-        self.ptr = P(self.buf.data_ptr() + 4 * off)
 
 
 class Out:
