@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 19
+#define HF_ABI_VERSION 20
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -196,6 +196,14 @@ int hf_pack(void* dst, const void* const* srcs, const int64_t* numels,
 int hf_pack_ex(void* dst, const void* const* srcs, const int64_t* numels, const int64_t* perm,
                const int64_t* splits, const int64_t* live, int n_tensors, double scale, int mode,
                int dtype, void* stream);
+/* hf_pack_ex into the COMPACT layout of the vector -- the flat vector with the entries of dead taps removed (the order
+ * of hf_live_copy): `compact` (HOST, 1 per tensor, or NULL = hf_pack_ex): 0 = tensor t keeps all its entries; else
+ * popcount(live[t]) (anything else is refused) = tensor t is stored [O, I, popcount(live)], taps in increasing order:
+ * dst index (o*I + i)*nl + rank(hw) instead of (o*I + i)*HW + hw; dead taps are neither read nor written.  Offsets
+ * in dst count compact entries; no padding.  One launch writes one layout: all-NULL / all-0 is the flat vector. */
+int hf_pack_compact(void* dst, const void* const* srcs, const int64_t* numels, const int64_t* perm,
+                    const int64_t* splits, const int64_t* live, const int64_t* compact, int n_tensors, double scale,
+                    int mode, int dtype, void* stream);
 /*
  * Multi-tensor scatter for the tangent sweep, the counterpart of hf_pack: tensor t is the
  * contiguous [O, slab] block at src + src_offs[t] (a weight-shaped slice of the CG
@@ -227,6 +235,12 @@ int hf_unpack_tangent_ex(const void* src, void* const* dsts, const int64_t* src_
 int hf_unpack_weights(const void* src, void* const* dsts, const int64_t* src_offs,
                       const int64_t* numels, const int64_t* slabs, const int64_t* inners,
                       const int64_t* live, const int64_t* halves, int n_tensors, int dtype, void* stream);
+/* hf_unpack_weights reading the COMPACT layout (hf_pack_compact): `compact` (HOST, 1 per tensor, or NULL) as there;
+ * a tensor with compact[t] = nl lies at src + src_offs[t] (a compact offset) as [O, I, nl]: source index
+ * (o*I + i)*nl + rank(hw).  NHWC destinations with a live mask only; transposed copies (halves[t] = 2) are refused. */
+int hf_unpack_weights_compact(const void* src, void* const* dsts, const int64_t* src_offs, const int64_t* numels,
+                              const int64_t* slabs, const int64_t* inners, const int64_t* live, const int64_t* halves,
+                              const int64_t* compact, int n_tensors, int dtype, void* stream);
 
 /*
  * Data-parallel products (the `result += N * mb_result` of optimizer.py:677-684, across GPUs): the
@@ -240,6 +254,16 @@ int hf_unpack_weights(const void* src, void* const* dsts, const int64_t* src_off
  */
 int hf_live_copy(void* full, void* compact, int scatter, const int64_t* full_offs, const int64_t* counts,
                  const int64_t* periods, const int64_t* masks, int n_segments, int dtype, void* stream);
+/* The same for `rows` vectors in ONE launch: row r of `full` starts at full + r*full_stride, of `compact` at
+ * compact + r*compact_stride (elements; the iterates a compact PCG solve hands back, cg.py). */
+int hf_live_copy_rows(void* full, void* compact, int scatter, int64_t rows, int64_t full_stride,
+                      int64_t compact_stride, const int64_t* full_offs, const int64_t* counts, const int64_t* periods,
+                      const int64_t* masks, int n_segments, int dtype, void* stream);
+/* *flag (a device int) = 0 if every DEAD entry (a tap outside its segment's mask) of the flat vectors `a` and `b`
+ * (`b` may be NULL) compares equal to 0.0 -- -0.0 does, NaN does not --, else 1.  Segments as hf_live_copy.  A PCG
+ * solve whose right-hand side and start vector pass may run on the compact vector: its dead entries stay zero. */
+int hf_live_dead_check(const void* a, const void* b, void* flag, const int64_t* full_offs, const int64_t* counts,
+                       const int64_t* periods, const int64_t* masks, int n_segments, int dtype, void* stream);
 
 /* minv = (diag + damping)^(-exponent)   (preconditioners.py:124, hoisted out of
  * the CG loop). */
@@ -481,6 +505,14 @@ int hf_conv2d_nhwc_slabs_unpack(void* out, const void* act, const void* mat, int
                                 const int64_t* unumels, const int64_t* uslabs, const int64_t* uinners,
                                 const int64_t* ulive, const int64_t* uhalves, int n_tensors, int dtype,
                                 void* stream);
+/* The same with the scatter reading the compact layout (`ucompact` as hf_unpack_weights_compact's `compact`). */
+int hf_conv2d_nhwc_slabs_unpack_compact(void* out, const void* act, const void* mat, int64_t n, int64_t h, int64_t w,
+                                        int64_t c, int64_t k, int64_t r, int64_t s, int64_t stride_h, int64_t stride_w,
+                                        int64_t pad_h, int64_t pad_w, int64_t act_ld, int64_t mat_ld, int splits,
+                                        int64_t slab_stride, const void* usrc, void* const* udsts,
+                                        const int64_t* usrc_offs, const int64_t* unumels, const int64_t* uslabs,
+                                        const int64_t* uinners, const int64_t* ulive, const int64_t* uhalves,
+                                        const int64_t* ucompact, int n_tensors, int dtype, void* stream);
 
 /*
  * Consumer-side reduction ("slab") variants: split s of the reduction writes its partial result,

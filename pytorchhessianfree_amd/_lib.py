@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HF_PCG_LIB") or os.path.join(_HERE, "csrc", "libhfpcg.so")
 
 HF_F32, HF_F64 = 0, 1
-ABI_VERSION = 19
+ABI_VERSION = 20
 HF_ERR_ARG = -1  # hf_status of include/hf_pcg.h: null / negative / inconsistent argument
 HF_M_NONE, HF_M_DIAG, HF_M_EXTERNAL = 0, 1, 2
 REASONS = {
@@ -109,11 +109,19 @@ SIGNATURES = {
         c_int,
         [c_void_p, ctypes.POINTER(c_void_p)] + [ctypes.POINTER(c_int64)] * 6 + [c_int, c_int, c_void_p],
     ),
+    "hf_unpack_weights_compact": (
+        c_int,
+        [c_void_p, ctypes.POINTER(c_void_p)] + [ctypes.POINTER(c_int64)] * 7 + [c_int, c_int, c_void_p],
+    ),
     "hf_bn_forward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int64] + [c_void_p] * 5
                       + [c_int64, c_int, c_int64, c_int64, c_int, c_void_p]),
     "hf_maxpool_forward_nhwc": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p] + [c_int64] * 12
                                 + [c_int, c_void_p]),
     "hf_live_copy": (c_int, [c_void_p, c_void_p, c_int] + [ctypes.POINTER(c_int64)] * 4 + [c_int, c_int, c_void_p]),
+    "hf_live_copy_rows": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64]
+                          + [ctypes.POINTER(c_int64)] * 4 + [c_int, c_int, c_void_p]),
+    "hf_live_dead_check": (c_int, [c_void_p, c_void_p, c_void_p] + [ctypes.POINTER(c_int64)] * 4
+                           + [c_int, c_int, c_void_p]),
     "hf_precond_build": (c_int, [c_void_p, c_void_p, c_double, c_double, c_int64, c_int, c_void_p]),
     "hf_axpy_out": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int64, c_int, c_void_p]),
     "hf_chan_affine": (c_int, [c_void_p] * 10 + [c_int, c_int64, c_int64, c_int64, c_int, c_int64, c_int64,
@@ -129,6 +137,9 @@ SIGNATURES = {
     "hf_conv2d_nhwc_slabs_unpack": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int64] * 13 + [c_int, c_int64, c_void_p,
                                             ctypes.POINTER(c_void_p)] + [ctypes.POINTER(c_int64)] * 6
                                     + [c_int, c_int, c_void_p]),
+    "hf_conv2d_nhwc_slabs_unpack_compact": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int64] * 13
+                                            + [c_int, c_int64, c_void_p, ctypes.POINTER(c_void_p)]
+                                            + [ctypes.POINTER(c_int64)] * 7 + [c_int, c_int, c_void_p]),
     "hf_conv2d_nhwc_group_slabs": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "hf_conv2d_nhwc_dw_slabs": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "hf_conv2d_nhwc_plan_info": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p]),
@@ -156,6 +167,10 @@ SIGNATURES = {
         c_int,
         [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int64), ctypes.POINTER(c_int64),
          ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_int, c_double, c_int, c_int, c_void_p],
+    ),
+    "hf_pack_compact": (
+        c_int,
+        [c_void_p, ctypes.POINTER(c_void_p)] + [ctypes.POINTER(c_int64)] * 5 + [c_int, c_double, c_int, c_int, c_void_p],
     ),
     "hf_softmax_ce_hvp": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int64, c_int64, c_int, c_void_p]),
     "hf_maxpool_tangent_nhwc": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int64] * 7 + [c_int, c_void_p]),
@@ -310,10 +325,27 @@ def unpack_tangent(v, slots, half=1):
     lib = load()
     require_device_tensor(v, "v")
     table = unpack_table(v, slots, half)
+    periods = compact_periods(slots)
+    if periods is not None:  # (slots of the compact layout: ``v`` is a compact vector)
+        check(
+            lib.hf_unpack_weights_compact(c_void_p(v.data_ptr()), *table[:-1], periods, table[-1], dtype_code(v.dtype),
+                                          current_stream_ptr(v.device)),
+            "hf_unpack_weights_compact",
+        )
+        return
     check(
         lib.hf_unpack_weights(c_void_p(v.data_ptr()), *table, dtype_code(v.dtype), current_stream_ptr(v.device)),
         "hf_unpack_weights",
     )
+
+
+def compact_periods(slots):
+    """The ``compact`` array of ``hf_unpack_weights_compact`` for slots ``(compact offset, buffer, I, live, nl)`` --
+    ``nl`` live taps per (o, i) group of a tensor that lies in the compact layout, 0 = all its entries --, or ``None``
+    when no slot carries the fifth field (the flat layout)."""
+    if not any(len(slot) > 4 for slot in slots):
+        return None
+    return (c_int64 * len(slots))(*[int(slot[4]) if len(slot) > 4 else 0 for slot in slots])
 
 
 def unpack_table(v, slots, half=1):
@@ -353,7 +385,8 @@ def unpack_table(v, slots, half=1):
         offs[k] = off
         slabs[k] = cin * hw
         numels[k] = buf.shape[0] * cin * hw
-        if off < 0 or off + numels[k] > v.numel():
+        nl = slot[4] if len(slot) > 4 else 0  # (compact layout: the source holds nl of the hw taps)
+        if off < 0 or off + (numels[k] // hw * nl if nl else numels[k]) > v.numel():
             raise RuntimeError("unpack_tangent: slice outside the vector")
     return dsts, offs, numels, slabs, inners, live, halves, n
 
@@ -450,11 +483,12 @@ def conv2d_nhwc_backward(dx, dw, dy, x, w_t, n, h, w, c, k, r, s, stride, paddin
     return dx, dw
 
 
-def pack_ex(dst, tensors, perms, splits, scale=1.0, live=None, mode=0):
+def pack_ex(dst, tensors, perms, splits, scale=1.0, live=None, mode=0, compact=None):
     """``pack`` for sources the caller describes itself: ``perms[i] = (I, H*W)`` marks tensor i as
     stored (O, H, W, I); ``splits[i] = (count, stride)`` makes it the sum of ``count`` split-K
     slabs ``stride`` elements apart (``hf_pack_ex``); ``live[i]`` = bit mask of the kernel taps
-    whose gradients are not structurally zero.  ``tensors[i]`` is the first slab."""
+    whose gradients are not structurally zero.  ``tensors[i]`` is the first slab.  ``compact[i] = nl``: ``dst`` is a vector
+    in the compact layout, where tensor i holds only its ``nl`` live taps (``hf_pack_compact``)."""
     lib = load()
     require_device_tensor(dst, "dst")
     n = len(tensors)
@@ -474,8 +508,17 @@ def pack_ex(dst, tensors, perms, splits, scale=1.0, live=None, mode=0):
             perm[2 * i], perm[2 * i + 1] = perms[i]
         spl[2 * i], spl[2 * i + 1] = splits.get(i, (1, 0))
         lv[i] = (live or {}).get(i, 0)
+        if compact and compact.get(i, 0):
+            total -= t.numel() - t.numel() // perm[2 * i + 1] * compact[i]
     if total != dst.numel():
         raise RuntimeError(f"pack_ex: {total} source elements for a vector of {dst.numel()}")
+    if compact:
+        cp = (c_int64 * n)(*[compact.get(i, 0) for i in range(n)])
+        check(
+            lib.hf_pack_compact(c_void_p(dst.data_ptr()), ptrs, numels, perm, spl, lv, cp, n, float(scale), int(mode),
+                                dtype_code(dst.dtype), current_stream_ptr(dst.device)),
+            "hf_pack_compact")
+        return dst
     check(
         lib.hf_pack_ex(c_void_p(dst.data_ptr()), ptrs, numels, perm, spl, lv, n, float(scale), int(mode),
                        dtype_code(dst.dtype), current_stream_ptr(dst.device)),

@@ -24,6 +24,10 @@ Fast paths, chosen by operator TYPE (any other callable still works):
   built once (preconditioners.py:124 recomputes the power every call) and the
   multiply is fused into K2/K3.
 
+* the operator exposes ``compact`` (``curvature.CompactFacet``: a persistent engine session whose parameter
+  vector has structurally-zero entries) -> the whole solve runs on the ``n_live`` entries that can be non-zero
+  (:func:`_compact_facet` states the rule; ``HF_COMPACT_PCG=0`` switches it off).
+
 There is NO CPU fallback: CPU tensors raise ``RuntimeError``.
 """
 
@@ -270,15 +274,13 @@ def cg(
     cg.py:103-115.
     """
     _lib.require_device_tensor(b, "b")
-    lib = _lib.load()
     if verbose:
         print("\nStarting cg...")
 
     b = _as_operand(b, b, "b")
     if b.dim() != 1:
         raise RuntimeError("`b` must be a 1-D vector")
-    n, dtype, device = b.numel(), b.dtype, b.device
-    max_iter = n if max_iter is None else int(max_iter)
+    max_iter = b.numel() if max_iter is None else int(max_iter)
     if max_iter < 1:
         raise ValueError(f"Invalid max_iter: {max_iter}")
 
@@ -287,14 +289,86 @@ def cg(
         store_x_at_iters = storing_grid(max_iter)
     store = sorted({int(i) for i in store_x_at_iters if 0 <= int(i) <= max_iter})
 
+    facet = _compact_facet(A, b, x0, M)
+    if facet is None:
+        return _solve(A, b, x0, M, max_iter, tol, atol, martens_conv_crit, store, verbose)
+
+    # ---- the solve on the entries that can be non-zero: gather, solve on n_live entries, scatter ----------
+    n = b.numel()
+    bc = facet.gather(b)
+    x0c = None if x0 is None else facet.gather(_as_operand(x0, b, "x0"))
+    Mc = None
+    if M is not None:
+        Mc = DiagonalPreconditioner.__new__(DiagonalPreconditioner)
+        Mc.diag, Mc.damping, Mc.exponent = None, M.damping, M.exponent
+        Mc.minv = facet.gather(_as_operand(M.minv, b, "M.minv"))
+    Ac = DampedCurvature(facet, A.damping, A.lockstep) if isinstance(A, DampedCurvature) else facet
+    rows = []
+    xs, m_iters, reason = _solve(Ac, bc, x0c, Mc, max_iter, tol, atol, martens_conv_crit, store, verbose, rows)
+    n_iters = len(xs) - 1
+    # row 0: the final iterate; rows 1 ...: the snapshots that occurred (a prefix of the sorted table) -- all of them
+    # into zero-initialised full-length storage by ONE launch
+    k = sum(1 for it in store if it <= n_iters)
+    width = 16 // b.element_size()
+    full = torch.zeros((k + 1, (n + width - 1) // width * width), dtype=b.dtype, device=b.device)
+    facet.scatter(rows[0][: k + 1], full)
+    x_iters = [None] * (n_iters + 1)
+    for slot, it in enumerate(store[:k]):
+        x_iters[it] = full[1 + slot, :n]
+    if x_iters[-1] is None:
+        x_iters[-1] = full[0, :n]
+    return x_iters, m_iters, reason
+
+
+def _compact_facet(A, b, x0, M):
+    """The operator's compact facet if this solve may run on it, else ``None`` (the full-length path).  The rule:
+    the operator exposes ``compact`` and runs in a single process; ``M`` is ``None`` or a
+    :class:`DiagonalPreconditioner` (any other callable expects full-length vectors); ``HF_COMPACT_PCG`` is not ``0``;
+    and the dead entries of ``b`` and ``x0`` are all zero (one check launch and one host wait per solve, before the
+    first iteration).  Then ``r``, ``p`` and ``x`` stay zero on the dead entries for the whole solve -- the product,
+    the gradient and ``lambda * p`` are zero there --, so the solve on the compact vector is the solve on the full one.
+    Anything else silently takes the full path: that is correct, not an error."""
+    if os.environ.get("HF_COMPACT_PCG", "1") == "0":
+        return None
+    matvec = A.mvp if isinstance(A, DampedCurvature) else A
+    facet = getattr(matvec, "compact", None)
+    if facet is None or not hasattr(facet, "dead_entries_zero") or getattr(matvec, "group", None) is not None:
+        return None
+    if not (M is None or (isinstance(M, DiagonalPreconditioner) and M.minv.is_cuda and M.minv.shape == b.shape
+                          and M.minv.dtype == b.dtype)):
+        return None
+    ib = facet.input_buffer
+    if b.numel() != facet.n_full or b.dtype != ib.dtype or b.device != ib.device:
+        return None
+    if x0 is not None:
+        x0 = _as_operand(x0, b, "x0")
+    return facet if facet.dead_entries_zero(b, x0) else None
+
+
+def _solve(A, b, x0, M, max_iter, tol, atol, martens_conv_crit, store, verbose, rows=None):
+    """The solve of :func:`cg` on prepared arguments (``b`` an operand, ``store`` the sorted snapshot table).
+    ``rows``: a list that receives the ONE [1 + len(store), stride] buffer then holding the final iterate (row 0)
+    and the snapshot slab (rows 1 ...)."""
+    lib = _lib.load()
+    n, dtype, device = b.numel(), b.dtype, b.device
+
     ws = _Workspace.get(device, n, dtype)
     stream = _lib.current_stream_ptr(device)
     width = 16 // b.element_size()
     stride = (n + width - 1) // width * width
 
     # fresh per-solve storage handed to the caller afterwards
-    x = torch.zeros(n, dtype=dtype, device=device) if x0 is None else _as_operand(x0, b, "x0").clone()
-    slab = torch.empty((len(store), stride), dtype=dtype, device=device) if store else None
+    if rows is not None:
+        buf = torch.empty((len(store) + 1, stride), dtype=dtype, device=device)
+        rows.append(buf)
+        x, slab = buf[0, :n], (buf[1:] if store else None)
+        if x0 is None:
+            x.zero_()
+        else:
+            x.copy_(_as_operand(x0, b, "x0"))
+    else:
+        x = torch.zeros(n, dtype=dtype, device=device) if x0 is None else _as_operand(x0, b, "x0").clone()
+        slab = torch.empty((len(store), stride), dtype=dtype, device=device) if store else None
     store_dev = torch.tensor(store, dtype=torch.int64, device=device) if store else None
     m_hist = torch.empty(max_iter + 1, dtype=dtype, device=device) if martens_conv_crit else None
 

@@ -152,6 +152,8 @@ SWITCHES = {
                         "tests/test_optimizer_gpu.py::test_graphed_operator_refuses_a_replay_that_differs_from_the_eager_product"),
     "HF_FUSE_ITERATION": ("1", "0: product, K1, K2, K3 as separate launches (no iteration graph)",
                           "tests/test_engine_gpu.py::test_solve_as_one_graph_per_iteration_equals_separate_launches"),
+    "HF_COMPACT_PCG": ("1", "0: every PCG solve on the full-length vector (no solve on the entries that can be non-zero)",
+                       "tests/test_compact_session_gpu.py::test_cg_on_the_compact_vector_against_the_full_path"),
     "HF_BN_EPILOGUE": ("1", "0: train-mode tangent partial sums by the reduction launch, not the convolution's epilogue",
                        "tests/test_engine_gpu.py::test_train_mode_prologue_form_variants_agree_and_state_is_independent_of_the_first_use_check"),
     "HF_BN_TRAIN_PAIR": ("1", "0: a downsample block's two train-mode units in launches of their own",

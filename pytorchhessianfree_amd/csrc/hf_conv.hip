@@ -1383,6 +1383,18 @@ int hf_conv2d_nhwc_slabs_unpack(void* out, const void* act, const void* mat, int
                                 const int64_t* unumels, const int64_t* uslabs, const int64_t* uinners,
                                 const int64_t* ulive, const int64_t* uhalves, int n_tensors, int dtype,
                                 void* stream) {
+  return hf_conv2d_nhwc_slabs_unpack_compact(out, act, mat, n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w, act_ld,
+                                             mat_ld, splits, slab_stride, usrc, udsts, usrc_offs, unumels, uslabs,
+                                             uinners, ulive, uhalves, nullptr, n_tensors, dtype, stream);
+}
+
+int hf_conv2d_nhwc_slabs_unpack_compact(void* out, const void* act, const void* mat, int64_t n, int64_t h, int64_t w,
+                                        int64_t c, int64_t k, int64_t r, int64_t s, int64_t stride_h, int64_t stride_w,
+                                        int64_t pad_h, int64_t pad_w, int64_t act_ld, int64_t mat_ld, int splits,
+                                        int64_t slab_stride, const void* usrc, void* const* udsts,
+                                        const int64_t* usrc_offs, const int64_t* unumels, const int64_t* uslabs,
+                                        const int64_t* uinners, const int64_t* ulive, const int64_t* uhalves,
+                                        const int64_t* ucompact, int n_tensors, int dtype, void* stream) {
   if (!usrc || !udsts || !usrc_offs || !unumels || !uslabs || !uinners || n_tensors < 1) return HF_ERR_ARG;
   if (uhalves)  // (transposed copies run as LDS-tiled workgroups of hf_unpack_weights' own kernel only)
     for (int t_ = 0; t_ < n_tensors; ++t_)
@@ -1396,7 +1408,8 @@ int hf_conv2d_nhwc_slabs_unpack(void* out, const void* act, const void* mat, int
   hf_shared::UnpackArgs u;
   int ublocks = 0;
   const int next = hf_shared::fill_unpack_args<float>(u, &ublocks, 0, udsts, usrc_offs, unumels, uslabs, uinners,
-                                                      ulive, uhalves, n_tensors, /*allow_transposed=*/false);
+                                                      ulive, uhalves, ucompact, n_tensors,
+                                                      /*allow_transposed=*/false);
   if (next < 0) return next;
   if (next != n_tensors || ublocks < 1) return HF_ERR_ARG;  // more tensors than one argument block holds
   launch_unpack(a, blocks, u, (const float*)usrc, ublocks, (hipStream_t)stream);

@@ -35,6 +35,9 @@ struct PackArgs {
   // gradients are structurally zero (3x3 kernels on 1x1 / 2x2 maps) and are written as zeros
   // without being read.  0 = every tap is read.
   unsigned short live[PACK_MAXT];
+  // compact destination (hf_pack_compact): the dead taps' entries do not exist -- tensor t is stored [O, I, cnl[t]],
+  // cnl = popcount(live), taps in increasing order, and dst_off counts compact entries.  0 = flat [O, I, HW].
+  unsigned char cnl[PACK_MAXT];
   int nt;
 };
 constexpr int TILE_BYTES = 32768;  // LDS staging of the layout-permuting paths
@@ -45,6 +48,9 @@ __device__ __forceinline__ T pack_op(T d, T s, T scale) {
   const T g = (T)(scale * s);
   return d + (T)(g * g);
 }
+
+// position of live tap hw among the live taps (compact layout)
+__device__ __forceinline__ unsigned tap_rank(unsigned live, unsigned hw) { return (unsigned)__popc(live & ((1u << hw) - 1u)); }
 
 template <typename T, int OP>
 __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackArgs a, T scale) {
@@ -72,6 +78,9 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
     const long long sps = a.split_stride[lo];
     const unsigned I = (unsigned)a.perm_I[lo], HW = (unsigned)a.perm_HW[lo], slab = I * HW;
     const unsigned live = a.live[lo];
+    const unsigned cnl = a.cnl[lo];  // compact destination: [O, I, cnl] (then I > 0 and live != 0)
+    // first compact entry of this block's slabs (compact blocks that need it hold whole slabs)
+    const long long j0c = cnl ? j0 / slab * (long long)(I * cnl) : j0;
     if (sizeof(T) == 4 && (((uintptr_t)src) & 15) == 0 && (sps & 3) == 0 && (j0 & 3) == 0 && (numel & 3) == 0 &&
         (I & 3) == 0) {
       // 16-byte loads: one quad of consecutive source elements per lane and pass (a quad never leaves its
@@ -80,8 +89,9 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
       // whole slabs per block (host: chunk = a few slabs): the permuted order is assembled in LDS and leaves as
       // 16-byte stores -- four 4-byte stores per lane, 144 bytes apart across the lanes, cost more L2
       // transactions than the loads they follow
+      // (compact with ONE live tap: source row (o, hw) IS the destination row (o, :) -- no permutation, straight stores)
       const bool staged = I > 0 && (unsigned)a.chunk[lo] % slab == 0 && (unsigned)a.chunk[lo] <= TILE &&
-                          (((uintptr_t)(out + j0)) & 15) == 0;
+                          (((uintptr_t)(out + j0c)) & 15) == 0 && cnl != 1;
       for (unsigned e = (unsigned)j0 + threadIdx.x * 4; e < j1u; e += BLOCK * 4) {
         unsigned jd = e, step = 1;  // destination of the quad's first element, distance between its elements
         bool rd = true;
@@ -91,6 +101,11 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
           jd = o * slab + i * HW + hw;
           step = HW;
           if (live) rd = (live >> hw) & 1u;
+          if (cnl) {
+            if (!rd) continue;  // a dead tap has no entry
+            jd = (o * I + i) * cnl + tap_rank(live, hw);
+            step = cnl;
+          }
         }
         VU<T> acc;
 #pragma unroll
@@ -134,12 +149,18 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
           // the swap in registers.
 #pragma unroll
           for (int c = 0; c < W; ++c) {
-            const unsigned q = jd - (unsigned)j0 + c * step;
+            const unsigned q = jd - (unsigned)j0c + c * step;
             tile[(q & ~3u) | ((q ^ (q >> 6)) & 3u)] = acc.e[c];
           }
         } else if (I == 0 && OP == 0 && (((uintptr_t)(out + jd)) & 15) == 0) {
 #pragma unroll
           for (int c = 0; c < W; ++c) acc.e[c] = pack_op<T, OP>((T)0, acc.e[c], scale);
+          *reinterpret_cast<V*>(out + jd) = acc.v;
+        } else if (cnl == 1 && (((uintptr_t)(out + jd)) & 15) == 0) {
+          VU<T> d;
+          if (OP == 1) d.v = *reinterpret_cast<const V*>(out + jd);
+#pragma unroll
+          for (int c = 0; c < W; ++c) acc.e[c] = pack_op<T, OP>(OP == 1 ? d.e[c] : (T)0, acc.e[c], scale);
           *reinterpret_cast<V*>(out + jd) = acc.v;
         } else {
 #pragma unroll
@@ -148,7 +169,8 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
       }
       if (staged) {
         __syncthreads();
-        const unsigned len = j1u - (unsigned)j0;  // (a multiple of 4: whole slabs, I % 4 == 0)
+        // (a multiple of 4: whole slabs, I % 4 == 0)
+        const unsigned len = cnl ? (j1u - (unsigned)j0) / HW * cnl : j1u - (unsigned)j0;
         for (unsigned t = threadIdx.x * 4; t < len; t += BLOCK * 4) {
           VU<T> v, d;
           v.v = *reinterpret_cast<const V*>(tile + t);
@@ -159,10 +181,10 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
             if (sw & 2u) { T x0 = e0; e0 = e2; e2 = x0; T x1 = e1; e1 = e3; e3 = x1; }
             v.e[0] = e0; v.e[1] = e1; v.e[2] = e2; v.e[3] = e3;
           }
-          if (OP == 1) d.v = *reinterpret_cast<const V*>(out + j0 + t);
+          if (OP == 1) d.v = *reinterpret_cast<const V*>(out + j0c + t);
 #pragma unroll
           for (int c = 0; c < W; ++c) v.e[c] = pack_op<T, OP>(OP == 1 ? d.e[c] : (T)0, v.e[c], scale);
-          *reinterpret_cast<V*>(out + j0 + t) = v.v;
+          *reinterpret_cast<V*>(out + j0c + t) = v.v;
         }
       }
       return;
@@ -217,6 +239,10 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
           const unsigned rem = j - o * slab;
           const unsigned hw = rem / I, i = rem - hw * I;
           j = o * slab + i * HW + hw;
+          if (cnl) {
+            if (!rd[k]) continue;  // a dead tap has no entry
+            j = (o * I + i) * cnl + tap_rank(live, hw);
+          }
         }
         out[j] = pack_op<T, OP>(out[j], acc[k], scale);
       }
@@ -229,8 +255,39 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
     // staging, no barrier -- the block is a stream of vector stores
     const unsigned I = (unsigned)a.perm_I[lo], HW = (unsigned)a.perm_HW[lo], slab = I * HW;
     const unsigned live = a.live[lo];
-    const bool al = (((uintptr_t)(out + j0)) & 15) == 0;
     const unsigned j1u = (unsigned)j1;
+    if (a.cnl[lo]) {
+      // compact destination [O, I, nl]: only the live taps exist -- no zero stream.  Blocks need not hold whole slabs:
+      // every flat destination index of the chunk is decoded on its own.
+      const unsigned nl = a.cnl[lo];
+      if (nl == 1 && (I & (W - 1)) == 0 && ((unsigned)j0 % slab) == 0 && ((j1u - (unsigned)j0) % slab) == 0 &&
+          (((uintptr_t)(out + (unsigned)j0 / HW)) & 15) == 0 && (((uintptr_t)src) & 15) == 0) {
+        // one live tap: source row (o, hw) is destination row (o, :), 16 bytes at a time
+        const unsigned hw = (unsigned)__ffs(live) - 1u;
+        const unsigned o0 = (unsigned)j0 / slab, total = (j1u - (unsigned)j0) / HW;  // compact entries of the block
+        for (unsigned q = threadIdx.x * W; q < total; q += BLOCK * W) {
+          const unsigned ol = q / I, i = q - ol * I;
+          VU<T> v, d;
+          v.v = *reinterpret_cast<const V*>(src + (size_t)(o0 + ol) * slab + hw * I + i);
+          T* o_ = out + (size_t)o0 * I + q;
+          if (OP == 1) d.v = *reinterpret_cast<const V*>(o_);
+#pragma unroll
+          for (int c = 0; c < W; ++c) v.e[c] = pack_op<T, OP>(OP == 1 ? d.e[c] : (T)0, v.e[c], scale);
+          *reinterpret_cast<V*>(o_) = v.v;
+        }
+        return;
+      }
+      // source order (o, hw, i): coalesced reads of the live rows, stores nl apart
+      for (unsigned e = (unsigned)j0 + threadIdx.x; e < j1u; e += BLOCK) {
+        const unsigned o = e / slab, rem = e - o * slab;
+        const unsigned hw = rem / I, i = rem - hw * I;
+        if (!((live >> hw) & 1u)) continue;
+        T* o_ = out + ((size_t)o * I + i) * nl + tap_rank(live, hw);
+        *o_ = pack_op<T, OP>(OP == 1 ? *o_ : (T)0, src[e], scale);
+      }
+      return;
+    }
+    const bool al = (((uintptr_t)(out + j0)) & 15) == 0;
     if (OP == 0 && al && ((unsigned)a.chunk[lo] % slab) == 0 && ((j1u - (unsigned)j0) & (W - 1)) == 0) {
       // whole (o) slabs per block: a pure stream of zero vectors over the chunk (no index arithmetic: the
       // per-element divisions of the walk below held this 33 MB store stream at 2.3 TB/s), then, behind a
@@ -355,9 +412,12 @@ struct LiveSegs {
 };
 
 // SCATTER = false: comp[k] = full[index(k)];  true: full[index(k)] = comp[k]
+// blockIdx.y: row of a [rows, stride] pair of matrices (hf_live_copy_rows: the snapshots of one solve in one launch)
 template <typename T, bool SCATTER>
 __global__ __launch_bounds__(BLOCK) void k_live_copy(T* __restrict__ full, T* __restrict__ comp,
-                                                     const LiveSegs a) {
+                                                     const LiveSegs a, long long full_stride, long long comp_stride) {
+  full += (long long)blockIdx.y * full_stride;
+  comp += (long long)blockIdx.y * comp_stride;
   int lo = 0, hi = a.ns;
   while (hi - lo > 1) {
     const int mid = (lo + hi) >> 1;
@@ -405,13 +465,61 @@ __global__ __launch_bounds__(BLOCK) void k_live_copy(T* __restrict__ full, T* __
   }
 }
 
+// Are the DEAD entries (taps outside the mask) of up to two flat vectors all zero?  One workgroup per DEAD_CHUNK
+// entries of a masked segment's full range; *flag (zeroed by the host on the same stream) receives 1 from every
+// workgroup that met a dead entry != 0.0 (NaN compares unequal: dirty; -0.0 equal: clean).  Plain loads, plain store.
+constexpr int DEAD_CHUNK = BLOCK * 16;
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_dead_check(const T* __restrict__ va, const T* __restrict__ vb,
+                                                      int* __restrict__ flag, const LiveSegs a) {
+  constexpr int W = VecOf<T>::W;
+  typedef typename VecOf<T>::type V;
+  int lo = 0, hi = a.ns;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (a.blk_start[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
+  }
+  const unsigned hw = (unsigned)a.hw[lo];
+  // (masked segments only: comp_off[] holds their FULL lengths here, see hf_live_dead_check)
+  const long long len = a.comp_off[lo + 1] - a.comp_off[lo];
+  const long long r0 = (long long)((int)blockIdx.x - a.blk_start[lo]) * DEAD_CHUNK;
+  const unsigned cnt = (unsigned)(len - r0 < DEAD_CHUNK ? len - r0 : DEAD_CHUNK);
+  unsigned mask = 0;
+  for (unsigned l = 0; l < (unsigned)a.nl[lo]; ++l) mask |= 1u << a.pos[lo][l];
+  const unsigned t0 = (unsigned)(r0 % hw);  // tap of the block's first entry
+  bool dirty = false;
+  for (int which = 0; which < 2; ++which) {
+    const T* __restrict__ v = which ? vb : va;
+    if (!v) continue;
+    v += a.full_off[lo] + r0;
+    if ((((uintptr_t)v) & 15) == 0) {
+      const unsigned nv = cnt / W;
+      for (unsigned i = threadIdx.x; i < nv; i += BLOCK) {
+        VU<T> x;
+        x.v = reinterpret_cast<const V*>(v)[i];
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+          const unsigned tap = (t0 + i * W + c) % hw;
+          dirty |= !((mask >> tap) & 1u) && !(x.e[c] == (T)0);
+        }
+      }
+      for (unsigned i = nv * W + threadIdx.x; i < cnt; i += BLOCK)
+        dirty |= !((mask >> ((t0 + i) % hw)) & 1u) && !(v[i] == (T)0);
+    } else {
+      for (unsigned i = threadIdx.x; i < cnt; i += BLOCK)
+        dirty |= !((mask >> ((t0 + i) % hw)) & 1u) && !(v[i] == (T)0);
+    }
+  }
+  if (__syncthreads_or(dirty) && threadIdx.x == 0) *flag = 1;
+}
+
 }  // namespace
 
 // ---- vector helpers -------------------------------------------------------
 template <typename T>
 static int pack_impl(void* dst, const void* const* srcs, const int64_t* numels,
-                     const int64_t* perm, const int64_t* splits, const int64_t* live, int nt,
-                     double scale, int mode, hipStream_t s) {
+                     const int64_t* perm, const int64_t* splits, const int64_t* live, const int64_t* compact,
+                     int nt, double scale, int mode, hipStream_t s) {
   int t = 0;
   long long off = 0;
   while (t < nt) {
@@ -420,6 +528,7 @@ static int pack_impl(void* dst, const void* const* srcs, const int64_t* numels,
     int k = 0, blocks = 0;
     while (t < nt && k < PACK_MAXT) {
       if (numels[t] < 0) return HF_ERR_ARG;
+      long long cnt = numels[t];  // entries of tensor t in the destination
       if (numels[t] > 0) {
         if (!srcs[t]) return HF_ERR_ARG;
         a.src[k] = srcs[t];
@@ -453,11 +562,19 @@ static int pack_impl(void* dst, const void* const* srcs, const int64_t* numels,
           else if (a.live[k] != 0 && a.nsplit[k] == 1 && I * HW <= 2 * PACK_CHUNK)
             a.chunk[k] = (int)(((PACK_CHUNK + I * HW - 1) / (I * HW)) * I * HW);  // zero stream + live stores
         }
+        if (compact && compact[t] != 0) {
+          // compact destination: exactly the live taps of a masked tensor, [O, I, popcount(live)]
+          int nl = 0;
+          for (unsigned m = a.live[k]; m; m &= m - 1) ++nl;
+          if (a.live[k] == 0 || compact[t] != nl) return HF_ERR_ARG;
+          a.cnl[k] = (unsigned char)nl;
+          cnt = numels[t] / a.perm_HW[k] * nl;
+        }
         a.blk_start[k] = blocks;
         blocks += (int)((numels[t] + a.chunk[k] - 1) / a.chunk[k]);
         ++k;
       }
-      off += numels[t];
+      off += cnt;
       ++t;
     }
     a.blk_start[k] = blocks;
@@ -474,18 +591,24 @@ static int pack_impl(void* dst, const void* const* srcs, const int64_t* numels,
 
 int hf_pack(void* dst, const void* const* srcs, const int64_t* numels, const int64_t* perm,
             int n_tensors, double scale, int mode, int dtype, void* stream) {
-  return hf_pack_ex(dst, srcs, numels, perm, nullptr, nullptr, n_tensors, scale, mode, dtype, stream);
+  return hf_pack_compact(dst, srcs, numels, perm, nullptr, nullptr, nullptr, n_tensors, scale, mode, dtype, stream);
 }
 
 int hf_pack_ex(void* dst, const void* const* srcs, const int64_t* numels, const int64_t* perm,
                const int64_t* splits, const int64_t* live, int n_tensors, double scale, int mode,
                int dtype, void* stream) {
+  return hf_pack_compact(dst, srcs, numels, perm, splits, live, nullptr, n_tensors, scale, mode, dtype, stream);
+}
+
+int hf_pack_compact(void* dst, const void* const* srcs, const int64_t* numels, const int64_t* perm,
+                    const int64_t* splits, const int64_t* live, const int64_t* compact, int n_tensors, double scale,
+                    int mode, int dtype, void* stream) {
   if (!dst || !srcs || !numels || n_tensors < 0 || (mode != 0 && mode != 1)) return HF_ERR_ARG;
   if (dtype == HF_F32)
-    return pack_impl<float>(dst, srcs, numels, perm, splits, live, n_tensors, scale, mode,
+    return pack_impl<float>(dst, srcs, numels, perm, splits, live, compact, n_tensors, scale, mode,
                             (hipStream_t)stream);
   if (dtype == HF_F64)
-    return pack_impl<double>(dst, srcs, numels, perm, splits, live, n_tensors, scale, mode,
+    return pack_impl<double>(dst, srcs, numels, perm, splits, live, compact, n_tensors, scale, mode,
                              (hipStream_t)stream);
   return HF_ERR_ARG;
 }
@@ -493,12 +616,12 @@ int hf_pack_ex(void* dst, const void* const* srcs, const int64_t* numels, const 
 template <typename T>
 static int unpack_impl(const void* src, void* const* dsts, const int64_t* src_offs,
                        const int64_t* numels, const int64_t* slabs, const int64_t* inners,
-                       const int64_t* live, const int64_t* halves, int nt, hipStream_t s) {
+                       const int64_t* live, const int64_t* halves, const int64_t* compact, int nt, hipStream_t s) {
   int t = 0;
   while (t < nt) {
     UnpackArgs a;
     int blocks = 0;
-    t = hf_shared::fill_unpack_args<T>(a, &blocks, t, dsts, src_offs, numels, slabs, inners, live, halves, nt, true);
+    t = hf_shared::fill_unpack_args<T>(a, &blocks, t, dsts, src_offs, numels, slabs, inners, live, halves, compact, nt, true);
     if (t < 0) return t;
     if (blocks == 0) continue;
     hipLaunchKernelGGL((k_unpack_tangent<T>), dim3(blocks), dim3(BLOCK), 0, s, (const T*)src, a);
@@ -522,22 +645,27 @@ int hf_unpack_tangent_ex(const void* src, void* const* dsts, const int64_t* src_
 int hf_unpack_weights(const void* src, void* const* dsts, const int64_t* src_offs,
                       const int64_t* numels, const int64_t* slabs, const int64_t* inners,
                       const int64_t* live, const int64_t* halves, int n_tensors, int dtype, void* stream) {
+  return hf_unpack_weights_compact(src, dsts, src_offs, numels, slabs, inners, live, halves, nullptr, n_tensors, dtype,
+                                   stream);
+}
+
+int hf_unpack_weights_compact(const void* src, void* const* dsts, const int64_t* src_offs, const int64_t* numels,
+                              const int64_t* slabs, const int64_t* inners, const int64_t* live, const int64_t* halves,
+                              const int64_t* compact, int n_tensors, int dtype, void* stream) {
   if (!src || !dsts || !src_offs || !numels || !slabs || !inners || n_tensors < 0) return HF_ERR_ARG;
   if (dtype == HF_F32)
-    return unpack_impl<float>(src, dsts, src_offs, numels, slabs, inners, live, halves, n_tensors,
+    return unpack_impl<float>(src, dsts, src_offs, numels, slabs, inners, live, halves, compact, n_tensors,
                               (hipStream_t)stream);
   if (dtype == HF_F64)
-    return unpack_impl<double>(src, dsts, src_offs, numels, slabs, inners, live, halves, n_tensors,
+    return unpack_impl<double>(src, dsts, src_offs, numels, slabs, inners, live, halves, compact, n_tensors,
                                (hipStream_t)stream);
   return HF_ERR_ARG;
 }
 
-int hf_live_copy(void* full, void* compact, int scatter, const int64_t* full_offs, const int64_t* counts,
-                 const int64_t* periods, const int64_t* masks, int n_segments, int dtype, void* stream) {
-  if (!full || !compact || !full_offs || !counts || !periods || !masks || n_segments < 1 ||
-      n_segments > LIVE_MAXS)
-    return HF_ERR_ARG;
-  LiveSegs a;
+// The segment table of hf_live_copy / hf_live_dead_check from the host arrays; *total_out: compact length.
+static int fill_live_segs(LiveSegs& a, const int64_t* full_offs, const int64_t* counts, const int64_t* periods,
+                          const int64_t* masks, int n_segments, long long* total_out) {
+  if (!full_offs || !counts || !periods || !masks || n_segments < 1 || n_segments > LIVE_MAXS) return HF_ERR_ARG;
   memset(&a, 0, sizeof(a));
   long long total = 0;
   for (int i = 0; i < n_segments; ++i) {
@@ -561,6 +689,25 @@ int hf_live_copy(void* full, void* compact, int scatter, const int64_t* full_off
   }
   a.comp_off[n_segments] = total;
   a.ns = n_segments;
+  *total_out = total;
+  return HF_OK;
+}
+
+int hf_live_copy(void* full, void* compact, int scatter, const int64_t* full_offs, const int64_t* counts,
+                 const int64_t* periods, const int64_t* masks, int n_segments, int dtype, void* stream) {
+  return hf_live_copy_rows(full, compact, scatter, 1, 0, 0, full_offs, counts, periods, masks, n_segments, dtype,
+                           stream);
+}
+
+int hf_live_copy_rows(void* full, void* compact, int scatter, int64_t rows, int64_t full_stride,
+                      int64_t compact_stride, const int64_t* full_offs, const int64_t* counts, const int64_t* periods,
+                      const int64_t* masks, int n_segments, int dtype, void* stream) {
+  if (!full || !compact || rows < 1 || rows > 65535 || full_stride < 0 || compact_stride < 0) return HF_ERR_ARG;
+  LiveSegs a;
+  long long total = 0;
+  const int rc = fill_live_segs(a, full_offs, counts, periods, masks, n_segments, &total);
+  if (rc) return rc;
+  if (rows > 1 && compact_stride < total) return HF_ERR_ARG;
   // blocks never straddle segments
   long long blocks = 0;
   for (int i = 0; i < n_segments; ++i) {
@@ -571,15 +718,59 @@ int hf_live_copy(void* full, void* compact, int scatter, const int64_t* full_off
   a.blk_start[n_segments] = (int)blocks;
   if (blocks < 1 || blocks > 0x7fffffffLL) return HF_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)blocks, (unsigned)rows);
+  const long long fs = full_stride, cs = compact_stride;
   if (dtype == HF_F32) {
-    if (scatter) hipLaunchKernelGGL((k_live_copy<float, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, (float*)full, (float*)compact, a);
-    else hipLaunchKernelGGL((k_live_copy<float, false>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, (float*)full, (float*)compact, a);
+    if (scatter) hipLaunchKernelGGL((k_live_copy<float, true>), grid, dim3(BLOCK), 0, s, (float*)full, (float*)compact, a, fs, cs);
+    else hipLaunchKernelGGL((k_live_copy<float, false>), grid, dim3(BLOCK), 0, s, (float*)full, (float*)compact, a, fs, cs);
   } else if (dtype == HF_F64) {
-    if (scatter) hipLaunchKernelGGL((k_live_copy<double, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, (double*)full, (double*)compact, a);
-    else hipLaunchKernelGGL((k_live_copy<double, false>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, (double*)full, (double*)compact, a);
+    if (scatter) hipLaunchKernelGGL((k_live_copy<double, true>), grid, dim3(BLOCK), 0, s, (double*)full, (double*)compact, a, fs, cs);
+    else hipLaunchKernelGGL((k_live_copy<double, false>), grid, dim3(BLOCK), 0, s, (double*)full, (double*)compact, a, fs, cs);
   } else {
     return HF_ERR_ARG;
   }
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+int hf_live_dead_check(const void* a_vec, const void* b_vec, void* flag, const int64_t* full_offs,
+                       const int64_t* counts, const int64_t* periods, const int64_t* masks, int n_segments, int dtype,
+                       void* stream) {
+  if (!a_vec || !flag || (dtype != HF_F32 && dtype != HF_F64)) return HF_ERR_ARG;
+  LiveSegs all;
+  long long total = 0;
+  const int rc = fill_live_segs(all, full_offs, counts, periods, masks, n_segments, &total);
+  if (rc) return rc;
+  // keep the masked segments that have dead taps; comp_off[] = running FULL length (one workgroup per DEAD_CHUNK of it)
+  LiveSegs a;
+  memset(&a, 0, sizeof(a));
+  int k = 0;
+  long long len = 0, blocks = 0;
+  for (int i = 0; i < n_segments; ++i) {
+    if (all.hw[i] == 0 || all.nl[i] == all.hw[i]) continue;
+    a.full_off[k] = all.full_off[i];
+    a.hw[k] = all.hw[i];
+    a.nl[k] = all.nl[i];
+    memcpy(a.pos[k], all.pos[i], sizeof(a.pos[k]));
+    a.comp_off[k] = len;
+    a.blk_start[k] = (int)blocks;
+    len += counts[i];
+    blocks += (counts[i] + DEAD_CHUNK - 1) / DEAD_CHUNK;
+    ++k;
+  }
+  a.comp_off[k] = len;
+  a.blk_start[k] = (int)blocks;
+  a.ns = k;
+  hipStream_t s = (hipStream_t)stream;
+  HF_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
+  if (k == 0) return HF_OK;  // nothing is dead: clean
+  if (blocks > 0x7fffffffLL) return HF_ERR_ARG;
+  if (dtype == HF_F32)
+    hipLaunchKernelGGL((k_dead_check<float>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, (const float*)a_vec,
+                       (const float*)b_vec, (int*)flag, a);
+  else
+    hipLaunchKernelGGL((k_dead_check<double>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, (const double*)a_vec,
+                       (const double*)b_vec, (int*)flag, a);
   HF_HIP(hipGetLastError());
   return HF_OK;
 }

@@ -36,6 +36,9 @@ struct UnpackArgs {
   int chunk[PACK_MAXT];  // elements per block
   unsigned short live[PACK_MAXT];  // NHWC, HW <= 16: taps whose slices are copied (0 = all), see PackArgs
   unsigned char half[PACK_MAXT];   // 1: the v_W half of the [W | v_W] operand, 0: the W half
+  // compact source (hf_unpack_weights_compact): tensor t lies at src_off[t] as [O, I, cnl[t]] -- only its live taps,
+  // in increasing order (cnl = popcount(live), NHWC destinations); 0 = flat [O, I, HW]
+  unsigned char cnl[PACK_MAXT];
   int nt;
 };
 
@@ -74,6 +77,38 @@ __device__ __forceinline__ void unpack_block(const T* __restrict__ src_base, con
   // destination order d = (o*HW + hw)*I + i  ->  dst[(o*HW + hw)*2I + half*I + i] = src[(o*I + i)*HW + hw]
   const unsigned HW = slab / I;
   const unsigned live = a.live[lo] ? a.live[lo] : 0xffffffffu;
+  const unsigned nl = a.cnl[lo];
+  if (nl) {  // compact source: src[(o*I + i)*nl + rank(hw)]
+    if (al && I % W == 0 && numel < 0x7fffffffLL) {
+      const unsigned j1u = (unsigned)j1;
+      for (unsigned d = (unsigned)j0 + threadIdx.x * W; d < j1u; d += BLOCK * W) {
+        const unsigned row = d / I;  // o*HW + hw
+        const unsigned i = d - row * I;
+        const unsigned o = row / HW;
+        const unsigned hw = row - o * HW;
+        if (!((live >> hw) & 1u)) continue;
+        const T* s = src + ((size_t)o * I + i) * nl + (unsigned)__popc(live & ((1u << hw) - 1u));
+        VU<T> v;
+        if (nl == 1) {  // one live tap: the quad is contiguous
+          v.v = *reinterpret_cast<const V*>(s);
+        } else {
+#pragma unroll
+          for (int c = 0; c < W; ++c) v.e[c] = s[c * nl];
+        }
+        *reinterpret_cast<V*>(dst + (size_t)row * 2 * I + i) = v.v;
+      }
+    } else {
+      for (long long d = j0 + threadIdx.x; d < j1; d += BLOCK) {
+        const long long row = d / I;
+        const unsigned i = (unsigned)(d - row * I);
+        const long long o = row / HW;
+        const unsigned hw = (unsigned)(row - o * HW);
+        if (!((live >> hw) & 1u)) continue;
+        dst[row * 2 * I + i] = src[(o * I + i) * nl + __popc(live & ((1u << hw) - 1u))];
+      }
+    }
+    return;
+  }
   if (al && I % W == 0 && numel < 0x7fffffffLL) {
     const unsigned j1u = (unsigned)j1;  // (32-bit index arithmetic: see k_pack)
     for (unsigned d = (unsigned)j0 + threadIdx.x * W; d < j1u; d += BLOCK * W) {
@@ -144,7 +179,7 @@ __device__ __forceinline__ bool unpack_transposed_block(const T* __restrict__ sr
 template <typename T>
 inline int fill_unpack_args(UnpackArgs& a, int* blocks_out, int t, void* const* dsts, const int64_t* src_offs,
                             const int64_t* numels, const int64_t* slabs, const int64_t* inners, const int64_t* live,
-                            const int64_t* halves, int nt, bool allow_transposed) {
+                            const int64_t* halves, const int64_t* compact, int nt, bool allow_transposed) {
   // allow_transposed: the caller's kernel runs unpack_transposed_block for half == 2 tensors (k_unpack_tangent does;
   // a launch that only runs unpack_block -- the convolution carrying the scatter -- must refuse them: unpack_block
   // returns without writing anything for such a tensor)
@@ -166,6 +201,13 @@ inline int fill_unpack_args(UnpackArgs& a, int* blocks_out, int t, void* const* 
         a.live[k] = (unsigned short)(live[t] & ((1 << (slab / I)) - 1));
       a.half[k] = (unsigned char)(!halves ? 1 : halves[t] == 0 ? 0 : halves[t] == 2 ? 2 : 1);
       if (a.half[k] == 2 && (I <= 0 || !allow_transposed)) return HF_ERR_ARG;
+      if (compact && compact[t] != 0) {
+        // a compact source holds exactly the live taps of a masked tensor; NHWC destinations, no transposed copies
+        int nl = 0;
+        for (unsigned m = a.live[k]; m; m &= m - 1) ++nl;
+        if (a.live[k] == 0 || compact[t] != nl || a.half[k] == 2) return HF_ERR_ARG;
+        a.cnl[k] = (unsigned char)nl;
+      }
       // (LDS-staged NHWC variants measured slower twice: round 1 30.9 vs 24.5 us; round 3 -- contiguous 16-byte
       // reads into LDS, lane = channel on the way out -- 21.2 vs 14.3 us, scripts/experiments/unpack_time.py)
       a.chunk[k] = PACK_CHUNK;

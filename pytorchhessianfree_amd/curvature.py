@@ -280,12 +280,19 @@ class CapturedOperator:
       then takes its unfused loop.  Under a group ``cg()`` calls ``replay_and_reduce()`` before every K1-K3 launch.
     * ``calls``: products taken, counted by ``cg()`` also for those it replays itself.  ``group``: the process
       group, ``None`` for a single process.  ``op``: the captured eager operator or engine.
+    * ``compact``: ``None``, or an object with this same contract over the ``n_live`` entries of the vector that can
+      be non-zero (:class:`CompactFacet`: its own ``input_buffer`` / ``output_buffer`` / product graph, products
+      counted on this operator) plus ``n_live``, ``gather(full, out)``, ``scatter(compact, out)`` and
+      ``dead_entries_zero(b, x0)``.  ``cg()`` runs its whole solve there when the dead entries of ``b`` and ``x0``
+      are zero (they then stay zero in ``r``, ``p``, ``x``); ``compact_decline`` says why there is none.
 
     The data-parallel all-reduce stays outside the graphs.  Subclasses build on the device's capture stream
     (``_enter_capture``), allocate the two buffers with ``_allocate`` and capture with ``_capture``."""
 
     calls = 0
     group = None
+    compact = None          # (the same product between compact vectors: CompactFacet)
+    compact_decline = None  # (why not)
     _side = None            # (two-phase products: the probed side stream of distributed.two_phase_all_reduce ...)
     side_runs_beside = None  # (... and the probe's verdict)
 
@@ -361,6 +368,74 @@ class CapturedOperator:
         else:
             self.replay_and_reduce()
         return self._result(out)
+
+
+class CompactFacet(CapturedOperator):
+    """The product of a :class:`CapturedOperator` (``parent``) between vectors in the COMPACT layout -- the flat vector
+    with the structurally-zero entries removed (``engine.compact_layout``; the order of ``hf_live_copy``).  A second
+    product graph over the parent's engine: only the scatter that reads ``input_buffer`` and the gather that writes
+    ``output_buffer`` differ from the parent's graph; every launch between them, and every buffer, is shared.
+
+    ``cg()`` solves on a facet exactly as on any captured operator (adopts ``input_buffer`` as ``p``, fuses the
+    product into its iteration graph); products are counted on the parent, and the iteration graphs are kept in the
+    parent's ``_iteration_graphs``."""
+
+    def __init__(self, parent, layout, capture):
+        """``capture(fn, pool)``: the parent's capture on its stream; called inside the parent's build."""
+        eng = parent.engine
+        self.parent, self.op, self.engine, self.layout = parent, eng, eng, layout
+        self.n_live, self.n_full = layout["n_live"], eng.n
+        self.stream = parent.stream
+        self._allocate(self.n_live, torch.float32, eng.dev)
+        self.n = self.n_live
+        self._flag = torch.zeros(1, dtype=torch.int32, device=eng.dev)
+        self.__dict__["_iteration_graphs"] = parent.__dict__.setdefault("_iteration_graphs", {})
+        product = lambda: eng.local_compact(self.input_buffer, self.output_buffer)  # noqa: E731
+        with torch.cuda.stream(self.stream), torch.no_grad():
+            product()  # warm-up (the argument tables of the compact launches)
+        self.stream.synchronize()
+        with torch.no_grad():
+            self.graph = capture(product, parent.graph.pool())
+
+    @property
+    def calls(self):
+        return self.parent.calls
+
+    @calls.setter
+    def calls(self, value):
+        self.parent.calls = value
+
+    def _live_copy(self, full, comp, scatter, rows=1, full_stride=0, comp_stride=0):
+        offs, counts, periods, masks, ns = self.layout["segs"]
+        _lib.check(_lib.load().hf_live_copy_rows(
+            _lib.c_void_p(full.data_ptr()), _lib.c_void_p(comp.data_ptr()), int(scatter), rows, full_stride, comp_stride,
+            offs, counts, periods, masks, ns, _lib.dtype_code(full.dtype), _lib.current_stream_ptr(full.device)),
+            "hf_live_copy_rows")
+
+    def gather(self, full, out=None):
+        """The live entries of the flat vector ``full``, in the compact layout."""
+        if out is None:
+            out = torch.empty(self.n_live, dtype=full.dtype, device=full.device)
+        self._live_copy(full, out, False)
+        return out
+
+    def scatter(self, compact, out):
+        """``compact`` into the live entries of ``out`` (a flat vector, or the rows of a [rows, stride] pair:
+        all rows in one launch); the dead entries of ``out`` are left as they are."""
+        if compact.dim() == 2:
+            self._live_copy(out, compact, True, compact.shape[0], out.stride(0), compact.stride(0))
+        else:
+            self._live_copy(out, compact, True)
+        return out
+
+    def dead_entries_zero(self, b, x0=None):
+        """Whether every dead entry of ``b`` (and ``x0``) is zero: one launch, one host wait."""
+        offs, counts, periods, masks, ns = self.layout["segs"]
+        _lib.check(_lib.load().hf_live_dead_check(
+            _lib.c_void_p(b.data_ptr()), _lib.c_void_p(x0.data_ptr()) if x0 is not None else None,
+            _lib.c_void_p(self._flag.data_ptr()), offs, counts, periods, masks, ns, _lib.dtype_code(b.dtype),
+            _lib.current_stream_ptr(b.device)), "hf_live_dead_check")
+        return int(self._flag.item()) == 0
 
 
 class GraphedOperator(CapturedOperator):

@@ -237,7 +237,8 @@ class _AdjointSweep:
             tensors[self.pfw] = g_fw
             if self.pfb is not None:
                 tensors[self.pfb] = g_fb
-        _lib.pack_ex(out, tensors, perms, splits, scale=self.weight, live=self._pack_live)
+        _lib.pack_ex(out, tensors, perms, splits, scale=self.weight, live=self._pack_live,
+                     compact=getattr(self, "_compact_nl", None))  # (local_compact: the compact layout)
         return out
 
     def _gather_range(self, out, g_fw, g_fb, lo, hi):

@@ -338,10 +338,17 @@ class _Buffers:
         if not (self._carry_ok and u.im2col and self._slot_list):
             return False
         n, h, w, c, k, r, s_, st, pd = u.geo
-        rc = _lib.load().hf_conv2d_nhwc_slabs_unpack(
-            _ptr(u.tbuf), _ptr(u.cols), _ptr(mat), n, h, w, c, k, r, s_, st[0], st[1], pd[0], pd[1], 0, 0, splits,
-            u.tbuf.shape[1], _ptr(src), *_lib.unpack_table(src, self._slot_list, half=half), _lib.HF_F32,
-            _lib.current_stream_ptr(self.dev))
+        table = _lib.unpack_table(src, self._slot_list, half=half)
+        periods = _lib.compact_periods(self._slot_list)
+        if periods is not None:  # (local_compact: ``src`` is a vector in the compact layout)
+            rc = _lib.load().hf_conv2d_nhwc_slabs_unpack_compact(
+                _ptr(u.tbuf), _ptr(u.cols), _ptr(mat), n, h, w, c, k, r, s_, st[0], st[1], pd[0], pd[1], 0, 0, splits,
+                u.tbuf.shape[1], _ptr(src), *table[:-1], periods, table[-1], _lib.HF_F32,
+                _lib.current_stream_ptr(self.dev))
+        else:
+            rc = _lib.load().hf_conv2d_nhwc_slabs_unpack(
+                _ptr(u.tbuf), _ptr(u.cols), _ptr(mat), n, h, w, c, k, r, s_, st[0], st[1], pd[0], pd[1], 0, 0, splits,
+                u.tbuf.shape[1], _ptr(src), *table, _lib.HF_F32, _lib.current_stream_ptr(self.dev))
         if rc == _lib.HF_ERR_ARG:
             self._carry_ok = False
             return False

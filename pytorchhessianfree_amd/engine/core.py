@@ -324,6 +324,30 @@ class FusedGGNEngine(_Topology, _Buffers, _Forward, _TangentSweep, _AdjointSweep
         self.calls += 1
         return self.reduce(self.local(v, out))
 
+    # ---- the product between vectors in the compact layout (dataparallel.compact_layout) ----------------
+    supports_compact = True
+
+    def local_compact(self, vc, out):
+        """``local`` on the entries that can be non-zero: ``vc`` and ``out`` are vectors of ``n_live`` entries in
+        the compact layout.  Same launches, same buffers, same kernels as ``local``: only the scatter of the v_W
+        halves reads, and the gather of the gradients writes, the compact layout (``hf_unpack_weights_compact``,
+        ``hf_pack_compact``), and every slice of the vector is taken at its compact offset.  With dead entries of
+        ``v`` zero, ``local_compact(gather(v)) == gather(local(v))`` bit for bit."""
+        lay = self.compact_layout()
+        if lay is None or self.hessian or not self.supports_compact:
+            raise RuntimeError("engine: no compact layout for this product")
+        slots = self.__dict__.get("_compact_slots")
+        if slots is None:
+            slots = self._compact_slots = [
+                (lay["offs"][u.pw],) + self._tangent_slots[id(u)][1:] + (lay["nl"].get(u.pw, 0),)
+                for u in self.units if id(u) in self._tangent_slots]
+        saved = self._offs, self._slot_list
+        self._offs, self._slot_list, self._compact_nl = lay["offs"], slots, lay["nl"]
+        try:
+            return self.local(vc, out=out)
+        finally:
+            (self._offs, self._slot_list), self._compact_nl = saved, None
+
 
     # ---- safety net --------------------------------------------------------------------------
     # relative max-norm distance to the autograd product above which the engine is refused; fp32

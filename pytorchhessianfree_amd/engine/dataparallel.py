@@ -32,6 +32,61 @@ class _DataParallel:
         self._gather_range(out, None, None, 0, first)
 
     # ---- data parallelism: only the entries that can be non-zero travel ----------------------
+    def _segment_table(self):
+        """THE segment table of the flat vector (the one place that derives it): consecutive segments
+        ``(full offset, count in the full vector, period, mask)`` -- dense runs (period 0) and conv weights
+        ``[O, I, period]`` of which only the kernel taps in ``mask`` can be non-zero (``_live_taps``) --, the number of
+        dead entries, and the masked parameters ``{index: unit}``.  The order of the live entries, segment after
+        segment, is the COMPACT layout: ``hf_live_copy``, the data-parallel staging vector (a suffix of it) and the
+        compact PCG solve (all of it, ``compact_layout``) share it."""
+        masked = {u.pw: u for u in self.units if not u.im2col and getattr(u, "live", 0) and u.pw is not None}
+        segs, dead, run_start = [], 0, None  # (full offset, count in the full vector, period, mask)
+        brk = getattr(self, "_seg_break", None)  # parameter index at which a dense run must end
+        self._seg_cut = None                     # (chunked all-reduce: the suffix starts a segment)
+        for i, p in enumerate(self.params):
+            off = self._offs[i]
+            if i == brk:
+                if run_start is not None:
+                    segs.append((run_start, off - run_start, 0, 0))
+                    run_start = None
+                self._seg_cut = (len(segs), off - dead)  # (segment index, compact offset) of the suffix
+            if i in masked:
+                if run_start is not None:
+                    segs.append((run_start, off - run_start, 0, 0))
+                    run_start = None
+                u = masked[i]
+                rs = p.shape[2] * p.shape[3]
+                segs.append((off, p.numel(), rs, u.live))
+                dead += p.numel() // rs * (rs - bin(u.live).count("1"))
+            elif run_start is None:
+                run_start = off
+        if run_start is not None:
+            segs.append((run_start, self.n - run_start, 0, 0))
+        return segs, dead, masked
+
+    def compact_layout(self):
+        """The compact layout of the whole vector for a PCG solve on the entries that can be non-zero, or ``None``
+        (nothing is dead, or more segments than ``hf_live_copy`` takes): dict with ``n_live``, ``offs`` (compact
+        offset of every parameter), ``nl`` (``{parameter index: live taps}`` of the masked tensors) and ``segs``
+        (the ``hf_live_copy`` arrays of ALL segments)."""
+        if "_compact_layout" not in self.__dict__:
+            self._compact_layout = None
+            had_cut = getattr(self, "_seg_cut", None)
+            segs, dead, masked = self._segment_table()
+            self._seg_cut = had_cut
+            if masked and dead > 0 and len(segs) <= 24:
+                offs, gone = [], 0
+                for i, p in enumerate(self.params):
+                    offs.append(self._offs[i] - gone)
+                    if i in masked:
+                        rs = p.shape[2] * p.shape[3]
+                        gone += p.numel() // rs * (rs - bin(masked[i].live).count("1"))
+                arr = lambda col: (_lib.c_int64 * len(segs))(*[sg[col] for sg in segs])  # noqa: E731
+                self._compact_layout = {"n_live": self.n - dead, "offs": offs,
+                                        "nl": {i: bin(u.live).count("1") for i, u in masked.items()},
+                                        "segs": (arr(0), arr(1), arr(2), arr(3), len(segs)), "table": segs}
+        return self._compact_layout
+
     def _live_segments(self):
         """Description of the product's entries that are not structurally zero -- the weight slices of
         kernel taps that never meet data are zero on every rank (``_live_taps``) --, or ``None`` when
@@ -43,29 +98,7 @@ class _DataParallel:
         the compact staging vector by ``hf_live_copy``, all-reduced there and scattered back."""
         if not hasattr(self, "_live_segs"):
             self._live_segs = None
-            masked = {u.pw: u for u in self.units if not u.im2col and getattr(u, "live", 0) and u.pw is not None}
-            segs, dead, run_start = [], 0, None  # (full offset, count in the full vector, period, mask)
-            brk = getattr(self, "_seg_break", None)  # parameter index at which a dense run must end
-            self._seg_cut = None                     # (chunked all-reduce: the suffix starts a segment)
-            for i, p in enumerate(self.params):
-                off = self._offs[i]
-                if i == brk:
-                    if run_start is not None:
-                        segs.append((run_start, off - run_start, 0, 0))
-                        run_start = None
-                    self._seg_cut = (len(segs), off - dead)  # (segment index, compact offset) of the suffix
-                if i in masked:
-                    if run_start is not None:
-                        segs.append((run_start, off - run_start, 0, 0))
-                        run_start = None
-                    u = masked[i]
-                    rs = p.shape[2] * p.shape[3]
-                    segs.append((off, p.numel(), rs, u.live))
-                    dead += p.numel() // rs * (rs - bin(u.live).count("1"))
-                elif run_start is None:
-                    run_start = off
-            if run_start is not None:
-                segs.append((run_start, self.n - run_start, 0, 0))
+            segs, dead, masked = self._segment_table()
             # the in-place prefix: leading dense segments (at most two: a chunk break may cut the run), each
             # worth a collective of its own (>= 1 MB) and 16-byte aligned
             n_pre, prefix = 0, 0

@@ -64,6 +64,7 @@ class DenseStackEngine(FusedGGNEngine):
     supports_hessian = True
     supports_session = False  # (per instance: True once the constructor has set up the session mode)
     supports_two_phase = False
+    supports_compact = False  # (no kernel taps, no dead entries: solves stay full-length)
     # acc_step builds one engine per data chunk and sums their products: not served here (asked before anything is built)
     acc_decline = "the dense-stack engine serves step() sessions only"
     session_decline = None    # why THIS engine, built with HF_DENSE_SESSION=1, has no session mode

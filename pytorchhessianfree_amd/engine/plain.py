@@ -24,6 +24,7 @@ class PlainStackEngine(FusedGGNEngine):
     # (g: first-order cotangent of the step, g': its tangent; ReLU masks are piecewise constant), all four
     # in ONE grouped launch whose extra results are simply more split-K slabs for the consumers to sum.
     supports_hessian = True
+    supports_compact = False  # (its own ``local``: no product between compact vectors)
     _extras_default = 1
 
     def _layout(self, model):

@@ -178,6 +178,9 @@ class HessianFree(_Accumulation, _SessionSteps, torch.optim.Optimizer):
                 "product": "two-phase (chunked / overlapped all-reduce)" if sess.split is not None
                            else "single graph + one compact all-reduce",
                 "validation": getattr(sess, "mode_validation", None), "timing_ms": getattr(sess, "mode_timing", None)}
+        if out["step"] is not None and out["step"]["path"] == "session" and hasattr(sess, "compact_report"):
+            # whether the session's PCG solves run on the entries that can be non-zero only, or why not
+            out["pcg_solve"] = sess.compact_report()
         return out
 
     def _note_path(self, kind, path, decline=None):

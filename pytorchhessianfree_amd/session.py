@@ -34,7 +34,7 @@ import os
 
 import torch
 
-from .curvature import CapturedOperator
+from .curvature import CapturedOperator, CompactFacet
 from .distributed import two_phase_all_reduce
 from .engine import FusedGGNEngine, loss_spec_of
 
@@ -160,10 +160,6 @@ class _Session(CapturedOperator):
 
 
 class EngineSession(_TwoPhaseProduct, _Session):
-    mode = ("persistent session: hipGraph replay of the " + FusedGGNEngine.mode
-            + "; engine, product graph and PCG iteration graph kept across steps, forward pass / "
-              "gradient / trial losses as graph replays on static buffers")
-
     # ------------------------------------------------------------------------------------
     @classmethod
     def try_create(cls, loss, outputs, params, weight=1.0, group=None, hessian=False, why=None):
@@ -243,6 +239,7 @@ class EngineSession(_TwoPhaseProduct, _Session):
             self._split_plan = self.split
             if self.split is not None:
                 self._capture_phases()
+        self._build_compact(eng)
         # (data parallel: ``choose_product_mode`` validates the forms on the live communicator -- and, policy
         # ``auto``, times them -- before the first solve)
         self.mode_pending = eng.group is not None
@@ -254,6 +251,44 @@ class EngineSession(_TwoPhaseProduct, _Session):
         self._signature = self._signature_of(eng)
         self._layers = eng.layer_signature()
         self._diag_graphs = {}
+
+    # ---- the PCG solve on the entries that can be non-zero ---------------------------------
+    def _build_compact(self, eng):
+        """``self.compact``: a second product graph between vectors in the compact layout (``CompactFacet``), when the
+        vector has dead entries that stay zero through a solve; else ``None`` and ``compact_decline`` says why."""
+        self.compact, self.compact_decline = None, None
+        layout = eng.compact_layout() if getattr(eng, "supports_compact", False) else None
+        if not getattr(eng, "supports_compact", False):
+            self.compact_decline = f"{type(eng).__name__} has no product between compact vectors"
+        elif layout is None:
+            self.compact_decline = "no structurally-zero entries in this model's parameter vector"
+        elif eng.group is not None:
+            self.compact_decline = "data-parallel session (its all-reduce is compact already; the solve is a follow-up)"
+        elif self.hessian:
+            self.compact_decline = ("Hessian products read the vector's weight slices as transposed copies, which have "
+                                    "no compact form")
+        elif getattr(eng, "_l2", None) is not None:
+            self.compact_decline = ("the loss carries a quadratic (L2) term: gradient and product are not zero on the "
+                                    "entries of taps that never meet data")
+        else:
+            self.compact = CompactFacet(self, layout, lambda fn, pool: self._capture(fn, keep=True, pool=pool))
+
+    @property
+    def mode(self):
+        c = self.compact
+        return (("persistent session: hipGraph replay of the " + FusedGGNEngine.mode
+                 + "; engine, product graph and PCG iteration graph kept across steps, forward pass / "
+                   "gradient / trial losses as graph replays on static buffers")
+                + (f"; PCG solve on the compact vector: n_live = {c.n_live} of {self.n} entries (the others are "
+                   "structurally zero)" if c is not None else ""))
+
+    def compact_report(self):
+        """For ``HessianFree.path_report()``: whether solves run on the compact vector, or why not."""
+        if self.compact is not None:
+            return {"path": "compact", "what": "PCG solves on the entries of the parameter vector that can be non-zero",
+                    "declined": None, "n_live": self.compact.n_live, "n": self.n}
+        return {"path": "full-length", "what": "PCG solves on the full-length parameter vector",
+                "declined": self.compact_decline, "n_live": None, "n": self.n}
 
     # ---- validity ------------------------------------------------------------------------
     @staticmethod
