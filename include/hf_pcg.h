@@ -409,6 +409,11 @@ int hf_chan_affine_train_pair(const hf_affine_train_problem* problems /* [2] */,
  * One-pass batch statistics of a train-mode BatchNorm in the engine's own forward pass (optimizer.py:216-229,
  * :288-294 on a model in train mode): a_out (nullable) = sum of `splits` slabs of a (split order), per-channel
  * sum a and sum a^2 in fp64 per row block -> `part`: [row_blocks, 2, c] doubles.  hf_bn_forward_train finalises them.
+ * Rounding sequence: the slabs are added in fp32 in split order (a_out is bitwise that sum); each value and its square
+ * (exact in fp64) are then accumulated in fp64 -- per thread over rows ty, ty + RP, ... of the workgroup's share of
+ * ceil(rows / row_blocks) rows, then over the row groups in a fixed order: at most (rows of the share) fp64 additions
+ * on any path.  A share that starts behind the last row writes exact zeros.  fp32 NHWC, c % 4 == 0, c <= 1024;
+ * HF_ERR_ARG otherwise, HF_ERR_ALIGN for a / a_out off the 16-byte grid or slab_stride % 4 != 0.
  */
 int hf_bn_stats_rows(void* a_out, const void* a, int splits, int64_t slab_stride, void* part, int64_t rows, int64_t c,
                      int row_blocks, int dtype, void* stream);
@@ -419,6 +424,13 @@ int hf_bn_stats_rows(void* a_out, const void* a, int splits, int64_t slab_stride
  * up (fixed order), forms mean, biased variance = E[a^2] - mean^2 (fp64) and rstd = 1/sqrt(var + eps), applies  y = act(((a - mean)*rstd)*w + b + res)  to its share (`a`: the summed convolution output), and
  * workgroup 0 writes mean / rstd and moves the running statistics as torch.nn.BatchNorm2d's
  * forward does (momentum < 0: not): r <- (1 - momentum) r + momentum * {mean, var * count/(count - 1)}.  fp32 NHWC, c % 4 == 0.
+ * Rounding sequence: the partial rows, mean, variance (clamped at 0), var + eps, sqrt, 1/x and the running updates are
+ * fp64; eps and momentum are rounded to fp32 at the launch; mean and rstd are rounded to fp32 ONCE each (what is
+ * stored is what normalises); the running mean moves towards the ROUNDED mean, the running variance towards the fp64
+ * unbiased variance (count == 1: the biased one), each stored with one rounding; y = ((a - mean)*rstd)*w, + b, + res
+ * in fp32, in this order.  mean / rstd / the running statistics are written by workgroup 0 alone; momentum < 0 or a
+ * NULL running pointer: the running buffers are not touched.  c <= 1024, y2_ld / res_ld >= c and multiples of 4
+ * (HF_ERR_ARG); y, y2, a, part, w, b, res on the 16-byte grid (HF_ERR_ALIGN).
  */
 int hf_bn_forward_train(void* y, void* y2, int64_t y2_ld, const void* a, const void* part, int nparts, void* mean,
                         void* rstd, void* running_mean, void* running_var, double count, double eps, double momentum,
@@ -674,9 +686,16 @@ int hf_maxpool_adjoint_nhwc(void* g, const void* gy_a, int a_splits, int64_t a_s
  * v_b, g_b nullable; p = softmax(logits) [rows, classes].  g_w and g_b are written as
  * hf_linear_ce_head_slabs(rows) PARTIAL sums (one per workgroup, classes*features resp. classes
  * elements apart) that hf_pack_ex adds up (`splits`), like split-K weight gradients.  Small heads
- * only: classes <= 64, features <= 512 and a multiple of 4, (2*classes + 4)*features floats within
- * 64 KB of LDS -- returns -1 otherwise (the caller keeps the GEMM path).  Replaced: 4 rocBLAS
- * GEMMs, a reduction and hf_softmax_ce_hvp.
+ * only: rows <= 4096, classes <= 64, features <= 512 and a multiple of 4, (2*classes + 4)*features +
+ * 4*classes floats (W, V_W, the workgroup's four feature rows and its four rows of HJv) within
+ * 64 KB of LDS, g_feat / g_w / t_feat / feat / w / v_w on the 16-byte grid -- returns -1 otherwise
+ * (the caller keeps the GEMM path).  Replaced: 4 rocBLAS GEMMs, a reduction and hf_softmax_ce_hvp.
+ * Rounding sequence (all fp32 but the dot product): lane l of a row's wave holds the float4 chunks
+ * l, l + 64 of the features and runs two interleaved fma chains over them (4 fmas per chain and
+ * chunk: t_feat*W, then feat*V_W), adds the two, six butterfly additions across the wave, + v_b;
+ * <p, Jv> is accumulated in fp64 and rounded once; `scale` is rounded to fp32; Jv - d, p*(.),
+ * scale*(.).  g_feat: one fma per class, in class order.  Slab g of g_w: one fma per row 4g .. 4g+3
+ * in row order; of g_b: their sum in row order; rows past the end contribute exact zeros.
  */
 int hf_linear_ce_head(void* g_feat, void* g_w, void* g_b, const void* t_feat, const void* feat, const void* w,
                       const void* v_w, const void* v_b, const void* p, double scale, int64_t rows,

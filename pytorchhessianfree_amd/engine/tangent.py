@@ -11,6 +11,15 @@ from .. import _lib
 from .common import _ptr
 
 
+def head_fused_shape_ok(rows, features, classes):
+    """The shapes ``hf_linear_ce_head`` accepts (``hf_head.hip``: its argument check): up to 4096 rows, 64 classes and
+    512 features in quads, with W, V_W, the workgroup's four feature rows and its four rows of HJv within 64 KB of LDS.
+    A head outside this keeps the GEMM path."""
+    lds = (2 * classes * features + 4 * features + 4 * classes) * 4
+    return (1 <= rows <= 4096 and 1 <= classes <= 64 and 4 <= features <= 512 and features % 4 == 0
+            and lds <= 64 * 1024)
+
+
 class _TangentSweep:
     def _bn_tangent(self, u, v, add, add_ld):
         """t_y = mask * (sum(T slabs) * w*rstd + xhat * v_w + v_b + add), into the consumer's operand."""
@@ -225,9 +234,9 @@ class _TangentSweep:
             k, f = fw.shape
             ok = (
                 self._ce is not None and hw == 1
-                and fw.is_contiguous() and fw.dtype == torch.float32 and k <= 64 and f <= 512 and f % 4 == 0
+                and fw.is_contiguous() and fw.dtype == torch.float32
+                and head_fused_shape_ok(self.logits.shape[0], f, k)
                 and self.feat.is_contiguous() and tuple(self.feat.shape) == (self.logits.shape[0], f)
-                and self.logits.shape[0] <= 4096 and ((2 * k + 4) * f + 4 * k) * 4 <= 64 * 1024
                 and self._offs[self.pfw] % 4 == 0 and self._ce[0].is_contiguous()
             )
             if ok:

@@ -531,3 +531,283 @@ def train_inputs(rows, c, splits, nparts):
     gen = gen_of("trainparts", rows, c, splits, nparts)
     o.px, o.p1 = randn(gen, nparts, c) * 3, randn(gen, nparts, c) * 3
     return o
+
+
+# =================================================================================================================
+# Train-mode BatchNorm forward (hf_bn_stats_rows, hf_bn_forward_train) and the linear head (hf_linear_ce_head)
+# =================================================================================================================
+# These references run in numpy.longdouble where the kernels run in fp64 (their bounds are stated in U64: a float64
+# reference would err as much as the kernel).  REF64 scales an fp64 rounding count for the reference's own roundings:
+# 1 + 2**-11 with an 80-bit longdouble, 2 where longdouble is float64.
+LDT = np.longdouble
+REF64 = 1.0 + (LD_EPS / 2) / U64
+
+
+def mixed(M, R, M64, R64):
+    """``R*U32*M + R64*U64*M64`` as the M of a comparison with R = 1, u = U32: a result with fp32 roundings on values
+    of magnitude M AND fp64 roundings on (larger, cancelling) values of magnitude M64."""
+    return R * M + (R64 * REF64 * U64 / U32) * M64
+
+
+def _ld(t):
+    return None if t is None else (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)).astype(LDT)
+
+
+def f32_slab_sum(a, upto=None):
+    """The split-order fp32 sum of the slabs [splits, ...]: bitwise what every slab loop of the library leaves."""
+    a = a.numpy()
+    s = a[0].copy()
+    for i in range(1, a.shape[0] if upto is None else upto):
+        s = s + a[i]
+    return torch.from_numpy(s)
+
+
+def bn_stats(a_slabs, row_blocks):
+    """hf_bn_stats_rows: s = split-order fp32 sum of the slabs [splits, rows, c] (bitwise); part[i] = (sum s, sum s*s)
+    over share i of ceil(rows / row_blocks) rows -- exact sums (the square of an fp32 value is exact in fp64), an empty
+    share gives zeros.  Unit U64; ``R[i]`` = the rows of share i (its fp64 additions, at least 1)."""
+    s = f32_slab_sum(a_slabs)
+    sl = _ld(s)
+    c = s.shape[-1]
+    part, M, R = np.zeros((row_blocks, 2, c), LDT), np.zeros((row_blocks, 2, c), LDT), np.ones(row_blocks)
+    for i, (lo, hi) in enumerate(row_shares(s.shape[0], row_blocks)):
+        if lo < hi:
+            blk = sl[lo:hi]
+            part[i, 0], part[i, 1] = blk.sum(0), (blk * blk).sum(0)
+            M[i, 0], M[i, 1] = np.abs(blk).sum(0), part[i, 1]
+            R[i] = hi - lo
+    return NS(s=s, part=part, Mpart=M, R=R)
+
+
+def ratio_rows(got, want, M, R, u=U64):
+    """``ratio`` with one R per leading index (partial rows of shares of different lengths)."""
+    return max(ratio(got[i], want[i], M[i], float(R[i]), u) for i in range(len(R)))
+
+
+def bn_forward_train(s, part, count, eps, momentum, w, b, res, relu, run_mean, run_var):
+    """hf_bn_forward_train on the partial rows AS GIVEN (float64 [nparts, 2, c]) and the summed activation s [rows, c]:
+    mean = S1/count, var = max(S2/count - mean^2, 0), rstd = 1/sqrt(var + eps) (eps exact),
+    running <- (1 - momentum) running + momentum * {mean, var * count/(count - 1)} (count == 1: var), and
+    y = act(((s - mean)*rstd)*w + b + res).  Every result with its fp32 magnitude M and, where fp64 roundings act on
+    larger cancelling values, M64 (see ``r_bn_forward_train`` / ``mixed``)."""
+    p_, sl, w, b, res, rm, rv = (_ld(t) for t in (part, s, w, b, res, run_mean, run_var))
+    count, eps = LDT(count), LDT(eps)
+    S1, S2 = p_[:, 0].sum(0), p_[:, 1].sum(0)
+    Mm, E2 = np.abs(p_[:, 0]).sum(0) / count, np.abs(p_[:, 1]).sum(0) / count
+    mean = S1 / count
+    var = np.maximum(S2 / count - mean * mean, 0)
+    Mvar = E2 + Mm * Mm + eps
+    rstd = 1 / np.sqrt(var + eps)
+    drstd = rstd ** 3 / 2                       # |d rstd / d var|
+    o = NS(mean=mean, Mmean=Mm, var=var, rstd=rstd, Mrstd=rstd + drstd * eps, Mrstd64=rstd + drstd * Mvar)
+    if momentum is not None and momentum >= 0 and rm is not None:
+        mo = LDT(momentum)
+        k = count / (count - 1) if count > 1 else LDT(1)
+        both = abs(1 - mo) + abs(mo)
+        o.rm, o.Mrm = (1 - mo) * rm + mo * mean, both * np.abs(rm) + abs(mo) * Mm
+        o.rv, o.Mrv = (1 - mo) * rv + mo * var * k, both * np.abs(rv) + abs(mo) * var * k
+        o.Mrv64 = o.Mrv + abs(mo) * k * Mvar
+    t = ((sl - mean) * rstd) * w
+    spread = (np.abs(sl) + Mm) * np.abs(w)
+    M, M64 = spread * rstd, spread * o.Mrstd64
+    for term in (b, res):
+        if term is not None:
+            t, M = t + term, M + np.abs(term)
+    o.y, o.My, o.My64 = (np.where(t > 0, t, 0) if relu else t), M, M64
+    return o
+
+
+def r_bn_forward_train(nparts, has_b, has_res):
+    """(R, R64) per result, from the kernel's order.  fp64 (unit U64): nparts - 1 additions per sum, /count; the
+    variance E[a^2] - mean^2 carries the mean's roundings twice (2*nparts), the product, the subtraction, + eps, sqrt,
+    1/x: 2*nparts + 5; the running variance further *count, /(count-1), two products and the addition.  fp32:
+      mean   -- its store;                       rstd -- eps rounded to fp32 and the store (one each on the two
+      terms of Mrstd = rstd + |d rstd/d var| eps);
+      running mean -- momentum rounded to fp32, the ROUNDED mean, the store;   running var -- momentum, the store;
+      y      -- mean's and rstd's stores, eps (half a rounding of rstd, counted as one), a - mean, *rstd, *w, + b, + res."""
+    return NS(mean=(1, nparts), rstd=(1, 2 * nparts + 5), rm=(3, nparts + 3), rv=(2, 2 * nparts + 10),
+              y=(6 + int(has_b) + int(has_res), 2 * nparts + 5))
+
+
+HEAD_ROWS, HEAD_KB = 4, 5        # rows per workgroup / classes per pass of k_linear_ce_head
+
+
+def linear_ce_head(t_feat, feat, w, v_w, v_b, p, scale):
+    """hf_linear_ce_head:  Jv = t_feat W^T + feat V_W^T + v_b;  h = scale * p * (Jv - <p, Jv>);  g_feat = h W;
+    per workgroup g (rows 4g .. 4g+3, those past the end contribute nothing):  g_w[g] = h^T feat, g_b[g] = sum h."""
+    t_feat, feat, w, v_w, v_b, p = (up(t) for t in (t_feat, feat, w, v_w, v_b, p))
+    jv, M = t_feat @ w.t() + feat @ v_w.t(), t_feat.abs() @ w.abs().t() + feat.abs() @ v_w.abs().t()
+    if v_b is not None:
+        jv, M = jv + v_b, M + v_b.abs()
+    d, Md = (p * jv).sum(1, keepdim=True), (p.abs() * M).sum(1, keepdim=True)
+    h, Mh = scale * (p * (jv - d)), abs(scale) * (p.abs() * (M + Md))
+    rows, groups = h.shape[0], -(-h.shape[0] // HEAD_ROWS)
+    sl = [slice(HEAD_ROWS * g, min(HEAD_ROWS * (g + 1), rows)) for g in range(groups)]
+    return NS(jv=jv, Mjv=M, h=h, Mh=Mh, g_feat=h @ w, Mg_feat=Mh @ w.abs(),
+              g_w=torch.stack([h[q].t() @ feat[q] for q in sl]), Mg_w=torch.stack([Mh[q].t() @ feat[q].abs() for q in sl]),
+              g_b=torch.stack([h[q].sum(0) for q in sl]), Mg_b=torch.stack([Mh[q].sum(0) for q in sl]))
+
+
+def head_chunks(features):
+    """template parameter CH of k_linear_ce_head: float4 chunks per lane"""
+    return -(-(features // 4) // 64)
+
+
+def r_linear_ce_head(features, classes, has_bias):
+    """Jv: each lane runs two interleaved fma chains over its CH chunks (4 fmas per chain and chunk), adds the two, six
+    shuffle additions, the bias.  h: + the fp64 dot product rounded once (its six fp64 additions: 6 U64), `scale`
+    rounded to fp32, Jv - d, p*(.), scale*(.).  g_feat: `classes` sequential fmas; a g_w slab: four fmas; a g_b slab:
+    three additions (the first is 0 + h)."""
+    jv = 4 * head_chunks(features) + 1 + 6 + int(has_bias)
+    h = jv + 5 + 6 * U64 / U32
+    return NS(jv=jv, h=h, g_feat=h + classes, g_w=h + HEAD_ROWS, g_b=h + HEAD_ROWS - 1)
+
+
+def head_shape_ok_ref(rows, features, classes):
+    """The entry point's shape rule, from the header: what the host's predicate and the library must both say."""
+    lds = (2 * classes * features + HEAD_ROWS * features + HEAD_ROWS * classes) * 4
+    return 1 <= rows <= 4096 and 1 <= classes <= 64 and 4 <= features <= 512 and features % 4 == 0 and lds <= 65536
+
+
+# ---- thread-map mirrors (what the branch-coverage test asserts the tables reach) ----------------------------------
+BLOCK = 256
+
+
+def stats_map(rows, c, splits, row_blocks):
+    """k_bn_stats_rows: quads, rows per pass RP, idle threads, shares shorter than a pass / empty, and whether the
+    8-deep slab loop ends on a partial batch (and in which pass)."""
+    quads = c // 4
+    rp = BLOCK // quads
+    sh = [hi - lo for lo, hi in row_shares(rows, row_blocks)]
+    passes = -(-(splits - 1) // 8)
+    return NS(quads=quads, RP=rp, idle=BLOCK - rp * quads, short=any(0 < n < rp for n in sh),
+              empty=any(n <= 0 for n in sh), several_passes=any(n > rp for n in sh), slab_passes=passes,
+              partial_batch=(splits - 1) % 8 != 0)
+
+
+def fwd_map(rows, c, nparts):
+    """k_bn_forward_train: prologue lanes, row groups G, column passes, whether nparts exceeds one 4*G batch or leaves
+    it partial, idle prologue threads, and whether the last workgroup has threads without a quad."""
+    lanes = min(c, BLOCK)
+    G = BLOCK // lanes
+    quads = rows * c // 4
+    return NS(lanes=lanes, G=G, col_passes=-(-c // lanes), batches=-(-nparts // (4 * G)), partial=nparts % (4 * G) != 0,
+              groups_without_rows=nparts < G, idle=BLOCK - G * lanes, wgs=-(-quads // BLOCK), have_false=quads % BLOCK != 0)
+
+
+def head_map(rows, features, classes):
+    """k_linear_ce_head: CH, live lanes of the last chunk, KB passes and the clamped surplus of the last one, rows of
+    the last workgroup, LDS bytes."""
+    f4 = features // 4
+    ch = head_chunks(features)
+    return NS(CH=ch, last_chunk_lanes=f4 - 64 * (ch - 1), passes=-(-classes // HEAD_KB), clamped=-classes % HEAD_KB,
+              all_lanes_hold_a_class=classes == 64, last_rows=rows - HEAD_ROWS * ((rows - 1) // HEAD_ROWS),
+              groups=-(-rows // HEAD_ROWS),
+              lds=(2 * classes * features + HEAD_ROWS * features + HEAD_ROWS * classes) * 4)
+
+
+# ---- inputs -------------------------------------------------------------------------------------------------------
+CONST_VALUE = 3.25               # the constant channel (exact in fp32; its sums and squares are exact in fp64)
+BN_EPS, BN_MOMENTUM = 1e-5, 0.1
+
+
+def train_fwd_activation(gen, rows, c):
+    """[rows, c] fp32: channel 0 constant, channel 1 mean ~ 100 / std ~ 0.1 (|mean|/std ~ 1e3), channel 2 std ~ 0.003
+    (variance of the order of eps), the others offset ~ N(0, 1), scale 0.1 ... 10."""
+    off = randn(gen, c, dtype=torch.float64)
+    sc = 10.0 ** (torch.rand(c, generator=gen, dtype=torch.float64) * 2 - 1)
+    off[0], sc[0] = CONST_VALUE, 0.0
+    if c > 1:
+        off[1], sc[1] = 100.0, 0.1
+    if c > 2:
+        off[2], sc[2] = 0.5, 0.003
+    return (off + sc * randn(gen, rows, c, dtype=torch.float64)).float()
+
+
+def stats_inputs(rows, c, splits):
+    """Slabs [splits, rows, c] whose split-order sum has the channels of ``train_fwd_activation``: slabs 1.. are
+    random (channel 0: the constants 0.25 k, so that every partial sum is exact), slab 0 holds the rest."""
+    gen = gen_of("bnstats", rows, c, splits)
+    target = train_fwd_activation(gen, rows, c)
+    a = randn(gen, splits, rows, c)
+    for k in range(1, splits):
+        a[k, :, 0] = 0.25 * k
+    a[0] = (target.double() - a[1:].double().sum(0)).float()
+    return a
+
+
+def share_sums(s, nparts):
+    """float64 [nparts, 2, c]: the exact share sums of s and s*s, rounded once (the forward kernel's input)."""
+    a = torch.zeros(1, *s.shape)
+    a[0] = s
+    return torch.from_numpy(bn_stats(a, nparts).part.astype(np.float64))
+
+
+def train_fwd_inputs(rows, c, nparts):
+    gen = gen_of("bnfwd", rows, c, nparts)
+    o = NS(rows=rows, c=c, nparts=nparts, s=train_fwd_activation(gen, rows, c))
+    o.part = share_sums(o.s, nparts)
+    o.w, o.b, o.rm = (randn(gen, c) for _ in range(3))
+    o.rv = randn(gen, c).abs() + 0.5
+    o.res = randn(gen, rows, c)
+    return o
+
+
+# (c, rows) of the statistics kernel; row_blocks from row_block_choices + one count with empty last shares
+STATS_SHAPES = [(c, r) for c in (4, 12, 96, 256) for r in (3, 37, 200)] + [(1024, 5)]
+STATS_SPLITS = [1, 3, 8, 9, 17, 18, 34]
+# a_out given | NULL;  slab stride dense | larger, NaN in the gap;  a whole NaN slab behind the last
+STATS_FORMS = [NS(a_out=1, gap=0, tail=0), NS(a_out=0, gap=0, tail=1), NS(a_out=1, gap=1, tail=0),
+               NS(a_out=0, gap=1, tail=1), NS(a_out=1, gap=1, tail=1)]
+
+
+def stats_cases():
+    """(rows, c, splits, row_blocks, form index): every row_blocks choice of every shape, splits and forms cycling
+    (5 forms, 7 split counts, 6 to 8 choices: coprime cycles, every split count meets every form)."""
+    out, i = [], 0
+    for c, rows in STATS_SHAPES:
+        for rb in row_block_choices(rows, c) + [rows + 2]:
+            out.append((rows, c, STATS_SPLITS[i % 7], rb, i % 5))
+            i += 1
+    return out
+
+
+FWD_C = [4, 12, 64, 96, 256, 1024]
+FWD_NPARTS = [1, 3, 7, 64, 257]
+# which of y / y2 (y2_ld = 2c);  residual: none | dense | res_ld = 2c;  b;  relu;  statistics: moved | momentum < 0 | NULL
+FWD_OUT, FWD_RES, FWD_STAT = ("y", "y2", "both"), ("none", "dense", "strided"), ("move", "neg", "null")
+
+
+def fwd_form(i):
+    return NS(out=FWD_OUT[i % 3], res=FWD_RES[(i // 3 + i) % 3], b=i % 4 != 3, relu=(i // 2) % 2,
+              stat=FWD_STAT[(i // 5 + i) % 3])
+
+
+def fwd_cases():
+    """(rows, c, nparts, i): c x nparts, rows cycling through sizes with and without a partial last workgroup (c = 1024:
+    3 and 5 rows); i picks the argument form.  Last: rows = count = 1."""
+    out = []
+    for ci, c in enumerate(FWD_C):
+        for pi, nparts in enumerate(FWD_NPARTS):
+            i = len(out)
+            rows = (5, 3)[pi % 2] if c == 1024 else (37, 3, 200, 50, 130)[(ci + pi) % 5]
+            out.append((rows, c, nparts, i))
+    return out + [(1, 12, 1, 0), (1, 1024, 3, 8)]
+
+
+LIN_HEAD_CASES = [(1, 4, 1, 1), (5, 64, 3, 0), (7, 260, 11, 1), (16, 256, 10, 1), (32, 512, 10, 1), (130, 64, 12, 0),
+                  (9, 120, 64, 1), (6, 512, 13, 1), (4, 8, 5, 1), (3, 8, 6, 0)]
+
+
+def linear_head_inputs(rows, features, classes, bias):
+    gen = gen_of("linhead", rows, features, classes, bias)
+    o = NS(rows=rows, features=features, classes=classes, scale=1.0 / rows)
+    o.t_feat, o.feat = randn(gen, rows, features), randn(gen, rows, features)
+    o.w, o.v_w = randn(gen, classes, features), randn(gen, classes, features)
+    o.v_b = randn(gen, classes) if bias else None
+    p = torch.softmax(randn(gen, rows, classes, dtype=torch.float64) * 2, 1)
+    if classes > 1:  # one row with one entry ~ 1 and the rest ~ 1e-8 (as softmax_inputs; not the first row, whose loss
+        p[rows // 2] = 1e-8  # from a slab must show)
+        p[rows // 2, classes // 2] = 1.0 - 1e-8 * (classes - 1)
+    o.p = p.float()
+    return o

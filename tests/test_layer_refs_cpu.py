@@ -4,6 +4,8 @@ formula, in the documented order, lies inside it on the very inputs the GPU test
 variants of that evaluation -- a slab dropped, ``mask_src >= 0``, the neighbouring channel's statistics, the second
 cotangent added behind the mask, a count off by one -- each violate it)."""
 
+from types import SimpleNamespace as NS
+
 import numpy as np
 import pytest
 import torch
@@ -399,3 +401,347 @@ def test_longdouble_references_agree_with_float64_ones():
     b64, bld = L.chan_affine_bwd(o.a, o.b, o.x, o.mean, o.rstd, o.w, o.mask), \
         L.chan_affine_bwd(o.a, o.b, o.x, o.mean, o.rstd, o.w, o.mask, ld=True)
     assert L.ratio(b64.gx, bld.gx, bld.Mgx, L.r_bwd_gx(9, 2), L.U64) <= 1.0
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# train-mode BatchNorm forward (hf_bn_stats_rows, hf_bn_forward_train) and the linear head (hf_linear_ce_head)
+# ---------------------------------------------------------------------------------------------------------------
+f32, f64 = np.float32, np.float64
+
+
+@pytest.mark.parametrize("relu,res", [(0, 0), (1, 1), (0, 1)])
+def test_train_batchnorm_forward_reference_matches_batch_norm(relu, res):
+    """``bn_stats`` + ``bn_forward_train`` = ``F.batch_norm(training=True)`` in float64, the moved running statistics
+    (unbiased variance) included, with residual and ReLU."""
+    gen = torch.Generator().manual_seed(11 + relu)
+    rows, c, splits, rb = 29, 8, 3, 4
+    a = torch.randn(splits, rows, c, generator=gen)
+    w, b, rm = (torch.randn(c, generator=gen) for _ in range(3))
+    rv, r_ = torch.randn(c, generator=gen).abs() + 0.5, (torch.randn(rows, c, generator=gen) if res else None)
+    st = L.bn_stats(a, rb)
+    assert torch.equal(st.s, (a[0] + a[1]) + a[2])
+    ref = L.bn_forward_train(st.s, torch.from_numpy(st.part.astype(f64)), rows, 1e-5, 0.1, w, b, r_, relu, rm, rv)
+    rm64, rv64 = rm.double().clone(), rv.double().clone()
+    want = F.batch_norm(st.s.double().t()[None], rm64, rv64, w.double(), b.double(), True, 0.1, 1e-5)[0].t()
+    if res:
+        want = want + r_.double()
+    want = torch.relu(want) if relu else want
+    s64 = st.s.double()
+    for got, exp in ((ref.y, want), (ref.rm, rm64), (ref.rv, rv64), (ref.mean, s64.mean(0)),
+                     (ref.rstd, (s64.var(0, unbiased=False) + 1e-5).rsqrt())):
+        assert float(np.abs(got.astype(f64) - exp.numpy()).max()) < 1e-12
+    assert float(np.abs((st.part[:, 0].sum(0) / rows).astype(f64) - s64.mean(0).numpy()).max()) < 1e-14
+
+
+@pytest.mark.parametrize("rows,features,classes,bias", [(5, 8, 3, 1), (9, 12, 7, 0)])
+def test_linear_head_reference_matches_autograd(rows, features, classes, bias):
+    """``linear_ce_head`` = J^T H_L J v of ``cross_entropy(linear(feat))`` with respect to (feat, weight, bias), each
+    factor by float64 autograd: J v by forward mode, H_L by double backward through the loss, J^T by a vjp.  (The
+    full Hessian of the composition adds the terms of the bilinear map's own second derivative; the engine adds those
+    outside this kernel.)  The per-workgroup slabs add up to the weight and bias gradients."""
+    gen = torch.Generator().manual_seed(rows + classes)
+    feat, w = _r(gen, rows, features).requires_grad_(), _r(gen, classes, features).requires_grad_()
+    b = _r(gen, classes).requires_grad_()
+    t_feat, v_w, v_b = _r(gen, rows, features), _r(gen, classes, features), _r(gen, classes)
+    if not bias:
+        v_b = v_b * 0
+    target = torch.randint(0, classes, (rows,), generator=gen)
+    logits = F.linear(feat, w, b)
+    _, jv = torch.func.jvp(F.linear, (feat.detach(), w.detach(), b.detach()), (t_feat, v_w, v_b))
+    z = logits.detach().requires_grad_()
+    (gz,) = torch.autograd.grad(F.cross_entropy(z, target), z, create_graph=True)
+    (hjv,) = torch.autograd.grad((gz * jv).sum(), z)
+    g_feat, g_w, g_b = torch.autograd.grad(logits, (feat, w, b), hjv)
+    ref = L.linear_ce_head(t_feat, feat.detach(), w.detach(), v_w, v_b if bias else None,
+                           torch.softmax(logits.detach(), 1), 1.0 / rows)
+    assert ref.g_w.shape[0] == -(-rows // 4)
+    for got, want in ((ref.jv, jv), (ref.h, hjv), (ref.g_feat, g_feat), (ref.g_w.sum(0), g_w), (ref.g_b.sum(0), g_b)):
+        assert float((got - want).abs().max()) < 1e-13
+    for M, v in ((ref.Mjv, ref.jv), (ref.Mh, ref.h), (ref.Mg_feat, ref.g_feat), (ref.Mg_w, ref.g_w), (ref.Mg_b, ref.g_b)):
+        assert bool((M >= v.abs() * (1 - 1e-12)).all())
+
+
+def emu_bn_stats(a, row_blocks, mut=""):
+    """fp32 slab additions in split order, then per share sequential fp64 sums of s and s*s (as one thread would)."""
+    s = L.f32_slab_sum(a, a.shape[0] - 1 if mut == "drop_slab" else None).numpy()
+    acc_t = f32 if mut == "f32_acc" else f64
+    shares = L.row_shares(s.shape[0], row_blocks)
+    if mut == "neighbour_row":   # the first row of share 1 is added to share 0
+        (l0, h0), (l1, h1) = shares[0], shares[1]
+        shares = [(l0, h0 + 1), (l1 + 1, h1)] + shares[2:]
+    part = np.zeros((row_blocks, 2, s.shape[1]), f64)
+    for i, (lo, hi) in enumerate(shares):
+        a1, a2 = np.zeros(s.shape[1], acc_t), np.zeros(s.shape[1], acc_t)
+        for r in range(lo, hi):
+            v = s[r].astype(acc_t)
+            a1 = a1 + v
+            a2 = a2 + ((s[r] * s[r]).astype(acc_t) if mut == "sq_after_round" else v * v)
+        part[i, 0], part[i, 1] = a1, a2
+    return torch.from_numpy(s), part
+
+
+def _stats_muts(rows, c, splits, rb):
+    """the wrong variants that are not the identity on this case"""
+    per = -(-rows // rb)
+    return ("f32_acc", "sq_after_round") + (("drop_slab",) if splits > 1 else ()) + \
+        (("neighbour_row",) if rb > 1 and rows > per else ())
+
+
+STATS = L.stats_cases()
+_ids = lambda v: str(v).replace(" ", "")  # noqa: E731
+
+
+@pytest.mark.parametrize("rows,c,splits,rb,form", STATS, ids=_ids)
+def test_fp32_evaluation_of_the_batch_statistics_and_its_wrong_variants(rows, c, splits, rb, form):
+    a = L.stats_inputs(rows, c, splits)
+    ref = L.bn_stats(a, rb)
+    s, part = emu_bn_stats(a, rb)
+    assert torch.equal(s, ref.s) and bool((s[:, 0] == L.CONST_VALUE).all())
+    assert L.ratio_rows(part, ref.part, ref.Mpart, ref.R) <= 1.0
+    for i, (lo, hi) in enumerate(L.row_shares(rows, rb)):
+        if lo >= hi:
+            assert not ref.part[i].any() and not ref.Mpart[i].any()   # an empty share: exact zeros, bound zero
+    for mut in _stats_muts(rows, c, splits, rb):
+        s, part = emu_bn_stats(a, rb, mut)
+        assert L.ratio_rows(part, ref.part, ref.Mpart, ref.R) > 1.0, mut
+        assert torch.equal(s, ref.s) == (mut != "drop_slab")   # (a_out is compared bitwise)
+    if rb > 1 and rows > -(-rows // rb):  # the misplaced row cancels in the total: only the single rows show it
+        _, part = emu_bn_stats(a, rb, "neighbour_row")
+        tot, Mt = ref.part.sum(0), ref.Mpart.sum(0)
+        assert L.ratio(part.sum(0), tot, Mt, rows) <= 1.0
+
+
+def emu_bn_forward_train(o, count, eps, momentum, b, res, relu, rm, rv, mut=""):
+    """The kernel's arithmetic in numpy: partial rows added in fp64, mean / var / rstd in fp64 with eps and momentum
+    rounded to fp32 first, one rounding to fp32 each, then y in fp32."""
+    part = o.part.numpy()
+    if mut == "drop_part":
+        part = part[1:]
+    if mut == "f32_sums":
+        S = part.astype(f32)[0].copy()
+        for i in range(1, part.shape[0]):
+            S = S + part.astype(f32)[i]
+        S = S.astype(f64)
+    else:
+        S = np.zeros_like(part[0])
+        for i in range(part.shape[0]):
+            S = S + part[i]
+    count = f64(count)
+    m = S[0] / count
+    var = np.maximum(S[1] / count - m * m, 0.0)
+    e = 0.0 if mut == "no_eps" else f64(f32(eps))
+    unb = var * count / (count - 1.0) if count > 1.0 else var
+    with np.errstate(divide="ignore"):
+        mf, rf = m.astype(f32), (1.0 / np.sqrt((unb if mut == "unbiased_rstd" else var) + e)).astype(f32)
+    out = NS(mean=mf, rstd=rf, rm=None, rv=None)
+    if momentum is not None and momentum >= 0 and rm is not None:
+        mo = f64(f32(momentum))
+        k_old, k_new = (mo, 1.0 - mo) if mut == "swap_momentum" else (1.0 - mo, mo)
+        out.rm = (k_old * rm.numpy().astype(f64) + k_new * mf.astype(f64)).astype(f32)
+        out.rv = (k_old * rv.numpy().astype(f64) + k_new * (var if mut == "biased_running" else unb)).astype(f32)
+    with np.errstate(invalid="ignore"):  # (no_eps: 0 * inf in the constant channel)
+        t = ((o.s.numpy() - mf) * rf) * o.w.numpy()
+    if b is not None:
+        t = t + b.numpy()
+    if mut == "res_after_relu":
+        t = np.maximum(t, f32(0)) + res.numpy()
+    else:
+        if res is not None:
+            t = t + res.numpy()
+        if relu:
+            t = np.maximum(t, f32(0))
+    assert t.dtype == f32
+    out.y = t
+    return out
+
+
+def fwd_worst(got, ref, R):
+    """worst value/bound per result of the forward (the GPU test asserts each on its own)"""
+    w = {"mean": L.ratio(got.mean, ref.mean, L.mixed(ref.Mmean, R.mean[0], ref.Mmean, R.mean[1]), 1),
+         "rstd": L.ratio(got.rstd, ref.rstd, L.mixed(ref.Mrstd, R.rstd[0], ref.Mrstd64, R.rstd[1]), 1),
+         "y": L.ratio(got.y, ref.y, L.mixed(ref.My, R.y[0], ref.My64, R.y[1]), 1)}
+    if got.rm is not None:
+        w["rm"] = L.ratio(got.rm, ref.rm, L.mixed(ref.Mrm, R.rm[0], ref.Mrm, R.rm[1]), 1)
+        w["rv"] = L.ratio(got.rv, ref.rv, L.mixed(ref.Mrv, R.rv[0], ref.Mrv64, R.rv[1]), 1)
+    return w
+
+
+def _fwd_muts(rows, nparts, f):
+    moved = f.stat == "move"
+    return ("no_eps", "f32_sums") + (("unbiased_rstd",) if rows > 1 else ()) + \
+        (("biased_running",) if moved and rows > 1 else ()) + (("swap_momentum",) if moved else ()) + \
+        (("drop_part",) if nparts > 1 else ()) + (("res_after_relu",) if f.relu and f.res != "none" else ())
+
+
+FWD = L.fwd_cases()
+
+
+@pytest.mark.parametrize("rows,c,nparts,i", FWD, ids=_ids)
+def test_fp32_evaluation_of_the_train_forward_and_its_wrong_variants(rows, c, nparts, i):
+    o, f = L.train_fwd_inputs(rows, c, nparts), L.fwd_form(i)
+    b, res = (o.b if f.b else None), (o.res if f.res != "none" else None)
+    mom = L.BN_MOMENTUM if f.stat != "neg" else -1.0
+    rm, rv = (o.rm, o.rv) if f.stat != "null" else (None, None)
+    args = (float(rows), L.BN_EPS, mom, b, res, f.relu, rm, rv)
+    ref = L.bn_forward_train(o.s, o.part, float(rows), L.BN_EPS, mom, o.w, b, res, f.relu, rm, rv)
+    R = L.r_bn_forward_train(nparts, f.b, res is not None)
+    got = emu_bn_forward_train(o, *args)
+    worst = fwd_worst(got, ref, R)
+    assert max(worst.values()) <= 1.0, worst
+    assert (f.stat == "move") == ("rm" in worst)
+    # the constant channel: var clamps to 0, a - mean is exactly 0 and y is exactly b + res
+    assert float(ref.var[0]) == 0.0 and float(got.mean[0]) == L.CONST_VALUE
+    exact = f32(b[0].item() if f.b else 0.0) + (res[:, 0].numpy() if res is not None else np.zeros(rows, f32))
+    assert np.array_equal(got.y[:, 0], np.maximum(exact, 0) if f.relu else exact)
+    for mut in _fwd_muts(rows, nparts, f):
+        w = fwd_worst(emu_bn_forward_train(o, *args, mut=mut), ref, R)
+        assert max(w.values()) > 1.0, (mut, w)
+    # and the fault must show in the result it belongs to
+    if rows > 1 and f.stat == "move":
+        assert fwd_worst(emu_bn_forward_train(o, *args, mut="biased_running"), ref, R)["rv"] > 1.0
+        assert fwd_worst(emu_bn_forward_train(o, *args, mut="swap_momentum"), ref, R)["rm"] > 1.0
+    if rows > 1:
+        assert fwd_worst(emu_bn_forward_train(o, *args, mut="f32_sums"), ref, R)["rstd"] > 1.0
+
+
+def _fma(a, b, c):
+    return (a.astype(f64) * b.astype(f64) + c.astype(f64)).astype(f32)
+
+
+def emu_linear_head(o, mut=""):
+    """k_linear_ce_head in numpy, thread by thread: lane l of a row's wave holds the float4 chunks l, l + 64, ...; two
+    interleaved fma chains, their sum, a six-step butterfly, the bias; <p, Jv> in fp64; h; g_feat by sequential fmas
+    over the classes; the slabs from the workgroup's four rows (zeros for rows past the end)."""
+    rows, F_, K = o.rows, o.features, o.classes
+    ch = L.head_chunks(F_)
+    pad = 256 * ch - F_
+
+    def lanes(t):  # [n, F] -> [n, CH, 64, 4]
+        return np.pad(t.numpy(), ((0, 0), (0, pad))).reshape(t.shape[0], ch, 64, 4)
+
+    W, V = (o.v_w, o.w) if mut == "swap_w" else (o.w, o.v_w)
+    tf, ff, w4, v4 = lanes(o.t_feat)[:, None], lanes(o.feat)[:, None], lanes(W)[None], lanes(V)[None]
+    p0 = p1 = np.zeros((rows, K, 64), f32)
+    for u in range(ch):
+        p0, p1 = _fma(tf[:, :, u, :, 0], w4[:, :, u, :, 0], p0), _fma(tf[:, :, u, :, 1], w4[:, :, u, :, 1], p1)
+        p0, p1 = _fma(tf[:, :, u, :, 2], w4[:, :, u, :, 2], p0), _fma(tf[:, :, u, :, 3], w4[:, :, u, :, 3], p1)
+        p0, p1 = _fma(ff[:, :, u, :, 0], v4[:, :, u, :, 0], p0), _fma(ff[:, :, u, :, 1], v4[:, :, u, :, 1], p1)
+        p0, p1 = _fma(ff[:, :, u, :, 2], v4[:, :, u, :, 2], p0), _fma(ff[:, :, u, :, 3], v4[:, :, u, :, 3], p1)
+    part = p0 + p1
+    for off in (32, 16, 8, 4, 2, 1):
+        part = part + part[..., np.arange(64) ^ off]
+    jv = part[..., 0]
+    if o.v_b is not None and mut != "no_bias":
+        jv = jv + o.v_b.numpy()
+    p = o.p.numpy()
+    pj = p.astype(f64) * jv.astype(f64)
+    if mut == "drop_class":
+        pj = np.delete(pj, K // 2, 1)
+    d = pj.sum(1, keepdims=True).astype(f32)
+    sc = f32(1.0 if mut == "no_scale" else o.scale)
+    h = sc * (p * (jv - d))
+    assert h.dtype == f32
+    wn = W.numpy()
+    gf = np.zeros((rows, F_), f32)
+    for k in range(K):
+        gf = _fma(h[:, k:k + 1], wn[k][None], gf)
+    groups = -(-rows // 4)
+    hp = np.zeros((groups * 4, K), f32)
+    fp = np.zeros((groups * 4, F_), f32)
+    hp[:rows], fp[:rows] = h, o.feat.numpy()
+    if mut == "tail_fill":   # the last workgroup's missing rows filled with the row before them
+        for r in range(rows, groups * 4):
+            hp[r], fp[r] = hp[r - 1], fp[r - 1]
+    if mut == "neighbour_slab":  # row 4 is credited to workgroup 0, row 3 to workgroup 1
+        hp[[3, 4]], fp[[3, 4]] = hp[[4, 3]], fp[[4, 3]]
+    hg, fg = hp.reshape(groups, 4, K), fp.reshape(groups, 4, F_)
+    gw, gb = np.zeros((groups, K, F_), f32), np.zeros((groups, K), f32)
+    for r in range(4):
+        gw = _fma(hg[:, r, :, None], fg[:, r, None, :], gw)
+        gb = gb + hg[:, r]
+    return NS(jv=jv, h=h, g_feat=gf, g_w=gw, g_b=gb)
+
+
+def head_worst(got, ref, R):
+    w = {k: L.ratio(torch.from_numpy(getattr(got, k)), getattr(ref, k), getattr(ref, "M" + k), getattr(R, k))
+         for k in ("g_feat", "g_w", "g_b")}
+    w["sum_w"] = L.ratio(torch.from_numpy(got.g_w.astype(f64).sum(0)), ref.g_w.sum(0), ref.Mg_w.sum(0), R.g_w)
+    w["sum_b"] = L.ratio(torch.from_numpy(got.g_b.astype(f64).sum(0)), ref.g_b.sum(0), ref.Mg_b.sum(0), R.g_b)
+    return w
+
+
+def _head_muts(rows, features, classes, bias):
+    if classes == 1:  # p = 1: Jv - <p, Jv> = 0 exactly, every output is zero whatever else is wrong
+        return ()
+    return ("drop_class", "swap_w") + (("no_bias",) if bias else ()) + (("no_scale",) if rows > 1 else ()) + \
+        (("neighbour_slab",) if rows > 4 else ()) + (("tail_fill",) if rows % 4 else ())
+
+
+@pytest.mark.parametrize("rows,features,classes,bias", L.LIN_HEAD_CASES, ids=_ids)
+def test_fp32_evaluation_of_the_linear_head_and_its_wrong_variants(rows, features, classes, bias):
+    o = L.linear_head_inputs(rows, features, classes, bias)
+    ref = L.linear_ce_head(o.t_feat, o.feat, o.w, o.v_w, o.v_b, o.p, o.scale)
+    R = L.r_linear_ce_head(features, classes, bias)
+    got = emu_linear_head(o)
+    assert L.ratio(torch.from_numpy(got.jv), ref.jv, ref.Mjv, R.jv) <= 1.0
+    assert L.ratio(torch.from_numpy(got.h), ref.h, ref.Mh, R.h) <= 1.0
+    worst = head_worst(got, ref, R)
+    assert max(worst.values()) <= 1.0, worst
+    if classes == 1:
+        assert not got.h.any() and not got.g_feat.any() and not got.g_w.any() and not got.g_b.any()
+    for mut in _head_muts(rows, features, classes, bias):
+        w = head_worst(emu_linear_head(o, mut), ref, R)
+        assert max(w.values()) > 1.0, (mut, w)
+        if mut in ("neighbour_slab", "tail_fill"):
+            assert w["g_w"] > 1.0 and w["g_b"] > 1.0, (mut, w)
+    if rows > 4:  # a row in the neighbouring slab cancels in the sum of the slabs: only the single slabs show it
+        w = head_worst(emu_linear_head(o, "neighbour_slab"), ref, R)
+        assert w["sum_w"] <= 1.0 and w["sum_b"] <= 1.0 and w["g_feat"] <= 1.0
+
+
+def test_case_tables_reach_every_branch_of_the_three_kernels():
+    """Mirrors of the kernels' thread maps (``layer_refs.stats_map`` / ``fwd_map`` / ``head_map``) on the case tables."""
+    sm = [(L.stats_map(r, c, s, rb), r, c, s, rb, L.STATS_FORMS[f]) for r, c, s, rb, f in STATS]
+    assert {m.quads for m, *_ in sm} == {1, 3, 24, 64, 256}
+    assert {m.idle for m, *_ in sm} == {0, 1, 16}              # c = 12: 85 row groups of 3 quads; c = 96: 10 of 24
+    assert {m.RP for m, *_ in sm} >= {256, 1}
+    for c in (4, 12, 96, 256):  # (c = 4 takes 256 rows per pass: no table row has more)
+        assert any(m.short for m, r, c_, *_ in sm if c_ == c)
+        assert c == 4 or any(m.several_passes for m, r, c_, *_ in sm if c_ == c)
+    assert any(m.several_passes for m, r, c_, *_ in sm if c_ == 1024)
+    assert all(any(m.empty for m, r, c_, *_ in sm if c_ == c) for c in (4, 12, 96, 256, 1024))
+    assert {s for _, _, _, s, _, _ in sm} == set(L.STATS_SPLITS)
+    assert {(m.slab_passes, m.partial_batch) for m, *_ in sm} >= {(0, False), (1, True), (1, False), (2, False), (3, True),
+                                                                  (5, True)}
+    for s in L.STATS_SPLITS:
+        forms = [f for _, _, _, s_, _, f in sm if s_ == s]
+        assert {f.a_out for f in forms} == {0, 1} and {f.gap for f in forms} == {0, 1} and {f.tail for f in forms} == {0, 1}
+    for c in (4, 12, 96, 256, 1024):
+        assert {f.a_out for _, _, c_, _, _, f in sm if c_ == c} == {0, 1}
+
+    fm = [(L.fwd_map(r, c, n), r, c, n, L.fwd_form(i)) for r, c, n, i in FWD]
+    assert {m.lanes for m, *_ in fm} == {4, 12, 64, 96, 256} and {m.G for m, *_ in fm} == {64, 21, 4, 2, 1}
+    assert {m.col_passes for m, *_ in fm} == {1, 4} and {m.idle for m, *_ in fm} == {0, 4, 64}
+    for c in L.FWD_C:  # nparts on both sides of one 4*G batch, and nparts == 1, for every c
+        mine = [(m, n) for m, _, c_, n, _ in fm if c_ == c]
+        assert {m.batches > 1 for m, _ in mine} == {False, True} and any(n == 1 for _, n in mine)
+        assert any(n == 257 for _, n in mine) and any(m.partial for m, _ in mine)
+    assert any(m.have_false and m.wgs > 1 for m, *_ in fm) and any(m.have_false and m.wgs == 1 for m, *_ in fm)
+    assert any(not m.have_false for m, *_ in fm) and any(m.groups_without_rows for m, *_ in fm)
+    forms = [f for *_, f in fm]
+    assert {f.out for f in forms} == set(L.FWD_OUT) and {f.res for f in forms} == set(L.FWD_RES)
+    assert {f.stat for f in forms} == set(L.FWD_STAT) and {f.b for f in forms} == {True, False}
+    assert {f.relu for f in forms} == {0, 1} and any(r == 1 for _, r, *_ in fm)
+    assert {(f.out, f.res) for f in forms} >= {("y2", "strided"), ("y", "none"), ("both", "dense")}
+    assert any(f.relu and f.res != "none" for f in forms) and any(f.stat == "move" and not f.b for f in forms)
+
+    hm = [(L.head_map(r, f, k), r, f, k, b) for r, f, k, b in L.LIN_HEAD_CASES]
+    assert {m.CH for m, *_ in hm} == {1, 2} and any(m.CH == 2 and m.last_chunk_lanes == 1 for m, *_ in hm)
+    assert any(m.CH == 2 and m.last_chunk_lanes == 64 for m, *_ in hm) and any(m.CH == 1 and m.last_chunk_lanes == 1 for m, *_ in hm)
+    assert any(m.all_lanes_hold_a_class and m.clamped for m, *_ in hm)
+    assert {m.clamped for m, *_ in hm} >= {0, 1, 4} and any(k == 1 for _, _, _, k, _ in hm)      # 5 | 6 = 5 + 1 | 4, 64 = 65 - 1
+    assert {m.last_rows for m, *_ in hm} == {1, 2, 3, 4} and any(m.groups > 1 and m.last_rows < 4 for m, *_ in hm)
+    assert sorted(m.lds for m, *_ in hm)[-2:] == [61648, 64384] and all(m.lds <= 65536 for m, *_ in hm)
+    assert all(L.head_shape_ok_ref(r, f, k) for _, r, f, k, _ in hm) and {b for *_, b in hm} == {0, 1}
+    for r, f, k in ((1, 124, 64), (1, 512, 14), (0, 4, 1), (4097, 4, 1), (1, 4, 65), (1, 2, 1), (1, 6, 1), (1, 516, 1)):
+        assert not L.head_shape_ok_ref(r, f, k)
