@@ -18,7 +18,11 @@
 //   W  dW [k][tap][c]       = sum_{m}     dY[m][k] * X[pix(m,tap)][c]
 // F and D are one kernel (operands contiguous along the reduction index: "NT"); W reduces
 // over the rows ("TN").  v_mfma_f32_32x32x2_f32, 64x64 block tiles, 4 waves of 32x32,
-// BK = 32, double-buffered LDS, register prefetch of the next tile.
+// BK = 32, double-buffered LDS, a hand-counted register ring of global loads in front of it: three steps deep in
+// the NT body and in the 128-wide configurations, two deep in the 64x64 TN body, whose loop is software-pipelined
+// (pipelined_share).  Measured per wave on MI355X (profiles/r19_conv_step_attribution.json): ~4 us of waiting in
+// front of the first MFMA whatever the step count (kernel arguments, then the first operands), then ~0.55 us per
+// step, 0.43 us of it the sixteen dependent MFMAs.
 //
 // MFMA operand maps (cdna_hip_programming.md section 3): lane l supplies A[i=l&31][k=l>>5],
 // B[k=l>>5][j=l&31]; C/D: col = l&31, row = (reg&3) + 8*(reg>>2) + 4*(l>>5).
@@ -190,6 +194,26 @@ __device__ __forceinline__ int gather_pixel(const ConvArgs& a, int n, int y, int
   return v ? (n * a.sh_ + sy) * a.sw_ + sx : 0;
 }
 
+// The forward rule alone (weight gradients gather through the forward window), for the pipelined K loop: no branch
+// on the direction, and the geometry held in scalar registers for the whole loop -- read through ConvArgs the compiler
+// re-loads a field from the kernel arguments wherever it is used, a scalar load and a wait inside the MFMA chain.
+struct Geom {
+  int sth, stw, ph, pw, sh, sw;
+};
+__device__ __forceinline__ void pin(int& v) { asm volatile("" : "+s"(v)); }
+__device__ __forceinline__ void pin(unsigned& v) { asm volatile("" : "+s"(v)); }
+__device__ __forceinline__ Geom make_geom(const ConvArgs& a) {
+  Geom g = {a.stride_h, a.stride_w, a.pad_h, a.pad_w, a.sh_, a.sw_};
+  pin(g.sth); pin(g.stw); pin(g.ph); pin(g.pw); pin(g.sh); pin(g.sw);
+  return g;
+}
+__device__ __forceinline__ int gather_pixel_fwd(const Geom& g, int n, int y, int x, int r, int q, bool& valid) {
+  const int sy = y * g.sth - g.ph + r, sx = x * g.stw - g.pw + q;
+  const bool v = ((unsigned)sy < (unsigned)g.sh) & ((unsigned)sx < (unsigned)g.sw);
+  valid = v;
+  return v ? (n * g.sh + sy) * g.sw + sx : 0;
+}
+
 __device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 // Staging loads the compiler does not see as loads: hipcc schedules the first use of a loaded
@@ -203,6 +227,125 @@ __device__ __forceinline__ void gload4(f32x4& dst, const float* p) {
 }
 #define HF_WAIT_SLOT(N, A, B) \
   asm volatile("s_waitcnt vmcnt(" #N ")" : "+v"(A[0]), "+v"(A[1]), "+v"(B[0]), "+v"(B[1]) : : "memory")
+
+// ---------------------------------------------------------------------------------
+// K loop of the 64x64 configuration (one accumulator per wave), software-pipelined.
+// ---------------------------------------------------------------------------------
+// A workgroup of these launches walks 1-6 steps with ONE wave per SIMD, so whatever is not issued between the
+// sixteen dependent MFMAs of a step (16 x 64 cycles) sits serially in front of them.  Here step j's MFMAs carry,
+// one piece per MFMA: the wait for and the LDS stash of step j+1 (into the other buffer), the address arithmetic
+// and issue of the next fetch, the step's one barrier, and step j+1's fragment reads (into the other fragment
+// registers).  The register ring is RING steps deep: a share of up to RING steps has every load in flight before
+// the first wait, longer shares refill a slot as soon as it is stashed.  What a wave does in front of its first wait
+// is NOT hidden -- the ring's slots are filled there, dead ones included -- and the weight-gradient shares of the
+// ResNet-18 product are 1-3 steps: measured (profiles/r19_tn_ring_depth.jsonl), a ring of 6 / 4 / 2 gives
+// 1 638 / 1 663 / 1 689 matvecs/s against 1 656 of the three-deep plain ring, so the ring is two deep.
+//   prep(live)            uniform part of the next fetch (and advance to the one after); !live: a step past the
+//                         share's end -- its loads read a dummy address and are stashed as zeros, never multiplied
+//   load(piece, dst)      piece 0..3 = A row 0, B row 0, A row 1, B row 1 of the staging thread: issues ONE
+//                         global_load_dwordx4 (unconditionally: the queue is counted by hand) and returns its ok bit
+//   stash(buf, u, a, b, ok), frag(buf, piece, av, bv): LDS writes of staged row u; a quarter of the fragment reads
+// The order of additions is the plain loop's: steps ascending, MFMA 0..15 of a step on the one accumulator.
+#ifndef HF_CONV_RING
+#define HF_CONV_RING 2  // (A/B knob: depth of the register ring of the pipelined loop; even)
+#endif
+constexpr int RING = HF_CONV_RING;
+#define HF_WAIT_RING(A, B)                                                              \
+  asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(A[0]), "+v"(A[1]), "+v"(B[0]), "+v"(B[1]) \
+               : [n] "n"(4 * (RING - 1)) : "memory")
+#define HF_DRAIN_RING(A, B) \
+  asm volatile("s_waitcnt vmcnt(0)" : "+v"(A[0]), "+v"(A[1]), "+v"(B[0]), "+v"(B[1]) : : "memory")
+
+template <typename Prep, typename Load, typename Stash, typename Frag>
+__device__ __forceinline__ void pipelined_share(int j0, int j1, f32x16& acc, Prep&& prep, Load&& load, Stash&& stash,
+                                                Frag&& frag) {
+  static_assert(RING % 2 == 0 && RING >= 2 && RING <= 14,
+                "LDS buffer and fragment set of a step are compile-time in the unrolled ring; vmcnt counts to 63");
+  f32x4 ra[RING][2], rb[RING][2];
+  unsigned ok[RING];
+  float av[2][16], bv[2][16];
+  if (j0 >= j1) return;
+  // No control flow around a load, anywhere: the compiler does not know that the ring's registers are pending until
+  // the matching wait, and a copy it places at a join of two paths would read them before the data has landed.
+#pragma unroll
+  for (int s = 0; s < RING; ++s) {
+    prep(j0 + s < j1);
+    ok[s] = load(0, ra[s][0]);
+    ok[s] |= load(1, rb[s][0]);
+    ok[s] |= load(2, ra[s][1]);
+    ok[s] |= load(3, rb[s][1]);
+  }
+  HF_WAIT_RING(ra[0], rb[0]);
+  stash(0, 0, ra[0][0], rb[0][0], ok[0]);
+  stash(0, 1, ra[0][1], rb[0][1], ok[0]);
+  prep(j0 + RING < j1);
+  ok[0] = load(0, ra[0][0]);
+  ok[0] |= load(1, rb[0][0]);
+  ok[0] |= load(2, ra[0][1]);
+  ok[0] |= load(3, rb[0][1]);
+  __syncthreads();
+#pragma unroll
+  for (int piece = 0; piece < 4; ++piece) frag(0, piece, av[0], bv[0]);
+#define HF_STEP_MFMA(K) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[p][K], bv[p][K], acc, 0, 0, 0)
+#define HF_SCHED_FENCE __builtin_amdgcn_sched_barrier(0)
+  for (int j = j0; j < j1; j += RING) {
+#pragma unroll
+    for (int s = 0; s < RING; ++s) {
+      if (j + s >= j1) break;  // (uniform)
+      // step j+s: fragments p, staged in LDS buffer p; next step: ring slot n, LDS buffer / fragments q.  Past the
+      // share's end the "next step" is a dead slot: zeros are stashed and read, never multiplied.
+      const int p = s & 1, q = p ^ 1, n = (s + 1) % RING;
+      HF_SCHED_FENCE;
+      HF_STEP_MFMA(0);
+      HF_WAIT_RING(ra[n], rb[n]);
+      HF_SCHED_FENCE;
+      HF_STEP_MFMA(1);
+      stash(q, 0, ra[n][0], rb[n][0], ok[n]);
+      HF_SCHED_FENCE;
+      HF_STEP_MFMA(2);
+      stash(q, 1, ra[n][1], rb[n][1], ok[n]);
+      HF_SCHED_FENCE;
+      HF_STEP_MFMA(3);
+      prep(j + s + 1 + RING < j1);
+      unsigned k = load(0, ra[n][0]);
+      HF_SCHED_FENCE;
+      HF_STEP_MFMA(4);
+      k |= load(1, rb[n][0]);
+      HF_SCHED_FENCE;
+      HF_STEP_MFMA(5);
+      k |= load(2, ra[n][1]);
+      HF_SCHED_FENCE;
+      HF_STEP_MFMA(6);
+      k |= load(3, rb[n][1]);
+      ok[n] = k;
+      HF_SCHED_FENCE;
+      HF_STEP_MFMA(7);
+      __syncthreads();
+      HF_SCHED_FENCE;
+      HF_STEP_MFMA(8);
+      frag(q, 0, av[q], bv[q]);
+      HF_SCHED_FENCE;
+      HF_STEP_MFMA(9);
+      frag(q, 1, av[q], bv[q]);
+      HF_SCHED_FENCE;
+      HF_STEP_MFMA(10);
+      frag(q, 2, av[q], bv[q]);
+      HF_SCHED_FENCE;
+      HF_STEP_MFMA(11);
+      frag(q, 3, av[q], bv[q]);
+      HF_SCHED_FENCE;
+      HF_STEP_MFMA(12);
+      HF_STEP_MFMA(13);
+      HF_STEP_MFMA(14);
+      HF_STEP_MFMA(15);
+      HF_SCHED_FENCE;
+    }
+  }
+#undef HF_STEP_MFMA
+#undef HF_SCHED_FENCE
+#pragma unroll
+  for (int s = 0; s < RING; ++s) HF_DRAIN_RING(ra[s], rb[s]);  // the registers may be reused from here on
+}
 
 // four consecutive floats of which only the first `valid` exist, no alignment assumed
 // (channel counts that are not multiples of 4: the 49-tap im2col of a 1-channel stem)
@@ -571,7 +714,9 @@ __device__ __forceinline__ void conv_nt_body(const ConvArgs& a, float* lds, int 
 // ---------------------------------------------------------------------------------
 // FLAT: the output columns are enumerated flat over (tap, channel) (see Flat96): column tile tile_n covers the
 // flattened columns [tile_n * BN, ...), every staging thread decodes the tap of ITS column quad once.
-template <bool SCALAR, typename C, bool FLAT = false>
+// PIPE: the pipelined K loop (64x64 tiles); the launches that mix tile configurations (ANYBIG) keep the plain ring
+// for their 64x64 problems, and with it the register count their 128-wide problems' occupancy depends on.
+template <bool SCALAR, typename C, bool FLAT = false, bool PIPE = true>
 __device__ __forceinline__ void conv_tn_body(const ConvArgs& a, float* lds, int bid) {
   constexpr int BM = C::BM, BN = C::BN, BK = C::BK, HK = C::HK, LDA = C::LDA, LDB = C::LDB;
   float (*As)[BK][LDA] = reinterpret_cast<float (*)[BK][LDA]>(lds);
@@ -664,7 +809,58 @@ __device__ __forceinline__ void conv_tn_body(const ConvArgs& a, float* lds, int 
   };
   const int jl = j1 - 1;
   int cur = 0;
-  if (!SCALAR) {
+  if constexpr (!SCALAR && PIPE && C::TM * C::TN == 1 && !FLAT) {
+    // 64x64 tiles: the pipelined loop (pipelined_share).  (n, y, x) of a staged row comes from two multiply-high
+    // divisions per load -- branch-free, where the incremental form below walks rw-sized strides in a per-lane loop
+    // (32 trips per step on a 1x1 map, in front of the loads it feeds)
+    const Geom g = make_geom(a);
+    int g_rows = a.rows, g_kout = a.kout, g_cs_ld = a.cs_ld, g_rw = a.rw, g_rh = a.rh;
+    pin(g_rows); pin(g_kout); pin(g_cs_ld); pin(g_rw); pin(g_rh);
+    FastDiv g_frw = a.fd_rw, g_frh = a.fd_rh;
+    pin(g_frw.mul); pin(g_frw.shift); pin(g_frh.mul); pin(g_frh.shift);
+    const float *g_src = a.src, *g_mat = a.mat;
+    int f_m0 = j0 * BK + kr;
+    int p_m0 = 0;
+    bool p_live = false;
+    auto prep = [&](bool live) {
+      p_m0 = f_m0;
+      p_live = live;
+      f_m0 += BK;
+    };
+    auto load = [&](int piece, f32x4& dst) -> unsigned {
+      const int u = piece >> 1;
+      const int m = p_m0 + RP * u;
+      const bool mok = (m < g_rows) & p_live;
+      if (!(piece & 1)) {
+        const bool va = mok & aok;
+        gload4(dst, g_mat + (va ? (size_t)m * g_kout + ka : 0));
+        return (va ? 1u : 0u) << (2 * u);
+      }
+      const int mm = mok ? m : 0;
+      const int tq = (int)fdiv((unsigned)mm, g_frw), xx = mm - tq * g_rw;
+      const int nn = (int)fdiv((unsigned)tq, g_frh), yy = tq - nn * g_rh;
+      bool vb;
+      const int pix = gather_pixel_fwd(g, nn, yy, xx, r, q, vb);
+      vb = vb & mok & bkok;
+      gload4(dst, g_src + (vb ? (size_t)pix * g_cs_ld + cb : 0));
+      return (vb ? 2u : 0u) << (2 * u);
+    };
+    auto stash_u = [&](int buf, int u, const f32x4& ra, const f32x4& rb, unsigned ok) {
+      const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+      *reinterpret_cast<f32x4*>(&As[buf][kr + RP * u][4 * cq]) = (ok >> (2 * u)) & 1u ? ra : zero;
+      *reinterpret_cast<f32x4*>(&Bs[buf][kr + RP * u][4 * cq]) = (ok >> (2 * u)) & 2u ? rb : zero;
+    };
+    auto frag = [&](int buf, int piece, float (&av)[HK], float (&bv)[HK]) {
+      static_assert(HK == 16, "four fragment pieces of eight elements each");
+      const int s0 = 8 * (piece & 1);
+#pragma unroll
+      for (int s = s0; s < s0 + 8; ++s) {
+        if (piece < 2) av[s] = As[buf][HK * h + s][wm * 32 + i];
+        else bv[s] = Bs[buf][HK * h + s][wn * 32 + i];
+      }
+    };
+    pipelined_share(j0, j1, acc[0][0], prep, load, stash_u, frag);
+  } else if (!SCALAR) {
     // the rows of consecutive steps advance by BK: (n, y, x) of each staged row is kept
     // incrementally (the per-step divisions were ~300 VALU instructions per thread and step)
     int f_step = j0, fn_[TU], fy_[TU], fx_[TU];
@@ -807,7 +1003,7 @@ __global__ __launch_bounds__(CT) void k_conv_dw(const ConvArgs d, const ConvArgs
     if (ANYBIG && w.big == 1) conv_tn_body<false, Big>(w, lds, blockIdx.x - nblocks_d);
     else if (ANYBIG && w.big == 2) conv_tn_body<false, Big96>(w, lds, blockIdx.x - nblocks_d);
     else if (ANYBIG && w.big == 3) conv_tn_body<false, Flat96, true>(w, lds, blockIdx.x - nblocks_d);
-    else conv_tn_body<false, Small>(w, lds, blockIdx.x - nblocks_d);
+    else conv_tn_body<false, Small, false, !ANYBIG>(w, lds, blockIdx.x - nblocks_d);
   }
 }
 
@@ -836,7 +1032,7 @@ __device__ __forceinline__ void group_run(const ConvArgs& a, int tn, float* lds,
     if (ANYBIG && a.big == 1) conv_tn_body<false, Big>(a, lds, local);
     else if (ANYBIG && a.big == 2) conv_tn_body<false, Big96>(a, lds, local);
     else if (ANYBIG && a.big == 3) conv_tn_body<false, Flat96, true>(a, lds, local);
-    else conv_tn_body<false, Small>(a, lds, local);
+    else conv_tn_body<false, Small, false, !ANYBIG>(a, lds, local);
   } else {
     if (ANYBIG && a.big == 1) conv_nt_body<false, Big, CLS>(a, lds, local);
     else if (ANYBIG && a.big == 2) conv_nt_body<false, Big96, CLS>(a, lds, local);
@@ -870,11 +1066,13 @@ inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 namespace {
 
 // Number of K-splits.  target_blocks > 0: split until about that many workgroups exist
-// (>= 2 steps per split).  Otherwise a cost model in microseconds (measured on MI355X):
-// one 64x64xBK step costs a global->LDS round trip that the one-step prefetch only partly
-// hides (~1.0 us at BK = 32, ~1.5 us at BK = 64; the fp32 MFMA work itself is 0.43 / 0.86 us),
-// a split run pays ~3 us to publish and collect tickets plus ~0.15 us per slab the last
-// arriver sums; workgroups beyond two per CU queue.
+// (>= 2 steps per split).  Otherwise a cost model in microseconds: a split run pays ~3 us to
+// publish and collect tickets plus ~0.15 us per slab the last arriver sums; workgroups beyond
+// two per CU queue.  Its per-step term (0.6 + 0.014 * BK: ~1.0 us at BK = 32) dates from the
+// one-step prefetch and is kept because the split counts it yields are pinned
+// (tests/golden/conv_plan.npz); behind the register rings a wave's step was measured at ~0.55 us
+// at BK = 32 (0.43 us of it MFMA), in front of a fixed ~4 us wait for the kernel arguments and
+// the first operands (profiles/r19_conv_step_attribution.json).
 #ifndef HF_BIG_TARGET_BLOCKS
 #define HF_BIG_TARGET_BLOCKS 512  // (whole-bench A/B, profiles/r05_big_target_blocks_ab*.jsonl: 256 / 384 / 512 / 768 / 1024 ->
 #endif                            //  configs[3] 576 / 579 / 601 / 582 / 544, All-CNN-C GGN 761 / 782 / 817 / 817 / 754)
