@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 20
+#define HF_ABI_VERSION 21
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -353,6 +353,49 @@ typedef struct hf_bn_adjoint_problem {
   int row_blocks;
 } hf_bn_adjoint_problem;
 int hf_chan_affine_bwd_pair(const hf_bn_adjoint_problem* problems /* [2] */, int dtype, void* stream);
+
+/*
+ * The eval-mode BatchNorm adjoint with its per-channel sums taken OFF the adjoint chain (ABI 21).  The chain needs only
+ * the elementwise part of hf_chan_affine_bwd_ex; gw / gb are read by hf_pack_ex at the end of the sweep.
+ *
+ * hf_bn_adjoint_v4: NHWC fp32 [rows, c], c % 4 == 0, every operand 16-byte aligned, slab strides multiples of 4 --
+ * anything else is HF_ERR_ARG (there is no scalar form behind it).  One 16-byte channel quad per thread:
+ *   g = sum of gy's slabs (split order);  h = sum of gy2's slabs (gy2 nullable);  g = g + h;
+ *   g = mask_src > 0 ? g : 0 (nullable)            -> g_out  (nullable)
+ *   g * ((w ? w[c] : 1) * (rstd ? rstd[c] : 1))    -> ga_out (nullable; not both NULL)
+ * Rounding: fp32, one rounding per operation in exactly this order -- bitwise what hf_chan_affine_bwd_ex
+ * (row_blocks > 1) writes to gres / gx from the same operands.
+ * hf_bn_adjoint_v4_pair: two problems in one launch; of hf_bn_adjoint_problem it reads gres (-> g_out), gx (-> ga_out),
+ * the cotangents, mask_src, w, rstd, n, hw, c; gw, gb, x, mean and row_blocks are not read.
+ *
+ * hf_bn_sums_multi: the sums of SEVERAL units' stored g in one launch.  Problem i:
+ *   gw[b*c + ch] = sum over row share b of g * xhat,  xhat = (float)((x - mean[ch]) * rstd[ch])   (nullable)
+ *   gb[b*c + ch] = sum over row share b of g                                                        (nullable; not both)
+ * row share b = rows [b*per, (b+1)*per), per = ceil(rows / row_blocks); accumulated in fp64 by the thread map and in the
+ * order of hf_chan_affine_bwd_ex's row-major kernel and rounded once per partial row: bitwise the rows that launch
+ * writes at the same row_blocks (also at row_blocks == 1, where hf_chan_affine_bwd_ex takes another kernel).
+ * hf_bn_sums_table validates `count` problems (c % 4 == 0, c <= 1024, rows*c < 2^31, g and x 16-byte aligned, no empty
+ * share, x / mean / rstd wherever gw; HF_ERR_ARG otherwise), fills rows_per_block and block0 (the running sum of
+ * row_blocks) in place and returns the total number of row blocks; the caller copies the array to device memory.
+ * hf_bn_sums_multi launches entries [first, first + count) of that table -- `table` is the host array, `table_dev` its
+ * device copy -- after the same validation; count <= HF_BN_SUMS_MAX, a range past table_count or fields that are not
+ * hf_bn_sums_table's are HF_ERR_ARG, and nothing is launched.
+ */
+int hf_bn_adjoint_v4(void* g_out, void* ga_out, const void* gy, int gy_splits, int64_t gy_slab, const void* gy2,
+                     int gy2_splits, int64_t gy2_slab, const void* mask_src, const void* w, const void* rstd,
+                     int64_t rows, int64_t c, int dtype, void* stream);
+int hf_bn_adjoint_v4_pair(const hf_bn_adjoint_problem* problems /* [2] */, int dtype, void* stream);
+#define HF_BN_SUMS_MAX 32
+typedef struct hf_bn_sums_problem {
+  void *gw, *gb;
+  const void *g, *x, *mean, *rstd;
+  uint32_t rows, c, row_blocks;
+  uint32_t rows_per_block, block0; /* filled by hf_bn_sums_table */
+  uint32_t reserved;
+} hf_bn_sums_problem;
+int64_t hf_bn_sums_table(hf_bn_sums_problem* problems, int count);
+int hf_bn_sums_multi(const void* table_dev, const hf_bn_sums_problem* table, int table_count, int first, int count,
+                     int dtype, void* stream);
 
 /*
  * Forward pass of conv -> (eval-BatchNorm | bias) (+ residual) (+ ReLU) from the convolution's split-K

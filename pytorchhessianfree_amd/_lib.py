@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HF_PCG_LIB") or os.path.join(_HERE, "csrc", "libhfpcg.so")
 
 HF_F32, HF_F64 = 0, 1
-ABI_VERSION = 20
+ABI_VERSION = 21
 HF_ERR_ARG = -1  # hf_status of include/hf_pcg.h: null / negative / inconsistent argument
 HF_M_NONE, HF_M_DIAG, HF_M_EXTERNAL = 0, 1, 2
 REASONS = {
@@ -163,6 +163,11 @@ SIGNATURES = {
     "hf_bn_stats_rows": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p]),
     "hf_bn_adjoint_pre": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_int64,
                                   c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
+    "hf_bn_adjoint_v4": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_int64,
+                                 c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
+    "hf_bn_adjoint_v4_pair": (c_int, [c_void_p, c_int, c_void_p]),
+    "hf_bn_sums_table": (c_int64, [c_void_p, c_int]),
+    "hf_bn_sums_multi": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "hf_pack_ex": (
         c_int,
         [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int64), ctypes.POINTER(c_int64),
@@ -543,6 +548,16 @@ class BnAdjointProblem(ctypes.Structure):
                                                                                  ("gy2_slab", c_int64)]
                 + [(nm, c_void_p) for nm in ("x", "mean", "rstd", "w", "mask_src")]
                 + [(nm, c_int64) for nm in ("n", "c", "hw")] + [("row_blocks", c_int)])
+
+
+class BnSumsProblem(ctypes.Structure):
+    """``hf_bn_sums_problem`` of include/hf_pcg.h."""
+
+    _fields_ = ([(nm, c_void_p) for nm in ("gw", "gb", "g", "x", "mean", "rstd")]
+                + [(nm, ctypes.c_uint32) for nm in ("rows", "c", "row_blocks", "rows_per_block", "block0", "reserved")])
+
+
+BN_SUMS_MAX = 32  # HF_BN_SUMS_MAX of include/hf_pcg.h: problems per hf_bn_sums_multi launch
 
 
 class AffineTrainProblem(ctypes.Structure):

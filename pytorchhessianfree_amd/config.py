@@ -158,6 +158,9 @@ SWITCHES = {
                        "tests/test_engine_gpu.py::test_train_mode_prologue_form_variants_agree_and_state_is_independent_of_the_first_use_check"),
     "HF_BN_TRAIN_PAIR": ("1", "0: a downsample block's two train-mode units in launches of their own",
                          "tests/test_engine_gpu.py::test_train_mode_prologue_form_variants_agree_and_state_is_independent_of_the_first_use_check"),
+    "HF_BN_SUMS_DEFER": ("1", "0: an eval-mode unit's BatchNorm adjoint as the fused launch (elementwise part and per-channel "
+                         "sums on the adjoint chain) instead of the elementwise launch + one sums launch before the gather",
+                         "tests/test_bn_defer_engine_gpu.py::test_deferred_sums_equal_the_fused_launches_bit_for_bit"),
     "HF_CHUNKED_ALLREDUCE": ("auto", "0 / 1: force the single-graph resp. the two-phase data-parallel product",
                              "tests/test_distributed_gpu.py::test_step_two_ranks_engine_session_equals_cpu_whole_batch"),
     "HF_DIRECT_RCCL": ("1", "0: every collective through torch.distributed (no communicator of the package's own)",

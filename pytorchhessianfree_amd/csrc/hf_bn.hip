@@ -801,6 +801,93 @@ __global__ __launch_bounds__(BLOCK) void k_bn_adjoint_pre(
   }
 }
 
+// The same pre-pass in the shape of chan_affine_v4_body (fp32, C % 4 == 0, every operand 16-byte aligned): one channel
+// quad per thread, every load -- both cotangents' slab 0, the mask, w, rstd, sixteen slabs of each cotangent -- issued
+// before the first use.  This is what the adjoint CHAIN needs of a BatchNorm unit; the per-channel sums of g (the
+// parameters' gradient, read by hf_pack_ex only) are taken off the chain by k_bn_sums_multi below.  Expressions and order
+// are bn_adjoint_rows_body's -- slabs of each cotangent in split order (guarded additions, not + 0), g + h, the mask,
+// g * (w*rstd) with w*rstd formed first: bitwise that kernel's gres / gx.
+struct BnAdjV4Args {
+  float *g_out, *ga_out;
+  const float* gy;
+  int s1;
+  long long l1;
+  const float* gy2;
+  int s2;
+  long long l2;
+  const float *mask_src, *w, *rstd;
+  unsigned total, C;
+};
+
+__device__ __forceinline__ void bn_adjoint_v4_body(
+    float* __restrict__ g_out, float* __restrict__ ga_out, const float* __restrict__ gy, int s1, long long l1,
+    const float* __restrict__ gy2, int s2, long long l2, const float* __restrict__ mask_src,
+    const float* __restrict__ w, const float* __restrict__ rstd, unsigned total, unsigned C, unsigned bid,
+    unsigned nblocks) {
+  const unsigned quads = total >> 2;
+  for (unsigned v = bid * BLOCK + threadIdx.x; v < quads; v += nblocks * BLOCK) {
+    const unsigned i = v << 2;
+    const unsigned c = i % C;
+    F4 g = ld4(gy + i), h, mv, rs4, w4;
+    if (gy2) h = ld4(gy2 + i);
+    if (mask_src) mv = ld4(mask_src + i);
+    if (rstd) rs4 = ld4(rstd + c);
+    if (w) w4 = ld4(w + c);
+    const bool hs = gy2 && s2 > 1;
+    const int smax = (hs && s2 > s1) ? s2 : s1;
+    for (int sp = 1; sp < smax; sp += 16) {
+      F4 vg[16], vh[16];
+      slab_issue(vg, gy, i, sp, s1, l1);
+      if (hs) slab_issue(vh, gy2, i, sp, s2, l2);
+      slab_add<true>(g, vg, sp, s1);
+      if (hs) slab_add<true>(h, vh, sp, s2);
+    }
+    F4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float a = gy2 ? g.e[k] + h.e[k] : g.e[k];
+      if (mask_src) a = mv.e[k] > 0.f ? a : 0.f;
+      g.e[k] = a;
+      o.e[k] = a * ((w ? w4.e[k] : 1.f) * (rstd ? rs4.e[k] : 1.f));
+    }
+    if (g_out) *reinterpret_cast<F4*>(g_out + i) = g;
+    if (ga_out) *reinterpret_cast<F4*>(ga_out + i) = o;
+  }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_bn_adjoint_v4(const BnAdjV4Args p) {
+  bn_adjoint_v4_body(p.g_out, p.ga_out, p.gy, p.s1, p.l1, p.gy2, p.s2, p.l2, p.mask_src, p.w, p.rstd, p.total, p.C,
+                     blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_bn_adjoint_v4_pair(const BnAdjV4Args A, const BnAdjV4Args B,
+                                                              unsigned blocks_a) {
+  const bool first = blockIdx.x < blocks_a;
+  const BnAdjV4Args& p = first ? A : B;
+  bn_adjoint_v4_body(p.g_out, p.ga_out, p.gy, p.s1, p.l1, p.gy2, p.s2, p.l2, p.mask_src, p.w, p.rstd, p.total, p.C,
+                     first ? blockIdx.x : blockIdx.x - blocks_a, first ? blocks_a : gridDim.x - blocks_a);
+}
+
+// The per-channel sums gw = sum g*xhat, gb = sum g of SEVERAL units' stored masked cotangents in ONE launch, off the
+// adjoint chain: workgroup b of the launch finds its problem in a table in device memory (entries [first, first + count),
+// in adjoint-sweep order; block0 = the running sum of the row-block counts from entry 0) and runs bn_adjoint_rows_body on
+// its row share -- one slab, no second cotangent, no mask, nothing elementwise stored: the thread map, the two-rows-per-
+// pass order and cross_row_sums of the fused launch, bitwise its partial rows.  The table is read, not passed by value:
+// one vector load per lane and a ballot find the entry, whose fields then arrive by uniform loads.
+__global__ __launch_bounds__(BLOCK) void k_bn_sums_multi(const hf_bn_sums_problem* __restrict__ tab, int first,
+                                                         int count, unsigned base) {
+  __shared__ double red[BLOCK * 8];
+  const unsigned b = blockIdx.x + base;
+  const int lane = threadIdx.x & 63;
+  unsigned b0 = 0xffffffffu;
+  if (lane < count) b0 = tab[first + lane].block0;
+  const int p = __builtin_amdgcn_readfirstlane(first + __popcll(__ballot(b0 <= b)) - 1);  // block0[first] == base <= b
+  const hf_bn_sums_problem& e = tab[p];
+  bn_adjoint_rows_body(nullptr, (float*)e.gw, (float*)e.gb, nullptr, (const float*)e.g, 1, 0, nullptr, 1, 0,
+                       (const float*)e.x, (const float*)e.mean, (const float*)e.rstd, nullptr, nullptr, e.rows, e.c,
+                       e.rows_per_block, b - e.block0, red);
+}
+
 // Forward of conv -> (eval-BatchNorm | bias) (+ residual) (+ ReLU) from the convolution's split-K slabs,
 // NHWC [rows, C]; one element per thread (activation-sized, latency-bound).  The rounding sequence
 // is chan_affine_body's forward: ((s - mean)*rstd)*w, + b, + res.
@@ -1430,6 +1517,104 @@ int hf_chan_affine_bwd_ex(void* gx, void* gw, void* gb, void* gres, const void* 
                                    channels_last, gy_splits, gy_slab, gy2_splits, gy2_slab, row_blocks);
   else
     return HF_ERR_ARG;
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+// One problem of the elementwise adjoint (hf_bn_adjoint_v4, hf_bn_adjoint_v4_pair): the quad walk's conditions are
+// refusals here, there is no scalar form behind it.
+static int fill_bn_adj_v4(BnAdjV4Args& k, void* g_out, void* ga_out, const void* gy, int gy_splits, int64_t gy_slab,
+                          const void* gy2, int gy2_splits, int64_t gy2_slab, const void* mask_src, const void* w,
+                          const void* rstd, int64_t rows, int64_t c) {
+  if (!gy || (!g_out && !ga_out) || rows <= 0 || c <= 0 || c % 4 || gy_splits < 1 || gy2_splits < 1) return HF_ERR_ARG;
+  if (gy_splits > 1 && (gy_slab <= 0 || (gy_slab & 3))) return HF_ERR_ARG;
+  if (gy2 && gy2_splits > 1 && (gy2_slab <= 0 || (gy2_slab & 3))) return HF_ERR_ARG;
+  if (rows * c > 0x7fffffffLL) return HF_ERR_ARG;
+  const void* ptrs[] = {g_out, ga_out, gy, gy2, mask_src, w, rstd};
+  for (const void* p : ptrs)
+    if (p && !aligned16(p)) return HF_ERR_ARG;
+  k = BnAdjV4Args{(float*)g_out, (float*)ga_out, (const float*)gy, gy_splits, (long long)gy_slab, (const float*)gy2,
+                  gy2 ? gy2_splits : 1, (long long)gy2_slab, (const float*)mask_src, (const float*)w,
+                  (const float*)rstd, (unsigned)(rows * c), (unsigned)c};
+  return HF_OK;
+}
+
+int hf_bn_adjoint_v4(void* g_out, void* ga_out, const void* gy, int gy_splits, int64_t gy_slab, const void* gy2,
+                     int gy2_splits, int64_t gy2_slab, const void* mask_src, const void* w, const void* rstd,
+                     int64_t rows, int64_t c, int dtype, void* stream) {
+  if (dtype != HF_F32) return HF_ERR_ARG;
+  BnAdjV4Args k;
+  const int rc = fill_bn_adj_v4(k, g_out, ga_out, gy, gy_splits, gy_slab, gy2, gy2_splits, gy2_slab, mask_src, w, rstd,
+                                rows, c);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_bn_adjoint_v4, dim3(wide_grid(k.total / 4)), dim3(BLOCK), 0, (hipStream_t)stream, k);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+int hf_bn_adjoint_v4_pair(const hf_bn_adjoint_problem* problems, int dtype, void* stream) {
+  if (!problems || dtype != HF_F32) return HF_ERR_ARG;
+  BnAdjV4Args q[2];
+  unsigned blocks[2];
+  for (int i = 0; i < 2; ++i) {
+    const hf_bn_adjoint_problem& p = problems[i];
+    if (p.n <= 0 || p.hw <= 0) return HF_ERR_ARG;
+    const int rc = fill_bn_adj_v4(q[i], p.gres, p.gx, p.gy, p.gy_splits, p.gy_slab, p.gy2, p.gy2_splits, p.gy2_slab,
+                                  p.mask_src, p.w, p.rstd, p.n * p.hw, p.c);
+    if (rc) return rc;
+    blocks[i] = (unsigned)wide_grid(q[i].total / 4);
+  }
+  hipLaunchKernelGGL(k_bn_adjoint_v4_pair, dim3(blocks[0] + blocks[1]), dim3(BLOCK), 0, (hipStream_t)stream, q[0],
+                     q[1], blocks[0]);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+// One entry of a sums table: what bn_adjoint_rows_body needs of it (fill_bn_adj_rows's conditions for one slab and no
+// elementwise output).  hf_bn_sums_table and hf_bn_sums_multi both run it.
+static int check_bn_sums(const hf_bn_sums_problem& p, uint32_t& per) {
+  if (!p.g || (!p.gw && !p.gb) || p.rows == 0 || p.c == 0 || p.row_blocks < 1) return HF_ERR_ARG;
+  if (!(p.c % 4 == 0 && p.c / 4 <= BLOCK)) return HF_ERR_ARG;
+  per = (p.rows + p.row_blocks - 1) / p.row_blocks;
+  if ((uint64_t)(p.row_blocks - 1) * per >= p.rows) return HF_ERR_ARG;  // an empty share
+  if (p.gw && (!p.x || !p.mean || !p.rstd)) return HF_ERR_ARG;
+  if ((uint64_t)p.rows * p.c > 0x7fffffffULL) return HF_ERR_ARG;
+  if (!aligned16(p.g) || (p.x && !aligned16(p.x))) return HF_ERR_ARG;
+  return HF_OK;
+}
+
+int64_t hf_bn_sums_table(hf_bn_sums_problem* problems, int count) {
+  if (!problems || count < 1) return HF_ERR_ARG;
+  uint64_t blocks = 0;
+  for (int i = 0; i < count; ++i) {
+    uint32_t per;
+    const int rc = check_bn_sums(problems[i], per);
+    if (rc) return rc;
+    if (!problems[i].gw) problems[i].x = nullptr;  // plain column sums (a bias gradient)
+    problems[i].rows_per_block = per;
+    problems[i].block0 = (uint32_t)blocks;
+    blocks += problems[i].row_blocks;
+    if (blocks > 0x7fffffffULL) return HF_ERR_ARG;
+  }
+  return (int64_t)blocks;
+}
+
+int hf_bn_sums_multi(const void* table_dev, const hf_bn_sums_problem* table, int table_count, int first, int count,
+                     int dtype, void* stream) {
+  if (!table_dev || !table || dtype != HF_F32 || table_count < 1 || first < 0 || count < 1 ||
+      count > HF_BN_SUMS_MAX || first > table_count - count)
+    return HF_ERR_ARG;
+  uint64_t blocks = 0;
+  for (int i = first; i < first + count; ++i) {
+    uint32_t per;
+    const int rc = check_bn_sums(table[i], per);
+    if (rc) return rc;
+    // (the derived fields as hf_bn_sums_table left them: the device copy was made from them)
+    if (table[i].rows_per_block != per || table[i].block0 != table[first].block0 + blocks) return HF_ERR_ARG;
+    blocks += table[i].row_blocks;
+  }
+  hipLaunchKernelGGL(k_bn_sums_multi, dim3((unsigned)blocks), dim3(BLOCK), 0, (hipStream_t)stream,
+                     (const hf_bn_sums_problem*)table_dev, first, count, table[first].block0);
   HF_HIP(hipGetLastError());
   return HF_OK;
 }

@@ -37,6 +37,12 @@ class _AdjointSweep:
             q.x, q.mean, q.rstd, q.w = u.a.data_ptr(), u.mean.data_ptr(), u.rstd.data_ptr(), u.bn.weight.data_ptr()
             q.mask_src = u.y.data_ptr() if u.relu else None
             q.n, q.c, q.hw, q.row_blocks = n, k, oh * ow, u.rb
+        if not train and self._split_now(u1) and self._split_now(u2):
+            # the chain's launch is the elementwise one; the per-channel sums wait for _flush_sums
+            _lib.check(_lib.load().hf_bn_adjoint_v4_pair(_lib.ctypes.cast(arr, _lib.c_void_p), _lib.HF_F32,
+                                                         _lib.current_stream_ptr(self.dev)), "hf_bn_adjoint_v4_pair")
+            self._sums_pending.update(u.sums_slot for u in (u1, u2) if u.defer)
+            return
         _lib.check(_lib.load().hf_chan_affine_bwd_pair(_lib.ctypes.cast(arr, _lib.c_void_p), _lib.HF_F32,
                                                        _lib.current_stream_ptr(self.dev)), "hf_chan_affine_bwd_pair")
 
@@ -109,6 +115,15 @@ class _AdjointSweep:
                 _ptr(ga), _ptr(u.g), _ptr(u.a), _ptr(u.mean), _ptr(u.rstd), _ptr(u.scale), _ptr(u.gw),
                 _ptr(u.gb), u.rb, None, None, float(n * oh * ow), None, None, n, k, oh * ow, 0, 0, 1, 0,
                 _lib.HF_F32, st), "hf_chan_affine_train")
+            return
+        if self._split_now(u):
+            # g = mask * (sum of both cotangents' slabs) -> u.g; g * w*rstd -> u.ga: all the chain needs.  The per-channel
+            # sums (the parameters' gradient: only the gather reads them) wait for _flush_sums
+            _lib.check(lib.hf_bn_adjoint_v4(
+                _ptr(u.g), _ptr(ga), _ptr(a), sa, la, _ptr(b), sb, lb, _ptr(u.y) if u.relu else None, _ptr(u.scale),
+                _ptr(u.rstd), n * oh * ow, k, _lib.HF_F32, st), "hf_bn_adjoint_v4")
+            if u.defer:
+                self._sums_pending.add(u.sums_slot)
             return
         # g = mask * (sum of both cotangents' slabs) -> u.g; g * w*rstd -> u.ga; per-channel sums
         bn = u.bn is not None
@@ -224,6 +239,7 @@ class _AdjointSweep:
 
     def _gather(self, out, g_fw, g_fb, first_order=False):
         """All parameter gradients into the flat vector (weight-gradient slabs summed on the way)."""
+        self._flush_sums()
         tensors, perms, splits = self._pack_args(first_order)
         tensors = list(tensors)
         if g_fw.dim() == 3:  # the head kernel's per-workgroup partial sums: slabs for hf_pack_ex
@@ -243,6 +259,7 @@ class _AdjointSweep:
 
     def _gather_range(self, out, g_fw, g_fb, lo, hi):
         """``_gather`` for the parameters ``lo ... hi-1`` only (a contiguous range of the flat vector)."""
+        self._flush_sums()  # (what this phase of the sweep has deferred)
         tensors, perms, splits = self._pack_args()
         tensors, splits = list(tensors), dict(splits)
         if g_fw is not None:

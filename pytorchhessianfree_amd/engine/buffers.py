@@ -12,8 +12,53 @@ from .. import _lib
 from .common import _Unsupported, _flat_view, _live_taps, _pair, _ptr
 
 
+def adjoint_split_ok(train, rb, hessian, map_bytes, max_bytes, enabled=True):
+    """Whether a unit's BatchNorm / bias adjoint runs as the ELEMENTWISE launch (``hf_bn_adjoint_v4``): eval mode, on the
+    row-major kernel today (``rb > 1``), not inside a Hessian engine (whose ``_swap_first_order`` swaps the buffers a
+    static sums table would point to), and a map small enough that reading ``g`` and ``x`` a second time costs less than
+    the reduction costs the adjoint chain."""
+    return bool(enabled and not train and rb > 1 and not hessian and map_bytes <= max_bytes)
+
+
+def defer_sums_ok(train, rb, hessian, has_gw, has_gb, map_bytes, max_bytes, enabled=True):
+    """Whether a unit's per-channel sums leave the adjoint chain for ``_flush_sums``: it takes the elementwise launch and
+    has at least one of gw / gb to produce (a frozen scale and shift have no sums at all)."""
+    return bool(adjoint_split_ok(train, rb, hessian, map_bytes, max_bytes, enabled) and (has_gw or has_gb))
+
+
+def sums_runs(pending, cap):
+    """The pending table entries as contiguous sub-ranges ``(first, count)`` of at most ``cap`` entries, ascending."""
+    runs = []
+    for i in sorted(set(pending)):
+        if runs and runs[-1][0] + runs[-1][1] == i and runs[-1][1] < cap:
+            runs[-1][1] += 1
+        else:
+            runs.append([i, 1])
+    return [tuple(r) for r in runs]
+
+
+def sums_table(problems):
+    """``(table, total row blocks)``: the ``hf_bn_sums_problem`` array of ``problems`` -- dicts of its fields -- validated
+    and completed (rows per block, block prefix) by the library's own host function; ``_lib.Refused`` on a problem the
+    sums kernel does not take."""
+    tab = (_lib.BnSumsProblem * len(problems))()
+    for q, prob in zip(tab, problems):
+        for name, val in prob.items():
+            setattr(q, name, val)
+    blocks = _lib.load().hf_bn_sums_table(_lib.ctypes.cast(tab, _lib.c_void_p), len(problems))
+    if blocks < 0:
+        _lib.check(int(blocks), "hf_bn_sums_table")
+    return tab, int(blocks)
+
+
 class _Buffers:
     ADJ_BYTES_PER_WG = 32768  # the BatchNorm adjoint's row-major kernel: one workgroup per this many bytes of the map
+    # Up to this map size an eval-mode unit's per-channel sums leave the adjoint chain (adjoint_split_ok): the chain runs
+    # the elementwise launch, ONE launch in front of the gather takes all units' sums from the stored g.  Above it the
+    # fused launch stays: the split form reads g and x a second time.  Four times the largest ResNet-18 map (the stem's,
+    # 1.6 MB): measured on the workloads with larger maps, deferral off / 1.6 MB / 6.4 MB -- All-CNN-C 835 / 841 / 844,
+    # ResNet-50 topology 341 / 347 / 357 matvecs/s (profiles/r20_bn_defer_threshold.jsonl); ResNet-18 is the same at both.
+    DEFER_MAX_BYTES = 4 * 6272 * 64 * 4
     # ---- buffers -------------------------------------------------------------------------
     def _plan(self, direction, u, forward=False):
         n, c, h, w = u.x.shape
@@ -135,6 +180,12 @@ class _Buffers:
                 u.rb = -(-u.rows // per)
                 if u.rb < 2:
                     u.rb = 1
+            enabled = os.environ.get("HF_BN_SUMS_DEFER", "1") != "0"
+            u.split = adjoint_split_ok(u.train, u.rb, self.hessian, u.a.numel() * 4, self.DEFER_MAX_BYTES, enabled)
+            u.defer = not u.dead and defer_sums_ok(u.train, u.rb, self.hessian, u.bn is not None and u.pg is not None,
+                                                   u.pb is not None, u.a.numel() * 4, self.DEFER_MAX_BYTES, enabled)
+            if u.defer and u.g is None:  # (deferred sums are taken of the STORED g, needed by a residual branch or not)
+                u.g = torch.empty_like(u.a)
             # (Hessian: the scale's second-order term arrives as `rb` more partial rows for hf_pack_ex to add)
             u.gw_rows = u.rb * (2 if (self.hessian and u.bn is not None) else 1)
             if self.hessian and u.train:
@@ -182,6 +233,7 @@ class _Buffers:
                 u.tout, u.tout_ld, u.yout2 = torch.empty_like(u.y), 0, None
         self._xcats = xcats
         self._slot_list = list(self._tangent_slots.values())
+        self._allocate_sums_table()
         self._carry_ok = True  # (the stem's launch carries the v_W scatter; False once the library refused it)
         # (I, H, W, O) copies: the weights (once per step) and, for Hessian products, V (per product)
         self._wt_slots = [(self._offs[u.pw], u.wT, u.x.shape[1]) for u in self.units
@@ -197,6 +249,74 @@ class _Buffers:
         # the parameters as ONE flat vector, when they are consecutive views of one (the optimizer's
         # arena): every W half is then refreshed by a single scatter launch
         self._flat_params = _flat_view(self.params, self.n)
+
+    def _adjoint_order(self):
+        """The units in the order the adjoint sweep visits them."""
+        if not self.blocks:
+            return list(reversed(self.units))
+        order = []
+        for chain, ds, _x in reversed(self.blocks):
+            order += list(reversed(chain)) + ([ds] if ds is not None else [])
+        return order + ([self.stem] if self.stem is not None else [])
+
+    def _allocate_sums_table(self):
+        """The deferred units' sums problems as ONE table in device memory, in adjoint-sweep order (static pointers: built
+        and uploaded here, outside any captured region); ``u.sums_slot``: the unit's entry."""
+        units = [u for u in self._adjoint_order() if u.defer]
+        self._sums_pending, self._sums_tab, self._sums_dev, self.sums_launches = set(), None, None, 0
+        self._sums_units, self.split_fallbacks = units, 0
+        if units:
+            self._build_sums_table()
+
+    def _build_sums_table(self):
+        problems = []
+        for i, u in enumerate(self._sums_units):
+            bn = u.bn is not None and u.pg is not None
+            u.sums_slot = i
+            problems.append(dict(gw=u.gw.data_ptr() if bn else None, gb=u.gb.data_ptr() if u.pb is not None else None,
+                                 g=u.g.data_ptr(), x=u.a.data_ptr() if bn else None,
+                                 mean=u.mean.data_ptr() if bn else None, rstd=u.rstd.data_ptr() if bn else None,
+                                 rows=u.rows, c=u.cout, row_blocks=u.rb))
+        self._sums_tab, _blocks = sums_table(problems)
+        host = torch.frombuffer(bytearray(bytes(self._sums_tab)), dtype=torch.uint8)
+        if self._sums_dev is None:
+            self._sums_dev = host.to(self.dev)
+        else:
+            self._sums_dev.copy_(host)  # (in place: captured launches hold this pointer)
+
+    def _split_now(self, u):
+        """Whether this launch of ``u``'s adjoint is the elementwise one: planned so (``u.split``) AND the scale -- the one
+        operand of that launch the model owns -- 16-byte aligned right now.  ``utils.ParameterArena`` binds the parameters
+        as views at unpadded offsets of one vector, at any time after the buffers were allocated, so ``bn.weight`` can sit
+        on any 4-byte boundary; the elementwise launch loads it by quads and has no scalar form, the fused launch reads
+        it by scalar loads.  A misaligned unit takes the fused launch, which leaves its sums itself: nothing is pending."""
+        if not u.split:
+            return False
+        w = u.scale
+        if w is None or w.data_ptr() % 16 == 0:
+            return True
+        self.split_fallbacks += 1
+        return False
+
+    def bn_adjoint_report(self):
+        """Which units' adjoints are planned as the elementwise launch, whose sums are deferred, how many sums launches
+        the engine has issued so far, and how many adjoints planned as elementwise took the fused launch instead (a
+        misaligned scale, ``_split_now``)."""
+        return {"elementwise": [u.name for u in self.units if u.split and not u.dead],
+                "deferred": [u.name for u in self._sums_units], "sums_launches": self.sums_launches,
+                "fused_fallbacks": self.split_fallbacks}
+
+    def _flush_sums(self):
+        """The per-channel sums of every unit the sweep has deferred since the last flush: one launch per contiguous
+        range of the table (one, for a whole sweep).  Runs in front of every gather."""
+        if not self._sums_pending:
+            return
+        lib, st = _lib.load(), _lib.current_stream_ptr(self.dev)
+        for first, count in sums_runs(self._sums_pending, _lib.BN_SUMS_MAX):
+            _lib.check(lib.hf_bn_sums_multi(self._sums_dev.data_ptr(), _lib.ctypes.cast(self._sums_tab, _lib.c_void_p),
+                                            len(self._sums_tab), first, count, _lib.HF_F32, st), "hf_bn_sums_multi")
+            self.sums_launches += 1
+        self._sums_pending.clear()
 
     def _allocate_pool(self):
         self.pool_t = self._xcats.get(id(self.pool_out))
@@ -248,6 +368,13 @@ class _Buffers:
             if u.bn is not None and not u.train and u.bn.running_var._version != u.rstd_version:
                 torch.rsqrt(u.bn.running_var + u.bn.eps, out=u.rstd)
                 u.rstd_version = u.bn.running_var._version
+        # The sums table holds addresses.  All but one are buffers of the engine's own, allocated once and never replaced
+        # (u.a, u.g, u.gw, u.gb, u.rstd; diag_ef allocates a u.g only where a unit has none, and a unit in the table has
+        # one); the running mean is the one tensor in it that the MODEL owns (a load_state_dict or .to() may re-bind it):
+        # rebuilt, eagerly, if that address moved
+        if any(u.bn is not None and u.pg is not None and u.mean.data_ptr() != self._sums_tab[u.sums_slot].mean
+               for u in self._sums_units):
+            self._build_sums_table()
         self.refresh_frozen()
         if targets is not None:
             self.set_targets(targets)

@@ -225,6 +225,7 @@ class PlainStackEngine(FusedGGNEngine):
         return out
 
     def _gather(self, out, g_fw, g_fb, first_order=False):
+        self._flush_sums()
         tensors, perms, splits = self._pack_args(first_order)
         _lib.pack_ex(out, list(tensors), perms, splits, scale=self.weight, live=self._pack_live)
         return out
