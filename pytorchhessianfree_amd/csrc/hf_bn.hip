@@ -1201,11 +1201,13 @@ int hf_softmax_ce_hvp(void* out, const void* p, const void* v, double scale, int
   return HF_OK;
 }
 
-static bool affine_vec4_ok(const void* out, const void* a, const void* x, const void* mean, const void* rstd,
-                          const void* w, const void* q, const void* r, const void* add, const void* mask_src,
-                          long long total, long long c, int nhwc, long long out_ld, long long add_ld,
-                          long long a_slab) {
-  const void* ptrs[] = {out, a, x, mean, rstd, w, q, r, add, mask_src};
+// The host functions below take a problem as the public struct that names its fields (include/hf_pcg.h); the positional
+// entry points fill that struct and run what the two-problem entry points run.
+
+// The quad-per-thread walk of the affine kernels: every operand given (`ptrs`) 16-byte aligned, NHWC, strides in quads.
+template <size_t N>
+static bool affine_vec4_ok(const void* const (&ptrs)[N], long long total, long long c, int nhwc, long long out_ld,
+                           long long add_ld, long long a_slab) {
   for (const void* p : ptrs)
     if (p && !aligned16(p)) return false;
   return nhwc && c % 4 == 0 && out_ld % 4 == 0 && add_ld % 4 == 0 && a_slab % 4 == 0 && 2 * total < 0x7fffffffLL;
@@ -1213,66 +1215,58 @@ static bool affine_vec4_ok(const void* out, const void* a, const void* x, const 
 
 // One problem of hf_chan_affine_ex / hf_chan_affine_pair, any dtype and size: the refusals, and whether the
 // quad-per-thread walk may run.
-static int check_aff(bool& vec4, const void* out, const void* a, const void* x, const void* mean, const void* rstd,
-                     const void* w, const void* q, const void* r, const void* add, const void* mask_src, int64_t n,
-                     int64_t c, int64_t hw, int channels_last, int64_t out_ld, int64_t add_ld, int a_splits,
-                     int64_t a_slab) {
-  if (a_splits < 1 || (a_splits > 1 && (!a || a_slab <= 0))) return HF_ERR_ARG;
-  if (!out || n <= 0 || c <= 0 || hw <= 0) return HF_ERR_ARG;
-  if (q && (!x || !mean || !rstd)) return HF_ERR_ARG;
+static int check_aff(bool& vec4, const hf_affine_problem& p, int channels_last) {
+  if (p.a_splits < 1 || (p.a_splits > 1 && (!p.a || p.a_slab <= 0))) return HF_ERR_ARG;
+  if (!p.out || p.n <= 0 || p.c <= 0 || p.hw <= 0) return HF_ERR_ARG;
+  if (p.q && (!p.x || !p.mean || !p.rstd)) return HF_ERR_ARG;
   // a leading dimension is that of a buffer with MORE channels: >= 2x would be the
   // tangent buffers' case, anything above the dense one is accepted
-  const int64_t dense = channels_last ? c : c * hw;
-  if ((out_ld && out_ld < dense) || (add_ld && (add_ld < dense || !add)) ||
-      out_ld > 0x3fffffffLL || add_ld > 0x3fffffffLL)
+  const int64_t dense = channels_last ? p.c : p.c * p.hw;
+  if ((p.out_ld && p.out_ld < dense) || (p.add_ld && (p.add_ld < dense || !p.add)) ||
+      p.out_ld > 0x3fffffffLL || p.add_ld > 0x3fffffffLL)
     return HF_ERR_ARG;
-  vec4 = affine_vec4_ok(out, a, x, mean, rstd, w, q, r, add, mask_src, (long long)n * c * hw, c,
-                        channels_last || hw == 1, out_ld, add_ld, a_slab);
+  const void* const ptrs[] = {p.out, p.a, p.x, p.mean, p.rstd, p.w, p.q, p.r, p.add, p.mask_src};
+  vec4 = affine_vec4_ok(ptrs, (long long)p.n * p.c * p.hw, p.c, channels_last || p.hw == 1, p.out_ld, p.add_ld,
+                        p.a_slab);
   return HF_OK;
 }
 
 // The same problem as the fp32 kernel arguments with 32-bit sizes, which hold while 2 * total < 2^31: larger problems
 // are refused, so a filled AffArgs is always valid.
-static int fill_aff(AffArgs& k, void* out, const void* a, const void* x, const void* mean, const void* rstd,
-                    const void* w, const void* q, const void* r, const void* add, const void* mask_src, int relu_self,
-                    int64_t n, int64_t c, int64_t hw, int channels_last, int64_t out_ld, int64_t add_ld, int a_splits,
-                    int64_t a_slab) {
+static int fill_aff(AffArgs& k, const hf_affine_problem& p, int channels_last) {
   bool vec4 = false;
-  const int rc = check_aff(vec4, out, a, x, mean, rstd, w, q, r, add, mask_src, n, c, hw, channels_last, out_ld, add_ld,
-                           a_splits, a_slab);
+  const int rc = check_aff(vec4, p, channels_last);
   if (rc) return rc;
-  const long long total = (long long)n * c * hw;
+  const long long total = (long long)p.n * p.c * p.hw;
   if (2 * total >= 0x7fffffffLL) return HF_ERR_ARG;
-  k = AffArgs{(float*)out, (const float*)a, (const float*)x, (const float*)mean, (const float*)rstd, (const float*)w,
-              (const float*)q, (const float*)r, (const float*)add, (const float*)mask_src, relu_self, (unsigned)total,
-              (unsigned)c, (unsigned)hw, channels_last, (unsigned)out_ld, (unsigned)add_ld, a_splits,
-              (long long)a_slab, vec4 ? 1 : 0};
+  k = AffArgs{(float*)p.out, (const float*)p.a, (const float*)p.x, (const float*)p.mean, (const float*)p.rstd,
+              (const float*)p.w, (const float*)p.q, (const float*)p.r, (const float*)p.add, (const float*)p.mask_src,
+              p.relu_self, (unsigned)total, (unsigned)p.c, (unsigned)p.hw, channels_last, (unsigned)p.out_ld,
+              (unsigned)p.add_ld, p.a_splits, (long long)p.a_slab, vec4 ? 1 : 0};
   return HF_OK;
 }
 
 template <typename T>
-static void launch_chan_affine(hipStream_t s, void* out, const void* a, const void* x,
-                               const void* mean, const void* rstd, const void* w, const void* q,
-                               const void* r, const void* add, const void* mask_src,
-                               int relu_self, long long total, long long c, long long hw,
-                               int nhwc, long long out_ld, long long add_ld, int a_splits, long long a_slab,
-                               bool vec4) {
+static void launch_chan_affine(hipStream_t s, const hf_affine_problem& p, int nhwc, bool vec4) {
+  const long long total = (long long)p.n * p.c * p.hw, c = p.c, hw = p.hw, out_ld = p.out_ld, add_ld = p.add_ld,
+                  a_slab = p.a_slab;
   if (sizeof(T) == 4 && vec4)
-    hipLaunchKernelGGL(k_chan_affine_v4, dim3(wide_grid(total / 4)), dim3(BLOCK), 0, s, (float*)out,
-                       (const float*)a, (const float*)x, (const float*)mean, (const float*)rstd, (const float*)w,
-                       (const float*)q, (const float*)r, (const float*)add, (const float*)mask_src, relu_self,
-                       (unsigned)total, (unsigned)c, (unsigned)out_ld, (unsigned)add_ld, a_splits, a_slab);
+    hipLaunchKernelGGL(k_chan_affine_v4, dim3(wide_grid(total / 4)), dim3(BLOCK), 0, s, (float*)p.out,
+                       (const float*)p.a, (const float*)p.x, (const float*)p.mean, (const float*)p.rstd,
+                       (const float*)p.w, (const float*)p.q, (const float*)p.r, (const float*)p.add,
+                       (const float*)p.mask_src, p.relu_self, (unsigned)total, (unsigned)c, (unsigned)out_ld,
+                       (unsigned)add_ld, p.a_splits, a_slab);
   else if (2 * total < 0x7fffffffLL)  // strided operands reach at most 2*total
     hipLaunchKernelGGL((k_chan_affine<T, unsigned>), dim3(wide_grid(total)), dim3(BLOCK), 0, s,
-                       (T*)out, (const T*)a, (const T*)x, (const T*)mean, (const T*)rstd,
-                       (const T*)w, (const T*)q, (const T*)r, (const T*)add, (const T*)mask_src,
-                       relu_self, (unsigned)total, (unsigned)c, (unsigned)hw, nhwc,
-                       (unsigned)out_ld, (unsigned)add_ld, a_splits, a_slab);
+                       (T*)p.out, (const T*)p.a, (const T*)p.x, (const T*)p.mean, (const T*)p.rstd,
+                       (const T*)p.w, (const T*)p.q, (const T*)p.r, (const T*)p.add, (const T*)p.mask_src,
+                       p.relu_self, (unsigned)total, (unsigned)c, (unsigned)hw, nhwc,
+                       (unsigned)out_ld, (unsigned)add_ld, p.a_splits, a_slab);
   else
     hipLaunchKernelGGL((k_chan_affine<T, long long>), dim3(wide_grid(total)), dim3(BLOCK), 0, s,
-                       (T*)out, (const T*)a, (const T*)x, (const T*)mean, (const T*)rstd,
-                       (const T*)w, (const T*)q, (const T*)r, (const T*)add, (const T*)mask_src,
-                       relu_self, total, c, hw, nhwc, out_ld, add_ld, a_splits, a_slab);
+                       (T*)p.out, (const T*)p.a, (const T*)p.x, (const T*)p.mean, (const T*)p.rstd,
+                       (const T*)p.w, (const T*)p.q, (const T*)p.r, (const T*)p.add, (const T*)p.mask_src,
+                       p.relu_self, total, c, hw, nhwc, out_ld, add_ld, p.a_splits, a_slab);
 }
 
 int hf_chan_affine(void* out, const void* a, const void* x, const void* mean, const void* rstd,
@@ -1288,42 +1282,42 @@ int hf_chan_affine_ex(void* out, const void* a, const void* x, const void* mean,
                       const void* mask_src, int relu_self, int64_t n, int64_t c, int64_t hw,
                       int channels_last, int64_t out_ld, int64_t add_ld, int a_splits, int64_t a_slab,
                       int dtype, void* stream) {
+  const hf_affine_problem p = {.out = out, .a = a, .x = x, .mean = mean, .rstd = rstd, .w = w, .q = q, .r = r,
+                               .add = add, .mask_src = mask_src, .relu_self = relu_self, .n = n, .c = c, .hw = hw,
+                               .out_ld = out_ld, .add_ld = add_ld, .a_splits = a_splits, .a_slab = a_slab};
   bool vec4 = false;
-  const int rc = check_aff(vec4, out, a, x, mean, rstd, w, q, r, add, mask_src, n, c, hw, channels_last, out_ld, add_ld,
-                           a_splits, a_slab);
+  const int rc = check_aff(vec4, p, channels_last);
   if (rc) return rc;
-  const long long total = (long long)n * c * hw;
   hipStream_t s = (hipStream_t)stream;
   if (dtype == HF_F32)
-    launch_chan_affine<float>(s, out, a, x, mean, rstd, w, q, r, add, mask_src, relu_self, total, c, hw,
-                              channels_last, out_ld, add_ld, a_splits, a_slab, vec4);
+    launch_chan_affine<float>(s, p, channels_last, vec4);
   else if (dtype == HF_F64)
-    launch_chan_affine<double>(s, out, a, x, mean, rstd, w, q, r, add, mask_src, relu_self, total, c, hw,
-                               channels_last, out_ld, add_ld, a_splits, a_slab, false);
+    launch_chan_affine<double>(s, p, channels_last, false);
   else
     return HF_ERR_ARG;
   HF_HIP(hipGetLastError());
   return HF_OK;
 }
 
-static int fill_aff_train(AffTrainArgs& q, void* out, const void* a, const void* x, const void* mean, const void* rstd,
-                          const void* w, const void* part_x, const void* part_1, int nparts, const void* vq,
-                          const void* vr, double count, const void* add, const void* mask_src, int64_t n, int64_t c,
-                          int64_t hw, int64_t out_ld, int64_t add_ld, int a_splits, int64_t a_slab, int dtype) {
-  if (!out || !a || !x || !mean || !rstd || !w || !part_x || !part_1 || nparts < 1 || count <= 0.0 || n <= 0 || c <= 0 ||
-      hw <= 0 || a_splits < 1 || (a_splits > 1 && a_slab <= 0) || dtype != HF_F32)
+// One problem of hf_chan_affine_train / hf_chan_affine_train_pair; `add_ld`: the one argument the struct lacks.
+static int fill_aff_train(AffTrainArgs& q, const hf_affine_train_problem& p, int64_t add_ld, int dtype) {
+  if (!p.out || !p.a || !p.x || !p.mean || !p.rstd || !p.w || !p.part_x || !p.part_1 || p.nparts < 1 ||
+      p.count <= 0.0 || p.n <= 0 || p.c <= 0 || p.hw <= 0 || p.a_splits < 1 || (p.a_splits > 1 && p.a_slab <= 0) ||
+      dtype != HF_F32)
     return HF_ERR_ARG;
-  if (!(c % 4 == 0 && c / 4 <= BLOCK)) return HF_ERR_ARG;
-  if ((out_ld && out_ld < c) || (add_ld && (add_ld < c || !add)) || out_ld > 0x3fffffffLL || add_ld > 0x3fffffffLL)
+  if (!(p.c % 4 == 0 && p.c / 4 <= BLOCK)) return HF_ERR_ARG;
+  if ((p.out_ld && p.out_ld < p.c) || (add_ld && (add_ld < p.c || !p.add)) || p.out_ld > 0x3fffffffLL ||
+      add_ld > 0x3fffffffLL)
     return HF_ERR_ARG;
-  const long long total = (long long)n * c * hw;
-  if (!affine_vec4_ok(out, a, x, mean, rstd, w, nullptr, nullptr, add, mask_src, total, c, 1, out_ld, add_ld, a_slab) ||
-      !aligned16(part_x) || !aligned16(part_1))
+  const long long total = (long long)p.n * p.c * p.hw;
+  const void* const ptrs[] = {p.out, p.a, p.x, p.mean, p.rstd, p.w, p.add, p.mask_src};
+  if (!affine_vec4_ok(ptrs, total, p.c, 1, p.out_ld, add_ld, p.a_slab) || !aligned16(p.part_x) || !aligned16(p.part_1))
     return HF_ERR_ALIGN;
-  q = AffTrainArgs{(float*)out, (const float*)a, (const float*)x, (const float*)mean, (const float*)rstd,
-                   (const float*)w, (const float*)part_x, (const float*)part_1, (unsigned)nparts, (const float*)vq,
-                   (const float*)vr, (float)(1.0 / count), (const float*)add, (const float*)mask_src, (unsigned)total,
-                   (unsigned)c, (unsigned)out_ld, (unsigned)add_ld, a_splits, (long long)a_slab};
+  q = AffTrainArgs{(float*)p.out, (const float*)p.a, (const float*)p.x, (const float*)p.mean, (const float*)p.rstd,
+                   (const float*)p.w, (const float*)p.part_x, (const float*)p.part_1, (unsigned)p.nparts,
+                   (const float*)p.vq, (const float*)p.vr, (float)(1.0 / p.count), (const float*)p.add,
+                   (const float*)p.mask_src, (unsigned)total, (unsigned)p.c, (unsigned)p.out_ld, (unsigned)add_ld,
+                   p.a_splits, (long long)p.a_slab};
   return HF_OK;
 }
 
@@ -1331,9 +1325,12 @@ int hf_chan_affine_train(void* out, const void* a, const void* x, const void* me
                          const void* part_x, const void* part_1, int nparts, const void* vq, const void* vr,
                          double count, const void* add, const void* mask_src, int64_t n, int64_t c, int64_t hw,
                          int64_t out_ld, int64_t add_ld, int a_splits, int64_t a_slab, int dtype, void* stream) {
+  const hf_affine_train_problem p = {.out = out, .a = a, .x = x, .mean = mean, .rstd = rstd, .w = w, .part_x = part_x,
+                                     .part_1 = part_1, .nparts = nparts, .vq = vq, .vr = vr, .count = count,
+                                     .add = add, .mask_src = mask_src, .n = n, .c = c, .hw = hw, .out_ld = out_ld,
+                                     .a_splits = a_splits, .a_slab = a_slab};
   AffTrainArgs q;
-  const int rc = fill_aff_train(q, out, a, x, mean, rstd, w, part_x, part_1, nparts, vq, vr, count, add, mask_src, n, c,
-                                hw, out_ld, add_ld, a_splits, a_slab, dtype);
+  const int rc = fill_aff_train(q, p, add_ld, dtype);
   if (rc) return rc;
   typedef void (*Kern)(AffTrainArgs);
   static const Kern kerns[8] = {
@@ -1353,9 +1350,7 @@ int hf_chan_affine_train_pair(const hf_affine_train_problem* problems, int dtype
   for (int i = 0; i < 2; ++i) {
     const hf_affine_train_problem& p = problems[i];
     if (p.add) return HF_ERR_ARG;  // (no residual operand in the paired form)
-    const int rc = fill_aff_train(q[i], p.out, p.a, p.x, p.mean, p.rstd, p.w, p.part_x, p.part_1, p.nparts, p.vq, p.vr,
-                                  p.count, nullptr, p.mask_src, p.n, p.c, p.hw, p.out_ld, 0, p.a_splits, p.a_slab,
-                                  dtype);
+    const int rc = fill_aff_train(q[i], p, 0, dtype);
     if (rc) return rc;
   }
   typedef void (*Kern)(AffTrainArgs, AffTrainArgs, unsigned);
@@ -1382,8 +1377,7 @@ int hf_chan_affine_pair(const hf_affine_problem* problems, int dtype, void* stre
   unsigned blocks[2];
   for (int i = 0; i < 2; ++i) {
     const hf_affine_problem& p = problems[i];
-    const int rc = fill_aff(q[i], p.out, p.a, p.x, p.mean, p.rstd, p.w, p.q, p.r, p.add, p.mask_src, p.relu_self, p.n,
-                            p.c, p.hw, 1 /* NHWC */, p.out_ld, p.add_ld, p.a_splits, p.a_slab);
+    const int rc = fill_aff(q[i], p, 1 /* NHWC */);
     if (rc) return rc;
     blocks[i] = (unsigned)wide_grid(q[i].vec4 ? q[i].total / 4 : q[i].total);
   }
@@ -1398,23 +1392,22 @@ int hf_chan_affine_pair(const hf_affine_problem* problems, int dtype, void* stre
 // inside the tensor (share i covers rows [i*per, (i+1)*per), per = ceil(rows / row_blocks): an empty share would be a
 // partial row of zeros the caller did not plan for), slab strides that keep the 16-byte loads aligned, and the
 // statistics whenever the scale's gradient is asked for (without x the kernel would leave gw = 0).
-static int fill_bn_adj_rows(BnAdjArgs& k, void* gx, void* gw, void* gb, void* gres, const void* gy, int gy_splits,
-                            int64_t gy_slab, const void* gy2, int gy2_splits, int64_t gy2_slab, const void* x,
-                            const void* mean, const void* rstd, const void* w, const void* mask_src, int64_t n,
-                            int64_t c, int64_t hw, int row_blocks) {
-  if (!gy || n <= 0 || c <= 0 || hw <= 0 || gy_splits < 1 || gy2_splits < 1 || row_blocks < 2) return HF_ERR_ARG;
-  if (!(c % 4 == 0 && c / 4 <= BLOCK)) return HF_ERR_ARG;
-  const int64_t rows = n * hw, per = (rows + row_blocks - 1) / row_blocks;
-  if ((int64_t)(row_blocks - 1) * per >= rows) return HF_ERR_ARG;
-  if (gy_splits > 1 && (gy_slab <= 0 || (gy_slab & 3))) return HF_ERR_ARG;
-  if (gy2 && gy2_splits > 1 && (gy2_slab <= 0 || (gy2_slab & 3))) return HF_ERR_ARG;
-  if (gw && (!x || !mean || !rstd)) return HF_ERR_ARG;
-  if (rows * c > 0x7fffffffLL || !aligned16(gy) || (gy2 && !aligned16(gy2)) || (x && !aligned16(x)) ||
-      (mask_src && !aligned16(mask_src)) || (gx && !aligned16(gx)) || (gres && !aligned16(gres)))
+static int fill_bn_adj_rows(BnAdjArgs& k, const hf_bn_adjoint_problem& p) {
+  if (!p.gy || p.n <= 0 || p.c <= 0 || p.hw <= 0 || p.gy_splits < 1 || p.gy2_splits < 1 || p.row_blocks < 2)
+    return HF_ERR_ARG;
+  if (!(p.c % 4 == 0 && p.c / 4 <= BLOCK)) return HF_ERR_ARG;
+  const int64_t rows = p.n * p.hw, per = (rows + p.row_blocks - 1) / p.row_blocks;
+  if ((int64_t)(p.row_blocks - 1) * per >= rows) return HF_ERR_ARG;
+  if (p.gy_splits > 1 && (p.gy_slab <= 0 || (p.gy_slab & 3))) return HF_ERR_ARG;
+  if (p.gy2 && p.gy2_splits > 1 && (p.gy2_slab <= 0 || (p.gy2_slab & 3))) return HF_ERR_ARG;
+  if (p.gw && (!p.x || !p.mean || !p.rstd)) return HF_ERR_ARG;
+  if (rows * p.c > 0x7fffffffLL || !aligned16(p.gy) || (p.gy2 && !aligned16(p.gy2)) || (p.x && !aligned16(p.x)) ||
+      (p.mask_src && !aligned16(p.mask_src)) || (p.gx && !aligned16(p.gx)) || (p.gres && !aligned16(p.gres)))
     return HF_ERR_ALIGN;
-  k = BnAdjArgs{(float*)gx, (float*)gw, (float*)gb, (float*)gres, (const float*)gy, gy_splits, (long long)gy_slab,
-                (const float*)gy2, gy2_splits, (long long)gy2_slab, (const float*)x, (const float*)mean,
-                (const float*)rstd, (const float*)w, (const float*)mask_src, (unsigned)rows, (unsigned)c, (unsigned)per};
+  k = BnAdjArgs{(float*)p.gx, (float*)p.gw, (float*)p.gb, (float*)p.gres, (const float*)p.gy, p.gy_splits,
+                (long long)p.gy_slab, (const float*)p.gy2, p.gy2_splits, (long long)p.gy2_slab, (const float*)p.x,
+                (const float*)p.mean, (const float*)p.rstd, (const float*)p.w, (const float*)p.mask_src, (unsigned)rows,
+                (unsigned)p.c, (unsigned)per};
   return HF_OK;
 }
 
@@ -1424,8 +1417,7 @@ int hf_chan_affine_bwd_pair(const hf_bn_adjoint_problem* problems, int dtype, vo
   unsigned blocks[2];
   for (int i = 0; i < 2; ++i) {
     const hf_bn_adjoint_problem& p = problems[i];
-    const int rc = fill_bn_adj_rows(q[i], p.gx, p.gw, p.gb, p.gres, p.gy, p.gy_splits, p.gy_slab, p.gy2, p.gy2_splits,
-                                    p.gy2_slab, p.x, p.mean, p.rstd, p.w, p.mask_src, p.n, p.c, p.hw, p.row_blocks);
+    const int rc = fill_bn_adj_rows(q[i], p);
     if (rc) return rc;
     blocks[i] = (unsigned)p.row_blocks;
   }
@@ -1436,21 +1428,18 @@ int hf_chan_affine_bwd_pair(const hf_bn_adjoint_problem* problems, int dtype, vo
 }
 
 template <typename T>
-static void launch_chan_affine_bwd(hipStream_t s, void* gx, void* gw, void* gb, void* gres,
-                                   const void* gy, const void* gy2, const void* x, const void* mean,
-                                   const void* rstd, const void* w, const void* mask_src,
-                                   long long n, long long c, long long hw, int nhwc, int s1 = 1,
-                                   long long l1 = 0, int s2 = 1, long long l2 = 0, int row_blocks = 1) {
-  const long long total = n * c * hw;
+static void launch_chan_affine_bwd(hipStream_t s, const hf_bn_adjoint_problem& p, int nhwc) {
+  const long long n = p.n, c = p.c, hw = p.hw, total = n * c * hw, l1 = p.gy_slab, l2 = p.gy2_slab;
+  const int s1 = p.gy_splits, s2 = p.gy2_splits;
   if (nhwc && hw > 1) {
-    const bool vec = c % 4 == 0 && aligned16(gy) && (!gy2 || aligned16(gy2)) && (!x || aligned16(x)) &&
-                     (!mask_src || aligned16(mask_src)) &&
-                     (!gx || aligned16(gx)) && (!gres || aligned16(gres)) && sizeof(T) == 4;
+    const bool vec = c % 4 == 0 && aligned16(p.gy) && (!p.gy2 || aligned16(p.gy2)) && (!p.x || aligned16(p.x)) &&
+                     (!p.mask_src || aligned16(p.mask_src)) &&
+                     (!p.gx || aligned16(p.gx)) && (!p.gres || aligned16(p.gres)) && sizeof(T) == 4;
 #define HF_BWD_CL(I, W, BS)                                                                        \
-  hipLaunchKernelGGL((k_chan_affine_bwd_nhwc<T, I, W, BS>), dim3((unsigned)(c / W * row_blocks)), dim3(BS), 0, s, \
-                     (T*)gx, (T*)gw, (T*)gb, (T*)gres, (const T*)gy, (const T*)gy2, (const T*)x,    \
-                     (const T*)mean, (const T*)rstd, (const T*)w, (const T*)mask_src, (I)(n * hw), (I)c,  \
-                     s1, l1, s2, l2, row_blocks)
+  hipLaunchKernelGGL((k_chan_affine_bwd_nhwc<T, I, W, BS>), dim3((unsigned)(c / W * p.row_blocks)), dim3(BS), 0, s, \
+                     (T*)p.gx, (T*)p.gw, (T*)p.gb, (T*)p.gres, (const T*)p.gy, (const T*)p.gy2, (const T*)p.x,    \
+                     (const T*)p.mean, (const T*)p.rstd, (const T*)p.w, (const T*)p.mask_src, (I)(n * hw), (I)c,  \
+                     s1, l1, s2, l2, p.row_blocks)
     // (512- and 1024-thread blocks for the early layers' tall reductions were measured: no
     // gain; a row-major kernel with a two-level reduction (block partials + last-ticket block)
     // was correct but slower end to end (885 vs 915 matvecs/s): its extra dependent round
@@ -1466,8 +1455,8 @@ static void launch_chan_affine_bwd(hipStream_t s, void* gx, void* gw, void* gb, 
   const bool small = n * hw <= 256;
 #define HF_BWD(I, TPC, GRID)                                                                    \
   hipLaunchKernelGGL((k_chan_affine_bwd<T, I, TPC>), dim3((unsigned)(GRID)), dim3(BLOCK), 0, s,  \
-                     (T*)gx, (T*)gw, (T*)gb, (T*)gres, (const T*)gy, (const T*)gy2, (const T*)x,  \
-                     (const T*)mean, (const T*)rstd, (const T*)w, (const T*)mask_src, (I)n, (I)c, (I)hw,  \
+                     (T*)p.gx, (T*)p.gw, (T*)p.gb, (T*)p.gres, (const T*)p.gy, (const T*)p.gy2, (const T*)p.x,  \
+                     (const T*)p.mean, (const T*)p.rstd, (const T*)p.w, (const T*)p.mask_src, (I)n, (I)c, (I)hw,  \
                      s1, l1, s2, l2)
   if (total < 0x7fffffffLL) {
     if (small) HF_BWD(unsigned, 64, (c + 3) / 4); else HF_BWD(unsigned, 256, c);
@@ -1491,12 +1480,15 @@ int hf_chan_affine_bwd_ex(void* gx, void* gw, void* gb, void* gres, const void* 
                           const void* mask_src, int64_t n, int64_t c, int64_t hw, int channels_last,
                           int row_blocks, int dtype, void* stream) {
   if (!gy || n <= 0 || c <= 0 || hw <= 0 || gy_splits < 1 || gy2_splits < 1 || row_blocks < 1) return HF_ERR_ARG;
+  hf_bn_adjoint_problem p = {.gx = gx, .gw = gw, .gb = gb, .gres = gres, .gy = gy, .gy_splits = gy_splits,
+                             .gy_slab = gy_slab, .gy2 = gy2, .gy2_splits = gy2_splits, .gy2_slab = gy2_slab, .x = x,
+                             .mean = mean, .rstd = rstd, .w = w, .mask_src = mask_src, .n = n, .c = c, .hw = hw,
+                             .row_blocks = row_blocks};
   // row shares: the row-major NHWC fp32 kernel
   if (row_blocks > 1) {
     if (!(channels_last && dtype == HF_F32)) return HF_ERR_ARG;
     BnAdjArgs k;
-    const int rc = fill_bn_adj_rows(k, gx, gw, gb, gres, gy, gy_splits, gy_slab, gy2, gy2_splits, gy2_slab, x, mean,
-                                    rstd, w, mask_src, n, c, hw, row_blocks);
+    const int rc = fill_bn_adj_rows(k, p);
     if (rc) return rc;
     hipLaunchKernelGGL(k_bn_adjoint_rows, dim3((unsigned)row_blocks), dim3(BLOCK), 0, (hipStream_t)stream, k.gx, k.gw,
                        k.gb, k.gres, k.gy, k.s1, k.l1, k.gy2, k.s2, k.l2, k.x, k.mean, k.rstd, k.w, k.mask_src, k.rows,
@@ -1507,14 +1499,12 @@ int hf_chan_affine_bwd_ex(void* gx, void* gw, void* gb, void* gres, const void* 
   if ((gy_splits > 1 && gy_slab <= 0) || (gy2 && gy2_splits > 1 && gy2_slab <= 0)) return HF_ERR_ARG;
   if ((gy_splits > 1 || gy2_splits > 1) && !(channels_last || hw == 1)) return HF_ERR_ARG;
   if (gw && (!x || !mean || !rstd)) return HF_ERR_ARG;  // (rstd == NULL: no BatchNorm, gx = g * w or g)
-  if (!gw) x = nullptr;  // plain per-channel sums (a conv layer's bias gradient)
+  if (!gw) p.x = nullptr;  // plain per-channel sums (a conv layer's bias gradient)
   hipStream_t s = (hipStream_t)stream;
   if (dtype == HF_F32)
-    launch_chan_affine_bwd<float>(s, gx, gw, gb, gres, gy, gy2, x, mean, rstd, w, mask_src, n, c, hw,
-                                  channels_last, gy_splits, gy_slab, gy2_splits, gy2_slab, row_blocks);
+    launch_chan_affine_bwd<float>(s, p, channels_last);
   else if (dtype == HF_F64)
-    launch_chan_affine_bwd<double>(s, gx, gw, gb, gres, gy, gy2, x, mean, rstd, w, mask_src, n, c, hw,
-                                   channels_last, gy_splits, gy_slab, gy2_splits, gy2_slab, row_blocks);
+    launch_chan_affine_bwd<double>(s, p, channels_last);
   else
     return HF_ERR_ARG;
   HF_HIP(hipGetLastError());
@@ -1523,19 +1513,21 @@ int hf_chan_affine_bwd_ex(void* gx, void* gw, void* gb, void* gres, const void* 
 
 // One problem of the elementwise adjoint (hf_bn_adjoint_v4, hf_bn_adjoint_v4_pair): the quad walk's conditions are
 // refusals here, there is no scalar form behind it.
-static int fill_bn_adj_v4(BnAdjV4Args& k, void* g_out, void* ga_out, const void* gy, int gy_splits, int64_t gy_slab,
-                          const void* gy2, int gy2_splits, int64_t gy2_slab, const void* mask_src, const void* w,
-                          const void* rstd, int64_t rows, int64_t c) {
-  if (!gy || (!g_out && !ga_out) || rows <= 0 || c <= 0 || c % 4 || gy_splits < 1 || gy2_splits < 1) return HF_ERR_ARG;
-  if (gy_splits > 1 && (gy_slab <= 0 || (gy_slab & 3))) return HF_ERR_ARG;
-  if (gy2 && gy2_splits > 1 && (gy2_slab <= 0 || (gy2_slab & 3))) return HF_ERR_ARG;
-  if (rows * c > 0x7fffffffLL) return HF_ERR_ARG;
-  const void* ptrs[] = {g_out, ga_out, gy, gy2, mask_src, w, rstd};
-  for (const void* p : ptrs)
-    if (p && !aligned16(p)) return HF_ERR_ARG;
-  k = BnAdjV4Args{(float*)g_out, (float*)ga_out, (const float*)gy, gy_splits, (long long)gy_slab, (const float*)gy2,
-                  gy2 ? gy2_splits : 1, (long long)gy2_slab, (const float*)mask_src, (const float*)w,
-                  (const float*)rstd, (unsigned)(rows * c), (unsigned)c};
+// Of the struct it reads gres (-> g_out), gx (-> ga_out), the cotangents, mask_src, w, rstd and rows = n * hw, c.
+static int fill_bn_adj_v4(BnAdjV4Args& k, const hf_bn_adjoint_problem& p) {
+  if (p.n <= 0 || p.hw <= 0) return HF_ERR_ARG;
+  const int64_t rows = p.n * p.hw;
+  if (!p.gy || (!p.gres && !p.gx) || rows <= 0 || p.c <= 0 || p.c % 4 || p.gy_splits < 1 || p.gy2_splits < 1)
+    return HF_ERR_ARG;
+  if (p.gy_splits > 1 && (p.gy_slab <= 0 || (p.gy_slab & 3))) return HF_ERR_ARG;
+  if (p.gy2 && p.gy2_splits > 1 && (p.gy2_slab <= 0 || (p.gy2_slab & 3))) return HF_ERR_ARG;
+  if (rows * p.c > 0x7fffffffLL) return HF_ERR_ARG;
+  const void* ptrs[] = {p.gres, p.gx, p.gy, p.gy2, p.mask_src, p.w, p.rstd};
+  for (const void* q : ptrs)
+    if (q && !aligned16(q)) return HF_ERR_ARG;
+  k = BnAdjV4Args{(float*)p.gres, (float*)p.gx, (const float*)p.gy, p.gy_splits, (long long)p.gy_slab,
+                  (const float*)p.gy2, p.gy2 ? p.gy2_splits : 1, (long long)p.gy2_slab, (const float*)p.mask_src,
+                  (const float*)p.w, (const float*)p.rstd, (unsigned)(rows * p.c), (unsigned)p.c};
   return HF_OK;
 }
 
@@ -1543,9 +1535,11 @@ int hf_bn_adjoint_v4(void* g_out, void* ga_out, const void* gy, int gy_splits, i
                      int gy2_splits, int64_t gy2_slab, const void* mask_src, const void* w, const void* rstd,
                      int64_t rows, int64_t c, int dtype, void* stream) {
   if (dtype != HF_F32) return HF_ERR_ARG;
+  const hf_bn_adjoint_problem p = {.gx = ga_out, .gres = g_out, .gy = gy, .gy_splits = gy_splits, .gy_slab = gy_slab,
+                                   .gy2 = gy2, .gy2_splits = gy2_splits, .gy2_slab = gy2_slab, .rstd = rstd, .w = w,
+                                   .mask_src = mask_src, .n = rows, .c = c, .hw = 1};
   BnAdjV4Args k;
-  const int rc = fill_bn_adj_v4(k, g_out, ga_out, gy, gy_splits, gy_slab, gy2, gy2_splits, gy2_slab, mask_src, w, rstd,
-                                rows, c);
+  const int rc = fill_bn_adj_v4(k, p);
   if (rc) return rc;
   hipLaunchKernelGGL(k_bn_adjoint_v4, dim3(wide_grid(k.total / 4)), dim3(BLOCK), 0, (hipStream_t)stream, k);
   HF_HIP(hipGetLastError());
@@ -1558,9 +1552,7 @@ int hf_bn_adjoint_v4_pair(const hf_bn_adjoint_problem* problems, int dtype, void
   unsigned blocks[2];
   for (int i = 0; i < 2; ++i) {
     const hf_bn_adjoint_problem& p = problems[i];
-    if (p.n <= 0 || p.hw <= 0) return HF_ERR_ARG;
-    const int rc = fill_bn_adj_v4(q[i], p.gres, p.gx, p.gy, p.gy_splits, p.gy_slab, p.gy2, p.gy2_splits, p.gy2_slab,
-                                  p.mask_src, p.w, p.rstd, p.n * p.hw, p.c);
+    const int rc = fill_bn_adj_v4(q[i], p);
     if (rc) return rc;
     blocks[i] = (unsigned)wide_grid(q[i].total / 4);
   }

@@ -8,43 +8,32 @@ import os
 import torch
 
 from .. import _lib
-from .common import _cl, _pair, _ptr
+from .common import _cl, _pair
+from .problems import (affine_args, affine_train_args, affine_train_problem, bn_adjoint_args, bn_adjoint_problem,
+                       bn_adjoint_v4_args, problem, sources)
 
 
 class _AdjointSweep:
+    @staticmethod
+    def _train_adjoint_problem(u, ga=None):
+        """Pass 2 of the train-mode adjoint: g_a from the masked cotangent u.g and the partial rows of its sums."""
+        return affine_train_problem(u, u.ga if ga is None else ga, 0, u.g, 1, 0, (u.gw, u.gb, u.rb))
+
     def _bn_adjoint_pair_train(self, u1, srcs1, u2, srcs2):
         """Train mode, prologue form: both units' reduction passes in one launch, both elementwise passes in one."""
         self._bn_adjoint_pair(u1, srcs1, u2, srcs2, train=True)
-        arr = (_lib.AffineTrainProblem * 2)()
-        for q, u in zip(arr, (u1, u2)):
-            self._affine_train_problem(q, u, u.ga, 0, u.g, 1, 0, u.gw, u.gb, u.rb, None, None, None)
-        _lib.check(_lib.load().hf_chan_affine_train_pair(_lib.ctypes.cast(arr, _lib.c_void_p), _lib.HF_F32,
-                                                         _lib.current_stream_ptr(self.dev)), "hf_chan_affine_train_pair")
+        self._launch_pair("hf_chan_affine_train_pair", self._train_adjoint_problem(u1), self._train_adjoint_problem(u2))
 
     def _bn_adjoint_pair(self, u1, srcs1, u2, srcs2, train=False):
         """The BatchNorm adjoints of two units (row-major kernel) in ONE launch.  ``train``: the reduction pass of the
         train-mode adjoint (masked cotangent and partial sums only)."""
-        arr = (_lib.BnAdjointProblem * 2)()
-        for q, u, srcs in zip(arr, (u1, u2), (srcs1, srcs2)):
-            if not 1 <= len(srcs) <= 2:
-                raise RuntimeError(f"{u.name}: {len(srcs)} consumers")
-            (a, sa, la) = srcs[0]
-            (b, sb, lb) = srcs[1] if len(srcs) == 2 else (None, 1, 0)
-            n, k, oh, ow = u.a.shape
-            q.gx, q.gw, q.gb, q.gres = (None if train else u.ga.data_ptr()), u.gw.data_ptr(), u.gb.data_ptr(), u.g.data_ptr()
-            q.gy, q.gy_splits, q.gy_slab = a.data_ptr(), sa, la
-            q.gy2, q.gy2_splits, q.gy2_slab = (None if b is None else b.data_ptr()), sb, lb
-            q.x, q.mean, q.rstd, q.w = u.a.data_ptr(), u.mean.data_ptr(), u.rstd.data_ptr(), u.bn.weight.data_ptr()
-            q.mask_src = u.y.data_ptr() if u.relu else None
-            q.n, q.c, q.hw, q.row_blocks = n, k, oh * ow, u.rb
+        probs = [bn_adjoint_problem(u, srcs, reduce=train) for u, srcs in ((u1, srcs1), (u2, srcs2))]
         if not train and self._split_now(u1) and self._split_now(u2):
             # the chain's launch is the elementwise one; the per-channel sums wait for _flush_sums
-            _lib.check(_lib.load().hf_bn_adjoint_v4_pair(_lib.ctypes.cast(arr, _lib.c_void_p), _lib.HF_F32,
-                                                         _lib.current_stream_ptr(self.dev)), "hf_bn_adjoint_v4_pair")
+            self._launch_pair("hf_bn_adjoint_v4_pair", *probs)
             self._sums_pending.update(u.sums_slot for u in (u1, u2) if u.defer)
             return
-        _lib.check(_lib.load().hf_chan_affine_bwd_pair(_lib.ctypes.cast(arr, _lib.c_void_p), _lib.HF_F32,
-                                                       _lib.current_stream_ptr(self.dev)), "hf_chan_affine_bwd_pair")
+        self._launch_pair("hf_chan_affine_bwd_pair", *probs)
 
     def _adjoint_unit(self, u, srcs):
         """srcs: up to two (tensor, splits, slab_stride) cotangents of the unit's output."""
@@ -54,10 +43,10 @@ class _AdjointSweep:
             self._conv_adjoint(u)
             return
         # ---- Hessian product: the tangent of the backward sweep through this unit --------------------------
-        lib, st = _lib.load(), _lib.current_stream_ptr(self.dev)
         n, k, oh, ow = u.a.shape
-        v = self._v
-        v_gamma = v[self._offs[u.pg]: self._offs[u.pg] + k] if u.pg is not None else self._zeros(k)  # (frozen scale)
+        v_gamma = self._param_slice(self._v, u.pg, k)
+        if v_gamma is None:  # (frozen scale)
+            v_gamma = self._zeros(k)
         if not self._extras_parallel:
             self._hessian_extras(u)
         if u.train:
@@ -65,19 +54,15 @@ class _AdjointSweep:
             # tangent sweep's a' sums), then  g_a' = c0 g_a + c1 g_z + c2 g_z' + c3 a' + c4 xhat + c5
             rb = u.rb
             tx, t1, nparts_t = u.tsums
-            _lib.check(lib.hf_bn_train_hessian_coeffs(
-                _ptr(u.hcoef), _ptr(u.gw[2 * rb:]), _ptr(u.gw), _ptr(u.gb), _ptr(u.gw[rb:]), rb, _ptr(tx), _ptr(t1),
-                nparts_t, _ptr(u.gg1), _ptr(u.gb1), _ptr(u.scale), _ptr(v_gamma), _ptr(u.rstd), float(n * oh * ow), k,
-                _lib.HF_F32, st), "hf_bn_train_hessian_coeffs")
-            _lib.check(lib.hf_bn_train_hessian_apply(
-                _ptr(u.gah), _ptr(u.ga1), _ptr(u.g1), _ptr(u.g), _ptr(u.tbuf), u.sT, u.tbuf.shape[1], _ptr(u.a),
-                _ptr(u.mean), _ptr(u.rstd), _ptr(u.hcoef), n * oh * ow, k, _lib.HF_F32, st),
-                "hf_bn_train_hessian_apply")
+            self._launch("hf_bn_train_hessian_coeffs", u.hcoef, u.gw[2 * rb:], u.gw, u.gb, u.gw[rb:], rb, tx, t1, nparts_t,
+                         u.gg1, u.gb1, u.scale, v_gamma, u.rstd, float(n * oh * ow), k)
+            self._launch("hf_bn_train_hessian_apply", u.gah, u.ga1, u.g1, u.g, u.tbuf, u.sT, u.tbuf.shape[1], u.a, u.mean,
+                         u.rstd, u.hcoef, n * oh * ow, k)
         else:
             # the convolution's cotangent tangent:  g_a' + g_z * rstd * v_gamma
-            _lib.check(lib.hf_chan_affine_ex(
-                _ptr(u.gah), _ptr(u.g1), None, None, _ptr(u.rstd), _ptr(v_gamma), None, None, _ptr(u.ga), None, 0, n,
-                k, oh * ow, 1, 0, 0, 1, 0, _lib.HF_F32, st), "hf_chan_affine_ex")
+            self._launch("hf_chan_affine_ex", *affine_args(problem(
+                _lib.AffineProblem, out=u.gah, a=u.g1, rstd=u.rstd, w=v_gamma, add=u.ga, n=n, c=k, hw=oh * ow,
+                a_splits=1)))
         if self._extras_mode == 2 and not u.im2col and not u.first and u.sD:
             # the chain's launch also computes conv_D(g_a, V) -- the one extra term the chain itself needs next
             _lib.conv_group_slabs([(1, u.dbuf, u.gah, u.wT, u.geo, u.sD, 0, 0), (2, u.wbuf, u.x, u.gah, u.geo, u.sW, 0, 0),
@@ -92,51 +77,29 @@ class _AdjointSweep:
     def _bn_adjoint(self, u, srcs, ga=None, reduce_only=False):
         """``reduce_only`` (train mode inside a Hessian product): the masked cotangent and its per-channel sums only --
         the elementwise pass is ``hf_bn_train_hessian_apply``'s."""
-        ga = u.ga if ga is None else ga
-        if not 1 <= len(srcs) <= 2:
-            raise RuntimeError(f"{u.name}: {len(srcs)} consumers")
         self._extras_wait(srcs)
-        (a, sa, la) = srcs[0]
-        (b, sb, lb) = srcs[1] if len(srcs) == 2 else (None, 1, 0)
-        lib, st = _lib.load(), _lib.current_stream_ptr(self.dev)
-        n, k, oh, ow = u.a.shape
         if u.train:
             # pass 1: g = mask * (sum of the cotangents' slabs) and its per-channel sums (the parameter
             # gradients); pass 2: g_a = rstd*w * [g - mean(g) - xhat * mean(xhat*g)] (the batch statistics'
             # share), by the elementwise kernel with the corrections folded into its per-channel vectors
             # (pass 2 adds the partial rows up in its prologue)
-            _lib.check(lib.hf_chan_affine_bwd_ex(
-                None, _ptr(u.gw), _ptr(u.gb), _ptr(u.g), _ptr(a), sa, la, _ptr(b), sb, lb, _ptr(u.a),
-                _ptr(u.mean), _ptr(u.rstd), _ptr(u.scale), _ptr(u.y) if u.relu else None, n, k, oh * ow, 1,
-                u.rb, _lib.HF_F32, st), "hf_chan_affine_bwd_ex")
-            if reduce_only:
-                return
-            _lib.check(lib.hf_chan_affine_train(
-                _ptr(ga), _ptr(u.g), _ptr(u.a), _ptr(u.mean), _ptr(u.rstd), _ptr(u.scale), _ptr(u.gw),
-                _ptr(u.gb), u.rb, None, None, float(n * oh * ow), None, None, n, k, oh * ow, 0, 0, 1, 0,
-                _lib.HF_F32, st), "hf_chan_affine_train")
+            self._launch("hf_chan_affine_bwd_ex", *bn_adjoint_args(bn_adjoint_problem(u, srcs, reduce=True)))
+            if not reduce_only:
+                self._launch("hf_chan_affine_train", *affine_train_args(self._train_adjoint_problem(u, ga)))
             return
         if self._split_now(u):
             # g = mask * (sum of both cotangents' slabs) -> u.g; g * w*rstd -> u.ga: all the chain needs.  The per-channel
             # sums (the parameters' gradient: only the gather reads them) wait for _flush_sums
-            _lib.check(lib.hf_bn_adjoint_v4(
-                _ptr(u.g), _ptr(ga), _ptr(a), sa, la, _ptr(b), sb, lb, _ptr(u.y) if u.relu else None, _ptr(u.scale),
-                _ptr(u.rstd), n * oh * ow, k, _lib.HF_F32, st), "hf_bn_adjoint_v4")
+            self._launch("hf_bn_adjoint_v4", *bn_adjoint_v4_args(bn_adjoint_problem(u, srcs, ga)))
             if u.defer:
                 self._sums_pending.add(u.sums_slot)
             return
         # g = mask * (sum of both cotangents' slabs) -> u.g; g * w*rstd -> u.ga; per-channel sums
-        bn = u.bn is not None
-        _lib.check(lib.hf_chan_affine_bwd_ex(
-            _ptr(ga), _ptr(u.gw) if bn else None, _ptr(u.gb) if u.pb is not None else None,
-            _ptr(u.g) if u.needs_g else None, _ptr(a), sa, la, _ptr(b), sb, lb, _ptr(u.a) if bn else None,
-            _ptr(u.mean), _ptr(u.rstd), _ptr(u.scale), _ptr(u.y) if u.relu else None, n, k,
-            oh * ow, 1, u.rb, _lib.HF_F32, st), "hf_chan_affine_bwd_ex")
+        self._launch("hf_chan_affine_bwd_ex", *bn_adjoint_args(bn_adjoint_problem(u, srcs, ga, only_needed=True)))
 
     def _conv_adjoint(self, u, ga=None):
         """Data + weight gradient of the unit's convolution from ``ga`` (default ``u.ga``), one launch."""
         ga = u.ga if ga is None else ga
-        lib, st = _lib.load(), _lib.current_stream_ptr(self.dev)
         if u.im2col:
             self._conv_slabs(2, u.wbuf, u.cols_pad, ga, u.geo_w, u.sW, out_c=u.jcols)
             return
@@ -149,10 +112,8 @@ class _AdjointSweep:
         # ResNet-50 topology 314 -> 253, All-CNN-C 753 -> 711.  A side branch pays when it forks ONCE: the Hessian
         # products' extras below.)
         n_, h, w, c, k_, r, s, sd, pd = u.geo
-        _lib.check(lib.hf_conv2d_nhwc_backward_slabs(
-            _ptr(u.dbuf), _ptr(u.wbuf), _ptr(ga), _ptr(u.x), _ptr(u.wT), n_, h, w, c, k_, r, s, sd[0], sd[1],
-            pd[0], pd[1], u.sD, u.dbuf.shape[1], u.sW, u.wbuf.shape[1], _lib.HF_F32, st),
-            "hf_conv2d_nhwc_backward_slabs")
+        self._launch("hf_conv2d_nhwc_backward_slabs", u.dbuf, u.wbuf, ga, u.x, u.wT, n_, h, w, c, k_, r, s, sd[0], sd[1],
+                     pd[0], pd[1], u.sD, u.dbuf.shape[1], u.sW, u.wbuf.shape[1])
 
     # ---- adjoint sweep -------------------------------------------------------------------------
     def _adjoint_blocks(self, g_last, first=None, last_block=0, incoming=None):
@@ -220,15 +181,12 @@ class _AdjointSweep:
             return
         ks, st_, pd, dl, cm = self.pool_args
         pn, ph, pw, poh, pow_, c0 = self._pool_geometry()
-        (a, sa, la), (b, sb, lb) = pool_srcs
         self._extras_wait(pool_srcs)
         # slab sums of both cotangents and the max-pool adjoint (gather form) in one launch
         g_stem = self._g_stem
         (kh, kw), (sh, sw), (pph, ppw) = _pair(ks), _pair(st_ if st_ is not None else ks), _pair(pd)
-        _lib.check(_lib.load().hf_maxpool_adjoint_nhwc(
-            _ptr(g_stem), _ptr(a), sa, la, _ptr(b), sb, lb, _ptr(self.pool_idx32), pn, ph, pw, poh, pow_,
-            c0, kh, kw, sh, sw, pph, ppw, _lib.HF_F32, _lib.current_stream_ptr(self.dev)),
-            "hf_maxpool_adjoint_nhwc")
+        self._launch("hf_maxpool_adjoint_nhwc", g_stem, *sources("max-pool", pool_srcs), self.pool_idx32, pn, ph, pw, poh,
+                     pow_, c0, kh, kw, sh, sw, pph, ppw)
         self._adjoint_unit(s, [(g_stem, 1, 0)])
 
     def _feature_cotangent(self, g_feat):
@@ -237,13 +195,10 @@ class _AdjointSweep:
             return g_feat.view(tail.y.shape)
         return _cl((g_feat / self._head_hw).view(g_feat.shape[0], -1, 1, 1).expand(tail.y.shape))
 
-    def _gather(self, out, g_fw, g_fb, first_order=False):
-        """All parameter gradients into the flat vector (weight-gradient slabs summed on the way)."""
-        self._flush_sums()
-        tensors, perms, splits = self._pack_args(first_order)
-        tensors = list(tensors)
+    def _head_entries(self, tensors, splits, g_fw, g_fb):
+        """The head's weight / bias gradients as entries of ``hf_pack_ex``'s tables (copies of them)."""
+        tensors, splits = list(tensors), dict(splits)
         if g_fw.dim() == 3:  # the head kernel's per-workgroup partial sums: slabs for hf_pack_ex
-            splits = dict(splits)
             tensors[self.pfw] = g_fw[0]
             splits[self.pfw] = (g_fw.shape[0], g_fw[0].numel())
             if self.pfb is not None:
@@ -253,6 +208,13 @@ class _AdjointSweep:
             tensors[self.pfw] = g_fw
             if self.pfb is not None:
                 tensors[self.pfb] = g_fb
+        return tensors, splits
+
+    def _gather(self, out, g_fw, g_fb, first_order=False):
+        """All parameter gradients into the flat vector (weight-gradient slabs summed on the way)."""
+        self._flush_sums()
+        tensors, perms, splits = self._pack_args(first_order)
+        tensors, splits = self._head_entries(tensors, splits, g_fw, g_fb)
         _lib.pack_ex(out, tensors, perms, splits, scale=self.weight, live=self._pack_live,
                      compact=getattr(self, "_compact_nl", None))  # (local_compact: the compact layout)
         return out
@@ -261,18 +223,8 @@ class _AdjointSweep:
         """``_gather`` for the parameters ``lo ... hi-1`` only (a contiguous range of the flat vector)."""
         self._flush_sums()  # (what this phase of the sweep has deferred)
         tensors, perms, splits = self._pack_args()
-        tensors, splits = list(tensors), dict(splits)
         if g_fw is not None:
-            if g_fw.dim() == 3:
-                tensors[self.pfw] = g_fw[0]
-                splits[self.pfw] = (g_fw.shape[0], g_fw[0].numel())
-                if self.pfb is not None:
-                    tensors[self.pfb] = g_fb[0]
-                    splits[self.pfb] = (g_fb.shape[0], g_fb.shape[1])
-            else:
-                tensors[self.pfw] = g_fw
-                if self.pfb is not None:
-                    tensors[self.pfb] = g_fb
+            tensors, splits = self._head_entries(tensors, splits, g_fw, g_fb)
         sub = lambda d: {i - lo: val for i, val in d.items() if lo <= i < hi}  # noqa: E731
         end = self._offs[hi] if hi < len(self.params) else self.n
         _lib.pack_ex(out[self._offs[lo]:end], tensors[lo:hi], sub(perms), sub(splits), scale=self.weight,

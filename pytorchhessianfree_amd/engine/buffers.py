@@ -9,7 +9,8 @@ import torch
 from torch import nn
 
 from .. import _lib
-from .common import _Unsupported, _flat_view, _live_taps, _pair, _ptr
+from .common import _Unsupported, _flat_view, _live_taps, _pair
+from .problems import bn_adjoint_args, chan_sums_problem
 
 
 def adjoint_split_ok(train, rb, hessian, map_bytes, max_bytes, enabled=True):
@@ -311,10 +312,9 @@ class _Buffers:
         range of the table (one, for a whole sweep).  Runs in front of every gather."""
         if not self._sums_pending:
             return
-        lib, st = _lib.load(), _lib.current_stream_ptr(self.dev)
         for first, count in sums_runs(self._sums_pending, _lib.BN_SUMS_MAX):
-            _lib.check(lib.hf_bn_sums_multi(self._sums_dev.data_ptr(), _lib.ctypes.cast(self._sums_tab, _lib.c_void_p),
-                                            len(self._sums_tab), first, count, _lib.HF_F32, st), "hf_bn_sums_multi")
+            self._launch("hf_bn_sums_multi", self._sums_dev, _lib.ctypes.cast(self._sums_tab, _lib.c_void_p),
+                         len(self._sums_tab), first, count)
             self.sums_launches += 1
         self._sums_pending.clear()
 
@@ -438,6 +438,15 @@ class _Buffers:
             cache[k] = torch.zeros(k, dtype=torch.float32, device=self.dev)
         return cache[k]
 
+    def _param_slice(self, v, index, count):
+        """``count`` entries of the flat vector ``v`` at parameter ``index`` (None: a frozen parameter -- no slice)."""
+        return None if index is None else v[self._offs[index]: self._offs[index] + count]
+
+    def _chan_sums(self, gy, splits, slab, n, c, hw, row_blocks, **operands):
+        """A plain per-channel reduction by the BatchNorm adjoint's launch (``problems.chan_sums_problem``)."""
+        self._launch("hf_chan_affine_bwd_ex",
+                     *bn_adjoint_args(chan_sums_problem(gy, splits, slab, n, c, hw, row_blocks, **operands)))
+
     # ---- tangent sweep -------------------------------------------------------------------------
     def _pool_geometry(self):
         """(n, h, w, oh, ow, c) of the stem's max-pool (window maxima's positions: ``forward_own``)."""
@@ -451,10 +460,8 @@ class _Buffers:
     # ---- kernels ---------------------------------------------------------------------------
     def _conv_slabs(self, direction, out, act, mat, geo, splits, act_ld=0, out_c=0, mat_ld=0):
         n, h, w, c, k, r, s, st, pd = geo
-        _lib.check(_lib.load().hf_conv2d_nhwc_slabs(
-            direction, _ptr(out), _ptr(act), _ptr(mat), n, h, w, c, k, r, s, st[0], st[1], pd[0], pd[1], act_ld,
-            mat_ld, out_c, splits, out.shape[1] if out.dim() == 2 else 0, _lib.HF_F32,
-            _lib.current_stream_ptr(self.dev)), "hf_conv2d_nhwc_slabs")
+        self._launch("hf_conv2d_nhwc_slabs", direction, out, act, mat, n, h, w, c, k, r, s, st[0], st[1], pd[0], pd[1],
+                     act_ld, mat_ld, out_c, splits, out.shape[1] if out.dim() == 2 else 0)
 
     def _conv_carrying_scatter(self, u, mat, splits, src, half):
         """The im2col'd first layer's convolution (its weight operand ``mat`` is a slice of a flat vector, no
@@ -467,15 +474,11 @@ class _Buffers:
         n, h, w, c, k, r, s_, st, pd = u.geo
         table = _lib.unpack_table(src, self._slot_list, half=half)
         periods = _lib.compact_periods(self._slot_list)
+        conv = (u.tbuf, u.cols, mat, n, h, w, c, k, r, s_, st[0], st[1], pd[0], pd[1], 0, 0, splits, u.tbuf.shape[1], src)
         if periods is not None:  # (local_compact: ``src`` is a vector in the compact layout)
-            rc = _lib.load().hf_conv2d_nhwc_slabs_unpack_compact(
-                _ptr(u.tbuf), _ptr(u.cols), _ptr(mat), n, h, w, c, k, r, s_, st[0], st[1], pd[0], pd[1], 0, 0, splits,
-                u.tbuf.shape[1], _ptr(src), *table[:-1], periods, table[-1], _lib.HF_F32,
-                _lib.current_stream_ptr(self.dev))
+            rc = self._launch_rc("hf_conv2d_nhwc_slabs_unpack_compact", *conv, *table[:-1], periods, table[-1])
         else:
-            rc = _lib.load().hf_conv2d_nhwc_slabs_unpack(
-                _ptr(u.tbuf), _ptr(u.cols), _ptr(mat), n, h, w, c, k, r, s_, st[0], st[1], pd[0], pd[1], 0, 0, splits,
-                u.tbuf.shape[1], _ptr(src), *table, _lib.HF_F32, _lib.current_stream_ptr(self.dev))
+            rc = self._launch_rc("hf_conv2d_nhwc_slabs_unpack", *conv, *table)
         if rc == _lib.HF_ERR_ARG:
             self._carry_ok = False
             return False

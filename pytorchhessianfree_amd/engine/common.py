@@ -13,6 +13,25 @@ def _ptr(t):
     return _P(t.data_ptr()) if t is not None else None
 
 
+class _Launcher:
+    """The one way an engine calls a launching entry point of the library (all end in ``int dtype, void* stream``): by
+    name, fetched from the loaded library at the moment of the call, on the current stream; tensors go as their addresses,
+    ``None`` as NULL."""
+
+    def _launch_rc(self, name, *args):
+        """The entry point's return code, for the callers that read it themselves."""
+        args = [_ptr(a) if isinstance(a, torch.Tensor) else a for a in args]
+        return getattr(_lib.load(), name)(*args, _lib.HF_F32, _lib.current_stream_ptr(self.dev))
+
+    def _launch(self, name, *args):
+        _lib.check(self._launch_rc(name, *args), name)
+
+    def _launch_pair(self, name, p1, p2):
+        """The two-problem form of a launch: the same descriptions the one-problem form takes apart (problems.py)."""
+        arr = (type(p1) * 2)(p1, p2)
+        self._launch(name, _lib.ctypes.cast(arr, _P))
+
+
 def _same(a, b):
     """Two records refer to the same activation (records are detached: compare storage)."""
     return a is not None and b is not None and a.data_ptr() == b.data_ptr() and a.shape == b.shape

@@ -40,7 +40,7 @@ import torch
 
 from .. import _lib
 from ..curvature import GGNOperator, _Operator
-from .common import _Node, _Unsupported, _ce_node, ce_loss_spec, loss_spec_of  # noqa: F401
+from .common import _Launcher, _Node, _Unsupported, _ce_node, ce_loss_spec, loss_spec_of  # noqa: F401
 from .adjoint import _AdjointSweep
 from .buffers import _Buffers
 from .dataparallel import _DataParallel
@@ -51,8 +51,8 @@ from .tangent import _TangentSweep
 from .topology import _Topology
 
 
-class FusedGGNEngine(_Topology, _Buffers, _Forward, _TangentSweep, _AdjointSweep, _HessianExtras, _DiagEF, _DataParallel,
-                     _Operator):
+class FusedGGNEngine(_Launcher, _Topology, _Buffers, _Forward, _TangentSweep, _AdjointSweep, _HessianExtras, _DiagEF,
+                     _DataParallel, _Operator):
     mode = ("fused curvature engine: own deterministic convolutions (split-K slabs summed by the consumer "
             "kernel), BatchNorm tangents/adjoints fused, 4 launches per conv-BN unit, downsample branches grouped "
             "with their block's first convolution")

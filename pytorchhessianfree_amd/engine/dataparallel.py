@@ -9,7 +9,7 @@ import torch
 
 from .. import _lib
 from ..curvature import _all_reduce_sum
-from .common import _live_taps, _ptr
+from .common import _live_taps
 
 
 class _DataParallel:
@@ -147,9 +147,7 @@ class _DataParallel:
         if hi <= lo:
             return
         sub = lambda a: (_lib.c_int64 * (hi - lo))(*a[lo:hi])  # noqa: E731
-        _lib.check(_lib.load().hf_live_copy(_ptr(full), _ptr(comp), int(scatter), sub(offs), sub(counts), sub(periods),
-                                            sub(masks), hi - lo, _lib.HF_F32, _lib.current_stream_ptr(self.dev)),
-                   "hf_live_copy")
+        self._launch("hf_live_copy", full, comp, int(scatter), sub(offs), sub(counts), sub(periods), sub(masks), hi - lo)
 
     @property
     def reduce_bytes(self):

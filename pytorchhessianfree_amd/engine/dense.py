@@ -9,7 +9,7 @@ from torch import nn
 
 from .. import _lib
 from ..curvature import GGNOperator, _Operator
-from .common import _Node, _P, _Unsupported, _ce_node, _flat_view, _ptr, _same, loss_spec_of
+from .common import _Node, _P, _Unsupported, _ce_node, _flat_view, _same, loss_spec_of
 from .core import FusedGGNEngine
 
 _ACT = {None: 0, nn.ReLU: 1, nn.Tanh: 2}
@@ -240,13 +240,7 @@ class DenseStackEngine(FusedGGNEngine):
         # is valid only while they stay where its graphs read them
         self._flat_params = _flat_view(self.params, self.n)
 
-    # ---- launches ----------------------------------------------------------------------------
-    def _launch(self, name, *args):
-        """One launching entry point of the library (all end in ``int dtype, void* stream``) on the current stream:
-        tensors go as their addresses."""
-        args = [_ptr(a) if isinstance(a, torch.Tensor) else a for a in args]
-        _lib.check(getattr(_lib.load(), name)(*args, _lib.HF_F32, _lib.current_stream_ptr(self.dev)), name)
-
+    # ---- launches (``_launch``: common._Launcher) ------------------------------------------------
     def _tangent(self, u, t_x, v_w):
         """``u.tslabs <- t_x W^T + x V^T`` (either term may be absent, not both)."""
         self._launch("hf_dense_tangent_slabs", u.tslabs, t_x, u.x, u.lin.weight, v_w, self.rows, u.c_in, u.c_out, 0, u.sT,

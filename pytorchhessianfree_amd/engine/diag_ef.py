@@ -6,7 +6,6 @@ Mixin of ``FusedGGNEngine`` (engine/core.py); see that class for the sweeps' ove
 import torch
 
 from .. import _lib
-from .common import _ptr
 
 
 class _DiagEF:
@@ -34,7 +33,6 @@ class _DiagEF:
             self._l2 = l2
         scale = float(n) if reduction == "mean" else 1.0   # the sweep's cotangents carry the loss's 1/N
         first_order = self.hessian
-        lib, st = _lib.load(), _lib.current_stream_ptr(self.dev)
         self._diag_buffers()
         tensors, perms, splits = self._diag_pack
         for i in range(n):
@@ -53,13 +51,9 @@ class _DiagEF:
                     continue
                 if u.bn is not None:
                     g = (u.g1 if first_order else u.g)[i:i + 1]
-                    _lib.check(lib.hf_chan_affine_bwd_ex(
-                        None, _ptr(u.gws), _ptr(u.gbs), None, _ptr(g), 1, 0, None, 1, 0, _ptr(u.a[i:i + 1]), _ptr(u.mean),
-                        _ptr(u.rstd), None, None, 1, k, hw, 1, 1, _lib.HF_F32, st), "hf_chan_affine_bwd_ex")
+                    self._chan_sums(g, 1, 0, 1, k, hw, 1, gw=u.gws, gb=u.gbs, x=u.a[i:i + 1], mean=u.mean, rstd=u.rstd)
                 elif u.pb is not None:
-                    _lib.check(lib.hf_chan_affine_bwd_ex(
-                        None, None, _ptr(u.gbs), None, _ptr(ga), 1, 0, None, 1, 0, None, None, None, None, None, 1, k, hw,
-                        1, 1, _lib.HF_F32, st), "hf_chan_affine_bwd_ex")
+                    self._chan_sums(ga, 1, 0, 1, k, hw, 1, gb=u.gbs)
             _lib.pack_ex(out, tensors, perms, splits, scale=scale, live=self._pack_live, mode=1)
         if self.fc is not None:
             # linear head: the per-sample weight gradient is the outer product g_i x feat_i, so the sum of its squares

@@ -6,8 +6,7 @@ Mixin of ``FusedGGNEngine`` (engine/core.py); see that class for the sweeps' ove
 import torch
 from torch import nn
 
-from .. import _lib
-from .common import _pair, _ptr
+from .common import _pair
 
 
 class _Forward:
@@ -17,26 +16,19 @@ class _Forward:
         if u.train:
             # ONE pass for the partial sums (the convolution's slabs summed into ``a``, per-channel sum a / sum a^2 in
             # fp64 per row block); the normalising launch adds them up in its prologue -- 2 launches per unit
-            bn, st = u.bn, _lib.current_stream_ptr(self.dev)
+            bn = u.bn
             move = update_running and bn.track_running_stats
             count = float(n * oh * ow)
-            _lib.check(_lib.load().hf_bn_stats_rows(
-                _ptr(u.a), _ptr(u.tbuf), splits, u.tbuf.shape[1], _ptr(u.stat_part), n * oh * ow, k, u.rb,
-                _lib.HF_F32, st), "hf_bn_stats_rows")
-            _lib.check(_lib.load().hf_bn_forward_train(
-                _ptr(u.y), _ptr(u.yout2), 2 * k if u.yout2 is not None else 0, _ptr(u.a), _ptr(u.stat_part), u.rb,
-                _ptr(u.mean_t), _ptr(u.rstd), _ptr(bn.running_mean) if move else None,
-                _ptr(bn.running_var) if move else None, count, float(bn.eps), float(bn.momentum) if move else -1.0,
-                _ptr(u.scale), _ptr(u.shift), _ptr(res), 0, 1 if u.relu else 0, n * oh * ow, k, _lib.HF_F32, st),
-                "hf_bn_forward_train")
+            self._launch("hf_bn_stats_rows", u.a, u.tbuf, splits, u.tbuf.shape[1], u.stat_part, n * oh * ow, k, u.rb)
+            self._launch("hf_bn_forward_train", u.y, u.yout2, 2 * k if u.yout2 is not None else 0, u.a, u.stat_part, u.rb,
+                         u.mean_t, u.rstd, bn.running_mean if move else None, bn.running_var if move else None, count,
+                         float(bn.eps), float(bn.momentum) if move else -1.0, u.scale, u.shift, res, 0,
+                         1 if u.relu else 0, n * oh * ow, k)
             if move:
                 bn.num_batches_tracked.add_(1)
             return
-        _lib.check(_lib.load().hf_bn_forward(
-            _ptr(u.y), _ptr(u.yout2), 2 * k if u.yout2 is not None else 0, _ptr(u.a), _ptr(u.tbuf), splits,
-            u.tbuf.shape[1], _ptr(u.mean), _ptr(u.rstd), _ptr(u.scale), _ptr(u.shift),
-            _ptr(res), 0, 1 if u.relu else 0, n * oh * ow, k, _lib.HF_F32, _lib.current_stream_ptr(self.dev)),
-            "hf_bn_forward")
+        self._launch("hf_bn_forward", u.y, u.yout2, 2 * k if u.yout2 is not None else 0, u.a, u.tbuf, splits,
+                     u.tbuf.shape[1], u.mean, u.rstd, u.scale, u.shift, res, 0, 1 if u.relu else 0, n * oh * ow, k)
 
     def _conv_forward(self, u):
         if u.im2col:  # 1x1 product over the im2col; the weight is read from the parameter itself
@@ -64,10 +56,8 @@ class _Forward:
         ks, st_, pd, _dl, _cm = self.pool_args
         pn, ph, pw, poh, pow_, c0 = self._pool_geometry()
         (kh, kw), (sh, sw), (pph, ppw) = _pair(ks), _pair(st_ if st_ is not None else ks), _pair(pd)
-        _lib.check(_lib.load().hf_maxpool_forward_nhwc(
-            _ptr(self.pool_out), _ptr(self.pool_t[:, c0:]), 2 * c0, _ptr(self.pool_idx32), _ptr(s.y), pn, ph, pw,
-            poh, pow_, c0, kh, kw, sh, sw, pph, ppw, _lib.HF_F32, _lib.current_stream_ptr(self.dev)),
-            "hf_maxpool_forward_nhwc")
+        self._launch("hf_maxpool_forward_nhwc", self.pool_out, self.pool_t[:, c0:], 2 * c0, self.pool_idx32, s.y, pn, ph, pw,
+                     poh, pow_, c0, kh, kw, sh, sw, pph, ppw)
         for chain, ds, _x in self.blocks:
             if ds is not None:
                 self._conv_forward(ds)

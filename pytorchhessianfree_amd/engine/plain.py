@@ -4,7 +4,7 @@ import torch
 from torch import nn
 
 from .. import _lib
-from .common import _Unit, _Unsupported, _cl, _ptr, _same
+from .common import _Unit, _Unsupported, _cl, _same
 from .core import FusedGGNEngine
 
 
@@ -196,9 +196,8 @@ class PlainStackEngine(FusedGGNEngine):
         if self.hessian and self._vt_slots:
             _lib.unpack_tangent(v, self._vt_slots, half=2)  # V as (I, H, W, O): the operand of conv_D(g, V)
         n, k = self.logits.shape
-        _lib.check(_lib.load().hf_pool_ce_head(
-            _ptr(self._g_last), None, _ptr(self.tail.tout), _ptr(self._ce[0]), float(self._ce[1]), n, self._head_hw, k,
-            _lib.HF_F32, _lib.current_stream_ptr(self.dev)), "hf_pool_ce_head")
+        self._launch("hf_pool_ce_head", self._g_last, None, self.tail.tout, self._ce[0], float(self._ce[1]), n,
+                     self._head_hw, k)
         if self.hessian:
             self._extras_fork()
         try:

@@ -8,7 +8,7 @@ import os
 import torch
 
 from .. import _lib
-from .common import _ptr
+from .problems import affine_args, affine_problem, affine_train_args, affine_train_problem
 
 
 def head_fused_shape_ok(rows, features, classes):
@@ -21,83 +21,60 @@ def head_fused_shape_ok(rows, features, classes):
 
 
 class _TangentSweep:
+    def _scale_shift_tangent(self, u, v):
+        k = u.a.shape[1]
+        return self._param_slice(v, u.pg, k), self._param_slice(v, u.pb, k)
+
+    def _scale_second_order_sum(self, u):
+        """rstd * sum_rows g_z * t_a  (g_z: the step's first-order masked cotangent; t_a: the sum of the tangent
+        convolution's slabs) as the second ``rb`` rows of gw, where the gather expects the scale's second-order share."""
+        n, k, oh, ow = u.a.shape
+        self._chan_sums(u.tbuf, u.sT, u.tbuf.shape[1], n, k, oh * ow, u.rb, gw=u.gw[u.rb:], x=u.g1, mean=self._zeros(k),
+                        rstd=u.rstd)
+
     def _bn_tangent(self, u, v, add, add_ld):
         """t_y = mask * (sum(T slabs) * w*rstd + xhat * v_w + v_b + add), into the consumer's operand."""
         n, k, oh, ow = u.a.shape
-        vg = v[self._offs[u.pg]: self._offs[u.pg] + k] if u.pg is not None else None
-        vb = v[self._offs[u.pb]: self._offs[u.pb] + k] if u.pb is not None else None
+        vg, vb = self._scale_shift_tangent(u, v)
         if u.train:
             # reduction (partial rows: by the convolution's epilogue, else by its own launch), then the elementwise
             # pass adds them up in its prologue
-            lib, st = _lib.load(), _lib.current_stream_ptr(self.dev)
-            px, p1, nparts = u.gw, u.gb, u.rb
+            parts = (u.gw, u.gb, u.rb)
             if self.hessian:
                 # the adjoint of a Hessian product reads these sums again (hf_bn_train_hessian_coeffs): rows of their
-                # own -- and  rstd * sum_rows g_z * t_a  (g_z: the step's first-order masked cotangent) as the second
-                # `rb` rows of gw, where the gather expects the scale's second-order share
-                px, p1 = u.hx, u.h1
-                _lib.check(lib.hf_chan_affine_bwd_ex(
-                    None, _ptr(u.gw[u.rb:]), None, None, _ptr(u.tbuf), u.sT, u.tbuf.shape[1], None, 1, 0, _ptr(u.g1),
-                    _ptr(self._zeros(k)), _ptr(u.rstd), None, None, n, k, oh * ow, 1, u.rb, _lib.HF_F32, st),
-                    "hf_chan_affine_bwd_ex")
+                # own -- and the scale's second-order sum
+                parts = (u.hx, u.h1, u.rb)
+                self._scale_second_order_sum(u)
             if u.tsum:
-                px, p1, nparts = u.tpx, u.tp1, u.tp1.shape[0]
-            u.tsums = (px, p1, nparts)  # (a Hessian product's adjoint reads them again)
+                parts = (u.tpx, u.tp1, u.tp1.shape[0])
+            u.tsums = parts  # (a Hessian product's adjoint reads them again)
             if not u.tsum:
-                _lib.check(lib.hf_chan_affine_bwd_ex(
-                    None, _ptr(px), _ptr(p1), None, _ptr(u.tbuf), u.sT, u.tbuf.shape[1], None, 1, 0, _ptr(u.a),
-                    _ptr(u.mean), _ptr(u.rstd), None, None, n, k, oh * ow, 1, u.rb, _lib.HF_F32, st),
-                    "hf_chan_affine_bwd_ex")
-            _lib.check(lib.hf_chan_affine_train(
-                _ptr(u.tout), _ptr(u.tbuf), _ptr(u.a), _ptr(u.mean), _ptr(u.rstd), _ptr(u.scale), _ptr(px),
-                _ptr(p1), nparts, _ptr(vg), _ptr(vb), float(n * oh * ow), _ptr(add), _ptr(u.y) if u.relu else None,
-                n, k, oh * ow, u.tout_ld, add_ld, u.sT, u.tbuf.shape[1], _lib.HF_F32, st), "hf_chan_affine_train")
+                self._chan_sums(u.tbuf, u.sT, u.tbuf.shape[1], n, k, oh * ow, u.rb, gw=parts[0], gb=parts[1], x=u.a,
+                                mean=u.mean, rstd=u.rstd)
+            self._launch("hf_chan_affine_train",
+                         *affine_train_args(self._train_tangent_problem(u, parts, vg, vb, add), add_ld))
             return
-        _lib.check(_lib.load().hf_chan_affine_ex(
-            _ptr(u.tout), _ptr(u.tbuf), _ptr(u.a), _ptr(u.mean), _ptr(u.rstd), _ptr(u.scale),
-            _ptr(vg), _ptr(vb), _ptr(add), _ptr(u.y) if u.relu else None, 0, n, k, oh * ow, 1, u.tout_ld, add_ld,
-            u.sT, u.tbuf.shape[1], _lib.HF_F32, _lib.current_stream_ptr(self.dev)), "hf_chan_affine_ex")
+        self._launch("hf_chan_affine_ex", *affine_args(affine_problem(u, vg, vb, add, add_ld)))
 
     def _train_pair_ok(self, u1, u2):
         return u1.train and u2.train and os.environ.get("HF_BN_TRAIN_PAIR", "1") != "0"
 
-    def _affine_train_problem(self, q, u, out, out_ld, a, a_splits, a_slab, px, p1, nparts, vq, vr, mask):
-        n, k, oh, ow = u.a.shape
-        q.out, q.a, q.x = out.data_ptr(), a.data_ptr(), u.a.data_ptr()
-        q.mean, q.rstd, q.w = u.mean.data_ptr(), u.rstd.data_ptr(), u.scale.data_ptr()
-        q.part_x, q.part_1, q.nparts = px.data_ptr(), p1.data_ptr(), nparts
-        q.vq = vq.data_ptr() if vq is not None else None
-        q.vr = vr.data_ptr() if vr is not None else None
-        q.count, q.add, q.mask_src = float(n * oh * ow), None, (mask.data_ptr() if mask is not None else None)
-        q.n, q.c, q.hw, q.out_ld, q.a_splits, q.a_slab = n, k, oh * ow, out_ld, a_splits, a_slab
+    @staticmethod
+    def _train_tangent_problem(u, parts, vg, vb, add=None):
+        return affine_train_problem(u, u.tout, u.tout_ld, u.tbuf, u.sT, u.tbuf.shape[1], parts, vg, vb,
+                                    u.y if u.relu else None, add)
 
     def _bn_tangent_pair_train(self, u1, u2, v):
         """Train mode, prologue form: the elementwise passes of two units without residual input in ONE launch (their
         partial sums came from the convolutions' epilogue)."""
-        arr = (_lib.AffineTrainProblem * 2)()
-        for q, u in zip(arr, (u1, u2)):
-            k = u.a.shape[1]
-            vg = v[self._offs[u.pg]: self._offs[u.pg] + k] if u.pg is not None else None
-            vb = v[self._offs[u.pb]: self._offs[u.pb] + k] if u.pb is not None else None
-            self._affine_train_problem(q, u, u.tout, u.tout_ld, u.tbuf, u.sT, u.tbuf.shape[1], u.tpx, u.tp1,
-                                       u.tp1.shape[0], vg, vb, u.y if u.relu else None)
-        _lib.check(_lib.load().hf_chan_affine_train_pair(_lib.ctypes.cast(arr, _lib.c_void_p), _lib.HF_F32,
-                                                         _lib.current_stream_ptr(self.dev)), "hf_chan_affine_train_pair")
+        self._launch_pair("hf_chan_affine_train_pair", *(
+            self._train_tangent_problem(u, (u.tpx, u.tp1, u.tp1.shape[0]), *self._scale_shift_tangent(u, v))
+            for u in (u1, u2)))
 
     def _bn_tangent_pair(self, u1, u2, v):
         """The BatchNorm tangents of two units without residual input in ONE launch."""
-        arr = (_lib.AffineProblem * 2)()
-        for q, u in zip(arr, (u1, u2)):
-            n, k, oh, ow = u.a.shape
-            q.out, q.a, q.x = u.tout.data_ptr(), u.tbuf.data_ptr(), u.a.data_ptr()
-            q.mean, q.rstd, q.w = u.bn.running_mean.data_ptr(), u.rstd.data_ptr(), u.bn.weight.data_ptr()
-            q.q = v.data_ptr() + 4 * self._offs[u.pg] if u.pg is not None else None  # (frozen scale / shift: no tangent)
-            q.r = v.data_ptr() + 4 * self._offs[u.pb] if u.pb is not None else None
-            q.add, q.mask_src, q.relu_self = None, (u.y.data_ptr() if u.relu else None), 0
-            q.n, q.c, q.hw, q.out_ld, q.add_ld = n, k, oh * ow, u.tout_ld, 0
-            q.a_splits, q.a_slab = u.sT, u.tbuf.shape[1]
-        _lib.check(_lib.load().hf_chan_affine_pair(_lib.ctypes.cast(arr, _lib.c_void_p), _lib.HF_F32,
-                                                   _lib.current_stream_ptr(self.dev)), "hf_chan_affine_pair")
+        self._launch_pair("hf_chan_affine_pair",
+                          *(affine_problem(u, *self._scale_shift_tangent(u, v)) for u in (u1, u2)))
 
     def _tangent_stem(self, v, carry_scatter=False):
         """Stem: conv(x, v_W) as a 1x1 convolution on the im2col'd input (the input has no tangent; v_W is a
@@ -118,9 +95,7 @@ class _TangentSweep:
             self._conv_slabs(0, s.tbuf, s.cols, vw, s.geo, s.sT)
         self._bn_tangent(s, v, None, 0)
         pn, ph, pw, poh, pow_, c0 = self._pool_geometry()
-        _lib.check(_lib.load().hf_maxpool_tangent_nhwc(
-            _ptr(self.pool_t), _ptr(s.tout), _ptr(self.pool_idx32), pn, ph, pw, poh, pow_, c0, 2 * c0,
-            _lib.HF_F32, _lib.current_stream_ptr(self.dev)), "hf_maxpool_tangent_nhwc")
+        self._launch("hf_maxpool_tangent_nhwc", self.pool_t, s.tout, self.pool_idx32, pn, ph, pw, poh, pow_, c0, 2 * c0)
 
     def _tangent_convs(self, units):
         """The tangent convolutions ``conv([t_x | x], [W | v_W])`` of one or two units in ONE launch.  In front of a
@@ -185,19 +160,21 @@ class _TangentSweep:
         t_last = tail.tout
         hw = t_last.shape[2] * t_last.shape[3]
         fw = self.fc.weight
-        nf = fw.numel()
-        v_fw = v[self._offs[self.pfw]: self._offs[self.pfw] + nf].view_as(fw)
-        v_fb = None if self.pfb is None else v[self._offs[self.pfb]: self._offs[self.pfb] + fw.shape[0]]
-        if self.hessian:
-            # forward-over-reverse through the linear head: besides H_L J v, the first-order cotangent g of the
-            # logits meets the tangents of the layer's two operands (g V -> features, g^T t_feat -> weight)
+        v_fw = self._param_slice(v, self.pfw, fw.numel()).view_as(fw)
+        v_fb = self._param_slice(v, self.pfb, fw.shape[0])
+
+        def loss_hessian_of_jv():
             t_feat = t_last.flatten(1) if hw == 1 else t_last.mean(dim=(2, 3))
             if self.pfb is not None:
                 Jv = torch.addmm(v_fb, t_feat, fw.detach().t())
             else:
                 Jv = t_feat @ fw.detach().t()
-            Jv = torch.addmm(Jv, self.feat, v_fw.t())
-            HJv = self._loss_hessian(Jv)
+            return t_feat, self._loss_hessian(torch.addmm(Jv, self.feat, v_fw.t()))
+
+        if self.hessian:
+            # forward-over-reverse through the linear head: besides H_L J v, the first-order cotangent g of the
+            # logits meets the tangents of the layer's two operands (g V -> features, g^T t_feat -> weight)
+            t_feat, HJv = loss_hessian_of_jv()
             g_fw = torch.addmm(self._gl1.t() @ t_feat, HJv.t(), self.feat)
             g_fb = HJv.sum(0) if self.pfb is not None else None
             g_feat = torch.addmm(self._gl1 @ v_fw, HJv, fw.detach())
@@ -205,21 +182,12 @@ class _TangentSweep:
         if self._head_fused(hw, v_fw):
             # ONE launch: logits' tangent, softmax-CE Hessian, the three gradients
             g_feat, g_fw, g_fb = self._head_bufs
-            _lib.check(_lib.load().hf_linear_ce_head(
-                _ptr(g_feat), _ptr(g_fw), _ptr(g_fb) if self.pfb is not None else None, _ptr(t_last),
-                _ptr(self.feat), _ptr(fw), _ptr(v_fw), _ptr(v_fb), _ptr(self._ce[0]), float(self._ce[1]),
-                g_feat.shape[0], g_feat.shape[1], fw.shape[0], _lib.HF_F32,
-                _lib.current_stream_ptr(self.dev)), "hf_linear_ce_head")
+            self._launch("hf_linear_ce_head", g_feat, g_fw, g_fb if self.pfb is not None else None, t_last, self.feat,
+                         fw, v_fw, v_fb, self._ce[0], float(self._ce[1]), g_feat.shape[0], g_feat.shape[1], fw.shape[0])
             if self.pfb is None:
                 g_fb = None
         else:
-            t_feat = t_last.flatten(1) if hw == 1 else t_last.mean(dim=(2, 3))
-            if self.pfb is not None:
-                Jv = torch.addmm(v_fb, t_feat, fw.detach().t())
-            else:
-                Jv = t_feat @ fw.detach().t()
-            Jv = torch.addmm(Jv, self.feat, v_fw.t())
-            HJv = self._loss_hessian(Jv)
+            _t_feat, HJv = loss_hessian_of_jv()
             g_fw = HJv.t() @ self.feat
             g_fb = HJv.sum(0) if self.pfb is not None else None
             g_feat = HJv @ fw.detach()

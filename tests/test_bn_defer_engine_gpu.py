@@ -11,87 +11,10 @@ import numpy as np
 import pack_refs as pr
 import pytest
 import torch
-from torch import nn
 
-from pytorchhessianfree_amd import modelprep
-from pytorchhessianfree_amd import testproblems as tp
-from pytorchhessianfree_amd.engine import FusedGGNEngine
-from pytorchhessianfree_amd.utils import ParameterArena
+from engine_nets import DEV, build
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-NETS = {"small": dict(batch=8, ch=8, blocks=[(8, 8, 1), (8, 16, 2)]),
-        "wide": dict(batch=16, ch=32, blocks=[(32, 32, 1), (32, 64, 2), (64, 64, 2)])}
-
-
-class SmallResNet(nn.Module):
-    def __init__(self, ch, blocks, classes=10):
-        super().__init__()
-        self.conv1 = nn.Conv2d(1, ch, 3, 1, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(ch)
-        self.relu = nn.ReLU(inplace=False)
-        self.maxpool = nn.MaxPool2d(3, 2, 1)  # 8x8 -> 4x4
-        self.layers = nn.Sequential(*[tp._BasicBlock(a, b, s) for a, b, s in blocks])
-        self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
-        self.fc = nn.Linear(blocks[-1][1], classes)
-
-    def forward(self, x):
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
-        x = self.avgpool(self.layers(x))
-        return self.fc(torch.flatten(x, -3))
-
-
-def _freeze(model, pattern):
-    if pattern == "stem":  # a dead stem: the sweep ends in front of it
-        for p in (*model.conv1.parameters(), *model.bn1.parameters()):
-            p.requires_grad_(False)
-    elif pattern == "scale_shift":  # one unit without sums at all, one with each of the two alone
-        bns = [model.bn1, model.layers[0].bn1, model.layers[0].bn2]
-        bns[0].weight.requires_grad_(False)
-        bns[0].bias.requires_grad_(False)
-        bns[1].weight.requires_grad_(False)
-        bns[2].bias.requires_grad_(False)
-    else:
-        assert pattern == "plain"
-
-
-def _arena_order(model, where):
-    """The trainable parameters with the head's 10-entry bias -- the one count that is no multiple of 4 -- moved in front
-    of the parameter named ``where``: bound into a ``ParameterArena`` in this order, every parameter behind it sits 8 bytes
-    off a 16-byte boundary."""
-    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad and n != "fc.bias"]
-    at = [n for n, _ in named].index(where)
-    return [p for _, p in named[:at]] + [model.fc.bias] + [p for _, p in named[at:]]
-
-
-def build(net, pattern="plain", train=False, hessian=False, arena_at=None):
-    spec = NETS[net]
-    torch.manual_seed(5)
-    model = SmallResNet(spec["ch"], spec["blocks"])
-    with torch.no_grad():
-        for m in model.modules():  # (statistics and scales away from their trivial initial values)
-            if isinstance(m, nn.BatchNorm2d):
-                m.running_mean.uniform_(-0.2, 0.2)
-                m.running_var.uniform_(0.7, 1.4)
-                m.weight.uniform_(0.6, 1.3)
-                m.bias.uniform_(-0.2, 0.2)
-                m.eps = 0.1
-    _freeze(model, pattern)
-    model.train(train)
-    x, t = torch.randn(spec["batch"], 1, 8, 8), torch.randint(0, 10, (spec["batch"],))
-    model = model.to(DEV)
-    modelprep.prepare_model(model, channels_last=True)
-    params = [p for p in model.parameters() if p.requires_grad]
-    if arena_at is not None:
-        params = _arena_order(model, arena_at)
-        model._arena = ParameterArena(params)  # (kept alive with the model: the parameters are views into it now)
-        at = next(i for i, p in enumerate(params) if p is model.fc.bias)
-        assert all(p.data_ptr() % 16 == (8 if i > at else 0) for i, p in enumerate(params))
-    out = model(x.to(DEV))
-    why = []
-    op = FusedGGNEngine.try_build(nn.functional.cross_entropy(out, t.to(DEV)), out, params, hessian=hessian, why=why)
-    assert isinstance(op, FusedGGNEngine), why
-    return op
 
 
 def products(op):
