@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 SOURCES = [os.path.join(HERE, f) for f in ("hf_pcg.hip", "hf_pack.hip", "hf_bn.hip", "hf_conv.hip", "hf_head.hip",
                                            "hf_dense.hip", "hf_rccl.hip")]
 HDR = os.path.join(ROOT, "include", "hf_pcg.h")
-HDRS_SHARED = [os.path.join(HERE, f) for f in ("hf_common.h", "hf_unpack.h")]
+HDRS_SHARED = [os.path.join(HERE, f) for f in ("hf_common.h", "hf_unpack.h", "hf_store.h")]
 OUT = os.path.join(HERE, "libhfpcg.so")
 
 FLAGS = [

@@ -47,7 +47,7 @@ __device__ __forceinline__ void chan_affine_body(
     if (add) acc += add[add_ld ? i + outer * (add_ld - (nhwc ? C : CHW)) : i];
     if (relu_self) acc = acc > (T)0 ? acc : (T)0;
     else if (mask_src) acc = mask_src[i] > (T)0 ? acc : (T)0;
-    out[out_ld ? i + outer * (out_ld - (nhwc ? C : CHW)) : i] = acc;
+    chain_store<HF_WT_ELEM>(&out[out_ld ? i + outer * (out_ld - (nhwc ? C : CHW)) : i], acc);
   }
 }
 
@@ -88,7 +88,7 @@ __device__ __forceinline__ void chan_affine_v4_body(
       else if (mask_src) acc = mv.e[k] > 0.f ? acc : 0.f;
       o.e[k] = acc;
     }
-    *reinterpret_cast<F4*>(out + (out_ld ? row * out_ld + c : i)) = o;
+    chain_store4<HF_WT_ELEM>(out + (out_ld ? row * out_ld + c : i), o);
   }
 }
 
@@ -190,8 +190,8 @@ __global__ __launch_bounds__(BLOCK) void k_chan_affine_bwd(
         T gg = g;
         if (gy2) gg = gg + h;
         if (mask_src) gg = m > (T)0 ? gg : (T)0;
-        if (gx) gx[idx] = gg * s;
-        if (gres) gres[idx] = gg;
+        if (gx) { const T o = gg * s; chain_store<HF_WT_ELEM>(&gx[idx], o); }
+        if (gres) chain_store<HF_WT_ELEM>(&gres[idx], gg);
         if (x) acc[0] += (double)gg * (double)(T)((xv - mu) * rs);
         acc[1] += (double)gg;
       }
@@ -231,8 +231,8 @@ __global__ __launch_bounds__(BLOCK) void k_chan_affine_bwd(
           T gg = g[t];
           if (gy2) gg = gg + h[t];  // the cotangents of the output's two consumers
           if (mask_src) gg = m[t] > (T)0 ? gg : (T)0;
-          if (gx) gx[idx[t]] = gg * s;
-          if (gres) gres[idx[t]] = gg;
+          if (gx) { const T o = gg * s; chain_store<HF_WT_ELEM>(&gx[idx[t]], o); }
+          if (gres) chain_store<HF_WT_ELEM>(&gres[idx[t]], gg);
           if (x) acc[0] += (double)gg * (double)(T)((xv[t] - mu) * rs);
           acc[1] += (double)gg;
         }
@@ -250,8 +250,8 @@ __global__ __launch_bounds__(BLOCK) void k_chan_affine_bwd(
     block_allreduce<2>(acc, lds);
   }
   if (live && lane == 0) {
-    if (gw) gw[c] = (T)acc[0];
-    if (gb) gb[c] = (T)acc[1];
+    if (gw) { const T sw = (T)acc[0]; chain_store<HF_WT_ELEM>(&gw[c], sw); }
+    if (gb) { const T sb = (T)acc[1]; chain_store<HF_WT_ELEM>(&gb[c], sb); }
   }
 }
 
@@ -351,12 +351,12 @@ __global__ __launch_bounds__(BS) void k_chan_affine_bwd_nhwc(
 #pragma unroll
           for (int k = 0; k < W; ++k) g[t].e[k] = m[t].e[k] > (T)0 ? g[t].e[k] : (T)0;
         }
-        if (gres) *reinterpret_cast<Col*>(gres + idx) = g[t];
+        if (gres) chain_store_col<HF_WT_ELEM>(gres + idx, g[t]);
         if (gx) {
           Col o;
 #pragma unroll
           for (int k = 0; k < W; ++k) o.e[k] = g[t].e[k] * sc[k];
-          *reinterpret_cast<Col*>(gx + idx) = o;
+          chain_store_col<HF_WT_ELEM>(gx + idx, o);
         }
 #pragma unroll
         for (int k = 0; k < W; ++k) {
@@ -370,8 +370,8 @@ __global__ __launch_bounds__(BS) void k_chan_affine_bwd_nhwc(
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < W; ++k) {
-      if (gw) gw[rb * C + c0 + k] = (T)acc[2 * k];
-      if (gb) gb[rb * C + c0 + k] = (T)acc[2 * k + 1];
+      if (gw) { const T sw = (T)acc[2 * k]; chain_store<HF_WT_ELEM>(&gw[rb * C + c0 + k], sw); }
+      if (gb) { const T sb = (T)acc[2 * k + 1]; chain_store<HF_WT_ELEM>(&gb[rb * C + c0 + k], sb); }
     }
   }
 }
@@ -496,13 +496,13 @@ __device__ __forceinline__ void bn_adjoint_rows_body(
           acc[2 * k + 1] += (double)a1;
         }
       }
-      if (gres) { *reinterpret_cast<F4*>(gres + idx0) = g0; if (two) *reinterpret_cast<F4*>(gres + idx1) = g1; }
-      if (gx) { *reinterpret_cast<F4*>(gx + idx0) = o0; if (two) *reinterpret_cast<F4*>(gx + idx1) = o1; }
+      if (gres) { chain_store4<HF_WT_ELEM>(gres + idx0, g0); if (two) chain_store4<HF_WT_ELEM>(gres + idx1, g1); }
+      if (gx) { chain_store4<HF_WT_ELEM>(gx + idx0, o0); if (two) chain_store4<HF_WT_ELEM>(gx + idx1, o1); }
     }
   }
   cross_row_sums(acc, red, RP, quads, tx, ty, live, [&](unsigned k, unsigned col, double sum) {
     float* dst = (k & 1) ? gb : gw;
-    if (dst) dst[bid * C + col * 4 + (k >> 1)] = (float)sum;
+    if (dst) { const float v = (float)sum; chain_store<HF_WT_ELEM>(&dst[bid * C + col * 4 + (k >> 1)], v); }
   });
 }
 
@@ -677,7 +677,7 @@ __device__ __forceinline__ void affine_train_body(const AffTrainArgs& p, unsigne
       if (MASK) acc = mv.e[k] > 0.f ? acc : 0.f;
       o.e[k] = acc;
     }
-    *reinterpret_cast<F4*>(out + (out_ld ? row * out_ld + c : i)) = o;
+    chain_store4<HF_WT_ELEM>(out + (out_ld ? row * out_ld + c : i), o);
   }
   // (a grid capped below one quad per thread: the rest by the plain walk)
   if (nblocks * BLOCK < quads_total)
@@ -850,8 +850,8 @@ __device__ __forceinline__ void bn_adjoint_v4_body(
       g.e[k] = a;
       o.e[k] = a * ((w ? w4.e[k] : 1.f) * (rstd ? rs4.e[k] : 1.f));
     }
-    if (g_out) *reinterpret_cast<F4*>(g_out + i) = g;
-    if (ga_out) *reinterpret_cast<F4*>(ga_out + i) = o;
+    if (g_out) chain_store4<HF_WT_ELEM>(g_out + i, g);
+    if (ga_out) chain_store4<HF_WT_ELEM>(ga_out + i, o);
   }
 }
 

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "hf_pcg.h"
+#include "hf_store.h"
 #include "hf_unpack.h"
 
 #define HF_HIP(expr)                         \
@@ -93,6 +94,30 @@ struct alignas(sizeof(T) * W) ColOf { T e[W]; };
 using F4 = ColOf<float, 4>;  // the 16-byte quad of floats
 
 __device__ __forceinline__ F4 ld4(const float* p) { return *reinterpret_cast<const F4*>(p); }
+
+using hf_shared::chain_store;
+using hf_shared::chain_store16;
+template <bool WT>
+__device__ __forceinline__ void chain_store4(float* p, const F4& v) { chain_store16<WT>(reinterpret_cast<F4*>(p), v); }
+// a W-wide column of any element type: one scalar, or whole 16-byte pieces
+template <bool WT, typename T, int W>
+__device__ __forceinline__ void chain_store_col(T* p, const ColOf<T, W>& v) {
+  if constexpr (!WT) {
+    *reinterpret_cast<ColOf<T, W>*>(p) = v;
+  } else if constexpr (W == 1) {
+    chain_store<true>(p, v.e[0]);
+  } else {
+    constexpr int PW = 16 / sizeof(T);
+    static_assert(W % PW == 0, "whole 16-byte pieces");
+#pragma unroll
+    for (int k = 0; k < W / PW; ++k) {
+      ColOf<T, PW> piece;
+#pragma unroll
+      for (int e = 0; e < PW; ++e) piece.e[e] = v.e[k * PW + e];
+      chain_store16<true>(reinterpret_cast<ColOf<T, PW>*>(p) + k, piece);
+    }
+  }
+}
 
 // s += v where `on`.  BRANCH picks the spelling: a select (the additions are straight-line code) or a branch around
 // them; the sums are the same, the register allocation of the kernel around them is not, so each site says which.

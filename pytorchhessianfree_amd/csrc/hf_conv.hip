@@ -29,13 +29,7 @@
 // The 32 k of a step are assigned as k = 16*(l>>5) + step (A and B alike), so that a lane's
 // 16 operands are 64 contiguous bytes of an LDS row.
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "hf_pcg.h"
-#include "hf_unpack.h"
+#include "hf_common.h"
 
 namespace {
 
@@ -400,8 +394,10 @@ __device__ __forceinline__ void finish_tile(const ConvArgs& a, const f32x16 (&ac
       const double sum = ((red[(kind * 4 + 0) * BN + c] + red[(kind * 4 + 1) * BN + c]) +
                           red[(kind * 4 + 2) * BN + c]) + red[(kind * 4 + 3) * BN + c];
       const int tile_m = (int)fdiv((unsigned)tile, a.fd_tiles_n);
-      if (col0 + c < col_lim)
-        (kind ? a.bn_part_x : a.bn_part_1)[(size_t)(tile_m * a.splits + split) * a.nout + col0 + c] = (float)sum;
+      if (col0 + c < col_lim) {
+        const float part = (float)sum;
+        chain_store<HF_WT_CONV>(&(kind ? a.bn_part_x : a.bn_part_1)[(size_t)(tile_m * a.splits + split) * a.nout + col0 + c], part);
+      }
     }
   }
   if (a.splits == 1 || a.slabs) {
@@ -422,7 +418,8 @@ __device__ __forceinline__ void finish_tile(const ConvArgs& a, const f32x16 (&ac
 #pragma unroll
         for (int in = 0; in < C::TN; ++in) {
           const int col = (wn * C::TN + in) * 32 + i;
-          if (rok && col0 + col < col_lim) dst[(size_t)orow * ldc + col0 + col] = acc[im][in][reg];
+          // (the accumulator layout gives a lane 4 bytes per row: its natural store width)
+          if (rok && col0 + col < col_lim) chain_store<HF_WT_CONV>(&dst[(size_t)orow * ldc + col0 + col], acc[im][in][reg]);
         }
       }
     return;
@@ -1053,15 +1050,7 @@ __global__ __launch_bounds__(CT) void k_conv_group(const ConvArgs a0, const Conv
   else group_run<ANYBIG, CLS, BNSUM>(a3, m.tn[3], lds, b - m.start[3]);
 }
 
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 }  // namespace
-
-#define HF_HIP(expr)                         \
-  do {                                       \
-    hipError_t e_ = (expr);                  \
-    if (e_ != hipSuccess) return (int)e_;    \
-  } while (0)
 
 namespace {
 

@@ -24,7 +24,8 @@ __global__ __launch_bounds__(HB) void k_maxpool_tangent(float* __restrict__ out,
   const unsigned i = blockIdx.x * HB + threadIdx.x;
   if (i >= total) return;
   const unsigned c = i % C, pix = i / C, n = pix / opix;
-  out[(size_t)pix * out_ld + c] = t[((size_t)n * ipix + (unsigned)idx[i]) * C + c];
+  const float v = t[((size_t)n * ipix + (unsigned)idx[i]) * C + c];
+  chain_store<HF_WT_ELEM>(&out[(size_t)pix * out_ld + c], v);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(HB) void k_maxpool_adjoint(float* __restrict__ g, c
       if (B) v = v + slab_sum<8>(w, B, o, b_splits, b_slab);
       acc += v;
     }
-  g[i] = acc;
+  chain_store<HF_WT_ELEM>(&g[i], acc);
 }
 
 // max-pool, forward with positions (ATen's rule: first maximum in scan order, NaN wins)
@@ -211,7 +212,7 @@ __global__ __launch_bounds__(HEAD_T) void k_linear_ce_head(
 #pragma unroll
     for (int u = 0; u < CH; ++u) {
       const int j = lane + 64 * u;
-      if (j < F4) reinterpret_cast<float4*>(g_feat + (size_t)b * F)[j] = acc[u];
+      if (j < F4) chain_store16<HF_WT_ELEM>(&reinterpret_cast<float4*>(g_feat + (size_t)b * F)[j], acc[u]);
     }
   }
   __syncthreads();
@@ -226,13 +227,13 @@ __global__ __launch_bounds__(HEAD_T) void k_linear_ce_head(
       const float4 f = s_feat[r * F4 + j];
       s.x = fmaf(hb, f.x, s.x); s.y = fmaf(hb, f.y, s.y); s.z = fmaf(hb, f.z, s.z); s.w = fmaf(hb, f.w, s.w);
     }
-    reinterpret_cast<float4*>(gw)[e] = s;
+    chain_store16<HF_WT_ELEM>(&reinterpret_cast<float4*>(gw)[e], s);
   }
   if (g_b && threadIdx.x < K) {
     float s = 0.f;
 #pragma unroll
     for (int r = 0; r < HEAD_R; ++r) s += s_h[r * K + threadIdx.x];
-    g_b[(size_t)blockIdx.x * K + threadIdx.x] = s;
+    chain_store<HF_WT_ELEM>(&g_b[(size_t)blockIdx.x * K + threadIdx.x], s);
   }
 }
 
@@ -256,7 +257,7 @@ __global__ __launch_bounds__(HB) void k_pool_ce_head(float* __restrict__ g, floa
     if (k < K) {
       for (int q = 0; q < HW; ++q) s += tn[(size_t)q * K + k];
       s = s / (float)HW;
-      if (jv_out) jv_out[(size_t)n * K + k] = s;
+      if (jv_out) chain_store<HF_WT_ELEM>(&jv_out[(size_t)n * K + k], s);
       part += (double)p[(size_t)n * K + k] * (double)s;
     }
     jv_mine[u] = s;
@@ -275,7 +276,10 @@ __global__ __launch_bounds__(HB) void k_pool_ce_head(float* __restrict__ g, floa
   }
   __syncthreads();
   float* gn = g + (size_t)n * HW * K;
-  for (int e = threadIdx.x; e < HW * K; e += HB) gn[e] = s_h[e % K];
+  for (int e = threadIdx.x; e < HW * K; e += HB) {
+    const float h = s_h[e % K];
+    chain_store<HF_WT_ELEM>(&gn[e], h);
+  }
 }
 
 inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }

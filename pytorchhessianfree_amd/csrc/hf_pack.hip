@@ -155,16 +155,19 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
         } else if (I == 0 && OP == 0 && (((uintptr_t)(out + jd)) & 15) == 0) {
 #pragma unroll
           for (int c = 0; c < W; ++c) acc.e[c] = pack_op<T, OP>((T)0, acc.e[c], scale);
-          *reinterpret_cast<V*>(out + jd) = acc.v;
+          chain_store16<HF_WT_VEC>(reinterpret_cast<V*>(out + jd), acc.v);
         } else if (cnl == 1 && (((uintptr_t)(out + jd)) & 15) == 0) {
           VU<T> d;
           if (OP == 1) d.v = *reinterpret_cast<const V*>(out + jd);
 #pragma unroll
           for (int c = 0; c < W; ++c) acc.e[c] = pack_op<T, OP>(OP == 1 ? d.e[c] : (T)0, acc.e[c], scale);
-          *reinterpret_cast<V*>(out + jd) = acc.v;
+          chain_store16<HF_WT_VEC>(reinterpret_cast<V*>(out + jd), acc.v);
         } else {
 #pragma unroll
-          for (int c = 0; c < W; ++c) out[jd + c * step] = pack_op<T, OP>(out[jd + c * step], acc.e[c], scale);
+          for (int c = 0; c < W; ++c) {
+            const T pv = pack_op<T, OP>(out[jd + c * step], acc.e[c], scale);
+            chain_store<HF_WT_VEC>(&out[jd + c * step], pv);
+          }
         }
       }
       if (staged) {
@@ -184,7 +187,7 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
           if (OP == 1) d.v = *reinterpret_cast<const V*>(out + j0c + t);
 #pragma unroll
           for (int c = 0; c < W; ++c) v.e[c] = pack_op<T, OP>(OP == 1 ? d.e[c] : (T)0, v.e[c], scale);
-          *reinterpret_cast<V*>(out + j0c + t) = v.v;
+          chain_store16<HF_WT_VEC>(reinterpret_cast<V*>(out + j0c + t), v.v);
         }
       }
       return;
@@ -244,7 +247,8 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
             j = (o * I + i) * cnl + tap_rank(live, hw);
           }
         }
-        out[j] = pack_op<T, OP>(out[j], acc[k], scale);
+        const T pv = pack_op<T, OP>(out[j], acc[k], scale);
+        chain_store<HF_WT_VEC>(&out[j], pv);
       }
     }
     return;
@@ -273,7 +277,7 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
           if (OP == 1) d.v = *reinterpret_cast<const V*>(o_);
 #pragma unroll
           for (int c = 0; c < W; ++c) v.e[c] = pack_op<T, OP>(OP == 1 ? d.e[c] : (T)0, v.e[c], scale);
-          *reinterpret_cast<V*>(o_) = v.v;
+          chain_store16<HF_WT_VEC>(reinterpret_cast<V*>(o_), v.v);
         }
         return;
       }
@@ -283,7 +287,8 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
         const unsigned hw = rem / I, i = rem - hw * I;
         if (!((live >> hw) & 1u)) continue;
         T* o_ = out + ((size_t)o * I + i) * nl + tap_rank(live, hw);
-        *o_ = pack_op<T, OP>(OP == 1 ? *o_ : (T)0, src[e], scale);
+        const T pv = pack_op<T, OP>(OP == 1 ? *o_ : (T)0, src[e], scale);
+        chain_store<HF_WT_VEC>(o_, pv);
       }
       return;
     }
@@ -296,7 +301,9 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
       VU<T> z;
 #pragma unroll
       for (int c = 0; c < W; ++c) z.e[c] = (T)0;
-      for (unsigned j = (unsigned)j0 + threadIdx.x * W; j < j1u; j += BLOCK * W) *reinterpret_cast<V*>(out + j) = z.v;
+      for (unsigned j = (unsigned)j0 + threadIdx.x * W; j < j1u; j += BLOCK * W) chain_store16<HF_WT_VEC>(reinterpret_cast<V*>(out + j), z.v);
+      // (the compiler does not count the write-through form's stores: their wait is spelled out)
+      if constexpr (HF_WT_VEC) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();  // (s_waitcnt vmcnt(0) + barrier: the zeros are acknowledged before any value store is issued)
       const unsigned o0 = (unsigned)j0 / slab, no = (j1u - (unsigned)j0) / slab;
       const unsigned nl = (unsigned)__popc(live);
@@ -312,7 +319,8 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
           seen += bit;
         }
         const unsigned ob = (o0 + ol) * slab;
-        out[ob + i * HW + hw] = pack_op<T, OP>((T)0, src[ob + hw * I + i], scale);
+        const T pv = pack_op<T, OP>((T)0, src[ob + hw * I + i], scale);
+        chain_store<HF_WT_VEC>(&out[ob + i * HW + hw], pv);
       }
       return;
     }
@@ -329,11 +337,14 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
       if (OP == 0 && al && j + W <= j1u) {
 #pragma unroll
         for (int c = 0; c < W; ++c) v.e[c] = pack_op<T, OP>((T)0, v.e[c], scale);
-        *reinterpret_cast<V*>(out + j) = v.v;
+        chain_store16<HF_WT_VEC>(reinterpret_cast<V*>(out + j), v.v);
       } else {
 #pragma unroll
         for (int c = 0; c < W; ++c)
-          if (j + c < j1u) out[j + c] = pack_op<T, OP>(out[j + c], v.e[c], scale);
+          if (j + c < j1u) {
+            const T pv = pack_op<T, OP>(out[j + c], v.e[c], scale);
+            chain_store<HF_WT_VEC>(&out[j + c], pv);
+          }
       }
     }
     return;
@@ -353,7 +364,8 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
       for (unsigned t = threadIdx.x; t < len; t += BLOCK) {
         const unsigned ol = t / slab, rem = t - ol * slab;
         const unsigned i = rem / HW, hw = rem - i * HW;
-        out[j0 + t] = pack_op<T, OP>(out[j0 + t], tile[(ol * HW + hw) * (I + 1) + i], scale);
+        const T pv = pack_op<T, OP>(out[j0 + t], tile[(ol * HW + hw) * (I + 1) + i], scale);
+        chain_store<HF_WT_VEC>(&out[j0 + t], pv);
       }
       return;
     }
@@ -361,7 +373,8 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
       const long long o = j / slab;
       const unsigned rem = (unsigned)(j - o * slab);
       const unsigned i = rem / HW, hw = rem - i * HW;
-      out[j] = pack_op<T, OP>(out[j], src[o * slab + (long long)hw * I + i], scale);
+      const T pv = pack_op<T, OP>(out[j], src[o * slab + (long long)hw * I + i], scale);
+      chain_store<HF_WT_VEC>(&out[j], pv);
     }
     return;
   }
@@ -374,13 +387,17 @@ __global__ __launch_bounds__(BLOCK) void k_pack(T* __restrict__ dst, const PackA
       if (OP == 1) d.v = reinterpret_cast<const V*>(out)[i];
 #pragma unroll
       for (int c = 0; c < W; ++c) d.e[c] = pack_op<T, OP>(d.e[c], s.e[c], scale);
-      reinterpret_cast<V*>(out)[i] = d.v;
+      chain_store16<HF_WT_VEC>(&reinterpret_cast<V*>(out)[i], d.v);
     }
-    for (long long j = v1 * W + threadIdx.x; j < j1; j += BLOCK)
-      out[j] = pack_op<T, OP>(out[j], src[j], scale);
+    for (long long j = v1 * W + threadIdx.x; j < j1; j += BLOCK) {
+      const T pv = pack_op<T, OP>(out[j], src[j], scale);
+      chain_store<HF_WT_VEC>(&out[j], pv);
+    }
   } else {
-    for (long long j = j0 + threadIdx.x; j < j1; j += BLOCK)
-      out[j] = pack_op<T, OP>(out[j], src[j], scale);
+    for (long long j = j0 + threadIdx.x; j < j1; j += BLOCK) {
+      const T pv = pack_op<T, OP>(out[j], src[j], scale);
+      chain_store<HF_WT_VEC>(&out[j], pv);
+    }
   }
 }
 

@@ -233,7 +233,7 @@ __global__ __launch_bounds__(BLOCK) void k_init_finalize(DevState* __restrict__ 
       __builtin_memcpy(&t_, &(src), sizeof(NV));                                            \
       __builtin_nontemporal_store(t_, reinterpret_cast<NV*>(ptr));                          \
     } else {                                                                                \
-      *(ptr) = (src);                                                                       \
+      chain_store16<HF_WT_VEC>(ptr, src); /* read next by the product / K3: hf_common.h */  \
     }                                                                                       \
   }
 template <typename T, int UNROLL, bool NT>
@@ -361,7 +361,7 @@ __global__ __launch_bounds__(BLOCK) void k_update_xr(
           acc[2] += (double)(T)(rn - vb[u].e[c]) * (double)xn;  // dot(r-b, x)  cg.py:97
         }
         HF_ST(NT, reinterpret_cast<V*>(x) + i, vx[u].v)
-        reinterpret_cast<V*>(r)[i] = vr[u].v;
+        HF_ST(false, &reinterpret_cast<V*>(r)[i], vr[u].v)
         if (snap) reinterpret_cast<V*>(snap)[i] = vx[u].v;
       }
     }

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "hf_pcg.h"
+#include "hf_store.h"  // unpack_block writes its outputs with chain stores (family VEC)
 
 namespace hf_shared {
 
@@ -66,10 +67,14 @@ __device__ __forceinline__ void unpack_block(const T* __restrict__ src_base, con
     if (al && slab % W == 0) {
       for (long long j = j0 + (long long)threadIdx.x * W; j < j1; j += (long long)BLOCK * W) {
         const long long o = j / slab;
-        *reinterpret_cast<V*>(dst + j + (o + half) * slab) = *reinterpret_cast<const V*>(src + j);
+        const V q = *reinterpret_cast<const V*>(src + j);
+        hf_shared::chain_store16<HF_WT_VEC>(reinterpret_cast<V*>(dst + j + (o + half) * slab), q);
       }
     } else {
-      for (long long j = j0 + threadIdx.x; j < j1; j += BLOCK) dst[j + (j / slab + half) * slab] = src[j];
+      for (long long j = j0 + threadIdx.x; j < j1; j += BLOCK) {
+        const T q = src[j];
+        hf_shared::chain_store<HF_WT_VEC>(&dst[j + (j / slab + half) * slab], q);
+      }
     }
     return;
   }
@@ -95,7 +100,7 @@ __device__ __forceinline__ void unpack_block(const T* __restrict__ src_base, con
 #pragma unroll
           for (int c = 0; c < W; ++c) v.e[c] = s[c * nl];
         }
-        *reinterpret_cast<V*>(dst + (size_t)row * 2 * I + i) = v.v;
+        hf_shared::chain_store16<HF_WT_VEC>(reinterpret_cast<V*>(dst + (size_t)row * 2 * I + i), v.v);
       }
     } else {
       for (long long d = j0 + threadIdx.x; d < j1; d += BLOCK) {
@@ -104,7 +109,8 @@ __device__ __forceinline__ void unpack_block(const T* __restrict__ src_base, con
         const long long o = row / HW;
         const unsigned hw = (unsigned)(row - o * HW);
         if (!((live >> hw) & 1u)) continue;
-        dst[row * 2 * I + i] = src[(o * I + i) * nl + __popc(live & ((1u << hw) - 1u))];
+        const T q = src[(o * I + i) * nl + __popc(live & ((1u << hw) - 1u))];
+        hf_shared::chain_store<HF_WT_VEC>(&dst[row * 2 * I + i], q);
       }
     }
     return;
@@ -121,7 +127,7 @@ __device__ __forceinline__ void unpack_block(const T* __restrict__ src_base, con
       VU<T> v;
 #pragma unroll
       for (int c = 0; c < W; ++c) v.e[c] = s[c * HW];
-      *reinterpret_cast<V*>(dst + (size_t)row * 2 * I + i) = v.v;
+      hf_shared::chain_store16<HF_WT_VEC>(reinterpret_cast<V*>(dst + (size_t)row * 2 * I + i), v.v);
     }
   } else {
     for (long long d = j0 + threadIdx.x; d < j1; d += BLOCK) {
@@ -130,7 +136,8 @@ __device__ __forceinline__ void unpack_block(const T* __restrict__ src_base, con
       const long long o = row / HW;
       const unsigned hw = (unsigned)(row - o * HW);
       if (!((live >> hw) & 1u)) continue;
-      dst[row * 2 * I + i] = src[o * slab + (long long)i * HW + hw];
+      const T q = src[o * slab + (long long)i * HW + hw];
+      hf_shared::chain_store<HF_WT_VEC>(&dst[row * 2 * I + i], q);
     }
   }
 }
