@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 21
+#define HF_ABI_VERSION 22
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -398,6 +398,21 @@ int hf_bn_sums_multi(const void* table_dev, const hf_bn_sums_problem* table, int
                      int dtype, void* stream);
 
 /*
+ * Sum over the samples of the SQUARED per-sample BatchNorm scale / shift (or convolution bias) gradient (ABI 22): the
+ * per-channel entries of the diagonal empirical Fisher in one launch.  NHWC fp32, g (and x) [n*hw, c]:
+ *   gw2[ch] = sum_i ( pre * sum_{hw} g_i[hw][ch] * xhat_i[hw][ch] )^2,   xhat = (float)((x - mean[ch]) * rstd[ch])
+ *   gb2[ch] = sum_i ( pre * sum_{hw} g_i[hw][ch] )^2
+ * x, mean, rstd: all three or none (a convolution bias has no xhat; gw2 needs them); gw2 / gb2 nullable, not both.
+ * row_blocks splits the SAMPLES: share b = samples [b*ceil(n/row_blocks), ...) writes partial row b of gw2 / gb2, rows
+ * c elements apart, for hf_pack_ex to add up (the convention of gw / gb above); an empty share is HF_ERR_ARG.
+ * Rounding: a sample's sums over hw are taken in fp64 (sixteen interleaved shares of the rows, added in a fixed order;
+ * xhat rounded to fp32 before the product) and rounded once to fp32; t = pre * sum (one rounding), acc += t * t (two
+ * roundings) in fp32, the samples in ascending order.  Two launches give the same bits.
+ */
+int hf_chan_sqsum(void* gw2, void* gb2, const void* g, const void* x, const void* mean, const void* rstd, int64_t n,
+                  int64_t c, int64_t hw, float pre, int row_blocks, int dtype, void* stream);
+
+/*
  * Forward pass of conv -> (eval-BatchNorm | bias) (+ residual) (+ ReLU) from the convolution's split-K
  * slabs, NHWC fp32 [rows = n*hw, c] -- what the reference evaluates by `forward()` for the loss
  * and for every trial point of LM damping / CG-backtracking / line search (optimizer.py:216-229,
@@ -663,6 +678,36 @@ int hf_conv2d_nhwc_group_slabs_bnsum(const hf_conv_problem* problems, int n_prob
  * conv_D(g', W), conv_W(x, g') and the pair that carries the network's own curvature, conv_D(g, V),
  * conv_W(t_x, g) with t_x read in place from the [t_x | x] operand (optimizer.py:450-455). */
 int hf_conv2d_nhwc_dw_slabs(const hf_conv_problem* d, const hf_conv_problem* w, int dtype, void* stream);
+
+/*
+ * Sum over the samples of the SQUARED per-sample weight gradient of a convolution (ABI 22): BackPACK's SumGradSquared,
+ * the weight entries of the diagonal empirical Fisher (preconditioners.py:11-60), in ONE launch whatever the batch:
+ *   out[k][tap][c] = sum_{i<n} ( pre * sum_{m in sample i} dY[m][k] * X[pix(m, tap)][c] )^2
+ * The squared-sum sibling of hf_conv2d_nhwc_slabs, direction 2: act = X [n,h,w,c] (pixel stride act_ld, 0 = c),
+ * mat = dY [n*oh*ow][k], out [k][r][q][out_c] (out_c: 0 = c; X may carry zero-padding channels), dead taps not written
+ * (zero-initialise the slabs once), 64x64 tiles only, channel counts / act_ld that are no multiples of 4 by the
+ * element-wise gathers.  No per-sample gradient is formed in memory.
+ * The SPLITS RUN OVER THE SAMPLES, not over the reduction: split s takes samples [s*ceil(n/splits), ...) and writes its
+ * partial sum to out + s*slab_stride for hf_pack_ex (mode 0) to add in split order -- no atomics, no tickets, one fixed
+ * order: two launches give the same bits.  hf_conv2d_nhwc_sqsum_plan (pure host arithmetic) returns the planned count:
+ * towards a workgroup target (target_blocks; 0 = the default, 2048 for the per-sample form and the conv planner's own
+ * K-split plan for oh*ow == 1), at most n, no split without a sample.
+ * The launch takes the planned count or any other that leaves no split empty (1 <= splits <= n and
+ * (splits - 1) * ceil(n/splits) < n); anything else, a slab_stride below k*r*s*out_c with splits > 1, or a `pre` that
+ * is not finite is HF_ERR_ARG before any launch; the other refusals are hf_conv2d_nhwc_slabs' for the same geometry.
+ * Rounding (fp32 MFMA accumulation, rows of a sample in ascending order):
+ *   oh*ow > 1: per sample g = the sample's gradient entry; t = g * pre (one rounding); sum += t * t (two roundings),
+ *              the samples of a split in ascending order;
+ *   oh*ow == 1 (the per-sample gradient is the outer product dY_i[k] * X_i[c]): both operands squared after the load
+ *              (one rounding each), reduced over the split's samples like a weight gradient, times pre*pre (rounded
+ *              once) at the end.
+ */
+int hf_conv2d_nhwc_sqsum_plan(int64_t n, int64_t h, int64_t w, int64_t c, int64_t k, int64_t r, int64_t s,
+                              int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int target_blocks);
+int hf_conv2d_nhwc_sqsum_slabs(void* out, const void* act, const void* mat, int64_t n, int64_t h, int64_t w, int64_t c,
+                               int64_t k, int64_t r, int64_t s, int64_t stride_h, int64_t stride_w, int64_t pad_h,
+                               int64_t pad_w, int64_t act_ld, int64_t out_c, float pre, int splits,
+                               int64_t slab_stride, int dtype, void* stream);
 
 /* Data gradient AND weight gradient of one layer (directions 1 and 2 above) in ONE launch:
  * both read dY [n,oh,ow,k], neither depends on the other.  dx [n,h,w,c]; dw [k][r][q][c]

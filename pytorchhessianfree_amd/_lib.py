@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HF_PCG_LIB") or os.path.join(_HERE, "csrc", "libhfpcg.so")
 
 HF_F32, HF_F64 = 0, 1
-ABI_VERSION = 21
+ABI_VERSION = 22
 HF_ERR_ARG = -1  # hf_status of include/hf_pcg.h: null / negative / inconsistent argument
 HF_M_NONE, HF_M_DIAG, HF_M_EXTERNAL = 0, 1, 2
 REASONS = {
@@ -134,6 +134,10 @@ SIGNATURES = {
     "hf_conv2d_nhwc_plan": (c_int, [c_int] + [c_int64] * 11 + [c_int]),
     "hf_conv2d_nhwc_slabs": (c_int, [c_int, c_void_p, c_void_p, c_void_p] + [c_int64] * 14
                              + [c_int, c_int64, c_int, c_void_p]),
+    "hf_conv2d_nhwc_sqsum_plan": (c_int, [c_int64] * 11 + [c_int]),
+    "hf_conv2d_nhwc_sqsum_slabs": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int64] * 13
+                                   + [ctypes.c_float, c_int, c_int64, c_int, c_void_p]),
+    "hf_chan_sqsum": (c_int, [c_void_p] * 6 + [c_int64] * 3 + [ctypes.c_float, c_int, c_int, c_void_p]),
     "hf_conv2d_nhwc_slabs_unpack": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int64] * 13 + [c_int, c_int64, c_void_p,
                                             ctypes.POINTER(c_void_p)] + [ctypes.POINTER(c_int64)] * 6
                                     + [c_int, c_int, c_void_p]),
@@ -681,3 +685,32 @@ def conv2d_nhwc_slabs(direction, out, act, mat, n, h, w, c, k, r, s, stride, pad
             out.shape[1], HF_F32, current_stream_ptr(out.device)),
         "hf_conv2d_nhwc_slabs")
     return out
+
+
+def conv_sqsum_plan(n, h, w, c, k, r, s, stride, padding, target_blocks=0):
+    """Number of sample splits a squared-sum launch of this geometry is planned with (``hf_conv2d_nhwc_sqsum_plan``)."""
+    sp = load().hf_conv2d_nhwc_sqsum_plan(n, h, w, c, k, r, s, stride[0], stride[1], padding[0], padding[1],
+                                          int(target_blocks))
+    if sp < 1:
+        check(sp, "hf_conv2d_nhwc_sqsum_plan")
+    return sp
+
+
+def conv2d_nhwc_sqsum_slabs(out, act, mat, n, h, w, c, k, r, s, stride, padding, splits, pre=1.0, act_ld=0, out_c=0):
+    """Sum over the samples of the squared per-sample weight gradient: ``out`` is [splits, numel] -- slab s receives the
+    partial sum of split s's samples (``hf_conv2d_nhwc_sqsum_slabs``)."""
+    check(
+        load().hf_conv2d_nhwc_sqsum_slabs(
+            c_void_p(out.data_ptr()), c_void_p(act.data_ptr()), c_void_p(mat.data_ptr()), n, h, w, c, k, r, s,
+            stride[0], stride[1], padding[0], padding[1], act_ld, out_c, float(pre), int(splits), out.shape[1], HF_F32,
+            current_stream_ptr(out.device)),
+        "hf_conv2d_nhwc_sqsum_slabs")
+    return out
+
+
+def chan_sqsum(g, n, c, hw, row_blocks, pre=1.0, gw2=None, gb2=None, x=None, mean=None, rstd=None):
+    """Sum over the samples of the squared per-sample scale / shift (bias) gradient, ``row_blocks`` partial rows each
+    (``hf_chan_sqsum``); ``None`` operands go as NULL."""
+    ptr = lambda t: None if t is None else c_void_p(t.data_ptr())  # noqa: E731
+    check(load().hf_chan_sqsum(ptr(gw2), ptr(gb2), ptr(g), ptr(x), ptr(mean), ptr(rstd), n, c, hw, float(pre),
+                               int(row_blocks), HF_F32, current_stream_ptr(g.device)), "hf_chan_sqsum")

@@ -161,6 +161,10 @@ SWITCHES = {
     "HF_BN_SUMS_DEFER": ("1", "0: an eval-mode unit's BatchNorm adjoint as the fused launch (elementwise part and per-channel "
                          "sums on the adjoint chain) instead of the elementwise launch + one sums launch before the gather",
                          "tests/test_bn_defer_engine_gpu.py::test_deferred_sums_equal_the_fused_launches_bit_for_bit"),
+    "HF_DIAG_EF_BATCHED": ("0", "1: engine.diag_ef of the conv-unit engines squares and sums the per-sample gradients "
+                           "inside ONE launch per layer (hf_conv2d_nhwc_sqsum_slabs, hf_chan_sqsum) and gathers once, "
+                           "instead of per-sample weight-gradient launches and one squaring gather per sample",
+                           "tests/test_diag_ef_batched_engine_gpu.py::test_without_the_switch_no_new_entry_point_is_called"),
     "HF_CHUNKED_ALLREDUCE": ("auto", "0 / 1: force the single-graph resp. the two-phase data-parallel product",
                              "tests/test_distributed_gpu.py::test_step_two_ranks_engine_session_equals_cpu_whole_batch"),
     "HF_DIRECT_RCCL": ("1", "0: every collective through torch.distributed (no communicator of the package's own)",

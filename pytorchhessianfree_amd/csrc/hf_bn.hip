@@ -1112,7 +1112,89 @@ __global__ __launch_bounds__(BLOCK) void k_bn_train_hessian_apply(
   }
 }
 
+// hf_chan_sqsum: sum over the samples of the SQUARED per-sample scale / shift (bias) gradient, NHWC [n*hw, c].
+// A workgroup takes 64 channels (one wave reads 64 consecutive channels of a row) and the samples of row share
+// blockIdx.y; the four waves split a sample's hw rows (row j to wave j % 4) and each wave keeps four fp64 sums (its
+// rows in turn: four independent loads in flight), added as (s0 + s1) + (s2 + s3).  Per sample: the four waves' shares
+// added through LDS in wave order, rounded once to fp32; then t = pre * sum, acc += t * t in fp32, the samples in
+// ascending order.  One fixed order: two launches give the same bits.
+constexpr int SQ_CH = 64, SQ_PARTS = BLOCK / SQ_CH;
+__global__ __launch_bounds__(BLOCK) void k_chan_sqsum(float* __restrict__ gw2, float* __restrict__ gb2,
+                                                      const float* __restrict__ g, const float* __restrict__ x,
+                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                      unsigned n, unsigned c, unsigned hw, unsigned per, float pre) {
+  __shared__ double red[2][SQ_PARTS][SQ_CH];
+  const unsigned cl = threadIdx.x % SQ_CH, part = threadIdx.x / SQ_CH, ch = blockIdx.x * SQ_CH + cl;
+  const bool cok = ch < c;
+  const unsigned i0 = blockIdx.y * per, i1 = i0 + per < n ? i0 + per : n;
+  const float mu = (x && cok) ? mean[ch] : 0.f, rs = (x && cok) ? rstd[ch] : 0.f;
+  float qw = 0.f, qb = 0.f;
+  for (unsigned i = i0; i < i1; ++i) {
+    double s1 = 0.0, sx = 0.0;
+    if (cok) {
+      double a1[4] = {0.0, 0.0, 0.0, 0.0}, ax[4] = {0.0, 0.0, 0.0, 0.0};
+      const size_t e0 = (size_t)i * hw * c + ch;
+      unsigned j = part;
+      for (; j + 3 * SQ_PARTS < hw; j += 4 * SQ_PARTS) {  // (every load first)
+        float gv[4], xv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const size_t e = e0 + (size_t)(j + u * SQ_PARTS) * c;
+          gv[u] = g[e];
+          xv[u] = x ? x[e] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          a1[u] += (double)gv[u];
+          if (x) ax[u] += (double)gv[u] * (double)(float)((xv[u] - mu) * rs);
+        }
+      }
+      for (; j < hw; j += SQ_PARTS) {
+        const size_t e = e0 + (size_t)j * c;
+        const float gv = g[e];
+        a1[0] += (double)gv;
+        if (x) ax[0] += (double)gv * (double)(float)((x[e] - mu) * rs);
+      }
+      s1 = (a1[0] + a1[1]) + (a1[2] + a1[3]);
+      sx = (ax[0] + ax[1]) + (ax[2] + ax[3]);
+    }
+    red[0][part][cl] = s1;
+    red[1][part][cl] = sx;
+    __syncthreads();
+    if (part == 0) {
+      const double t1 = ((red[0][0][cl] + red[0][1][cl]) + red[0][2][cl]) + red[0][3][cl];
+      const double tx = ((red[1][0][cl] + red[1][1][cl]) + red[1][2][cl]) + red[1][3][cl];
+      const float b = pre * (float)t1, wv = pre * (float)tx;
+      qb += b * b;
+      qw += wv * wv;
+    }
+    __syncthreads();
+  }
+  if (part == 0 && cok) {
+    if (gw2) gw2[(size_t)blockIdx.y * c + ch] = qw;
+    if (gb2) gb2[(size_t)blockIdx.y * c + ch] = qb;
+  }
+}
+static_assert(SQ_PARTS == 4, "k_chan_sqsum adds four waves' shares");
+
 }  // namespace
+
+int hf_chan_sqsum(void* gw2, void* gb2, const void* g, const void* x, const void* mean, const void* rstd, int64_t n,
+                  int64_t c, int64_t hw, float pre, int row_blocks, int dtype, void* stream) {
+  if (!g || (!gw2 && !gb2) || n <= 0 || c <= 0 || hw <= 0 || row_blocks < 1 || dtype != HF_F32) return HF_ERR_ARG;
+  if (!(pre - pre == 0.f)) return HF_ERR_ARG;                       // (NaN / infinity)
+  if ((x || mean || rstd) && !(x && mean && rstd)) return HF_ERR_ARG;  // xhat needs all three
+  if (gw2 && !x) return HF_ERR_ARG;
+  if (n > 0x7fffffffLL || c > 0x7fffffffLL || hw > 0x7fffffffLL || n * hw > 0x7fffffffLL) return HF_ERR_ARG;
+  const int64_t per = (n + row_blocks - 1) / row_blocks;
+  if (row_blocks > 65535 || (int64_t)(row_blocks - 1) * per >= n) return HF_ERR_ARG;  // an empty share
+  const dim3 grid((unsigned)((c + SQ_CH - 1) / SQ_CH), (unsigned)row_blocks);
+  hipLaunchKernelGGL(k_chan_sqsum, grid, dim3(BLOCK), 0, (hipStream_t)stream, (float*)gw2, (float*)gb2,
+                     (const float*)g, (const float*)x, (const float*)mean, (const float*)rstd, (unsigned)n, (unsigned)c,
+                     (unsigned)hw, (unsigned)per, pre);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
 
 int hf_bn_adjoint_pre(void* g_out, void* ga_out, const void* gy_a, int a_splits, int64_t a_slab,
                       const void* gy_b, int b_splits, int64_t b_slab, const void* mask_src, const void* w,

@@ -959,6 +959,144 @@ __device__ __forceinline__ void conv_tn_body(const ConvArgs& a, float* lds, int 
   }
 }
 
+// ---------------------------------------------------------------------------------
+// Squared-sum sibling of the TN kernel (hf_conv2d_nhwc_sqsum_slabs):
+//   out[k][tap][c] = sum_i ( pre * sum_{m in sample i} dY[m][k] * X[pix(m,tap)][c] )^2
+// ---------------------------------------------------------------------------------
+// The tile, the staging map, the LDS layout and the epilogue (finish_tile in slab mode) are conv_tn_body's in the 64x64
+// configuration; what differs is the reduction.  The splits run over SAMPLES: split s takes samples
+// [s*per, min(n, (s+1)*per)) and walks them as GROUPS of rows, each in ceil(glen / BK) steps whose staged rows are masked
+// on the GROUP's end (a group's last step is partial whenever glen % BK != 0, so no step ever mixes two groups):
+//   per-sample form (OUTER = false, P = oh*ow > 1): a group is one sample's P rows.  After its last step
+//     t = acc * pre (one rounding), sq += t * t (two roundings), acc = 0: 16 more accumulator registers per wave.
+//   squared-operand form (OUTER = true, P == 1): the per-sample gradient is the outer product dY_i[k] * X_i[c], so the
+//     share is ONE group of rows with both operands squared after the load (one rounding each) and the result
+//     acc * (pre * pre).
+// The loop is the plain one with one step of loads in flight (the next step's loads are issued in front of this step's
+// MFMAs); LDS is double-buffered with one barrier per step.
+struct SqArgs {
+  float pre;
+  int n, P, per;  // samples, rows per sample, samples per split
+};
+
+template <bool SCALAR, bool OUTER>
+__device__ __forceinline__ void conv_tn_sq_body(const ConvArgs& a, const SqArgs q, float* lds, int bid) {
+  typedef Small C;
+  constexpr int BM = C::BM, BN = C::BN, BK = C::BK, HK = C::HK, LDA = C::LDA, LDB = C::LDB;
+  float (*As)[BK][LDA] = reinterpret_cast<float (*)[BK][LDA]>(lds);
+  float (*Bs)[BK][LDB] = reinterpret_cast<float (*)[BK][LDB]>(lds + 2 * BK * LDA);
+  int& flag = *reinterpret_cast<int*>(lds + C::LDS_FLOATS - 4);
+  touch_args(a);
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave / C::WN, wn = wave % C::WN;
+  const int bq = (int)fdiv((unsigned)bid, a.fd_tiles_n), tile_n = bid - bq * a.tiles_n;
+  const int split = (int)fdiv((unsigned)bq, a.fd_tiles_m), tile_m = bq - split * a.tiles_m;
+  const int tile = tile_m * a.tiles_n + tile_n;
+  const int s0 = split * q.per < q.n ? split * q.per : q.n, s1 = s0 + q.per < q.n ? s0 + q.per : q.n;
+  const int glen = OUTER ? s1 - s0 : q.P, ngroups = OUTER ? (s1 > s0 ? 1 : 0) : s1 - s0;
+  const int gsteps = (glen + BK - 1) / BK, total = ngroups * gsteps;
+
+  const int cblocks = (a.cs + BN - 1) / BN;
+  const int ti = (int)fdiv((unsigned)tile_n, a.fd_cblocks), c0 = (tile_n - ti * cblocks) * BN;
+  constexpr int CQ = C::SM / 4, RP = CT / CQ, TU = BK / RP;
+  const int kr = t / CQ, cq = t % CQ;
+  const int ka = tile_m * BM + 4 * cq;  // dY channel
+  const int cb = c0 + 4 * cq;           // X channel
+  const bool bkok = (cb < a.cs) & (4 * cq < BN);
+  const int rs_ = a.tap_rs[ti], r = rs_ & 255, tq_ = rs_ >> 8;
+  const bool aok = (ka < a.kout) & (4 * cq < BM);
+
+  // step jj of group gi: rows base + jj*BK + kr + RP*u, those past the group's end masked
+  auto fetch = [&](int gi, int jj, float4 (&ra)[TU], float4 (&rb)[TU]) -> unsigned {
+    const int base = OUTER ? s0 : (s0 + gi) * q.P;
+    unsigned ok = 0;
+#pragma unroll
+    for (int u = 0; u < TU; ++u) {
+      const int local = jj * BK + kr + RP * u;
+      const bool mok = local < glen;
+      const int m = mok ? base + local : 0;
+      const int tq = (int)fdiv((unsigned)m, a.fd_rw), xx = m - tq * a.rw;
+      const int nn = (int)fdiv((unsigned)tq, a.fd_rh), yy = tq - nn * a.rh;
+      bool vb;
+      const int pix = gather_pixel(a, nn, yy, xx, r, tq_, vb);
+      vb = vb & mok & bkok;
+      const bool va = mok & aok;
+      const float* pa = a.mat + (va ? (size_t)m * a.kout + ka : 0);
+      const float* pb = a.src + (vb ? (size_t)pix * a.cs_ld + cb : 0);
+      if (SCALAR) {
+        ra[u] = ldg4s(pa, va ? a.kout - ka : 0);
+        rb[u] = ldg4s(pb, vb ? a.cs - cb : 0);
+      } else {  // (unconditional: a masked element reads a valid dummy address and is stashed as zero)
+        ra[u] = ldg4(pa);
+        rb[u] = ldg4(pb);
+      }
+      ok |= (va ? 1u : 0u) << (2 * u) | (vb ? 2u : 0u) << (2 * u);
+    }
+    return ok;
+  };
+  auto sqr = [](const float4& v) { return OUTER ? make_float4(v.x * v.x, v.y * v.y, v.z * v.z, v.w * v.w) : v; };
+  auto stash = [&](int buf, const float4 (&ra)[TU], const float4 (&rb)[TU], unsigned ok) {
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int u = 0; u < TU; ++u) {
+      *reinterpret_cast<float4*>(&As[buf][kr + RP * u][4 * cq]) = (ok >> (2 * u)) & 1u ? sqr(ra[u]) : zero;
+      *reinterpret_cast<float4*>(&Bs[buf][kr + RP * u][4 * cq]) = (ok >> (2 * u)) & 2u ? sqr(rb[u]) : zero;
+    }
+  };
+
+  f32x16 acc, sq[1][1];
+#pragma unroll
+  for (int x = 0; x < 16; ++x) acc[x] = sq[0][0][x] = 0.f;
+  const int i = lane & 31, h = lane >> 5;
+  auto compute = [&](int cur) {
+    float av[HK], bv[HK];
+#pragma unroll
+    for (int s = 0; s < HK; ++s) {
+      av[s] = As[cur][HK * h + s][wm * 32 + i];
+      bv[s] = Bs[cur][HK * h + s][wn * 32 + i];
+    }
+#pragma unroll
+    for (int s = 0; s < HK; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s], acc, 0, 0, 0);
+  };
+  const float pre2 = q.pre * q.pre;
+  float4 ra[TU], rb[TU];
+  unsigned ok = 0;
+  int fg = 0, fj = 0;  // (group, step) of the loads in flight
+  int cj = 0, cur = 0;
+  if (total > 0) ok = fetch(0, 0, ra, rb);
+  for (int st = 0; st < total; ++st) {
+    stash(cur, ra, rb, ok);
+    __syncthreads();
+    if (st + 1 < total) {  // (uniform) -- the last step re-fetches itself: loaded, never stashed
+      if (++fj == gsteps) { fj = 0; ++fg; }
+    }
+    ok = fetch(fg, fj, ra, rb);
+    compute(cur);
+    cur ^= 1;
+    if (++cj == gsteps) {  // (uniform) the group's last step
+      cj = 0;
+#pragma unroll
+      for (int x = 0; x < 16; ++x) {
+        if (OUTER) {
+          sq[0][0][x] = acc[x] * pre2;
+        } else {
+          const float tt = acc[x] * q.pre;
+          sq[0][0][x] += tt * tt;
+          acc[x] = 0.f;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  float* base = a.out + (size_t)(r * a.S + tq_) * a.out_c;
+  finish_tile<C>(a, sq, tile, split, wm, wn, lane, base, tile_m * BM, c0, a.kout, a.out_c, a.R * a.S * a.out_c, &flag);
+}
+
+template <bool SCALAR, bool OUTER>
+__global__ __launch_bounds__(CT) void k_conv_tn_sq(const ConvArgs a, const SqArgs q) {
+  __shared__ __attribute__((aligned(16))) float lds[Small::LDS_FLOATS];
+  conv_tn_sq_body<SCALAR, OUTER>(a, q, lds, blockIdx.x);
+}
+
 template <bool SCALAR, typename C, bool CLS = false, bool BNSUM = false>
 __global__ __launch_bounds__(CT) void k_conv_nt(const ConvArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[C::LDS_FLOATS];
@@ -1279,7 +1417,7 @@ struct Scratch {
 // Fill `a` for problem `p`; returns the number of workgroups (<= 0: error code).  `tickets`: ticket mode on the
 // scratch `sc`; else slab mode with p.splits splits (0: the plan -- choose them, towards sc->target_blocks workgroups
 // if `sc` names a count > 0).
-int64_t setup(ConvArgs& a, const hf_conv_problem& p, const Scratch* sc, bool tickets) {
+int64_t setup(ConvArgs& a, const hf_conv_problem& p, const Scratch* sc, bool tickets, bool force_small = false) {
   const int direction = p.direction, slab_splits = tickets ? -1 : p.splits, target_blocks = sc ? sc->target_blocks : 0;
   const int64_t n = p.n, h = p.h, w = p.w, c = p.c, k = p.k, r = p.r, s = p.s, stride_h = p.stride_h,
                 stride_w = p.stride_w, pad_h = p.pad_h, pad_w = p.pad_w;
@@ -1355,9 +1493,10 @@ int64_t setup(ConvArgs& a, const hf_conv_problem& p, const Scratch* sc, bool tic
         ++ncls;
       }
   }
-  a.big = direction <= 1 ? want_big(direction, rows, rows, a.nout, (int64_t)cls_taps_max * a.cs, 1, a.scalar)
-                         : want_big(direction, rows, a.kout, a.cs, rows, a.ntaps, a.scalar, a.ntaps == (int)(r * s),
-                                    slab_splits >= 0);
+  a.big = force_small      ? 0
+          : direction <= 1 ? want_big(direction, rows, rows, a.nout, (int64_t)cls_taps_max * a.cs, 1, a.scalar)
+                           : want_big(direction, rows, a.kout, a.cs, rows, a.ntaps, a.scalar, a.ntaps == (int)(r * s),
+                                      slab_splits >= 0);
   const int BM = a.big == 3 ? Flat96::BM : a.big ? Big::BM : Small::BM;
   const int BN = a.big == 2 ? Big96::BN : a.big ? Big::BN : Small::BN;
   const int BK = a.big ? Big::BK : Small::BK;
@@ -1436,6 +1575,7 @@ enum : unsigned {
   ALLOW_ALL = 7,
   PLAN_ONLY = 8,
   PLAN_TICKETS = 16,
+  FORCE_SMALL = 32,  // the 64x64 configuration whatever the geometry (the squared-sum kernel has no other)
 };
 
 int plan_problem(const hf_conv_problem& p, int dtype, const Scratch* sc, unsigned allow, ConvArgs& a, int64_t& blocks) {
@@ -1452,7 +1592,7 @@ int plan_problem(const hf_conv_problem& p, int dtype, const Scratch* sc, unsigne
     const int rc = check_common(p, oh, ow, dtype, sc);
     if (rc) return rc;
   }
-  blocks = setup(a, p, sc, tickets);
+  blocks = setup(a, p, sc, tickets, allow & FORCE_SMALL);
   if (blocks <= 0) return (int)blocks;
   if (slab_launch && a.splits != p.splits) return HF_ERR_ARG;
   if ((a.scalar && !(allow & ALLOW_SCALAR)) || (a.big && !(allow & ALLOW_BIG)) || (a.ncls > 0 && !(allow & ALLOW_CLS)))
@@ -1665,6 +1805,90 @@ int hf_conv2d_nhwc_group_slabs(const hf_conv_problem* problems, int n_problems, 
     if (group_add(m, i, problems[i].direction == 2, blocks)) return HF_ERR_ARG;
   }
   launch_group(a, m, /*bnsum=*/false, (hipStream_t)stream);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+// ---- sum over the samples of the squared per-sample weight gradient (BackPACK's SumGradSquared) ----------------------
+namespace {
+
+// a split count that leaves no split without a sample: split s takes samples [s*ceil(n/splits), ...)
+bool sq_shares_ok(int64_t n, int64_t splits) {
+  return splits >= 1 && splits <= n && ((n + splits - 1) / splits) * (splits - 1) < n;
+}
+
+// Workgroups the per-sample form is split towards.  Its workgroups are long -- a sample's ceil(P / BK) steps times the
+// samples of the share, with one step of loads in flight -- and four of them fit a CU (LDS, registers), so the matrix
+// pipe is fed by the OTHER resident workgroups while one waits: two rounds of a full chip.  Measured per layer of
+// All-CNN-C (batch 32 and 128) and ResNet-18 (batch 32), scripts/bench_diag_ef.py --split-sweep
+// (profiles/r23_sqsum_split_sweep.jsonl): from the 256 of the latency-bound product launches the time still halves
+// (All-CNN-C's 96 -> 96 layer on 32x32 maps, batch 128: 832 us at 288 workgroups, 467 at 1 152, 405 at 2 304, 399 at
+// 4 608); beyond ~2 000 it is flat or rises, and every further split is one more slab for the gather to read.
+#ifndef HF_SQSUM_TARGET_BLOCKS
+#define HF_SQSUM_TARGET_BLOCKS 2048
+#endif
+
+// Geometry of a squared-sum problem through THE planner (direction 2, slab mode, one split, 64x64 tiles), and the
+// planned split count over the samples: towards the workgroup target (the squared-operand form, P == 1, is an ordinary
+// reduction over n rows: the conv planner's own K-split plan over its ceil(n / BK) steps), at most n, no split left
+// without a sample.
+int sq_plan(const hf_conv_problem& p, int target_blocks, ConvArgs& a, int64_t& tiles, int64_t& P) {
+  int64_t blocks;
+  const int rc = plan_problem(p, HF_F32, nullptr, ALLOW_SCALAR | PLAN_ONLY | FORCE_SMALL, a, blocks);
+  if (rc) return rc;
+  P = (int64_t)a.rh * a.rw;
+  tiles = (int64_t)a.tiles_m * a.tiles_n;
+  int64_t sp;
+  if (P == 1) {
+    sp = choose_splits(tiles, (p.n + Small::BK - 1) / Small::BK, target_blocks, 0, true, Small::BK);
+  } else {
+    sp = ((target_blocks > 0 ? target_blocks : HF_SQSUM_TARGET_BLOCKS) + tiles - 1) / tiles;
+  }
+  if (sp > p.n) sp = p.n;
+  if (sp < 1) sp = 1;
+  while (!sq_shares_ok(p.n, sp)) --sp;
+  return (int)sp;
+}
+
+}  // namespace
+
+int hf_conv2d_nhwc_sqsum_plan(int64_t n, int64_t h, int64_t w, int64_t c, int64_t k, int64_t r, int64_t s,
+                              int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int target_blocks) {
+  const hf_conv_problem p = {2, nullptr, nullptr, nullptr, n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w,
+                             0, 0, 1, 0, 0};
+  ConvArgs a;
+  int64_t tiles, P;
+  return sq_plan(p, target_blocks, a, tiles, P);
+}
+
+int hf_conv2d_nhwc_sqsum_slabs(void* out, const void* act, const void* mat, int64_t n, int64_t h, int64_t w, int64_t c,
+                               int64_t k, int64_t r, int64_t s, int64_t stride_h, int64_t stride_w, int64_t pad_h,
+                               int64_t pad_w, int64_t act_ld, int64_t out_c, float pre, int splits,
+                               int64_t slab_stride, int dtype, void* stream) {
+  const hf_conv_problem p = {2, out, act, mat, n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w,
+                             act_ld, out_c, 1, slab_stride, 0};
+  ConvArgs a;
+  int64_t tiles, P;
+  if (act_ld < 0) return HF_ERR_ARG;
+  const int planned = sq_plan(p, 0, a, tiles, P);  // (field ranges, live taps, tiles: the planner's)
+  if (planned < 1) return planned;
+  const int rc = check_common(p, a.rh, a.rw, dtype, nullptr);
+  if (rc) return rc;
+  if (!(pre - pre == 0.f) || !sq_shares_ok(n, splits)) return HF_ERR_ARG;  // (NaN / infinity; an empty split)
+  if (splits > 1 && slab_stride < k * r * s * (int64_t)a.out_c) return HF_ERR_ARG;  // (slabs would overlap)
+  if (tiles * splits > 0x7fffffffLL) return HF_ERR_ARG;
+  a.splits = splits;
+  seal(a);
+  const SqArgs q = {pre, (int)n, (int)P, (int)((n + splits - 1) / splits)};
+  const dim3 grid((unsigned)(tiles * splits)), block(CT);
+  hipStream_t st = (hipStream_t)stream;
+  if (P == 1) {
+    if (a.scalar) hipLaunchKernelGGL((k_conv_tn_sq<true, true>), grid, block, 0, st, a, q);
+    else hipLaunchKernelGGL((k_conv_tn_sq<false, true>), grid, block, 0, st, a, q);
+  } else {
+    if (a.scalar) hipLaunchKernelGGL((k_conv_tn_sq<true, false>), grid, block, 0, st, a, q);
+    else hipLaunchKernelGGL((k_conv_tn_sq<false, false>), grid, block, 0, st, a, q);
+  }
   HF_HIP(hipGetLastError());
   return HF_OK;
 }

@@ -136,6 +136,7 @@ class FusedGGNEngine(_Launcher, _Topology, _Buffers, _Forward, _TangentSweep, _A
         self.hessian = bool(hessian)
         self._second = False  # (inside the adjoint sweep of a Hessian product)
         self._l2 = None
+        self._diag_batched = os.environ.get("HF_DIAG_EF_BATCHED", "0") == "1"  # (diag_ef: one launch per layer)
         self.outputs = outputs
         self.dev = outputs.device
         self._index = {id(p): i for i, p in enumerate(self.params)}

@@ -1,11 +1,12 @@
 """Diagonal of the empirical Fisher from one adjoint sweep + per-sample weight-gradient launches
-(preconditioners.py:11-105).
+(preconditioners.py:11-105) -- or, with ``HF_DIAG_EF_BATCHED=1``, + ONE squared-sum launch per layer and one gather.
 
 Mixin of ``FusedGGNEngine`` (engine/core.py); see that class for the sweeps' overall structure."""
 
 import torch
 
 from .. import _lib
+from .problems import chan_sqsum_args, conv_sqsum_args
 
 
 class _DiagEF:
@@ -17,7 +18,13 @@ class _DiagEF:
         from ONE adjoint sweep of the whole batch -- in eval mode the samples do not interact, so the batch
         cotangents ARE the per-sample cotangents -- followed, per sample, by the weight-gradient convolutions on that
         sample's rows and one squaring gather (``hf_pack_ex`` mode 1).  A tagged L2 term (each per-sample loss of
-        the reference carries it whole) enters in closed form: sum (a_i + b)^2 = sum a_i^2 + 2 b sum a_i + N b^2."""
+        the reference carries it whole) enters in closed form: sum (a_i + b)^2 = sum a_i^2 + 2 b sum a_i + N b^2.
+
+        ``HF_DIAG_EF_BATCHED=1`` (read when the engine is built): instead of the per-sample launches, per unit ONE
+        ``hf_conv2d_nhwc_sqsum_slabs`` on the whole-batch operands (it squares and sums the per-sample weight gradients
+        inside the launch: BackPACK's ``SumGradSquared``), ONE ``hf_chan_sqsum`` for the BatchNorm / bias entries, and
+        ONE plain gather (``hf_pack_ex`` mode 0) for all of them -- a number of launches that does not depend on the
+        batch.  The factor that undoes the loss's 1/N goes into the launches (``pre``: applied before squaring)."""
         if self.loss_spec is None or self.train_bn:
             raise RuntimeError("engine.diag_ef needs a softmax cross-entropy / MSE loss and eval-mode BatchNorm")
         if self.loss_spec["reduction"] != reduction:
@@ -26,6 +33,8 @@ class _DiagEF:
         if out is None:
             out = torch.empty(self.n, dtype=torch.float32, device=self.dev)
         out.zero_()
+        if self._diag_batched:
+            self._diag_buffers()  # (in front of the sweep: a masked cotangent allocated here is filled by it)
         l2, self._l2 = self._l2, None
         try:
             mean_grad = self.gradient()  # fills the units' cotangents (g / ga, or g1 / ga1 of a Hessian engine)
@@ -35,7 +44,9 @@ class _DiagEF:
         first_order = self.hessian
         self._diag_buffers()
         tensors, perms, splits = self._diag_pack
-        for i in range(n):
+        if self._diag_batched:
+            self._diag_batched_launches(out, n, scale, first_order)
+        for i in range(0 if self._diag_batched else n):
             for u in self.units:
                 if u.dead:  # (frozen, behind frozen layers only: the sweep left no cotangent here, nothing is gathered)
                     continue
@@ -71,8 +82,35 @@ class _DiagEF:
             out.div_(float(n))
         return out
 
+    def _diag_batched_launches(self, out, n, pre, first_order):
+        """The batched sweep behind the adjoint sweep: per live unit one squared-sum convolution and one squared channel
+        sum on the whole batch, then ONE gather of all their slabs and partial rows."""
+        tensors, perms, splits = self._diag_pack
+        for u in self.units:
+            if u.dead:  # (as below: no cotangent here, nothing is gathered)
+                continue
+            ga = u.ga1 if first_order else u.ga
+            if u.pw is not None:
+                act = u.cols_pad if u.im2col else u.x
+                self._launch("hf_conv2d_nhwc_sqsum_slabs",
+                             *conv_sqsum_args(u.wps, act, ga, u.geo1, u.sW1, pre, out_c=u.jcols if u.im2col else 0))
+            if u.pg is None and u.pb is None:
+                continue
+            k, hw = u.a.shape[1], u.a.shape[2] * u.a.shape[3]
+            gb2 = u.gbs if u.pb is not None else None
+            if u.bn is not None:
+                self._launch("hf_chan_sqsum",
+                             *chan_sqsum_args(u.g1 if first_order else u.g, n, k, hw, u.rb1, pre, gb2=gb2,
+                                              gw2=u.gws if u.pg is not None else None,
+                                              **(dict(x=u.a, mean=u.mean, rstd=u.rstd) if u.pg is not None else {})))
+            else:
+                self._launch("hf_chan_sqsum", *chan_sqsum_args(ga, n, k, hw, u.rb1, pre, gb2=gb2))
+        _lib.pack_ex(out, tensors, perms, splits, scale=1.0, live=self._pack_live, mode=0)
+
     def _diag_buffers(self):
-        """Per-sample (n = 1) geometry, split counts and slab buffers of ``diag_ef`` (allocated on first use)."""
+        """Per-sample (n = 1) geometry, split counts and slab buffers of ``diag_ef`` (allocated on first use).  Batched
+        sweep: the whole-batch geometry (the im2col'd stem as a 1x1 convolution over its [n, oh, ow] map of patches), the
+        planned sample splits, one slab per split and one partial row per share of the samples."""
         if getattr(self, "_diag_pack", None) is not None:
             return
         f32, dev = torch.float32, self.dev
@@ -81,7 +119,17 @@ class _DiagEF:
             k = u.a.shape[1]
             if u.bn is not None and not self.hessian and u.g is None:
                 u.g, u.needs_g = torch.empty_like(u.a), True  # (every unit's masked cotangent is needed per sample)
-            if u.im2col:
+            u.rb1 = 1
+            if self._diag_batched:
+                n = u.a.shape[0]
+                u.geo1 = ((n, u.a.shape[2], u.a.shape[3]) + tuple(u.geo_w[3:])) if u.im2col else tuple(u.geo)
+                n_, h, w, c, k_, r, s_, sd, pd = u.geo1
+                u.sW1 = _lib.conv_sqsum_plan(n_, h, w, c, k_, r, s_, sd, pd)
+                # shares of the samples for the channel sums: ~one workgroup per CU (64 channels each), none empty
+                u.rb1 = max(1, min(n, 256 // -(-k // 64)))
+                while -(-n // u.rb1) * (u.rb1 - 1) >= n:
+                    u.rb1 -= 1
+            elif u.im2col:
                 rows1 = u.a.shape[2] * u.a.shape[3]
                 u.geo_w1 = (rows1,) + tuple(u.geo_w[1:])
                 u.sW1 = self._plan_stem(2, u.geo_w1)
@@ -98,12 +146,13 @@ class _DiagEF:
                         perms[u.pw] = (c, r * s_)
                 if u.sW1 > 1:
                     splits[u.pw] = (u.sW1, u.wps.shape[1])
-            u.gws = torch.zeros((1, k), dtype=f32, device=dev)
-            u.gbs = torch.zeros((1, k), dtype=f32, device=dev)
-            if u.pg is not None:
-                tensors[u.pg] = u.gws[0]
-            if u.pb is not None:
-                tensors[u.pb] = u.gbs[0]
+            u.gws = torch.zeros((u.rb1, k), dtype=f32, device=dev)
+            u.gbs = torch.zeros((u.rb1, k), dtype=f32, device=dev)
+            for pi, buf in ((u.pg, u.gws), (u.pb, u.gbs)):
+                if pi is not None:
+                    tensors[pi] = buf[0]
+                    if u.rb1 > 1:
+                        splits[pi] = (u.rb1, k)
         if self.fc is not None:  # (filled in closed form afterwards: zeros here)
             self._diag_zero_fw = torch.zeros(self.fc.weight.numel(), dtype=f32, device=dev)
             tensors[self.pfw] = self._diag_zero_fw

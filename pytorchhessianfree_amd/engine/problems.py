@@ -87,3 +87,18 @@ def bn_adjoint_v4_args(q):
     """``hf_bn_adjoint_v4``: the elementwise part (gres -> g_out, gx -> ga_out); the sums' fields are not read."""
     return (q.gres, q.gx, q.gy, q.gy_splits, q.gy_slab, q.gy2, q.gy2_splits, q.gy2_slab, q.mask_src, q.w, q.rstd,
             q.n * q.hw, q.c)
+
+
+# ---- the squared-sum launches of the batched diagonal empirical Fisher (positional entry points, no struct) ------------
+def conv_sqsum_args(out, act, mat, geo, splits, pre, act_ld=0, out_c=0):
+    """``hf_conv2d_nhwc_sqsum_slabs``: ``out`` [splits, numel] receives split s's partial sum over its samples of the
+    squared per-sample weight gradient of ``act`` (X) and ``mat`` (dY), each scaled by ``pre`` before it is squared."""
+    n, h, w, c, k, r, s, st, pd = geo
+    return (out, act, mat, n, h, w, c, k, r, s, st[0], st[1], pd[0], pd[1], act_ld, out_c, float(pre), int(splits),
+            out.shape[1])
+
+
+def chan_sqsum_args(g, n, c, hw, row_blocks, pre, gw2=None, gb2=None, x=None, mean=None, rstd=None):
+    """``hf_chan_sqsum``: the squared per-sample scale (``gw2``, needs ``x`` / ``mean`` / ``rstd``) and shift or bias
+    (``gb2``) gradients summed over the samples, ``row_blocks`` partial rows each."""
+    return (gw2, gb2, g, x, mean, rstd, n, c, hw, float(pre), int(row_blocks))

@@ -125,7 +125,8 @@ class _SessionSteps:
         """Diagonal empirical-Fisher preconditioner at the CURRENT damping
         (optimizer.py:928-952).  Unlike the reference, the result is returned.  With a persistent engine
         session for ``model`` (from the second ``step`` on) the diagonal comes from ONE adjoint sweep of the engine
-        plus per-sample weight-gradient launches (``engine.diag_ef``) instead of one backward pass per sample
+        plus per-sample weight-gradient launches (``engine.diag_ef``; with ``HF_DIAG_EF_BATCHED=1`` plus one squared-sum
+        launch per layer, whatever the batch) instead of one backward pass per sample
         (``use_backpack=False``) / a batched per-sample-gradient pass (``True``): the same quantity.  Without a
         session, ``use_backpack=True`` on a prepared MLP with ``HF_DENSE_ENGINE=1`` takes the dense-stack engine's
         sweep (``preconditioners.diag_EF_backpack``)."""

@@ -379,8 +379,9 @@ class EngineSession(_TwoPhaseProduct, _Session):
         return self.grad_buffer
 
     def diag_ef(self, reduction):
-        """The diagonal empirical Fisher of the engine's current batch (``engine.diag_ef``: ~20 launches per sample)
-        as ONE graph replay; captured on first use.  Returns a fresh vector."""
+        """The diagonal empirical Fisher of the engine's current batch as ONE graph replay of whatever ``engine.diag_ef``
+        issues -- the adjoint sweep and then ``2 * units + 1`` launches per SAMPLE, or with ``HF_DIAG_EF_BATCHED=1``
+        about ``2 * units + 2`` launches in all; captured on first use.  Returns a fresh vector."""
         key = ("diag", reduction)
         if key not in self._diag_graphs:
             eng = self.engine
