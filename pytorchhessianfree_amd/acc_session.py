@@ -97,8 +97,11 @@ class AccumulatedSession(_Session):
         for a model that does not couple the samples of a batch their concatenation IS the accumulation -- the
         reference's own test states it (tests/test_optimizer_acc.py:116-175: [7, 8] chunks == one batch of 15).  Not
         merged: a model with a train-mode BatchNorm or an active dropout layer (per-chunk statistics / masks are part
-        of the reference's result), chunks that differ in more than the batch size.  Returns lists of slot indices,
-        in order of first appearance."""
+        of the reference's result), chunks that differ in more than the batch size.  What the loss function adds per
+        CALL rather than per sample -- a tagged quadratic regulariser -- is not the concatenation's: the reference adds
+        it once per chunk occurrence, which under ``mean`` comes to the merged engine's one term (the weights sum to the
+        group's) and under ``sum`` to as many terms as the group has chunks; ``_build`` gives a merged engine's
+        quadratic term that factor.  Returns lists of slot indices, in order of first appearance."""
         coupled = any((isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.training)
                       or (isinstance(m, torch.nn.modules.dropout._DropoutNd) and m.training and m.p > 0)
                       for m in model.modules())
@@ -164,6 +167,16 @@ class AccumulatedSession(_Session):
                     raise _NoEngine("the fused engine does not cover this model / loss")
                 engines.append(eng)
                 del out, loss
+            # What is per CHUNK rather than per sample does not merge by concatenation: a tagged quadratic term
+            # (testproblems.l2_regularized) is part of the user's loss function, which the reference calls once per chunk
+            # occurrence (optimizer.py:641, :678-684: ``result += eval_mb``).  Under ``mean`` the occurrences' weights sum to
+            # the merged engine's; under ``sum`` every occurrence weighs 1, so an engine that stands for a group of m
+            # chunks carries the term m times -- in its loss head, its gradient and its Hessian product, which all read
+            # ``_l2`` (the engine's weight per list then counts how often the GROUP is listed).
+            if reduction == "sum":
+                for eng, g in zip(engines, self.groups):
+                    if len(g) > 1 and eng._l2 is not None:
+                        eng._l2 = eng._l2 * float(len(g))
             self.engines = engines
             self._layers = [e.layer_signature() for e in engines]
             # (the compact all-reduce layout -- which kernel taps can meet data -- is engine[0]'s: it depends on the

@@ -6,6 +6,8 @@ kernel.  ``wide``: 8x8 inputs, batch 16, 32 / 64 channels and a third block on a
 downsample block whose two adjoints share one launch, and units with ``rb == 1``; its dead taps give the compact layout
 ``local_compact`` needs."""
 
+import copy
+
 import torch
 from torch import nn
 
@@ -59,7 +61,8 @@ def _arena_order(model, where):
     return [p for _, p in named[:at]] + [model.fc.bias] + [p for _, p in named[at:]]
 
 
-def build(net, pattern="plain", train=False, hessian=False, arena_at=None):
+def _resnet(net):
+    """The stock net of ``NETS[net]`` on the CPU, seeded."""
     spec = NETS[net]
     torch.manual_seed(5)
     model = SmallResNet(spec["ch"], spec["blocks"])
@@ -71,6 +74,12 @@ def build(net, pattern="plain", train=False, hessian=False, arena_at=None):
                 m.weight.uniform_(0.6, 1.3)
                 m.bias.uniform_(-0.2, 0.2)
                 m.eps = 0.1
+    return model
+
+
+def build(net, pattern="plain", train=False, hessian=False, arena_at=None):
+    spec = NETS[net]
+    model = _resnet(net)
     _freeze(model, pattern)
     model.train(train)
     x, t = torch.randn(spec["batch"], 1, 8, 8), torch.randint(0, 10, (spec["batch"],))
@@ -97,6 +106,27 @@ class SmallConvStack(nn.Module):
 
     def forward(self, x):
         return torch.flatten(self.net(x), -3)
+
+
+def three_forms(kind, train=False, prepared=True):
+    """One net in three forms: the stock fp32 model on the CPU, a float64 CPU twin with the same parameters and
+    buffers (a deep copy: nothing is shared), and a copy on the GPU prepared for the engine (``None`` without
+    ``prepared``: the tests that run without a GPU).  ``kind``: "resnet" (``SmallResNet`` of ``NETS["small"]``: 8x8
+    inputs of one channel, 10 classes) or "plain" (``SmallConvStack``: 8x8 inputs of three channels, 12 classes), in
+    eval or train mode."""
+    if kind == "resnet":
+        model = _resnet("small")
+    else:
+        assert kind == "plain"
+        torch.manual_seed(7)
+        model = SmallConvStack()
+    model.train(train)
+    twin = copy.deepcopy(model).double()
+    gpu = None
+    if prepared:
+        gpu = copy.deepcopy(model).to(DEV)
+        modelprep.prepare_model(gpu, channels_last=True)
+    return model, twin, gpu
 
 
 def build_plain(hessian=False):
