@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 22
+#define HF_ABI_VERSION 23
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -766,6 +766,47 @@ int hf_maxpool_adjoint_nhwc(void* g, const void* gy_a, int a_splits, int64_t a_s
                             int b_splits, int64_t b_slab, const void* idx, int64_t n, int64_t h, int64_t w,
                             int64_t oh, int64_t ow, int64_t c, int64_t kh, int64_t kw, int64_t stride_h,
                             int64_t stride_w, int64_t pad_h, int64_t pad_w, int dtype, void* stream);
+/*
+ * A plain stack's pooled layer  y_pool = max_pool(relu(a + b))  inside the sweeps, bias / ReLU / pool in ONE launch per
+ * direction (ABI 23).  ReLU masks and pool positions are piecewise constant, and a window's maximum of relu(.) is positive
+ * exactly where the pre-activation at its position is, so the mask is read off the POOLED map and the tangent sweep never
+ * forms the full-resolution tangent.  fp32 NHWC; idx int32 [n,oh,ow,c], flat y*w + x, as hf_maxpool_forward_nhwc writes it.
+ *
+ * hf_pool_act_tangent_nhwc:
+ *   out[n,oy,ox,c] = m * (sum_s slabs[s][n, idx[n,oy,ox,c], c] + v_b[c]),   m = relu ? (y_pool[n,oy,ox,c] > 0) : 1
+ * slabs: `splits` full-resolution [n,h,w,c] slabs `slab_stride` elements apart (the tangent convolution's split-K
+ * results); v_b nullable (any 4-byte boundary); y_pool only read with relu; out may be the first-channels slice of a wider
+ * NHWC buffer (out_ld floats per pixel, 0 = dense).  A position outside the plane is clamped to its last pixel, never
+ * followed.  Rounding: fp32; slab 0, then slabs 1 .. splits-1 added in split order (one rounding each), + v_b (one
+ * rounding), then the mask (a select).
+ *
+ * hf_pool_act_adjoint_nhwc (gather form: no zero-fill, no atomics):
+ *   ga[n,y,x,c] = sum over the windows (oy,ox) that contain (y,x) and whose idx is (y,x), in (oy,ox) order, of
+ *                 m * sum_s gy[s][n,oy,ox,c]
+ * gy: `gy_splits` pooled [n,oh,ow,c] slabs `gy_slab` elements apart (the consumer's data-gradient slabs); oh / ow must be
+ * the pooled extent of (kh, kw, stride, pad) without dilation or ceil_mode.  gb (nullable) receives `row_blocks` partial
+ * rows of sum ga over shares of the FULL-RESOLUTION rows, c elements apart -- the convention of hf_chan_affine_bwd_ex's
+ * gb, so hf_pack_ex adds them up unchanged: share b = rows [b*per, (b+1)*per), per = ceil(n*h*w / row_blocks); an empty
+ * share is HF_ERR_ARG; row_blocks is not read without gb (one thread per pixel and channel quad then).  Rounding: a
+ * window's slabs are added in split order in fp32, masked by a select, and added to the pixel's sum in window order
+ * (starting from +0); gb is accumulated in fp64 (each thread its rows in ascending order, the threads of a channel in a
+ * fixed order) and rounded once per partial row.
+ *
+ * Both: two launches on the same operands give the same bits; nothing outside the described extents is read or written.
+ * Refused with HF_ERR_ARG before any launch: a null required operand (y_pool with relu), splits outside
+ * 1 .. HF_POOL_ACT_MAX_SPLITS, slabs closer than one map (they would overlap), out_ld below c (other than 0), an extent
+ * below 1, oh / ow that are not the geometry's (adjoint), n*h*w*c, n*oh*ow*c or n*oh*ow*out_ld >= 2^31, another dtype.
+ * Channel counts that are multiples of 4 with 16-byte aligned operands (and slab strides / out_ld multiples of 4) run
+ * 16 bytes per thread, anything else element-wise: same sums, same bits.
+ */
+#define HF_POOL_ACT_MAX_SPLITS 1024
+int hf_pool_act_tangent_nhwc(void* out, int64_t out_ld, const void* slabs, int splits, int64_t slab_stride,
+                             const void* v_b, const void* idx, const void* y_pool, int relu, int64_t n, int64_t h,
+                             int64_t w, int64_t oh, int64_t ow, int64_t c, int dtype, void* stream);
+int hf_pool_act_adjoint_nhwc(void* ga, void* gb, int row_blocks, const void* gy, int gy_splits, int64_t gy_slab,
+                             const void* idx, const void* y_pool, int relu, int64_t n, int64_t h, int64_t w,
+                             int64_t oh, int64_t ow, int64_t c, int64_t kh, int64_t kw, int64_t stride_h,
+                             int64_t stride_w, int64_t pad_h, int64_t pad_w, int dtype, void* stream);
 /*
  * hf_linear_ce_head: the classifier head of J^T H_L J v in one launch (one workgroup per 4 rows):
  *   Jv = t_feat W^T + feat V_W^T + v_b;  HJv = scale * p * (Jv - <p, Jv>) (as hf_softmax_ce_hvp);

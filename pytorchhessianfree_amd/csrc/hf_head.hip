@@ -103,6 +103,163 @@ __global__ __launch_bounds__(HB) void k_maxpool_forward(float* __restrict__ out,
 }
 
 // ---------------------------------------------------------------------------------------
+// bias / ReLU / max-pool of a plain stack's pooled layer in ONE launch per direction.  ReLU masks and pool positions
+// are piecewise constant, so with  y_pool = max_pool(relu(a + b))  and idx the windows' positions
+//   tangent:  t_pool[n,oy,ox,c] = (y_pool > 0) * (t_a[n, idx, c] + v_b[c])
+//   adjoint:  g_a[n,y,x,c]      = sum over the windows whose idx is (y,x) of (y_pool > 0) * g_pool[n,oy,ox,c]
+// (a window's maximum of relu(.) is positive exactly where the pre-activation at idx is): neither sweep needs the
+// full-resolution tangent map, the mask comes from the pooled map.  A thread owns W consecutive channels of a pixel
+// (W = 4: 16-byte loads of idx / y_pool / cotangents, 16-byte stores; W = 1: any channel count and alignment).
+// ---------------------------------------------------------------------------------------
+template <int W>
+__global__ __launch_bounds__(HB) void k_pool_act_tangent(float* __restrict__ out, const float* __restrict__ slabs,
+                                                         int splits, long long slab_stride,
+                                                         const float* __restrict__ vb, const int* __restrict__ idx,
+                                                         const float* __restrict__ ypool, unsigned total,
+                                                         unsigned CQ, unsigned out_ld, unsigned opix, unsigned ipix) {
+  using VF = ColOf<float, W>;
+  using VI = ColOf<int, W>;
+  const unsigned i = blockIdx.x * HB + threadIdx.x;
+  if (i >= total) return;
+  const unsigned cq = i % CQ, pix = i / CQ, n = pix / opix, C = CQ * W, c0 = cq * W;
+  const unsigned e = pix * C + c0;
+  const VI ix = *reinterpret_cast<const VI*>(idx + e);
+  VF m, b, s;
+  if (ypool) m = *reinterpret_cast<const VF*>(ypool + e);
+  if (vb) {  // (a slice of the flat vector: on any 4-byte boundary)
+#pragma unroll
+    for (int k = 0; k < W; ++k) b.e[k] = vb[c0 + k];
+  }
+  unsigned off[W];
+#pragma unroll
+  for (int k = 0; k < W; ++k) {
+    // (a position outside the plane would be a read outside the slabs: clamped, never followed)
+    const unsigned p = (unsigned)ix.e[k] < ipix ? (unsigned)ix.e[k] : ipix - 1;
+    off[k] = (n * ipix + p) * C + c0 + k;
+    s.e[k] = slabs[off[k]];
+  }
+  // slab_sum, for the W channels together: one batch of all of them in flight, each channel added in split order
+  for (int sp = 1; sp < splits; sp += 8) {
+    float v[W][8];
+#pragma unroll
+    for (int k = 0; k < W; ++k) slab_issue(v[k], slabs, off[k], sp, splits, slab_stride);
+#pragma unroll
+    for (int k = 0; k < W; ++k) slab_add<false>(s.e[k], v[k], sp, splits);
+  }
+#pragma unroll
+  for (int k = 0; k < W; ++k) {
+    float t = s.e[k];
+    if (vb) t = t + b.e[k];
+    if (ypool) t = m.e[k] > 0.f ? t : 0.f;
+    s.e[k] = t;
+  }
+  chain_store_col<HF_WT_ELEM>(out + (size_t)pix * out_ld + c0, s);
+}
+
+// g_a of W channels of the full-resolution pixel (n, y, x): windows in (oy, ox) order, each one's slabs in split order
+template <int W>
+__device__ __forceinline__ ColOf<float, W> pool_act_adjoint_at(const float* __restrict__ gy, int splits,
+                                                               long long slab, const int* __restrict__ idx,
+                                                               const float* __restrict__ ypool, unsigned C,
+                                                               unsigned c0, int n, int y, int x, const PoolGeo& q) {
+  using VF = ColOf<float, W>;
+  using VI = ColOf<int, W>;
+  const int self = y * q.W + x;
+  // windows containing (y, x): oy*sh - ph <= y <= oy*sh - ph + kh - 1
+  int oy0 = y + q.ph - q.kh + 1; oy0 = oy0 > 0 ? (oy0 + q.sh - 1) / q.sh : 0;
+  int oy1 = (y + q.ph) / q.sh;   oy1 = oy1 < q.OH - 1 ? oy1 : q.OH - 1;
+  int ox0 = x + q.pw - q.kw + 1; ox0 = ox0 > 0 ? (ox0 + q.sw - 1) / q.sw : 0;
+  int ox1 = (x + q.pw) / q.sw;   ox1 = ox1 < q.OW - 1 ? ox1 : q.OW - 1;
+  VF acc;
+#pragma unroll
+  for (int k = 0; k < W; ++k) acc.e[k] = 0.f;
+  for (int oy = oy0; oy <= oy1; ++oy)
+    for (int ox = ox0; ox <= ox1; ++ox) {
+      const unsigned o = (unsigned)((n * q.OH + oy) * q.OW + ox) * C + c0;
+      const VI ix = *reinterpret_cast<const VI*>(idx + o);
+      bool any = false;
+#pragma unroll
+      for (int k = 0; k < W; ++k) any = any || ix.e[k] == self;
+      if (!any) continue;
+      VF v = *reinterpret_cast<const VF*>(gy + o);
+      VF m;
+      if (ypool) m = *reinterpret_cast<const VF*>(ypool + o);
+      v = slab_sum<8>(v, gy, o, splits, slab);
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        const bool on = ix.e[k] == self && (!ypool || m.e[k] > 0.f);
+        acc.e[k] += on ? v.e[k] : 0.f;
+      }
+    }
+  return acc;
+}
+
+// without bias sums: one pixel's W channels per thread
+template <int W>
+__global__ __launch_bounds__(HB) void k_pool_act_adjoint(float* __restrict__ ga, const float* __restrict__ gy,
+                                                         int splits, long long slab, const int* __restrict__ idx,
+                                                         const float* __restrict__ ypool, unsigned total,
+                                                         unsigned CQ, PoolGeo q) {
+  const unsigned i = blockIdx.x * HB + threadIdx.x;
+  if (i >= total) return;
+  const unsigned cq = i % CQ, C = CQ * W;
+  unsigned pix = i / CQ;
+  const unsigned row = pix;
+  const int x = pix % q.W; pix /= q.W;
+  const int y = pix % q.H;
+  const int n = pix / q.H;
+  const ColOf<float, W> v = pool_act_adjoint_at<W>(gy, splits, slab, idx, ypool, C, cq * W, n, y, x, q);
+  chain_store_col<HF_WT_ELEM>(ga + (size_t)row * C + cq * W, v);
+}
+
+// with bias sums: workgroup b owns the full-resolution rows [b*per, (b+1)*per) and all channels, as the row-major
+// BatchNorm adjoint (hf_bn.hip) does; thread (tx, ty) walks channel column tx of every G-th row of the share and keeps
+// its sum in fp64; the G sums of a column are added in ty order and rounded once -> gb[b*C + channel]
+template <int W>
+__global__ __launch_bounds__(HB) void k_pool_act_adjoint_rows(float* __restrict__ ga, float* __restrict__ gb,
+                                                              const float* __restrict__ gy, int splits,
+                                                              long long slab, const int* __restrict__ idx,
+                                                              const float* __restrict__ ypool, unsigned rows,
+                                                              unsigned per, unsigned CQ, PoolGeo q) {
+  __shared__ double red[HB * W];
+  const unsigned C = CQ * W, cols = CQ < HB ? CQ : HB, G = HB / cols;
+  const unsigned tx = threadIdx.x % cols, ty = threadIdx.x / cols;
+  const unsigned lo = blockIdx.x * per, hi = lo + per < rows ? lo + per : rows;
+  for (unsigned cb = 0; cb < CQ; cb += cols) {
+    const unsigned cq = cb + tx;
+    const bool live = ty < G && cq < CQ;
+    double acc[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) acc[k] = 0.0;
+    if (live) {
+      for (unsigned r = lo + ty; r < hi; r += G) {
+        unsigned pix = r;
+        const int x = pix % q.W; pix /= q.W;
+        const int y = pix % q.H;
+        const int n = pix / q.H;
+        const ColOf<float, W> v = pool_act_adjoint_at<W>(gy, splits, slab, idx, ypool, C, cq * W, n, y, x, q);
+        chain_store_col<HF_WT_ELEM>(ga + (size_t)r * C + cq * W, v);
+#pragma unroll
+        for (int k = 0; k < W; ++k) acc[k] += (double)v.e[k];
+      }
+#pragma unroll
+      for (int k = 0; k < W; ++k) red[(ty * cols + tx) * W + k] = acc[k];
+    }
+    __syncthreads();
+    if (ty == 0 && cq < CQ) {
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        double sum = 0.0;
+        for (unsigned t = 0; t < G; ++t) sum += red[(t * cols + tx) * W + k];
+        const float f = (float)sum;
+        chain_store<HF_WT_ELEM>(&gb[(size_t)blockIdx.x * C + cq * W + k], f);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------
 // Classifier head of the GGN product in one launch:
 //   Jv   = t_feat W^T + feat V_W^T + v_b          tangent of the logits        [B, K]
 //   HJv  = scale * p * (Jv - <p, Jv>)             softmax-CE Hessian, row-wise [B, K]
@@ -334,6 +491,84 @@ int hf_maxpool_adjoint_nhwc(void* g, const void* gy_a, int a_splits, int64_t a_s
                      (hipStream_t)stream, (float*)g, (const float*)gy_a, a_splits, (long long)a_slab,
                      (const float*)gy_b, b_splits, (long long)b_slab, (const int*)idx, (unsigned)total,
                      (unsigned)c, q);
+  return (int)hipGetLastError();
+}
+
+int hf_pool_act_tangent_nhwc(void* out, int64_t out_ld, const void* slabs, int splits, int64_t slab_stride,
+                             const void* v_b, const void* idx, const void* y_pool, int relu, int64_t n, int64_t h,
+                             int64_t w, int64_t oh, int64_t ow, int64_t c, int dtype, void* stream) {
+  if (dtype != HF_F32 || !out || !slabs || !idx || (relu && !y_pool)) return HF_ERR_ARG;
+  if (n < 1 || h < 1 || w < 1 || oh < 1 || ow < 1 || c < 1) return HF_ERR_ARG;
+  if (splits < 1 || splits > HF_POOL_ACT_MAX_SPLITS) return HF_ERR_ARG;
+  if (out_ld == 0) out_ld = c;
+  if (out_ld < c) return HF_ERR_ARG;
+  // (every factor below 2^31 first: the products cannot wrap)
+  const int64_t lim = 1LL << 31;
+  if (n >= lim || h >= lim || w >= lim || oh >= lim || ow >= lim || c >= lim || out_ld >= lim) return HF_ERR_ARG;
+  if (h * w >= lim || oh * ow >= lim || n * (h * w) >= lim || n * (oh * ow) >= lim) return HF_ERR_ARG;
+  const int64_t full = n * h * w * c, total = n * oh * ow * c;
+  if (full >= lim || total >= lim || n * oh * ow * out_ld >= lim) return HF_ERR_ARG;
+  if (splits > 1 && slab_stride < full) return HF_ERR_ARG;  // (slabs would overlap)
+  const float* yp = relu ? (const float*)y_pool : nullptr;
+  const bool quad = c % 4 == 0 && out_ld % 4 == 0 && al16(out) && al16(idx) && (!yp || al16(yp));
+  const unsigned cq = (unsigned)(quad ? c / 4 : c), items = (unsigned)(total / (quad ? 4 : 1));
+#define HF_PAT(W)                                                                                                  \
+  hipLaunchKernelGGL((k_pool_act_tangent<W>), dim3((items + HB - 1) / HB), dim3(HB), 0, (hipStream_t)stream,      \
+                     (float*)out, (const float*)slabs, splits, (long long)slab_stride, (const float*)v_b,         \
+                     (const int*)idx, yp, items, cq, (unsigned)out_ld, (unsigned)(oh * ow), (unsigned)(h * w))
+  if (quad) HF_PAT(4);
+  else HF_PAT(1);
+#undef HF_PAT
+  return (int)hipGetLastError();
+}
+
+int hf_pool_act_adjoint_nhwc(void* ga, void* gb, int row_blocks, const void* gy, int gy_splits, int64_t gy_slab,
+                             const void* idx, const void* y_pool, int relu, int64_t n, int64_t h, int64_t w,
+                             int64_t oh, int64_t ow, int64_t c, int64_t kh, int64_t kw, int64_t stride_h,
+                             int64_t stride_w, int64_t pad_h, int64_t pad_w, int dtype, void* stream) {
+  if (dtype != HF_F32 || !ga || !gy || !idx || (relu && !y_pool)) return HF_ERR_ARG;
+  if (n < 1 || h < 1 || w < 1 || oh < 1 || ow < 1 || c < 1) return HF_ERR_ARG;
+  if (kh < 1 || kw < 1 || stride_h < 1 || stride_w < 1 || pad_h < 0 || pad_w < 0) return HF_ERR_ARG;
+  if (gy_splits < 1 || gy_splits > HF_POOL_ACT_MAX_SPLITS) return HF_ERR_ARG;
+  const int64_t lim = 1LL << 31;
+  if (n >= lim || h >= lim || w >= lim || oh >= lim || ow >= lim || c >= lim) return HF_ERR_ARG;
+  if (kh >= lim || kw >= lim || stride_h >= lim || stride_w >= lim || pad_h >= lim || pad_w >= lim) return HF_ERR_ARG;
+  // the pooled extent of a max-pool without dilation / ceil_mode
+  if (h + 2 * pad_h < kh || w + 2 * pad_w < kw) return HF_ERR_ARG;
+  if (oh != (h + 2 * pad_h - kh) / stride_h + 1 || ow != (w + 2 * pad_w - kw) / stride_w + 1) return HF_ERR_ARG;
+  if (h * w >= lim || oh * ow >= lim || n * (h * w) >= lim || n * (oh * ow) >= lim) return HF_ERR_ARG;
+  const int64_t rows = n * h * w, full = rows * c, pooled = n * oh * ow * c;
+  if (full >= lim || pooled >= lim) return HF_ERR_ARG;
+  if (gy_splits > 1 && gy_slab < pooled) return HF_ERR_ARG;  // (slabs would overlap)
+  int64_t per = 0;
+  if (gb) {
+    if (row_blocks < 1) return HF_ERR_ARG;
+    per = (rows + row_blocks - 1) / row_blocks;
+    if ((int64_t)(row_blocks - 1) * per >= rows) return HF_ERR_ARG;  // an empty share
+  }
+  const float* yp = relu ? (const float*)y_pool : nullptr;
+  const bool quad = c % 4 == 0 && al16(ga) && al16(gy) && al16(idx) && (!yp || al16(yp)) &&
+                    (gy_splits == 1 || gy_slab % 4 == 0);
+  const unsigned cq = (unsigned)(quad ? c / 4 : c);
+  PoolGeo q{(int)h, (int)w, (int)oh, (int)ow, (int)kh, (int)kw, (int)stride_h, (int)stride_w, (int)pad_h, (int)pad_w};
+  hipStream_t s = (hipStream_t)stream;
+  if (gb) {
+#define HF_PAA(W)                                                                                                  \
+  hipLaunchKernelGGL((k_pool_act_adjoint_rows<W>), dim3((unsigned)row_blocks), dim3(HB), 0, s, (float*)ga,        \
+                     (float*)gb, (const float*)gy, gy_splits, (long long)gy_slab, (const int*)idx, yp,            \
+                     (unsigned)rows, (unsigned)per, cq, q)
+    if (quad) HF_PAA(4);
+    else HF_PAA(1);
+#undef HF_PAA
+  } else {
+    const unsigned items = (unsigned)(rows * cq);
+#define HF_PAE(W)                                                                                                  \
+  hipLaunchKernelGGL((k_pool_act_adjoint<W>), dim3((items + HB - 1) / HB), dim3(HB), 0, s, (float*)ga,            \
+                     (const float*)gy, gy_splits, (long long)gy_slab, (const int*)idx, yp, items, cq, q)
+    if (quad) HF_PAE(4);
+    else HF_PAE(1);
+#undef HF_PAE
+  }
   return (int)hipGetLastError();
 }
 

@@ -88,6 +88,9 @@ class _Buffers:
             self.pool_out = nhwc(self.pool_out.shape)
         for u in self.units:
             u.a, u.y = nhwc(u.a.shape), nhwc(u.y.shape)
+            if u.pool is not None:  # (plain stack) the pooled map -- what the consumer reads -- and the windows' positions
+                u.yp = nhwc(u.rp.shape)
+                u.pidx = torch.empty(tuple(u.yp.permute(0, 2, 3, 1).shape), dtype=torch.int32, device=dev)
             if u.train:
                 u.rstd_version = None  # (u.rstd: batch statistics -- recorded by the model's pass or the own one's)
             elif u.bn is not None:
@@ -95,7 +98,8 @@ class _Buffers:
                 u.rstd_version = u.bn.running_var._version
         tails = {id(c[-1]): c[0] for c, _, _ in self.blocks}
         for u in self.units:  # the convolution's input IS its producer's output buffer
-            u.x = self.x_in if u.src == "input" else self.pool_out if u.src == "pool" else u.src.y
+            u.x = (self.x_in if u.src == "input" else self.pool_out if u.src == "pool"
+                   else u.src.yp if u.src.pool is not None else u.src.y)
             if u.res_unit is not None:
                 u.res = u.res_unit.y
             elif u.res_identity:
@@ -185,7 +189,8 @@ class _Buffers:
             u.split = adjoint_split_ok(u.train, u.rb, self.hessian, u.a.numel() * 4, self.DEFER_MAX_BYTES, enabled)
             u.defer = not u.dead and defer_sums_ok(u.train, u.rb, self.hessian, u.bn is not None and u.pg is not None,
                                                    u.pb is not None, u.a.numel() * 4, self.DEFER_MAX_BYTES, enabled)
-            if u.defer and u.g is None:  # (deferred sums are taken of the STORED g, needed by a residual branch or not)
+            # (deferred sums are taken of the STORED g, needed by a residual branch or not; a pooled unit's is its ga)
+            if u.defer and u.g is None and u.pool is None:
                 u.g = torch.empty_like(u.a)
             # (Hessian: the scale's second-order term arrives as `rb` more partial rows for hf_pack_ex to add)
             u.gw_rows = u.rb * (2 if (self.hessian and u.bn is not None) else 1)
@@ -226,9 +231,15 @@ class _Buffers:
         # where each unit's output goes besides its own dense buffer: the [t_x | x] operand of its
         # consumer -- the tangent into the first half, the value (forward pass) into the second
         for u in self.units:
-            xc = xcats.get(id(u.y))
+            xc = xcats.get(id(u.yp if u.pool is not None else u.y))
             c = u.y.shape[1]
-            if xc is not None:
+            if u.pool is not None:
+                # the pooled tangent goes straight into the consumer's operand (no full-resolution tangent map); the
+                # value half is the pool launch's second output, not the bias / ReLU launch's
+                if xc is None:
+                    raise _Unsupported(f"{u.name}: nothing consumes the pooled map")
+                u.tout, u.tout_ld, u.yout2, u.pool_out2 = xc[:, :c], 2 * c, None, xc[:, c:]
+            elif xc is not None:
                 u.tout, u.tout_ld, u.yout2 = xc[:, :c], 2 * c, xc[:, c:]
             else:
                 u.tout, u.tout_ld, u.yout2 = torch.empty_like(u.y), 0, None
@@ -275,7 +286,7 @@ class _Buffers:
             bn = u.bn is not None and u.pg is not None
             u.sums_slot = i
             problems.append(dict(gw=u.gw.data_ptr() if bn else None, gb=u.gb.data_ptr() if u.pb is not None else None,
-                                 g=u.g.data_ptr(), x=u.a.data_ptr() if bn else None,
+                                 g=(u.ga if u.pool is not None else u.g).data_ptr(), x=u.a.data_ptr() if bn else None,
                                  mean=u.mean.data_ptr() if bn else None, rstd=u.rstd.data_ptr() if bn else None,
                                  rows=u.rows, c=u.cout, row_blocks=u.rb))
         self._sums_tab, _blocks = sums_table(problems)

@@ -59,6 +59,8 @@ class _Unit:
         self.src = None           # what the convolution reads: "input", "pool" or the producing unit
         self.dead = False         # frozen, behind frozen layers only: no tangent, no cotangent (topology._mark_dead_prefix)
         self.no_dgrad = False     # a live unit whose input carries no tangent: its data gradient is not needed
+        self.pool = None          # plain stack: (kh, kw, sh, sw, ph, pw) of the MaxPool2d behind the unit (its ReLU)
+        self.rp = None            # ... and the pooled map the model's forward pass recorded
 
     # per-channel affine map behind the convolution: BatchNorm statistics / scale / shift, or a bias
     @property

@@ -185,7 +185,7 @@ class FusedGGNEngine(_Launcher, _Topology, _Buffers, _Forward, _TangentSweep, _A
             if self.hessian:
                 self.gradient()  # the first-order cotangents the Hessian products read, at the same point
         for u in self.units:  # the model's own activations were only needed up to here
-            u.rx = u.ry = u.ra = None
+            u.rx = u.ry = u.ra = u.rp = None
             u.rec_stats = None
         self._rec_pool = None
         if self.loss_spec is not None:

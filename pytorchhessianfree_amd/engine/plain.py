@@ -4,7 +4,7 @@ import torch
 from torch import nn
 
 from .. import _lib
-from .common import _Unit, _Unsupported, _cl, _same
+from .common import _Unit, _Unsupported, _cl, _pair, _same
 from .core import FusedGGNEngine
 
 
@@ -14,10 +14,18 @@ class PlainStackEngine(FusedGGNEngine):
     examples (examples/example_utils.py:59-83, BASELINE.json configs[3]).  Per layer: tangent
     convolution -> bias tangent + ReLU mask (into the next layer's operand) / masked slab sum + bias
     gradient -> data + weight gradient; the head (average pool, loss Hessian, broadcast) is ONE launch
-    (``hf_pool_ce_head``).  3 launches per layer and product, bitwise repeatable."""
+    (``hf_pool_ce_head``).  4 launches per layer and product, bitwise repeatable.
+
+    ``nn.MaxPool2d`` layers between the convolutions (ConvPool-CNN-C, Network-in-Network: ``conv [ReLU] MaxPool2d``,
+    dilation 1, no ``ceil_mode``, any unit but the last): ReLU masks and pool positions are piecewise constant, so the
+    pooled unit's bias / ReLU / pool is ONE launch per direction -- ``hf_pool_act_tangent_nhwc`` gathers the tangent
+    convolution's slabs at the windows' positions, masks by the POOLED map and writes into the consumer's operand (no
+    full-resolution tangent map), ``hf_pool_act_adjoint_nhwc`` gathers the consumer's data-gradient slabs into the
+    full-resolution ``ga`` with the bias sums.  The forward pass adds ``hf_maxpool_forward_nhwc`` (pooled map, its copy
+    in the consumer's ``x`` half, positions).  Everything that reads ``u.ga`` / ``u.gb`` / ``u.x`` is unchanged."""
 
     mode = ("fused curvature engine (plain conv-ReLU stack): own deterministic convolutions (split-K slabs summed "
-            "by the consumer kernel), bias / ReLU fused, 4 launches per layer")
+            "by the consumer kernel), bias / ReLU / max-pool fused, 4 launches per layer")
     # Hessian products (optimizer.py:450-455) by forward-over-reverse on the same kernels: the tangent
     # sweep, then the TANGENT OF THE BACKWARD SWEEP -- per layer, besides the GGN's conv_D(g', W) and
     # conv_W(x, g'), the two terms that carry the network's own curvature, conv_D(g, V) and conv_W(t_x, g)
@@ -70,11 +78,32 @@ class PlainStackEngine(FusedGGNEngine):
                 u.pg = None
                 u.src, prev, cur = prev, u, y
                 units.append(u)
+            elif type(m) is nn.MaxPool2d:
+                # directly behind a unit (its ReLU, if it has one): the unit's bias / ReLU and the pool are one launch
+                # per sweep direction (hf_pool_act_*_nhwc)
+                where = f"MaxPool2d behind {units[-1].name}" if units else "MaxPool2d in front of the first convolution"
+                if not units or units[-1].pool is not None:
+                    raise _Unsupported(f"{where}: a pool must directly follow a convolution (and its ReLU)")
+                if _pair(m.dilation) != [1, 1] or m.ceil_mode or m.return_indices:
+                    raise _Unsupported(f"{where}: dilation / ceil_mode / return_indices are not covered")
+                px, py = io(m)
+                if not _same(px, cur):
+                    raise _Unsupported(f"{where}: its recorded input is not the unit's output")
+                u = units[-1]
+                u.pool = tuple(_pair(m.kernel_size) + _pair(m.stride if m.stride is not None else m.kernel_size)
+                               + _pair(m.padding))
+                u.rp, cur = py, py
             elif isinstance(m, nn.AdaptiveAvgPool2d) and m.output_size in (1, (1, 1)):
                 px, py = io(m)
                 if not units or not _same(px, cur):
                     raise _Unsupported("the pooling layer does not follow the last convolution")
+                if units[-1].pool is not None:
+                    raise _Unsupported(f"MaxPool2d behind {units[-1].name}: a pool between the last convolution and the "
+                                       "global average pool is not covered")
                 pooled = py
+            elif type(m) is nn.ReLU and units and units[-1].pool is not None:
+                raise _Unsupported(f"ReLU behind the MaxPool2d of {units[-1].name}: the activation must stand in front of "
+                                   "the pool")
             else:
                 raise _Unsupported(f"unsupported layer {type(m).__name__}")
             i += 1
@@ -130,11 +159,51 @@ class PlainStackEngine(FusedGGNEngine):
             if not (carried and u is first):
                 self._conv_forward(u)
             self._bn_forward(u, u.sF)
+            if u.pool is not None:
+                # the pooled map, its copy in the x half of the consumer's [t_x | x] operand, the positions
+                c = u.y.shape[1]
+                self._launch("hf_maxpool_forward_nhwc", u.yp, u.pool_out2, 2 * c, u.pidx, u.y, *self._pool_dims(u), *u.pool)
         torch.mean(self.tail.y, dim=(2, 3), out=self.logits)
         if getattr(self, "loss_spec", None) is not None:
             self._loss_head()
         self._at = "own"
         return self.logits
+
+    def _load_recorded(self, outputs):
+        FusedGGNEngine._load_recorded(self, outputs)
+        for u in self.units:
+            if u.pool is not None:  # the model's pooled map, and the positions of ITS windows (as the stem's, forward.py)
+                kh, kw, sh, sw, ph, pw = u.pool
+                _, idx = torch.nn.functional.max_pool2d(u.ry, (kh, kw), (sh, sw), (ph, pw), return_indices=True)
+                # (ATen: flat y*w + x inside the (n, c) plane -- what hf_maxpool_forward_nhwc writes)
+                u.pidx.copy_(idx.permute(0, 2, 3, 1))
+                u.yp.copy_(u.rp)
+                u.pool_out2.copy_(u.rp)
+
+    # ---- pooled units: bias / ReLU / max-pool in one launch per direction ---------------------------
+    @staticmethod
+    def _pool_dims(u):
+        """(n, h, w, oh, ow, c) of a pooled unit."""
+        n, c, h, w = u.y.shape
+        return n, h, w, u.yp.shape[2], u.yp.shape[3], c
+
+    def _pool_tangent(self, u, v):
+        """t_pool = (y_pool > 0) * (t_a[idx] + v_b) from the tangent convolution's slabs into the consumer's operand."""
+        vb = self._param_slice(v, u.pb, u.cout)
+        self._launch("hf_pool_act_tangent_nhwc", u.tout, u.tout_ld, u.tbuf, u.sT, u.tbuf.shape[1], vb, u.pidx, u.yp,
+                     1 if u.relu else 0, *self._pool_dims(u))
+
+    def _pool_adjoint(self, u, srcs, ga):
+        """g_a at full resolution from the consumer's data-gradient slabs; the bias sums as partial rows -- or, where
+        the unit's sums are deferred, left to the sums table (which reads this ``ga``)."""
+        self._extras_wait(srcs)
+        (gy, splits, slab), = srcs
+        defer = u.defer and ga is u.ga
+        gb = None if (defer or u.pb is None) else u.gb
+        self._launch("hf_pool_act_adjoint_nhwc", ga, gb, u.rb, gy, splits, slab, u.pidx, u.yp, 1 if u.relu else 0,
+                     *self._pool_dims(u), *u.pool)
+        if defer:
+            self._sums_pending.add(u.sums_slot)
 
     # ---- product ------------------------------------------------------------------------------
     def _tangent_sweep(self, v):
@@ -156,7 +225,10 @@ class PlainStackEngine(FusedGGNEngine):
                     self._conv_slabs(0, u.tbuf, u.cols, vw, u.geo, u.sT)
             else:
                 self._conv_slabs(0, u.tbuf, u.xcat, u.wcat, self._tgeo(u), u.sT)
-            self._bn_tangent(u, v, None, 0)
+            if u.pool is not None:
+                self._pool_tangent(u, v)
+            else:
+                self._bn_tangent(u, v, None, 0)
 
     def _adjoint_sweep(self, g_last, first_order=False):
         """``first_order``: the gradient's sweep (cotangents kept in ``ga1`` for later Hessian products);
@@ -168,7 +240,10 @@ class PlainStackEngine(FusedGGNEngine):
             if u.dead:  # (nobody needs a cotangent behind the first trainable layer)
                 break
             ga = u.ga1 if (self.hessian and first_order) else u.ga
-            self._bn_adjoint(u, srcs, ga)
+            if u.pool is not None:
+                self._pool_adjoint(u, srcs, ga)
+            else:
+                self._bn_adjoint(u, srcs, ga)
             if second and not u.im2col and not u.first and u.sD:
                 # (two launches of two problems each; four in one grouped launch ran 3x slower -- with four
                 # by-value problem descriptions hipcc spills them to scratch memory.  The second one -- conv_D(g, V),

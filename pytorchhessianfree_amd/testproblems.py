@@ -132,6 +132,49 @@ class AllCNNC(nn.Module):
         return torch.flatten(self.net(x), -3)  # also for one unbatched sample [C,H,W]
 
 
+class ConvPoolCNNC(nn.Module):
+    """ConvPool-CNN-C (Springenberg et al., "Striving for Simplicity", table 2): the net All-CNN-C was derived from, with
+    a 3x3 / stride-2 max-pool where All-CNN-C has a strided convolution.  Dropout as in ``AllCNNC``."""
+
+    def __init__(self, num_classes=100):
+        super().__init__()
+
+        def c(i, o, k, p=0):
+            return [nn.Conv2d(i, o, k, 1, p), nn.ReLU()]
+
+        self.net = nn.Sequential(
+            nn.Dropout(0.2),
+            *c(3, 96, 3, 1), *c(96, 96, 3, 1), *c(96, 96, 3, 1), nn.MaxPool2d(3, 2),
+            nn.Dropout(0.5),
+            *c(96, 192, 3, 1), *c(192, 192, 3, 1), *c(192, 192, 3, 1), nn.MaxPool2d(3, 2),
+            nn.Dropout(0.5),
+            *c(192, 192, 3, 0), *c(192, 192, 1), *c(192, num_classes, 1),
+            nn.AdaptiveAvgPool2d((1, 1)),
+        )
+
+    def forward(self, x):
+        return torch.flatten(self.net(x), -3)
+
+
+class ConvPoolSmall(nn.Module):
+    """The smallest pooled stack that takes every path of the pooled-layer kernels: conv3(3->8, pad 1) + ReLU +
+    MaxPool(3, 2) (the im2col'd first layer pooled, overlapping windows, 12x12 -> 5x5: an odd map), conv3(8->8, pad 1) +
+    ReLU + MaxPool(2, 2) (disjoint windows that leave the last row and column out, 5x5 -> 2x2), conv1(8->classes), global
+    average pool."""
+
+    def __init__(self, num_classes=4):
+        super().__init__()
+        self.net = nn.Sequential(
+            nn.Conv2d(3, 8, 3, 1, 1), nn.ReLU(), nn.MaxPool2d(3, 2),
+            nn.Conv2d(8, 8, 3, 1, 1), nn.ReLU(), nn.MaxPool2d(2, 2),
+            nn.Conv2d(8, num_classes, 1),
+            nn.AdaptiveAvgPool2d((1, 1)),
+        )
+
+    def forward(self, x):
+        return torch.flatten(self.net(x), -3)
+
+
 def l2_regularized(loss_function, model, l2=5e-4):
     """``loss + 0.5 * l2 * sum ||W||^2`` over the WEIGHTS (no biases): the regularised
     loss the reference's All-CNN-C example trains (examples/example_utils.py:77-81 adds
@@ -238,6 +281,25 @@ def allcnnc_cifar100(batch_size=32, seed=0, device="cpu", data_seed=None):
     g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
     inputs = torch.rand(batch_size, 3, 32, 32, generator=g)
     targets = torch.randint(0, 100, (batch_size,), generator=g)
+    return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
+
+
+def convpoolcnnc_cifar100(batch_size=32, seed=0, device="cpu", data_seed=None):
+    torch.manual_seed(seed)
+    model = ConvPoolCNNC(100).eval()
+    g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
+    inputs = torch.rand(batch_size, 3, 32, 32, generator=g)
+    targets = torch.randint(0, 100, (batch_size,), generator=g)
+    return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
+
+
+def convpool_small(batch_size=2, seed=0, device="cpu", data_seed=None):
+    """``ConvPoolSmall`` in eval mode; inputs U[0,1) [B,3,12,12], 4 classes, CE-mean."""
+    torch.manual_seed(seed)
+    model = ConvPoolSmall(4).eval()
+    g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
+    inputs = torch.rand(batch_size, 3, 12, 12, generator=g)
+    targets = torch.randint(0, 4, (batch_size,), generator=g)
     return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
 
 

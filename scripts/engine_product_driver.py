@@ -203,6 +203,19 @@ class Recorder:
         return [("k_maxpool_adjoint", po * (1 + sa + (sb if b else 0)), 4 * n * h * w * c, 0.0)]
 
     @staticmethod
+    def _cost_hf_pool_act_tangent_nhwc(out, ld, slabs, splits, slab, vb, idx, yp, relu, n, h, w, oh, ow, c, dtype, stream):
+        tot = 4 * n * oh * ow * c
+        # idx + the pooled map (mask) + one gathered element per slab (a 32-B sector at least: counted as 2)
+        return [("k_pool_act_tangent", tot * (1 + (1 if relu else 0) + 2 * splits), tot, 1.0 * n * oh * ow * c * splits)]
+
+    @staticmethod
+    def _cost_hf_pool_act_adjoint_nhwc(ga, gb, rb, gy, splits, slab, idx, yp, relu, n, h, w, oh, ow, c, kh, kw, sh, sw, ph,
+                                       pw, dtype, stream):
+        po = 4 * n * oh * ow * c
+        name = "k_pool_act_adjoint_rows" if gb else "k_pool_act_adjoint<"
+        return [(name, po * (1 + (1 if relu else 0) + splits), 4 * n * h * w * c, 1.0 * n * oh * ow * c * splits)]
+
+    @staticmethod
     def _cost_hf_pool_ce_head(g, jv, t, p, scale, n, hw, k, dtype, stream):
         tot = 4 * n * hw * k
         return [("k_pool_ce_head", tot + 4 * n * k, tot, 0.0)]
@@ -223,7 +236,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--products", type=int, default=20)
     ap.add_argument("--out", default="")
-    ap.add_argument("--workload", default="resnet18", choices=["resnet18", "allcnnc", "resnet50"])
+    ap.add_argument("--workload", default="resnet18", choices=["resnet18", "allcnnc", "convpoolcnnc", "resnet50"])
     ap.add_argument("--curvature", default="ggn", choices=["ggn", "hessian"])
     ap.add_argument("--bn", default="eval", choices=["eval", "train"])
     ap.add_argument("--freeze", default="", choices=["", "stem+layer1"])
@@ -234,6 +247,8 @@ def main():
         model, (x, t), lossf = tp.resnet18_mnist(batch_size=32, device=dev, data_seed=tp.RESNET18_B32_SEPARATED_SEEDS[0])
     elif args.workload == "allcnnc":
         model, (x, t), lossf = tp.allcnnc_cifar100(batch_size=32, device=dev)
+    elif args.workload == "convpoolcnnc":
+        model, (x, t), lossf = tp.convpoolcnnc_cifar100(batch_size=32, device=dev)
     else:
         model, (x, t), lossf = tp.resnet50_small_images(batch_size=32, device=dev)
     if args.bn == "train":
