@@ -375,6 +375,11 @@ class _Buffers:
                                               padding=tuple(s.conv.padding), stride=tuple(s.conv.stride))
             s.cols.copy_(cols.transpose(1, 2))
             s.cols_pad[:, :, :s.jcols].copy_(s.cols)
+        elif getattr(s, "xcat", None) is not None:
+            # a first layer that reads the input itself (a plain stack with 4 or more input channels): the x half of its
+            # [t_x | x] operand has no producer unit to fill it -- the tangent convolution's conv(x, v_W) reads it here
+            # (the t_x half stays zero: the input carries no tangent)
+            s.xcat[:, self.x_in.shape[1]:].copy_(self.x_in)
         for u in self.units:  # eval-mode statistics are constants -- unless somebody retrained them
             if u.bn is not None and not u.train and u.bn.running_var._version != u.rstd_version:
                 torch.rsqrt(u.bn.running_var + u.bn.eps, out=u.rstd)

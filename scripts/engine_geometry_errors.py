@@ -1,0 +1,84 @@
+"""Stock fp32 autograd and the conv engines against the float64 reference on the cases of ``tests/geometry_nets.py``: one
+JSON line per (series, case, quantity) with the error of every parameter tensor -- the record the bounds of
+``tests/test_engine_geometry_gpu.py`` are taken from (3x the worst ``stock_fp32`` figure per quantity, one significant
+digit, rounded up; the last lines printed list them).
+
+    python scripts/engine_geometry_errors.py --out profiles/rNN_engine_geometry.jsonl
+
+A case the engine gets wrong is recorded (``"failed"``) and the run goes on; any other error ends it."""
+
+import argparse
+import json
+import math
+import os
+import sys
+import time
+import traceback
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import torch  # noqa: E402
+
+import pytorchhessianfree_amd  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--series", default="all", choices=["all", "stock_fp32", "engine"])
+    args = ap.parse_args()
+    pytorchhessianfree_amd.configure()  # (as tests/conftest.py: the accurate MIOpen solvers for the stock side)
+    import geometry_nets as gn
+    import test_engine_geometry_gpu as tests
+
+    fh = open(args.out, "w")
+    worst = {}
+
+    def emit(series, case, quantity, errs, **kw):
+        top = max(errs.values()) if errs else None
+        fh.write(json.dumps({"series": series, "case": case, "quantity": quantity, "worst": top, "errors": errs, **kw}) + "\n")
+        fh.flush()
+        print(series, case, quantity, "failed" if top is None else f"{top:.2e}", flush=True)
+        if series == "stock_fp32" and top is not None:
+            worst[quantity] = max(worst.get(quantity, 0.0), top)
+
+    def run(series, case, what, fn, prefix=""):
+        t0 = time.time()
+        try:
+            res = fn()
+        except AssertionError:
+            emit(series, case, what, {}, failed=traceback.format_exc()[-1500:].replace(ROOT + os.sep, ""))
+            return
+        for quantity, errs in res.items():
+            if isinstance(errs, dict):
+                emit(series, case, prefix + quantity, errs, seconds=round(time.time() - t0, 2))
+
+    def stock_train(case):
+        res = gn.stock_fp32_errors(case, "cuda", train=True)
+        return {"ggn_train": res["ggn"], "hessian_train": res["hessian"]}
+
+    for case in gn.CASES if args.series in ("all", "stock_fp32") else []:
+        run("stock_fp32", case, "stock", lambda: gn.stock_fp32_errors(case, "cuda"))
+        if case in gn.TRAIN_CASES:
+            run("stock_fp32", case, "stock_train", lambda: stock_train(case))
+    for case in gn.CASES if args.series in ("all", "engine") else []:
+        run("engine", case, "forward", lambda: tests.forward_errors(case))
+        run("engine", case, "gradient", lambda: tests.gradient_errors(case))
+        run("engine", case, "ggn", lambda: tests.product_errors(case))
+        run("engine", case, "hessian", lambda: tests.product_errors(case, hessian=True))
+        if case in gn.TRAIN_CASES:
+            run("engine", case, "ggn_train", lambda: tests.product_errors(case, train=True))
+            run("engine", case, "hessian_train", lambda: tests.product_errors(case, hessian=True, train=True))
+        for batched, prefix in (("0", "per_sample/"), ("1", "batched/")):
+            os.environ["HF_DIAG_EF_BATCHED"] = batched  # (read when the engine is built)
+            run("engine", case, "diag_ef", lambda: tests.diag_errors(case), prefix=prefix)
+        os.environ.pop("HF_DIAG_EF_BATCHED")
+    torch.cuda.synchronize()
+    for quantity, top in worst.items():
+        e = math.floor(math.log10(3 * top))
+        print(f"bound {quantity}: 3 x {top:.3e} -> {math.ceil(3 * top / 10 ** e - 1e-9)}e{e}")
+
+
+if __name__ == "__main__":
+    main()

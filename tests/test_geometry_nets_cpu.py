@@ -1,0 +1,216 @@
+"""CPU: the cases of ``geometry_nets.py`` reach what they are named for, and its float64 reference is one -- without a
+GPU.
+
+Per case the map sizes, the live-tap masks (``common._live_taps``) and the BatchNorm adjoint's row-block counts equal the
+literals of ``geometry_nets.GEOMETRY`` (the row-block rule is restated there: the engine's own ``u.rb`` is compared with
+the same literals by the GPU tests); the library's planner (host arithmetic) takes every layer in all three directions;
+the fp32 and the float64 forward pass take the same ReLU decisions (what lets the GPU tests cap the replayed decisions at
+a handful); the reference's GGN product is ``J^T H J v`` of an explicitly built Jacobian, symmetric, its diagonal Fisher
+the diagonal of the summed outer products; and ``row_map`` / ``col_map`` are each other's transpose, told apart without
+the transposition."""
+
+import copy
+
+import geometry_nets as gn
+import pytest
+import torch
+from torch import nn
+
+from pytorchhessianfree_amd import _lib
+from pytorchhessianfree_amd.engine.common import _live_taps
+
+POOLED = {"nonsquare_odd": (6, 3), "asym_stride": (4, 3), "row_map": (2, 6), "col_map": (6, 2), "batch_one": (4, 4),
+          "wide_rows": (6, 5), "stem7": (4, 3), "plain_rect": (3, 9), "plain_quads_in": (2, 4)}
+IM2COL_COLUMNS = {"nonsquare_odd": 9, "asym_stride": 27, "row_map": 9, "col_map": 9, "batch_one": 9, "wide_rows": 9,
+                  "stem7": 147, "plain_rect": 9, "plain_quads_in": None}  # (4 input channels: no im2col)
+
+
+def _layers(case):
+    model, batches = gn.make(case)
+    x = batches[0][0]
+    mods = dict(model.named_modules())
+    return model, x, [(mods[name], name, h, w, r, s, st, pd, oh, ow)
+                      for name, h, w, r, s, st, pd, oh, ow in gn.conv_geometry(model, x)]
+
+
+def test_the_case_list_is_the_issues():
+    assert gn.CASES == list(gn.GEOMETRY) and len(gn.CASES) == 9
+    assert {"row_map", "col_map"} <= set(gn.CASES)  # (each alone is symmetric to a swap of the other kind)
+    assert gn.RESNETS["row_map"]["x"] == (5, 1, 4, 12) and gn.RESNETS["col_map"]["x"] == (5, 1, 12, 4)
+    assert {k: v for k, v in gn.RESNETS["row_map"].items() if k != "x"} == {
+        k: v for k, v in gn.RESNETS["col_map"].items() if k != "x"}
+
+
+@pytest.mark.parametrize("case", gn.CASES)
+def test_map_sizes_live_taps_and_row_blocks(case):
+    model, x, layers = _layers(case)
+    n = x.shape[0]
+    got = [(name, (h, w), (oh, ow), _live_taps(h, w, r, s, st, pd), gn.adjoint_row_blocks(n * oh * ow, m.out_channels))
+           for m, name, h, w, r, s, st, pd, oh, ow in layers]
+    assert got == gn.GEOMETRY[case]
+    # the map behind the (first) max-pool, and the first layer's im2col
+    pools = [m for m in model.modules() if isinstance(m, nn.MaxPool2d)]
+    assert len(pools) == 1
+    seen = []
+    hook = pools[0].register_forward_hook(lambda m, i, o: seen.append(tuple(o.shape[2:])))
+    with torch.no_grad():
+        out = model(x)
+    hook.remove()
+    assert seen == [POOLED[case]]
+    first = layers[0][0]
+    cols = first.in_channels * first.kernel_size[0] * first.kernel_size[1]
+    assert (cols if (case in gn.RESNETS or first.in_channels < 4) else None) == IM2COL_COLUMNS[case]
+    classes = (gn.RESNETS.get(case) or gn.STACKS[case])["classes"]
+    assert tuple(out.shape) == (n, classes)
+    # what the table names, in the model's own terms
+    if case == "asym_stride":
+        assert tuple(model.conv1.stride) == (1, 2) and tuple(model.maxpool.stride) == (2, 1)
+        assert tuple(model.layers[0].conv1.stride) == tuple(model.layers[0].downsample[0].stride) == (2, 1)
+        assert -(-cols // 4) * 4 == 28
+    if case == "plain_rect":
+        assert [tuple(m.kernel_size) for m, *_ in layers] == [(1, 3), (3, 1), (3, 3), (1, 1)]
+        assert tuple(pools[0].kernel_size) == (3, 2) and tuple(pools[0].stride) == (2, 1)
+
+
+@pytest.mark.parametrize("case", gn.CASES)
+def test_the_planner_accepts_every_layer_in_every_direction(case):
+    """``hf_conv2d_nhwc_plan`` as ``buffers._plan`` / ``_plan_stem`` ask it: direction 0 with ``c`` (forward) and ``2c``
+    (the ``[t_x | x]`` operand), 1 and 2; the im2col'd first layer as a 1x1 product over its columns (padded to a
+    multiple of 4 for the weight gradient)."""
+    plan = _lib.load().hf_conv2d_nhwc_plan
+    model, x, layers = _layers(case)
+    n = x.shape[0]
+    for i, (m, name, h, w, r, s, st, pd, oh, ow) in enumerate(layers):
+        c, k = m.in_channels, m.out_channels
+        if i == 0 and IM2COL_COLUMNS[case] is not None:
+            j = c * r * s
+            asked = [(0, n * oh * ow, 1, 1, j, k, 1, 1, 1, 1, 0, 0), (2, n * oh * ow, 1, 1, -(-j // 4) * 4, k, 1, 1, 1, 1, 0, 0)]
+        else:
+            asked = [(d, n, h, w, cc, k, r, s, st[0], st[1], pd[0], pd[1]) for d, cc in ((0, c), (0, 2 * c), (1, c), (2, c))]
+        for args in asked:
+            assert plan(*args, 0) >= 1, (name, args)
+
+
+def _differing_decisions(model, x):
+    a32 = gn.relu_inputs(copy.deepcopy(model), x)
+    a64 = gn.relu_inputs(copy.deepcopy(model).double(), x.double())
+    assert len(a32) == len(a64) > 0
+    return sum(int(((p > 0) != (q > 0)).sum()) for p, q in zip(a32, a64))
+
+
+@pytest.mark.parametrize("case", gn.CASES)
+def test_fp32_and_float64_take_the_same_relu_decisions(case):
+    for train in ([False, True] if case in gn.TRAIN_CASES else [False]):
+        model, batches = gn.make(case, train)
+        for x, _ in batches:
+            assert _differing_decisions(model, x) == 0, (case, train)
+
+
+def _flat_jacobian(model, x):
+    """d logits / d theta, ``[n * classes, P]``, in float64 by ``torch.autograd.functional.jacobian``."""
+    names = [n for n, p in model.named_parameters() if p.requires_grad]
+    params = tuple(dict(model.named_parameters())[n].detach() for n in names)
+
+    def fn(*ps):
+        return torch.func.functional_call(model, dict(zip(names, ps)), (x,)).reshape(-1)
+
+    jac = torch.autograd.functional.jacobian(fn, params)
+    return torch.cat([j.reshape(j.shape[0], -1) for j in jac], dim=1)
+
+
+@pytest.mark.parametrize("case", ["nonsquare_odd", "plain_rect"])
+def test_the_reference_is_the_explicit_ggn_symmetric_and_its_diagonal_the_summed_outer_products(case):
+    model, batches = gn.make(case)
+    x, t = batches[0]
+    ref = gn.Reference(model, x, t)
+    n = ref.gradient().numel()
+    J = _flat_jacobian(ref.model, ref.x)
+    H = torch.autograd.functional.hessian(lambda z: nn.functional.cross_entropy(z.view_as(ref.out), ref.t),
+                                          ref.out.detach().reshape(-1))
+    u, v = gn.probe(n, 1).double(), gn.probe(n, 2).double()
+    gv, gu = ref.ggn(v), ref.ggn(u)
+    want = J.t() @ (H @ (J @ v))
+    assert float((gv - want).abs().max() / want.abs().max()) < 1e-10
+    a, b = float(u @ gv), float(v @ gu)
+    assert abs(a - b) <= 1e-12 * abs(a)
+    # the gradient and the loss by the same Jacobian
+    dl = torch.autograd.grad(nn.functional.cross_entropy(z := ref.out.detach().clone().requires_grad_(True), ref.t), z)[0]
+    assert float((ref.gradient() - J.t() @ dl.reshape(-1)).abs().max() / ref.gradient().abs().max()) < 1e-10
+    # diagonal Fisher: single-sample passes (another route than the reference's batch pass), outer products summed
+    G = []
+    for i in range(x.shape[0]):
+        g = torch.autograd.grad(nn.functional.cross_entropy(ref.model(ref.x[i:i + 1]), ref.t[i:i + 1]), ref.params)
+        G.append(torch.cat([a.reshape(-1) for a in g]))
+    idx = torch.arange(0, n, 1 if n < 4000 else 7)  # (every entry of the small net; every 7th of the larger one)
+    outer = sum(torch.outer(g[idx], g[idx]) for g in G) / x.shape[0]
+    d = ref.diag_ef()
+    assert float((d[idx] - outer.diagonal()).abs().max() / d.abs().max()) < 1e-12
+    assert float(ref.loss()) > 0 and bool((d >= 0).all())
+
+
+def _transposed_twin():
+    """``col_map``'s net holding ``row_map``'s parameters with every kernel transposed, and ``row_map``'s input
+    transposed: the same function of the same numbers, with the two map axes exchanged."""
+    row, rb = gn.make("row_map")
+    col, _ = gn.make("col_map")
+    state = {k: (v.transpose(2, 3).contiguous() if v.dim() == 4 else v.clone()) for k, v in row.state_dict().items()}
+    col.load_state_dict(state)
+    for a, b in zip(row.modules(), col.modules()):
+        if isinstance(a, nn.BatchNorm2d):
+            b.eps = a.eps
+    x, t = rb[0]
+    return row, col, x, t
+
+
+def _transpose_kernels(vec, model):
+    out, off = [], 0
+    for p in (p for p in model.parameters() if p.requires_grad):
+        piece = vec[off:off + p.numel()].view_as(p)
+        out.append((piece.transpose(2, 3) if p.dim() == 4 else piece).reshape(-1))
+        off += p.numel()
+    return torch.cat(out)
+
+
+def test_row_map_and_col_map_are_transposes_and_the_reference_tells_them_apart():
+    row, col, x, t = _transposed_twin()
+    ref_r = gn.Reference(row, x, t)
+    ref_c = gn.Reference(col, x.transpose(2, 3).contiguous(), t)
+    assert tuple(ref_c.x.shape) == gn.RESNETS["col_map"]["x"]
+    n = ref_r.gradient().numel()
+    v = gn.probe(n, 3).double()
+    got = ref_c.ggn(_transpose_kernels(v, row))   # v in col_map's layout
+    want = _transpose_kernels(ref_r.ggn(v), row)  # row_map's product in col_map's layout
+    assert float((got - want).abs().max() / want.abs().max()) < 1e-12
+    assert abs(ref_r.loss() - ref_c.loss()) < 1e-13
+    # without the permutation the two products are far apart: a reference (or an engine) that exchanged the axes
+    # somewhere cannot pass for the other
+    plain = ref_c.ggn(v)
+    assert float((plain - ref_r.ggn(v)).abs().max() / want.abs().max()) > 1e-2
+    with pytest.raises(AssertionError, match="exactly zero"):  # (dead kernel ROWS of one are live in the other)
+        gn.per_tensor_errors(plain, ref_r.ggn(v), gn.named_sizes(row))
+
+
+def test_per_tensor_measure_sees_a_small_block_and_demands_exact_zeros():
+    sizes = [("big", 6), ("small", 2)]
+    want = torch.tensor([100.0, -50.0, 0.0, 3.0, 2.0, 1.0, 1e-6, -2e-6], dtype=torch.float64)
+    got = want.clone()
+    got[6] = 2e-6  # the small block wrong by half of its own size: 1e-8 of the whole vector's max-norm
+    errs = gn.per_tensor_errors(got, want, sizes)
+    assert errs["big"] == 0.0 and abs(errs["small"] - 0.5) < 1e-12
+    assert float((got - want).abs().max() / want.abs().max()) < 1.1e-8
+    got[2] = 1e-30
+    with pytest.raises(AssertionError, match="exactly zero"):
+        gn.per_tensor_errors(got, want, sizes)
+    assert gn.per_tensor_errors(torch.zeros(8), torch.zeros(8, dtype=torch.float64), sizes) == {"big": 0.0, "small": 0.0}
+
+
+def test_replayed_decisions_are_bounded():
+    """A replayed mask may differ from the float64 net's own in at most ``MAX_FLIPS`` entries, all next to zero."""
+    model, batches = gn.make("nonsquare_odd")
+    x, t = batches[0]
+    masks = gn.own_masks(copy.deepcopy(model).double(), x.double())
+    assert gn.Reference(model, x, t, masks=masks).flips == [0]
+    far = [m.clone() for m in masks]
+    far[1].view(-1)[0] = ~far[1].view(-1)[0]  # one decision the other way, at an input that is not next to zero
+    with pytest.raises(AssertionError, match="far from zero"):
+        gn.Reference(model, x, t, masks=far)
