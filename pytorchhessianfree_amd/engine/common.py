@@ -82,6 +82,30 @@ class _Unsupported(Exception):
     pass
 
 
+def records_of(m, n=2, with_input=False):
+    """The ``n`` activations the patched layer ``m`` recorded during the step's forward pass (``modelprep``);
+    ``with_input``: the first of them, the layer's input, must not be ``None`` (the stacks' own condition)."""
+    rec = getattr(m, "_hf_io", None)
+    if rec is None or len(rec) != n or (with_input and rec[0] is None):
+        raise _Unsupported(f"{type(m).__name__} has no record of this forward pass")
+    return rec
+
+
+def mark_dead_prefix(layers):
+    """Frozen layers at the input end of a stack (no ``pw``, no ``pb``): ``dead`` for both sweeps -- no tangent reaches
+    them, nobody needs a cotangent behind the first trainable layer.  Returns how many there are; the layer behind them
+    reads a tangent-free input and needs no data gradient (the caller's flag)."""
+    dead = 0
+    for u in layers:
+        if u.pw is not None or u.pb is not None:
+            break
+        u.dead = True
+        dead += 1
+    if dead == len(layers):
+        raise _Unsupported("every layer is frozen")
+    return dead
+
+
 def ce_loss_spec(loss, outputs, check_values=True):
     """``{"reduction", "targets"}`` if ``loss`` is ``F.cross_entropy(outputs, targets)`` with class-index
     targets, no class weights, no label smoothing and no ignored target -- read off the autograd

@@ -34,14 +34,14 @@ operator's product on a random vector.
 """
 
 import os
-import warnings
 
 import torch
 
 from .. import _lib
-from ..curvature import GGNOperator, _Operator
+from ..curvature import GGNOperator
 from .common import _Launcher, _Node, _Unsupported, _ce_node, ce_loss_spec, loss_spec_of  # noqa: F401
 from .adjoint import _AdjointSweep
+from .base import _Engine
 from .buffers import _Buffers
 from .dataparallel import _DataParallel
 from .diag_ef import _DiagEF
@@ -51,64 +51,13 @@ from .tangent import _TangentSweep
 from .topology import _Topology
 
 
-class FusedGGNEngine(_Launcher, _Topology, _Buffers, _Forward, _TangentSweep, _AdjointSweep, _HessianExtras, _DiagEF,
-                     _DataParallel, _Operator):
+class FusedGGNEngine(_Topology, _Buffers, _Forward, _TangentSweep, _AdjointSweep, _HessianExtras, _DiagEF, _DataParallel,
+                     _Engine):
+    # (the base LAST: ``_DataParallel`` overrides its single-process ``reduce`` / ``reduce_bytes``; ``try_build``, the
+    # contract's defaults, ``unavailable`` and the constructors' shared pieces stand in engine/base.py)
     mode = ("fused curvature engine: own deterministic convolutions (split-K slabs summed by the consumer "
             "kernel), BatchNorm tangents/adjoints fused, 4 launches per conv-BN unit, downsample branches grouped "
             "with their block's first convolution")
-
-    # ------------------------------------------------------------------------------------
-    @classmethod
-    def try_build(cls, loss, outputs, params, weight=1.0, group=None, hessian=False, why=None, need_session=False,
-                  for_acc=False):
-        """The engine for the model that produced ``outputs``, or ``None``; ``why`` (a list) receives one line per
-        reason it was not taken -- what ``HessianFree.path_report()`` and its one-time warning quote.
-        ``need_session``: the caller (a persistent session) needs the engine's own forward pass, loss head and
-        gradient sweep; kinds without them are not built.  ``for_acc``: the caller is ``acc_step``'s accumulated session
-        (one engine per data chunk); kinds that serve ``step()`` sessions only (``acc_decline``) are not built."""
-        why = [] if why is None else why
-        if os.environ.get("HF_ENGINE", "1") == "0":
-            why.append("the fused engine is switched off (HF_ENGINE=0)")
-            return None
-        ref = getattr(outputs, "_hf_model", None)
-        model = ref() if ref is not None else None
-        if model is None:
-            why.append("the model is not a prepared one (modelprep.prepare_model(model, channels_last=True) installs "
-                       "the layers the fused engine reads)")
-            return None
-        if not outputs.is_cuda or outputs.dtype != torch.float32 or outputs.dim() != 2:
-            why.append(f"the model output is not a CUDA float32 [batch, classes] tensor (got {outputs.dtype}, "
-                       f"{tuple(outputs.shape)}, {outputs.device})")
-            return None
-        from .dense import DenseStackEngine
-        from .plain import PlainStackEngine
-
-        kinds = [cls] if cls is not FusedGGNEngine else [FusedGGNEngine, PlainStackEngine, DenseStackEngine]
-        if any(isinstance(m, torch.nn.Conv2d) for m in model.modules()):
-            kinds = [k for k in kinds if k is not DenseStackEngine]  # (a conv net is no dense stack: nothing to say)
-        for kind in kinds:
-            # (asked of the CLASS, in the kinds' order: nothing is built that the caller could not use)
-            reason = kind.unavailable(hessian, need_session)
-            if reason is None and for_acc:
-                reason = kind.acc_decline
-            if reason is not None:
-                why.append(f"{kind.__name__}: {reason}")
-                continue
-            try:
-                return kind(model, loss, outputs, params, weight, group, hessian=hessian)
-            except _Unsupported as exc:
-                # (a model the engine does not cover is the normal case: quiet unless asked;
-                # a product that FAILED its check is always reported)
-                why.append(f"{kind.__name__}: {exc}")
-                if os.environ.get("HF_ENGINE_DEBUG") or getattr(exc, "loud", False):
-                    warnings.warn(f"fused curvature engine ({kind.__name__}) not used: {exc}")
-                if getattr(exc, "loud", False):
-                    return None
-            except _lib.Refused as exc:  # a kernel refused its arguments (alignment, size limits ...)
-                why.append(f"{kind.__name__}: a kernel refused its arguments: {exc}")
-                warnings.warn(f"fused curvature engine ({kind.__name__}) not used: {exc}")
-                return None
-        return None
 
     # Hessian products (optimizer.py:450-455) by forward-over-reverse on the same kernels; residual nets with
     # EVAL-mode BatchNorm (the layer is a per-channel affine map; ReLU masks and max-pool positions are
@@ -118,35 +67,13 @@ class FusedGGNEngine(_Launcher, _Topology, _Buffers, _Forward, _TangentSweep, _A
     # TRAIN-mode BatchNorm (round 5): the batch statistics' share of the adjoint's tangent in closed form per channel
     # (hf_bn_train_hessian_coeffs / _apply; the formulas stand in csrc/hf_bn.hip and DESIGN.md section 4.3).
     supports_hessian = True
-    supports_session = True
     supports_two_phase = True  # (phase_split / local_phase_a / local_phase_b: the chunked, overlapped all-reduce)
-    acc_decline = None         # why this kind does not serve acc_step's accumulated session, if it does not
-
-    @classmethod
-    def unavailable(cls, hessian, need_session):
-        """Why this kind cannot serve a caller who wants Hessian products / a persistent session, or ``None``."""
-        if hessian and not cls.supports_hessian:
-            return "no Hessian products (GGN only)"
-        if need_session and not cls.supports_session:
-            return "no persistent session on this engine yet"
-        return None
 
     def __init__(self, model, loss, outputs, params, weight, group, hessian=False):
-        super().__init__(params, weight, group)
-        self.hessian = bool(hessian)
+        self._begin(params, weight, group, outputs, hessian)
         self._second = False  # (inside the adjoint sweep of a Hessian product)
-        self._l2 = None
         self._diag_batched = os.environ.get("HF_DIAG_EF_BATCHED", "0") == "1"  # (diag_ef: one launch per layer)
-        self.outputs = outputs
-        self.dev = outputs.device
-        self._index = {id(p): i for i, p in enumerate(self.params)}
-        offs, o = [], 0
-        for p in self.params:
-            offs.append(o)
-            o += p.numel()
-        self._offs = offs
-        self.train_bn = False
-        self.frozen_any, self.dead_blocks = False, 0
+        self.dead_blocks = 0
         self._layout(model)
         if self.hessian:
             for u in self.units:
@@ -162,17 +89,12 @@ class FusedGGNEngine(_Launcher, _Topology, _Buffers, _Forward, _TangentSweep, _A
             # reproduces the model's output here (with the running statistics left alone)
             if (all(u.bn.momentum is not None and u.bn.track_running_stats for u in self.units if u.train)):
                 self.forward_own(update_running=False)
-                want = outputs.detach()
-                err = float((self.logits - want).abs().max() / want.abs().max().clamp_min(1e-30))
-                self.train_own = err < 1e-4
+                self.train_own = self._forward_error(outputs) < 1e-4
             self._load_recorded(outputs)
         else:
             # own forward pass on the engine's static buffers; it must reproduce the model's output
             self.forward_own()
-            want = outputs.detach()
-            err = float((self.logits - want).abs().max() / want.abs().max().clamp_min(1e-30))
-            if not err < 1e-4:
-                raise _Unsupported(f"the engine's forward pass differs from the model's output by {err:.2e}")
+            self._check_forward(outputs)
         self._loss_setup(loss, outputs)
         self._verify(loss)
         # ONE linearisation point after construction, whether or not the first-use check ran (it is skipped for a
@@ -188,16 +110,11 @@ class FusedGGNEngine(_Launcher, _Topology, _Buffers, _Forward, _TangentSweep, _A
             u.rx = u.ry = u.ra = u.rp = None
             u.rec_stats = None
         self._rec_pool = None
-        if self.loss_spec is not None:
-            self.outputs = None  # nothing of the step's autograd graph stays alive in the engine
-            from ..modelprep import release_records
-
-            release_records(model)  # (the layers' records pinned this pass's activations until the next one)
+        self._release(model)
 
     # ---- loss Hessian (same contract as GGNOperator) -------------------------------------
     def _loss_setup(self, loss, outputs):
-        (self._dl,) = torch.autograd.grad(loss, outputs, create_graph=True, retain_graph=True)
-        self._ce = GGNOperator._closed_form_loss_hessian(self, _Node(_ce_node(loss)), outputs)
+        self._closed_form(loss, outputs)
         # a plain softmax cross-entropy (checked numerically above): the engine can then evaluate
         # loss, probabilities and d loss / d logits itself, on its own forward pass -- which is what
         # lets ONE engine serve many steps and trial points (``session.EngineSession``)
@@ -222,30 +139,6 @@ class FusedGGNEngine(_Launcher, _Topology, _Buffers, _Forward, _TangentSweep, _A
                 raise _Unsupported("Hessian products on the engine need a plain softmax cross-entropy or mean-squared-"
                                    "error loss")
             self.gradient()  # fills the first-order cotangents the Hessian products read
-
-    def _set_quadratic(self, terms):
-        """``loss = cross-entropy + sum_j 0.5 * coef_j * ||w_j||^2`` (the L2 term of the reference's
-        All-CNN-C example, examples/example_utils.py:77-81): per-entry coefficients of the flat vector.
-        Loss value, gradient and Hessian product of that term are ``0.5 <d*theta, theta>``,
-        ``d*theta`` and ``d*v``."""
-        self._l2 = None
-        if not terms:
-            return
-        d = torch.zeros(self.n, dtype=torch.float32, device=self.dev)
-        for coef, tensors in terms:
-            for w in tensors:
-                i = self._index.get(id(w))
-                if i is None:
-                    # (a frozen tensor would add a constant to the loss value the engine's own loss head reports)
-                    raise _Unsupported("a regularised tensor is not among the optimizer's parameters")
-                d[self._offs[i]: self._offs[i] + w.numel()] += float(coef)
-        self._l2 = d
-
-    def _theta(self):
-        flat = self._flat_params
-        if flat is not None and flat.data_ptr() == self.params[0].data_ptr():
-            return flat
-        return torch.cat([p.detach().reshape(-1) for p in self.params])
 
     def gradient(self, out=None):
         """``weight * d loss / d params`` of the softmax cross-entropy by ONE adjoint sweep of the
@@ -279,8 +172,7 @@ class FusedGGNEngine(_Launcher, _Topology, _Buffers, _Forward, _TangentSweep, _A
                 if u.train:
                     torch.sum(u.gw[:u.rb], 0, out=u.gg1)
                     torch.sum(u.gb, 0, out=u.gb1)
-        if self._l2 is not None:
-            out.addcmul_(self._l2, self._theta(), value=self.weight)
+        self._add_quadratic(out)
         return out
 
     def _dlogits(self):
@@ -296,11 +188,7 @@ class FusedGGNEngine(_Launcher, _Topology, _Buffers, _Forward, _TangentSweep, _A
 
     # ---- the product -------------------------------------------------------------------------
     def local(self, v, out=None):
-        if out is None:
-            out = torch.empty(self.n, dtype=torch.float32, device=self.dev)
-        v = v.detach()
-        if not v.is_contiguous():
-            v = v.contiguous()
+        v, out = self._product_vectors(v, out)
         self._tangent_stem(v, carry_scatter=True)  # + the v_W halves of all [W | v_W] operands, same launch
         self._tangent_blocks(v)
         if self.hessian:
@@ -317,13 +205,9 @@ class FusedGGNEngine(_Launcher, _Topology, _Buffers, _Forward, _TangentSweep, _A
         finally:
             self._second, self._v = False, None
         self._gather(out, g_fw, g_fb)
-        if self.hessian and self._l2 is not None:  # the regulariser's Hessian: coef on its tensors' entries
-            out.addcmul_(self._l2, v, value=self.weight)
+        if self.hessian:  # the regulariser's Hessian: coef on its tensors' entries
+            self._add_quadratic(out, v)
         return out
-
-    def __call__(self, v, out=None):
-        self.calls += 1
-        return self.reduce(self.local(v, out))
 
     # ---- the product between vectors in the compact layout (dataparallel.compact_layout) ----------------
     supports_compact = True
@@ -348,51 +232,3 @@ class FusedGGNEngine(_Launcher, _Topology, _Buffers, _Forward, _TangentSweep, _A
             return self.local(vc, out=out)
         finally:
             (self._offs, self._slot_list), self._compact_nl = saved, None
-
-
-    # ---- safety net --------------------------------------------------------------------------
-    # relative max-norm distance to the autograd product above which the engine is refused; fp32
-    # products of the shipped workloads agree to ~1e-6.  Deep, badly conditioned nets (the random-init
-    # ResNet-50) scatter more for EVERY fp32 implementation: callers that have measured what stock
-    # fp32 autograd achieves against float64 (bench.py) raise it to max(1e-5, 5 x that error)
-    verify_tol = 1e-5
-
-    def _verify(self, loss):
-        """First product of every (model, shape) signature against the autograd operator, both on the
-        activations the model's own forward pass recorded (``_load_recorded``)."""
-        policy = os.environ.get("HF_ENGINE_VERIFY", "first")
-        key = ("hessian" if self.hessian else "ggn", self.train_bn,
-               tuple(type(m).__name__ for m in self.model_ref.modules()), self.n,
-               tuple(tuple(p.shape) for p in self.params), tuple(self.logits.shape), tuple(self.x_in.shape),
-               str(self.dev))
-        # (kept ON the model: a registry keyed by id(model) outlives the model, and CPython hands the address of a
-        # collected model to the next one)
-        verified = self.model_ref.__dict__.setdefault("_hf_engine_verified", set())
-        if policy == "never" or (policy != "always" and key in verified):
-            return
-        gen = torch.Generator(device=self.dev).manual_seed(4321)
-        v = torch.randn(self.n, device=self.dev, generator=gen)
-        weight, self.weight = self.weight, 1.0
-        self._load_recorded(self.outputs)
-        try:
-            if self.hessian:
-                self.gradient()  # first-order cotangents at the recorded activations
-            got = self.local(v).clone()
-        finally:
-            self.weight = weight  # (the constructor moves the engine to its final linearisation point afterwards)
-        if self.hessian:
-            from ..curvature import HessianOperator
-
-            want = HessianOperator(loss, self.params).local(v)
-        else:
-            want = GGNOperator(loss, self.outputs, self.params).local(v)
-        err = float((got - want).abs().max() / want.abs().max().clamp_min(1e-30))
-        # (Hessian products through batch statistics: stock fp32 double backward is itself 6e-6 from float64 on the
-        # train-mode ResNet-18, this engine 3e-6 ... 7e-6 -- two fp32 results may be the sum of both apart)
-        tol = FusedGGNEngine.verify_tol * (3.0 if (self.hessian and self.train_bn) else 1.0)
-        if not err < tol:
-            exc = _Unsupported(f"engine {'Hessian ' if self.hessian else ''}product differs from the autograd product by {err:.2e} "
-                               f"(tolerance {tol:.1e}); using the autograd operator")
-            exc.loud = True
-            raise exc
-        verified.add(key)

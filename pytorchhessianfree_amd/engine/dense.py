@@ -8,9 +8,8 @@ import torch
 from torch import nn
 
 from .. import _lib
-from ..curvature import GGNOperator, _Operator
-from .common import _Node, _P, _Unsupported, _ce_node, _flat_view, _same, loss_spec_of
-from .core import FusedGGNEngine
+from .base import _Engine
+from .common import _P, _Unsupported, _flat_view, _same, loss_spec_of, mark_dead_prefix, records_of
 
 _ACT = {None: 0, nn.ReLU: 1, nn.Tanh: 2}
 _OPT_IN = "the dense-stack engine is opt-in (set HF_DENSE_ENGINE=1)"
@@ -30,7 +29,7 @@ def _addr(base, words):
     return _P(base + 4 * words)
 
 
-class DenseStackEngine(FusedGGNEngine):
+class DenseStackEngine(_Engine):
     """The sweeps of the GGN product for a stack of fully-connected layers.  Per live layer and product: the tangent GEMM
     ``t_x W^T + x V^T`` (W and the vector's slice V read in place in the flat vectors) -> bias tangent and ``act'``;
     the loss Hessian on the output tangent; in reverse ``act'`` and the bias gradient -> the weight gradient, written
@@ -98,25 +97,14 @@ class DenseStackEngine(FusedGGNEngine):
         return os.environ.get("HF_DENSE_SESSION", "0") == "1"
 
     def __init__(self, model, loss, outputs, params, weight, group, hessian=False):
-        _Operator.__init__(self, params, weight, group)
+        self._begin(params, weight, group, outputs, hessian)
         if group is not None:
             raise _Unsupported("data parallelism is not implemented for dense stacks")
-        self.hessian, self.train_bn, self.frozen_any = bool(hessian), False, False
-        self.outputs, self.dev = outputs, outputs.device
-        self._index = {id(p): i for i, p in enumerate(self.params)}
-        offs, o = [], 0
-        for p in self.params:
-            offs.append(o)
-            o += p.numel()
-        self._offs = offs
         self.loss_spec = None  # (set by _loss_setup in session mode: no own loss head before)
         self._layout(model)
         self._allocate()
         self.forward_own()
-        want = outputs.detach()
-        err = float((self.logits - want).abs().max() / want.abs().max().clamp_min(1e-30))
-        if not err < 1e-4:
-            raise _Unsupported(f"the engine's forward pass differs from the model's output by {err:.2e}")
+        self._check_forward(outputs)
         self._loss_setup(loss, outputs)
         self._verify(loss)
         if self._at != "own":
@@ -126,11 +114,7 @@ class DenseStackEngine(FusedGGNEngine):
         for u in self.layers:  # the model's own activations were only needed up to here
             u.rx = u.ry = None
         self._rec_in = None
-        if self.loss_spec is not None:
-            self.outputs = None  # nothing of the step's autograd graph stays alive in the engine
-            from ..modelprep import release_records
-
-            release_records(model)
+        self._release(model)
 
     # ---- topology ----------------------------------------------------------------------------
     def _layout(self, model):
@@ -138,12 +122,6 @@ class DenseStackEngine(FusedGGNEngine):
         if not isinstance(x_in, torch.Tensor) or x_in.dtype != torch.float32 or not x_in.is_cuda:
             raise _Unsupported("no recorded float32 GPU input")
         leaves = [m for m in model.modules() if not list(m.children())]
-
-        def io(m):
-            rec = getattr(m, "_hf_io", None)
-            if rec is None or len(rec) != 2 or rec[0] is None:
-                raise _Unsupported(f"{type(m).__name__} has no record of this forward pass")
-            return rec
 
         layers, cur, i = [], x_in.detach(), 0
         while i < len(leaves):
@@ -155,12 +133,12 @@ class DenseStackEngine(FusedGGNEngine):
             if dropout:
                 raise _Unsupported("a training-mode model with active dropout")
             if type(m) is nn.Flatten and not layers:
-                fx, fy = io(m)
+                fx, fy = records_of(m, with_input=True)
                 if not _same(fx, cur) or fy.dim() != 2:
                     raise _Unsupported("Flatten does not turn the input into [batch, features]")
                 cur = fy
             elif type(m) is nn.Linear:
-                cx, cy = io(m)
+                cx, cy = records_of(m, with_input=True)
                 if cx.dim() != 2 or not _same(cx, cur):
                     raise _Unsupported(f"linear {len(layers)}: its input is not the previous [batch, features] activation")
                 nxt = leaves[i + 1] if i + 1 < len(leaves) else None
@@ -168,7 +146,7 @@ class DenseStackEngine(FusedGGNEngine):
                 if type(nxt) in (nn.ReLU, nn.Tanh):
                     if getattr(nxt, "inplace", False):
                         raise _Unsupported(f"linear {len(layers)}: followed by an in-place activation")
-                    rx, ry = io(nxt)
+                    rx, ry = records_of(nxt, with_input=True)
                     if not _same(rx, cy):
                         raise _Unsupported(f"{type(nxt).__name__} does not read linear {len(layers)}'s output")
                     act, y = type(nxt), ry
@@ -197,14 +175,7 @@ class DenseStackEngine(FusedGGNEngine):
             raise _Unsupported("the parameter list has entries the engine's layers do not cover")
         # frozen layers at the input end: dead for both sweeps; the first layer with a trainable parameter reads a
         # tangent-free input and needs no data gradient
-        self.dead_layers = 0
-        for u in layers:
-            if u.pw is not None or u.pb is not None:
-                break
-            u.dead = True
-            self.dead_layers += 1
-        if self.dead_layers == len(layers):
-            raise _Unsupported("every layer is frozen")
+        self.dead_layers = mark_dead_prefix(layers)
         layers[self.dead_layers].first_live = True
         self.layers, self.model_ref = layers, model
         self._rec_in, self._in_shape = layers[0].rx, tuple(x_in.shape)
@@ -278,8 +249,7 @@ class DenseStackEngine(FusedGGNEngine):
 
     # ---- loss --------------------------------------------------------------------------------
     def _loss_setup(self, loss, outputs):
-        (self._dl,) = torch.autograd.grad(loss, outputs, create_graph=True, retain_graph=True)
-        self._ce = GGNOperator._closed_form_loss_hessian(self, _Node(_ce_node(loss)), outputs)
+        self._closed_form(loss, outputs)
         self._mse2 = None
         if self._ce is None:
             spec = loss_spec_of(loss, outputs)
@@ -433,24 +403,9 @@ class DenseStackEngine(FusedGGNEngine):
             slabs, splits, stride = u.dslabs, u.sD, u.dslabs.shape[1]
         return out
 
-    def _not_here(what):  # noqa: N805  (the conv engines' entry points this kind inherits but does not have)
-        def refuse(self, *args, **kwargs):
-            raise RuntimeError(f"the dense-stack engine has no {what}: it serves one process only (no data "
-                               "parallelism, no two-phase product)")
-        refuse.__name__ = what
-        return refuse
-
-    for _name in ("phase_split", "local_phase_a", "local_phase_b"):
-        locals()[_name] = _not_here(_name)
-    del _name, _not_here
-
     # ---- the product -------------------------------------------------------------------------
     def local(self, v, out=None):
-        if out is None:
-            out = torch.empty(self.n, dtype=torch.float32, device=self.dev)
-        v = v.detach()
-        if not v.is_contiguous():
-            v = v.contiguous()
+        v, out = self._product_vectors(v, out)
         self._flat("vector and product", v, out)
         vp, offs = v.data_ptr(), self._offs
         t_x = None
@@ -493,14 +448,6 @@ class DenseStackEngine(FusedGGNEngine):
             out = torch.empty(self.n, dtype=torch.float32, device=self.dev)
         self._flat("the diagonal", out)
         return self._adjoint_sweep(_DIAG_EF, self._g_ef, out, scale=1.0 / self.rows if reduction == "mean" else 1.0)
-
-    # ---- one process only ----------------------------------------------------------------------
-    @property
-    def reduce_bytes(self):
-        return 4 * self.n
-
-    def reduce(self, t, group=None):
-        return t
 
 
 def diag_ef_of(model, loss_function, inputs, targets, reduction, why=None):

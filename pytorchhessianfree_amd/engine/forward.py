@@ -87,7 +87,7 @@ class _Forward:
             torch.softmax(self.logits, 1, out=self._p)
             lsm = torch.log_softmax(self.logits, 1)
             val = torch.nn.functional.nll_loss(lsm, self._targets, reduction=self.loss_spec["reduction"])
-        if getattr(self, "_l2", None) is not None:
+        if self._l2 is not None:
             theta = self._theta()
             val = val + 0.5 * torch.dot(self._l2 * theta, theta)
         self.loss_buf.copy_(val)

@@ -4,7 +4,7 @@ import torch
 from torch import nn
 
 from .. import _lib
-from .common import _Unit, _Unsupported, _cl, _pair, _same
+from .common import _Unit, _Unsupported, _cl, _pair, _same, mark_dead_prefix, records_of
 from .core import FusedGGNEngine
 
 
@@ -43,12 +43,6 @@ class PlainStackEngine(FusedGGNEngine):
             raise _Unsupported("the model must be in eval mode")
         leaves = [m for m in model.modules() if not list(m.children())]
 
-        def io(m):
-            rec = getattr(m, "_hf_io", None)
-            if rec is None or len(rec) != 2 or rec[0] is None:
-                raise _Unsupported(f"{type(m).__name__} has no record of this forward pass")
-            return rec
-
         units, cur, prev, pooled, i = [], x_in.detach(), "input", None, 0
         while i < len(leaves):
             m = leaves[i]
@@ -60,14 +54,14 @@ class PlainStackEngine(FusedGGNEngine):
             if type(m) is nn.Conv2d:
                 if m.groups != 1 or tuple(m.dilation) != (1, 1) or not getattr(m, "_hf_channels_last", False):
                     raise _Unsupported(f"conv {len(units)}: needs prepare_model(channels_last=True), groups = dilation = 1")
-                cx, cy = io(m)
+                cx, cy = records_of(m, with_input=True)
                 if not _same(cx, cur):
                     raise _Unsupported(f"conv {len(units)}: input is not the previous activation")
                 u = _Unit(f"conv{len(units)}", m, None)
                 y, u.relu = cy, False
                 nxt = leaves[i + 1] if i + 1 < len(leaves) else None
                 if type(nxt) is nn.ReLU and not nxt.inplace:
-                    rx, ry = io(nxt)
+                    rx, ry = records_of(nxt, with_input=True)
                     if _same(rx, cy):
                         y, u.relu = ry, True
                         i += 1
@@ -86,7 +80,7 @@ class PlainStackEngine(FusedGGNEngine):
                     raise _Unsupported(f"{where}: a pool must directly follow a convolution (and its ReLU)")
                 if _pair(m.dilation) != [1, 1] or m.ceil_mode or m.return_indices:
                     raise _Unsupported(f"{where}: dilation / ceil_mode / return_indices are not covered")
-                px, py = io(m)
+                px, py = records_of(m, with_input=True)
                 if not _same(px, cur):
                     raise _Unsupported(f"{where}: its recorded input is not the unit's output")
                 u = units[-1]
@@ -94,7 +88,7 @@ class PlainStackEngine(FusedGGNEngine):
                                + _pair(m.padding))
                 u.rp, cur = py, py
             elif isinstance(m, nn.AdaptiveAvgPool2d) and m.output_size in (1, (1, 1)):
-                px, py = io(m)
+                px, py = records_of(m, with_input=True)
                 if not units or not _same(px, cur):
                     raise _Unsupported("the pooling layer does not follow the last convolution")
                 if units[-1].pool is not None:
@@ -123,14 +117,7 @@ class PlainStackEngine(FusedGGNEngine):
             raise _Unsupported("the parameter list has entries the engine's layers do not cover")
         # frozen layers at the input end (round 6, as FusedGGNEngine._mark_dead_prefix): dead for both sweeps; the first
         # layer with a trainable parameter reads a tangent-free input and needs no data gradient
-        self.dead_units = 0
-        for u in units:
-            if u.pw is not None or u.pb is not None:
-                break
-            u.dead = True
-            self.dead_units += 1
-        if self.dead_units == len(units):
-            raise _Unsupported("every layer is frozen")
+        self.dead_units = mark_dead_prefix(units)
         if self.dead_units:
             units[self.dead_units].no_dgrad = True
 
@@ -262,11 +249,7 @@ class PlainStackEngine(FusedGGNEngine):
                 srcs = [(u.dbuf, u.nD if second else u.sD, u.dbuf.shape[1])]
 
     def local(self, v, out=None):
-        if out is None:
-            out = torch.empty(self.n, dtype=torch.float32, device=self.dev)
-        v = v.detach()
-        if not v.is_contiguous():
-            v = v.contiguous()
+        v, out = self._product_vectors(v, out)
         self._tangent_sweep(v)
         if self.hessian and self._vt_slots:
             _lib.unpack_tangent(v, self._vt_slots, half=2)  # V as (I, H, W, O): the operand of conv_D(g, V)
@@ -282,8 +265,8 @@ class PlainStackEngine(FusedGGNEngine):
         finally:
             self._second = False
         self._gather(out, None, None)
-        if self.hessian and self._l2 is not None:  # the regulariser's Hessian: coef on its tensors' entries
-            out.addcmul_(self._l2, v, value=self.weight)
+        if self.hessian:  # the regulariser's Hessian: coef on its tensors' entries
+            self._add_quadratic(out, v)
         return out
 
     def gradient(self, out=None):
@@ -294,8 +277,7 @@ class PlainStackEngine(FusedGGNEngine):
         self._g_last.permute(0, 2, 3, 1).copy_(g.view(n, 1, 1, k).expand(n, h, w, k))
         self._adjoint_sweep(self._g_last, first_order=True)
         self._gather(out, None, None, first_order=True)
-        if self._l2 is not None:
-            out.addcmul_(self._l2, self._theta(), value=self.weight)
+        self._add_quadratic(out)
         return out
 
     def _gather(self, out, g_fw, g_fb, first_order=False):

@@ -5,24 +5,11 @@ Mixin of ``FusedGGNEngine`` (engine/core.py); see that class for the sweeps' ove
 
 from torch import nn
 
-from .common import _Unit, _Unsupported, _cl, _same
+from .common import _Unit, _Unsupported, _cl, _same, records_of
 
 
 class _Topology:
     # ---- topology ---------------------------------------------------------------------
-    def _param(self, p):
-        """Index of a layer parameter in the optimizer's (trainable) list; ``None``: the layer has no such parameter
-        or it is FROZEN (``requires_grad = False``: it is a constant of the product -- no tangent, no gradient entry;
-        reference utils.py:31-32 skips it the same way)."""
-        if p is None:
-            return None
-        i = self._index.get(id(p))
-        if i is None:
-            if p.requires_grad:
-                raise _Unsupported("a trainable layer parameter is not among the optimizer's parameters")
-            self.frozen_any = True
-        return i
-
     def _layout(self, model):
         need = ("conv1", "bn1", "maxpool", "avgpool", "fc")
         if not all(isinstance(getattr(model, a, None), nn.Module) for a in need):
@@ -37,12 +24,6 @@ class _Topology:
         if x_in is None:
             raise _Unsupported("no recorded input")
 
-        def io(m, n):
-            rec = getattr(m, "_hf_io", None)
-            if rec is None or len(rec) != n:
-                raise _Unsupported(f"{type(m).__name__} has no record of this forward pass")
-            return rec
-
         units = []
         group_is_set = self.group is not None
         self.frozen_any = False
@@ -55,7 +36,7 @@ class _Topology:
             if not isinstance(bn, nn.BatchNorm2d):
                 raise _Unsupported(f"{name}: not a BatchNorm2d")
             u = _Unit(name, conv, bn)
-            cx, cy = io(conv, 2)
+            cx, cy = records_of(conv)
             rec = getattr(bn, "_hf_io", None)
             if bn.training:
                 # train mode: the layer ran on stock ops and recorded its batch statistics (modelprep)
@@ -68,7 +49,7 @@ class _Topology:
                 rstd, u.mean_t = rstd.clone(), mean_t.clone()
                 u.train = True
             else:
-                bx, bres, by, brelu, rstd = io(bn, 5)
+                bx, bres, by, brelu, rstd = records_of(bn, 5)
             if not _same(cy, bx):
                 raise _Unsupported(f"{name}: the BatchNorm does not consume the convolution's output")
             if brelu != relu_expected:
@@ -87,7 +68,7 @@ class _Topology:
             raise _Unsupported("stem does not start at the network input")
         stem.src, stem.im2col, stem.first = "input", True, True
         self.model_ref, self._in_shape = model, tuple(x_in.shape)
-        mp_x, mp_y = io(model.maxpool, 2)
+        mp_x, mp_y = records_of(model.maxpool)
         if not _same(mp_x, stem.ry):
             raise _Unsupported(f"maxpool does not follow the stem ({tuple(mp_x.shape)} {mp_x.stride()} "
                                f"{mp_x.data_ptr():x} vs {tuple(stem.y.shape)} {stem.y.stride()} {stem.y.data_ptr():x})")
@@ -130,11 +111,11 @@ class _Topology:
             self.blocks.append((chain, ds, cur))
             cur = tail.ry
             prev = tail
-        ap_x, ap_y = io(model.avgpool, 2)
+        ap_x, ap_y = records_of(model.avgpool)
         if not _same(ap_x, cur):
             raise _Unsupported("avgpool does not follow the last block")
         fc = model.fc
-        fc_x, fc_y = io(fc, 2)
+        fc_x, fc_y = records_of(fc)
         if fc_x.dim() != 2 or fc_x.shape[0] != cur.shape[0] or fc_x.shape[1] != cur.shape[1]:
             raise _Unsupported("the classifier does not take the pooled features")
         if not _same(fc_y, self.outputs.detach()):

@@ -36,7 +36,7 @@ import torch
 
 from .curvature import CapturedOperator, CompactFacet
 from .distributed import two_phase_all_reduce
-from .engine import FusedGGNEngine, loss_spec_of
+from .engine import FusedGGNEngine, _Engine, loss_spec_of
 
 
 class _TwoPhaseProduct:
@@ -74,7 +74,7 @@ class _TwoPhaseProduct:
             tail_fraction = 0.7
         if os.environ.get("HF_CHUNKED_ALLREDUCE", "auto") == "0" or not hasattr(eng, "phase_split"):
             return None
-        if getattr(eng, "hessian", False) or getattr(eng, "train_bn", False):
+        if eng.hessian or eng.train_bn:
             return None
         split = eng.phase_split(tail_fraction)
         if split is None:
@@ -187,7 +187,8 @@ class EngineSession(_TwoPhaseProduct, _Session):
             sess._build(builder, params)
         except _NoEngine as exc:
             # (an engine that was built but declines the session says so itself; else the kinds' own lines stand)
-            if not why or getattr(holder.get("eng"), "session_decline", None):
+            eng = holder.get("eng")
+            if not why or (eng is not None and eng.session_decline):
                 why.append(exc.reason)
             return None
         return sess
@@ -201,14 +202,14 @@ class EngineSession(_TwoPhaseProduct, _Session):
                 cur.wait_stream(self.stream)
                 raise _NoEngine("the fused engine does not cover this model" if eng is None else
                                 f"{type(eng).__name__}: {eng.session_decline}"
-                                if getattr(eng, "session_decline", None) else
+                                if eng.session_decline else
                                 "the dense-stack engine has no session yet (its products run as engine-graphed)"
-                                if not getattr(eng, "supports_session", True) else
+                                if not eng.supports_session else
                                 "the engine's own forward pass does not reproduce this train-mode model, or the loss "
                                 "is neither a plain softmax cross-entropy nor a mean-squared error")
             self.op = self.engine = eng
             self.group, self.params, self.weight = eng.group, eng.params, eng.weight
-            self.hessian = bool(getattr(eng, "hessian", False))
+            self.hessian = bool(eng.hessian)
             self._allocate(eng.n, torch.float32, eng.dev)
             # data parallel: the product as two graphs, its all-reduce chunked by stage and overlapped
             self.split = self.plan_phases(eng) if eng.group is not None else None
@@ -225,7 +226,7 @@ class EngineSession(_TwoPhaseProduct, _Session):
         with torch.no_grad():
             # (an engine that reads its weights in place has nothing to capture here: an empty hipGraph warns)
             self.g_wT = (self._capture(lambda: eng.refresh_weights(transposed=True))
-                         if getattr(eng, "has_weight_copies", True) else _NoGraph())
+                         if eng.has_weight_copies else _NoGraph())
             self.g_fwd = self._capture(lambda: eng.forward_own(refresh=True))
             # train-mode BatchNorm: a forward pass moves the running statistics.  The step that CREATES the
             # session has already run the model itself (the stock layers moved them): its refresh replays a
@@ -257,8 +258,8 @@ class EngineSession(_TwoPhaseProduct, _Session):
         """``self.compact``: a second product graph between vectors in the compact layout (``CompactFacet``), when the
         vector has dead entries that stay zero through a solve; else ``None`` and ``compact_decline`` says why."""
         self.compact, self.compact_decline = None, None
-        layout = eng.compact_layout() if getattr(eng, "supports_compact", False) else None
-        if not getattr(eng, "supports_compact", False):
+        layout = eng.compact_layout() if eng.supports_compact else None
+        if not eng.supports_compact:
             self.compact_decline = f"{type(eng).__name__} has no product between compact vectors"
         elif layout is None:
             self.compact_decline = "no structurally-zero entries in this model's parameter vector"
@@ -267,7 +268,7 @@ class EngineSession(_TwoPhaseProduct, _Session):
         elif self.hessian:
             self.compact_decline = ("Hessian products read the vector's weight slices as transposed copies, which have "
                                     "no compact form")
-        elif getattr(eng, "_l2", None) is not None:
+        elif eng._l2 is not None:
             self.compact_decline = ("the loss carries a quadratic (L2) term: gradient and product are not zero on the "
                                     "entries of taps that never meet data")
         else:
@@ -523,7 +524,7 @@ class ChunkedEngineOperator(_TwoPhaseProduct, CapturedOperator):
         cur = self._enter_capture()
         with torch.cuda.stream(self.stream):
             eng = builder()
-            if not isinstance(eng, FusedGGNEngine) or not eng.supports_session or not eng.supports_two_phase:
+            if not isinstance(eng, _Engine) or not eng.supports_session or not eng.supports_two_phase:
                 raise TypeError("ChunkedEngineOperator needs the fused curvature engine")
             self.split = self.plan_phases(eng, tail_fraction)
             if self.split is None:

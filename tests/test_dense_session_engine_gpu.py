@@ -21,7 +21,7 @@ from tol import within
 import pytorchhessianfree_amd as hf
 from pytorchhessianfree_amd import modelprep, preconditioners
 from pytorchhessianfree_amd import testproblems as tp
-from pytorchhessianfree_amd.engine import FusedGGNEngine
+from pytorchhessianfree_amd.engine import FusedGGNEngine, _Unsupported
 from pytorchhessianfree_amd.engine.dense import DenseStackEngine
 from pytorchhessianfree_amd.session import EngineSession
 from pytorchhessianfree_amd.utils import ParameterArena
@@ -408,9 +408,13 @@ def test_switch_and_declines(monkeypatch):
     assert EngineSession.try_create(lossf(out, t), out, trainable(model), group=object(), why=why) is None
     assert any("DenseStackEngine: data parallelism is not implemented" in w for w in why), why
     eng = build(model, x, t, lossf)
+    # (one process only: the two-phase product's entry points do not exist on this kind, and the constructor -- above,
+    # and here directly -- refuses a group before anything is laid out)
     for name in ("phase_split", "local_phase_a", "local_phase_b"):
-        with pytest.raises(RuntimeError, match="the dense-stack engine has no " + name):
-            getattr(eng, name)()
+        assert not hasattr(eng, name), name
+    assert not eng.supports_two_phase and eng.group is None
+    with pytest.raises(_Unsupported, match="data parallelism is not implemented for dense stacks"):
+        DenseStackEngine(model, lossf(out, t), out, trainable(model), 1.0, object())
     from pytorchhessianfree_amd.session import ChunkedEngineOperator
 
     with pytest.raises(TypeError, match="needs the fused curvature engine"):
