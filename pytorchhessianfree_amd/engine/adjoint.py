@@ -1,23 +1,18 @@
 """Adjoint sweep J^T u: per unit the BatchNorm adjoint and data + weight gradient in one launch; the gather of all
 parameter gradients into the flat vector -- which also leaves the PCG curvature scalar (optimizer.py:457-462, L-op).
 
-Mixin of ``FusedGGNEngine`` (engine/core.py); see that class for the sweeps' overall structure."""
-
-import os
-
-import torch
+Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overall structure."""
 
 from .. import _lib
-from .common import _cl, _pair
 from .problems import (affine_args, affine_train_args, affine_train_problem, bn_adjoint_args, bn_adjoint_problem,
-                       bn_adjoint_v4_args, problem, sources)
+                       bn_adjoint_v4_args, problem)
 
 
 class _AdjointSweep:
     @staticmethod
-    def _train_adjoint_problem(u, ga=None):
+    def _train_adjoint_problem(u):
         """Pass 2 of the train-mode adjoint: g_a from the masked cotangent u.g and the partial rows of its sums."""
-        return affine_train_problem(u, u.ga if ga is None else ga, 0, u.g, 1, 0, (u.gw, u.gb, u.rb))
+        return affine_train_problem(u, u.ga, 0, u.g, 1, 0, (u.gw, u.gb, u.rb))
 
     def _bn_adjoint_pair_train(self, u1, srcs1, u2, srcs2):
         """Train mode, prologue form: both units' reduction passes in one launch, both elementwise passes in one."""
@@ -37,12 +32,27 @@ class _AdjointSweep:
 
     def _adjoint_unit(self, u, srcs):
         """srcs: up to two (tensor, splits, slab_stride) cotangents of the unit's output."""
-        second = self._second and u.bn is not None
-        self._bn_adjoint(u, srcs, reduce_only=second and u.train)
+        second = self._second
+        if u.pool is not None:  # (a pooled unit of a plain stack: bias / ReLU / pool adjoint in one launch)
+            self._pool_adjoint(u, srcs)
+        else:
+            self._bn_adjoint(u, srcs, reduce_only=second and u.train)
         if not second:
             self._conv_adjoint(u)
             return
         # ---- Hessian product: the tangent of the backward sweep through this unit --------------------------
+        if u.bn is None:
+            # a bias has no second-order term of its own: the convolutions read g_a itself.  (The chain's D + W launch
+            # through the two-problem entry point -- the same pair of problems ``_conv_adjoint`` launches --, and in
+            # sequence the extras BEHIND it: as the plain stack has always issued them)
+            if not u.im2col and not u.first and u.sD:
+                _lib.conv_dw_slabs((1, u.dbuf, u.ga, u.wT, u.geo, u.sD, 0, 0), (2, u.wbuf, u.x, u.ga, u.geo, u.sW, 0, 0),
+                                   self.dev)
+            else:
+                self._conv_adjoint(u)
+            if not self._extras_parallel:
+                self._hessian_extras(u)
+            return
         n, k, oh, ow = u.a.shape
         v_gamma = self._param_slice(self._v, u.pg, k)
         if v_gamma is None:  # (frozen scale)
@@ -74,7 +84,7 @@ class _AdjointSweep:
         """How many data-gradient slabs the consumers of ``u``'s input cotangent must sum in the current sweep."""
         return u.nD if self._second else u.sD
 
-    def _bn_adjoint(self, u, srcs, ga=None, reduce_only=False):
+    def _bn_adjoint(self, u, srcs, reduce_only=False):
         """``reduce_only`` (train mode inside a Hessian product): the masked cotangent and its per-channel sums only --
         the elementwise pass is ``hf_bn_train_hessian_apply``'s."""
         self._extras_wait(srcs)
@@ -85,17 +95,17 @@ class _AdjointSweep:
             # (pass 2 adds the partial rows up in its prologue)
             self._launch("hf_chan_affine_bwd_ex", *bn_adjoint_args(bn_adjoint_problem(u, srcs, reduce=True)))
             if not reduce_only:
-                self._launch("hf_chan_affine_train", *affine_train_args(self._train_adjoint_problem(u, ga)))
+                self._launch("hf_chan_affine_train", *affine_train_args(self._train_adjoint_problem(u)))
             return
         if self._split_now(u):
             # g = mask * (sum of both cotangents' slabs) -> u.g; g * w*rstd -> u.ga: all the chain needs.  The per-channel
             # sums (the parameters' gradient: only the gather reads them) wait for _flush_sums
-            self._launch("hf_bn_adjoint_v4", *bn_adjoint_v4_args(bn_adjoint_problem(u, srcs, ga)))
+            self._launch("hf_bn_adjoint_v4", *bn_adjoint_v4_args(bn_adjoint_problem(u, srcs)))
             if u.defer:
                 self._sums_pending.add(u.sums_slot)
             return
         # g = mask * (sum of both cotangents' slabs) -> u.g; g * w*rstd -> u.ga; per-channel sums
-        self._launch("hf_chan_affine_bwd_ex", *bn_adjoint_args(bn_adjoint_problem(u, srcs, ga, only_needed=True)))
+        self._launch("hf_chan_affine_bwd_ex", *bn_adjoint_args(bn_adjoint_problem(u, srcs, only_needed=True)))
 
     def _conv_adjoint(self, u, ga=None):
         """Data + weight gradient of the unit's convolution from ``ga`` (default ``u.ga``), one launch."""
@@ -115,108 +125,14 @@ class _AdjointSweep:
         self._launch("hf_conv2d_nhwc_backward_slabs", u.dbuf, u.wbuf, ga, u.x, u.wT, n_, h, w, c, k_, r, s, sd[0], sd[1],
                      pd[0], pd[1], u.sD, u.dbuf.shape[1], u.sW, u.wbuf.shape[1])
 
-    # ---- adjoint sweep -------------------------------------------------------------------------
-    def _adjoint_blocks(self, g_last, first=None, last_block=0, incoming=None):
-        """Walks the blocks ``first`` (default: the last one) ... ``last_block`` backwards; returns the
-        two cotangents of the pooled stem output -- or, when the walk stops before block 0, the state
-        (``incoming``) a later call continues from (the product in two phases, ``local_phases``)."""
-        group = self._grouping()
-        tail = self.tail
-        if incoming is None:
-            incoming = {id(tail): [(g_last, 1, 0)]}
-        pool_srcs = None
-        first = len(self.blocks) - 1 if first is None else first
-        stop = max(last_block, self.dead_blocks)  # (dead blocks: nobody needs their cotangents)
-        for bi in range(first, stop - 1, -1):
-            chain, ds, _x = self.blocks[bi]
-            head, last = chain[0], chain[-1]
-            for k in range(len(chain) - 1, -1, -1):
-                u = chain[k]
-                if k == 0 and ds is not None and group:
-                    # both BatchNorm adjoints, then the data + weight gradients of the block's first
-                    # convolution AND of its downsample branch in ONE launch (four problems)
-                    if u.rb > 1 and ds.rb > 1 and not u.train and not ds.train:
-                        self._bn_adjoint_pair(u, incoming.pop(id(u)), ds, [(last.g, 1, 0)])
-                    elif u.rb > 1 and ds.rb > 1 and self._train_pair_ok(u, ds):
-                        self._bn_adjoint_pair_train(u, incoming.pop(id(u)), ds, [(last.g, 1, 0)])
-                    else:
-                        self._bn_adjoint(u, incoming.pop(id(u)))
-                        self._bn_adjoint(ds, [(last.g, 1, 0)])
-                    if u.no_dgrad:  # (the block input carries no tangent: the two weight gradients only)
-                        _lib.conv_group_slabs(
-                            [(2, u.wbuf, u.x, u.ga, u.geo, u.sW, 0, 0), (2, ds.wbuf, ds.x, ds.ga, ds.geo, ds.sW, 0, 0)],
-                            self.dev)
-                    else:
-                        _lib.conv_group_slabs(
-                            [(1, u.dbuf, u.ga, u.wT, u.geo, u.sD, 0, 0), (2, u.wbuf, u.x, u.ga, u.geo, u.sW, 0, 0),
-                             (1, ds.dbuf, ds.ga, ds.wT, ds.geo, ds.sD, 0, 0),
-                             (2, ds.wbuf, ds.x, ds.ga, ds.geo, ds.sW, 0, 0)], self.dev)
-                else:
-                    self._adjoint_unit(u, incoming.pop(id(u)))
-                if k > 0:
-                    incoming.setdefault(id(chain[k - 1]), []).append((u.dbuf, self._dslabs(u), u.dbuf.shape[1]))
-            if head.no_dgrad:  # (everything in front of this block is frozen: the sweep ends here)
-                if ds is not None and not group:
-                    self._adjoint_unit(ds, [(last.g, 1, 0)])
-                return None
-            # the block input receives conv1's data gradient and the residual branch's cotangent
-            srcs = [(head.dbuf, self._dslabs(head), head.dbuf.shape[1])]
-            if ds is not None:
-                if not group:
-                    self._adjoint_unit(ds, [(last.g, 1, 0)])
-                srcs.append((ds.dbuf, self._dslabs(ds), ds.dbuf.shape[1]))
-            else:
-                srcs.append((last.g, 1, 0))
-            if bi > 0:
-                incoming[id(self.blocks[bi - 1][0][-1])] = srcs
-            else:
-                pool_srcs = srcs
-        return pool_srcs if last_block == 0 else incoming
-
-    def _adjoint_stem(self, pool_srcs):
-        """Block 0's input is the pooled stem output: sum its two cotangents, undo the max-pool,
-        then the stem's own adjoint."""
-        s = self.stem
-        if s.dead or pool_srcs is None:  # (frozen stem: nothing to differentiate)
-            return
-        ks, st_, pd, dl, cm = self.pool_args
-        pn, ph, pw, poh, pow_, c0 = self._pool_geometry()
-        self._extras_wait(pool_srcs)
-        # slab sums of both cotangents and the max-pool adjoint (gather form) in one launch
-        g_stem = self._g_stem
-        (kh, kw), (sh, sw), (pph, ppw) = _pair(ks), _pair(st_ if st_ is not None else ks), _pair(pd)
-        self._launch("hf_maxpool_adjoint_nhwc", g_stem, *sources("max-pool", pool_srcs), self.pool_idx32, pn, ph, pw, poh,
-                     pow_, c0, kh, kw, sh, sw, pph, ppw)
-        self._adjoint_unit(s, [(g_stem, 1, 0)])
-
-    def _feature_cotangent(self, g_feat):
-        tail = self.tail
-        if self._head_hw == 1:
-            return g_feat.view(tail.y.shape)
-        return _cl((g_feat / self._head_hw).view(g_feat.shape[0], -1, 1, 1).expand(tail.y.shape))
-
-    def _head_entries(self, tensors, splits, g_fw, g_fb):
-        """The head's weight / bias gradients as entries of ``hf_pack_ex``'s tables (copies of them)."""
-        tensors, splits = list(tensors), dict(splits)
-        if g_fw.dim() == 3:  # the head kernel's per-workgroup partial sums: slabs for hf_pack_ex
-            tensors[self.pfw] = g_fw[0]
-            splits[self.pfw] = (g_fw.shape[0], g_fw[0].numel())
-            if self.pfb is not None:
-                tensors[self.pfb] = g_fb[0]
-                splits[self.pfb] = (g_fb.shape[0], g_fb.shape[1])
-        else:
-            tensors[self.pfw] = g_fw
-            if self.pfb is not None:
-                tensors[self.pfb] = g_fb
-        return tensors, splits
-
     def _gather(self, out, g_fw, g_fb, first_order=False):
         """All parameter gradients into the flat vector (weight-gradient slabs summed on the way)."""
         self._flush_sums()
         tensors, perms, splits = self._pack_args(first_order)
-        tensors, splits = self._head_entries(tensors, splits, g_fw, g_fb)
+        if g_fw is not None:  # (a head with parameters of its own)
+            tensors, splits = self._head_entries(tensors, splits, g_fw, g_fb)
         _lib.pack_ex(out, tensors, perms, splits, scale=self.weight, live=self._pack_live,
-                     compact=getattr(self, "_compact_nl", None))  # (local_compact: the compact layout)
+                     compact=self._compact_nl)  # (local_compact: the compact layout)
         return out
 
     def _gather_range(self, out, g_fw, g_fb, lo, hi):
@@ -248,7 +164,7 @@ class _AdjointSweep:
                     else:
                         splits.pop(u.pg, None)
             return tensors, perms, splits
-        if getattr(self, "_pack", None) is None:
+        if self._pack is None:
             tensors, perms, splits = [None] * len(self.params), {}, {}
             self._pack_live = {}
             for u in self.units:

@@ -1,10 +1,11 @@
 """What every engine kind is, and nothing about convolutions: the contract sessions and the optimizer read, the choice
 of a kind for a model (``try_build``), the shared pieces of the kinds' constructors and the first-use check.
 
-The kinds: ``FusedGGNEngine`` (engine/core.py, with the conv mixins), ``PlainStackEngine`` (engine/plain.py, a
-``FusedGGNEngine``) and ``DenseStackEngine`` (engine/dense.py, this base alone).  A kind provides ``_layout``,
-``_allocate``, ``forward_own``, ``_load_recorded``, ``_loss_setup``, ``local``, ``gradient`` and -- with a ``loss_spec`` --
-``set_batch`` / ``set_targets`` / ``refresh_weights`` / ``layer_signature``."""
+The kinds: ``FusedGGNEngine`` (engine/core.py: residual nets) and ``PlainStackEngine`` (engine/plain.py: conv + bias
+stacks), siblings on ``_ConvEngine`` (engine/conv.py: the conv mixins, one constructor, one ``local``, one ``gradient``;
+its docstring lists the hooks a conv kind supplies), and ``DenseStackEngine`` (engine/dense.py, this base alone).  A kind
+provides ``_layout``, ``_allocate``, ``forward_own``, ``_load_recorded``, ``_loss_setup``, ``local``, ``gradient`` and --
+with a ``loss_spec`` -- ``set_batch`` / ``set_targets`` / ``refresh_weights`` / ``layer_signature``."""
 
 import os
 import warnings

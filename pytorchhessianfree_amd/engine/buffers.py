@@ -1,15 +1,14 @@
 """Every buffer the sweeps touch -- owned by the engine and STATIC -- and the launches that fill them per batch /
 per parameter point: split-K slab buffers, [t_x | x] / [W | v_W] operands, (I,H,W,O) weight copies, targets.
 
-Mixin of ``FusedGGNEngine`` (engine/core.py); see that class for the sweeps' overall structure."""
+Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overall structure."""
 
 import os
 
 import torch
-from torch import nn
 
 from .. import _lib
-from .common import _Unsupported, _flat_view, _live_taps, _pair
+from .common import _Unsupported, _flat_view, _live_taps
 from .problems import bn_adjoint_args, chan_sums_problem
 
 
@@ -84,8 +83,6 @@ class _Buffers:
 
         self._nhwc = nhwc
         self.x_in = nhwc(self._in_shape)
-        if self.pool_args is not None:
-            self.pool_out = nhwc(self.pool_out.shape)
         for u in self.units:
             u.a, u.y = nhwc(u.a.shape), nhwc(u.y.shape)
             if u.pool is not None:  # (plain stack) the pooled map -- what the consumer reads -- and the windows' positions
@@ -96,14 +93,14 @@ class _Buffers:
             elif u.bn is not None:
                 u.rstd = torch.rsqrt(u.bn.running_var + u.bn.eps)
                 u.rstd_version = u.bn.running_var._version
-        tails = {id(c[-1]): c[0] for c, _, _ in self.blocks}
         for u in self.units:  # the convolution's input IS its producer's output buffer
-            u.x = (self.x_in if u.src == "input" else self.pool_out if u.src == "pool"
+            u.x = (self.x_in if u.src == "input" else u.src if isinstance(u.src, torch.Tensor)
                    else u.src.yp if u.src.pool is not None else u.src.y)
+        for u in self.units:
             if u.res_unit is not None:
                 u.res = u.res_unit.y
-            elif u.res_identity:
-                u.res = tails[id(u)].x  # the block input
+            elif u.res_identity is not None:
+                u.res = u.res_identity.x  # the block input
             else:
                 u.res = None
         xcats = {}
@@ -256,20 +253,10 @@ class _Buffers:
         self._frozen_seen = {}
         self._vt_slots = [(self._offs[u.pw], u.vT, u.x.shape[1]) for u in self.units
                           if self.hessian and not u.im2col and u.sD and u.pw is not None]
-        self._allocate_pool()
         self._allocate_head()
         # the parameters as ONE flat vector, when they are consecutive views of one (the optimizer's
         # arena): every W half is then refreshed by a single scatter launch
         self._flat_params = _flat_view(self.params, self.n)
-
-    def _adjoint_order(self):
-        """The units in the order the adjoint sweep visits them."""
-        if not self.blocks:
-            return list(reversed(self.units))
-        order = []
-        for chain, ds, _x in reversed(self.blocks):
-            order += list(reversed(chain)) + ([ds] if ds is not None else [])
-        return order + ([self.stem] if self.stem is not None else [])
 
     def _allocate_sums_table(self):
         """The deferred units' sums problems as ONE table in device memory, in adjoint-sweep order (static pointers: built
@@ -328,32 +315,6 @@ class _Buffers:
                          len(self._sums_tab), first, count)
             self.sums_launches += 1
         self._sums_pending.clear()
-
-    def _allocate_pool(self):
-        self.pool_t = self._xcats.get(id(self.pool_out))
-        if self.pool_t is None:
-            raise _Unsupported("nothing consumes the pooled stem output")
-        if _pair(self.pool_args[3]) != [1, 1] or self.pool_args[4]:
-            raise _Unsupported("max-pool with dilation / ceil_mode")
-        self.pool_idx32 = torch.empty(tuple(self.pool_out.permute(0, 2, 3, 1).shape), dtype=torch.int32,
-                                      device=self.dev)
-        self._g_stem = torch.empty_like(self.stem.y)
-
-    def _allocate_head(self):
-        """Classifier head: (global average pool ->) linear layer."""
-        f32, dev = torch.float32, self.dev
-        tail = self.tail
-        n, k = tail.y.shape[0], tail.y.shape[1]
-        self._head_hw = tail.y.shape[2] * tail.y.shape[3]
-        if self._head_hw == 1:
-            self.feat = tail.y.permute(0, 2, 3, 1).reshape(n, k)  # a view: NHWC with a 1x1 map is [n, k]
-            if self.feat.data_ptr() != tail.y.data_ptr():
-                raise _Unsupported("feature view")
-        else:
-            self.feat = torch.empty((n, k), dtype=f32, device=dev)
-        self.logits = torch.empty((n, self.fc.weight.shape[0]), dtype=f32, device=dev)
-        self._p = torch.empty_like(self.logits)
-        self.loss_buf = torch.zeros((), dtype=f32, device=dev)
 
     def _plan_stem(self, direction, geo):
         n, h, w, c, k, r, s, st, pd = geo
@@ -462,12 +423,6 @@ class _Buffers:
         """A plain per-channel reduction by the BatchNorm adjoint's launch (``problems.chan_sums_problem``)."""
         self._launch("hf_chan_affine_bwd_ex",
                      *bn_adjoint_args(chan_sums_problem(gy, splits, slab, n, c, hw, row_blocks, **operands)))
-
-    # ---- tangent sweep -------------------------------------------------------------------------
-    def _pool_geometry(self):
-        """(n, h, w, oh, ow, c) of the stem's max-pool (window maxima's positions: ``forward_own``)."""
-        pn, _, ph, pw = self.stem.y.shape
-        return pn, ph, pw, self.pool_out.shape[2], self.pool_out.shape[3], self.pool_out.shape[1]
 
     def _tgeo(self, u):
         n, h, w, c, k, r, s, st, pd = u.geo

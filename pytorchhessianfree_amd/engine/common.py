@@ -54,9 +54,9 @@ class _Unit:
         self.mean_t = None        # the statistics' dependence on the layer input
         self.epi = self.tsum = False  # train mode: the tangent's partial sums come from the convolution's epilogue
         self.res_unit = None      # downsample unit whose output is added before the activation
-        self.res_identity = False  # ... or the block input itself
+        self.res_identity = None  # ... or the block input itself: the block's first unit, which reads it
         self.consumers = 0
-        self.src = None           # what the convolution reads: "input", "pool" or the producing unit
+        self.src = None           # what the convolution reads: "input", the producing unit or a buffer of the kind's own
         self.dead = False         # frozen, behind frozen layers only: no tangent, no cotangent (topology._mark_dead_prefix)
         self.no_dgrad = False     # a live unit whose input carries no tangent: its data gradient is not needed
         self.pool = None          # plain stack: (kh, kw, sh, sw, ph, pw) of the MaxPool2d behind the unit (its ReLU)

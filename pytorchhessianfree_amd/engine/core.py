@@ -33,28 +33,18 @@ the autograd operator.  The first product of every model signature is compared w
 operator's product on a random vector.
 """
 
-import os
-
 import torch
 
 from .. import _lib
-from ..curvature import GGNOperator
-from .common import _Launcher, _Node, _Unsupported, _ce_node, ce_loss_spec, loss_spec_of  # noqa: F401
-from .adjoint import _AdjointSweep
-from .base import _Engine
-from .buffers import _Buffers
-from .dataparallel import _DataParallel
-from .diag_ef import _DiagEF
-from .forward import _Forward
-from .hessian import _HessianExtras
-from .tangent import _TangentSweep
+from .common import _Unsupported, _cl, _pair
+from .conv import _ConvEngine
+from .problems import sources
+from .tangent import head_fused_shape_ok
 from .topology import _Topology
 
 
-class FusedGGNEngine(_Topology, _Buffers, _Forward, _TangentSweep, _AdjointSweep, _HessianExtras, _DiagEF, _DataParallel,
-                     _Engine):
-    # (the base LAST: ``_DataParallel`` overrides its single-process ``reduce`` / ``reduce_bytes``; ``try_build``, the
-    # contract's defaults, ``unavailable`` and the constructors' shared pieces stand in engine/base.py)
+class FusedGGNEngine(_Topology, _ConvEngine):
+    # (``_Topology``: the residual layout, dead prefix, two-phase split; here its walks, the stem's max-pool, the head)
     mode = ("fused curvature engine: own deterministic convolutions (split-K slabs summed by the consumer "
             "kernel), BatchNorm tangents/adjoints fused, 4 launches per conv-BN unit, downsample branches grouped "
             "with their block's first convolution")
@@ -66,152 +56,365 @@ class FusedGGNEngine(_Topology, _Buffers, _Forward, _TangentSweep, _AdjointSweep
     # scale's own second-order terms  g_a' += g_z * rstd * v_gamma ,  g_gamma' += sum g_z * rstd * t_a .
     # TRAIN-mode BatchNorm (round 5): the batch statistics' share of the adjoint's tangent in closed form per channel
     # (hf_bn_train_hessian_coeffs / _apply; the formulas stand in csrc/hf_bn.hip and DESIGN.md section 4.3).
-    supports_hessian = True
     supports_two_phase = True  # (phase_split / local_phase_a / local_phase_b: the chunked, overlapped all-reduce)
+    supports_compact = True    # (compact_layout / local_compact)
 
-    def __init__(self, model, loss, outputs, params, weight, group, hessian=False):
-        self._begin(params, weight, group, outputs, hessian)
-        self._second = False  # (inside the adjoint sweep of a Hessian product)
-        self._diag_batched = os.environ.get("HF_DIAG_EF_BATCHED", "0") == "1"  # (diag_ef: one launch per layer)
-        self.dead_blocks = 0
-        self._layout(model)
-        if self.hessian:
-            for u in self.units:
-                u.needs_g = True  # (the first-order masked cotangent of every unit is kept)
-        self._allocate()
-        self.set_batch(getattr(outputs, "_hf_input").detach(), None)
-        self.refresh_weights(transposed=True)
-        self.train_own = False
-        if self.train_bn:
-            # train-mode BatchNorm: the engine linearises at the activations and batch statistics the MODEL's
-            # forward pass recorded.  Its own forward pass (batch statistics by own kernels, running statistics
-            # moved as the layers' forward moves them) lets a persistent session serve such a model too -- if it
-            # reproduces the model's output here (with the running statistics left alone)
-            if (all(u.bn.momentum is not None and u.bn.track_running_stats for u in self.units if u.train)):
-                self.forward_own(update_running=False)
-                self.train_own = self._forward_error(outputs) < 1e-4
-            self._load_recorded(outputs)
+    # ---- buffers of the stem's max-pool and of the head ---------------------------------------------------
+    def _allocate_pool(self):
+        self.pool_t = self._xcats.get(id(self.pool_out))
+        if self.pool_t is None:
+            raise _Unsupported("nothing consumes the pooled stem output")
+        if _pair(self.pool_args[3]) != [1, 1] or self.pool_args[4]:
+            raise _Unsupported("max-pool with dilation / ceil_mode")
+        self.pool_idx32 = torch.empty(tuple(self.pool_out.permute(0, 2, 3, 1).shape), dtype=torch.int32,
+                                      device=self.dev)
+        self._g_stem = torch.empty_like(self.stem.y)
+
+    def _allocate_head(self):
+        """Classifier head: (global average pool ->) linear layer."""
+        self._allocate_pool()
+        f32, dev = torch.float32, self.dev
+        tail = self.tail
+        n, k = tail.y.shape[0], tail.y.shape[1]
+        self._head_hw = tail.y.shape[2] * tail.y.shape[3]
+        if self._head_hw == 1:
+            self.feat = tail.y.permute(0, 2, 3, 1).reshape(n, k)  # a view: NHWC with a 1x1 map is [n, k]
+            if self.feat.data_ptr() != tail.y.data_ptr():
+                raise _Unsupported("feature view")
         else:
-            # own forward pass on the engine's static buffers; it must reproduce the model's output
-            self.forward_own()
-            self._check_forward(outputs)
-        self._loss_setup(loss, outputs)
-        self._verify(loss)
-        # ONE linearisation point after construction, whether or not the first-use check ran (it is skipped for a
-        # model signature that has passed before): the engine's OWN forward pass where it has one, else -- a
-        # train-mode model whose layers the own pass does not reproduce -- everything the model recorded, batch
-        # statistics included.  (Round 4 left a train-mode engine whose check was skipped at the recorded
-        # activations with its own statistics: 3.65e-6 / one ReLU decision away from the checked one, GPUTEST_r04.)
-        if self._at != "own" and (not self.train_bn or self.train_own):
-            self.forward_own(update_running=False)  # (eval mode: nothing to move)
-            if self.hessian:
-                self.gradient()  # the first-order cotangents the Hessian products read, at the same point
-        for u in self.units:  # the model's own activations were only needed up to here
-            u.rx = u.ry = u.ra = u.rp = None
-            u.rec_stats = None
-        self._rec_pool = None
-        self._release(model)
+            self.feat = torch.empty((n, k), dtype=f32, device=dev)
+        self.logits = torch.empty((n, self.fc.weight.shape[0]), dtype=f32, device=dev)
+        self._p = torch.empty_like(self.logits)
+        self.loss_buf = torch.zeros((), dtype=f32, device=dev)
 
-    # ---- loss Hessian (same contract as GGNOperator) -------------------------------------
-    def _loss_setup(self, loss, outputs):
-        self._closed_form(loss, outputs)
-        # a plain softmax cross-entropy (checked numerically above): the engine can then evaluate
-        # loss, probabilities and d loss / d logits itself, on its own forward pass -- which is what
-        # lets ONE engine serve many steps and trial points (``session.EngineSession``)
-        # ... or a mean-squared error (round 6; the loss of the reference's own examples / tests): gradient
-        # 2c (out - t), Hessian 2c I
-        self.loss_spec = None
-        if not self.train_bn or self.train_own:
-            spec = loss_spec_of(loss, outputs)
-            if spec is not None and (spec["kind"] == "mse" or self._ce is not None):
-                self.loss_spec = spec
-                self._set_quadratic(spec.get("quadratic"))
-                self.set_targets(spec["targets"])
-                if spec["kind"] == "mse":
-                    self._ce = None
-                    self._mse2 = 2.0 / float(outputs.numel()) if spec["reduction"] == "mean" else 2.0
-                self._loss_head()
-                if spec["kind"] == "ce":
-                    self._ce = (self._p, self._ce[1])  # the static buffer the own forward pass refreshes
-                self._dl = None                        # (nothing of this step's autograd graph is kept)
+    def _pool_geometry(self):
+        """(n, h, w, oh, ow, c) of the stem's max-pool (window maxima's positions: ``forward_own``)."""
+        pn, _, ph, pw = self.stem.y.shape
+        return pn, ph, pw, self.pool_out.shape[2], self.pool_out.shape[3], self.pool_out.shape[1]
+
+    def _adjoint_order(self):
+        """The units in the order the adjoint sweep visits them."""
+        order = []
+        for chain, ds, _x in reversed(self.blocks):
+            order += list(reversed(chain)) + ([ds] if ds is not None else [])
+        return order + [self.stem]
+
+    # ---- forward -----------------------------------------------------------------------------
+    def _forward_units(self, refresh, update_running):
+        s = self.stem
+        flat = self._flat_params
+        carried = (refresh and flat is not None and flat.data_ptr() == self.params[0].data_ptr()
+                   and self._conv_carrying_scatter(s, s.conv.weight.detach(), s.sF, flat, 0))
+        if not carried:
+            if refresh:
+                self.refresh_weights()
+            self._conv_forward(s)
+        self._bn_forward(s, s.sF, update_running)
+        ks, st_, pd, _dl, _cm = self.pool_args
+        pn, ph, pw, poh, pow_, c0 = self._pool_geometry()
+        (kh, kw), (sh, sw), (pph, ppw) = _pair(ks), _pair(st_ if st_ is not None else ks), _pair(pd)
+        self._launch("hf_maxpool_forward_nhwc", self.pool_out, self.pool_t[:, c0:], 2 * c0, self.pool_idx32, s.y, pn, ph, pw,
+                     poh, pow_, c0, kh, kw, sh, sw, pph, ppw)
+        for chain, ds, _x in self.blocks:
+            if ds is not None:
+                self._conv_forward(ds)
+                self._bn_forward(ds, ds.sF, update_running)
+            for u in chain:
+                self._conv_forward(u)
+                self._bn_forward(u, u.sF, update_running)
+        if self._head_hw > 1:
+            torch.mean(self.tail.y, dim=(2, 3), out=self.feat)
+        fw = self.fc.weight.detach()
+        if self.pfb is not None:
+            torch.addmm(self.fc.bias.detach(), self.feat, fw.t(), out=self.logits)
+        else:
+            torch.mm(self.feat, fw.t(), out=self.logits)
+
+    def _load_recorded(self, outputs):
+        super()._load_recorded(outputs)
+        ks, st_, pd, dl, cm = self.pool_args  # the positions of the MODEL's windows, its pooled map, its features
+        _, idx = torch.nn.functional.max_pool2d(self.stem.ry, ks, st_, pd, dl, cm, return_indices=True)
+        self.pool_idx32.copy_(idx.permute(0, 2, 3, 1))
+        self.pool_out.copy_(self.stem.rp)
+        c0 = self.pool_out.shape[1]
+        self.pool_t[:, c0:].copy_(self.stem.rp)
+        if self._head_hw > 1:
+            torch.mean(self.tail.y, dim=(2, 3), out=self.feat)
+
+    # ---- tangent sweep -------------------------------------------------------------------------
+    def _tangent_sweep(self, v):
+        self._tangent_stem(v)  # + the v_W halves of all [W | v_W] operands, same launch
+        self._tangent_blocks(v)
+
+    def _tangent_stem(self, v):
+        """Stem: conv(x, v_W) as a 1x1 convolution on the im2col'd input (the input has no tangent; v_W is a
+        slice of ``v`` itself).  The launch also carries the scatter of every other layer's v_W into its ``[W | v_W]``
+        operand (``hf_conv2d_nhwc_slabs_unpack``) -- nothing in the stem reads those."""
+        s = self.stem
+        if s.dead:  # (frozen stem: its output carries no tangent -- only the scatter it would have carried is left)
+            if self._slot_list:
+                _lib.unpack_tangent(v, self._slot_list)
+            return
+        if s.pw is None:  # (frozen stem weight under a trainable BatchNorm: conv(x, 0) = 0)
+            vw = self._zeros(s.conv.weight.numel())
+        else:
+            vw = v[self._offs[s.pw]: self._offs[s.pw] + s.conv.weight.numel()]
+        if not self._conv_carrying_scatter(s, vw, s.sT, v, 1):
+            _lib.unpack_tangent(v, self._slot_list)  # v_W halves of all [W | v_W] operands: one launch
+            self._conv_slabs(0, s.tbuf, s.cols, vw, s.geo, s.sT)
+        self._bn_tangent(s, v, None, 0)
+        pn, ph, pw, poh, pow_, c0 = self._pool_geometry()
+        self._launch("hf_maxpool_tangent_nhwc", self.pool_t, s.tout, self.pool_idx32, pn, ph, pw, poh, pow_, c0, 2 * c0)
+
+    def _tangent_blocks(self, v):
+        group = self._grouping()
+        for chain, ds, _x in self.blocks[self.dead_blocks:]:  # (dead blocks: frozen, behind frozen layers -- no tangent)
+            head = chain[0]
+            paired = False
+            if ds is not None and group:
+                # the downsample branch and the block's first convolution read the same operand:
+                # both tangent convolutions in ONE launch
+                self._tangent_convs([ds, head])
+                alone = head.res_unit is None and head.res_identity is None and len(chain) > 1
+                paired = alone and not head.train and not ds.train
+                if paired:  # ... and both BatchNorm tangents in one
+                    self._bn_tangent_pair(ds, head, v)
+                elif alone and self._train_pair_ok(ds, head) and ds.tsum and head.tsum:
+                    self._bn_tangent_pair_train(ds, head, v)  # (train mode: the same, prologue form)
+                    paired = True
+                else:
+                    self._bn_tangent(ds, v, None, 0)
+            elif ds is not None:
+                self._tangent_convs([ds])
+                self._bn_tangent(ds, v, None, 0)
+            for u in chain:
+                if u is head and paired:
+                    continue
+                if not (u is head and ds is not None and group):
+                    self._tangent_convs([u])
+                add, add_ld = None, 0
+                if u.res_unit is not None:
+                    add, add_ld = u.res_unit.tout, u.res_unit.tout_ld
+                elif u.res_identity is not None:
+                    c = head.x.shape[1]
+                    add, add_ld = head.xcat[:, :c], 2 * c
+                self._bn_tangent(u, v, add, add_ld)
+
+    # ---- classifier head: logits' tangent, loss Hessian, the head's gradients ----------------------
+    def _head(self, v):
+        """Returns the cotangent of the last unit's output and the head's weight / bias gradients."""
+        tail = self.tail
+        t_last = tail.tout
+        hw = t_last.shape[2] * t_last.shape[3]
+        fw = self.fc.weight
+        v_fw = self._param_slice(v, self.pfw, fw.numel()).view_as(fw)
+        v_fb = self._param_slice(v, self.pfb, fw.shape[0])
+
+        def loss_hessian_of_jv():
+            t_feat = t_last.flatten(1) if hw == 1 else t_last.mean(dim=(2, 3))
+            if self.pfb is not None:
+                Jv = torch.addmm(v_fb, t_feat, fw.detach().t())
+            else:
+                Jv = t_feat @ fw.detach().t()
+            return t_feat, self._loss_hessian(torch.addmm(Jv, self.feat, v_fw.t()))
+
         if self.hessian:
-            if self.loss_spec is None:
-                raise _Unsupported("Hessian products on the engine need a plain softmax cross-entropy or mean-squared-"
-                                   "error loss")
-            self.gradient()  # fills the first-order cotangents the Hessian products read
+            # forward-over-reverse through the linear head: besides H_L J v, the first-order cotangent g of the
+            # logits meets the tangents of the layer's two operands (g V -> features, g^T t_feat -> weight)
+            t_feat, HJv = loss_hessian_of_jv()
+            g_fw = torch.addmm(self._gl1.t() @ t_feat, HJv.t(), self.feat)
+            g_fb = HJv.sum(0) if self.pfb is not None else None
+            g_feat = torch.addmm(self._gl1 @ v_fw, HJv, fw.detach())
+            return self._feature_cotangent(g_feat), g_fw, g_fb
+        if self._head_fused(hw, v_fw):
+            # ONE launch: logits' tangent, softmax-CE Hessian, the three gradients
+            g_feat, g_fw, g_fb = self._head_bufs
+            self._launch("hf_linear_ce_head", g_feat, g_fw, g_fb if self.pfb is not None else None, t_last, self.feat,
+                         fw, v_fw, v_fb, self._ce[0], float(self._ce[1]), g_feat.shape[0], g_feat.shape[1], fw.shape[0])
+            if self.pfb is None:
+                g_fb = None
+        else:
+            _t_feat, HJv = loss_hessian_of_jv()
+            g_fw = HJv.t() @ self.feat
+            g_fb = HJv.sum(0) if self.pfb is not None else None
+            g_feat = HJv @ fw.detach()
+        return self._feature_cotangent(g_feat), g_fw, g_fb
 
-    def gradient(self, out=None):
-        """``weight * d loss / d params`` of the softmax cross-entropy by ONE adjoint sweep of the
-        engine (the gradient the reference takes with ``torch.autograd.grad``, optimizer.py:231-234),
-        on the activations of the last ``forward_own``."""
-        if self.loss_spec is None:
-            raise RuntimeError("engine.gradient needs a softmax cross-entropy loss")
-        if out is None:
-            out = torch.empty(self.n, dtype=torch.float32, device=self.dev)
-        g = self._dlogits()  # d loss / d logits
+    def _first_order_seed(self):
+        """The gradient sweep's seed: ``d loss / d logits`` through the linear layer."""
+        g = self._dlogits()
         fw = self.fc.weight.detach()
         g_fw = g.t() @ self.feat
         g_fb = g.sum(0) if self.pfb is not None else None
         g_feat = g @ fw
-        if self.hessian:
-            # the first-order cotangents stay for the step's Hessian products: the sweep below writes the units'
-            # g1 / ga1 instead of g / ga (buffers swapped for its duration)
-            if getattr(self, "_gl1", None) is None:
+        if self.hessian:  # (the head of a Hessian product reads the logits' first-order cotangent)
+            if self._gl1 is None:
                 self._gl1 = torch.empty_like(g)
             self._gl1.copy_(g)
-            self._swap_first_order()
-        try:
-            pool_srcs = self._adjoint_blocks(self._feature_cotangent(g_feat))
-            self._adjoint_stem(pool_srcs)
-        finally:
-            if self.hessian:
-                self._swap_first_order()
-        self._gather(out, g_fw, g_fb, first_order=True)
-        if self.hessian and self.train_bn:
-            for u in self.units:  # the layer's own first-order parameter gradients: hf_bn_train_hessian_coeffs reads them
-                if u.train:
-                    torch.sum(u.gw[:u.rb], 0, out=u.gg1)
-                    torch.sum(u.gb, 0, out=u.gb1)
-        self._add_quadratic(out)
-        return out
+        return self._feature_cotangent(g_feat), g_fw, g_fb
 
-    def _dlogits(self):
-        """``d loss / d logits`` of the engine's own loss head at the current logits."""
-        if self.loss_spec["kind"] == "mse":
-            return (self.logits - self._targets) * self._mse2
-        return (self._p - self._onehot) * self._ce[1]
+    def _head_fused(self, hw, v_fw):
+        """Whether ``hf_linear_ce_head`` applies: closed-form softmax-CE Hessian, a 1x1 final map
+        (the pooling is then the identity), a small dense head, 16-byte aligned operands."""
+        ok = getattr(self, "_head_ok", None)
+        if ok is None:
+            fw = self.fc.weight
+            k, f = fw.shape
+            ok = (
+                self._ce is not None and hw == 1
+                and fw.is_contiguous() and fw.dtype == torch.float32
+                and head_fused_shape_ok(self.logits.shape[0], f, k)
+                and self.feat.is_contiguous() and tuple(self.feat.shape) == (self.logits.shape[0], f)
+                and self._offs[self.pfw] % 4 == 0 and self._ce[0].is_contiguous()
+            )
+            if ok:
+                b = self.logits.shape[0]
+                g = _lib.load().hf_linear_ce_head_slabs(b)  # partial sums per workgroup, added up by hf_pack_ex
+                kw = dict(dtype=torch.float32, device=self.dev)
+                self._head_bufs = (torch.empty((b, f), **kw), torch.empty((g, k, f), **kw),
+                                   torch.empty((g, k), **kw))
+            self._head_ok = ok
+        return ok and v_fw.data_ptr() % 16 == 0
 
-    def _loss_hessian(self, Jv):
-        if self.loss_spec is not None and self.loss_spec["kind"] == "mse":
-            return Jv * self._mse2
-        return GGNOperator._loss_hessian(self, Jv)
+    def _grouping(self):
+        # (Hessian products carry extra terms per unit: the plain one-unit launches)
+        return not self.hessian
 
-    # ---- the product -------------------------------------------------------------------------
-    def local(self, v, out=None):
-        v, out = self._product_vectors(v, out)
-        self._tangent_stem(v, carry_scatter=True)  # + the v_W halves of all [W | v_W] operands, same launch
-        self._tangent_blocks(v)
-        if self.hessian:
-            if self._vt_slots:
-                _lib.unpack_tangent(v, self._vt_slots, half=2)  # V as (I, H, W, O): the operand of conv_D(g, V)
-            self._second, self._v = True, v
-            self._extras_fork()
-        try:
-            g_last, g_fw, g_fb = self._head(v)
-            pool_srcs = self._adjoint_blocks(g_last)
-            self._adjoint_stem(pool_srcs)
-            if self.hessian:
-                self._extras_join()
-        finally:
-            self._second, self._v = False, None
-        self._gather(out, g_fw, g_fb)
-        if self.hessian:  # the regulariser's Hessian: coef on its tensors' entries
-            self._add_quadratic(out, v)
-        return out
+    # ---- adjoint sweep -------------------------------------------------------------------------
+    def _adjoint_sweep(self, g_last):
+        self._adjoint_stem(self._adjoint_blocks(g_last))
+
+    def _adjoint_blocks(self, g_last, first=None, last_block=0, incoming=None):
+        """Walks the blocks ``first`` (default: the last one) ... ``last_block`` backwards; returns the
+        two cotangents of the pooled stem output -- or, when the walk stops before block 0, the state
+        (``incoming``) a later call continues from (the product in two phases, ``local_phases``)."""
+        group = self._grouping()
+        tail = self.tail
+        if incoming is None:
+            incoming = {id(tail): [(g_last, 1, 0)]}
+        pool_srcs = None
+        first = len(self.blocks) - 1 if first is None else first
+        stop = max(last_block, self.dead_blocks)  # (dead blocks: nobody needs their cotangents)
+        for bi in range(first, stop - 1, -1):
+            chain, ds, _x = self.blocks[bi]
+            head, last = chain[0], chain[-1]
+            for k in range(len(chain) - 1, -1, -1):
+                u = chain[k]
+                if k == 0 and ds is not None and group:
+                    # both BatchNorm adjoints, then the data + weight gradients of the block's first
+                    # convolution AND of its downsample branch in ONE launch (four problems)
+                    if u.rb > 1 and ds.rb > 1 and not u.train and not ds.train:
+                        self._bn_adjoint_pair(u, incoming.pop(id(u)), ds, [(last.g, 1, 0)])
+                    elif u.rb > 1 and ds.rb > 1 and self._train_pair_ok(u, ds):
+                        self._bn_adjoint_pair_train(u, incoming.pop(id(u)), ds, [(last.g, 1, 0)])
+                    else:
+                        self._bn_adjoint(u, incoming.pop(id(u)))
+                        self._bn_adjoint(ds, [(last.g, 1, 0)])
+                    if u.no_dgrad:  # (the block input carries no tangent: the two weight gradients only)
+                        _lib.conv_group_slabs(
+                            [(2, u.wbuf, u.x, u.ga, u.geo, u.sW, 0, 0), (2, ds.wbuf, ds.x, ds.ga, ds.geo, ds.sW, 0, 0)],
+                            self.dev)
+                    else:
+                        _lib.conv_group_slabs(
+                            [(1, u.dbuf, u.ga, u.wT, u.geo, u.sD, 0, 0), (2, u.wbuf, u.x, u.ga, u.geo, u.sW, 0, 0),
+                             (1, ds.dbuf, ds.ga, ds.wT, ds.geo, ds.sD, 0, 0),
+                             (2, ds.wbuf, ds.x, ds.ga, ds.geo, ds.sW, 0, 0)], self.dev)
+                else:
+                    self._adjoint_unit(u, incoming.pop(id(u)))
+                if k > 0:
+                    incoming.setdefault(id(chain[k - 1]), []).append((u.dbuf, self._dslabs(u), u.dbuf.shape[1]))
+            if head.no_dgrad:  # (everything in front of this block is frozen: the sweep ends here)
+                if ds is not None and not group:
+                    self._adjoint_unit(ds, [(last.g, 1, 0)])
+                return None
+            # the block input receives conv1's data gradient and the residual branch's cotangent
+            srcs = [(head.dbuf, self._dslabs(head), head.dbuf.shape[1])]
+            if ds is not None:
+                if not group:
+                    self._adjoint_unit(ds, [(last.g, 1, 0)])
+                srcs.append((ds.dbuf, self._dslabs(ds), ds.dbuf.shape[1]))
+            else:
+                srcs.append((last.g, 1, 0))
+            if bi > 0:
+                incoming[id(self.blocks[bi - 1][0][-1])] = srcs
+            else:
+                pool_srcs = srcs
+        return pool_srcs if last_block == 0 else incoming
+
+    def _adjoint_stem(self, pool_srcs):
+        """Block 0's input is the pooled stem output: sum its two cotangents, undo the max-pool,
+        then the stem's own adjoint."""
+        s = self.stem
+        if s.dead or pool_srcs is None:  # (frozen stem: nothing to differentiate)
+            return
+        ks, st_, pd, dl, cm = self.pool_args
+        pn, ph, pw, poh, pow_, c0 = self._pool_geometry()
+        self._extras_wait(pool_srcs)
+        # slab sums of both cotangents and the max-pool adjoint (gather form) in one launch
+        g_stem = self._g_stem
+        (kh, kw), (sh, sw), (pph, ppw) = _pair(ks), _pair(st_ if st_ is not None else ks), _pair(pd)
+        self._launch("hf_maxpool_adjoint_nhwc", g_stem, *sources("max-pool", pool_srcs), self.pool_idx32, pn, ph, pw, poh,
+                     pow_, c0, kh, kw, sh, sw, pph, ppw)
+        self._adjoint_unit(s, [(g_stem, 1, 0)])
+
+    def _feature_cotangent(self, g_feat):
+        tail = self.tail
+        if self._head_hw == 1:
+            return g_feat.view(tail.y.shape)
+        return _cl((g_feat / self._head_hw).view(g_feat.shape[0], -1, 1, 1).expand(tail.y.shape))
+
+    def _head_entries(self, tensors, splits, g_fw, g_fb):
+        """The head's weight / bias gradients as entries of ``hf_pack_ex``'s tables (copies of them)."""
+        tensors, splits = list(tensors), dict(splits)
+        if g_fw.dim() == 3:  # the head kernel's per-workgroup partial sums: slabs for hf_pack_ex
+            tensors[self.pfw] = g_fw[0]
+            splits[self.pfw] = (g_fw.shape[0], g_fw[0].numel())
+            if self.pfb is not None:
+                tensors[self.pfb] = g_fb[0]
+                splits[self.pfb] = (g_fb.shape[0], g_fb.shape[1])
+        else:
+            tensors[self.pfw] = g_fw
+            if self.pfb is not None:
+                tensors[self.pfb] = g_fb
+        return tensors, splits
+
+    # ---- diag_ef: the linear head in closed form -------------------------------------------------------
+    def _diag_head_buffers(self, tensors):
+        """(filled in closed form afterwards: zeros here)"""
+        self._diag_zero_fw = torch.zeros(self.fc.weight.numel(), dtype=torch.float32, device=self.dev)
+        tensors[self.pfw] = self._diag_zero_fw
+        if self.pfb is not None:
+            self._diag_zero_fb = torch.zeros(self.fc.weight.shape[0], dtype=torch.float32, device=self.dev)
+            tensors[self.pfb] = self._diag_zero_fb
+
+    def _diag_head(self, out, scale):
+        """The per-sample weight gradient is the outer product g_i x feat_i, so the sum of its squares is
+        (g o g)^T (feat o feat)."""
+        g = self._dlogits() * scale
+        nf = self.fc.weight.numel()
+        out[self._offs[self.pfw]: self._offs[self.pfw] + nf].copy_(((g * g).t() @ (self.feat * self.feat)).reshape(-1))
+        if self.pfb is not None:
+            out[self._offs[self.pfb]: self._offs[self.pfb] + g.shape[1]].copy_((g * g).sum(0))
+
+    # ---- the product in two phases (``phase_split``) -------------------------------------------------
+    def local_phase_a(self, v, out, split):
+        """Tangent sweep, head, adjoint sweep of blocks ``cut ...``, and the suffix of the product they
+        determine (``out[offset:]``)."""
+        cut, first, offset = split
+        v = v.detach()
+        self._tangent_sweep(v)
+        g_last, g_fw, g_fb = self._head(v)
+        self._phase_state = self._adjoint_blocks(g_last, last_block=cut)
+        self._gather_range(out, g_fw, g_fb, first, len(self.params))
+
+    def local_phase_b(self, out, split):
+        """The rest of the adjoint sweep and ``out[:offset]``."""
+        cut, first, offset = split
+        pool_srcs = self._adjoint_blocks(None, first=cut - 1, last_block=0, incoming=self._phase_state)
+        self._adjoint_stem(pool_srcs)
+        self._gather_range(out, None, None, 0, first)
 
     # ---- the product between vectors in the compact layout (dataparallel.compact_layout) ----------------
-    supports_compact = True
-
     def local_compact(self, vc, out):
         """``local`` on the entries that can be non-zero: ``vc`` and ``out`` are vectors of ``n_live`` entries in
         the compact layout.  Same launches, same buffers, same kernels as ``local``: only the scatter of the v_W
@@ -219,7 +422,7 @@ class FusedGGNEngine(_Topology, _Buffers, _Forward, _TangentSweep, _AdjointSweep
         ``hf_pack_compact``), and every slice of the vector is taken at its compact offset.  With dead entries of
         ``v`` zero, ``local_compact(gather(v)) == gather(local(v))`` bit for bit."""
         lay = self.compact_layout()
-        if lay is None or self.hessian or not self.supports_compact:
+        if lay is None or self.hessian:
             raise RuntimeError("engine: no compact layout for this product")
         slots = self.__dict__.get("_compact_slots")
         if slots is None:

@@ -1,36 +1,15 @@
 """Data parallelism (optimizer.py:677-684 across GPUs): only the entries of the product that can be non-zero travel;
 the product in two phases so that the all-reduce of the late layers overlaps the rest of the sweep.
 
-Mixin of ``FusedGGNEngine`` (engine/core.py); see that class for the sweeps' overall structure."""
-
-import os
+Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overall structure."""
 
 import torch
 
 from .. import _lib
 from ..curvature import _all_reduce_sum
-from .common import _live_taps
 
 
 class _DataParallel:
-    def local_phase_a(self, v, out, split):
-        """Tangent sweep, head, adjoint sweep of blocks ``cut ...``, and the suffix of the product they
-        determine (``out[offset:]``)."""
-        cut, first, offset = split
-        v = v.detach()
-        self._tangent_stem(v, carry_scatter=True)
-        self._tangent_blocks(v)
-        g_last, g_fw, g_fb = self._head(v)
-        self._phase_state = self._adjoint_blocks(g_last, last_block=cut)
-        self._gather_range(out, g_fw, g_fb, first, len(self.params))
-
-    def local_phase_b(self, out, split):
-        """The rest of the adjoint sweep and ``out[:offset]``."""
-        cut, first, offset = split
-        pool_srcs = self._adjoint_blocks(None, first=cut - 1, last_block=0, incoming=self._phase_state)
-        self._adjoint_stem(pool_srcs)
-        self._gather_range(out, None, None, 0, first)
-
     # ---- data parallelism: only the entries that can be non-zero travel ----------------------
     def _segment_table(self):
         """THE segment table of the flat vector (the one place that derives it): consecutive segments

@@ -1,7 +1,7 @@
 """Diagonal of the empirical Fisher from one adjoint sweep + per-sample weight-gradient launches
 (preconditioners.py:11-105) -- or, with ``HF_DIAG_EF_BATCHED=1``, + ONE squared-sum launch per layer and one gather.
 
-Mixin of ``FusedGGNEngine`` (engine/core.py); see that class for the sweeps' overall structure."""
+Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overall structure."""
 
 import torch
 
@@ -66,14 +66,7 @@ class _DiagEF:
                 elif u.pb is not None:
                     self._chan_sums(ga, 1, 0, 1, k, hw, 1, gb=u.gbs)
             _lib.pack_ex(out, tensors, perms, splits, scale=scale, live=self._pack_live, mode=1)
-        if self.fc is not None:
-            # linear head: the per-sample weight gradient is the outer product g_i x feat_i, so the sum of its squares
-            # is (g o g)^T (feat o feat)
-            g = self._dlogits() * scale
-            nf = self.fc.weight.numel()
-            out[self._offs[self.pfw]: self._offs[self.pfw] + nf].copy_(((g * g).t() @ (self.feat * self.feat)).reshape(-1))
-            if self.pfb is not None:
-                out[self._offs[self.pfb]: self._offs[self.pfb] + g.shape[1]].copy_((g * g).sum(0))
+        self._diag_head(out, scale)
         if l2 is not None:
             sum_a = mean_grad * (scale / self.weight)  # sum_i a_i
             b = l2 * self._theta()
@@ -81,6 +74,12 @@ class _DiagEF:
         if reduction == "mean":
             out.div_(float(n))
         return out
+
+    def _diag_head_buffers(self, tensors):
+        """A kind whose head has parameters: their entries of the gather's table ..."""
+
+    def _diag_head(self, out, scale):
+        """... and their values, written straight into ``out``."""
 
     def _diag_batched_launches(self, out, n, pre, first_order):
         """The batched sweep behind the adjoint sweep: per live unit one squared-sum convolution and one squared channel
@@ -111,7 +110,7 @@ class _DiagEF:
         """Per-sample (n = 1) geometry, split counts and slab buffers of ``diag_ef`` (allocated on first use).  Batched
         sweep: the whole-batch geometry (the im2col'd stem as a 1x1 convolution over its [n, oh, ow] map of patches), the
         planned sample splits, one slab per split and one partial row per share of the samples."""
-        if getattr(self, "_diag_pack", None) is not None:
+        if self._diag_pack is not None:
             return
         f32, dev = torch.float32, self.dev
         tensors, perms, splits = [None] * len(self.params), {}, {}
@@ -153,11 +152,6 @@ class _DiagEF:
                     tensors[pi] = buf[0]
                     if u.rb1 > 1:
                         splits[pi] = (u.rb1, k)
-        if self.fc is not None:  # (filled in closed form afterwards: zeros here)
-            self._diag_zero_fw = torch.zeros(self.fc.weight.numel(), dtype=f32, device=dev)
-            tensors[self.pfw] = self._diag_zero_fw
-            if self.pfb is not None:
-                self._diag_zero_fb = torch.zeros(self.fc.weight.shape[0], dtype=f32, device=dev)
-                tensors[self.pfb] = self._diag_zero_fb
+        self._diag_head_buffers(tensors)
         self._pack_args()  # (makes sure _pack_live exists)
         self._diag_pack = (tensors, perms, splits)

@@ -1,9 +1,7 @@
 """The terms of a Hessian product that do not depend on the adjoint chain (optimizer.py:450-455 by
 forward-over-reverse), issued on a parallel graph branch.
 
-Mixin of ``FusedGGNEngine`` (engine/core.py); see that class for the sweeps' overall structure."""
-
-import os
+Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overall structure."""
 
 import torch
 
@@ -49,7 +47,7 @@ class _HessianExtras:
         # (measured, profiles/r04_hessian_parallel_branch.jsonl: ResNet-18 form 1 922-930, form 2 947-959 matvecs/s;
         # All-CNN-C form 1 521, form 2 283 -- its 128-wide tile configurations spill a three-problem argument block)
         mode = self._extras_default
-        self._extras_parallel = getattr(self, "_extras_allowed", True)
+        self._extras_parallel = self._extras_allowed
         self._extras_mode = mode if self._extras_parallel else 0
         if not self._extras_parallel:
             return
@@ -92,6 +90,9 @@ class _HessianExtras:
             self._xev = {id(u): torch.cuda.Event() for u in self.units}
 
     def _swap_first_order(self):
+        """For the duration of a Hessian engine's gradient sweep: the sweep writes the first-order cotangents the step's
+        products read, ``ga1`` (and ``g1``, the masked one only a BatchNorm's second-order terms read)."""
         for u in self.units:
-            u.g, u.g1 = u.g1, u.g
+            if u.bn is not None:
+                u.g, u.g1 = u.g1, u.g
             u.ga, u.ga1 = u.ga1, u.ga

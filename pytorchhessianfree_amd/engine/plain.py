@@ -5,10 +5,10 @@ from torch import nn
 
 from .. import _lib
 from .common import _Unit, _Unsupported, _cl, _pair, _same, mark_dead_prefix, records_of
-from .core import FusedGGNEngine
+from .conv import _ConvEngine
 
 
-class PlainStackEngine(FusedGGNEngine):
+class PlainStackEngine(_ConvEngine):
     """The same sweeps for a plain stack ``[Dropout] conv(+bias) [ReLU] ... -> AdaptiveAvgPool2d(1) ->
     flatten`` with a softmax cross-entropy on the pooled map -- the All-CNN-C of the reference's
     examples (examples/example_utils.py:59-83, BASELINE.json configs[3]).  Per layer: tangent
@@ -31,9 +31,8 @@ class PlainStackEngine(FusedGGNEngine):
     # conv_W(x, g'), the two terms that carry the network's own curvature, conv_D(g, V) and conv_W(t_x, g)
     # (g: first-order cotangent of the step, g': its tangent; ReLU masks are piecewise constant), all four
     # in ONE grouped launch whose extra results are simply more split-K slabs for the consumers to sum.
-    supports_hessian = True
-    supports_compact = False  # (its own ``local``: no product between compact vectors)
     _extras_default = 1
+    _fork_behind_head = True  # (the head is ONE launch: the side branch of a Hessian product forks behind it)
 
     def _layout(self, model):
         x_in = getattr(self.outputs, "_hf_input", None)
@@ -109,8 +108,7 @@ class PlainStackEngine(FusedGGNEngine):
         first = units[0]
         first.first = True
         first.im2col = first.a.shape[1] > 0 and first.rx.shape[1] < 4
-        self.units, self.tail, self.blocks = units, units[-1], []
-        self.stem, self.pool_args, self.fc, self.pfw, self.pfb = None, None, None, None, None
+        self.units, self.tail = units, units[-1]
         self.model_ref, self._in_shape = model, tuple(x_in.shape)
         used = {i for u in units for i in (u.pw, u.pb) if i is not None}
         if used != set(range(len(self.params))):
@@ -120,9 +118,6 @@ class PlainStackEngine(FusedGGNEngine):
         self.dead_units = mark_dead_prefix(units)
         if self.dead_units:
             units[self.dead_units].no_dgrad = True
-
-    def _allocate_pool(self):
-        pass
 
     def _allocate_head(self):
         f32, dev = torch.float32, self.dev
@@ -136,7 +131,7 @@ class PlainStackEngine(FusedGGNEngine):
             raise _Unsupported("more than 1024 classes")
 
     # ---- forward -----------------------------------------------------------------------------
-    def forward_own(self, refresh=False, update_running=True):  # (no BatchNorm in a plain stack: nothing to move)
+    def _forward_units(self, refresh, update_running):  # (no BatchNorm in a plain stack: nothing to move)
         first, flat = self.units[0], self._flat_params
         carried = (refresh and flat is not None and flat.data_ptr() == self.params[0].data_ptr()
                    and self._conv_carrying_scatter(first, first.conv.weight.detach(), first.sF, flat, 0))
@@ -151,13 +146,9 @@ class PlainStackEngine(FusedGGNEngine):
                 c = u.y.shape[1]
                 self._launch("hf_maxpool_forward_nhwc", u.yp, u.pool_out2, 2 * c, u.pidx, u.y, *self._pool_dims(u), *u.pool)
         torch.mean(self.tail.y, dim=(2, 3), out=self.logits)
-        if getattr(self, "loss_spec", None) is not None:
-            self._loss_head()
-        self._at = "own"
-        return self.logits
 
     def _load_recorded(self, outputs):
-        FusedGGNEngine._load_recorded(self, outputs)
+        super()._load_recorded(outputs)
         for u in self.units:
             if u.pool is not None:  # the model's pooled map, and the positions of ITS windows (as the stem's, forward.py)
                 kh, kw, sh, sw, ph, pw = u.pool
@@ -180,16 +171,15 @@ class PlainStackEngine(FusedGGNEngine):
         self._launch("hf_pool_act_tangent_nhwc", u.tout, u.tout_ld, u.tbuf, u.sT, u.tbuf.shape[1], vb, u.pidx, u.yp,
                      1 if u.relu else 0, *self._pool_dims(u))
 
-    def _pool_adjoint(self, u, srcs, ga):
+    def _pool_adjoint(self, u, srcs):
         """g_a at full resolution from the consumer's data-gradient slabs; the bias sums as partial rows -- or, where
-        the unit's sums are deferred, left to the sums table (which reads this ``ga``)."""
+        the unit's sums are deferred, left to the sums table (which reads ``u.ga``)."""
         self._extras_wait(srcs)
         (gy, splits, slab), = srcs
-        defer = u.defer and ga is u.ga
-        gb = None if (defer or u.pb is None) else u.gb
-        self._launch("hf_pool_act_adjoint_nhwc", ga, gb, u.rb, gy, splits, slab, u.pidx, u.yp, 1 if u.relu else 0,
+        gb = None if (u.defer or u.pb is None) else u.gb
+        self._launch("hf_pool_act_adjoint_nhwc", u.ga, gb, u.rb, gy, splits, slab, u.pidx, u.yp, 1 if u.relu else 0,
                      *self._pool_dims(u), *u.pool)
-        if defer:
+        if u.defer:
             self._sums_pending.add(u.sums_slot)
 
     # ---- product ------------------------------------------------------------------------------
@@ -217,76 +207,32 @@ class PlainStackEngine(FusedGGNEngine):
             else:
                 self._bn_tangent(u, v, None, 0)
 
-    def _adjoint_sweep(self, g_last, first_order=False):
-        """``first_order``: the gradient's sweep (cotangents kept in ``ga1`` for later Hessian products);
-        otherwise the product's sweep -- for a Hessian engine with the two extra convolutions per layer."""
-        second = self.hessian and not first_order
-        srcs = [(g_last, 1, 0)]
-        self._second = second  # (the chain waits for the side branch's slabs, _extras_wait)
-        for u in reversed(self.units):
-            if u.dead:  # (nobody needs a cotangent behind the first trainable layer)
-                break
-            ga = u.ga1 if (self.hessian and first_order) else u.ga
-            if u.pool is not None:
-                self._pool_adjoint(u, srcs, ga)
-            else:
-                self._bn_adjoint(u, srcs, ga)
-            if second and not u.im2col and not u.first and u.sD:
-                # (two launches of two problems each; four in one grouped launch ran 3x slower -- with four
-                # by-value problem descriptions hipcc spills them to scratch memory.  The second one -- conv_D(g, V),
-                # conv_W(t_x, g): no dependence on this chain -- runs on the side branch, see _extras_fork)
-                if self._extras_mode == 2:
-                    _lib.conv_group_slabs([(1, u.dbuf, ga, u.wT, u.geo, u.sD, 0, 0), (2, u.wbuf, u.x, ga, u.geo, u.sW, 0, 0),
-                                           (1, u.dbuf[u.sD:], u.ga1, u.vT, u.geo, u.sD, 0, 0)], self.dev)
-                else:
-                    _lib.conv_dw_slabs((1, u.dbuf, ga, u.wT, u.geo, u.sD, 0, 0),
-                                       (2, u.wbuf, u.x, ga, u.geo, u.sW, 0, 0), self.dev)
-                if not self._extras_parallel:
-                    self._hessian_extras(u)
-            else:
-                self._conv_adjoint(u, ga)
-            if u.sD:
-                srcs = [(u.dbuf, u.nD if second else u.sD, u.dbuf.shape[1])]
-
-    def local(self, v, out=None):
-        v, out = self._product_vectors(v, out)
-        self._tangent_sweep(v)
-        if self.hessian and self._vt_slots:
-            _lib.unpack_tangent(v, self._vt_slots, half=2)  # V as (I, H, W, O): the operand of conv_D(g, V)
+    def _head(self, v):
+        """Average pool, loss Hessian and broadcast back over the last map in ONE launch; no parameters of its own."""
         n, k = self.logits.shape
         self._launch("hf_pool_ce_head", self._g_last, None, self.tail.tout, self._ce[0], float(self._ce[1]), n,
                      self._head_hw, k)
-        if self.hessian:
-            self._extras_fork()
-        try:
-            self._adjoint_sweep(self._g_last)
-            if self.hessian:
-                self._extras_join()
-        finally:
-            self._second = False
-        self._gather(out, None, None)
-        if self.hessian:  # the regulariser's Hessian: coef on its tensors' entries
-            self._add_quadratic(out, v)
-        return out
+        return self._g_last, None, None
 
-    def gradient(self, out=None):
-        if out is None:
-            out = torch.empty(self.n, dtype=torch.float32, device=self.dev)
+    def _first_order_seed(self):
         n, k, h, w = self.tail.y.shape
         g = (self._p - self._onehot) * (self._ce[1] / self._head_hw)  # d loss / d (last map), per pixel
         self._g_last.permute(0, 2, 3, 1).copy_(g.view(n, 1, 1, k).expand(n, h, w, k))
-        self._adjoint_sweep(self._g_last, first_order=True)
-        self._gather(out, None, None, first_order=True)
-        self._add_quadratic(out)
-        return out
+        return self._g_last, None, None
 
-    def _gather(self, out, g_fw, g_fb, first_order=False):
-        self._flush_sums()
-        tensors, perms, splits = self._pack_args(first_order)
-        _lib.pack_ex(out, list(tensors), perms, splits, scale=self.weight, live=self._pack_live)
-        return out
+    def _adjoint_sweep(self, g_last):
+        srcs = [(g_last, 1, 0)]
+        for u in self._adjoint_order():
+            if u.dead:  # (nobody needs a cotangent behind the first trainable layer)
+                break
+            self._adjoint_unit(u, srcs)
+            if u.sD:
+                srcs = [(u.dbuf, self._dslabs(u), u.dbuf.shape[1])]
+
+    def _adjoint_order(self):
+        return list(reversed(self.units))
 
     def _loss_setup(self, loss, outputs):
-        FusedGGNEngine._loss_setup(self, loss, outputs)
+        super()._loss_setup(loss, outputs)
         if self.loss_spec is None or self.loss_spec["kind"] != "ce":
             raise _Unsupported("the plain-stack engine needs a plain softmax cross-entropy loss")

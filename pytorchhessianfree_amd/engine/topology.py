@@ -1,8 +1,9 @@
 """Layer topology of a prepared ResNet-family model, read off its module tree and the activations its patched
-layers recorded (identity by storage); what the captured graphs bake in about the layers; the two-phase split.
+layers recorded (identity by storage); the frozen prefix; the two-phase split.
 
-Mixin of ``FusedGGNEngine`` (engine/core.py); see that class for the sweeps' overall structure."""
+Mixin of ``FusedGGNEngine`` (engine/core.py), the residual kind; see that class for the sweeps' overall structure."""
 
+import torch
 from torch import nn
 
 from .common import _Unit, _Unsupported, _cl, _same, records_of
@@ -74,10 +75,12 @@ class _Topology:
                                f"{mp_x.data_ptr():x} vs {tuple(stem.y.shape)} {stem.y.stride()} {stem.y.data_ptr():x})")
         mp = model.maxpool
         self.stem, self.pool_args = stem, (mp.kernel_size, mp.stride, mp.padding, mp.dilation, mp.ceil_mode)
-        cur = mp_y
-        self.pool_out, self.pool_key, self._rec_pool = _cl(mp_y), mp_y.data_ptr(), mp_y
+        cur = stem.rp = mp_y
+        # the pooled stem output: a static buffer of the engine's own, like the units' (``_allocate``)
+        self.pool_out = torch.empty(tuple(mp_y.shape), dtype=torch.float32, device=self.dev).contiguous(
+            memory_format=torch.channels_last)
         self.blocks = []
-        prev = "pool"  # producer of the current block input
+        prev = self.pool_out  # producer of the current block input
         for bi, b in enumerate(blocks):
             convs = [n for n in ("conv1", "conv2", "conv3") if isinstance(getattr(b, n, None), nn.Conv2d)]
             if not getattr(b, "_hf_block_patched", False) or len(convs) < 2:
@@ -107,7 +110,7 @@ class _Topology:
             else:
                 if not _same(tail.res, cur):
                     raise _Unsupported(f"block {bi}: identity wiring")
-                tail.res_identity = True
+                tail.res_identity = chain[0]
             self.blocks.append((chain, ds, cur))
             cur = tail.ry
             prev = tail
@@ -161,12 +164,6 @@ class _Topology:
         if ds is not None:
             ds.no_dgrad = True
 
-    def layer_signature(self):
-        """What the captured graphs of a session bake in about the model's layers besides shapes: module
-        identities and every BatchNorm's mode / eps / momentum (kernel arguments).  Compared per step."""
-        return tuple((id(u.conv), id(u.bn), None if u.bn is None else (u.bn.training, u.bn.eps, u.bn.momentum))
-                     for u in self.units) + (bool(self.model_ref.training) if not self.units[0].bn is None else None,)
-
     # ---- the product in two phases, for overlapping the all-reduce with the rest of the sweep ----
     def phase_split(self, tail_fraction=0.7):
         """Block index ``cut`` such that the parameters of blocks ``cut ...`` and of the classifier are a
@@ -174,8 +171,6 @@ class _Topology:
         (the adjoint sweep finishes them first: ResNet-18 on 28x28 inputs, layer3 + layer4 + fc = 14 of
         17 MB after ~60 % of the product), with the flat offset of that suffix; ``None`` if the layout does
         not allow it."""
-        if not self.blocks or self.fc is None:
-            return None
         live = self._live_counts()
         total = sum(live)
         acc = live[self.pfw] + (live[self.pfb] if self.pfb is not None else 0)

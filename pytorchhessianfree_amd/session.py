@@ -72,7 +72,7 @@ class _TwoPhaseProduct:
         engine is left as it was: single graph, single compact / plain all-reduce)."""
         if tail_fraction is None:
             tail_fraction = 0.7
-        if os.environ.get("HF_CHUNKED_ALLREDUCE", "auto") == "0" or not hasattr(eng, "phase_split"):
+        if os.environ.get("HF_CHUNKED_ALLREDUCE", "auto") == "0" or not eng.supports_two_phase:
             return None
         if eng.hessian or eng.train_bn:
             return None

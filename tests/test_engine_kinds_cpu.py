@@ -15,6 +15,7 @@ from pytorchhessianfree_amd.engine import DenseStackEngine, FusedGGNEngine, Plai
 from pytorchhessianfree_amd.engine.adjoint import _AdjointSweep
 from pytorchhessianfree_amd.engine.buffers import _Buffers
 from pytorchhessianfree_amd.engine.common import mark_dead_prefix, records_of
+from pytorchhessianfree_amd.engine.conv import _ConvEngine
 from pytorchhessianfree_amd.engine.dataparallel import _DataParallel
 from pytorchhessianfree_amd.engine.diag_ef import _DiagEF
 from pytorchhessianfree_amd.engine.forward import _Forward
@@ -38,17 +39,32 @@ def _contract_of_base():
             if not k.startswith("__") and not callable(v) and not isinstance(v, (classmethod, staticmethod, property))}
 
 
+RESIDUAL_ONLY = ("phase_split", "local_phase_a", "local_phase_b", "local_compact", "_tangent_stem", "_tangent_blocks",
+                 "_adjoint_blocks", "_adjoint_stem", "_grouping", "_head_fused")
+RESIDUAL_ATTRIBUTES = ("stem", "blocks", "fc", "pool_args", "pfw", "pfb")
+
+
 def test_who_inherits_what():
-    conv_mixins = (_Topology, _Buffers, _Forward, _TangentSweep, _AdjointSweep, _HessianExtras, _DiagEF, _DataParallel)
+    unit_mixins = (_Buffers, _Forward, _TangentSweep, _AdjointSweep, _HessianExtras, _DiagEF, _DataParallel)
+    conv_mixins = (_Topology,) + unit_mixins
     assert _Engine in DenseStackEngine.__mro__
-    assert not set(conv_mixins) & set(DenseStackEngine.__mro__)
+    assert not set(conv_mixins + (_ConvEngine,)) & set(DenseStackEngine.__mro__)
     assert FusedGGNEngine not in DenseStackEngine.__mro__
     for name in ("phase_split", "local_phase_a", "local_phase_b", "compact_layout", "local_compact"):
         assert not hasattr(DenseStackEngine, name), name
         assert hasattr(FusedGGNEngine, name), name
-    assert issubclass(PlainStackEngine, FusedGGNEngine)
+    # the two conv kinds: siblings on the conv base, the residual walks on the residual kind alone
+    assert _ConvEngine in FusedGGNEngine.__mro__ and _ConvEngine in PlainStackEngine.__mro__
+    assert not issubclass(PlainStackEngine, FusedGGNEngine) and _Topology not in PlainStackEngine.__mro__
     assert issubclass(FusedGGNEngine, _Engine) and issubclass(PlainStackEngine, _Engine)
-    assert set(conv_mixins) <= set(FusedGGNEngine.__mro__)
+    assert set(conv_mixins) <= set(FusedGGNEngine.__mro__) and set(unit_mixins) <= set(PlainStackEngine.__mro__)
+    for kind in (FusedGGNEngine, PlainStackEngine):
+        for name in ("local", "gradient", "_gather", "forward_own", "diag_ef"):  # ONE skeleton
+            assert getattr(kind, name) is getattr(_ConvEngine, name), (kind.__name__, name)
+        assert hasattr(kind, "compact_layout")
+    for name in RESIDUAL_ONLY:
+        assert not hasattr(PlainStackEngine, name), name
+        assert hasattr(FusedGGNEngine, name), name
     # one process on the base, the compact all-reduce on the conv kinds
     assert DenseStackEngine.reduce is _Engine.reduce and DenseStackEngine.reduce_bytes is _Engine.reduce_bytes
     assert FusedGGNEngine.reduce is _DataParallel.reduce and FusedGGNEngine.reduce_bytes is _DataParallel.reduce_bytes
@@ -62,7 +78,7 @@ def test_contract_values_per_kind():
             getattr(kind, name)  # readable on the class
     #          hessian session two_phase compact acc_decline has_weight_copies
     table = {FusedGGNEngine: (True, True, True, True, None, True),
-             PlainStackEngine: (True, True, True, False, None, True),
+             PlainStackEngine: (True, True, False, False, None, True),
              DenseStackEngine: (True, False, False, False, ACC_ONLY, False)}
     for kind, want in table.items():
         got = (kind.supports_hessian, kind.supports_session, kind.supports_two_phase, kind.supports_compact,
@@ -175,3 +191,18 @@ def test_callers_read_the_contract():
                     and len(node.args) >= 2 and isinstance(node.args[0], (ast.Name, ast.Attribute))
                     and isinstance(node.args[1], ast.Constant)):
                 assert node.args[1].value not in contract, (name, node.lineno, node.args[1].value)
+
+
+def test_unit_level_code_reads_nothing_residual():
+    """The conv base and the unit-level mixins know a list of conv units and nothing about how a residual net wires
+    them: no ``self.stem`` / ``blocks`` / ``fc`` / ``pool_args`` / ``pfw`` / ``pfb`` in any of these files (the residual
+    kind's walks, its max-pool and its linear head stand in engine/core.py and engine/topology.py)."""
+    for name in ("conv.py", "buffers.py", "diag_ef.py", "hessian.py", "forward.py", "tangent.py", "adjoint.py",
+                 "dataparallel.py", "plain.py"):
+        path = os.path.join(ROOT, "pytorchhessianfree_amd", "engine", name)
+        for node in ast.walk(ast.parse(open(path).read())):
+            if isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id == "self":
+                assert node.attr not in RESIDUAL_ATTRIBUTES, (name, node.lineno, node.attr)
+            if (isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id in ("getattr", "hasattr")
+                    and len(node.args) >= 2 and isinstance(node.args[1], ast.Constant)):
+                assert node.args[1].value not in RESIDUAL_ATTRIBUTES, (name, node.lineno, node.args[1].value)

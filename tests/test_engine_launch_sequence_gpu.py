@@ -28,7 +28,8 @@ import torch
 from torch.utils._python_dispatch import TorchDispatchMode
 
 from engine_nets import DEV, build, build_plain
-from pytorchhessianfree_amd import _lib
+from pytorchhessianfree_amd import _lib, curvature, modelprep
+from pytorchhessianfree_amd import testproblems as tp
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "engine_launch_sequence.json.gz")
@@ -44,8 +45,43 @@ CASES = {
     "hessian_train": lambda: build("wide", train=True, hessian=True),
     "stack": lambda: build_plain(),
     "stack_hessian": lambda: build_plain(hessian=True),
+    # ``testproblems.convpool_small`` as ``test_pooled_stack_engine_gpu.py`` builds it, batch 2: two pooled units
+    "stack_pooled": lambda: build_pooled(),
+    "stack_pooled_hessian": lambda: build_pooled(hessian=True),
+    "stack_frozen": lambda: build_pooled(freeze_first=True),  # (the pooled first layer dead for both sweeps)
+    # the Hessian extras in sequence (``acc_session.AccumulatedSession``'s parallel chunks: no side branch)
+    "hessian_seq": lambda: sequential_extras(build("wide", hessian=True)),
+    "stack_hessian_seq": lambda: sequential_extras(build_plain(hessian=True)),
+    "diag_batched": lambda: build("wide"),  # (HF_DIAG_EF_BATCHED=1, see ENV: one squared-sum launch per layer)
+    "stack_diag_batched": lambda: build_plain(),
 }
-ENV = {"fused": {"HF_BN_SUMS_DEFER": "0"}}
+ENV = {"fused": {"HF_BN_SUMS_DEFER": "0"}, "diag_batched": {"HF_DIAG_EF_BATCHED": "1"},
+       "stack_diag_batched": {"HF_DIAG_EF_BATCHED": "1"}}
+# the operations recorded per case: all four for the first eight, the diagonal only where it is the case's subject (most
+# of the file's lines are ``diag_ef``'s per-sample launches)
+OPS = {case: ("forward_own", "local", "gradient") for case in
+       ("stack_pooled", "stack_pooled_hessian", "stack_frozen", "hessian_seq", "stack_hessian_seq")}
+OPS.update(diag_batched=("diag_ef",), stack_diag_batched=("diag_ef",))
+
+
+def build_pooled(hessian=False, freeze_first=False):
+    model, (x, t), lossf = tp.convpool_small(batch_size=2, device="cpu")
+    if freeze_first:
+        for p in next(m for m in model.modules() if isinstance(m, torch.nn.Conv2d)).parameters():
+            p.requires_grad_(False)
+    model, x, t = model.to(DEV), x.to(DEV), t.to(DEV)
+    modelprep.prepare_model(model, channels_last=True)
+    out = model(x)
+    make_op = curvature.hessian_operator if hessian else curvature.ggn_operator
+    op = make_op(lossf(out, t), out, [p for p in model.parameters() if p.requires_grad])
+    assert type(op).__name__ == "PlainStackEngine" and op.hessian == hessian
+    return op
+
+
+def sequential_extras(op):
+    op._extras_allowed = False
+    return op
+
 
 # every BatchNorm / affine / adjoint / sums / statistics / pooling / head / pack / convolution entry point the engine
 # mixins call in these four operations: the cases together must reach each of them
@@ -56,7 +92,8 @@ REQUIRED = [
     "hf_bn_adjoint_v4_pair", "hf_bn_sums_multi", "hf_bn_train_hessian_coeffs", "hf_bn_train_hessian_apply",
     "hf_linear_ce_head", "hf_pool_ce_head", "hf_pack_ex", "hf_unpack_weights", "hf_conv2d_nhwc_slabs",
     "hf_conv2d_nhwc_slabs_unpack", "hf_conv2d_nhwc_backward_slabs", "hf_conv2d_nhwc_group_slabs",
-    "hf_conv2d_nhwc_group_slabs_bnsum", "hf_conv2d_nhwc_dw_slabs",
+    "hf_conv2d_nhwc_group_slabs_bnsum", "hf_conv2d_nhwc_dw_slabs", "hf_pool_act_tangent_nhwc",
+    "hf_pool_act_adjoint_nhwc", "hf_conv2d_nhwc_sqsum_slabs", "hf_chan_sqsum",
 ]
 
 # struct arguments: entry point -> {argument index: (struct, count or the index of the argument that holds it)}
@@ -151,6 +188,8 @@ def record(case, setenv, patch_load):
     got = {}
     for what, call in (("forward_own", op.forward_own), ("local", lambda: op.local(v)),
                        ("gradient", lambda: op.gradient(out)), ("diag_ef", lambda: op.diag_ef("mean"))):
+        if what not in OPS.get(case, (what,)):
+            continue
         rec.restart()
         with KeepAlive():
             try:
