@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 23
+#define HF_ABI_VERSION 24
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -841,6 +841,31 @@ int hf_linear_ce_head_slabs(int64_t rows);
  */
 int hf_pool_ce_head(void* g, void* jv_out, const void* t, const void* p, double scale, int64_t n, int64_t hw,
                     int64_t k, int dtype, void* stream);
+/*
+ * The boundary between a conv stack and a classifier tail behind nn.Flatten (ABI 24).  The conv side keeps maps NHWC;
+ * Flatten of the model's logically-NCHW tensor orders a row's features (c, h, w), and the first Linear's weight is read
+ * in place in that order: a per-sample hw x c transpose, through an LDS tile (16-byte accesses along c on the NHWC
+ * side, contiguous along p on the row side for any hw).  fp32.
+ *
+ * hf_flatten_nhwc_rows:     out[r*out_ld + ch*hw + p] = in[(r*hw + p)*in_ld + ch]
+ *   in: n maps of hw pixels, c channels at a pixel pitch of in_ld floats (one half of a [t_x | x] operand: in_ld = 2c;
+ *   a plain map: in_ld = c); out: the [n, c*hw] operand of hf_dense_tangent_slabs at row pitch out_ld (its ld_x).  A
+ *   permutation: every value is copied, nothing between the rows of a padded `out` is written.
+ * hf_unflatten_slabs_nhwc:  out[(r*hw + p)*c + ch] = sum_s slabs[s*slab_stride + r*c*hw + ch*hw + p]
+ *   slabs: `splits` [n, c*hw] slabs (hf_dense_dgrad_slabs' results), added as slab 0, then slabs 1 .. splits-1 in split
+ *   order (one fp32 rounding each) -- the sum every other consumer of slabs forms; out: a dense NHWC map.
+ *
+ * Both: two launches on the same operands give the same bits; nothing outside the described extents is read or written;
+ * hw = 1 is served by the same kernel.  Refused with HF_ERR_ARG before any launch: a null pointer, an extent below 1,
+ * c % 4 != 0, in_ld < c or in_ld % 4 != 0, out_ld < c*hw, splits outside 1 .. HF_POOL_ACT_MAX_SPLITS, slab_stride <
+ * n*c*hw with more than one slab, c*hw > HF_FLATTEN_MAX_FEATURES (the dense kernels' limit), n*hw*in_ld, n*out_ld or
+ * n*c*hw >= 2^31, another dtype.  HF_ERR_ALIGN: the NHWC operand (`in` / `out`) off the 16-byte grid.
+ */
+#define HF_FLATTEN_MAX_FEATURES (1 << 20)
+int hf_flatten_nhwc_rows(void* out, int64_t out_ld, const void* in, int64_t in_ld, int64_t n, int64_t hw, int64_t c,
+                         int dtype, void* stream);
+int hf_unflatten_slabs_nhwc(void* out, const void* slabs, int splits, int64_t slab_stride, int64_t n, int64_t hw,
+                            int64_t c, int dtype, void* stream);
 
 /* ---- fully-connected layers inside the GGN product (hf_dense.hip) ---------------- */
 /*

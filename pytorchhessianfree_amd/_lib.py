@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HF_PCG_LIB") or os.path.join(_HERE, "csrc", "libhfpcg.so")
 
 HF_F32, HF_F64 = 0, 1
-ABI_VERSION = 23
+ABI_VERSION = 24
 HF_ERR_ARG = -1  # hf_status of include/hf_pcg.h: null / negative / inconsistent argument
 HF_M_NONE, HF_M_DIAG, HF_M_EXTERNAL = 0, 1, 2
 REASONS = {
@@ -192,6 +192,8 @@ SIGNATURES = {
     "hf_linear_ce_head": (c_int, [c_void_p] * 9 + [c_double, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "hf_linear_ce_head_slabs": (c_int, [c_int64]),
     "hf_pool_ce_head": (c_int, [c_void_p] * 4 + [c_double, c_int64, c_int64, c_int64, c_int, c_void_p]),
+    "hf_flatten_nhwc_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),
+    "hf_unflatten_slabs_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "hf_dense_plan": (c_int, [c_int64, c_int64, c_int64, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "hf_dense_tangent_slabs": (c_int, [c_void_p] * 5 + [c_int64] * 4 + [c_int, c_int64, c_int, c_void_p]),
     "hf_dense_dgrad_slabs": (c_int, [c_void_p] * 3 + [c_int64] * 3 + [c_int, c_int64, c_int, c_void_p]),

@@ -439,7 +439,93 @@ __global__ __launch_bounds__(HB) void k_pool_ce_head(float* __restrict__ g, floa
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// The boundary between a conv stack (NHWC maps) and a classifier tail behind nn.Flatten (rows whose features run
+// (c, h, w), the order the first Linear's weight is read in): a per-sample hw x c transpose, both directions.
+//   flatten:    out[r][ch*hw + p] = in[(r*hw + p)*in_ld + ch]
+//   unflatten:  out[(r*hw + p)*c + ch] = sum_s slabs[s][r][ch*hw + p]          (slab_sum: slab 0, then 1 .. n-1)
+// One workgroup per FT x FT tile of one sample through LDS, so both global sides run contiguously: 16 bytes per lane
+// along c on the NHWC side (lane = (pixel t/8, channel quad t%8)), 4 bytes per lane along p on the row side (lane =
+// (channel t/32 + 8k, pixel t%32): hw is arbitrary, rows start on any 4-byte boundary).  The tile lies [channel][pixel]
+// with a pitch of FT + 1 dwords.  Row side: a 32-lane half is one channel and 32 consecutive pixels -> 32 banks.
+// NHWC side, component j: dword (4q + j)*33 + p, bank (4q + j + p) % 32 with q = 0..7 and four consecutive p per half
+// -> 4q + (p - p_lo) covers 0..31 once.  Conflict-free on both sides (ds_write_b32 / ds_read_b32 bank as (a/4) % 32 per
+// 32-lane half).
+// ---------------------------------------------------------------------------------------
+constexpr int FT = 32, FPITCH = FT + 1;
+
+__global__ __launch_bounds__(HB) void k_flatten_rows(float* __restrict__ out, const float* __restrict__ in,
+                                                     unsigned out_ld, unsigned in_ld, unsigned hw, unsigned c,
+                                                     unsigned tiles_p, unsigned tiles_c) {
+  __shared__ float tile[FT * FPITCH];
+  unsigned b = blockIdx.x;
+  const unsigned c0 = (b % tiles_c) * FT; b /= tiles_c;
+  const unsigned p0 = (b % tiles_p) * FT;
+  const unsigned r = b / tiles_p;
+  {
+    const unsigned q = threadIdx.x % 8, p = threadIdx.x / 8;
+    if (p0 + p < hw && c0 + 4 * q < c) {
+      const F4 v = ld4(in + ((size_t)r * hw + p0 + p) * in_ld + c0 + 4 * q);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) tile[(4 * q + j) * FPITCH + p] = v.e[j];
+    }
+  }
+  __syncthreads();
+  const unsigned p = threadIdx.x % FT;
+  if (p0 + p >= hw) return;
+#pragma unroll
+  for (int k = 0; k < FT / 8; ++k) {
+    const unsigned ch = threadIdx.x / FT + 8 * k;
+    if (c0 + ch < c)
+      chain_store<HF_WT_ELEM>(&out[(size_t)r * out_ld + (size_t)(c0 + ch) * hw + p0 + p], tile[ch * FPITCH + p]);
+  }
+}
+
+__global__ __launch_bounds__(HB) void k_unflatten_slabs(float* __restrict__ out, const float* __restrict__ slabs,
+                                                        int splits, long long slab_stride, unsigned hw, unsigned c,
+                                                        unsigned tiles_p, unsigned tiles_c) {
+  __shared__ float tile[FT * FPITCH];
+  unsigned b = blockIdx.x;
+  const unsigned c0 = (b % tiles_c) * FT; b /= tiles_c;
+  const unsigned p0 = (b % tiles_p) * FT;
+  const unsigned r = b / tiles_p;
+  {
+    const unsigned p = threadIdx.x % FT;
+    if (p0 + p < hw) {
+#pragma unroll
+      for (int k = 0; k < FT / 8; ++k) {
+        const unsigned ch = threadIdx.x / FT + 8 * k;
+        if (c0 + ch < c) {
+          const size_t off = ((size_t)r * c + c0 + ch) * hw + p0 + p;
+          tile[ch * FPITCH + p] = slab_sum<8>(slabs[off], slabs, off, splits, slab_stride);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const unsigned q = threadIdx.x % 8, p = threadIdx.x / 8;
+  if (p0 + p < hw && c0 + 4 * q < c) {
+    F4 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v.e[j] = tile[(4 * q + j) * FPITCH + p];
+    chain_store4<HF_WT_ELEM>(out + ((size_t)r * hw + p0 + p) * c + c0 + 4 * q, v);
+  }
+}
+
 inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// what the two boundary kernels share: extents, the dense kernels' feature limit, the tile grid
+inline int flatten_grid(int64_t n, int64_t hw, int64_t c, int dtype, unsigned* tiles_p, unsigned* tiles_c,
+                        unsigned* blocks) {
+  if (dtype != HF_F32 || n < 1 || hw < 1 || c < 1 || c % 4) return HF_ERR_ARG;
+  const int64_t lim = 1LL << 31;
+  if (n >= lim || hw > HF_FLATTEN_MAX_FEATURES || c > HF_FLATTEN_MAX_FEATURES || c * hw > HF_FLATTEN_MAX_FEATURES)
+    return HF_ERR_ARG;
+  const int64_t tp = (hw + FT - 1) / FT, tc = (c + FT - 1) / FT;
+  if (n * tp * tc >= lim) return HF_ERR_ARG;
+  *tiles_p = (unsigned)tp; *tiles_c = (unsigned)tc; *blocks = (unsigned)(n * tp * tc);
+  return HF_OK;
+}
 
 }  // namespace
 
@@ -601,6 +687,34 @@ int hf_pool_ce_head(void* g, void* jv_out, const void* t, const void* p, double 
   if (n * hw * k >= (1LL << 31)) return -1;
   hipLaunchKernelGGL(k_pool_ce_head, dim3((unsigned)n), dim3(HB), 0, (hipStream_t)stream, (float*)g,
                      (float*)jv_out, (const float*)t, (const float*)p, (float)scale, (int)hw, (int)k);
+  return (int)hipGetLastError();
+}
+
+int hf_flatten_nhwc_rows(void* out, int64_t out_ld, const void* in, int64_t in_ld, int64_t n, int64_t hw, int64_t c,
+                         int dtype, void* stream) {
+  unsigned tiles_p, tiles_c, blocks;
+  if (!out || !in) return HF_ERR_ARG;
+  if (const int rc = flatten_grid(n, hw, c, dtype, &tiles_p, &tiles_c, &blocks)) return rc;
+  const int64_t lim = 1LL << 31;
+  if (in_ld < c || in_ld % 4 || in_ld >= lim || out_ld < c * hw || out_ld >= lim) return HF_ERR_ARG;
+  if (n * hw * in_ld >= lim || n * out_ld >= lim) return HF_ERR_ARG;
+  if (!al16(in)) return HF_ERR_ALIGN;
+  hipLaunchKernelGGL(k_flatten_rows, dim3(blocks), dim3(HB), 0, (hipStream_t)stream, (float*)out, (const float*)in,
+                     (unsigned)out_ld, (unsigned)in_ld, (unsigned)hw, (unsigned)c, tiles_p, tiles_c);
+  return (int)hipGetLastError();
+}
+
+int hf_unflatten_slabs_nhwc(void* out, const void* slabs, int splits, int64_t slab_stride, int64_t n, int64_t hw,
+                            int64_t c, int dtype, void* stream) {
+  unsigned tiles_p, tiles_c, blocks;
+  if (!out || !slabs) return HF_ERR_ARG;
+  if (const int rc = flatten_grid(n, hw, c, dtype, &tiles_p, &tiles_c, &blocks)) return rc;
+  if (splits < 1 || splits > HF_POOL_ACT_MAX_SPLITS) return HF_ERR_ARG;
+  if (n * c * hw >= (1LL << 31)) return HF_ERR_ARG;
+  if (splits > 1 && slab_stride < n * c * hw) return HF_ERR_ARG;  // (slabs would overlap)
+  if (!al16(out)) return HF_ERR_ALIGN;
+  hipLaunchKernelGGL(k_unflatten_slabs, dim3(blocks), dim3(HB), 0, (hipStream_t)stream, (float*)out,
+                     (const float*)slabs, splits, (long long)slab_stride, (unsigned)hw, (unsigned)c, tiles_p, tiles_c);
   return (int)hipGetLastError();
 }
 

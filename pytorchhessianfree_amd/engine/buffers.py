@@ -225,6 +225,12 @@ class _Buffers:
                 if u.epi:
                     u.tp1 = torch.empty((tp_rows, k), dtype=f32, device=dev)
                     u.tpx = torch.empty((tp_rows, k), dtype=f32, device=dev)
+        # a head that reads the last map through an operand of its own (a plain stack's classifier tail) is a consumer
+        # like a convolution: the same [t_x | x] NHWC buffer
+        for t in self._head_operands():
+            if id(t) not in xcats:
+                n, c, h, w = t.shape
+                xcats[id(t)] = torch.zeros((n, 2 * c, h, w), dtype=f32, device=dev).contiguous(memory_format=cl)
         # where each unit's output goes besides its own dense buffer: the [t_x | x] operand of its
         # consumer -- the tangent into the first half, the value (forward pass) into the second
         for u in self.units:
@@ -257,6 +263,10 @@ class _Buffers:
         # the parameters as ONE flat vector, when they are consecutive views of one (the optimizer's
         # arena): every W half is then refreshed by a single scatter launch
         self._flat_params = _flat_view(self.params, self.n)
+
+    def _head_operands(self):
+        """The maps (``u.y`` / ``u.yp`` buffers) a kind's head reads as ``[t_x | x]`` operands; none by default."""
+        return ()
 
     def _allocate_sums_table(self):
         """The deferred units' sums problems as ONE table in device memory, in adjoint-sweep order (static pointers: built

@@ -175,6 +175,60 @@ class ConvPoolSmall(nn.Module):
         return torch.flatten(self.net(x), -3)
 
 
+def _batched(net, x):
+    """``net(x)``, also for one unbatched sample [C,H,W] (``nn.Flatten`` keeps dimension 0)."""
+    return net(x[None])[0] if x.dim() == 3 else net(x)
+
+
+class ConvFCSmall(nn.Module):
+    """The smallest conv stack with a classifier tail (LeNet / DeepOBS 2c2d shape): ``ConvPoolSmall``'s two pooled units
+    (12x12 -> 5x5 -> 2x2: the last unit is pooled), ``Flatten`` to 32 features, ``Linear(32->20) ReLU Linear(20->10)``.
+    10 and 20 are no multiples of 4: the dense kernels' unaligned paths, and later parameters off 16-byte boundaries in an
+    arena."""
+
+    def __init__(self, num_classes=10):
+        super().__init__()
+        self.net = nn.Sequential(
+            nn.Conv2d(3, 8, 3, 1, 1), nn.ReLU(), nn.MaxPool2d(3, 2),
+            nn.Conv2d(8, 8, 3, 1, 1), nn.ReLU(), nn.MaxPool2d(2, 2),
+            nn.Flatten(),
+            nn.Linear(32, 20), nn.ReLU(), nn.Linear(20, num_classes),
+        )
+
+    def forward(self, x):
+        return _batched(self.net, x)
+
+
+class ConvFCFlat(nn.Module):
+    """One unpooled, im2col'd unit that is first and last, a non-square 6x5 map (hw = 30) and a one-layer tail:
+    ``Conv(3->8, 3, pad 1) ReLU Flatten Linear(240->10)`` on 3x6x5 inputs."""
+
+    def __init__(self, num_classes=10):
+        super().__init__()
+        self.net = nn.Sequential(nn.Conv2d(3, 8, 3, 1, 1), nn.ReLU(), nn.Flatten(), nn.Linear(240, num_classes))
+
+    def forward(self, x):
+        return _batched(self.net, x)
+
+
+class C3D3(nn.Module):
+    """A DeepOBS ``3c3d``-sized net from stock modules: three conv + ReLU + MaxPool(3, 2, 1) units (32x32 -> 14 -> 6 -> 3),
+    ``Flatten`` to 1152 features, ``Linear(1152->512) ReLU Linear(512->256) ReLU Linear(256->classes)``."""
+
+    def __init__(self, num_classes=10):
+        super().__init__()
+        self.net = nn.Sequential(
+            nn.Conv2d(3, 64, 5), nn.ReLU(), nn.MaxPool2d(3, 2, 1),
+            nn.Conv2d(64, 96, 3), nn.ReLU(), nn.MaxPool2d(3, 2, 1),
+            nn.Conv2d(96, 128, 3, 1, 1), nn.ReLU(), nn.MaxPool2d(3, 2, 1),
+            nn.Flatten(),
+            nn.Linear(1152, 512), nn.ReLU(), nn.Linear(512, 256), nn.ReLU(), nn.Linear(256, num_classes),
+        )
+
+    def forward(self, x):
+        return _batched(self.net, x)
+
+
 def l2_regularized(loss_function, model, l2=5e-4):
     """``loss + 0.5 * l2 * sum ||W||^2`` over the WEIGHTS (no biases): the regularised
     loss the reference's All-CNN-C example trains (examples/example_utils.py:77-81 adds
@@ -300,6 +354,36 @@ def convpool_small(batch_size=2, seed=0, device="cpu", data_seed=None):
     g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
     inputs = torch.rand(batch_size, 3, 12, 12, generator=g)
     targets = torch.randint(0, 4, (batch_size,), generator=g)
+    return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
+
+
+def convfc_small(batch_size=2, seed=0, device="cpu", data_seed=None):
+    """``ConvFCSmall`` in eval mode; inputs U[0,1) [B,3,12,12], 10 classes, CE-mean."""
+    torch.manual_seed(seed)
+    model = ConvFCSmall(10).eval()
+    g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
+    inputs = torch.rand(batch_size, 3, 12, 12, generator=g)
+    targets = torch.randint(0, 10, (batch_size,), generator=g)
+    return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
+
+
+def convfc_flat(batch_size=3, seed=0, device="cpu", data_seed=None):
+    """``ConvFCFlat`` in eval mode; inputs U[0,1) [B,3,6,5], 10 classes, CE-mean."""
+    torch.manual_seed(seed)
+    model = ConvFCFlat(10).eval()
+    g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
+    inputs = torch.rand(batch_size, 3, 6, 5, generator=g)
+    targets = torch.randint(0, 10, (batch_size,), generator=g)
+    return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
+
+
+def c3d3_cifar10(batch_size=32, seed=0, device="cpu", data_seed=None):
+    """``C3D3`` in eval mode; inputs U[0,1) [B,3,32,32], 10 classes, CE-mean."""
+    torch.manual_seed(seed)
+    model = C3D3(10).eval()
+    g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
+    inputs = torch.rand(batch_size, 3, 32, 32, generator=g)
+    targets = torch.randint(0, 10, (batch_size,), generator=g)
     return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
 
 
