@@ -179,6 +179,9 @@ class PlainStackEngine(_ConvEngine):
             raise _Unsupported(f"Linear tail: batch {out.shape[0]} > {MAX_TAIL_ROWS} rows (the dense kernels' limit)")
         if out.shape[1] > MAX_CLASSES:
             raise _Unsupported(f"Linear tail: more than {MAX_CLASSES} classes")
+        c = units[-1].a.shape[1]
+        if c % 4:  # (an im2col'd unit's channel count is checked nowhere else; hf_flatten_nhwc_rows would refuse it)
+            raise _Unsupported(f"Linear tail: the last map has {c} channels (the flatten kernels take multiples of 4)")
         if self.hessian:
             raise _Unsupported("Hessian products through a classifier tail are not covered")
         if self.group is not None:

@@ -4,6 +4,10 @@ JSON line per (series, case, quantity) with the error of every parameter tensor 
 digit, rounded up; the last lines printed list them).
 
     python scripts/engine_geometry_errors.py --out profiles/rNN_engine_geometry.jsonl
+    python scripts/engine_geometry_errors.py --cases tail --out profiles/rNN_tail_geometry.jsonl
+
+``--cases tail``: the classifier-tail cases (``geometry_nets.TAIL_CASES``) and the measures of
+``tests/test_tail_geometry_gpu.py`` -- the record of its ``BOUND_TAIL`` (GGN products only: no Hessian, no train mode).
 
 A case the engine gets wrong is recorded (``"failed"``) and the run goes on; any other error ends it."""
 
@@ -27,10 +31,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
     ap.add_argument("--series", default="all", choices=["all", "stock_fp32", "engine"])
+    ap.add_argument("--cases", default="geometry", choices=["geometry", "tail"])
     args = ap.parse_args()
     pytorchhessianfree_amd.configure()  # (as tests/conftest.py: the accurate MIOpen solvers for the stock side)
     import geometry_nets as gn
-    import test_engine_geometry_gpu as tests
+    if args.cases == "tail":
+        import test_tail_geometry_gpu as tests
+    else:
+        import test_engine_geometry_gpu as tests
+    tail = args.cases == "tail"
+    cases = gn.TAIL_CASES if tail else gn.CASES
 
     fh = open(args.out, "w")
     worst = {}
@@ -40,8 +50,8 @@ def main():
         fh.write(json.dumps({"series": series, "case": case, "quantity": quantity, "worst": top, "errors": errs, **kw}) + "\n")
         fh.flush()
         print(series, case, quantity, "failed" if top is None else f"{top:.2e}", flush=True)
-        if series == "stock_fp32" and top is not None:
-            worst[quantity] = max(worst.get(quantity, 0.0), top)
+        if series == "stock_fp32" and top is not None and top > worst.get(quantity, (0.0, None))[0]:
+            worst[quantity] = (top, case)
 
     def run(series, case, what, fn, prefix=""):
         t0 = time.time()
@@ -58,15 +68,22 @@ def main():
         res = gn.stock_fp32_errors(case, "cuda", train=True)
         return {"ggn_train": res["ggn"], "hessian_train": res["hessian"]}
 
-    for case in gn.CASES if args.series in ("all", "stock_fp32") else []:
-        run("stock_fp32", case, "stock", lambda: gn.stock_fp32_errors(case, "cuda"))
+    def stock(case):
+        res = gn.stock_fp32_errors(case, "cuda")
+        if tail:
+            del res["hessian"]  # (the engine makes no Hessian products through a classifier tail: no bound to take)
+        return res
+
+    for case in cases if args.series in ("all", "stock_fp32") else []:
+        run("stock_fp32", case, "stock", lambda: stock(case))
         if case in gn.TRAIN_CASES:
             run("stock_fp32", case, "stock_train", lambda: stock_train(case))
-    for case in gn.CASES if args.series in ("all", "engine") else []:
+    for case in cases if args.series in ("all", "engine") else []:
         run("engine", case, "forward", lambda: tests.forward_errors(case))
         run("engine", case, "gradient", lambda: tests.gradient_errors(case))
         run("engine", case, "ggn", lambda: tests.product_errors(case))
-        run("engine", case, "hessian", lambda: tests.product_errors(case, hessian=True))
+        if not tail:
+            run("engine", case, "hessian", lambda: tests.product_errors(case, hessian=True))
         if case in gn.TRAIN_CASES:
             run("engine", case, "ggn_train", lambda: tests.product_errors(case, train=True))
             run("engine", case, "hessian_train", lambda: tests.product_errors(case, hessian=True, train=True))
@@ -75,9 +92,9 @@ def main():
             run("engine", case, "diag_ef", lambda: tests.diag_errors(case), prefix=prefix)
         os.environ.pop("HF_DIAG_EF_BATCHED")
     torch.cuda.synchronize()
-    for quantity, top in worst.items():
+    for quantity, (top, case) in worst.items():
         e = math.floor(math.log10(3 * top))
-        print(f"bound {quantity}: 3 x {top:.3e} -> {math.ceil(3 * top / 10 ** e - 1e-9)}e{e}")
+        print(f"bound {quantity}: 3 x {top:.3e} ({case}) -> {math.ceil(3 * top / 10 ** e - 1e-9)}e{e}")
 
 
 if __name__ == "__main__":

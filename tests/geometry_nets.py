@@ -13,9 +13,16 @@ and the pool's ``(kernel, stride, padding)`` and the block strides free, ints or
 (``GeometryStack``).  Seeding and BatchNorm state as ``engine_nets._resnet``: seed 5, statistics and scales off their
 trivial values, ``eps = 0.1``, input from ``torch.randn`` drawn after the model.
 
+``TAIL_CASES``: five plain stacks that end in ``nn.Flatten`` and ``Linear [ReLU] ... Linear`` (``GeometryTail``), for
+the classifier tail of the plain-stack engine: what ``convfc_small`` / ``convfc_flat`` never reach at engine level --
+summed data-gradient slabs, tail tensors off the 16-byte grid of the flat vector, partial flatten tiles, a 1x1 and a
+pooled non-square last map, batch 1 and 256 (``TAIL_GEOMETRY`` says which case reaches what).  Same seeding; kept apart
+from ``CASES`` (GGN products only, bounds of their own).
+
 The reference (``Reference``): float64 autograd of a deep copy of the STOCK model on the CPU -- loss, gradient, GGN
 product (``curvature.GGNOperator``), Hessian product (``curvature.HessianOperator``), diagonal empirical Fisher by
-per-sample gradients --, optionally on replayed ReLU decisions (``_replay_relu_decisions``: bounded).
+per-sample gradients --, optionally on replayed ReLU decisions and max-pool positions (``_replay_relu_decisions``,
+``_replay_pool_positions``: bounded).
 
 The measure (``per_tensor_errors``): per parameter tensor ``T``, ``max|got_T - want_T| / max|want_T|`` -- a whole-vector
 max-norm lets a small block (a BatchNorm shift) be entirely wrong below 1e-6 of the classifier's entries --, and exactly
@@ -58,6 +65,27 @@ STACKS = {
         nn.Conv2d(16, 8, 1), nn.AdaptiveAvgPool2d((1, 1))]),
 }
 CASES = list(RESNETS) + list(STACKS)
+
+# Plain stacks with a classifier tail (``nn.Flatten``, then ``Linear [ReLU] ... Linear``; ``GeometryTail``), at the
+# shapes the tail's host arithmetic and kernels meet nowhere else at engine level -- what each reaches stands with its
+# literals in ``TAIL_GEOMETRY``
+TAILS = {
+    "tail_rect_pooled": dict(x=(3, 3, 9, 7), classes=7, layers=lambda: [
+        nn.Conv2d(3, 8, 3, 1, 1), nn.ReLU(), nn.MaxPool2d((2, 3), (2, 2)),
+        nn.Conv2d(8, 12, (3, 1), 1, (1, 0)), nn.ReLU(), nn.MaxPool2d((2, 1), (2, 1)),
+        nn.Flatten(), nn.Dropout(0.5), nn.Linear(72, 21), nn.ReLU(), nn.Linear(21, 7)]),
+    "tail_wide_first": dict(x=(2, 1, 5, 7), classes=5, layers=lambda: [
+        nn.Conv2d(1, 36, 3, 1, 1), nn.ReLU(), nn.Flatten(), nn.Linear(1260, 70), nn.ReLU(),
+        nn.Linear(70, 33, bias=False), nn.ReLU(), nn.Linear(33, 5)]),
+    "tail_pixel": dict(x=(1, 4, 4, 4), classes=10, layers=lambda: [
+        nn.Conv2d(4, 8, 3, 1, 1), nn.ReLU(), nn.MaxPool2d(2, 2), nn.Conv2d(8, 16, 2), nn.Flatten(), nn.Linear(16, 10)]),
+    "tail_rows_256": dict(x=(256, 1, 3, 2), classes=3, layers=lambda: [
+        nn.Conv2d(1, 4, 3, 1, 1), nn.ReLU(), nn.Flatten(), nn.Linear(24, 3)]),
+    "tail_col_map": dict(x=(4, 1, 12, 1), classes=6, layers=lambda: [
+        nn.Conv2d(1, 8, 3, 1, 1), nn.ReLU(), nn.MaxPool2d((2, 1), (2, 1)), nn.Conv2d(8, 8, 3, (2, 1), 1), nn.ReLU(),
+        nn.Flatten(), nn.Linear(24, 40), nn.ReLU(), nn.Linear(40, 6)]),
+}
+TAIL_CASES = list(TAILS)
 
 # per convolution in call order: (module, input map, output map, live-tap mask (0: all live), row blocks of the adjoint)
 GEOMETRY = {
@@ -136,6 +164,42 @@ GEOMETRY = {
         ("net.5", (2, 2), (2, 2), 0, 1),
     ],
 }
+# per tail case -- "convs": as GEOMETRY; "linears", per Linear: (c_in, c_out, sT, sD, weight offset, bias offset or None)
+# (split counts of the tangent / data-gradient GEMM by ``dense_plan``, offsets in the flat vector); "last": (rows, hw, c)
+# of the map ``nn.Flatten`` reads; "pools": per unit (kh, kw, sh, sw, ph, pw) or None; "n": entries of the flat vector
+TAIL_GEOMETRY = {
+    # the last map pooled and non-square (2x3); Linear(21,7) at offset 2057 (1 mod 4) with row pitch 21: the dense
+    # kernels' element-wise operand form; a Dropout leaf inside the tail
+    "tail_rect_pooled": dict(
+        convs=[("net.0", (9, 7), (9, 7), 0, 2), ("net.3", (4, 3), (4, 3), 0, 1)],
+        linears=[(72, 21, 3, 1, 524, 2036), (21, 7, 1, 1, 2057, 2204)],
+        last=(3, 6, 12), pools=[(2, 3, 2, 2, 0, 0), (2, 1, 2, 1, 0, 0)], n=2211),
+    # an unpooled map of the im2col'd first unit; hw = 35 and c = 36: two flatten tiles each way, the last one partial;
+    # the first data-gradient split counts above 1 (3, 2); a bias-free Linear at offset 88630 (2 mod 4), the last bias at
+    # 91105 (1 mod 4); three tail layers
+    "tail_wide_first": dict(
+        convs=[("net.0", (5, 7), (5, 7), 0, 3)],
+        linears=[(1260, 70, 20, 3, 360, 88560), (70, 33, 3, 2, 88630, None), (33, 5, 2, 1, 90940, 91105)],
+        last=(2, 35, 36), pools=[None], n=91110),
+    # hw = 1, batch 1, the last unit without ReLU, the first unit not im2col'd (4 input channels)
+    "tail_pixel": dict(
+        convs=[("net.0", (4, 4), (4, 4), 0, 1), ("net.3", (2, 2), (1, 1), 0, 1)],
+        linears=[(16, 10, 1, 1, 824, 984)],
+        last=(1, 1, 16), pools=[(2, 2, 2, 2, 0, 0), None], n=994),
+    # 256 rows: the dense kernels' limit, eight row tiles
+    "tail_rows_256": dict(
+        convs=[("net.0", (3, 2), (3, 2), 0, 6)],
+        linears=[(24, 3, 1, 1, 40, 112)],
+        last=(256, 6, 4), pools=[None], n=115),
+    # a one-column map: kernel columns 0 and 2 of both convolutions meet only padding (0b010010010); sD = 2
+    "tail_col_map": dict(
+        convs=[("net.0", (12, 1), (12, 1), 146, 1), ("net.3", (6, 1), (3, 1), 146, 1)],
+        linears=[(24, 40, 1, 2, 664, 1624), (40, 6, 2, 1, 1664, 1904)],
+        last=(4, 3, 8), pools=[(2, 1, 2, 1, 0, 0), None], n=1910),
+}
+TAIL_CAPTURED_CASES = ["tail_wide_first", "tail_rect_pooled"]
+FLATTEN_TILE = 32  # (hf_head.hip: the flatten kernels move 32 x 32 tiles of the [hw, c] plane of one sample)
+
 TRAIN_CASES = ["nonsquare_odd", "row_map", "col_map", "wide_rows", "stem7"]  # (batch_one: a 1x1 map of ONE sample has no
 COMPACT_CASES = ["row_map", "col_map", "batch_one"]                           # batch statistics; plain stacks: no BatchNorm)
 CAPTURED_CASES = ["asym_stride", "plain_rect"]
@@ -167,11 +231,25 @@ class GeometryStack(nn.Module):
         return torch.flatten(self.net(x), -3)
 
 
+class GeometryTail(nn.Module):
+    """(``nn.Flatten`` is one of ``layers``: the net's output is the last ``Linear``'s, unchanged)"""
+
+    def __init__(self, layers):
+        super().__init__()
+        self.net = nn.Sequential(*layers)
+
+    def forward(self, x):
+        return self.net(x)
+
+
 def make(case, train=False):
     """The stock fp32 net of ``case`` on the CPU, seeded, and two batches ``[(x, t), (x2, t2)]`` drawn after it (the
     second: for the tests that hand the engine a new batch)."""
     torch.manual_seed(SEED)
-    if case in RESNETS:
+    if case in TAILS:
+        spec = TAILS[case]
+        model = GeometryTail(spec["layers"]())
+    elif case in RESNETS:
         spec = RESNETS[case]
         model = GeometryResNet(spec["x"][1], spec["stem"], spec["pool"], spec["blocks"], spec["classes"])
         with torch.no_grad():
@@ -228,6 +306,52 @@ def adjoint_row_blocks(rows, k, bytes_per_wg=32768):
     return rb if rb >= 2 else 1
 
 
+def dense_planned_splits(length, out_cols, kstep=32, target_blocks=512, max_splits=32):
+    """Slabs of one skinny GEMM of a ``Linear`` layer that reduces over ``length`` entries into ``out_cols`` columns, by
+    the rule of hf_dense.hip (``dense_kper`` / ``dense_split_ok`` / ``dense_planned_splits``, restated: the library's
+    own ``hf_dense_plan`` is compared with it on the CPU, the engine's ``u.sT`` / ``u.sD`` with the same literals on the
+    GPU): about ``target_blocks`` workgroups of one 32-column tile each, every split a multiple of ``kstep`` entries,
+    none starting behind the end."""
+    def kper(splits):
+        return -(-(-(-length // splits)) // kstep) * kstep
+
+    s = min(max_splits, -(-target_blocks // (-(-out_cols // 32))))
+    while s > 1 and not (s - 1) * kper(s) < length:
+        s -= 1
+    return s
+
+
+def dense_plan(c_in, c_out):
+    """``(sT, sD)`` of a ``Linear(c_in, c_out)``: the tangent / forward GEMM reduces over ``c_in``, the data gradient
+    over ``c_out``."""
+    return dense_planned_splits(c_in, c_out), dense_planned_splits(c_out, c_in)
+
+
+def linear_geometry(model):
+    """Per ``nn.Linear`` in module order: ``(c_in, c_out, sT, sD, weight offset, bias offset or None)`` -- the offsets
+    in the flat vector of the trainable parameters, in the order of ``model.parameters()``."""
+    offs, o = {}, 0
+    for p in model.parameters():
+        if p.requires_grad:
+            offs[id(p)] = o
+            o += p.numel()
+    return [(m.in_features, m.out_features, *dense_plan(m.in_features, m.out_features), offs.get(id(m.weight)),
+             None if m.bias is None else offs.get(id(m.bias)))
+            for m in model.modules() if isinstance(m, nn.Linear)]
+
+
+def last_map(model, x):
+    """``(rows, hw, c)`` of the map ``nn.Flatten`` turns into the first ``Linear``'s rows."""
+    seen = []
+    flat = next(m for m in model.modules() if isinstance(m, nn.Flatten))
+    hook = flat.register_forward_hook(lambda m, inp, out: seen.append(tuple(inp[0].shape)))
+    with torch.no_grad():
+        model(x)
+    hook.remove()
+    (n, c, h, w), = seen
+    return n, h * w, c
+
+
 def relu_inputs(model, x):
     """The input of every ``nn.ReLU`` call of one forward pass, in call order."""
     seen, hooks = [], []
@@ -268,22 +392,72 @@ def _replay_relu_decisions(model, masks, max_flips=200, margin=1e-5):
     return flips
 
 
-# The fp32 and the float64 forward pass of every case take the SAME ReLU decisions (test_geometry_nets_cpu.py): what an
-# engine replays into the reference may differ from the float64 net's own in a handful of entries next to zero, no more
+def pool_positions(model, x):
+    """The positions every ``nn.MaxPool2d`` call of one forward pass takes, in call order: ``[n, c, oh, ow]`` int64,
+    flat ``y * w + x`` inside the ``(n, c)`` plane (ATen's ``return_indices``)."""
+    seen, hooks = [], []
+
+    def hook(m, inp, out):
+        seen.append(nn.functional.max_pool2d(inp[0].detach(), m.kernel_size, m.stride, m.padding, return_indices=True)[1])
+
+    for m in model.modules():
+        if isinstance(m, nn.MaxPool2d):
+            hooks.append(m.register_forward_hook(hook))
+    with torch.no_grad():
+        model(x)
+    for h in hooks:
+        h.remove()
+    return seen
+
+
+def _replay_pool_positions(model, pools, flips, max_flips=200, margin=1e-5):
+    """Make every ``nn.MaxPool2d`` call of ``model`` read its windows at the positions ``pools`` (in call order, as
+    ``pool_positions`` gives them) -- bounded as the ReLU decisions are: the value at a replayed position may lie below
+    the window's own maximum only within ``margin`` x the map's max-norm, and the positions that differ from the
+    model's own count against the same ``max_flips`` (``flips``: the counter ``_replay_relu_decisions`` returned)."""
+    cursor = [0]
+
+    def pool_forward(self, inp):
+        idx = pools[cursor[0]].to(device=inp.device, dtype=torch.int64)
+        cursor[0] += 1
+        own, own_idx = nn.functional.max_pool2d(inp, self.kernel_size, self.stride, self.padding, return_indices=True)
+        assert idx.shape == own_idx.shape, (cursor[0] - 1, tuple(idx.shape), tuple(own_idx.shape))
+        assert int(idx.min()) >= 0 and int(idx.max()) < inp.shape[2] * inp.shape[3]
+        got = inp.flatten(2).gather(2, idx.flatten(2)).view_as(own)
+        n = int((idx != own_idx).sum())
+        if n:
+            flips[0] += n
+            worst = float((own - got).detach().abs().max() / inp.detach().abs().max().clamp_min(1e-300))
+            within(worst, margin, note=("replayed pool position far from the window's maximum", cursor[0] - 1, n))
+            within(flips[0], max_flips, strict=False, note="replayed decisions that differ from the model's own")
+        return got
+
+    for mod in model.modules():
+        if isinstance(mod, nn.MaxPool2d):
+            mod.forward = types.MethodType(pool_forward, mod)
+
+
+# The fp32 and the float64 forward pass of every case take the SAME ReLU decisions (test_geometry_nets_cpu.py; the tail
+# cases: the same pool positions too): what an engine replays into the reference may differ from the float64 net's own
+# in a handful of entries next to zero (of positions next to their window's maximum), no more
 MAX_FLIPS, MARGIN = 4, 1e-5
 
 
 class Reference:
     """float64 autograd of a deep copy of ``model`` on the CPU at the batch ``(x, t)``; ``masks``: the ReLU decisions to
-    take instead of the float64 net's own (replayed under ``MAX_FLIPS`` / ``MARGIN``).  Every result is a flat float64
+    take instead of the float64 net's own, ``pools``: the ``nn.MaxPool2d`` positions (``pool_positions``' form), both in
+    call order and replayed under ``MAX_FLIPS`` / ``MARGIN`` (one count for both).  Every result is a flat float64
     vector in the order of ``model.parameters()`` (the trainable ones)."""
 
-    def __init__(self, model, x, t, masks=None):
+    def __init__(self, model, x, t, masks=None, pools=None):
         self.model = copy.deepcopy(model).cpu().double()
         self.x, self.t = x.detach().cpu().double(), t.detach().cpu()
         self.flips = None
         if masks is not None:
             self.flips = _replay_relu_decisions(self.model, [m.cpu() for m in masks], max_flips=MAX_FLIPS, margin=MARGIN)
+        if pools is not None:
+            self.flips = [0] if self.flips is None else self.flips
+            _replay_pool_positions(self.model, [p.cpu() for p in pools], self.flips, max_flips=MAX_FLIPS, margin=MARGIN)
         self.params = [p for p in self.model.parameters() if p.requires_grad]
         self.out = self.model(self.x)
         self.loss_t = nn.functional.cross_entropy(self.out, self.t)
@@ -361,7 +535,10 @@ def stock_fp32_errors(case, device, train=False, seeds=(11, 12)):
     model, batches = make(case, train)
     x, t = batches[0]
     sizes = named_sizes(model)
-    ref = Reference(model, x, t, masks=own_masks(copy.deepcopy(model).to(device), x.to(device)))
+    own = copy.deepcopy(model).to(device)
+    # (the tail cases: on its own pool positions too, as the engine's reference is on the engine's)
+    ref = Reference(model, x, t, masks=own_masks(own, x.to(device)),
+                    pools=pool_positions(own, x.to(device)) if case in TAILS else None)
     model, x, t = model.to(device), x.to(device), t.to(device)
     params = [p for p in model.parameters() if p.requires_grad]
     out = model(x)

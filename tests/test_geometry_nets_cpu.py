@@ -7,7 +7,13 @@ the same literals by the GPU tests); the library's planner (host arithmetic) tak
 the fp32 and the float64 forward pass take the same ReLU decisions (what lets the GPU tests cap the replayed decisions at
 a handful); the reference's GGN product is ``J^T H J v`` of an explicitly built Jacobian, symmetric, its diagonal Fisher
 the diagonal of the summed outer products; and ``row_map`` / ``col_map`` are each other's transpose, told apart without
-the transposition."""
+the transposition.
+
+The classifier-tail cases (``geometry_nets.TAILS``, at the end of the file): the same against ``TAIL_GEOMETRY``, with the
+offsets of the tail's tensors in the flat vector and the dense kernels' split counts (the rule restated in
+``geometry_nets.dense_plan`` against the library's ``hf_dense_plan``); fp32 and float64 take the same pool positions too;
+the replay of pool positions is bounded; and a net whose first tail weight has its columns in another feature order than
+(c, h, w) is told apart."""
 
 import copy
 
@@ -214,3 +220,200 @@ def test_replayed_decisions_are_bounded():
     far[1].view(-1)[0] = ~far[1].view(-1)[0]  # one decision the other way, at an input that is not next to zero
     with pytest.raises(AssertionError, match="far from zero"):
         gn.Reference(model, x, t, masks=far)
+
+
+# ---- the classifier-tail cases (``geometry_nets.TAILS``) -----------------------------------------------------------
+def test_the_tail_case_list_is_the_issues():
+    assert gn.TAIL_CASES == list(gn.TAIL_GEOMETRY) == ["tail_rect_pooled", "tail_wide_first", "tail_pixel",
+                                                       "tail_rows_256", "tail_col_map"]
+    assert not set(gn.TAIL_CASES) & set(gn.CASES) and set(gn.TAIL_CAPTURED_CASES) <= set(gn.TAIL_CASES)
+
+
+def _pool_tuple(m):
+    pair = lambda a: list(a) if isinstance(a, (tuple, list)) else [a, a]  # noqa: E731
+    return tuple(pair(m.kernel_size) + pair(m.stride) + pair(m.padding))
+
+
+@pytest.mark.parametrize("case", gn.TAIL_CASES)
+def test_tail_map_sizes_live_taps_offsets_and_plan(case):
+    """Map sizes, live taps, row blocks, the pools, the offsets in the flat vector and the restated dense plan equal the
+    literals of ``geometry_nets.TAIL_GEOMETRY``; the net's output is ``[batch, classes]``."""
+    model, x, layers = _layers(case)
+    lit, n = gn.TAIL_GEOMETRY[case], x.shape[0]
+    got = [(name, (h, w), (oh, ow), _live_taps(h, w, r, s, st, pd), gn.adjoint_row_blocks(n * oh * ow, m.out_channels))
+           for m, name, h, w, r, s, st, pd, oh, ow in layers]
+    assert got == lit["convs"]
+    assert gn.linear_geometry(model) == lit["linears"]
+    assert gn.last_map(model, x) == lit["last"]
+    assert sum(k for _, k in gn.named_sizes(model)) == lit["n"]
+    leaves = [m for m in model.modules() if not list(m.children())]
+    pools = []
+    for a, b in zip(leaves, leaves[1:] + [None]):  # per convolution: the pool behind it (behind its ReLU), or None
+        if isinstance(a, nn.Conv2d):
+            pools.append(None)
+        elif isinstance(a, nn.MaxPool2d):
+            pools[-1] = _pool_tuple(a)
+    assert pools == lit["pools"]
+    rows, hw, c = lit["last"]
+    assert lit["linears"][0][0] == hw * c and rows == n
+    assert [b[0] for b in lit["linears"][1:]] == [a[1] for a in lit["linears"][:-1]]
+    with torch.no_grad():
+        assert tuple(model(x).shape) == (n, gn.TAILS[case]["classes"]) == (n, lit["linears"][-1][1])
+
+
+@pytest.mark.parametrize("case", gn.TAIL_CASES)
+def test_the_librarys_dense_plan_is_the_restated_rule(case):
+    """``hf_dense_plan`` (host arithmetic) counts the slabs ``geometry_nets.dense_plan`` restates."""
+    lib = _lib.load()
+    rows = gn.TAIL_GEOMETRY[case]["last"][0]
+    for c_in, c_out, s_t, s_d, _, _ in gn.TAIL_GEOMETRY[case]["linears"]:
+        st, sd = _lib.c_int(), _lib.c_int()
+        assert lib.hf_dense_plan(rows, c_in, c_out, st, sd) == 0
+        assert (st.value, sd.value) == (s_t, s_d) == gn.dense_plan(c_in, c_out), (c_in, c_out)
+
+
+def test_the_tail_cases_reach_what_they_are_named_for():
+    G = gn.TAIL_GEOMETRY
+    # data-gradient slabs that are summed: by hf_unflatten_slabs_nhwc (a FIRST tail layer) and by the layer in front
+    assert G["tail_wide_first"]["linears"][0][3] == 3 and G["tail_wide_first"]["linears"][1][3] == 2
+    assert G["tail_col_map"]["linears"][0][3] == 2
+    assert [(a[2], a[3]) for a in G["tail_wide_first"]["linears"]] == [(20, 3), (3, 2), (2, 1)]
+    assert [(a[2], a[3]) for a in G["tail_col_map"]["linears"]] == [(1, 2), (2, 1)]
+    # operands off the 16-byte grid, row pitches that are no multiple of 4
+    c_in, _, _, _, w_off, b_off = G["tail_rect_pooled"]["linears"][1]
+    assert (w_off, w_off % 4, c_in % 4) == (2057, 1, 1) and b_off % 4 == 0
+    c_in, _, _, _, w_off, b_off = G["tail_wide_first"]["linears"][1]
+    assert (w_off, w_off % 4, c_in % 4, b_off) == (88630, 2, 2, None)
+    assert G["tail_wide_first"]["linears"][2][5] == 91105 and 91105 % 4 == 1
+    # two flatten tiles with a partial last one, both ways
+    _, hw, c = G["tail_wide_first"]["last"]
+    for d in (hw, c):
+        assert -(-d // gn.FLATTEN_TILE) == 2 and d % gn.FLATTEN_TILE
+    assert G["tail_wide_first"]["pools"] == [None] and len(G["tail_wide_first"]["linears"]) == 3
+    # the last map pooled and non-square; a Dropout leaf behind Flatten
+    assert G["tail_rect_pooled"]["pools"][-1] is not None and G["tail_rect_pooled"]["last"] == (3, 2 * 3, 12)
+    model, _ = gn.make("tail_rect_pooled")
+    kinds = [type(m) for m in model.net]
+    assert kinds.index(nn.Dropout) == kinds.index(nn.Flatten) + 1 and not model.training
+    # one pixel, one sample, no ReLU behind the last convolution, four input channels (no im2col)
+    assert G["tail_pixel"]["last"][:2] == (1, 1)
+    model, _ = gn.make("tail_pixel")
+    kinds = [type(m) for m in model.net]
+    assert kinds[kinds.index(nn.Flatten) - 1] is nn.Conv2d and model.net[0].in_channels == 4
+    assert G["tail_rows_256"]["last"][0] == 256
+    # a one-column map: the outer kernel columns of both convolutions meet only padding
+    assert [a[3] for a in G["tail_col_map"]["convs"]] == [0b010010010] * 2
+
+
+def _differing_positions(model, x):
+    p32 = gn.pool_positions(copy.deepcopy(model), x)
+    p64 = gn.pool_positions(copy.deepcopy(model).double(), x.double())
+    assert len(p32) == len(p64)
+    return sum(int((a != b).sum()) for a, b in zip(p32, p64))
+
+
+@pytest.mark.parametrize("case", gn.TAIL_CASES)
+def test_tail_fp32_and_float64_take_the_same_relu_decisions_and_pool_positions(case):
+    model, batches = gn.make(case)
+    assert len(gn.pool_positions(model, batches[0][0])) == sum(p is not None for p in gn.TAIL_GEOMETRY[case]["pools"])
+    for x, t in batches:
+        assert _differing_decisions(model, x) == 0, case
+        assert _differing_positions(model, x) == 0, case
+        # ... and the reference on the fp32 pass's decisions is the reference on its own, with nothing replayed
+        ref = gn.Reference(model, x, t, masks=gn.own_masks(model, x), pools=gn.pool_positions(model, x))
+        assert ref.flips == [0] and abs(ref.loss() - gn.Reference(model, x, t).loss()) == 0.0
+
+
+@pytest.mark.parametrize("case", ["tail_rect_pooled", "tail_wide_first"])
+def test_the_tail_reference_is_the_explicit_ggn(case):
+    """``J^T H J v`` of an explicitly built Jacobian, symmetric; gradient and diagonal Fisher by the same Jacobian."""
+    model, batches = gn.make(case)
+    x, t = batches[0]
+    ref = gn.Reference(model, x, t)
+    n = ref.gradient().numel()
+    assert n == gn.TAIL_GEOMETRY[case]["n"]
+    J = _flat_jacobian(ref.model, ref.x)
+    H = torch.autograd.functional.hessian(lambda z: nn.functional.cross_entropy(z.view_as(ref.out), ref.t),
+                                          ref.out.detach().reshape(-1))
+    u, v = gn.probe(n, 1).double(), gn.probe(n, 2).double()
+    gv, gu = ref.ggn(v), ref.ggn(u)
+    want = J.t() @ (H @ (J @ v))
+    assert float((gv - want).abs().max() / want.abs().max()) < 1e-10
+    a, b = float(u @ gv), float(v @ gu)
+    assert abs(a - b) <= 1e-12 * abs(a)
+    dl = torch.autograd.grad(nn.functional.cross_entropy(z := ref.out.detach().clone().requires_grad_(True), ref.t), z)[0]
+    assert float((ref.gradient() - J.t() @ dl.reshape(-1)).abs().max() / ref.gradient().abs().max()) < 1e-10
+    # diagonal Fisher: sample i's gradient is J_i^T (d loss_i / d logits_i) -- rows of the same Jacobian, unaveraged
+    rows, classes = ref.out.shape
+    gi = torch.einsum("ikp,ik->ip", J.view(rows, classes, n), dl * rows)
+    d = ref.diag_ef()
+    assert float((d - (gi ** 2).sum(0) / rows).abs().max() / d.abs().max()) < 1e-12
+    assert float(ref.loss()) > 0 and bool((d >= 0).all())
+
+
+def _misordered_twin(order):
+    """``tail_rect_pooled`` as an engine would compute it that flattened the last map's features in ``order`` instead of
+    (c, h, w) and read the first Linear's weight in place: the net whose first tail weight has its columns permuted;
+    returns it with the maps of a flat vector into its layout and back."""
+    model, batches = gn.make("tail_rect_pooled")
+    _, hw, c = gn.TAIL_GEOMETRY["tail_rect_pooled"]["last"]
+    h, w = 2, 3
+    assert h * w == hw
+    true = torch.arange(c * h * w).view(c, h, w)
+    perm = true.permute(*["chw".index(a) for a in order]).reshape(-1)  # wrong flat position j holds true feature perm[j]
+    inv = torch.argsort(perm)
+    assert not torch.equal(perm, torch.arange(c * hw))
+    first = next(m for m in model.modules() if isinstance(m, nn.Linear))
+    twin = copy.deepcopy(model)
+    with torch.no_grad():
+        next(m for m in twin.modules() if isinstance(m, nn.Linear)).weight.copy_(first.weight[:, inv])
+    off = gn.TAIL_GEOMETRY["tail_rect_pooled"]["linears"][0][4]
+
+    def columns(vec, index):
+        out = vec.clone()
+        out[off:off + first.weight.numel()] = vec[off:off + first.weight.numel()].view_as(first.weight)[:, index].reshape(-1)
+        return out
+
+    return model, twin, batches[0], (lambda vec: columns(vec, inv)), (lambda vec: columns(vec, perm))
+
+
+@pytest.mark.parametrize("order", ["cwh", "hwc"])
+def test_the_measure_sees_a_wrong_feature_order(order):
+    """The analogue of the transposed twin for the ``nn.Flatten`` boundary: with the columns of the first tail weight
+    and of the vector permuted as if the features ran (c, w, h) or (h, w, c), the reference product is far from the
+    true one -- an engine that flattened in another order than (c, h, w) cannot pass for the right one."""
+    model, twin, (x, t), into, back = _misordered_twin(order)
+    ref, ref_p = gn.Reference(model, x, t), gn.Reference(twin, x, t)
+    n = ref.gradient().numel()
+    v = gn.probe(n, 3).double()
+    assert torch.equal(back(into(v)), v)
+    true = ref.ggn(v)
+    wrong = back(ref_p.ggn(into(v)))
+    assert float((wrong - true).abs().max() / true.abs().max()) > 1e-2
+    assert float((ref_p.ggn(v) - true).abs().max() / true.abs().max()) > 1e-2  # (nor without the way back)
+    off = 0
+    for name, k in gn.named_sizes(model):  # every tensor: the tail's and the convolutions' in front of it
+        a, b = wrong[off:off + k], true[off:off + k]
+        assert float((a - b).abs().max() / b.abs().max()) > 1e-2, name
+        off += k
+    assert gn.scalar_error(ref_p.loss(), ref.loss()) > 1e-2
+    g = back(ref_p.gradient())
+    assert float((g - ref.gradient()).abs().max() / ref.gradient().abs().max()) > 1e-2
+
+
+def test_replayed_pool_positions_are_bounded():
+    """A replayed position may leave its window's own maximum only next to a tie, and counts as a differing decision."""
+    model, batches = gn.make("tail_rect_pooled")
+    x, t = batches[0]
+    pools = gn.pool_positions(copy.deepcopy(model).double(), x.double())
+    assert [tuple(p.shape) for p in pools] == [(3, 8, 4, 3), (3, 12, 2, 3)]
+    assert gn.Reference(model, x, t, pools=pools).flips == [0]
+    far = [p.clone() for p in pools]
+    own = far[1][0, 0, 0, 0].item()  # (the second pool: windows of two rows, one column of a 4x3 map)
+    far[1][0, 0, 0, 0] = 3 - own if own in (0, 3) else own  # the window's other entry
+    values = gn.relu_inputs(copy.deepcopy(model).double(), x.double())[1].clamp_min(0)[0, 0].reshape(-1)
+    assert far[1][0, 0, 0, 0] != own and values[own] - values[3 - own] > 1e-3 * values.max()
+    with pytest.raises(AssertionError, match="far from the window's maximum"):
+        gn.Reference(model, x, t, pools=far)
+    with pytest.raises(AssertionError):  # (a position outside the map is no decision at all)
+        gn.Reference(model, x, t, pools=[pools[0], pools[1] + 12])
