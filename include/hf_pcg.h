@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 24
+#define HF_ABI_VERSION 25
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -807,6 +807,37 @@ int hf_pool_act_adjoint_nhwc(void* ga, void* gb, int row_blocks, const void* gy,
                              const void* idx, const void* y_pool, int relu, int64_t n, int64_t h, int64_t w,
                              int64_t oh, int64_t ow, int64_t c, int64_t kh, int64_t kw, int64_t stride_h,
                              int64_t stride_w, int64_t pad_h, int64_t pad_w, int dtype, void* stream);
+/*
+ * The same pair for a pooled unit with an eval-mode BatchNorm instead of a bias (ABI 25):
+ *   y_pool = max_pool(relu?(xhat*w + b)),  xhat = (a - mean)*rstd;  a [n,h,w,c]: the convolution's output; mean, rstd, w
+ * per channel (any 4-byte boundary), all four required.  The mask is the pooled map's, as above (the BatchNorm in front of
+ * the ReLU does not change where a window's maximum is positive).
+ *
+ * hf_pool_bn_act_tangent_nhwc, with p = idx[n,oy,ox,c] and T = sum_s slabs[s][n,p,c] in split order:
+ *   out[n,oy,ox,c] = m * (T*(w[c]*rstd[c]) + ((a[n,p,c] - mean[c])*rstd[c])*v_w[c] + v_b[c])
+ * v_w / v_b nullable (frozen parameters; slices of the flat vector on any 4-byte boundary; a is only read with v_w).
+ * Rounding: hf_chan_affine_ex's sequence for the same element -- w*rstd first, T times it, xhat = (a - mean)*rstd, times
+ * v_w, added, + v_b, one rounding each, then the mask as a select: bitwise that kernel's unmasked dense output gathered at
+ * idx and masked.
+ *
+ * hf_pool_bn_act_adjoint_nhwc: g_ = what hf_pool_act_adjoint_nhwc writes to its ga from the same gy / idx / y_pool (bitwise)
+ *   g (nullable) = g_;   ga = g_ * (w[c]*rstd[c])  (w*rstd formed first: hf_bn_adjoint_v4's rounding);
+ *   gb[b] = sum over row share b of g_,   gw[b] = sum over row share b of g_ * (float)((a - mean)*rstd)
+ * gw / gb: each nullable, `row_blocks` partial rows c elements apart for hf_pack_ex, shares and the empty-share refusal as
+ * above, accumulated in fp64 (thread order as above) and rounded once per partial row.  gw == gb == NULL: one pixel per
+ * thread, row_blocks is not read (the sums are then somebody else's: hf_bn_sums_multi on the stored g).
+ * Both: the refusals, the 16-byte / element-wise forms (also g and, in the adjoint, a must be 16-byte aligned for the wide
+ * form) and the repeatability of the bias pair; a null a, mean, rstd or w is HF_ERR_ARG.
+ */
+int hf_pool_bn_act_tangent_nhwc(void* out, int64_t out_ld, const void* slabs, int splits, int64_t slab_stride,
+                                const void* a, const void* mean, const void* rstd, const void* w, const void* v_w,
+                                const void* v_b, const void* idx, const void* y_pool, int relu, int64_t n, int64_t h,
+                                int64_t w_, int64_t oh, int64_t ow, int64_t c, int dtype, void* stream);
+int hf_pool_bn_act_adjoint_nhwc(void* ga, void* g, void* gw, void* gb, int row_blocks, const void* gy, int gy_splits,
+                                int64_t gy_slab, const void* a, const void* mean, const void* rstd, const void* w,
+                                const void* idx, const void* y_pool, int relu, int64_t n, int64_t h, int64_t w_,
+                                int64_t oh, int64_t ow, int64_t c, int64_t kh, int64_t kw, int64_t stride_h,
+                                int64_t stride_w, int64_t pad_h, int64_t pad_w, int dtype, void* stream);
 /*
  * hf_linear_ce_head: the classifier head of J^T H_L J v in one launch (one workgroup per 4 rows):
  *   Jv = t_feat W^T + feat V_W^T + v_b;  HJv = scale * p * (Jv - <p, Jv>) (as hf_softmax_ce_hvp);

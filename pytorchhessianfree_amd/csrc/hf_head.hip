@@ -111,12 +111,21 @@ __global__ __launch_bounds__(HB) void k_maxpool_forward(float* __restrict__ out,
 // full-resolution tangent map, the mask comes from the pooled map.  A thread owns W consecutive channels of a pixel
 // (W = 4: 16-byte loads of idx / y_pool / cotangents, 16-byte stores; W = 1: any channel count and alignment).
 // ---------------------------------------------------------------------------------------
-template <int W>
+// A pooled BatchNorm unit  y_pool = max_pool(relu?(xhat*w + b)),  xhat = (a - mean)*rstd  (eval mode), is the same pair
+// of kernels under the flag BN, with these operands (the bias instantiations carry them unread and keep their bits):
+//   tangent:  t_pool = m * (t_a[idx]*(w*rstd) + xhat[idx]*v_w + v_b)    -- hf_chan_affine_ex's rounding sequence
+//   adjoint:  g = the bias form's g_a (unscaled, masked);  g_a = g*(w*rstd);  gb = sum g,  gw = sum g*xhat
+struct PoolBn {
+  const float *a, *mean, *rstd, *w, *vw;
+};
+
+template <int W, bool BN>
 __global__ __launch_bounds__(HB) void k_pool_act_tangent(float* __restrict__ out, const float* __restrict__ slabs,
                                                          int splits, long long slab_stride,
                                                          const float* __restrict__ vb, const int* __restrict__ idx,
                                                          const float* __restrict__ ypool, unsigned total,
-                                                         unsigned CQ, unsigned out_ld, unsigned opix, unsigned ipix) {
+                                                         unsigned CQ, unsigned out_ld, unsigned opix, unsigned ipix,
+                                                         const PoolBn bn) {
   using VF = ColOf<float, W>;
   using VI = ColOf<int, W>;
   const unsigned i = blockIdx.x * HB + threadIdx.x;
@@ -130,6 +139,15 @@ __global__ __launch_bounds__(HB) void k_pool_act_tangent(float* __restrict__ out
 #pragma unroll
     for (int k = 0; k < W; ++k) b.e[k] = vb[c0 + k];
   }
+  VF sc, rs, mu, q, av;  // (BN) per channel: w*rstd, rstd, mean, v_w; the convolution output at the position
+  if constexpr (BN) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      rs.e[k] = bn.rstd[c0 + k];
+      sc.e[k] = bn.w[c0 + k] * rs.e[k];
+      if (bn.vw) { mu.e[k] = bn.mean[c0 + k]; q.e[k] = bn.vw[c0 + k]; }
+    }
+  }
   unsigned off[W];
 #pragma unroll
   for (int k = 0; k < W; ++k) {
@@ -137,6 +155,9 @@ __global__ __launch_bounds__(HB) void k_pool_act_tangent(float* __restrict__ out
     const unsigned p = (unsigned)ix.e[k] < ipix ? (unsigned)ix.e[k] : ipix - 1;
     off[k] = (n * ipix + p) * C + c0 + k;
     s.e[k] = slabs[off[k]];
+    if constexpr (BN) {
+      if (bn.vw) av.e[k] = bn.a[off[k]];
+    }
   }
   // slab_sum, for the W channels together: one batch of all of them in flight, each channel added in split order
   for (int sp = 1; sp < splits; sp += 8) {
@@ -149,6 +170,10 @@ __global__ __launch_bounds__(HB) void k_pool_act_tangent(float* __restrict__ out
 #pragma unroll
   for (int k = 0; k < W; ++k) {
     float t = s.e[k];
+    if constexpr (BN) {
+      t = t * sc.e[k];
+      if (bn.vw) t = t + ((av.e[k] - mu.e[k]) * rs.e[k]) * q.e[k];
+    }
     if (vb) t = t + b.e[k];
     if (ypool) t = m.e[k] > 0.f ? t : 0.f;
     s.e[k] = t;
@@ -194,12 +219,22 @@ __device__ __forceinline__ ColOf<float, W> pool_act_adjoint_at(const float* __re
   return acc;
 }
 
-// without bias sums: one pixel's W channels per thread
+// (BN) g_a = g * (w*rstd), w*rstd formed first: hf_bn_adjoint_v4's rounding
 template <int W>
-__global__ __launch_bounds__(HB) void k_pool_act_adjoint(float* __restrict__ ga, const float* __restrict__ gy,
-                                                         int splits, long long slab, const int* __restrict__ idx,
+__device__ __forceinline__ ColOf<float, W> pool_bn_scale(const ColOf<float, W>& g, const PoolBn& bn, unsigned c0) {
+  ColOf<float, W> o;
+#pragma unroll
+  for (int k = 0; k < W; ++k) o.e[k] = g.e[k] * (bn.w[c0 + k] * bn.rstd[c0 + k]);
+  return o;
+}
+
+// without per-channel sums: one pixel's W channels per thread
+template <int W, bool BN>
+__global__ __launch_bounds__(HB) void k_pool_act_adjoint(float* __restrict__ ga, float* __restrict__ g,
+                                                         const float* __restrict__ gy, int splits, long long slab,
+                                                         const int* __restrict__ idx,
                                                          const float* __restrict__ ypool, unsigned total,
-                                                         unsigned CQ, PoolGeo q) {
+                                                         unsigned CQ, PoolGeo q, const PoolBn bn) {
   const unsigned i = blockIdx.x * HB + threadIdx.x;
   if (i >= total) return;
   const unsigned cq = i % CQ, C = CQ * W;
@@ -209,50 +244,79 @@ __global__ __launch_bounds__(HB) void k_pool_act_adjoint(float* __restrict__ ga,
   const int y = pix % q.H;
   const int n = pix / q.H;
   const ColOf<float, W> v = pool_act_adjoint_at<W>(gy, splits, slab, idx, ypool, C, cq * W, n, y, x, q);
-  chain_store_col<HF_WT_ELEM>(ga + (size_t)row * C + cq * W, v);
+  if constexpr (BN) {
+    if (g) chain_store_col<HF_WT_ELEM>(g + (size_t)row * C + cq * W, v);
+    chain_store_col<HF_WT_ELEM>(ga + (size_t)row * C + cq * W, pool_bn_scale<W>(v, bn, cq * W));
+  } else {
+    chain_store_col<HF_WT_ELEM>(ga + (size_t)row * C + cq * W, v);
+  }
 }
 
-// with bias sums: workgroup b owns the full-resolution rows [b*per, (b+1)*per) and all channels, as the row-major
+// with per-channel sums: workgroup b owns the full-resolution rows [b*per, (b+1)*per) and all channels, as the row-major
 // BatchNorm adjoint (hf_bn.hip) does; thread (tx, ty) walks channel column tx of every G-th row of the share and keeps
 // its sum in fp64; the G sums of a column are added in ty order and rounded once -> gb[b*C + channel]
-template <int W>
-__global__ __launch_bounds__(HB) void k_pool_act_adjoint_rows(float* __restrict__ ga, float* __restrict__ gb,
+// (BN: a second sum per channel, of g * xhat with xhat rounded to fp32 first -> gw[b*C + channel]; either is nullable)
+template <int W, bool BN>
+__global__ __launch_bounds__(HB) void k_pool_act_adjoint_rows(float* __restrict__ ga, float* __restrict__ g,
+                                                              float* __restrict__ gw, float* __restrict__ gb,
                                                               const float* __restrict__ gy, int splits,
                                                               long long slab, const int* __restrict__ idx,
                                                               const float* __restrict__ ypool, unsigned rows,
-                                                              unsigned per, unsigned CQ, PoolGeo q) {
-  __shared__ double red[HB * W];
+                                                              unsigned per, unsigned CQ, PoolGeo q, const PoolBn bn) {
+  constexpr int S = BN ? 2 : 1;  // sums per channel
+  __shared__ double red[HB * W * S];
   const unsigned C = CQ * W, cols = CQ < HB ? CQ : HB, G = HB / cols;
   const unsigned tx = threadIdx.x % cols, ty = threadIdx.x / cols;
   const unsigned lo = blockIdx.x * per, hi = lo + per < rows ? lo + per : rows;
   for (unsigned cb = 0; cb < CQ; cb += cols) {
     const unsigned cq = cb + tx;
     const bool live = ty < G && cq < CQ;
-    double acc[W];
+    double acc[W * S];
 #pragma unroll
-    for (int k = 0; k < W; ++k) acc[k] = 0.0;
+    for (int k = 0; k < W * S; ++k) acc[k] = 0.0;
     if (live) {
+      float rs[W], mu[W];
+      if constexpr (BN) {
+        if (gw) {
+#pragma unroll
+          for (int k = 0; k < W; ++k) { rs[k] = bn.rstd[cq * W + k]; mu[k] = bn.mean[cq * W + k]; }
+        }
+      }
       for (unsigned r = lo + ty; r < hi; r += G) {
         unsigned pix = r;
         const int x = pix % q.W; pix /= q.W;
         const int y = pix % q.H;
         const int n = pix / q.H;
+        ColOf<float, W> av;
+        if constexpr (BN) {
+          if (gw) av = *reinterpret_cast<const ColOf<float, W>*>(bn.a + (size_t)r * C + cq * W);
+        }
         const ColOf<float, W> v = pool_act_adjoint_at<W>(gy, splits, slab, idx, ypool, C, cq * W, n, y, x, q);
-        chain_store_col<HF_WT_ELEM>(ga + (size_t)r * C + cq * W, v);
+        if constexpr (BN) {
+          if (g) chain_store_col<HF_WT_ELEM>(g + (size_t)r * C + cq * W, v);
+          chain_store_col<HF_WT_ELEM>(ga + (size_t)r * C + cq * W, pool_bn_scale<W>(v, bn, cq * W));
+          if (gw) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) acc[W + k] += (double)v.e[k] * (double)(float)((av.e[k] - mu[k]) * rs[k]);
+          }
+        } else {
+          chain_store_col<HF_WT_ELEM>(ga + (size_t)r * C + cq * W, v);
+        }
 #pragma unroll
         for (int k = 0; k < W; ++k) acc[k] += (double)v.e[k];
       }
 #pragma unroll
-      for (int k = 0; k < W; ++k) red[(ty * cols + tx) * W + k] = acc[k];
+      for (int k = 0; k < W * S; ++k) red[(ty * cols + tx) * W * S + k] = acc[k];
     }
     __syncthreads();
     if (ty == 0 && cq < CQ) {
 #pragma unroll
-      for (int k = 0; k < W; ++k) {
+      for (int k = 0; k < W * S; ++k) {
+        float* dst = k < W ? gb : gw;
         double sum = 0.0;
-        for (unsigned t = 0; t < G; ++t) sum += red[(t * cols + tx) * W + k];
+        for (unsigned t = 0; t < G; ++t) sum += red[(t * cols + tx) * W * S + k];
         const float f = (float)sum;
-        chain_store<HF_WT_ELEM>(&gb[(size_t)blockIdx.x * C + cq * W + k], f);
+        if (dst) chain_store<HF_WT_ELEM>(&dst[(size_t)blockIdx.x * C + cq * W + (k < W ? k : k - W)], f);
       }
     }
     __syncthreads();
@@ -527,6 +591,91 @@ inline int flatten_grid(int64_t n, int64_t hw, int64_t c, int dtype, unsigned* t
   return HF_OK;
 }
 
+// the two pooled-unit entry points of each direction share everything but the BatchNorm operands (bn: NULL = a bias unit)
+int pool_act_tangent(void* out, int64_t out_ld, const void* slabs, int splits, int64_t slab_stride, const void* v_b,
+                     const void* idx, const void* y_pool, int relu, int64_t n, int64_t h, int64_t w, int64_t oh,
+                     int64_t ow, int64_t c, int dtype, void* stream, const PoolBn* bn) {
+  if (dtype != HF_F32 || !out || !slabs || !idx || (relu && !y_pool)) return HF_ERR_ARG;
+  if (n < 1 || h < 1 || w < 1 || oh < 1 || ow < 1 || c < 1) return HF_ERR_ARG;
+  if (splits < 1 || splits > HF_POOL_ACT_MAX_SPLITS) return HF_ERR_ARG;
+  if (out_ld == 0) out_ld = c;
+  if (out_ld < c) return HF_ERR_ARG;
+  // (every factor below 2^31 first: the products cannot wrap)
+  const int64_t lim = 1LL << 31;
+  if (n >= lim || h >= lim || w >= lim || oh >= lim || ow >= lim || c >= lim || out_ld >= lim) return HF_ERR_ARG;
+  if (h * w >= lim || oh * ow >= lim || n * (h * w) >= lim || n * (oh * ow) >= lim) return HF_ERR_ARG;
+  const int64_t full = n * h * w * c, total = n * oh * ow * c;
+  if (full >= lim || total >= lim || n * oh * ow * out_ld >= lim) return HF_ERR_ARG;
+  if (splits > 1 && slab_stride < full) return HF_ERR_ARG;  // (slabs would overlap)
+  const float* yp = relu ? (const float*)y_pool : nullptr;
+  const bool quad = c % 4 == 0 && out_ld % 4 == 0 && al16(out) && al16(idx) && (!yp || al16(yp));
+  const unsigned cq = (unsigned)(quad ? c / 4 : c), items = (unsigned)(total / (quad ? 4 : 1));
+  const PoolBn ops = bn ? *bn : PoolBn{};
+#define HF_PAT(W, BN)                                                                                              \
+  hipLaunchKernelGGL((k_pool_act_tangent<W, BN>), dim3((items + HB - 1) / HB), dim3(HB), 0, (hipStream_t)stream,  \
+                     (float*)out, (const float*)slabs, splits, (long long)slab_stride, (const float*)v_b,         \
+                     (const int*)idx, yp, items, cq, (unsigned)out_ld, (unsigned)(oh * ow), (unsigned)(h * w), ops)
+  if (bn) { if (quad) HF_PAT(4, true); else HF_PAT(1, true); }
+  else if (quad) HF_PAT(4, false);
+  else HF_PAT(1, false);
+#undef HF_PAT
+  return (int)hipGetLastError();
+}
+
+int pool_act_adjoint(void* ga, void* g, void* gw, void* gb, int row_blocks, const void* gy, int gy_splits, int64_t gy_slab,
+                     const void* idx, const void* y_pool, int relu, int64_t n, int64_t h, int64_t w, int64_t oh,
+                     int64_t ow, int64_t c, int64_t kh, int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h,
+                     int64_t pad_w, int dtype, void* stream, const PoolBn* bn) {
+  if (dtype != HF_F32 || !ga || !gy || !idx || (relu && !y_pool)) return HF_ERR_ARG;
+  if (n < 1 || h < 1 || w < 1 || oh < 1 || ow < 1 || c < 1) return HF_ERR_ARG;
+  if (kh < 1 || kw < 1 || stride_h < 1 || stride_w < 1 || pad_h < 0 || pad_w < 0) return HF_ERR_ARG;
+  if (gy_splits < 1 || gy_splits > HF_POOL_ACT_MAX_SPLITS) return HF_ERR_ARG;
+  const int64_t lim = 1LL << 31;
+  if (n >= lim || h >= lim || w >= lim || oh >= lim || ow >= lim || c >= lim) return HF_ERR_ARG;
+  if (kh >= lim || kw >= lim || stride_h >= lim || stride_w >= lim || pad_h >= lim || pad_w >= lim) return HF_ERR_ARG;
+  // the pooled extent of a max-pool without dilation / ceil_mode
+  if (h + 2 * pad_h < kh || w + 2 * pad_w < kw) return HF_ERR_ARG;
+  if (oh != (h + 2 * pad_h - kh) / stride_h + 1 || ow != (w + 2 * pad_w - kw) / stride_w + 1) return HF_ERR_ARG;
+  if (h * w >= lim || oh * ow >= lim || n * (h * w) >= lim || n * (oh * ow) >= lim) return HF_ERR_ARG;
+  const int64_t rows = n * h * w, full = rows * c, pooled = n * oh * ow * c;
+  if (full >= lim || pooled >= lim) return HF_ERR_ARG;
+  if (gy_splits > 1 && gy_slab < pooled) return HF_ERR_ARG;  // (slabs would overlap)
+  int64_t per = 0;
+  if (gb || gw) {
+    if (row_blocks < 1) return HF_ERR_ARG;
+    per = (rows + row_blocks - 1) / row_blocks;
+    if ((int64_t)(row_blocks - 1) * per >= rows) return HF_ERR_ARG;  // an empty share
+  }
+  const float* yp = relu ? (const float*)y_pool : nullptr;
+  const bool quad = c % 4 == 0 && al16(ga) && al16(gy) && al16(idx) && (!yp || al16(yp)) &&
+                    (gy_splits == 1 || gy_slab % 4 == 0) && al16(g) && (!bn || al16(bn->a));
+  const unsigned cq = (unsigned)(quad ? c / 4 : c);
+  PoolGeo q{(int)h, (int)w, (int)oh, (int)ow, (int)kh, (int)kw, (int)stride_h, (int)stride_w, (int)pad_h, (int)pad_w};
+  hipStream_t s = (hipStream_t)stream;
+  const PoolBn ops = bn ? *bn : PoolBn{};
+  if (gb || gw) {
+#define HF_PAA(W, BN)                                                                                              \
+  hipLaunchKernelGGL((k_pool_act_adjoint_rows<W, BN>), dim3((unsigned)row_blocks), dim3(HB), 0, s, (float*)ga,    \
+                     (float*)g, (float*)gw, (float*)gb, (const float*)gy, gy_splits, (long long)gy_slab,          \
+                     (const int*)idx, yp, (unsigned)rows, (unsigned)per, cq, q, ops)
+    if (bn) { if (quad) HF_PAA(4, true); else HF_PAA(1, true); }
+    else if (quad) HF_PAA(4, false);
+    else HF_PAA(1, false);
+#undef HF_PAA
+  } else {
+    const unsigned items = (unsigned)(rows * cq);
+#define HF_PAE(W, BN)                                                                                              \
+  hipLaunchKernelGGL((k_pool_act_adjoint<W, BN>), dim3((items + HB - 1) / HB), dim3(HB), 0, s, (float*)ga,        \
+                     (float*)g, (const float*)gy, gy_splits, (long long)gy_slab, (const int*)idx, yp, items, cq, q, \
+                     ops)
+    if (bn) { if (quad) HF_PAE(4, true); else HF_PAE(1, true); }
+    else if (quad) HF_PAE(4, false);
+    else HF_PAE(1, false);
+#undef HF_PAE
+  }
+  return (int)hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" {
@@ -583,79 +732,37 @@ int hf_maxpool_adjoint_nhwc(void* g, const void* gy_a, int a_splits, int64_t a_s
 int hf_pool_act_tangent_nhwc(void* out, int64_t out_ld, const void* slabs, int splits, int64_t slab_stride,
                              const void* v_b, const void* idx, const void* y_pool, int relu, int64_t n, int64_t h,
                              int64_t w, int64_t oh, int64_t ow, int64_t c, int dtype, void* stream) {
-  if (dtype != HF_F32 || !out || !slabs || !idx || (relu && !y_pool)) return HF_ERR_ARG;
-  if (n < 1 || h < 1 || w < 1 || oh < 1 || ow < 1 || c < 1) return HF_ERR_ARG;
-  if (splits < 1 || splits > HF_POOL_ACT_MAX_SPLITS) return HF_ERR_ARG;
-  if (out_ld == 0) out_ld = c;
-  if (out_ld < c) return HF_ERR_ARG;
-  // (every factor below 2^31 first: the products cannot wrap)
-  const int64_t lim = 1LL << 31;
-  if (n >= lim || h >= lim || w >= lim || oh >= lim || ow >= lim || c >= lim || out_ld >= lim) return HF_ERR_ARG;
-  if (h * w >= lim || oh * ow >= lim || n * (h * w) >= lim || n * (oh * ow) >= lim) return HF_ERR_ARG;
-  const int64_t full = n * h * w * c, total = n * oh * ow * c;
-  if (full >= lim || total >= lim || n * oh * ow * out_ld >= lim) return HF_ERR_ARG;
-  if (splits > 1 && slab_stride < full) return HF_ERR_ARG;  // (slabs would overlap)
-  const float* yp = relu ? (const float*)y_pool : nullptr;
-  const bool quad = c % 4 == 0 && out_ld % 4 == 0 && al16(out) && al16(idx) && (!yp || al16(yp));
-  const unsigned cq = (unsigned)(quad ? c / 4 : c), items = (unsigned)(total / (quad ? 4 : 1));
-#define HF_PAT(W)                                                                                                  \
-  hipLaunchKernelGGL((k_pool_act_tangent<W>), dim3((items + HB - 1) / HB), dim3(HB), 0, (hipStream_t)stream,      \
-                     (float*)out, (const float*)slabs, splits, (long long)slab_stride, (const float*)v_b,         \
-                     (const int*)idx, yp, items, cq, (unsigned)out_ld, (unsigned)(oh * ow), (unsigned)(h * w))
-  if (quad) HF_PAT(4);
-  else HF_PAT(1);
-#undef HF_PAT
-  return (int)hipGetLastError();
+  return pool_act_tangent(out, out_ld, slabs, splits, slab_stride, v_b, idx, y_pool, relu, n, h, w, oh, ow, c, dtype,
+                          stream, nullptr);
+}
+
+int hf_pool_bn_act_tangent_nhwc(void* out, int64_t out_ld, const void* slabs, int splits, int64_t slab_stride,
+                                const void* a, const void* mean, const void* rstd, const void* w, const void* v_w,
+                                const void* v_b, const void* idx, const void* y_pool, int relu, int64_t n, int64_t h,
+                                int64_t w_, int64_t oh, int64_t ow, int64_t c, int dtype, void* stream) {
+  if (!a || !mean || !rstd || !w) return HF_ERR_ARG;
+  const PoolBn bn{(const float*)a, (const float*)mean, (const float*)rstd, (const float*)w, (const float*)v_w};
+  return pool_act_tangent(out, out_ld, slabs, splits, slab_stride, v_b, idx, y_pool, relu, n, h, w_, oh, ow, c, dtype,
+                          stream, &bn);
 }
 
 int hf_pool_act_adjoint_nhwc(void* ga, void* gb, int row_blocks, const void* gy, int gy_splits, int64_t gy_slab,
                              const void* idx, const void* y_pool, int relu, int64_t n, int64_t h, int64_t w,
                              int64_t oh, int64_t ow, int64_t c, int64_t kh, int64_t kw, int64_t stride_h,
                              int64_t stride_w, int64_t pad_h, int64_t pad_w, int dtype, void* stream) {
-  if (dtype != HF_F32 || !ga || !gy || !idx || (relu && !y_pool)) return HF_ERR_ARG;
-  if (n < 1 || h < 1 || w < 1 || oh < 1 || ow < 1 || c < 1) return HF_ERR_ARG;
-  if (kh < 1 || kw < 1 || stride_h < 1 || stride_w < 1 || pad_h < 0 || pad_w < 0) return HF_ERR_ARG;
-  if (gy_splits < 1 || gy_splits > HF_POOL_ACT_MAX_SPLITS) return HF_ERR_ARG;
-  const int64_t lim = 1LL << 31;
-  if (n >= lim || h >= lim || w >= lim || oh >= lim || ow >= lim || c >= lim) return HF_ERR_ARG;
-  if (kh >= lim || kw >= lim || stride_h >= lim || stride_w >= lim || pad_h >= lim || pad_w >= lim) return HF_ERR_ARG;
-  // the pooled extent of a max-pool without dilation / ceil_mode
-  if (h + 2 * pad_h < kh || w + 2 * pad_w < kw) return HF_ERR_ARG;
-  if (oh != (h + 2 * pad_h - kh) / stride_h + 1 || ow != (w + 2 * pad_w - kw) / stride_w + 1) return HF_ERR_ARG;
-  if (h * w >= lim || oh * ow >= lim || n * (h * w) >= lim || n * (oh * ow) >= lim) return HF_ERR_ARG;
-  const int64_t rows = n * h * w, full = rows * c, pooled = n * oh * ow * c;
-  if (full >= lim || pooled >= lim) return HF_ERR_ARG;
-  if (gy_splits > 1 && gy_slab < pooled) return HF_ERR_ARG;  // (slabs would overlap)
-  int64_t per = 0;
-  if (gb) {
-    if (row_blocks < 1) return HF_ERR_ARG;
-    per = (rows + row_blocks - 1) / row_blocks;
-    if ((int64_t)(row_blocks - 1) * per >= rows) return HF_ERR_ARG;  // an empty share
-  }
-  const float* yp = relu ? (const float*)y_pool : nullptr;
-  const bool quad = c % 4 == 0 && al16(ga) && al16(gy) && al16(idx) && (!yp || al16(yp)) &&
-                    (gy_splits == 1 || gy_slab % 4 == 0);
-  const unsigned cq = (unsigned)(quad ? c / 4 : c);
-  PoolGeo q{(int)h, (int)w, (int)oh, (int)ow, (int)kh, (int)kw, (int)stride_h, (int)stride_w, (int)pad_h, (int)pad_w};
-  hipStream_t s = (hipStream_t)stream;
-  if (gb) {
-#define HF_PAA(W)                                                                                                  \
-  hipLaunchKernelGGL((k_pool_act_adjoint_rows<W>), dim3((unsigned)row_blocks), dim3(HB), 0, s, (float*)ga,        \
-                     (float*)gb, (const float*)gy, gy_splits, (long long)gy_slab, (const int*)idx, yp,            \
-                     (unsigned)rows, (unsigned)per, cq, q)
-    if (quad) HF_PAA(4);
-    else HF_PAA(1);
-#undef HF_PAA
-  } else {
-    const unsigned items = (unsigned)(rows * cq);
-#define HF_PAE(W)                                                                                                  \
-  hipLaunchKernelGGL((k_pool_act_adjoint<W>), dim3((items + HB - 1) / HB), dim3(HB), 0, s, (float*)ga,            \
-                     (const float*)gy, gy_splits, (long long)gy_slab, (const int*)idx, yp, items, cq, q)
-    if (quad) HF_PAE(4);
-    else HF_PAE(1);
-#undef HF_PAE
-  }
-  return (int)hipGetLastError();
+  return pool_act_adjoint(ga, nullptr, nullptr, gb, row_blocks, gy, gy_splits, gy_slab, idx, y_pool, relu, n, h, w, oh,
+                          ow, c, kh, kw, stride_h, stride_w, pad_h, pad_w, dtype, stream, nullptr);
+}
+
+int hf_pool_bn_act_adjoint_nhwc(void* ga, void* g, void* gw, void* gb, int row_blocks, const void* gy, int gy_splits,
+                                int64_t gy_slab, const void* a, const void* mean, const void* rstd, const void* w,
+                                const void* idx, const void* y_pool, int relu, int64_t n, int64_t h, int64_t w_,
+                                int64_t oh, int64_t ow, int64_t c, int64_t kh, int64_t kw, int64_t stride_h,
+                                int64_t stride_w, int64_t pad_h, int64_t pad_w, int dtype, void* stream) {
+  if (!a || !mean || !rstd || !w) return HF_ERR_ARG;
+  const PoolBn bn{(const float*)a, (const float*)mean, (const float*)rstd, (const float*)w, nullptr};
+  return pool_act_adjoint(ga, g, gw, gb, row_blocks, gy, gy_splits, gy_slab, idx, y_pool, relu, n, h, w_, oh, ow, c, kh,
+                          kw, stride_h, stride_w, pad_h, pad_w, dtype, stream, &bn);
 }
 
 int hf_linear_ce_head(void* g_feat, void* g_w, void* g_b, const void* t_feat, const void* feat, const void* w,

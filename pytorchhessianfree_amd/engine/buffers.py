@@ -283,8 +283,9 @@ class _Buffers:
             bn = u.bn is not None and u.pg is not None
             u.sums_slot = i
             problems.append(dict(gw=u.gw.data_ptr() if bn else None, gb=u.gb.data_ptr() if u.pb is not None else None,
-                                 g=(u.ga if u.pool is not None else u.g).data_ptr(), x=u.a.data_ptr() if bn else None,
-                                 mean=u.mean.data_ptr() if bn else None, rstd=u.rstd.data_ptr() if bn else None,
+                                 g=(u.ga if u.pool is not None and u.bn is None else u.g).data_ptr(),
+                                 x=u.a.data_ptr() if bn else None, mean=u.mean.data_ptr() if bn else None,
+                                 rstd=u.rstd.data_ptr() if bn else None,
                                  rows=u.rows, c=u.cout, row_blocks=u.rb))
         self._sums_tab, _blocks = sums_table(problems)
         host = torch.frombuffer(bytearray(bytes(self._sums_tab)), dtype=torch.uint8)

@@ -92,12 +92,12 @@ def records_of(m, n=2, with_input=False):
 
 
 def mark_dead_prefix(layers):
-    """Frozen layers at the input end of a stack (no ``pw``, no ``pb``): ``dead`` for both sweeps -- no tangent reaches
+    """Frozen layers at the input end of a stack (no ``pw``, no ``pb``, no ``pg``): ``dead`` for both sweeps -- no tangent reaches
     them, nobody needs a cotangent behind the first trainable layer.  Returns how many there are; the layer behind them
     reads a tangent-free input and needs no data gradient (the caller's flag)."""
     dead = 0
     for u in layers:
-        if u.pw is not None or u.pb is not None:
+        if u.pw is not None or u.pb is not None or getattr(u, "pg", None) is not None:
             break
         u.dead = True
         dead += 1

@@ -12,7 +12,7 @@ MAX_TAIL_ROWS, MAX_CLASSES = 256, 1024  # the dense kernels' row limit; the loss
 
 
 class PlainStackEngine(_ConvEngine):
-    """The same sweeps for a plain stack ``[Dropout] conv(+bias) [ReLU] ... -> AdaptiveAvgPool2d(1) ->
+    """The same sweeps for a plain stack ``[Dropout] conv(+bias | +eval BatchNorm) [ReLU] ... -> AdaptiveAvgPool2d(1) ->
     flatten`` with a softmax cross-entropy on the pooled map -- the All-CNN-C of the reference's
     examples (examples/example_utils.py:59-83, BASELINE.json configs[3]).  Per layer: tangent
     convolution -> bias tangent + ReLU mask (into the next layer's operand) / masked slab sum + bias
@@ -26,6 +26,12 @@ class PlainStackEngine(_ConvEngine):
     full-resolution tangent map), ``hf_pool_act_adjoint_nhwc`` gathers the consumer's data-gradient slabs into the
     full-resolution ``ga`` with the bias sums.  The forward pass adds ``hf_maxpool_forward_nhwc`` (pooled map, its copy
     in the consumer's ``x`` half, positions).  Everything that reads ``u.ga`` / ``u.gb`` / ``u.x`` is unchanged.
+
+    Eval-mode ``BatchNorm2d`` units (VGG-BN style nets): ``Conv2d(bias=False) BatchNorm2d [ReLU] [MaxPool2d]`` is one unit,
+    anywhere a bias unit may stand.  Unpooled, it runs on the shared BatchNorm launches of the mixins; pooled, BatchNorm /
+    ReLU / pool is ONE launch per direction as for a bias -- ``hf_pool_bn_act_tangent_nhwc`` adds the scale (w*rstd) and the
+    ``xhat * v_w`` term at the windows' positions, ``hf_pool_bn_act_adjoint_nhwc`` writes the unscaled masked cotangent
+    ``u.g`` (what the sums table, Hessian products and ``diag_ef`` read), ``u.ga = g * w*rstd`` and the scale's / shift's sums.
 
     A classifier tail instead of the global average pool (LeNet, VGG-style nets, DeepOBS 2c2d / 3c3d): units as above
     (the last one may be pooled), ``nn.Flatten``, then ``Linear [ReLU] ... Linear``.  The tail is the kind's HEAD, with
@@ -72,19 +78,33 @@ class PlainStackEngine(_ConvEngine):
                 cx, cy = records_of(m, with_input=True)
                 if not _same(cx, cur):
                     raise _Unsupported(f"conv {len(units)}: input is not the previous activation")
-                u = _Unit(f"conv{len(units)}", m, None)
-                y, u.relu = cy, False
                 nxt = leaves[i + 1] if i + 1 < len(leaves) else None
-                if type(nxt) is nn.ReLU and not nxt.inplace:
+                bn = nxt if type(nxt) is nn.BatchNorm2d else None
+                u = _Unit(f"conv{len(units)}", m, bn)
+                y, u.relu = cy, False
+                if bn is not None:
+                    y, u.relu = self._layout_bn(u, bn, cy)
+                    i += 1
+                    if u.relu:  # (modelprep fused the following ReLU module into the layer: its output is the unit's)
+                        nxt = leaves[i + 1] if i + 1 < len(leaves) else None
+                        if type(nxt) is not nn.ReLU or nxt.inplace or not _same(records_of(nxt, with_input=True)[1], y):
+                            raise _Unsupported(f"{u.name}: the ReLU fused into its BatchNorm2d is not the next layer")
+                        i += 1
+                elif type(nxt) is nn.ReLU and not nxt.inplace:
                     rx, ry = records_of(nxt, with_input=True)
                     if _same(rx, cy):
                         y, u.relu = ry, True
                         i += 1
                 u.kx, u.ky, u.rx, u.ry, u.ra = cx.data_ptr(), y.data_ptr(), cx, y, cy
-                u.a, u.y, u.needs_g = _cl(cy), _cl(y), False
+                # (a BatchNorm unit keeps its masked cotangent, as the residual kind's units do: the sums table and
+                # ``diag_ef`` take the scale's sums from it)
+                u.a, u.y, u.needs_g = _cl(cy), _cl(y), bn is not None
                 u.pw = self._param(m.weight)
-                u.pb = self._param(m.bias) if m.bias is not None else None
-                u.pg = None
+                if bn is None:
+                    u.pb = self._param(m.bias) if m.bias is not None else None
+                    u.pg = None
+                else:
+                    u.pg, u.pb = self._param(bn.weight), self._param(bn.bias)
                 u.src, prev, cur = prev, u, y
                 units.append(u)
             elif type(m) is nn.MaxPool2d:
@@ -115,6 +135,10 @@ class PlainStackEngine(_ConvEngine):
                 if not _same(fx, cur) or fy.dim() != 2 or fy.shape[1] != cur.shape[1] * cur.shape[2] * cur.shape[3]:
                     raise _Unsupported("Flatten does not turn the last unit's output into [batch, c*h*w]")
                 dense, cur, self._rec_flat = [], fy, fy
+            elif type(m) is nn.BatchNorm2d:
+                where = (f"behind {units[-1].name}" + ("'s MaxPool2d" if units[-1].pool is not None else "'s activation")
+                         if units else "in front of the first convolution")
+                raise _Unsupported(f"BatchNorm2d {where}: a BatchNorm must directly follow a convolution")
             elif type(m) is nn.ReLU and units and units[-1].pool is not None:
                 raise _Unsupported(f"ReLU behind the MaxPool2d of {units[-1].name}: the activation must stand in front of "
                                    "the pool")
@@ -134,7 +158,7 @@ class PlainStackEngine(_ConvEngine):
         first.im2col = first.a.shape[1] > 0 and first.rx.shape[1] < 4
         self.units, self.tail = units, units[-1]
         self.model_ref, self._in_shape = model, tuple(x_in.shape)
-        used = {i for u in units + self.classifier for i in (u.pw, u.pb) if i is not None}
+        used = {i for u in units + self.classifier for i in (u.pw, getattr(u, "pg", None), u.pb) if i is not None}
         if used != set(range(len(self.params))):
             raise _Unsupported("the parameter list has entries the engine's layers do not cover")
         # frozen layers at the input end (round 6, as FusedGGNEngine._mark_dead_prefix): dead for both sweeps; the first
@@ -142,6 +166,20 @@ class PlainStackEngine(_ConvEngine):
         self.dead_units = mark_dead_prefix(units)
         if self.dead_units:
             units[self.dead_units].no_dgrad = True
+
+    def _layout_bn(self, u, bn, cy):
+        """The eval-mode BatchNorm behind ``u``'s convolution (output record ``cy``): what the unit's output record and
+        ReLU flag are -- ``modelprep`` fuses a following ``nn.ReLU`` into the layer and leaves one 5-entry record."""
+        if u.conv.bias is not None:
+            raise _Unsupported(f"{u.name}: a convolution bias in front of a BatchNorm2d is not covered (bias=False)")
+        rec = getattr(bn, "_hf_io", None)
+        if rec is None or len(rec) != 5:
+            raise _Unsupported(f"{u.name}: its BatchNorm2d has no fused eval record of this forward pass (it must be "
+                               "affine, with running statistics)")
+        bx, bres, by, brelu, _rstd = rec
+        if bres is not None or not _same(bx, cy):
+            raise _Unsupported(f"{u.name}: the BatchNorm2d does not consume the convolution's output")
+        return by, bool(brelu)
 
     # ---- classifier tail: layout -----------------------------------------------------------------
     def _layout_tail_layer(self, leaves, i, dense, cur):
@@ -186,7 +224,7 @@ class PlainStackEngine(_ConvEngine):
             raise _Unsupported("Hessian products through a classifier tail are not covered")
         if self.group is not None:
             raise _Unsupported("data parallelism is not covered for a classifier tail")
-        if all(u.pw is None and u.pb is None for u in units):
+        if all(u.pw is None and u.pg is None and u.pb is None for u in units):
             raise _Unsupported("every convolution in front of the classifier tail is frozen: not covered")
 
     def _head_operands(self):
@@ -285,19 +323,32 @@ class PlainStackEngine(_ConvEngine):
         return n, h, w, u.yp.shape[2], u.yp.shape[3], c
 
     def _pool_tangent(self, u, v):
-        """t_pool = (y_pool > 0) * (t_a[idx] + v_b) from the tangent convolution's slabs into the consumer's operand."""
+        """t_pool = (y_pool > 0) * (t_a[idx] + v_b) from the tangent convolution's slabs into the consumer's operand; with
+        a BatchNorm  (y_pool > 0) * (t_a[idx] * w*rstd + xhat[idx] * v_w + v_b)."""
+        tail = (u.pidx, u.yp, 1 if u.relu else 0, *self._pool_dims(u))
+        if u.bn is not None:
+            vg, vb = self._scale_shift_tangent(u, v)
+            self._launch("hf_pool_bn_act_tangent_nhwc", u.tout, u.tout_ld, u.tbuf, u.sT, u.tbuf.shape[1], u.a, u.mean,
+                         u.rstd, u.scale, vg, vb, *tail)
+            return
         vb = self._param_slice(v, u.pb, u.cout)
-        self._launch("hf_pool_act_tangent_nhwc", u.tout, u.tout_ld, u.tbuf, u.sT, u.tbuf.shape[1], vb, u.pidx, u.yp,
-                     1 if u.relu else 0, *self._pool_dims(u))
+        self._launch("hf_pool_act_tangent_nhwc", u.tout, u.tout_ld, u.tbuf, u.sT, u.tbuf.shape[1], vb, *tail)
 
     def _pool_adjoint(self, u, srcs):
         """g_a at full resolution from the consumer's data-gradient slabs; the bias sums as partial rows -- or, where
-        the unit's sums are deferred, left to the sums table (which reads ``u.ga``)."""
+        the unit's sums are deferred, left to the sums table (which reads ``u.ga``).  With a BatchNorm: the unscaled
+        masked cotangent -> ``u.g`` (where the unit keeps one: the sums table, Hessian products and ``diag_ef`` read it),
+        ``u.ga`` = it times w*rstd, and the scale's and shift's sums."""
         self._extras_wait(srcs)
         (gy, splits, slab), = srcs
         gb = None if (u.defer or u.pb is None) else u.gb
-        self._launch("hf_pool_act_adjoint_nhwc", u.ga, gb, u.rb, gy, splits, slab, u.pidx, u.yp, 1 if u.relu else 0,
-                     *self._pool_dims(u), *u.pool)
+        tail = (u.pidx, u.yp, 1 if u.relu else 0, *self._pool_dims(u), *u.pool)
+        if u.bn is not None:
+            gw = None if (u.defer or u.pg is None) else u.gw
+            self._launch("hf_pool_bn_act_adjoint_nhwc", u.ga, u.g, gw, gb, u.rb, gy, splits, slab, u.a, u.mean, u.rstd,
+                         u.scale, *tail)
+        else:
+            self._launch("hf_pool_act_adjoint_nhwc", u.ga, gb, u.rb, gy, splits, slab, *tail)
         if u.defer:
             self._sums_pending.add(u.sums_slot)
 

@@ -211,6 +211,82 @@ class ConvFCFlat(nn.Module):
         return _batched(self.net, x)
 
 
+def seed_batchnorm(model, seed=0):
+    """Non-trivial eval-mode state for every BatchNorm of ``model``: running mean ~ N(0, 0.25), running variance
+    U[0.5, 2], weight U[0.5, 1.5], bias ~ N(0, 0.25), from a generator of its own.  The constructors' 0 / 1 / 1 / 0 would
+    hide every error in how a kernel uses ``mean``, ``rstd`` and the scale.  Returns the model."""
+    g = torch.Generator().manual_seed(1000 + seed)
+    with torch.no_grad():
+        for m in model.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                k = m.num_features
+                for t, val in ((m.running_mean, 0.5 * torch.randn(k, generator=g)),
+                               (m.running_var, 0.5 + 1.5 * torch.rand(k, generator=g)),
+                               (m.weight, 0.5 + torch.rand(k, generator=g)), (m.bias, 0.5 * torch.randn(k, generator=g))):
+                    if t is not None:  # (no running statistics / not affine)
+                        t.copy_(val)
+    return model
+
+
+class ConvBNSmall(nn.Module):
+    """The smallest plain stack with BatchNorm units of every kind: conv3(3->8, pad 1, no bias) + BN + ReLU +
+    MaxPool(3, 2) (the im2col'd first layer, pooled, overlapping windows, 12x12 -> 5x5), conv3(8->8) + BN + ReLU (unpooled),
+    conv3(8->12) + BN + MaxPool(2, 2) (pooled without a ReLU, 5x5 -> 2x2), conv1(12->classes) with a bias, global average
+    pool."""
+
+    def __init__(self, num_classes=4):
+        super().__init__()
+        self.net = nn.Sequential(
+            nn.Conv2d(3, 8, 3, 1, 1, bias=False), nn.BatchNorm2d(8), nn.ReLU(), nn.MaxPool2d(3, 2),
+            nn.Conv2d(8, 8, 3, 1, 1, bias=False), nn.BatchNorm2d(8), nn.ReLU(),
+            nn.Conv2d(8, 12, 3, 1, 1, bias=False), nn.BatchNorm2d(12), nn.MaxPool2d(2, 2),
+            nn.Conv2d(12, num_classes, 1),
+            nn.AdaptiveAvgPool2d((1, 1)),
+        )
+
+    def forward(self, x):  # (BatchNorm2d takes no unbatched sample)
+        return torch.flatten(_batched(self.net, x), -3)
+
+
+class ConvBNFCSmall(nn.Module):
+    """``ConvBNSmall``'s first unit, conv3(8->8) + BN + ReLU + MaxPool(2, 2) (5x5 -> 2x2: the last unit is pooled),
+    ``Flatten`` to 32 features, ``Linear(32->20) ReLU Linear(20->10)``."""
+
+    def __init__(self, num_classes=10):
+        super().__init__()
+        self.net = nn.Sequential(
+            nn.Conv2d(3, 8, 3, 1, 1, bias=False), nn.BatchNorm2d(8), nn.ReLU(), nn.MaxPool2d(3, 2),
+            nn.Conv2d(8, 8, 3, 1, 1, bias=False), nn.BatchNorm2d(8), nn.ReLU(), nn.MaxPool2d(2, 2),
+            nn.Flatten(),
+            nn.Linear(32, 20), nn.ReLU(), nn.Linear(20, num_classes),
+        )
+
+    def forward(self, x):
+        return _batched(self.net, x)
+
+
+class VGG11BN(nn.Module):
+    """VGG-11 with BatchNorm for 32x32 inputs (the usual CIFAR form): conv3 + BN + ReLU units of 64, 128, 256, 256, 512,
+    512, 512, 512 channels, a MaxPool(2, 2) behind units 1, 2, 4, 6 and 8 (32 -> 1), ``Flatten``, ``Linear(512->classes)``.
+    The convolutions carry no bias (the BatchNorm's shift takes its place)."""
+
+    CFG = (64, "M", 128, "M", 256, 256, "M", 512, 512, "M", 512, 512, "M")
+
+    def __init__(self, num_classes=10):
+        super().__init__()
+        layers, c = [], 3
+        for k in self.CFG:
+            if k == "M":
+                layers.append(nn.MaxPool2d(2, 2))
+            else:
+                layers += [nn.Conv2d(c, k, 3, 1, 1, bias=False), nn.BatchNorm2d(k), nn.ReLU()]
+                c = k
+        self.net = nn.Sequential(*layers, nn.Flatten(), nn.Linear(512, num_classes))
+
+    def forward(self, x):
+        return _batched(self.net, x)
+
+
 class C3D3(nn.Module):
     """A DeepOBS ``3c3d``-sized net from stock modules: three conv + ReLU + MaxPool(3, 2, 1) units (32x32 -> 14 -> 6 -> 3),
     ``Flatten`` to 1152 features, ``Linear(1152->512) ReLU Linear(512->256) ReLU Linear(256->classes)``."""
@@ -373,6 +449,36 @@ def convfc_flat(batch_size=3, seed=0, device="cpu", data_seed=None):
     model = ConvFCFlat(10).eval()
     g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
     inputs = torch.rand(batch_size, 3, 6, 5, generator=g)
+    targets = torch.randint(0, 10, (batch_size,), generator=g)
+    return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
+
+
+def convbn_small(batch_size=2, seed=0, device="cpu", data_seed=None):
+    """``ConvBNSmall`` in eval mode with seeded BatchNorm state; inputs U[0,1) [B,3,12,12], 4 classes, CE-mean."""
+    torch.manual_seed(seed)
+    model = seed_batchnorm(ConvBNSmall(4), seed).eval()
+    g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
+    inputs = torch.rand(batch_size, 3, 12, 12, generator=g)
+    targets = torch.randint(0, 4, (batch_size,), generator=g)
+    return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
+
+
+def convbn_fc_small(batch_size=2, seed=0, device="cpu", data_seed=None):
+    """``ConvBNFCSmall`` in eval mode with seeded BatchNorm state; inputs U[0,1) [B,3,12,12], 10 classes, CE-mean."""
+    torch.manual_seed(seed)
+    model = seed_batchnorm(ConvBNFCSmall(10), seed).eval()
+    g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
+    inputs = torch.rand(batch_size, 3, 12, 12, generator=g)
+    targets = torch.randint(0, 10, (batch_size,), generator=g)
+    return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
+
+
+def vgg11bn_cifar10(batch_size=32, seed=0, device="cpu", data_seed=None):
+    """``VGG11BN`` in eval mode with seeded BatchNorm state; inputs U[0,1) [B,3,32,32], 10 classes, CE-mean."""
+    torch.manual_seed(seed)
+    model = seed_batchnorm(VGG11BN(10), seed).eval()
+    g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
+    inputs = torch.rand(batch_size, 3, 32, 32, generator=g)
     targets = torch.randint(0, 10, (batch_size,), generator=g)
     return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
 
