@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 25
+#define HF_ABI_VERSION 26
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -838,6 +838,43 @@ int hf_pool_bn_act_adjoint_nhwc(void* ga, void* g, void* gw, void* gb, int row_b
                                 const void* idx, const void* y_pool, int relu, int64_t n, int64_t h, int64_t w_,
                                 int64_t oh, int64_t ow, int64_t c, int64_t kh, int64_t kw, int64_t stride_h,
                                 int64_t stride_w, int64_t pad_h, int64_t pad_w, int dtype, void* stream);
+/*
+ * The pooled unit with a TRAIN-mode BatchNorm (batch statistics; ABI 26): mean / rstd are the batch's, the tangent and the
+ * cotangent carry the statistics' own derivative, which needs per-channel sums over ALL n*h*w rows.
+ *
+ * hf_pool_bn_act_tangent_train_nhwc: hf_pool_bn_act_tangent_nhwc's operands plus the partial rows of
+ *   S_x = sum_rows xhat*T,  S_1 = sum_rows T   (T: the full-resolution tangent, the sum of the slabs)
+ * as part_x / part_1 [nparts, c] (by the tangent convolution's epilogue, hf_conv2d_nhwc_group_slabs_bnsum, or one
+ * hf_chan_affine_bwd_ex reduction over the slabs) and count = n*h*w.  Prologue, in every workgroup: the nparts rows of
+ * each set added up in hf_chan_affine_train's fixed order (fp64; thread ty of a channel quad takes rows ty, ty + G, ...,
+ * G = 256 / (c/4), the G sums added in ty order), then with k = (w*rstd) * (float)(1/count)
+ *   q = v_w - k*(float)S_x,   r = v_b - k*(float)S_1      (a null v_w / v_b counts as 0; any 4-byte boundary)
+ * -- that kernel's six roundings: w*rstd, times 1/count, the two sums to fp32, k times each, the two differences.  Then
+ * with p = idx[n,oy,ox,c]
+ *   out[n,oy,ox,c] = m * (T[p]*(w*rstd) + ((a[n,p,c] - mean)*rstd)*q + r)
+ * in hf_chan_affine_ex's per-element sequence (slabs in split order, w*rstd first, one rounding per operation, the mask
+ * a select).  Bitwise hf_chan_affine_train's unmasked dense output on the same operands, gathered at idx and masked by
+ * the pooled map -- in the 16-byte form (out, idx, y_pool 16-byte aligned, out_ld % 4 == 0) and the element-wise one.
+ * The full-resolution tangent map is never formed.  Refusals before any launch: hf_pool_bn_act_tangent_nhwc's, a null
+ * part_x / part_1, nparts < 1, count <= 0, c % 4 != 0, c > 1024 (HF_ERR_ARG); part_x / part_1 off the 16-byte grid
+ * (HF_ERR_ALIGN).  Two launches on the same operands give the same bits; nothing outside the extents is read or written.
+ *
+ * hf_pool_bn_act_adjoint_reduce_nhwc: pass 1 of the train-mode adjoint -- hf_pool_bn_act_adjoint_nhwc without ga:
+ *   g = the masked, unscaled cotangent at full resolution;  gb[b] = sum over row share b of g,  gw[b] = ... of g*xhat
+ * all three REQUIRED (HF_ERR_ARG otherwise), bitwise what that entry point writes to its g / gw / gb from the same
+ * operands (same template, the ga store compiled out); its other refusals, forms and repeatability.  Pass 2 is
+ * hf_chan_affine_train on g and the partial rows: a grid-wide sum stands between the passes.
+ */
+int hf_pool_bn_act_tangent_train_nhwc(void* out, int64_t out_ld, const void* slabs, int splits, int64_t slab_stride,
+                                      const void* a, const void* mean, const void* rstd, const void* w, const void* v_w,
+                                      const void* v_b, const void* part_x, const void* part_1, int nparts, double count,
+                                      const void* idx, const void* y_pool, int relu, int64_t n, int64_t h, int64_t w_,
+                                      int64_t oh, int64_t ow, int64_t c, int dtype, void* stream);
+int hf_pool_bn_act_adjoint_reduce_nhwc(void* g, void* gw, void* gb, int row_blocks, const void* gy, int gy_splits,
+                                       int64_t gy_slab, const void* a, const void* mean, const void* rstd, const void* w,
+                                       const void* idx, const void* y_pool, int relu, int64_t n, int64_t h, int64_t w_,
+                                       int64_t oh, int64_t ow, int64_t c, int64_t kh, int64_t kw, int64_t stride_h,
+                                       int64_t stride_w, int64_t pad_h, int64_t pad_w, int dtype, void* stream);
 /*
  * hf_linear_ce_head: the classifier head of J^T H_L J v in one launch (one workgroup per 4 rows):
  *   Jv = t_feat W^T + feat V_W^T + v_b;  HJv = scale * p * (Jv - <p, Jv>) (as hf_softmax_ce_hvp);

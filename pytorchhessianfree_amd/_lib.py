@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HF_PCG_LIB") or os.path.join(_HERE, "csrc", "libhfpcg.so")
 
 HF_F32, HF_F64 = 0, 1
-ABI_VERSION = 25
+ABI_VERSION = 26
 HF_ERR_ARG = -1  # hf_status of include/hf_pcg.h: null / negative / inconsistent argument
 HF_M_NONE, HF_M_DIAG, HF_M_EXTERNAL = 0, 1, 2
 REASONS = {
@@ -193,6 +193,11 @@ SIGNATURES = {
                                     + [c_int64] * 6 + [c_int, c_void_p]),
     "hf_pool_bn_act_adjoint_nhwc": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, c_int64] + [c_void_p] * 6 + [c_int]
                                     + [c_int64] * 12 + [c_int, c_void_p]),
+    "hf_pool_bn_act_tangent_train_nhwc": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64] + [c_void_p] * 8
+                                          + [c_int, c_double, c_void_p, c_void_p, c_int] + [c_int64] * 6
+                                          + [c_int, c_void_p]),
+    "hf_pool_bn_act_adjoint_reduce_nhwc": (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_int, c_int64] + [c_void_p] * 6
+                                           + [c_int] + [c_int64] * 12 + [c_int, c_void_p]),
     "hf_linear_ce_head": (c_int, [c_void_p] * 9 + [c_double, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "hf_linear_ce_head_slabs": (c_int, [c_int64]),
     "hf_pool_ce_head": (c_int, [c_void_p] * 4 + [c_double, c_int64, c_int64, c_int64, c_int, c_void_p]),

@@ -705,6 +705,82 @@ __global__ __launch_bounds__(BLOCK) void k_chan_affine_v4_train_pair(const AffTr
   else affine_train_body<SB, false, MB>(B, blockIdx.x - blocks_a, gridDim.x - blocks_a, scratch, fin, qs, rsh);
 }
 
+// ---- a plain stack's POOLED train-mode BatchNorm unit: the tangent at the windows' positions ----------------------------
+// k_chan_affine_v4_train's prologue (the same partial rows added in the same order: the same q / r in every workgroup),
+// then hf_head.hip's pooled BatchNorm tangent with q / r in place of v_w / v_b: with p = idx[n,oy,ox,c]
+//   out[n,oy,ox,c] = m * (T[p]*(w*rstd) + xhat[p]*q + r),   T[p]: the tangent convolution's slabs at p, in split order
+// -- bitwise the train kernel's unmasked dense output gathered at idx; the full-resolution tangent is never formed (its
+// sums S_x / S_1 came from the convolution's epilogue or one reduction launch over the slabs).  A thread owns W consecutive
+// channels of a pooled pixel (W = 4: 16-byte loads of idx / y_pool, 16-byte stores; W = 1: any alignment of those).
+struct PoolTrainArgs {
+  float* out;
+  const float *slabs, *a, *mean, *rstd, *w, *part_x, *part_1, *vq, *vr, *ypool;
+  const int* idx;
+  unsigned nparts;
+  float inv_m;
+  unsigned items, CQ, out_ld, opix, ipix;
+  int splits;
+  long long slab_stride;
+};
+
+template <int W>
+__global__ __launch_bounds__(BLOCK) void k_pool_bn_act_tangent_train(const PoolTrainArgs p) {
+  __shared__ double scratch[8 * BLOCK];
+  __shared__ double fin[2 * 4 * BLOCK];
+  __shared__ float qs[4 * BLOCK], rsh[4 * BLOCK];
+  using VF = ColOf<float, W>;
+  using VI = ColOf<int, W>;
+  const unsigned v = blockIdx.x * BLOCK + threadIdx.x;
+  const bool have = v < p.items;
+  const unsigned i = have ? v : 0u;  // (threads past the end read item 0 and store nothing: they serve the prologue)
+  const unsigned C = p.CQ * W, cq = i % p.CQ, pix = i / p.CQ, n = pix / p.opix, c0 = cq * W;
+  const unsigned e = pix * C + c0;
+  const float* __restrict__ ypool = p.ypool;
+  VI ix;
+  VF m;
+  final_column_sums2(p.part_x, p.part_1, p.nparts, C, scratch, fin, fin + 4 * BLOCK, [&]() {
+    // the element's own first round trip (positions, mask) rides with the partial rows'
+    ix = *reinterpret_cast<const VI*>(p.idx + e);
+    if (ypool) m = *reinterpret_cast<const VF*>(ypool + e);
+  });
+  for (unsigned ch = threadIdx.x; ch < C; ch += BLOCK) {  // (k_chan_affine_v4_train's finalisation, to the letter)
+    const float k = p.w[ch] * p.rstd[ch] * p.inv_m;
+    qs[ch] = (p.vq ? p.vq[ch] : 0.f) - k * (float)fin[ch];
+    rsh[ch] = (p.vr ? p.vr[ch] : 0.f) - k * (float)fin[4 * BLOCK + ch];
+  }
+  __syncthreads();
+  if (!have) return;
+  const float* __restrict__ slabs = p.slabs;
+  VF s, av;
+  unsigned off[W];
+#pragma unroll
+  for (int k = 0; k < W; ++k) {
+    // (a position outside the plane would be a read outside the slabs: clamped, never followed)
+    const unsigned pos = (unsigned)ix.e[k] < p.ipix ? (unsigned)ix.e[k] : p.ipix - 1;
+    off[k] = (n * p.ipix + pos) * C + c0 + k;
+    s.e[k] = slabs[off[k]];
+    av.e[k] = p.a[off[k]];
+  }
+  // (the W channels' slabs: one batch of all of them in flight, each channel added in split order)
+  for (int sp = 1; sp < p.splits; sp += 8) {
+    float t[W][8];
+#pragma unroll
+    for (int k = 0; k < W; ++k) slab_issue(t[k], slabs, off[k], sp, p.splits, p.slab_stride);
+#pragma unroll
+    for (int k = 0; k < W; ++k) slab_add<false>(s.e[k], t[k], sp, p.splits);
+  }
+#pragma unroll
+  for (int k = 0; k < W; ++k) {
+    const float rs = p.rstd[c0 + k];
+    float acc = s.e[k] * (p.w[c0 + k] * rs);
+    acc += ((av.e[k] - p.mean[c0 + k]) * rs) * qs[c0 + k];
+    acc += rsh[c0 + k];
+    if (ypool) acc = m.e[k] > 0.f ? acc : 0.f;
+    s.e[k] = acc;
+  }
+  chain_store_col<HF_WT_ELEM>(p.out + (size_t)pix * p.out_ld + c0, s);
+}
+
 // One-pass batch statistics of a train-mode BatchNorm's forward: sums the convolution's split-K slabs into
 // a_out (row-major walk as k_bn_adjoint_rows), per-channel sum a and sum a^2 in fp64 per thread / block.
 // part: [gridDim.x, 2, C] doubles; the normalising launch (k_bn_forward_train) adds the rows up in its prologue:
@@ -1739,6 +1815,42 @@ int hf_bn_train_hessian_apply(void* out, const void* ga1, const void* gz1, const
                      (float*)out, (const float*)ga1, (const float*)gz1, (const float*)gz2, (const float*)t, t_splits,
                      (long long)t_slab, (const float*)a, (const float*)mean, (const float*)rstd, (const float*)coef,
                      (unsigned)total4, (unsigned)c);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+int hf_pool_bn_act_tangent_train_nhwc(void* out, int64_t out_ld, const void* slabs, int splits, int64_t slab_stride,
+                                      const void* a, const void* mean, const void* rstd, const void* w, const void* v_w,
+                                      const void* v_b, const void* part_x, const void* part_1, int nparts, double count,
+                                      const void* idx, const void* y_pool, int relu, int64_t n, int64_t h, int64_t w_,
+                                      int64_t oh, int64_t ow, int64_t c, int dtype, void* stream) {
+  // hf_pool_bn_act_tangent_nhwc's refusals ...
+  if (dtype != HF_F32 || !out || !slabs || !idx || (relu && !y_pool) || !a || !mean || !rstd || !w) return HF_ERR_ARG;
+  if (n < 1 || h < 1 || w_ < 1 || oh < 1 || ow < 1 || c < 1) return HF_ERR_ARG;
+  if (splits < 1 || splits > HF_POOL_ACT_MAX_SPLITS) return HF_ERR_ARG;
+  // ... and the prologue's
+  if (!part_x || !part_1 || nparts < 1 || !(count > 0.0) || c % 4 || c / 4 > BLOCK) return HF_ERR_ARG;
+  if (out_ld == 0) out_ld = c;
+  if (out_ld < c) return HF_ERR_ARG;
+  // (every factor below 2^31 first: the products cannot wrap)
+  const int64_t lim = 1LL << 31;
+  if (n >= lim || h >= lim || w_ >= lim || oh >= lim || ow >= lim || out_ld >= lim) return HF_ERR_ARG;
+  if (h * w_ >= lim || oh * ow >= lim || n * (h * w_) >= lim || n * (oh * ow) >= lim) return HF_ERR_ARG;
+  const int64_t full = n * h * w_ * c, total = n * oh * ow * c;
+  if (full >= lim || total >= lim || n * oh * ow * out_ld >= lim) return HF_ERR_ARG;
+  if (splits > 1 && slab_stride < full) return HF_ERR_ARG;  // (slabs would overlap)
+  if (!aligned16(part_x) || !aligned16(part_1)) return HF_ERR_ALIGN;  // (the prologue reads the rows by quads)
+  const float* yp = relu ? (const float*)y_pool : nullptr;
+  const bool quad = out_ld % 4 == 0 && aligned16(out) && aligned16(idx) && (!yp || aligned16(yp));
+  const unsigned items = (unsigned)(total / (quad ? 4 : 1));
+  const PoolTrainArgs q{(float*)out, (const float*)slabs, (const float*)a, (const float*)mean, (const float*)rstd,
+                        (const float*)w, (const float*)part_x, (const float*)part_1, (const float*)v_w, (const float*)v_b,
+                        yp, (const int*)idx, (unsigned)nparts, (float)(1.0 / count), items,
+                        (unsigned)(quad ? c / 4 : c), (unsigned)out_ld, (unsigned)(oh * ow), (unsigned)(h * w_), splits,
+                        (long long)slab_stride};
+  const dim3 grid((items + BLOCK - 1) / BLOCK);
+  if (quad) hipLaunchKernelGGL(k_pool_bn_act_tangent_train<4>, grid, dim3(BLOCK), 0, (hipStream_t)stream, q);
+  else hipLaunchKernelGGL(k_pool_bn_act_tangent_train<1>, grid, dim3(BLOCK), 0, (hipStream_t)stream, q);
   HF_HIP(hipGetLastError());
   return HF_OK;
 }

@@ -256,7 +256,9 @@ __global__ __launch_bounds__(HB) void k_pool_act_adjoint(float* __restrict__ ga,
 // BatchNorm adjoint (hf_bn.hip) does; thread (tx, ty) walks channel column tx of every G-th row of the share and keeps
 // its sum in fp64; the G sums of a column are added in ty order and rounded once -> gb[b*C + channel]
 // (BN: a second sum per channel, of g * xhat with xhat rounded to fp32 first -> gw[b*C + channel]; either is nullable)
-template <int W, bool BN>
+// (GA = false, BN only: the reduction pass of a TRAIN-mode unit -- g and the sums; no ga = g*(w*rstd), which batch
+// statistics would throw away: the store is compiled out, `ga` is not touched)
+template <int W, bool BN, bool GA = true>
 __global__ __launch_bounds__(HB) void k_pool_act_adjoint_rows(float* __restrict__ ga, float* __restrict__ g,
                                                               float* __restrict__ gw, float* __restrict__ gb,
                                                               const float* __restrict__ gy, int splits,
@@ -294,7 +296,7 @@ __global__ __launch_bounds__(HB) void k_pool_act_adjoint_rows(float* __restrict_
         const ColOf<float, W> v = pool_act_adjoint_at<W>(gy, splits, slab, idx, ypool, C, cq * W, n, y, x, q);
         if constexpr (BN) {
           if (g) chain_store_col<HF_WT_ELEM>(g + (size_t)r * C + cq * W, v);
-          chain_store_col<HF_WT_ELEM>(ga + (size_t)r * C + cq * W, pool_bn_scale<W>(v, bn, cq * W));
+          if constexpr (GA) chain_store_col<HF_WT_ELEM>(ga + (size_t)r * C + cq * W, pool_bn_scale<W>(v, bn, cq * W));
           if (gw) {
 #pragma unroll
             for (int k = 0; k < W; ++k) acc[W + k] += (double)v.e[k] * (double)(float)((av.e[k] - mu[k]) * rs[k]);
@@ -625,8 +627,10 @@ int pool_act_tangent(void* out, int64_t out_ld, const void* slabs, int splits, i
 int pool_act_adjoint(void* ga, void* g, void* gw, void* gb, int row_blocks, const void* gy, int gy_splits, int64_t gy_slab,
                      const void* idx, const void* y_pool, int relu, int64_t n, int64_t h, int64_t w, int64_t oh,
                      int64_t ow, int64_t c, int64_t kh, int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h,
-                     int64_t pad_w, int dtype, void* stream, const PoolBn* bn) {
-  if (dtype != HF_F32 || !ga || !gy || !idx || (relu && !y_pool)) return HF_ERR_ARG;
+                     int64_t pad_w, int dtype, void* stream, const PoolBn* bn, bool reduce = false) {
+  // (reduce: a train-mode unit's reduction pass -- no ga; g and both sum rows are what it is for)
+  if (reduce ? (ga || !g || !gw || !gb || !bn) : !ga) return HF_ERR_ARG;
+  if (dtype != HF_F32 || !gy || !idx || (relu && !y_pool)) return HF_ERR_ARG;
   if (n < 1 || h < 1 || w < 1 || oh < 1 || ow < 1 || c < 1) return HF_ERR_ARG;
   if (kh < 1 || kw < 1 || stride_h < 1 || stride_w < 1 || pad_h < 0 || pad_w < 0) return HF_ERR_ARG;
   if (gy_splits < 1 || gy_splits > HF_POOL_ACT_MAX_SPLITS) return HF_ERR_ARG;
@@ -654,13 +658,14 @@ int pool_act_adjoint(void* ga, void* g, void* gw, void* gb, int row_blocks, cons
   hipStream_t s = (hipStream_t)stream;
   const PoolBn ops = bn ? *bn : PoolBn{};
   if (gb || gw) {
-#define HF_PAA(W, BN)                                                                                              \
-  hipLaunchKernelGGL((k_pool_act_adjoint_rows<W, BN>), dim3((unsigned)row_blocks), dim3(HB), 0, s, (float*)ga,    \
+#define HF_PAA(W, BN, GA)                                                                                          \
+  hipLaunchKernelGGL((k_pool_act_adjoint_rows<W, BN, GA>), dim3((unsigned)row_blocks), dim3(HB), 0, s, (float*)ga, \
                      (float*)g, (float*)gw, (float*)gb, (const float*)gy, gy_splits, (long long)gy_slab,          \
                      (const int*)idx, yp, (unsigned)rows, (unsigned)per, cq, q, ops)
-    if (bn) { if (quad) HF_PAA(4, true); else HF_PAA(1, true); }
-    else if (quad) HF_PAA(4, false);
-    else HF_PAA(1, false);
+    if (reduce) { if (quad) HF_PAA(4, true, false); else HF_PAA(1, true, false); }
+    else if (bn) { if (quad) HF_PAA(4, true, true); else HF_PAA(1, true, true); }
+    else if (quad) HF_PAA(4, false, true);
+    else HF_PAA(1, false, true);
 #undef HF_PAA
   } else {
     const unsigned items = (unsigned)(rows * cq);
@@ -763,6 +768,17 @@ int hf_pool_bn_act_adjoint_nhwc(void* ga, void* g, void* gw, void* gb, int row_b
   const PoolBn bn{(const float*)a, (const float*)mean, (const float*)rstd, (const float*)w, nullptr};
   return pool_act_adjoint(ga, g, gw, gb, row_blocks, gy, gy_splits, gy_slab, idx, y_pool, relu, n, h, w_, oh, ow, c, kh,
                           kw, stride_h, stride_w, pad_h, pad_w, dtype, stream, &bn);
+}
+
+int hf_pool_bn_act_adjoint_reduce_nhwc(void* g, void* gw, void* gb, int row_blocks, const void* gy, int gy_splits,
+                                       int64_t gy_slab, const void* a, const void* mean, const void* rstd, const void* w,
+                                       const void* idx, const void* y_pool, int relu, int64_t n, int64_t h, int64_t w_,
+                                       int64_t oh, int64_t ow, int64_t c, int64_t kh, int64_t kw, int64_t stride_h,
+                                       int64_t stride_w, int64_t pad_h, int64_t pad_w, int dtype, void* stream) {
+  if (!a || !mean || !rstd || !w) return HF_ERR_ARG;
+  const PoolBn bn{(const float*)a, (const float*)mean, (const float*)rstd, (const float*)w, nullptr};
+  return pool_act_adjoint(nullptr, g, gw, gb, row_blocks, gy, gy_splits, gy_slab, idx, y_pool, relu, n, h, w_, oh, ow, c,
+                          kh, kw, stride_h, stride_w, pad_h, pad_w, dtype, stream, &bn, true);
 }
 
 int hf_linear_ce_head(void* g_feat, void* g_w, void* g_b, const void* t_feat, const void* feat, const void* w,

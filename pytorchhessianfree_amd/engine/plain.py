@@ -7,12 +7,13 @@ from .. import _lib
 from .common import _Unit, _Unsupported, _cl, _pair, _same, mark_dead_prefix, records_of
 from .conv import _ConvEngine
 from .dense import _Layer
+from .problems import affine_train_args
 
 MAX_TAIL_ROWS, MAX_CLASSES = 256, 1024  # the dense kernels' row limit; the loss head's class limit
 
 
 class PlainStackEngine(_ConvEngine):
-    """The same sweeps for a plain stack ``[Dropout] conv(+bias | +eval BatchNorm) [ReLU] ... -> AdaptiveAvgPool2d(1) ->
+    """The same sweeps for a plain stack ``[inert Dropout] conv(+bias | +BatchNorm) [ReLU] ... -> AdaptiveAvgPool2d(1) ->
     flatten`` with a softmax cross-entropy on the pooled map -- the All-CNN-C of the reference's
     examples (examples/example_utils.py:59-83, BASELINE.json configs[3]).  Per layer: tangent
     convolution -> bias tangent + ReLU mask (into the next layer's operand) / masked slab sum + bias
@@ -32,6 +33,14 @@ class PlainStackEngine(_ConvEngine):
     ReLU / pool is ONE launch per direction as for a bias -- ``hf_pool_bn_act_tangent_nhwc`` adds the scale (w*rstd) and the
     ``xhat * v_w`` term at the windows' positions, ``hf_pool_bn_act_adjoint_nhwc`` writes the unscaled masked cotangent
     ``u.g`` (what the sums table, Hessian products and ``diag_ef`` read), ``u.ga = g * w*rstd`` and the scale's / shift's sums.
+
+    Train-mode ``BatchNorm2d`` units (each BatchNorm's own ``bn.training``; eval and train units mix): batch statistics in
+    the own forward pass (``hf_bn_stats_rows`` / ``hf_bn_forward_train``, running statistics moved per evaluation), in the
+    tangent -- the per-channel sums over ALL full-resolution rows come from the tangent convolution's epilogue or one
+    reduction launch (``_train_tangent_sums``); a pooled unit's gather ``hf_pool_bn_act_tangent_train_nhwc`` adds them up in
+    its prologue and still forms no full-resolution tangent map -- and in the two-pass adjoint
+    (``hf_pool_bn_act_adjoint_reduce_nhwc``: ``u.g`` and its sums; then ``hf_chan_affine_train``, or inside a Hessian product
+    ``hf_bn_train_hessian_*``).  5-6 launches per such unit and product; one process; no active ``Dropout``.
 
     A classifier tail instead of the global average pool (LeNet, VGG-style nets, DeepOBS 2c2d / 3c3d): units as above
     (the last one may be pooled), ``nn.Flatten``, then ``Linear [ReLU] ... Linear``.  The tail is the kind's HEAD, with
@@ -56,15 +65,18 @@ class PlainStackEngine(_ConvEngine):
         x_in = getattr(self.outputs, "_hf_input", None)
         if x_in is None or x_in.dim() != 4:
             raise _Unsupported("no recorded input")
-        if model.training:
-            raise _Unsupported("the model must be in eval mode")
         leaves = [m for m in model.modules() if not list(m.children())]
+        self._dropouts = [m for m in leaves if isinstance(m, (nn.Dropout, nn.Dropout2d))]
 
         units, cur, prev, pooled, i = [], x_in.detach(), "input", None, 0
         dense = None  # the layers of a classifier tail, once nn.Flatten has been met
         while i < len(leaves):
             m = leaves[i]
             if isinstance(m, (nn.Dropout, nn.Dropout2d, nn.Identity)):
+                if not isinstance(m, nn.Identity) and m.training and m.p > 0:
+                    where = f"behind {units[-1].name}" if units else "in front of the first convolution"
+                    raise _Unsupported(f"{type(m).__name__}(p={m.p}) {where} is active (train mode): a random mask the "
+                                       "engine cannot replay")
                 i += 1
                 continue
             if pooled is not None:
@@ -157,6 +169,7 @@ class PlainStackEngine(_ConvEngine):
         first.first = True
         first.im2col = first.a.shape[1] > 0 and first.rx.shape[1] < 4
         self.units, self.tail = units, units[-1]
+        self.train_bn = any(u.train for u in units)
         self.model_ref, self._in_shape = model, tuple(x_in.shape)
         used = {i for u in units + self.classifier for i in (u.pw, getattr(u, "pg", None), u.pb) if i is not None}
         if used != set(range(len(self.params))):
@@ -168,15 +181,29 @@ class PlainStackEngine(_ConvEngine):
             units[self.dead_units].no_dgrad = True
 
     def _layout_bn(self, u, bn, cy):
-        """The eval-mode BatchNorm behind ``u``'s convolution (output record ``cy``): what the unit's output record and
-        ReLU flag are -- ``modelprep`` fuses a following ``nn.ReLU`` into the layer and leaves one 5-entry record."""
+        """The BatchNorm behind ``u``'s convolution (output record ``cy``): what the unit's output record and ReLU flag
+        are.  Eval mode: ``modelprep`` fuses a following ``nn.ReLU`` into the layer and leaves one 5-entry record.  Train
+        mode (the layer's own ``bn.training``, as ``topology.make_unit``): the layer ran on stock ops and left a 6-entry
+        record with its batch statistics, which a following ``nn.ReLU`` completed; the unit gets clones of them that the
+        own forward pass rewrites."""
         if u.conv.bias is not None:
             raise _Unsupported(f"{u.name}: a convolution bias in front of a BatchNorm2d is not covered (bias=False)")
         rec = getattr(bn, "_hf_io", None)
-        if rec is None or len(rec) != 5:
-            raise _Unsupported(f"{u.name}: its BatchNorm2d has no fused eval record of this forward pass (it must be "
-                               "affine, with running statistics)")
-        bx, bres, by, brelu, _rstd = rec
+        if bn.training:
+            if self.group is not None:
+                raise _Unsupported(f"{u.name}: train-mode BatchNorm under data parallelism: batch statistics couple the "
+                                   "samples of a shard")
+            if rec is None or len(rec) != 6:
+                raise _Unsupported(f"{u.name}: train-mode BatchNorm without a record of this forward pass (it must be "
+                                   "affine, float32, on the GPU)")
+            bx, bres, by, brelu, rstd, mean_t = rec
+            u.rec_stats = (mean_t, rstd)
+            u.rstd, u.mean_t, u.train = rstd.clone(), mean_t.clone(), True
+        else:
+            if rec is None or len(rec) != 5:
+                raise _Unsupported(f"{u.name}: its BatchNorm2d has no fused eval record of this forward pass (it must be "
+                                   "affine, with running statistics)")
+            bx, bres, by, brelu, _rstd = rec
         if bres is not None or not _same(bx, cy):
             raise _Unsupported(f"{u.name}: the BatchNorm2d does not consume the convolution's output")
         return by, bool(brelu)
@@ -277,7 +304,7 @@ class PlainStackEngine(_ConvEngine):
             raise _Unsupported("more than 1024 classes")
 
     # ---- forward -----------------------------------------------------------------------------
-    def _forward_units(self, refresh, update_running):  # (no BatchNorm in a plain stack: nothing to move)
+    def _forward_units(self, refresh, update_running):
         first, flat = self.units[0], self._flat_params
         carried = (refresh and flat is not None and flat.data_ptr() == self.params[0].data_ptr()
                    and self._conv_carrying_scatter(first, first.conv.weight.detach(), first.sF, flat, 0))
@@ -286,7 +313,7 @@ class PlainStackEngine(_ConvEngine):
         for u in self.units:
             if not (carried and u is first):
                 self._conv_forward(u)
-            self._bn_forward(u, u.sF)
+            self._bn_forward(u, u.sF, update_running)  # (train mode: batch statistics; moves the running ones)
             if u.pool is not None:
                 # the pooled map, its copy in the x half of the consumer's [t_x | x] operand, the positions
                 c = u.y.shape[1]
@@ -326,6 +353,15 @@ class PlainStackEngine(_ConvEngine):
         """t_pool = (y_pool > 0) * (t_a[idx] + v_b) from the tangent convolution's slabs into the consumer's operand; with
         a BatchNorm  (y_pool > 0) * (t_a[idx] * w*rstd + xhat[idx] * v_w + v_b)."""
         tail = (u.pidx, u.yp, 1 if u.relu else 0, *self._pool_dims(u))
+        if u.train:
+            # batch statistics: the sums over ALL full-resolution rows (partial rows by the convolution's epilogue or one
+            # reduction over the slabs), then the gather with the finalisation in its prologue
+            vg, vb = self._scale_shift_tangent(u, v)
+            part_x, part_1, nparts = self._train_tangent_sums(u)
+            n, h, w = tail[3:6]
+            self._launch("hf_pool_bn_act_tangent_train_nhwc", u.tout, u.tout_ld, u.tbuf, u.sT, u.tbuf.shape[1], u.a, u.mean,
+                         u.rstd, u.scale, vg, vb, part_x, part_1, nparts, float(n * h * w), *tail)
+            return
         if u.bn is not None:
             vg, vb = self._scale_shift_tangent(u, v)
             self._launch("hf_pool_bn_act_tangent_nhwc", u.tout, u.tout_ld, u.tbuf, u.sT, u.tbuf.shape[1], u.a, u.mean,
@@ -343,7 +379,14 @@ class PlainStackEngine(_ConvEngine):
         (gy, splits, slab), = srcs
         gb = None if (u.defer or u.pb is None) else u.gb
         tail = (u.pidx, u.yp, 1 if u.relu else 0, *self._pool_dims(u), *u.pool)
-        if u.bn is not None:
+        if u.train:
+            # pass 1: the masked cotangent at full resolution and its sums; pass 2 (a grid-wide sum stands between them):
+            # g_a by the elementwise train kernel -- inside a Hessian product ``hf_bn_train_hessian_apply``'s instead
+            self._launch("hf_pool_bn_act_adjoint_reduce_nhwc", u.g, u.gw, u.gb, u.rb, gy, splits, slab, u.a, u.mean, u.rstd,
+                         u.scale, *tail)
+            if not self._second:
+                self._launch("hf_chan_affine_train", *affine_train_args(self._train_adjoint_problem(u)))
+        elif u.bn is not None:
             gw = None if (u.defer or u.pg is None) else u.gw
             self._launch("hf_pool_bn_act_adjoint_nhwc", u.ga, u.g, gw, gb, u.rb, gy, splits, slab, u.a, u.mean, u.rstd,
                          u.scale, *tail)
@@ -370,6 +413,8 @@ class PlainStackEngine(_ConvEngine):
                       else self._zeros(u.conv.weight.numel()))
                 if not (carried and u is first):
                     self._conv_slabs(0, u.tbuf, u.cols, vw, u.geo, u.sT)
+            elif u.train:  # (the epilogue writes the tangent's per-channel partial sums where it takes the geometry)
+                self._tangent_convs([u])
             else:
                 self._conv_slabs(0, u.tbuf, u.xcat, u.wcat, self._tgeo(u), u.sT)
             if u.pool is not None:
@@ -447,6 +492,8 @@ class PlainStackEngine(_ConvEngine):
         """Besides the units': the tail's module identities and the addresses of its FROZEN tensors (kernel arguments of
         the captured graphs; the trainable ones are covered by the flat vector's address)."""
         sig = super().layer_signature()
+        if self._dropouts:  # (skipped as inert: one that becomes active is another network)
+            sig = sig + (tuple(bool(m.training and m.p > 0) for m in self._dropouts),)
         if not self.classifier:
             return sig
         return sig + (tuple((id(u.lin), u.act) for u in self.classifier), tuple(t.data_ptr() for t in self._sig_tail))

@@ -30,25 +30,32 @@ class _TangentSweep:
         self._chan_sums(u.tbuf, u.sT, u.tbuf.shape[1], n, k, oh * ow, u.rb, gw=u.gw[u.rb:], x=u.g1, mean=self._zeros(k),
                         rstd=u.rstd)
 
+    def _train_tangent_sums(self, u):
+        """The partial rows ``(of S_x, of S_1, their count)`` of a train-mode unit's tangent sums over all its rows -- by
+        the convolution's epilogue (``u.tsum``), else by a reduction launch of their own over the slabs; left in
+        ``u.tsums``.  What the elementwise pass of an unpooled unit and the gather of a pooled one add up."""
+        n, k, oh, ow = u.a.shape
+        parts = (u.gw, u.gb, u.rb)
+        if self.hessian:
+            # the adjoint of a Hessian product reads these sums again (hf_bn_train_hessian_coeffs): rows of their
+            # own -- and the scale's second-order sum
+            parts = (u.hx, u.h1, u.rb)
+            self._scale_second_order_sum(u)
+        if u.tsum:
+            parts = (u.tpx, u.tp1, u.tp1.shape[0])
+        u.tsums = parts  # (a Hessian product's adjoint reads them again)
+        if not u.tsum:
+            self._chan_sums(u.tbuf, u.sT, u.tbuf.shape[1], n, k, oh * ow, u.rb, gw=parts[0], gb=parts[1], x=u.a,
+                            mean=u.mean, rstd=u.rstd)
+        return parts
+
     def _bn_tangent(self, u, v, add, add_ld):
         """t_y = mask * (sum(T slabs) * w*rstd + xhat * v_w + v_b + add), into the consumer's operand."""
         n, k, oh, ow = u.a.shape
         vg, vb = self._scale_shift_tangent(u, v)
         if u.train:
-            # reduction (partial rows: by the convolution's epilogue, else by its own launch), then the elementwise
-            # pass adds them up in its prologue
-            parts = (u.gw, u.gb, u.rb)
-            if self.hessian:
-                # the adjoint of a Hessian product reads these sums again (hf_bn_train_hessian_coeffs): rows of their
-                # own -- and the scale's second-order sum
-                parts = (u.hx, u.h1, u.rb)
-                self._scale_second_order_sum(u)
-            if u.tsum:
-                parts = (u.tpx, u.tp1, u.tp1.shape[0])
-            u.tsums = parts  # (a Hessian product's adjoint reads them again)
-            if not u.tsum:
-                self._chan_sums(u.tbuf, u.sT, u.tbuf.shape[1], n, k, oh * ow, u.rb, gw=parts[0], gb=parts[1], x=u.a,
-                                mean=u.mean, rstd=u.rstd)
+            # reduction, then the elementwise pass adds the partial rows up in its prologue
+            parts = self._train_tangent_sums(u)
             self._launch("hf_chan_affine_train",
                          *affine_train_args(self._train_tangent_problem(u, parts, vg, vb, add), add_ld))
             return
