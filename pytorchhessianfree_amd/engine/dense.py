@@ -7,26 +7,11 @@ import os
 import torch
 from torch import nn
 
-from .. import _lib
 from .base import _Engine
-from .common import _P, _Unsupported, _flat_view, _same, loss_spec_of, mark_dead_prefix, records_of
+from .common import _Unsupported, _flat_view, _same, loss_spec_of, records_of
+from .linear import DIAG_EF, GRADIENT, MAX_CLASSES, PRODUCT, _Chain, _Layer  # noqa: F401  (_Layer: plain.py's tail reads it here)
 
-_ACT = {None: 0, nn.ReLU: 1, nn.Tanh: 2}
 _OPT_IN = "the dense-stack engine is opt-in (set HF_DENSE_ENGINE=1)"
-_GRADIENT, _PRODUCT, _DIAG_EF = range(3)  # what an adjoint sweep is for
-
-
-class _Layer:
-    """``Linear(+bias) [ReLU | Tanh]``: the module, its activation code, parameter indices and static buffers."""
-
-    def __init__(self, lin, act):
-        self.lin, self.act = lin, act
-        self.c_out, self.c_in = lin.weight.shape
-        self.dead = self.first_live = False
-
-
-def _addr(base, words):
-    return _P(base + 4 * words)
 
 
 class DenseStackEngine(_Engine):
@@ -68,7 +53,6 @@ class DenseStackEngine(_Engine):
     acc_decline = "the dense-stack engine serves step() sessions only"
     session_decline = None    # why THIS engine, built with HF_DENSE_SESSION=1, has no session mode
     has_weight_copies = False  # (weights are read in place: a session captures no refresh graph)
-    max_rows = 256
 
     @classmethod
     def unavailable(cls, hessian, need_session):
@@ -111,9 +95,7 @@ class DenseStackEngine(_Engine):
             self.forward_own()
         if self.hessian:
             self.gradient()  # the first-order cotangents the Hessian products read, at the final linearisation point
-        for u in self.layers:  # the model's own activations were only needed up to here
-            u.rx = u.ry = None
-        self._rec_in = None
+        self.chain.release()
         self._release(model)
 
     # ---- topology ----------------------------------------------------------------------------
@@ -122,8 +104,8 @@ class DenseStackEngine(_Engine):
         if not isinstance(x_in, torch.Tensor) or x_in.dtype != torch.float32 or not x_in.is_cuda:
             raise _Unsupported("no recorded float32 GPU input")
         leaves = [m for m in model.modules() if not list(m.children())]
-
-        layers, cur, i = [], x_in.detach(), 0
+        chain = _Chain(self.dev, self._offs, (nn.ReLU, nn.Tanh), ("linear", "stack", "batch {} > {} rows"))
+        layers, cur, i = chain.layers, x_in.detach(), 0
         while i < len(leaves):
             m = leaves[i]
             dropout = isinstance(m, (nn.Dropout, nn.Dropout1d, nn.Dropout2d, nn.Dropout3d, nn.AlphaDropout))
@@ -138,84 +120,32 @@ class DenseStackEngine(_Engine):
                     raise _Unsupported("Flatten does not turn the input into [batch, features]")
                 cur = fy
             elif type(m) is nn.Linear:
-                cx, cy = records_of(m, with_input=True)
-                if cx.dim() != 2 or not _same(cx, cur):
-                    raise _Unsupported(f"linear {len(layers)}: its input is not the previous [batch, features] activation")
-                nxt = leaves[i + 1] if i + 1 < len(leaves) else None
-                act, y = None, cy
-                if type(nxt) in (nn.ReLU, nn.Tanh):
-                    if getattr(nxt, "inplace", False):
-                        raise _Unsupported(f"linear {len(layers)}: followed by an in-place activation")
-                    rx, ry = records_of(nxt, with_input=True)
-                    if not _same(rx, cy):
-                        raise _Unsupported(f"{type(nxt).__name__} does not read linear {len(layers)}'s output")
-                    act, y = type(nxt), ry
-                    i += 1
-                u = _Layer(m, _ACT[act])
-                u.rx, u.ry = cx, y
-                u.pw = self._param(m.weight)
-                u.pb = self._param(m.bias) if m.bias is not None else None
-                layers.append(u)
-                cur = y
+                i, cur = chain.layout_layer(leaves, i, cur, self._param)
+                continue
             else:
                 raise _Unsupported(f"unsupported layer {type(m).__name__}")
             i += 1
         if not layers:
             raise _Unsupported("no Linear layer")
-        if layers[-1].act != 0:
-            raise _Unsupported("the stack does not end in a Linear layer")
-        out = self.outputs.detach()
-        if out.data_ptr() != layers[-1].ry.data_ptr() or tuple(out.shape) != tuple(layers[-1].ry.shape):
-            raise _Unsupported("the network output is not the last Linear layer's output")
-        self.rows = int(out.shape[0])
-        if self.rows > self.max_rows:
-            raise _Unsupported(f"batch {self.rows} > {self.max_rows} rows")
+        self.rows = chain.check_end(self.outputs.detach())
         used = {k for u in layers for k in (u.pw, u.pb) if k is not None}
         if used != set(range(len(self.params))):
             raise _Unsupported("the parameter list has entries the engine's layers do not cover")
-        # frozen layers at the input end: dead for both sweeps; the first layer with a trainable parameter reads a
-        # tangent-free input and needs no data gradient
-        self.dead_layers = mark_dead_prefix(layers)
-        layers[self.dead_layers].first_live = True
-        self.layers, self.model_ref = layers, model
-        self._rec_in, self._in_shape = layers[0].rx, tuple(x_in.shape)
+        self.dead_layers = chain.mark_dead_prefix()
+        self.chain, self.layers, self.model_ref, self._in_shape = chain, layers, model, tuple(x_in.shape)
 
     def _allocate(self):
-        f32, dev, rows, lib = torch.float32, self.dev, self.rows, _lib.load()
         # the input in the MODEL's shape (what a session's ``set_batch`` receives); the first layer reads it flattened
-        self.x_in = torch.empty(self._in_shape, dtype=f32, device=dev)
-        self._x2d = self.x_in.view(rows, self.layers[0].c_in)
-        self._x2d.copy_(self._rec_in)
-        x, widest = self._x2d, 0
-        for u in self.layers:
-            st, sd = _lib.c_int(), _lib.c_int()
-            _lib.check(lib.hf_dense_plan(rows, u.c_in, u.c_out, st, sd), "hf_dense_plan")
-            u.sT, u.sD = st.value, sd.value
-            u.x = x
-            u.y = torch.empty((rows, u.c_out), dtype=f32, device=dev)
-            u.tslabs = torch.empty((u.sT, rows * u.c_out), dtype=f32, device=dev)
-            if not u.dead:
-                u.ty = torch.empty_like(u.y)
-                u.ga = torch.empty_like(u.y)
-                u.dslabs = None if u.first_live else torch.empty((u.sD, rows * u.c_in), dtype=f32, device=dev)
-                u.g1 = u.h1 = None
-                if self.hessian:  # first-order g_l = h_l * act'(a_l); h_l where the activation has a curvature
-                    u.g1 = torch.empty_like(u.y)
-                    u.h1 = torch.empty_like(u.y) if u.act == 2 else None
-            widest = max(widest, u.c_out)
-            x = u.y
-        self.logits = self.layers[-1].y
+        self.x_in = torch.empty(self._in_shape, dtype=torch.float32, device=self.dev)
+        x2d = self.x_in.view(self.rows, self.layers[0].c_in)
+        self.logits = self.chain.allocate(self.rows, x2d, None, hessian=self.hessian)
+        x2d.copy_(self.layers[0].rx)
         self._g_last = torch.empty_like(self.logits)
-        self._zero = torch.zeros(rows * widest, dtype=f32, device=dev)  # (a tangent GEMM with no live term)
+        # (a tangent GEMM with no live term: only the bias of the first live layer carries a tangent)
+        self.chain.zero = torch.zeros(self.rows * max(u.c_out for u in self.layers), dtype=torch.float32, device=self.dev)
         # the parameters as ONE flat vector, when they are consecutive views of one (the optimizer's arena): a session
         # is valid only while they stay where its graphs read them
         self._flat_params = _flat_view(self.params, self.n)
-
-    # ---- launches (``_launch``: common._Launcher) ------------------------------------------------
-    def _tangent(self, u, t_x, v_w):
-        """``u.tslabs <- t_x W^T + x V^T`` (either term may be absent, not both)."""
-        self._launch("hf_dense_tangent_slabs", u.tslabs, t_x, u.x, u.lin.weight, v_w, self.rows, u.c_in, u.c_out, 0, u.sT,
-                     u.tslabs.shape[1])
 
     def _flat(self, noun, *vecs):
         for t in vecs:
@@ -224,25 +154,16 @@ class DenseStackEngine(_Engine):
 
     # ---- forward -----------------------------------------------------------------------------
     def forward_own(self, refresh=False, update_running=True):
-        """The model's forward pass on the engine's static buffers: the tangent kernel with ``t_x = NULL, V = W`` is
-        the forward GEMM; slab sum, bias and activation in one pass (``hf_dense_act_forward``); in session mode the loss
-        head.  Weights are read in place (``refresh``: nothing to do), there are no running statistics.  Two launches
-        per layer, no allocation, no host synchronisation: capturable."""
-        for u in self.layers:
-            self._tangent(u, None, u.lin.weight)
-            self._launch("hf_dense_act_forward", u.y, u.tslabs, u.sT, u.tslabs.shape[1], u.lin.bias, u.act, self.rows,
-                         u.c_out)
+        """The model's forward pass on the static buffers (``_Chain.forward``: two launches per layer); in session mode the
+        loss head.  Weights are read in place (``refresh``: nothing to do), no running statistics; capturable."""
+        self.chain.forward()
         if self.loss_spec is not None:
             self._loss_head()
         self._at = "own"
         return self.logits
 
     def _load_recorded(self, outputs):
-        """The activations the MODEL's forward pass recorded (same ReLU decisions as the autograd operator the first
-        product is compared with)."""
-        self._x2d.copy_(self._rec_in)
-        for u in self.layers:
-            u.y.copy_(u.ry)
+        self.chain.load_recorded()  # (the MODEL's activations: the ReLU decisions of the operator it is compared with)
         if self.loss_spec is not None:
             self._loss_head()
         self._at = "recorded"
@@ -256,8 +177,8 @@ class DenseStackEngine(_Engine):
             if spec is None or spec["kind"] != "mse":
                 raise _Unsupported("the loss is neither a plain softmax cross-entropy nor a mean-squared error")
             self._mse2 = 2.0 / float(outputs.numel()) if spec["reduction"] == "mean" else 2.0
-        elif self._ce[0].shape[1] > 1024:
-            raise _Unsupported("more than 1024 classes")
+        elif self._ce[0].shape[1] > MAX_CLASSES:
+            raise _Unsupported(f"more than {MAX_CLASSES} classes")
         else:  # (no host read of the targets: a batch with an ignored target has failed the closed form's check)
             spec = loss_spec_of(loss, outputs, check_values=False)
         # diag_ef: the reduction of a PLAIN cross-entropy / MSE (None: no per-sample reading of this loss) and the
@@ -294,8 +215,7 @@ class DenseStackEngine(_Engine):
         self._work = torch.empty(512, dtype=torch.float64, device=self.dev)
         self.loss_spec, self.supports_session = spec, True
         self._sig_slots = self._signature_slots()
-        self._sig_frozen = [t for u in self.layers for t, k in ((u.lin.weight, u.pw), (u.lin.bias, u.pb))
-                            if k is None and t is not None]
+        self._sig_frozen = self.chain.frozen_tensors()
         self._loss_head()
 
     def _loss_head(self):
@@ -362,70 +282,21 @@ class DenseStackEngine(_Engine):
             raise RuntimeError("the dense-stack engine keeps first-order cotangents in Hessian mode only")
         if out is not None:
             self._flat("the gradient", out)
-        return self._adjoint_sweep(_GRADIENT, self._h_last, out)
-
-    def _adjoint_sweep(self, what, seed, out, v=None, scale=None):
-        """THE adjoint sweep: from the cotangent ``seed`` at the logits through the live layers in reverse, per layer the
-        activation adjoint -> the weight output -> (``_DIAG_EF``) the bias output -> the data gradient, as slabs the next
-        activation adjoint sums.  ``_GRADIENT`` keeps ``g_l`` (``h_l`` of tanh layers) where a Hessian engine has buffers
-        for them and writes ``weight * gradient`` if there is an ``out``; ``_PRODUCT`` carries, on a Hessian engine, the
-        second-order terms of the vector ``v`` where a layer has them; ``_DIAG_EF`` writes sums of squares times
-        ``scale`` (per-sample cotangents: the rank ``weight`` does not enter, the bias has a kernel of its own)."""
-        launch, rows, offs, weight = self._launch, self.rows, self._offs, self.weight
-        diag, second = what == _DIAG_EF, what == _PRODUCT and self.hessian
-        slabs, splits, stride = seed, 1, 0
-        for u in reversed(self.layers[self.dead_layers:]):
-            o_w = _addr(out.data_ptr(), offs[u.pw]) if out is not None and u.pw is not None else None
-            o_b = _addr(out.data_ptr(), offs[u.pb]) if out is not None and u.pb is not None else None
-            g = u.g1 if what == _GRADIENT and u.g1 is not None else u.ga
-            if what == _GRADIENT and u.h1 is not None:  # h_l itself: the slab sum, no factor
-                launch("hf_dense_act_adjoint", u.h1, None, slabs, splits, stride, None, 0, rows, u.c_out, 1.0)
-            if second and u.act == 2:  # tanh: the curvature term -2 a t_a h
-                launch("hf_dense_act_adjoint2", g, o_b, slabs, splits, stride, u.y, u.act, u.ty, u.h1, rows, u.c_out, weight)
-            else:
-                launch("hf_dense_act_adjoint", g, None if diag else o_b, slabs, splits, stride, u.y, u.act, rows, u.c_out,
-                       1.0 if diag else weight)
-            if o_w is not None and diag:
-                launch("hf_dense_sq_wgrad", o_w, g, u.x, rows, u.c_in, u.c_out, scale)
-            elif o_w is not None and second and u.t_in is not None:  # + g^T t_x (none enters the first live layer)
-                launch("hf_dense_wgrad2", o_w, g, u.x, u.g1, u.t_in, rows, u.c_in, u.c_out, weight)
-            elif o_w is not None:
-                launch("hf_dense_wgrad", o_w, g, u.x, rows, u.c_in, u.c_out, weight)
-            if o_b is not None and diag:
-                launch("hf_dense_sq_colsum", o_b, g, rows, u.c_out, scale)
-            if u.first_live:
-                break
-            if second and u.pw is not None:  # + g V (a frozen weight has no tangent)
-                launch("hf_dense_dgrad2_slabs", u.dslabs, g, u.lin.weight, u.g1, _addr(v.data_ptr(), offs[u.pw]), rows,
-                       u.c_in, u.c_out, u.sD, u.dslabs.shape[1])
-            else:
-                launch("hf_dense_dgrad_slabs", u.dslabs, g, u.lin.weight, rows, u.c_in, u.c_out, u.sD, u.dslabs.shape[1])
-            slabs, splits, stride = u.dslabs, u.sD, u.dslabs.shape[1]
+        self.chain.adjoint(GRADIENT, self._h_last, out, self.weight)
         return out
 
     # ---- the product -------------------------------------------------------------------------
     def local(self, v, out=None):
         v, out = self._product_vectors(v, out)
         self._flat("vector and product", v, out)
-        vp, offs = v.data_ptr(), self._offs
-        t_x = None
-        for u in self.layers[self.dead_layers:]:
-            u.t_in = t_x  # (the tangent of the layer's input: the Hessian's second weight-gradient term)
-            v_w = _addr(vp, offs[u.pw]) if u.pw is not None else None
-            v_b = _addr(vp, offs[u.pb]) if u.pb is not None else None
-            if t_x is None and v_w is None:  # (only the bias of the first live layer carries a tangent)
-                slabs, splits = self._zero, 1
-            else:
-                self._tangent(u, t_x, v_w)
-                slabs, splits = u.tslabs, u.sT
-            self._launch("hf_dense_act_tangent", u.ty, slabs, splits, u.tslabs.shape[1], v_b, u.y, u.act, self.rows, u.c_out)
-            t_x = u.ty
+        t_x = self.chain.tangent(v)
         if self._ce is not None:
             self._launch("hf_softmax_ce_hvp", self._g_last, self._ce[0], t_x, float(self._ce[1]), self.rows,
                          self.logits.shape[1])
         else:
             torch.mul(t_x, self._mse2, out=self._g_last)
-        return self._adjoint_sweep(_PRODUCT, self._g_last, out, v=v)
+        self.chain.adjoint(PRODUCT, self._g_last, out, self.weight, v=v)
+        return out
 
     # ---- diagonal of the empirical Fisher ---------------------------------------------------------
     def diag_ef(self, reduction="mean", out=None):
@@ -447,7 +318,8 @@ class DenseStackEngine(_Engine):
         if out is None:
             out = torch.empty(self.n, dtype=torch.float32, device=self.dev)
         self._flat("the diagonal", out)
-        return self._adjoint_sweep(_DIAG_EF, self._g_ef, out, scale=1.0 / self.rows if reduction == "mean" else 1.0)
+        self.chain.adjoint(DIAG_EF, self._g_ef, out, scale=1.0 / self.rows if reduction == "mean" else 1.0)
+        return out
 
 
 def diag_ef_of(model, loss_function, inputs, targets, reduction, why=None):

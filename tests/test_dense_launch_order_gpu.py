@@ -98,14 +98,8 @@ class Recorder:
         return call
 
 
-def build(net, kind, monkeypatch):
-    """(engine, the list its launches are recorded in) of net ``net`` as a ``ggn`` / ``hessian`` / ``session`` engine."""
-    monkeypatch.setenv("HF_DENSE_ENGINE", "1")
-    monkeypatch.setenv("HF_DENSE_HESSIAN", "1" if kind == "hessian" else "0")
-    monkeypatch.setenv("HF_DENSE_SESSION", "1" if kind == "session" else "0")
-    names = []
-    proxy = Recorder(_lib.load(), names)
-    monkeypatch.setattr(_lib, "load", lambda: proxy)
+def net_and_loss(net):
+    """(prepared model, its outputs, the loss) of net ``net`` on the GPU, seeded on the CPU."""
     torch.manual_seed(0)
     model = torch.nn.Sequential(torch.nn.Linear(7, 5), torch.nn.ReLU(), torch.nn.Linear(5, 5), torch.nn.Tanh(),
                                 torch.nn.Linear(5, 3))
@@ -120,8 +114,20 @@ def build(net, kind, monkeypatch):
     model = model.to(DEV)
     modelprep.prepare_model(model)
     out = model(x)
+    return model, out, lossf(out, t)
+
+
+def build(net, kind, monkeypatch):
+    """(engine, the list its launches are recorded in) of net ``net`` as a ``ggn`` / ``hessian`` / ``session`` engine."""
+    monkeypatch.setenv("HF_DENSE_ENGINE", "1")
+    monkeypatch.setenv("HF_DENSE_HESSIAN", "1" if kind == "hessian" else "0")
+    monkeypatch.setenv("HF_DENSE_SESSION", "1" if kind == "session" else "0")
+    names = []
+    proxy = Recorder(_lib.load(), names)
+    monkeypatch.setattr(_lib, "load", lambda: proxy)
+    model, out, loss = net_and_loss(net)
     why = []
-    eng = FusedGGNEngine.try_build(lossf(out, t), out, [p for p in model.parameters() if p.requires_grad],
+    eng = FusedGGNEngine.try_build(loss, out, [p for p in model.parameters() if p.requires_grad],
                                    hessian=kind == "hessian", why=why, need_session=kind == "session")
     assert isinstance(eng, DenseStackEngine) and eng.hessian == (kind == "hessian"), why
     assert (eng.loss_spec is not None) == (kind == "session"), why

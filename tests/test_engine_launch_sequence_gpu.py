@@ -1,11 +1,14 @@
-"""GPU: the launch sequence of the conv-unit engines (``FusedGGNEngine``, ``PlainStackEngine``) WITH ARGUMENTS -- every
-``hf_*`` call that ``forward_own()``, ``local(v)``, ``gradient(out)`` and ``diag_ef("mean")`` issue, eagerly, on small
-nets -- against ``tests/golden/engine_launch_sequence.json.gz`` (one call per line; gzip, since most of its 2 000 lines are
-the per-sample launches of ``diag_ef``, equal but for the addresses' ranks).
+"""GPU: the launch sequence of the engines (``FusedGGNEngine``, ``PlainStackEngine``, ``DenseStackEngine``) WITH ARGUMENTS
+-- every ``hf_*`` call that ``forward_own()``, ``local(v)``, ``gradient(out)`` (on a dense stack also ``gradient()``) and
+``diag_ef("mean")`` issue, eagerly, on small nets -- against
+``tests/golden/engine_launch_sequence.json.gz`` (one call per line; gzip, since most of its 2 500 lines are the per-sample
+launches of ``diag_ef``, equal but for the addresses' ranks).
 
 The golden file is a recording of the commit BEFORE the launcher and the problem builders (``engine/common._Launcher``,
-``engine/problems.py``) replaced the raw ctypes calls: the code under test is never the source of its own expectation.  It
-is rewritten only from a checkout that is trusted to launch correctly, put first on ``PYTHONPATH``::
+``engine/problems.py``) replaced the raw ctypes calls; the ``dense_*`` cases of the commit BEFORE the chain of ``Linear``
+layers (``engine/linear.py``) replaced the dense-stack engine's own loops: the code under test is never the source of its
+own expectation.  It is rewritten only from a checkout that is trusted to launch correctly, put first on
+``PYTHONPATH``::
 
     PYTHONPATH=<trusted checkout> python tests/test_engine_launch_sequence_gpu.py tests/golden/engine_launch_sequence.json.gz
 
@@ -30,6 +33,8 @@ from torch.utils._python_dispatch import TorchDispatchMode
 from engine_nets import DEV, build, build_plain
 from pytorchhessianfree_amd import _lib, curvature, modelprep
 from pytorchhessianfree_amd import testproblems as tp
+from pytorchhessianfree_amd.engine import FusedGGNEngine
+from test_dense_launch_order_gpu import net_and_loss
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "engine_launch_sequence.json.gz")
@@ -54,14 +59,27 @@ CASES = {
     "stack_hessian_seq": lambda: sequential_extras(build_plain(hessian=True)),
     "diag_batched": lambda: build("wide"),  # (HF_DIAG_EF_BATCHED=1, see ENV: one squared-sum launch per layer)
     "stack_diag_batched": lambda: build_plain(),
+    # the dense stack: nets A and D of ``test_dense_launch_order_gpu.py`` (D: only a bias tangent enters the first layer)
+    "dense_ggn": lambda: build_dense("A", "ggn"),
+    "dense_hessian": lambda: build_dense("A", "hessian"),
+    "dense_session": lambda: build_dense("A", "session"),
+    "dense_bias_only": lambda: build_dense("D", "ggn"),
 }
+DENSE = {"ggn": {"HF_DENSE_ENGINE": "1", "HF_DENSE_HESSIAN": "0", "HF_DENSE_SESSION": "0"},
+         "hessian": {"HF_DENSE_ENGINE": "1", "HF_DENSE_HESSIAN": "1", "HF_DENSE_SESSION": "0"},
+         "session": {"HF_DENSE_ENGINE": "1", "HF_DENSE_HESSIAN": "0", "HF_DENSE_SESSION": "1"}}
 ENV = {"fused": {"HF_BN_SUMS_DEFER": "0"}, "diag_batched": {"HF_DIAG_EF_BATCHED": "1"},
-       "stack_diag_batched": {"HF_DIAG_EF_BATCHED": "1"}}
-# the operations recorded per case: all four for the first eight, the diagonal only where it is the case's subject (most
+       "stack_diag_batched": {"HF_DIAG_EF_BATCHED": "1"}, "dense_ggn": DENSE["ggn"], "dense_hessian": DENSE["hessian"],
+       "dense_session": DENSE["session"], "dense_bias_only": DENSE["ggn"]}
+# the operations recorded per case: all four unless listed here, the diagonal only where it is the case's subject (most
 # of the file's lines are ``diag_ef``'s per-sample launches)
-OPS = {case: ("forward_own", "local", "gradient") for case in
+ALL_OPS = ("forward_own", "local", "gradient", "diag_ef")
+OPS = {case: ALL_OPS[:3] for case in
        ("stack_pooled", "stack_pooled_hessian", "stack_frozen", "hessian_seq", "stack_hessian_seq")}
 OPS.update(diag_batched=("diag_ef",), stack_diag_batched=("diag_ef",))
+# the dense stack: what ``test_dense_launch_order_gpu.py`` runs per kind (``gradient(out)`` of a GGN engine outside session
+# mode raises before anything is launched)
+OPS.update(dense_hessian=ALL_OPS + ("gradient_kept",), dense_session=ALL_OPS + ("gradient_kept",))
 
 
 def build_pooled(hessian=False, freeze_first=False):
@@ -75,6 +93,15 @@ def build_pooled(hessian=False, freeze_first=False):
     make_op = curvature.hessian_operator if hessian else curvature.ggn_operator
     op = make_op(lossf(out, t), out, [p for p in model.parameters() if p.requires_grad])
     assert type(op).__name__ == "PlainStackEngine" and op.hessian == hessian
+    return op
+
+
+def build_dense(net, kind):
+    model, out, loss = net_and_loss(net)
+    why = []
+    op = FusedGGNEngine.try_build(loss, out, [p for p in model.parameters() if p.requires_grad], hessian=kind == "hessian",
+                                  why=why, need_session=kind == "session")
+    assert type(op).__name__ == "DenseStackEngine" and (op.loss_spec is not None) == (kind == "session"), why
     return op
 
 
@@ -94,6 +121,10 @@ REQUIRED = [
     "hf_conv2d_nhwc_slabs_unpack", "hf_conv2d_nhwc_backward_slabs", "hf_conv2d_nhwc_group_slabs",
     "hf_conv2d_nhwc_group_slabs_bnsum", "hf_conv2d_nhwc_dw_slabs", "hf_pool_act_tangent_nhwc",
     "hf_pool_act_adjoint_nhwc", "hf_conv2d_nhwc_sqsum_slabs", "hf_chan_sqsum",
+    # the chain of ``Linear`` layers (the dense stack)
+    "hf_softmax_ce_hvp", "hf_dense_tangent_slabs", "hf_dense_act_forward", "hf_dense_act_tangent", "hf_dense_act_adjoint",
+    "hf_dense_act_adjoint2", "hf_dense_wgrad", "hf_dense_wgrad2", "hf_dense_dgrad_slabs", "hf_dense_dgrad2_slabs",
+    "hf_dense_sq_wgrad", "hf_dense_sq_colsum", "hf_dense_loss_head",
 ]
 
 # struct arguments: entry point -> {argument index: (struct, count or the index of the argument that holds it)}
@@ -187,8 +218,9 @@ def record(case, setenv, patch_load):
     out = torch.empty(op.n, device=DEV)
     got = {}
     for what, call in (("forward_own", op.forward_own), ("local", lambda: op.local(v)),
-                       ("gradient", lambda: op.gradient(out)), ("diag_ef", lambda: op.diag_ef("mean"))):
-        if what not in OPS.get(case, (what,)):
+                       ("gradient", lambda: op.gradient(out)), ("gradient_kept", lambda: op.gradient()),
+                       ("diag_ef", lambda: op.diag_ef("mean"))):
+        if what not in OPS.get(case, ALL_OPS):
             continue
         rec.restart()
         with KeepAlive():
