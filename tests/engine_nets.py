@@ -1,5 +1,6 @@
 """The small ResNet-style nets the engine's GPU tests build (stem + max-pool and residual blocks, one of them with a
-downsample branch) and one conv + bias stack for the plain-stack engine.
+downsample branch), one conv + bias stack for the plain-stack engine and the five-layer MLPs of the dense-stack engine's
+launch tests (``net_and_loss``).
 
 ``small``: 8x8 inputs, batch 8, 8 / 16 channels (two blocks) -- at these sizes the stem is the one unit on the row-major
 kernel.  ``wide``: 8x8 inputs, batch 16, 32 / 64 channels and a third block on a 1x1 map -- the stem, an identity block, a
@@ -146,3 +147,27 @@ def build_plain(hessian=False):
                                   hessian=hessian, why=why)
     assert isinstance(op, PlainStackEngine) and op.hessian == hessian, why
     return op
+
+
+# the dense stack's nets A-E (``test_dense_launch_order_gpu.py`` describes them): frozen parameters per net as (index in
+# the Sequential, attribute)
+DENSE_FROZEN = {"A": (), "B": ((0, "weight"), (0, "bias")), "C": ((2, "weight"),), "D": ((0, "weight"),), "E": ()}
+DENSE_ROWS = 3
+
+
+def net_and_loss(net):
+    """(prepared model, its outputs, the loss) of dense net ``net`` on the GPU, seeded on the CPU."""
+    torch.manual_seed(0)
+    model = nn.Sequential(nn.Linear(7, 5), nn.ReLU(), nn.Linear(5, 5), nn.Tanh(), nn.Linear(5, 3))
+    for index, attr in DENSE_FROZEN[net]:
+        getattr(model[index], attr).requires_grad = False
+    gen = torch.Generator().manual_seed(1)
+    x = torch.randn(DENSE_ROWS, 7, generator=gen).to(DEV)
+    if net == "E":
+        t, lossf = torch.randn(DENSE_ROWS, 3, generator=gen).to(DEV), nn.MSELoss()
+    else:
+        t, lossf = torch.randint(0, 3, (DENSE_ROWS,), generator=gen).to(DEV), nn.CrossEntropyLoss()
+    model = model.to(DEV)
+    modelprep.prepare_model(model)
+    out = model(x)
+    return model, out, lossf(out, t)

@@ -5,112 +5,27 @@ im2col'd first unit pooled (3x3 / stride 2, 12x12 -> 5x5), an unpooled BatchNorm
 stride 2 on the odd 5x5 map), a 1x1 bias layer -- and ``testproblems.convbn_fc_small`` (two pooled BatchNorm units in front
 of a ``Flatten, Linear, ReLU, Linear`` tail).  The BatchNorm state is seeded (``testproblems.seed_batchnorm``).
 
-Reference sides, as ``test_pooled_stack_engine_gpu.py`` (whose replay helpers are imported): float64 autograd of the STOCK
-model on the engine's own ReLU and pooling decisions, and the fixture the real reference wrote
-(``tests/golden/convnet_convbn.npz``, ``make_golden_convbn.py``).  Bounds are that file's: 1e-6 (GGN) and 2e-6 (Hessian,
-gradient, logits, diagonal) against float64, 1e-5 against the reference's fp32 results."""
-
-import copy
-import warnings
+Reference sides (``stack_harness.py``): float64 autograd of the STOCK model on the engine's own ReLU and pooling
+decisions, and the fixture the real reference wrote (``tests/golden/convnet_convbn.npz``, ``make_golden_convbn.py``).
+Bounds are the project's: 1e-6 (GGN) and 2e-6 (Hessian, gradient, logits, diagonal) against float64, 1e-5 against the
+reference's fp32 results."""
 
 import pytest
 import torch
 from tol import within
 
-import pytorchhessianfree_amd as hf
 from helpers import RefTrace, compare_trace
-from pytorchhessianfree_amd import _lib, curvature, modelprep
+from pytorchhessianfree_amd import curvature, modelprep
 from pytorchhessianfree_amd import testproblems as tp
 from pytorchhessianfree_amd.engine import FusedGGNEngine, PlainStackEngine
-from test_pooled_stack_engine_gpu import _Net, _Recorder, _rel, _replay
+from stack_harness import (DEV, _Net, check_point, declined_net, diag64, engine, float64_twin, grad64, product64,
+                           record_launches, rel, run_steps)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 N_SMALL, N_FC = 1764, 1694  # parameters of convbn_small / convbn_fc_small
 # (make_golden_convbn.NETS: the reference's fp32 and float64 traces agree on these data seeds)
 STEPS = {"small": (tp.convbn_small, (41, 42, 43), 2), "fc": (tp.convbn_fc_small, (61, 62, 63), 5)}
 POOL_T, POOL_A = "hf_pool_bn_act_tangent_nhwc", "hf_pool_bn_act_adjoint_nhwc"
-
-
-def _engine(batch, hessian=False, prep=None, make=tp.convbn_small):
-    model, (x, t), lossf = make(batch_size=batch, device="cpu")
-    if prep is not None:
-        prep(model)
-    cpu_params = [p.detach().clone() for p in model.parameters() if p.requires_grad]
-    model, x, t = model.to(DEV), x.to(DEV), t.to(DEV)
-    modelprep.prepare_model(model, channels_last=True)
-    params = [p for p in model.parameters() if p.requires_grad]
-    out = model(x)
-    make_op = curvature.hessian_operator if hessian else curvature.ggn_operator
-    op = make_op(lossf(out, t), out, params)
-    return op, model, (x, t), lossf, cpu_params
-
-
-def _float64(batch, op, prep=None, make=tp.convbn_small):
-    """The float64 twin on the engine's decisions (the units' ReLU masks at full resolution, then the tail's, in call
-    order; the pool positions): (params, out, loss, t)."""
-    model, (x, t), lossf = make(batch_size=batch, device=DEV)
-    if prep is not None:
-        prep(model)
-    model, x = model.double(), x.double()
-    masks = [(u.y > 0) for u in op.units if u.relu] + [(u.y > 0) for u in op.classifier if u.act == 1]
-    pools = [u.pidx.permute(0, 3, 1, 2).long() for u in op.units if u.pool is not None]
-    _replay(model, masks, pools)
-    params = [p for p in model.parameters() if p.requires_grad]
-    out = model(x)
-    return params, out, lossf(out, t), t
-
-
-def _diag64(lossf, p64, out64, t64, batch, n):
-    """Per-sample float64 gradients on the same decisions (eval mode: the samples do not interact)."""
-    want = torch.zeros(n, dtype=torch.float64, device=DEV)
-    for i in range(batch):
-        g_i = torch.autograd.grad(lossf(out64[i:i + 1], t64[i:i + 1]), p64, retain_graph=True)
-        want += torch.cat([g.reshape(-1) for g in g_i]) ** 2
-    return want / batch
-
-
-def _check_point(op, family, batch, hessian, x, t, lossf, cpu_params, make):
-    """Product (bitwise repeatable, symmetric), gradient, logits, loss and diagonal of ``op`` against float64 on its own
-    decisions and against the fixture."""
-    ref = RefTrace("convbn", f"{family}/b{batch}")
-    ref.check_inputs(cpu_params, x.cpu())
-    rp = RefTrace("convbn", f"{family}/b{batch}/" + ("hessian" if hessian else "ggn"))
-    v = rp.probe().to(DEV)
-    got = op(v).clone()
-    for _ in range(3):
-        assert torch.equal(op(v), got)  # bitwise repeatable
-    p64, out64, loss64, t64 = _float64(batch, op, make=make)
-    want = (curvature.HessianOperator(loss64, p64) if hessian else curvature.GGNOperator(loss64, out64, p64))(v.double())
-    tight = 2e-6 if hessian else 1e-6
-    e = _rel(got, want)
-    print(f"{family}-b{batch}-{'hessian' if hessian else 'ggn'}: product vs float64 {e:.2e}, vs the reference's float64 "
-          f"{rp.vec_err64('', got):.2e}, fp32 {rp.vec_err('', got):.2e}")
-    within(e, tight)
-    within(rp.vec_err64("", got), tight)
-    within(rp.vec_err("", got), 1e-5)
-    u = torch.randn(op.n, device=DEV, generator=torch.Generator(device=DEV).manual_seed(4))
-    gu = op(u).clone()
-    a, b = float(u.double() @ got.double()), float(v.double() @ gu.double())
-    within(abs(a - b), 1e-5 * abs(a), strict=False)  # symmetric operator
-    grad64 = torch.cat([g.reshape(-1) for g in torch.autograd.grad(loss64, p64, retain_graph=True)])
-    grad = op.gradient().clone()
-    print(f"  gradient vs float64 {_rel(grad, grad64):.2e}, logits {_rel(op.logits, out64.detach()):.2e}")
-    within(_rel(grad, grad64), 2e-6)
-    within(ref.vec_err64("grad", grad), 2e-6)
-    within(ref.vec_err("grad", grad), 1e-5)
-    within(_rel(op.logits, out64.detach()), 2e-6)
-    within(_rel(op.logits.cpu(), torch.from_numpy(ref.array("logits"))), 1e-5)
-    within(abs(float(op.loss_buf) - float(loss64.detach())), 2e-6 * abs(float(loss64.detach())), strict=False)
-    within(abs(float(op.loss_buf) - ref.scalar("loss")), 1e-5 * abs(ref.scalar("loss")), strict=False)
-    want_d = _diag64(lossf, p64, out64, t64, batch, op.n)
-    got_d = op.diag_ef("mean").clone()
-    print(f"  diag_ef vs float64 {_rel(got_d, want_d):.2e}")
-    within(_rel(got_d, want_d), 2e-6)
-    within(ref.vec_err64("diag", got_d), 2e-6)
-    within(ref.vec_err("diag", got_d), 1e-5)
-    assert torch.equal(op.diag_ef("mean"), got_d)
-    assert torch.equal(op(v), got)  # (the products are untouched by the first-order sweeps)
 
 
 @pytest.mark.parametrize("batch", [2, 5])
@@ -119,27 +34,27 @@ def test_convbn_small_is_a_plain_stack_engine_and_matches_float64_and_the_refere
     """``curvature.ggn_operator`` / ``hessian_operator`` of prepared ``convbn_small`` IS a ``PlainStackEngine`` (without
     the BatchNorm units it is the autograd operator, "unsupported layer BatchNorm2d": this is the assertion that fails on
     the parent commit)."""
-    op, model, (x, t), lossf, cpu_params = _engine(batch, hessian)
+    op, model, (x, t), lossf, cpu_params = engine(tp.convbn_small, batch, hessian)
     assert isinstance(op, PlainStackEngine) and op.hessian == hessian
     assert [u.pool for u in op.units] == [(3, 3, 2, 2, 0, 0), None, (2, 2, 2, 2, 0, 0), None]
     assert [type(u.bn).__name__ for u in op.units] == ["BatchNorm2d"] * 3 + ["NoneType"]
     assert [u.relu for u in op.units] == [True, True, False, False]
     assert op.units[0].im2col and op.n == N_SMALL and not op.classifier
-    _check_point(op, "small", batch, hessian, x, t, lossf, cpu_params, tp.convbn_small)
+    check_point(op, tp.convbn_small, batch, x, lossf, cpu_params, ("convbn", f"small/b{batch}"), f"small-b{batch}")
 
 
 @pytest.mark.parametrize("batch", [2, 5])
 def test_convbn_fc_small_runs_the_tail_behind_pooled_batchnorm_units(batch):
-    op, model, (x, t), lossf, cpu_params = _engine(batch, make=tp.convbn_fc_small)
+    op, model, (x, t), lossf, cpu_params = engine(tp.convbn_fc_small, batch)
     assert isinstance(op, PlainStackEngine) and not op.hessian
     assert [u.pool for u in op.units] == [(3, 3, 2, 2, 0, 0), (2, 2, 2, 2, 0, 0)] and op.n == N_FC
     assert all(isinstance(u.bn, torch.nn.BatchNorm2d) and u.relu for u in op.units)
     assert [(u.c_in, u.c_out, u.act) for u in op.classifier] == [(32, 20, 1), (20, 10, 0)]
-    _check_point(op, "fc", batch, False, x, t, lossf, cpu_params, tp.convbn_fc_small)
+    check_point(op, tp.convbn_fc_small, batch, x, lossf, cpu_params, ("convbn", f"fc/b{batch}"), f"fc-b{batch}")
 
 
 def test_hessian_products_through_the_tail_stay_refused():
-    op, *_ = _engine(2, hessian=True, make=tp.convbn_fc_small)
+    op, *_ = engine(tp.convbn_fc_small, 2, hessian=True)
     assert type(op) is curvature.HessianOperator
     model, (x, t), lossf = tp.convbn_fc_small(batch_size=2, device=DEV)
     modelprep.prepare_model(model, channels_last=True)
@@ -154,11 +69,11 @@ def test_batched_diagonal_matches_float64_and_the_reference(family, batch, monke
     unscaled ``g``)."""
     monkeypatch.setenv("HF_DIAG_EF_BATCHED", "1")
     make = STEPS[family][0]
-    op, model, (x, t), lossf, _ = _engine(batch, make=make)
+    op, model, (x, t), lossf, _ = engine(make, batch)
     assert isinstance(op, PlainStackEngine) and op._diag_batched
     got_d = op.diag_ef("mean").clone()
-    p64, out64, _loss64, t64 = _float64(batch, op, make=make)
-    within(_rel(got_d, _diag64(lossf, p64, out64, t64, batch, op.n)), 2e-6)
+    p64, out64, _loss64, t64 = float64_twin(make, batch, op)
+    within(rel(got_d, diag64(lossf, p64, out64, t64, batch, op.n)), 2e-6)
     ref = RefTrace("convbn", f"{family}/b{batch}")
     within(ref.vec_err64("diag", got_d), 2e-6)
     within(ref.vec_err("diag", got_d), 1e-5)
@@ -172,10 +87,8 @@ def test_a_pooled_batchnorm_unit_costs_four_launches_per_product(defer, monkeypa
     BatchNorm or bias -- and the head's one.  The first unit's map is large enough for its sums to leave the chain
     (``HF_BN_SUMS_DEFER``, the default): one ``hf_bn_sums_multi`` launch in front of the gather; switched off, none."""
     monkeypatch.setenv("HF_BN_SUMS_DEFER", defer)
-    names = []
-    proxy = _Recorder(_lib.load(), names)
-    monkeypatch.setattr(_lib, "load", lambda: proxy)
-    op, *_ = _engine(2)
+    names = record_launches(monkeypatch)
+    op, *_ = engine(tp.convbn_small, 2)
     assert isinstance(op, PlainStackEngine) and names
     assert [u.defer for u in op.units] == [defer == "1", False, False, False]
     v = torch.randn(op.n, device=DEV, generator=torch.Generator(device=DEV).manual_seed(6))
@@ -217,7 +130,7 @@ def test_frozen_parameters(prep, hessian):
     """The pooled first unit frozen (convolution, scale and shift: dead for both sweeps), and every BatchNorm's scale
     frozen (no ``v_w`` term, no scale sums; the shifts stay trainable): products, gradient and diagonal on the trainable
     subset against float64, the frozen tensors untouched."""
-    op, model, (x, t), lossf, _ = _engine(2, hessian, prep=prep)
+    op, model, (x, t), lossf, _ = engine(tp.convbn_small, 2, hessian, prep=prep)
     assert isinstance(op, PlainStackEngine)
     if prep is _freeze_first_unit:
         assert op.dead_units == 1 and op.n == N_SMALL - (8 * 27 + 16)
@@ -228,12 +141,10 @@ def test_frozen_parameters(prep, hessian):
     v = torch.randn(op.n, device=DEV, generator=torch.Generator(device=DEV).manual_seed(8))
     got = op(v).clone()
     assert torch.equal(op(v), got)
-    p64, out64, loss64, t64 = _float64(2, op, prep=prep)
-    want = (curvature.HessianOperator(loss64, p64) if hessian else curvature.GGNOperator(loss64, out64, p64))(v.double())
-    within(_rel(got, want), 2e-6 if hessian else 1e-6)
-    grad64 = torch.cat([g.reshape(-1) for g in torch.autograd.grad(loss64, p64, retain_graph=True)])
-    within(_rel(op.gradient(), grad64), 2e-6)
-    within(_rel(op.diag_ef("mean"), _diag64(lossf, p64, out64, t64, 2, op.n)), 2e-6)
+    p64, out64, loss64, t64 = float64_twin(tp.convbn_small, 2, op, prep=prep)
+    within(rel(got, product64(p64, out64, loss64, v, hessian)), 2e-6 if hessian else 1e-6)
+    within(rel(op.gradient(), grad64(loss64, p64)), 2e-6)
+    within(rel(op.diag_ef("mean"), diag64(lossf, p64, out64, t64, 2, op.n)), 2e-6)
     assert all(torch.equal(a, b.detach()) and b.grad is None for a, b in zip(before, frozen))
 
 
@@ -243,24 +154,7 @@ def test_three_default_steps_through_the_session_match_the_reference_trace(famil
     pool launches, loss head, gradient sweep, graphed products); the three-step trace against the real reference's at
     ``compare_trace``'s defaults."""
     make, seeds, batch = STEPS[family]
-    ref = RefTrace("convbn", f"{family}/steps")
-    model, _, lossf = make(batch_size=batch, device="cpu", data_seed=seeds[0])
-    ref.check_inputs([p for p in model.parameters() if p.requires_grad])
-    model = model.to(DEV)
-    modelprep.prepare_model(model, channels_last=True)
-    opt = hf.HessianFree(model.parameters(), graph_matvec=True)
-    finals = []
-    for i in range(3):
-        _, (x, t), _ = make(batch_size=batch, device="cpu", data_seed=seeds[i])
-        ref.check_inputs(x=x, step=i)
-        x, t = x.to(DEV), t.to(DEV)
-
-        def forward():
-            out = model(x)
-            return lossf(out, t), out
-
-        finals.append(opt.step(forward))
-        assert opt.path_report()["step"]["path"] == "session", opt.path_report()
+    opt, finals, _, ref = run_steps(make, seeds, batch, ("convbn", f"{family}/steps"), graph_matvec=True)
     assert opt._session is not None and opt._session.steps == 3
     assert isinstance(opt._session.engine, PlainStackEngine)
     compare_trace(opt.state, finals, ref)
@@ -288,34 +182,4 @@ def _declined_variants():
 @pytest.mark.parametrize("name", sorted(_declined_variants()))
 def test_declined_variants_keep_the_autograd_path_and_say_why(name):
     build, reason = _declined_variants()[name]
-    torch.manual_seed(0)
-    model = tp.seed_batchnorm(build()).eval()
-    gen = torch.Generator().manual_seed(1)
-    x, t = torch.rand(2, 3, 8, 8, generator=gen), torch.randint(0, 4, (2,), generator=gen)
-    m64 = copy.deepcopy(model).double().to(DEV)
-    model, x, t = model.to(DEV), x.to(DEV), t.to(DEV)
-    modelprep.prepare_model(model, channels_last=True)
-    lossf = torch.nn.CrossEntropyLoss()
-    params = list(model.parameters())
-    out = model(x)
-    why = []
-    assert FusedGGNEngine.try_build(lossf(out, t), out, params, why=why) is None
-    assert any(reason in w for w in why), why
-    out = model(x)
-    op = curvature.ggn_operator(lossf(out, t), out, params)
-    assert type(op) is curvature.GGNOperator
-    v = torch.randn(op.n, device=DEV, generator=torch.Generator(device=DEV).manual_seed(2))
-    out64 = m64(x.double())
-    want = curvature.GGNOperator(lossf(out64, t), out64, list(m64.parameters()))(v.double())
-    within(_rel(op(v), want), 1e-6)
-    opt = hf.HessianFree(model.parameters(), cg_max_iter=3)
-
-    def forward():
-        o = model(x)
-        return lossf(o, t), o
-
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        opt.step(forward)
-    rep = opt.path_report()["step"]
-    assert rep["path"] == "eager" and reason in rep["declined"], rep
+    declined_net(lambda: tp.seed_batchnorm(build()), reason)

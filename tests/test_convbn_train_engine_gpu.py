@@ -5,7 +5,7 @@ launches, a pooled one on ``hf_pool_bn_act_tangent_train_nhwc``) and in the two-
 ``convbn_fc_small`` after ``model.train()``.
 
 Reference sides: float64 autograd of the STOCK train-mode model on the engine's own ReLU and pooling decisions (the replay
-helpers of ``test_pooled_stack_engine_gpu.py``), and the fixture the real reference wrote in train mode
+of ``stack_harness.py``), and the fixture the real reference wrote in train mode
 (``tests/golden/convnet_convbn_train.npz``, ``make_golden_convbn_train.py``).
 
 The float64 bounds are 3x the worst figure of this package's STOCK fp32 autograd operator (``curvature.GGNOperator`` /
@@ -22,13 +22,12 @@ from tol import within
 
 import pytorchhessianfree_amd as hf
 from helpers import RefTrace, compare_trace
-from pytorchhessianfree_amd import _lib, curvature, modelprep
+from pytorchhessianfree_amd import curvature, modelprep
 from pytorchhessianfree_amd import testproblems as tp
 from pytorchhessianfree_amd.engine import FusedGGNEngine, PlainStackEngine
-from test_pooled_stack_engine_gpu import _Net, _Recorder, _rel, _replay
+from stack_harness import DEV, _Net, declined, engine, float64_twin, grad64, product64, record_launches, rel, run_steps
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 N_SMALL, N_FC = 1764, 1694
 # 3x the worst stock_fp32 figure per quantity of profiles/r30_convbn_train.jsonl, one significant digit, rounded up
 # (stock: ggn 1.31e-6, hessian 9.9e-7, grad 5.2e-7, logits 5.8e-7, loss 7.9e-8; the engine's own worst figures there:
@@ -73,38 +72,9 @@ MIXED = [("small", 2, h, prep) for prep in (_one_eval, _one_train, _one_train_fi
          for h in (False, True)]
 
 
-def _prepare(model, prep):
-    model.train()
-    if prep is not None:
-        prep(model)
-    return model
-
-
 def _engine(family, batch, hessian=False, prep=None):
-    make = STEPS[family][0]
-    model, (x, t), lossf = make(batch_size=batch, device="cpu")
-    _prepare(model, prep)
-    cpu_params = [p.detach().clone() for p in model.parameters() if p.requires_grad]
-    model, x, t = model.to(DEV), x.to(DEV), t.to(DEV)
-    modelprep.prepare_model(model, channels_last=True)
-    params = [p for p in model.parameters() if p.requires_grad]
-    out = model(x)
-    make_op = curvature.hessian_operator if hessian else curvature.ggn_operator
-    op = make_op(lossf(out, t), out, params)
-    return op, model, (x, t), lossf, cpu_params
-
-
-def _float64(family, batch, op, prep=None):
-    """The float64 twin in the same modes on the engine's decisions: (params, out, loss)."""
-    model, (x, t), lossf = STEPS[family][0](batch_size=batch, device=DEV)
-    _prepare(model, prep)
-    model, x = model.double(), x.double()
-    masks = [(u.y > 0) for u in op.units if u.relu] + [(u.y > 0) for u in op.classifier if u.act == 1]
-    pools = [u.pidx.permute(0, 3, 1, 2).long() for u in op.units if u.pool is not None]
-    _replay(model, masks, pools)
-    params = [p for p in model.parameters() if p.requires_grad]
-    out = model(x)
-    return params, out, lossf(out, t)
+    """``model.train()`` first, ``prep`` then (the float64 twin of ``measure`` in the same modes)."""
+    return engine(STEPS[family][0], batch, hessian, prep, train=True)
 
 
 def measure(family, batch, hessian, prep, stock=False):
@@ -114,9 +84,8 @@ def measure(family, batch, hessian, prep, stock=False):
     op, model, (x, t), lossf, _ = _engine(family, batch, hessian, prep)
     assert isinstance(op, PlainStackEngine)
     v = torch.randn(op.n, device=DEV, generator=torch.Generator(device=DEV).manual_seed(8))
-    p64, out64, loss64 = _float64(family, batch, op, prep)
-    want = (curvature.HessianOperator(loss64, p64) if hessian else curvature.GGNOperator(loss64, out64, p64))(v.double())
-    grad64 = torch.cat([g.reshape(-1) for g in torch.autograd.grad(loss64, p64, retain_graph=True)])
+    p64, out64, loss64, _ = float64_twin(STEPS[family][0], batch, op, prep, train=True)
+    want, want_grad = product64(p64, out64, loss64, v, hessian), grad64(loss64, p64)
     if stock:
         params = [p for p in model.parameters() if p.requires_grad]
         out = model(x)
@@ -127,8 +96,8 @@ def measure(family, batch, hessian, prep, stock=False):
     else:
         got, grad, logits, lossv = op(v).clone(), op.gradient().clone(), op.logits, float(op.loss_buf)
     l64 = float(loss64.detach())
-    return {"hessian" if hessian else "ggn": _rel(got, want), "grad": _rel(grad, grad64),
-            "logits": _rel(logits, out64.detach()), "loss": abs(lossv - l64) / abs(l64)}, op
+    return {"hessian" if hessian else "ggn": rel(got, want), "grad": rel(grad, want_grad),
+            "logits": rel(logits, out64.detach()), "loss": abs(lossv - l64) / abs(l64)}, op
 
 
 def _check_float64(family, batch, hessian, prep):
@@ -160,9 +129,9 @@ def _check_fixture(op, family, batch, hessian, x, cpu_params):
     grad = op.gradient().clone()
     within(ref.vec_err64("grad", grad), BOUND["grad"])
     within(ref.vec_err("grad", grad), ref.envelope("grad", BOUND["grad"]))
-    within(_rel(op.logits.cpu(), torch.from_numpy(ref.array("logits_f64"))), BOUND["logits"])
-    own = _rel(torch.from_numpy(ref.array("logits")), torch.from_numpy(ref.array("logits_f64")))
-    within(_rel(op.logits.cpu(), torch.from_numpy(ref.array("logits"))), BOUND["logits"] + 3 * own)
+    within(rel(op.logits.cpu(), torch.from_numpy(ref.array("logits_f64"))), BOUND["logits"])
+    own = rel(torch.from_numpy(ref.array("logits")), torch.from_numpy(ref.array("logits_f64")))
+    within(rel(op.logits.cpu(), torch.from_numpy(ref.array("logits"))), BOUND["logits"] + 3 * own)
     l64 = ref.scalar("loss_f64")
     within(abs(float(op.loss_buf) - l64), BOUND["loss"] * abs(l64), strict=False)
     within(abs(float(op.loss_buf) - ref.scalar("loss")), BOUND["loss"] * abs(l64) + 3 * abs(ref.scalar("loss") - l64),
@@ -207,9 +176,7 @@ def test_launches_per_ggn_product(monkeypatch):
     ``hf_pool_bn_act_tangent_train_nhwc``; ONE ``hf_pool_bn_act_adjoint_reduce_nhwc``, ONE ``hf_chan_affine_train``, the
     convolution's gradients -- 5 or 6, as an unpooled train unit; the bias unit 4 as before.  None of the eval-mode pooled
     launches, none of the stem's max-pool launches."""
-    names = []
-    proxy = _Recorder(_lib.load(), names)
-    monkeypatch.setattr(_lib, "load", lambda: proxy)
+    names = record_launches(monkeypatch)
     op, *_ = _engine("small", 2)
     assert isinstance(op, PlainStackEngine) and op.train_bn and names
     v = torch.randn(op.n, device=DEV, generator=torch.Generator(device=DEV).manual_seed(6))
@@ -265,32 +232,11 @@ def test_mixed_modes_and_frozen_parameters(prep, hessian):
 
 def _run_steps(family, session):
     make, batch = STEPS[family]
-    ref = RefTrace("convbn_train", f"{family}/steps")
-    seeds = [int(s) for s in ref.array("seeds")]
-    model, _, lossf = make(batch_size=batch, device="cpu", data_seed=seeds[0])
-    model.train()
-    ref.check_inputs([p for p in model.parameters() if p.requires_grad])
-    model = model.to(DEV)
-    modelprep.prepare_model(model, channels_last=True)
-    opt = hf.HessianFree(model.parameters(), graph_matvec=True)
-    if not session:
-        opt._session_off = True
-    finals = []
-    for i in range(3):
-        _, (x, t), _ = make(batch_size=batch, device="cpu", data_seed=seeds[i])
-        ref.check_inputs(x=x, step=i)
-        x, t = x.to(DEV), t.to(DEV)
-
-        def forward():
-            out = model(x)
-            return lossf(out, t), out
-
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            finals.append(opt.step(forward))
-        if session:
-            assert opt.path_report()["step"]["path"] == "session", opt.path_report()
-    return opt, finals, model, ref
+    fixture = ("convbn_train", f"{family}/steps")
+    seeds = [int(s) for s in RefTrace(*fixture).array("seeds")]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        return run_steps(make, seeds, batch, fixture, train=True, session=session, graph_matvec=True)
 
 
 @pytest.mark.parametrize("family", sorted(STEPS))
@@ -313,7 +259,7 @@ def test_three_default_steps_through_the_session_match_the_reference_trace_and_t
     # in test_own_forward_moves_the_running_statistics_as_the_stock_layers_do
     for x, y in zip(_bns(ma), _bns(mb)):
         print(f"  num_batches_tracked session {int(x.num_batches_tracked)} autograd path {int(y.num_batches_tracked)}, "
-              f"running_mean {_rel(x.running_mean, y.running_mean):.1e} running_var {_rel(x.running_var, y.running_var):.1e}")
+              f"running_mean {rel(x.running_mean, y.running_mean):.1e} running_var {rel(x.running_var, y.running_var):.1e}")
         for m in (x, y):
             assert int(m.num_batches_tracked) > 3 and float(m.running_mean.abs().max()) > 0
             assert bool(torch.isfinite(m.running_var).all()) and float(m.running_var.min()) > 0
@@ -338,41 +284,21 @@ def test_own_forward_moves_the_running_statistics_as_the_stock_layers_do(family)
     assert all(torch.equal(a, b) for now, was in zip(state(), saved) for a, b in zip(now, was))
     op.forward_own(update_running=True)
     for m, (rm, rv, nb), (_, _, nb0) in zip(bns, stock, saved):
-        within(_rel(m.running_mean, rm), 1e-6)
-        within(_rel(m.running_var, rv), 5e-6)
+        within(rel(m.running_mean, rm), 1e-6)
+        within(rel(m.running_var, rv), 5e-6)
         assert int(m.num_batches_tracked) == int(nb) == int(nb0) + 1
-
-
-def _declined(model, x, t, reason, group=None):
-    lossf = torch.nn.CrossEntropyLoss()
-    model, x, t = model.to(DEV), x.to(DEV), t.to(DEV)
-    modelprep.prepare_model(model, channels_last=True)
-    params = list(model.parameters())
-    out = model(x)
-    why = []
-    assert FusedGGNEngine.try_build(lossf(out, t), out, params, group=group, why=why) is None
-    assert any(reason in w for w in why), why
-    return model, x, t, lossf
 
 
 def test_an_active_dropout_keeps_the_autograd_path_and_is_named():
     C, B, R, D, G = torch.nn.Conv2d, torch.nn.BatchNorm2d, torch.nn.ReLU, torch.nn.Dropout, torch.nn.AdaptiveAvgPool2d
     torch.manual_seed(0)
     gen = torch.Generator().manual_seed(1)
-    x, t = torch.rand(2, 3, 8, 8, generator=gen), torch.randint(0, 4, (2,), generator=gen)
+    x, t = torch.rand(2, 3, 8, 8, generator=gen).to(DEV), torch.randint(0, 4, (2,), generator=gen).to(DEV)
     build = lambda p: tp.seed_batchnorm(_Net([C(3, 8, 3, 1, 1, bias=False), B(8), R(), D(p), C(8, 4, 1), G(1)])).train()  # noqa: E731
-    model, x, t, lossf = _declined(build(0.5), x, t, "Dropout(p=0.5) behind conv0 is active")
-    opt = hf.HessianFree(model.parameters(), cg_max_iter=3)
-
-    def forward():
-        o = model(x)
-        return lossf(o, t), o
-
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        opt.step(forward)
-    rep = opt.path_report()["step"]
-    assert rep["path"] == "eager" and "Dropout(p=0.5) behind conv0 is active" in rep["declined"], rep
+    lossf = torch.nn.CrossEntropyLoss()
+    model = build(0.5).to(DEV)
+    modelprep.prepare_model(model, channels_last=True)
+    declined(model, x, t, lossf, "Dropout(p=0.5) behind conv0 is active")
     # p = 0, or the module in eval mode inside the train-mode model: skipped as before
     for variant in (build(0.0), build(0.5)):
         for m in variant.modules():

@@ -4,9 +4,10 @@ products are captured into hipGraphs: the sequence IS the graph, and the docstri
 most 4 launches per live layer" are read off it.
 
 ``_lib.load`` is replaced by a function that returns a proxy around the real library; the proxy forwards every call and
-notes the name of every ``hf_*`` function called.  Recording starts after the engine is built.
+notes the name of every ``hf_*`` function called (``stack_harness.record_launches``).  Recording starts after the engine
+is built.
 
-Nets: ``Linear(7,5) ReLU Linear(5,5) Tanh Linear(5,3)``, 3 rows, seeded on the CPU, a mean cross-entropy unless stated:
+Nets (``engine_nets.net_and_loss``): ``Linear(7,5) ReLU Linear(5,5) Tanh Linear(5,3)``, 3 rows, seeded on the CPU, a mean cross-entropy unless stated:
 A all trainable; B layer 0 frozen (dead, layer 1 is the first live one); C layer 1's weight frozen, its bias trainable;
 D layer 0's weight frozen, its bias trainable (the first live layer carries only a bias tangent); E net A with a mean
 MSE.  Each as a GGN engine, a Hessian engine (``HF_DENSE_HESSIAN=1``) and a GGN engine in session mode
@@ -25,21 +26,17 @@ input tangent; ``hf_dense_sq_wgrad`` in ``diag_ef``; none in ``gradient()`` with
 import pytest
 import torch
 
-from pytorchhessianfree_amd import _lib, modelprep
+from engine_nets import DEV, DENSE_FROZEN as FROZEN, net_and_loss
 from pytorchhessianfree_amd.engine import FusedGGNEngine
 from pytorchhessianfree_amd.engine.dense import DenseStackEngine
+from stack_harness import record_launches
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-ROWS = 3
 
 SHORT = {"T": "hf_dense_tangent_slabs", "AT": "hf_dense_act_tangent", "ce": "hf_softmax_ce_hvp",
          "aa": "hf_dense_act_adjoint", "aa2": "hf_dense_act_adjoint2", "w": "hf_dense_wgrad", "w2": "hf_dense_wgrad2",
          "d": "hf_dense_dgrad_slabs", "d2": "hf_dense_dgrad2_slabs", "sqw": "hf_dense_sq_wgrad",
          "sqc": "hf_dense_sq_colsum", "af": "hf_dense_act_forward", "lh": "hf_dense_loss_head"}
-
-# frozen parameters per net as (index in the Sequential, attribute)
-FROZEN = {"A": (), "B": ((0, "weight"), (0, "bias")), "C": ((2, "weight"),), "D": ((0, "weight"),), "E": ()}
 
 # local: the product of a GGN / a Hessian engine; grad_out, grad: gradient(out) / gradient() of a Hessian engine (keeps
 # h_l of the tanh layer) and of a session-mode GGN engine; diag, forward: the same for every kind (session mode appends
@@ -80,51 +77,12 @@ def names_of(text):
     return [name for group in layers_of(text) for name in group]
 
 
-class Recorder:
-    """Forwards every attribute to the real library; a call of an ``hf_*`` function appends its name to ``names``."""
-
-    def __init__(self, lib, names):
-        self._lib, self._names = lib, names
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if not name.startswith("hf_"):
-            return fn
-
-        def call(*args):
-            self._names.append(name)
-            return fn(*args)
-
-        return call
-
-
-def net_and_loss(net):
-    """(prepared model, its outputs, the loss) of net ``net`` on the GPU, seeded on the CPU."""
-    torch.manual_seed(0)
-    model = torch.nn.Sequential(torch.nn.Linear(7, 5), torch.nn.ReLU(), torch.nn.Linear(5, 5), torch.nn.Tanh(),
-                                torch.nn.Linear(5, 3))
-    for index, attr in FROZEN[net]:
-        getattr(model[index], attr).requires_grad = False
-    gen = torch.Generator().manual_seed(1)
-    x = torch.randn(ROWS, 7, generator=gen).to(DEV)
-    if net == "E":
-        t, lossf = torch.randn(ROWS, 3, generator=gen).to(DEV), torch.nn.MSELoss()
-    else:
-        t, lossf = torch.randint(0, 3, (ROWS,), generator=gen).to(DEV), torch.nn.CrossEntropyLoss()
-    model = model.to(DEV)
-    modelprep.prepare_model(model)
-    out = model(x)
-    return model, out, lossf(out, t)
-
-
 def build(net, kind, monkeypatch):
     """(engine, the list its launches are recorded in) of net ``net`` as a ``ggn`` / ``hessian`` / ``session`` engine."""
     monkeypatch.setenv("HF_DENSE_ENGINE", "1")
     monkeypatch.setenv("HF_DENSE_HESSIAN", "1" if kind == "hessian" else "0")
     monkeypatch.setenv("HF_DENSE_SESSION", "1" if kind == "session" else "0")
-    names = []
-    proxy = Recorder(_lib.load(), names)
-    monkeypatch.setattr(_lib, "load", lambda: proxy)
+    names = record_launches(monkeypatch)
     model, out, loss = net_and_loss(net)
     why = []
     eng = FusedGGNEngine.try_build(loss, out, [p for p in model.parameters() if p.requires_grad],

@@ -30,11 +30,10 @@ import pytest
 import torch
 from torch.utils._python_dispatch import TorchDispatchMode
 
-from engine_nets import DEV, build, build_plain
+from engine_nets import DEV, build, build_plain, net_and_loss
 from pytorchhessianfree_amd import _lib, curvature, modelprep
 from pytorchhessianfree_amd import testproblems as tp
 from pytorchhessianfree_amd.engine import FusedGGNEngine
-from test_dense_launch_order_gpu import net_and_loss
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "engine_launch_sequence.json.gz")
