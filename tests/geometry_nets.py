@@ -19,6 +19,11 @@ summed data-gradient slabs, tail tensors off the 16-byte grid of the flat vector
 pooled non-square last map, batch 1 and 256 (``TAIL_GEOMETRY`` says which case reaches what).  Same seeding; kept apart
 from ``CASES`` (GGN products only, bounds of their own).
 
+``BN_CASES``: six plain stacks with BatchNorm units (``BN_STACKS``; five end in the global average pool, one in a
+classifier tail), eval and train mode, on per-axis windows / strides / paddings, dead taps, many row blocks, one-row /
+one-column / 1x1 maps (``BN_GEOMETRY`` says which case reaches what).  Same seeding and BatchNorm state as the ResNets;
+kept apart from ``CASES`` (bounds of their own).
+
 The reference (``Reference``): float64 autograd of a deep copy of the STOCK model on the CPU -- loss, gradient, GGN
 product (``curvature.GGNOperator``), Hessian product (``curvature.HessianOperator``), diagonal empirical Fisher by
 per-sample gradients --, optionally on replayed ReLU decisions and max-pool positions (``_replay_relu_decisions``,
@@ -86,6 +91,44 @@ TAILS = {
         nn.Flatten(), nn.Linear(24, 40), nn.ReLU(), nn.Linear(40, 6)]),
 }
 TAIL_CASES = list(TAILS)
+
+
+def _C(cin, cout, k, s=1, p=0):
+    return nn.Conv2d(cin, cout, k, s, p, bias=False)
+
+
+# Plain stacks with BatchNorm units (``Conv2d(bias=False) BatchNorm2d [ReLU] [MaxPool2d]``; BatchNorm state as the
+# ResNets'), in eval and in train mode: per-axis windows, strides and paddings behind a BatchNorm, a pooled unit without
+# ReLU, dead kernel taps, many row blocks in the pooled adjoint, one-row / one-column / 1x1 maps, batch statistics over
+# 15 rows, a first unit that is not im2col'd, pooled BatchNorm units in front of a classifier tail -- what each reaches
+# stands with its literals in ``BN_GEOMETRY``.  ``bn_row_map`` is ``bn_col_map``'s transpose.
+BN_STACKS = {
+    "bn_rect_pooled": dict(x=(3, 3, 7, 10), classes=12, layers=lambda: [
+        _C(3, 8, (1, 3), 1, (0, 1)), nn.BatchNorm2d(8), nn.ReLU(), nn.MaxPool2d((3, 2), (2, 1), (1, 0)),
+        _C(8, 12, (3, 1), (2, 1), (1, 0)), nn.BatchNorm2d(12), nn.MaxPool2d((1, 2), (1, 2)),
+        _C(12, 20, 3, 1, 1), nn.BatchNorm2d(20), nn.ReLU(), nn.Conv2d(20, 12, 1), nn.AdaptiveAvgPool2d((1, 1))]),
+    "bn_col_map": dict(x=(5, 1, 12, 1), classes=8, layers=lambda: [
+        _C(1, 8, 3, 1, 1), nn.BatchNorm2d(8), nn.ReLU(), nn.MaxPool2d((2, 1), (2, 1)),
+        _C(8, 8, 3, (2, 1), 1), nn.BatchNorm2d(8), nn.ReLU(), nn.Conv2d(8, 8, 1), nn.AdaptiveAvgPool2d((1, 1))]),
+    "bn_row_map": dict(x=(5, 1, 1, 12), classes=8, layers=lambda: [
+        _C(1, 8, 3, 1, 1), nn.BatchNorm2d(8), nn.ReLU(), nn.MaxPool2d((1, 2), (1, 2)),
+        _C(8, 8, 3, (1, 2), 1), nn.BatchNorm2d(8), nn.ReLU(), nn.Conv2d(8, 8, 1), nn.AdaptiveAvgPool2d((1, 1))]),
+    "bn_wide_rows": dict(x=(4, 1, 12, 10), classes=16, layers=lambda: [
+        _C(1, 132, 3, 1, 1), nn.BatchNorm2d(132), nn.ReLU(), nn.MaxPool2d(3, 2, 1),
+        _C(132, 260, 3, 1, 1), nn.BatchNorm2d(260), nn.ReLU(), nn.MaxPool2d((2, 3), (2, 2), (0, 1)),
+        nn.Conv2d(260, 16, 1), nn.AdaptiveAvgPool2d((1, 1))]),
+    "bn_pixel_one": dict(x=(1, 4, 4, 4), classes=8, layers=lambda: [
+        _C(4, 8, 3, 1, 1), nn.BatchNorm2d(8), nn.ReLU(), nn.MaxPool2d(2, 2),
+        _C(8, 16, 2), nn.BatchNorm2d(16), nn.ReLU(), nn.Conv2d(16, 8, 1), nn.AdaptiveAvgPool2d((1, 1))]),
+    "bn_tail_rect": dict(x=(3, 3, 9, 7), classes=7, layers=lambda: [
+        _C(3, 8, 3, 1, 1), nn.BatchNorm2d(8), nn.ReLU(), nn.MaxPool2d((2, 3), (2, 2), (0, 1)),
+        _C(8, 12, (3, 1), 1, (1, 0)), nn.BatchNorm2d(12), nn.MaxPool2d((2, 1), (2, 1)),
+        nn.Flatten(), nn.Linear(96, 21), nn.ReLU(), nn.Linear(21, 7)]),
+}
+BN_CASES = list(BN_STACKS)
+BN_TRAIN_CASES = [c for c in BN_CASES if c != "bn_pixel_one"]  # (a 1x1 map of ONE sample has no batch statistics)
+BN_HESSIAN_CASES = [c for c in BN_CASES if c != "bn_tail_rect"]  # (no Hessian products through a classifier tail)
+BN_CAPTURED_CASES = [("bn_rect_pooled", True), ("bn_wide_rows", False)]  # (case, train mode)
 
 # per convolution in call order: (module, input map, output map, live-tap mask (0: all live), row blocks of the adjoint)
 GEOMETRY = {
@@ -197,11 +240,49 @@ TAIL_GEOMETRY = {
         linears=[(24, 40, 1, 2, 664, 1624), (40, 6, 2, 1, 1664, 1904)],
         last=(4, 3, 8), pools=[(2, 1, 2, 1, 0, 0), None], n=1910),
 }
+# per BatchNorm-stack case -- "convs", per convolution in call order: (module, input map, output map, live-tap mask, row
+# blocks of the adjoint (``adjoint_row_blocks``), pool (kh, kw, sh, sw, ph, pw) or None, pooled map or None); "im2col":
+# whether the first unit is im2col'd (fewer than 4 input channels); "n": entries of the flat vector
+BN_GEOMETRY = {
+    # every pair of axis parameters unequal (kernels 1x3 / 3x1, stride (2,1), paddings (0,1) / (1,0), pools 3x2 by (2,1)
+    # padded (1,0) and 1x2 by (1,2)); a padded pool; a pooled unit WITHOUT ReLU; an im2col'd pooled first unit, rb = 2
+    "bn_rect_pooled": dict(convs=[
+        ("net.0", (7, 10), (7, 10), 0, 2, (3, 2, 2, 1, 1, 0), (4, 9)),
+        ("net.4", (4, 9), (2, 9), 0, 1, (1, 2, 1, 2, 0, 0), (2, 4)),
+        ("net.7", (2, 4), (2, 4), 0, 1, None, None),
+        ("net.10", (2, 4), (2, 4), 0, 1, None, None)], im2col=True, n=2852),
+    # a one-column map: kernel columns 0 and 2 meet only padding (0b010010010) under a BatchNorm; the second unit's
+    # train-mode statistics run over 5 x 3 x 1 = 15 rows
+    "bn_col_map": dict(convs=[
+        ("net.0", (12, 1), (12, 1), 146, 1, (2, 1, 2, 1, 0, 0), (6, 1)),
+        ("net.4", (6, 1), (3, 1), 146, 1, None, None),
+        ("net.7", (3, 1), (3, 1), 0, 1, None, None)], im2col=True, n=752),
+    # its transpose: kernel rows 0 and 2 (0b000111000)
+    "bn_row_map": dict(convs=[
+        ("net.0", (1, 12), (1, 12), 56, 1, (1, 2, 1, 2, 0, 0), (1, 6)),
+        ("net.4", (1, 6), (1, 3), 56, 1, None, None),
+        ("net.7", (1, 3), (1, 3), 0, 1, None, None)], im2col=True, n=752),
+    # the pooled adjoint with 60 row blocks (480 rows in shares of 8, 33 channel quads) and 40 (120 rows in shares of 3,
+    # 65 quads); a pool padded (0, 1)
+    "bn_wide_rows": dict(convs=[
+        ("net.0", (12, 10), (12, 10), 0, 60, (3, 3, 2, 2, 1, 1), (6, 5)),
+        ("net.4", (6, 5), (6, 5), 0, 40, (2, 3, 2, 2, 0, 1), (3, 3)),
+        ("net.8", (3, 3), (3, 3), 0, 1, None, None)], im2col=True, n=315028),
+    # batch 1, a 1x1 map behind the second unit, four input channels: the first unit is not im2col'd (eval mode only)
+    "bn_pixel_one": dict(convs=[
+        ("net.0", (4, 4), (4, 4), 0, 1, (2, 2, 2, 2, 0, 0), (2, 2)),
+        ("net.4", (2, 2), (1, 1), 0, 1, None, None),
+        ("net.7", (1, 1), (1, 1), 0, 1, None, None)], im2col=False, n=984),
+    # pooled BatchNorm units (the second without ReLU) in front of a classifier tail; the last map 2x4 (GGN only)
+    "bn_tail_rect": dict(convs=[
+        ("net.0", (9, 7), (9, 7), 0, 2, (2, 3, 2, 2, 0, 1), (4, 4)),
+        ("net.4", (4, 4), (4, 4), 0, 1, (2, 1, 2, 1, 0, 0), (2, 4))], im2col=True, n=2735),
+}
 TAIL_CAPTURED_CASES = ["tail_wide_first", "tail_rect_pooled"]
 FLATTEN_TILE = 32  # (hf_head.hip: the flatten kernels move 32 x 32 tiles of the [hw, c] plane of one sample)
 
 TRAIN_CASES = ["nonsquare_odd", "row_map", "col_map", "wide_rows", "stem7"]  # (batch_one: a 1x1 map of ONE sample has no
-COMPACT_CASES = ["row_map", "col_map", "batch_one"]                           # batch statistics; plain stacks: no BatchNorm)
+COMPACT_CASES = ["row_map", "col_map", "batch_one"]                           # batch statistics; ``STACKS``: no BatchNorm)
 CAPTURED_CASES = ["asym_stride", "plain_rect"]
 
 
@@ -249,20 +330,23 @@ def make(case, train=False):
     if case in TAILS:
         spec = TAILS[case]
         model = GeometryTail(spec["layers"]())
+    elif case in BN_STACKS:
+        spec = BN_STACKS[case]
+        model = (GeometryTail if case == "bn_tail_rect" else GeometryStack)(spec["layers"]())
     elif case in RESNETS:
         spec = RESNETS[case]
         model = GeometryResNet(spec["x"][1], spec["stem"], spec["pool"], spec["blocks"], spec["classes"])
-        with torch.no_grad():
-            for m in model.modules():  # (statistics and scales away from their trivial initial values)
-                if isinstance(m, nn.BatchNorm2d):
-                    m.running_mean.uniform_(-0.2, 0.2)
-                    m.running_var.uniform_(0.7, 1.4)
-                    m.weight.uniform_(0.6, 1.3)
-                    m.bias.uniform_(-0.2, 0.2)
-                    m.eps = 0.1
     else:
         spec = STACKS[case]
         model = GeometryStack(spec["layers"]())
+    with torch.no_grad():
+        for m in model.modules():  # (statistics and scales away from their trivial initial values)
+            if isinstance(m, nn.BatchNorm2d):
+                m.running_mean.uniform_(-0.2, 0.2)
+                m.running_var.uniform_(0.7, 1.4)
+                m.weight.uniform_(0.6, 1.3)
+                m.bias.uniform_(-0.2, 0.2)
+                m.eps = 0.1
     model.train(train)
     batches = []
     for _ in range(2):
@@ -482,6 +566,12 @@ class Reference:
     def hessian(self, v):
         return curvature.HessianOperator(self.loss_t, self.params)(v.detach().cpu().double()).clone()
 
+    def running(self):
+        """``{name: buffer}`` of every BatchNorm's ``running_mean`` / ``running_var`` / ``num_batches_tracked`` behind the
+        reference's ONE forward pass (train mode: moved once from the state ``model`` was handed over in)."""
+        return {f"{n}.{k}": getattr(m, k).detach().clone() for n, m in self.model.named_modules()
+                if isinstance(m, nn.BatchNorm2d) for k in ("running_mean", "running_var", "num_batches_tracked")}
+
     def diag_ef(self):
         """``(1/N) sum_i g_i^2`` over the per-sample gradients (eval mode: the samples do not interact, so the gradient
         of sample i's loss through the batch's pass is its per-sample gradient)."""
@@ -514,6 +604,20 @@ def per_tensor_errors(got, want, sizes):
     return errs
 
 
+def running_errors(model, ref):
+    """``{buffer: max|got - want| / max|want|}`` of ``model``'s running statistics against ``ref.running()``;
+    ``num_batches_tracked`` must be equal (asserted)."""
+    mods, errs = dict(model.named_modules()), {}
+    for key, want in ref.running().items():
+        name, attr = key.rsplit(".", 1)
+        got = getattr(mods[name], attr).detach().cpu()
+        if attr == "num_batches_tracked":
+            assert int(got) == int(want), (key, int(got), int(want))
+        else:
+            errs[key] = float((got.double() - want).abs().max() / want.abs().max())
+    return errs
+
+
 def scalar_error(got, want):
     return abs(float(got) - float(want)) / abs(float(want))
 
@@ -536,20 +640,24 @@ def stock_fp32_errors(case, device, train=False, seeds=(11, 12)):
     x, t = batches[0]
     sizes = named_sizes(model)
     own = copy.deepcopy(model).to(device)
-    # (the tail cases: on its own pool positions too, as the engine's reference is on the engine's)
+    # (the tail and BatchNorm-stack cases: on its own pool positions too, as the engine's reference is on the engine's)
     ref = Reference(model, x, t, masks=own_masks(own, x.to(device)),
-                    pools=pool_positions(own, x.to(device)) if case in TAILS else None)
+                    pools=pool_positions(own, x.to(device)) if (case in TAILS or case in BN_STACKS) else None)
     model, x, t = model.to(device), x.to(device), t.to(device)
     params = [p for p in model.parameters() if p.requires_grad]
     out = model(x)
     loss = nn.functional.cross_entropy(out, t)
     res = {"logits": {"logits": float((out.detach().cpu().double() - ref.logits).abs().max() / ref.logits.abs().max())},
            "loss": {"loss": scalar_error(loss, ref.loss())}}
+    if train:  # (the one train-mode pass above moved the running statistics, as the reference's one pass moved its own)
+        res["running"] = running_errors(model, ref)
     grad = torch.cat([g.reshape(-1) for g in torch.autograd.grad(loss, params, retain_graph=True)])
     res["gradient"] = per_tensor_errors(grad, ref.gradient(), sizes)
     n = grad.numel()
     for name, op, want in (("ggn", curvature.GGNOperator(loss, out, params), ref.ggn),
                            ("hessian", curvature.HessianOperator(loss, params), ref.hessian)):
+        if name == "hessian" and case == "bn_tail_rect":
+            continue  # (the engine makes no Hessian products through a classifier tail: no bound to take)
         worst = {}
         for seed in seeds:
             v = probe(n, seed, device)

@@ -12,8 +12,35 @@ GEOMS = [(2, 2, 0), (3, 2, 0), (3, 2, 1), (2, 1, 0), (3, 3, 1)]  # (kernel, stri
 MAPS = [(5, 7), (4, 4), (3, 3)]
 
 
+def _transposed(geom, hw):
+    return tuple((a[1], a[0]) for a in geom), (hw[1], hw[0])
+
+
+# per-axis windows, ((kh, kw), (sh, sw), (ph, pw)), (h, w): every pair that differs is told from its exchange by the
+# adjoint (``test_pool_act_refs_cpu.py``), and each entry is followed by its transpose, so an exchange shows both ways
+AXIS_GEOMS = [e for g in [(((3, 2), (2, 1), (1, 0)), (5, 7)), (((2, 3), (2, 2), (0, 1)), (6, 5)),
+                          (((1, 2), (1, 2), (0, 0)), (2, 9))] for e in (g, _transposed(*g))]
+
+
+def exchanges(geom):
+    """(name, geometry) for each of (kh, kw), (sh, sw), (ph, pw) of ``geom`` whose two values differ, with that pair
+    exchanged: what a kernel that reads the wrong axis' parameter would take the windows to be."""
+    out = []
+    for j, name in enumerate(("kernel", "stride", "padding")):
+        a, b = pair(geom[j])
+        if a != b:
+            out.append((name, tuple((b, a) if i == j else pair(g) for i, g in enumerate(geom))))
+    return out
+
+
+def pair(v):
+    """A geometry parameter, an int (both axes) or an (h, w) pair, as the pair."""
+    return (v, v) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
 def out_hw(h, w, k, s, p):
-    return (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
+    (kh, kw), (sh, sw), (ph, pw) = pair(k), pair(s), pair(p)
+    return (h + 2 * ph - kh) // sh + 1, (w + 2 * pw - kw) // sw + 1
 
 
 def _seed(*key):
@@ -69,8 +96,10 @@ def adjoint(gy, idx, y_pool, relu, h, w, k, s, p, row_blocks=0):
     """ga[n,y,x,c] = sum over the windows containing (y,x) whose idx is (y,x) of m * sum_s gy[s][n,oy,ox,c]; gy
     [S, n, oh, ow, c].  Returns float64 (ga [n,h,w,c], M, gb, windows): ``gb`` [row_blocks, c] the partial rows of
     sum ga over the shares ``[b*per, (b+1)*per)`` of the n*h*w full-resolution rows, per = ceil(rows / row_blocks)
-    (None for row_blocks = 0; an empty share raises), ``windows`` the largest number of windows one pixel collected."""
+    (None for row_blocks = 0; an empty share raises), ``windows`` the largest number of windows one pixel collected.
+    ``k``, ``s``, ``p``: an int or an (h, w) pair each; they enter the window predicate only."""
     S, n, oh, ow, c = gy.shape
+    (kh, kw), (sh, sw), (ph, pw) = pair(k), pair(s), pair(p)
     g = gy.double().numpy()
     ix = idx.numpy()
     ga = np.zeros((n, h, w, c))
@@ -80,10 +109,10 @@ def adjoint(gy, idx, y_pool, relu, h, w, k, s, p, row_blocks=0):
         for y in range(h):
             for x in range(w):
                 for oy in range(oh):
-                    if not oy * s - p <= y <= oy * s - p + k - 1:
+                    if not oy * sh - ph <= y <= oy * sh - ph + kh - 1:
                         continue
                     for ox in range(ow):
-                        if not ox * s - p <= x <= ox * s - p + k - 1:
+                        if not ox * sw - pw <= x <= ox * sw - pw + kw - 1:
                             continue
                         for ci in range(c):
                             if ix[ni, oy, ox, ci] != y * w + x:
@@ -108,7 +137,8 @@ def adjoint(gy, idx, y_pool, relu, h, w, k, s, p, row_blocks=0):
 def case(n, c, h, w, k, s, p, splits, gy_splits, exact=True, tag=""):
     """Seeded operands of one kernel case.  ``exact``: multiples of 1/8 (every sum exact in fp32), else standard normal.
     The pre-activation ``a + b`` has distinct values inside every window (a permutation of distinct multiples of 1/8
-    per plane, shifted so that roughly a third of the windows' maxima are <= 0: those windows are masked)."""
+    per plane, shifted so that roughly a third of the windows' maxima are <= 0: those windows are masked).  ``k``, ``s``,
+    ``p``: an int or an (h, w) pair each (an int seeds as it always did)."""
     gen = torch.Generator().manual_seed(_seed("pool-act", n, c, h, w, k, s, p, splits, gy_splits, exact, tag))
     oh, ow = out_hw(h, w, k, s, p)
     hw = h * w

@@ -14,6 +14,7 @@ import torch
 import pool_act_refs as R
 
 GEOMS, MAPS, out_hw = R.GEOMS, R.MAPS, R.out_hw
+AXIS_GEOMS, pair = R.AXIS_GEOMS, R.pair  # (every k / s / p below: an int or an (h, w) pair, as in ``pool_act_refs``)
 
 
 def xhat(o):

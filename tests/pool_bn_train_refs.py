@@ -21,6 +21,7 @@ EPS = 1e-5
 # centre in four); 2/2 windows on 6x4 -> 3x2 (every pixel in exactly one).  A pixel that is no window's maximum gets no
 # cotangent and is never read by the tangent: most pixels of both.
 GEOMS = [((3, 2, 0), (5, 5)), ((2, 2, 0), (6, 4))]
+AXIS_GEOMS = R.AXIS_GEOMS  # per-axis windows, ((kh, kw), (sh, sw), (ph, pw)), (h, w): every function below takes pairs
 BLOCK, FCS_BATCH = 256, 8  # hf_common.h; HF_FCS_BATCH of hf_bn.hip
 
 

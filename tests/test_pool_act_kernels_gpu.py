@@ -69,8 +69,23 @@ SHAPES = [(g, m, c) for g in R.GEOMS for m in R.MAPS for c in (4, 12)] + [((3, 2
 OPTS = list(itertools.product((1, 2, 9), (0, 1), (0, 1), (0, 1), (4, 6)))  # splits, wide out, relu, v_b, stride pad
 
 
+# per-axis windows (kh != kw, sh != sw or ph != pw, each with its transpose) x both channel forms (16 bytes, element-wise)
+AXIS_SHAPES = [(g, m, c) for g, m in R.AXIS_GEOMS for c in (4, 3)]
+# the row-sum kernel's second pass over the channel columns (more than 256 per row): channels, row blocks, gy splits, relu
+WIDE = [(258, 1, 2, 1), (258, 3, 1, 0), (1028, 1, 1, 1), (1028, 3, 2, 0)]
+WIDE_GEOM, WIDE_MAP = (2, 2, 0), (4, 4)
+
+
 def _opts(i):
     return OPTS[(7 * i + i // len(OPTS)) % len(OPTS)]
+
+
+def _axis_opts(j):
+    return OPTS[(8 * j + 3 * (j // 2)) % len(OPTS)]
+
+
+def _ids(shapes):
+    return dict(argvalues=range(len(shapes)), ids=lambda i: "-".join(str(x) for x in shapes[i]).replace(" ", ""))
 
 
 def test_every_option_value_is_exercised():
@@ -87,14 +102,39 @@ def test_every_option_value_is_exercised():
     assert masked >= 8
 
 
+def test_every_option_value_meets_a_per_axis_window():
+    for c in (4, 3):  # in each channel form: both relu values, with and without the sums / v_b, row blocks 1 and 3
+        mine = [_axis_opts(j) for j, (_g, _m, cj) in enumerate(AXIS_SHAPES) if cj == c]
+        assert [len({o[k] for o in mine}) for k in range(5)] == [3, 2, 2, 2, 2], c
+        rows = [o for o in mine if o[1]]  # (the row-sum kernel: only with the sums)
+        assert {o[2] for o in rows} == {0, 1} and {o[3] for o in rows} == {0, 1}, c
+    for g in range(len(R.AXIS_GEOMS)):  # every window runs through the row-sum kernel in one channel form at least
+        assert _axis_opts(2 * g)[1] or _axis_opts(2 * g + 1)[1]
+    for j, ((k, s, pd), (h, w), c) in enumerate(AXIS_SHAPES):
+        assert R.exchanges((k, s, pd))
+        if _axis_opts(j)[2]:
+            assert bool((_forward(R.case(2, c, h, w, k, s, pd, 1, 1), k, s, pd, 1)[0] <= 0).any())
+    assert {(c, rb) for c, rb, _s, _r in WIDE} == {(258, 1), (258, 3), (1028, 1), (1028, 3)}
+    assert {x[2] for x in WIDE} == {1, 2} and {x[3] for x in WIDE} == {0, 1}
+
+
 def _forward(o, k, s, pd, relu):
     return R.forward(o["a"], o["b"], k, s, pd, relu)
 
 
-@pytest.mark.parametrize("i", range(len(SHAPES)), ids=lambda i: "-".join(str(x) for x in SHAPES[i]).replace(" ", ""))
+@pytest.mark.parametrize("i", **_ids(SHAPES))
 def test_tangent_equals_float64_bitwise(i):
-    ((k, s, pd), (h, w), c), n = SHAPES[i], 2
-    splits, wide, relu, with_vb, pad = _opts(i)
+    _tangent(SHAPES[i], _opts(i))
+
+
+@pytest.mark.parametrize("j", **_ids(AXIS_SHAPES))
+def test_tangent_on_per_axis_windows_equals_float64_bitwise(j):
+    _tangent(AXIS_SHAPES[j], _axis_opts(j))
+
+
+def _tangent(shape, opts):
+    ((k, s, pd), (h, w), c), n = shape, 2
+    splits, wide, relu, with_vb, pad = opts
     o = R.case(n, c, h, w, k, s, pd, splits, 1)
     y_pool, idx = _forward(o, k, s, pd, relu)
     oh, ow = o["oh"], o["ow"]
@@ -118,15 +158,36 @@ def test_tangent_equals_float64_bitwise(i):
     assert torch.equal(a.val.cpu().double(), want.reshape(orow, c))
 
 
-@pytest.mark.parametrize("i", range(len(SHAPES)), ids=lambda i: "-".join(str(x) for x in SHAPES[i]).replace(" ", ""))
+@pytest.mark.parametrize("i", **_ids(SHAPES))
 def test_adjoint_equals_float64_bitwise(i):
-    ((k, s, pd), (h, w), c), n = SHAPES[i], 2
     gy_splits, with_gb, relu, rb3, pad = _opts(i)
-    row_blocks = 3 if rb3 else 1
+    _adjoint(SHAPES[i], 2, gy_splits, with_gb, relu, 3 if rb3 else 1, pad)
+
+
+@pytest.mark.parametrize("j", **_ids(AXIS_SHAPES))
+def test_adjoint_on_per_axis_windows_equals_float64_bitwise(j):
+    """kh, kw, stride_h, stride_w, pad_h, pad_w each reach their own axis: the reference with any unequal pair exchanged
+    differs on these operands (asserted), and the kernel equals the right one."""
+    gy_splits, with_gb, relu, rb3, pad = _axis_opts(j)
+    _adjoint(AXIS_SHAPES[j], 2, gy_splits, with_gb, relu, 3 if rb3 else 1, pad)
+
+
+@pytest.mark.parametrize("c, row_blocks, gy_splits, relu", WIDE, ids=lambda v: str(v))
+def test_adjoint_row_sums_beyond_256_channel_columns_equal_float64_bitwise(c, row_blocks, gy_splits, relu):
+    """c = 258: the element-wise form, 258 columns -- a second pass with 2 live columns; c = 1028: the 16-byte form, 257
+    quads -- a second pass with one.  The reduction buffer is reused between the passes."""
+    _adjoint((WIDE_GEOM, WIDE_MAP, c), 1, gy_splits, 1, relu, row_blocks, 4)
+
+
+def _adjoint(shape, n, gy_splits, with_gb, relu, row_blocks, pad):
+    (k, s, pd), (h, w), c = shape
+    (kh, kw), (sh, sw), (ph, pw) = R.pair(k), R.pair(s), R.pair(pd)
     o = R.case(n, c, h, w, k, s, pd, 1, gy_splits)
     y_pool, idx = _forward(o, k, s, pd, relu)
     oh, ow = o["oh"], o["ow"]
     want, _, want_gb, _ = R.adjoint(o["gy"], idx, y_pool, relu, h, w, k, s, pd, row_blocks)
+    for name, (k2, s2, p2) in R.exchanges((k, s, pd)):
+        assert not torch.equal(R.adjoint(o["gy"], idx, y_pool, relu, h, w, k2, s2, p2)[0], want), name
     slab = n * oh * ow * c + pad
     gd = slabs_dev(o["gy"], slab)
     idxd, yd = idx.to(torch.int32).to(DEV), (y_pool.to(DEV) if relu else None)
@@ -135,7 +196,7 @@ def test_adjoint_equals_float64_bitwise(i):
     def launch():
         ga, gb = Out(rows, c), (Out(row_blocks, c) if with_gb else None)
         _lib.check(lib.hf_pool_act_adjoint_nhwc(ga.ptr, gb.ptr if gb else None, row_blocks, p(gd), gy_splits, slab,
-                                                p(idxd), p(yd), relu, n, h, w, oh, ow, c, k, k, s, s, pd, pd,
+                                                p(idxd), p(yd), relu, n, h, w, oh, ow, c, kh, kw, sh, sw, ph, pw,
                                                 _lib.HF_F32, st()), "hf_pool_act_adjoint_nhwc")
         return ga, gb
 

@@ -18,12 +18,9 @@ def _f(relu, k, s, p):
     return f
 
 
-@pytest.mark.parametrize("hw", R.MAPS)
-@pytest.mark.parametrize("geom", R.GEOMS)
-@pytest.mark.parametrize("relu", [0, 1])
-def test_references_equal_autograd_in_float64(geom, hw, relu):
+def _anchor(geom, hw, relu, c):
     (k, s, p), (h, w) = geom, hw
-    n, c = 2, 4
+    n = 2
     o = R.case(n, c, h, w, k, s, p, 2, 3)
     y_pool, idx = R.forward(o["a"], o["b"], k, s, p, relu)
     if relu:
@@ -49,8 +46,73 @@ def test_references_equal_autograd_in_float64(geom, hw, relu):
         rows, per = n * h * w, -(-n * h * w // rb)
         for b in range(rb):  # share b = rows [b*per, (b+1)*per) of the full-resolution map
             assert torch.equal(gb[b], want_ga.reshape(rows, c)[b * per:(b + 1) * per].sum(0))
-        assert 1 <= windows <= ((k + s - 1) // s) ** 2
+        (kh, kw), (sh, sw) = R.pair(k), R.pair(s)
+        assert 1 <= windows <= ((kh + sh - 1) // sh) * ((kw + sw - 1) // sw)
     assert R.adjoint(o["gy"], idx, y_pool, relu, h, w, k, s, p, 0)[2] is None
+
+
+@pytest.mark.parametrize("hw", R.MAPS)
+@pytest.mark.parametrize("geom", R.GEOMS)
+@pytest.mark.parametrize("relu", [0, 1])
+def test_references_equal_autograd_in_float64(geom, hw, relu):
+    _anchor(geom, hw, relu, 4)
+
+
+AXIS_IDS = [str(e).replace(" ", "") for e in R.AXIS_GEOMS]
+
+
+@pytest.mark.parametrize("geom, hw", R.AXIS_GEOMS, ids=AXIS_IDS)
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("c", [4, 3])
+def test_references_equal_autograd_on_per_axis_windows(geom, hw, relu, c):
+    _anchor(geom, hw, relu, c)
+
+
+def test_an_int_is_the_pair_of_itself():
+    """Integer geometries keep their operands (the seed string is the int's) and mean what the pair means."""
+    for (k, s, p) in R.GEOMS:
+        h, w = 5, 7
+        assert R.out_hw(h, w, k, s, p) == R.out_hw(h, w, (k, k), (s, s), (p, p))
+        o = R.case(2, 4, h, w, k, s, p, 1, 2)
+        y_pool, idx = R.forward(o["a"], o["b"], k, s, p)
+        a = R.adjoint(o["gy"], idx, y_pool, 1, h, w, k, s, p, 3)
+        b = R.adjoint(o["gy"], idx, y_pool, 1, h, w, (k, k), (s, s), (p, p), 3)
+        assert all(torch.equal(x, y) for x, y in zip(a[:3], b[:3])) and a[3] == b[3]
+    assert R._seed("pool-act", 2, 4, 5, 7, 3, 2, 1) != R._seed("pool-act", 2, 4, 5, 7, (3, 3), (2, 2), (1, 1))
+    # the first plane of an integer case is the first draw behind the seed string of the int, as it always was
+    gen = torch.Generator().manual_seed(R._seed("pool-act", 2, 4, 5, 7, 3, 2, 1, 1, 2, True, ""))
+    first = (torch.randperm(35, generator=gen).view(5, 7).float() - 0.75 * 35) / 8.0
+    o = R.case(2, 4, 5, 7, 3, 2, 1, 1, 2)
+    assert torch.equal(o["a"][0, :, :, 0] + o["b"][0], first)
+
+
+def test_axis_geoms_hold_every_entry_with_its_transpose():
+    assert len(R.AXIS_GEOMS) >= 6 and len(set(R.AXIS_GEOMS)) == len(R.AXIS_GEOMS)
+    for geom, (h, w) in R.AXIS_GEOMS:
+        assert (tuple((b, a) for a, b in geom), (w, h)) in R.AXIS_GEOMS
+        assert R.exchanges(geom), "a square entry"
+        oh, ow = R.out_hw(h, w, *geom)
+        assert oh >= 1 and ow >= 1 and all(2 * pd <= k for k, pd in zip(geom[0], geom[2]))
+    for need in ((((3, 2), (2, 1), (1, 0)), (5, 7)), (((2, 3), (2, 2), (0, 1)), (6, 5)), (((1, 2), (1, 2), (0, 0)), (2, 9)),
+                 (((2, 3), (1, 2), (0, 1)), (7, 5))):
+        assert need in R.AXIS_GEOMS
+
+
+@pytest.mark.parametrize("geom, hw", R.AXIS_GEOMS, ids=AXIS_IDS)
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("c", [4, 3])
+def test_per_axis_cases_tell_an_exchanged_window_apart(geom, hw, relu, c):
+    """The adjoint with (kh, kw), (sh, sw) or (ph, pw) exchanged in the window predicate alone -- the map, oh, ow and
+    idx as they are: what ``pool_act_adjoint_at`` would compute from the other axis' parameter -- differs from the right
+    one, in ga and in every number of row blocks' sums, on the operands of the GPU tests."""
+    (k, s, p), (h, w) = geom, hw
+    o = R.case(2, c, h, w, k, s, p, 1, 2)
+    y_pool, idx = R.forward(o["a"], o["b"], k, s, p, relu)
+    ga, _, gb, _ = R.adjoint(o["gy"], idx, y_pool, relu, h, w, k, s, p, 1)
+    for name, (k2, s2, p2) in R.exchanges(geom):
+        ga2, _, gb2, _ = R.adjoint(o["gy"], idx, y_pool, relu, h, w, k2, s2, p2, 1)
+        assert not torch.equal(ga2, ga), name
+        assert not torch.equal(gb2, gb), name
 
 
 def test_an_empty_share_is_an_error():

@@ -38,6 +38,24 @@ def _a_opts(i):
     return A_OPTS[(85 * i + 7 * (i // 6)) % len(A_OPTS)]
 
 
+# per-axis windows x both channel forms, and the row-sum kernel beyond 256 channel columns (``test_pool_act_kernels_gpu``)
+AXIS_SHAPES = [(g, m, c) for g, m in B.AXIS_GEOMS for c in (4, 3)]
+WIDE = [(258, 1, 2, 1, "wb"), (258, 3, 1, 0, "wb"), (1028, 1, 1, 1, "wb"), (1028, 3, 2, 0, "wb"),  # c, rb, gy splits, relu
+        (258, 3, 2, 1, "w"), (1028, 3, 1, 1, "b")]
+
+
+def _axis_t_opts(j):
+    return T_OPTS[(5 * j + 14) % len(T_OPTS)]
+
+
+def _axis_a_opts(j):
+    return A_OPTS[(17 * j + 5) % len(A_OPTS)]
+
+
+def _ids(shapes):
+    return dict(argvalues=range(len(shapes)), ids=lambda i: "-".join(str(x) for x in shapes[i]).replace(" ", ""))
+
+
 def _row_blocks(sums, rb):
     return rb if sums else 0  # (without sums: the one-pixel-per-thread form, row_blocks is not read)
 
@@ -64,14 +82,40 @@ def test_every_option_value_is_exercised():
     assert ragged >= 3
 
 
+def test_every_option_value_meets_a_per_axis_window():
+    for opts, values in ((_axis_t_opts, T_VALUES), (_axis_a_opts, A_VALUES)):
+        seen = [{opts(j)[k] for j in range(len(AXIS_SHAPES))} for k in range(len(values))]
+        assert [len(s) for s in seen] == values
+    for c in (4, 3):  # ... and in each channel form
+        mine = [j for j, (_g, _m, cj) in enumerate(AXIS_SHAPES) if cj == c]
+        assert all({_axis_t_opts(j)[k] for j in mine} == {0, 1} for k in (1, 2, 3, 4)), c
+        assert {_axis_a_opts(j)[1] for j in mine} == {0, 1} and {_axis_a_opts(j)[2] for j in mine} == {0, 1}, c
+        rows = [_axis_a_opts(j) for j in mine if _axis_a_opts(j)[3]]  # (the row-sum kernel: only with sums)
+        assert {"w" in o[3] for o in rows} == {False, True} and {o[4] for o in rows} >= {1, 3}, c
+        assert {o[1] for o in rows} == {0, 1}, c  # (a pooled unit without the ReLU takes its sums there too)
+    for g in range(len(B.AXIS_GEOMS)):  # every window runs through the row-sum kernel in one channel form at least
+        assert _axis_a_opts(2 * g)[3] or _axis_a_opts(2 * g + 1)[3]
+    assert {(x[0], x[1]) for x in WIDE} == {(258, 1), (258, 3), (1028, 1), (1028, 3)}
+    assert {x[2] for x in WIDE} == {1, 2} and {x[3] for x in WIDE} == {0, 1} and {x[4] for x in WIDE} == {"wb", "w", "b"}
+
+
 def _dev(o, *names):
     return [o[k].to(DEV) for k in names]
 
 
-@pytest.mark.parametrize("i", range(len(SHAPES)), ids=lambda i: "-".join(str(x) for x in SHAPES[i]).replace(" ", ""))
+@pytest.mark.parametrize("i", **_ids(SHAPES))
 def test_tangent_equals_float64_bitwise(i):
-    ((k, s, pd), (h, w), c), n = SHAPES[i], 2
-    splits, wide, relu, with_vw, with_vb, pad = _t_opts(i)
+    _tangent(SHAPES[i], _t_opts(i))
+
+
+@pytest.mark.parametrize("j", **_ids(AXIS_SHAPES))
+def test_tangent_on_per_axis_windows_equals_float64_bitwise(j):
+    _tangent(AXIS_SHAPES[j], _axis_t_opts(j))
+
+
+def _tangent(shape, opts):
+    ((k, s, pd), (h, w), c), n = shape, 2
+    splits, wide, relu, with_vw, with_vb, pad = opts
     o = B.case(n, c, h, w, k, s, pd, splits, 1)
     y_pool, idx = B.forward(o, k, s, pd, relu)
     oh, ow = o["oh"], o["ow"]
@@ -98,15 +142,35 @@ def test_tangent_equals_float64_bitwise(i):
     assert torch.equal(a.val.cpu().double(), want.reshape(orow, c))
 
 
-@pytest.mark.parametrize("i", range(len(SHAPES)), ids=lambda i: "-".join(str(x) for x in SHAPES[i]).replace(" ", ""))
+@pytest.mark.parametrize("i", **_ids(SHAPES))
 def test_adjoint_equals_float64_bitwise(i):
-    ((k, s, pd), (h, w), c), n = SHAPES[i], 2
-    gy_splits, relu, with_g, sums, rb, pad = _a_opts(i)
+    _adjoint(SHAPES[i], 2, *_a_opts(i))
+
+
+@pytest.mark.parametrize("j", **_ids(AXIS_SHAPES))
+def test_adjoint_on_per_axis_windows_equals_float64_bitwise(j):
+    """kh, kw, stride_h, stride_w, pad_h, pad_w each reach their own axis: the reference with any unequal pair exchanged
+    differs on these operands (asserted), and the kernel equals the right one."""
+    _adjoint(AXIS_SHAPES[j], 2, *_axis_a_opts(j))
+
+
+@pytest.mark.parametrize("c, rb, gy_splits, relu, sums", WIDE, ids=lambda v: str(v))
+def test_adjoint_row_sums_beyond_256_channel_columns_equal_float64_bitwise(c, rb, gy_splits, relu, sums):
+    """c = 258: the element-wise form, 258 columns -- a second pass with 2 live columns; c = 1028: the 16-byte form, 257
+    quads -- a second pass with one.  Both sums per channel share the reduction buffer, reused between the passes."""
+    _adjoint(((2, 2, 0), (4, 4), c), 1, gy_splits, relu, 1, sums, rb, 4)
+
+
+def _adjoint(shape, n, gy_splits, relu, with_g, sums, rb, pad):
+    (k, s, pd), (h, w), c = shape
+    (kh, kw), (sh, sw), (ph, pw) = B.pair(k), B.pair(s), B.pair(pd)
     row_blocks = _row_blocks(sums, rb)
     o = B.case(n, c, h, w, k, s, pd, 1, gy_splits)
     y_pool, idx = B.forward(o, k, s, pd, relu)
     oh, ow = o["oh"], o["ow"]
     want = B.adjoint(o, idx, y_pool, relu, h, w, k, s, pd, row_blocks)
+    for name, (k2, s2, p2) in B.R.exchanges((k, s, pd)):
+        assert not torch.equal(B.R.adjoint(o["gy"], idx, y_pool, relu, h, w, k2, s2, p2)[0], want["g"]), name
     slab = n * oh * ow * c + pad
     gd = slabs_dev(o["gy"], slab)
     ad, md, rd, wd = _dev(o, "a", "mean", "rstd", "w")
@@ -119,7 +183,8 @@ def test_adjoint_equals_float64_bitwise(i):
         ptr = {name: (t.ptr if t is not None else None) for name, t in outs.items()}
         _lib.check(lib.hf_pool_bn_act_adjoint_nhwc(ptr["ga"], ptr["g"], ptr["gw"], ptr["gb"], row_blocks, p(gd), gy_splits,
                                                    slab, p(ad), p(md), p(rd), p(wd), p(idxd), p(yd), relu, n, h, w, oh, ow,
-                                                   c, k, k, s, s, pd, pd, _lib.HF_F32, st()), "hf_pool_bn_act_adjoint_nhwc")
+                                                   c, kh, kw, sh, sw, ph, pw, _lib.HF_F32, st()),
+                   "hf_pool_bn_act_adjoint_nhwc")
         return outs
 
     a, b = launch(), launch()

@@ -22,8 +22,11 @@ def _unit(o, k, s, p, relu):
     return f
 
 
+AXIS_CASES = [(geom, hw, c, relu) for geom, hw in B.AXIS_GEOMS for c in (4, 3) for relu in (0, 1)]
+
+
 @pytest.mark.parametrize("exact", [True, False])
-@pytest.mark.parametrize("geom, hw, c, relu", CASES)
+@pytest.mark.parametrize("geom, hw, c, relu", CASES + AXIS_CASES)
 def test_references_equal_autograd(geom, hw, c, relu, exact):
     (k, s, p), (h, w), n = geom, hw, 2
     o = B.case(n, c, h, w, k, s, p, 2, 3, exact=exact)
@@ -56,14 +59,18 @@ def test_dyadic_references_are_fp32_numbers():
     def fp32(t):
         return torch.equal(t.float().double(), t)
 
-    for (k, s, p) in B.GEOMS:
-        for (h, w) in B.MAPS:
-            for relu in (0, 1):
-                o = B.case(2, 4, h, w, k, s, p, 9, 9)
-                y_pool, idx = B.forward(o, k, s, p, relu)
-                assert fp32(B.tangent(o, o["v_w"], o["v_b"], idx, y_pool, relu)[0])
-                r = B.adjoint(o, idx, y_pool, relu, h, w, k, s, p, 1)
-                assert all(fp32(r[name]) for name in ("g", "ga", "gw", "gb"))
+    for (k, s, p), (h, w) in [(g, m) for g in B.GEOMS for m in B.MAPS] + B.AXIS_GEOMS:
+        for relu in (0, 1):
+            o = B.case(2, 4, h, w, k, s, p, 9, 9)
+            y_pool, idx = B.forward(o, k, s, p, relu)
+            assert fp32(B.tangent(o, o["v_w"], o["v_b"], idx, y_pool, relu)[0])
+            r = B.adjoint(o, idx, y_pool, relu, h, w, k, s, p, 1)
+            assert all(fp32(r[name]) for name in ("g", "ga", "gw", "gb"))
+    for c in (258, 1028):  # the wide cases of the row-sum kernel: n = 1, shares of up to 16 rows
+        o = B.case(1, c, 4, 4, 2, 2, 0, 1, 2)
+        y_pool, idx = B.forward(o, 2, 2, 0, 1)
+        r = B.adjoint(o, idx, y_pool, 1, 4, 4, 2, 2, 0, 1)
+        assert all(fp32(r[name]) for name in ("g", "ga", "gw", "gb"))
 
 
 def test_the_cases_mask_windows():
@@ -74,3 +81,26 @@ def test_the_cases_mask_windows():
             y_pool, _ = B.forward(o, k, s, p, 1)
             masked += bool((y_pool <= 0).any()) and bool((y_pool > 0).any())
     assert masked >= 8
+
+
+@pytest.mark.parametrize("geom, hw, c, relu", AXIS_CASES)
+def test_per_axis_cases_tell_an_exchanged_window_apart(geom, hw, c, relu):
+    """Every output of the adjoint -- g, ga and both sum rows -- computed with (kh, kw), (sh, sw) or (ph, pw) exchanged in
+    the window predicate alone differs from the right one (without the ReLU as well: the pooled no-ReLU unit)."""
+    (k, s, p), (h, w) = geom, hw
+    o = B.case(2, c, h, w, k, s, p, 1, 2)
+    y_pool, idx = B.forward(o, k, s, p, relu)
+    r = B.adjoint(o, idx, y_pool, relu, h, w, k, s, p, 1)
+    assert B.R.exchanges(geom)
+    for name, (k2, s2, p2) in B.R.exchanges(geom):
+        r2 = B.adjoint(o, idx, y_pool, relu, h, w, k2, s2, p2, 1)
+        for out in ("g", "ga", "gw", "gb"):
+            assert not torch.equal(r2[out], r[out]), (name, out)
+
+
+def test_the_per_axis_cases_mask_windows():
+    for (k, s, p), (h, w) in B.AXIS_GEOMS:
+        for c in (4, 3):
+            o = B.case(2, c, h, w, k, s, p, 1, 1)
+            y_pool, _ = B.forward(o, k, s, p, 1)
+            assert bool((y_pool <= 0).any()) and bool((y_pool > 0).any())

@@ -30,6 +30,15 @@ T_CASES = [(i % 2, (8, 12)[(i // 2) % 2], (i // 4) % 3, (1, 3)[(i // 12) % 2], (
 # reduction cases: geometry, channels, gy splits, relu, row blocks
 A_CASES = [(i % 2, (8, 12)[(i // 2) % 2], (1, 3)[(i // 4) % 2], (i + i // 4) % 2, (1, 3)[(i // 2 + i // 8) % 2])
            for i in range(16)]
+# per-axis windows (``pool_act_refs.AXIS_GEOMS``: geometry = its index there).  The tangent takes multiples of 4 channels
+# only: 4, its 16-byte form on even cases and the element-wise form (out_ld = 2c + 2) on odd ones; the reduction pass runs
+# 4 channels (16 bytes) and 3 (element-wise) on every window
+AXIS_T_CASES = [(j // 2, 4, (j + j // 6) % 3, (1, 3)[(j // 2 + j // 6) % 2], (j // 2 + j // 4) % 2,
+                 ("", "w", "b")[(j // 2) % 3], 2 if j % 2 else (j // 2) % 2) for j in range(12)]
+AXIS_A_CASES = [(j // 2, (4, 3)[j % 2], (1, 3)[(j // 2 + j // 6) % 2], (j + j // 4) % 2, (1, 3)[(j // 2 + j // 4) % 2])
+                for j in range(12)]
+# the row-sum kernel beyond 256 channel columns, in its form without ga: channels, row blocks, gy splits, relu
+WIDE = [(258, 1, 2, 1), (258, 3, 1, 0), (1028, 1, 1, 1), (1028, 3, 2, 0)]
 
 
 def test_every_option_value_is_exercised():
@@ -40,6 +49,22 @@ def test_every_option_value_is_exercised():
         assert T.nparts_choices(c)[2] > T.FCS_BATCH * (T.BLOCK // (c // 4))
         mine = [t for t in A_CASES if t[1] == c]
         assert all({t[j] for t in mine} == vals for j, vals in ((0, {0, 1}), (2, {1, 3}), (3, {0, 1}), (4, {1, 3})))
+
+
+def test_every_option_value_meets_a_per_axis_window():
+    assert {t[0] for t in AXIS_T_CASES} == {t[0] for t in AXIS_A_CASES} == set(range(len(T.AXIS_GEOMS)))
+    for quad in (True, False):  # the tangent's two forms
+        mine = [t for t in AXIS_T_CASES if (t[6] != 2) == quad]
+        assert {t[0] for t in mine} == set(range(len(T.AXIS_GEOMS)))
+        assert {t[2] for t in mine} == {0, 1, 2} and {t[3] for t in mine} == {1, 3} and {t[4] for t in mine} == {0, 1}
+        assert {t[5] for t in mine} == {"", "w", "b"}
+    assert {t[6] for t in AXIS_T_CASES} == {0, 1, 2}
+    for c in (4, 3):
+        mine = [t for t in AXIS_A_CASES if t[1] == c]
+        assert {t[0] for t in mine} == set(range(len(T.AXIS_GEOMS)))
+        assert all({t[j] for t in mine} == vals for j, vals in ((2, {1, 3}), (3, {0, 1}), (4, {1, 3})))
+        assert {(t[3], t[4]) for t in mine} >= {(0, 3), (1, 1)}
+    assert {(c, rb) for c, rb, _s, _r in WIDE} == {(258, 1), (258, 3), (1028, 1), (1028, 3)}
 
 
 def _dev(o, *names):
@@ -59,8 +84,17 @@ def _slice(t, off):
 
 @pytest.mark.parametrize("case", T_CASES, ids=lambda t: "-".join(str(x) for x in t))
 def test_tangent_is_the_train_kernels_dense_output_gathered_and_within_its_bound(case):
-    gi, c, npi, splits, relu, null, ldk = case
-    (k, s, pd), (h, w) = T.GEOMS[gi]
+    _tangent(T.GEOMS[case[0]], case)
+
+
+@pytest.mark.parametrize("case", AXIS_T_CASES, ids=lambda t: "-".join(str(x) for x in t))
+def test_tangent_on_per_axis_windows_is_the_dense_output_gathered_and_within_its_bound(case):
+    _tangent(T.AXIS_GEOMS[case[0]], case)
+
+
+def _tangent(geom, case):
+    _gi, c, npi, splits, relu, null, ldk = case
+    (k, s, pd), (h, w) = geom
     nparts = T.nparts_choices(c)[npi]
     o = T.case(N, c, h, w, k, s, pd, splits, 1, nparts)
     y_pool, idx = B.forward(o, k, s, pd, relu)
@@ -104,8 +138,55 @@ def test_tangent_is_the_train_kernels_dense_output_gathered_and_within_its_bound
 
 @pytest.mark.parametrize("case", A_CASES, ids=lambda t: "-".join(str(x) for x in t))
 def test_reduce_writes_the_fused_entry_points_g_and_sums_and_no_ga(case):
-    gi, c, gy_splits, relu, rb = case
-    (k, s, pd), (h, w) = T.GEOMS[gi]
+    _reduce(T.GEOMS[case[0]], case)
+
+
+@pytest.mark.parametrize("case", AXIS_A_CASES, ids=lambda t: "-".join(str(x) for x in t))
+def test_reduce_on_per_axis_windows_writes_g_and_sums_and_no_ga(case):
+    """kh, kw, stride_h, stride_w, pad_h, pad_w each reach their own axis: with any unequal pair exchanged the reference
+    moves by more than 1000 x the bound (``test_pool_bn_train_refs_cpu.py``), and the bound here is the square cases'."""
+    _reduce(T.AXIS_GEOMS[case[0]], case)
+
+
+@pytest.mark.parametrize("c, rb, gy_splits, relu", WIDE, ids=lambda v: str(v))
+def test_reduce_row_sums_beyond_256_channel_columns_equal_float64_bitwise(c, rb, gy_splits, relu):
+    """c = 258: the element-wise form, 258 columns -- a second pass with 2 live columns; c = 1028: the 16-byte form, 257
+    quads.  Dyadic operands (``pool_bn_act_refs.case``): g, gw and gb equal the float64 reference bitwise, and nothing is
+    written where the fused entry point's ga would be."""
+    n, (k, s, pd), (h, w) = 1, (2, 2, 0), (4, 4)
+    o = B.case(n, c, h, w, k, s, pd, 1, gy_splits)
+    y_pool, idx = B.forward(o, k, s, pd, relu)
+    oh, ow = o["oh"], o["ow"]
+    want = B.adjoint(o, idx, y_pool, relu, h, w, k, s, pd, rb)
+    slab, rows = n * oh * ow * c + 4, n * h * w
+    gd = slabs_dev(o["gy"], slab)
+    ad, md, rd, wd = _dev(o, "a", "mean", "rstd", "w")
+    idxd, yd = idx.to(torch.int32).to(DEV), (y_pool.to(DEV) if relu else None)
+    lib = _lib.load()
+
+    def launch():
+        both, gw, gb = Out(2 * rows, c), Out(rb, c), Out(rb, c)
+        g_ptr = _lib.c_void_p(both.buf.data_ptr() + 4 * rows * c)
+        _lib.check(lib.hf_pool_bn_act_adjoint_reduce_nhwc(
+            g_ptr, gw.ptr, gb.ptr, rb, p(gd), gy_splits, slab, p(ad), p(md), p(rd), p(wd), p(idxd), p(yd), relu, n, h, w, oh,
+            ow, c, k, k, s, s, pd, pd, _lib.HF_F32, st()), "hf_pool_bn_act_adjoint_reduce_nhwc")
+        return both, gw, gb
+
+    (both, gw, gb), second = launch(), launch()
+    torch.cuda.synchronize()
+    for x, y in zip((both, gw, gb), second):
+        assert x.same(y), "two launches on the same operands differ"
+        assert x.untouched()
+    assert bool(torch.isnan(both.val[:rows]).all()), "something was written where ga would be"
+    assert torch.equal(both.val[rows:].cpu().double(), want["g"].reshape(rows, c)), "g"
+    assert torch.equal(gw.val.cpu().double(), want["gw"]), "gw"
+    assert torch.equal(gb.val.cpu().double(), want["gb"]), "gb"
+
+
+def _reduce(geom, case):
+    _gi, c, gy_splits, relu, rb = case
+    (k, s, pd), (h, w) = geom
+    (kh, kw), (sh, sw), (ph, pw) = B.pair(k), B.pair(s), B.pair(pd)
     o = T.case(N, c, h, w, k, s, pd, 1, gy_splits, 1)
     y_pool, idx = B.forward(o, k, s, pd, relu)
     oh, ow = o["oh"], o["ow"]
@@ -115,8 +196,8 @@ def test_reduce_writes_the_fused_entry_points_g_and_sums_and_no_ga(case):
     ad, md, rd, wd = _dev(o, "a", "mean", "rstd", "w")
     idxd, yd = idx.to(torch.int32).to(DEV), (y_pool.to(DEV) if relu else None)
     lib, F32 = _lib.load(), _lib.HF_F32
-    tail = (p(gd), gy_splits, slab, p(ad), p(md), p(rd), p(wd), p(idxd), p(yd), relu, N, h, w, oh, ow, c, k, k, s, s, pd, pd,
-            F32)
+    tail = (p(gd), gy_splits, slab, p(ad), p(md), p(rd), p(wd), p(idxd), p(yd), relu, N, h, w, oh, ow, c, kh, kw, sh, sw, ph,
+            pw, F32)
 
     def launch():
         # g sits where the fused entry point's argument order has it: behind a map-sized region where ga would be

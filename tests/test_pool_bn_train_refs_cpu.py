@@ -11,6 +11,7 @@ import pool_bn_train_refs as T
 
 B = T.B
 CASES = [(geom, hw, c, relu) for geom, hw in T.GEOMS for c in (8, 12) for relu in (0, 1)]
+AXIS_CASES = [(geom, hw, c, relu) for geom, hw in T.AXIS_GEOMS for c in (4, 3) for relu in (0, 1)]
 
 
 def _exact(o):
@@ -30,7 +31,7 @@ def _unit(k, s, p, relu):
     return f
 
 
-@pytest.mark.parametrize("geom, hw, c, relu", CASES)
+@pytest.mark.parametrize("geom, hw, c, relu", CASES + AXIS_CASES)
 def test_references_equal_autograd(geom, hw, c, relu):
     (k, s, p), (h, w), n = geom, hw, 2
     o, t_a = _exact(T.case(n, c, h, w, k, s, p, 3, 3, 3))
@@ -84,3 +85,22 @@ def test_references_discriminate_the_batch_statistics_corrections(geom, hw, c):
         ratio = float(((moved - r["ga"]).abs() / bound.clamp_min(1e-300))[bound > 0].max())
         print(f"adjoint without {name}: {ratio:.3g} x the bound")
         assert ratio > 1000
+
+
+@pytest.mark.parametrize("geom, hw, c, relu", AXIS_CASES)
+def test_per_axis_cases_tell_an_exchanged_window_apart(geom, hw, c, relu):
+    """The reduction pass (g and both sum rows) and the two-pass ga with (kh, kw), (sh, sw) or (ph, pw) exchanged in the
+    window predicate alone move some element by more than 1000 times the bound the GPU test allows it."""
+    (k, s, p), (h, w) = geom, hw
+    o = T.case(2, c, h, w, k, s, p, 1, 3, 1)
+    y_pool, idx = B.forward(o, k, s, p, relu)
+    r = T.adjoint(o, idx, y_pool, relu, h, w, k, s, p, 3)
+    R_ = 3 * r["windows"] + 2
+    bounds = dict(g=R_ * L.U32 * r["M"], gb=R_ * L.U32 * r["Mb"], gw=(R_ + 4) * L.U32 * r["Mw"],
+                  ga=L.r_chan_affine_train(1, False) * L.U32 * r["Mga"])
+    assert T.R.exchanges(geom)
+    for name, (k2, s2, p2) in T.R.exchanges(geom):
+        r2 = T.adjoint(o, idx, y_pool, relu, h, w, k2, s2, p2, 3)
+        for out, bound in bounds.items():
+            ratio = float(((r2[out] - r[out]).abs() / bound.clamp_min(1e-300))[bound > 0].max())
+            assert ratio > 1000, (name, out, ratio)
