@@ -25,6 +25,33 @@ CONFIGS = ("Small", "Big", "Big96", "Flat96")
 TILE = {0: (64, 64), 1: (128, 128), 2: (128, 96), 3: (96, 128)}   # (BM, BN) per configuration (hf_conv.hip: Cfg)
 BK = {0: 32, 1: 16, 2: 16, 3: 16}
 
+# the geometries of the float-operand tests (``test_conv_gpu.py``, the merged launches of ``test_layer_kernels_gpu.py``,
+# the planner sweep of ``test_host_logic_cpu.py``): (N, H, W, C, K, R, S, stride, padding)
+GEOMS = [
+    (32, 7, 7, 64, 64, 3, 3, (1, 1), (1, 1)),      # ResNet-18 layer1
+    (32, 7, 7, 64, 128, 3, 3, (2, 2), (1, 1)),     # layer2.0.conv1 (7 -> 4)
+    (32, 7, 7, 64, 128, 1, 1, (2, 2), (0, 0)),     # layer2.0.downsample
+    (32, 4, 4, 128, 128, 3, 3, (1, 1), (1, 1)),    # layer2
+    (32, 2, 2, 256, 256, 3, 3, (1, 1), (1, 1)),    # layer3: every tap meets data somewhere
+    (32, 2, 2, 256, 512, 3, 3, (2, 2), (1, 1)),    # layer4.0.conv1: 4 of 9 taps live
+    (32, 1, 1, 512, 512, 3, 3, (1, 1), (1, 1)),    # layer4: centre tap only
+    (32, 7, 7, 128, 64, 3, 3, (1, 1), (1, 1)),     # tangent operands: 2*Cin channels
+    (4, 5, 6, 12, 20, 3, 2, (2, 1), (1, 0)),       # ragged everything
+    (2, 9, 9, 8, 100, 5, 5, (1, 1), (2, 2)),       # K not a multiple of the tile
+    (3, 6, 5, 36, 8, 1, 1, (1, 1), (0, 0)),
+    (8, 16, 16, 96, 96, 3, 3, (1, 1), (1, 1)),     # All-CNN-C-like: many tiles, no split needed
+    (1, 3, 3, 4, 4, 3, 3, (1, 1), (0, 0)),         # one output pixel
+    (3, 8, 8, 3, 6, 3, 3, (1, 1), (1, 1)),         # channel counts not multiples of 4: scalar gathers
+    (32 * 196, 1, 1, 49, 64, 1, 1, (1, 1), (0, 0)),  # the stem as a 1x1 product over its im2col
+    # large-M problems: the 128x128-tile configuration (four accumulators per wave)
+    (32, 32, 32, 96, 96, 3, 3, (1, 1), (1, 1)),    # All-CNN-C conv2: 32768 rows
+    (32, 16, 16, 96, 192, 3, 3, (2, 2), (1, 1)),   # strided, 96 -> 192
+    (8, 16, 16, 192, 192, 3, 3, (1, 1), (0, 0)),   # no padding, ragged row tile (8*14*14 = 1568 rows: small config)
+    (32, 16, 16, 192, 192, 3, 3, (1, 1), (1, 1)),  # All-CNN-C conv5: weight gradient on 96 x 128 tiles, columns flat over (tap, c)
+    (32, 12, 12, 192, 100, 1, 1, (1, 1), (0, 0)),  # 1x1, 100 output channels (ragged column tile)
+    (16, 16, 16, 256, 128, 1, 1, (1, 1), (0, 0)),  # ResNet-50-like 1x1 reduction
+]
+
 # d: 0 forward, 1 data gradient, 2 weight gradient; act_ld / mat_ld: 0 = dense; splits: 0 = the planner's choice
 Problem = namedtuple("Problem", "d n h w c k r s stride pad act_ld mat_ld splits")
 # what the planner must answer: configuration, scalar gathers, taps per residue class (() = plain enumeration), live

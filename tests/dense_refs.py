@@ -12,6 +12,7 @@ import numpy as np
 U32 = 2.0 ** -24
 KSTEP, MAX_SPLITS, MAX_ROWS = 32, 32, 256
 IDENTITY, RELU, TANH = 0, 1, 2
+ACTS = (IDENTITY, RELU, TANH)
 
 # (rows, c_in, c_out): one element | odd everything | the mwe net | small_nn's last layer | just over one row tile with
 # ragged columns | whole tiles | c_in over two 128-column blocks, c_out over one | one row over two tiles | full batch

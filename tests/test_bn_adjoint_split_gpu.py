@@ -13,77 +13,10 @@ import torch
 from tol import within
 
 import layer_refs as L
+from guarded import DEV, ERR_ARG, GAP, GUARD, P, FlatOut, _ids, bits_equal, optr, ptr, slabs_dev, st, twice
 from pytorchhessianfree_amd import _lib
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-GUARD, GAP = 64, 8
-NAN = float("nan")
-P = _lib.c_void_p
-ERR_ARG = _lib.HF_ERR_ARG
-_ids = lambda v: str(v).replace(" ", "")  # noqa: E731
-
-
-def st():
-    return _lib.current_stream_ptr(torch.device(DEV))
-
-
-class Out:
-    """``n`` words between two guard regions, everything NaN."""
-
-    def __init__(self, n, shape=None):
-        self.n, self.shape = n, shape
-        self.buf = torch.full((n + 2 * GUARD,), NAN, device=DEV)
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + 4 * GUARD
-
-    @property
-    def val(self):
-        v = self.buf[GUARD:GUARD + self.n]
-        return v.view(self.shape) if self.shape else v
-
-    def guards_intact(self):
-        return bool(torch.isnan(self.buf[:GUARD]).all()) and bool(torch.isnan(self.buf[GUARD + self.n:]).all())
-
-    def same(self, other):
-        return torch.equal(self.buf.view(torch.int32), other.buf.view(torch.int32))
-
-    def all_nan(self):
-        return bool(torch.isnan(self.buf).all())
-
-
-def optr(o):
-    return o.ptr if o is not None else None
-
-
-def ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-def bits_equal(a, b):
-    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def slabs(t):
-    """[s, rows, c] -> the slabs ``rows*c + GAP`` words apart in one device buffer whose gaps hold NaN; (tensor, stride)."""
-    if t is None:
-        return None, 0
-    s, n = t.shape[0], t[0].numel()
-    buf = torch.full((s, n + GAP), NAN)
-    buf[:, :n] = t.reshape(s, n)
-    return buf.to(DEV), n + GAP
-
-
-def twice(launch):
-    a, b = launch(), launch()
-    torch.cuda.synchronize()
-    for x, y in zip(a, b):
-        if x is not None:
-            assert x.same(y), "two launches on the same inputs differ"
-            assert x.guards_intact(), "a guard word was written"
-    return a
 
 
 def rb_for(rows, c, i):
@@ -108,15 +41,16 @@ class Problem:
         mask, w = (o.mask if use_mask else None), (o.w if use_w else None)
         self.ref = L.bn_adjoint_pre(o.a, o.b, mask, w, o.rstd)
         self.mask_host = mask
-        (self.a, self.la), (self.b, self.lb) = slabs(o.a), slabs(o.b)
+        self.la, self.lb = self.rows * self.c + GAP, (self.rows * self.c + GAP if o.b is not None else 0)
+        self.a, self.b = slabs_dev(o.a, self.la), slabs_dev(o.b, self.lb)
         self.mask, self.w, self.rstd = (t.to(DEV) if t is not None else None for t in (mask, w, o.rstd))
         self.rb = rb
 
     def outs(self):
-        return Out(self.rows * self.c, (self.rows, self.c)), Out(self.rows * self.c, (self.rows, self.c))
+        return tuple(FlatOut(self.rows * self.c, front=GUARD, shape=(self.rows, self.c)) for _ in range(2))
 
     def fused(self, lib):
-        gx, gres, gb = *self.outs(), Out(self.rb * self.c)
+        gx, gres, gb = *self.outs(), FlatOut(self.rb * self.c, front=GUARD)
         _lib.check(lib.hf_chan_affine_bwd_ex(
             gx.ptr, None, gb.ptr, gres.ptr, ptr(self.a), self.s1, self.la, ptr(self.b), self.s2 or 1, self.lb, None, None,
             ptr(self.rstd), ptr(self.w), ptr(self.mask), self.rows, self.c, 1, 1, self.rb, _lib.HF_F32, st()),
@@ -218,7 +152,7 @@ class SumsProblem:
 
     def outs(self):
         n = self.rb * self.c
-        return (Out(n) if "w" in self.form else None), (Out(n) if "b" in self.form else None)
+        return tuple(FlatOut(n, front=GUARD) if k in self.form else None for k in "wb")
 
     def fused(self, lib):
         gw, gb = self.outs()
@@ -273,7 +207,7 @@ def test_sums_multi_equals_the_fused_launch_bit_for_bit(count, first, launched):
                 assert (got is None) == (want is None)
                 assert got is None or got.same(want), f"problem {j}: partial rows differ from the fused launch's"
         else:
-            assert all(o is None or o.all_nan() for o in (gw, gb)), f"problem {j} is outside the range but was written"
+            assert all(o is None or o.pristine() for o in (gw, gb)), f"problem {j} is outside the range but was written"
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -284,14 +218,14 @@ def test_refusals_write_nothing():
     rows = 8
     src = torch.ones(rows * 12 + 8, device=DEV)
     vec = torch.ones(16, device=DEV)
-    g, ga = Out(rows * 12), Out(rows * 12)
+    g, ga = FlatOut(rows * 12, front=GUARD), FlatOut(rows * 12, front=GUARD)
 
     def v4(gp, gap, gy, c, slab=0, s1=1, rstd=vec.data_ptr()):
         return lib.hf_bn_adjoint_v4(gp, gap, gy, s1, slab, None, 1, 0, None, None, rstd, rows, c, _lib.HF_F32, st())
 
     assert v4(g.ptr, ga.ptr, src.data_ptr(), 6) == ERR_ARG               # c % 4 != 0
     assert v4(g.ptr, ga.ptr, src.data_ptr() + 4, 12) == ERR_ARG          # a misaligned cotangent
-    assert v4(g.ptr + 4, ga.ptr, src.data_ptr(), 12) == ERR_ARG          # a misaligned output
+    assert v4(P(g.ptr.value + 4), ga.ptr, src.data_ptr(), 12) == ERR_ARG          # a misaligned output
     assert v4(g.ptr, ga.ptr, src.data_ptr(), 12, rstd=vec.data_ptr() + 4) == ERR_ARG
     assert v4(g.ptr, ga.ptr, src.data_ptr(), 12, slab=rows * 12 + 2, s1=2) == ERR_ARG  # a slab stride off the quads
     assert v4(None, None, src.data_ptr(), 12) == ERR_ARG
@@ -335,4 +269,4 @@ def test_refusals_write_nothing():
     bad[2].block0 += 1                                                    # derived fields that are not the builder's
     assert multi(bad, 0, 4) == ERR_ARG
     torch.cuda.synchronize()
-    assert g.all_nan() and ga.all_nan(), "a refused call wrote something"
+    assert g.pristine() and ga.pristine(), "a refused call wrote something"

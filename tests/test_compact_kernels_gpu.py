@@ -11,20 +11,11 @@ import pytest
 import torch
 
 import compact_refs as cr
+from guarded import DEV, GUARD, NAN, P, Payload, dev
 from pytorchhessianfree_amd import _lib
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-GUARD = 64
-NAN = pr.NAN
-P = _lib.c_void_p
 _CODE = {np.float32: _lib.HF_F32, np.float64: _lib.HF_F64}
-
-
-def _dev(a):
-    t = torch.from_numpy(a).to(DEV)
-    assert t.numel() == 0 or t.data_ptr() % 16 == 0
-    return t
 
 
 def _seed(*key):
@@ -33,14 +24,6 @@ def _seed(*key):
 
 def _i64(vals):
     return (_lib.c_int64 * len(vals))(*[int(v) for v in vals])
-
-
-def _guarded(payload):
-    """``payload`` on the device between GUARD NaN sentinels; returns (whole buffer, payload view, host image)."""
-    guard = np.full(GUARD, NAN, payload.dtype)
-    host = np.concatenate([guard, payload, guard])
-    buf = _dev(host)
-    return buf, buf[GUARD:GUARD + payload.size], host
 
 
 # ---- gather ------------------------------------------------------------------------------------------------------------
@@ -56,7 +39,7 @@ def test_gather_into_the_compact_layout_is_the_compact_image_of_the_flat_gather(
     size = np.dtype(dtype).itemsize
     tensors, perms, splits, live = [], {}, {}, {}
     for i, (buf, s) in enumerate(zip(bufs, case.srcs)):
-        t = _dev(buf)[s.src_off:s.src_off + s.numel]
+        t = dev(buf)[s.src_off:s.src_off + s.numel]
         assert s.numel == 0 or t.data_ptr() % 16 == s.src_off * size % 16
         tensors.append(t)
         if s.perm:
@@ -75,12 +58,11 @@ def test_gather_into_the_compact_layout_is_the_compact_image_of_the_flat_gather(
         before = rng.randint(-4, 5, size=idx.size).astype(dtype) if mode == 1 else np.full(idx.size, NAN, dtype)
         flat_before = np.zeros(n, dtype)
         flat_before[idx] = before
-        buf, view, host = _guarded(before)
-        _lib.pack_ex(view, tensors, perms, splits, scale=scale, live=live, mode=mode, compact=compact)
+        dst = Payload(before)
+        _lib.pack_ex(dst.t, tensors, perms, splits, scale=scale, live=live, mode=mode, compact=compact)
         want = pr.pack_ref(flat_before, sources, scale, mode)[idx]
         assert not np.isnan(want).any()
-        host[GUARD:GUARD + idx.size] = want
-        got = buf.cpu().numpy()
+        got, host = dst.after(), dst.expect(want)
         bad = np.nonzero(~((got == host) | (np.isnan(got) & np.isnan(host))))[0]
         assert bad.size == 0, (scale, bad.size, int(bad[0]) - GUARD, got[bad[0]], host[bad[0]])
 
@@ -125,7 +107,7 @@ def _scatter_setup(I, front, dtype):
                 out.append((int(offs_f[k0 + k]), buf, I, s.live))
         return out
 
-    return _dev(v), _dev(vc), slots
+    return dev(v), dev(vc), slots
 
 
 def _same_buffers(a, b):
@@ -200,14 +182,14 @@ def test_live_copy_of_rows_moves_every_row_in_one_launch(dtype):
     rows, fs, cs = 3, n + 3, idx.size + 5
     full = np.random.RandomState(2).standard_normal((rows, fs)).astype(dtype)
     comp = np.full((rows, cs), NAN, dtype)
-    dfull, dcomp = _dev(full), _dev(comp)
+    dfull, dcomp = dev(full), dev(comp)
     lib = _lib.load()
     assert lib.hf_live_copy_rows(P(dfull.data_ptr()), P(dcomp.data_ptr()), 0, rows, fs, cs, *cols, len(segs), _CODE[dtype],
                                  None) == 0
     want = comp.copy()
     want[:, :idx.size] = full[:, idx]
     assert pr.same(dcomp.cpu().numpy(), want)
-    back = _dev(np.zeros((rows, fs), dtype))
+    back = dev(np.zeros((rows, fs), dtype))
     assert lib.hf_live_copy_rows(P(back.data_ptr()), P(dcomp.data_ptr()), 1, rows, fs, cs, *cols, len(segs), _CODE[dtype],
                                  None) == 0
     wantb = np.zeros((rows, fs), dtype)
@@ -228,7 +210,7 @@ def test_dead_entry_check(front, dtype):
     flag = torch.full((1,), 7, dtype=torch.int32, device=DEV)
 
     def check(a, b):
-        da, db = _dev(a), (None if b is None else _dev(b))
+        da, db = dev(a), (None if b is None else dev(b))
         rc = lib.hf_live_dead_check(P(da.data_ptr()), None if db is None else P(db.data_ptr()), P(flag.data_ptr()), *cols,
                                     len(segs), _CODE[dtype], None)
         assert rc == 0

@@ -13,37 +13,10 @@ from tol import within
 
 import dense_diag_refs as ddr
 import dense_refs as dr
-from dense_guarded import DEV, ERR_ARG, F32, GUARD, NAN, In, P, _ids, st
+from guarded import DEV, ERR_ARG, F32, GUARD, NAN, FlatOut, In, P, _ids, st, twice
 from pytorchhessianfree_amd import _lib
 
 pytestmark = pytest.mark.gpu
-
-
-class Out:
-    """``numel`` output elements ``off`` floats behind a 16-byte boundary of a NaN-filled buffer, GUARD words on either
-    side."""
-
-    def __init__(self, numel, off):
-        self.numel, self.lo = numel, GUARD + off
-        self.buf = torch.full((GUARD + off + numel + GUARD,), NAN, device=DEV)
-        self.ptr = P(self.buf.data_ptr() + 4 * self.lo)
-
-    def val(self, shape):
-        return self.buf[self.lo:self.lo + self.numel].reshape(shape).cpu().numpy()
-
-    def untouched(self):
-        return bool(torch.isnan(self.buf[:self.lo]).all()) and bool(torch.isnan(self.buf[self.lo + self.numel:]).all())
-
-    def same(self, other):
-        return torch.equal(self.buf.view(torch.int32), other.buf.view(torch.int32))
-
-
-def twice(launch):
-    a, b = launch(), launch()
-    torch.cuda.synchronize()
-    assert a.same(b), "two launches on the same inputs differ"
-    assert a.untouched(), "a guard word before or behind the output was written"
-    return a
 
 
 @pytest.mark.parametrize("off", (0, 1))
@@ -55,14 +28,14 @@ def test_sq_wgrad(shape, off):
     for scale in (1.0, 1.0 / rows):
 
         def launch():
-            out = Out(c_out * c_in, off)
+            out = FlatOut(c_out * c_in, off, front=GUARD)
             rc = lib.hf_dense_sq_wgrad(out.ptr, g.ptr, x.ptr, rows, c_in, c_out, scale, F32, st())
             assert rc == 0, rc
             return out
 
         out = twice(launch)
         want, M, L = ddr.sq_wgrad(c["g"], c["x"], scale)
-        within(dr.ratio(out.val((c_out, c_in)), want, M, L + ddr.R_SQ_WGRAD), 1.0, note=(shape, off, scale))
+        within(dr.ratio(out.val.view(c_out, c_in).cpu().numpy(), want, M, L + ddr.R_SQ_WGRAD), 1.0, note=(shape, off, scale))
 
 
 @pytest.mark.parametrize("off", (0, 1))
@@ -74,14 +47,14 @@ def test_sq_colsum(shape, off):
     for scale in (1.0, 1.0 / rows):
 
         def launch():
-            out = Out(c, off)
+            out = FlatOut(c, off, front=GUARD)
             rc = lib.hf_dense_sq_colsum(out.ptr, g.ptr, rows, c, scale, F32, st())
             assert rc == 0, rc
             return out
 
         out = twice(launch)
         want, M = ddr.sq_colsum(cs["g"], scale)
-        within(dr.ratio(out.val((c,)), want, M, ddr.R_SQ_COLSUM), 1.0, note=(shape, off, scale))
+        within(dr.ratio(out.val.cpu().numpy(), want, M, ddr.R_SQ_COLSUM), 1.0, note=(shape, off, scale))
 
 
 def test_sq_entry_points_refuse_bad_arguments():

@@ -17,7 +17,7 @@ from tol import within
 
 import dense_hess_refs as hr
 import dense_refs as dr
-from dense_guarded import ACTS, DEV, ERR_ARG, F32, NAN, In, Out, P, _ids, pp, st, twice
+from guarded import DEV, ERR_ARG, F32, NAN, FlatOut, In, P, _ids, pp, st, twice
 from pytorchhessianfree_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -38,14 +38,14 @@ def test_wgrad2(shape, off):
     ops = [In(c[k], off) for k in ("g", "x", "g1", "t_x")]
 
     def launch():
-        out = Out(c_out * c_in, off)
+        out = FlatOut(c_out * c_in, off)
         rc = lib.hf_dense_wgrad2(out.ptr, *[pp(o) for o in ops], rows, c_in, c_out, c["scale"], F32, st())
         assert rc == 0, rc
         return (out,)
 
     (out,) = twice(launch)
     want, M, L = hr.wgrad2(c["g"], c["x"], c["g1"], c["t_x"], c["scale"])
-    within(dr.ratio(out.val((c_out, c_in))[0], want, M, L + hr.R_WGRAD2), 1.0, note=(shape, off))
+    within(dr.ratio(out.val.view(c_out, c_in).cpu().numpy(), want, M, L + hr.R_WGRAD2), 1.0, note=(shape, off))
 
 
 # ---- D2 --------------------------------------------------------------------------------------------------------------
@@ -59,18 +59,18 @@ def test_dgrad2_slabs(shape, off):
         stride = rows * c_in + (5 if splits > 1 else 0)
 
         def launch():
-            out = Out(rows * c_in, off, splits, stride)
+            out = FlatOut(rows * c_in, off, splits, stride)
             rc = lib.hf_dense_dgrad2_slabs(out.ptr, *[pp(o) for o in ops], rows, c_in, c_out, splits, stride, F32, st())
             assert rc == 0, rc
             return (out,)
 
         (out,) = twice(launch)
         want, M, L = hr.dgrad2_slabs(c["g"], c["W"], c["g1"], c["V"], splits)
-        within(dr.ratio(out.val((rows, c_in)), want, M, L + dr.R_SLAB), 1.0, note=(shape, off, splits))
+        within(dr.ratio(out.body.reshape(-1, rows, c_in).cpu().numpy(), want, M, L + dr.R_SLAB), 1.0, note=(shape, off, splits))
 
 
 # ---- the elementwise pass --------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("act", ACTS)
+@pytest.mark.parametrize("act", dr.ACTS)
 @pytest.mark.parametrize("off", (0, 1))
 @pytest.mark.parametrize("shape", dr.SHAPES, ids=_ids)
 def test_act_adjoint2(shape, off, act):
@@ -91,7 +91,7 @@ def test_act_adjoint2(shape, off, act):
                 curv = [(None, None), (In(nan, off), In(nan, off))]
             for ty_in, h_in in curv:
                 def launch():
-                    ga, gb = Out(rows * c, off), (Out(c, off) if with_b else None)
+                    ga, gb = FlatOut(rows * c, off), (FlatOut(c, off) if with_b else None)
                     rc = lib.hf_dense_act_adjoint2(ga.ptr, pp(gb), s_in.ptr, splits, stride, y_in.ptr, act, pp(ty_in),
                                                    pp(h_in), rows, c, cs["scale"], F32, st())
                     assert rc == 0, rc
@@ -99,13 +99,13 @@ def test_act_adjoint2(shape, off, act):
 
                 ga, gb = twice(launch)
                 want_a, Ma, want_b, Mb = hr.act_adjoint2(slabs, y, act, t_y, h, cs["scale"])
-                within(dr.ratio(ga.val((rows, c))[0], want_a, Ma, hr.r_act2(splits, act)), 1.0,
+                within(dr.ratio(ga.val.view(rows, c).cpu().numpy(), want_a, Ma, hr.r_act2(splits, act)), 1.0,
                        note=(shape, off, act, splits))
                 if with_b:
-                    within(dr.ratio(gb.val((c,))[0], want_b, Mb, hr.r_bias2(splits, act)), 1.0,
+                    within(dr.ratio(gb.val.cpu().numpy(), want_b, Mb, hr.r_bias2(splits, act)), 1.0,
                            note=(shape, off, act, splits))
                 if act != dr.TANH:  # bitwise hf_dense_act_adjoint on the same inputs
-                    ga1, gb1 = Out(rows * c, off), (Out(c, off) if with_b else None)
+                    ga1, gb1 = FlatOut(rows * c, off), (FlatOut(c, off) if with_b else None)
                     assert lib.hf_dense_act_adjoint(ga1.ptr, pp(gb1), s_in.ptr, splits, stride, y_in.ptr, act, rows, c,
                                                     cs["scale"], F32, st()) == 0
                     torch.cuda.synchronize()
@@ -132,7 +132,7 @@ def test_hessian_entry_points_refuse_bad_arguments():
     assert D2(b, b, b, b, b, 4, 4, 40, 33, 16, F32, s) == ERR_ARG    # splits > 32
     assert D2(b, b, b, b, b, 4, 4, 64, 3, 16, F32, s) == ERR_ARG     # the third split would be empty
     assert D2(b, b, b, b, b, 4, 4, 40, 2, 15, F32, s) == ERR_ARG     # slabs would overlap
-    for act in ACTS:
+    for act in dr.ACTS:
         assert J2(None, b, b, 1, 0, b, act, b, b, 4, 4, 1.0, F32, s) == ERR_ARG   # no output
         assert J2(b, b, None, 1, 0, b, act, b, b, 4, 4, 1.0, F32, s) == ERR_ARG   # no slabs
         assert J2(b, b, b, 0, 0, b, act, b, b, 4, 4, 1.0, F32, s) == ERR_ARG and J2(b, b, b, 33, 16, b, act, b, b, 4, 4, 1.0, F32, s) == ERR_ARG

@@ -15,7 +15,7 @@ import torch
 from tol import within
 
 import dense_refs as dr
-from dense_guarded import ACTS, DEV, ERR_ARG, F32, NAN, Out, P, _ids, ip, pp, st, twice
+from guarded import DEV, ERR_ARG, F32, NAN, FlatOut, P, _ids, ip, pp, st, twice
 from pytorchhessianfree_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -50,7 +50,7 @@ def test_tangent_slabs(shape, off):
             stride = rows * c_out + (3 if splits > 1 else 0)
 
             def launch():
-                out = Out(rows * c_out, off, splits, stride)
+                out = FlatOut(rows * c_out, off, splits, stride)
                 rc = lib.hf_dense_tangent_slabs(out.ptr, *[pp(o) for o in ops], rows, c_in, c_out, 0, splits, stride, F32,
                                                 st())
                 assert rc == 0, rc
@@ -58,7 +58,7 @@ def test_tangent_slabs(shape, off):
 
             (out,) = twice(launch)
             want, M, L = dr.tangent_slabs(t_x, c["x"], c["W"], V, splits)
-            within(dr.ratio(out.val((rows, c_out)), want, M, L + dr.R_SLAB), 1.0, note=(shape, off, splits, k_tx, k_v))
+            within(dr.ratio(out.body.reshape(-1, rows, c_out).cpu().numpy(), want, M, L + dr.R_SLAB), 1.0, note=(shape, off, splits, k_tx, k_v))
 
 
 def test_tangent_slabs_row_pitch():
@@ -69,14 +69,14 @@ def test_tangent_slabs_row_pitch():
     ops = [ip(wide(c["t_x"]), 0), ip(wide(c["x"]), 0), ip(c["W"], 0), ip(c["V"], 0)]
 
     def launch():
-        out = Out(rows * c_out, 0, 2, rows * c_out)
+        out = FlatOut(rows * c_out, 0, 2, rows * c_out)
         assert lib.hf_dense_tangent_slabs(out.ptr, *[pp(o) for o in ops], rows, c_in, c_out, ld, 2, rows * c_out, F32,
                                           st()) == 0
         return (out,)
 
     (out,) = twice(launch)
     want, M, L = dr.tangent_slabs(c["t_x"], c["x"], c["W"], c["V"], 2)
-    within(dr.ratio(out.val((rows, c_out)), want, M, L + dr.R_SLAB), 1.0)
+    within(dr.ratio(out.body.reshape(-1, rows, c_out).cpu().numpy(), want, M, L + dr.R_SLAB), 1.0)
 
 
 # ---- D ---------------------------------------------------------------------------------------------------------------
@@ -90,14 +90,14 @@ def test_dgrad_slabs(shape, off):
         stride = rows * c_in + (5 if splits > 1 else 0)
 
         def launch():
-            out = Out(rows * c_in, off, splits, stride)
+            out = FlatOut(rows * c_in, off, splits, stride)
             rc = lib.hf_dense_dgrad_slabs(out.ptr, *[pp(o) for o in ops], rows, c_in, c_out, splits, stride, F32, st())
             assert rc == 0, rc
             return (out,)
 
         (out,) = twice(launch)
         want, M, L = dr.dgrad_slabs(c["g"], c["W"], splits)
-        within(dr.ratio(out.val((rows, c_in)), want, M, L + dr.R_SLAB), 1.0, note=(shape, off, splits))
+        within(dr.ratio(out.body.reshape(-1, rows, c_in).cpu().numpy(), want, M, L + dr.R_SLAB), 1.0, note=(shape, off, splits))
 
 
 # ---- W ---------------------------------------------------------------------------------------------------------------
@@ -109,18 +109,18 @@ def test_wgrad(shape, off):
     ops = [ip(c["g"], off), ip(c["x"], off)]
 
     def launch():
-        out = Out(c_out * c_in, off)
+        out = FlatOut(c_out * c_in, off)
         rc = lib.hf_dense_wgrad(out.ptr, *[pp(o) for o in ops], rows, c_in, c_out, c["scale"], F32, st())
         assert rc == 0, rc
         return (out,)
 
     (out,) = twice(launch)
     want, M, L = dr.wgrad(c["g"], c["x"], c["scale"])
-    within(dr.ratio(out.val((c_out, c_in))[0], want, M, L + dr.R_WGRAD), 1.0, note=(shape, off))
+    within(dr.ratio(out.val.view(c_out, c_in).cpu().numpy(), want, M, L + dr.R_WGRAD), 1.0, note=(shape, off))
 
 
 # ---- the elementwise passes ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("act", ACTS)
+@pytest.mark.parametrize("act", dr.ACTS)
 @pytest.mark.parametrize("off", (0, 1))
 @pytest.mark.parametrize("shape", dr.SHAPES, ids=_ids)
 def test_act_tangent(shape, off, act):
@@ -136,7 +136,7 @@ def test_act_tangent(shape, off, act):
             ops = [ip(padded, off), ip(v_b, off), ip(y, off) if not (act == dr.IDENTITY and v_b is None) else None]
 
             def launch():
-                out = Out(rows * c, off)
+                out = FlatOut(rows * c, off)
                 rc = lib.hf_dense_act_tangent(out.ptr, pp(ops[0]), splits, stride, pp(ops[1]), pp(ops[2]), act, rows, c,
                                               F32, st())
                 assert rc == 0, rc
@@ -144,11 +144,11 @@ def test_act_tangent(shape, off, act):
 
             (out,) = twice(launch)
             want, M = dr.act_tangent(slabs, v_b, y, act)
-            within(dr.ratio(out.val((rows, c))[0], want, M, dr.r_act(splits, v_b is not None, act)), 1.0,
+            within(dr.ratio(out.val.view(rows, c).cpu().numpy(), want, M, dr.r_act(splits, v_b is not None, act)), 1.0,
                    note=(shape, off, act, splits))
 
 
-@pytest.mark.parametrize("act", ACTS)
+@pytest.mark.parametrize("act", dr.ACTS)
 @pytest.mark.parametrize("off", (0, 1))
 @pytest.mark.parametrize("shape", dr.SHAPES, ids=_ids)
 def test_act_adjoint(shape, off, act):
@@ -164,7 +164,7 @@ def test_act_adjoint(shape, off, act):
             ops = [ip(padded, off), ip(y, off)]
 
             def launch():
-                ga, gb = Out(rows * c, off), (Out(c, off) if with_b else None)
+                ga, gb = FlatOut(rows * c, off), (FlatOut(c, off) if with_b else None)
                 rc = lib.hf_dense_act_adjoint(ga.ptr, pp(gb), pp(ops[0]), splits, stride, pp(ops[1]), act, rows, c,
                                               cs["scale"], F32, st())
                 assert rc == 0, rc
@@ -172,10 +172,10 @@ def test_act_adjoint(shape, off, act):
 
             ga, gb = twice(launch)
             want_a, Ma, want_b, Mb = dr.act_adjoint(slabs, y, act, cs["scale"])
-            within(dr.ratio(ga.val((rows, c))[0], want_a, Ma, dr.r_act(splits, False, act)), 1.0,
+            within(dr.ratio(ga.val.view(rows, c).cpu().numpy(), want_a, Ma, dr.r_act(splits, False, act)), 1.0,
                    note=(shape, off, act, splits))
             if with_b:
-                within(dr.ratio(gb.val((c,))[0], want_b, Mb, dr.r_bias(splits, act)), 1.0, note=(shape, off, act, splits))
+                within(dr.ratio(gb.val.cpu().numpy(), want_b, Mb, dr.r_bias(splits, act)), 1.0, note=(shape, off, act, splits))
 
 
 # ---- refusals: one HF_ERR_ARG case per validated field, nothing is launched ---------------------------------------

@@ -22,21 +22,12 @@ import torch.nn.functional as F
 from tol import within
 
 import dense_session_refs as sr
+from guarded import DEV, ERR_ARG, F32, NAN, FlatOut, P, st
 from pytorchhessianfree_amd import _lib
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-GUARD = 64
-NAN = float("nan")
-P = _lib.c_void_p
-ERR_ARG = _lib.HF_ERR_ARG
-F32 = _lib.HF_F32
 DRAWS = 8
 POOL_BELOW = 64  # results of at most this many numbers are pooled over the draws (see above); larger ones: per draw
-
-
-def st():
-    return _lib.current_stream_ptr(torch.device(DEV))
 
 
 def put(arr, off=1):
@@ -46,28 +37,6 @@ def put(arr, off=1):
         torch.zeros(t.numel() + off + 8, dtype=t.dtype, device=DEV)
     buf[off:off + t.numel()].copy_(t)
     return buf, P(buf.data_ptr() + buf.element_size() * off)
-
-
-class Out:
-    """An output of ``numel`` elements behind ``off`` NaN words, GUARD NaN words behind it."""
-
-    def __init__(self, numel, off=1, dtype=torch.float32):
-        self.numel, self.off = numel, off
-        self.buf = torch.full((off + numel + GUARD,), NAN, device=DEV) if dtype.is_floating_point else \
-            torch.full((off + numel + GUARD,), -7, dtype=dtype, device=DEV)
-        self.ptr = P(self.buf.data_ptr() + self.buf.element_size() * off)
-
-    @property
-    def val(self):
-        return self.buf[self.off:self.off + self.numel]
-
-    def untouched(self):
-        rest = torch.cat([self.buf[:self.off], self.buf[self.off + self.numel:]])
-        return bool(torch.isnan(rest).all()) if rest.dtype.is_floating_point else bool((rest == -7).all())
-
-    def pristine(self):
-        return self.untouched() and (bool(torch.isnan(self.val).all()) if self.val.dtype.is_floating_point
-                                     else bool((self.val == -7).all()))
 
 
 def dist(a, b):
@@ -98,7 +67,7 @@ def test_act_forward_is_exact_and_tanh_is_within_three_times_other_fp32_tanh_of_
             b_buf, b_ptr = put(b) if with_b else (None, None)
             outs = {}
             for act in (sr.IDENTITY, sr.RELU, sr.TANH):
-                y, y2 = Out(rows * c), Out(rows * c)
+                y, y2 = FlatOut(rows * c, 1), FlatOut(rows * c, 1)
                 for o in (y, y2):
                     rc = lib.hf_dense_act_forward(o.ptr, s_ptr, splits, stride, b_ptr, act, rows, c, F32, st())
                     assert rc == 0, rc
@@ -129,7 +98,7 @@ def test_act_forward_relu_keeps_a_nan_and_turns_minus_zero_into_plus_zero():
     loss); ``-0`` becomes ``+0``."""
     pre = np.array([[NAN, -0.0, 0.0, -1.5, 2.5]], np.float32)
     s_buf, s_ptr = put(pre)
-    y = Out(5)
+    y = FlatOut(5, 1)
     assert _lib.load().hf_dense_act_forward(y.ptr, s_ptr, 1, 0, None, sr.RELU, 1, 5, F32, st()) == 0
     torch.cuda.synchronize()
     want = torch.relu(torch.from_numpy(pre).to(DEV)).reshape(-1)
@@ -146,7 +115,8 @@ def _ce_call(x, t, reduction, ps=True, off=1):
     xb, xp = put(x, off)
     tb, tp = put(t, off)
     work = torch.full((512,), NAN, dtype=torch.float64, device=DEV)
-    outs = [Out(rows * c, off), Out(rows * c, off), Out(rows * c, off) if ps else None, Out(1), Out(1, dtype=torch.int32)]
+    outs = [FlatOut(rows * c, off), FlatOut(rows * c, off), FlatOut(rows * c, off) if ps else None, FlatOut(1, 1),
+            FlatOut(1, 1, dtype=torch.int32)]
     rc = lib.hf_dense_loss_head(sr.CE, xp, tp, *[None if o is None else o.ptr for o in outs], P(work.data_ptr()), sg, sps,
                                 coef, rows, c, F32, st())
     assert rc == 0, rc
@@ -273,8 +243,9 @@ def test_mse_head_against_float64_and_torch(rows, c, reduction):
         runs = []
         for _ in range(2):
             work = torch.full((512,), NAN, dtype=torch.float64, device=DEV)
-            p = Out(rows * c)  # (not touched by this kind)
-            dl, dl_ps, loss, flag = Out(rows * c), Out(rows * c), Out(1), Out(1, dtype=torch.int32)
+            p = FlatOut(rows * c, 1)  # (not touched by this kind)
+            dl, dl_ps = FlatOut(rows * c, 1), FlatOut(rows * c, 1)
+            loss, flag = FlatOut(1, 1), FlatOut(1, 1, dtype=torch.int32)
             rc = lib.hf_dense_loss_head(sr.MSE, xp, tp, p.ptr, dl.ptr, dl_ps.ptr, loss.ptr, flag.ptr, P(work.data_ptr()),
                                         sg, sps, coef, rows, c, F32, st())
             assert rc == 0, rc

@@ -4,8 +4,8 @@ ABI against the float64 references of ``diag_sq_refs.py``, EXACTLY: the operands
 two, so every intermediate of every split is exactly representable (the module states the condition) and the result
 must equal the reference at every element whatever the split count.
 
-The harness is that of ``test_conv_kernels_gpu.py``: every output lies between GUARD NaN sentinels, slabs are GAP floats
-apart and the gaps are NaN too.  After a launch: guards and gaps untouched; every slab completely written except the
+The outputs are ``guarded.SlabOut``, as in the convolution tests: every output lies between GUARD NaN sentinels, slabs are
+SLAB_GAP floats apart and the gaps are NaN too.  After a launch: guards and gaps untouched; every slab completely written except the
 entries of dead taps, which keep the sentinel and have a zero reference; the float64 sum of the slabs IS the reference; a
 second launch gives the same bits; ``0.5 * pre`` scales the result by exactly 0.25; a refused launch leaves the outputs
 untouched.  Every case runs with the planned split count and with the forced counts 1, 2 and n."""
@@ -15,51 +15,17 @@ import pytest
 import torch
 
 import diag_sq_refs as dr
+from guarded import DEV, GUARD, NAN, P, SlabOut, bits_equal, dev, st
 from pytorchhessianfree_amd import _lib
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-GUARD, GAP = 64, 96
-NAN = dr.NAN
-PTR = _lib.c_void_p
 
 
 def _ids(cases):
     return [c.name for c in cases]
 
 
-def _st():
-    return _lib.current_stream_ptr(torch.device(DEV))
-
-
-def _dev(a):
-    t = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-    assert t.data_ptr() % 16 == 0
-    return t
-
-
-def _bits(t):
-    return t.view(torch.int32)
-
-
-class Out:
-    """``splits`` slabs of ``numel`` floats, ``stride`` = numel (rounded up to a 16-byte multiple) + GAP apart, between
-    GUARD floats on each side; all NaN."""
-
-    def __init__(self, numel, splits):
-        self.numel, self.splits = numel, splits
-        self.stride = -(-numel // 4) * 4 + GAP
-        self.buf = torch.full((2 * GUARD + splits * self.stride,), NAN, device=DEV)
-        self.ptr = self.buf.data_ptr() + 4 * GUARD
-        assert self.ptr % 16 == 0
-        inside = torch.zeros(splits, self.stride, dtype=torch.bool, device=DEV)
-        inside[:, :numel] = True
-        pad = torch.zeros(GUARD, dtype=torch.bool, device=DEV)
-        self.inside = torch.cat([pad, inside.reshape(-1), pad])
-
-    def slabs(self):
-        return self.buf[GUARD:GUARD + self.splits * self.stride].view(self.splits, self.stride)[:, :self.numel]
-
+class Out(SlabOut):
     def check(self, what, want, dead=None):
         """Guards, gaps, complete slabs, dead entries, exact sum (``want``: float64, flat)."""
         assert bool(torch.isnan(self.buf[~self.inside]).all()), "%s: a guard or a gap between slabs was written" % what
@@ -77,10 +43,6 @@ class Out:
             raise AssertionError("%s: %d of %d elements differ from the float64 reference, first at %d: %r != %r" % (
                 what, bad.numel(), got.numel(), i, float(got[i]), float(want[i])))
 
-    def untouched(self):
-        return bool(torch.isnan(self.buf).all())
-
-
 _CONV = {}
 
 
@@ -91,7 +53,7 @@ def _conv(p):
         host = dr.conv_operands(p)
         ref = dr.conv_reference(p, host).reshape(-1).to(DEV)
         assert torch.equal(ref, ref.round()) and float(ref.max()) < dr.EXACT_LIMIT
-        _CONV[p.name] = (_dev(host["x"]), _dev(host["gy"]), ref, torch.from_numpy(dr.dead_mask(p).reshape(-1)).to(DEV))
+        _CONV[p.name] = (dev(host["x"]), dev(host["gy"]), ref, torch.from_numpy(dr.dead_mask(p).reshape(-1)).to(DEV))
     return _CONV[p.name]
 
 
@@ -102,8 +64,8 @@ def _geo(p):
 def _sqsum(p, out, pre, splits=None):
     x, gy = _conv(p)[:2]
     return _lib.load().hf_conv2d_nhwc_sqsum_slabs(
-        PTR(out.ptr), PTR(x.data_ptr()), PTR(gy.data_ptr()), *_geo(p), p.act_ld, p.out_c, pre,
-        out.splits if splits is None else splits, out.stride, _lib.HF_F32, _st())
+        P(out.ptr), P(x.data_ptr()), P(gy.data_ptr()), *_geo(p), p.act_ld, p.out_c, pre,
+        out.splits if splits is None else splits, out.stride, _lib.HF_F32, st())
 
 
 def _split_counts(p):
@@ -125,7 +87,7 @@ def test_conv_sqsum_equals_float64_exactly_at_every_split_count(p):
         first = out.buf.clone()
         _lib.check(_sqsum(p, out, dr.PRE), what)
         torch.cuda.synchronize()
-        assert torch.equal(_bits(out.buf), _bits(first)), "%s: a second launch gives other bits" % what
+        assert bits_equal(out.buf, first), "%s: a second launch gives other bits" % what
         half = Out(numel, splits)
         _lib.check(_sqsum(p, half, 0.5 * dr.PRE), what)
         torch.cuda.synchronize()
@@ -156,31 +118,31 @@ def test_refused_split_counts_leave_the_outputs_untouched(n, splits):
     ch = dr.CHAN_CASES[0]
     g = torch.zeros(n, ch.hw, ch.c, device=DEV)
     rows = Out(ch.c * max(splits, 1), 1)
-    rc = _lib.load().hf_chan_sqsum(None, PTR(rows.ptr), PTR(g.data_ptr()), None, None, None, n, ch.c, ch.hw, dr.PRE,
-                                   splits, _lib.HF_F32, _st())
+    rc = _lib.load().hf_chan_sqsum(None, P(rows.ptr), P(g.data_ptr()), None, None, None, n, ch.c, ch.hw, dr.PRE,
+                                   splits, _lib.HF_F32, st())
     assert rc == _lib.HF_ERR_ARG
     torch.cuda.synchronize()
-    assert out.untouched() and rows.untouched()
+    assert out.pristine() and rows.pristine()
 
 
 def _chan(p, row_blocks, pre, gw2=True, gb2=True, x=True):
     host = dr.chan_operands(p)
-    dev = {k: _dev(v) for k, v in host.items()}
+    ops = {k: dev(v) for k, v in host.items()}
     # (partial rows are c elements apart by the ABI: dense rows between guards)
     bw = torch.full((2 * GUARD + row_blocks * p.c,), NAN, device=DEV)
     bb = torch.full((2 * GUARD + row_blocks * p.c,), NAN, device=DEV)
 
     def launch():
         _lib.check(_lib.load().hf_chan_sqsum(
-            PTR(bw.data_ptr() + 4 * GUARD) if gw2 else None, PTR(bb.data_ptr() + 4 * GUARD) if gb2 else None,
-            PTR(dev["g"].data_ptr()), *((PTR(dev[k].data_ptr()) if x else None) for k in ("x", "mean", "rstd")),
-            p.n, p.c, p.hw, pre, row_blocks, _lib.HF_F32, _st()), "hf_chan_sqsum")
+            P(bw.data_ptr() + 4 * GUARD) if gw2 else None, P(bb.data_ptr() + 4 * GUARD) if gb2 else None,
+            P(ops["g"].data_ptr()), *((P(ops[k].data_ptr()) if x else None) for k in ("x", "mean", "rstd")),
+            p.n, p.c, p.hw, pre, row_blocks, _lib.HF_F32, st()), "hf_chan_sqsum")
         torch.cuda.synchronize()
 
     launch()
     first = (bw.clone(), bb.clone())
     launch()
-    assert torch.equal(_bits(bw), _bits(first[0])) and torch.equal(_bits(bb), _bits(first[1])), "second launch: other bits"
+    assert bits_equal(bw, first[0]) and bits_equal(bb, first[1]), "second launch: other bits"
     want_w, want_b = dr.chan_reference(p, host, pre, with_x=x)
     for buf, on, want in ((bw, gw2, want_w), (bb, gb2, want_b)):
         assert bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[GUARD + row_blocks * p.c:]).all())

@@ -625,11 +625,11 @@ def test_path_report_names_the_path_of_every_call():
 
 def conv_plan_geometries():
     """The geometries of ``tests/golden/conv_plan.npz``, rows of (direction, n, h, w, c, k, r, s, stride_h, stride_w,
-    pad_h, pad_w): the shapes of ``test_conv_gpu.GEOMS``; every convolution of the three bench topologies at batch 32,
+    pad_h, pad_w): the shapes of ``conv_refs.GEOMS``; every convolution of the three bench topologies at batch 32,
     each also with 2c input channels (the tangent operand); the stem as a product over its im2col; a grid over strides,
     pads, windows and map heights; geometries the planner refuses."""
+    from conv_refs import GEOMS
     from pytorchhessianfree_amd import testproblems as tp
-    from test_conv_gpu import GEOMS
 
     geoms = [(n, h, w, c, k, r, s, *st, *pd) for n, h, w, c, k, r, s, st, pd in GEOMS]
     for net, shape in ((tp.ResNet18(), (1, 28, 28)), (tp.AllCNNC(), (3, 32, 32)), (tp.ResNet50(), (3, 64, 64))):

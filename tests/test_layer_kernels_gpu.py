@@ -13,76 +13,13 @@ import pytest
 import torch
 from tol import within
 
+from conv_refs import GEOMS
+from guarded import DEV, ERR_ARG, GUARD, NAN, P, RowOut, _ids, dv, optr, p, st, twice, wide
 import layer_refs as L
 from layer_refs import U32, U64
 from pytorchhessianfree_amd import _lib
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-GUARD = 64
-NAN = float("nan")
-P = _lib.c_void_p
-ERR_ARG = _lib.HF_ERR_ARG
-
-
-def p(t):
-    return P(t.data_ptr()) if t is not None else None
-
-
-def dv(t):
-    return t.to(DEV).contiguous() if t is not None else None
-
-
-def st():
-    return _lib.current_stream_ptr(torch.device(DEV))
-
-
-class Out:
-    """An output of ``rows`` x ``c`` elements inside a NaN-filled buffer: pixel stride ``ld`` (0 = dense), ``extra``
-    more rows that must stay untouched, and GUARD words behind it."""
-
-    def __init__(self, rows, c, ld=0, extra=0, dtype=torch.float32):
-        self.rows, self.c, self.w = rows, c, (ld or c)
-        self.buf = torch.full(((rows + extra) * self.w + GUARD,), NAN, device=DEV, dtype=dtype)
-
-    @property
-    def ptr(self):
-        return P(self.buf.data_ptr())
-
-    @property
-    def val(self):
-        return self.buf[:self.rows * self.w].view(self.rows, self.w)[:, :self.c]
-
-    def untouched(self):
-        body = self.buf[:self.rows * self.w].view(self.rows, self.w)[:, self.c:]
-        return bool(torch.isnan(body).all()) and bool(torch.isnan(self.buf[self.rows * self.w:]).all())
-
-    def same(self, other):
-        iv = torch.int32 if self.buf.dtype == torch.float32 else torch.int64
-        return torch.equal(self.buf.view(iv), other.buf.view(iv))
-
-
-def optr(o):
-    return o.ptr if o is not None else None
-
-
-def wide(t, ld):
-    """[rows, c] -> the first-c-channels slice of a [rows, ld] device buffer whose other channels hold NaN."""
-    if t is None or not ld:
-        return dv(t)
-    buf = torch.full((t.shape[0], ld), NAN, dtype=t.dtype)
-    buf[:, :t.shape[1]] = t
-    return buf.to(DEV)
-
-
-def twice(launch):
-    a, b = launch(), launch()
-    torch.cuda.synchronize()
-    for x, y in zip(a, b):
-        if x is not None:
-            assert x.same(y), "two launches on the same inputs differ"
-            assert x.untouched(), "a guard word or the other half of a wider buffer was written"
-    return a
 
 
 def _ld(v, c):
@@ -90,7 +27,6 @@ def _ld(v, c):
 
 
 CASES = L.eval_cases()
-_ids = lambda v: str(v).replace(" ", "")  # noqa: E731
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -130,7 +66,7 @@ def test_chan_affine_ex_against_float64(shape, slabs, i):
     n, hw = (k.rows, 1) if i % 2 else (1, k.rows)
 
     def launch():
-        out = Out(k.rows, k.c, k.ld)
+        out = RowOut(k.rows, k.c, k.ld)
         _lib.check(lib.hf_chan_affine_ex(out.ptr, *(p(t) for t in k.dev), k.v.relu_self, n, k.c, hw, 1, k.ld, k.add_ld,
                                          k.s1, k.rows * k.c, _lib.HF_F32, st()), "hf_chan_affine_ex")
         return (out,)
@@ -152,7 +88,7 @@ def test_chan_affine_pair_against_float64(pair):
     def launch():
         arr, outs = (_lib.AffineProblem * 2)(), []
         for q, k in zip(arr, ks):
-            out = Out(k.rows, k.c, k.ld)
+            out = RowOut(k.rows, k.c, k.ld)
             outs.append(out)
             q.out = out.buf.data_ptr()
             for name, t in zip(("a", "x", "mean", "rstd", "w", "q", "r", "add", "mask_src"), k.dev):
@@ -177,8 +113,8 @@ def _bwd_case(shape, slabs, i, rb):
 
 
 def _bwd_outs(k):
-    return [None if "gx" in k.drop else Out(k.rows, k.c), None if "gw" in k.drop else Out(k.rb, k.c, extra=2),
-            None if "gb" in k.drop else Out(k.rb, k.c, extra=2), None if "gres" in k.drop else Out(k.rows, k.c)]
+    return [None if "gx" in k.drop else RowOut(k.rows, k.c), None if "gw" in k.drop else RowOut(k.rb, k.c, extra=2),
+            None if "gb" in k.drop else RowOut(k.rb, k.c, extra=2), None if "gres" in k.drop else RowOut(k.rows, k.c)]
 
 
 def _check_bwd(k, outs):
@@ -308,7 +244,7 @@ def test_bn_adjoint_pre_against_float64(shape, slabs, i):
     mode = i % 3  # both outputs / g_out only / ga_out only
 
     def launch():
-        g, ga = (Out(rows, c) if mode != 2 else None), (Out(rows, c) if mode != 1 else None)
+        g, ga = (RowOut(rows, c) if mode != 2 else None), (RowOut(rows, c) if mode != 1 else None)
         _lib.check(lib.hf_bn_adjoint_pre(optr(g), optr(ga), p(a), s1, rows * c, p(b), s2 or 1, rows * c, p(m_), p(w_),
                                          p(rstd), rows, c, _lib.HF_F32, st()), "hf_bn_adjoint_pre")
         return g, ga
@@ -340,8 +276,8 @@ def test_bn_forward_against_float64(shape, slabs, i):
     lib = _lib.load()
 
     def launch():
-        y, y2 = (Out(rows, c) if mode != 2 else None), (Out(rows, c, y2_ld) if mode != 1 else None)
-        a_out = Out(rows, c) if i % 2 else None
+        y, y2 = (RowOut(rows, c) if mode != 2 else None), (RowOut(rows, c, y2_ld) if mode != 1 else None)
+        a_out = RowOut(rows, c) if i % 2 else None
         a, mu, rs, w_, b_, r_ = dev
         _lib.check(lib.hf_bn_forward(optr(y), optr(y2), y2_ld if y2 is not None else 0, optr(a_out), p(a), s1, rows * c,
                                      p(mu), p(rs), p(w_), p(b_), p(r_), res_ld, relu, rows, c, _lib.HF_F32, st()),
@@ -478,7 +414,7 @@ def test_bn_adjoint_pre_fp64_against_longdouble_float64(i):
     a, b, m_, w_, rstd = dv(o.a), dv(o.b), dv(o.mask), dv(o.w), dv(o.rstd)
 
     def launch():
-        g, ga = Out(rows, c, dtype=torch.float64), Out(rows, c, dtype=torch.float64)
+        g, ga = RowOut(rows, c, dtype=torch.float64), RowOut(rows, c, dtype=torch.float64)
         _lib.check(_lib.load().hf_bn_adjoint_pre(g.ptr, ga.ptr, p(a), s1, rows * c, p(b), s2 or 1, rows * c, p(m_),
                                                  p(w_), p(rstd), rows, c, _lib.HF_F64, st()), "hf_bn_adjoint_pre")
         return g, ga
@@ -518,7 +454,7 @@ def test_chan_affine_train_against_float64(i, case):
     lib = _lib.load()
 
     def launch():
-        out = Out(k.rows, k.c, k.ld)
+        out = RowOut(k.rows, k.c, k.ld)
         a, x, mean, rstd, w, px, p1 = k.dev
         _lib.check(lib.hf_chan_affine_train(out.ptr, p(a), p(x), p(mean), p(rstd), p(w), p(px), p(p1), k.nparts, p(k.vq),
                                             p(k.vr), float(k.rows), p(k.add), p(k.dmask), k.rows, k.c, 1, k.ld,
@@ -541,7 +477,7 @@ def test_chan_affine_train_pair_against_float64(ia, ib):
     def launch():
         arr, outs = (_lib.AffineTrainProblem * 2)(), []
         for q, k in zip(arr, ks):
-            out = Out(k.rows, k.c, k.ld)
+            out = RowOut(k.rows, k.c, k.ld)
             outs.append(out)
             q.out = out.buf.data_ptr()
             for name, t in zip(("a", "x", "mean", "rstd", "w", "part_x", "part_1"), k.dev):
@@ -581,7 +517,7 @@ def test_train_hessian_kernels_against_float64(shape, parts, sp):
     vecs = [dv(t) for t in (gg1, gb1, pr.gam, pr.dgam, pr.rstd)]
 
     def launch_c():
-        coef, corr = Out(6, c), Out(1, c)
+        coef, corr = RowOut(6, c), RowOut(1, c)
         _lib.check(lib.hf_bn_train_hessian_coeffs(coef.ptr, corr.ptr, p(dev[0]), p(dev[1]), p(dev[2]), nparts, p(dev[3]),
                                                   p(dev[4]), nparts_t, *(p(t) for t in vecs), float(rows), c,
                                                   _lib.HF_F32, st()), "hf_bn_train_hessian_coeffs")
@@ -596,7 +532,7 @@ def test_train_hessian_kernels_against_float64(shape, parts, sp):
     kcoef = coef.val.contiguous()
 
     def launch_a():
-        out = Out(rows, c)
+        out = RowOut(rows, c)
         _lib.check(lib.hf_bn_train_hessian_apply(out.ptr, p(ops[0]), p(ops[1]), p(ops[2]), p(ops[3]), sp, rows * c,
                                                  p(ops[4]), p(ops[5]), p(ops[6]), p(kcoef), rows, c, _lib.HF_F32,
                                                  st()), "hf_bn_train_hessian_apply")
@@ -635,7 +571,7 @@ def test_maxpool_forward_equals_aten_reference(i, geom):
     orow = n * oh * ow
 
     def launch():
-        out, out2 = (Out(orow, c) if mode != 2 else None), (Out(orow, c, 2 * c) if mode != 1 else None)
+        out, out2 = (RowOut(orow, c) if mode != 2 else None), (RowOut(orow, c, 2 * c) if mode != 1 else None)
         idx = torch.full((orow * c + GUARD,), -7, dtype=torch.int32, device=DEV)
         _lib.check(lib.hf_maxpool_forward_nhwc(optr(out), optr(out2), 2 * c if out2 is not None else 0, p(idx), p(xd), n,
                                                h, w, oh, ow, c, kh, kw, sh, sw, ph, pw, _lib.HF_F32, st()),
@@ -656,13 +592,13 @@ def test_maxpool_forward_equals_aten_reference(i, geom):
     # the three kernels agree on the index convention
     gen = L.gen_of("pool-t", *geom)
     t = L.randn(gen, n, h, w, c)
-    tout, td = Out(orow, c, 2 * c), dv(t)
+    tout, td = RowOut(orow, c, 2 * c), dv(t)
     _lib.check(lib.hf_maxpool_tangent_nhwc(tout.ptr, p(td), p(idx), n, h, w, oh, ow, c, 2 * c, _lib.HF_F32, st()),
                "hf_maxpool_tangent_nhwc")
     want_t = t.permute(0, 3, 1, 2).flatten(2).gather(2, widx.flatten(2)).view(n, c, oh, ow).permute(0, 2, 3, 1)
     assert torch.equal(tout.val.cpu(), want_t.reshape(orow, c)) and tout.untouched()
     ga, gb_ = L.randn(gen, 2, orow, c), L.randn(gen, 1, orow, c)
-    g, gad, gbd = Out(n * h * w, c), dv(ga), dv(gb_)
+    g, gad, gbd = RowOut(n * h * w, c), dv(ga), dv(gb_)
     _lib.check(lib.hf_maxpool_adjoint_nhwc(g.ptr, p(gad), 2, orow * c, p(gbd), 1, 0, p(idx), n, h, w, oh, ow, c,
                                            kh, kw, sh, sw, ph, pw, _lib.HF_F32, st()), "hf_maxpool_adjoint_nhwc")
     gy = (ga.double().sum(0) + gb_[0].double()).view(n, oh, ow, c).permute(0, 3, 1, 2)
@@ -686,7 +622,7 @@ def test_pool_ce_head_against_float64(n, hw, k, with_jv):
     lib = _lib.load()
 
     def launch():
-        g, jv = Out(n * hw, k), (Out(n, k) if with_jv else None)
+        g, jv = RowOut(n * hw, k), (RowOut(n, k) if with_jv else None)
         _lib.check(lib.hf_pool_ce_head(g.ptr, optr(jv), p(td), p(pd), 1.0 / n, n, hw, k, _lib.HF_F32, st()),
                    "hf_pool_ce_head")
         return g, jv
@@ -720,7 +656,7 @@ def test_softmax_ce_hvp_against_float64(dtype, rows, cols):
     pd, vd = dv(pm), dv(v)
 
     def launch():
-        out = Out(rows, cols, dtype=dtype)
+        out = RowOut(rows, cols, dtype=dtype)
         _lib.check(_lib.load().hf_softmax_ce_hvp(out.ptr, p(pd), p(vd), 1.0 / rows, rows, cols, _lib.dtype_code(dtype),
                                                  st()), "hf_softmax_ce_hvp")
         return (out,)
@@ -734,8 +670,6 @@ def test_softmax_ce_hvp_against_float64(dtype, rows, cols):
 # merged convolution launches
 # ---------------------------------------------------------------------------------------------------------------
 def _conv_geoms():
-    from test_conv_gpu import GEOMS
-
     out = []
     for g in GEOMS:
         n, h, w, c, k, r, s, stride, padding = g

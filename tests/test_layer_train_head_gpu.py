@@ -1,6 +1,6 @@
 """GPU: the train-mode BatchNorm forward kernels (``hf_bn_stats_rows``, ``hf_bn_forward_train``) and the linear
 classifier head (``hf_linear_ce_head``) through the C ABI against the references of ``layer_refs`` -- the sibling of
-``test_layer_kernels_gpu.py`` (same helpers, same house style: CPU-seeded inputs, bounds ``R * u * M`` derived from the
+``test_layer_kernels_gpu.py`` (same house style: CPU-seeded inputs, bounds ``R * u * M`` derived from the
 kernel's order, NaN-filled destinations, guard words, two launches bitwise equal).  ``test_layer_refs_cpu.py`` shows on
 the same inputs that an fp32 evaluation sits inside every bound used here and that the named wrong variants do not."""
 
@@ -9,15 +9,14 @@ import pytest
 import torch
 from tol import within
 
+from guarded import DEV, ERR_ARG, NAN, RowOut, _ids, dv, optr, p, st, twice, wide
 import layer_refs as L
 from layer_refs import U64
 from pytorchhessianfree_amd import _lib
 from pytorchhessianfree_amd.engine.tangent import head_fused_shape_ok
-from test_layer_kernels_gpu import DEV, NAN, Out, dv, optr, p, st, twice, wide
 
 pytestmark = pytest.mark.gpu
-ERR_ARG, ERR_ALIGN = _lib.HF_ERR_ARG, -2  # hf_status of include/hf_pcg.h
-_ids = lambda v: str(v).replace(" ", "")  # noqa: E731
+ERR_ALIGN = -2  # hf_status of include/hf_pcg.h
 f32 = np.float32
 
 
@@ -26,8 +25,8 @@ def _bits(t):
 
 
 def _filled(values, rows, c, ld=0):
-    """an ``Out`` that already holds ``values`` (an in-place operand: the guard words behind it still apply)"""
-    out = Out(rows, c, ld)
+    """a ``RowOut`` that already holds ``values`` (an in-place operand: the guard words behind it still apply)"""
+    out = RowOut(rows, c, ld)
     out.val.copy_(values.view(rows, c))
     return out
 
@@ -45,7 +44,7 @@ def _slab_buffer(a, gap, tail):
 
 
 def _stats_launch(lib, a_dev, stride, splits, rows, c, rb, want_a_out):
-    part, a_out = Out(rb * 2, c, dtype=torch.float64), (Out(rows, c) if want_a_out else None)
+    part, a_out = RowOut(rb * 2, c, dtype=torch.float64), (RowOut(rows, c) if want_a_out else None)
     _lib.check(lib.hf_bn_stats_rows(optr(a_out), p(a_dev), splits, stride, part.ptr, rows, c, rb, _lib.HF_F32, st()),
                "hf_bn_stats_rows")
     return part, a_out
@@ -93,9 +92,9 @@ def _fwd_problem(rows, c, nparts, i, part=None):
 
 def _fwd_launch(lib, k):
     f, rows, c, d = k.f, k.rows, k.c, k.dev
-    y = Out(rows, c) if f.out != "y2" else None
-    y2 = Out(rows, c, 2 * c) if f.out != "y" else None
-    mean, rstd = Out(1, c), Out(1, c)
+    y = RowOut(rows, c) if f.out != "y2" else None
+    y2 = RowOut(rows, c, 2 * c) if f.out != "y" else None
+    mean, rstd = RowOut(1, c), RowOut(1, c)
     rm, rv = _filled(dv(k.o.rm), 1, c), _filled(dv(k.o.rv), 1, c)
     give = f.stat != "null"
     _lib.check(lib.hf_bn_forward_train(optr(y), optr(y2), 2 * c if y2 is not None else 0, p(d.s), p(d.part), k.nparts,
@@ -178,7 +177,7 @@ def test_linear_ce_head_against_float64(rows, features, classes, bias):
     d = [dv(t) for t in (o.t_feat, o.feat, o.w, o.v_w, o.v_b, o.p)]
 
     def launch():
-        gf, gw, gb = Out(rows, features), Out(groups * classes, features), Out(groups, classes)
+        gf, gw, gb = RowOut(rows, features), RowOut(groups * classes, features), RowOut(groups, classes)
         _lib.check(lib.hf_linear_ce_head(gf.ptr, gw.ptr, gb.ptr if bias else None, *(p(t) for t in d), o.scale, rows,
                                          features, classes, _lib.HF_F32, st()), "hf_linear_ce_head")
         return gf, gw, gb

@@ -12,58 +12,22 @@ import zlib
 
 import numpy as np
 import pytest
-import torch
 
 import pack_refs as pr
+from guarded import ERR_ARG, GUARD, NAN, P, Payload, dev, st
 from pytorchhessianfree_amd import _lib
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-GUARD = 64
-NAN = pr.NAN
-P = _lib.c_void_p
-ERR_ARG = _lib.HF_ERR_ARG
 _CODE = {np.float32: _lib.HF_F32, np.float64: _lib.HF_F64}
 _DT_IDS = [np.dtype(d).name for d in pr.DTYPES]
-
-
-def _dev(a):
-    t = torch.from_numpy(a).to(DEV)
-    assert t.numel() == 0 or t.data_ptr() % 16 == 0
-    return t
 
 
 def _seed(*key):
     return zlib.crc32(repr(key).encode()) & 0x7fffffff
 
 
-def _st():
-    return _lib.current_stream_ptr(torch.device(DEV))
-
-
 def _i64(vals):
     return (_lib.c_int64 * len(vals))(*vals)
-
-
-class Guarded:
-    """``payload`` on the device between GUARD NaN sentinels on each side (the payload itself stays 16-byte aligned)."""
-
-    def __init__(self, payload):
-        guard = np.full(GUARD, NAN, payload.dtype)
-        self.before = np.concatenate([guard, payload, guard])
-        self.buf = _dev(self.before)
-        self.t = self.buf[GUARD:GUARD + payload.size]
-
-    def after(self):
-        return self.buf.cpu().numpy()
-
-    def expect(self, payload):
-        e = self.before.copy()
-        e[GUARD:e.size - GUARD] = payload
-        return e
-
-    def untouched(self):
-        return pr.same(self.after(), self.before)
 
 
 def _diff(got, want):
@@ -84,7 +48,7 @@ def _check_pack(case, dtype, mode):
     size = np.dtype(dtype).itemsize
     tensors, perms, splits, live = [], {}, {}, {}
     for i, (buf, s) in enumerate(zip(bufs, case.srcs)):
-        t = _dev(buf)[s.src_off:s.src_off + s.numel]
+        t = dev(buf)[s.src_off:s.src_off + s.numel]
         assert s.numel == 0 or t.data_ptr() % 16 == s.src_off * size % 16
         tensors.append(t)
         if s.perm:
@@ -98,7 +62,7 @@ def _check_pack(case, dtype, mode):
     for scale in pr.SCALES:
         # mode 0 overwrites every entry (NaN shows one that it left), mode 1 adds to random values
         before = rng.standard_normal(n).astype(dtype) if mode == 1 else np.full(n, NAN, dtype)
-        dst = Guarded(before)
+        dst = Payload(before)
         _lib.pack_ex(dst.t, tensors, perms, splits, scale=scale, live=live, mode=mode)
         want = pr.pack_ref(before, sources, scale, mode)
         assert not np.isnan(want).any()
@@ -138,7 +102,7 @@ def _unpack(v, slots, halves, dtype):
     guarded, views, tables = [], [], []
     for s, h in zip(slots, halves):
         O, I, H, W = s.shape
-        g = Guarded(np.full(O * I * H * W * (1 if h == 2 else 2), NAN, dtype))
+        g = Payload(np.full(O * I * H * W * (1 if h == 2 else 2), NAN, dtype))
         if h == 2:
             view = g.t.view(I, H, W, O)
         elif s.nhwc:
@@ -155,12 +119,12 @@ def _unpack(v, slots, halves, dtype):
     n = len(slots)
     dsts = (P * n)(*[tab[0][0] for tab in tables])
     cols = [_i64([tab[c][0] for tab in tables]) for c in range(1, 7)]
-    _lib.check(_lib.load().hf_unpack_weights(P(v.data_ptr()), dsts, *cols, n, _CODE[dtype], _st()), "hf_unpack_weights")
+    _lib.check(_lib.load().hf_unpack_weights(P(v.data_ptr()), dsts, *cols, n, _CODE[dtype], st()), "hf_unpack_weights")
     return guarded, views
 
 
 def _check_unpack(v_host, slots, halves, dtype):
-    v = _dev(v_host)
+    v = dev(v_host)
     guarded, views = _unpack(v, slots, halves, dtype)
     for s, h, g, view, want in zip(slots, halves, guarded, views, pr.unpack_ref(v_host, slots, halves)):
         got = view.cpu().numpy()
@@ -202,7 +166,7 @@ def test_unpack_of_halves_0_1_and_2_in_one_launch(dtype):
 def _live_copy(full, comp, scatter, segs, dtype, n_segments=None):
     cols = [_i64([s[c] for s in segs]) for c in range(4)]
     return _lib.load().hf_live_copy(P(full.data_ptr()), P(comp.data_ptr()), scatter, *cols,
-                                    len(segs) if n_segments is None else n_segments, _CODE[dtype], _st())
+                                    len(segs) if n_segments is None else n_segments, _CODE[dtype], st())
 
 
 @pytest.mark.parametrize("dtype", pr.DTYPES, ids=_DT_IDS)
@@ -214,12 +178,12 @@ def test_live_copy_gathers_and_scatters_exactly_the_live_entries(name, dtype):
     segs, n = pr.LIVE_LAYOUTS[name]
     full_host = np.random.RandomState(_seed(name)).standard_normal(n).astype(dtype)
     idx = pr.live_index(segs)
-    full, comp = Guarded(full_host), Guarded(np.full(idx.size, NAN, dtype))
+    full, comp = Payload(full_host), Payload(np.full(idx.size, NAN, dtype))
     assert _live_copy(full.t, comp.t, 0, segs, dtype) == 0
     got, want = comp.after(), comp.expect(pr.live_copy_ref(full_host, segs))
     assert pr.same(got, want), _diff(got, want)
-    assert full.untouched()
-    target = Guarded(np.full(n, NAN, dtype))
+    assert full.pristine()
+    target = Payload(np.full(n, NAN, dtype))
     assert _live_copy(target.t, comp.t, 1, segs, dtype) == 0
     restored = np.full(n, NAN, dtype)
     restored[idx] = full_host[idx]
@@ -245,18 +209,18 @@ _PACK_REFUSED = {
 def _pack_call(dst, src, a):
     srcs = (P * 1)(None if a["null_src"] else src.data_ptr())
     return _lib.load().hf_pack_ex(P(dst.data_ptr()), srcs, _i64([a["numel"]]), _i64([a["I"], a["HW"]]),
-                                  _i64([a["count"], a["stride"]]), _i64([0]), 1, 0.5, a["mode"], a["dtype"], _st())
+                                  _i64([a["count"], a["stride"]]), _i64([0]), 1, 0.5, a["mode"], a["dtype"], st())
 
 
 @pytest.mark.parametrize("fault", list(_PACK_REFUSED))
 def test_pack_ex_refuses(fault):
-    src = _dev(np.ones(2 * 72, np.float32))
-    ok = Guarded(np.full(72, NAN, np.float32))
+    src = dev(np.ones(2 * 72, np.float32))
+    ok = Payload(np.full(72, NAN, np.float32))
     assert _pack_call(ok.t, src, _PACK_OK) == 0  # (the call every row differs from in one argument)
     assert pr.same(ok.after(), ok.expect(np.full(72, 0.5, np.float32)))
-    dst = Guarded(np.full(72, NAN, np.float32))
+    dst = Payload(np.full(72, NAN, np.float32))
     assert _pack_call(dst.t, src, {**_PACK_OK, **_PACK_REFUSED[fault]}) == ERR_ARG
-    assert dst.untouched()
+    assert dst.pristine()
 
 
 _UNPACK_OK = dict(null_dst=False, off=4, numel=72, slab=18, inner=0, half=1)
@@ -273,21 +237,21 @@ _UNPACK_REFUSED = {
 def _unpack_call(v, dst, a):
     dsts = (P * 1)(None if a["null_dst"] else dst.data_ptr())
     return _lib.load().hf_unpack_weights(P(v.data_ptr()), dsts, _i64([a["off"]]), _i64([a["numel"]]), _i64([a["slab"]]),
-                                         _i64([a["inner"]]), _i64([0]), _i64([a["half"]]), 1, _lib.HF_F32, _st())
+                                         _i64([a["inner"]]), _i64([0]), _i64([a["half"]]), 1, _lib.HF_F32, st())
 
 
 @pytest.mark.parametrize("fault", list(_UNPACK_REFUSED))
 def test_unpack_weights_refuses(fault):
     v_host = np.arange(80, dtype=np.float32)
-    v = _dev(v_host)
-    ok = Guarded(np.full(144, NAN, np.float32))
+    v = dev(v_host)
+    ok = Payload(np.full(144, NAN, np.float32))
     assert _unpack_call(v, ok.t, _UNPACK_OK) == 0
     want = np.full((4, 2, 18), NAN, np.float32)
     want[:, 1] = v_host[4:76].reshape(4, 18)
     assert pr.same(ok.after(), ok.expect(want.reshape(-1)))
-    dst = Guarded(np.full(144, NAN, np.float32))
+    dst = Payload(np.full(144, NAN, np.float32))
     assert _unpack_call(v, dst.t, {**_UNPACK_OK, **_UNPACK_REFUSED[fault]}) == ERR_ARG
-    assert dst.untouched()
+    assert dst.pristine()
 
 
 _DENSE25 = [(4 * k, 4, 0, 0) for k in range(25)]
@@ -305,11 +269,11 @@ _LIVE_REFUSED = {  # segments, n_segments
 @pytest.mark.parametrize("fault", list(_LIVE_REFUSED))
 def test_live_copy_refuses(fault, scatter):
     full_host = np.arange(100, dtype=np.float32)
-    ok_full, ok_comp = Guarded(full_host), Guarded(np.full(100, NAN, np.float32))
+    ok_full, ok_comp = Payload(full_host), Payload(np.full(100, NAN, np.float32))
     assert _live_copy(ok_full.t, ok_comp.t, 0, [(0, 36, 9, pr.CENTRE)], np.float32) == 0
     assert _live_copy(ok_full.t, ok_comp.t, 0, _DENSE25[:24], np.float32) == 0  # (24 segments are the limit)
     assert pr.same(ok_comp.after()[GUARD:GUARD + 96], full_host[:96])
-    full, comp = Guarded(full_host), Guarded(np.full(100, NAN, np.float32))
+    full, comp = Payload(full_host), Payload(np.full(100, NAN, np.float32))
     segs, n_segments = _LIVE_REFUSED[fault]
     assert _live_copy(full.t, comp.t, scatter, segs, np.float32, n_segments) == ERR_ARG
-    assert full.untouched() and comp.untouched()
+    assert full.pristine() and comp.pristine()

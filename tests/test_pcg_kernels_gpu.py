@@ -19,51 +19,15 @@ import torch
 
 import pcg_refs as pr
 import tol
+from guarded import DEV, GUARD, P, Payload, dev, p as _ptr, st as _st  # (p, st: names of locals here)
 from pytorchhessianfree_amd import _lib
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-GUARD = 64
-P = _lib.c_void_p
 _CODE = {np.float32: _lib.HF_F32, np.float64: _lib.HF_F64}
 ERR_ARG, ERR_ALIGN, ERR_STATE = -1, -2, -3
 # hf_precond_build: worst distance seen on the MI355X from (diag + lambda)^(-a) evaluated in float64 and rounded to T was
 # 1 ulp (fp32) / 1 ulp (fp64); asserted at 3x that (profiles/r15_pcg_tolerance_sites.jsonl)
 POW_ULPS = {np.float32: 3.0, np.float64: 3.0}
-
-
-def _st():
-    return _lib.current_stream_ptr(torch.device(DEV))
-
-
-def _dev(a):
-    t = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-    assert t.numel() == 0 or t.data_ptr() % 16 == 0
-    return t
-
-
-def _ptr(t):
-    return None if t is None else P(t.data_ptr())
-
-
-class Guarded:
-    """``payload`` on the device between GUARD NaN sentinels on each side; the payload starts 16-byte aligned."""
-
-    def __init__(self, payload):
-        guard = np.full(GUARD, pr.NAN, payload.dtype)
-        self.size = payload.size
-        self.before = np.concatenate([guard, payload, guard])
-        self.buf = _dev(self.before)
-        self.t = self.buf[GUARD:GUARD + payload.size]
-        assert self.t.data_ptr() % 16 == 0
-
-    def after(self):
-        return self.buf.cpu().numpy()
-
-    def expect(self, payload):
-        e = self.before.copy()
-        e[GUARD:GUARD + self.size] = np.asarray(payload).ravel()
-        return e
 
 
 def _bits(a):
@@ -105,18 +69,18 @@ class Solve:
         self.hd, self.lib, self.h, self.mode = handle, handle.lib, handle.h, mode
         T = self.T = np.dtype(handle.dtype).type
         n = self.n = handle.n
-        self.x = Guarded(x0.astype(T))
-        self.r, self.p = Guarded(np.full(n, pr.NAN, T)), Guarded(np.full(n, pr.NAN, T))
+        self.x = Payload(x0.astype(T))
+        self.r, self.p = Payload(np.full(n, pr.NAN, T)), Payload(np.full(n, pr.NAN, T))
         self.n_store = len(store_iters)
-        self.slab = Guarded(np.full(self.n_store * slab_stride, pr.NAN, T)) if self.n_store else None
-        self.m_hist = Guarded(np.full(max_iter + 1, pr.NAN, T)) if martens else None
+        self.slab = Payload(np.full(self.n_store * slab_stride, pr.NAN, T)) if self.n_store else None
+        self.m_hist = Payload(np.full(max_iter + 1, pr.NAN, T)) if martens else None
         self.inputs = {"b": [b.astype(T), None]}
         if mode == pr.M_DIAG:
             self.inputs["minv"] = [minv.astype(T), None]
         if self.n_store:
             self.inputs["store_iters"] = [np.asarray(store_iters, np.int64), None]
         for rec in self.inputs.values():
-            rec[1] = _dev(rec[0])
+            rec[1] = dev(rec[0])
         for name in ("Ax0", "Bp", "y"):
             self.inputs[name] = [np.zeros(n, T), torch.zeros(n, dtype=torch.from_numpy(np.zeros(1, T)).dtype, device=DEV)]
         dv = lambda name: _ptr(self.inputs[name][1]) if name in self.inputs else None  # noqa: E731
@@ -493,8 +457,8 @@ def test_axpy_out_bitwise_aligned_offset_and_in_place(dtype):
         a, s = g.standard_normal(n + 1).astype(T), g.standard_normal(n + 1).astype(T)
         for off, in_place in ((0, False), (1, False), (0, True), (1, True)):
             want = a[off:off + n] + (T(alpha) * s[off:off + n])
-            da, ds = Guarded(a), _dev(s)
-            out = da if in_place else Guarded(np.full(n + 1, pr.NAN, T))
+            da, ds = Payload(a), dev(s)
+            out = da if in_place else Payload(np.full(n + 1, pr.NAN, T))
             rc = lib.hf_axpy_out(_ptr(out.t[off:off + n]), _ptr(da.t[off:off + n]), _ptr(ds[off:off + n]), alpha, n,
                                  _CODE[dtype], _st())
             assert rc == 0
@@ -513,7 +477,7 @@ def test_precond_build_against_float64_power_in_ulps(dtype):
     diag = (g.random(n) * 3).astype(T)
     diag[:4] = T(0), T(1) - T(lam), T(1e-6), T(1e4)
     for exponent in (0.75, 1.0, 0.5):
-        out, dd = Guarded(np.full(n, pr.NAN, T)), _dev(diag)
+        out, dd = Payload(np.full(n, pr.NAN, T)), dev(diag)
         assert lib.hf_precond_build(_ptr(out.t), _ptr(dd), lam, exponent, n, _CODE[dtype], _st()) == 0
         base = (diag + T(lam)).astype(np.float64)                    # the kernel's own base, exact in float64
         want = np.array([math.pow(v, float(T(-exponent))) for v in base.tolist()]).astype(T)

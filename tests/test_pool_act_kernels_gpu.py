@@ -13,56 +13,11 @@ import pytest
 import torch
 from tol import within
 
+from guarded import DEV, ERR_ARG, U32, RowOut, p, slabs_dev, st, twice
 import pool_act_refs as R
 from pytorchhessianfree_amd import _lib
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-GUARD = 64
-NAN = float("nan")
-P = _lib.c_void_p
-ERR_ARG = _lib.HF_ERR_ARG
-U32 = 2.0 ** -24
-
-
-def p(t):
-    return P(t.data_ptr()) if t is not None else None
-
-
-def st():
-    return _lib.current_stream_ptr(torch.device(DEV))
-
-
-class Out:
-    """``rows`` x ``c`` floats inside a NaN-filled buffer: pixel stride ``ld`` (0 = dense) and GUARD words behind it."""
-
-    def __init__(self, rows, c, ld=0):
-        self.rows, self.c, self.w = rows, c, (ld or c)
-        self.buf = torch.full((rows * self.w + GUARD,), NAN, device=DEV)
-
-    @property
-    def ptr(self):
-        return P(self.buf.data_ptr())
-
-    @property
-    def val(self):
-        return self.buf[:self.rows * self.w].view(self.rows, self.w)[:, :self.c]
-
-    def untouched(self):
-        body = self.buf[:self.rows * self.w].view(self.rows, self.w)[:, self.c:]
-        return bool(torch.isnan(body).all()) and bool(torch.isnan(self.buf[self.rows * self.w:]).all())
-
-    def same(self, other):
-        return torch.equal(self.buf.view(torch.int32), other.buf.view(torch.int32))
-
-
-def slabs_dev(t, stride):
-    """[S, ...] -> S slabs ``stride`` elements apart on the device, NaN in between and behind."""
-    S, numel = t.shape[0], t[0].numel()
-    buf = torch.full((S, stride), NAN)
-    buf[:, :numel] = t.reshape(S, numel)
-    return buf.to(DEV)
-
 
 # every geometry x map x channel count; the other options cycle so that each value meets each geometry class
 SHAPES = [(g, m, c) for g in R.GEOMS for m in R.MAPS for c in (4, 12)] + [((3, 2, 1), (5, 7), 3), ((2, 2, 0), (4, 4), 6)]
@@ -146,16 +101,12 @@ def _tangent(shape, opts):
     lib, ld, orow = _lib.load(), (2 * c if wide else 0), n * oh * ow
 
     def launch():
-        out = Out(orow, c, ld)
+        out = RowOut(orow, c, ld)
         _lib.check(lib.hf_pool_act_tangent_nhwc(out.ptr, ld, p(sd), splits, stride, p(vd), p(idxd), p(yd), relu, n, h, w,
                                                 oh, ow, c, _lib.HF_F32, st()), "hf_pool_act_tangent_nhwc")
         return out
 
-    a, b = launch(), launch()
-    torch.cuda.synchronize()
-    assert a.same(b), "two launches on the same operands differ"
-    assert a.untouched(), "the other half of the wider buffer or a guard word was written"
-    assert torch.equal(a.val.cpu().double(), want.reshape(orow, c))
+    assert torch.equal(twice(launch).val.cpu().double(), want.reshape(orow, c))
 
 
 @pytest.mark.parametrize("i", **_ids(SHAPES))
@@ -194,18 +145,13 @@ def _adjoint(shape, n, gy_splits, with_gb, relu, row_blocks, pad):
     lib, rows = _lib.load(), n * h * w
 
     def launch():
-        ga, gb = Out(rows, c), (Out(row_blocks, c) if with_gb else None)
+        ga, gb = RowOut(rows, c), (RowOut(row_blocks, c) if with_gb else None)
         _lib.check(lib.hf_pool_act_adjoint_nhwc(ga.ptr, gb.ptr if gb else None, row_blocks, p(gd), gy_splits, slab,
                                                 p(idxd), p(yd), relu, n, h, w, oh, ow, c, kh, kw, sh, sw, ph, pw,
                                                 _lib.HF_F32, st()), "hf_pool_act_adjoint_nhwc")
         return ga, gb
 
-    a, b = launch(), launch()
-    torch.cuda.synchronize()
-    for x, y in zip(a, b):
-        if x is not None:
-            assert x.same(y), "two launches on the same operands differ"
-            assert x.untouched()
+    a = twice(launch)
     assert torch.equal(a[0].val.cpu().double(), want.reshape(rows, c))
     if with_gb:
         assert torch.equal(a[1].val.cpu().double(), want_gb)
@@ -223,7 +169,7 @@ def test_random_operands_within_the_derived_bound():
     idxd, yd = idx.to(torch.int32).to(DEV), y_pool.to(DEV)
     want, M = R.tangent(o["slabs"], o["v_b"], idx, y_pool, 1)
     stride = n * h * w * c + 4
-    out, sd, vd = Out(n * oh * ow, c), slabs_dev(o["slabs"], stride), o["v_b"].to(DEV)
+    out, sd, vd = RowOut(n * oh * ow, c), slabs_dev(o["slabs"], stride), o["v_b"].to(DEV)
     _lib.check(lib.hf_pool_act_tangent_nhwc(out.ptr, 0, p(sd), splits, stride, p(vd), p(idxd), p(yd), 1, n, h, w, oh, ow,
                                             c, _lib.HF_F32, st()), "hf_pool_act_tangent_nhwc")
     err = (out.val.cpu().double() - want.reshape(-1, c)).abs()
@@ -233,7 +179,7 @@ def test_random_operands_within_the_derived_bound():
     want_ga, Mg, want_gb, windows = R.adjoint(o["gy"], idx, y_pool, 1, h, w, k, s, pd, rb)
     assert windows >= 2
     slab = n * oh * ow * c + 4
-    ga, gb, gd = Out(n * h * w, c), Out(rb, c), slabs_dev(o["gy"], slab)
+    ga, gb, gd = RowOut(n * h * w, c), RowOut(rb, c), slabs_dev(o["gy"], slab)
     _lib.check(lib.hf_pool_act_adjoint_nhwc(ga.ptr, gb.ptr, rb, p(gd), gy_splits, slab, p(idxd), p(yd), 1, n, h, w, oh,
                                             ow, c, k, k, s, s, pd, pd, _lib.HF_F32, st()), "hf_pool_act_adjoint_nhwc")
     R_ = gy_splits * windows + 2
@@ -258,7 +204,7 @@ def test_refusals_return_err_arg_and_leave_the_outputs_alone():
     lib, F32, big = _lib.load(), _lib.HF_F32, 1 << 20
     MAXS = 1024  # HF_POOL_ACT_MAX_SPLITS of include/hf_pcg.h
 
-    out = Out(n * oh * ow, c, 2 * c)
+    out = RowOut(n * oh * ow, c, 2 * c)
     good_t = dict(out=out.ptr, out_ld=2 * c, slabs=p(sd), splits=2, stride=full + 4, v_b=p(vd), idx=p(idxd), y=p(yd),
                   relu=1, n=n, h=h, w=w, oh=oh, ow=ow, c=c, dtype=F32)
 
@@ -276,7 +222,7 @@ def test_refusals_return_err_arg_and_leave_the_outputs_alone():
     assert bool(torch.isnan(out.buf).all())
     assert tangent() == 0 and tangent(y=None, relu=0) == 0 and tangent(v_b=None) == 0  # (the complete call is taken)
 
-    ga, gb = Out(n * h * w, c), Out(3, c)
+    ga, gb = RowOut(n * h * w, c), RowOut(3, c)
     good_a = dict(ga=ga.ptr, gb=gb.ptr, rb=3, gy=p(gd), splits=2, slab=pooled + 4, idx=p(idxd), y=p(yd), relu=1, n=n, h=h,
                   w=w, oh=oh, ow=ow, c=c, k=k, s=s, pd=pd, dtype=F32)
 

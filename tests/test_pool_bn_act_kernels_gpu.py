@@ -15,12 +15,11 @@ import pytest
 import torch
 from tol import within
 
+from guarded import DEV, ERR_ARG, NAN, U32, RowOut, p, slabs_dev, st, twice
 import pool_bn_act_refs as B
 from pytorchhessianfree_amd import _lib
-from test_pool_act_kernels_gpu import ERR_ARG, NAN, U32, Out, p, slabs_dev, st
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 
 # every geometry x map x channel count (16 bytes per thread), and two element-wise channel counts
 SHAPES = [(g, m, c) for g in B.GEOMS for m in B.MAPS for c in (4, 12)] + [((3, 2, 1), (5, 7), 3), ((2, 2, 0), (4, 4), 6)]
@@ -129,17 +128,13 @@ def _tangent(shape, opts):
     lib, ld, orow = _lib.load(), (2 * c if wide else 0), n * oh * ow
 
     def launch():
-        out = Out(orow, c, ld)
+        out = RowOut(orow, c, ld)
         _lib.check(lib.hf_pool_bn_act_tangent_nhwc(out.ptr, ld, p(sd), splits, stride, p(ad), p(md), p(rd), p(wd), p(vwd),
                                                    p(vbd), p(idxd), p(yd), relu, n, h, w, oh, ow, c, _lib.HF_F32, st()),
                    "hf_pool_bn_act_tangent_nhwc")
         return out
 
-    a, b = launch(), launch()
-    torch.cuda.synchronize()
-    assert a.same(b), "two launches on the same operands differ"
-    assert a.untouched(), "the other half of the wider buffer or a guard word was written"
-    assert torch.equal(a.val.cpu().double(), want.reshape(orow, c))
+    assert torch.equal(twice(launch).val.cpu().double(), want.reshape(orow, c))
 
 
 @pytest.mark.parametrize("i", **_ids(SHAPES))
@@ -178,8 +173,8 @@ def _adjoint(shape, n, gy_splits, relu, with_g, sums, rb, pad):
     lib, rows = _lib.load(), n * h * w
 
     def launch():
-        outs = dict(ga=Out(rows, c), g=Out(rows, c) if with_g else None, gw=Out(row_blocks, c) if "w" in sums else None,
-                    gb=Out(row_blocks, c) if "b" in sums else None)
+        outs = dict(ga=RowOut(rows, c), g=RowOut(rows, c) if with_g else None, gw=RowOut(row_blocks, c) if "w" in sums else None,
+                    gb=RowOut(row_blocks, c) if "b" in sums else None)
         ptr = {name: (t.ptr if t is not None else None) for name, t in outs.items()}
         _lib.check(lib.hf_pool_bn_act_adjoint_nhwc(ptr["ga"], ptr["g"], ptr["gw"], ptr["gb"], row_blocks, p(gd), gy_splits,
                                                    slab, p(ad), p(md), p(rd), p(wd), p(idxd), p(yd), relu, n, h, w, oh, ow,
@@ -212,7 +207,7 @@ def test_random_operands_within_the_derived_bounds_and_the_identities():
     ad, md, rd, wd, vwd, vbd = _dev(o, "a", "mean", "rstd", "w", "v_w", "v_b")
     want, M = B.tangent(o, o["v_w"], o["v_b"], idx, y_pool, 1)
     stride = n * h * w * c + 4
-    out, sd = Out(n * oh * ow, c), slabs_dev(o["slabs"], stride)
+    out, sd = RowOut(n * oh * ow, c), slabs_dev(o["slabs"], stride)
     _lib.check(lib.hf_pool_bn_act_tangent_nhwc(out.ptr, 0, p(sd), splits, stride, p(ad), p(md), p(rd), p(wd), p(vwd),
                                                p(vbd), p(idxd), p(yd), 1, n, h, w, oh, ow, c, F32, st()), "tangent")
     err = (out.val.cpu().double() - want.reshape(-1, c)).abs()
@@ -230,7 +225,7 @@ def test_random_operands_within_the_derived_bounds_and_the_identities():
     r = B.adjoint(o, idx, y_pool, 1, h, w, k, s, pd, rb)
     assert r["windows"] >= 2
     slab, rows = n * oh * ow * c + 4, n * h * w
-    ga, g, gw, gb, gd = Out(rows, c), Out(rows, c), Out(rb, c), Out(rb, c), slabs_dev(o["gy"], slab)
+    ga, g, gw, gb, gd = RowOut(rows, c), RowOut(rows, c), RowOut(rb, c), RowOut(rb, c), slabs_dev(o["gy"], slab)
     _lib.check(lib.hf_pool_bn_act_adjoint_nhwc(ga.ptr, g.ptr, gw.ptr, gb.ptr, rb, p(gd), gy_splits, slab, p(ad), p(md), p(rd),
                                                p(wd), p(idxd), p(yd), 1, n, h, w, oh, ow, c, k, k, s, s, pd, pd, F32, st()),
                "adjoint")
@@ -241,16 +236,16 @@ def test_random_operands_within_the_derived_bounds_and_the_identities():
         err, bound = (got.val.cpu().double() - ref.reshape(-1, c)).abs(), bound.reshape(-1, c)
         assert bool((err[bound == 0] == 0).all()), name
         within(float((err / bound.clamp_min(1e-300)).max()), 1.0, strict=False, note=name)
-    ga0 = Out(rows, c)
+    ga0 = RowOut(rows, c)
     _lib.check(lib.hf_pool_act_adjoint_nhwc(ga0.ptr, None, 0, p(gd), gy_splits, slab, p(idxd), p(yd), 1, n, h, w, oh, ow, c,
                                             k, k, s, s, pd, pd, F32, st()), "hf_pool_act_adjoint_nhwc")
     assert g.same(ga0), "g is not the bias form's ga"
-    scaled = Out(rows, c)
+    scaled = RowOut(rows, c)
     _lib.check(lib.hf_bn_adjoint_v4(None, scaled.ptr, g.ptr, 1, 0, None, 1, 0, None, p(wd), p(rd), rows, c, F32, st()),
                "hf_bn_adjoint_v4")
     assert ga.same(scaled), "ga is not hf_bn_adjoint_v4's scaling of g"
     # the one-pixel-per-thread form (no sums) writes the same g and ga
-    ga1, g1 = Out(rows, c), Out(rows, c)
+    ga1, g1 = RowOut(rows, c), RowOut(rows, c)
     _lib.check(lib.hf_pool_bn_act_adjoint_nhwc(ga1.ptr, g1.ptr, None, None, 0, p(gd), gy_splits, slab, p(ad), p(md), p(rd),
                                                p(wd), p(idxd), p(yd), 1, n, h, w, oh, ow, c, k, k, s, s, pd, pd, F32, st()),
                "adjoint, elementwise")
@@ -270,7 +265,7 @@ def test_refusals_return_err_arg_and_leave_the_outputs_alone():
     lib, F32, big = _lib.load(), _lib.HF_F32, 1 << 20
     MAXS = 1024  # HF_POOL_ACT_MAX_SPLITS of include/hf_pcg.h
 
-    out = Out(n * oh * ow, c, 2 * c)
+    out = RowOut(n * oh * ow, c, 2 * c)
     good_t = dict(out=out.ptr, out_ld=2 * c, slabs=p(sd), splits=2, stride=full + 4, a=p(ad), mean=p(md), rstd=p(rd),
                   w_=p(wd), v_w=p(vwd), v_b=p(vbd), idx=p(idxd), y=p(yd), relu=1, n=n, h=h, w=w, oh=oh, ow=ow, c=c, dtype=F32)
 
@@ -288,7 +283,7 @@ def test_refusals_return_err_arg_and_leave_the_outputs_alone():
     assert bool(torch.isnan(out.buf).all())
     assert tangent() == 0 and tangent(y=None, relu=0) == 0 and tangent(v_b=None) == 0 and tangent(v_w=None) == 0
 
-    outs = dict(ga=Out(n * h * w, c), g=Out(n * h * w, c), gw=Out(3, c), gb=Out(3, c))
+    outs = dict(ga=RowOut(n * h * w, c), g=RowOut(n * h * w, c), gw=RowOut(3, c), gb=RowOut(3, c))
     good_a = dict({name: t.ptr for name, t in outs.items()}, rb=3, gy=p(gd), splits=2, slab=pooled + 4, a=p(ad), mean=p(md),
                   rstd=p(rd), w_=p(wd), idx=p(idxd), y=p(yd), relu=1, n=n, h=h, w=w, oh=oh, ow=ow, c=c, k=k, s=s, pd=pd,
                   dtype=F32)

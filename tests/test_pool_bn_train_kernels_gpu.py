@@ -13,13 +13,12 @@ import pytest
 import torch
 from tol import within
 
+from guarded import DEV, ERR_ARG, NAN, P, U32, RowOut, p, slabs_dev, st, twice
 import layer_refs as L
 import pool_bn_train_refs as T
 from pytorchhessianfree_amd import _lib
-from test_pool_act_kernels_gpu import ERR_ARG, NAN, U32, Out, p, slabs_dev, st
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 B = T.B
 ERR_ALIGN = -2  # HF_ERR_ALIGN of include/hf_pcg.h
 N = 2
@@ -110,7 +109,7 @@ def _tangent(geom, case):
     lib, F32, ld, orow = _lib.load(), _lib.HF_F32, (0, 2 * c, 2 * c + 2)[ldk], N * oh * ow
 
     def launch():
-        out = Out(orow, c, ld)
+        out = RowOut(orow, c, ld)
         _lib.check(lib.hf_pool_bn_act_tangent_train_nhwc(
             out.ptr, ld, p(sd), splits, stride, p(ad), p(md), p(rd), p(wd), p(vwd), p(vbd), p(pxd), p(p1d), nparts,
             o["count"], p(idxd), p(yd), relu, N, h, w, oh, ow, c, F32, st()), "hf_pool_bn_act_tangent_train_nhwc")
@@ -165,18 +164,14 @@ def test_reduce_row_sums_beyond_256_channel_columns_equal_float64_bitwise(c, rb,
     lib = _lib.load()
 
     def launch():
-        both, gw, gb = Out(2 * rows, c), Out(rb, c), Out(rb, c)
-        g_ptr = _lib.c_void_p(both.buf.data_ptr() + 4 * rows * c)
+        both, gw, gb = RowOut(2 * rows, c), RowOut(rb, c), RowOut(rb, c)
+        g_ptr = P(both.buf.data_ptr() + 4 * rows * c)
         _lib.check(lib.hf_pool_bn_act_adjoint_reduce_nhwc(
             g_ptr, gw.ptr, gb.ptr, rb, p(gd), gy_splits, slab, p(ad), p(md), p(rd), p(wd), p(idxd), p(yd), relu, n, h, w, oh,
             ow, c, k, k, s, s, pd, pd, _lib.HF_F32, st()), "hf_pool_bn_act_adjoint_reduce_nhwc")
         return both, gw, gb
 
-    (both, gw, gb), second = launch(), launch()
-    torch.cuda.synchronize()
-    for x, y in zip((both, gw, gb), second):
-        assert x.same(y), "two launches on the same operands differ"
-        assert x.untouched()
+    both, gw, gb = twice(launch)
     assert bool(torch.isnan(both.val[:rows]).all()), "something was written where ga would be"
     assert torch.equal(both.val[rows:].cpu().double(), want["g"].reshape(rows, c)), "g"
     assert torch.equal(gw.val.cpu().double(), want["gw"]), "gw"
@@ -201,14 +196,14 @@ def _reduce(geom, case):
 
     def launch():
         # g sits where the fused entry point's argument order has it: behind a map-sized region where ga would be
-        both, gw, gb = Out(2 * rows, c), Out(rb, c), Out(rb, c)
-        g_ptr = _lib.c_void_p(both.buf.data_ptr() + 4 * rows * c)
+        both, gw, gb = RowOut(2 * rows, c), RowOut(rb, c), RowOut(rb, c)
+        g_ptr = P(both.buf.data_ptr() + 4 * rows * c)
         _lib.check(lib.hf_pool_bn_act_adjoint_reduce_nhwc(g_ptr, gw.ptr, gb.ptr, rb, *tail, st()),
                    "hf_pool_bn_act_adjoint_reduce_nhwc")
         return both, gw, gb
 
     (both, gw, gb), second = launch(), launch()
-    ga0, g0, gw0, gb0 = Out(rows, c), Out(rows, c), Out(rb, c), Out(rb, c)
+    ga0, g0, gw0, gb0 = RowOut(rows, c), RowOut(rows, c), RowOut(rb, c), RowOut(rb, c)
     _lib.check(lib.hf_pool_bn_act_adjoint_nhwc(ga0.ptr, g0.ptr, gw0.ptr, gb0.ptr, rb, *tail, st()),
                "hf_pool_bn_act_adjoint_nhwc")
     torch.cuda.synchronize()
@@ -243,7 +238,7 @@ def test_refusals_come_before_any_launch():
     MAXS = 1024  # HF_POOL_ACT_MAX_SPLITS of include/hf_pcg.h
     off = torch.zeros(3 * c + 4, device=DEV)[1:]  # partial rows one float behind a 16-byte boundary
 
-    out = Out(N * oh * ow, c, 2 * c)
+    out = RowOut(N * oh * ow, c, 2 * c)
     good_t = dict(out=out.ptr, out_ld=2 * c, slabs=p(sd), splits=2, stride=full + 4, a=p(ad), mean=p(md), rstd=p(rd),
                   w_=p(wd), v_w=p(vwd), v_b=p(vbd), px=p(pxd), p1=p(p1d), nparts=3, count=o["count"], idx=p(idxd), y=p(yd),
                   relu=1, n=N, h=h, w=w, oh=oh, ow=ow, c=c, dtype=F32)
@@ -266,7 +261,7 @@ def test_refusals_come_before_any_launch():
     assert bool(torch.isnan(out.buf).all())
     assert tangent() == 0 and tangent(y=None, relu=0) == 0 and tangent(v_b=None) == 0 and tangent(v_w=None) == 0
 
-    outs = dict(g=Out(N * h * w, c), gw=Out(3, c), gb=Out(3, c))
+    outs = dict(g=RowOut(N * h * w, c), gw=RowOut(3, c), gb=RowOut(3, c))
     good_a = dict({name: t.ptr for name, t in outs.items()}, rb=3, gy=p(gd), splits=2, slab=pooled + 4, a=p(ad), mean=p(md),
                   rstd=p(rd), w_=p(wd), idx=p(idxd), y=p(yd), relu=1, n=N, h=h, w=w, oh=oh, ow=ow, c=c, k=k, s=s, pd=pd,
                   dtype=F32)
