@@ -597,63 +597,11 @@ class ConvProblem(ctypes.Structure):
                                                             ("mat_ld", c_int64)]
 
 
-def _fill_problem(q, prob):
-    direction, out, act, mat, geo, splits, act_ld, out_c = prob[:8]
-    q.mat_ld = prob[8] if len(prob) > 8 else 0
-    n, h, w, c, k, r, s, st, pd = geo
-    q.direction, q.out, q.act, q.mat = int(direction), out.data_ptr(), act.data_ptr(), mat.data_ptr()
-    q.n, q.h, q.w, q.c, q.k, q.r, q.s = n, h, w, c, k, r, s
-    q.stride_h, q.stride_w, q.pad_h, q.pad_w = st[0], st[1], pd[0], pd[1]
-    q.act_ld, q.out_c, q.splits = act_ld, out_c, splits
-    q.slab_stride = out.shape[1] if out.dim() == 2 else 0
-
-
-def conv_group_slabs(problems, device):
-    """One launch for up to 4 slab-mode convolutions; ``problems``: tuples ``(direction, out, act, mat,
-    (n, h, w, c, k, r, s, stride, padding), splits, act_ld, out_c[, mat_ld])`` with ``out`` a [splits, ...] buffer."""
-    arr = (ConvProblem * len(problems))()
-    for q, prob in zip(arr, problems):
-        _fill_problem(q, prob)
-    check(load().hf_conv2d_nhwc_group_slabs(ctypes.cast(arr, c_void_p), len(problems), HF_F32,
-                                            current_stream_ptr(device)), "hf_conv2d_nhwc_group_slabs")
-
-
 class ConvBnSum(ctypes.Structure):
     """``hf_conv_bnsum`` (include/hf_pcg.h)."""
 
     _fields_ = [("x", c_void_p), ("mean", c_void_p), ("rstd", c_void_p), ("part_x", c_void_p), ("part_1", c_void_p),
                 ("part_rows", c_int64)]
-
-
-def conv_group_slabs_bnsum(problems, sums, device):
-    """``conv_group_slabs`` for tangent convolutions whose epilogue also writes the per-channel partial sums of a
-    train-mode BatchNorm behind them; ``sums``: per problem ``None`` or ``(x, mean, rstd, part_x, part_1)`` with
-    ``part_*`` of shape [ceil(rows / 64) * splits, k].  Returns False when the library refuses the geometry (the caller
-    issues the plain launch + the reduction launch)."""
-    arr = (ConvProblem * len(problems))()
-    bn = (ConvBnSum * len(problems))()
-    for q, b, prob, sm in zip(arr, bn, problems, sums):
-        _fill_problem(q, prob)
-        if sm is not None:
-            x, mean, rstd, part_x, part_1 = sm
-            b.x, b.mean, b.rstd = x.data_ptr(), mean.data_ptr(), rstd.data_ptr()
-            b.part_x, b.part_1, b.part_rows = part_x.data_ptr(), part_1.data_ptr(), part_1.shape[0]
-    rc = load().hf_conv2d_nhwc_group_slabs_bnsum(ctypes.cast(arr, c_void_p), len(problems), ctypes.cast(bn, c_void_p),
-                                                 HF_F32, current_stream_ptr(device))
-    if rc == HF_ERR_ARG:
-        return False
-    check(rc, "hf_conv2d_nhwc_group_slabs_bnsum")
-    return True
-
-
-def conv_dw_slabs(d_problem, w_problem, device):
-    """One data-gradient (or forward) problem and one weight-gradient problem in ONE launch; tuples as for
-    ``conv_group_slabs``."""
-    arr = (ConvProblem * 2)()
-    _fill_problem(arr[0], d_problem)
-    _fill_problem(arr[1], w_problem)
-    check(load().hf_conv2d_nhwc_dw_slabs(ctypes.byref(arr[0]), ctypes.byref(arr[1]), HF_F32,
-                                         current_stream_ptr(device)), "hf_conv2d_nhwc_dw_slabs")
 
 
 def conv_plan(direction, n, h, w, c, k, r, s, stride, padding):

@@ -22,6 +22,8 @@ On CPU tensors (host-logic tests, gloo tests) the gather is ``torch.cat``; on a
 GPU the HIP kernel is mandatory (``_lib`` raises if the library is missing).
 """
 
+import gc
+
 import torch
 
 from . import _lib
@@ -317,8 +319,18 @@ class CapturedOperator:
         """``fn`` captured on ``self.stream``.  ``keep``: the raw ``hipGraph_t`` stays available (``cg()`` clones
         it into its one-launch-per-iteration graph, product -> K1 -> K2 -> K3, hf_pcg_graph_*)."""
         g = torch.cuda.CUDAGraph(keep_graph=True) if keep else torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=self.stream, pool=pool):
-            fn()
+        # No cycle collection while the stream captures: a dead ``CUDAGraph`` that only the collector frees (an earlier
+        # session's, held in a reference cycle) synchronises the device in its destructor, which a capture in progress
+        # forbids -- the destructor throws and the process aborts.  ``torch.cuda.graph`` no longer collects on entry, so
+        # which allocation inside ``fn`` starts a collection is a matter of the process's history.
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g, stream=self.stream, pool=pool):
+                fn()
+        finally:
+            if collecting:
+                gc.enable()
         if keep:
             g.instantiate()
         return g
@@ -472,7 +484,6 @@ class GraphedOperator(CapturedOperator):
             warmup = 1 if GraphedOperator._captured_before else 3
         if not torch.cuda.is_available():
             raise RuntimeError("GraphedOperator needs a GPU")
-        import gc
 
         first = not GraphedOperator._captured_before
         GraphedOperator._captured_before = True

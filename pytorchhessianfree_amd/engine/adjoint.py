@@ -5,7 +5,7 @@ Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overal
 
 from .. import _lib
 from .problems import (affine_args, affine_train_args, affine_train_problem, bn_adjoint_args, bn_adjoint_problem,
-                       bn_adjoint_v4_args, problem)
+                       bn_adjoint_v4_args, conv_args, conv_backward_args, conv_problem, problem)
 
 
 class _AdjointSweep:
@@ -45,9 +45,8 @@ class _AdjointSweep:
             # a bias has no second-order term of its own: the convolutions read g_a itself.  (The chain's D + W launch
             # through the two-problem entry point -- the same pair of problems ``_conv_adjoint`` launches --, and in
             # sequence the extras BEHIND it: as the plain stack has always issued them)
-            if not u.im2col and not u.first and u.sD:
-                _lib.conv_dw_slabs((1, u.dbuf, u.ga, u.wT, u.geo, u.sD, 0, 0), (2, u.wbuf, u.x, u.ga, u.geo, u.sW, 0, 0),
-                                   self.dev)
+            if not u.im2col and not u.first and u.sD:  # (sD == 0, a tangent-free input: the weight gradient alone)
+                self._launch("hf_conv2d_nhwc_dw_slabs", *([q] for q in self._dw_problems(u, u.ga)))
             else:
                 self._conv_adjoint(u)
             if not self._extras_parallel:
@@ -75,8 +74,7 @@ class _AdjointSweep:
                 a_splits=1)))
         if self._extras_mode == 2 and not u.im2col and not u.first and u.sD:
             # the chain's launch also computes conv_D(g_a, V) -- the one extra term the chain itself needs next
-            _lib.conv_group_slabs([(1, u.dbuf, u.gah, u.wT, u.geo, u.sD, 0, 0), (2, u.wbuf, u.x, u.gah, u.geo, u.sW, 0, 0),
-                                   (1, u.dbuf[u.sD:], u.ga1, u.vT, u.geo, u.sD, 0, 0)], self.dev)
+            self._launch("hf_conv2d_nhwc_group_slabs", [*self._dw_problems(u, u.gah), self._dgrad_extra(u)], 3)
         else:
             self._conv_adjoint(u, u.gah)
 
@@ -107,6 +105,12 @@ class _AdjointSweep:
         # g = mask * (sum of both cotangents' slabs) -> u.g; g * w*rstd -> u.ga; per-channel sums
         self._launch("hf_chan_affine_bwd_ex", *bn_adjoint_args(bn_adjoint_problem(u, srcs, only_needed=True)))
 
+    @staticmethod
+    def _dw_problems(u, ga, dgrad=True):
+        """The data-gradient (``dgrad``) and the weight-gradient problem of the unit's convolution from ``ga``."""
+        d = [conv_problem(1, u.dbuf, ga, u.wT, u.geo, u.sD)] if dgrad else []
+        return d + [conv_problem(2, u.wbuf, u.x, ga, u.geo, u.sW)]
+
     def _conv_adjoint(self, u, ga=None):
         """Data + weight gradient of the unit's convolution from ``ga`` (default ``u.ga``), one launch."""
         ga = u.ga if ga is None else ga
@@ -114,16 +118,14 @@ class _AdjointSweep:
             self._conv_slabs(2, u.wbuf, u.cols_pad, ga, u.geo_w, u.sW, out_c=u.jcols)
             return
         if u.first or u.no_dgrad:  # the network input (or the output of frozen layers) needs no gradient
-            self._conv_slabs(2, u.wbuf, u.x, ga, u.geo, u.sW)
+            self._launch("hf_conv2d_nhwc_slabs", *conv_args(*self._dw_problems(u, ga, dgrad=False)))
             return
         # (Measured and rejected, round 4: the weight gradient -- off the adjoint chain, only the gather reads it -- as
         # its own launch on a side branch, the chain's launch computing the data gradient alone: one cross-branch
         # dependency PER UNIT costs far more than the shorter chain saves -- ResNet-18 1 518 -> 1 037 matvecs/s,
         # ResNet-50 topology 314 -> 253, All-CNN-C 753 -> 711.  A side branch pays when it forks ONCE: the Hessian
         # products' extras below.)
-        n_, h, w, c, k_, r, s, sd, pd = u.geo
-        self._launch("hf_conv2d_nhwc_backward_slabs", u.dbuf, u.wbuf, ga, u.x, u.wT, n_, h, w, c, k_, r, s, sd[0], sd[1],
-                     pd[0], pd[1], u.sD, u.dbuf.shape[1], u.sW, u.wbuf.shape[1])
+        self._launch("hf_conv2d_nhwc_backward_slabs", *conv_backward_args(*self._dw_problems(u, ga)))
 
     def _gather(self, out, g_fw, g_fb, first_order=False):
         """All parameter gradients into the flat vector (weight-gradient slabs summed on the way)."""

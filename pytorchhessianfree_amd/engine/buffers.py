@@ -9,7 +9,7 @@ import torch
 
 from .. import _lib
 from .common import _Unsupported, _flat_view, _live_taps
-from .problems import bn_adjoint_args, chan_sums_problem
+from .problems import Geometry, bn_adjoint_args, chan_sums_problem, conv_args, conv_problem
 
 
 def adjoint_split_ok(train, rb, hessian, map_bytes, max_bytes, enabled=True):
@@ -60,15 +60,11 @@ class _Buffers:
     # ResNet-50 topology 341 / 347 / 357 matvecs/s (profiles/r20_bn_defer_threshold.jsonl); ResNet-18 is the same at both.
     DEFER_MAX_BYTES = 4 * 6272 * 64 * 4
     # ---- buffers -------------------------------------------------------------------------
-    def _plan(self, direction, u, forward=False):
-        n, c, h, w = u.x.shape
-        k, _, r, s = u.conv.weight.shape
-        cin = 2 * c if (direction == 0 and not forward) else c
-        sp = _lib.load().hf_conv2d_nhwc_plan(direction, n, h, w, cin, k, r, s, u.conv.stride[0], u.conv.stride[1],
-                                             u.conv.padding[0], u.conv.padding[1],
-                                             0)
+    def _plan(self, direction, geo, name=None):
+        """The K-splits a slab-mode launch of this geometry uses; ``name``: the unit's (none: the im2col'd stem)."""
+        sp = _lib.load().hf_conv2d_nhwc_plan(direction, *geo.dims(), 0)
         if sp < 1:
-            raise _Unsupported(f"{u.name}: convolution geometry refused ({sp})")
+            raise _Unsupported(f"{name}: convolution geometry refused ({sp})" if name else f"stem geometry refused ({sp})")
         return sp
 
     def _allocate(self):
@@ -114,19 +110,19 @@ class _Buffers:
                 oh, ow = u.a.shape[2], u.a.shape[3]
                 j = c * r * s
                 u.cols = torch.empty((n, oh * ow, j), dtype=f32, device=dev)  # [N, OH*OW, c*r*s]
-                u.geo = (n * oh * ow, 1, 1, j, k, 1, 1, (1, 1), (0, 0))
+                u.geo = Geometry(n * oh * ow, 1, 1, j, k, 1, 1, (1, 1), (0, 0))
                 # the weight gradient reads the im2col with rows padded to 16-byte multiples (zero
                 # channels): 16-byte gathers instead of element-wise ones (28 -> 11 us for the 49-tap stem)
                 jp = -(-j // 4) * 4
                 u.cols_pad = torch.zeros((n, oh * ow, jp), dtype=f32, device=dev)
-                u.geo_w = (n * oh * ow, 1, 1, jp, k, 1, 1, (1, 1), (0, 0))
+                u.geo_w = u.geo._replace(c=jp)
                 u.jcols = j
                 if not u.conv.weight.is_contiguous():
                     raise _Unsupported(f"{u.name}: weight layout")
             else:
                 if c % 4 or k % 4:
                     raise _Unsupported(f"{u.name}: channel counts must be multiples of 4")
-                u.geo = (n, h, w, c, k, r, s, tuple(u.conv.stride), tuple(u.conv.padding))
+                u.geo = Geometry(n, h, w, c, k, r, s, tuple(u.conv.stride), tuple(u.conv.padding))
                 key = id(u.x)
                 if key not in xcats:
                     xcats[key] = torch.zeros((n, 2 * c, h, w), dtype=f32, device=dev).contiguous(memory_format=cl)
@@ -141,13 +137,13 @@ class _Buffers:
             u.rows, u.cout = n * oh * ow, k
             # split-K slab buffers
             if u.im2col:
-                u.sT = u.sF = self._plan_stem(0, u.geo)
-                u.sW = self._plan_stem(2, u.geo_w)
+                u.sT = u.sF = self._plan(0, u.geo)
+                u.sW = self._plan(2, u.geo_w)
                 u.sD = 0
             else:
-                u.sT, u.sW = self._plan(0, u), self._plan(2, u)
-                u.sD = 0 if (u.first or u.no_dgrad or u.dead) else self._plan(1, u)
-                u.sF = self._plan(0, u, forward=True)
+                u.sT, u.sW = self._plan(0, u.geo.doubled(), u.name), self._plan(2, u.geo, u.name)
+                u.sD = 0 if (u.first or u.no_dgrad or u.dead) else self._plan(1, u.geo, u.name)
+                u.sF = self._plan(0, u.geo, u.name)
             u.tbuf = torch.empty((max(u.sT, u.sF), u.rows * k), dtype=f32, device=dev)
             # Hessian products add, per layer, conv_W(t_x, g) to the weight gradient and conv_D(g, V) to the
             # data gradient (g: the step's first-order cotangent): as MORE SLABS of the same buffers, which
@@ -327,14 +323,6 @@ class _Buffers:
             self.sums_launches += 1
         self._sums_pending.clear()
 
-    def _plan_stem(self, direction, geo):
-        n, h, w, c, k, r, s, st, pd = geo
-        sp = _lib.load().hf_conv2d_nhwc_plan(direction, n, h, w, c, k, r, s, 1, 1, 0, 0,
-                                             0)
-        if sp < 1:
-            raise _Unsupported(f"stem geometry refused ({sp})")
-        return sp
-
     # ---- own forward pass ------------------------------------------------------------------
     def set_batch(self, x, targets=None):
         """A new input batch of the same shape (and its targets): static input, the stem's im2col."""
@@ -430,20 +418,20 @@ class _Buffers:
         """``count`` entries of the flat vector ``v`` at parameter ``index`` (None: a frozen parameter -- no slice)."""
         return None if index is None else v[self._offs[index]: self._offs[index] + count]
 
+    def _weight_tangent(self, v, u):
+        """v_W of ``u``'s convolution as a slice of ``v``; zeros for a frozen weight (conv(x, 0) = 0)."""
+        vw = self._param_slice(v, u.pw, u.conv.weight.numel())
+        return self._zeros(u.conv.weight.numel()) if vw is None else vw
+
     def _chan_sums(self, gy, splits, slab, n, c, hw, row_blocks, **operands):
         """A plain per-channel reduction by the BatchNorm adjoint's launch (``problems.chan_sums_problem``)."""
         self._launch("hf_chan_affine_bwd_ex",
                      *bn_adjoint_args(chan_sums_problem(gy, splits, slab, n, c, hw, row_blocks, **operands)))
 
-    def _tgeo(self, u):
-        n, h, w, c, k, r, s, st, pd = u.geo
-        return (n, h, w, 2 * c, k, r, s, st, pd)
-
     # ---- kernels ---------------------------------------------------------------------------
-    def _conv_slabs(self, direction, out, act, mat, geo, splits, act_ld=0, out_c=0, mat_ld=0):
-        n, h, w, c, k, r, s, st, pd = geo
-        self._launch("hf_conv2d_nhwc_slabs", direction, out, act, mat, n, h, w, c, k, r, s, st[0], st[1], pd[0], pd[1],
-                     act_ld, mat_ld, out_c, splits, out.shape[1] if out.dim() == 2 else 0)
+    def _conv_slabs(self, direction, out, act, mat, geo, splits, **lds):
+        """One slab-mode convolution (``problems.conv_problem``)."""
+        self._launch("hf_conv2d_nhwc_slabs", *conv_args(conv_problem(direction, out, act, mat, geo, splits, **lds)))
 
     def _conv_carrying_scatter(self, u, mat, splits, src, half):
         """The im2col'd first layer's convolution (its weight operand ``mat`` is a slice of a flat vector, no
@@ -453,16 +441,13 @@ class _Buffers:
         geometry / tensor count the merged launch refuses) -- the caller issues the two launches."""
         if not (self._carry_ok and u.im2col and self._slot_list):
             return False
-        n, h, w, c, k, r, s_, st, pd = u.geo
         table = _lib.unpack_table(src, self._slot_list, half=half)
         periods = _lib.compact_periods(self._slot_list)
-        conv = (u.tbuf, u.cols, mat, n, h, w, c, k, r, s_, st[0], st[1], pd[0], pd[1], 0, 0, splits, u.tbuf.shape[1], src)
+        conv = (u.tbuf, u.cols, mat, *u.geo.dims(), 0, 0, splits, u.tbuf.shape[1], src)
         if periods is not None:  # (local_compact: ``src`` is a vector in the compact layout)
-            rc = self._launch_rc("hf_conv2d_nhwc_slabs_unpack_compact", *conv, *table[:-1], periods, table[-1])
+            taken = self._launch_unless_refused("hf_conv2d_nhwc_slabs_unpack_compact", *conv, *table[:-1], periods,
+                                                table[-1])
         else:
-            rc = self._launch_rc("hf_conv2d_nhwc_slabs_unpack", *conv, *table)
-        if rc == _lib.HF_ERR_ARG:
-            self._carry_ok = False
-            return False
-        _lib.check(rc, "hf_conv2d_nhwc_slabs_unpack")
-        return True
+            taken = self._launch_unless_refused("hf_conv2d_nhwc_slabs_unpack", *conv, *table)
+        self._carry_ok = taken  # (a refusal: not tried again)
+        return taken

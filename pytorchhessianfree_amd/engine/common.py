@@ -16,20 +16,34 @@ def _ptr(t):
 class _Launcher:
     """The one way an engine calls a launching entry point of the library (all end in ``int dtype, void* stream``): by
     name, fetched from the loaded library at the moment of the call, on the current stream; tensors go as their addresses,
-    ``None`` as NULL."""
+    ``None`` as NULL, a (non-empty) list of problem structs of one kind (problems.py) as a contiguous array of them."""
+
+    @staticmethod
+    def _arg(a):
+        if isinstance(a, torch.Tensor):
+            return _ptr(a)
+        if isinstance(a, list):  # (the array itself, not a ``ctypes.cast`` of it: a cast leaves a reference cycle behind)
+            return (type(a[0]) * len(a))(*a)
+        return a
 
     def _launch_rc(self, name, *args):
         """The entry point's return code, for the callers that read it themselves."""
-        args = [_ptr(a) if isinstance(a, torch.Tensor) else a for a in args]
-        return getattr(_lib.load(), name)(*args, _lib.HF_F32, _lib.current_stream_ptr(self.dev))
+        return getattr(_lib.load(), name)(*map(self._arg, args), _lib.HF_F32, _lib.current_stream_ptr(self.dev))
 
     def _launch(self, name, *args):
         _lib.check(self._launch_rc(name, *args), name)
 
+    def _launch_unless_refused(self, name, *args):
+        """False where the entry point refuses its arguments (``HF_ERR_ARG``: nothing was launched, the caller has
+        another form of the same work); any other code is checked."""
+        rc = self._launch_rc(name, *args)
+        if rc != _lib.HF_ERR_ARG:
+            _lib.check(rc, name)
+        return rc != _lib.HF_ERR_ARG
+
     def _launch_pair(self, name, p1, p2):
         """The two-problem form of a launch: the same descriptions the one-problem form takes apart (problems.py)."""
-        arr = (type(p1) * 2)(p1, p2)
-        self._launch(name, _lib.ctypes.cast(arr, _P))
+        self._launch(name, [p1, p2])
 
 
 def _same(a, b):

@@ -155,10 +155,7 @@ class FusedGGNEngine(_Topology, _ConvEngine):
             if self._slot_list:
                 _lib.unpack_tangent(v, self._slot_list)
             return
-        if s.pw is None:  # (frozen stem weight under a trainable BatchNorm: conv(x, 0) = 0)
-            vw = self._zeros(s.conv.weight.numel())
-        else:
-            vw = v[self._offs[s.pw]: self._offs[s.pw] + s.conv.weight.numel()]
+        vw = self._weight_tangent(v, s)  # (zeros for a frozen stem weight under a trainable BatchNorm)
         if not self._conv_carrying_scatter(s, vw, s.sT, v, 1):
             _lib.unpack_tangent(v, self._slot_list)  # v_W halves of all [W | v_W] operands: one launch
             self._conv_slabs(0, s.tbuf, s.cols, vw, s.geo, s.sT)
@@ -310,15 +307,9 @@ class FusedGGNEngine(_Topology, _ConvEngine):
                     else:
                         self._bn_adjoint(u, incoming.pop(id(u)))
                         self._bn_adjoint(ds, [(last.g, 1, 0)])
-                    if u.no_dgrad:  # (the block input carries no tangent: the two weight gradients only)
-                        _lib.conv_group_slabs(
-                            [(2, u.wbuf, u.x, u.ga, u.geo, u.sW, 0, 0), (2, ds.wbuf, ds.x, ds.ga, ds.geo, ds.sW, 0, 0)],
-                            self.dev)
-                    else:
-                        _lib.conv_group_slabs(
-                            [(1, u.dbuf, u.ga, u.wT, u.geo, u.sD, 0, 0), (2, u.wbuf, u.x, u.ga, u.geo, u.sW, 0, 0),
-                             (1, ds.dbuf, ds.ga, ds.wT, ds.geo, ds.sD, 0, 0),
-                             (2, ds.wbuf, ds.x, ds.ga, ds.geo, ds.sW, 0, 0)], self.dev)
+                    # (a block input that carries no tangent: the two weight gradients only)
+                    probs = [q for b in (u, ds) for q in self._dw_problems(b, b.ga, dgrad=not u.no_dgrad)]
+                    self._launch("hf_conv2d_nhwc_group_slabs", probs, len(probs))
                 else:
                     self._adjoint_unit(u, incoming.pop(id(u)))
                 if k > 0:

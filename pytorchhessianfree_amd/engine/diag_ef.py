@@ -121,21 +121,19 @@ class _DiagEF:
             u.rb1 = 1
             if self._diag_batched:
                 n = u.a.shape[0]
-                u.geo1 = ((n, u.a.shape[2], u.a.shape[3]) + tuple(u.geo_w[3:])) if u.im2col else tuple(u.geo)
-                n_, h, w, c, k_, r, s_, sd, pd = u.geo1
-                u.sW1 = _lib.conv_sqsum_plan(n_, h, w, c, k_, r, s_, sd, pd)
+                u.geo1 = u.geo_w._replace(n=n, h=u.a.shape[2], w=u.a.shape[3]) if u.im2col else u.geo
+                u.sW1 = _lib.conv_sqsum_plan(*u.geo1)
                 # shares of the samples for the channel sums: ~one workgroup per CU (64 channels each), none empty
                 u.rb1 = max(1, min(n, 256 // -(-k // 64)))
                 while -(-n // u.rb1) * (u.rb1 - 1) >= n:
                     u.rb1 -= 1
             elif u.im2col:
                 rows1 = u.a.shape[2] * u.a.shape[3]
-                u.geo_w1 = (rows1,) + tuple(u.geo_w[1:])
-                u.sW1 = self._plan_stem(2, u.geo_w1)
+                u.geo_w1 = u.geo_w.with_n(rows1)
+                u.sW1 = self._plan(2, u.geo_w1)
             else:
-                u.geo1 = (1,) + tuple(u.geo[1:])
-                n_, h, w, c, k_, r, s_, sd, pd = u.geo1
-                u.sW1 = _lib.conv_plan(2, 1, h, w, c, k_, r, s_, sd, pd)
+                u.geo1 = u.geo.with_n(1)
+                u.sW1 = self._plan(2, u.geo1, u.name)
             u.wps = torch.zeros((u.sW1, u.conv.weight.numel()), dtype=f32, device=dev)  # dead taps stay 0
             if u.pw is not None:
                 tensors[u.pw] = u.wps[0]

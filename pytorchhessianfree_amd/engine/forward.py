@@ -32,8 +32,7 @@ class _Forward:
         if u.im2col:  # 1x1 product over the im2col; the weight is read from the parameter itself
             self._conv_slabs(0, u.tbuf, u.cols, u.conv.weight.detach(), u.geo, u.sF)
             return
-        n, h, w, c, k, r, s, st, pd = u.geo
-        self._conv_slabs(0, u.tbuf, u.x, u.wcat, u.geo, u.sF, mat_ld=2 * c)
+        self._conv_slabs(0, u.tbuf, u.x, u.wcat, u.geo, u.sF, mat_ld=u.geo.doubled().c)
 
     def _loss_head(self):
         """Softmax probabilities and the cross-entropy value of the current logits (the reference's

@@ -5,7 +5,7 @@ Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overal
 
 import torch
 
-from .. import _lib
+from .problems import conv_args, conv_problem
 
 
 class _HessianExtras:
@@ -19,12 +19,17 @@ class _HessianExtras:
         if u.bn is not None and not u.train:  # (train mode: the tangent sweep left this sum, engine/tangent.py)
             self._scale_second_order_sum(u)
         if not u.im2col and not u.first and u.sD:  # (u.sD == 0: a tangent-free input -- both terms vanish)
-            c = u.x.shape[1]
+            # conv_W(t_x, g_a): t_x read in place, the first half of the [t_x | x] operand
+            w_extra = conv_problem(2, u.wbuf[u.sW:], u.xcat, u.ga1, u.geo, u.sW, act_ld=u.geo.doubled().c)
             if self._extras_mode == 2:  # (conv_D(g_a, V) rides in the chain's launch: only the weight term here)
-                self._conv_slabs(2, u.wbuf[u.sW:], u.xcat, u.ga1, u.geo, u.sW, act_ld=2 * c)
+                self._launch("hf_conv2d_nhwc_slabs", *conv_args(w_extra))
             else:
-                _lib.conv_dw_slabs((1, u.dbuf[u.sD:], u.ga1, u.vT, u.geo, u.sD, 0, 0),
-                                   (2, u.wbuf[u.sW:], u.xcat, u.ga1, u.geo, u.sW, 2 * c, 0), self.dev)
+                self._launch("hf_conv2d_nhwc_dw_slabs", [self._dgrad_extra(u)], [w_extra])
+
+    @staticmethod
+    def _dgrad_extra(u):
+        """conv_D(g_a, V) as ``sD`` more slabs of the unit's data-gradient buffer."""
+        return conv_problem(1, u.dbuf[u.sD:], u.ga1, u.vT, u.geo, u.sD)
 
     # Those extras are half of a Hessian product's launches and none of them is on the adjoint sweep's dependency
     # chain: they are issued on a SECOND STREAM forked off after the tangent sweep (inside a hipGraph capture: a

@@ -400,23 +400,19 @@ class PlainStackEngine(_ConvEngine):
         first = self.units[0]
         carried = False
         if first.im2col and not first.dead:  # (the first layer's launch carries the v_W scatter of all the others)
-            vw = (v[self._offs[first.pw]: self._offs[first.pw] + first.conv.weight.numel()] if first.pw is not None
-                  else self._zeros(first.conv.weight.numel()))
-            carried = self._conv_carrying_scatter(first, vw, first.sT, v, 1)
+            carried = self._conv_carrying_scatter(first, self._weight_tangent(v, first), first.sT, v, 1)
         if self._slot_list and not carried:
             _lib.unpack_tangent(v, self._slot_list)  # v_W halves of all [W | v_W] operands: one launch
         for u in self.units:
             if u.dead:  # (frozen, behind frozen layers only: no tangent)
                 continue
             if u.im2col:  # no input tangent: conv(x, v_W) as a 1x1 product over the im2col
-                vw = (v[self._offs[u.pw]: self._offs[u.pw] + u.conv.weight.numel()] if u.pw is not None
-                      else self._zeros(u.conv.weight.numel()))
                 if not (carried and u is first):
-                    self._conv_slabs(0, u.tbuf, u.cols, vw, u.geo, u.sT)
+                    self._conv_slabs(0, u.tbuf, u.cols, self._weight_tangent(v, u), u.geo, u.sT)
             elif u.train:  # (the epilogue writes the tangent's per-channel partial sums where it takes the geometry)
                 self._tangent_convs([u])
             else:
-                self._conv_slabs(0, u.tbuf, u.xcat, u.wcat, self._tgeo(u), u.sT)
+                self._conv_slabs(0, u.tbuf, u.xcat, u.wcat, u.geo.doubled(), u.sT)
             if u.pool is not None:
                 self._pool_tangent(u, v)
             else:

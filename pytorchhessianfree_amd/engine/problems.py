@@ -1,11 +1,35 @@
-"""The one place a BatchNorm / bias launch of the conv-unit engines is described: per struct kind of include/hf_pcg.h ONE
-builder that fills the struct from a unit, and one ``*_args`` function that takes a filled struct apart into the positional
-argument list (without ``dtype, stream``) of the one-problem entry point.  The one-problem form launches
-``*_args(problem)``, the two-problem form an array of two of the same problems (``_Launcher._launch_pair``).
+"""The one place a layer launch of the conv-unit engines is described: per struct kind of include/hf_pcg.h ONE builder
+that fills the struct (from a unit; a convolution's from its operands and its ``Geometry``), and one ``*_args`` function
+that takes a filled struct apart into the positional argument list (without ``dtype, stream``) of the one-problem entry
+point.  The one-problem form launches ``*_args(problem)``, the array forms a list of the same problems (``_Launcher``).
 
 Nothing here touches the device: a unit is anything with the attributes read below."""
 
+from collections import namedtuple
+
 from .. import _lib
+
+
+class Geometry(namedtuple("Geometry", "n h w c k r s stride padding")):
+    """A convolution's geometry: input [n, h, w, c] (NHWC), ``k`` filters of ``r`` x ``s`` taps, ``stride`` and ``padding``
+    per axis as (along h, along w)."""
+
+    __slots__ = ()
+
+    def doubled(self):
+        """Over the ``[t_x | x]`` operand: twice the input channels."""
+        return self._replace(c=2 * self.c)
+
+    def with_n(self, n):
+        """The same layer on ``n`` samples (rows, for an im2col'd layer)."""
+        return self._replace(n=n)
+
+    def dims(self):
+        """``n, h, w, c, k, r, s, stride_h, stride_w, pad_h, pad_w``: as every positional entry point lists them."""
+        return self[:7] + (self.stride[0], self.stride[1], self.padding[0], self.padding[1])
+
+
+_DIMS = ("n", "h", "w", "c", "k", "r", "s", "stride_h", "stride_w", "pad_h", "pad_w")  # ... and hf_conv_problem names them
 
 
 def problem(kind, **fields):
@@ -89,13 +113,44 @@ def bn_adjoint_v4_args(q):
             q.n * q.hw, q.c)
 
 
+# ---- hf_conv_problem: every slab-mode convolution, alone, grouped or as a D + W pair --------------------------------
+def conv_problem(direction, out, act, mat, geo, splits, act_ld=0, out_c=0, mat_ld=0):
+    """Direction 0 (forward / tangent), 1 (data gradient) or 2 (weight gradient) of the layer ``geo``: ``out`` receives
+    ``splits`` slabs, ``out.shape[1]`` apart where it is a [splits, numel] buffer; ``act_ld`` / ``mat_ld``: the pixel
+    stride of an operand that is a channel slice of a wider buffer, ``out_c``: of a weight gradient with padded rows."""
+    return problem(_lib.ConvProblem, direction=int(direction), out=out, act=act, mat=mat, **dict(zip(_DIMS, geo.dims())),
+                   act_ld=act_ld, out_c=out_c, splits=int(splits), mat_ld=mat_ld,
+                   slab_stride=out.shape[1] if out is not None and out.dim() == 2 else 0)
+
+
+def conv_args(q):
+    """``hf_conv2d_nhwc_slabs``."""
+    return (q.direction, q.out, q.act, q.mat, *(getattr(q, name) for name in _DIMS), q.act_ld, q.mat_ld, q.out_c, q.splits,
+            q.slab_stride)
+
+
+def conv_backward_args(d, w):
+    """``hf_conv2d_nhwc_backward_slabs``: the data-gradient problem ``d`` and the weight-gradient problem ``w`` of ONE
+    layer on dense operands, both from the same cotangent (``d.act`` and ``w.mat``)."""
+    dims = tuple(getattr(d, name) for name in _DIMS)
+    if dims != tuple(getattr(w, name) for name in _DIMS) or d.act != w.mat or any(
+            (q.act_ld, q.out_c, q.mat_ld) != (0, 0, 0) for q in (d, w)):
+        raise RuntimeError("conv_backward_args: not the dense D + W pair of one layer")
+    return (d.out, w.out, d.act, w.act, d.mat, *dims, d.splits, d.slab_stride, w.splits, w.slab_stride)
+
+
+def conv_bnsum(x, mean, rstd, part_x, part_1):
+    """``hf_conv_bnsum``: the tangent convolution's epilogue leaves the partial sums of a train-mode BatchNorm behind it
+    (``x``: the recorded convolution output) in ``part_x`` / ``part_1`` [ceil(rows / 64) * splits, k]; a problem without:
+    ``_lib.ConvBnSum()``."""
+    return problem(_lib.ConvBnSum, x=x, mean=mean, rstd=rstd, part_x=part_x, part_1=part_1, part_rows=part_1.shape[0])
+
+
 # ---- the squared-sum launches of the batched diagonal empirical Fisher (positional entry points, no struct) ------------
 def conv_sqsum_args(out, act, mat, geo, splits, pre, act_ld=0, out_c=0):
     """``hf_conv2d_nhwc_sqsum_slabs``: ``out`` [splits, numel] receives split s's partial sum over its samples of the
     squared per-sample weight gradient of ``act`` (X) and ``mat`` (dY), each scaled by ``pre`` before it is squared."""
-    n, h, w, c, k, r, s, st, pd = geo
-    return (out, act, mat, n, h, w, c, k, r, s, st[0], st[1], pd[0], pd[1], act_ld, out_c, float(pre), int(splits),
-            out.shape[1])
+    return (out, act, mat, *Geometry(*geo).dims(), act_ld, out_c, float(pre), int(splits), out.shape[1])
 
 
 def chan_sqsum_args(g, n, c, hw, row_blocks, pre, gw2=None, gb2=None, x=None, mean=None, rstd=None):

@@ -6,7 +6,8 @@ Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overal
 import os
 
 from .. import _lib
-from .problems import affine_args, affine_problem, affine_train_args, affine_train_problem
+from .problems import (affine_args, affine_problem, affine_train_args, affine_train_problem, conv_args, conv_bnsum,
+                       conv_problem)
 
 
 def head_fused_shape_ok(rows, features, classes):
@@ -86,10 +87,10 @@ class _TangentSweep:
         train-mode BatchNorm the launch's epilogue also writes the per-channel partial sums of its output tiles
         (``hf_conv2d_nhwc_group_slabs_bnsum``): the reduction launch between convolution and elementwise pass is gone
         (``u.tsum``: ``_bn_tangent`` then adds ``u.tp1 / u.tpx`` up instead of ``u.gb / u.gw``)."""
-        probs = [(0, u.tbuf, u.xcat, u.wcat, self._tgeo(u), u.sT, 0, 0) for u in units]
+        probs = [conv_problem(0, u.tbuf, u.xcat, u.wcat, u.geo.doubled(), u.sT) for u in units]
         if any(u.epi for u in units):
-            sums = [(u.a, u.mean, u.rstd, u.tpx, u.tp1) if u.epi else None for u in units]
-            if _lib.conv_group_slabs_bnsum(probs, sums, self.dev):
+            sums = [conv_bnsum(u.a, u.mean, u.rstd, u.tpx, u.tp1) if u.epi else _lib.ConvBnSum() for u in units]
+            if self._launch_unless_refused("hf_conv2d_nhwc_group_slabs_bnsum", probs, len(probs), sums):
                 for u in units:
                     u.tsum = u.epi
                 return
@@ -98,8 +99,6 @@ class _TangentSweep:
         for u in units:
             u.tsum = False
         if len(units) == 1:
-            u = units[0]
-            self._conv_slabs(0, u.tbuf, u.xcat, u.wcat, self._tgeo(u), u.sT)
+            self._launch("hf_conv2d_nhwc_slabs", *conv_args(probs[0]))
         else:
-            _lib.conv_group_slabs(probs, self.dev)
-
+            self._launch("hf_conv2d_nhwc_group_slabs", probs, len(probs))

@@ -14,6 +14,8 @@ from tol import within
 
 from conv_refs import GEOMS
 from pytorchhessianfree_amd import _lib
+from pytorchhessianfree_amd.engine.common import _Launcher
+from pytorchhessianfree_amd.engine.problems import Geometry, conv_bnsum, conv_problem
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -215,7 +217,14 @@ def test_tangent_convolution_with_batchnorm_partial_sums_in_its_epilogue(geom):
     gen = torch.Generator(device=DEV).manual_seed(7 + c + k)
     x = _cl(torch.randn(n, c, h, w_, device=DEV, generator=gen))
     wt = _cl(torch.randn(k, c, r, s, device=DEV, generator=gen) / (c * r * s) ** 0.5)
-    geo = (n, h, w_, c, k, r, s, stride, padding)
+    geo = Geometry(n, h, w_, c, k, r, s, stride, padding)
+    eng = _Launcher()  # (what an engine is to its launches: a launcher with a device)
+    eng.dev = torch.device(DEV)
+
+    def group_slabs_bnsum(problems, sums):
+        """The tangent sweep's launch: False where the library refuses the table (HF_ERR_ARG)."""
+        return eng._launch_unless_refused("hf_conv2d_nhwc_group_slabs_bnsum", problems, len(problems), sums)
+
     splits = _lib.conv_plan(0, n, h, w_, c, k, r, s, stride, padding)
     oh, ow = (h + 2 * padding[0] - r) // stride[0] + 1, (w_ + 2 * padding[1] - s) // stride[1] + 1
     rows = n * oh * ow
@@ -227,8 +236,8 @@ def test_tangent_convolution_with_batchnorm_partial_sums_in_its_epilogue(geom):
     nparts = -(-rows // 64) * splits
     out = torch.empty_like(plain)
     p1, px = (torch.full((nparts, k), float("nan"), device=DEV) for _ in range(2))
-    probs = [(0, out, x, wt, geo, splits, 0, 0)]
-    assert _lib.conv_group_slabs_bnsum(probs, [(a, mean, rstd, px, p1)], DEV)
+    probs = [conv_problem(0, out, x, wt, geo, splits)]
+    assert group_slabs_bnsum(probs, [conv_bnsum(a, mean, rstd, px, p1)])
     assert torch.equal(out, plain)
     t64 = plain.double().sum(0).view(rows, k)
     xhat = ((a - mean) * rstd).double()
@@ -236,17 +245,17 @@ def test_tangent_convolution_with_batchnorm_partial_sums_in_its_epilogue(geom):
         assert torch.isfinite(got).all()
         within(float(((got.double().sum(0) - ref).abs() / mag.clamp_min(1e-30)).max()), 2e-6)
     p1b, pxb = torch.empty_like(p1), torch.empty_like(px)
-    assert _lib.conv_group_slabs_bnsum(probs, [(a, mean, rstd, pxb, p1b)], DEV)
+    assert group_slabs_bnsum(probs, [conv_bnsum(a, mean, rstd, pxb, p1b)])
     assert torch.equal(p1b, p1) and torch.equal(pxb, px)
     # two problems in one launch: the first without sums
     out2, out3 = torch.empty_like(plain), torch.empty_like(plain)
     p1c, pxc = torch.empty_like(p1), torch.empty_like(px)
-    assert _lib.conv_group_slabs_bnsum([(0, out2, x, wt, geo, splits, 0, 0), (0, out3, x, wt, geo, splits, 0, 0)],
-                                       [None, (a, mean, rstd, pxc, p1c)], DEV)
+    assert group_slabs_bnsum([conv_problem(0, out2, x, wt, geo, splits), conv_problem(0, out3, x, wt, geo, splits)],
+                             [_lib.ConvBnSum(), conv_bnsum(a, mean, rstd, pxc, p1c)])
     assert torch.equal(out2, plain) and torch.equal(out3, plain)
     assert torch.equal(p1c, p1) and torch.equal(pxc, px)
     # a wrong number of partial rows is refused (the caller then takes the two-launch path)
-    assert not _lib.conv_group_slabs_bnsum(probs, [(a, mean, rstd, px[:-1], p1[:-1])], DEV)
+    assert not group_slabs_bnsum(probs, [conv_bnsum(a, mean, rstd, px[:-1], p1[:-1])])
 
 
 def test_weight_gradient_of_a_zero_padded_operand_on_the_flat_96_row_tiles():

@@ -935,7 +935,11 @@ def test_grouped_launches_equal_the_single_ones_bitwise():
     ``hf_chan_affine_pair`` and ``hf_chan_affine_bwd_pair`` write exactly what the corresponding
     single launches write."""
     from pytorchhessianfree_amd import _lib
+    from pytorchhessianfree_amd.engine.common import _Launcher
+    from pytorchhessianfree_amd.engine.problems import Geometry, conv_problem
 
+    eng = _Launcher()  # (what an engine is to its launches: a launcher with a device)
+    eng.dev = torch.device(DEV)
     gen = torch.Generator(device=DEV).manual_seed(77)
     r_ = lambda *s: torch.randn(*s, device=DEV, generator=gen)
     n, h, w_, c, k = 8, 7, 7, 64, 128
@@ -957,8 +961,8 @@ def test_grouped_launches_equal_the_single_ones_bitwise():
             _lib.conv2d_nhwc_slabs(d, a, act, mat, *geo[:7], geo[7], geo[8], sp)
             singles.append(a)
             grouped.append(b)
-            group_args.append((d, b, act, mat, geo, sp, 0, 0))
-        _lib.conv_group_slabs(group_args, x.device)
+            group_args.append((d, b, act, mat, Geometry(*geo), sp))
+        eng._launch("hf_conv2d_nhwc_group_slabs", [conv_problem(*q) for q in group_args], len(group_args))
         for a, b in zip(singles, grouped):
             assert torch.equal(a, b)
         return singles, group_args
@@ -975,7 +979,7 @@ def test_grouped_launches_equal_the_single_ones_bitwise():
     singles, group_args = singles_and_group([(1, geo_s, gyb, ws.permute(1, 2, 3, 0).contiguous(), xb.numel()),
                                              (2, geo_s, xb, gyb, ws.numel()), (0, geo_f, xb, wf, 32 * 32 * 32 * 96)])
     merged = [torch.zeros_like(t) for t in singles[:2]]
-    _lib.conv_dw_slabs(*((q[0], out, *q[2:]) for q, out in zip(group_args, merged)), x.device)
+    eng._launch("hf_conv2d_nhwc_dw_slabs", *([conv_problem(q[0], out, *q[2:])] for q, out in zip(group_args, merged)))
     assert torch.equal(merged[0], singles[0]) and torch.equal(merged[1], singles[1])
 
     # BatchNorm tangent / adjoint pairs against the single launches

@@ -206,3 +206,46 @@ def test_unit_level_code_reads_nothing_residual():
             if (isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id in ("getattr", "hasattr")
                     and len(node.args) >= 2 and isinstance(node.args[1], ast.Constant)):
                 assert node.args[1].value not in RESIDUAL_ATTRIBUTES, (name, node.lineno, node.args[1].value)
+
+
+REMOVED_FROM_LIB = ("conv_group_slabs", "conv_group_slabs_bnsum", "conv_dw_slabs", "_fill_problem")
+# what the engines ask the library without launching anything: the planners and the table-size queries
+PLANNERS = {"hf_conv2d_nhwc_plan", "hf_conv2d_nhwc_sqsum_plan", "hf_dense_plan", "hf_linear_ce_head_slabs",
+            "hf_bn_sums_table"}
+
+
+def _engine_sources():
+    folder = os.path.join(ROOT, "pytorchhessianfree_amd", "engine")
+    return {name: open(os.path.join(folder, name)).read() for name in sorted(os.listdir(folder)) if name.endswith(".py")}
+
+
+def test_one_path_to_the_launching_entry_points():
+    """The binding holds no engine code for the grouped / paired convolutions, and outside ``common.py`` (the launcher)
+    no engine file calls an ``hf_*`` attribute of the loaded library itself -- but the planners, which launch nothing."""
+    from pytorchhessianfree_amd import _lib
+
+    for name in REMOVED_FROM_LIB:
+        assert not hasattr(_lib, name), name
+    sources = _engine_sources()
+    assert "common.py" in sources and len(sources) > 10
+    for name, text in sources.items():
+        if name == "common.py":
+            continue
+        for node in ast.walk(ast.parse(text)):
+            if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr.startswith("hf_"):
+                assert node.func.attr in PLANNERS, (name, node.lineno, node.func.attr)
+            if isinstance(node, ast.Call) and isinstance(node.func, ast.Name):
+                assert node.func.id != "getattr" or not any(  # (nor fetches one by name)
+                    isinstance(a, ast.Call) and isinstance(a.func, ast.Attribute) and a.func.attr == "load"
+                    for a in node.args[:1]), (name, node.lineno)
+
+
+def test_geometries_are_read_by_field():
+    """No engine file indexes or slices a geometry (``geo[``) or unpacks one into nine names."""
+    for name, text in _engine_sources().items():
+        assert "geo[" not in text and "geo1[" not in text and "geo_w[" not in text, name
+        for node in ast.walk(ast.parse(text)):
+            if isinstance(node, (ast.Assign, ast.For)):
+                targets = node.targets if isinstance(node, ast.Assign) else [node.target]
+                for t in targets:
+                    assert not (isinstance(t, ast.Tuple) and len(t.elts) == 9), (name, node.lineno)

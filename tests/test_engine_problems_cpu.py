@@ -1,9 +1,10 @@
-"""CPU: the descriptions of the conv-unit engines' BatchNorm / bias launches (``engine/problems.py``) and the launcher
-(``engine/common._Launcher``).  Per struct kind of include/hf_pcg.h: the builder fills the struct from a stand-in unit
-(CPU tensors), and the ``*_args`` function puts every field where the one-problem entry point's prototype has it -- against
-the literal argument lists below, written from the header."""
+"""CPU: the descriptions of the conv-unit engines' BatchNorm / bias and convolution launches (``engine/problems.py``) and
+the launcher (``engine/common._Launcher``).  Per struct kind of include/hf_pcg.h: the builder fills the struct from a
+stand-in unit or from stand-in operands (CPU tensors), and the ``*_args`` function puts every field where the one-problem
+entry point's prototype has it -- against the literal argument lists below, written from the header."""
 
 import ctypes
+import gc
 
 import pytest
 import torch
@@ -22,6 +23,12 @@ BWD_EX = ("gx", "gw", "gb", "gres", "gy", "gy_splits", "gy_slab", "gy2", "gy2_sp
 ADJOINT_V4 = ("g_out", "ga_out", "gy", "gy_splits", "gy_slab", "gy2", "gy2_splits", "gy2_slab", "mask_src", "w", "rstd",
               "rows", "c")
 V4_FROM = {"g_out": "gres", "ga_out": "gx"}  # hf_bn_adjoint_v4_pair's reading of hf_bn_adjoint_problem
+GEOMETRY = ("n", "h", "w", "c", "k", "r", "s", "stride_h", "stride_w", "pad_h", "pad_w")
+CONV_SLABS = ("direction", "out", "act", "mat") + GEOMETRY + ("act_ld", "mat_ld", "out_c", "splits", "slab_stride")
+BACKWARD_SLABS = ("dx", "dw", "dy", "x", "w_t") + GEOMETRY + ("splits_d", "slab_stride_d", "splits_w", "slab_stride_w")
+# hf_conv2d_nhwc_backward_slabs's reading of the data-gradient problem ``d`` and the weight-gradient problem ``w``
+BACKWARD_FROM = {"dx": "d.out", "dw": "w.out", "dy": "d.act", "x": "w.act", "w_t": "d.mat", "splits_d": "d.splits",
+                 "slab_stride_d": "d.slab_stride", "splits_w": "w.splits", "slab_stride_w": "w.slab_stride"}
 
 # entry point -> (prototype, struct, args function, arguments that are no field of the struct)
 KINDS = {
@@ -29,6 +36,7 @@ KINDS = {
     "hf_chan_affine_train": (AFFINE_TRAIN, _lib.AffineTrainProblem, P.affine_train_args, {"add_ld": 0}),
     "hf_chan_affine_bwd_ex": (BWD_EX, _lib.BnAdjointProblem, P.bn_adjoint_args, {"channels_last": 1}),
     "hf_bn_adjoint_v4": (ADJOINT_V4, _lib.BnAdjointProblem, P.bn_adjoint_v4_args, {}),
+    "hf_conv2d_nhwc_slabs": (CONV_SLABS, _lib.ConvProblem, P.conv_args, {}),
 }
 
 
@@ -166,6 +174,21 @@ class FakeLib:
         self.calls.append(tuple((q.out, q.a_slab) for q in ctypes.cast(problems, ctypes.POINTER(_lib.AffineProblem * 2)).contents))
         return self.code
 
+    def hf_fake_group(self, problems, count, dtype, stream):
+        arr = ctypes.cast(problems, ctypes.POINTER(_lib.ConvProblem * count)).contents
+        self.calls.append(([(q.out, q.slab_stride) for q in arr], dtype, stream))
+        return self.code
+
+    def hf_fake_bnsum(self, problems, count, sums, dtype, stream):
+        arr = ctypes.cast(problems, ctypes.POINTER(_lib.ConvProblem * count)).contents
+        bn = ctypes.cast(sums, ctypes.POINTER(_lib.ConvBnSum * count)).contents
+        self.calls.append(([(q.out, b.part_1, b.part_rows) for q, b in zip(arr, bn)], dtype, stream))
+        return self.code
+
+    def hf_fake_dw(self, d, w, dtype, stream):
+        self.calls.append(tuple(ctypes.cast(q, ctypes.POINTER(_lib.ConvProblem)).contents.out for q in (d, w)))
+        return self.code
+
     def hf_error_string(self, code):
         return b"refused"
 
@@ -192,3 +215,100 @@ def test_launcher_fetches_the_entry_point_at_call_time(monkeypatch):
     p2.out = 7
     eng._launch_pair("hf_fake_pair", p1, p2)
     assert first.calls[-1] == ((101, p1.a_slab), (7, p1.a_slab))
+
+
+def test_launcher_passes_lists_of_problems_as_contiguous_arrays(monkeypatch):
+    """The array forms (grouped convolutions: ``array, count``; with BatchNorm sums: ``array, count, array``; the D + W
+    launch: two pointers): the name is looked up at call time, every list arrives as one contiguous array of the given
+    structs, ``dtype, stream`` are appended, and the refusal of a table is a return code the caller reads."""
+    eng = _Launcher()
+    eng.dev = torch.device("cpu")
+    monkeypatch.setattr(_lib, "current_stream_ptr", lambda dev: "stream")
+    first, second = FakeLib(), FakeLib(code=_lib.HF_ERR_ARG)
+    probs = [numbered(_lib.ConvProblem) for _ in range(3)]
+    for i, q in enumerate(probs):
+        q.out = 7 + i
+    monkeypatch.setattr(_lib, "load", lambda: first)
+    eng._launch("hf_fake_group", probs, len(probs))
+    assert first.calls == [([(7, probs[0].slab_stride), (8, probs[0].slab_stride), (9, probs[0].slab_stride)],
+                            _lib.HF_F32, "stream")]
+    sums = [_lib.ConvBnSum(), P.conv_bnsum(*(torch.zeros(5, 8) for _ in range(5)))]
+    monkeypatch.setattr(_lib, "load", lambda: second)
+    assert eng._launch_rc("hf_fake_bnsum", probs[:2], 2, sums) == _lib.HF_ERR_ARG and not first.calls[1:]
+    assert second.calls == [([(7, None, 0), (8, sums[1].part_1, 5)], _lib.HF_F32, "stream")]
+    assert eng._launch_unless_refused("hf_fake_bnsum", probs[:2], 2, sums) is False and len(second.calls) == 2
+    monkeypatch.setattr(_lib, "load", lambda: FakeLib(code=-3))  # (any other failure is no refusal)
+    with pytest.raises(RuntimeError, match="hf_fake_bnsum failed with code -3"):
+        eng._launch_unless_refused("hf_fake_bnsum", probs[:2], 2, sums)
+    monkeypatch.setattr(_lib, "load", lambda: first)
+    assert eng._launch_unless_refused("hf_fake_bnsum", probs[:2], 2, sums) is True
+    eng._launch("hf_fake_dw", [probs[2]], [probs[0]])
+    assert first.calls[-1] == (9, 7)
+    # ... and no launch leaves work for the cycle collector (``ctypes.cast`` would: a captured sweep must not start it)
+    gc.collect()
+    gc.disable()
+    try:
+        for _ in range(50):
+            eng._launch("hf_fake", probs, len(probs), sums, torch.zeros(1), None)
+            eng._launch_pair("hf_fake", probs[0], probs[1])
+        assert gc.collect() == 0
+    finally:
+        gc.enable()
+
+
+def test_backward_args_take_every_position_from_the_right_problem():
+    d, w = numbered(_lib.ConvProblem), numbered(_lib.ConvProblem)
+    for q, direction in ((d, 1), (w, 2)):
+        q.direction, q.act_ld, q.out_c, q.mat_ld = direction, 0, 0, 0
+    for name in ("out", "act", "splits", "slab_stride"):  # what the two problems do not share
+        setattr(w, name, getattr(w, name) + 1000)
+    w.mat = d.act  # both read the same cotangent
+    args = P.conv_backward_args(d, w)
+    assert len(args) == len(BACKWARD_SLABS) == len(_lib.SIGNATURES["hf_conv2d_nhwc_backward_slabs"][1]) - 2
+    for pos, name in enumerate(BACKWARD_SLABS):
+        if name in GEOMETRY:
+            assert args[pos] == getattr(d, name) == getattr(w, name), name
+        else:
+            which, field = BACKWARD_FROM[name].split(".")
+            assert args[pos] == getattr({"d": d, "w": w}[which], field), name
+    assert len(set(args)) == len(args)  # (no value stands at two positions: none was taken from the other problem)
+    for name in GEOMETRY + ("mat", "act_ld", "out_c", "mat_ld"):  # another layer, another cotangent, a sliced operand
+        other = _lib.ConvProblem.from_buffer_copy(w)
+        setattr(other, name, getattr(w, name) + 1)
+        with pytest.raises(RuntimeError, match="not the dense D \\+ W pair of one layer"):
+            P.conv_backward_args(d, other)
+    d.out_c = 4
+    with pytest.raises(RuntimeError, match="not the dense"):
+        P.conv_backward_args(d, w)
+
+
+GEO = P.Geometry(5, 7, 6, 8, 12, 3, 2, (2, 1), (0, 1))  # r != s, per-axis stride and padding
+
+
+def test_convolution_problem_from_operands_and_geometry():
+    out2, out1, out4 = torch.zeros(3, 40), torch.zeros(40), torch.zeros(5, 12, 3, 6)
+    act, mat = torch.zeros(5, 8, 7, 6), torch.zeros(12, 8, 3, 2)
+    q = P.conv_problem(0, out2, act, mat, GEO, 3)
+    assert (q.direction, q.out, q.act, q.mat) == (0, addr(out2), addr(act), addr(mat))
+    assert tuple(getattr(q, name) for name in GEOMETRY) == (5, 7, 6, 8, 12, 3, 2, 2, 1, 0, 1)
+    assert (q.act_ld, q.out_c, q.mat_ld, q.splits, q.slab_stride) == (0, 0, 0, 3, 40)
+    # slabs are ``out.shape[1]`` apart in a [splits, numel] buffer; any other ``out`` is one slab
+    assert [P.conv_problem(2, o, act, mat, GEO, 1).slab_stride for o in (out1, out2, out4)] == [0, 40, 0]
+    q = P.conv_problem(2, out2, act, None, GEO, 2, act_ld=16, out_c=7, mat_ld=24)
+    assert (q.direction, q.mat, q.act_ld, q.out_c, q.mat_ld, q.splits) == (2, None, 16, 7, 24, 2)
+    b = P.conv_bnsum(act, None, out1, out2, out4)
+    assert (b.x, b.mean, b.rstd, b.part_x, b.part_1, b.part_rows) == (addr(act), None, addr(out1), addr(out2), addr(out4), 5)
+    z = _lib.ConvBnSum()  # a problem without sums
+    assert (z.x, z.part_1, z.part_rows) == (None, None, 0)
+
+
+def test_geometry_record():
+    assert P.Geometry._fields == ("n", "h", "w", "c", "k", "r", "s", "stride", "padding")
+    n, h, w, c, k, r, s, stride, padding = GEO  # (still a tuple: what reads ``u.geo`` positionally keeps working)
+    assert (n, h, w, c, k, r, s, stride, padding) == (5, 7, 6, 8, 12, 3, 2, (2, 1), (0, 1)) == tuple(GEO)
+    assert GEO.doubled() == GEO._replace(c=16) and GEO.doubled()._replace(c=8) == GEO
+    assert GEO.with_n(1) == GEO._replace(n=1) and GEO.with_n(1)._replace(n=5) == GEO
+    for g in (GEO.doubled(), GEO.with_n(42), GEO.doubled().with_n(1)):
+        assert isinstance(g, P.Geometry) and (g.r, g.s, g.stride, g.padding) == (3, 2, (2, 1), (0, 1))
+    assert GEO.dims() == (5, 7, 6, 8, 12, 3, 2, 2, 1, 0, 1) and len(GEO.dims()) == len(GEOMETRY)
+    assert P.conv_sqsum_args(torch.zeros(2, 9), None, None, GEO, 2, 0.5, out_c=7)[3:] == GEO.dims() + (0, 7, 0.5, 2, 9)

@@ -80,7 +80,7 @@ def test_map_sizes_live_taps_and_row_blocks(case):
 
 @pytest.mark.parametrize("case", gn.CASES)
 def test_the_planner_accepts_every_layer_in_every_direction(case):
-    """``hf_conv2d_nhwc_plan`` as ``buffers._plan`` / ``_plan_stem`` ask it: direction 0 with ``c`` (forward) and ``2c``
+    """``hf_conv2d_nhwc_plan`` as ``buffers._Buffers._plan`` asks it: direction 0 with ``c`` (forward) and ``2c``
     (the ``[t_x | x]`` operand), 1 and 2; the im2col'd first layer as a 1x1 product over its columns (padded to a
     multiple of 4 for the weight gradient)."""
     plan = _lib.load().hf_conv2d_nhwc_plan

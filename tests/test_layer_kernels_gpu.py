@@ -18,6 +18,8 @@ from guarded import DEV, ERR_ARG, GUARD, NAN, P, RowOut, _ids, dv, optr, p, st, 
 import layer_refs as L
 from layer_refs import U32, U64
 from pytorchhessianfree_amd import _lib
+from pytorchhessianfree_amd.engine.common import _Launcher
+from pytorchhessianfree_amd.engine.problems import Geometry, conv_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -679,6 +681,13 @@ def _conv_geoms():
     return out
 
 
+def launcher(device):
+    """What an engine is to its launches: a ``_Launcher`` with a device."""
+    eng = _Launcher()
+    eng.dev = torch.device(device)
+    return eng
+
+
 def _cl(t):
     return t.contiguous(memory_format=torch.channels_last)
 
@@ -701,9 +710,10 @@ def test_merged_convolution_launches_against_float64(geom):
     xd, gyd = _cl(x.to(DEV)), _cl(gy.to(DEV))
     wT, vT = (m.permute(1, 2, 3, 0).contiguous().to(DEV) for m in (w, v))
     wide_ = _cl(torch.cat([t_x, x], 1).to(DEV))  # NHWC rows of [t_x | x]
-    geo = (n, h, w_, c, k, r, s, stride, padding)
+    geo = Geometry(n, h, w_, c, k, r, s, stride, padding)
     sd, sw = _lib.conv_plan(1, *geo), _lib.conv_plan(2, *geo)
     nd, nw = x.numel(), w.numel()
+    dw_slabs = lambda d, w: launcher(xd.device)._launch("hf_conv2d_nhwc_dw_slabs", [d], [w])  # noqa: E731
 
     def rel(slabs, ref, shape):
         got = slabs.double().sum(0).view(shape).permute(0, 3, 1, 2).cpu()
@@ -720,7 +730,7 @@ def test_merged_convolution_launches_against_float64(geom):
         p(dx2), p(dw2), p(gyd), p(xd), p(wT), n, h, w_, c, k, r, s, stride[0], stride[1], padding[0], padding[1], sd, nd,
         sw, nw, _lib.HF_F32, st()), "hf_conv2d_nhwc_backward_slabs")
     dx3, dw3 = fresh()
-    _lib.conv_dw_slabs((1, dx3, gyd, wT, geo, sd, 0, 0), (2, dw3, xd, gyd, geo, sw, 0, 0), xd.device)
+    dw_slabs(conv_problem(1, dx3, gyd, wT, geo, sd), conv_problem(2, dw3, xd, gyd, geo, sw))
     for a, b in ((dx2, dw2), (dx3, dw3)):
         assert torch.equal(a, dx1) and torch.equal(b, dw1)
         within(rel(a, gx64, (n, h, w_, c)), 2e-5, note=geom)
@@ -730,7 +740,7 @@ def test_merged_convolution_launches_against_float64(geom):
     _lib.conv2d_nhwc_slabs(1, dx4, gyd, vT, *geo, sd)
     _lib.conv2d_nhwc_slabs(2, dw4, wide_, gyd, *geo, sw, act_ld=2 * c)
     dx5, dw5 = fresh()
-    _lib.conv_dw_slabs((1, dx5, gyd, vT, geo, sd, 0, 0), (2, dw5, wide_, gyd, geo, sw, 2 * c, 0), xd.device)
+    dw_slabs(conv_problem(1, dx5, gyd, vT, geo, sd), conv_problem(2, dw5, wide_, gyd, geo, sw, act_ld=2 * c))
     assert torch.equal(dx5, dx4) and torch.equal(dw5, dw4)
     within(rel(dx5, gxv64, (n, h, w_, c)), 2e-5, note=geom)
     within(rel(dw5, gwt64, (k, r, s, c)), 2e-5, note=geom)

@@ -3,6 +3,7 @@ evaluation (``optimizer._SessionTrials``), the prefetch hooks of CG-backtracking
 (reference ``hessianfree/cg_backtracking.py:53-112``, ``hessianfree/linesearch.py:8-103``: same results, same
 early exits, fewer device->host reads), and the structural loss detection (``engine.ce_loss_spec``)."""
 
+import pytest
 import torch
 
 from pytorchhessianfree_amd.cg_backtracking import cg_efficient_backtracking
@@ -280,3 +281,45 @@ def test_iteration_graph_of_an_operator_without_a_product_graph_is_none(monkeypa
     op = TwoGraphs()
     assert hfcg._iteration_graph(op, None, None, 0.1, 0, with_product=True) is None
     assert not getattr(op, "_iteration_graphs", None)
+
+
+@pytest.mark.parametrize("was_enabled", [True, False])
+def test_no_cycle_collection_while_a_product_is_captured(monkeypatch, was_enabled):
+    """``CapturedOperator._capture``: the collector is off for exactly the span of the capture -- a dead graph freed by
+    it synchronises the device, which a capture in progress forbids -- and is left as it was found, also when the
+    captured function raises.  (Stand-ins for the graph and its context: no GPU.)"""
+    import gc
+
+    from pytorchhessianfree_amd import curvature
+
+    seen = []
+
+    class Graph:
+        def __init__(self, **kw):
+            seen.append(("graph", gc.isenabled()))
+
+    class Capturing:
+        def __init__(self, g, stream=None, pool=None):
+            pass
+
+        def __enter__(self):
+            seen.append(("begin", gc.isenabled()))
+
+        def __exit__(self, *exc):
+            seen.append(("end", gc.isenabled()))
+
+    class Op:
+        stream = None
+
+    monkeypatch.setattr(curvature.torch.cuda, "CUDAGraph", Graph)
+    monkeypatch.setattr(curvature.torch.cuda, "graph", Capturing)
+    before = gc.isenabled()
+    try:
+        gc.enable() if was_enabled else gc.disable()
+        curvature.CapturedOperator._capture(Op(), lambda: seen.append(("fn", gc.isenabled())))
+        assert seen[1:] == [("begin", False), ("fn", False), ("end", False)] and gc.isenabled() == was_enabled
+        with pytest.raises(ZeroDivisionError):
+            curvature.CapturedOperator._capture(Op(), lambda: 1 / 0)
+        assert gc.isenabled() == was_enabled
+    finally:
+        gc.enable() if before else gc.disable()
