@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 26
+#define HF_ABI_VERSION 27
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -1053,6 +1053,50 @@ int hf_dense_act_forward(void* y, const void* slabs, int splits, int64_t slab_st
 int hf_dense_loss_head(int kind, const void* logits, const void* targets, void* p, void* dl, void* dl_ps, void* loss,
                        void* flag, void* work, double scale_g, double scale_ps, double coef, int64_t rows, int64_t c,
                        int dtype, void* stream);
+
+/* ---- depthwise convolutions inside the GGN product (hf_dwconv.hip) ---------------- */
+/*
+ * The sweeps through a depthwise nn.Conv2d (groups == c_in == c_out == c, weight [c, 1, r, s]) of a plain stack
+ * (engine/plain.py), on kernels of their own: a lane owns 4 consecutive channels, a workgroup a channel block x an 8x8
+ * pixel tile whose halo it stages into LDS once (padding = zeros in LDS); the weight W and the CG vector's slice V (same
+ * shape) are read IN PLACE -- no [W | v_W] operand, no transposed copy.  Common contract: HF_F32 only, NHWC, c % 4 == 0,
+ * 1 <= r*s <= 49 taps, stride 1 .. 8 and padding 0 .. kernel extent - 1 per axis, dilation 1, the padded map at least
+ * one kernel large, n*h*w*c and n*oh*ow*c < 2^31.  Operands need only 4-byte alignment (act_ld need not be a multiple of
+ * 4): the 16-byte forms are chosen on the host where base pointers and pixel pitches allow them.  No atomics; two launches
+ * on the same operands give the same bits; nothing outside the operands' extents is read or written.  Anything else is
+ * refused with HF_ERR_ARG before any launch; one host function is the definition of what is accepted, and every entry
+ * point below runs it.
+ *   hf_dwconv2d_nhwc_plan: the number of weight-gradient slabs (splits_w >= 1) a backward launch of this geometry
+ *                          writes, or HF_ERR_ARG.  The (sample, 8x8 output tile) units in ascending order are cut into
+ *                          splits_w consecutive runs of ceil(units / want) units, want = min(units, 64, ceil(512 / channel
+ *                          blocks)); the last run may be shorter, none is empty.
+ *   hf_dwconv2d_nhwc_tangent:
+ *       out[n,oh,ow,ch] = sum_{i,j} t_x[n, oh*stride_h - pad_h + i, ow*stride_w - pad_w + j, ch] * W[ch,i,j]
+ *                                 + x[same pixel, ch] * V[ch,i,j]            (a pixel outside the map counts as zero)
+ *       t_x and x share the pixel pitch act_ld (0 = c): the two halves of the producer's [t_x | x] operand (2c), or a
+ *       dense map (c).  Either term may be absent, not both: t_x == NULL (a tangent-free input; W is not read) or
+ *       V == NULL (a frozen weight; x is not read).  The forward pass is t_x = NULL, V = W.  One fmaf chain from zero over
+ *       the taps in ascending (i, j); within a tap first t_x * W, then x * V.  out: ONE dense slab [n, oh, ow, c].
+ *   hf_dwconv2d_nhwc_backward_slabs: data and weight gradient of the cotangent ga [n, oh, ow, c] in ONE launch.
+ *       dx[n,h,w,ch] = sum_{i,j} ga[n, (h + pad_h - i) / stride_h, (w + pad_w - j) / stride_w, ch] * W[ch,i,j] over the
+ *       taps whose divisions are exact and in range: one fmaf chain from zero over those taps in ascending (i, j); ONE
+ *       dense slab.  dx == NULL (the first live unit): not computed, W is not read.
+ *       gw_slabs[s][ch,i,j] = sum over run s's units of ga[n,oh,ow,ch] * x[n, oh*stride_h - pad_h + i, .., ch]  -- splits_w
+ *       slabs of [c*r*s] in PARAMETER order, slab_stride elements apart (>= c*r*s where splits_w > 1), for hf_pack_ex to
+ *       add in split order (no permutation).  Per unit and tap: a lane's fmaf chain over its pixels of the tile
+ *       (ascending), a __shfl_down tree over the wave's pixel slots (offsets 32, 16, .. channel-block quads), the four
+ *       waves in wave order, then added to the run's sum (units ascending).  x at pixel pitch act_ld, ga dense.
+ *       splits_w must be hf_dwconv2d_nhwc_plan's count for the geometry (HF_ERR_ARG otherwise).
+ */
+int hf_dwconv2d_nhwc_plan(int64_t n, int64_t h, int64_t w, int64_t c, int64_t r, int64_t s, int64_t stride_h,
+                          int64_t stride_w, int64_t pad_h, int64_t pad_w);
+int hf_dwconv2d_nhwc_tangent(void* out, const void* t_x, const void* x, int64_t act_ld, const void* W, const void* V,
+                             int64_t n, int64_t h, int64_t w, int64_t c, int64_t r, int64_t s, int64_t stride_h,
+                             int64_t stride_w, int64_t pad_h, int64_t pad_w, int dtype, void* stream);
+int hf_dwconv2d_nhwc_backward_slabs(void* dx, void* gw_slabs, const void* ga, const void* x, int64_t act_ld, const void* W,
+                                    int64_t n, int64_t h, int64_t w, int64_t c, int64_t r, int64_t s, int64_t stride_h,
+                                    int64_t stride_w, int64_t pad_h, int64_t pad_w, int splits_w, int64_t slab_stride,
+                                    int dtype, void* stream);
 
 /* ---- RCCL (resolved at run time from the already-loaded librccl) ----------- */
 typedef struct hf_comm hf_comm_t;

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HF_PCG_LIB") or os.path.join(_HERE, "csrc", "libhfpcg.so")
 
 HF_F32, HF_F64 = 0, 1
-ABI_VERSION = 26
+ABI_VERSION = 27
 HF_ERR_ARG = -1  # hf_status of include/hf_pcg.h: null / negative / inconsistent argument
 HF_M_NONE, HF_M_DIAG, HF_M_EXTERNAL = 0, 1, 2
 REASONS = {
@@ -220,6 +220,11 @@ SIGNATURES = {
     "hf_dense_act_forward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int64, c_int,
                                      c_void_p]),
     "hf_dense_loss_head": (c_int, [c_int] + [c_void_p] * 8 + [c_double] * 3 + [c_int64, c_int64, c_int, c_void_p]),
+    "hf_dwconv2d_nhwc_plan": (c_int, [c_int64] * 10),
+    "hf_dwconv2d_nhwc_tangent": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p] + [c_int64] * 10
+                                 + [c_int, c_void_p]),
+    "hf_dwconv2d_nhwc_backward_slabs": (c_int, [c_void_p] * 4 + [c_int64, c_void_p] + [c_int64] * 10
+                                        + [c_int, c_int64, c_int, c_void_p]),
     "hf_comm_unique_id": (c_int, [ctypes.c_char_p]),
     "hf_comm_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.c_char_p, c_int, c_int]),
     "hf_comm_destroy": (c_int, [c_void_p]),
@@ -648,6 +653,14 @@ def conv2d_nhwc_slabs(direction, out, act, mat, n, h, w, c, k, r, s, stride, pad
             out.shape[1], HF_F32, current_stream_ptr(out.device)),
         "hf_conv2d_nhwc_slabs")
     return out
+
+
+def dwconv_plan(n, h, w, c, r, s, stride, padding):
+    """Number of weight-gradient slabs a depthwise backward launch of this geometry writes (``hf_dwconv2d_nhwc_plan``)."""
+    sp = load().hf_dwconv2d_nhwc_plan(n, h, w, c, r, s, stride[0], stride[1], padding[0], padding[1])
+    if sp < 1:
+        check(sp, "hf_dwconv2d_nhwc_plan")
+    return sp
 
 
 def conv_sqsum_plan(n, h, w, c, k, r, s, stride, padding, target_blocks=0):

@@ -165,6 +165,10 @@ SWITCHES = {
                            "inside ONE launch per layer (hf_conv2d_nhwc_sqsum_slabs, hf_chan_sqsum) and gathers once, "
                            "instead of per-sample weight-gradient launches and one squaring gather per sample",
                            "tests/test_diag_ef_batched_engine_gpu.py::test_without_the_switch_no_new_entry_point_is_called"),
+    "HF_DW_ENGINE": ("0", "1: the plain-stack engine takes depthwise Conv2d units (groups = channels) on the kernels of "
+                     "hf_dwconv.hip; off by default until its GGN products per second are measured against the "
+                     "autograd path on a MobileNet-style stack -- without it such a net keeps that path",
+                     "tests/test_dwsep_engine_gpu.py::test_eval_point_against_float64"),
     "HF_CHUNKED_ALLREDUCE": ("auto", "0 / 1: force the single-graph resp. the two-phase data-parallel product",
                              "tests/test_distributed_gpu.py::test_step_two_ranks_engine_session_equals_cpu_whole_batch"),
     "HF_DIRECT_RCCL": ("1", "0: every collective through torch.distributed (no communicator of the package's own)",

@@ -11,9 +11,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 # one translation unit per kernel family: PCG solver | gather / scatter | BatchNorm / bias maps | convolutions |
-# pooling + classifier heads | fully-connected layers | the RCCL shim
+# pooling + classifier heads | fully-connected layers | depthwise convolutions | the RCCL shim
 SOURCES = [os.path.join(HERE, f) for f in ("hf_pcg.hip", "hf_pack.hip", "hf_bn.hip", "hf_conv.hip", "hf_head.hip",
-                                           "hf_dense.hip", "hf_rccl.hip")]
+                                           "hf_dense.hip", "hf_dwconv.hip", "hf_rccl.hip")]
 HDR = os.path.join(ROOT, "include", "hf_pcg.h")
 HDRS_SHARED = [os.path.join(HERE, f) for f in ("hf_common.h", "hf_unpack.h", "hf_store.h")]
 OUT = os.path.join(HERE, "libhfpcg.so")
@@ -29,6 +29,9 @@ FLAGS = [
     "-Wall",
     "-Wno-unused-function",
 ]
+# per translation unit: hf_dwconv.hip keeps its fp32 arithmetic scalar per lane (no packed v_pk_*_f32 forms: each fmaf
+# of its documented chains is one instruction of its own)
+SOURCE_FLAGS = {"hf_dwconv.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def needs_build():
@@ -53,7 +56,7 @@ def build(force=False, verbose=True, out=None, extra_flags=()):
 
         def compile_one(pair):
             src, obj = pair
-            cmd = [hipcc, *FLAGS, *extra_flags, "-I", os.path.join(ROOT, "include"), "-c", src, "-o", obj]
+            cmd = [hipcc, *FLAGS, *SOURCE_FLAGS.get(os.path.basename(src), ()), *extra_flags, "-I", os.path.join(ROOT, "include"), "-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd), flush=True)
             subprocess.run(cmd, check=True)

@@ -9,7 +9,7 @@ import torch
 
 from .. import _lib
 from .common import _Unsupported, _flat_view, _live_taps
-from .problems import Geometry, bn_adjoint_args, chan_sums_problem, conv_args, conv_problem
+from .problems import Geometry, bn_adjoint_args, chan_sums_problem, conv_args, conv_problem, dwconv_args, dwconv_problem
 
 
 def adjoint_split_ok(train, rb, hessian, map_bytes, max_bytes, enabled=True):
@@ -67,6 +67,13 @@ class _Buffers:
             raise _Unsupported(f"{name}: convolution geometry refused ({sp})" if name else f"stem geometry refused ({sp})")
         return sp
 
+    def _plan_depthwise(self, geo, name):
+        """The weight-gradient slabs a depthwise backward launch of this geometry writes (``hf_dwconv2d_nhwc_plan``)."""
+        try:
+            return _lib.dwconv_plan(geo.n, geo.h, geo.w, geo.c, geo.r, geo.s, geo.stride, geo.padding)
+        except _lib.Refused as e:
+            raise _Unsupported(f"{name}: depthwise convolution geometry refused ({e})") from None
+
     def _allocate(self):
         """Every buffer the sweeps touch is owned by the engine and STATIC: the activations are
         recomputed in place by ``forward_own`` (own kernels), so one engine -- and the hipGraphs
@@ -119,6 +126,16 @@ class _Buffers:
                 u.jcols = j
                 if not u.conv.weight.is_contiguous():
                     raise _Unsupported(f"{u.name}: weight layout")
+            elif u.depthwise:
+                # the weight [c, 1, r, s] and its tangent (the CG vector's slice) are read in place: no [W | v_W] operand,
+                # no (I, H, W, O) copy, no tangent slot; the input operand is the shared [t_x | x] buffer
+                u.geo = Geometry(n, h, w, c, k, r, s, tuple(u.conv.stride), tuple(u.conv.padding))
+                key = id(u.x)
+                if key not in xcats:
+                    xcats[key] = torch.zeros((n, 2 * c, h, w), dtype=f32, device=dev).contiguous(memory_format=cl)
+                u.xcat, u.live = xcats[key], 0
+                if not u.conv.weight.is_contiguous():
+                    raise _Unsupported(f"{u.name}: weight layout")
             else:
                 if c % 4 or k % 4:
                     raise _Unsupported(f"{u.name}: channel counts must be multiples of 4")
@@ -140,6 +157,10 @@ class _Buffers:
                 u.sT = u.sF = self._plan(0, u.geo)
                 u.sW = self._plan(2, u.geo_w)
                 u.sD = 0
+            elif u.depthwise:  # (one slab per direction; the weight gradient's count from the kernels' own plan)
+                u.sT = u.sF = 1
+                u.sW = self._plan_depthwise(u.geo, u.name)
+                u.sD = 0 if (u.no_dgrad or u.dead) else 1
             else:
                 u.sT, u.sW = self._plan(0, u.geo.doubled(), u.name), self._plan(2, u.geo, u.name)
                 u.sD = 0 if (u.first or u.no_dgrad or u.dead) else self._plan(1, u.geo, u.name)
@@ -204,7 +225,7 @@ class _Buffers:
                 # (row tile, split): beyond 256 rows the separate reduction's `rb` rows are cheaper
                 # for the elementwise pass to add up)
                 tp_rows = -(-u.rows // 64) * u.sT
-                u.epi = (not u.im2col and not u.first and hasattr(u, "xcat")
+                u.epi = (not u.im2col and not u.first and not u.depthwise and hasattr(u, "xcat")
                          and tp_rows <= 256
                          and os.environ.get("HF_BN_EPILOGUE", "1") != "0")
                 if self.hessian:
@@ -248,13 +269,13 @@ class _Buffers:
         self._carry_ok = True  # (the stem's launch carries the v_W scatter; False once the library refused it)
         # (I, H, W, O) copies: the weights (once per step) and, for Hessian products, V (per product)
         self._wt_slots = [(self._offs[u.pw], u.wT, u.x.shape[1]) for u in self.units
-                          if not u.im2col and not u.first and u.pw is not None and u.sD]
+                          if not u.im2col and not u.depthwise and not u.first and u.pw is not None and u.sD]
         # frozen convolution weights: constants the flat parameter vector does not hold -- their W half / (I, H, W, O)
         # copy come from the parameter itself (`refresh_frozen`: at construction and whenever it was written to)
-        self._frozen_w = [u for u in self.units if not u.im2col and u.pw is None]
+        self._frozen_w = [u for u in self.units if not u.im2col and not u.depthwise and u.pw is None]
         self._frozen_seen = {}
         self._vt_slots = [(self._offs[u.pw], u.vT, u.x.shape[1]) for u in self.units
-                          if self.hessian and not u.im2col and u.sD and u.pw is not None]
+                          if self.hessian and not u.im2col and not u.depthwise and u.sD and u.pw is not None]
         self._allocate_head()
         # the parameters as ONE flat vector, when they are consecutive views of one (the optimizer's
         # arena): every W half is then refreshed by a single scatter launch
@@ -397,7 +418,7 @@ class _Buffers:
             _lib.unpack_tangent(flat, self._slot_list, half=0)
         else:
             for u in self.units:
-                if not u.im2col and u.pw is not None:
+                if not u.im2col and not u.depthwise and u.pw is not None:
                     c = u.x.shape[1]
                     u.wcat[:, :c].copy_(self.params[u.pw].detach())
         if transposed:
@@ -405,7 +426,7 @@ class _Buffers:
                 _lib.unpack_tangent(flat, self._wt_slots, half=2)
             else:
                 for u in self.units:
-                    if not u.im2col and not u.first and u.pw is not None and u.sD:
+                    if not u.im2col and not u.depthwise and not u.first and u.pw is not None and u.sD:
                         u.wT.copy_(self.params[u.pw].detach().permute(1, 2, 3, 0))
 
     def _zeros(self, k):
@@ -432,6 +453,11 @@ class _Buffers:
     def _conv_slabs(self, direction, out, act, mat, geo, splits, **lds):
         """One slab-mode convolution (``problems.conv_problem``)."""
         self._launch("hf_conv2d_nhwc_slabs", *conv_args(conv_problem(direction, out, act, mat, geo, splits, **lds)))
+
+    def _dwconv(self, u, x, act_ld, **operands):
+        """One launch of the depthwise unit ``u`` on the input ``x`` (``problems.dwconv_problem``)."""
+        geo = operands.pop("geo", u.geo)
+        self._launch(*dwconv_args(dwconv_problem(geo, x, act_ld, u.conv.weight, **operands)))
 
     def _conv_carrying_scatter(self, u, mat, splits, src, half):
         """The im2col'd first layer's convolution (its weight operand ``mat`` is a slice of a flat vector, no

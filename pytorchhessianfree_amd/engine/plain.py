@@ -1,5 +1,7 @@
 """The plain conv-ReLU stack engine (All-CNN-C, BASELINE.json configs[3])."""
 
+import os
+
 import torch
 from torch import nn
 
@@ -49,7 +51,14 @@ class PlainStackEngine(_ConvEngine):
     its weight is read in place), the layers run on the skinny GEMMs of hf_dense.hip (W and the vector's slice V in
     place; 2 launches per layer forward / tangent, 3 adjoint), ``hf_unflatten_slabs_nhwc`` sums the first layer's
     data-gradient slabs into the NHWC cotangent of the last map.  Weight / bias gradients go into buffers of the engine
-    and enter the gather as ordinary entries.  GGN products, one process, batch <= 256."""
+    and enter the gather as ordinary entries.  GGN products, one process, batch <= 256.
+
+    Depthwise units (``HF_DW_ENGINE=1``; MobileNet-style ``dw + pw`` pairs): ``Conv2d(groups = in = out = c)``, ``c % 4 == 0``,
+    up to 49 taps, anywhere but first in the net, with the same bias / BatchNorm / ReLU / max-pool behind it as a dense unit.
+    The kernels of hf_dwconv.hip read the weight ``[c, 1, r, s]`` and the vector's slice V in place (no ``[W | v_W]``
+    operand, no transposed copy, no tangent slot) and leave ONE slab per direction: ``hf_dwconv2d_nhwc_tangent`` on the
+    halves of the producer's ``[t_x | x]`` operand, ``hf_dwconv2d_nhwc_backward_slabs`` for the data gradient and the weight
+    gradient's slabs (parameter order: no permutation in the gather).  GGN products, one process."""
 
     mode = ("fused curvature engine (plain conv-ReLU stack): own deterministic convolutions (split-K slabs summed "
             "by the consumer kernel), bias / ReLU / max-pool fused, 4 launches per layer")
@@ -85,14 +94,18 @@ class PlainStackEngine(_ConvEngine):
                 i, cur = self._layout_tail_layer(leaves, i, dense, cur)
                 continue
             if type(m) is nn.Conv2d:
-                if m.groups != 1 or tuple(m.dilation) != (1, 1) or not getattr(m, "_hf_channels_last", False):
-                    raise _Unsupported(f"conv {len(units)}: needs prepare_model(channels_last=True), groups = dilation = 1")
+                if tuple(m.dilation) != (1, 1) or not getattr(m, "_hf_channels_last", False):
+                    raise _Unsupported(f"conv {len(units)}: needs prepare_model(channels_last=True), dilation = 1")
+                depthwise = m.groups != 1
+                if depthwise:
+                    self._layout_depthwise(m, f"conv {len(units)}", first=not units)
                 cx, cy = records_of(m, with_input=True)
                 if not _same(cx, cur):
                     raise _Unsupported(f"conv {len(units)}: input is not the previous activation")
                 nxt = leaves[i + 1] if i + 1 < len(leaves) else None
                 bn = nxt if type(nxt) is nn.BatchNorm2d else None
                 u = _Unit(f"conv{len(units)}", m, bn)
+                u.depthwise = depthwise
                 y, u.relu = cy, False
                 if bn is not None:
                     y, u.relu = self._layout_bn(u, bn, cy)
@@ -179,6 +192,29 @@ class PlainStackEngine(_ConvEngine):
         self.dead_units = mark_dead_prefix(units)
         if self.dead_units:
             units[self.dead_units].no_dgrad = True
+
+    def _layout_depthwise(self, m, name, first):
+        """What a grouped ``Conv2d`` must be to become a depthwise unit (the kernels of hf_dwconv.hip): one filter per
+        channel, zero padding, channel quads, at most 49 taps, behind a unit that fills its ``[t_x | x]`` operand; GGN
+        products of one process."""
+        c, (r, s) = m.in_channels, m.kernel_size
+        if m.groups != c or m.out_channels != c:
+            raise _Unsupported(f"{name}: groups = {m.groups} with {c} -> {m.out_channels} channels: only depthwise "
+                               "convolutions (groups = in_channels = out_channels) are covered, no depth multiplier")
+        if m.padding_mode != "zeros" or isinstance(m.padding, str):
+            raise _Unsupported(f"{name}: a depthwise convolution needs numeric zero padding")
+        if os.environ.get("HF_DW_ENGINE", "0") != "1":
+            raise _Unsupported(f"{name}: depthwise units are opt-in (HF_DW_ENGINE=1)")
+        if first:
+            raise _Unsupported(f"{name}: a depthwise first layer is not covered (its input has no [t_x | x] operand)")
+        if c % 4:
+            raise _Unsupported(f"{name}: depthwise over {c} channels (the kernels take multiples of 4)")
+        if r * s > 49:
+            raise _Unsupported(f"{name}: depthwise with {r * s} taps (the kernels take up to 49)")
+        if self.hessian:
+            raise _Unsupported(f"{name}: Hessian products through a depthwise convolution are not covered")
+        if self.group is not None:
+            raise _Unsupported(f"{name}: data parallelism is not covered for a depthwise convolution")
 
     def _layout_bn(self, u, bn, cy):
         """The BatchNorm behind ``u``'s convolution (output record ``cy``): what the unit's output record and ReLU flag
@@ -409,6 +445,14 @@ class PlainStackEngine(_ConvEngine):
             if u.im2col:  # no input tangent: conv(x, v_W) as a 1x1 product over the im2col
                 if not (carried and u is first):
                     self._conv_slabs(0, u.tbuf, u.cols, self._weight_tangent(v, u), u.geo, u.sT)
+            elif u.depthwise:
+                # t_x and x: the halves of the producer's operand; V: the vector's slice in place (frozen: no x * V term;
+                # behind frozen layers only: no t_x * W term)
+                c, vw = u.geo.c, self._param_slice(v, u.pw, u.conv.weight.numel())
+                t_x = None if (u.no_dgrad and vw is not None) else u.xcat[:, :c]
+                self._dwconv(u, u.xcat[:, c:], 2 * c, out=u.tbuf, t_x=t_x, v=vw)
+                if u.train:
+                    u.tsum = False  # (the sums over the tangent's rows: a reduction launch of their own)
             elif u.train:  # (the epilogue writes the tangent's per-channel partial sums where it takes the geometry)
                 self._tangent_convs([u])
             else:
@@ -490,6 +534,8 @@ class PlainStackEngine(_ConvEngine):
         sig = super().layer_signature()
         if self._dropouts:  # (skipped as inert: one that becomes active is another network)
             sig = sig + (tuple(bool(m.training and m.p > 0) for m in self._dropouts),)
+        if any(u.depthwise for u in self.units):  # (read in place: a frozen one's address is a kernel argument)
+            sig = sig + (tuple(u.conv.weight.data_ptr() for u in self.units if u.depthwise),)
         if not self.classifier:
             return sig
         return sig + (tuple((id(u.lin), u.act) for u in self.classifier), tuple(t.data_ptr() for t in self._sig_tail))

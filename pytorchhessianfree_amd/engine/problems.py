@@ -146,6 +146,30 @@ def conv_bnsum(x, mean, rstd, part_x, part_1):
     return problem(_lib.ConvBnSum, x=x, mean=mean, rstd=rstd, part_x=part_x, part_1=part_1, part_rows=part_1.shape[0])
 
 
+# ---- depthwise convolutions (positional entry points, no struct): tangent / forward, and data + weight gradient --------
+DwConvProblem = namedtuple("DwConvProblem", "geo x act_ld w out t_x v ga dx slabs splits")
+
+
+def dwconv_problem(geo, x, act_ld, w, out=None, t_x=None, v=None, ga=None, dx=None, slabs=None, splits=0):
+    """A depthwise layer ``geo`` (``k == c``) on the input ``x`` at pixel pitch ``act_ld`` and the weight ``w`` [c, 1, r, s]
+    read in place.  With ``out``: ``out = conv(t_x, w) + conv(x, v)`` -- ``t_x`` (same pitch) or ``v`` (the CG vector's slice)
+    may be None, not both; the forward pass is ``v = w`` alone.  With ``ga``: the data gradient -> ``dx`` (None: not needed)
+    and the weight gradient -> ``slabs`` [splits, c*r*s] of that cotangent, one launch."""
+    if geo.k != geo.c or (out is None) == (ga is None):
+        raise RuntimeError("dwconv_problem: a depthwise geometry, and either an output or a cotangent")
+    return DwConvProblem(geo, x, act_ld, w, out, t_x, v, ga, dx, slabs, int(splits))
+
+
+def dwconv_args(q):
+    """The entry point's name, then its arguments: ``hf_dwconv2d_nhwc_tangent`` or ``hf_dwconv2d_nhwc_backward_slabs``."""
+    dims = q.geo.dims()[:4] + q.geo.dims()[5:]  # (no k)
+    if q.ga is None:
+        return ("hf_dwconv2d_nhwc_tangent", q.out, q.t_x, q.x if q.v is not None else None, q.act_ld,
+                q.w if q.t_x is not None else None, q.v, *dims)
+    return ("hf_dwconv2d_nhwc_backward_slabs", q.dx, q.slabs, q.ga, q.x, q.act_ld, q.w if q.dx is not None else None,
+            *dims, q.splits, q.slabs.shape[1])
+
+
 # ---- the squared-sum launches of the batched diagonal empirical Fisher (positional entry points, no struct) ------------
 def conv_sqsum_args(out, act, mat, geo, splits, pre, act_ld=0, out_c=0):
     """``hf_conv2d_nhwc_sqsum_slabs``: ``out`` [splits, numel] receives split s's partial sum over its samples of the

@@ -924,7 +924,10 @@ def _conv_forward(self, x):
         and not isinstance(self.padding, str)
     )
     if not usable:
-        return self._hf_stock_forward(x)
+        # (grouped / depthwise layers run the stock forward; the plain-stack engine's layout still needs the record)
+        y = self._hf_stock_forward(x)
+        self._hf_io = (x.detach(), y.detach())
+        return y
     y = _Conv.apply(x, self.weight, self.bias, list(self.stride), list(self.padding),
                     list(self.dilation), bool(getattr(self, "_hf_channels_last", False)),
                     getattr(self, "_hf_conv_mode", None))

@@ -265,6 +265,30 @@ class ConvBNFCSmall(nn.Module):
         return _batched(self.net, x)
 
 
+class DWSepSmall(nn.Module):
+    """The smallest depthwise-separable plain stack: conv3(3->8, pad 1) ReLU (the im2col'd first layer), dw3x3(8, pad 1)
+    ReLU + conv1(8->16) ReLU, dw3x3(16, stride 2, pad 1) without a ReLU + conv1(16->12) ReLU, conv1(12->classes), global
+    average pool.  ``bn``: the two depthwise units and their pointwise partners are ``Conv(bias=False) BatchNorm2d [ReLU]``.
+    12 classes, not 10: the last unit is a dense convolution, and the engine's dense units take channel quads."""
+
+    def __init__(self, num_classes=12, bn=False):
+        super().__init__()
+
+        def unit(conv, relu=True):
+            return ([conv, nn.BatchNorm2d(conv.out_channels)] if bn else [conv]) + ([nn.ReLU()] if relu else [])
+
+        self.net = nn.Sequential(
+            nn.Conv2d(3, 8, 3, 1, 1), nn.ReLU(),
+            *unit(nn.Conv2d(8, 8, 3, 1, 1, groups=8, bias=not bn)), *unit(nn.Conv2d(8, 16, 1, bias=not bn)),
+            *unit(nn.Conv2d(16, 16, 3, 2, 1, groups=16, bias=not bn), relu=False), *unit(nn.Conv2d(16, 12, 1, bias=not bn)),
+            nn.Conv2d(12, num_classes, 1),
+            nn.AdaptiveAvgPool2d((1, 1)),
+        )
+
+    def forward(self, x):  # (BatchNorm2d takes no unbatched sample)
+        return torch.flatten(_batched(self.net, x), -3)
+
+
 class VGG11BN(nn.Module):
     """VGG-11 with BatchNorm for 32x32 inputs (the usual CIFAR form): conv3 + BN + ReLU units of 64, 128, 256, 256, 512,
     512, 512, 512 channels, a MaxPool(2, 2) behind units 1, 2, 4, 6 and 8 (32 -> 1), ``Flatten``, ``Linear(512->classes)``.
@@ -460,6 +484,16 @@ def convbn_small(batch_size=2, seed=0, device="cpu", data_seed=None):
     g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
     inputs = torch.rand(batch_size, 3, 12, 12, generator=g)
     targets = torch.randint(0, 4, (batch_size,), generator=g)
+    return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
+
+
+def dwsep_small(batch_size=3, seed=0, device="cpu", data_seed=None, bn=False):
+    """``DWSepSmall`` in eval mode (``bn``: with seeded BatchNorm state); inputs U[0,1) [B,3,9,7], 12 classes, CE-mean."""
+    torch.manual_seed(seed)
+    model = seed_batchnorm(DWSepSmall(12, bn), seed).eval()
+    g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
+    inputs = torch.rand(batch_size, 3, 9, 7, generator=g)
+    targets = torch.randint(0, 12, (batch_size,), generator=g)
     return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
 
 
