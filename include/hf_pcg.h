@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 27
+#define HF_ABI_VERSION 28
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -1087,6 +1087,35 @@ int hf_dense_loss_head(int kind, const void* logits, const void* targets, void* 
  *       (ascending), a __shfl_down tree over the wave's pixel slots (offsets 32, 16, .. channel-block quads), the four
  *       waves in wave order, then added to the run's sum (units ascending).  x at pixel pitch act_ld, ga dense.
  *       splits_w must be hf_dwconv2d_nhwc_plan's count for the geometry (HF_ERR_ARG otherwise).
+ *   hf_dwconv2d_nhwc_backward2_slabs (ABI 28): the TANGENT of that backward sweep -- a Hessian product's second-order
+ *       backward through the layer -- in ONE launch, with one slab per direction as the one-term launch:
+ *         dx       = D(ga_t, W) + D(ga, V)        gw_slabs = W(x, ga_t) + W(t_x, ga)
+ *       (D / W: the data / weight gradient above.)  ga_t = g', the cotangent's tangent, and ga = g, the step's first-order
+ *       cotangent: dense [n, oh, ow, c].  x and t_x: two pointers with ONE pixel pitch act_ld (0 = c), the halves of the
+ *       producer's [t_x | x] operand.  W: the parameter, V: the CG vector's slice, both read in place.  Same work split and
+ *       staging as the one-term launch, with two tap tables / two cotangent tiles (data gradient) and two halo / two
+ *       cotangent tiles (weight gradient) in LDS, so the form has a plan of its own: hf_dwconv2d_nhwc_plan2 returns ITS
+ *       slab count (the same rule on its own channel blocks: 3x3 and 5x5 stride 1 keep 32 channels per workgroup at
+ *       48 000 / 61 312 bytes of LDS, 7x7 stride 1 takes 16 at 38 976), or HF_ERR_ARG where the form does not fit 64 KB
+ *       at 4 channels.  Rounding: dx one fmaf chain from zero over the exact taps in ascending (i, j), within a tap first
+ *       ga_t * W, then ga * V; gw per pixel first ga_t * x, then ga * t_x in the lane's one chain, then the one-term
+ *       launch's wave tree, wave order and unit order.  No atomics; two launches give the same bits.  Refused with
+ *       HF_ERR_ARG before any launch: a NULL among the eight operands, splits_w other than hf_dwconv2d_nhwc_plan2's count,
+ *       slab_stride < c*r*s with more than one slab, act_ld < c, and what the common contract refuses.  A vanishing term
+ *       (frozen weight, tangent-free input) is the one-term launch's case, not this one's.
+ *   hf_dwconv2d_nhwc_sqsum_slabs (ABI 28): the sum over the samples of the SQUARED per-sample weight gradient, the
+ *       depthwise sibling of hf_conv2d_nhwc_sqsum_slabs with its conventions:
+ *         out[ch][i][j] = sum_{m<n} ( pre * sum_{p in sample m} ga[m,p,ch] * x[m, pix(p,i,j), ch] )^2
+ *       in PARAMETER order [c][r*s].  The SPLITS RUN OVER THE SAMPLES: split t takes samples [t*ceil(n/splits), ...) and
+ *       writes its partial sum to out + t*slab_stride for hf_pack_ex (mode 0) to add in split order.  A workgroup owns
+ *       (split, channel block) and runs the weight-gradient loop over a sample's output tiles (ascending, rounding as
+ *       above) into a per-sample accumulator; at the sample's end t = acc * pre (one rounding), sum += t * t (two
+ *       roundings), the samples ascending.  No per-sample gradient is formed in memory; no atomics; two launches give the
+ *       same bits; every entry of every slab is written.  hf_dwconv2d_nhwc_sqsum_plan returns the planned count: towards
+ *       target_blocks workgroups (0 = 512), at most min(n, 64), no split without a sample.  The launch takes that count or
+ *       any other that leaves no split empty (1 <= splits <= n, (splits - 1) * ceil(n/splits) < n); anything else, a
+ *       slab_stride below c*r*s with splits > 1, a NULL operand, act_ld < c or a `pre` that is not finite is HF_ERR_ARG
+ *       before any launch.  (Its channel blocks: the widest that fit LDS, halved down to 16 while n * blocks < 512.)
  */
 int hf_dwconv2d_nhwc_plan(int64_t n, int64_t h, int64_t w, int64_t c, int64_t r, int64_t s, int64_t stride_h,
                           int64_t stride_w, int64_t pad_h, int64_t pad_w);
@@ -1097,6 +1126,18 @@ int hf_dwconv2d_nhwc_backward_slabs(void* dx, void* gw_slabs, const void* ga, co
                                     int64_t n, int64_t h, int64_t w, int64_t c, int64_t r, int64_t s, int64_t stride_h,
                                     int64_t stride_w, int64_t pad_h, int64_t pad_w, int splits_w, int64_t slab_stride,
                                     int dtype, void* stream);
+int hf_dwconv2d_nhwc_plan2(int64_t n, int64_t h, int64_t w, int64_t c, int64_t r, int64_t s, int64_t stride_h,
+                           int64_t stride_w, int64_t pad_h, int64_t pad_w);
+int hf_dwconv2d_nhwc_backward2_slabs(void* dx, void* gw_slabs, const void* ga_t, const void* ga, const void* x,
+                                     const void* t_x, int64_t act_ld, const void* W, const void* V, int64_t n, int64_t h,
+                                     int64_t w, int64_t c, int64_t r, int64_t s, int64_t stride_h, int64_t stride_w,
+                                     int64_t pad_h, int64_t pad_w, int splits_w, int64_t slab_stride, int dtype,
+                                     void* stream);
+int hf_dwconv2d_nhwc_sqsum_plan(int64_t n, int64_t h, int64_t w, int64_t c, int64_t r, int64_t s, int64_t stride_h,
+                                int64_t stride_w, int64_t pad_h, int64_t pad_w, int target_blocks);
+int hf_dwconv2d_nhwc_sqsum_slabs(void* out, const void* ga, const void* x, int64_t act_ld, int64_t n, int64_t h, int64_t w,
+                                 int64_t c, int64_t r, int64_t s, int64_t stride_h, int64_t stride_w, int64_t pad_h,
+                                 int64_t pad_w, float pre, int splits, int64_t slab_stride, int dtype, void* stream);
 
 /* ---- RCCL (resolved at run time from the already-loaded librccl) ----------- */
 typedef struct hf_comm hf_comm_t;

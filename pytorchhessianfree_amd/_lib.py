@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HF_PCG_LIB") or os.path.join(_HERE, "csrc", "libhfpcg.so")
 
 HF_F32, HF_F64 = 0, 1
-ABI_VERSION = 27
+ABI_VERSION = 28
 HF_ERR_ARG = -1  # hf_status of include/hf_pcg.h: null / negative / inconsistent argument
 HF_M_NONE, HF_M_DIAG, HF_M_EXTERNAL = 0, 1, 2
 REASONS = {
@@ -225,6 +225,12 @@ SIGNATURES = {
                                  + [c_int, c_void_p]),
     "hf_dwconv2d_nhwc_backward_slabs": (c_int, [c_void_p] * 4 + [c_int64, c_void_p] + [c_int64] * 10
                                         + [c_int, c_int64, c_int, c_void_p]),
+    "hf_dwconv2d_nhwc_plan2": (c_int, [c_int64] * 10),
+    "hf_dwconv2d_nhwc_backward2_slabs": (c_int, [c_void_p] * 6 + [c_int64, c_void_p, c_void_p] + [c_int64] * 10
+                                         + [c_int, c_int64, c_int, c_void_p]),
+    "hf_dwconv2d_nhwc_sqsum_plan": (c_int, [c_int64] * 10 + [c_int]),
+    "hf_dwconv2d_nhwc_sqsum_slabs": (c_int, [c_void_p] * 3 + [c_int64] * 11 + [ctypes.c_float, c_int, c_int64, c_int,
+                                                                                c_void_p]),
     "hf_comm_unique_id": (c_int, [ctypes.c_char_p]),
     "hf_comm_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.c_char_p, c_int, c_int]),
     "hf_comm_destroy": (c_int, [c_void_p]),
@@ -655,11 +661,23 @@ def conv2d_nhwc_slabs(direction, out, act, mat, n, h, w, c, k, r, s, stride, pad
     return out
 
 
-def dwconv_plan(n, h, w, c, r, s, stride, padding):
-    """Number of weight-gradient slabs a depthwise backward launch of this geometry writes (``hf_dwconv2d_nhwc_plan``)."""
-    sp = load().hf_dwconv2d_nhwc_plan(n, h, w, c, r, s, stride[0], stride[1], padding[0], padding[1])
+def dwconv_plan(n, h, w, c, r, s, stride, padding, terms=1):
+    """Number of weight-gradient slabs a depthwise backward launch of this geometry writes (``hf_dwconv2d_nhwc_plan``;
+    ``terms=2``: the two-term launch of a Hessian product, ``hf_dwconv2d_nhwc_plan2``)."""
+    name = "hf_dwconv2d_nhwc_plan2" if terms == 2 else "hf_dwconv2d_nhwc_plan"
+    sp = getattr(load(), name)(n, h, w, c, r, s, stride[0], stride[1], padding[0], padding[1])
     if sp < 1:
-        check(sp, "hf_dwconv2d_nhwc_plan")
+        check(sp, name)
+    return sp
+
+
+def dwconv_sqsum_plan(n, h, w, c, r, s, stride, padding, target_blocks=0):
+    """Number of sample splits a depthwise squared-sum launch of this geometry is planned with
+    (``hf_dwconv2d_nhwc_sqsum_plan``)."""
+    sp = load().hf_dwconv2d_nhwc_sqsum_plan(n, h, w, c, r, s, stride[0], stride[1], padding[0], padding[1],
+                                            int(target_blocks))
+    if sp < 1:
+        check(sp, "hf_dwconv2d_nhwc_sqsum_plan")
     return sp
 
 

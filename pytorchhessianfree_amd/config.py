@@ -169,6 +169,10 @@ SWITCHES = {
                      "hf_dwconv.hip; off by default until its GGN products per second are measured against the "
                      "autograd path on a MobileNet-style stack -- without it such a net keeps that path",
                      "tests/test_dwsep_engine_gpu.py::test_eval_point_against_float64"),
+    "HF_DW_HESSIAN": ("0", "1: with HF_DW_ENGINE=1, curvature_opt='hessian' on a net with depthwise units takes the plain-"
+                      "stack engine (the second-order backward of a depthwise unit in one launch, "
+                      "hf_dwconv2d_nhwc_backward2_slabs) instead of the autograd operator; unmeasured, hence opt-in",
+                      "tests/test_dwsep_hessian_engine_gpu.py::test_hessian_products_against_float64"),
     "HF_CHUNKED_ALLREDUCE": ("auto", "0 / 1: force the single-graph resp. the two-phase data-parallel product",
                              "tests/test_distributed_gpu.py::test_step_two_ranks_engine_session_equals_cpu_whole_batch"),
     "HF_DIRECT_RCCL": ("1", "0: every collective through torch.distributed (no communicator of the package's own)",

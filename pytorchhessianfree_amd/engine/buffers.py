@@ -67,10 +67,11 @@ class _Buffers:
             raise _Unsupported(f"{name}: convolution geometry refused ({sp})" if name else f"stem geometry refused ({sp})")
         return sp
 
-    def _plan_depthwise(self, geo, name):
-        """The weight-gradient slabs a depthwise backward launch of this geometry writes (``hf_dwconv2d_nhwc_plan``)."""
+    def _plan_depthwise(self, geo, name, terms=1):
+        """The weight-gradient slabs a depthwise backward launch of this geometry writes (``hf_dwconv2d_nhwc_plan``;
+        ``terms=2``: the two-term launch of a Hessian product, ``hf_dwconv2d_nhwc_plan2``)."""
         try:
-            return _lib.dwconv_plan(geo.n, geo.h, geo.w, geo.c, geo.r, geo.s, geo.stride, geo.padding)
+            return _lib.dwconv_plan(geo.n, geo.h, geo.w, geo.c, geo.r, geo.s, geo.stride, geo.padding, terms)
         except _lib.Refused as e:
             raise _Unsupported(f"{name}: depthwise convolution geometry refused ({e})") from None
 
@@ -171,7 +172,14 @@ class _Buffers:
             # the consumers sum anyway
             u.nW = u.sW * (2 if (self.hessian and not u.first) else 1)
             u.nD = u.sD * (2 if self.hessian else 1)
-            u.wbuf = torch.zeros((u.nW, u.conv.weight.numel()), dtype=f32, device=dev)  # dead taps stay 0
+            if u.depthwise:
+                # no extras slabs: the second-order backward is ONE two-term launch (hf_dwconv2d_nhwc_backward2_slabs) that
+                # leaves one data-gradient slab and its own plan's count of weight-gradient slabs -- where a term vanishes
+                # (frozen weight, tangent-free input) the one-term launch and its count
+                u.two_term = self.hessian and u.pw is not None and bool(u.sD)
+                u.nW = self._plan_depthwise(u.geo, u.name, terms=2) if u.two_term else u.sW
+                u.nD = u.sD
+            u.wbuf = torch.zeros((max(u.nW, u.sW), u.conv.weight.numel()), dtype=f32, device=dev)  # dead taps stay 0
             if u.sD:
                 u.dbuf = torch.empty((u.nD, u.x.numel()), dtype=f32, device=dev)
             if self.hessian:
@@ -179,7 +187,7 @@ class _Buffers:
                 if u.bn is not None:
                     u.g1 = torch.empty_like(u.a)   # ... and of the BatchNorm output (masked), per step
                     u.gah = torch.empty_like(u.a)  # g_a' + g_z * rstd * v_gamma: what the convolutions' adjoints read
-                if u.sD:
+                if u.sD and not u.depthwise:  # (a depthwise unit reads V in place)
                     # V as (I, H, W, O), per product (a frozen weight has V = 0: zeros, never scattered into)
                     u.vT = torch.zeros((c, r, s, k), dtype=f32, device=dev)
             u.g = torch.empty_like(u.a) if u.needs_g else None  # masked cotangent of the unit's output

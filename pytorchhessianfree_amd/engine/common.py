@@ -65,6 +65,7 @@ class _Unit:
         self.needs_g = True       # the masked cotangent itself is read by a residual branch
         self.im2col = False       # tiny-Cin layer: runs as a 1x1 product over the im2col of the input
         self.depthwise = False    # plain stack: groups = channels, on the kernels of hf_dwconv.hip (weight read in place)
+        self.two_term = False     # ... whose second-order backward is the two-term launch (Hessian engine, both terms live)
         self.train = False        # train-mode BatchNorm: batch statistics (recorded), tangent / adjoint carry
         self.mean_t = None        # the statistics' dependence on the layer input
         self.epi = self.tsum = False  # train mode: the tangent's partial sums come from the convolution's epilogue

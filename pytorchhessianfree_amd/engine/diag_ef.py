@@ -6,7 +6,7 @@ Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overal
 import torch
 
 from .. import _lib
-from .problems import chan_sqsum_args, conv_sqsum_args
+from .problems import chan_sqsum_args, conv_sqsum_args, dwconv_sqsum_args
 
 
 class _DiagEF:
@@ -21,9 +21,9 @@ class _DiagEF:
         the reference carries it whole) enters in closed form: sum (a_i + b)^2 = sum a_i^2 + 2 b sum a_i + N b^2.
 
         ``HF_DIAG_EF_BATCHED=1`` (read when the engine is built): instead of the per-sample launches, per unit ONE
-        ``hf_conv2d_nhwc_sqsum_slabs`` on the whole-batch operands (it squares and sums the per-sample weight gradients
-        inside the launch: BackPACK's ``SumGradSquared``), ONE ``hf_chan_sqsum`` for the BatchNorm / bias entries, and
-        ONE plain gather (``hf_pack_ex`` mode 0) for all of them -- a number of launches that does not depend on the
+        ``hf_conv2d_nhwc_sqsum_slabs`` (a depthwise unit: ``hf_dwconv2d_nhwc_sqsum_slabs``) on the whole-batch operands (it
+        squares and sums the per-sample weight gradients inside the launch: BackPACK's ``SumGradSquared``), ONE
+        ``hf_chan_sqsum`` for the BatchNorm / bias entries, and ONE plain gather (``hf_pack_ex`` mode 0) for all of them -- a number of launches that does not depend on the
         batch.  The factor that undoes the loss's 1/N goes into the launches (``pre``: applied before squaring)."""
         if self.loss_spec is None or self.train_bn:
             raise RuntimeError("engine.diag_ef needs a softmax cross-entropy / MSE loss and eval-mode BatchNorm")
@@ -91,7 +91,9 @@ class _DiagEF:
             if u.dead:  # (as below: no cotangent here, nothing is gathered)
                 continue
             ga = u.ga1 if first_order else u.ga
-            if u.pw is not None:
+            if u.pw is not None and u.depthwise:  # (slabs in parameter order: no permutation in the gather)
+                self._launch("hf_dwconv2d_nhwc_sqsum_slabs", *dwconv_sqsum_args(u.wps, ga, u.x, u.geo.c, u.geo1, u.sW1, pre))
+            elif u.pw is not None:
                 act = u.cols_pad if u.im2col else u.x
                 self._launch("hf_conv2d_nhwc_sqsum_slabs",
                              *conv_sqsum_args(u.wps, act, ga, u.geo1, u.sW1, pre, out_c=u.jcols if u.im2col else 0))
@@ -124,7 +126,11 @@ class _DiagEF:
             if self._diag_batched:
                 n = u.a.shape[0]
                 u.geo1 = u.geo_w._replace(n=n, h=u.a.shape[2], w=u.a.shape[3]) if u.im2col else u.geo
-                u.sW1 = _lib.conv_sqsum_plan(*u.geo1)
+                if u.depthwise:  # (its own squared-sum kernel and plan: hf_dwconv.hip)
+                    g = u.geo1
+                    u.sW1 = _lib.dwconv_sqsum_plan(g.n, g.h, g.w, g.c, g.r, g.s, g.stride, g.padding)
+                else:
+                    u.sW1 = _lib.conv_sqsum_plan(*u.geo1)
                 # shares of the samples for the channel sums: ~one workgroup per CU (64 channels each), none empty
                 u.rb1 = max(1, min(n, 256 // -(-k // 64)))
                 while -(-n // u.rb1) * (u.rb1 - 1) >= n:

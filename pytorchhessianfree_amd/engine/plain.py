@@ -58,7 +58,12 @@ class PlainStackEngine(_ConvEngine):
     The kernels of hf_dwconv.hip read the weight ``[c, 1, r, s]`` and the vector's slice V in place (no ``[W | v_W]``
     operand, no transposed copy, no tangent slot) and leave ONE slab per direction: ``hf_dwconv2d_nhwc_tangent`` on the
     halves of the producer's ``[t_x | x]`` operand, ``hf_dwconv2d_nhwc_backward_slabs`` for the data gradient and the weight
-    gradient's slabs (parameter order: no permutation in the gather).  GGN products, one process."""
+    gradient's slabs (parameter order: no permutation in the gather).  One process.  Hessian products on top
+    (``HF_DW_HESSIAN=1``; bias, eval- and train-mode BatchNorm units): the second-order backward of such a unit is ONE
+    launch, ``hf_dwconv2d_nhwc_backward2_slabs`` -- ``dx = D(g', W) + D(g, V)``, ``slabs = W(x, g') + W(t_x, g)`` -- so it has
+    no extras slabs (``nD = sD``, ``nW`` from the two-term plan); a frozen weight or a tangent-free input keeps the one-term
+    launch.  With ``HF_DIAG_EF_BATCHED=1`` its weight entries of ``diag_ef`` come from ONE ``hf_dwconv2d_nhwc_sqsum_slabs``
+    launch on the whole batch.  All of it opt-in: none of these routes' speed is measured."""
 
     mode = ("fused curvature engine (plain conv-ReLU stack): own deterministic convolutions (split-K slabs summed "
             "by the consumer kernel), bias / ReLU / max-pool fused, 4 launches per layer")
@@ -195,8 +200,8 @@ class PlainStackEngine(_ConvEngine):
 
     def _layout_depthwise(self, m, name, first):
         """What a grouped ``Conv2d`` must be to become a depthwise unit (the kernels of hf_dwconv.hip): one filter per
-        channel, zero padding, channel quads, at most 49 taps, behind a unit that fills its ``[t_x | x]`` operand; GGN
-        products of one process."""
+        channel, zero padding, channel quads, at most 49 taps, behind a unit that fills its ``[t_x | x]`` operand; one
+        process; Hessian products only with ``HF_DW_HESSIAN=1``."""
         c, (r, s) = m.in_channels, m.kernel_size
         if m.groups != c or m.out_channels != c:
             raise _Unsupported(f"{name}: groups = {m.groups} with {c} -> {m.out_channels} channels: only depthwise "
@@ -211,8 +216,9 @@ class PlainStackEngine(_ConvEngine):
             raise _Unsupported(f"{name}: depthwise over {c} channels (the kernels take multiples of 4)")
         if r * s > 49:
             raise _Unsupported(f"{name}: depthwise with {r * s} taps (the kernels take up to 49)")
-        if self.hessian:
-            raise _Unsupported(f"{name}: Hessian products through a depthwise convolution are not covered")
+        if self.hessian and os.environ.get("HF_DW_HESSIAN", "0") != "1":
+            raise _Unsupported(f"{name}: Hessian products through a depthwise convolution are not covered (opt-in on top "
+                               "of HF_DW_ENGINE=1: HF_DW_HESSIAN=1)")
         if self.group is not None:
             raise _Unsupported(f"{name}: data parallelism is not covered for a depthwise convolution")
 

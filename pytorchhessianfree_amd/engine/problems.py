@@ -146,28 +146,48 @@ def conv_bnsum(x, mean, rstd, part_x, part_1):
     return problem(_lib.ConvBnSum, x=x, mean=mean, rstd=rstd, part_x=part_x, part_1=part_1, part_rows=part_1.shape[0])
 
 
-# ---- depthwise convolutions (positional entry points, no struct): tangent / forward, and data + weight gradient --------
-DwConvProblem = namedtuple("DwConvProblem", "geo x act_ld w out t_x v ga dx slabs splits")
+# ---- depthwise convolutions (positional entry points, no struct): tangent / forward, data + weight gradient, and the
+# two-term form of the latter (a Hessian product's second-order backward) ----------------------------------------------
+DwConvProblem = namedtuple("DwConvProblem", "geo x act_ld w out t_x v ga ga1 dx slabs splits")
 
 
-def dwconv_problem(geo, x, act_ld, w, out=None, t_x=None, v=None, ga=None, dx=None, slabs=None, splits=0):
+def dwconv_problem(geo, x, act_ld, w, out=None, t_x=None, v=None, ga=None, ga1=None, dx=None, slabs=None, splits=0):
     """A depthwise layer ``geo`` (``k == c``) on the input ``x`` at pixel pitch ``act_ld`` and the weight ``w`` [c, 1, r, s]
     read in place.  With ``out``: ``out = conv(t_x, w) + conv(x, v)`` -- ``t_x`` (same pitch) or ``v`` (the CG vector's slice)
     may be None, not both; the forward pass is ``v = w`` alone.  With ``ga``: the data gradient -> ``dx`` (None: not needed)
-    and the weight gradient -> ``slabs`` [splits, c*r*s] of that cotangent, one launch."""
+    and the weight gradient -> ``slabs`` [splits, c*r*s] of that cotangent, one launch.  With ``ga`` AND ``ga1`` (the step's
+    first-order cotangent; ``ga`` is then its tangent): ``dx = D(ga, w) + D(ga1, v)``, ``slabs = W(x, ga) + W(t_x, ga1)``,
+    one launch -- ``t_x``, ``v`` and ``dx`` are all needed, ``splits`` is the two-term plan's count."""
     if geo.k != geo.c or (out is None) == (ga is None):
         raise RuntimeError("dwconv_problem: a depthwise geometry, and either an output or a cotangent")
-    return DwConvProblem(geo, x, act_ld, w, out, t_x, v, ga, dx, slabs, int(splits))
+    if ga1 is not None and (ga is None or t_x is None or v is None or dx is None):
+        raise RuntimeError("dwconv_problem: the two-term backward needs both cotangents, t_x, v and dx")
+    return DwConvProblem(geo, x, act_ld, w, out, t_x, v, ga, ga1, dx, slabs, int(splits))
+
+
+def _dw_dims(geo):
+    return geo.dims()[:4] + geo.dims()[5:]  # (no k)
 
 
 def dwconv_args(q):
-    """The entry point's name, then its arguments: ``hf_dwconv2d_nhwc_tangent`` or ``hf_dwconv2d_nhwc_backward_slabs``."""
-    dims = q.geo.dims()[:4] + q.geo.dims()[5:]  # (no k)
+    """The entry point's name, then its arguments: ``hf_dwconv2d_nhwc_tangent``, ``hf_dwconv2d_nhwc_backward_slabs`` or
+    ``hf_dwconv2d_nhwc_backward2_slabs``."""
+    dims = _dw_dims(q.geo)
     if q.ga is None:
         return ("hf_dwconv2d_nhwc_tangent", q.out, q.t_x, q.x if q.v is not None else None, q.act_ld,
                 q.w if q.t_x is not None else None, q.v, *dims)
+    if q.ga1 is not None:
+        return ("hf_dwconv2d_nhwc_backward2_slabs", q.dx, q.slabs, q.ga, q.ga1, q.x, q.t_x, q.act_ld, q.w, q.v, *dims,
+                q.splits, q.slabs.shape[1])
     return ("hf_dwconv2d_nhwc_backward_slabs", q.dx, q.slabs, q.ga, q.x, q.act_ld, q.w if q.dx is not None else None,
             *dims, q.splits, q.slabs.shape[1])
+
+
+def dwconv_sqsum_args(out, ga, x, act_ld, geo, splits, pre):
+    """``hf_dwconv2d_nhwc_sqsum_slabs``: ``out`` [splits, c*r*s] receives split s's partial sum over its samples of the
+    squared per-sample weight gradient of the depthwise layer ``geo`` (``x`` at pixel pitch ``act_ld``, cotangent ``ga``),
+    each scaled by ``pre`` before it is squared; parameter order."""
+    return (out, ga, x, act_ld, *_dw_dims(geo), float(pre), int(splits), out.shape[1])
 
 
 # ---- the squared-sum launches of the batched diagonal empirical Fisher (positional entry points, no struct) ------------
