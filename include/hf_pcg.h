@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 28
+#define HF_ABI_VERSION 29
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -1138,6 +1138,55 @@ int hf_dwconv2d_nhwc_sqsum_plan(int64_t n, int64_t h, int64_t w, int64_t c, int6
 int hf_dwconv2d_nhwc_sqsum_slabs(void* out, const void* ga, const void* x, int64_t act_ld, int64_t n, int64_t h, int64_t w,
                                  int64_t c, int64_t r, int64_t s, int64_t stride_h, int64_t stride_w, int64_t pad_h,
                                  int64_t pad_w, float pre, int splits, int64_t slab_stride, int dtype, void* stream);
+
+/* ---- grouped convolutions inside the GGN product (hf_gconv.hip, ABI 29) ---------------- */
+/*
+ * The sweeps through a grouped nn.Conv2d (c_in -> c_out in `groups` groups, weight [c_out, cg_in, r, s] with cg_in =
+ * c_in / groups input and cg_out = c_out / groups output channels per group) of a plain stack (engine/plain.py), on
+ * kernels of their own around v_mfma_f32_4x4x1_16b_f32: one issue is 4 pixels x 64 consecutive channels, each of its 16
+ * blocks a channel quad that reads its own group (hf_gconv.hip's header has the work split, the LDS and register
+ * arithmetic).  The operand conventions are the depthwise family's: the weight W and the CG vector's slice V (same shape)
+ * are read IN PLACE, activations come at a pixel pitch act_ld (0 = c_in; the halves of the producer's [t_x | x] operand,
+ * 2*c_in, or a dense map), each direction leaves ONE dense slab, the weight-gradient slabs are in PARAMETER order.
+ * Common contract: HF_F32 only, NHWC, c_in == groups * cg_in and c_out == groups * cg_out with both widths multiples of 4
+ * and <= 64, 1 <= r*s <= 49 taps, stride 1 .. 8 and padding 0 .. kernel extent - 1 per axis, dilation 1, the padded map at
+ * least one kernel large, n*h*w*2*c_in and n*oh*ow*c_out < 2^31, c_in <= act_ld <= 2*c_in, a staging tile that fits 64 KB of
+ * LDS at 4 channels per group and 2 tile rows.  Operands need only 4-byte alignment (the 16-byte loads are chosen on the
+ * host where base pointers and pitches allow them).  No atomics; two launches on the same operands give the same bits;
+ * nothing outside the operands' extents is read or written.  Anything else is refused with HF_ERR_ARG before any launch;
+ * one host function is the definition of what is accepted, and every entry point below runs it.
+ *   hf_gconv2d_nhwc_plan: the number of weight-gradient slabs (splits_w >= 1) a backward launch of this geometry writes,
+ *       or HF_ERR_ARG.  The (sample, th x 8 output tile) units in ascending order are cut into splits_w consecutive runs
+ *       of ceil(units / want) units, want = min(units, 64, ceil(512 / (spans of 64 output channels * passes))); the last
+ *       run may be shorter, none is empty.
+ *   hf_gconv2d_nhwc_tangent:
+ *       out[n,oh,ow,co] = sum_{ci<cg_in,i,j} t_x[n, oh*stride_h - pad_h + i, ow*stride_w - pad_w + j, g*cg_in + ci] * W[co,ci,i,j]
+ *                                          + x[same pixel and channel] * V[co,ci,i,j]          (g = co / cg_out)
+ *       (a pixel outside the map counts as zero).  Either term may be absent, not both: t_x == NULL (a tangent-free
+ *       input; W is not read) or V == NULL (a frozen weight; x is not read).  The forward pass is t_x = NULL, V = W.  One
+ *       chain of single products from zero: all of t_x * W, then all of x * V; per term ci ascending, per ci the taps in
+ *       ascending (i, j).  out: ONE dense slab [n, oh, ow, c_out].
+ *   hf_gconv2d_nhwc_backward_slabs: data and weight gradient of the cotangent ga [n, oh, ow, c_out] (dense) in ONE launch.
+ *       dx[n,h,w,g*cg_in+ci] = sum_{co<cg_out,i,j} ga[n, (h + pad_h - i) / stride_h, (w + pad_w - j) / stride_w, g*cg_out + co]
+ *       * W[g*cg_out+co,ci,i,j] over the taps whose divisions are exact and in range: one chain from zero, co ascending,
+ *       per co the taps in ascending (i, j); ONE dense slab [n, h, w, c_in].  dx == NULL (the first live unit): not
+ *       computed, W is not read.
+ *       gw_slabs[s][co,ci,i,j] = sum over run s's units of ga[n,oh,ow,co] * x[n, oh*stride_h - pad_h + i, .., g*cg_in + ci]
+ *       -- splits_w slabs of [c_out*cg_in*r*s] in PARAMETER order, slab_stride elements apart (>= that size where
+ *       splits_w > 1), for hf_pack_ex to add in split order (no permutation).  One chain per entry: the run's units
+ *       ascending, a unit's pixels in row-major order.  x at pixel pitch act_ld.  splits_w must be hf_gconv2d_nhwc_plan's
+ *       count for the geometry (HF_ERR_ARG otherwise).
+ */
+int hf_gconv2d_nhwc_plan(int64_t n, int64_t h, int64_t w, int64_t c_in, int64_t c_out, int64_t groups, int64_t r, int64_t s,
+                         int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w);
+int hf_gconv2d_nhwc_tangent(void* out, const void* t_x, const void* x, int64_t act_ld, const void* W, const void* V,
+                            int64_t n, int64_t h, int64_t w, int64_t c_in, int64_t c_out, int64_t groups, int64_t r,
+                            int64_t s, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int dtype,
+                            void* stream);
+int hf_gconv2d_nhwc_backward_slabs(void* dx, void* gw_slabs, const void* ga, const void* x, int64_t act_ld, const void* W,
+                                   int64_t n, int64_t h, int64_t w, int64_t c_in, int64_t c_out, int64_t groups, int64_t r,
+                                   int64_t s, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
+                                   int splits_w, int64_t slab_stride, int dtype, void* stream);
 
 /* ---- RCCL (resolved at run time from the already-loaded librccl) ----------- */
 typedef struct hf_comm hf_comm_t;

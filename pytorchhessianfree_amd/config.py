@@ -173,6 +173,11 @@ SWITCHES = {
                       "stack engine (the second-order backward of a depthwise unit in one launch, "
                       "hf_dwconv2d_nhwc_backward2_slabs) instead of the autograd operator; unmeasured, hence opt-in",
                       "tests/test_dwsep_hessian_engine_gpu.py::test_hessian_products_against_float64"),
+    "HF_GROUP_ENGINE": ("0", "1: the plain-stack engine takes grouped Conv2d units (group widths that are multiples of 4 up "
+                        "to 64; ResNeXt / RegNet / ShuffleNet-style layers) on the block-MFMA kernels of hf_gconv.hip; off "
+                        "by default: its GGN products per second are not measured against the autograd path -- without it "
+                        "such a net keeps that path",
+                        "tests/test_group_engine_gpu.py::test_eval_point_against_float64"),
     "HF_CHUNKED_ALLREDUCE": ("auto", "0 / 1: force the single-graph resp. the two-phase data-parallel product",
                              "tests/test_distributed_gpu.py::test_step_two_ranks_engine_session_equals_cpu_whole_batch"),
     "HF_DIRECT_RCCL": ("1", "0: every collective through torch.distributed (no communicator of the package's own)",

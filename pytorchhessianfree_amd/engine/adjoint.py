@@ -134,8 +134,8 @@ class _AdjointSweep:
         if u.im2col:
             self._conv_slabs(2, u.wbuf, u.cols_pad, ga, u.geo_w, u.sW, out_c=u.jcols)
             return
-        if u.depthwise:  # (data + weight gradient in one launch; no data gradient behind a tangent-free input)
-            self._dwconv(u, u.x, u.geo.c, ga=ga, dx=u.dbuf if u.sD else None, slabs=u.wbuf, splits=u.sW)
+        if u.in_place:  # (data + weight gradient in one launch; no data gradient behind a tangent-free input)
+            self._in_place_conv(u, u.x, u.geo.c, ga=ga, dx=u.dbuf if u.sD else None, slabs=u.wbuf, splits=u.sW)
             return
         if u.first or u.no_dgrad:  # the network input (or the output of frozen layers) needs no gradient
             self._launch("hf_conv2d_nhwc_slabs", *conv_args(*self._dw_problems(u, ga, dgrad=False)))
@@ -198,7 +198,7 @@ class _AdjointSweep:
                                 splits[pi] = (rows, u.cout)
                     continue
                 tensors[u.pw] = u.wbuf[0]
-                if not u.im2col and not u.depthwise:  # (a depthwise unit's slabs are in the parameter's own order)
+                if not u.im2col and not u.in_place:  # (a depthwise / grouped unit's slabs are in the parameter's own order)
                     k, c, r, s_ = u.conv.weight.shape
                     if r * s_ > 1:
                         perms[u.pw] = (c, r * s_)  # stored (O, H, W, I); 1x1 kernels: already in order

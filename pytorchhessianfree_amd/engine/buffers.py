@@ -9,7 +9,8 @@ import torch
 
 from .. import _lib
 from .common import _Unsupported, _flat_view, _live_taps
-from .problems import Geometry, bn_adjoint_args, chan_sums_problem, conv_args, conv_problem, dwconv_args, dwconv_problem
+from .problems import (Geometry, bn_adjoint_args, chan_sums_problem, conv_args, conv_problem, dwconv_args, dwconv_problem,
+                       gconv_args, gconv_dims, gconv_problem)
 
 
 def adjoint_split_ok(train, rb, hessian, map_bytes, max_bytes, enabled=True):
@@ -75,6 +76,17 @@ class _Buffers:
         except _lib.Refused as e:
             raise _Unsupported(f"{name}: depthwise convolution geometry refused ({e})") from None
 
+    def _plan_in_place(self, u, geo):
+        """The weight-gradient slabs the backward launch of the depthwise or grouped unit ``u`` writes on ``geo``: the
+        count of its kernel family's own plan (``hf_dwconv2d_nhwc_plan`` / ``hf_gconv2d_nhwc_plan``)."""
+        if u.depthwise:
+            return self._plan_depthwise(geo, u.name)
+        try:
+            d = gconv_dims(geo, u.conv.groups)
+            return _lib.gconv_plan(*d[:8], d[8:10], d[10:])
+        except _lib.Refused as e:
+            raise _Unsupported(f"{u.name}: grouped convolution geometry refused ({e})") from None
+
     def _allocate(self):
         """Every buffer the sweeps touch is owned by the engine and STATIC: the activations are
         recomputed in place by ``forward_own`` (own kernels), so one engine -- and the hipGraphs
@@ -127,8 +139,8 @@ class _Buffers:
                 u.jcols = j
                 if not u.conv.weight.is_contiguous():
                     raise _Unsupported(f"{u.name}: weight layout")
-            elif u.depthwise:
-                # the weight [c, 1, r, s] and its tangent (the CG vector's slice) are read in place: no [W | v_W] operand,
+            elif u.in_place:
+                # the weight [k, c / groups, r, s] and its tangent (the CG vector's slice) are read in place: no [W | v_W] operand,
                 # no (I, H, W, O) copy, no tangent slot; the input operand is the shared [t_x | x] buffer
                 u.geo = Geometry(n, h, w, c, k, r, s, tuple(u.conv.stride), tuple(u.conv.padding))
                 key = id(u.x)
@@ -158,9 +170,9 @@ class _Buffers:
                 u.sT = u.sF = self._plan(0, u.geo)
                 u.sW = self._plan(2, u.geo_w)
                 u.sD = 0
-            elif u.depthwise:  # (one slab per direction; the weight gradient's count from the kernels' own plan)
+            elif u.in_place:  # (one slab per direction; the weight gradient's count from the kernels' own plan)
                 u.sT = u.sF = 1
-                u.sW = self._plan_depthwise(u.geo, u.name)
+                u.sW = self._plan_in_place(u, u.geo)
                 u.sD = 0 if (u.no_dgrad or u.dead) else 1
             else:
                 u.sT, u.sW = self._plan(0, u.geo.doubled(), u.name), self._plan(2, u.geo, u.name)
@@ -187,7 +199,7 @@ class _Buffers:
                 if u.bn is not None:
                     u.g1 = torch.empty_like(u.a)   # ... and of the BatchNorm output (masked), per step
                     u.gah = torch.empty_like(u.a)  # g_a' + g_z * rstd * v_gamma: what the convolutions' adjoints read
-                if u.sD and not u.depthwise:  # (a depthwise unit reads V in place)
+                if u.sD and not u.in_place:  # (a depthwise unit reads V in place)
                     # V as (I, H, W, O), per product (a frozen weight has V = 0: zeros, never scattered into)
                     u.vT = torch.zeros((c, r, s, k), dtype=f32, device=dev)
             u.g = torch.empty_like(u.a) if u.needs_g else None  # masked cotangent of the unit's output
@@ -233,7 +245,7 @@ class _Buffers:
                 # (row tile, split): beyond 256 rows the separate reduction's `rb` rows are cheaper
                 # for the elementwise pass to add up)
                 tp_rows = -(-u.rows // 64) * u.sT
-                u.epi = (not u.im2col and not u.first and not u.depthwise and hasattr(u, "xcat")
+                u.epi = (not u.im2col and not u.first and not u.in_place and hasattr(u, "xcat")
                          and tp_rows <= 256
                          and os.environ.get("HF_BN_EPILOGUE", "1") != "0")
                 if self.hessian:
@@ -277,13 +289,13 @@ class _Buffers:
         self._carry_ok = True  # (the stem's launch carries the v_W scatter; False once the library refused it)
         # (I, H, W, O) copies: the weights (once per step) and, for Hessian products, V (per product)
         self._wt_slots = [(self._offs[u.pw], u.wT, u.x.shape[1]) for u in self.units
-                          if not u.im2col and not u.depthwise and not u.first and u.pw is not None and u.sD]
+                          if not u.im2col and not u.in_place and not u.first and u.pw is not None and u.sD]
         # frozen convolution weights: constants the flat parameter vector does not hold -- their W half / (I, H, W, O)
         # copy come from the parameter itself (`refresh_frozen`: at construction and whenever it was written to)
-        self._frozen_w = [u for u in self.units if not u.im2col and not u.depthwise and u.pw is None]
+        self._frozen_w = [u for u in self.units if not u.im2col and not u.in_place and u.pw is None]
         self._frozen_seen = {}
         self._vt_slots = [(self._offs[u.pw], u.vT, u.x.shape[1]) for u in self.units
-                          if self.hessian and not u.im2col and not u.depthwise and u.sD and u.pw is not None]
+                          if self.hessian and not u.im2col and not u.in_place and u.sD and u.pw is not None]
         self._allocate_head()
         # the parameters as ONE flat vector, when they are consecutive views of one (the optimizer's
         # arena): every W half is then refreshed by a single scatter launch
@@ -426,7 +438,7 @@ class _Buffers:
             _lib.unpack_tangent(flat, self._slot_list, half=0)
         else:
             for u in self.units:
-                if not u.im2col and not u.depthwise and u.pw is not None:
+                if not u.im2col and not u.in_place and u.pw is not None:
                     c = u.x.shape[1]
                     u.wcat[:, :c].copy_(self.params[u.pw].detach())
         if transposed:
@@ -434,7 +446,7 @@ class _Buffers:
                 _lib.unpack_tangent(flat, self._wt_slots, half=2)
             else:
                 for u in self.units:
-                    if not u.im2col and not u.depthwise and not u.first and u.pw is not None and u.sD:
+                    if not u.im2col and not u.in_place and not u.first and u.pw is not None and u.sD:
                         u.wT.copy_(self.params[u.pw].detach().permute(1, 2, 3, 0))
 
     def _zeros(self, k):
@@ -466,6 +478,15 @@ class _Buffers:
         """One launch of the depthwise unit ``u`` on the input ``x`` (``problems.dwconv_problem``)."""
         geo = operands.pop("geo", u.geo)
         self._launch(*dwconv_args(dwconv_problem(geo, x, act_ld, u.conv.weight, **operands)))
+
+    def _gconv(self, u, x, act_ld, **operands):
+        """One launch of the grouped unit ``u`` on the input ``x`` (``problems.gconv_problem``)."""
+        geo = operands.pop("geo", u.geo)
+        self._launch(*gconv_args(gconv_problem(geo, u.conv.groups, x, act_ld, u.conv.weight, **operands)))
+
+    def _in_place_conv(self, u, x, act_ld, **operands):
+        """The launch of a depthwise or grouped unit: the same operands, its own family's entry points."""
+        (self._dwconv if u.depthwise else self._gconv)(u, x, act_ld, **operands)
 
     def _conv_carrying_scatter(self, u, mat, splits, src, half):
         """The im2col'd first layer's convolution (its weight operand ``mat`` is a slice of a flat vector, no

@@ -66,6 +66,7 @@ class _Unit:
         self.im2col = False       # tiny-Cin layer: runs as a 1x1 product over the im2col of the input
         self.depthwise = False    # plain stack: groups = channels, on the kernels of hf_dwconv.hip (weight read in place)
         self.two_term = False     # ... whose second-order backward is the two-term launch (Hessian engine, both terms live)
+        self.grouped = False      # plain stack: any other grouped layer, on the kernels of hf_gconv.hip (weight read in place)
         self.train = False        # train-mode BatchNorm: batch statistics (recorded), tangent / adjoint carry
         self.mean_t = None        # the statistics' dependence on the layer input
         self.epi = self.tsum = False  # train mode: the tangent's partial sums come from the convolution's epilogue
@@ -77,6 +78,13 @@ class _Unit:
         self.no_dgrad = False     # a live unit whose input carries no tangent: its data gradient is not needed
         self.pool = None          # plain stack: (kh, kw, sh, sw, ph, pw) of the MaxPool2d behind the unit (its ReLU)
         self.rp = None            # ... and the pooled map the model's forward pass recorded
+
+    @property
+    def in_place(self):
+        """A depthwise or grouped unit: its kernels read the weight and the vector's slice V in place (no ``[W | v_W]``
+        operand, no (I, H, W, O) copies, no tangent slot) and leave ONE slab per direction, the weight gradient's in the
+        parameter's own order."""
+        return self.depthwise or self.grouped
 
     # per-channel affine map behind the convolution: BatchNorm statistics / scale / shift, or a bias
     @property

@@ -53,8 +53,8 @@ class _DiagEF:
                 ga = (u.ga1 if first_order else u.ga)[i:i + 1]
                 if u.pw is None:
                     pass  # (frozen weight: no entry)
-                elif u.depthwise:
-                    self._dwconv(u, u.x[i:i + 1], u.geo.c, geo=u.geo1, ga=ga, slabs=u.wps, splits=u.sW1)
+                elif u.in_place:
+                    self._in_place_conv(u, u.x[i:i + 1], u.geo.c, geo=u.geo1, ga=ga, slabs=u.wps, splits=u.sW1)
                 elif u.im2col:
                     self._conv_slabs(2, u.wps, u.cols_pad[i:i + 1], ga, u.geo_w1, u.sW1, out_c=u.jcols)
                 else:
@@ -139,16 +139,16 @@ class _DiagEF:
                 rows1 = u.a.shape[2] * u.a.shape[3]
                 u.geo_w1 = u.geo_w.with_n(rows1)
                 u.sW1 = self._plan(2, u.geo_w1)
-            elif u.depthwise:
+            elif u.in_place:
                 u.geo1 = u.geo.with_n(1)
-                u.sW1 = self._plan_depthwise(u.geo1, u.name)
+                u.sW1 = self._plan_in_place(u, u.geo1)
             else:
                 u.geo1 = u.geo.with_n(1)
                 u.sW1 = self._plan(2, u.geo1, u.name)
             u.wps = torch.zeros((u.sW1, u.conv.weight.numel()), dtype=f32, device=dev)  # dead taps stay 0
             if u.pw is not None:
                 tensors[u.pw] = u.wps[0]
-                if not u.im2col and not u.depthwise:
+                if not u.im2col and not u.in_place:
                     k_, c, r, s_ = u.conv.weight.shape
                     if r * s_ > 1:
                         perms[u.pw] = (c, r * s_)

@@ -32,8 +32,8 @@ class _Forward:
         if u.im2col:  # 1x1 product over the im2col; the weight is read from the parameter itself
             self._conv_slabs(0, u.tbuf, u.cols, u.conv.weight.detach(), u.geo, u.sF)
             return
-        if u.depthwise:  # (the one-term form on x and the parameter itself)
-            self._dwconv(u, u.x, u.geo.c, out=u.tbuf, v=u.conv.weight)
+        if u.in_place:  # (depthwise / grouped: the one-term form on x and the parameter itself)
+            self._in_place_conv(u, u.x, u.geo.c, out=u.tbuf, v=u.conv.weight)
             return
         self._conv_slabs(0, u.tbuf, u.x, u.wcat, u.geo, u.sF, mat_ld=u.geo.doubled().c)
 

@@ -63,7 +63,15 @@ class PlainStackEngine(_ConvEngine):
     launch, ``hf_dwconv2d_nhwc_backward2_slabs`` -- ``dx = D(g', W) + D(g, V)``, ``slabs = W(x, g') + W(t_x, g)`` -- so it has
     no extras slabs (``nD = sD``, ``nW`` from the two-term plan); a frozen weight or a tangent-free input keeps the one-term
     launch.  With ``HF_DIAG_EF_BATCHED=1`` its weight entries of ``diag_ef`` come from ONE ``hf_dwconv2d_nhwc_sqsum_slabs``
-    launch on the whole batch.  All of it opt-in: none of these routes' speed is measured."""
+    launch on the whole batch.  All of it opt-in: none of these routes' speed is measured.
+
+    Grouped units (``HF_GROUP_ENGINE=1``; ResNeXt / RegNet / ShuffleNet-style layers): any other ``Conv2d(groups = G)`` whose
+    group widths ``c_in / G`` and ``c_out / G`` are multiples of 4 up to 64, up to 49 taps, anywhere but first, with the same
+    bias / BatchNorm / ReLU / max-pool behind it.  The kernels of hf_gconv.hip (``v_mfma_f32_4x4x1_16b_f32``: 4 pixels x 64
+    channels per issue, each of the 16 blocks a channel quad on its own group) follow the depthwise conventions -- weight
+    and V in place, one slab per direction, slabs in parameter order: ``hf_gconv2d_nhwc_tangent`` and
+    ``hf_gconv2d_nhwc_backward_slabs``.  GGN products, one process; ``diag_ef`` by per-sample launches.  Opt-in: its speed
+    against the autograd route is not measured."""
 
     mode = ("fused curvature engine (plain conv-ReLU stack): own deterministic convolutions (split-K slabs summed "
             "by the consumer kernel), bias / ReLU / max-pool fused, 4 launches per layer")
@@ -101,16 +109,18 @@ class PlainStackEngine(_ConvEngine):
             if type(m) is nn.Conv2d:
                 if tuple(m.dilation) != (1, 1) or not getattr(m, "_hf_channels_last", False):
                     raise _Unsupported(f"conv {len(units)}: needs prepare_model(channels_last=True), dilation = 1")
-                depthwise = m.groups != 1
+                depthwise = m.groups != 1 and m.groups == m.in_channels == m.out_channels
                 if depthwise:
                     self._layout_depthwise(m, f"conv {len(units)}", first=not units)
+                elif m.groups != 1:
+                    self._layout_grouped(m, f"conv {len(units)}", first=not units)
                 cx, cy = records_of(m, with_input=True)
                 if not _same(cx, cur):
                     raise _Unsupported(f"conv {len(units)}: input is not the previous activation")
                 nxt = leaves[i + 1] if i + 1 < len(leaves) else None
                 bn = nxt if type(nxt) is nn.BatchNorm2d else None
                 u = _Unit(f"conv{len(units)}", m, bn)
-                u.depthwise = depthwise
+                u.depthwise, u.grouped = depthwise, m.groups != 1 and not depthwise
                 y, u.relu = cy, False
                 if bn is not None:
                     y, u.relu = self._layout_bn(u, bn, cy)
@@ -203,9 +213,6 @@ class PlainStackEngine(_ConvEngine):
         channel, zero padding, channel quads, at most 49 taps, behind a unit that fills its ``[t_x | x]`` operand; one
         process; Hessian products only with ``HF_DW_HESSIAN=1``."""
         c, (r, s) = m.in_channels, m.kernel_size
-        if m.groups != c or m.out_channels != c:
-            raise _Unsupported(f"{name}: groups = {m.groups} with {c} -> {m.out_channels} channels: only depthwise "
-                               "convolutions (groups = in_channels = out_channels) are covered, no depth multiplier")
         if m.padding_mode != "zeros" or isinstance(m.padding, str):
             raise _Unsupported(f"{name}: a depthwise convolution needs numeric zero padding")
         if os.environ.get("HF_DW_ENGINE", "0") != "1":
@@ -221,6 +228,28 @@ class PlainStackEngine(_ConvEngine):
                                "of HF_DW_ENGINE=1: HF_DW_HESSIAN=1)")
         if self.group is not None:
             raise _Unsupported(f"{name}: data parallelism is not covered for a depthwise convolution")
+
+    def _layout_grouped(self, m, name, first):
+        """What any other grouped ``Conv2d`` must be to become a grouped unit (the kernels of hf_gconv.hip): opted in,
+        group widths that are multiples of 4 up to 64 on both sides, zero padding, at most 49 taps, behind a unit that fills
+        its ``[t_x | x]`` operand; one process; GGN products."""
+        cgi, cgo, (r, s) = m.in_channels // m.groups, m.out_channels // m.groups, m.kernel_size
+        what = f"{name}: groups = {m.groups} with {m.in_channels} -> {m.out_channels} channels"
+        if cgi == 1 or os.environ.get("HF_GROUP_ENGINE", "0") != "1":
+            raise _Unsupported(f"{what}: only depthwise convolutions (groups = in_channels = out_channels) are covered, no "
+                               "depth multiplier" + ("" if cgi == 1 else "; other grouped layers are opt-in (HF_GROUP_ENGINE=1)"))
+        if cgi % 4 or cgo % 4 or max(cgi, cgo) > 64:
+            raise _Unsupported(f"{what}: {cgi} -> {cgo} channels per group (the grouped kernels take multiples of 4 up to 64)")
+        if m.padding_mode != "zeros" or isinstance(m.padding, str):
+            raise _Unsupported(f"{name}: a grouped convolution needs numeric zero padding")
+        if r * s > 49:
+            raise _Unsupported(f"{name}: grouped with {r * s} taps (the kernels take up to 49)")
+        if first:
+            raise _Unsupported(f"{name}: a grouped first layer is not covered (its input has no [t_x | x] operand)")
+        if self.hessian:
+            raise _Unsupported(f"{name}: Hessian products through a grouped convolution are not covered")
+        if self.group is not None:
+            raise _Unsupported(f"{name}: data parallelism is not covered for a grouped convolution")
 
     def _layout_bn(self, u, bn, cy):
         """The BatchNorm behind ``u``'s convolution (output record ``cy``): what the unit's output record and ReLU flag
@@ -451,12 +480,12 @@ class PlainStackEngine(_ConvEngine):
             if u.im2col:  # no input tangent: conv(x, v_W) as a 1x1 product over the im2col
                 if not (carried and u is first):
                     self._conv_slabs(0, u.tbuf, u.cols, self._weight_tangent(v, u), u.geo, u.sT)
-            elif u.depthwise:
+            elif u.in_place:
                 # t_x and x: the halves of the producer's operand; V: the vector's slice in place (frozen: no x * V term;
                 # behind frozen layers only: no t_x * W term)
                 c, vw = u.geo.c, self._param_slice(v, u.pw, u.conv.weight.numel())
                 t_x = None if (u.no_dgrad and vw is not None) else u.xcat[:, :c]
-                self._dwconv(u, u.xcat[:, c:], 2 * c, out=u.tbuf, t_x=t_x, v=vw)
+                self._in_place_conv(u, u.xcat[:, c:], 2 * c, out=u.tbuf, t_x=t_x, v=vw)
                 if u.train:
                     u.tsum = False  # (the sums over the tangent's rows: a reduction launch of their own)
             elif u.train:  # (the epilogue writes the tangent's per-channel partial sums where it takes the geometry)
@@ -540,8 +569,8 @@ class PlainStackEngine(_ConvEngine):
         sig = super().layer_signature()
         if self._dropouts:  # (skipped as inert: one that becomes active is another network)
             sig = sig + (tuple(bool(m.training and m.p > 0) for m in self._dropouts),)
-        if any(u.depthwise for u in self.units):  # (read in place: a frozen one's address is a kernel argument)
-            sig = sig + (tuple(u.conv.weight.data_ptr() for u in self.units if u.depthwise),)
+        if any(u.in_place for u in self.units):  # (read in place: a frozen one's address is a kernel argument)
+            sig = sig + (tuple(u.conv.weight.data_ptr() for u in self.units if u.in_place),)
         if not self.classifier:
             return sig
         return sig + (tuple((id(u.lin), u.act) for u in self.classifier), tuple(t.data_ptr() for t in self._sig_tail))

@@ -190,6 +190,36 @@ def dwconv_sqsum_args(out, ga, x, act_ld, geo, splits, pre):
     return (out, ga, x, act_ld, *_dw_dims(geo), float(pre), int(splits), out.shape[1])
 
 
+# ---- grouped convolutions (hf_gconv.hip): the depthwise pair's conventions, with the group count ---------------------
+GConvProblem = namedtuple("GConvProblem", "geo groups x act_ld w out t_x v ga dx slabs splits")
+
+
+def gconv_problem(geo, groups, x, act_ld, w, out=None, t_x=None, v=None, ga=None, dx=None, slabs=None, splits=0):
+    """A grouped layer ``geo`` (``c`` -> ``k`` channels in ``groups`` groups) on the input ``x`` at pixel pitch ``act_ld`` and
+    the weight ``w`` [k, c / groups, r, s] read in place.  With ``out``: ``out = conv(t_x, w) + conv(x, v)`` -- ``t_x`` (same
+    pitch) or ``v`` (the CG vector's slice) may be None, not both; the forward pass is ``v = w`` alone.  With ``ga``: the data
+    gradient -> ``dx`` (None: not needed) and the weight gradient -> ``slabs`` [splits, k*(c/groups)*r*s], one launch."""
+    if geo.c % groups or geo.k % groups or (out is None) == (ga is None):
+        raise RuntimeError("gconv_problem: channel counts that are multiples of the groups, and either an output or a cotangent")
+    return GConvProblem(geo, int(groups), x, act_ld, w, out, t_x, v, ga, dx, slabs, int(splits))
+
+
+def gconv_dims(geo, groups):
+    """``n, h, w, c_in, c_out, groups, r, s, stride_h, stride_w, pad_h, pad_w``: as the grouped entry points list them."""
+    d = geo.dims()
+    return d[:5] + (int(groups),) + d[5:]
+
+
+def gconv_args(q):
+    """The entry point's name, then its arguments: ``hf_gconv2d_nhwc_tangent`` or ``hf_gconv2d_nhwc_backward_slabs``."""
+    dims = gconv_dims(q.geo, q.groups)
+    if q.ga is None:
+        return ("hf_gconv2d_nhwc_tangent", q.out, q.t_x, q.x if q.v is not None else None, q.act_ld,
+                q.w if q.t_x is not None else None, q.v, *dims)
+    return ("hf_gconv2d_nhwc_backward_slabs", q.dx, q.slabs, q.ga, q.x, q.act_ld, q.w if q.dx is not None else None,
+            *dims, q.splits, q.slabs.shape[1])
+
+
 # ---- the squared-sum launches of the batched diagonal empirical Fisher (positional entry points, no struct) ------------
 def conv_sqsum_args(out, act, mat, geo, splits, pre, act_ld=0, out_c=0):
     """``hf_conv2d_nhwc_sqsum_slabs``: ``out`` [splits, numel] receives split s's partial sum over its samples of the

@@ -289,6 +289,30 @@ class DWSepSmall(nn.Module):
         return torch.flatten(_batched(self.net, x), -3)
 
 
+class GroupSmall(nn.Module):
+    """The smallest plain stack with grouped layers: conv3(3->8, pad 1) ReLU (the im2col'd first layer), g3x3(8->8, 2 groups,
+    pad 1) ReLU + conv1(8->16) ReLU, g3x3(16->32, 4 groups, stride 2, pad 1: 4 -> 8 channels per group) without a ReLU +
+    conv1(32->classes), global average pool.  ``bn``: the two grouped units and their pointwise partners are
+    ``Conv(bias=False) BatchNorm2d [ReLU]``."""
+
+    def __init__(self, num_classes=12, bn=False):
+        super().__init__()
+
+        def unit(conv, relu=True):
+            return ([conv, nn.BatchNorm2d(conv.out_channels)] if bn else [conv]) + ([nn.ReLU()] if relu else [])
+
+        self.net = nn.Sequential(
+            nn.Conv2d(3, 8, 3, 1, 1), nn.ReLU(),
+            *unit(nn.Conv2d(8, 8, 3, 1, 1, groups=2, bias=not bn)), *unit(nn.Conv2d(8, 16, 1, bias=not bn)),
+            *unit(nn.Conv2d(16, 32, 3, 2, 1, groups=4, bias=not bn), relu=False),
+            *unit(nn.Conv2d(32, num_classes, 1, bias=not bn), relu=False),
+            nn.AdaptiveAvgPool2d((1, 1)),
+        )
+
+    def forward(self, x):  # (BatchNorm2d takes no unbatched sample)
+        return torch.flatten(_batched(self.net, x), -3)
+
+
 class VGG11BN(nn.Module):
     """VGG-11 with BatchNorm for 32x32 inputs (the usual CIFAR form): conv3 + BN + ReLU units of 64, 128, 256, 256, 512,
     512, 512, 512 channels, a MaxPool(2, 2) behind units 1, 2, 4, 6 and 8 (32 -> 1), ``Flatten``, ``Linear(512->classes)``.
@@ -491,6 +515,17 @@ def dwsep_small(batch_size=3, seed=0, device="cpu", data_seed=None, bn=False):
     """``DWSepSmall`` in eval mode (``bn``: with seeded BatchNorm state); inputs U[0,1) [B,3,9,7], 12 classes, CE-mean."""
     torch.manual_seed(seed)
     model = seed_batchnorm(DWSepSmall(12, bn), seed).eval()
+    g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
+    inputs = torch.rand(batch_size, 3, 9, 7, generator=g)
+    targets = torch.randint(0, 12, (batch_size,), generator=g)
+    return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
+
+
+def group_small(batch_size=3, seed=0, device="cpu", data_seed=None, bn=False):
+    """``GroupSmall`` in eval mode (``bn``: with seeded BatchNorm state) on ``dwsep_small``'s inputs: U[0,1) [B,3,9,7],
+    12 classes, CE-mean."""
+    torch.manual_seed(seed)
+    model = seed_batchnorm(GroupSmall(12, bn), seed).eval()
     g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
     inputs = torch.rand(batch_size, 3, 9, 7, generator=g)
     targets = torch.randint(0, 12, (batch_size,), generator=g)
