@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 29
+#define HF_ABI_VERSION 30
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -1139,7 +1139,7 @@ int hf_dwconv2d_nhwc_sqsum_slabs(void* out, const void* ga, const void* x, int64
                                  int64_t c, int64_t r, int64_t s, int64_t stride_h, int64_t stride_w, int64_t pad_h,
                                  int64_t pad_w, float pre, int splits, int64_t slab_stride, int dtype, void* stream);
 
-/* ---- grouped convolutions inside the GGN product (hf_gconv.hip, ABI 29) ---------------- */
+/* ---- grouped convolutions inside the GGN product (hf_gconv.hip, ABI 29 / 30) ----------- */
 /*
  * The sweeps through a grouped nn.Conv2d (c_in -> c_out in `groups` groups, weight [c_out, cg_in, r, s] with cg_in =
  * c_in / groups input and cg_out = c_out / groups output channels per group) of a plain stack (engine/plain.py), on
@@ -1176,6 +1176,35 @@ int hf_dwconv2d_nhwc_sqsum_slabs(void* out, const void* ga, const void* x, int64
  *       splits_w > 1), for hf_pack_ex to add in split order (no permutation).  One chain per entry: the run's units
  *       ascending, a unit's pixels in row-major order.  x at pixel pitch act_ld.  splits_w must be hf_gconv2d_nhwc_plan's
  *       count for the geometry (HF_ERR_ARG otherwise).
+ *   hf_gconv2d_nhwc_backward2_slabs (ABI 30): the TANGENT of that backward sweep -- a Hessian product's second-order
+ *       backward through the layer -- in ONE launch, with one slab per direction as the one-term launch:
+ *         dx       = D(ga_t, W) + D(ga, V)        gw_slabs = W(x, ga_t) + W(t_x, ga)
+ *       (D / W: the data / weight gradient above.)  ga_t = g', the cotangent's tangent, and ga = g, the step's first-order
+ *       cotangent: dense [n, oh, ow, c_out].  x and t_x: two pointers with ONE pixel pitch act_ld, the halves of the
+ *       producer's [t_x | x] operand.  W: the parameter, V: the CG vector's slice, both read in place.  The terms run one
+ *       after the other through the one-term launch's staging area into its accumulators, so LDS, registers, the plan
+ *       (hf_gconv2d_nhwc_plan's count) and the grid are the one-term launch's.  Rounding, one chain from zero each:
+ *       dx all of ga_t * W (co ascending, per co the taps in ascending (i, j)), then all of ga * V in the same order;
+ *       gw per unit the pixels of (ga_t, x) in row-major order, then those of (ga, t_x), the run's units ascending.
+ *       No atomics; two launches give the same bits.  Refused with HF_ERR_ARG before any launch: a NULL among the eight
+ *       operands, splits_w other than the plan's count, slab_stride < c_out*cg_in*r*s with more than one slab, act_ld
+ *       outside [c_in, 2*c_in] (0 = c_in), and what the common contract refuses.  A vanishing term (frozen weight,
+ *       tangent-free input) is the one-term launch's case, not this one's.
+ *   hf_gconv2d_nhwc_sqsum_slabs (ABI 30): the sum over the samples of the SQUARED per-sample weight gradient, the grouped
+ *       sibling of hf_dwconv2d_nhwc_sqsum_slabs with its conventions:
+ *         out[co][ci][i][j] = sum_{m<n} ( pre * sum_{p in sample m} ga[m,p,co] * x[m, pix(p,i,j), g*cg_in + ci] )^2
+ *       in PARAMETER order [c_out][cg_in][r*s].  The SPLITS RUN OVER THE SAMPLES: split t takes samples
+ *       [t*ceil(n/splits), ...) and writes its partial sum to out + t*slab_stride for hf_pack_ex (mode 0) to add in split
+ *       order.  A workgroup owns (split, pass, span of 64 output channels) and runs the weight-gradient loop over a
+ *       sample's output tiles (ascending, the one-term chain) into its slot accumulators; at the sample's end every lane
+ *       folds the entries it owns, t = acc * pre (one rounding), sum += t * t (two roundings), acc = 0; the samples
+ *       ascending.  Every entry has one owner lane: no shuffle, no LDS reduction, no per-sample gradient in memory, no
+ *       atomics; two launches give the same bits; every entry of every slab is written.  hf_gconv2d_nhwc_sqsum_plan
+ *       returns the planned count: towards target_blocks workgroups (0 = 512) at spans * passes workgroups per split, at
+ *       most min(n, 64), no split without a sample.  The launch takes that count or any other that leaves no split empty
+ *       (1 <= splits <= n, (splits - 1) * ceil(n/splits) < n); anything else, a slab_stride below c_out*cg_in*r*s with
+ *       splits > 1, a NULL operand, act_ld outside [c_in, 2*c_in] or a `pre` that is not finite is HF_ERR_ARG before any
+ *       launch.
  */
 int hf_gconv2d_nhwc_plan(int64_t n, int64_t h, int64_t w, int64_t c_in, int64_t c_out, int64_t groups, int64_t r, int64_t s,
                          int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w);
@@ -1187,6 +1216,18 @@ int hf_gconv2d_nhwc_backward_slabs(void* dx, void* gw_slabs, const void* ga, con
                                    int64_t n, int64_t h, int64_t w, int64_t c_in, int64_t c_out, int64_t groups, int64_t r,
                                    int64_t s, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
                                    int splits_w, int64_t slab_stride, int dtype, void* stream);
+int hf_gconv2d_nhwc_backward2_slabs(void* dx, void* gw_slabs, const void* ga_t, const void* ga, const void* x,
+                                    const void* t_x, int64_t act_ld, const void* W, const void* V, int64_t n, int64_t h,
+                                    int64_t w, int64_t c_in, int64_t c_out, int64_t groups, int64_t r, int64_t s,
+                                    int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int splits_w,
+                                    int64_t slab_stride, int dtype, void* stream);
+int hf_gconv2d_nhwc_sqsum_plan(int64_t n, int64_t h, int64_t w, int64_t c_in, int64_t c_out, int64_t groups, int64_t r,
+                               int64_t s, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
+                               int target_blocks);
+int hf_gconv2d_nhwc_sqsum_slabs(void* out, const void* ga, const void* x, int64_t act_ld, int64_t n, int64_t h, int64_t w,
+                                int64_t c_in, int64_t c_out, int64_t groups, int64_t r, int64_t s, int64_t stride_h,
+                                int64_t stride_w, int64_t pad_h, int64_t pad_w, float pre, int splits, int64_t slab_stride,
+                                int dtype, void* stream);
 
 /* ---- RCCL (resolved at run time from the already-loaded librccl) ----------- */
 typedef struct hf_comm hf_comm_t;

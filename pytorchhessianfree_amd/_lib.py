@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HF_PCG_LIB") or os.path.join(_HERE, "csrc", "libhfpcg.so")
 
 HF_F32, HF_F64 = 0, 1
-ABI_VERSION = 29
+ABI_VERSION = 30
 HF_ERR_ARG = -1  # hf_status of include/hf_pcg.h: null / negative / inconsistent argument
 HF_M_NONE, HF_M_DIAG, HF_M_EXTERNAL = 0, 1, 2
 REASONS = {
@@ -236,6 +236,11 @@ SIGNATURES = {
                                 + [c_int, c_void_p]),
     "hf_gconv2d_nhwc_backward_slabs": (c_int, [c_void_p] * 4 + [c_int64, c_void_p] + [c_int64] * 12
                                        + [c_int, c_int64, c_int, c_void_p]),
+    "hf_gconv2d_nhwc_backward2_slabs": (c_int, [c_void_p] * 6 + [c_int64, c_void_p, c_void_p] + [c_int64] * 12
+                                        + [c_int, c_int64, c_int, c_void_p]),
+    "hf_gconv2d_nhwc_sqsum_plan": (c_int, [c_int64] * 12 + [c_int]),
+    "hf_gconv2d_nhwc_sqsum_slabs": (c_int, [c_void_p] * 3 + [c_int64] * 13 + [ctypes.c_float, c_int, c_int64, c_int,
+                                                                               c_void_p]),
     "hf_comm_unique_id": (c_int, [ctypes.c_char_p]),
     "hf_comm_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.c_char_p, c_int, c_int]),
     "hf_comm_destroy": (c_int, [c_void_p]),
@@ -691,6 +696,16 @@ def dwconv_sqsum_plan(n, h, w, c, r, s, stride, padding, target_blocks=0):
                                             int(target_blocks))
     if sp < 1:
         check(sp, "hf_dwconv2d_nhwc_sqsum_plan")
+    return sp
+
+
+def gconv_sqsum_plan(n, h, w, c_in, c_out, groups, r, s, stride, padding, target_blocks=0):
+    """Number of sample splits a grouped squared-sum launch of this geometry is planned with
+    (``hf_gconv2d_nhwc_sqsum_plan``)."""
+    sp = load().hf_gconv2d_nhwc_sqsum_plan(n, h, w, c_in, c_out, groups, r, s, stride[0], stride[1], padding[0], padding[1],
+                                           int(target_blocks))
+    if sp < 1:
+        check(sp, "hf_gconv2d_nhwc_sqsum_plan")
     return sp
 
 

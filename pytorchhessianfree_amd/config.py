@@ -178,6 +178,10 @@ SWITCHES = {
                         "by default: its GGN products per second are not measured against the autograd path -- without it "
                         "such a net keeps that path",
                         "tests/test_group_engine_gpu.py::test_eval_point_against_float64"),
+    "HF_GROUP_HESSIAN": ("0", "1: with HF_GROUP_ENGINE=1, curvature_opt='hessian' on a net with grouped units takes the plain-"
+                         "stack engine (the second-order backward of a grouped unit in one launch, "
+                         "hf_gconv2d_nhwc_backward2_slabs) instead of the autograd operator; unmeasured, hence opt-in",
+                         "tests/test_group_hessian_engine_gpu.py::test_hessian_products_against_float64"),
     "HF_CHUNKED_ALLREDUCE": ("auto", "0 / 1: force the single-graph resp. the two-phase data-parallel product",
                              "tests/test_distributed_gpu.py::test_step_two_ranks_engine_session_equals_cpu_whole_batch"),
     "HF_DIRECT_RCCL": ("1", "0: every collective through torch.distributed (no communicator of the package's own)",

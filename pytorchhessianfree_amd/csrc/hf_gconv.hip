@@ -1,8 +1,9 @@
 // hf_gconv.hip -- grouped convolutions (Conv2d(c_in -> c_out, groups = G), group widths cg_in = c_in / G and cg_out =
 // c_out / G both multiples of 4 and <= 64) of the plain-stack engine (engine/plain.py): the tangent / forward map, and the
-// data + weight gradient of one cotangent in ONE launch.  fp32, wave64, NHWC, r*s <= 49 taps, per-axis stride and
-// padding, dilation 1, zero padding.  No atomics; every output is summed in one fixed order (below), so two launches on
-// the same operands agree bitwise.
+// data + weight gradient of one cotangent in ONE launch; the two-term form of the latter (a Hessian product's second-order
+// backward) and the squared per-sample weight gradient summed over the batch (diag_ef), one launch each.  fp32, wave64,
+// NHWC, r*s <= 49 taps, per-axis stride and padding, dilation 1, zero padding.  No atomics; every output is summed in one
+// fixed order (below), so two launches on the same operands agree bitwise.
 //
 // Why a design of its own.  A grouped layer's reduction is r*s*cg_in long and block-diagonal over the channels.  The 64x64
 // MFMA tiles of hf_conv.hip would be 1/16 .. 1/4 full per group and need one launch per group; the depthwise kernels have no
@@ -61,6 +62,32 @@
 //                   skipped row taps add nothing, the zero-fed column taps and out-of-map pixels add an exact zero.
 //   weight gradient: units of the run ascending, inside a unit the tile's pixels in row-major order (pixels outside
 //                   the map: an exact zero); hf_pack_ex then adds the slabs in split order.
+//
+// The two-term backward (hf_gconv2d_nhwc_backward2_slabs): dx = D(g', W) + D(g, V), slabs = W(x, g') + W(t_x, g), the
+// tangent of the backward sweep in ONE launch -- the same device functions under a template flag (TWO), by design point
+// (1): the terms one after the other through ONE staging area.  A data-gradient block runs its chunk loop over (g', W),
+// then over (g, V), through the same cotangent tile and weight table into the same acc[]; a weight-gradient block stages
+// per unit the x halo and the g' tile, runs the pixel loop, and behind a barrier stages the t_x halo and the g tile and
+// runs it again, the slot accumulators kept over both and over the run.  LDS words and accumulator registers are
+// therefore the one-term launch's: the same gc_plan, the same split count, the same grid.
+//   data gradient:  all of g' * W (co ascending, per co the taps ascending (i, j)), then all of g * V in that order.
+//   weight gradient: per unit the pixels of (g', x) in row-major order, then those of (g, t_x); units ascending.
+//
+// The squared sum (hf_gconv2d_nhwc_sqsum_slabs): out[co][ci][tap] = sum_m (pre * gw_m[co][ci][tap])^2 over the per-sample
+// weight gradients gw_m.  It is the weight-gradient loop (flag SQ) with a sample boundary in it: a workgroup owns (split of
+// the SAMPLES, pass, span of 64 output channels), runs a sample's output tiles in ascending order into the slot
+// accumulators, and at the sample's last tile every lane folds the entries it owns, in registers:  t = acc * pre (one
+// rounding), sq += t * t (two roundings), acc = 0; samples ascending; sq goes to the split's slab in parameter order, every
+// entry of it.  One owner lane per entry: no shuffle, no LDS, no per-sample gradient in memory.  The samples are cut into
+// min(n, 64, ceil(target / (spans * passes))) runs of ceil(n / runs) samples, none empty.  The running sums double the
+// accumulator registers (16 slots per wave: 64 + 64); the slot cap stays 16 -- the compiler's figures show no scratch.
+//
+// Resource usage (gfx950, -O3, the compiler's remarks; LDS is dynamic, the weight gradient's words above -- 3x3 stride 1:
+// width 4 42.6 KB, width 16 42.6 KB (100*65 + 64*65), width 64 28.2 KB -- for the two-term form and the squared sum alike):
+//                                                            VGPRs   AGPRs   scratch
+//   k_gc_tangent   (every form)                             50-52       4         0
+//   k_gc_backward  (one term and TWO: the same figures)        92      64         0
+//   k_gc_sqsum                                                176      64         0     (2 waves per SIMD)
 #include "hf_common.h"
 
 namespace {
@@ -290,9 +317,10 @@ k_gc_tangent(float* __restrict__ out, const float* __restrict__ tx, const float*
 }
 
 // ---- data gradient: one workgroup per (sample, th x 8 tile of INPUT pixels, span of 64 input channels) ----------------
-template <bool AL>
-__device__ __forceinline__ void gc_dgrad(float* __restrict__ dx, const float* __restrict__ ga, const float* __restrict__ W,
-                                         const GcPlan& g, int b) {
+// TWO: D(ga, W) + D(ga1, V) -- the chunk loop once per term through the same cotangent tile and weight table, one acc[]
+template <bool AL, bool TWO>
+__device__ __forceinline__ void gc_dgrad(float* __restrict__ dx, const float* __restrict__ ga, const float* __restrict__ ga1,
+                                         const float* __restrict__ W, const float* __restrict__ V, const GcPlan& g, int b) {
   const GcDir d = g.d;
   const int rs = g.r * g.s, qw = d.th >> 1;
   const int span = b % g.ispans;
@@ -310,40 +338,44 @@ __device__ __forceinline__ void gc_dgrad(float* __restrict__ dx, const float* __
   gc_v4 acc[GC_QW];
 #pragma unroll
   for (int q = 0; q < GC_QW; ++q) acc[q] = gc_v4{0.f, 0.f, 0.f, 0.f};
-  for (int o0 = 0; o0 < g.cgo; o0 += d.ck) {
-    const int cke = min(d.ck, g.cgo - o0);
-    __syncthreads();
-    gc_stage<AL>(cot, ga, g.co, img, g.oh, g.ow, g.cgo, l.g0, l.ng, o0, cke, d.ck, gy0, gx0, d.sh_, d.sw_, d.pitch);
-    // W[group's output channel o0 + ol][input channel of the span][tap] -> wl[(ol, tap)][input channel]: consecutive
-    // channels of one group are one contiguous run of the parameter
-    for (int idx = threadIdx.x; idx < cke * GC_SPAN * rs; idx += BLOCK) {
-      const int tap = idx % rs, t = idx / rs;
-      const int cl = t % GC_SPAN, ol = t / GC_SPAN;
-      const int c = l.c0 + cl;
-      float v = 0.f;
-      if (c < g.ci) {
-        const int grp = c / g.cgi, cil = c - grp * g.cgi;
-        v = W[((int64_t)(grp * g.cgo + o0 + ol) * g.cgi + cil) * rs + tap];
+  for (int term = 0; term < (TWO ? 2 : 1); ++term) {
+    const float* __restrict__ cog = term ? ga1 : ga;
+    const float* __restrict__ mat = term ? V : W;
+    for (int o0 = 0; o0 < g.cgo; o0 += d.ck) {
+      const int cke = min(d.ck, g.cgo - o0);
+      __syncthreads();
+      gc_stage<AL>(cot, cog, g.co, img, g.oh, g.ow, g.cgo, l.g0, l.ng, o0, cke, d.ck, gy0, gx0, d.sh_, d.sw_, d.pitch);
+      // W[group's output channel o0 + ol][input channel of the span][tap] -> wl[(ol, tap)][input channel]: consecutive
+      // channels of one group are one contiguous run of the parameter
+      for (int idx = threadIdx.x; idx < cke * GC_SPAN * rs; idx += BLOCK) {
+        const int tap = idx % rs, t = idx / rs;
+        const int cl = t % GC_SPAN, ol = t / GC_SPAN;
+        const int c = l.c0 + cl;
+        float v = 0.f;
+        if (c < g.ci) {
+          const int grp = c / g.cgi, cil = c - grp * g.cgi;
+          v = mat[((int64_t)(grp * g.cgo + o0 + ol) * g.cgi + cil) * rs + tap];
+        }
+        wl[(ol * rs + tap) * GC_WP + cl] = v;
       }
-      wl[(ol * rs + tap) * GC_WP + cl] = v;
-    }
-    __syncthreads();
-    for (int ol = 0; ol < cke; ++ol) {
-      for (int i = 0; i < g.r; ++i) {
-        for (int j = 0; j < g.s; ++j) {
-          const float bv = wl[(ol * rs + i * g.s + j) * GC_WP + l.lane];
+      __syncthreads();
+      for (int ol = 0; ol < cke; ++ol) {
+        for (int i = 0; i < g.r; ++i) {
+          for (int j = 0; j < g.s; ++j) {
+            const float bv = wl[(ol * rs + i * g.s + j) * GC_WP + l.lane];
 #pragma unroll
-          for (int q = 0; q < GC_QW; ++q) {
-            if (q >= qw) continue;
-            const int qi = l.wave * qw + q;
-            const int t = h0 + (qi >> 1) + g.ph - i;  // (uniform for the quad)
-            if (t < 0 || t % g.sh) continue;
-            const int ly = t / g.sh - gy0;   // 0 <= ly < sh_: (t_max - t_min) / stride <= (th + r - 2) / stride
-            const int u = w0 + 4 * (qi & 1) + l.li + g.pw - j;
-            const bool on = u >= 0 && u % g.sw == 0;
-            const int lx = on ? u / g.sw - gx0 : 0;
-            const float av = cot[(ly * d.sw_ + lx) * d.pitch + l.gl * d.ck + ol];
-            acc[q] = gc_mfma(on ? av : 0.f, bv, acc[q]);
+            for (int q = 0; q < GC_QW; ++q) {
+              if (q >= qw) continue;
+              const int qi = l.wave * qw + q;
+              const int t = h0 + (qi >> 1) + g.ph - i;  // (uniform for the quad)
+              if (t < 0 || t % g.sh) continue;
+              const int ly = t / g.sh - gy0;   // 0 <= ly < sh_: (t_max - t_min) / stride <= (th + r - 2) / stride
+              const int u = w0 + 4 * (qi & 1) + l.li + g.pw - j;
+              const bool on = u >= 0 && u % g.sw == 0;
+              const int lx = on ? u / g.sw - gx0 : 0;
+              const float av = cot[(ly * d.sw_ + lx) * d.pitch + l.gl * d.ck + ol];
+              acc[q] = gc_mfma(on ? av : 0.f, bv, acc[q]);
+            }
           }
         }
       }
@@ -364,9 +396,13 @@ __device__ __forceinline__ void gc_dgrad(float* __restrict__ dx, const float* __
 }
 
 // ---- weight gradient: one workgroup per (run of units, pass, span of 64 output channels) -------------------------------
-template <bool AL>
-__device__ __forceinline__ void gc_wgrad(float* __restrict__ gw, const float* __restrict__ ga, const float* __restrict__ x,
-                                         int64_t ld, int64_t slab_stride, const GcPlan& g, int b) {
+// TWO: W(x, ga) + W(tx, ga1) -- per unit the halo of x and the tile of ga, the pixel loop, then the halo of tx and the tile
+// of ga1 through the same staging area, the pixel loop again; the slot accumulators are kept over both.
+// SQ (the squared sum): a run is `per` SAMPLES; at a sample's last tile every lane folds the entries it owns.
+template <bool AL, bool TWO, bool SQ>
+__device__ __forceinline__ void gc_wgrad(float* __restrict__ gw, const float* __restrict__ ga, const float* __restrict__ ga1,
+                                         const float* __restrict__ x, const float* __restrict__ tx, int64_t ld,
+                                         int64_t slab_stride, float pre, const GcPlan& g, int b) {
   const GcDir d = g.g;
   const int rs = g.r * g.s, npix = d.th * GC_TW;
   const int span = b % g.ospans;
@@ -378,35 +414,57 @@ __device__ __forceinline__ void gc_wgrad(float* __restrict__ gw, const float* __
   float* gt = gc_lds + d.sh_ * d.sw_ * d.pitch;   // [th * 8][GC_WP]
   int soff[GC_WSLOTS];                            // the slot's offset from a pixel's first word of the halo tile
   gc_v4 acc[GC_WSLOTS];
+  gc_v4 sq[SQ ? GC_WSLOTS : 1];                   // SQ: the run's sums of squares, entry for entry as acc[]
 #pragma unroll
   for (int m = 0; m < GC_WSLOTS; ++m) {
     const int sl = l.wave + WAVES * m, tap = sl / qk, ciq = sl - tap * qk;
     soff[m] = sl < nslots ? ((tap / g.s) * d.sw_ + tap % g.s) * d.pitch + 4 * ciq : 0;
     acc[m] = gc_v4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (SQ) sq[m] = gc_v4{0.f, 0.f, 0.f, 0.f};
   }
-  const int u0 = split * g.per, u1 = min(g.units, u0 + g.per);
+  const int tiles = g.tiles_x * d.tiles_y;  // (units per sample)
+  const int u0 = split * g.per * (SQ ? tiles : 1);
+  const int u1 = SQ ? min(g.n, (split + 1) * g.per) * tiles : min(g.units, u0 + g.per);
   for (int u = u0; u < u1; ++u) {
-    const int tix = u % g.tiles_x, tiy = (u / g.tiles_x) % d.tiles_y, img = u / (g.tiles_x * d.tiles_y);
-    __syncthreads();  // (the previous unit's readers are done)
-    gc_stage<AL>(xt, x, ld, img, g.h, g.w, g.cgi, l.g0, l.ng, c0, cke, d.ck, tiy * d.th * g.sh - g.ph,
-                 tix * GC_TW * g.sw - g.pw, d.sh_, d.sw_, d.pitch);
-    // the cotangent tile, zeros outside the map and past the last channel
-    for (int idx = threadIdx.x; idx < npix * (GC_SPAN / 4); idx += BLOCK) {
-      const int qd = idx % (GC_SPAN / 4), p = idx / (GC_SPAN / 4);
-      const int oy = tiy * d.th + p / GC_TW, ox = tix * GC_TW + p % GC_TW, ch = l.c0 + 4 * qd;
-      F4 v;
-      v.e[0] = v.e[1] = v.e[2] = v.e[3] = 0.f;
-      if (oy < g.oh && ox < g.ow && ch < g.co) v = gc_ld_quad<AL>(ga + ((int64_t)(img * g.oh + oy) * g.ow + ox) * g.co + ch);
+    const int tix = u % g.tiles_x, tiy = (u / g.tiles_x) % d.tiles_y, img = u / tiles;
+    for (int term = 0; term < (TWO ? 2 : 1); ++term) {
+      const float* __restrict__ act = term ? tx : x;
+      const float* __restrict__ cog = term ? ga1 : ga;
+      __syncthreads();  // (the previous unit's or term's readers are done)
+      gc_stage<AL>(xt, act, ld, img, g.h, g.w, g.cgi, l.g0, l.ng, c0, cke, d.ck, tiy * d.th * g.sh - g.ph,
+                   tix * GC_TW * g.sw - g.pw, d.sh_, d.sw_, d.pitch);
+      // the cotangent tile, zeros outside the map and past the last channel
+      for (int idx = threadIdx.x; idx < npix * (GC_SPAN / 4); idx += BLOCK) {
+        const int qd = idx % (GC_SPAN / 4), p = idx / (GC_SPAN / 4);
+        const int oy = tiy * d.th + p / GC_TW, ox = tix * GC_TW + p % GC_TW, ch = l.c0 + 4 * qd;
+        F4 v;
+        v.e[0] = v.e[1] = v.e[2] = v.e[3] = 0.f;
+        if (oy < g.oh && ox < g.ow && ch < g.co)
+          v = gc_ld_quad<AL>(cog + ((int64_t)(img * g.oh + oy) * g.ow + ox) * g.co + ch);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) gt[p * GC_WP + 4 * qd + e] = v.e[e];
+        for (int e = 0; e < 4; ++e) gt[p * GC_WP + 4 * qd + e] = v.e[e];
+      }
+      __syncthreads();
+      for (int p = 0; p < npix; ++p) {
+        const float av = gt[p * GC_WP + l.lane];  // (A: block = output-channel quad, row i = its channel)
+        const int base = ((p / GC_TW) * g.sh * d.sw_ + (p % GC_TW) * g.sw) * d.pitch + l.gl * d.ck + l.li;
+#pragma unroll
+        for (int m = 0; m < GC_WSLOTS; ++m)
+          if (l.wave + WAVES * m < nslots) acc[m] = gc_mfma(av, xt[base + soff[m]], acc[m]);
+      }
     }
-    __syncthreads();
-    for (int p = 0; p < npix; ++p) {
-      const float av = gt[p * GC_WP + l.lane];  // (A: block = output-channel quad, row i = its channel)
-      const int base = ((p / GC_TW) * g.sh * d.sw_ + (p % GC_TW) * g.sw) * d.pitch + l.gl * d.ck + l.li;
+    if constexpr (SQ) {
+      if ((u + 1) % tiles == 0) {  // the sample boundary: registers only, each entry by its one owner lane
 #pragma unroll
-      for (int m = 0; m < GC_WSLOTS; ++m)
-        if (l.wave + WAVES * m < nslots) acc[m] = gc_mfma(av, xt[base + soff[m]], acc[m]);
+        for (int m = 0; m < GC_WSLOTS; ++m) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float t = acc[m][i] * pre;  // (one rounding; then two)
+            sq[m][i] += t * t;
+          }
+          acc[m] = gc_v4{0.f, 0.f, 0.f, 0.f};
+        }
+      }
     }
   }
   // D: register i = channel i of the block's output quad, lane's column j = channel j of the slot's input quad
@@ -419,19 +477,77 @@ __device__ __forceinline__ void gc_wgrad(float* __restrict__ gw, const float* __
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int co = l.c0 + 4 * l.blk + i;
-      if (co < g.co) chain_store<GC_WT>(slab + ((int64_t)co * g.cgi + c0 + 4 * ciq + l.li) * rs + tap, acc[m][i]);
+      if (co < g.co)
+        chain_store<GC_WT>(slab + ((int64_t)co * g.cgi + c0 + 4 * ciq + l.li) * rs + tap, SQ ? sq[m][i] : acc[m][i]);
     }
   }
 }
 
 // the one grid of a backward launch: data-gradient blocks first, then the weight-gradient blocks
+template <bool AL, bool TWO>
+__global__ void __launch_bounds__(BLOCK)
+k_gc_backward(float* __restrict__ dx, float* __restrict__ gw, const float* __restrict__ ga, const float* __restrict__ ga1,
+              const float* __restrict__ x, const float* __restrict__ tx, int64_t ld, const float* __restrict__ W,
+              const float* __restrict__ V, int64_t slab_stride, int d_blocks, const GcPlan g) {
+  const int b = blockIdx.x;
+  if (b < d_blocks) gc_dgrad<AL, TWO>(dx, ga, ga1, W, V, g, b);
+  else gc_wgrad<AL, TWO, false>(gw, ga, ga1, x, tx, ld, slab_stride, 0.f, g, b - d_blocks);
+}
+
+// ---- squared sum: one workgroup per (split of the samples, pass, span of 64 output channels); g.per = samples per split
 template <bool AL>
 __global__ void __launch_bounds__(BLOCK)
-k_gc_backward(float* __restrict__ dx, float* __restrict__ gw, const float* __restrict__ ga, const float* __restrict__ x,
-              int64_t ld, const float* __restrict__ W, int64_t slab_stride, int d_blocks, const GcPlan g) {
-  const int b = blockIdx.x;
-  if (b < d_blocks) gc_dgrad<AL>(dx, ga, W, g, b);
-  else gc_wgrad<AL>(gw, ga, x, ld, slab_stride, g, b - d_blocks);
+k_gc_sqsum(float* __restrict__ out, const float* __restrict__ ga, const float* __restrict__ x, int64_t ld, float pre,
+           int64_t slab_stride, const GcPlan g) {
+  gc_wgrad<AL, false, true>(out, ga, nullptr, x, nullptr, ld, slab_stride, pre, g, blockIdx.x);
+}
+
+// The squared sum's plan: gc_plan, then the split of the SAMPLES towards `target` workgroups (0: GC_TARGET_BLOCKS).
+inline int gc_sq_plan(int64_t n, int64_t h, int64_t w, int64_t ci, int64_t co, int64_t groups, int64_t r, int64_t s,
+                      int64_t sh, int64_t sw, int64_t ph, int64_t pw, int target, GcPlan* p) {
+  if (target < 0 || gc_plan(n, h, w, ci, co, groups, r, s, sh, sw, ph, pw, p) != HF_OK) return HF_ERR_ARG;
+  const int64_t wg = (int64_t)p->ospans * p->passes;  // workgroups per split
+  int64_t want = ((target ? target : GC_TARGET_BLOCKS) + wg - 1) / wg;
+  if (want > GC_MAX_SPLITS) want = GC_MAX_SPLITS;
+  if (want > n) want = n;
+  const int64_t per = (n + want - 1) / want;
+  p->per = (int)per, p->splits_w = (int)((n + per - 1) / per);  // (no split without a sample)
+  return HF_OK;
+}
+
+// The backward launch of both forms.  terms == 1: ga1, tx and V are NULL; dx may be NULL (W is then not read).
+int gc_backward_launch(int terms, void* dx, void* gw_slabs, const void* ga, const void* ga1, const void* x, const void* tx,
+                       int64_t act_ld, const void* W, const void* V, int64_t n, int64_t h, int64_t w, int64_t c_in,
+                       int64_t c_out, int64_t groups, int64_t r, int64_t s, int64_t stride_h, int64_t stride_w,
+                       int64_t pad_h, int64_t pad_w, int splits_w, int64_t slab_stride, int dtype, void* stream) {
+  GcPlan p;
+  if (gc_plan(n, h, w, c_in, c_out, groups, r, s, stride_h, stride_w, pad_h, pad_w, &p) != HF_OK) return HF_ERR_ARG;
+  if (dtype != HF_F32 || !gw_slabs || !ga || !x) return HF_ERR_ARG;
+  if (terms == 2 && (!dx || !ga1 || !tx || !W || !V)) return HF_ERR_ARG;
+  if (dx && !W) return HF_ERR_ARG;
+  if (splits_w != p.splits_w) return HF_ERR_ARG;
+  if (splits_w > 1 && slab_stride < (int64_t)p.co * p.cgi * p.r * p.s) return HF_ERR_ARG;
+  if (act_ld == 0) act_ld = c_in;
+  if (act_ld < c_in || act_ld > 2 * c_in) return HF_ERR_ARG;
+  const bool al = quad_ok(x, act_ld) && aligned16(ga) && (terms == 1 || (quad_ok(tx, act_ld) && aligned16(ga1)));
+  const int d_blocks = dx ? p.n * p.d.tiles_y * p.dtiles_x * p.ispans : 0;
+  const unsigned grid = (unsigned)(d_blocks + p.ospans * p.passes * p.splits_w);
+  int64_t words = gc_lds_words(p.g, p.g.th * GC_TW);
+  if (dx && gc_lds_words(p.d, p.d.ck * p.r * p.s) > words) words = gc_lds_words(p.d, p.d.ck * p.r * p.s);
+  hipStream_t st = (hipStream_t)stream;
+#define HF_GC_B(AL, TWO)                                                                                               \
+  k_gc_backward<AL, TWO><<<grid, BLOCK, (size_t)words * 4, st>>>(                                                      \
+      (float*)dx, (float*)gw_slabs, (const float*)ga, (const float*)ga1, (const float*)x, (const float*)tx, act_ld,    \
+      (const float*)W, (const float*)V, slab_stride, d_blocks, p)
+  if (terms == 2) {
+    if (al) HF_GC_B(true, true);
+    else HF_GC_B(false, true);
+  } else {
+    if (al) HF_GC_B(true, false);
+    else HF_GC_B(false, false);
+  }
+#undef HF_GC_B
+  return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -481,28 +597,50 @@ int hf_gconv2d_nhwc_backward_slabs(void* dx, void* gw_slabs, const void* ga, con
                                    int64_t n, int64_t h, int64_t w, int64_t c_in, int64_t c_out, int64_t groups, int64_t r,
                                    int64_t s, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
                                    int splits_w, int64_t slab_stride, int dtype, void* stream) {
+  return gc_backward_launch(1, dx, gw_slabs, ga, nullptr, x, nullptr, act_ld, W, nullptr, n, h, w, c_in, c_out, groups, r, s,
+                            stride_h, stride_w, pad_h, pad_w, splits_w, slab_stride, dtype, stream);
+}
+
+int hf_gconv2d_nhwc_backward2_slabs(void* dx, void* gw_slabs, const void* ga_t, const void* ga, const void* x,
+                                    const void* t_x, int64_t act_ld, const void* W, const void* V, int64_t n, int64_t h,
+                                    int64_t w, int64_t c_in, int64_t c_out, int64_t groups, int64_t r, int64_t s,
+                                    int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int splits_w,
+                                    int64_t slab_stride, int dtype, void* stream) {
+  return gc_backward_launch(2, dx, gw_slabs, ga_t, ga, x, t_x, act_ld, W, V, n, h, w, c_in, c_out, groups, r, s, stride_h,
+                            stride_w, pad_h, pad_w, splits_w, slab_stride, dtype, stream);
+}
+
+int hf_gconv2d_nhwc_sqsum_plan(int64_t n, int64_t h, int64_t w, int64_t c_in, int64_t c_out, int64_t groups, int64_t r,
+                               int64_t s, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
+                               int target_blocks) {
   GcPlan p;
-  if (gc_plan(n, h, w, c_in, c_out, groups, r, s, stride_h, stride_w, pad_h, pad_w, &p) != HF_OK) return HF_ERR_ARG;
-  if (dtype != HF_F32 || !gw_slabs || !ga || !x) return HF_ERR_ARG;
-  if (dx && !W) return HF_ERR_ARG;
-  if (splits_w != p.splits_w) return HF_ERR_ARG;
-  if (splits_w > 1 && slab_stride < (int64_t)p.co * p.cgi * p.r * p.s) return HF_ERR_ARG;
+  if (gc_sq_plan(n, h, w, c_in, c_out, groups, r, s, stride_h, stride_w, pad_h, pad_w, target_blocks, &p) != HF_OK)
+    return HF_ERR_ARG;
+  return p.splits_w;
+}
+
+int hf_gconv2d_nhwc_sqsum_slabs(void* out, const void* ga, const void* x, int64_t act_ld, int64_t n, int64_t h, int64_t w,
+                                int64_t c_in, int64_t c_out, int64_t groups, int64_t r, int64_t s, int64_t stride_h,
+                                int64_t stride_w, int64_t pad_h, int64_t pad_w, float pre, int splits, int64_t slab_stride,
+                                int dtype, void* stream) {
+  GcPlan p;
+  if (gc_sq_plan(n, h, w, c_in, c_out, groups, r, s, stride_h, stride_w, pad_h, pad_w, 0, &p) != HF_OK) return HF_ERR_ARG;
+  if (dtype != HF_F32 || !out || !ga || !x) return HF_ERR_ARG;
+  if (!(pre - pre == 0.f)) return HF_ERR_ARG;  // (NaN / infinity)
+  if (splits < 1 || splits > n) return HF_ERR_ARG;
+  const int per = (int)((n + splits - 1) / splits);
+  if ((int64_t)(splits - 1) * per >= n) return HF_ERR_ARG;  // (a split without a sample)
+  if (splits > 1 && slab_stride < (int64_t)p.co * p.cgi * p.r * p.s) return HF_ERR_ARG;
   if (act_ld == 0) act_ld = c_in;
   if (act_ld < c_in || act_ld > 2 * c_in) return HF_ERR_ARG;
-  const bool al = quad_ok(x, act_ld) && aligned16(ga);
-  const int d_blocks = dx ? p.n * p.d.tiles_y * p.dtiles_x * p.ispans : 0;
-  const unsigned grid = (unsigned)(d_blocks + p.ospans * p.passes * p.splits_w);
-  int64_t words = gc_lds_words(p.g, p.g.th * GC_TW);
-  if (dx && gc_lds_words(p.d, p.d.ck * p.r * p.s) > words) words = gc_lds_words(p.d, p.d.ck * p.r * p.s);
+  p.per = per, p.splits_w = splits;
+  const unsigned grid = (unsigned)((int64_t)p.ospans * p.passes * splits);
+  const size_t lds = (size_t)gc_lds_words(p.g, p.g.th * GC_TW) * 4;
   hipStream_t st = (hipStream_t)stream;
-  if (al)
-    k_gc_backward<true><<<grid, BLOCK, (size_t)words * 4, st>>>((float*)dx, (float*)gw_slabs, (const float*)ga,
-                                                                (const float*)x, act_ld, (const float*)W, slab_stride,
-                                                                d_blocks, p);
+  if (quad_ok(x, act_ld) && aligned16(ga))
+    k_gc_sqsum<true><<<grid, BLOCK, lds, st>>>((float*)out, (const float*)ga, (const float*)x, act_ld, pre, slab_stride, p);
   else
-    k_gc_backward<false><<<grid, BLOCK, (size_t)words * 4, st>>>((float*)dx, (float*)gw_slabs, (const float*)ga,
-                                                                 (const float*)x, act_ld, (const float*)W, slab_stride,
-                                                                 d_blocks, p);
+    k_gc_sqsum<false><<<grid, BLOCK, lds, st>>>((float*)out, (const float*)ga, (const float*)x, act_ld, pre, slab_stride, p);
   return (int)hipGetLastError();
 }
 

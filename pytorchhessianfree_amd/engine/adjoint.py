@@ -45,8 +45,8 @@ class _AdjointSweep:
             # a bias has no second-order term of its own: the convolutions read g_a itself.  (The chain's D + W launch
             # through the two-problem entry point -- the same pair of problems ``_conv_adjoint`` launches --, and in
             # sequence the extras BEHIND it: as the plain stack has always issued them)
-            if u.depthwise:
-                self._dw_second_order(u, u.ga)
+            if u.in_place:
+                self._in_place_second_order(u, u.ga)
             elif not u.im2col and not u.first and u.sD:  # (sD == 0, a tangent-free input: the weight gradient alone)
                 self._launch("hf_conv2d_nhwc_dw_slabs", *([q] for q in self._dw_problems(u, u.ga)))
             else:
@@ -74,26 +74,26 @@ class _AdjointSweep:
             self._launch("hf_chan_affine_ex", *affine_args(problem(
                 _lib.AffineProblem, out=u.gah, a=u.g1, rstd=u.rstd, w=v_gamma, add=u.ga, n=n, c=k, hw=oh * ow,
                 a_splits=1)))
-        if u.depthwise:
-            self._dw_second_order(u, u.gah)
+        if u.in_place:
+            self._in_place_second_order(u, u.gah)
         elif self._extras_mode == 2 and not u.im2col and not u.first and u.sD:
             # the chain's launch also computes conv_D(g_a, V) -- the one extra term the chain itself needs next
             self._launch("hf_conv2d_nhwc_group_slabs", [*self._dw_problems(u, u.gah), self._dgrad_extra(u)], 3)
         else:
             self._conv_adjoint(u, u.gah)
 
-    def _dw_second_order(self, u, ga_t):
-        """The tangent of the backward sweep through a depthwise unit from ``ga_t`` (the tangent of the convolution
-        output's cotangent) in ONE launch:  dx = D(ga_t, W) + D(g_a, V),  slabs = W(x, ga_t) + W(t_x, g_a)  -- g_a: the
-        step's first-order cotangent ``u.ga1``, t_x / x: the halves of the producer's operand, V: the vector's slice in
+    def _in_place_second_order(self, u, ga_t):
+        """The tangent of the backward sweep through a depthwise or grouped unit from ``ga_t`` (the tangent of the
+        convolution output's cotangent) in ONE launch:  dx = D(ga_t, W) + D(g_a, V),  slabs = W(x, ga_t) + W(t_x, g_a)
+        -- g_a: the step's first-order cotangent ``u.ga1``, t_x / x: the halves of the producer's operand, V: the vector's slice in
         place.  Where a term vanishes (a frozen weight: no V, its slabs are not gathered; a tangent-free input: t_x = 0
         and no dx) the one-term launch is the whole of it."""
         if not u.two_term:
             self._conv_adjoint(u, ga_t)
             return
         c = u.geo.c
-        self._dwconv(u, u.xcat[:, c:], 2 * c, ga=ga_t, ga1=u.ga1, t_x=u.xcat[:, :c],
-                     v=self._param_slice(self._v, u.pw, u.conv.weight.numel()), dx=u.dbuf, slabs=u.wbuf, splits=u.nW)
+        self._in_place_conv(u, u.xcat[:, c:], 2 * c, ga=ga_t, ga1=u.ga1, t_x=u.xcat[:, :c],
+                            v=self._param_slice(self._v, u.pw, u.conv.weight.numel()), dx=u.dbuf, slabs=u.wbuf, splits=u.nW)
 
     def _dslabs(self, u):
         """How many data-gradient slabs the consumers of ``u``'s input cotangent must sum in the current sweep."""

@@ -184,12 +184,13 @@ class _Buffers:
             # the consumers sum anyway
             u.nW = u.sW * (2 if (self.hessian and not u.first) else 1)
             u.nD = u.sD * (2 if self.hessian else 1)
-            if u.depthwise:
-                # no extras slabs: the second-order backward is ONE two-term launch (hf_dwconv2d_nhwc_backward2_slabs) that
-                # leaves one data-gradient slab and its own plan's count of weight-gradient slabs -- where a term vanishes
-                # (frozen weight, tangent-free input) the one-term launch and its count
+            if u.in_place:
+                # no extras slabs: the second-order backward is ONE two-term launch (hf_dwconv2d_nhwc_backward2_slabs /
+                # hf_gconv2d_nhwc_backward2_slabs) that leaves one data-gradient slab and -- depthwise -- its own plan's count
+                # of weight-gradient slabs, or -- grouped -- the one-term count; where a term vanishes (frozen weight,
+                # tangent-free input) the one-term launch and its count
                 u.two_term = self.hessian and u.pw is not None and bool(u.sD)
-                u.nW = self._plan_depthwise(u.geo, u.name, terms=2) if u.two_term else u.sW
+                u.nW = self._plan_depthwise(u.geo, u.name, terms=2) if u.two_term and u.depthwise else u.sW
                 u.nD = u.sD
             u.wbuf = torch.zeros((max(u.nW, u.sW), u.conv.weight.numel()), dtype=f32, device=dev)  # dead taps stay 0
             if u.sD:

@@ -38,10 +38,6 @@ class _ConvEngine(_Buffers, _Forward, _TangentSweep, _AdjointSweep, _HessianExtr
         self._extras_allowed = True  # (False: the caller runs this engine on one of several parallel capture branches)
         self._layout(model)
         self.diag_batched_declined = None  # (why ``diag_ef`` keeps the per-sample route although the batched one is on)
-        if self._diag_batched and any(u.grouped for u in self.units):
-            self._diag_batched = False
-            self.diag_batched_declined = ("a grouped unit has no squared-sum kernel: diag_ef runs its per-sample weight-"
-                                          "gradient launches")
         if self.hessian:
             for u in self.units:
                 u.needs_g = True  # (the first-order masked cotangent of every unit is kept)

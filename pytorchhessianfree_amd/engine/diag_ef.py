@@ -6,7 +6,7 @@ Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overal
 import torch
 
 from .. import _lib
-from .problems import chan_sqsum_args, conv_sqsum_args, dwconv_sqsum_args
+from .problems import chan_sqsum_args, conv_sqsum_args, dwconv_sqsum_args, gconv_dims, gconv_sqsum_args
 
 
 class _DiagEF:
@@ -21,7 +21,8 @@ class _DiagEF:
         the reference carries it whole) enters in closed form: sum (a_i + b)^2 = sum a_i^2 + 2 b sum a_i + N b^2.
 
         ``HF_DIAG_EF_BATCHED=1`` (read when the engine is built): instead of the per-sample launches, per unit ONE
-        ``hf_conv2d_nhwc_sqsum_slabs`` (a depthwise unit: ``hf_dwconv2d_nhwc_sqsum_slabs``) on the whole-batch operands (it
+        ``hf_conv2d_nhwc_sqsum_slabs`` (a depthwise unit: ``hf_dwconv2d_nhwc_sqsum_slabs``, a grouped one:
+        ``hf_gconv2d_nhwc_sqsum_slabs``) on the whole-batch operands (it
         squares and sums the per-sample weight gradients inside the launch: BackPACK's ``SumGradSquared``), ONE
         ``hf_chan_sqsum`` for the BatchNorm / bias entries, and ONE plain gather (``hf_pack_ex`` mode 0) for all of them -- a number of launches that does not depend on the
         batch.  The factor that undoes the loss's 1/N goes into the launches (``pre``: applied before squaring)."""
@@ -93,6 +94,9 @@ class _DiagEF:
             ga = u.ga1 if first_order else u.ga
             if u.pw is not None and u.depthwise:  # (slabs in parameter order: no permutation in the gather)
                 self._launch("hf_dwconv2d_nhwc_sqsum_slabs", *dwconv_sqsum_args(u.wps, ga, u.x, u.geo.c, u.geo1, u.sW1, pre))
+            elif u.pw is not None and u.grouped:  # (likewise)
+                self._launch("hf_gconv2d_nhwc_sqsum_slabs",
+                             *gconv_sqsum_args(u.wps, ga, u.x, u.geo.c, u.geo1, u.conv.groups, u.sW1, pre))
             elif u.pw is not None:
                 act = u.cols_pad if u.im2col else u.x
                 self._launch("hf_conv2d_nhwc_sqsum_slabs",
@@ -129,6 +133,9 @@ class _DiagEF:
                 if u.depthwise:  # (its own squared-sum kernel and plan: hf_dwconv.hip)
                     g = u.geo1
                     u.sW1 = _lib.dwconv_sqsum_plan(g.n, g.h, g.w, g.c, g.r, g.s, g.stride, g.padding)
+                elif u.grouped:  # (likewise: hf_gconv.hip)
+                    d = gconv_dims(u.geo1, u.conv.groups)
+                    u.sW1 = _lib.gconv_sqsum_plan(*d[:8], d[8:10], d[10:])
                 else:
                     u.sW1 = _lib.conv_sqsum_plan(*u.geo1)
                 # shares of the samples for the channel sums: ~one workgroup per CU (64 channels each), none empty

@@ -18,7 +18,7 @@ class _HessianExtras:
             return
         if u.bn is not None and not u.train:  # (train mode: the tangent sweep left this sum, engine/tangent.py)
             self._scale_second_order_sum(u)
-        if u.depthwise:  # (both terms ride in the chain's own two-term launch: adjoint._dw_second_order)
+        if u.in_place:  # (both terms ride in the chain's own two-term launch: adjoint._in_place_second_order)
             return
         if not u.im2col and not u.first and u.sD:  # (u.sD == 0: a tangent-free input -- both terms vanish)
             # conv_W(t_x, g_a): t_x read in place, the first half of the [t_x | x] operand
@@ -66,7 +66,7 @@ class _HessianExtras:
         with torch.cuda.stream(self._xside):
             for u in reversed(self.units):
                 self._hessian_extras(u)
-                if self._extras_mode == 1 and getattr(u, "sD", 0) and not u.im2col and not u.first and not u.depthwise:
+                if self._extras_mode == 1 and getattr(u, "sD", 0) and not u.im2col and not u.first and not u.in_place:
                     ev = self._xev[id(u)]
                     ev.record(self._xside)
                     self._xwait[u.dbuf.data_ptr()] = ev

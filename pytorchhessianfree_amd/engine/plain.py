@@ -70,8 +70,12 @@ class PlainStackEngine(_ConvEngine):
     bias / BatchNorm / ReLU / max-pool behind it.  The kernels of hf_gconv.hip (``v_mfma_f32_4x4x1_16b_f32``: 4 pixels x 64
     channels per issue, each of the 16 blocks a channel quad on its own group) follow the depthwise conventions -- weight
     and V in place, one slab per direction, slabs in parameter order: ``hf_gconv2d_nhwc_tangent`` and
-    ``hf_gconv2d_nhwc_backward_slabs``.  GGN products, one process; ``diag_ef`` by per-sample launches.  Opt-in: its speed
-    against the autograd route is not measured."""
+    ``hf_gconv2d_nhwc_backward_slabs``.  One process.  Hessian products on top (``HF_GROUP_HESSIAN=1``; bias, eval- and
+    train-mode BatchNorm units): the second-order backward is ONE launch, ``hf_gconv2d_nhwc_backward2_slabs``, its two terms
+    one after the other through the one-term launch's staging area -- the same plan and slab count, no extras slabs
+    (``nD = sD``, ``nW = sW``); a frozen weight or a tangent-free input keeps the one-term launch.  With
+    ``HF_DIAG_EF_BATCHED=1`` its weight entries of ``diag_ef`` come from ONE ``hf_gconv2d_nhwc_sqsum_slabs`` launch on the
+    whole batch.  All of it opt-in: against the autograd route only ``diag_ef`` is measured, no product."""
 
     mode = ("fused curvature engine (plain conv-ReLU stack): own deterministic convolutions (split-K slabs summed "
             "by the consumer kernel), bias / ReLU / max-pool fused, 4 launches per layer")
@@ -232,7 +236,7 @@ class PlainStackEngine(_ConvEngine):
     def _layout_grouped(self, m, name, first):
         """What any other grouped ``Conv2d`` must be to become a grouped unit (the kernels of hf_gconv.hip): opted in,
         group widths that are multiples of 4 up to 64 on both sides, zero padding, at most 49 taps, behind a unit that fills
-        its ``[t_x | x]`` operand; one process; GGN products."""
+        its ``[t_x | x]`` operand; one process; Hessian products only with ``HF_GROUP_HESSIAN=1``."""
         cgi, cgo, (r, s) = m.in_channels // m.groups, m.out_channels // m.groups, m.kernel_size
         what = f"{name}: groups = {m.groups} with {m.in_channels} -> {m.out_channels} channels"
         if cgi == 1 or os.environ.get("HF_GROUP_ENGINE", "0") != "1":
@@ -246,8 +250,9 @@ class PlainStackEngine(_ConvEngine):
             raise _Unsupported(f"{name}: grouped with {r * s} taps (the kernels take up to 49)")
         if first:
             raise _Unsupported(f"{name}: a grouped first layer is not covered (its input has no [t_x | x] operand)")
-        if self.hessian:
-            raise _Unsupported(f"{name}: Hessian products through a grouped convolution are not covered")
+        if self.hessian and os.environ.get("HF_GROUP_HESSIAN", "0") != "1":
+            raise _Unsupported(f"{name}: Hessian products through a grouped convolution are not covered (opt-in on top "
+                               "of HF_GROUP_ENGINE=1: HF_GROUP_HESSIAN=1)")
         if self.group is not None:
             raise _Unsupported(f"{name}: data parallelism is not covered for a grouped convolution")
 

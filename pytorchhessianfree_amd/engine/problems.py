@@ -191,17 +191,21 @@ def dwconv_sqsum_args(out, ga, x, act_ld, geo, splits, pre):
 
 
 # ---- grouped convolutions (hf_gconv.hip): the depthwise pair's conventions, with the group count ---------------------
-GConvProblem = namedtuple("GConvProblem", "geo groups x act_ld w out t_x v ga dx slabs splits")
+GConvProblem = namedtuple("GConvProblem", "geo groups x act_ld w out t_x v ga ga1 dx slabs splits")
 
 
-def gconv_problem(geo, groups, x, act_ld, w, out=None, t_x=None, v=None, ga=None, dx=None, slabs=None, splits=0):
+def gconv_problem(geo, groups, x, act_ld, w, out=None, t_x=None, v=None, ga=None, ga1=None, dx=None, slabs=None, splits=0):
     """A grouped layer ``geo`` (``c`` -> ``k`` channels in ``groups`` groups) on the input ``x`` at pixel pitch ``act_ld`` and
     the weight ``w`` [k, c / groups, r, s] read in place.  With ``out``: ``out = conv(t_x, w) + conv(x, v)`` -- ``t_x`` (same
     pitch) or ``v`` (the CG vector's slice) may be None, not both; the forward pass is ``v = w`` alone.  With ``ga``: the data
-    gradient -> ``dx`` (None: not needed) and the weight gradient -> ``slabs`` [splits, k*(c/groups)*r*s], one launch."""
+    gradient -> ``dx`` (None: not needed) and the weight gradient -> ``slabs`` [splits, k*(c/groups)*r*s], one launch.  With
+    ``ga`` AND ``ga1`` (the step's first-order cotangent; ``ga`` is then its tangent): ``dx = D(ga, w) + D(ga1, v)``,
+    ``slabs = W(x, ga) + W(t_x, ga1)``, one launch -- ``t_x``, ``v`` and ``dx`` are all needed, ``splits`` is the same count."""
     if geo.c % groups or geo.k % groups or (out is None) == (ga is None):
         raise RuntimeError("gconv_problem: channel counts that are multiples of the groups, and either an output or a cotangent")
-    return GConvProblem(geo, int(groups), x, act_ld, w, out, t_x, v, ga, dx, slabs, int(splits))
+    if ga1 is not None and (ga is None or t_x is None or v is None or dx is None):
+        raise RuntimeError("gconv_problem: the two-term backward needs both cotangents, t_x, v and dx")
+    return GConvProblem(geo, int(groups), x, act_ld, w, out, t_x, v, ga, ga1, dx, slabs, int(splits))
 
 
 def gconv_dims(geo, groups):
@@ -211,13 +215,24 @@ def gconv_dims(geo, groups):
 
 
 def gconv_args(q):
-    """The entry point's name, then its arguments: ``hf_gconv2d_nhwc_tangent`` or ``hf_gconv2d_nhwc_backward_slabs``."""
+    """The entry point's name, then its arguments: ``hf_gconv2d_nhwc_tangent``, ``hf_gconv2d_nhwc_backward_slabs`` or
+    ``hf_gconv2d_nhwc_backward2_slabs``."""
     dims = gconv_dims(q.geo, q.groups)
     if q.ga is None:
         return ("hf_gconv2d_nhwc_tangent", q.out, q.t_x, q.x if q.v is not None else None, q.act_ld,
                 q.w if q.t_x is not None else None, q.v, *dims)
+    if q.ga1 is not None:
+        return ("hf_gconv2d_nhwc_backward2_slabs", q.dx, q.slabs, q.ga, q.ga1, q.x, q.t_x, q.act_ld, q.w, q.v, *dims,
+                q.splits, q.slabs.shape[1])
     return ("hf_gconv2d_nhwc_backward_slabs", q.dx, q.slabs, q.ga, q.x, q.act_ld, q.w if q.dx is not None else None,
             *dims, q.splits, q.slabs.shape[1])
+
+
+def gconv_sqsum_args(out, ga, x, act_ld, geo, groups, splits, pre):
+    """``hf_gconv2d_nhwc_sqsum_slabs``: ``out`` [splits, k*(c/groups)*r*s] receives split s's partial sum over its samples of
+    the squared per-sample weight gradient of the grouped layer ``geo`` (``x`` at pixel pitch ``act_ld``, cotangent ``ga``),
+    each scaled by ``pre`` before it is squared; parameter order."""
+    return (out, ga, x, act_ld, *gconv_dims(geo, groups), float(pre), int(splits), out.shape[1])
 
 
 # ---- the squared-sum launches of the batched diagonal empirical Fisher (positional entry points, no struct) ------------

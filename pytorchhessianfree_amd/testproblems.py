@@ -313,6 +313,24 @@ class GroupSmall(nn.Module):
         return torch.flatten(_batched(self.net, x), -3)
 
 
+class GroupStack(nn.Module):
+    """A ResNeXt-style plain stack (no shortcuts) for 32x32 inputs: conv3(3->64, pad 1) ReLU, then three bottleneck units
+    ``conv1(c->w) ReLU, g3x3(w->w, groups of 16 channels, pad 1) ReLU, conv1(w->w) ReLU`` of width 128 (stride 1), 256
+    (stride 2) and 256 (stride 2) -- 32x32, 16x16, 8x8 maps --, conv1(256->classes), global average pool."""
+
+    def __init__(self, num_classes=12):
+        super().__init__()
+        layers, c = [nn.Conv2d(3, 64, 3, 1, 1), nn.ReLU()], 64
+        for w, stride in ((128, 1), (256, 2), (256, 2)):
+            layers += [nn.Conv2d(c, w, 1), nn.ReLU(), nn.Conv2d(w, w, 3, stride, 1, groups=w // 16), nn.ReLU(),
+                       nn.Conv2d(w, w, 1), nn.ReLU()]
+            c = w
+        self.net = nn.Sequential(*layers, nn.Conv2d(c, num_classes, 1), nn.AdaptiveAvgPool2d((1, 1)))
+
+    def forward(self, x):
+        return torch.flatten(_batched(self.net, x), -3)
+
+
 class VGG11BN(nn.Module):
     """VGG-11 with BatchNorm for 32x32 inputs (the usual CIFAR form): conv3 + BN + ReLU units of 64, 128, 256, 256, 512,
     512, 512, 512 channels, a MaxPool(2, 2) behind units 1, 2, 4, 6 and 8 (32 -> 1), ``Flatten``, ``Linear(512->classes)``.
@@ -528,6 +546,16 @@ def group_small(batch_size=3, seed=0, device="cpu", data_seed=None, bn=False):
     model = seed_batchnorm(GroupSmall(12, bn), seed).eval()
     g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
     inputs = torch.rand(batch_size, 3, 9, 7, generator=g)
+    targets = torch.randint(0, 12, (batch_size,), generator=g)
+    return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
+
+
+def group_stack_cifar(batch_size=32, seed=0, device="cpu", data_seed=None):
+    """``GroupStack`` in eval mode; inputs U[0,1) [B,3,32,32], 12 classes, CE-mean."""
+    torch.manual_seed(seed)
+    model = GroupStack(12).eval()
+    g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
+    inputs = torch.rand(batch_size, 3, 32, 32, generator=g)
     targets = torch.randint(0, 12, (batch_size,), generator=g)
     return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
 

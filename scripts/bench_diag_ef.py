@@ -5,7 +5,8 @@ weight-gradient launches and one squaring gather per sample -- and on -- one squ
 
     python scripts/bench_diag_ef.py [--out profiles/<round>_diag_ef_batched.jsonl]
 
-Configurations: ResNet-18 on MNIST shapes at batch 32, All-CNN-C (CIFAR-100 shapes) at batch 32 and at batch 128.  One
+Configurations: ResNet-18 on MNIST shapes at batch 32, All-CNN-C (CIFAR-100 shapes) at batch 32 and at batch 128, and a
+plain stack with grouped 3x3 layers of width 16 on 32x32 inputs at batch 32 (its children run with ``HF_GROUP_ENGINE=1``).  One
 child process per (configuration, switch), the two switches ALTERNATING, ``--rounds`` times over, so that both routes see
 the same state of the machine.  A child builds the model, takes one ``step()`` (which leaves the persistent session at that
 batch), warms the replay up ``--warmup`` times and times ``--reps`` (>= 5) replays, each with its final synchronisation;
@@ -31,7 +32,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 CONFIGS = {"resnet18_b32": ("resnet18_mnist", 32), "allcnnc_b32": ("allcnnc_cifar100", 32),
-           "allcnnc_b128": ("allcnnc_cifar100", 128)}
+           "allcnnc_b128": ("allcnnc_cifar100", 128),
+           "groupstack_b32": ("group_stack_cifar", 32)}
+ENV = {"groupstack_b32": {"HF_GROUP_ENGINE": "1"}}  # (what a configuration's children need besides the switch: opt-in units)
 SWITCH = "HF_DIAG_EF_BATCHED"
 
 
@@ -119,7 +122,7 @@ def split_sweep(config, reps, out):
     eng = opt._session.engine
     eng.diag_ef(eng.loss_spec["reduction"])  # (cotangents and the sweep's geometry)
     for u in eng.units:
-        if u.dead or u.pw is None:
+        if u.dead or u.pw is None or u.in_place:  # (depthwise / grouped units: kernels and plans of their own)
             continue
         n, h, w, c, k, r, s, st, pd = u.geo1
         act, ga = (u.cols_pad if u.im2col else u.x), (u.ga1 if eng.hessian else u.ga)
@@ -202,7 +205,7 @@ def main():
         for rnd in range(args.rounds):
             for switch in ("0", "1"):
                 p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", config, "--warmup",
-                                    str(args.warmup), "--reps", str(args.reps)], env=dict(os.environ, **{SWITCH: switch}),
+                                    str(args.warmup), "--reps", str(args.reps)], env=dict(os.environ, **ENV.get(config, {}), **{SWITCH: switch}),
                                    capture_output=True, text=True, timeout=600)
                 if p.returncode != 0:
                     sys.stderr.write(p.stderr[-3000:])
