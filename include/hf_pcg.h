@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 30
+#define HF_ABI_VERSION 31
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -1053,6 +1053,60 @@ int hf_dense_act_forward(void* y, const void* slabs, int splits, int64_t slab_st
 int hf_dense_loss_head(int kind, const void* logits, const void* targets, void* p, void* dl, void* dl_ps, void* loss,
                        void* flag, void* work, double scale_g, double scale_ps, double coef, int64_t rows, int64_t c,
                        int dtype, void* stream);
+
+/* ---- fully-connected layers on TALL batches (hf_dense_tall.hip, ABI 31) ---------------- */
+/*
+ * The same sweeps for 257 <= rows <= 8192 (rows * c_in, rows * c_out and c_out * c_in < 2^31: the kernels index with
+ * `int`), as LDS-tiled fp32 MFMA GEMMs: a 256-thread workgroup owns a 128 x 128 output tile (4 waves x 2 x 2 tiles of
+ * v_mfma_f32_32x32x2f32), the reduction runs in steps of 16 through two LDS stages.  Contract of the hf_dense_* siblings:
+ * operands read IN PLACE, 4-byte alignment suffices, ragged sizes, the 16-byte forms chosen on the host, nothing outside
+ * rows x c is read or written, no atomics, bitwise repeatable, HF_F32 only; anything else is refused with HF_ERR_ARG
+ * before any launch.  The hf_dense_* entry points keep their own range (rows <= 256); these refuse rows <= 256.
+ *
+ * Splits: a reduction of `len` entries accepts 1 <= splits <= 32 with (splits - 1) * kper < len, kper =
+ * ceil(ceil(len / splits) / 16) * 16.  hf_dense_tall_plan returns the counts the engine uses (about 512 workgroups per
+ * launch: splits_t over c_in, splits_d over c_out, splits_w over the rows) and `row_blocks`, the number of row blocks of
+ * the two row reductions over [rows, c_out]; one host function is the definition, every launching entry point runs it.
+ *
+ * Rounding.  A slab entry is ONE fmaf-like chain of the MFMA over its split's range, entries ascending in pairs; the
+ * two-term forms of T and D add, per pair, first the first term's products (t_x W; g_a W), then the second's (x V; g V).
+ *   hf_dense_tall_tangent_slabs: arguments and meaning of hf_dense_tangent_slabs.
+ *   hf_dense_tall_dgrad_slabs:   out_slabs[s][r][i] = sum over split s's share of c_out of g_a[r][o] W[o][i]
+ *                                (+ g[r][o] V[o][i] where g and V are given: both or neither).
+ *   hf_dense_tall_wgrad:         out[o][i] = scale * sum_r g1[r][o] x1[r][i]  (mode 0);  both operands squared once after
+ *                                their load (mode 1: the diagonal of the empirical Fisher);  + sum_r g2[r][o] x2[r][i]
+ *                                (mode 2: each pair has a chain of its own, the chains are added once).  splits == 1: the
+ *                                sum is multiplied by `scale` (rounded to fp32) and written to `out`; ws may be NULL.
+ *                                splits > 1: split s's sum goes to ws + s * c_out * c_in (`splits` such slabs, floats); a
+ *                                second launch adds slab 0, then slabs 1 .. splits-1 in split order, multiplies by `scale`
+ *                                and writes `out`.
+ *   hf_dense_tall_act_forward / hf_dense_tall_act_tangent: hf_dense_act_forward / hf_dense_act_tangent (the same kernels).
+ *   hf_dense_tall_act_adjoint:   g_a as hf_dense_act_adjoint2 computes it (t_y and h: both or neither; the curvature term
+ *                                enters for tanh only).  g_b_out (nullable): row block b (consecutive rows, as the plan divides them) leaves one fp64 partial per column in
+ *                                ws[b][col] (`row_blocks * c` doubles, 8-byte aligned; required with g_b_out) -- four
+ *                                fp64 chains over every fourth row of the block, ascending, joined as ((s0 + s1) + s2) + s3
+ *                                --; a second launch adds the partials in ascending block order in fp64, rounds to fp32
+ *                                once, then multiplies by `scale` rounded to fp32.
+ *   hf_dense_tall_sq_colsum:     out[j] = scale * sum_r g_a[r][j]^2 by the same two launches (squares exact in fp64).
+ */
+int hf_dense_tall_plan(int64_t rows, int64_t c_in, int64_t c_out, int* splits_t, int* splits_d, int* splits_w,
+                       int* row_blocks);
+int hf_dense_tall_tangent_slabs(void* out_slabs, const void* t_x, const void* x, const void* W, const void* V,
+                                int64_t rows, int64_t c_in, int64_t c_out, int64_t ld_x, int splits, int64_t slab_stride,
+                                int dtype, void* stream);
+int hf_dense_tall_dgrad_slabs(void* out_slabs, const void* g_a, const void* W, const void* g, const void* V, int64_t rows,
+                              int64_t c_in, int64_t c_out, int splits, int64_t slab_stride, int dtype, void* stream);
+int hf_dense_tall_wgrad(void* out, void* ws, const void* g1, const void* x1, const void* g2, const void* x2, int64_t rows,
+                        int64_t c_in, int64_t c_out, int mode, double scale, int splits, int dtype, void* stream);
+int hf_dense_tall_act_forward(void* y, const void* slabs, int splits, int64_t slab_stride, const void* b, int act,
+                              int64_t rows, int64_t c, int dtype, void* stream);
+int hf_dense_tall_act_tangent(void* t_y, const void* slabs, int splits, int64_t slab_stride, const void* v_b,
+                              const void* y, int act, int64_t rows, int64_t c, int dtype, void* stream);
+int hf_dense_tall_act_adjoint(void* g_a, void* g_b_out, void* ws, const void* slabs, int splits, int64_t slab_stride,
+                              const void* y, int act, const void* t_y, const void* h, int64_t rows, int64_t c,
+                              double scale, int dtype, void* stream);
+int hf_dense_tall_sq_colsum(void* out, void* ws, const void* g_a, int64_t rows, int64_t c, double scale, int dtype,
+                            void* stream);
 
 /* ---- depthwise convolutions inside the GGN product (hf_dwconv.hip) ---------------- */
 /*

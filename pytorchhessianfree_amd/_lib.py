@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HF_PCG_LIB") or os.path.join(_HERE, "csrc", "libhfpcg.so")
 
 HF_F32, HF_F64 = 0, 1
-ABI_VERSION = 30
+ABI_VERSION = 31
 HF_ERR_ARG = -1  # hf_status of include/hf_pcg.h: null / negative / inconsistent argument
 HF_M_NONE, HF_M_DIAG, HF_M_EXTERNAL = 0, 1, 2
 REASONS = {
@@ -219,6 +219,17 @@ SIGNATURES = {
                                       c_int64, c_int64, c_double, c_int, c_void_p]),
     "hf_dense_act_forward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int64, c_int,
                                      c_void_p]),
+    "hf_dense_tall_plan": (c_int, [c_int64, c_int64, c_int64] + [ctypes.POINTER(c_int)] * 4),
+    "hf_dense_tall_tangent_slabs": (c_int, [c_void_p] * 5 + [c_int64] * 4 + [c_int, c_int64, c_int, c_void_p]),
+    "hf_dense_tall_dgrad_slabs": (c_int, [c_void_p] * 5 + [c_int64] * 3 + [c_int, c_int64, c_int, c_void_p]),
+    "hf_dense_tall_wgrad": (c_int, [c_void_p] * 6 + [c_int64] * 3 + [c_int, c_double, c_int, c_int, c_void_p]),
+    "hf_dense_tall_act_forward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int64, c_int,
+                                          c_void_p]),
+    "hf_dense_tall_act_tangent": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_int64, c_int64,
+                                          c_int, c_void_p]),
+    "hf_dense_tall_act_adjoint": (c_int, [c_void_p] * 4 + [c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                                          c_int64, c_double, c_int, c_void_p]),
+    "hf_dense_tall_sq_colsum": (c_int, [c_void_p] * 3 + [c_int64] * 2 + [c_double, c_int, c_void_p]),
     "hf_dense_loss_head": (c_int, [c_int] + [c_void_p] * 8 + [c_double] * 3 + [c_int64, c_int64, c_int, c_void_p]),
     "hf_dwconv2d_nhwc_plan": (c_int, [c_int64] * 10),
     "hf_dwconv2d_nhwc_tangent": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p] + [c_int64] * 10

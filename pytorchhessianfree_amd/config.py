@@ -132,6 +132,11 @@ SWITCHES = {
                          "runs on a persistent session of the dense-stack engine (forward pass, loss head, gradient "
                          "and trial losses as graph replays) instead of engine-graphed",
                          "tests/test_dense_session_engine_gpu.py::test_switch_and_declines"),
+    "HF_DENSE_TALL": ("0", "1: with HF_DENSE_ENGINE=1, prepared MLPs at batches of 257 .. 8192 rows take the dense-stack engine "
+                      "on the LDS-tiled GEMMs of hf_dense_tall.hip (GGN / Hessian products, gradient, diag_ef; no session) "
+                      "instead of the autograd path; batches up to 256 rows keep the skinny kernels.  Measured SLOWER than the "
+                      "hipGraph-replayed autograd sweeps (0.76-0.80 x their matvecs/s, DESIGN.md section 6.3), hence opt-in",
+                      "tests/test_dense_tall_engine_gpu.py::test_products_gradient_and_diag_ef_against_float64"),
     "HF_ENGINE_VERIFY": ("first", "always / never: the engine's first-use check against the autograd product",
                          "tests/test_engine_gpu.py::test_train_mode_prologue_form_variants_agree_and_state_is_independent_of_the_first_use_check"),
     "HF_ENGINE_DEBUG": ("", "1: say why a model was not taken by the engine",

@@ -11,11 +11,12 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 # one translation unit per kernel family: PCG solver | gather / scatter | BatchNorm / bias maps | convolutions |
-# pooling + classifier heads | fully-connected layers | depthwise convolutions | grouped convolutions | the RCCL shim
+# pooling + classifier heads | fully-connected layers (batches <= 256 rows | taller ones) | depthwise convolutions |
+# grouped convolutions | the RCCL shim
 SOURCES = [os.path.join(HERE, f) for f in ("hf_pcg.hip", "hf_pack.hip", "hf_bn.hip", "hf_conv.hip", "hf_head.hip",
-                                           "hf_dense.hip", "hf_dwconv.hip", "hf_gconv.hip", "hf_rccl.hip")]
+                                           "hf_dense.hip", "hf_dense_tall.hip", "hf_dwconv.hip", "hf_gconv.hip", "hf_rccl.hip")]
 HDR = os.path.join(ROOT, "include", "hf_pcg.h")
-HDRS_SHARED = [os.path.join(HERE, f) for f in ("hf_common.h", "hf_unpack.h", "hf_store.h")]
+HDRS_SHARED = [os.path.join(HERE, f) for f in ("hf_common.h", "hf_unpack.h", "hf_store.h", "hf_dense_act.h")]
 OUT = os.path.join(HERE, "libhfpcg.so")
 
 FLAGS = [
@@ -31,9 +32,10 @@ FLAGS = [
 ]
 # per translation unit: hf_dwconv.hip keeps its fp32 arithmetic scalar per lane (no packed v_pk_*_f32 forms: each fmaf
 # of its documented chains is one instruction of its own); hf_gconv.hip likewise: its arithmetic is the MFMA's, and what
-# scalar fp32 code there is (none on the hot path) stays unpacked
+# scalar fp32 code there is (none on the hot path) stays unpacked; hf_dense_tall.hip: the squares of its staged operands and the
+# scale of its epilogue are one rounding each, never a packed pair
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-SOURCE_FLAGS = {"hf_dwconv.hip": _NO_PACKED_FP32, "hf_gconv.hip": _NO_PACKED_FP32}
+SOURCE_FLAGS = {"hf_dwconv.hip": _NO_PACKED_FP32, "hf_gconv.hip": _NO_PACKED_FP32, "hf_dense_tall.hip": _NO_PACKED_FP32}
 
 
 def needs_build():

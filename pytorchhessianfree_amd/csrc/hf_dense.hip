@@ -20,15 +20,13 @@
 // Operands may sit anywhere in a flat parameter vector (4-byte aligned, row lengths that are no multiple of 4): the host
 // picks the 16-byte form only when base pointers and row pitches allow it, else the kernels load element by element.
 // Every load is predicated on its row and column: nothing outside rows x c is ever read.
-#include "hf_common.h"
+#include "hf_dense_act.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int DENSE_MAX_ROWS = 256;
-constexpr int DENSE_MAX_SPLITS = 32;
-constexpr int64_t DENSE_MAX_C = 1 << 20;
 constexpr int DENSE_KSTEP = 32;        // reduction entries one pass of a workgroup consumes: 4 waves x 8
 constexpr int DENSE_TARGET_BLOCKS = 512;
 
@@ -70,26 +68,7 @@ inline int dense_plan(int64_t rows, int64_t c_in, int64_t c_out, DensePlan* p) {
   return HF_OK;
 }
 
-inline bool quad_ok(const void* p, int64_t pitch) { return aligned16(p) && (pitch & 3) == 0; }
-
-// ---- device helpers ------------------------------------------------------------------------------------------------
-struct Quad { float e[4]; };
-
-// p[k .. k+3] of a row that ends at `end`; `ok` = the row exists.  Entries outside read as zero and are not touched.
-template <bool ALIGNED>
-__device__ __forceinline__ Quad ld_quad(const float* __restrict__ p, int k, int end, bool ok) {
-  Quad q;
-  if (ALIGNED && ok && k + 4 <= end) {
-    const F4 v = ld4(p + k);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) q.e[e] = v.e[e];
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) q.e[e] = (ok && k + e < end) ? p[k + e] : 0.0f;
-  }
-  return q;
-}
-
+// ---- device helpers (Quad / ld_quad: hf_dense_act.h) ---------------------------------------------------------------
 // The four waves of a workgroup hold partial sums of the same 32x32 tile (each took every fourth 8-entry step of the
 // split's range): added in wave order ((w0 + w1) + w2) + w3 through LDS and written to out[row0 + .][col0 + .].
 __device__ __forceinline__ void store_tile_sum(float (*red)[1024], const f32x16& acc, float* __restrict__ out, int row0,
@@ -278,30 +257,7 @@ __global__ __launch_bounds__(BLOCK) void k_dense_wgrad(float* __restrict__ out, 
   }
 }
 
-// ---- activation factor ---------------------------------------------------------------------------------------------
-enum { ACT_IDENTITY = 0, ACT_RELU = 1, ACT_TANH = 2 };
-
-// s * act'(y): relu  y > 0 ? s : 0  (as k_chan_affine);  tanh  s * (1 - y*y)  (three roundings)
-__device__ __forceinline__ float act_apply(float s, const float* __restrict__ y, int idx, int act) {
-  if (act == ACT_RELU) return y[idx] > 0.0f ? s : 0.0f;
-  if (act == ACT_TANH) {
-    const float yy = y[idx];
-    return s * (1.0f - yy * yy);
-  }
-  return s;
-}
-
-// t_y = (sum of slabs + v_b[col]) * act'(y)
-__global__ __launch_bounds__(BLOCK) void k_dense_act_tangent(float* __restrict__ ty, const float* __restrict__ slabs,
-                                                             int splits, long long stride, const float* __restrict__ vb,
-                                                             const float* __restrict__ y, int act, int total, int c) {
-  const int idx = blockIdx.x * BLOCK + threadIdx.x;
-  if (idx >= total) return;
-  float s = slab_sum<4>(slabs[idx], slabs, idx, splits, stride);
-  if (vb) s += vb[idx % c];
-  ty[idx] = act_apply(s, y, idx, act);
-}
-
+// ---- activation passes (act_apply, k_dense_act_tangent, k_dense_act_forward: hf_dense_act.h) -------------------------
 // g_a = (sum of slabs) * act'(y);  g_b[col] = scale * sum_rows g_a -- one thread per column walks the rows in order,
 // the column sum is kept in fp64 and rounded to fp32 once, then multiplied by `scale`.
 // CURV (hf_dense_act_adjoint2 with tanh; the adjoint of the Hessian product, where act' itself has a tangent):
@@ -320,9 +276,7 @@ __global__ __launch_bounds__(ADJ_BLOCK) void k_dense_act_adjoint(float* __restri
   double sum = 0.0;
   for (int r = 0; r < rows; ++r) {
     const int idx = r * c + col;
-    const float s = slab_sum<4>(slabs[idx], slabs, idx, splits, stride);
-    float gv = act_apply(s, y, idx, act);
-    if (CURV) gv = fmaf((-2.0f * y[idx]) * ty[idx], h1[idx], gv);
+    const float gv = act_adjoint_value<CURV>(slabs, idx, splits, stride, y, act, ty, h1);
     ga[idx] = gv;
     sum += (double)gv;
   }
@@ -345,17 +299,8 @@ __global__ __launch_bounds__(ADJ_BLOCK) void k_dense_sq_colsum(float* __restrict
 
 inline bool act_args_ok(const void* slabs, int splits, int64_t slab_stride, const void* y, int act, int64_t rows,
                         int64_t c, int dtype) {
-  if (dtype != HF_F32 || !slabs) return false;
-  if (rows < 1 || rows > DENSE_MAX_ROWS || c < 1 || c > DENSE_MAX_C) return false;
-  if (splits < 1 || splits > DENSE_MAX_SPLITS) return false;
-  if (splits > 1 && slab_stride < rows * c) return false;
-  if (act < ACT_IDENTITY || act > ACT_TANH) return false;
-  if (act != ACT_IDENTITY && !y) return false;
-  return true;
+  return act_args_in(slabs, splits, slab_stride, y, act, rows, c, dtype, 1, DENSE_MAX_ROWS);
 }
-
-// the curvature term's operands: tanh needs the tangent output and the first-order cotangent (act'' = 0 otherwise)
-inline bool act_curv_args_ok(int act, const void* t_y, const void* h) { return act != ACT_TANH || (t_y && h); }
 
 // hf_dense_act_adjoint (second = false) and hf_dense_act_adjoint2: one validator sequence, one launch.  Identity and relu
 // have no curvature term: they take the sibling's instantiation, which never sees t_y / h.
@@ -439,21 +384,6 @@ int dense_dgrad_launch(void* out_slabs, const void* g_a, const void* W, const vo
   DENSE_MT_SWITCH(mt, CALL_D)
 #undef CALL_D
   return (int)hipGetLastError();
-}
-
-// ---- forward pass of a layer: y = act(sum of slabs + b[col]) ------------------------------------------------------
-// The slab sum and the bias addition are k_dense_act_tangent's; then relu  s <= 0 ? +0 : s  (a NaN stays a NaN, as in
-// ATen's relu: a trial point whose hidden layer is NaN must not report a finite loss) or  tanhf(s).
-__global__ __launch_bounds__(BLOCK) void k_dense_act_forward(float* __restrict__ y, const float* __restrict__ slabs,
-                                                             int splits, long long stride, const float* __restrict__ b,
-                                                             int act, int total, int c) {
-  const int idx = blockIdx.x * BLOCK + threadIdx.x;
-  if (idx >= total) return;
-  float s = slab_sum<4>(slabs[idx], slabs, idx, splits, stride);
-  if (b) s += b[idx % c];
-  if (act == ACT_RELU) s = s <= 0.0f ? 0.0f : s;
-  if (act == ACT_TANH) s = tanhf(s);
-  y[idx] = s;
 }
 
 // ---- the loss head on logits [rows, c] --------------------------------------------------------------------------------
@@ -654,12 +584,7 @@ int hf_dense_sq_colsum(void* out, const void* g_a, int64_t rows, int64_t c, doub
 
 int hf_dense_act_tangent(void* t_y, const void* slabs, int splits, int64_t slab_stride, const void* v_b, const void* y,
                          int act, int64_t rows, int64_t c, int dtype, void* stream) {
-  if (!t_y || !act_args_ok(slabs, splits, slab_stride, y, act, rows, c, dtype)) return HF_ERR_ARG;
-  const int total = (int)(rows * c);
-  k_dense_act_tangent<<<(total + BLOCK - 1) / BLOCK, BLOCK, 0, (hipStream_t)stream>>>(
-      (float*)t_y, (const float*)slabs, splits, (long long)slab_stride, (const float*)v_b, (const float*)y, act, total,
-      (int)c);
-  return (int)hipGetLastError();
+  return dense_act_tangent_launch(t_y, slabs, splits, slab_stride, v_b, y, act, rows, c, dtype, stream, 1, DENSE_MAX_ROWS);
 }
 
 int hf_dense_act_adjoint(void* g_a, void* g_b_out, const void* slabs, int splits, int64_t slab_stride, const void* y,
@@ -677,11 +602,7 @@ int hf_dense_act_adjoint2(void* g_a, void* g_b_out, const void* slabs, int split
 
 int hf_dense_act_forward(void* y, const void* slabs, int splits, int64_t slab_stride, const void* b, int act,
                          int64_t rows, int64_t c, int dtype, void* stream) {
-  if (!y || !act_args_ok(slabs, splits, slab_stride, y, act, rows, c, dtype)) return HF_ERR_ARG;
-  const int total = (int)(rows * c);
-  k_dense_act_forward<<<(total + BLOCK - 1) / BLOCK, BLOCK, 0, (hipStream_t)stream>>>(
-      (float*)y, (const float*)slabs, splits, (long long)slab_stride, (const float*)b, act, total, (int)c);
-  return (int)hipGetLastError();
+  return dense_act_forward_launch(y, slabs, splits, slab_stride, b, act, rows, c, dtype, stream, 1, DENSE_MAX_ROWS);
 }
 
 int hf_dense_loss_head(int kind, const void* logits, const void* targets, void* p, void* dl, void* dl_ps, void* loss,

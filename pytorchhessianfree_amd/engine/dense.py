@@ -9,7 +9,7 @@ from torch import nn
 
 from .base import _Engine
 from .common import _Unsupported, _flat_view, _same, loss_spec_of, records_of
-from .linear import DIAG_EF, GRADIENT, MAX_CLASSES, PRODUCT, _Chain, _Layer  # noqa: F401  (_Layer: plain.py's tail reads it here)
+from .linear import DIAG_EF, GRADIENT, MAX_CLASSES, MAX_ROWS, PRODUCT, _Chain, _Layer  # noqa: F401  (_Layer: plain.py's tail reads it here)
 
 _OPT_IN = "the dense-stack engine is opt-in (set HF_DENSE_ENGINE=1)"
 
@@ -39,7 +39,14 @@ class DenseStackEngine(_Engine):
 
     ``diag_ef``: the diagonal of the empirical Fisher (Martens' preconditioner) of the same batch from ONE adjoint sweep
     with per-sample cotangents -- per layer the weight-gradient GEMM on squared operands and a column sum of squares,
-    written straight into the flat vector: at most 4 launches per live layer, no per-sample gradient is formed."""
+    written straight into the flat vector: at most 4 launches per live layer, no per-sample gradient is formed.
+
+    Tall batches (opt-in: ``HF_DENSE_TALL=1``): 257 .. 8192 rows run the same sweeps -- GGN and Hessian products, the
+    gradient, ``diag_ef`` -- on the LDS-tiled GEMMs of csrc/hf_dense_tall.hip (128 x 128 output tiles, split reductions as
+    slabs; a split weight gradient and the bias sums take a finishing launch inside their call).  Batches up to 256 rows
+    keep the skinny kernels whatever the switch says.  The session mode stays at 256 rows (the loss head's limit): a
+    taller batch runs ``engine-graphed``.  Measured slower than the hipGraph-replayed autograd sweeps on the 25.5 M-parameter
+    MLP, hence opt-in."""
 
     mode = ("fused curvature engine (dense stack): own skinny MFMA GEMMs that read the weights and the vector in place "
             "(split reductions as slabs summed by the consumer kernel), bias / activation fused, 5 launches per hidden "
@@ -104,7 +111,8 @@ class DenseStackEngine(_Engine):
         if not isinstance(x_in, torch.Tensor) or x_in.dtype != torch.float32 or not x_in.is_cuda:
             raise _Unsupported("no recorded float32 GPU input")
         leaves = [m for m in model.modules() if not list(m.children())]
-        chain = _Chain(self.dev, self._offs, (nn.ReLU, nn.Tanh), ("linear", "stack", "batch {} > {} rows"))
+        chain = _Chain(self.dev, self._offs, (nn.ReLU, nn.Tanh), ("linear", "stack", "batch {} > {} rows"),
+                       tall_switch=("HF_DENSE_TALL", os.environ.get("HF_DENSE_TALL", "0") == "1"))
         layers, cur, i = chain.layers, x_in.detach(), 0
         while i < len(leaves):
             m = leaves[i]
@@ -128,6 +136,8 @@ class DenseStackEngine(_Engine):
         if not layers:
             raise _Unsupported("no Linear layer")
         self.rows = chain.check_end(self.outputs.detach())
+        if chain.tall:  # (what path reports and benchmarks print)
+            self.mode = self.mode.replace("own skinny MFMA GEMMs", "own LDS-tiled MFMA GEMMs (tall batch: 128 x 128 tiles)")
         used = {k for u in layers for k in (u.pw, u.pb) if k is not None}
         if used != set(range(len(self.params))):
             raise _Unsupported("the parameter list has entries the engine's layers do not cover")
@@ -195,6 +205,10 @@ class DenseStackEngine(_Engine):
         if self._reduction is None:
             self.session_decline = ("the dense-stack engine's session takes a plain cross-entropy / MSE loss (no "
                                     "quadratic regulariser)")
+            return
+        if self.rows > MAX_ROWS:  # (hf_dense_loss_head's finishing kernel holds 512 terms in LDS)
+            self.session_decline = (f"the dense-stack engine's session serves batches up to {MAX_ROWS} rows (its loss "
+                                    f"head's limit); batch {self.rows} runs engine-graphed")
             return
         # session mode: the engine's own loss head fills static buffers at every forward pass
         rows, c = self.logits.shape
@@ -325,8 +339,8 @@ class DenseStackEngine(_Engine):
 def diag_ef_of(model, loss_function, inputs, targets, reduction, why=None):
     """The diagonal of the empirical Fisher of ``loss_function(model(inputs), targets)`` on the dense-stack engine, or
     ``None`` (``why``, a list, receives the reason): the switch is unset, the tensors are not CUDA float32, the model
-    has a convolution or is no prepared MLP the engine covers, batch > 256, another loss.  Only this engine kind is
-    ever built from here."""
+    has a convolution or is no prepared MLP the engine covers, batch > 256 (> 8192 with ``HF_DENSE_TALL=1``, which
+    serves 257 .. 8192 rows on the tall kernels), another loss.  Only this engine kind is ever built from here."""
     why = [] if why is None else why
     if not DenseStackEngine._engine_switch():
         why.append(_OPT_IN)

@@ -1,4 +1,5 @@
-"""A chain of ``Linear [activation]`` layers on the skinny GEMMs of csrc/hf_dense.hip -- the layout of one layer, the static
+"""A chain of ``Linear [activation]`` layers on the skinny GEMMs of csrc/hf_dense.hip (batches up to 256 rows) or, as a
+``tall`` chain, on the LDS-tiled GEMMs of csrc/hf_dense_tall.hip (257 .. 8192 rows) -- the layout of one layer, the static
 buffers, the forward / tangent / adjoint loops: what the dense-stack engine (engine/dense.py) runs on.  The plain-stack
 engine's classifier tail (engine/plain.py) is the same chain and still carries loops of its own."""
 
@@ -8,9 +9,15 @@ from torch import nn
 from .. import _lib
 from .common import _P, _Launcher, _Unsupported, _same, mark_dead_prefix, records_of
 
-MAX_ROWS, MAX_CLASSES = 256, 1024  # the dense kernels' row limit; the loss heads' class limit
+MAX_ROWS, MAX_CLASSES = 256, 1024  # the skinny dense kernels' row limit; the loss heads' class limit
+MAX_TALL_ROWS = 8192               # the tall kernels' (hf_dense_tall.hip)
 _ACT = {None: 0, nn.ReLU: 1, nn.Tanh: 2}
 GRADIENT, PRODUCT, DIAG_EF = range(3)  # what an adjoint sweep is for
+# the entry points whose arguments are the same in both kernel families, by the chain's form (``tall``)
+_NAMES = {False: {"plan": "hf_dense_plan", "slabs": "hf_dense_tangent_slabs", "forward": "hf_dense_act_forward",
+                  "tangent": "hf_dense_act_tangent"},
+          True: {"plan": "hf_dense_tall_plan", "slabs": "hf_dense_tall_tangent_slabs",
+                 "forward": "hf_dense_tall_act_forward", "tangent": "hf_dense_tall_act_tangent"}}
 
 
 class _Layer:
@@ -26,10 +33,12 @@ class _Layer:
 class _Chain(_Launcher):
     """The layers of one chain and their launches, on the engine's device and its offsets into the flat vectors.  ``acts``:
     the activations accepted behind a ``Linear``; ``words``: a layer's and the chain's name in decline reasons, the row
-    limit's message."""
+    limit's message; ``tall_switch``: the name of the caller's opt-in switch for batches beyond ``MAX_ROWS`` and whether it
+    is set (``None``: the caller has no such form)."""
 
-    def __init__(self, dev, offs, acts, words):
-        self.dev, self.offs, self.acts = dev, offs, acts
+    def __init__(self, dev, offs, acts, words, tall_switch=None):
+        self.dev, self.offs, self.acts, self.tall_switch = dev, offs, acts, tall_switch
+        self.tall, self.names = False, _NAMES[False]
         self.name, self.whole, self.rows_msg = words
         self.layers, self.dead, self.zero = [], 0, None  # (zero: a slab of zeros, where a first layer may have no ``t_x``)
 
@@ -69,9 +78,15 @@ class _Chain(_Launcher):
         last = self.layers[-1].ry
         if out.data_ptr() != last.data_ptr() or tuple(out.shape) != tuple(last.shape):
             raise _Unsupported("the network output is not the last Linear layer's output")
-        if out.shape[0] > MAX_ROWS:
-            raise _Unsupported(self.rows_msg.format(out.shape[0], MAX_ROWS))
-        return int(out.shape[0])
+        rows = int(out.shape[0])
+        if rows > MAX_ROWS:
+            name, on = self.tall_switch or (None, False)
+            if not on or rows > MAX_TALL_ROWS:
+                hint = "" if name is None else (f" ({name}=1 serves up to {MAX_TALL_ROWS})" if on else
+                                                f" (up to {MAX_TALL_ROWS} rows are opt-in: {name}=1)")
+                raise _Unsupported(self.rows_msg.format(rows, MAX_ROWS) + hint)
+            self.tall, self.names = True, _NAMES[True]
+        return rows
 
     def mark_dead_prefix(self):
         """Frozen layers at the input end are dead for both sweeps; the first live one needs no data gradient."""
@@ -84,15 +99,21 @@ class _Chain(_Launcher):
         return [t for u in self.layers for t, k in ((u.lin.weight, u.pw), (u.lin.bias, u.pb)) if k is None and t is not None]
 
     def allocate(self, rows, x, t_x, hessian=False):
-        """Per layer ``hf_dense_plan``'s split-K slab counts, output and tangent slabs; per LIVE layer tangent, cotangent
-        and (unless ``first_live``) data-gradient slabs, on a Hessian engine ``g1`` / ``h1``.  The first layer reads ``x``
-        (``t_x``: its tangent, or ``None``)."""
+        """Per layer the plan's split-K slab counts, output and tangent slabs; per LIVE layer tangent, cotangent
+        and (unless ``first_live``) data-gradient slabs, on a Hessian engine ``g1`` / ``h1``; on a tall chain the two
+        workspaces the plan sizes (weight-gradient slabs, the row blocks' column partials), shared by the layers.  The
+        first layer reads ``x`` (``t_x``: its tangent, or ``None``)."""
         f32, dev, lib = torch.float32, self.dev, _lib.load()
         self.rows, self.hessian = rows, hessian
+        ws_w = ws_col = 0
         for u in self.layers:
-            st, sd = _lib.c_int(), _lib.c_int()
-            _lib.check(lib.hf_dense_plan(rows, u.c_in, u.c_out, st, sd), "hf_dense_plan")
-            u.sT, u.sD, u.x, u.t_x = st.value, sd.value, x, t_x
+            counts = [_lib.c_int() for _ in range(4 if self.tall else 2)]
+            _lib.check(getattr(lib, self.names["plan"])(rows, u.c_in, u.c_out, *counts), self.names["plan"])
+            u.sT, u.sD, u.x, u.t_x = counts[0].value, counts[1].value, x, t_x
+            if self.tall:
+                u.sW = counts[2].value
+                ws_w = max(ws_w, u.sW * u.c_out * u.c_in if u.sW > 1 else 0)
+                ws_col = max(ws_col, counts[3].value * u.c_out)
             u.y = torch.empty((rows, u.c_out), dtype=f32, device=dev)
             u.tslabs = torch.empty((u.sT, rows * u.c_out), dtype=f32, device=dev)
             x = u.y
@@ -104,6 +125,9 @@ class _Chain(_Launcher):
                 u.g1 = torch.empty_like(u.y)
                 u.h1 = torch.empty_like(u.y) if u.act == 2 else None
             t_x = u.ty
+        if self.tall:  # (launches of one stream: one workspace of each kind serves every layer in turn)
+            self.ws_w = torch.empty(max(ws_w, 1), dtype=f32, device=dev)
+            self.ws_col = torch.empty(ws_col, dtype=torch.float64, device=dev)
         return self.layers[-1].y
 
     def release(self):  # (the model's own activations were only needed up to the end of the construction)
@@ -113,14 +137,14 @@ class _Chain(_Launcher):
     # ---- launches ----------------------------------------------------------------------------
     def _slabs(self, u, t_x, v_w):
         """``u.tslabs <- t_x W^T + x V^T`` (either term may be absent, not both)."""
-        self._launch("hf_dense_tangent_slabs", u.tslabs, t_x, u.x, u.lin.weight, v_w, self.rows, u.c_in, u.c_out, 0, u.sT,
+        self._launch(self.names["slabs"], u.tslabs, t_x, u.x, u.lin.weight, v_w, self.rows, u.c_in, u.c_out, 0, u.sT,
                      u.tslabs.shape[1])
 
     def forward(self):
         """The tangent kernel with ``t_x = NULL, V = W`` is the forward GEMM; then slab sum, bias, activation in one pass."""
         for u in self.layers:
             self._slabs(u, None, u.lin.weight)
-            self._launch("hf_dense_act_forward", u.y, u.tslabs, u.sT, u.tslabs.shape[1], u.lin.bias, u.act, self.rows,
+            self._launch(self.names["forward"], u.y, u.tslabs, u.sT, u.tslabs.shape[1], u.lin.bias, u.act, self.rows,
                          u.c_out)
 
     def load_recorded(self):
@@ -138,8 +162,40 @@ class _Chain(_Launcher):
             else:
                 self._slabs(u, u.t_x, v_w)
                 slabs, splits = u.tslabs, u.sT
-            self._launch("hf_dense_act_tangent", u.ty, slabs, splits, u.tslabs.shape[1], v_b, u.y, u.act, self.rows, u.c_out)
+            self._launch(self.names["tangent"], u.ty, slabs, splits, u.tslabs.shape[1], v_b, u.y, u.act, self.rows, u.c_out)
         return u.ty
+
+    # the launches whose arguments differ between the two families: ONE place each that knows both spellings
+    def _act_adjoint(self, u, g, o_b, src, y, act, scale, t_y=None, h=None):
+        """``g <- (sum of slabs) * act'(y)`` (+ the tanh curvature term where ``t_y`` / ``h`` are given), ``o_b``: its
+        column sums times ``scale``."""
+        slabs, splits, stride = src
+        if self.tall:
+            self._launch("hf_dense_tall_act_adjoint", g, o_b, self.ws_col, slabs, splits, stride, y, act, t_y, h, self.rows,
+                         u.c_out, scale)
+        elif t_y is not None:
+            self._launch("hf_dense_act_adjoint2", g, o_b, slabs, splits, stride, y, act, t_y, h, self.rows, u.c_out, scale)
+        else:
+            self._launch("hf_dense_act_adjoint", g, o_b, slabs, splits, stride, y, act, self.rows, u.c_out, scale)
+
+    def _wgrad(self, u, o_w, mode, g, x, g2, x2, scale):
+        """``o_w <- scale * g^T x``; ``mode`` 1: on squared operands, 2: ``+ g2^T x2``."""
+        if self.tall:
+            self._launch("hf_dense_tall_wgrad", o_w, self.ws_w, g, x, g2, x2, self.rows, u.c_in, u.c_out, mode, scale, u.sW)
+        elif mode == 2:
+            self._launch("hf_dense_wgrad2", o_w, g, x, g2, x2, self.rows, u.c_in, u.c_out, scale)
+        else:
+            self._launch(("hf_dense_wgrad", "hf_dense_sq_wgrad")[mode], o_w, g, x, self.rows, u.c_in, u.c_out, scale)
+
+    def _dgrad(self, u, g, g2, v_w):
+        """``u.dslabs <- g W`` (``+ g2 V`` where given)."""
+        tail = (self.rows, u.c_in, u.c_out, u.sD, u.dslabs.shape[1])
+        if self.tall:
+            self._launch("hf_dense_tall_dgrad_slabs", u.dslabs, g, u.lin.weight, g2, v_w, *tail)
+        elif g2 is not None:
+            self._launch("hf_dense_dgrad2_slabs", u.dslabs, g, u.lin.weight, g2, v_w, *tail)
+        else:
+            self._launch("hf_dense_dgrad_slabs", u.dslabs, g, u.lin.weight, *tail)
 
     def adjoint(self, what, seed, out=None, weight=1.0, v=None, scale=None):
         """THE adjoint sweep: from the cotangent ``seed`` at the logits through the live layers in reverse, per layer the
@@ -149,33 +205,33 @@ class _Chain(_Launcher):
         ``GRADIENT`` keeps ``g_l`` (``h_l`` of tanh layers) where a Hessian engine has buffers for them; ``PRODUCT`` carries,
         on a Hessian engine, the second-order terms of ``v``; ``DIAG_EF`` writes sums of squares times ``scale`` (per-sample
         cotangents: ``weight`` does not enter, the bias has a kernel of its own).  Returns the last ``(slabs, splits, stride)``."""
-        launch, rows = self._launch, self.rows
         diag, second = what == DIAG_EF, what == PRODUCT and self.hessian
-        slabs, splits, stride = seed, 1, 0
+        src = (seed, 1, 0)
         for u in reversed(self.layers[self.dead:]):
             o_w, o_b = self._at(out, u.pw), self._at(out, u.pb)
             g = u.g1 if what == GRADIENT and u.g1 is not None else u.ga
             if what == GRADIENT and u.h1 is not None:  # h_l itself: the slab sum, no factor
-                launch("hf_dense_act_adjoint", u.h1, None, slabs, splits, stride, None, 0, rows, u.c_out, 1.0)
+                self._act_adjoint(u, u.h1, None, src, None, 0, 1.0)
             if second and u.act == 2:  # tanh: the curvature term -2 a t_a h
-                launch("hf_dense_act_adjoint2", g, o_b, slabs, splits, stride, u.y, u.act, u.ty, u.h1, rows, u.c_out, weight)
+                self._act_adjoint(u, g, o_b, src, u.y, u.act, weight, u.ty, u.h1)
             else:
-                launch("hf_dense_act_adjoint", g, None if diag else o_b, slabs, splits, stride, u.y, u.act, rows, u.c_out,
-                       1.0 if diag else weight)
+                self._act_adjoint(u, g, None if diag else o_b, src, u.y, u.act, 1.0 if diag else weight)
             if o_w is not None and diag:
-                launch("hf_dense_sq_wgrad", o_w, g, u.x, rows, u.c_in, u.c_out, scale)
+                self._wgrad(u, o_w, 1, g, u.x, None, None, scale)
             elif o_w is not None and second and u.t_x is not None:  # + g^T t_x (none enters the first live layer)
-                launch("hf_dense_wgrad2", o_w, g, u.x, u.g1, u.t_x, rows, u.c_in, u.c_out, weight)
+                self._wgrad(u, o_w, 2, g, u.x, u.g1, u.t_x, weight)
             elif o_w is not None:
-                launch("hf_dense_wgrad", o_w, g, u.x, rows, u.c_in, u.c_out, weight)
+                self._wgrad(u, o_w, 0, g, u.x, None, None, weight)
             if o_b is not None and diag:
-                launch("hf_dense_sq_colsum", o_b, g, rows, u.c_out, scale)
+                if self.tall:
+                    self._launch("hf_dense_tall_sq_colsum", o_b, self.ws_col, g, self.rows, u.c_out, scale)
+                else:
+                    self._launch("hf_dense_sq_colsum", o_b, g, self.rows, u.c_out, scale)
             if u.first_live:
                 break
             if second and u.pw is not None:  # + g V (a frozen weight has no tangent)
-                launch("hf_dense_dgrad2_slabs", u.dslabs, g, u.lin.weight, u.g1, self._at(v, u.pw), rows, u.c_in, u.c_out,
-                       u.sD, u.dslabs.shape[1])
+                self._dgrad(u, g, u.g1, self._at(v, u.pw))
             else:
-                launch("hf_dense_dgrad_slabs", u.dslabs, g, u.lin.weight, rows, u.c_in, u.c_out, u.sD, u.dslabs.shape[1])
-            slabs, splits, stride = u.dslabs, u.sD, u.dslabs.shape[1]
-        return slabs, splits, stride
+                self._dgrad(u, g, None, None)
+            src = (u.dslabs, u.sD, u.dslabs.shape[1])
+        return src

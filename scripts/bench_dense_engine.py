@@ -6,6 +6,8 @@ the 1-GPU leg of BASELINE.json configs[4] as ``tests/test_optimizer_gpu.py::_mlp
     python scripts/bench_dense_engine.py --prepared 0     # the autograd sweeps, hipGraph-replayed
     python scripts/bench_dense_engine.py --curvature hessian --prepared 1   # forward over reverse on the engine
     python scripts/bench_dense_engine.py --curvature hessian --prepared 0   # autograd double backward, hipGraph-replayed
+    python scripts/bench_dense_engine.py --batch 512 --tall 1   # a tall batch on the engine's LDS-tiled GEMMs (HF_DENSE_TALL=1)
+    python scripts/bench_dense_engine.py --batch 512 --tall 0   # the same batch with the switch off: autograd-graphed
 
 The operator is the one ``HessianFree(graph_matvec=True).step()`` hands to ``cg()`` (``HessianFree.linearise``); the
 timed region is ``--reps`` repetitions of ``--steps`` solves of ``--iters`` iterations (``tol = 0``: every solve runs
@@ -42,12 +44,12 @@ import pytorchhessianfree_amd as hf  # noqa: E402
 from pytorchhessianfree_amd import modelprep  # noqa: E402
 
 
-def mlp25m(device):
+def mlp25m(device, batch=64):
     torch.manual_seed(0)
     net = torch.nn.Sequential(torch.nn.Linear(3072, 4096), torch.nn.Tanh(), torch.nn.Linear(4096, 3072), torch.nn.Tanh(),
                               torch.nn.Linear(3072, 100))
     g = torch.Generator().manual_seed(1)
-    x, t = torch.rand(64, 3072, generator=g), torch.randint(0, 100, (64,), generator=g)
+    x, t = torch.rand(batch, 3072, generator=g), torch.randint(0, 100, (batch,), generator=g)
     return net.to(device), x.to(device), t.to(device)
 
 
@@ -197,6 +199,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--damping", type=float, default=1.0)
+    ap.add_argument("--batch", type=int, default=64, help="rows of the product benchmark's batch")
+    ap.add_argument("--tall", type=int, default=0, help="1: HF_DENSE_TALL=1 (batches of 257 .. 8192 rows on the engine)")
     args = ap.parse_args()
     if args.diag_ef_route:
         return diag_ef_route(args.diag_ef_route, args.warmup, args.reps)
@@ -205,10 +209,11 @@ def main():
     if args.step_ms:
         return step_ms(args)
     dev = torch.device("cuda")
-    model, x, t = mlp25m(dev)
+    model, x, t = mlp25m(dev, args.batch)
     if args.prepared:
         os.environ["HF_DENSE_ENGINE"] = "1"  # (the engine is opt-in until this script's figures stand in DESIGN.md)
         os.environ["HF_DENSE_HESSIAN"] = "1"
+        os.environ["HF_DENSE_TALL"] = "1" if args.tall else "0"
         modelprep.prepare_model(model)
     lossf = torch.nn.CrossEntropyLoss()
     opt = hf.HessianFree(model.parameters(), curvature_opt=args.curvature, graph_matvec=True)
@@ -249,7 +254,7 @@ def main():
     mid = sorted(rates)[len(rates) // 2]
     print(json.dumps({
         "bench": "dense_engine_mlp25m", "curvature": args.curvature, "prepared": bool(args.prepared), "path": opt.path_report()["step"]["path"],
-        "mode": getattr(op, "mode", ""), "n": n, "batch": 64, "iters": args.iters, "iters_done": iters_done,
+        "mode": getattr(op, "mode", ""), "n": n, "batch": args.batch, "tall_switch": bool(args.tall), "iters": args.iters, "iters_done": iters_done,
         "steps": args.steps, "reps": args.reps, "matvecs_per_s": [round(r, 1) for r in rates],
         "median_matvecs_per_s": round(mid, 1), "spread": round(max(rates) - min(rates), 1),
         "us_per_matvec_incl_pcg": round(1e6 / mid, 1), f"floor_us_{words}n_words": round(floor_us, 1), "initial_loss": loss,
