@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 31
+#define HF_ABI_VERSION 32
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -1282,6 +1282,46 @@ int hf_gconv2d_nhwc_sqsum_slabs(void* out, const void* ga, const void* x, int64_
                                 int64_t c_in, int64_t c_out, int64_t groups, int64_t r, int64_t s, int64_t stride_h,
                                 int64_t stride_w, int64_t pad_h, int64_t pad_w, float pre, int splits, int64_t slab_stride,
                                 int dtype, void* stream);
+
+/* ---- GroupNorm units of the plain-stack engine (hf_gn.hip) ------------------------------------------------------------
+ * conv -> GroupNorm(affine) -> [ReLU], fp32 NHWC [rows = n*hw, c], `groups` groups of cg = c / groups channels, statistics
+ * mean / rstd [n, groups].  One workgroup owns one sample x one span of whole groups (hf_gn_plan returns the span's
+ * channels), sums the split-K slabs of its hw x span block once into LDS and takes every reduction from it, so forward,
+ * tangent and adjoint are ONE launch each.  Lanes keep fp32 partial sums over fixed sets of elements, everything behind
+ * them is fp64 in an order that depends on the shape alone: no atomics, two launches give the same bits.  The arithmetic
+ * chains and their roundings stand in hf_gn.hip's header.
+ *
+ * Limits, refused with HF_ERR_ARG before anything is launched or written: cg % 4 == 0; hw * cg <= 16 384 floats (the LDS
+ * block must hold at least one whole group); n <= 65 535; the maps, slabs and row tables 16-byte aligned, leading
+ * dimensions and slab strides multiples of 4 (ld >= c, stride >= n*hw*c); HF_F32.  Per-channel vectors (gamma, beta, the
+ * convolution bias and the CG vector's slices) may sit on any 4-byte boundary.
+ *
+ * With xh = (a - mean)*rstd, m = relu ? (y > 0) : 1 and E[.] the mean over the (sample, group) block:
+ *   hf_gn_forward      s = sum of a's slabs (+ conv_bias[c], nullable) -> a_out (nullable);  mean, rstd (exact two-pass
+ *                      variance, biased, + eps);  y = act(gamma*xh + beta) -> y (dense) and y2 (pixel stride y2_ld); either
+ *                      may be NULL, not both.  splits = 1, a_out = NULL: statistics and output of a given map.
+ *   hf_gn_act_tangent  t = sum of t_a's slabs (+ v_conv_bias[c]);
+ *                      out = m * (gamma*rstd*(t - E[t] - xh*E[xh t]) + v_gamma*xh + v_beta), pixel stride out_ld (0 = c);
+ *                      v_conv_bias / v_gamma / v_beta: slices of the CG vector read in place, NULL where frozen.
+ *   hf_gn_act_adjoint  g = m * (sum of gy's slabs) -> g (nullable);  ga = rstd*(gamma g - E[gamma g] - xh*E[gamma g xh]);
+ *                      per-sample rows [n, c]: gw_rows = sum_hw g*xh, gb_rows = sum_hw g, gcb_rows = sum_hw ga (the
+ *                      convolution bias's); each nullable.  hf_pack_ex (splits = (n, c)) adds the rows.
+ *   hf_gn_rows_sqsum   out_*[c] = sum_n (pre * rows_*[n][c])^2 for up to three tables (NULL: skipped; not all): the
+ *                      GroupNorm entries of the diagonal empirical Fisher.  out_* on any 4-byte boundary.
+ */
+int hf_gn_plan(int64_t n, int64_t hw, int64_t c, int64_t groups);
+int hf_gn_forward(void* y, void* y2, int64_t y2_ld, void* a_out, void* mean, void* rstd, const void* a, int splits,
+                  int64_t slab_stride, const void* conv_bias, const void* gamma, const void* beta, double eps, int relu,
+                  int64_t n, int64_t hw, int64_t c, int64_t groups, int dtype, void* stream);
+int hf_gn_act_tangent(void* out, int64_t out_ld, const void* t_a, int splits, int64_t slab_stride, const void* v_conv_bias,
+                      const void* a, const void* mean, const void* rstd, const void* gamma, const void* v_gamma,
+                      const void* v_beta, const void* mask_src, int64_t n, int64_t hw, int64_t c, int64_t groups, int dtype,
+                      void* stream);
+int hf_gn_act_adjoint(void* ga, void* g, void* gw_rows, void* gb_rows, void* gcb_rows, const void* gy, int splits,
+                      int64_t slab_stride, const void* a, const void* mean, const void* rstd, const void* gamma,
+                      const void* mask_src, int64_t n, int64_t hw, int64_t c, int64_t groups, int dtype, void* stream);
+int hf_gn_rows_sqsum(void* out_w, const void* rows_w, void* out_b, const void* rows_b, void* out_cb, const void* rows_cb,
+                     double pre, int64_t n, int64_t c, int dtype, void* stream);
 
 /* ---- RCCL (resolved at run time from the already-loaded librccl) ----------- */
 typedef struct hf_comm hf_comm_t;

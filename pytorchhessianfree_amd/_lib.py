@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HF_PCG_LIB") or os.path.join(_HERE, "csrc", "libhfpcg.so")
 
 HF_F32, HF_F64 = 0, 1
-ABI_VERSION = 31
+ABI_VERSION = 32
 HF_ERR_ARG = -1  # hf_status of include/hf_pcg.h: null / negative / inconsistent argument
 HF_M_NONE, HF_M_DIAG, HF_M_EXTERNAL = 0, 1, 2
 REASONS = {
@@ -252,6 +252,13 @@ SIGNATURES = {
     "hf_gconv2d_nhwc_sqsum_plan": (c_int, [c_int64] * 12 + [c_int]),
     "hf_gconv2d_nhwc_sqsum_slabs": (c_int, [c_void_p] * 3 + [c_int64] * 13 + [ctypes.c_float, c_int, c_int64, c_int,
                                                                                c_void_p]),
+    "hf_gn_plan": (c_int, [c_int64] * 4),
+    "hf_gn_forward": (c_int, [c_void_p, c_void_p, c_int64] + [c_void_p] * 4 + [c_int, c_int64] + [c_void_p] * 3
+                      + [c_double, c_int] + [c_int64] * 4 + [c_int, c_void_p]),
+    "hf_gn_act_tangent": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64] + [c_void_p] * 8 + [c_int64] * 4
+                          + [c_int, c_void_p]),
+    "hf_gn_act_adjoint": (c_int, [c_void_p] * 6 + [c_int, c_int64] + [c_void_p] * 5 + [c_int64] * 4 + [c_int, c_void_p]),
+    "hf_gn_rows_sqsum": (c_int, [c_void_p] * 6 + [c_double, c_int64, c_int64, c_int, c_void_p]),
     "hf_comm_unique_id": (c_int, [ctypes.c_char_p]),
     "hf_comm_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.c_char_p, c_int, c_int]),
     "hf_comm_destroy": (c_int, [c_void_p]),
@@ -698,6 +705,14 @@ def gconv_plan(n, h, w, c_in, c_out, groups, r, s, stride, padding):
     if sp < 1:
         check(sp, "hf_gconv2d_nhwc_plan")
     return sp
+
+
+def gn_plan(n, hw, c, groups):
+    """The channels of the span one workgroup of the GroupNorm launches owns on this shape (``hf_gn_plan``)."""
+    span = load().hf_gn_plan(n, hw, c, groups)
+    if span < 1:
+        check(span, "hf_gn_plan")
+    return span
 
 
 def dwconv_sqsum_plan(n, h, w, c, r, s, stride, padding, target_blocks=0):

@@ -187,6 +187,11 @@ SWITCHES = {
                          "stack engine (the second-order backward of a grouped unit in one launch, "
                          "hf_gconv2d_nhwc_backward2_slabs) instead of the autograd operator; unmeasured, hence opt-in",
                          "tests/test_group_hessian_engine_gpu.py::test_hessian_products_against_float64"),
+    "HF_GN_ENGINE": ("0", "1: the plain-stack engine takes conv -> GroupNorm(affine) -> [ReLU] units on the one-launch "
+                     "kernels of hf_gn.hip (forward, tangent, adjoint: one workgroup per sample and span of groups); off by "
+                     "default: measured on one net only (1.6x the captured autograd route, profiles/gn_stack.jsonl) -- "
+                     "without it such a net keeps the autograd path",
+                     "tests/test_gn_engine_gpu.py::test_eval_point_against_float64"),
     "HF_CHUNKED_ALLREDUCE": ("auto", "0 / 1: force the single-graph resp. the two-phase data-parallel product",
                              "tests/test_distributed_gpu.py::test_step_two_ranks_engine_session_equals_cpu_whole_batch"),
     "HF_DIRECT_RCCL": ("1", "0: every collective through torch.distributed (no communicator of the package's own)",

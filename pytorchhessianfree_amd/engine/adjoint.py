@@ -5,7 +5,7 @@ Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overal
 
 from .. import _lib
 from .problems import (affine_args, affine_train_args, affine_train_problem, bn_adjoint_args, bn_adjoint_problem,
-                       bn_adjoint_v4_args, conv_args, conv_backward_args, conv_problem, problem)
+                       bn_adjoint_v4_args, conv_args, conv_backward_args, conv_problem, gn_adjoint_args, problem)
 
 
 class _AdjointSweep:
@@ -103,6 +103,11 @@ class _AdjointSweep:
         """``reduce_only`` (train mode inside a Hessian product): the masked cotangent and its per-channel sums only --
         the elementwise pass is ``hf_bn_train_hessian_apply``'s."""
         self._extras_wait(srcs)
+        if u.gn is not None:
+            # GroupNorm: ONE launch, no grid-wide sum -- g = mask * (sum of the cotangent's slabs), g_a = rstd * (w g -
+            # E[w g] - xhat * E[w g xhat]) and the parameters' sums as one partial row per sample (the gather adds them)
+            self._launch("hf_gn_act_adjoint", *gn_adjoint_args(u, srcs))
+            return
         if u.train:
             # pass 1: g = mask * (sum of the cotangents' slabs) and its per-channel sums (the parameter
             # gradients); pass 2: g_a = rstd*w * [g - mean(g) - xhat * mean(xhat*g)] (the batch statistics'
@@ -168,6 +173,13 @@ class _AdjointSweep:
         _lib.pack_ex(out[self._offs[lo]:end], tensors[lo:hi], sub(perms), sub(splits), scale=self.weight,
                      live=sub(self._pack_live))
 
+    @staticmethod
+    def _row_entries(u):
+        """(parameter index, partial rows, their count) of the unit's per-channel parameters: scale and shift -- or the bias
+        --, and behind a GroupNorm the convolution's own bias."""
+        rows = [(u.pg, u.gw, u.gw_rows), (u.pb, u.gb, u.rb)]
+        return rows + [(u.pcb, u.gcb, u.rb)] if u.pcb is not None else rows
+
     def _pack_args(self, first_order=False):
         """(tensors, perms, splits) of ``hf_pack_ex``.  ``first_order``: a gradient sweep of a Hessian
         engine fills only the first ``sW`` weight-gradient slabs of each layer."""
@@ -191,7 +203,7 @@ class _AdjointSweep:
             self._pack_live = {}
             for u in self.units:
                 if u.pw is None:  # (frozen weight: its gradient slabs, if the fused launch wrote any, are not gathered)
-                    for pi, buf, rows in ((u.pg, u.gw, u.gw_rows), (u.pb, u.gb, u.rb)):
+                    for pi, buf, rows in self._row_entries(u):
                         if pi is not None:
                             tensors[pi] = buf[0]
                             if rows > 1:
@@ -206,7 +218,7 @@ class _AdjointSweep:
                             self._pack_live[u.pw] = u.live
                 if u.nW > 1:
                     splits[u.pw] = (u.nW, u.wbuf.shape[1])
-                for pi, buf, rows in ((u.pg, u.gw, u.gw_rows), (u.pb, u.gb, u.rb)):
+                for pi, buf, rows in self._row_entries(u):
                     if pi is not None:
                         tensors[pi] = buf[0]
                         if rows > 1:

@@ -220,7 +220,11 @@ class _Buffers:
                 u.rb = -(-u.rows // per)
                 if u.rb < 2:
                     u.rb = 1
-            enabled = os.environ.get("HF_BN_SUMS_DEFER", "1") != "0"
+            if u.gn is not None:
+                # GroupNorm: one workgroup owns a (sample, span of groups) block, so the sums arrive as ONE partial row per
+                # sample -- which are also the per-sample gradients ``diag_ef`` squares; no elementwise / deferred form
+                u.rb = n
+            enabled = os.environ.get("HF_BN_SUMS_DEFER", "1") != "0" and u.gn is None
             u.split = adjoint_split_ok(u.train, u.rb, self.hessian, u.a.numel() * 4, self.DEFER_MAX_BYTES, enabled)
             u.defer = not u.dead and defer_sums_ok(u.train, u.rb, self.hessian, u.bn is not None and u.pg is not None,
                                                    u.pb is not None, u.a.numel() * 4, self.DEFER_MAX_BYTES, enabled)
@@ -233,6 +237,10 @@ class _Buffers:
                 u.gw_rows += 1  # (+ the closed-form share of the scale's second-order term: hf_bn_train_hessian_coeffs)
             u.gw = torch.empty((u.gw_rows, k), dtype=f32, device=dev)
             u.gb = torch.empty((u.rb, k), dtype=f32, device=dev)
+            if u.gn is not None:  # the (sample, group) statistics, and the convolution bias's rows
+                u.gn_mean = torch.empty((n, u.gn.num_groups), dtype=f32, device=dev)
+                u.gn_rstd = torch.empty_like(u.gn_mean)
+                u.gcb = torch.empty((u.rb, k), dtype=f32, device=dev) if u.pcb is not None else None
             if u.train:
                 # The per-channel finalisation of a train-mode tangent / adjoint runs in the PROLOGUE of the elementwise
                 # pass: its workgroups add the reduction's partial rows up themselves (hf_chan_affine_train).  The

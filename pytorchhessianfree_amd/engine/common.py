@@ -78,6 +78,8 @@ class _Unit:
         self.no_dgrad = False     # a live unit whose input carries no tangent: its data gradient is not needed
         self.pool = None          # plain stack: (kh, kw, sh, sw, ph, pw) of the MaxPool2d behind the unit (its ReLU)
         self.rp = None            # ... and the pooled map the model's forward pass recorded
+        self.gn = None            # plain stack: the GroupNorm behind the convolution (hf_gn.hip; ``bn`` is then None)
+        self.pcb = None           # ... and the index of that convolution's own bias (``pb`` is the GroupNorm's shift)
 
     @property
     def in_place(self):
@@ -116,12 +118,12 @@ def records_of(m, n=2, with_input=False):
 
 
 def mark_dead_prefix(layers):
-    """Frozen layers at the input end of a stack (no ``pw``, no ``pb``, no ``pg``): ``dead`` for both sweeps -- no tangent reaches
+    """Frozen layers at the input end of a stack (no ``pw``, no ``pb``, no ``pg``, no ``pcb``): ``dead`` for both sweeps -- no tangent reaches
     them, nobody needs a cotangent behind the first trainable layer.  Returns how many there are; the layer behind them
     reads a tangent-free input and needs no data gradient (the caller's flag)."""
     dead = 0
     for u in layers:
-        if u.pw is not None or u.pb is not None or getattr(u, "pg", None) is not None:
+        if any(i is not None for i in (u.pw, u.pb, getattr(u, "pg", None), getattr(u, "pcb", None))):
             break
         u.dead = True
         dead += 1

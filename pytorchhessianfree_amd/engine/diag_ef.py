@@ -6,7 +6,8 @@ Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overal
 import torch
 
 from .. import _lib
-from .problems import chan_sqsum_args, conv_sqsum_args, dwconv_sqsum_args, gconv_dims, gconv_sqsum_args
+from .problems import (chan_sqsum_args, conv_sqsum_args, dwconv_sqsum_args, gconv_dims, gconv_sqsum_args,
+                       gn_rows_sqsum_args)
 
 
 class _DiagEF:
@@ -61,7 +62,7 @@ class _DiagEF:
                 else:
                     self._conv_slabs(2, u.wps, u.x[i:i + 1], ga, u.geo1, u.sW1)
                 k, hw = u.a.shape[1], u.a.shape[2] * u.a.shape[3]
-                if u.pg is None and u.pb is None:
+                if (u.pg is None and u.pb is None) or u.gn is not None:  # (GroupNorm: ``_diag_gn``, once for the batch)
                     continue
                 if u.bn is not None:
                     g = (u.g1 if first_order else u.g)[i:i + 1]
@@ -69,6 +70,7 @@ class _DiagEF:
                 elif u.pb is not None:
                     self._chan_sums(ga, 1, 0, 1, k, hw, 1, gb=u.gbs)
             _lib.pack_ex(out, tensors, perms, splits, scale=scale, live=self._pack_live, mode=1)
+        self._diag_gn(out, scale)
         self._diag_head(out, scale)
         if l2 is not None:
             sum_a = mean_grad * (scale / self.weight)  # sum_i a_i
@@ -77,6 +79,14 @@ class _DiagEF:
         if reduction == "mean":
             out.div_(float(n))
         return out
+
+    def _diag_gn(self, out, pre):
+        """The GroupNorm units' entries, on both routes: the adjoint launch of the sweep left, per sample, the rows of the
+        scale's, the shift's and the convolution bias's gradient -- the per-sample gradients themselves.  ONE launch per
+        unit squares and adds them over the samples, straight into ``out`` (the gathers wrote zeros there)."""
+        for u in self.units:
+            if u.gn is not None and not u.dead and any(i is not None for i in (u.pg, u.pb, u.pcb)):
+                self._launch("hf_gn_rows_sqsum", *gn_rows_sqsum_args(u, out, self._offs, pre))
 
     def _diag_head_buffers(self, tensors):
         """A kind whose head has parameters: their entries of the gather's table ..."""
@@ -101,7 +111,7 @@ class _DiagEF:
                 act = u.cols_pad if u.im2col else u.x
                 self._launch("hf_conv2d_nhwc_sqsum_slabs",
                              *conv_sqsum_args(u.wps, act, ga, u.geo1, u.sW1, pre, out_c=u.jcols if u.im2col else 0))
-            if u.pg is None and u.pb is None:
+            if (u.pg is None and u.pb is None) or u.gn is not None:  # (GroupNorm: ``_diag_gn``)
                 continue
             k, hw = u.a.shape[1], u.a.shape[2] * u.a.shape[3]
             gb2 = u.gbs if u.pb is not None else None
@@ -163,6 +173,11 @@ class _DiagEF:
                     splits[u.pw] = (u.sW1, u.wps.shape[1])
             u.gws = torch.zeros((u.rb1, k), dtype=f32, device=dev)
             u.gbs = torch.zeros((u.rb1, k), dtype=f32, device=dev)
+            if u.gn is not None:  # (written straight into ``out`` behind the gathers, ``_diag_gn``: zeros here)
+                for pi in (u.pg, u.pb, u.pcb):
+                    if pi is not None:
+                        tensors[pi] = self._zeros(k)
+                continue
             for pi, buf in ((u.pg, u.gws), (u.pb, u.gbs)):
                 if pi is not None:
                     tensors[pi] = buf[0]

@@ -6,11 +6,18 @@ Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overal
 
 import torch
 
+from .problems import gn_forward_args
+
 
 class _Forward:
     def _bn_forward(self, u, splits, update_running=True):
         n, k, oh, ow = u.a.shape
         res = u.res
+        if u.gn is not None:
+            # GroupNorm: ONE launch -- the slabs (+ the convolution's bias) summed into LDS, the (sample, group) statistics
+            # taken from the resident block, the output into ``u.y`` and the consumer's x half
+            self._launch("hf_gn_forward", *gn_forward_args(u, u.tbuf, splits, u.tbuf.shape[1], u.a, u.conv.bias))
+            return
         if u.train:
             # ONE pass for the partial sums (the convolution's slabs summed into ``a``, per-channel sum a / sum a^2 in
             # fp64 per row block); the normalising launch adds them up in its prologue -- 2 launches per unit
@@ -59,6 +66,8 @@ class _Forward:
         of a deep net by ~1e-4 of its max-norm: not an error of either, but it would drown the comparison below."""
         for u in self.units:
             u.a.copy_(u.ra)
+            if u.gn is not None:  # (the statistics of the model's map -- its output is overwritten just below)
+                self._launch("hf_gn_forward", *gn_forward_args(u, u.a, 1, 0))
             u.y.copy_(u.ry)
             if u.yout2 is not None:
                 u.yout2.copy_(u.ry)

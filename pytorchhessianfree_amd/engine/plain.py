@@ -12,6 +12,7 @@ from .dense import _Layer
 from .problems import affine_train_args
 
 MAX_TAIL_ROWS, MAX_CLASSES = 256, 1024  # the dense kernels' row limit; the loss head's class limit
+GN_LDS_FLOATS = 16384  # the (sample, span of groups) block one workgroup of hf_gn.hip keeps in LDS
 
 
 class PlainStackEngine(_ConvEngine):
@@ -75,7 +76,16 @@ class PlainStackEngine(_ConvEngine):
     one after the other through the one-term launch's staging area -- the same plan and slab count, no extras slabs
     (``nD = sD``, ``nW = sW``); a frozen weight or a tangent-free input keeps the one-term launch.  With
     ``HF_DIAG_EF_BATCHED=1`` its weight entries of ``diag_ef`` come from ONE ``hf_gconv2d_nhwc_sqsum_slabs`` launch on the
-    whole batch.  All of it opt-in: against the autograd route only ``diag_ef`` is measured, no product."""
+    whole batch.  All of it opt-in: against the autograd route only ``diag_ef`` is measured, no product.
+
+    GroupNorm units (``HF_GN_ENGINE=1``): ``Conv2d`` (dense, depthwise or grouped; a bias is a parameter of its own)
+    ``GroupNorm(affine=True) [ReLU]`` is one unit anywhere a bias unit may stand, groups of channel quads.  A statistic
+    belongs to one (sample, group), so one workgroup of hf_gn.hip owns a sample x span of whole groups, sums the split-K slabs
+    of its block once into LDS (at most 16 384 floats) and takes every reduction from it: ``hf_gn_forward`` (exact two-pass
+    variance), ``hf_gn_act_tangent`` and ``hf_gn_act_adjoint`` are ONE launch each -- 4 launches per unit and product, as a
+    bias unit -- and the adjoint leaves the parameters' sums as one partial row per sample (``u.rb = n``), which the gather
+    adds and ``diag_ef`` squares in one ``hf_gn_rows_sqsum`` launch (train-mode BatchNorm has no per-sample gradients).  GGN
+    products, one process, no ``MaxPool2d`` behind such a unit.  Opt-in; measured on one net."""
 
     mode = ("fused curvature engine (plain conv-ReLU stack): own deterministic convolutions (split-K slabs summed "
             "by the consumer kernel), bias / ReLU / max-pool fused, 4 launches per layer")
@@ -126,7 +136,10 @@ class PlainStackEngine(_ConvEngine):
                 u = _Unit(f"conv{len(units)}", m, bn)
                 u.depthwise, u.grouped = depthwise, m.groups != 1 and not depthwise
                 y, u.relu = cy, False
-                if bn is not None:
+                if type(nxt) is nn.GroupNorm:
+                    y, u.relu = self._layout_gn(u, nxt, cy, leaves[i + 2] if i + 2 < len(leaves) else None)
+                    i += 2 if u.relu else 1
+                elif bn is not None:
                     y, u.relu = self._layout_bn(u, bn, cy)
                     i += 1
                     if u.relu:  # (modelprep fused the following ReLU module into the layer: its output is the unit's)
@@ -144,7 +157,10 @@ class PlainStackEngine(_ConvEngine):
                 # ``diag_ef`` take the scale's sums from it)
                 u.a, u.y, u.needs_g = _cl(cy), _cl(y), bn is not None
                 u.pw = self._param(m.weight)
-                if bn is None:
+                if u.gn is not None:  # (the convolution's bias: a parameter of its own, with sums of its own)
+                    u.pg, u.pb = self._param(u.gn.weight), self._param(u.gn.bias)
+                    u.pcb = self._param(m.bias) if m.bias is not None else None
+                elif bn is None:
                     u.pb = self._param(m.bias) if m.bias is not None else None
                     u.pg = None
                 else:
@@ -157,6 +173,8 @@ class PlainStackEngine(_ConvEngine):
                 where = f"MaxPool2d behind {units[-1].name}" if units else "MaxPool2d in front of the first convolution"
                 if not units or units[-1].pool is not None:
                     raise _Unsupported(f"{where}: a pool must directly follow a convolution (and its ReLU)")
+                if units[-1].gn is not None:
+                    raise _Unsupported(f"{where}: a pool behind a GroupNorm unit is not covered")
                 if _pair(m.dilation) != [1, 1] or m.ceil_mode or m.return_indices:
                     raise _Unsupported(f"{where}: dilation / ceil_mode / return_indices are not covered")
                 px, py = records_of(m, with_input=True)
@@ -203,7 +221,8 @@ class PlainStackEngine(_ConvEngine):
         self.units, self.tail = units, units[-1]
         self.train_bn = any(u.train for u in units)
         self.model_ref, self._in_shape = model, tuple(x_in.shape)
-        used = {i for u in units + self.classifier for i in (u.pw, getattr(u, "pg", None), u.pb) if i is not None}
+        used = {i for u in units + self.classifier for i in (u.pw, getattr(u, "pg", None), u.pb, getattr(u, "pcb", None))
+                if i is not None}
         if used != set(range(len(self.params))):
             raise _Unsupported("the parameter list has entries the engine's layers do not cover")
         # frozen layers at the input end (round 6, as FusedGGNEngine._mark_dead_prefix): dead for both sweeps; the first
@@ -283,6 +302,36 @@ class PlainStackEngine(_ConvEngine):
         if bres is not None or not _same(bx, cy):
             raise _Unsupported(f"{u.name}: the BatchNorm2d does not consume the convolution's output")
         return by, bool(brelu)
+
+    def _layout_gn(self, u, gn, cy, nxt):
+        """The GroupNorm behind ``u``'s convolution (output record ``cy``) and the layer ``nxt`` behind it: the unit's output
+        record and ReLU flag.  What the kernels of hf_gn.hip take: opted in, affine, groups of channel quads, a (sample,
+        group) block of ``h*w*cg`` floats within one workgroup's LDS; GGN products, one process."""
+        n, c, h, w = cy.shape
+        cg = c // gn.num_groups
+        what = f"{u.name}: GroupNorm({gn.num_groups}, {c})"
+        if os.environ.get("HF_GN_ENGINE", "0") != "1":
+            raise _Unsupported(f"{what}: GroupNorm units are opt-in (HF_GN_ENGINE=1)")
+        if not gn.affine:
+            raise _Unsupported(f"{what}: affine=False is not covered")
+        if cg % 4:
+            raise _Unsupported(f"{what}: {cg} channels per group (the kernels take multiples of 4)")
+        if h * w * cg > GN_LDS_FLOATS:
+            raise _Unsupported(f"{what}: a block of h*w*span = {h * w} * {cg} = {h * w * cg} floats (one workgroup's LDS holds "
+                               f"{GN_LDS_FLOATS})")
+        if self.hessian:
+            raise _Unsupported(f"{what}: Hessian products through a GroupNorm unit are not covered")
+        if self.group is not None:
+            raise _Unsupported(f"{what}: data parallelism is not covered for a GroupNorm unit")
+        gx, gy = records_of(gn, with_input=True)
+        if not _same(gx, cy):
+            raise _Unsupported(f"{what}: it does not consume the convolution's output")
+        u.gn = gn
+        if type(nxt) is nn.ReLU and not nxt.inplace:
+            rx, ry = records_of(nxt, with_input=True)
+            if _same(rx, gy):
+                return ry, True
+        return gy, False
 
     # ---- classifier tail: layout -----------------------------------------------------------------
     def _layout_tail_layer(self, leaves, i, dense, cur):
@@ -576,6 +625,11 @@ class PlainStackEngine(_ConvEngine):
             sig = sig + (tuple(bool(m.training and m.p > 0) for m in self._dropouts),)
         if any(u.in_place for u in self.units):  # (read in place: a frozen one's address is a kernel argument)
             sig = sig + (tuple(u.conv.weight.data_ptr() for u in self.units if u.in_place),)
+        if any(u.gn is not None for u in self.units):  # (kernel arguments: the groups, eps, the frozen tensors' addresses)
+            sig = sig + (tuple((id(u.gn), u.gn.num_groups, u.gn.eps)
+                               + tuple(t.data_ptr() for t, k in ((u.gn.weight, u.pg), (u.gn.bias, u.pb), (u.conv.bias, u.pcb))
+                                       if k is None and t is not None)
+                               for u in self.units if u.gn is not None),)
         if not self.classifier:
             return sig
         return sig + (tuple((id(u.lin), u.act) for u in self.classifier), tuple(t.data_ptr() for t in self._sig_tail))

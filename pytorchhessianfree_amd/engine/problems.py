@@ -113,6 +113,45 @@ def bn_adjoint_v4_args(q):
             q.n * q.hw, q.c)
 
 
+# ---- GroupNorm units (hf_gn.hip; positional entry points, no struct) ---------------------------------------------------
+def _gn_dims(u):
+    n, k, oh, ow = u.a.shape
+    return n, oh * ow, k, u.gn.num_groups
+
+
+def gn_forward_args(u, a, splits, slab, a_out=None, conv_bias=None):
+    """``hf_gn_forward``: statistics and ``y = act(gamma * xhat + beta)`` from the slabs ``a`` (+ the convolution's bias),
+    into ``u.y`` and the x half of the consumer's operand; the summed map -> ``a_out``.  ``splits = 1`` on a given map,
+    no ``a_out``: the statistics and the output of that map."""
+    k = u.a.shape[1]
+    return (u.y, u.yout2, 2 * k if u.yout2 is not None else 0, a_out, u.gn_mean, u.gn_rstd, a, splits, slab, conv_bias,
+            u.gn.weight, u.gn.bias, float(u.gn.eps), 1 if u.relu else 0, *_gn_dims(u))
+
+
+def gn_tangent_args(u, v_cb, vg, vb):
+    """``hf_gn_act_tangent``: the unit's tangent from the tangent convolution's slabs into the consumer's operand; ``v_cb`` /
+    ``vg`` / ``vb``: the convolution bias's, the scale's and the shift's slice of ``v`` (None where frozen)."""
+    return (u.tout, u.tout_ld, u.tbuf, u.sT, u.tbuf.shape[1], v_cb, u.a, u.gn_mean, u.gn_rstd, u.gn.weight, vg, vb,
+            u.y if u.relu else None, *_gn_dims(u))
+
+
+def gn_adjoint_args(u, srcs):
+    """``hf_gn_act_adjoint``: ``u.ga`` (and ``u.g`` where the unit keeps it) from the one cotangent of the unit's output, and
+    the per-sample rows of the trainable ones among scale, shift and convolution bias."""
+    (gy, splits, slab), = srcs
+    return (u.ga, u.g if u.needs_g else None, u.gw if u.pg is not None else None, u.gb if u.pb is not None else None,
+            u.gcb if u.pcb is not None else None, gy, splits, slab, u.a, u.gn_mean, u.gn_rstd, u.gn.weight,
+            u.y if u.relu else None, *_gn_dims(u))
+
+
+def gn_rows_sqsum_args(u, out, offs, pre):
+    """``hf_gn_rows_sqsum``: the unit's entries of ``diag_ef`` straight into ``out`` (``offs``: the parameters' offsets) from
+    the per-sample rows the adjoint launch left, each scaled by ``pre`` before it is squared."""
+    tabs = [x for pi, rows in ((u.pg, u.gw), (u.pb, u.gb), (u.pcb, getattr(u, "gcb", None)))
+            for x in ((out[offs[pi]:], rows) if pi is not None else (None, None))]
+    return (*tabs, float(pre), u.a.shape[0], u.a.shape[1])
+
+
 # ---- hf_conv_problem: every slab-mode convolution, alone, grouped or as a D + W pair --------------------------------
 def conv_problem(direction, out, act, mat, geo, splits, act_ld=0, out_c=0, mat_ld=0):
     """Direction 0 (forward / tangent), 1 (data gradient) or 2 (weight gradient) of the layer ``geo``: ``out`` receives

@@ -7,7 +7,7 @@ import os
 
 from .. import _lib
 from .problems import (affine_args, affine_problem, affine_train_args, affine_train_problem, conv_args, conv_bnsum,
-                       conv_problem)
+                       conv_problem, gn_tangent_args)
 
 
 def head_fused_shape_ok(rows, features, classes):
@@ -54,6 +54,11 @@ class _TangentSweep:
         """t_y = mask * (sum(T slabs) * w*rstd + xhat * v_w + v_b + add), into the consumer's operand."""
         n, k, oh, ow = u.a.shape
         vg, vb = self._scale_shift_tangent(u, v)
+        if u.gn is not None:
+            # GroupNorm: t_y = mask * (w*rstd * (t_a - E[t_a] - xhat * E[xhat t_a]) + xhat * v_w + v_b), the two means over
+            # the (sample, group) block taken inside the launch; t_a: the slabs' sum + the convolution bias's tangent
+            self._launch("hf_gn_act_tangent", *gn_tangent_args(u, self._param_slice(v, u.pcb, k), vg, vb))
+            return
         if u.train:
             # reduction, then the elementwise pass adds the partial rows up in its prologue
             parts = self._train_tangent_sums(u)

@@ -313,6 +313,25 @@ class GroupSmall(nn.Module):
         return torch.flatten(_batched(self.net, x), -3)
 
 
+class GNSmall(nn.Module):
+    """The smallest plain stack with GroupNorm units: conv3(3->8, pad 1) GroupNorm(2, 8) ReLU (the im2col'd first layer),
+    conv3(8->24, stride 2, pad 1, with a bias of its own) GroupNorm(3, 24) ReLU, conv1(24->16) GroupNorm(1, 16) without a
+    ReLU, conv1(16->classes), global average pool."""
+
+    def __init__(self, num_classes=12):
+        super().__init__()
+        self.net = nn.Sequential(
+            nn.Conv2d(3, 8, 3, 1, 1, bias=False), nn.GroupNorm(2, 8), nn.ReLU(),
+            nn.Conv2d(8, 24, 3, 2, 1), nn.GroupNorm(3, 24), nn.ReLU(),
+            nn.Conv2d(24, 16, 1, bias=False), nn.GroupNorm(1, 16),
+            nn.Conv2d(16, num_classes, 1, bias=False),
+            nn.AdaptiveAvgPool2d((1, 1)),
+        )
+
+    def forward(self, x):
+        return torch.flatten(_batched(self.net, x), -3)
+
+
 class GroupStack(nn.Module):
     """A ResNeXt-style plain stack (no shortcuts) for 32x32 inputs: conv3(3->64, pad 1) ReLU, then three bottleneck units
     ``conv1(c->w) ReLU, g3x3(w->w, groups of 16 channels, pad 1) ReLU, conv1(w->w) ReLU`` of width 128 (stride 1), 256
@@ -546,6 +565,23 @@ def group_small(batch_size=3, seed=0, device="cpu", data_seed=None, bn=False):
     model = seed_batchnorm(GroupSmall(12, bn), seed).eval()
     g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
     inputs = torch.rand(batch_size, 3, 9, 7, generator=g)
+    targets = torch.randint(0, 12, (batch_size,), generator=g)
+    return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
+
+
+def gn_small(batch_size=3, seed=0, device="cpu", data_seed=None):
+    """``GNSmall`` in eval mode with seeded GroupNorm scales and shifts; inputs U[0,1) [B,3,10,9], 12 classes (the
+    convolutions' kernels take channel counts in multiples of 4), CE-mean."""
+    torch.manual_seed(seed)
+    model = GNSmall(12).eval()
+    g = torch.Generator().manual_seed(seed + 1000)
+    with torch.no_grad():
+        for m in model.modules():
+            if isinstance(m, nn.GroupNorm):
+                m.weight.copy_(0.5 + torch.rand(m.weight.shape, generator=g))
+                m.bias.copy_(0.2 * torch.randn(m.bias.shape, generator=g))
+    g = torch.Generator().manual_seed(seed if data_seed is None else data_seed)
+    inputs = torch.rand(batch_size, 3, 10, 9, generator=g)
     targets = torch.randint(0, 12, (batch_size,), generator=g)
     return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
 
