@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 32
+#define HF_ABI_VERSION 33
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -1287,7 +1287,7 @@ int hf_gconv2d_nhwc_sqsum_slabs(void* out, const void* ga, const void* x, int64_
  * conv -> GroupNorm(affine) -> [ReLU], fp32 NHWC [rows = n*hw, c], `groups` groups of cg = c / groups channels, statistics
  * mean / rstd [n, groups].  One workgroup owns one sample x one span of whole groups (hf_gn_plan returns the span's
  * channels), sums the split-K slabs of its hw x span block once into LDS and takes every reduction from it, so forward,
- * tangent and adjoint are ONE launch each.  Lanes keep fp32 partial sums over fixed sets of elements, everything behind
+ * tangent, adjoint and the adjoint's tangent are ONE launch each.  Lanes keep fp32 partial sums over fixed sets of elements, everything behind
  * them is fp64 in an order that depends on the shape alone: no atomics, two launches give the same bits.  The arithmetic
  * chains and their roundings stand in hf_gn.hip's header.
  *
@@ -1306,6 +1306,16 @@ int hf_gconv2d_nhwc_sqsum_slabs(void* out, const void* ga, const void* x, int64_
  *   hf_gn_act_adjoint  g = m * (sum of gy's slabs) -> g (nullable);  ga = rstd*(gamma g - E[gamma g] - xh*E[gamma g xh]);
  *                      per-sample rows [n, c]: gw_rows = sum_hw g*xh, gb_rows = sum_hw g, gcb_rows = sum_hw ga (the
  *                      convolution bias's); each nullable.  hf_pack_ex (splits = (n, c)) adds the rows.
+ *   hf_gn_act_adjoint2 (ABI 33) the TANGENT of hf_gn_act_adjoint -- the unit's second-order half of a Hessian product --
+ *                      in one launch.  g = the step's first-order masked cotangent (a map, as given), p = gamma*g;
+ *                      t = sum of t_a's slabs (+ v_conv_bias[c]);  g' = m * (sum of gy2's slabs);  p' = v_gamma*g + gamma*g':
+ *                        T1 = E[t]   Tx = E[xh t]    tau = (t - T1) - xh*Tx
+ *                        P1 = E[p]   Px = E[p xh]    ga  = rstd*((p - P1) - xh*Px)
+ *                        Q1 = E[p']  Qx = E[p' xh]   Qt  = rstd*E[p tau]
+ *                        ga2 = rstd*((p' - Q1) - xh*(Qx + Qt) - (rstd*tau)*Px) - (rstd*Tx)*ga
+ *                      per-sample rows [n, c], each nullable: gb_rows = sum_hw g', gw_rows = sum_hw (g'*xh + g*rstd*tau),
+ *                      gcb_rows = sum_hw ga2.  v_gamma / v_conv_bias / mask_src: NULL where frozen / absent.  The blocks
+ *                      of g' and t are both resident: the launch takes the smallest of three LDS sizes that holds them.
  *   hf_gn_rows_sqsum   out_*[c] = sum_n (pre * rows_*[n][c])^2 for up to three tables (NULL: skipped; not all): the
  *                      GroupNorm entries of the diagonal empirical Fisher.  out_* on any 4-byte boundary.
  */
@@ -1320,6 +1330,11 @@ int hf_gn_act_tangent(void* out, int64_t out_ld, const void* t_a, int splits, in
 int hf_gn_act_adjoint(void* ga, void* g, void* gw_rows, void* gb_rows, void* gcb_rows, const void* gy, int splits,
                       int64_t slab_stride, const void* a, const void* mean, const void* rstd, const void* gamma,
                       const void* mask_src, int64_t n, int64_t hw, int64_t c, int64_t groups, int dtype, void* stream);
+int hf_gn_act_adjoint2(void* ga2, void* gw_rows, void* gb_rows, void* gcb_rows, const void* gy2, int splits,
+                       int64_t slab_stride, const void* t_a, int t_splits, int64_t t_slab_stride, const void* v_conv_bias,
+                       const void* a, const void* g, const void* mean, const void* rstd, const void* gamma,
+                       const void* v_gamma, const void* mask_src, int64_t n, int64_t hw, int64_t c, int64_t groups, int dtype,
+                       void* stream);
 int hf_gn_rows_sqsum(void* out_w, const void* rows_w, void* out_b, const void* rows_b, void* out_cb, const void* rows_cb,
                      double pre, int64_t n, int64_t c, int dtype, void* stream);
 

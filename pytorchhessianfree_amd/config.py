@@ -192,6 +192,11 @@ SWITCHES = {
                      "default: measured on one net only (1.6x the captured autograd route, profiles/gn_stack.jsonl) -- "
                      "without it such a net keeps the autograd path",
                      "tests/test_gn_engine_gpu.py::test_eval_point_against_float64"),
+    "HF_GN_HESSIAN": ("0", "1: with HF_GN_ENGINE=1, curvature_opt='hessian' on a net with GroupNorm units takes the plain-"
+                      "stack engine (the second-order half of a GroupNorm unit in one launch, hf_gn_act_adjoint2: the "
+                      "blocks of g' and t both resident in LDS) instead of the autograd operator; opt-in like the engine "
+                      "it stands on (profiles/gn_hessian.jsonl)",
+                      "tests/test_gn_hessian_engine_gpu.py::test_hessian_products_against_float64"),
     "HF_CHUNKED_ALLREDUCE": ("auto", "0 / 1: force the single-graph resp. the two-phase data-parallel product",
                              "tests/test_distributed_gpu.py::test_step_two_ranks_engine_session_equals_cpu_whole_batch"),
     "HF_DIRECT_RCCL": ("1", "0: every collective through torch.distributed (no communicator of the package's own)",

@@ -1,6 +1,6 @@
 // hf_gn.hip -- GroupNorm units of the plain-stack engine (engine/plain.py): conv -> GroupNorm(affine) -> [ReLU].  Forward,
-// tangent and adjoint of the normalisation are ONE launch each, and the per-sample parameter rows of the adjoint make the
-// diagonal empirical Fisher one more.  fp32, wave64, NHWC [rows = n*hw, c], `groups` groups of cg = c / groups channels,
+// tangent and adjoint of the normalisation are ONE launch each -- the adjoint's own tangent, a Hessian product's second-order
+// half, included -- and the per-sample parameter rows of the adjoint make the diagonal empirical Fisher one more.  fp32, wave64, NHWC [rows = n*hw, c], `groups` groups of cg = c / groups channels,
 // cg % 4 == 0; statistics mean / rstd [n, groups].  Plain C++/HIP, no atomics: two launches on the same operands agree bitwise.
 //
 // Why a design of its own.  hf_bn.hip reduces per CHANNEL over all rows: its workgroups share a channel column and a
@@ -52,8 +52,23 @@
 //   m1       = fp32( fp64 sum of the chains of p / (hw*cg) );  mx = fp32( .. of the chains of p * xh .. )
 //   ga       = rstd * ((p - m1) - xh * mx)                                              4 behind p, xh, m1, mx
 //   gb_rows[n][c] = fp32( fp64 sum over the slots of the chains of g ),  gw_rows: of g * xh (1 more),  gcb_rows: of ga
+// hf_gn_act_adjoint2  (the tangent of hf_gn_act_adjoint inside a Hessian product; mu, rstd and g -- the step's first-order
+//                      masked cotangent -- as given; g and a are read from global memory in every pass)
+//   g'       = (y > 0 | no ReLU) ? s of the second sweep's cotangent slabs : 0          resident block 1
+//   t        = s of the tangent convolution's slabs [+ v_conv_bias[c]]                  resident block 2
+//   xh       = (a - mu) * rstd  (2);   p = gamma[c] * g  (1);   p' = gamma[c] * g'  (1)  [p' = v_gamma[c] * g + p'  (2)]
+//   round 1:   T1, Tx, P1, Px, Q1, Qx = fp32( fp64 sum of the chains of t, xh * t, p, p * xh, p', p' * xh / (hw*cg) )
+//   tau      = (t - T1) - xh * Tx                                                        3 behind t, xh, T1, Tx
+//   round 2:   Qt = rstd * fp32( fp64 sum of the chains of p * tau / (hw*cg) )          (taken directly: no cancelling form)
+//   Qs       = Qx + Qt  (1);   rT = rstd * Tx  (1);   rt = rstd * tau  (1);   ga = rstd * ((p - P1) - xh * Px)  (4)
+//   ga'      = rstd * (((p' - Q1) - xh * Qs) - rt * Px) - rT * ga                        8 behind p', xh, rt, ga, Q1, Qs, Px, rT
+//   gb_rows[n][c] = fp32( fp64 sum over the slots of the chains of g' ),  gw_rows: of g' * xh + g * rt (3 more),
+//   gcb_rows: of ga'
+//   Two blocks resident (g' and t), so the LDS is sized to the launch: instantiations for blocks of up to 2 048, 8 192 and
+//   16 384 floats (25 / 73 / 137 KB with the reductions' scratch; gfx950 has 160 KB per CU), static, the smallest that holds
+//   the plan's hw x span.
 // hf_gn_rows_sqsum
-//   out[c]   = fp32( fp64 sum over the samples, ascending, of fp32(t * t),  t = fp32(pre * rows[n][c]) )
+//   out[c]   =fp32( fp64 sum over the samples, ascending, of fp32(t * t),  t = fp32(pre * rows[n][c]) )
 #include "hf_common.h"
 
 #include <math.h>
@@ -152,6 +167,22 @@ __device__ __forceinline__ void gn_stage(F4* tile, const GnBlock& b, const float
       for (int k = 0; k < 4; ++k) v.e[k] += e.e[k];
     }
     if (copy) *reinterpret_cast<F4*>(copy + gi) = v;
+    tile[q] = v;
+  }
+}
+
+// the same for a cotangent: g = mask * (sum of the slabs), `mask_src` (nullable): the unit's output, y > 0
+__device__ __forceinline__ void gn_stage_masked(F4* tile, const GnBlock& b, const float* gy, int splits, long long slab,
+                                                const float* mask_src, int c) {
+  for (int q = threadIdx.x; q < b.nq; q += BLOCK) {
+    const int p = q / b.sq, j = q - p * b.sq;
+    const long long gi = b.base + (long long)p * c + 4 * j;
+    F4 v = slab_sum<8>(ld4(gy + gi), gy, gi, splits, slab);
+    if (mask_src) {
+      const F4 m = ld4(mask_src + gi);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v.e[k] = m.e[k] > 0.f ? v.e[k] : 0.f;
+    }
     tile[q] = v;
   }
 }
@@ -326,18 +357,7 @@ __global__ __launch_bounds__(BLOCK) void k_gn_act_adjoint(
   __shared__ double rsum[BLOCK * 4];
   __shared__ float sm1[GN_MAX_GPS], smx[GN_MAX_GPS];
   const GnBlock b = gn_block(hw, c, groups, cg, gps);
-  // g = mask * (sum of the slabs), resident
-  for (int q = threadIdx.x; q < b.nq; q += BLOCK) {
-    const int p = q / b.sq, j = q - p * b.sq;
-    const long long gi = b.base + (long long)p * c + 4 * j;
-    F4 v = slab_sum<8>(ld4(gy + gi), gy, gi, splits, slab);
-    if (mask_src) {
-      const F4 m = ld4(mask_src + gi);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v.e[k] = m.e[k] > 0.f ? v.e[k] : 0.f;
-    }
-    tile[q] = v;
-  }
+  gn_stage_masked(tile, b, gy, splits, slab, mask_src, c);  // g, resident
   __syncthreads();
   const double cnt = (double)hw * (double)cg;
   const float* stat_mu = mean + (long long)b.nb * groups + b.g0;
@@ -391,6 +411,137 @@ __global__ __launch_bounds__(BLOCK) void k_gn_act_adjoint(
         }
         *reinterpret_cast<F4*>(ga_out + gi) = o;
         if (g_out) *reinterpret_cast<F4*>(g_out + gi) = g;
+      }
+    }
+    const long long at = (long long)b.nb * c + b.ch0 + 4 * j;
+    if (gw_rows) gn_row_store(gw_rows, sw, rsum, slots, cols, slot, jl, act, at);
+    if (gb_rows) gn_row_store(gb_rows, sb, rsum, slots, cols, slot, jl, act, at);
+    if (gcb_rows) gn_row_store(gcb_rows, sc, rsum, slots, cols, slot, jl, act, at);
+  }
+}
+
+// ---- the tangent of the adjoint (a Hessian product's second sweep): TWO resident blocks ---------------------------------
+// what the three passes of k_gn_act_adjoint2 share per element: xh, p = gamma g and p' = v_gamma g + gamma g'
+struct Gn2Point {
+  float xh, p, pp;
+};
+
+__device__ __forceinline__ Gn2Point gn2_point(float x, float g, float gp, float w, float vg, bool has_vg, float mu, float rs) {
+  Gn2Point o;
+  o.xh = (x - mu) * rs;
+  o.p = w * g;
+  o.pp = w * gp;
+  if (has_vg) o.pp = vg * g + o.pp;
+  return o;
+}
+
+// per-group results of the two rounds, as the elementwise part reads them
+enum { G2_T1, G2_TX, G2_P1, G2_PX, G2_Q1, G2_QS, G2_RT, G2_STATS };
+
+// FLOATS: the floats of ONE resident block this instantiation reserves (hw * span <= FLOATS); the launch takes the smallest
+template <int FLOATS>
+__global__ __launch_bounds__(BLOCK) void k_gn_act_adjoint2(
+    float* __restrict__ ga2_out, float* __restrict__ gw_rows, float* __restrict__ gb_rows, float* __restrict__ gcb_rows,
+    const float* __restrict__ gy2, int splits, long long slab, const float* __restrict__ ta, int t_splits, long long t_slab,
+    const float* __restrict__ v_cb, const float* __restrict__ a, const float* __restrict__ g1,
+    const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
+    const float* __restrict__ v_gamma, const float* __restrict__ mask_src, int hw, int c, int groups, int cg, int gps) {
+  __shared__ F4 tg[FLOATS / 4];  // g' = mask * (sum of the second sweep's cotangent slabs)
+  __shared__ F4 tt[FLOATS / 4];  // t  = sum of the tangent convolution's slabs [+ v_conv_bias]
+  __shared__ double red[6 * WAVES];
+  __shared__ double rsum[BLOCK * 4];
+  __shared__ float stats[G2_STATS][GN_MAX_GPS];
+  const GnBlock b = gn_block(hw, c, groups, cg, gps);
+  gn_stage_masked(tg, b, gy2, splits, slab, mask_src, c);
+  gn_stage(tt, b, ta, t_splits, t_slab, v_cb, nullptr, c);
+  __syncthreads();
+  const double cnt = (double)hw * (double)cg;
+  const float* stat_mu = mean + (long long)b.nb * groups + b.g0;
+  const float* stat_rs = rstd + (long long)b.nb * groups + b.g0;
+  const bool has_vg = v_gamma != nullptr;
+  const F4 zero = {{0.f, 0.f, 0.f, 0.f}};
+  for (int it = 0; it < b.iters; ++it) {
+    const int gl = b.team + it * b.nteams;
+    const bool on = gl < b.ng;
+    const int gq = on ? hw * b.qpg : 0;
+    const float mu = on ? stat_mu[gl] : 0.f, rs = on ? stat_rs[gl] : 0.f;
+    // round 1: T1, Tx, P1, Px, Q1, Qx
+    F4 s[6] = {zero, zero, zero, zero, zero, zero};
+    for (int e = b.lt; e < gq; e += b.T) {
+      const int p = e / b.qpg, jj = e - p * b.qpg, j = gl * b.qpg + jj;
+      const long long gi = b.base + (long long)p * c + 4 * j;
+      const F4 gp = tg[p * b.sq + j], t = tt[p * b.sq + j], x = ld4(a + gi), g = ld4(g1 + gi);
+      const F4 w = ld4s(gamma + b.ch0 + 4 * j), vg = has_vg ? ld4s(v_gamma + b.ch0 + 4 * j) : zero;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const Gn2Point o = gn2_point(x.e[k], g.e[k], gp.e[k], w.e[k], vg.e[k], has_vg, mu, rs);
+        s[0].e[k] += t.e[k];
+        s[1].e[k] += o.xh * t.e[k];
+        s[2].e[k] += o.p;
+        s[3].e[k] += o.p * o.xh;
+        s[4].e[k] += o.pp;
+        s[5].e[k] += o.pp * o.xh;
+      }
+    }
+    double v[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) v[i] = quad_sum(s[i]);
+    gn_team_sum<6>(v, red, b);
+    const float T1 = (float)(v[0] / cnt), Tx = (float)(v[1] / cnt);
+    // round 2: E[p * tau], from the resident block, T1 and Tx known (no E[p t] - T1 P1 - Tx Px: that form cancels)
+    F4 s2 = zero;
+    for (int e = b.lt; e < gq; e += b.T) {
+      const int p = e / b.qpg, jj = e - p * b.qpg, j = gl * b.qpg + jj;
+      const long long gi = b.base + (long long)p * c + 4 * j;
+      const F4 t = tt[p * b.sq + j], x = ld4(a + gi), g = ld4(g1 + gi), w = ld4s(gamma + b.ch0 + 4 * j);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float xh = (x.e[k] - mu) * rs, tau = (t.e[k] - T1) - xh * Tx;
+        s2.e[k] += (w.e[k] * g.e[k]) * tau;
+      }
+    }
+    double v2[1] = {quad_sum(s2)};
+    gn_team_sum<1>(v2, red, b);
+    if (on && b.lt == 0) {
+      const float Qt = rs * (float)(v2[0] / cnt);
+      stats[G2_T1][gl] = T1;
+      stats[G2_TX][gl] = Tx;
+      stats[G2_P1][gl] = (float)(v[2] / cnt);
+      stats[G2_PX][gl] = (float)(v[3] / cnt);
+      stats[G2_Q1][gl] = (float)(v[4] / cnt);
+      stats[G2_QS][gl] = (float)(v[5] / cnt) + Qt;
+      stats[G2_RT][gl] = rs * Tx;
+    }
+  }
+  __syncthreads();
+  // the elementwise part and the per-sample rows, laid out as in k_gn_act_adjoint
+  const int cols = b.sq < BLOCK ? b.sq : BLOCK, slots = BLOCK / cols;
+  const int slot = threadIdx.x / cols, jl = threadIdx.x - slot * cols;
+  for (int j0 = 0; j0 < b.sq; j0 += cols) {
+    const int j = j0 + jl;
+    const bool act = slot < slots && j < b.sq;
+    F4 sb = zero, sw = zero, sc = zero;
+    if (act) {
+      const int gl = j / b.qpg;
+      const float mu = stat_mu[gl], rs = stat_rs[gl];
+      const float T1 = stats[G2_T1][gl], Tx = stats[G2_TX][gl], P1 = stats[G2_P1][gl], Px = stats[G2_PX][gl];
+      const float Q1 = stats[G2_Q1][gl], Qs = stats[G2_QS][gl], rT = stats[G2_RT][gl];
+      const F4 w = ld4s(gamma + b.ch0 + 4 * j), vg = has_vg ? ld4s(v_gamma + b.ch0 + 4 * j) : zero;
+      for (int p = slot; p < hw; p += slots) {
+        const long long gi = b.base + (long long)p * c + 4 * j;
+        const F4 gp = tg[p * b.sq + j], t = tt[p * b.sq + j], x = ld4(a + gi), g = ld4(g1 + gi);
+        F4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const Gn2Point e = gn2_point(x.e[k], g.e[k], gp.e[k], w.e[k], vg.e[k], has_vg, mu, rs);
+          const float rt = rs * ((t.e[k] - T1) - e.xh * Tx);
+          const float ga = rs * ((e.p - P1) - e.xh * Px);
+          o.e[k] = rs * (((e.pp - Q1) - e.xh * Qs) - rt * Px) - rT * ga;
+          sb.e[k] += gp.e[k];
+          sw.e[k] += gp.e[k] * e.xh + g.e[k] * rt;
+          sc.e[k] += o.e[k];
+        }
+        *reinterpret_cast<F4*>(ga2_out + gi) = o;
       }
     }
     const long long at = (long long)b.nb * c + b.ch0 + 4 * j;
@@ -494,6 +645,33 @@ int hf_gn_act_adjoint(void* ga, void* g, void* gw_rows, void* gb_rows, void* gcb
                      (float*)gw_rows, (float*)gb_rows, (float*)gcb_rows, (const float*)gy, splits, (long long)slab_stride,
                      (const float*)a, (const float*)mean, (const float*)rstd, (const float*)gamma, (const float*)mask_src,
                      p.hw, p.c, p.groups, p.cg, p.gps);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+int hf_gn_act_adjoint2(void* ga2, void* gw_rows, void* gb_rows, void* gcb_rows, const void* gy2, int splits,
+                       int64_t slab_stride, const void* t_a, int t_splits, int64_t t_slab_stride, const void* v_conv_bias,
+                       const void* a, const void* g, const void* mean, const void* rstd, const void* gamma,
+                       const void* v_gamma, const void* mask_src, int64_t n, int64_t hw, int64_t c, int64_t groups, int dtype,
+                       void* stream) {
+  GnPlan p;
+  if (dtype != HF_F32 || gn_plan(p, n, hw, c, groups) != HF_OK) return HF_ERR_ARG;
+  if (!ga2 || !a || !g || !mean || !rstd || !gamma) return HF_ERR_ARG;
+  if (gn_slabs_ok(gy2, splits, slab_stride, p) != HF_OK || gn_slabs_ok(t_a, t_splits, t_slab_stride, p) != HF_OK)
+    return HF_ERR_ARG;
+  const void* al[] = {ga2, gw_rows, gb_rows, gcb_rows, gy2, t_a, a, g, mask_src};
+  if (gn_aligned(al) != HF_OK) return HF_ERR_ARG;
+  // LDS sized to the launch: three instantiations with static LDS (2 blocks of 8 / 32 / 64 KB + 9 KB of scratch), the
+  // smallest that holds the plan's block hw * span -- nothing to set at run time, and nothing a graph capture could meet
+  const int block = p.hw * p.gps * p.cg;
+  auto kernel = block <= GN_LDS_FLOATS / 8   ? k_gn_act_adjoint2<GN_LDS_FLOATS / 8>
+                : block <= GN_LDS_FLOATS / 2 ? k_gn_act_adjoint2<GN_LDS_FLOATS / 2>
+                                             : k_gn_act_adjoint2<GN_LDS_FLOATS>;
+  hipLaunchKernelGGL(kernel, dim3(p.spans, p.n), dim3(BLOCK), 0, (hipStream_t)stream, (float*)ga2, (float*)gw_rows,
+                     (float*)gb_rows, (float*)gcb_rows, (const float*)gy2, splits, (long long)slab_stride, (const float*)t_a,
+                     t_splits, (long long)t_slab_stride, (const float*)v_conv_bias, (const float*)a, (const float*)g,
+                     (const float*)mean, (const float*)rstd, (const float*)gamma, (const float*)v_gamma,
+                     (const float*)mask_src, p.hw, p.c, p.groups, p.cg, p.gps);
   HF_HIP(hipGetLastError());
   return HF_OK;
 }

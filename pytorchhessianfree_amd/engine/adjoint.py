@@ -5,7 +5,8 @@ Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overal
 
 from .. import _lib
 from .problems import (affine_args, affine_train_args, affine_train_problem, bn_adjoint_args, bn_adjoint_problem,
-                       bn_adjoint_v4_args, conv_args, conv_backward_args, conv_problem, gn_adjoint_args, problem)
+                       bn_adjoint_v4_args, conv_args, conv_backward_args, conv_problem, gn_adjoint2_args,
+                       gn_adjoint_args, problem)
 
 
 class _AdjointSweep:
@@ -35,13 +36,20 @@ class _AdjointSweep:
         second = self._second
         if u.pool is not None:  # (a pooled unit of a plain stack: bias / ReLU / pool adjoint in one launch)
             self._pool_adjoint(u, srcs)
+        elif second and u.gn is not None:
+            # GroupNorm inside a Hessian product: ONE launch is the whole tangent of the first-order adjoint -- u.gah and
+            # the complete second-order rows of scale, shift and convolution bias (formulas: csrc/hf_gn.hip)
+            self._extras_wait(srcs)
+            k = u.a.shape[1]
+            self._launch("hf_gn_act_adjoint2", *gn_adjoint2_args(u, srcs, self._param_slice(self._v, u.pcb, k),
+                                                                  self._param_slice(self._v, u.pg, k)))
         else:
             self._bn_adjoint(u, srcs, reduce_only=second and u.train)
         if not second:
             self._conv_adjoint(u)
             return
         # ---- Hessian product: the tangent of the backward sweep through this unit --------------------------
-        if u.bn is None:
+        if u.bn is None and u.gn is None:
             # a bias has no second-order term of its own: the convolutions read g_a itself.  (The chain's D + W launch
             # through the two-problem entry point -- the same pair of problems ``_conv_adjoint`` launches --, and in
             # sequence the extras BEHIND it: as the plain stack has always issued them)
@@ -60,7 +68,9 @@ class _AdjointSweep:
             v_gamma = self._zeros(k)
         if not self._extras_parallel:
             self._hessian_extras(u)
-        if u.train:
+        if u.gn is not None:
+            pass  # (u.gah is hf_gn_act_adjoint2's, above)
+        elif u.train:
             # batch statistics: the per-channel finalisation of the five row reductions (this pass's g_z' sums, the
             # tangent sweep's a' sums), then  g_a' = c0 g_a + c1 g_z + c2 g_z' + c3 a' + c4 xhat + c5
             rb = u.rb

@@ -197,9 +197,10 @@ class _Buffers:
                 u.dbuf = torch.empty((u.nD, u.x.numel()), dtype=f32, device=dev)
             if self.hessian:
                 u.ga1 = torch.empty_like(u.a)  # first-order cotangent of the convolution output (per step)
-                if u.bn is not None:
-                    u.g1 = torch.empty_like(u.a)   # ... and of the BatchNorm output (masked), per step
-                    u.gah = torch.empty_like(u.a)  # g_a' + g_z * rstd * v_gamma: what the convolutions' adjoints read
+                if u.bn is not None or u.gn is not None:
+                    u.g1 = torch.empty_like(u.a)   # ... and of the BatchNorm / GroupNorm output (masked), per step
+                    # g_a' + g_z * rstd * v_gamma (GroupNorm: hf_gn_act_adjoint2's ga'): what the convolutions' adjoints read
+                    u.gah = torch.empty_like(u.a)
                 if u.sD and not u.in_place:  # (a depthwise unit reads V in place)
                     # V as (I, H, W, O), per product (a frozen weight has V = 0: zeros, never scattered into)
                     u.vT = torch.zeros((c, r, s, k), dtype=f32, device=dev)
@@ -231,7 +232,8 @@ class _Buffers:
             # (deferred sums are taken of the STORED g, needed by a residual branch or not; a pooled unit's is its ga)
             if u.defer and u.g is None and u.pool is None:
                 u.g = torch.empty_like(u.a)
-            # (Hessian: the scale's second-order term arrives as `rb` more partial rows for hf_pack_ex to add)
+            # (Hessian: the scale's second-order term arrives as `rb` more partial rows for hf_pack_ex to add; a GroupNorm
+            # unit's second-order launch writes complete rows: no second set)
             u.gw_rows = u.rb * (2 if (self.hessian and u.bn is not None) else 1)
             if self.hessian and u.train:
                 u.gw_rows += 1  # (+ the closed-form share of the scale's second-order term: hf_bn_train_hessian_coeffs)

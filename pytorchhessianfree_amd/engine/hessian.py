@@ -16,7 +16,9 @@ class _HessianExtras:
         conv_W(t_x, g_a) as MORE SLABS of the same buffers (the consumers sum them anyway)."""
         if u.dead:  # (frozen, behind frozen layers only: no tangent reaches it, no cotangent is needed behind it)
             return
-        if u.bn is not None and not u.train:  # (train mode: the tangent sweep left this sum, engine/tangent.py)
+        # (train mode: the tangent sweep left this sum, engine/tangent.py; GroupNorm -- ``u.bn`` is None --: the scale's
+        # whole second-order row is hf_gn_act_adjoint2's)
+        if u.bn is not None and not u.train:
             self._scale_second_order_sum(u)
         if u.in_place:  # (both terms ride in the chain's own two-term launch: adjoint._in_place_second_order)
             return
@@ -98,8 +100,8 @@ class _HessianExtras:
 
     def _swap_first_order(self):
         """For the duration of a Hessian engine's gradient sweep: the sweep writes the first-order cotangents the step's
-        products read, ``ga1`` (and ``g1``, the masked one only a BatchNorm's second-order terms read)."""
+        products read, ``ga1`` (and ``g1``, the masked one only a BatchNorm's / GroupNorm's second-order terms read)."""
         for u in self.units:
-            if u.bn is not None:
+            if u.bn is not None or u.gn is not None:
                 u.g, u.g1 = u.g1, u.g
             u.ga, u.ga1 = u.ga1, u.ga

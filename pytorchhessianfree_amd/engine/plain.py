@@ -84,8 +84,12 @@ class PlainStackEngine(_ConvEngine):
     of its block once into LDS (at most 16 384 floats) and takes every reduction from it: ``hf_gn_forward`` (exact two-pass
     variance), ``hf_gn_act_tangent`` and ``hf_gn_act_adjoint`` are ONE launch each -- 4 launches per unit and product, as a
     bias unit -- and the adjoint leaves the parameters' sums as one partial row per sample (``u.rb = n``), which the gather
-    adds and ``diag_ef`` squares in one ``hf_gn_rows_sqsum`` launch (train-mode BatchNorm has no per-sample gradients).  GGN
-    products, one process, no ``MaxPool2d`` behind such a unit.  Opt-in; measured on one net."""
+    adds and ``diag_ef`` squares in one ``hf_gn_rows_sqsum`` launch (train-mode BatchNorm has no per-sample gradients).  One
+    process, no ``MaxPool2d`` behind such a unit.  Hessian products on top (``HF_GN_HESSIAN=1``): the tangent of the adjoint
+    is ONE launch too, ``hf_gn_act_adjoint2`` -- its seven (sample, group) means in two rounds from TWO resident blocks (the
+    second sweep's masked cotangent and the tangent convolution's sum), the cotangent ``u.gah`` the convolution's second-order
+    backward reads, and complete second-order rows of scale, shift and convolution bias -- so such a unit costs a Hessian
+    product the launches of a bias unit.  Opt-in; measured on one net."""
 
     mode = ("fused curvature engine (plain conv-ReLU stack): own deterministic convolutions (split-K slabs summed "
             "by the consumer kernel), bias / ReLU / max-pool fused, 4 launches per layer")
@@ -306,7 +310,8 @@ class PlainStackEngine(_ConvEngine):
     def _layout_gn(self, u, gn, cy, nxt):
         """The GroupNorm behind ``u``'s convolution (output record ``cy``) and the layer ``nxt`` behind it: the unit's output
         record and ReLU flag.  What the kernels of hf_gn.hip take: opted in, affine, groups of channel quads, a (sample,
-        group) block of ``h*w*cg`` floats within one workgroup's LDS; GGN products, one process."""
+        group) block of ``h*w*cg`` floats within one workgroup's LDS; one process; Hessian products only with
+        ``HF_GN_HESSIAN=1``."""
         n, c, h, w = cy.shape
         cg = c // gn.num_groups
         what = f"{u.name}: GroupNorm({gn.num_groups}, {c})"
@@ -319,8 +324,9 @@ class PlainStackEngine(_ConvEngine):
         if h * w * cg > GN_LDS_FLOATS:
             raise _Unsupported(f"{what}: a block of h*w*span = {h * w} * {cg} = {h * w * cg} floats (one workgroup's LDS holds "
                                f"{GN_LDS_FLOATS})")
-        if self.hessian:
-            raise _Unsupported(f"{what}: Hessian products through a GroupNorm unit are not covered")
+        if self.hessian and os.environ.get("HF_GN_HESSIAN", "0") != "1":
+            raise _Unsupported(f"{what}: Hessian products through a GroupNorm unit are not covered (opt-in on top of "
+                               "HF_GN_ENGINE=1: HF_GN_HESSIAN=1)")
         if self.group is not None:
             raise _Unsupported(f"{what}: data parallelism is not covered for a GroupNorm unit")
         gx, gy = records_of(gn, with_input=True)

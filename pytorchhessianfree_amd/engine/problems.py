@@ -144,6 +144,17 @@ def gn_adjoint_args(u, srcs):
             u.y if u.relu else None, *_gn_dims(u))
 
 
+def gn_adjoint2_args(u, srcs, v_cb, v_gamma):
+    """``hf_gn_act_adjoint2``: inside a Hessian product, ``u.gah`` and the second-order rows of the trainable ones among
+    scale, shift and convolution bias from the second sweep's cotangent ``srcs``, the tangent convolution's slabs (still in
+    ``u.tbuf``) and the step's first-order masked cotangent ``u.g1``; ``v_cb`` / ``v_gamma``: the vector's slices, None where
+    frozen."""
+    (gy, splits, slab), = srcs
+    return (u.gah, u.gw if u.pg is not None else None, u.gb if u.pb is not None else None,
+            u.gcb if u.pcb is not None else None, gy, splits, slab, u.tbuf, u.sT, u.tbuf.shape[1], v_cb, u.a, u.g1,
+            u.gn_mean, u.gn_rstd, u.gn.weight, v_gamma, u.y if u.relu else None, *_gn_dims(u))
+
+
 def gn_rows_sqsum_args(u, out, offs, pre):
     """``hf_gn_rows_sqsum``: the unit's entries of ``diag_ef`` straight into ``out`` (``offs``: the parameters' offsets) from
     the per-sample rows the adjoint launch left, each scaled by ``pre`` before it is squared."""

@@ -1,7 +1,8 @@
-"""GGN products per second of All-CNN-C with ``GroupNorm(8, .)`` behind every convolution but the last (32x32 inputs, 100
+"""GGN (or, ``--curvature hessian``, Hessian) products per second of All-CNN-C with ``GroupNorm(8, .)`` behind every convolution but the last (32x32 inputs, 100
 classes, ``--batch`` 32 / 128) as hipGraph replays with a device synchronise: the plain-stack engine with its GroupNorm
 units on the one-launch kernels of hf_gn.hip (``HF_GN_ENGINE=1``) against the path such a model takes without the switch
--- autograd sweeps over the prepared model, captured.  ``--reps`` repetitions (default 9) of at least ``--seconds`` each,
+-- autograd sweeps over the prepared model, captured (``--curvature hessian``: ``HF_GN_ENGINE=1 HF_GN_HESSIAN=1`` against the
+captured autograd ``HessianOperator``).  ``--reps`` repetitions (default 9) of at least ``--seconds`` each,
 the two operators alternating on one device; one JSON line per operator to ``--out`` with every repetition's rate, the
 median and the spread (max - min); the engine's record also counts the library launches of one product."""
 import argparse
@@ -37,7 +38,7 @@ class AllCNNCGN(nn.Module):
         return torch.flatten(self.net(x), -3)
 
 
-def graphed(engine, batch, dev="cuda"):
+def graphed(engine, batch, dev="cuda", hessian=False):
     torch.manual_seed(0)
     model = AllCNNCGN().eval().to(dev)
     gen = torch.Generator().manual_seed(0)
@@ -48,13 +49,17 @@ def graphed(engine, batch, dev="cuda"):
 
     def builder():
         out = model(x)
+        if hessian:
+            return curvature.hessian_operator(lossf(out, t), out, params)
         return curvature.ggn_operator(lossf(out, t), out, params)
 
-    os.environ["HF_GN_ENGINE"] = "1" if engine else "0"
+    switches = ("HF_GN_ENGINE", "HF_GN_HESSIAN") if hessian else ("HF_GN_ENGINE",)
+    os.environ.update({name: "1" if engine else "0" for name in switches})
     try:
         op = curvature.maybe_graphed(builder, params=params)
     finally:
-        del os.environ["HF_GN_ENGINE"]
+        for name in switches:
+            del os.environ[name]
     assert isinstance(op, curvature.GraphedOperator), "the product was not captured"
     assert ("engine" in op.op.mode) == engine, op.op.mode
     return op
@@ -66,6 +71,7 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--seconds", type=float, default=0.5)
     ap.add_argument("--out", default="")
+    ap.add_argument("--curvature", choices=("ggn", "hessian"), default="ggn")
     args = ap.parse_args()
     hf.configure()
 
@@ -76,9 +82,11 @@ def main():
             with open(args.out, "a") as fh:
                 fh.write(json.dumps(rec) + "\n")
 
-    base = dict(workload="allcnnc_groupnorm8", batch=args.batch, unit="GGN products/s (hipGraph replay + device sync)",
+    hessian = args.curvature == "hessian"
+    kind = "Hessian" if hessian else "GGN"
+    base = dict(workload="allcnnc_groupnorm8", batch=args.batch, unit=f"{kind} products/s (hipGraph replay + device sync)",
                 device=torch.cuda.get_device_name(0))
-    eng, ref = graphed(True, args.batch), graphed(False, args.batch)
+    eng, ref = graphed(True, args.batch, hessian=hessian), graphed(False, args.batch, hessian=hessian)
     v = torch.randn(eng.n, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
     for op in (eng, ref):
         op.input_buffer.copy_(v)
