@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 33
+#define HF_ABI_VERSION 34
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -1337,6 +1337,60 @@ int hf_gn_act_adjoint2(void* ga2, void* gw_rows, void* gb_rows, void* gcb_rows, 
                        void* stream);
 int hf_gn_rows_sqsum(void* out_w, const void* rows_w, void* out_b, const void* rows_b, void* out_cb, const void* rows_cb,
                      double pre, int64_t n, int64_t c, int dtype, void* stream);
+
+/* ---- GroupNorm units whose block exceeds one workgroup's LDS: the split family (hf_gn.hip, ABI 34) ----------------------
+ * The same unit, layouts and limits as above, but a (sample, group) block of hw*cg floats may be of any size with
+ * cg <= 16 384: it is cut along the pixels into `parts` ranges of `part_pixels` pixels (the last one: what is left), one
+ * workgroup owns sample x span of whole groups x one part, resident in LDS (part_pixels * span <= 16 384 floats), grid
+ * (parts, spans, n).  hf_gn_split_plan reports the plan every launching entry point runs itself.  Each direction is TWO
+ * ordinary launches in stream order -- no cooperative launch, no waiting between workgroups, no atomics: a REDUCE launch
+ * leaves, per (sample, group, part), two fp64 partial sums in `partials` [n, groups, parts, 2] (8-byte aligned; the
+ * caller's, one table per unit), and every workgroup of the APPLY launch adds the partials of its groups itself, in part
+ * order, in fp64.  Two launches on the same operands agree bitwise.  Refused with HF_ERR_ARG before anything is launched or
+ * written: what hf_gn_plan refuses except the block size, cg > 16 384, more than 65 535 spans.  The arithmetic chains stand
+ * in hf_gn.hip's header.
+ *
+ * With n_i the elements of part i of a group, N = hw*cg, xh = (a - mean)*rstd, m = relu ? (y > 0) : 1:
+ *   hf_gn_split_stats         s = sum of a's slabs (+ conv_bias[c]) -> a_out (nullable);  partials: S_i = sum s and
+ *                             Q_i = sum (s - c_i)^2 about the part's own centre c_i = fp32(S_i / n_i).
+ *   hf_gn_split_forward       mean = sum_i S_i / N;  M2 = sum_i (Q_i - n_i (S_i/n_i - c_i)^2) + sum_i n_i (S_i/n_i - mean)^2;
+ *                             rstd = 1/sqrt(M2/N + eps);  y = act(gamma*(s - mean)*rstd + beta) from the summed map `s` (the
+ *                             a_out of the stats launch, or the given map where it had splits = 1 and no a_out) -> y (dense)
+ *                             and y2 (pixel stride y2_ld), either may be NULL, not both;  mean / rstd [n, groups].
+ *   hf_gn_split_tangent_sums  t = sum of t_a's slabs (+ v_conv_bias[c]) -> out, raw, pixel stride out_ld (0 = c);
+ *                             partials: sum t, sum xh*t.
+ *   hf_gn_split_act_tangent   out = m * (gamma*rstd*(t - E[t] - xh*E[xh t]) + v_gamma*xh + v_beta), t read from `out` and
+ *                             rewritten in place;  E[.] = the partials' sum / N.
+ *   hf_gn_split_adjoint_sums  g = m * (sum of gy's slabs) -> g;  partials: sum gamma*g, sum gamma*g*xh;  rows [n * parts, c]
+ *                             (row n_index * parts + part), each nullable: gw_rows = sum g*xh, gb_rows = sum g over the part.
+ *   hf_gn_split_act_adjoint   ga = rstd*(gamma g - E[gamma g] - xh*E[gamma g xh]) from the map g (ga itself is allowed: in
+ *                             place);  gcb_rows [n * parts, c] = sum ga over the part (nullable).  hf_pack_ex
+ *                             (splits = (n * parts, c)) adds the rows.
+ *   hf_gn_split_rows_sqsum    out_*[c] = sum_n (pre * row_*[n][c])^2, row[n] = the sample's `parts` partial rows added in
+ *                             part order in fp64 and rounded once; otherwise as hf_gn_rows_sqsum.
+ */
+int hf_gn_split_plan(int64_t n, int64_t hw, int64_t c, int64_t groups, int* span, int* parts, int* part_pixels);
+int hf_gn_split_stats(void* a_out, void* partials, const void* a, int splits, int64_t slab_stride, const void* conv_bias,
+                      int64_t n, int64_t hw, int64_t c, int64_t groups, int dtype, void* stream);
+int hf_gn_split_forward(void* y, void* y2, int64_t y2_ld, void* mean, void* rstd, const void* s, const void* partials,
+                        const void* gamma, const void* beta, double eps, int relu, int64_t n, int64_t hw, int64_t c,
+                        int64_t groups, int dtype, void* stream);
+int hf_gn_split_tangent_sums(void* out, int64_t out_ld, void* partials, const void* t_a, int splits, int64_t slab_stride,
+                             const void* v_conv_bias, const void* a, const void* mean, const void* rstd, int64_t n,
+                             int64_t hw, int64_t c, int64_t groups, int dtype, void* stream);
+int hf_gn_split_act_tangent(void* out, int64_t out_ld, const void* partials, const void* a, const void* mean,
+                            const void* rstd, const void* gamma, const void* v_gamma, const void* v_beta,
+                            const void* mask_src, int64_t n, int64_t hw, int64_t c, int64_t groups, int dtype,
+                            void* stream);
+int hf_gn_split_adjoint_sums(void* g, void* partials, void* gw_rows, void* gb_rows, const void* gy, int splits,
+                             int64_t slab_stride, const void* a, const void* mean, const void* rstd, const void* gamma,
+                             const void* mask_src, int64_t n, int64_t hw, int64_t c, int64_t groups, int dtype,
+                             void* stream);
+int hf_gn_split_act_adjoint(void* ga, void* gcb_rows, const void* g, const void* partials, const void* a, const void* mean,
+                            const void* rstd, const void* gamma, int64_t n, int64_t hw, int64_t c, int64_t groups,
+                            int dtype, void* stream);
+int hf_gn_split_rows_sqsum(void* out_w, const void* rows_w, void* out_b, const void* rows_b, void* out_cb,
+                           const void* rows_cb, double pre, int64_t n, int64_t parts, int64_t c, int dtype, void* stream);
 
 /* ---- RCCL (resolved at run time from the already-loaded librccl) ----------- */
 typedef struct hf_comm hf_comm_t;

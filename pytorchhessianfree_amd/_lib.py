@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HF_PCG_LIB") or os.path.join(_HERE, "csrc", "libhfpcg.so")
 
 HF_F32, HF_F64 = 0, 1
-ABI_VERSION = 33
+ABI_VERSION = 34
 HF_ERR_ARG = -1  # hf_status of include/hf_pcg.h: null / negative / inconsistent argument
 HF_M_NONE, HF_M_DIAG, HF_M_EXTERNAL = 0, 1, 2
 REASONS = {
@@ -261,6 +261,17 @@ SIGNATURES = {
     "hf_gn_act_adjoint2": (c_int, [c_void_p] * 5 + [c_int, c_int64, c_void_p, c_int, c_int64] + [c_void_p] * 8
                            + [c_int64] * 4 + [c_int, c_void_p]),
     "hf_gn_rows_sqsum": (c_int, [c_void_p] * 6 + [c_double, c_int64, c_int64, c_int, c_void_p]),
+    "hf_gn_split_plan": (c_int, [c_int64] * 4 + [ctypes.POINTER(c_int)] * 3),
+    "hf_gn_split_stats": (c_int, [c_void_p] * 3 + [c_int, c_int64, c_void_p] + [c_int64] * 4 + [c_int, c_void_p]),
+    "hf_gn_split_forward": (c_int, [c_void_p, c_void_p, c_int64] + [c_void_p] * 6 + [c_double, c_int] + [c_int64] * 4
+                            + [c_int, c_void_p]),
+    "hf_gn_split_tangent_sums": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int64] + [c_void_p] * 4
+                                 + [c_int64] * 4 + [c_int, c_void_p]),
+    "hf_gn_split_act_tangent": (c_int, [c_void_p, c_int64] + [c_void_p] * 8 + [c_int64] * 4 + [c_int, c_void_p]),
+    "hf_gn_split_adjoint_sums": (c_int, [c_void_p] * 5 + [c_int, c_int64] + [c_void_p] * 5 + [c_int64] * 4
+                                 + [c_int, c_void_p]),
+    "hf_gn_split_act_adjoint": (c_int, [c_void_p] * 8 + [c_int64] * 4 + [c_int, c_void_p]),
+    "hf_gn_split_rows_sqsum": (c_int, [c_void_p] * 6 + [c_double, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "hf_comm_unique_id": (c_int, [ctypes.c_char_p]),
     "hf_comm_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.c_char_p, c_int, c_int]),
     "hf_comm_destroy": (c_int, [c_void_p]),
@@ -715,6 +726,15 @@ def gn_plan(n, hw, c, groups):
     if span < 1:
         check(span, "hf_gn_plan")
     return span
+
+
+def gn_split_plan(n, hw, c, groups):
+    """(span, parts, part_pixels) of the split GroupNorm launches on this shape (``hf_gn_split_plan``): the channels of a
+    workgroup's span, the parts a (sample, group) block is cut into along the pixels, and the pixels of a part."""
+    span, parts, pp = c_int(), c_int(), c_int()
+    check(load().hf_gn_split_plan(n, hw, c, groups, ctypes.byref(span), ctypes.byref(parts), ctypes.byref(pp)),
+          "hf_gn_split_plan")
+    return span.value, parts.value, pp.value
 
 
 def dwconv_sqsum_plan(n, h, w, c, r, s, stride, padding, target_blocks=0):

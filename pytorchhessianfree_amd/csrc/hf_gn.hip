@@ -69,6 +69,56 @@
 //   the plan's hw x span.
 // hf_gn_rows_sqsum
 //   out[c]   =fp32( fp64 sum over the samples, ascending, of fp32(t * t),  t = fp32(pre * rows[n][c]) )
+//
+// Split family (hf_gn_split_*): blocks beyond one workgroup's LDS -- GroupNorm(1, C), large maps; any hw * cg with
+// cg <= 16 384.  A bigger tile would not do (160 KB of LDS per CU: 2.4 x the limit), so the work is split differently:
+//
+// Work split.  A (sample, group) block is cut along the PIXELS into `parts` ranges of part_pixels pixels, the last one
+// what is left.  A workgroup owns sample x span of whole groups x one part: a GnBlock with a pixel offset and a pixel
+// count, part_pixels * span <= GN_LDS_FLOATS, so the part is resident exactly as a whole block is above -- the same staging
+// helpers, teams and slots x columns layout, over the part's pixels.  Grid (parts, spans, n).  gn_split_plan: the span aims
+// at GN_SEG channels and is not traded for workgroups; part_pixels is (halved while the launch has fewer than 256 workgroups
+// and a part keeps GN_PART_FLOOR = 4 096 floats).
+//
+// Two ordinary launches per direction, in stream order: a REDUCE launch stages the part once, writes what the apply
+// launch reads back (the summed map, the raw tangent, the masked cotangent) and leaves two fp64 partial sums per (sample,
+// group, part) in the caller's table [n, groups, parts, 2]; every workgroup of the APPLY launch adds the partials of its
+// groups itself (lane gl < groups of the span, part order, fp64) and does the elementwise part from global memory -- it
+// keeps no tile (128 B - 8 KB of LDS), the part is L2-resident from the launch before.  No cooperative launch, no waiting
+// of one workgroup on another, no atomics: every order depends on the shape alone, two launches agree bitwise.
+//
+// Arithmetic chains (n_i = pixels of part i x cg, N = hw * cg; "chains" = the lanes' fp32 chains over the PART, at most
+// ceil(part_pixels * cg / 256) terms, added in fp64 as above; everything over the parts is fp64)
+// hf_gn_split_stats
+//   s        = slab 0 + slab 1 + .. [+ conv_bias[c]]  -> a_out                           as above
+//   S_i      = fp64 sum of the chains of s
+//   c_i      = fp32( S_i / n_i )                                                         the part's own centre, ONE rounding
+//   Q_i      = fp64 sum of the chains of q,  d = s - c_i;  q = d * d                     (a shifted sum about the part's own
+//              mean: no E[x^2] - mu^2)
+// hf_gn_split_forward
+//   m        = (S_0 + S_1 + ..) / N;   c_i = fp32( S_i / n_i ) again: the same number
+//   M2       = sum_i (Q_i - n_i (S_i/n_i - c_i)^2) + sum_i n_i (S_i/n_i - m)^2            the two sums apart, each in part
+//              order; exact for any c_i; a constant block gives 0 + 0, clamped at 0
+//   mu       = fp32( m );   rstd = fp32( 1 / sqrt( M2 / N + eps ) )                       ONE rounding each
+//   y        = act( ((s - mu) * rstd) * gamma[c] + beta[c] )                              hf_gn_forward's chain, s from the map
+// hf_gn_split_tangent_sums
+//   t        = s of the tangent convolution's slabs [+ v_conv_bias[c]]  -> out (raw, pitch out_ld)
+//   xh       = (a - mu) * rstd                                                            2
+//   partials = fp64 sums of the chains of t and of xh * t
+// hf_gn_split_act_tangent  (t: read back from out by the lane that rewrites it)
+//   m1, mx   = fp32( fp64 sum of the parts' partials / N )
+//   r        = (gamma[c] * rstd) * ((t - m1) - xh * mx);  += v_gamma[c] * xh;  += v_beta[c];  the mask       hf_gn_act_tangent's
+// hf_gn_split_adjoint_sums
+//   g        = (y > 0 | no ReLU) ? s of the consumer's data-gradient slabs : 0  -> g
+//   p        = gamma[c] * g  (1);   partials = fp64 sums of the chains of p and of p * xh
+//   gb_rows[n * parts + part][c] = fp32( fp64 sum over the slots of the chains of g down the part's pixels ),  gw_rows: of g * xh
+// hf_gn_split_act_adjoint  (g: read back; it may be ga's own buffer)
+//   m1, mx   = fp32( fp64 sum of the parts' partials / N )
+//   ga       = rstd * ((p - m1) - xh * mx)                                                hf_gn_act_adjoint's
+//   gcb_rows[n * parts + part][c] = fp32( fp64 sum over the slots of the chains of ga )
+// hf_gn_split_rows_sqsum
+//   row      = fp32( fp64 sum over the sample's parts, part order, of rows[n * parts + part][c] )      ONE rounding
+//   out[c]   = fp32( fp64 sum over the samples, ascending, of fp32(t * t),  t = fp32(pre * row) )
 #include "hf_common.h"
 
 #include <math.h>
@@ -98,23 +148,58 @@ inline int gn_plan(GnPlan& p, int64_t n, int64_t hw, int64_t c, int64_t groups) 
   return HF_OK;
 }
 
+// ---- the split family's plan: ONE definition, run by hf_gn_split_plan and by every launching entry point of the family ---
+// The span as above (GN_SEG channels of a pixel, whole groups; never traded for workgroups: the parts are).  A part:
+// part_pixels = min(hw, GN_LDS_FLOATS / span) pixels, halved (rounded up) while the launch has fewer than 256 workgroups
+// and a part keeps at least GN_PART_FLOOR = 4 096 floats -- four quads per lane: below that the staging loop is one or two
+// passes and a workgroup's fixed cost (the teams' trees, the barriers) outweighs what it moves.  parts = ceil(hw /
+// part_pixels) <= hw; the last part takes what is left.
+constexpr int GN_PART_FLOOR = 4096;
+
+struct GnSplitPlan {
+  GnPlan g;       // hw, c, groups, cg, gps, spans as in the one-launch family
+  int parts, pp;  // parts per (sample, group) block, pixels of a part
+};
+
+inline int gn_split_plan(GnSplitPlan& s, int64_t n, int64_t hw, int64_t c, int64_t groups) {
+  if (n <= 0 || hw <= 0 || c <= 0 || groups <= 0 || c % groups) return HF_ERR_ARG;
+  const int64_t cg = c / groups;
+  if (cg % 4 || cg > GN_LDS_FLOATS || n > 65535 || n * hw * c > 0x7fffffffLL) return HF_ERR_ARG;
+  int64_t gps = (GN_SEG + cg - 1) / cg;
+  if (gps > groups) gps = groups;
+  const int64_t span = gps * cg, spans = (groups + gps - 1) / gps;  // span <= max(cg, 2 * GN_SEG) <= GN_LDS_FLOATS
+  if (spans > 65535) return HF_ERR_ARG;
+  int64_t pp = GN_LDS_FLOATS / span;
+  if (pp > hw) pp = hw;
+  while (n * spans * ((hw + pp - 1) / pp) < GN_TARGET_WGS && ((pp + 1) / 2) * span >= GN_PART_FLOOR) pp = (pp + 1) / 2;
+  s.g = GnPlan{(int)n, (int)hw, (int)c, (int)groups, (int)cg, (int)gps, (int)spans};
+  s.parts = (int)((hw + pp - 1) / pp);
+  s.pp = (int)pp;
+  return HF_OK;
+}
+
 // ---- what a workgroup owns, and its lanes' places in the two reductions ------------------------------------------------
 struct GnBlock {
   int nb, g0, ng, ch0, sq, nq, qpg;  // sample, first group, groups, first channel, quads per pixel, quads, quads per group and pixel
-  long long base;                    // float index of (sample, pixel 0, channel ch0) in a dense [rows, c] map
+  int p0, np;                        // first pixel and pixels of the block (a whole sample: 0, hw; a part of the split family: its range)
+  long long row0, base;              // row of pixel p0, and the float index of (that row, channel ch0), in a dense [rows, c] map
   int wpt, nteams, team, lt, T, iters;
 };
 
-__device__ __forceinline__ GnBlock gn_block(int hw, int c, int groups, int cg, int gps) {
+// sample nb, span sx, the pixels p0 .. p0 + np - 1
+__device__ __forceinline__ GnBlock gn_block_of(int nb, int sx, int p0, int np, int hw, int c, int groups, int cg, int gps) {
   GnBlock b;
-  b.nb = blockIdx.y;
-  b.g0 = blockIdx.x * gps;
+  b.nb = nb;
+  b.g0 = sx * gps;
   b.ng = groups - b.g0 < gps ? groups - b.g0 : gps;
   b.ch0 = b.g0 * cg;
   b.qpg = cg >> 2;
   b.sq = b.ng * b.qpg;
-  b.nq = hw * b.sq;
-  b.base = (long long)b.nb * hw * c + b.ch0;
+  b.p0 = p0;
+  b.np = np;
+  b.nq = np * b.sq;
+  b.row0 = (long long)nb * hw + p0;
+  b.base = b.row0 * c + b.ch0;
   b.wpt = b.ng == 1 ? WAVES : b.ng == 2 ? WAVES / 2 : 1;
   b.nteams = WAVES / b.wpt;
   b.T = b.wpt * 64;
@@ -122,6 +207,17 @@ __device__ __forceinline__ GnBlock gn_block(int hw, int c, int groups, int cg, i
   b.lt = threadIdx.x - b.team * b.T;
   b.iters = (b.ng + b.nteams - 1) / b.nteams;
   return b;
+}
+
+// one-launch family, grid (spans, n): the whole (sample, span) block
+__device__ __forceinline__ GnBlock gn_block(int hw, int c, int groups, int cg, int gps) {
+  return gn_block_of(blockIdx.y, blockIdx.x, 0, hw, hw, c, groups, cg, gps);
+}
+
+// split family, grid (parts, spans, n): part blockIdx.x of the block, pp pixels (the last part: what is left)
+__device__ __forceinline__ GnBlock gn_part(int hw, int c, int groups, int cg, int gps, int pp) {
+  const int p0 = blockIdx.x * pp;
+  return gn_block_of(blockIdx.z, blockIdx.y, p0, hw - p0 < pp ? hw - p0 : pp, hw, c, groups, cg, gps);
 }
 
 __device__ __forceinline__ double quad_sum(const F4& s) { return (((double)s.e[0] + (double)s.e[1]) + (double)s.e[2]) + (double)s.e[3]; }
@@ -154,9 +250,10 @@ __device__ __forceinline__ void gn_team_sum(double (&v)[K], double* red, const G
 // four consecutive per-channel values (the model's parameters and the CG vector's slices sit on any 4-byte boundary)
 __device__ __forceinline__ F4 ld4s(const float* p) { return F4{{p[0], p[1], p[2], p[3]}}; }
 
-// the block's slabs summed into LDS, thread order; `extra` (nullable): a per-channel vector added behind the slab sum
+// the block's slabs summed into LDS, thread order; `extra` (nullable): a per-channel vector added behind the slab sum;
+// `copy` (nullable): the sum also goes to a [rows, copy_ld] map
 __device__ __forceinline__ void gn_stage(F4* tile, const GnBlock& b, const float* src, int splits, long long slab,
-                                         const float* extra, float* copy, int c) {
+                                         const float* extra, float* copy, int c, long long copy_ld) {
   for (int q = threadIdx.x; q < b.nq; q += BLOCK) {
     const int p = q / b.sq, j = q - p * b.sq;
     const long long gi = b.base + (long long)p * c + 4 * j;
@@ -166,7 +263,7 @@ __device__ __forceinline__ void gn_stage(F4* tile, const GnBlock& b, const float
 #pragma unroll
       for (int k = 0; k < 4; ++k) v.e[k] += e.e[k];
     }
-    if (copy) *reinterpret_cast<F4*>(copy + gi) = v;
+    if (copy) *reinterpret_cast<F4*>(copy + (b.row0 + p) * copy_ld + b.ch0 + 4 * j) = v;
     tile[q] = v;
   }
 }
@@ -196,7 +293,7 @@ __global__ __launch_bounds__(BLOCK) void k_gn_forward(
   __shared__ double red[WAVES];
   __shared__ float smu[GN_MAX_GPS], srs[GN_MAX_GPS];
   const GnBlock b = gn_block(hw, c, groups, cg, gps);
-  gn_stage(tile, b, a, splits, slab, cbias, a_out, c);
+  gn_stage(tile, b, a, splits, slab, cbias, a_out, c, c);
   __syncthreads();
   const double cnt = (double)hw * (double)cg;
   for (int it = 0; it < b.iters; ++it) {
@@ -265,7 +362,7 @@ __global__ __launch_bounds__(BLOCK) void k_gn_act_tangent(
   __shared__ double red[2 * WAVES];
   __shared__ float sm1[GN_MAX_GPS], smx[GN_MAX_GPS];
   const GnBlock b = gn_block(hw, c, groups, cg, gps);
-  gn_stage(tile, b, ta, splits, slab, v_cb, nullptr, c);
+  gn_stage(tile, b, ta, splits, slab, v_cb, nullptr, c, c);
   __syncthreads();
   const double cnt = (double)hw * (double)cg;
   const float* stat_mu = mean + (long long)b.nb * groups + b.g0;
@@ -453,7 +550,7 @@ __global__ __launch_bounds__(BLOCK) void k_gn_act_adjoint2(
   __shared__ float stats[G2_STATS][GN_MAX_GPS];
   const GnBlock b = gn_block(hw, c, groups, cg, gps);
   gn_stage_masked(tg, b, gy2, splits, slab, mask_src, c);
-  gn_stage(tt, b, ta, t_splits, t_slab, v_cb, nullptr, c);
+  gn_stage(tt, b, ta, t_splits, t_slab, v_cb, nullptr, c, c);
   __syncthreads();
   const double cnt = (double)hw * (double)cg;
   const float* stat_mu = mean + (long long)b.nb * groups + b.g0;
@@ -565,6 +662,330 @@ __global__ __launch_bounds__(BLOCK) void k_gn_rows_sqsum(GnSqTables tabs, float 
   double s = 0.0;
   for (int i = 0; i < n; ++i) {
     const float t = pre * rows[(long long)i * c + ch];
+    s += (double)(t * t);
+  }
+  out[ch] = (float)s;
+}
+
+// ---- the split family: blocks beyond one workgroup's LDS, a reduce and an apply launch per direction -------------------
+// (the header's "Split family" section: work split, partials table, arithmetic chains)
+
+// the partials of (sample, group gl of the block's span): [parts][2] doubles of the table [n, groups, parts, 2]
+template <typename D>
+__device__ __forceinline__ D* gn_tab(D* tab, const GnBlock& b, int groups, int gl) {
+  return tab + ((long long)b.nb * groups + b.g0 + gl) * gridDim.x * 2;
+}
+
+// apply launches: lane gl < ng adds the two partial sums of its group over the parts, in part order, and leaves their
+// means over the whole block (one rounding each) in sm1 / smx; ends with a barrier
+__device__ __forceinline__ void gn_parts_means(float* sm1, float* smx, const double* tab, const GnBlock& b, int groups,
+                                               double cnt) {
+  if ((int)threadIdx.x < b.ng) {
+    const double* t = gn_tab(tab, b, groups, threadIdx.x);
+    double s1 = 0.0, sx = 0.0;
+    for (int i = 0; i < (int)gridDim.x; ++i) {
+      s1 += t[2 * i];
+      sx += t[2 * i + 1];
+    }
+    sm1[threadIdx.x] = (float)(s1 / cnt);
+    smx[threadIdx.x] = (float)(sx / cnt);
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(BLOCK) void k_gn_split_stats(float* a_out, double* __restrict__ tab, const float* a, int splits,
+                                                          long long slab, const float* __restrict__ cbias, int hw, int c,
+                                                          int groups, int cg, int gps, int pp) {
+  __shared__ F4 tile[GN_LDS_FLOATS / 4];
+  __shared__ double red[WAVES];
+  const GnBlock b = gn_part(hw, c, groups, cg, gps, pp);
+  gn_stage(tile, b, a, splits, slab, cbias, a_out, c, c);
+  __syncthreads();
+  const double cnt = (double)b.np * (double)cg;  // n_i
+  for (int it = 0; it < b.iters; ++it) {
+    const int gl = b.team + it * b.nteams;
+    const bool on = gl < b.ng;
+    const int gq = on ? b.np * b.qpg : 0;
+    F4 s = {{0.f, 0.f, 0.f, 0.f}};
+    for (int e = b.lt; e < gq; e += b.T) {
+      const int p = e / b.qpg, jj = e - p * b.qpg;
+      const F4 x = tile[p * b.sq + gl * b.qpg + jj];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) s.e[k] += x.e[k];
+    }
+    double v[1] = {quad_sum(s)};
+    gn_team_sum<1>(v, red, b);
+    const double S = v[0];
+    const float ci = (float)(S / cnt);  // the part's own centre: the apply launch takes the same number from S and n_i
+    s = F4{{0.f, 0.f, 0.f, 0.f}};
+    for (int e = b.lt; e < gq; e += b.T) {
+      const int p = e / b.qpg, jj = e - p * b.qpg;
+      const F4 x = tile[p * b.sq + gl * b.qpg + jj];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float d = x.e[k] - ci;
+        s.e[k] += d * d;
+      }
+    }
+    v[0] = quad_sum(s);
+    gn_team_sum<1>(v, red, b);
+    if (on && b.lt == 0) {
+      double* o = gn_tab(tab, b, groups, gl) + 2 * blockIdx.x;
+      o[0] = S;
+      o[1] = v[0];
+    }
+  }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_gn_split_forward(
+    float* __restrict__ y, float* __restrict__ y2, unsigned y2_ld, float* __restrict__ mean_out,
+    float* __restrict__ rstd_out, const float* __restrict__ s_map, const double* __restrict__ tab,
+    const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int relu, int hw, int c, int groups, int cg,
+    int gps, int pp) {
+  __shared__ float smu[GN_MAX_GPS], srs[GN_MAX_GPS];
+  const GnBlock b = gn_part(hw, c, groups, cg, gps, pp);
+  if ((int)threadIdx.x < b.ng) {  // Chan's combination of the parts' (S_i, Q_i about c_i), all fp64, part order
+    const double* t = gn_tab(tab, b, groups, threadIdx.x);
+    const int parts = gridDim.x;
+    const double cnt = (double)hw * (double)cg;
+    double S = 0.0;
+    for (int i = 0; i < parts; ++i) S += t[2 * i];
+    const double m = S / cnt;
+    double within = 0.0, between = 0.0;
+    for (int i = 0; i < parts; ++i) {
+      const int np = hw - i * pp < pp ? hw - i * pp : pp;
+      const double ni = (double)np * (double)cg, mi = t[2 * i] / ni;
+      const double dc = mi - (double)(float)mi, dm = mi - m;
+      within += t[2 * i + 1] - ni * (dc * dc);
+      between += ni * (dm * dm);
+    }
+    double M2 = within + between;
+    M2 = M2 > 0.0 ? M2 : 0.0;
+    const float mu = (float)m, rs = (float)(1.0 / sqrt(M2 / cnt + (double)eps));
+    smu[threadIdx.x] = mu;
+    srs[threadIdx.x] = rs;
+    if (blockIdx.x == 0) {
+      mean_out[(long long)b.nb * groups + b.g0 + threadIdx.x] = mu;
+      rstd_out[(long long)b.nb * groups + b.g0 + threadIdx.x] = rs;
+    }
+  }
+  __syncthreads();
+  for (int q = threadIdx.x; q < b.nq; q += BLOCK) {
+    const int p = q / b.sq, j = q - p * b.sq, gl = j / b.qpg;
+    const float mu = smu[gl], rs = srs[gl];
+    const F4 x = ld4(s_map + b.base + (long long)p * c + 4 * j), w = ld4s(gamma + b.ch0 + 4 * j);
+    F4 t;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t.e[k] = ((x.e[k] - mu) * rs) * w.e[k];
+    if (beta) {
+      const F4 bq = ld4s(beta + b.ch0 + 4 * j);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) t.e[k] += bq.e[k];
+    }
+    if (relu) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) t.e[k] = t.e[k] > 0.f ? t.e[k] : 0.f;
+    }
+    const long long row = b.row0 + p;
+    if (y) *reinterpret_cast<F4*>(y + row * c + b.ch0 + 4 * j) = t;
+    if (y2) *reinterpret_cast<F4*>(y2 + row * y2_ld + b.ch0 + 4 * j) = t;
+  }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_gn_split_tangent_sums(
+    float* __restrict__ out, unsigned out_ld, double* __restrict__ tab, const float* __restrict__ ta, int splits,
+    long long slab, const float* __restrict__ v_cb, const float* __restrict__ a, const float* __restrict__ mean,
+    const float* __restrict__ rstd, int hw, int c, int groups, int cg, int gps, int pp) {
+  __shared__ F4 tile[GN_LDS_FLOATS / 4];
+  __shared__ double red[2 * WAVES];
+  const GnBlock b = gn_part(hw, c, groups, cg, gps, pp);
+  gn_stage(tile, b, ta, splits, slab, v_cb, out, c, out_ld);  // t, resident, and raw into the destination
+  __syncthreads();
+  const float* stat_mu = mean + (long long)b.nb * groups + b.g0;
+  const float* stat_rs = rstd + (long long)b.nb * groups + b.g0;
+  for (int it = 0; it < b.iters; ++it) {
+    const int gl = b.team + it * b.nteams;
+    const bool on = gl < b.ng;
+    const int gq = on ? b.np * b.qpg : 0;
+    const float mu = on ? stat_mu[gl] : 0.f, rs = on ? stat_rs[gl] : 0.f;
+    F4 s1 = {{0.f, 0.f, 0.f, 0.f}}, sx = {{0.f, 0.f, 0.f, 0.f}};
+    for (int e = b.lt; e < gq; e += b.T) {
+      const int p = e / b.qpg, jj = e - p * b.qpg, j = gl * b.qpg + jj;
+      const F4 t = tile[p * b.sq + j], x = ld4(a + b.base + (long long)p * c + 4 * j);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float xh = (x.e[k] - mu) * rs;
+        s1.e[k] += t.e[k];
+        sx.e[k] += xh * t.e[k];
+      }
+    }
+    double v[2] = {quad_sum(s1), quad_sum(sx)};
+    gn_team_sum<2>(v, red, b);
+    if (on && b.lt == 0) {
+      double* o = gn_tab(tab, b, groups, gl) + 2 * blockIdx.x;
+      o[0] = v[0];
+      o[1] = v[1];
+    }
+  }
+}
+
+// (out: read and rewritten in place, each element by the lane that read it -- no __restrict__)
+__global__ __launch_bounds__(BLOCK) void k_gn_split_act_tangent(
+    float* out, unsigned out_ld, const double* __restrict__ tab, const float* __restrict__ a,
+    const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
+    const float* __restrict__ v_gamma, const float* __restrict__ v_beta, const float* __restrict__ mask_src, int hw, int c,
+    int groups, int cg, int gps, int pp) {
+  __shared__ float sm1[GN_MAX_GPS], smx[GN_MAX_GPS];
+  const GnBlock b = gn_part(hw, c, groups, cg, gps, pp);
+  gn_parts_means(sm1, smx, tab, b, groups, (double)hw * (double)cg);
+  const float* stat_mu = mean + (long long)b.nb * groups + b.g0;
+  const float* stat_rs = rstd + (long long)b.nb * groups + b.g0;
+  for (int q = threadIdx.x; q < b.nq; q += BLOCK) {
+    const int p = q / b.sq, j = q - p * b.sq, gl = j / b.qpg;
+    const float mu = stat_mu[gl], rs = stat_rs[gl], m1 = sm1[gl], mx = smx[gl];
+    const long long row = b.row0 + p, gi = row * c + b.ch0 + 4 * j;
+    float* dst = out + row * out_ld + b.ch0 + 4 * j;
+    const F4 t = ld4(dst), x = ld4(a + gi), w = ld4s(gamma + b.ch0 + 4 * j);
+    F4 xh, r;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      xh.e[k] = (x.e[k] - mu) * rs;
+      r.e[k] = (w.e[k] * rs) * ((t.e[k] - m1) - xh.e[k] * mx);
+    }
+    if (v_gamma) {
+      const F4 vg = ld4s(v_gamma + b.ch0 + 4 * j);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) r.e[k] += vg.e[k] * xh.e[k];
+    }
+    if (v_beta) {
+      const F4 vb = ld4s(v_beta + b.ch0 + 4 * j);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) r.e[k] += vb.e[k];
+    }
+    if (mask_src) {
+      const F4 m = ld4(mask_src + gi);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) r.e[k] = m.e[k] > 0.f ? r.e[k] : 0.f;
+    }
+    *reinterpret_cast<F4*>(dst) = r;
+  }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_gn_split_adjoint_sums(
+    float* __restrict__ g_out, double* __restrict__ tab, float* __restrict__ gw_rows, float* __restrict__ gb_rows,
+    const float* __restrict__ gy, int splits, long long slab, const float* __restrict__ a, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ mask_src, int hw, int c,
+    int groups, int cg, int gps, int pp) {
+  __shared__ F4 tile[GN_LDS_FLOATS / 4];
+  __shared__ double red[2 * WAVES];
+  __shared__ double rsum[BLOCK * 4];
+  const GnBlock b = gn_part(hw, c, groups, cg, gps, pp);
+  gn_stage_masked(tile, b, gy, splits, slab, mask_src, c);  // g, resident
+  __syncthreads();
+  const float* stat_mu = mean + (long long)b.nb * groups + b.g0;
+  const float* stat_rs = rstd + (long long)b.nb * groups + b.g0;
+  for (int it = 0; it < b.iters; ++it) {
+    const int gl = b.team + it * b.nteams;
+    const bool on = gl < b.ng;
+    const int gq = on ? b.np * b.qpg : 0;
+    const float mu = on ? stat_mu[gl] : 0.f, rs = on ? stat_rs[gl] : 0.f;
+    F4 s1 = {{0.f, 0.f, 0.f, 0.f}}, sx = {{0.f, 0.f, 0.f, 0.f}};
+    for (int e = b.lt; e < gq; e += b.T) {
+      const int p = e / b.qpg, jj = e - p * b.qpg, j = gl * b.qpg + jj;
+      const F4 g = tile[p * b.sq + j], x = ld4(a + b.base + (long long)p * c + 4 * j), w = ld4s(gamma + b.ch0 + 4 * j);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float xh = (x.e[k] - mu) * rs, pg = w.e[k] * g.e[k];
+        s1.e[k] += pg;
+        sx.e[k] += pg * xh;
+      }
+    }
+    double v[2] = {quad_sum(s1), quad_sum(sx)};
+    gn_team_sum<2>(v, red, b);
+    if (on && b.lt == 0) {
+      double* o = gn_tab(tab, b, groups, gl) + 2 * blockIdx.x;
+      o[0] = v[0];
+      o[1] = v[1];
+    }
+  }
+  // g leaves, and the part's rows of scale and shift: lane (slot, column) walks its channel quad down the part's pixels
+  const int cols = b.sq < BLOCK ? b.sq : BLOCK, slots = BLOCK / cols;
+  const int slot = threadIdx.x / cols, jl = threadIdx.x - slot * cols;
+  for (int j0 = 0; j0 < b.sq; j0 += cols) {
+    const int j = j0 + jl;
+    const bool act = slot < slots && j < b.sq;
+    F4 sb = {{0.f, 0.f, 0.f, 0.f}}, sw = {{0.f, 0.f, 0.f, 0.f}};
+    if (act) {
+      const int gl = j / b.qpg;
+      const float mu = stat_mu[gl], rs = stat_rs[gl];
+      for (int p = slot; p < b.np; p += slots) {
+        const long long gi = b.base + (long long)p * c + 4 * j;
+        const F4 g = tile[p * b.sq + j], x = ld4(a + gi);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float xh = (x.e[k] - mu) * rs;
+          sb.e[k] += g.e[k];
+          sw.e[k] += g.e[k] * xh;
+        }
+        *reinterpret_cast<F4*>(g_out + gi) = g;
+      }
+    }
+    const long long at = ((long long)b.nb * gridDim.x + blockIdx.x) * c + b.ch0 + 4 * j;
+    if (gw_rows) gn_row_store(gw_rows, sw, rsum, slots, cols, slot, jl, act, at);
+    if (gb_rows) gn_row_store(gb_rows, sb, rsum, slots, cols, slot, jl, act, at);
+  }
+}
+
+// (g may be ga_out itself: read and rewritten in place, each element by the lane that read it -- no __restrict__)
+__global__ __launch_bounds__(BLOCK) void k_gn_split_act_adjoint(
+    float* ga_out, float* __restrict__ gcb_rows, const float* g_in, const double* __restrict__ tab,
+    const float* __restrict__ a, const float* __restrict__ mean, const float* __restrict__ rstd,
+    const float* __restrict__ gamma, int hw, int c, int groups, int cg, int gps, int pp) {
+  __shared__ double rsum[BLOCK * 4];
+  __shared__ float sm1[GN_MAX_GPS], smx[GN_MAX_GPS];
+  const GnBlock b = gn_part(hw, c, groups, cg, gps, pp);
+  gn_parts_means(sm1, smx, tab, b, groups, (double)hw * (double)cg);
+  const float* stat_mu = mean + (long long)b.nb * groups + b.g0;
+  const float* stat_rs = rstd + (long long)b.nb * groups + b.g0;
+  const int cols = b.sq < BLOCK ? b.sq : BLOCK, slots = BLOCK / cols;
+  const int slot = threadIdx.x / cols, jl = threadIdx.x - slot * cols;
+  for (int j0 = 0; j0 < b.sq; j0 += cols) {
+    const int j = j0 + jl;
+    const bool act = slot < slots && j < b.sq;
+    F4 sc = {{0.f, 0.f, 0.f, 0.f}};
+    if (act) {
+      const int gl = j / b.qpg;
+      const float mu = stat_mu[gl], rs = stat_rs[gl], m1 = sm1[gl], mx = smx[gl];
+      const F4 w = ld4s(gamma + b.ch0 + 4 * j);
+      for (int p = slot; p < b.np; p += slots) {
+        const long long gi = b.base + (long long)p * c + 4 * j;
+        const F4 g = ld4(g_in + gi), x = ld4(a + gi);
+        F4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float xh = (x.e[k] - mu) * rs, pg = w.e[k] * g.e[k];
+          o.e[k] = rs * ((pg - m1) - xh * mx);
+          sc.e[k] += o.e[k];
+        }
+        *reinterpret_cast<F4*>(ga_out + gi) = o;
+      }
+    }
+    const long long at = ((long long)b.nb * gridDim.x + blockIdx.x) * c + b.ch0 + 4 * j;
+    if (gcb_rows) gn_row_store(gcb_rows, sc, rsum, slots, cols, slot, jl, act, at);
+  }
+}
+
+// out[c] = sum_n (pre * row[n][c])^2, row[n] = the sample's `parts` partial rows added in part order (fp64, one rounding)
+__global__ __launch_bounds__(BLOCK) void k_gn_split_rows_sqsum(GnSqTables tabs, float pre, int n, int parts, int c) {
+  float* out = tabs.out[blockIdx.y];
+  const float* rows = tabs.rows[blockIdx.y];
+  const int ch = blockIdx.x * BLOCK + threadIdx.x;
+  if (!out || ch >= c) return;
+  double s = 0.0;
+  for (int i = 0; i < n; ++i) {
+    double r = 0.0;
+    for (int pt = 0; pt < parts; ++pt) r += (double)rows[((long long)i * parts + pt) * c + ch];
+    const float t = pre * (float)r;
     s += (double)(t * t);
   }
   out[ch] = (float)s;
@@ -684,6 +1105,139 @@ int hf_gn_rows_sqsum(void* out_w, const void* rows_w, void* out_b, const void* r
                      {(const float*)rows_w, (const float*)rows_b, (const float*)rows_cb}};
   hipLaunchKernelGGL(k_gn_rows_sqsum, dim3((unsigned)((c + BLOCK - 1) / BLOCK), 3), dim3(BLOCK), 0, (hipStream_t)stream,
                      tabs, (float)pre, (int)n, (int)c);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+// ---- the split family's entry points ------------------------------------------------------------------------------------
+namespace {
+
+// what every launching entry point of the family checks first: the plan, and the fp64 partials table
+inline int gn_split_ok(GnSplitPlan& s, const void* partials, int64_t n, int64_t hw, int64_t c, int64_t groups, int dtype) {
+  if (dtype != HF_F32 || gn_split_plan(s, n, hw, c, groups) != HF_OK) return HF_ERR_ARG;
+  return partials && ((uintptr_t)partials & 7) == 0 ? HF_OK : HF_ERR_ARG;
+}
+
+inline dim3 gn_split_grid(const GnSplitPlan& s) { return dim3(s.parts, s.g.spans, s.g.n); }
+
+}  // namespace
+
+int hf_gn_split_plan(int64_t n, int64_t hw, int64_t c, int64_t groups, int* span, int* parts, int* part_pixels) {
+  GnSplitPlan s;
+  if (!span || !parts || !part_pixels || gn_split_plan(s, n, hw, c, groups) != HF_OK) return HF_ERR_ARG;
+  *span = s.g.gps * s.g.cg;
+  *parts = s.parts;
+  *part_pixels = s.pp;
+  return HF_OK;
+}
+
+int hf_gn_split_stats(void* a_out, void* partials, const void* a, int splits, int64_t slab_stride, const void* conv_bias,
+                      int64_t n, int64_t hw, int64_t c, int64_t groups, int dtype, void* stream) {
+  GnSplitPlan s;
+  if (gn_split_ok(s, partials, n, hw, c, groups, dtype) != HF_OK) return HF_ERR_ARG;
+  if (gn_slabs_ok(a, splits, slab_stride, s.g) != HF_OK) return HF_ERR_ARG;
+  const void* al[] = {a_out, a};
+  if (gn_aligned(al) != HF_OK) return HF_ERR_ARG;
+  hipLaunchKernelGGL(k_gn_split_stats, gn_split_grid(s), dim3(BLOCK), 0, (hipStream_t)stream, (float*)a_out,
+                     (double*)partials, (const float*)a, splits, (long long)slab_stride, (const float*)conv_bias, s.g.hw,
+                     s.g.c, s.g.groups, s.g.cg, s.g.gps, s.pp);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+int hf_gn_split_forward(void* y, void* y2, int64_t y2_ld, void* mean, void* rstd, const void* s_map, const void* partials,
+                        const void* gamma, const void* beta, double eps, int relu, int64_t n, int64_t hw, int64_t c,
+                        int64_t groups, int dtype, void* stream) {
+  GnSplitPlan s;
+  if (gn_split_ok(s, partials, n, hw, c, groups, dtype) != HF_OK) return HF_ERR_ARG;
+  if ((!y && !y2) || !mean || !rstd || !s_map || !gamma || !(eps >= 0.0) || !(eps - eps == 0.0)) return HF_ERR_ARG;
+  if (y2 && (y2_ld == 0 || !gn_ld_ok(y2_ld, s.g))) return HF_ERR_ARG;
+  const void* al[] = {y, y2, s_map};
+  if (gn_aligned(al) != HF_OK) return HF_ERR_ARG;
+  hipLaunchKernelGGL(k_gn_split_forward, gn_split_grid(s), dim3(BLOCK), 0, (hipStream_t)stream, (float*)y, (float*)y2,
+                     (unsigned)y2_ld, (float*)mean, (float*)rstd, (const float*)s_map, (const double*)partials,
+                     (const float*)gamma, (const float*)beta, (float)eps, relu, s.g.hw, s.g.c, s.g.groups, s.g.cg, s.g.gps,
+                     s.pp);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+int hf_gn_split_tangent_sums(void* out, int64_t out_ld, void* partials, const void* t_a, int splits, int64_t slab_stride,
+                             const void* v_conv_bias, const void* a, const void* mean, const void* rstd, int64_t n,
+                             int64_t hw, int64_t c, int64_t groups, int dtype, void* stream) {
+  GnSplitPlan s;
+  if (gn_split_ok(s, partials, n, hw, c, groups, dtype) != HF_OK) return HF_ERR_ARG;
+  if (!out || !a || !mean || !rstd || !gn_ld_ok(out_ld, s.g)) return HF_ERR_ARG;
+  if (gn_slabs_ok(t_a, splits, slab_stride, s.g) != HF_OK) return HF_ERR_ARG;
+  const void* al[] = {out, t_a, a};
+  if (gn_aligned(al) != HF_OK) return HF_ERR_ARG;
+  hipLaunchKernelGGL(k_gn_split_tangent_sums, gn_split_grid(s), dim3(BLOCK), 0, (hipStream_t)stream, (float*)out,
+                     (unsigned)(out_ld ? out_ld : c), (double*)partials, (const float*)t_a, splits, (long long)slab_stride,
+                     (const float*)v_conv_bias, (const float*)a, (const float*)mean, (const float*)rstd, s.g.hw, s.g.c,
+                     s.g.groups, s.g.cg, s.g.gps, s.pp);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+int hf_gn_split_act_tangent(void* out, int64_t out_ld, const void* partials, const void* a, const void* mean,
+                            const void* rstd, const void* gamma, const void* v_gamma, const void* v_beta,
+                            const void* mask_src, int64_t n, int64_t hw, int64_t c, int64_t groups, int dtype,
+                            void* stream) {
+  GnSplitPlan s;
+  if (gn_split_ok(s, partials, n, hw, c, groups, dtype) != HF_OK) return HF_ERR_ARG;
+  if (!out || !a || !mean || !rstd || !gamma || !gn_ld_ok(out_ld, s.g)) return HF_ERR_ARG;
+  const void* al[] = {out, a, mask_src};
+  if (gn_aligned(al) != HF_OK) return HF_ERR_ARG;
+  hipLaunchKernelGGL(k_gn_split_act_tangent, gn_split_grid(s), dim3(BLOCK), 0, (hipStream_t)stream, (float*)out,
+                     (unsigned)(out_ld ? out_ld : c), (const double*)partials, (const float*)a, (const float*)mean,
+                     (const float*)rstd, (const float*)gamma, (const float*)v_gamma, (const float*)v_beta,
+                     (const float*)mask_src, s.g.hw, s.g.c, s.g.groups, s.g.cg, s.g.gps, s.pp);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+int hf_gn_split_adjoint_sums(void* g, void* partials, void* gw_rows, void* gb_rows, const void* gy, int splits,
+                             int64_t slab_stride, const void* a, const void* mean, const void* rstd, const void* gamma,
+                             const void* mask_src, int64_t n, int64_t hw, int64_t c, int64_t groups, int dtype,
+                             void* stream) {
+  GnSplitPlan s;
+  if (gn_split_ok(s, partials, n, hw, c, groups, dtype) != HF_OK) return HF_ERR_ARG;
+  if (!g || !a || !mean || !rstd || !gamma || (int64_t)s.g.n * s.parts * s.g.c > 0x7fffffffLL) return HF_ERR_ARG;
+  if (gn_slabs_ok(gy, splits, slab_stride, s.g) != HF_OK) return HF_ERR_ARG;
+  const void* al[] = {g, gw_rows, gb_rows, gy, a, mask_src};
+  if (gn_aligned(al) != HF_OK) return HF_ERR_ARG;
+  hipLaunchKernelGGL(k_gn_split_adjoint_sums, gn_split_grid(s), dim3(BLOCK), 0, (hipStream_t)stream, (float*)g,
+                     (double*)partials, (float*)gw_rows, (float*)gb_rows, (const float*)gy, splits, (long long)slab_stride,
+                     (const float*)a, (const float*)mean, (const float*)rstd, (const float*)gamma, (const float*)mask_src,
+                     s.g.hw, s.g.c, s.g.groups, s.g.cg, s.g.gps, s.pp);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+int hf_gn_split_act_adjoint(void* ga, void* gcb_rows, const void* g, const void* partials, const void* a, const void* mean,
+                            const void* rstd, const void* gamma, int64_t n, int64_t hw, int64_t c, int64_t groups,
+                            int dtype, void* stream) {
+  GnSplitPlan s;
+  if (gn_split_ok(s, partials, n, hw, c, groups, dtype) != HF_OK) return HF_ERR_ARG;
+  if (!ga || !g || !a || !mean || !rstd || !gamma || (int64_t)s.g.n * s.parts * s.g.c > 0x7fffffffLL) return HF_ERR_ARG;
+  const void* al[] = {ga, gcb_rows, g, a};
+  if (gn_aligned(al) != HF_OK) return HF_ERR_ARG;
+  hipLaunchKernelGGL(k_gn_split_act_adjoint, gn_split_grid(s), dim3(BLOCK), 0, (hipStream_t)stream, (float*)ga,
+                     (float*)gcb_rows, (const float*)g, (const double*)partials, (const float*)a, (const float*)mean,
+                     (const float*)rstd, (const float*)gamma, s.g.hw, s.g.c, s.g.groups, s.g.cg, s.g.gps, s.pp);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+int hf_gn_split_rows_sqsum(void* out_w, const void* rows_w, void* out_b, const void* rows_b, void* out_cb,
+                           const void* rows_cb, double pre, int64_t n, int64_t parts, int64_t c, int dtype, void* stream) {
+  if (dtype != HF_F32 || n <= 0 || parts <= 0 || c <= 0 || n * parts * c > 0x7fffffffLL || !(pre - pre == 0.0))
+    return HF_ERR_ARG;
+  if ((!out_w && !out_b && !out_cb) || (out_w && !rows_w) || (out_b && !rows_b) || (out_cb && !rows_cb)) return HF_ERR_ARG;
+  GnSqTables tabs = {{(float*)out_w, (float*)out_b, (float*)out_cb},
+                     {(const float*)rows_w, (const float*)rows_b, (const float*)rows_cb}};
+  hipLaunchKernelGGL(k_gn_split_rows_sqsum, dim3((unsigned)((c + BLOCK - 1) / BLOCK), 3), dim3(BLOCK), 0,
+                     (hipStream_t)stream, tabs, (float)pre, (int)n, (int)parts, (int)c);
   HF_HIP(hipGetLastError());
   return HF_OK;
 }

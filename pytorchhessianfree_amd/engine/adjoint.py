@@ -6,7 +6,7 @@ Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overal
 from .. import _lib
 from .problems import (affine_args, affine_train_args, affine_train_problem, bn_adjoint_args, bn_adjoint_problem,
                        bn_adjoint_v4_args, conv_args, conv_backward_args, conv_problem, gn_adjoint2_args,
-                       gn_adjoint_args, problem)
+                       gn_adjoint_args, gn_split_adjoint_args, problem)
 
 
 class _AdjointSweep:
@@ -116,6 +116,11 @@ class _AdjointSweep:
         if u.gn is not None:
             # GroupNorm: ONE launch, no grid-wide sum -- g = mask * (sum of the cotangent's slabs), g_a = rstd * (w g -
             # E[w g] - xhat * E[w g xhat]) and the parameters' sums as one partial row per sample (the gather adds them)
+            if u.gn_parts:  # (split unit: g, the parts' sums and rows, then g_a from the added partials)
+                sums, act = gn_split_adjoint_args(u, srcs)
+                self._launch("hf_gn_split_adjoint_sums", *sums)
+                self._launch("hf_gn_split_act_adjoint", *act)
+                return
             self._launch("hf_gn_act_adjoint", *gn_adjoint_args(u, srcs))
             return
         if u.train:

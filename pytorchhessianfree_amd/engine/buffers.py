@@ -224,7 +224,7 @@ class _Buffers:
             if u.gn is not None:
                 # GroupNorm: one workgroup owns a (sample, span of groups) block, so the sums arrive as ONE partial row per
                 # sample -- which are also the per-sample gradients ``diag_ef`` squares; no elementwise / deferred form
-                u.rb = n
+                u.rb = n * max(u.gn_parts, 1)  # (a split unit: one row per sample and part)
             enabled = os.environ.get("HF_BN_SUMS_DEFER", "1") != "0" and u.gn is None
             u.split = adjoint_split_ok(u.train, u.rb, self.hessian, u.a.numel() * 4, self.DEFER_MAX_BYTES, enabled)
             u.defer = not u.dead and defer_sums_ok(u.train, u.rb, self.hessian, u.bn is not None and u.pg is not None,
@@ -243,6 +243,8 @@ class _Buffers:
                 u.gn_mean = torch.empty((n, u.gn.num_groups), dtype=f32, device=dev)
                 u.gn_rstd = torch.empty_like(u.gn_mean)
                 u.gcb = torch.empty((u.rb, k), dtype=f32, device=dev) if u.pcb is not None else None
+                if u.gn_parts:  # the reduce launches' fp64 partials, one pair per (sample, group, part)
+                    u.gn_tab = torch.empty((n, u.gn.num_groups, u.gn_parts, 2), dtype=torch.float64, device=dev)
             if u.train:
                 # The per-channel finalisation of a train-mode tangent / adjoint runs in the PROLOGUE of the elementwise
                 # pass: its workgroups add the reduction's partial rows up themselves (hf_chan_affine_train).  The

@@ -79,6 +79,7 @@ class _Unit:
         self.pool = None          # plain stack: (kh, kw, sh, sw, ph, pw) of the MaxPool2d behind the unit (its ReLU)
         self.rp = None            # ... and the pooled map the model's forward pass recorded
         self.gn = None            # plain stack: the GroupNorm behind the convolution (hf_gn.hip; ``bn`` is then None)
+        self.gn_parts = 0         # ... cut into this many parts along the pixels (the split kernels; 0: one launch)
         self.pcb = None           # ... and the index of that convolution's own bias (``pb`` is the GroupNorm's shift)
 
     @property

@@ -86,7 +86,8 @@ class _DiagEF:
         unit squares and adds them over the samples, straight into ``out`` (the gathers wrote zeros there)."""
         for u in self.units:
             if u.gn is not None and not u.dead and any(i is not None for i in (u.pg, u.pb, u.pcb)):
-                self._launch("hf_gn_rows_sqsum", *gn_rows_sqsum_args(u, out, self._offs, pre))
+                self._launch("hf_gn_split_rows_sqsum" if u.gn_parts else "hf_gn_rows_sqsum",
+                             *gn_rows_sqsum_args(u, out, self._offs, pre))
 
     def _diag_head_buffers(self, tensors):
         """A kind whose head has parameters: their entries of the gather's table ..."""

@@ -6,7 +6,7 @@ Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overal
 
 import torch
 
-from .problems import gn_forward_args
+from .problems import gn_forward_args, gn_split_forward_args, gn_split_stats_args
 
 
 class _Forward:
@@ -16,6 +16,10 @@ class _Forward:
         if u.gn is not None:
             # GroupNorm: ONE launch -- the slabs (+ the convolution's bias) summed into LDS, the (sample, group) statistics
             # taken from the resident block, the output into ``u.y`` and the consumer's x half
+            if u.gn_parts:  # (a block beyond one workgroup's LDS: the parts' statistics, then their combination and y)
+                self._launch("hf_gn_split_stats", *gn_split_stats_args(u, u.tbuf, splits, u.tbuf.shape[1], u.a, u.conv.bias))
+                self._launch("hf_gn_split_forward", *gn_split_forward_args(u, u.a))
+                return
             self._launch("hf_gn_forward", *gn_forward_args(u, u.tbuf, splits, u.tbuf.shape[1], u.a, u.conv.bias))
             return
         if u.train:
@@ -66,7 +70,10 @@ class _Forward:
         of a deep net by ~1e-4 of its max-norm: not an error of either, but it would drown the comparison below."""
         for u in self.units:
             u.a.copy_(u.ra)
-            if u.gn is not None:  # (the statistics of the model's map -- its output is overwritten just below)
+            if u.gn is not None and u.gn_parts:  # (the statistics of the model's map -- its output is overwritten just below)
+                self._launch("hf_gn_split_stats", *gn_split_stats_args(u, u.a, 1, 0))
+                self._launch("hf_gn_split_forward", *gn_split_forward_args(u, u.a))
+            elif u.gn is not None:
                 self._launch("hf_gn_forward", *gn_forward_args(u, u.a, 1, 0))
             u.y.copy_(u.ry)
             if u.yout2 is not None:

@@ -89,7 +89,15 @@ class PlainStackEngine(_ConvEngine):
     is ONE launch too, ``hf_gn_act_adjoint2`` -- its seven (sample, group) means in two rounds from TWO resident blocks (the
     second sweep's masked cotangent and the tangent convolution's sum), the cotangent ``u.gah`` the convolution's second-order
     backward reads, and complete second-order rows of scale, shift and convolution bias -- so such a unit costs a Hessian
-    product the launches of a bias unit.  Opt-in; measured on one net."""
+    product the launches of a bias unit.  Opt-in; measured on one net.
+
+    Split GroupNorm units (``HF_GN_SPLIT=1`` on top): a (sample, group) block beyond 16 384 floats -- ``GroupNorm(1, C)``,
+    large maps -- is cut along the pixels into ``u.gn_parts`` parts, one workgroup per sample x span x part, and every
+    direction is a reduce and an apply launch in stream order (``hf_gn_split_stats`` / ``_forward``, ``_tangent_sums`` /
+    ``_act_tangent``, ``_adjoint_sums`` / ``_act_adjoint``): per-part fp64 partials in ``u.gn_tab``, added in part order by
+    every workgroup of the apply launch, no atomics.  Such a unit costs 6 launches per product (tangent convolution, 2, 2,
+    D + W gradient); its rows arrive as ``u.rb = n * parts`` and ``diag_ef`` takes ``hf_gn_split_rows_sqsum``.  GGN only:
+    Hessian products through a split unit are declined.  Units within the limit keep the one-launch kernels."""
 
     mode = ("fused curvature engine (plain conv-ReLU stack): own deterministic convolutions (split-K slabs summed "
             "by the consumer kernel), bias / ReLU / max-pool fused, 4 launches per layer")
@@ -310,8 +318,8 @@ class PlainStackEngine(_ConvEngine):
     def _layout_gn(self, u, gn, cy, nxt):
         """The GroupNorm behind ``u``'s convolution (output record ``cy``) and the layer ``nxt`` behind it: the unit's output
         record and ReLU flag.  What the kernels of hf_gn.hip take: opted in, affine, groups of channel quads, a (sample,
-        group) block of ``h*w*cg`` floats within one workgroup's LDS; one process; Hessian products only with
-        ``HF_GN_HESSIAN=1``."""
+        group) block of ``h*w*cg`` floats within one workgroup's LDS -- beyond it, with ``HF_GN_SPLIT=1``, the split kernels
+        (``u.gn_parts`` parts per block, GGN products only); one process; Hessian products only with ``HF_GN_HESSIAN=1``."""
         n, c, h, w = cy.shape
         cg = c // gn.num_groups
         what = f"{u.name}: GroupNorm({gn.num_groups}, {c})"
@@ -321,9 +329,16 @@ class PlainStackEngine(_ConvEngine):
             raise _Unsupported(f"{what}: affine=False is not covered")
         if cg % 4:
             raise _Unsupported(f"{what}: {cg} channels per group (the kernels take multiples of 4)")
-        if h * w * cg > GN_LDS_FLOATS:
+        split = h * w * cg > GN_LDS_FLOATS
+        if split and os.environ.get("HF_GN_SPLIT", "0") != "1":
             raise _Unsupported(f"{what}: a block of h*w*span = {h * w} * {cg} = {h * w * cg} floats (one workgroup's LDS holds "
-                               f"{GN_LDS_FLOATS})")
+                               f"{GN_LDS_FLOATS}) (opt-in on top of HF_GN_ENGINE=1: HF_GN_SPLIT=1)")
+        if split and cg > GN_LDS_FLOATS:
+            raise _Unsupported(f"{what}: {cg} channels per group (one pixel of a group must fit one workgroup's LDS: "
+                               f"{GN_LDS_FLOATS} floats)")
+        if split and self.hessian:
+            raise _Unsupported(f"{what}: Hessian products through a split GroupNorm unit are not covered (a block of "
+                               f"{h * w * cg} floats: hf_gn_act_adjoint2 needs two resident blocks)")
         if self.hessian and os.environ.get("HF_GN_HESSIAN", "0") != "1":
             raise _Unsupported(f"{what}: Hessian products through a GroupNorm unit are not covered (opt-in on top of "
                                "HF_GN_ENGINE=1: HF_GN_HESSIAN=1)")
@@ -333,6 +348,8 @@ class PlainStackEngine(_ConvEngine):
         if not _same(gx, cy):
             raise _Unsupported(f"{what}: it does not consume the convolution's output")
         u.gn = gn
+        # (a block beyond one workgroup's LDS: the split kernels, a reduce and an apply launch per direction)
+        u.gn_parts = _lib.gn_split_plan(n, h * w, c, gn.num_groups)[1] if split else 0
         if type(nxt) is nn.ReLU and not nxt.inplace:
             rx, ry = records_of(nxt, with_input=True)
             if _same(rx, gy):

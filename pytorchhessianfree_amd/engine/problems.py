@@ -155,11 +155,45 @@ def gn_adjoint2_args(u, srcs, v_cb, v_gamma):
             u.gn_mean, u.gn_rstd, u.gn.weight, v_gamma, u.y if u.relu else None, *_gn_dims(u))
 
 
+def gn_split_stats_args(u, a, splits, slab, a_out=None, conv_bias=None):
+    """``hf_gn_split_stats``: the parts' partial statistics of the slabs ``a`` (+ the convolution's bias) into ``u.gn_tab``;
+    the summed map -> ``a_out``."""
+    return (a_out, u.gn_tab, a, splits, slab, conv_bias, *_gn_dims(u))
+
+
+def gn_split_forward_args(u, s):
+    """``hf_gn_split_forward``: the statistics from ``u.gn_tab`` and the unit's output from the summed map ``s``."""
+    k = u.a.shape[1]
+    return (u.y, u.yout2, 2 * k if u.yout2 is not None else 0, u.gn_mean, u.gn_rstd, s, u.gn_tab, u.gn.weight, u.gn.bias,
+            float(u.gn.eps), 1 if u.relu else 0, *_gn_dims(u))
+
+
+def gn_split_tangent_args(u, v_cb, vg, vb):
+    """``hf_gn_split_tangent_sums`` and ``hf_gn_split_act_tangent``: the tangent convolution's sum raw into the consumer's
+    operand and its partial sums into ``u.gn_tab``; then the operand rewritten in place."""
+    return ((u.tout, u.tout_ld, u.gn_tab, u.tbuf, u.sT, u.tbuf.shape[1], v_cb, u.a, u.gn_mean, u.gn_rstd, *_gn_dims(u)),
+            (u.tout, u.tout_ld, u.gn_tab, u.a, u.gn_mean, u.gn_rstd, u.gn.weight, vg, vb, u.y if u.relu else None,
+             *_gn_dims(u)))
+
+
+def gn_split_adjoint_args(u, srcs):
+    """``hf_gn_split_adjoint_sums`` and ``hf_gn_split_act_adjoint``: the masked cotangent into ``u.g`` where the unit keeps
+    it (else into ``u.ga``, which the second launch rewrites in place), the parts' rows of scale and shift; then ``u.ga``
+    and the parts' rows of the convolution bias."""
+    (gy, splits, slab), = srcs
+    g = u.g if u.needs_g else u.ga
+    return ((g, u.gn_tab, u.gw if u.pg is not None else None, u.gb if u.pb is not None else None, gy, splits, slab, u.a,
+             u.gn_mean, u.gn_rstd, u.gn.weight, u.y if u.relu else None, *_gn_dims(u)),
+            (u.ga, u.gcb if u.pcb is not None else None, g, u.gn_tab, u.a, u.gn_mean, u.gn_rstd, u.gn.weight, *_gn_dims(u)))
+
+
 def gn_rows_sqsum_args(u, out, offs, pre):
-    """``hf_gn_rows_sqsum``: the unit's entries of ``diag_ef`` straight into ``out`` (``offs``: the parameters' offsets) from
+    """``hf_gn_rows_sqsum`` (a split unit: ``hf_gn_split_rows_sqsum``): the unit's entries of ``diag_ef`` straight into ``out`` (``offs``: the parameters' offsets) from
     the per-sample rows the adjoint launch left, each scaled by ``pre`` before it is squared."""
     tabs = [x for pi, rows in ((u.pg, u.gw), (u.pb, u.gb), (u.pcb, getattr(u, "gcb", None)))
             for x in ((out[offs[pi]:], rows) if pi is not None else (None, None))]
+    if u.gn_parts:  # (``hf_gn_split_rows_sqsum``: the sample's parts added first)
+        return (*tabs, float(pre), u.a.shape[0], u.gn_parts, u.a.shape[1])
     return (*tabs, float(pre), u.a.shape[0], u.a.shape[1])
 
 

@@ -7,7 +7,7 @@ import os
 
 from .. import _lib
 from .problems import (affine_args, affine_problem, affine_train_args, affine_train_problem, conv_args, conv_bnsum,
-                       conv_problem, gn_tangent_args)
+                       conv_problem, gn_split_tangent_args, gn_tangent_args)
 
 
 def head_fused_shape_ok(rows, features, classes):
@@ -57,6 +57,11 @@ class _TangentSweep:
         if u.gn is not None:
             # GroupNorm: t_y = mask * (w*rstd * (t_a - E[t_a] - xhat * E[xhat t_a]) + xhat * v_w + v_b), the two means over
             # the (sample, group) block taken inside the launch; t_a: the slabs' sum + the convolution bias's tangent
+            if u.gn_parts:  # (split unit: the raw sum into the operand + the parts' sums, then the operand in place)
+                sums, act = gn_split_tangent_args(u, self._param_slice(v, u.pcb, k), vg, vb)
+                self._launch("hf_gn_split_tangent_sums", *sums)
+                self._launch("hf_gn_split_act_tangent", *act)
+                return
             self._launch("hf_gn_act_tangent", *gn_tangent_args(u, self._param_slice(v, u.pcb, k), vg, vb))
             return
         if u.train:

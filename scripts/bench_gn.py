@@ -4,7 +4,11 @@ units on the one-launch kernels of hf_gn.hip (``HF_GN_ENGINE=1``) against the pa
 -- autograd sweeps over the prepared model, captured (``--curvature hessian``: ``HF_GN_ENGINE=1 HF_GN_HESSIAN=1`` against the
 captured autograd ``HessianOperator``).  ``--reps`` repetitions (default 9) of at least ``--seconds`` each,
 the two operators alternating on one device; one JSON line per operator to ``--out`` with every repetition's rate, the
-median and the spread (max - min); the engine's record also counts the library launches of one product."""
+median and the spread (max - min); the engine's record also counts the library launches of one product.
+
+``--groups 1``: ``GroupNorm(1, .)`` instead -- every unit at 32x32 and 16x16 is then beyond one workgroup's LDS and takes
+the split kernels (``HF_GN_ENGINE=1 HF_GN_SPLIT=1``; GGN only), against the captured autograd operator the same model runs
+on without the switches; the record counts the split units (``profiles/gn_split.jsonl``)."""
 import argparse
 import json
 import os
@@ -38,9 +42,9 @@ class AllCNNCGN(nn.Module):
         return torch.flatten(self.net(x), -3)
 
 
-def graphed(engine, batch, dev="cuda", hessian=False):
+def graphed(engine, batch, dev="cuda", hessian=False, groups=8):
     torch.manual_seed(0)
-    model = AllCNNCGN().eval().to(dev)
+    model = AllCNNCGN(groups=groups).eval().to(dev)
     gen = torch.Generator().manual_seed(0)
     x, t = torch.rand(batch, 3, 32, 32, generator=gen).to(dev), torch.randint(0, 100, (batch,), generator=gen).to(dev)
     lossf = nn.CrossEntropyLoss()
@@ -53,7 +57,7 @@ def graphed(engine, batch, dev="cuda", hessian=False):
             return curvature.hessian_operator(lossf(out, t), out, params)
         return curvature.ggn_operator(lossf(out, t), out, params)
 
-    switches = ("HF_GN_ENGINE", "HF_GN_HESSIAN") if hessian else ("HF_GN_ENGINE",)
+    switches = ("HF_GN_ENGINE", "HF_GN_HESSIAN") if hessian else ("HF_GN_ENGINE", "HF_GN_SPLIT")
     os.environ.update({name: "1" if engine else "0" for name in switches})
     try:
         op = curvature.maybe_graphed(builder, params=params)
@@ -72,6 +76,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=0.5)
     ap.add_argument("--out", default="")
     ap.add_argument("--curvature", choices=("ggn", "hessian"), default="ggn")
+    ap.add_argument("--groups", type=int, default=8, help="groups of every GroupNorm (1: blocks beyond the LDS, split units)")
     args = ap.parse_args()
     hf.configure()
 
@@ -84,9 +89,12 @@ def main():
 
     hessian = args.curvature == "hessian"
     kind = "Hessian" if hessian else "GGN"
-    base = dict(workload="allcnnc_groupnorm8", batch=args.batch, unit=f"{kind} products/s (hipGraph replay + device sync)",
+    base = dict(workload=f"allcnnc_groupnorm{args.groups}", batch=args.batch, unit=f"{kind} products/s (hipGraph replay + device sync)",
                 device=torch.cuda.get_device_name(0))
-    eng, ref = graphed(True, args.batch, hessian=hessian), graphed(False, args.batch, hessian=hessian)
+    eng, ref = (graphed(e, args.batch, hessian=hessian, groups=args.groups) for e in (True, False))
+    split_units = sum(bool(u.gn_parts) for u in eng.op.units)
+    if split_units:
+        base["split_units"] = split_units
     v = torch.randn(eng.n, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
     for op in (eng, ref):
         op.input_buffer.copy_(v)
