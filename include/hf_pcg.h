@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 34
+#define HF_ABI_VERSION 35
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -1368,6 +1368,20 @@ int hf_gn_rows_sqsum(void* out_w, const void* rows_w, void* out_b, const void* r
  *                             (splits = (n * parts, c)) adds the rows.
  *   hf_gn_split_rows_sqsum    out_*[c] = sum_n (pre * row_*[n][c])^2, row[n] = the sample's `parts` partial rows added in
  *                             part order in fp64 and rounded once; otherwise as hf_gn_rows_sqsum.
+ *
+ * The tangent of the split adjoint (ABI 35): what hf_gn_act_adjoint2 computes -- g, p, t, g', p' and the formulas as there --
+ * as a reduce and an apply launch.  T1 = E[t] and Tx = E[xh t] are not reduced again: `t_partials` is the table
+ * hf_gn_split_tangent_sums left for the SAME t_a (and v_conv_bias) in the tangent sweep of the same product, untouched
+ * since; with them known, tau is formed in the reduce launch and E[p tau] is taken directly -- ONE reduce launch.
+ *   hf_gn_split_adjoint2_sums g' = m * (sum of gy2's slabs) -> gp;  t = sum of t_a's slabs (+ v_conv_bias[c]) -> t (two dense
+ *                             maps, gp != t; gp may be the ga2 of the apply launch);  partials [n, groups, parts, 5] (its own
+ *                             table, not t_partials): sum p, sum p*xh, sum p', sum p'*xh, sum p*tau;  rows [n * parts, c],
+ *                             each nullable: gb_rows = sum g', gw_rows = sum (g'*xh + g*rstd*tau) over the part.  Both
+ *                             blocks of the part are resident: the smaller of two LDS sizes that holds them.
+ *   hf_gn_split_act_adjoint2  P1, Px, Q1, Qx, E[p tau] = the partials' sums / N, T1, Tx from t_partials;  ga2 as above from
+ *                             the maps gp (ga2 itself is allowed: in place), t, a and g;  gcb_rows [n * parts, c] = sum ga2
+ *                             over the part (nullable).  hf_pack_ex (splits = (n * parts, c)) adds the rows.
+ *                             v_gamma / v_conv_bias / mask_src: NULL where frozen / absent.
  */
 int hf_gn_split_plan(int64_t n, int64_t hw, int64_t c, int64_t groups, int* span, int* parts, int* part_pixels);
 int hf_gn_split_stats(void* a_out, void* partials, const void* a, int splits, int64_t slab_stride, const void* conv_bias,
@@ -1391,6 +1405,15 @@ int hf_gn_split_act_adjoint(void* ga, void* gcb_rows, const void* g, const void*
                             int dtype, void* stream);
 int hf_gn_split_rows_sqsum(void* out_w, const void* rows_w, void* out_b, const void* rows_b, void* out_cb,
                            const void* rows_cb, double pre, int64_t n, int64_t parts, int64_t c, int dtype, void* stream);
+int hf_gn_split_adjoint2_sums(void* gp, void* t, void* partials, void* gw_rows, void* gb_rows, const void* gy2, int splits,
+                              int64_t slab_stride, const void* t_a, int t_splits, int64_t t_slab_stride,
+                              const void* v_conv_bias, const void* t_partials, const void* a, const void* g, const void* mean,
+                              const void* rstd, const void* gamma, const void* v_gamma, const void* mask_src, int64_t n,
+                              int64_t hw, int64_t c, int64_t groups, int dtype, void* stream);
+int hf_gn_split_act_adjoint2(void* ga2, void* gcb_rows, const void* gp, const void* t, const void* partials,
+                             const void* t_partials, const void* a, const void* g, const void* mean, const void* rstd,
+                             const void* gamma, const void* v_gamma, int64_t n, int64_t hw, int64_t c, int64_t groups,
+                             int dtype, void* stream);
 
 /* ---- RCCL (resolved at run time from the already-loaded librccl) ----------- */
 typedef struct hf_comm hf_comm_t;

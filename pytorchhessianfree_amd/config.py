@@ -194,14 +194,15 @@ SWITCHES = {
                      "tests/test_gn_engine_gpu.py::test_eval_point_against_float64"),
     "HF_GN_HESSIAN": ("0", "1: with HF_GN_ENGINE=1, curvature_opt='hessian' on a net with GroupNorm units takes the plain-"
                       "stack engine (the second-order half of a GroupNorm unit in one launch, hf_gn_act_adjoint2: the "
-                      "blocks of g' and t both resident in LDS) instead of the autograd operator; opt-in like the engine "
-                      "it stands on (profiles/gn_hessian.jsonl)",
+                      "blocks of g' and t both resident in LDS; with HF_GN_SPLIT=1 a split unit's in a reduce and an apply "
+                      "launch, hf_gn_split_adjoint2_sums / hf_gn_split_act_adjoint2) instead of the autograd operator; "
+                      "opt-in like the engine it stands on (profiles/gn_hessian.jsonl, profiles/gn_split_hessian.jsonl)",
                       "tests/test_gn_hessian_engine_gpu.py::test_hessian_products_against_float64"),
     "HF_GN_SPLIT": ("0", "1: with HF_GN_ENGINE=1, a GroupNorm unit whose (sample, group) block exceeds one workgroup's LDS "
                     "(16 384 floats: GroupNorm(1, C), large maps) takes the split kernels of hf_gn.hip -- the block cut "
                     "along the pixels, a reduce and an apply launch per direction, 6 launches per unit and product -- "
-                    "instead of declining the model; GGN products only; opt-in like the engine it stands on "
-                    "(profiles/gn_split.jsonl)",
+                    "instead of declining the model; Hessian products through such a unit with HF_GN_HESSIAN=1 as the third "
+                    "switch (a reduce and an apply launch there too); opt-in like the engine it stands on (profiles/gn_split.jsonl)",
                     "tests/test_gn_split_engine_gpu.py::test_eval_point_against_float64"),
     "HF_CHUNKED_ALLREDUCE": ("auto", "0 / 1: force the single-graph resp. the two-phase data-parallel product",
                              "tests/test_distributed_gpu.py::test_step_two_ranks_engine_session_equals_cpu_whole_batch"),

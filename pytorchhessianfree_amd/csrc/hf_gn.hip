@@ -116,6 +116,28 @@
 //   m1, mx   = fp32( fp64 sum of the parts' partials / N )
 //   ga       = rstd * ((p - m1) - xh * mx)                                                hf_gn_act_adjoint's
 //   gcb_rows[n * parts + part][c] = fp32( fp64 sum over the slots of the chains of ga )
+// hf_gn_split_adjoint2_sums  (the split form of hf_gn_act_adjoint2; mu, rstd, g as there.  ONE reduce launch although Qt's
+//                      mean needs T1 and Tx first: they are the tangent sweep's -- hf_gn_split_tangent_sums left sum t and
+//                      sum xh * t of the SAME t per part in its table, and nothing between that sweep and this one of the same
+//                      product writes it -- so tau is formed here and p * tau is reduced directly: five sums, no cancelling
+//                      E[p t] - T1 P1 - Tx Px)
+//   g'       = (y > 0 | no ReLU) ? s of the second sweep's cotangent slabs : 0  -> gp     resident block 1
+//   t        = s of the tangent convolution's slabs [+ v_conv_bias[c]]  -> t              resident block 2 (the tangent sweep
+//              rewrote its operand in place: the raw t is summed again, the same additions in the same order)
+//   T1, Tx   = fp32( fp64 sum of the tangent table's partials, part order / N )           hf_gn_split_act_tangent's m1, mx
+//   xh, p, p' as in hf_gn_act_adjoint2;   tau = (t - T1) - xh * Tx                        3 behind t, xh, T1, Tx
+//   partials = fp64 sums of the chains of p, p * xh, p', p' * xh, p * tau                 [n, groups, parts, 5]
+//   gb_rows[n * parts + part][c] = fp32( fp64 sum over the slots of the chains of g' down the part's pixels ),
+//   gw_rows: of g' * xh + g * rt,  rt = rstd * tau  (3 more)
+//   Both blocks resident as in hf_gn_act_adjoint2: instantiations for parts of up to 8 192 and 16 384 floats (73 / 137 KB).
+//   Bytes per element: this launch reads 4 (s2 + sT) of slabs [+ 4: the mask] + 8 (a, g; again from L2 in the rows' pass) and
+//   writes 8 (g', t); the apply launch reads 16 (g', t, a, g) and writes 4.  Summing the slabs again in the apply launch would
+//   trade those 8 + 8 for 4 (s2 + sT) [+ 4] more reads: no gain from s2 + sT = 3 [4] on, and a Hessian product's cotangent
+//   alone arrives in two slabs or more wherever the consumer is a dense convolution (its extras are more slabs).
+// hf_gn_split_act_adjoint2  (g': read back; it may be ga2's own buffer)
+//   P1, Px, Q1, Qx = fp32( fp64 sum of the parts' partials / N );  Qt = rstd * fp32( .. of p * tau .. );  T1, Tx as above
+//   Qs, rT, rt, ga, ga'                                                                    hf_gn_act_adjoint2's, per element
+//   gcb_rows[n * parts + part][c] = fp32( fp64 sum over the slots of the chains of ga' )
 // hf_gn_split_rows_sqsum
 //   row      = fp32( fp64 sum over the sample's parts, part order, of rows[n * parts + part][c] )      ONE rounding
 //   out[c]   = fp32( fp64 sum over the samples, ascending, of fp32(t * t),  t = fp32(pre * row) )
@@ -535,6 +557,14 @@ __device__ __forceinline__ Gn2Point gn2_point(float x, float g, float gp, float 
 // per-group results of the two rounds, as the elementwise part reads them
 enum { G2_T1, G2_TX, G2_P1, G2_PX, G2_Q1, G2_QS, G2_RT, G2_STATS };
 
+// ga' of one element from the group's seven numbers; rt = rstd * tau on the way (the scale's row reads it)
+__device__ __forceinline__ float gn2_ga2(const Gn2Point& e, float t, float rs, float T1, float Tx, float P1, float Px,
+                                         float Q1, float Qs, float rT, float& rt) {
+  rt = rs * ((t - T1) - e.xh * Tx);
+  const float ga = rs * ((e.p - P1) - e.xh * Px);
+  return rs * (((e.pp - Q1) - e.xh * Qs) - rt * Px) - rT * ga;
+}
+
 // FLOATS: the floats of ONE resident block this instantiation reserves (hw * span <= FLOATS); the launch takes the smallest
 template <int FLOATS>
 __global__ __launch_bounds__(BLOCK) void k_gn_act_adjoint2(
@@ -631,9 +661,8 @@ __global__ __launch_bounds__(BLOCK) void k_gn_act_adjoint2(
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const Gn2Point e = gn2_point(x.e[k], g.e[k], gp.e[k], w.e[k], vg.e[k], has_vg, mu, rs);
-          const float rt = rs * ((t.e[k] - T1) - e.xh * Tx);
-          const float ga = rs * ((e.p - P1) - e.xh * Px);
-          o.e[k] = rs * (((e.pp - Q1) - e.xh * Qs) - rt * Px) - rT * ga;
+          float rt;
+          o.e[k] = gn2_ga2(e, t.e[k], rs, T1, Tx, P1, Px, Q1, Qs, rT, rt);
           sb.e[k] += gp.e[k];
           sw.e[k] += gp.e[k] * e.xh + g.e[k] * rt;
           sc.e[k] += o.e[k];
@@ -670,10 +699,10 @@ __global__ __launch_bounds__(BLOCK) void k_gn_rows_sqsum(GnSqTables tabs, float 
 // ---- the split family: blocks beyond one workgroup's LDS, a reduce and an apply launch per direction -------------------
 // (the header's "Split family" section: work split, partials table, arithmetic chains)
 
-// the partials of (sample, group gl of the block's span): [parts][2] doubles of the table [n, groups, parts, 2]
+// the partials of (sample, group gl of the block's span): [parts][K] doubles of the table [n, groups, parts, K]
 template <typename D>
-__device__ __forceinline__ D* gn_tab(D* tab, const GnBlock& b, int groups, int gl) {
-  return tab + ((long long)b.nb * groups + b.g0 + gl) * gridDim.x * 2;
+__device__ __forceinline__ D* gn_tab(D* tab, const GnBlock& b, int groups, int gl, int K = 2) {
+  return tab + ((long long)b.nb * groups + b.g0 + gl) * gridDim.x * K;
 }
 
 // apply launches: lane gl < ng adds the two partial sums of its group over the parts, in part order, and leaves their
@@ -975,6 +1004,159 @@ __global__ __launch_bounds__(BLOCK) void k_gn_split_act_adjoint(
   }
 }
 
+// ---- the tangent of the split adjoint (a Hessian product's second sweep through a split unit) ---------------------------
+// the five partial sums per (sample, group, part): of p, p * xh, p', p' * xh and p * tau
+enum { S2_P1, S2_PX, S2_Q1, S2_QX, S2_PT, S2_K };
+
+// FLOATS: the floats of ONE resident block (part_pixels * span <= FLOATS), as for k_gn_act_adjoint2
+template <int FLOATS>
+__global__ __launch_bounds__(BLOCK) void k_gn_split_adjoint2_sums(
+    float* __restrict__ gp_out, float* __restrict__ t_out, double* __restrict__ tab, float* __restrict__ gw_rows,
+    float* __restrict__ gb_rows, const float* __restrict__ gy2, int splits, long long slab, const float* __restrict__ ta,
+    int t_splits, long long t_slab, const float* __restrict__ v_cb, const double* __restrict__ t_tab,
+    const float* __restrict__ a, const float* __restrict__ g1, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ v_gamma,
+    const float* __restrict__ mask_src, int hw, int c, int groups, int cg, int gps, int pp) {
+  __shared__ F4 tg[FLOATS / 4];  // g' of the part
+  __shared__ F4 tt[FLOATS / 4];  // t of the part
+  __shared__ double red[S2_K * WAVES];
+  __shared__ double rsum[BLOCK * 4];
+  __shared__ float sT1[GN_MAX_GPS], sTx[GN_MAX_GPS];
+  const GnBlock b = gn_part(hw, c, groups, cg, gps, pp);
+  gn_parts_means(sT1, sTx, t_tab, b, groups, (double)hw * (double)cg);  // T1, Tx: the tangent sweep's partials
+  gn_stage_masked(tg, b, gy2, splits, slab, mask_src, c);
+  gn_stage(tt, b, ta, t_splits, t_slab, v_cb, t_out, c, c);  // t, resident, and out for the apply launch
+  __syncthreads();
+  const float* stat_mu = mean + (long long)b.nb * groups + b.g0;
+  const float* stat_rs = rstd + (long long)b.nb * groups + b.g0;
+  const bool has_vg = v_gamma != nullptr;
+  const F4 zero = {{0.f, 0.f, 0.f, 0.f}};
+  for (int it = 0; it < b.iters; ++it) {
+    const int gl = b.team + it * b.nteams;
+    const bool on = gl < b.ng;
+    const int gq = on ? b.np * b.qpg : 0;
+    const float mu = on ? stat_mu[gl] : 0.f, rs = on ? stat_rs[gl] : 0.f;
+    const float T1 = on ? sT1[gl] : 0.f, Tx = on ? sTx[gl] : 0.f;
+    F4 s[S2_K] = {zero, zero, zero, zero, zero};
+    for (int e = b.lt; e < gq; e += b.T) {
+      const int p = e / b.qpg, jj = e - p * b.qpg, j = gl * b.qpg + jj;
+      const long long gi = b.base + (long long)p * c + 4 * j;
+      const F4 gp = tg[p * b.sq + j], t = tt[p * b.sq + j], x = ld4(a + gi), g = ld4(g1 + gi);
+      const F4 w = ld4s(gamma + b.ch0 + 4 * j), vg = has_vg ? ld4s(v_gamma + b.ch0 + 4 * j) : zero;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const Gn2Point o = gn2_point(x.e[k], g.e[k], gp.e[k], w.e[k], vg.e[k], has_vg, mu, rs);
+        const float tau = (t.e[k] - T1) - o.xh * Tx;
+        s[S2_P1].e[k] += o.p;
+        s[S2_PX].e[k] += o.p * o.xh;
+        s[S2_Q1].e[k] += o.pp;
+        s[S2_QX].e[k] += o.pp * o.xh;
+        s[S2_PT].e[k] += o.p * tau;
+      }
+    }
+    double v[S2_K];
+#pragma unroll
+    for (int i = 0; i < S2_K; ++i) v[i] = quad_sum(s[i]);
+    gn_team_sum<S2_K>(v, red, b);
+    if (on && b.lt == 0) {
+      double* o = gn_tab(tab, b, groups, gl, S2_K) + S2_K * blockIdx.x;
+#pragma unroll
+      for (int i = 0; i < S2_K; ++i) o[i] = v[i];
+    }
+  }
+  // g' leaves, and the part's rows of scale and shift: lane (slot, column) walks its channel quad down the part's pixels
+  const int cols = b.sq < BLOCK ? b.sq : BLOCK, slots = BLOCK / cols;
+  const int slot = threadIdx.x / cols, jl = threadIdx.x - slot * cols;
+  for (int j0 = 0; j0 < b.sq; j0 += cols) {
+    const int j = j0 + jl;
+    const bool act = slot < slots && j < b.sq;
+    F4 sb = zero, sw = zero;
+    if (act) {
+      const int gl = j / b.qpg;
+      const float mu = stat_mu[gl], rs = stat_rs[gl], T1 = sT1[gl], Tx = sTx[gl];
+      for (int p = slot; p < b.np; p += slots) {
+        const long long gi = b.base + (long long)p * c + 4 * j;
+        const F4 gp = tg[p * b.sq + j], t = tt[p * b.sq + j], x = ld4(a + gi), g = ld4(g1 + gi);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float xh = (x.e[k] - mu) * rs, rt = rs * ((t.e[k] - T1) - xh * Tx);
+          sb.e[k] += gp.e[k];
+          sw.e[k] += gp.e[k] * xh + g.e[k] * rt;
+        }
+        *reinterpret_cast<F4*>(gp_out + gi) = gp;
+      }
+    }
+    const long long at = ((long long)b.nb * gridDim.x + blockIdx.x) * c + b.ch0 + 4 * j;
+    if (gw_rows) gn_row_store(gw_rows, sw, rsum, slots, cols, slot, jl, act, at);
+    if (gb_rows) gn_row_store(gb_rows, sb, rsum, slots, cols, slot, jl, act, at);
+  }
+}
+
+// (gp may be ga2_out itself: read and rewritten in place, each element by the lane that read it -- no __restrict__)
+__global__ __launch_bounds__(BLOCK) void k_gn_split_act_adjoint2(
+    float* ga2_out, float* __restrict__ gcb_rows, const float* gp_in, const float* __restrict__ t_map,
+    const double* __restrict__ tab, const double* __restrict__ t_tab, const float* __restrict__ a,
+    const float* __restrict__ g1, const float* __restrict__ mean, const float* __restrict__ rstd,
+    const float* __restrict__ gamma, const float* __restrict__ v_gamma, int hw, int c, int groups, int cg, int gps, int pp) {
+  __shared__ double rsum[BLOCK * 4];
+  __shared__ float stats[G2_STATS][GN_MAX_GPS];
+  const GnBlock b = gn_part(hw, c, groups, cg, gps, pp);
+  const float* stat_mu = mean + (long long)b.nb * groups + b.g0;
+  const float* stat_rs = rstd + (long long)b.nb * groups + b.g0;
+  if ((int)threadIdx.x < b.ng) {  // the group's seven numbers from the parts' partials, part order, fp64
+    const double* q = gn_tab(tab, b, groups, threadIdx.x, S2_K);
+    const double* tq = gn_tab(t_tab, b, groups, threadIdx.x);
+    const double cnt = (double)hw * (double)cg;
+    double v[S2_K] = {0.0, 0.0, 0.0, 0.0, 0.0}, t1 = 0.0, tx = 0.0;
+    for (int i = 0; i < (int)gridDim.x; ++i) {
+#pragma unroll
+      for (int k = 0; k < S2_K; ++k) v[k] += q[S2_K * i + k];
+      t1 += tq[2 * i];
+      tx += tq[2 * i + 1];
+    }
+    const float rs = stat_rs[threadIdx.x], Tx = (float)(tx / cnt), Qt = rs * (float)(v[S2_PT] / cnt);
+    stats[G2_T1][threadIdx.x] = (float)(t1 / cnt);
+    stats[G2_TX][threadIdx.x] = Tx;
+    stats[G2_P1][threadIdx.x] = (float)(v[S2_P1] / cnt);
+    stats[G2_PX][threadIdx.x] = (float)(v[S2_PX] / cnt);
+    stats[G2_Q1][threadIdx.x] = (float)(v[S2_Q1] / cnt);
+    stats[G2_QS][threadIdx.x] = (float)(v[S2_QX] / cnt) + Qt;
+    stats[G2_RT][threadIdx.x] = rs * Tx;
+  }
+  __syncthreads();
+  const bool has_vg = v_gamma != nullptr;
+  const F4 zero = {{0.f, 0.f, 0.f, 0.f}};
+  const int cols = b.sq < BLOCK ? b.sq : BLOCK, slots = BLOCK / cols;
+  const int slot = threadIdx.x / cols, jl = threadIdx.x - slot * cols;
+  for (int j0 = 0; j0 < b.sq; j0 += cols) {
+    const int j = j0 + jl;
+    const bool act = slot < slots && j < b.sq;
+    F4 sc = zero;
+    if (act) {
+      const int gl = j / b.qpg;
+      const float mu = stat_mu[gl], rs = stat_rs[gl];
+      const float T1 = stats[G2_T1][gl], Tx = stats[G2_TX][gl], P1 = stats[G2_P1][gl], Px = stats[G2_PX][gl];
+      const float Q1 = stats[G2_Q1][gl], Qs = stats[G2_QS][gl], rT = stats[G2_RT][gl];
+      const F4 w = ld4s(gamma + b.ch0 + 4 * j), vg = has_vg ? ld4s(v_gamma + b.ch0 + 4 * j) : zero;
+      for (int p = slot; p < b.np; p += slots) {
+        const long long gi = b.base + (long long)p * c + 4 * j;
+        const F4 gp = ld4(gp_in + gi), t = ld4(t_map + gi), x = ld4(a + gi), g = ld4(g1 + gi);
+        F4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const Gn2Point e = gn2_point(x.e[k], g.e[k], gp.e[k], w.e[k], vg.e[k], has_vg, mu, rs);
+          float rt;
+          o.e[k] = gn2_ga2(e, t.e[k], rs, T1, Tx, P1, Px, Q1, Qs, rT, rt);
+          sc.e[k] += o.e[k];
+        }
+        *reinterpret_cast<F4*>(ga2_out + gi) = o;
+      }
+    }
+    const long long at = ((long long)b.nb * gridDim.x + blockIdx.x) * c + b.ch0 + 4 * j;
+    if (gcb_rows) gn_row_store(gcb_rows, sc, rsum, slots, cols, slot, jl, act, at);
+  }
+}
+
 // out[c] = sum_n (pre * row[n][c])^2, row[n] = the sample's `parts` partial rows added in part order (fp64, one rounding)
 __global__ __launch_bounds__(BLOCK) void k_gn_split_rows_sqsum(GnSqTables tabs, float pre, int n, int parts, int c) {
   float* out = tabs.out[blockIdx.y];
@@ -1225,6 +1407,54 @@ int hf_gn_split_act_adjoint(void* ga, void* gcb_rows, const void* g, const void*
   hipLaunchKernelGGL(k_gn_split_act_adjoint, gn_split_grid(s), dim3(BLOCK), 0, (hipStream_t)stream, (float*)ga,
                      (float*)gcb_rows, (const float*)g, (const double*)partials, (const float*)a, (const float*)mean,
                      (const float*)rstd, (const float*)gamma, s.g.hw, s.g.c, s.g.groups, s.g.cg, s.g.gps, s.pp);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+int hf_gn_split_adjoint2_sums(void* gp, void* t, void* partials, void* gw_rows, void* gb_rows, const void* gy2, int splits,
+                              int64_t slab_stride, const void* t_a, int t_splits, int64_t t_slab_stride,
+                              const void* v_conv_bias, const void* t_partials, const void* a, const void* g, const void* mean,
+                              const void* rstd, const void* gamma, const void* v_gamma, const void* mask_src, int64_t n,
+                              int64_t hw, int64_t c, int64_t groups, int dtype, void* stream) {
+  GnSplitPlan s;
+  if (gn_split_ok(s, partials, n, hw, c, groups, dtype) != HF_OK) return HF_ERR_ARG;
+  if (!t_partials || ((uintptr_t)t_partials & 7) || t_partials == partials) return HF_ERR_ARG;
+  if (!gp || !t || gp == t || !a || !g || !mean || !rstd || !gamma || (int64_t)s.g.n * s.parts * s.g.c > 0x7fffffffLL)
+    return HF_ERR_ARG;
+  if (gn_slabs_ok(gy2, splits, slab_stride, s.g) != HF_OK || gn_slabs_ok(t_a, t_splits, t_slab_stride, s.g) != HF_OK)
+    return HF_ERR_ARG;
+  const void* al[] = {gp, t, gw_rows, gb_rows, gy2, t_a, a, g, mask_src};
+  if (gn_aligned(al) != HF_OK) return HF_ERR_ARG;
+  // two resident blocks, static LDS sized to the plan's part (as hf_gn_act_adjoint2; a part keeps at least 4 096 floats
+  // wherever the plan could choose, so the smallest size there has no use here)
+  auto kernel = s.pp * s.g.gps * s.g.cg <= GN_LDS_FLOATS / 2 ? k_gn_split_adjoint2_sums<GN_LDS_FLOATS / 2>
+                                                             : k_gn_split_adjoint2_sums<GN_LDS_FLOATS>;
+  hipLaunchKernelGGL(kernel, gn_split_grid(s), dim3(BLOCK), 0, (hipStream_t)stream, (float*)gp, (float*)t,
+                     (double*)partials, (float*)gw_rows, (float*)gb_rows, (const float*)gy2, splits, (long long)slab_stride,
+                     (const float*)t_a, t_splits, (long long)t_slab_stride, (const float*)v_conv_bias,
+                     (const double*)t_partials, (const float*)a, (const float*)g, (const float*)mean, (const float*)rstd,
+                     (const float*)gamma, (const float*)v_gamma, (const float*)mask_src, s.g.hw, s.g.c, s.g.groups, s.g.cg,
+                     s.g.gps, s.pp);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+int hf_gn_split_act_adjoint2(void* ga2, void* gcb_rows, const void* gp, const void* t, const void* partials,
+                             const void* t_partials, const void* a, const void* g, const void* mean, const void* rstd,
+                             const void* gamma, const void* v_gamma, int64_t n, int64_t hw, int64_t c, int64_t groups,
+                             int dtype, void* stream) {
+  GnSplitPlan s;
+  if (gn_split_ok(s, partials, n, hw, c, groups, dtype) != HF_OK) return HF_ERR_ARG;
+  if (!t_partials || ((uintptr_t)t_partials & 7)) return HF_ERR_ARG;
+  if (!ga2 || !gp || !t || t == ga2 || !a || !g || !mean || !rstd || !gamma ||
+      (int64_t)s.g.n * s.parts * s.g.c > 0x7fffffffLL)
+    return HF_ERR_ARG;
+  const void* al[] = {ga2, gcb_rows, gp, t, a, g};
+  if (gn_aligned(al) != HF_OK) return HF_ERR_ARG;
+  hipLaunchKernelGGL(k_gn_split_act_adjoint2, gn_split_grid(s), dim3(BLOCK), 0, (hipStream_t)stream, (float*)ga2,
+                     (float*)gcb_rows, (const float*)gp, (const float*)t, (const double*)partials,
+                     (const double*)t_partials, (const float*)a, (const float*)g, (const float*)mean, (const float*)rstd,
+                     (const float*)gamma, (const float*)v_gamma, s.g.hw, s.g.c, s.g.groups, s.g.cg, s.g.gps, s.pp);
   HF_HIP(hipGetLastError());
   return HF_OK;
 }

@@ -6,7 +6,7 @@ Mixin of ``_ConvEngine`` (engine/conv.py); see that class for the sweeps' overal
 from .. import _lib
 from .problems import (affine_args, affine_train_args, affine_train_problem, bn_adjoint_args, bn_adjoint_problem,
                        bn_adjoint_v4_args, conv_args, conv_backward_args, conv_problem, gn_adjoint2_args,
-                       gn_adjoint_args, gn_split_adjoint_args, problem)
+                       gn_adjoint_args, gn_split_adjoint2_args, gn_split_adjoint_args, problem)
 
 
 class _AdjointSweep:
@@ -37,12 +37,18 @@ class _AdjointSweep:
         if u.pool is not None:  # (a pooled unit of a plain stack: bias / ReLU / pool adjoint in one launch)
             self._pool_adjoint(u, srcs)
         elif second and u.gn is not None:
-            # GroupNorm inside a Hessian product: ONE launch is the whole tangent of the first-order adjoint -- u.gah and
-            # the complete second-order rows of scale, shift and convolution bias (formulas: csrc/hf_gn.hip)
+            # GroupNorm inside a Hessian product: ONE launch (a split unit: a reduce and an apply launch) is the whole
+            # tangent of the first-order adjoint -- u.gah and the complete second-order rows of scale, shift and convolution
+            # bias (formulas: csrc/hf_gn.hip)
             self._extras_wait(srcs)
             k = u.a.shape[1]
-            self._launch("hf_gn_act_adjoint2", *gn_adjoint2_args(u, srcs, self._param_slice(self._v, u.pcb, k),
-                                                                  self._param_slice(self._v, u.pg, k)))
+            v_cb, v_gamma = self._param_slice(self._v, u.pcb, k), self._param_slice(self._v, u.pg, k)
+            if u.gn_parts:  # (split unit: g', t, the parts' sums and rows, then u.gah from the added partials)
+                sums, act = gn_split_adjoint2_args(u, srcs, v_cb, v_gamma)
+                self._launch("hf_gn_split_adjoint2_sums", *sums)
+                self._launch("hf_gn_split_act_adjoint2", *act)
+            else:
+                self._launch("hf_gn_act_adjoint2", *gn_adjoint2_args(u, srcs, v_cb, v_gamma))
         else:
             self._bn_adjoint(u, srcs, reduce_only=second and u.train)
         if not second:

@@ -245,6 +245,11 @@ class _Buffers:
                 u.gcb = torch.empty((u.rb, k), dtype=f32, device=dev) if u.pcb is not None else None
                 if u.gn_parts:  # the reduce launches' fp64 partials, one pair per (sample, group, part)
                     u.gn_tab = torch.empty((n, u.gn.num_groups, u.gn_parts, 2), dtype=torch.float64, device=dev)
+                    if self.hessian:
+                        # the second-order adjoint's five sums per part -- a table of its own: it reads the tangent sweep's
+                        # pair in u.gn_tab next to them -- and the tangent convolution's sum between its two launches
+                        u.gn_tab2 = torch.empty((n, u.gn.num_groups, u.gn_parts, 5), dtype=torch.float64, device=dev)
+                        u.gn_t2 = torch.empty_like(u.a)
             if u.train:
                 # The per-channel finalisation of a train-mode tangent / adjoint runs in the PROLOGUE of the elementwise
                 # pass: its workgroups add the reduction's partial rows up themselves (hf_chan_affine_train).  The

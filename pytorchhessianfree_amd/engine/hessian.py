@@ -17,7 +17,7 @@ class _HessianExtras:
         if u.dead:  # (frozen, behind frozen layers only: no tangent reaches it, no cotangent is needed behind it)
             return
         # (train mode: the tangent sweep left this sum, engine/tangent.py; GroupNorm -- ``u.bn`` is None --: the scale's
-        # whole second-order row is hf_gn_act_adjoint2's)
+        # whole second-order row is hf_gn_act_adjoint2's -- a split unit's ``n * parts`` rows hf_gn_split_adjoint2_sums')
         if u.bn is not None and not u.train:
             self._scale_second_order_sum(u)
         if u.in_place:  # (both terms ride in the chain's own two-term launch: adjoint._in_place_second_order)

@@ -96,8 +96,12 @@ class PlainStackEngine(_ConvEngine):
     direction is a reduce and an apply launch in stream order (``hf_gn_split_stats`` / ``_forward``, ``_tangent_sums`` /
     ``_act_tangent``, ``_adjoint_sums`` / ``_act_adjoint``): per-part fp64 partials in ``u.gn_tab``, added in part order by
     every workgroup of the apply launch, no atomics.  Such a unit costs 6 launches per product (tangent convolution, 2, 2,
-    D + W gradient); its rows arrive as ``u.rb = n * parts`` and ``diag_ef`` takes ``hf_gn_split_rows_sqsum``.  GGN only:
-    Hessian products through a split unit are declined.  Units within the limit keep the one-launch kernels."""
+    D + W gradient); its rows arrive as ``u.rb = n * parts`` and ``diag_ef`` takes ``hf_gn_split_rows_sqsum``.  Hessian
+    products (``HF_GN_HESSIAN=1`` as the third switch): the second-order half is a reduce and an apply launch too,
+    ``hf_gn_split_adjoint2_sums`` / ``hf_gn_split_act_adjoint2`` -- ONE reduce launch, because E[t] and E[xh t] are already in
+    ``u.gn_tab`` from the tangent sweep of the same product; five more sums per part go to ``u.gn_tab2``, ``n * parts``
+    second-order rows to the gather -- so such a unit costs a Hessian product one launch more than a one-launch GroupNorm
+    unit in that half (and the two more of its tangent).  Units within the limit keep the one-launch kernels."""
 
     mode = ("fused curvature engine (plain conv-ReLU stack): own deterministic convolutions (split-K slabs summed "
             "by the consumer kernel), bias / ReLU / max-pool fused, 4 launches per layer")
@@ -319,7 +323,8 @@ class PlainStackEngine(_ConvEngine):
         """The GroupNorm behind ``u``'s convolution (output record ``cy``) and the layer ``nxt`` behind it: the unit's output
         record and ReLU flag.  What the kernels of hf_gn.hip take: opted in, affine, groups of channel quads, a (sample,
         group) block of ``h*w*cg`` floats within one workgroup's LDS -- beyond it, with ``HF_GN_SPLIT=1``, the split kernels
-        (``u.gn_parts`` parts per block, GGN products only); one process; Hessian products only with ``HF_GN_HESSIAN=1``."""
+        (``u.gn_parts`` parts per block); one process; Hessian products, split units included, only with
+        ``HF_GN_HESSIAN=1``."""
         n, c, h, w = cy.shape
         cg = c // gn.num_groups
         what = f"{u.name}: GroupNorm({gn.num_groups}, {c})"
@@ -336,9 +341,9 @@ class PlainStackEngine(_ConvEngine):
         if split and cg > GN_LDS_FLOATS:
             raise _Unsupported(f"{what}: {cg} channels per group (one pixel of a group must fit one workgroup's LDS: "
                                f"{GN_LDS_FLOATS} floats)")
-        if split and self.hessian:
-            raise _Unsupported(f"{what}: Hessian products through a split GroupNorm unit are not covered (a block of "
-                               f"{h * w * cg} floats: hf_gn_act_adjoint2 needs two resident blocks)")
+        if split and self.hessian and os.environ.get("HF_GN_HESSIAN", "0") != "1":
+            raise _Unsupported(f"{what}: Hessian products through a split GroupNorm unit are not covered (opt-in on top of "
+                               "HF_GN_SPLIT=1: HF_GN_HESSIAN=1)")
         if self.hessian and os.environ.get("HF_GN_HESSIAN", "0") != "1":
             raise _Unsupported(f"{what}: Hessian products through a GroupNorm unit are not covered (opt-in on top of "
                                "HF_GN_ENGINE=1: HF_GN_HESSIAN=1)")

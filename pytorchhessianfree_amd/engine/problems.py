@@ -187,6 +187,19 @@ def gn_split_adjoint_args(u, srcs):
             (u.ga, u.gcb if u.pcb is not None else None, g, u.gn_tab, u.a, u.gn_mean, u.gn_rstd, u.gn.weight, *_gn_dims(u)))
 
 
+def gn_split_adjoint2_args(u, srcs, v_cb, v_gamma):
+    """``hf_gn_split_adjoint2_sums`` and ``hf_gn_split_act_adjoint2``: ``gn_adjoint2_args``'s operands for a split unit.  The
+    masked cotangent goes to ``u.gah`` (which the second launch rewrites in place) and the tangent convolution's sum to
+    ``u.gn_t2``; the parts' five sums to ``u.gn_tab2`` -- E[t] and E[xh t] come from ``u.gn_tab``, where the tangent sweep of
+    this product left them --, the parts' rows of scale and shift; then ``u.gah`` and the convolution bias's rows."""
+    (gy, splits, slab), = srcs
+    return ((u.gah, u.gn_t2, u.gn_tab2, u.gw if u.pg is not None else None, u.gb if u.pb is not None else None, gy, splits,
+             slab, u.tbuf, u.sT, u.tbuf.shape[1], v_cb, u.gn_tab, u.a, u.g1, u.gn_mean, u.gn_rstd, u.gn.weight, v_gamma,
+             u.y if u.relu else None, *_gn_dims(u)),
+            (u.gah, u.gcb if u.pcb is not None else None, u.gah, u.gn_t2, u.gn_tab2, u.gn_tab, u.a, u.g1, u.gn_mean,
+             u.gn_rstd, u.gn.weight, v_gamma, *_gn_dims(u)))
+
+
 def gn_rows_sqsum_args(u, out, offs, pre):
     """``hf_gn_rows_sqsum`` (a split unit: ``hf_gn_split_rows_sqsum``): the unit's entries of ``diag_ef`` straight into ``out`` (``offs``: the parameters' offsets) from
     the per-sample rows the adjoint launch left, each scaled by ``pre`` before it is squared."""

@@ -7,8 +7,9 @@ the two operators alternating on one device; one JSON line per operator to ``--o
 median and the spread (max - min); the engine's record also counts the library launches of one product.
 
 ``--groups 1``: ``GroupNorm(1, .)`` instead -- every unit at 32x32 and 16x16 is then beyond one workgroup's LDS and takes
-the split kernels (``HF_GN_ENGINE=1 HF_GN_SPLIT=1``; GGN only), against the captured autograd operator the same model runs
-on without the switches; the record counts the split units (``profiles/gn_split.jsonl``)."""
+the split kernels (``HF_GN_ENGINE=1 HF_GN_SPLIT=1``; with ``--curvature hessian`` also ``HF_GN_HESSIAN=1``), against the
+captured autograd operator the same model runs on without the switches; the record counts the split units
+(``profiles/gn_split.jsonl``, ``profiles/gn_split_hessian.jsonl``)."""
 import argparse
 import json
 import os
@@ -57,7 +58,7 @@ def graphed(engine, batch, dev="cuda", hessian=False, groups=8):
             return curvature.hessian_operator(lossf(out, t), out, params)
         return curvature.ggn_operator(lossf(out, t), out, params)
 
-    switches = ("HF_GN_ENGINE", "HF_GN_HESSIAN") if hessian else ("HF_GN_ENGINE", "HF_GN_SPLIT")
+    switches = ("HF_GN_ENGINE", "HF_GN_SPLIT") + (("HF_GN_HESSIAN",) if hessian else ())
     os.environ.update({name: "1" if engine else "0" for name in switches})
     try:
         op = curvature.maybe_graphed(builder, params=params)
