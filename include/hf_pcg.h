@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HF_ABI_VERSION 35
+#define HF_ABI_VERSION 36
 
 enum hf_dtype { HF_F32 = 0, HF_F64 = 1 };
 
@@ -1414,6 +1414,45 @@ int hf_gn_split_act_adjoint2(void* ga2, void* gcb_rows, const void* gp, const vo
                              const void* t_partials, const void* a, const void* g, const void* mean, const void* rstd,
                              const void* gamma, const void* v_gamma, int64_t n, int64_t hw, int64_t c, int64_t groups,
                              int dtype, void* stream);
+
+/* ---- LayerNorm layers of the dense-stack engine (hf_ln.hip, ABI 36) -----------------------------------------------------
+ * Linear(+bias) -> LayerNorm(affine) -> [ReLU | Tanh] as one layer of the dense chain: fp32 activations [rows, c] (dense),
+ * rows <= 256, c <= 16 384, statistics per row.  One owner per row -- a wave (c <= 1024: the row in registers, four rows
+ * per workgroup) or a workgroup (the summed row staged once in LDS) -- sums the split-K slabs of its row once and takes
+ * every reduction from it; lanes keep fp32 partial sums over fixed sets of columns, everything behind them is fp64 in an
+ * order that depends on the shape alone: no atomics, two launches give the same bits.  The arithmetic chains and their
+ * roundings stand in hf_ln.hip's header.  `slabs`: `splits` (1 .. 32) slabs `slab_stride` elements apart (>= rows*c where
+ * splits > 1), added by the rule of the dense kernels.  act: 0 identity, 1 relu, 2 tanh (the codes of hf_dense_act_*).
+ *
+ * Refused before anything is launched or written.  HF_ERR_ARG: rows or c outside the limits, another dtype than HF_F32,
+ * a split count outside 1 .. 32, a NULL required pointer.  HF_ERR_ALIGN: at c % 4 == 0 (the 16-byte form) a row map --
+ * slabs, y, xhat, t_y, g_a, s -- off the 16-byte grid or a slab_stride that is no multiple of 4; any other c takes
+ * element loads and has no such rule.  Per-column vectors (b, gamma, beta, the CG vector's slices v_*, the outputs o_*)
+ * may sit on any 4-byte boundary.
+ *
+ *   hf_ln_act_forward  a = sum of slabs (+ b[col], nullable);  mu = mean(a);  rstd = 1/sqrt(mean((a - mu)^2) + eps) (exact
+ *                      two-pass variance, biased) -> rstd [rows];  xhat = (a - mu)*rstd -> xhat [rows, c];
+ *                      y = act(gamma*xhat + beta) -> y.  relu keeps a NaN a NaN (hf_dense_act_forward's rule).
+ *   hf_ln_act_tangent  t = sum of slabs (+ v_b[col]);  tx = rstd*(t - mean(t) - xhat*mean(xhat t));
+ *                      t_y = act'(y) * (gamma*tx + v_gamma*xhat + v_beta);  v_b / v_gamma / v_beta: slices of the CG vector
+ *                      read in place, NULL where frozen;  y: required unless act = 0.
+ *   hf_ln_act_adjoint  s = act'(y) * (sum of slabs) -> s;  q = gamma*s;  g_a = rstd*(q - mean(q) - xhat*mean(q xhat)) -> g_a,
+ *                      the cotangent of the Linear's output (what hf_dense_wgrad / hf_dense_dgrad_slabs read as g_a).
+ *   hf_ln_param_sums   o_gamma[col] = scale * sum_r s*xhat,  o_beta[col] = scale * sum_r s,  o_b[col] = scale * sum_r g_a
+ *                      (the Linear's bias); each nullable, not all.  squared = 1: the sums of (s*xhat)^2, s^2, g_a^2 -- with
+ *                      per-sample cotangents the entries of the diagonal empirical Fisher.  Rows are added in row order.
+ */
+int hf_ln_act_forward(void* y, void* xhat, void* rstd, const void* slabs, int splits, int64_t slab_stride, const void* b,
+                      const void* gamma, const void* beta, double eps, int act, int64_t rows, int64_t c, int dtype,
+                      void* stream);
+int hf_ln_act_tangent(void* t_y, const void* slabs, int splits, int64_t slab_stride, const void* v_b, const void* xhat,
+                      const void* rstd, const void* gamma, const void* v_gamma, const void* v_beta, const void* y, int act,
+                      int64_t rows, int64_t c, int dtype, void* stream);
+int hf_ln_act_adjoint(void* g_a, void* s, const void* slabs, int splits, int64_t slab_stride, const void* xhat,
+                      const void* rstd, const void* gamma, const void* y, int act, int64_t rows, int64_t c, int dtype,
+                      void* stream);
+int hf_ln_param_sums(void* o_gamma, void* o_beta, void* o_b, const void* s, const void* xhat, const void* g_a, int squared,
+                     double scale, int64_t rows, int64_t c, int dtype, void* stream);
 
 /* ---- RCCL (resolved at run time from the already-loaded librccl) ----------- */
 typedef struct hf_comm hf_comm_t;

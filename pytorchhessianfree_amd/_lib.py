@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HF_PCG_LIB") or os.path.join(_HERE, "csrc", "libhfpcg.so")
 
 HF_F32, HF_F64 = 0, 1
-ABI_VERSION = 35
+ABI_VERSION = 36
 HF_ERR_ARG = -1  # hf_status of include/hf_pcg.h: null / negative / inconsistent argument
 HF_M_NONE, HF_M_DIAG, HF_M_EXTERNAL = 0, 1, 2
 REASONS = {
@@ -275,6 +275,13 @@ SIGNATURES = {
     "hf_gn_split_adjoint2_sums": (c_int, [c_void_p] * 6 + [c_int, c_int64, c_void_p, c_int, c_int64] + [c_void_p] * 9
                                   + [c_int64] * 4 + [c_int, c_void_p]),
     "hf_gn_split_act_adjoint2": (c_int, [c_void_p] * 12 + [c_int64] * 4 + [c_int, c_void_p]),
+    "hf_ln_act_forward": (c_int, [c_void_p] * 4 + [c_int, c_int64] + [c_void_p] * 3 + [c_double, c_int, c_int64, c_int64,
+                                                                                      c_int, c_void_p]),
+    "hf_ln_act_tangent": (c_int, [c_void_p] * 2 + [c_int, c_int64] + [c_void_p] * 7 + [c_int, c_int64, c_int64, c_int,
+                                                                                      c_void_p]),
+    "hf_ln_act_adjoint": (c_int, [c_void_p] * 3 + [c_int, c_int64] + [c_void_p] * 4 + [c_int, c_int64, c_int64, c_int,
+                                                                                      c_void_p]),
+    "hf_ln_param_sums": (c_int, [c_void_p] * 6 + [c_int, c_double, c_int64, c_int64, c_int, c_void_p]),
     "hf_comm_unique_id": (c_int, [ctypes.c_char_p]),
     "hf_comm_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.c_char_p, c_int, c_int]),
     "hf_comm_destroy": (c_int, [c_void_p]),

@@ -137,6 +137,11 @@ SWITCHES = {
                       "instead of the autograd path; batches up to 256 rows keep the skinny kernels.  Measured SLOWER than the "
                       "hipGraph-replayed autograd sweeps (0.76-0.80 x their matvecs/s, DESIGN.md section 6.3), hence opt-in",
                       "tests/test_dense_tall_engine_gpu.py::test_products_gradient_and_diag_ef_against_float64"),
+    "HF_DENSE_LN": ("0", "1: with HF_DENSE_ENGINE=1, a prepared MLP with Linear(+bias), LayerNorm(affine) [ReLU | Tanh] layers "
+                    "takes the dense-stack engine, each such layer on the row-resident kernels of hf_ln.hip (GGN products, "
+                    "gradient, diag_ef; 6 launches per layer and product; no Hessian products, no tall chain, no session) "
+                    "instead of declining the model; opt-in like the engine it stands on (profiles/dense_ln.jsonl)",
+                    "tests/test_dense_ln_engine_gpu.py::test_products_gradient_and_diag_ef_against_float64"),
     "HF_ENGINE_VERIFY": ("first", "always / never: the engine's first-use check against the autograd product",
                          "tests/test_engine_gpu.py::test_train_mode_prologue_form_variants_agree_and_state_is_independent_of_the_first_use_check"),
     "HF_ENGINE_DEBUG": ("", "1: say why a model was not taken by the engine",

@@ -12,10 +12,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 # one translation unit per kernel family: PCG solver | gather / scatter | BatchNorm / bias maps | convolutions |
 # pooling + classifier heads | fully-connected layers (batches <= 256 rows | taller ones) | depthwise convolutions |
-# grouped convolutions | GroupNorm units | the RCCL shim
+# grouped convolutions | GroupNorm units | LayerNorm layers of the dense chain | the RCCL shim
 SOURCES = [os.path.join(HERE, f) for f in ("hf_pcg.hip", "hf_pack.hip", "hf_bn.hip", "hf_conv.hip", "hf_head.hip",
                                            "hf_dense.hip", "hf_dense_tall.hip", "hf_dwconv.hip", "hf_gconv.hip", "hf_gn.hip",
-                                           "hf_rccl.hip")]
+                                           "hf_ln.hip", "hf_rccl.hip")]
 HDR = os.path.join(ROOT, "include", "hf_pcg.h")
 HDRS_SHARED = [os.path.join(HERE, f) for f in ("hf_common.h", "hf_unpack.h", "hf_store.h", "hf_dense_act.h")]
 OUT = os.path.join(HERE, "libhfpcg.so")

@@ -119,12 +119,12 @@ def records_of(m, n=2, with_input=False):
 
 
 def mark_dead_prefix(layers):
-    """Frozen layers at the input end of a stack (no ``pw``, no ``pb``, no ``pg``, no ``pcb``): ``dead`` for both sweeps -- no tangent reaches
+    """Frozen layers at the input end of a stack (no ``pw``, no ``pb``, no ``pg``, no ``pcb``, no ``pb_ln``): ``dead`` for both sweeps -- no tangent reaches
     them, nobody needs a cotangent behind the first trainable layer.  Returns how many there are; the layer behind them
     reads a tangent-free input and needs no data gradient (the caller's flag)."""
     dead = 0
     for u in layers:
-        if any(i is not None for i in (u.pw, u.pb, getattr(u, "pg", None), getattr(u, "pcb", None))):
+        if any(i is not None for i in (u.pw, u.pb, getattr(u, "pg", None), getattr(u, "pcb", None), getattr(u, "pb_ln", None))):
             break
         u.dead = True
         dead += 1

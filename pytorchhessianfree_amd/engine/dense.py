@@ -46,7 +46,15 @@ class DenseStackEngine(_Engine):
     slabs; a split weight gradient and the bias sums take a finishing launch inside their call).  Batches up to 256 rows
     keep the skinny kernels whatever the switch says.  The session mode stays at 256 rows (the loss head's limit): a
     taller batch runs ``engine-graphed``.  Measured slower than the hipGraph-replayed autograd sweeps on the 25.5 M-parameter
-    MLP, hence opt-in."""
+    MLP, hence opt-in.
+
+    LayerNorm layers (opt-in: ``HF_DENSE_LN=1``): ``Linear(+bias), LayerNorm(c_out, elementwise_affine=True) [ReLU |
+    Tanh]`` is ONE layer of the chain on the row-resident kernels of csrc/hf_ln.hip -- a statistic belongs to one row, so
+    one wave (up to 1024 features) or one workgroup (up to 16 384) sums the split-K slabs of its row once and takes every
+    reduction from it.  Per product 6 launches: tangent GEMM, LayerNorm tangent, LayerNorm adjoint (rows), the column
+    sums of scale / shift / bias straight into the product, weight gradient, data gradient.  GGN products, ``gradient()``
+    and ``diag_ef`` (the column launch's squared mode); declined: Hessian products, the tall chain, the session mode,
+    a LayerNorm without affine parameters or behind a ``Linear`` without bias."""
 
     mode = ("fused curvature engine (dense stack): own skinny MFMA GEMMs that read the weights and the vector in place "
             "(split reductions as slabs summed by the consumer kernel), bias / activation fused, 5 launches per hidden "
@@ -112,7 +120,8 @@ class DenseStackEngine(_Engine):
             raise _Unsupported("no recorded float32 GPU input")
         leaves = [m for m in model.modules() if not list(m.children())]
         chain = _Chain(self.dev, self._offs, (nn.ReLU, nn.Tanh), ("linear", "stack", "batch {} > {} rows"),
-                       tall_switch=("HF_DENSE_TALL", os.environ.get("HF_DENSE_TALL", "0") == "1"))
+                       tall_switch=("HF_DENSE_TALL", os.environ.get("HF_DENSE_TALL", "0") == "1"),
+                       ln_switch=("HF_DENSE_LN", os.environ.get("HF_DENSE_LN", "0") == "1"))
         layers, cur, i = chain.layers, x_in.detach(), 0
         while i < len(leaves):
             m = leaves[i]
@@ -138,9 +147,15 @@ class DenseStackEngine(_Engine):
         self.rows = chain.check_end(self.outputs.detach())
         if chain.tall:  # (what path reports and benchmarks print)
             self.mode = self.mode.replace("own skinny MFMA GEMMs", "own LDS-tiled MFMA GEMMs (tall batch: 128 x 128 tiles)")
-        used = {k for u in layers for k in (u.pw, u.pb) if k is not None}
+        used = {k for u in layers for k in (u.pw, u.pb, u.pg, u.pb_ln) if k is not None}
         if used != set(range(len(self.params))):
             raise _Unsupported("the parameter list has entries the engine's layers do not cover")
+        self.has_ln = any(u.ln is not None for u in layers)
+        if self.has_ln and self.hessian:
+            raise _Unsupported("Hessian products through a LayerNorm layer are not covered (GGN products only)")
+        if self.has_ln:
+            self.mode = self.mode.replace("5 launches per hidden layer", "5 launches per hidden layer (6 with a LayerNorm: "
+                                          "row-resident statistics, own kernels)")
         self.dead_layers = chain.mark_dead_prefix()
         self.chain, self.layers, self.model_ref, self._in_shape = chain, layers, model, tuple(x_in.shape)
 
@@ -198,13 +213,19 @@ class DenseStackEngine(_Engine):
         if self._reduction is not None:
             per_sample = float(outputs.shape[0]) if self._reduction == "mean" else 1.0
             self._g_ef = (self._dl.detach() * per_sample).contiguous()
-        self._h_last = self._dl.detach().contiguous() if self.hessian else None  # d loss / d logits
+        # d loss / d logits: what ``gradient()`` starts from (a LayerNorm stack serves it in GGN mode too: it has no
+        # Hessian form and no session that would)
+        self._h_last = self._dl.detach().contiguous() if self.hessian or self.has_ln else None
         self._dl = None
         if not self._session_switch():  # (no own loss head without the session mode: loss_spec stays None)
             return
         if self._reduction is None:
             self.session_decline = ("the dense-stack engine's session takes a plain cross-entropy / MSE loss (no "
                                     "quadratic regulariser)")
+            return
+        if self.has_ln:
+            self.session_decline = ("the dense-stack engine's session does not cover LayerNorm layers; the model runs "
+                                    "engine-graphed")
             return
         if self.rows > MAX_ROWS:  # (hf_dense_loss_head's finishing kernel holds 512 terms in LDS)
             self.session_decline = (f"the dense-stack engine's session serves batches up to {MAX_ROWS} rows (its loss "
@@ -291,8 +312,8 @@ class DenseStackEngine(_Engine):
         """The first-order adjoint sweep from ``d loss / d logits`` at the activations the buffers hold: keeps ``g_l`` of
         every live layer (``h_l`` of tanh layers) for the Hessian products; with ``out`` also ``weight * d loss /
         d params`` in the flat vector.  In session mode also for a GGN engine: its cotangents go through the products'
-        own ``ga`` buffers (nothing is kept).  Existing kernels only; no allocation, no host synchronisation."""
-        if not self.hessian and self.loss_spec is None:
+        own ``ga`` buffers (nothing is kept), and so for a GGN engine over LayerNorm layers.  The sweeps' kernels only; no allocation, no host synchronisation."""
+        if not self.hessian and self.loss_spec is None and not self.has_ln:
             raise RuntimeError("the dense-stack engine keeps first-order cotangents in Hessian mode only")
         if out is not None:
             self._flat("the gradient", out)

@@ -633,6 +633,20 @@ def mwe_mlp(batch_size=16, dim=10, seed=0, device="cpu"):
     return model.to(device), (inputs.to(device), targets.to(device)), nn.MSELoss()
 
 
+def mlp_layernorm(batch_size=64, seed=0, device="cpu", widths=(3072, 4096, 3072, 100)):
+    """The 25.5 M-parameter MLP's widths (3072-4096-3072-100, Tanh) with a LayerNorm behind every hidden ``Linear``;
+    inputs U[0,1) [B, widths[0]], CE-mean."""
+    torch.manual_seed(seed)
+    layers = []
+    for i, o in zip(widths[:-2], widths[1:-1]):
+        layers += [nn.Linear(i, o), nn.LayerNorm(o), nn.Tanh()]
+    model = nn.Sequential(*layers, nn.Linear(widths[-2], widths[-1]))
+    g = torch.Generator().manual_seed(seed + 1)
+    inputs = torch.rand(batch_size, widths[0], generator=g)
+    targets = torch.randint(0, widths[-1], (batch_size,), generator=g)
+    return model.to(device), (inputs.to(device), targets.to(device)), nn.CrossEntropyLoss()
+
+
 def small_nn(batch_size=32, seed=0, device="cpu", freeze_layer1=True):
     torch.manual_seed(seed)
     model = nn.Sequential(
